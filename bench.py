@@ -14,10 +14,16 @@ A "step" is one pass of the hot path over one batch of synthetic input that is a
   --config C4 | C5 : the sibling matchers (LongestMatchSet / WholeWordMatchMap case-insensitive) at BASELINE's sizes,
         same sharding driver; not the headline line.
   --backend gloo : the N>1 path with host-staged collectives (several ranks on one GPU; what tests/test_dist_gpu.py runs).
-Prints ONE JSON line (rank 0).  Outside the timed region the line is checked and annotated: the records of the last
-step are compared with the CPU oracle on a prefix of the haystack ("verified"), the CPU restatement is timed on that
-prefix ("cpu_baseline": pinned to one core, median of 5 runs after a warm-up), the tile kernels' access pattern is timed
-as a pure read ("roofline.attainable"), and the host-buffer entry point acgpu_match_u16 is timed ("end_to_end").
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the line.
+  --dump-outputs DIR : after the timed steps, the records of the last step -- what a caller of the path receives -- go to
+        DIR/records.npy (float64, one row per record: start, end[, keyword_id], whole-text positions; a seeded sample of
+        rows, their indices in DIR/records_rows.npy, when all of them would exceed 64 MB).
+  --full : outside the timed region the line is also checked and annotated: the records of the last step are compared
+        with the CPU oracle on a prefix of the haystack ("verified"), the CPU restatement is timed on that prefix
+        ("cpu_baseline": pinned to one core, median of 5 runs after a warm-up), the tile kernels' access pattern is timed
+        as a pure read ("roofline.attainable"), the steps are run with the ordering in launches of their own
+        ("roofline.separate_launches"), and the host-buffer entry points are timed ("end_to_end", "end_to_end_stream",
+        "single_call").  --no-cpu-baseline / --no-separate-launches leave parts of that out.
 """
 import argparse
 import ctypes
@@ -78,7 +84,16 @@ def main():
     ap.add_argument("--tunable", action="append", default=[], metavar="NAME=VALUE",
                     help="development: an acgpu_set_tunable knob for A/B on one box (e.g. tile_form=1: a finalize launch behind the scan); "
                          "recorded in config.tunables")
+    ap.add_argument("--full", action="store_true",
+                    help="also the checks and figures beside the headline: oracle verification, CPU baseline, pure-read roofline, "
+                         "separate launches, host-buffer entry points (a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's records to DIR/records.npy (float64)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: what the headline figure needs, nothing else
+        args.no_cpu_baseline = args.no_separate_launches = True
+    if args.dump_outputs and (args.config == "README" or args.single_process):
+        ap.error("--dump-outputs: the sharded driver only (not --config README or --single-process)")
 
     if args.config == "README":
         return main_readme(args)
@@ -197,6 +212,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if args.backend == "gloo" else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_records(args.dump_outputs, matcher.global_records())
 
     total_units = n_units * world
     ms_per_step = elapsed / args.steps * 1e3
@@ -273,14 +290,14 @@ def main():
     # tile kernels' own access pattern reads at (pattern 0: their stream alone)
     ms = ctypes.c_float(0)
     cur = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    if N.lib().acgpu_stream_probe(matcher.own_ptr(), n_units * 2, cur, 7, 1, ctypes.byref(ms)) == N.OK and ms.value > 0:
+    if args.full and N.lib().acgpu_stream_probe(matcher.own_ptr(), n_units * 2, cur, 7, 1, ctypes.byref(ms)) == N.OK and ms.value > 0:
         att = n_units * 2 / (ms.value * 1e-3) / 1e9
         out["roofline"]["attainable"] = round(att, 1)
         out["roofline"]["attainable_ms"] = round(ms.value, 4)
         out["roofline"]["frac_of_attainable"] = round(achieved / att, 4)
         out["roofline"]["attainable_what"] = ("k_stream_probe_best: the fastest pure read of the shard found on this chip (2 KiB tiles dealt "
                                               "round robin to 2048 workgroups of 256 lanes, 32 B per lane, four tiles in flight)")
-    if N.lib().acgpu_stream_probe(matcher.own_ptr(), n_units * 2, cur, 7, 0, ctypes.byref(ms)) == N.OK and ms.value > 0:
+    if args.full and N.lib().acgpu_stream_probe(matcher.own_ptr(), n_units * 2, cur, 7, 0, ctypes.byref(ms)) == N.OK and ms.value > 0:
         out["roofline"]["kernel_pattern_read_gbps"] = round(n_units * 2 / (ms.value * 1e-3) / 1e9, 1)
         out["roofline"]["kernel_pattern_what"] = "k_stream_probe: the tile kernels' own pattern as a pure read (one span per wave, 64 B per lane and tile)"
 
@@ -633,6 +650,26 @@ def launch_ranks(n):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     return subprocess.run(cmd, env=env).returncode
+
+
+DUMP_BYTES = 64 * 10 ** 6  # --dump-outputs writes at most this much in all
+
+
+def dump_records(out_dir, recs):
+    """--dump-outputs: the records of the last timed step ((n, 2|3) int64 tensor, whole-text positions) as float64, which holds
+    every position and keyword id exactly -- all of them, or, when that would exceed DUMP_BYTES, a sample of rows drawn with
+    seed 0 (so fixed by the record count), in order, with their row indices in records_rows.npy."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n, cols = recs.shape
+    rows_path = os.path.join(out_dir, "records_rows.npy")
+    if n * cols * 8 > DUMP_BYTES - 4096:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=(DUMP_BYTES - 4096) // ((cols + 1) * 8), replace=False))
+        recs = recs[torch.from_numpy(rows).to(recs.device)]
+        np.save(rows_path, rows.astype(np.float64))
+    elif os.path.exists(rows_path):
+        os.remove(rows_path)  # (left by an earlier run into the same directory)
+    np.save(os.path.join(out_dir, "records.npy"), recs.cpu().numpy().astype(np.float64))
 
 
 def _oracle(cfg_name, kws):

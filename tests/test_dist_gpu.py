@@ -99,7 +99,7 @@ def test_bench_self_launches_its_ranks(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1",
-                        "--units-log2", "24", "--cpu-sample-log2", "20"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                        "--units-log2", "24", "--cpu-sample-log2", "20", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        timeout=600)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]

@@ -12,9 +12,9 @@ cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 PART=${PART:-all}
 if [ "$PART" != B ]; then
-python3 bench.py --steps 20 --warmup 3 > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"
-python3 bench.py --config C4 --steps 10 --warmup 2 > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err"
-python3 bench.py --config C5 --steps 20 --warmup 3 > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err"
+python3 bench.py --full --steps 20 --warmup 3 > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"
+python3 bench.py --full --config C4 --steps 10 --warmup 2 > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err"
+python3 bench.py --full --config C5 --steps 20 --warmup 3 > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err"
 # per-kernel time: the program itself after "--"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_c2" -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-separate-launches > "$OUT/stats_c2.log" 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_c4" -- python3 bench.py --config C4 --steps 3 --warmup 1 --no-cpu-baseline --no-separate-launches > "$OUT/stats_c4.log" 2>&1
@@ -32,7 +32,7 @@ python3 tools/pmc_traffic.py "$OUT" "$OUT/pmc_traffic.json"
 bash tools/pmc_sq.sh "${1:-final}/pmc_sq" "$V" > "$OUT/pmc_sq.txt" 2>&1
 unset ACGPU_LIB
 # config 3's share on one GPU (Set records, R = 8), and the sibling kernels' counters (SQ + HBM traffic)
-python3 bench.py --config C3 --steps 20 --warmup 3 > "$OUT/bench_c3_1gpu.json" 2> "$OUT/bench_c3_1gpu.err"
+python3 bench.py --full --config C3 --steps 20 --warmup 3 > "$OUT/bench_c3_1gpu.json" 2> "$OUT/bench_c3_1gpu.err"
 bash tools/pmc_sq.sh "${1:-final}/pmc_sq_c4" '{"c4":{}}' "--config C4 --set" k_longest > "$OUT/pmc_sq_c4.txt" 2>&1
 bash tools/pmc_sq.sh "${1:-final}/pmc_sq_c5" '{"c5":{}}' "--config C5" k_ww_ > "$OUT/pmc_sq_c5.txt" 2>&1
 for c in C2 C4 C5; do
@@ -45,9 +45,9 @@ fi
 if [ "$PART" = A ]; then cat "$OUT/bench_c2.json"; exit 0; fi
 # round 4: the multi-device entries through ONE host process (a one-GPU box: RCCL over a world of one; peer copies over the
 # device named twice), the reference's own published workload, the CU reserve, the chunked entry
-python3 bench.py --gpus 1 --single-process --config C3 --steps 20 --warmup 3 > "$OUT/bench_c3_single_process_rccl.json" 2> "$OUT/bench_c3_sp.err"
-python3 bench.py --gpus 2 --devices 0,0 --single-process --units-log2 28 --steps 10 --warmup 2 > "$OUT/bench_c3_single_process_peer2.json" 2>> "$OUT/bench_c3_sp.err"
-python3 bench.py --config README --steps 5 --warmup 1 > "$OUT/bench_readme.json" 2> "$OUT/bench_readme.err"
+python3 bench.py --full --gpus 1 --single-process --config C3 --steps 20 --warmup 3 > "$OUT/bench_c3_single_process_rccl.json" 2> "$OUT/bench_c3_sp.err"
+python3 bench.py --full --gpus 2 --devices 0,0 --single-process --units-log2 28 --steps 10 --warmup 2 > "$OUT/bench_c3_single_process_peer2.json" 2>> "$OUT/bench_c3_sp.err"
+python3 bench.py --full --config README --steps 5 --warmup 1 > "$OUT/bench_readme.json" 2> "$OUT/bench_readme.err"
 python3 tools/kbench.py --rounds 9 --variants '{"reserve_cus=0":{},"reserve_cus=4":{"reserve_cus":4},"reserve_cus=8":{"reserve_cus":8},"reserve_cus=16":{"reserve_cus":16},"reserve_cus=32":{"reserve_cus":32}}' > "$OUT/reserve_cus.txt" 2>&1
 python3 tools/stream_rate.py > "$OUT/stream_rate.txt" 2>&1
 python3 tools/latency.py > "$OUT/latency.txt" 2>&1
@@ -62,7 +62,7 @@ python3 tools/map_flavours.py 2>&1 | grep -v amdgpu.ids > "$OUT/map_flavours.txt
 # the three bench lines once more with this collection's traffic attached (bench.py attaches profiles/latest_traffic.json only
 # when it was measured on the sources it runs; the copy of the repository on this box is scratch)
 [ -f "$OUT/latest_traffic.json" ] && cp "$OUT/latest_traffic.json" profiles/latest_traffic.json
-python3 bench.py --steps 20 --warmup 3 > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"
-python3 bench.py --config C4 --steps 10 --warmup 2 > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err"
-python3 bench.py --config C5 --steps 20 --warmup 3 > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err"
+python3 bench.py --full --steps 20 --warmup 3 > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"
+python3 bench.py --full --config C4 --steps 10 --warmup 2 > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err"
+python3 bench.py --full --config C5 --steps 20 --warmup 3 > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err"
 cat "$OUT/bench_c2.json"
