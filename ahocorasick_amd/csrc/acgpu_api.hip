@@ -263,14 +263,52 @@ DevTables folded_tables(const DeviceState &d) {
     return T;
 }
 
-// ALL-mode pipeline on one shard, the form for texts with dense matches: see match_all.
+// ---- the call record: enqueue, then collect() ----
+
+// Starts a call in `r`: the call's arguments, the record's events and pinned slot (done: a ticket's completion marker, null for a
+// synchronous call).  Until a form fills it in, the record is complete with nothing found.
+void open_call(CallRecord &r, hipEvent_t *ev, hipEvent_t done, unsigned long long *slot, const acgpu_shard &sh, acgpu_shard *user,
+               int record_kind, void *d_out, uint64_t cap, hipStream_t stream, bool profiled, bool folded) {
+    r = CallRecord{};
+    r.shard = sh; r.user_shard = user; r.record_kind = record_kind; r.d_out = d_out; r.cap = cap; r.stream = stream;
+    r.ev = ev; r.done = done; r.h_slot = slot; r.profiled = profiled; r.folded = folded;
+}
+
+// what a ticket's call is complete with: its marker, or the last kernel's own end
+hipEvent_t completion(const CallRecord &r) { return r.done_is_ev2 ? r.ev[2] : r.done; }
+
+// the device address of the record's pinned slot
+int slot_on_device(const CallRecord &r, unsigned long long **d_slot) {
+    HIP_TRY(hipHostGetDevicePointer((void **)d_slot, r.h_slot, 0));
+    return ACGPU_OK;
+}
+
+// The end of an enqueue: the form, what the profile reports, and a ticket's completion marker -- unless the call's last kernel
+// delivers its own end to ev[2] (done_is_ev2: no marker packet behind the call).
+int close_call(CallRecord &r, CallForm form, const char *kname, uint64_t scanned, bool done_is_ev2 = false) {
+    r.form = form;
+    r.scanned = scanned;
+    std::snprintf(r.kname, sizeof(r.kname), "%s", kname);
+    r.done_is_ev2 = done_is_ev2;
+    if (r.done && !done_is_ev2) HIP_TRY(hipEventRecord(r.done, r.stream));
+    return ACGPU_OK;
+}
+
+// A call with nothing to scan: the device result says so, the slot is written here (no kernel will write it).
+int enqueue_empty(CallRecord &r, int64_t chain_exit) {
+    r.h_slot[0] = r.h_slot[1] = 0;
+    r.h_slot[2] = (unsigned long long)chain_exit;
+    if (r.shard.d_result) HIP_TRY(hipMemsetAsync(r.shard.d_result, 0, sizeof(acgpu_device_result), r.stream));
+    return close_call(r, CallForm::Complete, "", 0);
+}
+
+// ALL-mode pipeline on one shard, the form for texts with dense matches: see enqueue_all.
 constexpr double kStatesFormDensity = 0.05; // records per unit of the pool's last call from which k_ac_states is taken
-int match_all_states(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_kind, void *d_out, uint64_t cap, uint64_t *n_out,
-                     hipStream_t stream, acgpu_profile *prof, Ticket *tk, uint32_t hot_rows) {
+int enqueue_states(acgpu_automaton *a, DeviceState &d, CallRecord &r, uint32_t hot_rows) {
     const HostTables &t = a->t;
-    hipEvent_t *ev = tk ? tk->ev : d.ev;
-    const bool timed = tk ? tk->profiled : prof != nullptr;
-    const uint64_t own_len = sh->own_end - sh->own_begin;
+    const acgpu_shard *sh = &r.shard;
+    hipEvent_t *ev = r.ev;
+    const hipStream_t stream = r.stream;
     int rc;
     AcStatesLaunch S{};
     S.d_hay = sh->d_hay;
@@ -296,554 +334,555 @@ int match_all_states(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int re
     S.d_state = (uint32_t *)d.statebuf.p;
     S.d_counts = (uint32_t *)d.chunk_counts.p;
     S.d_offsets = (const uint64_t *)d.offsets.p;
-    S.d_out = d_out;
-    S.cap = cap;
+    S.d_out = r.d_out;
+    S.cap = r.cap;
     S.grid = (int)std::min<uint64_t>((uint64_t)d.n_cu * (ac_states_lanes_per_cu() / 1024u), (S.n_waves + 15) / 16);
     HIP_TRY(hipMemsetAsync(d.counter.p, 0, 64, stream)); // (word 1: the "redo" flag of the result -- never raised here)
-    d.cclean[0] = false; // (match_all's first set of slot counters lives here)
-    if (timed) HIP_TRY(hipEventRecord(ev[0], stream));
+    d.cclean[0] = false; // (enqueue_all's first set of slot counters lives here)
+    if (r.profiled) HIP_TRY(hipEventRecord(ev[0], stream));
     HIP_TRY(launch_ac_states(d.T, S, t.range_cls, stream));
-    if (timed) HIP_TRY(hipEventRecord(ev[1], stream));
+    if (r.profiled) HIP_TRY(hipEventRecord(ev[1], stream));
     HIP_TRY(launch_exclusive_scan(S.d_counts, S.n_chunks, (uint64_t *)d.offsets.p, (uint64_t *)d.scan_tmp.p, stream));
-    HIP_TRY(launch_ac_states_out(d.T, S, record_kind == ACGPU_REC_MAP, stream));
-    if (timed) HIP_TRY(hipEventRecord(ev[2], stream));
-    unsigned long long *h_slot = tk ? tk->h_count : d.h_counter, *d_slot = nullptr;
-    HIP_TRY(hipHostGetDevicePointer((void **)&d_slot, h_slot, 0));
+    HIP_TRY(launch_ac_states_out(d.T, S, r.record_kind == ACGPU_REC_MAP, stream));
+    if (r.profiled) HIP_TRY(hipEventRecord(ev[2], stream));
+    unsigned long long *d_slot = nullptr;
+    if ((rc = slot_on_device(r, &d_slot))) return rc;
     HIP_TRY(launch_publish_result((const unsigned long long *)d.scan_tmp.p + scan_tiles_for(S.n_chunks), (const unsigned long long *)d.counter.p, d_slot,
                                   reinterpret_cast<acgpu_device_result *>(sh->d_result), stream));
-    if (tk) {
-        tk->shard = *sh;
-        tk->record_kind = record_kind;
-        tk->d_out = d_out;
-        tk->stream = stream;
-        tk->done_is_ev2 = false;
-        HIP_TRY(hipEventRecord(tk->done, stream));
-        tk->scanned = own_len;
-        std::snprintf(tk->kname, sizeof(tk->kname), "k_ac_states");
-        return ACGPU_OK;
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
-    *n_out = *d.h_counter;
-    d.all_density = (double)*n_out / (double)own_len;
-    if (prof) {
-        HIP_TRY(hipEventElapsedTime(&prof->scan_ms, d.ev[0], d.ev[1]));
-        HIP_TRY(hipEventElapsedTime(&prof->finalize_ms, d.ev[1], d.ev[2]));
-        HIP_TRY(hipEventElapsedTime(&prof->total_ms, d.ev[0], d.ev[2]));
-        prof->scan_units = own_len;
-        prof->n_matches = *n_out;
-        std::snprintf(prof->scan_kernel, sizeof(prof->scan_kernel), "k_ac_states");
-    }
-    return *n_out > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
+    return close_call(r, CallForm::States, "k_ac_states", sh->own_end - sh->own_begin);
 }
 
-// ALL-mode pipeline on one shard.
-// With a ticket the call returns after enqueueing (no host synchronisation); acgpu_match_device_end collects it.
-int match_all(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_kind, void *d_out, uint64_t cap,
-              uint64_t *n_out, hipStream_t stream, acgpu_profile *prof, Ticket *tk = nullptr, bool fused_only = false,
-              const DevTables *Tov = nullptr) {
-    // (Tov: WHOLEWORD -- the tables of a folding scan, see folded_tables)
-    // (fused_only: the redo after an overflow of the split form's candidate slices or of a scratch slice -- the fused
-    // kernel, one scratch slice)
+int collect(acgpu_automaton *a, DeviceState &d, CallRecord *r, uint64_t *n_out, acgpu_profile *prof, bool *redone);
+int enqueue_all(acgpu_automaton *a, DeviceState &d, CallRecord &r, int level);
+using EnqueueFn = int (*)(acgpu_automaton *, DeviceState &, CallRecord &, int);
+int run_sync(EnqueueFn enqueue, acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_kind, void *d_out, uint64_t cap,
+             uint64_t *n_out, hipStream_t stream, acgpu_profile *prof, bool folded = false);
+
+// Texts in which this dictionary matches densely (natural words in natural text: every filter passes, every verification walk
+// is long): the automaton's state behind every unit (k_ac_states over the compact automaton of acgpu_build.cpp 6d), then the
+// records from the states (acgpu_states.hip).  Its cost does not depend on the text (~ one gather per unit), the tile kernel's
+// does: what this pool's last call found decides (records per unit; a pool's first call looks at the beginning of a long text,
+// and takes the tile kernel for a short one or when it may not wait).
+// Tunable all_form, bits: 1 = never, 2 = whatever the last call found, 4 = also for short texts.
+// *hot: k_ac_states' hot rows when the call takes this form, 0 otherwise.
+int choose_states_form(acgpu_automaton *a, DeviceState &d, const CallRecord &r, uint32_t *hot) {
     const HostTables &t = a->t;
-    hipEvent_t *ev = tk ? tk->ev : d.ev;
-    const bool timed = tk ? tk->profiled : prof != nullptr;
+    const uint64_t own_len = r.shard.own_end - r.shard.own_begin;
+    *hot = 0;
+    const int64_t aform = tunables().all_form;
+    const size_t st_pages = (!t.range_cls && !t.dfa_pages.empty()) ? t.dfa_pages.size() * 2 : 0;
+    const uint32_t st_hot = (t.mode != ACGPU_MODE_WHOLEWORD && t.hy_n_states && (t.range_cls || st_pages > 0))
+                                ? ac_states_hot_rows(t.n_cls, t.hy_n_dense, (uint32_t)st_pages) : 0;
+    const bool usable = st_hot > 0 && !(aform & 1) && tunables().force_kernel == 0 && r.level == 0 && (own_len >= (1ull << 20) || (aform & 4));
+    // a pool that knows nothing yet and a long text (a synchronous call): the first 2^20 units of the shard are counted first (a
+    // synchronous call of this form on the pool's record, no records written: 60 us) -- the whole text then takes the form its
+    // beginning suggests
+    if (usable && !r.done && d.all_density < 0.0 && !(aform & 2) && own_len >= (1ull << 23)) {
+        CallRecord head = r;
+        head.shard.own_end = head.shard.own_begin + (1ull << 20);
+        head.shard.d_result = nullptr;
+        head.cap = 0;
+        head.profiled = false;
+        uint64_t n_head = 0;
+        int prc = enqueue_states(a, d, head, st_hot);
+        if (prc == ACGPU_OK) prc = collect(a, d, &head, &n_head, nullptr, nullptr);
+        // (no room for the probe's state words: like the call itself below, the tile kernel it is -- the pool stays without a
+        // density, so a later call asks again)
+        if (prc != ACGPU_OK && prc != ACGPU_E_OVERFLOW && prc != ACGPU_E_NOMEM) return prc;
+    }
+    if (usable && ((aform & 2) || d.all_density >= kStatesFormDensity)) *hot = st_hot;
+    return ACGPU_OK;
+}
+
+// An ALL / WHOLEWORD scan into the scratch slices: what a scan form's setup is given, and what it leaves for the ordering stage.
+struct AllScan {
+    const DevTables *T = nullptr; // the scan's tables (WHOLEWORD: folded_tables for a scan that folds in every lookup)
+    unsigned long long *counters = nullptr, *counters_next = nullptr; // this call's set of slot counters, the next call's
+    uint32_t *overflow_word = nullptr;
+    uint64_t scratch_cap = 0;
+    bool fused_only = false; // the redo: the fused kernel, one scratch slice
+    // left by the setup
+    enum class Order { Permute, PermuteWg, WwCompact, FusedTail } order = Order::Permute;
+    uint32_t n_slices = 1, n_chunks = 0, chunk_units = 0, perm_base = 0, regions_per_wg = 0, ww_region_cap = 0;
+    uint64_t slice_slots = 0;
+    const uint32_t *id_map = nullptr;
+    int by_start = 0;
+    const char *kname = "";
+    uint64_t scanned = 0;
+};
+
+// The fused tail's part of a tile launch (TileLaunch::fused_tail): the records' final place and where the call's result goes.
+int set_fused_tail(TileLaunch &L, const CallRecord &r, AllScan &A, const uint32_t *id_map) {
+    int rc;
+    A.order = AllScan::Order::FusedTail;
+    L.fused_tail = 1;
+    L.d_out = r.d_out;
+    L.out_cap = r.cap;
+    L.out_map = r.record_kind == ACGPU_REC_MAP ? 1 : 0;
+    L.d_id_map = id_map;
+    if ((rc = slot_on_device(r, &L.tail_result))) return rc;
+    L.tail_d_result = reinterpret_cast<acgpu_device_result *>(r.shard.d_result);
+    L.tail_zero_counters = A.counters_next;
+    return ACGPU_OK;
+}
+
+#ifdef ACGPU_TIMING
+// ACGPU_TIMING builds: the scan kernels' s_memtime counters (8 words per wave, 16 waves per workgroup), read back after a
+// synchronous call
+DevBuf g_timing;
+int timing_arm(TileLaunch &L, hipStream_t stream) {
+    int rc;
+    if ((rc = g_timing.ensure((size_t)L.grid * 16 * 8 * 8))) return rc;
+    HIP_TRY(hipMemsetAsync(g_timing.p, 0, (size_t)L.grid * 16 * 8 * 8, stream));
+    L.d_timing = (unsigned long long *)g_timing.p;
+    return ACGPU_OK;
+}
+
+int timing_read(const TileLaunch &L, hipStream_t stream, std::vector<unsigned long long> &h) {
+    HIP_TRY(hipStreamSynchronize(stream));
+    h.assign((size_t)L.grid * 16 * 8, 0);
+    HIP_TRY(hipMemcpy(h.data(), g_timing.p, h.size() * 8, hipMemcpyDeviceToHost));
+    return ACGPU_OK;
+}
+
+// where a WholeWord wave's time goes (s_memtime ticks, 100 MHz), averaged over the waves
+int timing_report_ww(const TileLaunch &L, bool fused_tail, hipStream_t stream) {
+    std::vector<unsigned long long> h;
+    if (int rc = timing_read(L, stream, h)) return rc;
+    double sum[8] = {0}; size_t nw = 0;
+    for (size_t w = 0; w < h.size() / 8; ++w) {
+        if (!h[w * 8]) continue;
+        nw++;
+        for (int i = 0; i < 8; ++i) sum[i] += (double)h[w * 8 + i];
+    }
+    if (fused_tail) { // the workgroups in the order of their numbers: scan end, counts there, copy done (s_memtime ticks from the first scan end)
+        unsigned long long t0 = ~0ull;
+        for (size_t w = 0; w < h.size() / 8; ++w) if (h[w * 8]) t0 = std::min(t0, h[w * 8]);
+        const size_t G = (size_t)L.grid;
+        for (size_t b0 = 0; b0 < G; b0 += std::max<size_t>(G / 16, 1)) {
+            double se = 0, be = 0, ce = 0; size_t k = 0;
+            for (size_t b = b0; b < std::min(G, b0 + std::max<size_t>(G / 16, 1)); ++b)
+                for (size_t w = b * 16; w < b * 16 + 16; ++w) if (h[w * 8]) { se = std::max(se, (double)(h[w * 8] - t0)); be = std::max(be, (double)(h[w * 8 + 1] - t0)); ce = std::max(ce, (double)(h[w * 8 + 2] - t0)); k++; }
+            fprintf(stderr, "[ww fused tail] workgroups %3zu..: last scan end %8.0f | counts below there %8.0f | last copy done %8.0f\n", b0, se, be, ce);
+        }
+    } else
+    if (nw) fprintf(stderr, "[ww timing] waves %zu total %.0f | windows %.0f | chunk1 %.0f | chunk2 %.0f | hash+bloom %.0f | probes %.0f | emission %.0f | calls %.1f\n",
+                    nw, sum[0] / nw, sum[1] / nw, sum[2] / nw, sum[3] / nw, sum[4] / nw, sum[5] / nw, sum[6] / nw, sum[7] / nw);
+    return ACGPU_OK;
+}
+
+// where an AhoCorasick tile wave's time goes, and the spread of the waves' durations
+int timing_report_tile(const TileLaunch &L, hipStream_t stream) {
+    std::vector<unsigned long long> h;
+    if (int rc = timing_read(L, stream, h)) return rc;
+    double sum[8] = {0}, mx0 = 0, vt[4] = {0, 0, 0, 0}; size_t nw = 0;
+    for (size_t w = 0; w < h.size() / 8; ++w) {
+        if (!h[w * 8]) continue;
+        nw++;
+        for (int i = 0; i < 6; ++i) sum[i] += (double)h[w * 8 + i];
+        vt[0] += (double)(h[w * 8 + 6] & 0xffffffffu); vt[1] += (double)(h[w * 8 + 6] >> 32);
+        vt[2] += (double)(h[w * 8 + 7] & 0xffffffffu); vt[3] += (double)(h[w * 8 + 7] >> 32);
+        mx0 = std::max(mx0, (double)h[w * 8]);
+    }
+    { // spread of the waves' durations: per XCD (workgroup modulo 8) and per workgroup
+        double xs[8] = {0}, xm[8] = {0}; size_t xn[8] = {0}; double bmin = 1e30, bmax = 0, wmin = 1e30;
+        for (size_t b = 0; b < (size_t)L.grid; ++b) {
+            double bs = 0; size_t bn = 0;
+            for (size_t w = b * 16; w < b * 16 + 16; ++w) if (h[w * 8]) { bs += (double)h[w * 8]; bn++; xm[b % 8] = std::max(xm[b % 8], (double)h[w * 8]); wmin = std::min(wmin, (double)h[w * 8]); }
+            if (!bn) continue;
+            xs[b % 8] += bs; xn[b % 8] += bn;
+            bmin = std::min(bmin, bs / bn); bmax = std::max(bmax, bs / bn);
+        }
+        fprintf(stderr, "[timing] wave min %.0f; workgroup averages %.0f .. %.0f; per XCD avg/max:", wmin, bmin, bmax);
+        for (int x = 0; x < 8; ++x) if (xn[x]) fprintf(stderr, " %.0f/%.0f", xs[x] / xn[x], xm[x]);
+        fprintf(stderr, "\n[timing] by wave slot in the workgroup:");
+        for (size_t sl = 0; sl < 16; ++sl) {
+            double a = 0; size_t n2 = 0;
+            for (size_t b = 0; b < (size_t)L.grid; ++b) if (h[(b * 16 + sl) * 8]) { a += (double)h[(b * 16 + sl) * 8]; n2++; }
+            fprintf(stderr, " %.0f", n2 ? a / n2 : 0.0);
+        }
+        fprintf(stderr, "\n");
+    }
+    if (nw) fprintf(stderr, "[timing] verification: windows %.0f | K-gram nodes %.0f | walks %.0f | emission %.0f\n", vt[0] / nw, vt[1] / nw, vt[2] / nw, vt[3] / nw);
+    if (nw) fprintf(stderr, "[timing] waves %zu  total avg %.0f max %.0f | stream wait %.0f | drain %.0f (%.1f calls) | filter+L2 %.0f | passes %.1f  (s_memtime ticks, 100 MHz)\n",
+                    nw, sum[0] / nw, mx0, sum[1] / nw, sum[2] / nw, sum[5] / nw, sum[3] / nw, sum[4] / nw);
+    return ACGPU_OK;
+}
+#endif
+
+// WHOLEWORD (fold-consistent tables): the WholeWord tile kernels over regions -- run starts instead of K-gram candidates, ranks
+// by match start, halos of 1 unit on the left and max_len + 1 on the right.
+int setup_ww_scan(acgpu_automaton *a, DeviceState &d, CallRecord &r, AllScan &A) {
+    const HostTables &t = a->t;
+    const acgpu_shard *sh = &r.shard;
+    const DevTables &T = *A.T;
     const uint64_t own_len = sh->own_end - sh->own_begin;
-    // WHOLEWORD (fold-consistent tables) is the same pipeline around another scan kernel: run starts instead of K-gram
-    // candidates, ranks by match start, halos of 1 unit on the left and max_len + 1 on the right
+    int rc;
+    TileLaunch L{};
+    L.block = tile_block_threads();
+    const int waves_per_block = L.block / 64;
+    // regions as large as still gives every wave one (fewer forced drains: 65536 against 16384 units -2 % at config 5's share)
+    const uint64_t ww_waves = (uint64_t)d.n_cu * ww_blocks_per_cu() * waves_per_block;
+    uint64_t R = tunables().region_units > 0 ? (uint64_t)tunables().region_units
+                 : own_len >= 65536 * ww_waves ? 65536 : own_len >= 32768 * ww_waves ? 32768 : 16384;
+    if (tunables().region_units <= 0 && own_len >= 32768 * ww_waves) { // long shards: regions that fill the waves evenly
+        const uint64_t Rb = balanced_region_units(sh->own_end - (sh->own_begin & ~7ull), ww_waves, tile_group_units(), 16384, 16, 65536);
+        if (Rb) R = Rb;
+    }
+    { const uint64_t g = tile_group_units(); R = std::max<uint64_t>(g, (R + g - 1) / g * g); }
+    L.region_units = (uint32_t)R;
+    const uint64_t base8 = sh->own_begin & ~7ull;
+    L.n_regions = (uint32_t)((sh->own_end - base8 + R - 1) / R);
+    L.regions_per_wave = (uint32_t)((L.n_regions + ww_waves - 1) / ww_waves);
+    const uint64_t waves_used = ((uint64_t)L.n_regions + L.regions_per_wave - 1) / L.regions_per_wave;
+    L.grid = (int)((waves_used + waves_per_block - 1) / waves_per_block);
+    A.perm_base = (uint32_t)base8;
+    A.by_start = 1;
+    L.d_hay = sh->d_hay;
+    L.n_units = (uint32_t)sh->n_units;
+    L.own_begin = (uint32_t)sh->own_begin;
+    L.own_end = (uint32_t)sh->own_end;
+    L.cap = A.scratch_cap;
+    L.lds_bytes = ww_lds_bytes(L.block, T);
+    L.debug = (uint32_t)tunables().tile_debug | (tunables().force_kernel == 1 ? 256u : 0u); // 256: trie-walk verification
+    L.d_overflow = A.overflow_word;
+    // one scratch slice and slot counter per workgroup (config 5 emits 15 M records per shard: 60 k reservations that one
+    // counter would serve at under 100 per microsecond); a slice that fills up -> redo with one slice
+    if (!A.fused_only && L.grid > 1 && !(L.debug & 16384u)) {
+        A.n_slices = (uint32_t)std::min<int>(L.grid, kMaxSlices);
+        A.slice_slots = A.scratch_cap / A.n_slices;
+    }
+    L.n_slices = A.n_slices;
+    L.slice_slots = (uint32_t)A.slice_slots;
+    if ((rc = d.chunk_counts.ensure((size_t)L.n_regions * 4))) return rc;
+    if ((rc = d.offsets.ensure((size_t)L.n_regions * 8))) return rc;
+    if ((rc = d.scan_tmp.ensure(((size_t)L.n_regions / 2048 + 2) * 8))) return rc;
+    L.d_scratch = (ScratchRec *)d.scratch.p;
+    L.d_counter = A.counters;
+    L.d_region_counts = (uint32_t *)d.chunk_counts.p;
+    // region-local record slots (a region of R units holds at most R/2 + 1 words): no slot reservations in the scan, and a
+    // coalesced copy instead of the permutation (tunable tile_debug bit 134217728: the scratch slices + k_permute, for A/B)
+    L.d_region_recs = nullptr;
+    L.region_cap = (uint32_t)(R / 2 + 1);
+    const uint64_t ww_rec_bytes = (uint64_t)L.n_regions * L.region_cap * 12;
+    bool direct = !(tunables().tile_debug & 134217728) && ww_rec_bytes <= (24ull << 30);
+    // The fused tail of k_ww_pp (TileLaunch::fused_tail, ft_total16): no counts, prefix sums or copy pass behind the scan -- a
+    // wave's records go to its own area and, when the workgroups with lower numbers are done, from there to their final
+    // place.  (Tunable ww_ramp_pm: spans that grow with the workgroup's number, so that copies would run while later
+    // workgroups still scan -- measured slower at every slope, 0 by default: EXPERIMENTS.md, round 6.)
+    // Tunable tile_form bit 2: never (the region-local slots + k_ww_compact: A/B, tests).
+    // Its areas take the place of the region-local slots: which of the two is decided before the one allocation below.
+    bool fused = false;
+    int block_ft = L.block;
+    uint64_t total16 = 0, G = 0, area_recs = 0;
+    if (direct && !A.fused_only && !(tunables().tile_form & 2) && ww_pp_serves(T, L)) {
+        // (tunable ww_block: workgroups of fewer waves, two to a CU when their LDS allows -- A/B)
+        const int64_t wb = tunables().ww_block;
+        block_ft = (wb >= 64 && wb <= 1024 && wb % 64 == 0) ? (int)wb : L.block;
+        const uint64_t wpb = (uint64_t)block_ft / 64;
+        // (two workgroups: when each needs at most half the LDS, and for the 16-unit form only -- the 32-unit form's registers allow four waves per SIMD)
+        const uint64_t per_cu = wb > 0 && t.max_len <= 16 && ww_pp_lds_total(T, L, block_ft) <= 80 * 1024 ? 2 : 1;
+        const uint64_t tiles = (sh->own_end - base8 + 511) / 512;
+        total16 = (tiles + wpb - 1) / wpb;
+        G = std::min<uint64_t>((uint64_t)d.n_cu * per_cu, total16);
+        area_recs = total16 * wpb * 512 / 2 + G * wpb + 8;
+        fused = G >= 1 && G <= (uint64_t)kMaxSlices && area_recs < (1ull << 32);
+    }
+    if (direct) {
+        // (about 6 bytes per haystack unit: on a device that cannot spare them the call falls back to the scratch slices +
+        // k_permute instead of failing; tunable tile_debug bit 2^40: the allocation "fails", for the test of that path)
+        rc = (tunables().tile_debug & (1ll << 40)) ? ACGPU_E_NOMEM : d.ww_recs.ensure((fused ? area_recs * 12 : ww_rec_bytes) + 64);
+        if (rc == ACGPU_E_NOMEM) direct = fused = false;
+        else if (rc != ACGPU_OK) return rc;
+    }
+    if (direct) {
+        L.d_region_recs = (int32_t *)d.ww_recs.p;
+        A.order = AllScan::Order::WwCompact;
+        A.ww_region_cap = L.region_cap;
+    }
+    if (fused) {
+        L.grid = (int)G;
+        L.block = block_ft;
+        L.ft_total16 = (uint32_t)total16;
+        const int64_t ramp = tunables().ww_ramp_pm;
+        L.ft_ramp_pm = (uint32_t)(ramp < 0 ? 0 : std::min<int64_t>(ramp, 1000));
+        if ((rc = set_fused_tail(L, r, A, nullptr))) return rc;
+    } else {
+        HIP_TRY(hipMemsetAsync(d.chunk_counts.p, 0, (size_t)L.n_regions * 4, r.stream));
+    }
+#ifdef ACGPU_TIMING
+    if ((rc = timing_arm(L, r.stream))) return rc;
+#endif
+    if (r.profiled) { // (the kernel's own dispatch timestamps: no marker packets around it)
+        L.ev_start = r.ev[0];
+        L.ev_stop = r.ev[1];
+    }
+    if (fused) L.ev_stop = (r.profiled || r.done) ? r.ev[2] : nullptr; // the scan is the call's only kernel: its end is the call's
+    HIP_TRY(launch_ww_tile(T, L, r.stream, &A.kname));
+#ifdef ACGPU_TIMING
+    if (!r.done && (rc = timing_report_ww(L, fused, r.stream))) return rc;
+#endif
+    A.n_chunks = L.n_regions;
+    A.chunk_units = L.region_units;
+    A.scanned = own_len;
+    return ACGPU_OK;
+}
+
+// ALL: the position-parallel K-gram tile kernel (fused, or the split form: filter + verification) over regions.
+int setup_tile_scan(acgpu_automaton *a, DeviceState &d, CallRecord &r, AllScan &A) {
+    const acgpu_shard *sh = &r.shard;
+    const uint64_t own_len = sh->own_end - sh->own_begin;
+    int rc;
+    TileLaunch L{};
+    L.block = tile_block_threads();
+    const int waves_per_block = L.block / 64;
+    // regions of 16384 units, or 32768 when that still leaves every wave two of them (fewer forced drains: -1.1 % at
+    // config 2 in interleaved A/B; 65536 was no better)
+    uint64_t R = tunables().region_units > 0 ? (uint64_t)tunables().region_units
+                 : own_len >= 2ull * 32768 * d.n_cu * waves_per_block ? 32768 : 16384;
+    if (tunables().region_units <= 0 && own_len >= 2ull * 16384 * d.n_cu * waves_per_block) { // long shards: regions that fill the waves evenly
+        const uint64_t Rb = balanced_region_units(sh->own_end - (sh->own_begin & ~7ull), (uint64_t)d.n_cu * waves_per_block, tile_group_units(),
+                                                  12288, 16, 32768);
+        if (Rb) R = Rb;
+    }
+    { const uint64_t g = tile_group_units(); R = std::max<uint64_t>(g, (R + g - 1) / g * g); }
+    L.region_units = (uint32_t)R;
+    const uint64_t base8 = sh->own_begin & ~7ull; // regions are laid out from the 16-byte aligned start
+    L.n_regions = (uint32_t)((sh->own_end - base8 + R - 1) / R);
+    const uint64_t waves_max = (uint64_t)d.n_cu * waves_per_block;
+    L.regions_per_wave = (uint32_t)((L.n_regions + waves_max - 1) / waves_max);
+    const uint64_t waves_used = ((uint64_t)L.n_regions + L.regions_per_wave - 1) / L.regions_per_wave;
+    L.grid = (int)((waves_used + waves_per_block - 1) / waves_per_block);
+    A.perm_base = (uint32_t)base8;
+    A.id_map = d.T.rterm;
+    L.d_hay = sh->d_hay;
+    L.n_units = (uint32_t)sh->n_units;
+    L.own_begin = (uint32_t)sh->own_begin;
+    L.own_end = (uint32_t)sh->own_end;
+    L.cap = A.scratch_cap;
+    L.lds_bytes = tile_lds_bytes(d.T, L.block);
+    L.debug = (uint32_t)tunables().tile_debug;
+    L.d_overflow = A.overflow_word;
+    // one scratch slice and slot counter per workgroup (the redo after an overflow takes one slice)
+    if (!A.fused_only && L.grid > 1 && !(L.debug & 16384u)) { // 16384: A/B, one counter
+        A.n_slices = (uint32_t)std::min<int>(L.grid, kMaxSlices);
+        A.slice_slots = A.scratch_cap / A.n_slices;
+    }
+    L.n_slices = A.n_slices;
+    L.slice_slots = (uint32_t)A.slice_slots;
+    L.wg_sums = 0;
+    if ((rc = d.chunk_counts.ensure((size_t)L.n_regions * 4))) return rc;
+    if ((rc = d.offsets.ensure((size_t)L.n_regions * 8))) return rc;
+    if ((rc = d.scan_tmp.ensure(((size_t)L.n_regions / 2048 + 2) * 8))) return rc;
+    L.d_scratch = (ScratchRec *)d.scratch.p;
+    L.d_counter = A.counters;
+    L.d_region_counts = (uint32_t *)d.chunk_counts.p;
+    // (every region's count is written by the wave that owns the region: no memset)
+    bool split = !A.fused_only && use_split_form(d.T);
+    if (split) {
+        L.n_slices = A.n_slices = 1; // (the verification kernel's grid is not the filter's)
+        L.slice_slots = (uint32_t)(A.slice_slots = A.scratch_cap);
+        // a wave's slice holds one candidate per 8 units of its span (the filter passes ~2 % on selective
+        // dictionaries); a haystack that needs more is redone with the fused kernel
+        const uint64_t per_wave = (uint64_t)L.regions_per_wave * R / (uint64_t)std::max<int64_t>(1, tunables().split_cand_div) + 2 * 1024;
+        if (per_wave * waves_used >= (1ull << 32)) split = false;
+        else {
+            L.cands_per_wave = (uint32_t)per_wave;
+            if ((rc = d.cands.ensure(per_wave * waves_used * 4 + 64))) return rc;
+            if ((rc = d.region_cands.ensure((size_t)L.n_regions * 8))) return rc;
+            L.d_cands = (uint32_t *)d.cands.p;
+            L.d_region_cands = (uint2 *)d.region_cands.p;
+            HIP_TRY(hipMemsetAsync(d.region_cands.p, 0, (size_t)L.n_regions * 8, r.stream)); // unwritten = no candidates
+            L.verify_grid = (int)std::min<uint64_t>(((uint64_t)L.n_regions + 3) / 4, (uint64_t)d.n_cu * 8);
+            // every verification wave may hold one partly used reservation of scratch slots
+            const uint64_t need = std::min<uint64_t>(std::max<uint64_t>(r.cap, 1) + (uint64_t)L.verify_grid * 4 * tile_reserve_slots(),
+                                                     0xffffffe0ull);
+            if (need > L.cap) {
+                if ((rc = d.scratch.ensure(need * sizeof(ScratchRec)))) return rc;
+                L.cap = A.scratch_cap = need;
+                L.slice_slots = (uint32_t)(A.slice_slots = A.scratch_cap);
+                L.d_scratch = (ScratchRec *)d.scratch.p;
+            }
+        }
+    }
+    // one finalize launch instead of three (prefix-sum kernels + permute) when a scratch slice is a workgroup: the scan
+    // kernel leaves every workgroup's record count next to its slot counter and the permute pass (k_permute_wg) derives
+    // its offsets from those and the region counts of its own workgroup.  (tunable tile_debug bit 262144: the old way)
+    const bool fused_finalize = !split && A.n_slices == (uint32_t)L.grid && L.grid <= kMaxSlices &&
+                                (uint64_t)waves_per_block * L.regions_per_wave <= kPermuteWgRegions && !(L.debug & 262144u);
+    if (fused_finalize) A.order = AllScan::Order::PermuteWg;
+    L.wg_sums = fused_finalize ? 1u : 0u;
+    A.regions_per_wg = (uint32_t)waves_per_block * L.regions_per_wave;
+    // The fused tail (TileLaunch::fused_tail): no finalize launch at all -- the scan's workgroups put their own slices in order
+    // when their spans are scanned, each behind the counts of the workgroups that started before it, and the last one
+    // reports the call's result.  Same conditions as the one-launch finalize.  Tunable tile_form bit 1: never (A/B, tests).
+    const bool fused = fused_finalize && !(tunables().tile_form & 1);
+    if (fused) {
+        L.wg_sums = 0; // (the workgroups' sums go through their own LDS)
+        if ((rc = set_fused_tail(L, r, A, A.id_map))) return rc;
+    }
+#ifdef ACGPU_TIMING
+    if ((rc = timing_arm(L, r.stream))) return rc;
+#endif
+    if (split) {
+        if (r.profiled) HIP_TRY(hipEventRecord(r.ev[0], r.stream));
+        HIP_TRY(launch_ac_filter(d.T, L, r.stream, &A.kname));
+        if (r.profiled) HIP_TRY(hipEventRecord(r.ev[1], r.stream)); // the verification is accounted with the ordering
+        HIP_TRY(launch_ac_verify(d.T, L, r.stream));
+    } else {
+        if (r.profiled) { // (the kernel's own dispatch timestamps: no marker packets around it)
+            L.ev_start = r.ev[0];
+            L.ev_stop = r.ev[1];
+        }
+        if (fused) L.ev_stop = (r.profiled || r.done) ? r.ev[2] : nullptr; // the scan is the call's only kernel: its end is the call's
+        HIP_TRY(launch_ac_tile(d.T, L, r.stream, &A.kname));
+    }
+#ifdef ACGPU_TIMING
+    if (!r.done && !split && (rc = timing_report_tile(L, r.stream))) return rc;
+#endif
+    A.n_chunks = L.n_regions;
+    A.chunk_units = L.region_units;
+    A.scanned = own_len;
+    return ACGPU_OK;
+}
+
+// ALL: the general DFA chunk scan (any alphabet, any keyword lengths).
+int setup_dfa_scan(acgpu_automaton *a, DeviceState &d, CallRecord &r, AllScan &A) {
+    const HostTables &t = a->t;
+    const acgpu_shard *sh = &r.shard;
+    const uint64_t own_len = sh->own_end - sh->own_begin;
+    const uint32_t halo = t.max_len > 0 ? t.max_len - 1 : 0;
+    int rc;
+    ScanLaunch L{};
+    L.block = scan_block_threads();
+    L.grid = d.n_cu * (int)std::max<int64_t>(1, tunables().blocks_per_cu);
+    // tile_debug bit 2^43: the one-chain kernel of rounds 1-3 (A/B); bit 2^45 (ablation build): no lookups in global memory
+    L.debug = (uint32_t)((tunables().tile_debug >> 43) & 5);
+    if (sh->n_units < 64) L.debug |= 1u; // (k_ac_dfa takes the buffer's last vector whole: the old kernel reads unit by unit)
+    const uint64_t lanes = (uint64_t)L.grid * L.block * (uint64_t)((L.debug & 1u) ? 1 : std::max(1, scan_chains(d.T)));
+    uint64_t C = tunables().chunk_units > 0 ? (uint64_t)tunables().chunk_units
+                                            : std::max<uint64_t>({(own_len + lanes - 1) / lanes, 256, 16ull * halo});
+    C = std::max<uint32_t>(8, round_up8(C));
+    L.chunk_units = (uint32_t)C;
+    L.n_chunks = (uint32_t)((own_len + C - 1) / C);
+    // do not launch more workgroups than there are chunks
+    L.grid = (int)std::min<uint64_t>((uint64_t)L.grid, ((uint64_t)L.n_chunks + L.block - 1) / L.block);
+    L.d_hay = sh->d_hay;
+    L.n_units = (uint32_t)sh->n_units;
+    L.own_begin = (uint32_t)sh->own_begin;
+    L.own_end = (uint32_t)sh->own_end;
+    L.cap = A.scratch_cap; // every slot below min(counter, scratch_cap) must be written: the permute pass reads them all
+    L.lds_bytes = scan_queue_bytes(L.block) + (size_t)d.T.lds_entries * t.entry_bytes + 16;
+    if ((rc = d.chunk_counts.ensure((size_t)L.n_chunks * 4))) return rc;
+    if ((rc = d.offsets.ensure((size_t)L.n_chunks * 8))) return rc;
+    if ((rc = d.scan_tmp.ensure(((size_t)L.n_chunks / 2048 + 2) * 8))) return rc;
+    L.d_scratch = (ScratchRec *)d.scratch.p;
+    L.d_counter = A.counters;
+    L.d_chunk_counts = (uint32_t *)d.chunk_counts.p;
+    if (r.profiled) HIP_TRY(hipEventRecord(r.ev[0], r.stream));
+    HIP_TRY(launch_ac_scan(d.T, L, r.stream, &A.kname));
+    if (r.profiled) HIP_TRY(hipEventRecord(r.ev[1], r.stream));
+    A.n_chunks = L.n_chunks;
+    A.chunk_units = L.chunk_units;
+    A.scanned = own_len + (uint64_t)L.n_chunks * halo;
+    return ACGPU_OK;
+}
+
+// The ordering stage behind a scan form: the fused tail has done it inside the scan; otherwise the prefix sum of the chunk
+// counts (k_permute_wg derives its own) and the pass that puts the records in order, which reports {record count, overflow
+// word} into the record's pinned slot, clears the word and zeroes the other set of slot counters for the next call: no copy or
+// memset operations on the stream.
+int order_records(DeviceState &d, CallRecord &r, const AllScan &A) {
+    const int cs = d.cset;
+    if (A.order == AllScan::Order::FusedTail) { // nothing behind the scan kernel: it has ordered its records, reports the count and has zeroed the other counter set
+        d.cclean[1 - cs] = true;
+        d.cset = 1 - cs;
+        r.one_kernel = true;
+        return close_call(r, CallForm::FusedTail, A.kname, A.scanned, /*done_is_ev2=*/true);
+    }
+    int rc;
+    const hipStream_t stream = r.stream;
+    if (A.order != AllScan::Order::PermuteWg)
+        HIP_TRY(launch_exclusive_scan((const uint32_t *)d.chunk_counts.p, A.n_chunks, (uint64_t *)d.offsets.p,
+                                      (uint64_t *)d.scan_tmp.p, stream));
+    unsigned long long *d_slot = nullptr;
+    if ((rc = slot_on_device(r, &d_slot))) return rc;
+    const PermuteTail tail{d_slot, (const uint64_t *)d.scan_tmp.p + scan_tiles_for(A.n_chunks), A.overflow_word, A.counters_next,
+                           reinterpret_cast<acgpu_device_result *>(r.shard.d_result)};
+    // (k_ww_compact and k_permute_wg are one kernel that ends the call: profiled, it delivers its own end timestamp; a ticket's
+    // completion is that timestamp too, profiled or not -- no marker packet behind the call)
+    const bool ext_stop = (A.order == AllScan::Order::WwCompact || A.order == AllScan::Order::PermuteWg) && (r.profiled || r.done);
+    if (A.order == AllScan::Order::WwCompact)
+        HIP_TRY(launch_ww_compact((const int32_t *)d.ww_recs.p, A.ww_region_cap, (const uint32_t *)d.chunk_counts.p, (const uint64_t *)d.offsets.p,
+                                  A.n_chunks, r.record_kind, r.d_out, r.cap, stream, &tail, ext_stop ? r.ev[2] : nullptr));
+    else if (A.order == AllScan::Order::PermuteWg)
+        HIP_TRY(launch_permute_wg((const ScratchRec *)d.scratch.p, A.counters, A.n_slices, A.slice_slots, (const uint32_t *)d.chunk_counts.p,
+                                  A.n_chunks, A.regions_per_wg, A.perm_base, A.chunk_units, r.record_kind, r.d_out, r.cap, A.id_map, stream, &tail,
+                                  ext_stop ? r.ev[2] : nullptr));
+    else
+        HIP_TRY(launch_permute((const ScratchRec *)d.scratch.p, A.counters, A.n_slices, A.slice_slots,
+                               (const uint64_t *)d.offsets.p, A.perm_base, A.chunk_units, A.by_start, r.record_kind, r.d_out, r.cap, A.id_map,
+                               stream, &tail));
+    d.cclean[1 - cs] = true; // zeroed by the pass just launched
+    d.cset = 1 - cs;
+    if (r.profiled && !ext_stop) HIP_TRY(hipEventRecord(r.ev[2], stream));
+    return close_call(r, CallForm::Ordered, A.kname, A.scanned, ext_stop);
+}
+
+// ALL-mode pipeline on one shard (and WHOLEWORD over fold-consistent tables, or folded ones: r.folded): the empty call, the
+// states form, or a scan form (WholeWord tile kernels, the AhoCorasick tile kernel, the DFA chunk scan) and the ordering stage.
+// level 1: the redo after an overflow of the split form's candidate slices or of a scratch slice -- the fused kernel, one
+// scratch slice.
+int enqueue_all(acgpu_automaton *a, DeviceState &d, CallRecord &r, int level) {
+    const HostTables &t = a->t;
+    const acgpu_shard *sh = &r.shard;
+    const uint64_t own_len = sh->own_end - sh->own_begin;
     const bool ww = t.mode == ACGPU_MODE_WHOLEWORD;
     const uint32_t halo = ww ? 1u : (t.max_len > 0 ? t.max_len - 1 : 0);
     if (!sh->text_begin && sh->own_begin < halo) return ACGPU_E_INVALID; // left halo too short
     if (ww && !sh->text_end && sh->n_units - sh->own_end < (uint64_t)t.max_len + 1) return ACGPU_E_INVALID; // right halo
-    if (prof) {
-        std::memset(prof, 0, sizeof(*prof));
-    }
-    if (own_len == 0 || t.n_states <= 1) {
-        if (sh->d_result) HIP_TRY(hipMemsetAsync(sh->d_result, 0, sizeof(acgpu_device_result), stream));
-        if (tk) {
-            tk->h_count[0] = tk->h_count[1] = 0; // (no kernel will write the slot)
-            tk->profiled = false;
-            tk->stream = stream;
-            HIP_TRY(hipEventRecord(tk->done, stream));
-            return ACGPU_OK;
-        }
-        *n_out = 0;
-        return ACGPU_OK;
-    }
-    // Texts in which this dictionary matches densely (natural words in natural text: every filter passes, every verification walk
-    // is long): the automaton's state behind every unit (k_ac_states over the compact automaton of acgpu_build.cpp 6d), then the
-    // records from the states (acgpu_states.hip).  Its cost does not depend on the text (~ one gather per unit), the tile kernel's
-    // does: what this pool's last call found decides (records per unit; a pool's first call looks at the beginning of a long text,
-    // and takes the tile kernel for a short one or when it may not wait).
-    // Tunable all_form, bits: 1 = never, 2 = whatever the last call found, 4 = also for short texts.
-    {
-        const int64_t aform = tunables().all_form;
-        const size_t st_pages = (!t.range_cls && !t.dfa_pages.empty()) ? t.dfa_pages.size() * 2 : 0;
-        const uint32_t st_hot = (!ww && !Tov && t.hy_n_states && (t.range_cls || st_pages > 0))
-                                    ? ac_states_hot_rows(t.n_cls, t.hy_n_dense, (uint32_t)st_pages) : 0;
-        const bool usable = st_hot > 0 && !(aform & 1) && tunables().force_kernel == 0 && !fused_only && (own_len >= (1ull << 20) || (aform & 4));
-        // a pool that knows nothing yet and a long text (a call that may wait): the first 2^20 units of the shard are counted
-        // first (this form, no records written: 60 us) -- the whole text then takes the form its beginning suggests
-        if (usable && !tk && d.all_density < 0.0 && !(aform & 2) && own_len >= (1ull << 23)) {
-            acgpu_shard head = *sh;
-            head.own_end = head.own_begin + (1ull << 20);
-            head.d_result = nullptr;
-            uint64_t n_head = 0;
-            const int prc = match_all_states(a, d, &head, record_kind, d_out, 0, &n_head, stream, nullptr, nullptr, st_hot);
-            // (no room for the probe's state words: like the call itself below, the tile kernel it is -- the pool stays without a
-            // density, so a later call asks again)
-            if (prc != ACGPU_OK && prc != ACGPU_E_OVERFLOW && prc != ACGPU_E_NOMEM) return prc;
-        }
-        if (usable && ((aform & 2) || d.all_density >= kStatesFormDensity)) {
-            const int src = match_all_states(a, d, sh, record_kind, d_out, cap, n_out, stream, prof, tk, st_hot);
-            if (src != ACGPU_E_NOMEM) return src; // (no room for 4 bytes of state per unit -- before anything was launched: the tile kernel it is)
-        }
-    }
+    r.level = level;
+    if (own_len == 0 || t.n_states <= 1) return enqueue_empty(r, 0);
     int rc;
+    uint32_t st_hot = 0;
+    if ((rc = choose_states_form(a, d, r, &st_hot))) return rc;
+    if (st_hot) {
+        rc = enqueue_states(a, d, r, st_hot);
+        if (rc != ACGPU_E_NOMEM) return rc; // (no room for 4 bytes of state per unit -- before anything was launched: the tile kernel it is)
+    }
+    AllScan A;
+    const DevTables Tf = r.folded ? folded_tables(d) : DevTables{};
+    A.T = r.folded ? &Tf : &d.T;
+    A.fused_only = level > 0;
     const size_t counter_bytes = (size_t)kMaxSlices * kCounterStride * 8; // one set; layout: [set 0][set 1][overflow word]
     if ((rc = d.counter.ensure(2 * counter_bytes + 64))) return rc;
     if (d.counter.p != d.counter_seen) {
         d.counter_seen = d.counter.p;
         d.cclean[0] = d.cclean[1] = false;
-        HIP_TRY(hipMemsetAsync((char *)d.counter.p + 2 * counter_bytes, 0, 64, stream));
+        HIP_TRY(hipMemsetAsync((char *)d.counter.p + 2 * counter_bytes, 0, 64, r.stream));
     }
     const int cs = d.cset;
-    unsigned long long *counters = (unsigned long long *)((char *)d.counter.p + (size_t)cs * counter_bytes);
-    unsigned long long *counters_next = (unsigned long long *)((char *)d.counter.p + (size_t)(1 - cs) * counter_bytes);
-    uint32_t *overflow_word = (uint32_t *)((char *)d.counter.p + 2 * counter_bytes);
+    A.counters = (unsigned long long *)((char *)d.counter.p + (size_t)cs * counter_bytes);
+    A.counters_next = (unsigned long long *)((char *)d.counter.p + (size_t)(1 - cs) * counter_bytes);
+    A.overflow_word = (uint32_t *)((char *)d.counter.p + 2 * counter_bytes);
     // the tile kernel reserves scratch slots 256 at a time per wave: head-room for the unused tails; a quarter more than
     // the caller's capacity so that the scratch slices (one per workgroup) tolerate unevenly spread matches
-    uint64_t scratch_cap = std::min<uint64_t>(
-        std::max<uint64_t>(cap, 1) + cap / 4 +
+    A.scratch_cap = std::min<uint64_t>(
+        std::max<uint64_t>(r.cap, 1) + r.cap / 4 +
             (uint64_t)d.n_cu * (ww ? ww_blocks_per_cu() : 1) * (tile_block_threads() / 64) * tile_reserve_slots(),
         0xffffffe0ull);
-    if ((rc = d.scratch.ensure(scratch_cap * sizeof(ScratchRec)))) return rc;
-    if (!d.cclean[cs]) HIP_TRY(hipMemsetAsync(counters, 0, counter_bytes, stream)); // (normally zeroed by the previous call's permute pass)
+    if ((rc = d.scratch.ensure(A.scratch_cap * sizeof(ScratchRec)))) return rc;
+    if (!d.cclean[cs]) HIP_TRY(hipMemsetAsync(A.counters, 0, counter_bytes, r.stream)); // (normally zeroed by the previous call's permute pass)
     // from here on this set is in use; the other set only counts as clean once the permute pass that zeroes it has been
-    // launched (below) -- an early error return leaves both marked dirty and the next call clears its set itself
+    // launched (order_records) -- an early error return leaves both marked dirty and the next call clears its set itself
     d.cclean[0] = d.cclean[1] = false;
-    uint32_t n_slices = 1;
-    uint64_t slice_slots = scratch_cap;
-    const char *kname = "";
-    uint64_t scanned = 0;
-    uint32_t n_chunks = 0, chunk_units = 0, perm_base = (uint32_t)sh->own_begin;
-    const uint32_t *id_map = nullptr;
-    bool split = false, fused_finalize = false, ww_direct = false, ext_timed = false, fused_tail = false;
-    uint32_t regions_per_wg = 0, ww_region_cap = 0;
-    int by_start = 0;
-    if (ww) {
-        TileLaunch L{};
-        L.block = tile_block_threads();
-        const int waves_per_block = L.block / 64;
-        // regions as large as still gives every wave one (fewer forced drains: 65536 against 16384 units -2 % at config 5's share)
-        const uint64_t ww_waves = (uint64_t)d.n_cu * ww_blocks_per_cu() * waves_per_block;
-        uint64_t R = tunables().region_units > 0 ? (uint64_t)tunables().region_units
-                     : own_len >= 65536 * ww_waves ? 65536 : own_len >= 32768 * ww_waves ? 32768 : 16384;
-        if (tunables().region_units <= 0 && own_len >= 32768 * ww_waves) { // long shards: regions that fill the waves evenly
-            const uint64_t Rb = balanced_region_units(sh->own_end - (sh->own_begin & ~7ull), ww_waves, tile_group_units(), 16384, 16, 65536);
-            if (Rb) R = Rb;
-        }
-        { const uint64_t g = tile_group_units(); R = std::max<uint64_t>(g, (R + g - 1) / g * g); }
-        L.region_units = (uint32_t)R;
-        const uint64_t base8 = sh->own_begin & ~7ull;
-        L.n_regions = (uint32_t)((sh->own_end - base8 + R - 1) / R);
-        L.regions_per_wave = (uint32_t)((L.n_regions + ww_waves - 1) / ww_waves);
-        const uint64_t waves_used = ((uint64_t)L.n_regions + L.regions_per_wave - 1) / L.regions_per_wave;
-        L.grid = (int)((waves_used + waves_per_block - 1) / waves_per_block);
-        perm_base = (uint32_t)base8;
-        by_start = 1;
-        L.d_hay = sh->d_hay;
-        L.n_units = (uint32_t)sh->n_units;
-        L.own_begin = (uint32_t)sh->own_begin;
-        L.own_end = (uint32_t)sh->own_end;
-        L.cap = scratch_cap;
-        L.lds_bytes = ww_lds_bytes(L.block, Tov ? *Tov : d.T);
-        L.debug = (uint32_t)tunables().tile_debug | (tunables().force_kernel == 1 ? 256u : 0u); // 256: trie-walk verification
-        L.d_overflow = overflow_word;
-        // one scratch slice and slot counter per workgroup (config 5 emits 15 M records per shard: 60 k reservations that one
-        // counter would serve at under 100 per microsecond); a slice that fills up -> redo with one slice
-        if (!fused_only && L.grid > 1 && !(L.debug & 16384u)) {
-            n_slices = (uint32_t)std::min<int>(L.grid, kMaxSlices);
-            slice_slots = scratch_cap / n_slices;
-        }
-        L.n_slices = n_slices;
-        L.slice_slots = (uint32_t)slice_slots;
-        if ((rc = d.chunk_counts.ensure((size_t)L.n_regions * 4))) return rc;
-        if ((rc = d.offsets.ensure((size_t)L.n_regions * 8))) return rc;
-        if ((rc = d.scan_tmp.ensure(((size_t)L.n_regions / 2048 + 2) * 8))) return rc;
-        L.d_scratch = (ScratchRec *)d.scratch.p;
-        L.d_counter = counters;
-        L.d_region_counts = (uint32_t *)d.chunk_counts.p;
-        // region-local record slots (a region of R units holds at most R/2 + 1 words): no slot reservations in the scan, and a
-        // coalesced copy instead of the permutation (tunable tile_debug bit 134217728: the scratch slices + k_permute, for A/B)
-        L.d_region_recs = nullptr;
-        L.region_cap = (uint32_t)(R / 2 + 1);
-        const uint64_t ww_rec_bytes = (uint64_t)L.n_regions * L.region_cap * 12;
-        if (!(tunables().tile_debug & 134217728) && ww_rec_bytes <= (24ull << 30)) {
-            // (about 6 bytes per haystack unit: on a device that cannot spare them the call falls back to the scratch slices +
-            // k_permute instead of failing; tunable tile_debug bit 2^40: the allocation "fails", for the test of that path)
-            rc = (tunables().tile_debug & (1ll << 40)) ? ACGPU_E_NOMEM : d.ww_recs.ensure(ww_rec_bytes + 64);
-            if (rc == ACGPU_OK) {
-                L.d_region_recs = (int32_t *)d.ww_recs.p;
-                ww_direct = true;
-            } else if (rc != ACGPU_E_NOMEM) {
-                return rc;
-            }
-        }
-        // The fused tail of k_ww_pp (TileLaunch::fused_tail, ft_total16): no counts, prefix sums or copy pass behind the scan -- a
-        // wave's records go to its own area and, when the workgroups with lower numbers are done, from there to their final
-        // place.  (Tunable ww_ramp_pm: spans that grow with the workgroup's number, so that copies would run while later
-        // workgroups still scan -- measured slower at every slope, 0 by default: EXPERIMENTS.md, round 6.)
-        // Tunable tile_form bit 2: never (the region-local slots + k_ww_compact: A/B, tests).
-        if (ww_direct && !fused_only && !(tunables().tile_form & 2) && ww_pp_serves(Tov ? *Tov : d.T, L)) {
-            // (tunable ww_block: workgroups of fewer waves, two to a CU when their LDS allows -- A/B)
-            const int64_t wb = tunables().ww_block;
-            const int block_ft = (wb >= 64 && wb <= 1024 && wb % 64 == 0) ? (int)wb : L.block;
-            const uint64_t wpb = (uint64_t)block_ft / 64;
-            // (two workgroups: when each needs at most half the LDS, and for the 16-unit form only -- the 32-unit form's registers allow four waves per SIMD)
-            const uint64_t per_cu = wb > 0 && t.max_len <= 16 && ww_pp_lds_total(Tov ? *Tov : d.T, L, block_ft) <= 80 * 1024 ? 2 : 1;
-            const uint64_t tiles = (sh->own_end - base8 + 511) / 512, total16 = (tiles + wpb - 1) / wpb;
-            const uint64_t G = std::min<uint64_t>((uint64_t)d.n_cu * per_cu, total16);
-            const uint64_t area_recs = total16 * wpb * 512 / 2 + G * wpb + 8;
-            if (G >= 1 && G <= (uint64_t)kMaxSlices && area_recs < (1ull << 32) && (rc = d.ww_recs.ensure(area_recs * 12 + 64)) == ACGPU_OK) {
-                fused_tail = true;
-                L.d_region_recs = (int32_t *)d.ww_recs.p;
-                L.fused_tail = 1;
-                L.grid = (int)G;
-                L.block = block_ft;
-                L.ft_total16 = (uint32_t)total16;
-                const int64_t ramp = tunables().ww_ramp_pm;
-                L.ft_ramp_pm = (uint32_t)(ramp < 0 ? 0 : std::min<int64_t>(ramp, 1000));
-                L.d_out = d_out;
-                L.out_cap = cap;
-                L.out_map = record_kind == ACGPU_REC_MAP ? 1 : 0;
-                L.d_id_map = nullptr;
-                unsigned long long *h_slot_t = tk ? tk->h_count : d.h_counter, *d_slot_t = nullptr;
-                HIP_TRY(hipHostGetDevicePointer((void **)&d_slot_t, h_slot_t, 0));
-                L.tail_result = d_slot_t;
-                L.tail_d_result = reinterpret_cast<acgpu_device_result *>(sh->d_result);
-                L.tail_zero_counters = counters_next;
-            } else if (rc != ACGPU_OK && rc != ACGPU_E_NOMEM) {
-                return rc;
-            }
-        }
-        if (!fused_tail) HIP_TRY(hipMemsetAsync(d.chunk_counts.p, 0, (size_t)L.n_regions * 4, stream));
-#ifdef ACGPU_TIMING
-        static DevBuf ww_timing;
-        if ((rc = ww_timing.ensure((size_t)L.grid * 16 * 8 * 8))) return rc;
-        HIP_TRY(hipMemsetAsync(ww_timing.p, 0, (size_t)L.grid * 16 * 8 * 8, stream));
-        L.d_timing = (unsigned long long *)ww_timing.p;
-#endif
-        if (timed) { // (the kernel's own dispatch timestamps: no marker packets around it)
-            L.ev_start = ev[0];
-            L.ev_stop = ev[1];
-            ext_timed = true;
-        }
-        if (fused_tail) L.ev_stop = (timed || tk) ? ev[2] : nullptr; // the scan is the call's only kernel: its end is the call's
-        HIP_TRY(launch_ww_tile(Tov ? *Tov : d.T, L, stream, &kname));
-#ifdef ACGPU_TIMING
-        if (!tk) { // where a wave's time goes (s_memtime ticks, 100 MHz), averaged over the waves
-            HIP_TRY(hipStreamSynchronize(stream));
-            std::vector<unsigned long long> h((size_t)L.grid * 16 * 8);
-            HIP_TRY(hipMemcpy(h.data(), ww_timing.p, h.size() * 8, hipMemcpyDeviceToHost));
-            double sum[8] = {0}; size_t nw = 0;
-            for (size_t w = 0; w < h.size() / 8; ++w) {
-                if (!h[w * 8]) continue;
-                nw++;
-                for (int i = 0; i < 8; ++i) sum[i] += (double)h[w * 8 + i];
-            }
-            if (fused_tail) { // the workgroups in the order of their numbers: scan end, counts there, copy done (s_memtime ticks from the first scan end)
-                unsigned long long t0 = ~0ull;
-                for (size_t w = 0; w < h.size() / 8; ++w) if (h[w * 8]) t0 = std::min(t0, h[w * 8]);
-                const size_t G = (size_t)L.grid;
-                for (size_t b0 = 0; b0 < G; b0 += std::max<size_t>(G / 16, 1)) {
-                    double se = 0, be = 0, ce = 0; size_t k = 0;
-                    for (size_t b = b0; b < std::min(G, b0 + std::max<size_t>(G / 16, 1)); ++b)
-                        for (size_t w = b * 16; w < b * 16 + 16; ++w) if (h[w * 8]) { se = std::max(se, (double)(h[w * 8] - t0)); be = std::max(be, (double)(h[w * 8 + 1] - t0)); ce = std::max(ce, (double)(h[w * 8 + 2] - t0)); k++; }
-                    fprintf(stderr, "[ww fused tail] workgroups %3zu..: last scan end %8.0f | counts below there %8.0f | last copy done %8.0f\n", b0, se, be, ce);
-                }
-            } else
-            if (nw) fprintf(stderr, "[ww timing] waves %zu total %.0f | windows %.0f | chunk1 %.0f | chunk2 %.0f | hash+bloom %.0f | probes %.0f | emission %.0f | calls %.1f\n",
-                            nw, sum[0] / nw, sum[1] / nw, sum[2] / nw, sum[3] / nw, sum[4] / nw, sum[5] / nw, sum[6] / nw, sum[7] / nw);
-        }
-#endif
-        n_chunks = L.n_regions;
-        chunk_units = L.region_units;
-        scanned = own_len;
-        ww_region_cap = L.region_cap;
-    } else if (use_tile_kernel(t)) {
-        TileLaunch L{};
-        L.block = tile_block_threads();
-        const int waves_per_block = L.block / 64;
-        // regions of 16384 units, or 32768 when that still leaves every wave two of them (fewer forced drains: -1.1 % at
-        // config 2 in interleaved A/B; 65536 was no better)
-        uint64_t R = tunables().region_units > 0 ? (uint64_t)tunables().region_units
-                     : own_len >= 2ull * 32768 * d.n_cu * waves_per_block ? 32768 : 16384;
-        if (tunables().region_units <= 0 && own_len >= 2ull * 16384 * d.n_cu * waves_per_block) { // long shards: regions that fill the waves evenly
-            const uint64_t Rb = balanced_region_units(sh->own_end - (sh->own_begin & ~7ull), (uint64_t)d.n_cu * waves_per_block, tile_group_units(),
-                                                      12288, 16, 32768);
-            if (Rb) R = Rb;
-        }
-        { const uint64_t g = tile_group_units(); R = std::max<uint64_t>(g, (R + g - 1) / g * g); }
-        L.region_units = (uint32_t)R;
-        const uint64_t base8 = sh->own_begin & ~7ull; // regions are laid out from the 16-byte aligned start
-        L.n_regions = (uint32_t)((sh->own_end - base8 + R - 1) / R);
-        const uint64_t waves_max = (uint64_t)d.n_cu * waves_per_block;
-        L.regions_per_wave = (uint32_t)((L.n_regions + waves_max - 1) / waves_max);
-        const uint64_t waves_used = ((uint64_t)L.n_regions + L.regions_per_wave - 1) / L.regions_per_wave;
-        L.grid = (int)((waves_used + waves_per_block - 1) / waves_per_block);
-        perm_base = (uint32_t)base8;
-        id_map = d.T.rterm;
-        L.d_hay = sh->d_hay;
-        L.n_units = (uint32_t)sh->n_units;
-        L.own_begin = (uint32_t)sh->own_begin;
-        L.own_end = (uint32_t)sh->own_end;
-        L.cap = scratch_cap;
-        L.lds_bytes = tile_lds_bytes(d.T, L.block);
-        L.debug = (uint32_t)tunables().tile_debug;
-        L.d_overflow = overflow_word;
-        // one scratch slice and slot counter per workgroup (the redo after an overflow takes one slice)
-        if (!fused_only && L.grid > 1 && !(L.debug & 16384u)) { // 16384: A/B, one counter
-            n_slices = (uint32_t)std::min<int>(L.grid, kMaxSlices);
-            slice_slots = scratch_cap / n_slices;
-        }
-        L.n_slices = n_slices;
-        L.slice_slots = (uint32_t)slice_slots;
-        L.wg_sums = 0;
-        if ((rc = d.chunk_counts.ensure((size_t)L.n_regions * 4))) return rc;
-        if ((rc = d.offsets.ensure((size_t)L.n_regions * 8))) return rc;
-        if ((rc = d.scan_tmp.ensure(((size_t)L.n_regions / 2048 + 2) * 8))) return rc;
-        L.d_scratch = (ScratchRec *)d.scratch.p;
-        L.d_counter = counters;
-        L.d_region_counts = (uint32_t *)d.chunk_counts.p;
-        // (every region's count is written by the wave that owns the region: no memset)
-        split = !fused_only && use_split_form(d.T);
-        if (split) {
-            L.n_slices = n_slices = 1; // (the verification kernel's grid is not the filter's)
-            L.slice_slots = (uint32_t)(slice_slots = scratch_cap);
-            // a wave's slice holds one candidate per 8 units of its span (the filter passes ~2 % on selective
-            // dictionaries); a haystack that needs more is redone with the fused kernel
-            const uint64_t per_wave = (uint64_t)L.regions_per_wave * R / (uint64_t)std::max<int64_t>(1, tunables().split_cand_div) + 2 * 1024;
-            if (per_wave * waves_used >= (1ull << 32)) split = false;
-            else {
-                L.cands_per_wave = (uint32_t)per_wave;
-                if ((rc = d.cands.ensure(per_wave * waves_used * 4 + 64))) return rc;
-                if ((rc = d.region_cands.ensure((size_t)L.n_regions * 8))) return rc;
-                L.d_cands = (uint32_t *)d.cands.p;
-                L.d_region_cands = (uint2 *)d.region_cands.p;
-                HIP_TRY(hipMemsetAsync(d.region_cands.p, 0, (size_t)L.n_regions * 8, stream)); // unwritten = no candidates
-                L.verify_grid = (int)std::min<uint64_t>(((uint64_t)L.n_regions + 3) / 4, (uint64_t)d.n_cu * 8);
-                // every verification wave may hold one partly used reservation of scratch slots
-                const uint64_t need = std::min<uint64_t>(std::max<uint64_t>(cap, 1) + (uint64_t)L.verify_grid * 4 * tile_reserve_slots(),
-                                                         0xffffffe0ull);
-                if (need > L.cap) {
-                    if ((rc = d.scratch.ensure(need * sizeof(ScratchRec)))) return rc;
-                    L.cap = scratch_cap = need;
-                    L.slice_slots = (uint32_t)(slice_slots = scratch_cap);
-                    L.d_scratch = (ScratchRec *)d.scratch.p;
-                }
-            }
-        }
-        // one finalize launch instead of three (prefix-sum kernels + permute) when a scratch slice is a workgroup: the scan
-        // kernel leaves every workgroup's record count next to its slot counter and the permute pass (k_permute_wg) derives
-        // its offsets from those and the region counts of its own workgroup.  (tunable tile_debug bit 262144: the old way)
-        fused_finalize = !split && n_slices == (uint32_t)L.grid && L.grid <= kMaxSlices &&
-                         (uint64_t)waves_per_block * L.regions_per_wave <= kPermuteWgRegions && !(L.debug & 262144u);
-        L.wg_sums = fused_finalize ? 1u : 0u;
-        regions_per_wg = (uint32_t)waves_per_block * L.regions_per_wave;
-        // The fused tail (TileLaunch::fused_tail): no finalize launch at all -- the scan's workgroups put their own slices in order
-        // when their spans are scanned, each behind the counts of the workgroups that started before it, and the last one
-        // reports the call's result.  Same conditions as the one-launch finalize.  Tunable tile_form bit 1: never (A/B, tests).
-        if (fused_finalize && !(tunables().tile_form & 1)) {
-            fused_tail = true;
-            L.fused_tail = 1;
-            L.wg_sums = 0; // (the workgroups' sums go through their own LDS)
-            L.d_out = d_out;
-            L.out_cap = cap;
-            L.out_map = record_kind == ACGPU_REC_MAP ? 1 : 0;
-            L.d_id_map = id_map;
-            unsigned long long *h_slot_t = tk ? tk->h_count : d.h_counter, *d_slot_t = nullptr;
-            HIP_TRY(hipHostGetDevicePointer((void **)&d_slot_t, h_slot_t, 0));
-            L.tail_result = d_slot_t;
-            L.tail_d_result = reinterpret_cast<acgpu_device_result *>(sh->d_result);
-            L.tail_zero_counters = counters_next;
-        }
-#ifdef ACGPU_TIMING
-        static DevBuf timing;
-        if ((rc = timing.ensure((size_t)L.grid * 16 * 8 * 8))) return rc;
-        HIP_TRY(hipMemsetAsync(timing.p, 0, (size_t)L.grid * 16 * 8 * 8, stream));
-        L.d_timing = (unsigned long long *)timing.p;
-#endif
-        if (split) {
-            if (timed) HIP_TRY(hipEventRecord(ev[0], stream));
-            HIP_TRY(launch_ac_filter(d.T, L, stream, &kname));
-            if (timed) HIP_TRY(hipEventRecord(ev[1], stream)); // the verification is accounted with the ordering
-            HIP_TRY(launch_ac_verify(d.T, L, stream));
-        } else {
-            if (timed) { // (the kernel's own dispatch timestamps: no marker packets around it)
-                L.ev_start = ev[0];
-                L.ev_stop = ev[1];
-                ext_timed = true;
-            }
-            if (fused_tail) L.ev_stop = (timed || tk) ? ev[2] : nullptr; // the scan is the call's only kernel: its end is the call's
-            HIP_TRY(launch_ac_tile(d.T, L, stream, &kname));
-        }
-#ifdef ACGPU_TIMING
-        if (!tk && !split) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            std::vector<unsigned long long> h((size_t)L.grid * 16 * 8);
-            HIP_TRY(hipMemcpy(h.data(), timing.p, h.size() * 8, hipMemcpyDeviceToHost));
-            double sum[8] = {0}, mx0 = 0, vt[4] = {0, 0, 0, 0}; size_t nw = 0;
-            for (size_t w = 0; w < h.size() / 8; ++w) {
-                if (!h[w * 8]) continue;
-                nw++;
-                for (int i = 0; i < 6; ++i) sum[i] += (double)h[w * 8 + i];
-                vt[0] += (double)(h[w * 8 + 6] & 0xffffffffu); vt[1] += (double)(h[w * 8 + 6] >> 32);
-                vt[2] += (double)(h[w * 8 + 7] & 0xffffffffu); vt[3] += (double)(h[w * 8 + 7] >> 32);
-                mx0 = std::max(mx0, (double)h[w * 8]);
-            }
-            { // spread of the waves' durations: per XCD (workgroup modulo 8) and per workgroup
-                double xs[8] = {0}, xm[8] = {0}; size_t xn[8] = {0}; double bmin = 1e30, bmax = 0, wmin = 1e30;
-                for (size_t b = 0; b < (size_t)L.grid; ++b) {
-                    double bs = 0; size_t bn = 0;
-                    for (size_t w = b * 16; w < b * 16 + 16; ++w) if (h[w * 8]) { bs += (double)h[w * 8]; bn++; xm[b % 8] = std::max(xm[b % 8], (double)h[w * 8]); wmin = std::min(wmin, (double)h[w * 8]); }
-                    if (!bn) continue;
-                    xs[b % 8] += bs; xn[b % 8] += bn;
-                    bmin = std::min(bmin, bs / bn); bmax = std::max(bmax, bs / bn);
-                }
-                fprintf(stderr, "[timing] wave min %.0f; workgroup averages %.0f .. %.0f; per XCD avg/max:", wmin, bmin, bmax);
-                for (int x = 0; x < 8; ++x) if (xn[x]) fprintf(stderr, " %.0f/%.0f", xs[x] / xn[x], xm[x]);
-                fprintf(stderr, "\n[timing] by wave slot in the workgroup:");
-                for (size_t sl = 0; sl < 16; ++sl) {
-                    double a = 0; size_t n2 = 0;
-                    for (size_t b = 0; b < (size_t)L.grid; ++b) if (h[(b * 16 + sl) * 8]) { a += (double)h[(b * 16 + sl) * 8]; n2++; }
-                    fprintf(stderr, " %.0f", n2 ? a / n2 : 0.0);
-                }
-                fprintf(stderr, "\n");
-            }
-            if (nw) fprintf(stderr, "[timing] verification: windows %.0f | K-gram nodes %.0f | walks %.0f | emission %.0f\n", vt[0] / nw, vt[1] / nw, vt[2] / nw, vt[3] / nw);
-            if (nw) fprintf(stderr, "[timing] waves %zu  total avg %.0f max %.0f | stream wait %.0f | drain %.0f (%.1f calls) | filter+L2 %.0f | passes %.1f  (s_memtime ticks, 100 MHz)\n",
-                            nw, sum[0] / nw, mx0, sum[1] / nw, sum[2] / nw, sum[5] / nw, sum[3] / nw, sum[4] / nw);
-        }
-#endif
-        n_chunks = L.n_regions;
-        chunk_units = L.region_units;
-        scanned = own_len;
-    } else {
-        ScanLaunch L{};
-        L.block = scan_block_threads();
-        L.grid = d.n_cu * (int)std::max<int64_t>(1, tunables().blocks_per_cu);
-        // tile_debug bit 2^43: the one-chain kernel of rounds 1-3 (A/B); bit 2^45 (ablation build): no lookups in global memory
-        L.debug = (uint32_t)((tunables().tile_debug >> 43) & 5);
-        if (sh->n_units < 64) L.debug |= 1u; // (k_ac_dfa takes the buffer's last vector whole: the old kernel reads unit by unit)
-        const uint64_t lanes = (uint64_t)L.grid * L.block * (uint64_t)((L.debug & 1u) ? 1 : std::max(1, scan_chains(d.T)));
-        uint64_t C = tunables().chunk_units > 0 ? (uint64_t)tunables().chunk_units
-                                                : std::max<uint64_t>({(own_len + lanes - 1) / lanes, 256, 16ull * halo});
-        C = std::max<uint32_t>(8, round_up8(C));
-        L.chunk_units = (uint32_t)C;
-        L.n_chunks = (uint32_t)((own_len + C - 1) / C);
-        // do not launch more workgroups than there are chunks
-        L.grid = (int)std::min<uint64_t>((uint64_t)L.grid, ((uint64_t)L.n_chunks + L.block - 1) / L.block);
-        L.d_hay = sh->d_hay;
-        L.n_units = (uint32_t)sh->n_units;
-        L.own_begin = (uint32_t)sh->own_begin;
-        L.own_end = (uint32_t)sh->own_end;
-        L.cap = scratch_cap; // every slot below min(counter, scratch_cap) must be written: the permute pass reads them all
-        L.lds_bytes = scan_queue_bytes(L.block) + (size_t)d.T.lds_entries * t.entry_bytes + 16;
-        if ((rc = d.chunk_counts.ensure((size_t)L.n_chunks * 4))) return rc;
-        if ((rc = d.offsets.ensure((size_t)L.n_chunks * 8))) return rc;
-        if ((rc = d.scan_tmp.ensure(((size_t)L.n_chunks / 2048 + 2) * 8))) return rc;
-        L.d_scratch = (ScratchRec *)d.scratch.p;
-        L.d_counter = counters;
-        L.d_chunk_counts = (uint32_t *)d.chunk_counts.p;
-        if (timed) HIP_TRY(hipEventRecord(ev[0], stream));
-        HIP_TRY(launch_ac_scan(d.T, L, stream, &kname));
-        if (timed) HIP_TRY(hipEventRecord(ev[1], stream));
-        n_chunks = L.n_chunks;
-        chunk_units = L.chunk_units;
-        scanned = own_len + (uint64_t)L.n_chunks * halo;
-    }
-    if (fused_tail) { // nothing behind the scan kernel: it has ordered its records, reports the count and has zeroed the other counter set
-        d.cclean[1 - cs] = true;
-        d.cset = 1 - cs;
-        if (tk) {
-            tk->shard = *sh;
-            tk->record_kind = record_kind;
-            tk->d_out = d_out;
-            tk->stream = stream;
-            tk->done_is_ev2 = true;
-            tk->one_kernel = true;
-            tk->scanned = scanned;
-            std::snprintf(tk->kname, sizeof(tk->kname), "%s", kname);
-            return ACGPU_OK;
-        }
-        HIP_TRY(hipStreamSynchronize(stream));
-        if ((uint32_t)d.h_counter[1] != 0) // a scratch slice overflowed: fused kernel, one scratch slice
-            return match_all(a, d, sh, record_kind, d_out, cap, n_out, stream, prof, nullptr, true, Tov);
-        *n_out = *d.h_counter;
-        if (!ww) d.all_density = (double)*n_out / (double)own_len;
-        if (prof) {
-            HIP_TRY(hipEventElapsedTime(&prof->scan_ms, d.ev[0], d.ev[2]));
-            prof->finalize_ms = 0.0f;
-            prof->total_ms = prof->scan_ms;
-            prof->scan_units = scanned;
-            prof->n_matches = *n_out;
-            std::snprintf(prof->scan_kernel, sizeof(prof->scan_kernel), "%s", kname);
-        }
-        return *n_out > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
-    }
-    if (!fused_finalize)
-        HIP_TRY(launch_exclusive_scan((const uint32_t *)d.chunk_counts.p, n_chunks, (uint64_t *)d.offsets.p,
-                                      (uint64_t *)d.scan_tmp.p, stream));
-    // the permute pass reports {record count, overflow word} into the pinned host slot of this call, clears the word and
-    // zeroes the other set of slot counters for the next call: no copy or memset operations on the stream
-    unsigned long long *h_slot = tk ? tk->h_count : d.h_counter, *d_slot = nullptr;
-    HIP_TRY(hipHostGetDevicePointer((void **)&d_slot, h_slot, 0));
-    const PermuteTail tail{d_slot, (const uint64_t *)d.scan_tmp.p + scan_tiles_for(n_chunks), overflow_word, counters_next,
-                           reinterpret_cast<acgpu_device_result *>(sh->d_result)};
-    // (profiled: the last kernel of the finalize delivers its own end timestamp where it is ONE kernel that ends the call)
-    // (a ticket's completion is that timestamp too, profiled or not: no marker packet behind the call)
-    const bool ext_stop = ((timed && ext_timed) || (tk != nullptr && !split)) && (ww_direct || fused_finalize);
-    if (ww_direct)
-        HIP_TRY(launch_ww_compact((const int32_t *)d.ww_recs.p, ww_region_cap, (const uint32_t *)d.chunk_counts.p, (const uint64_t *)d.offsets.p,
-                                  n_chunks, record_kind, d_out, cap, stream, &tail, ext_stop ? ev[2] : nullptr));
-    else if (fused_finalize)
-        HIP_TRY(launch_permute_wg((const ScratchRec *)d.scratch.p, counters, n_slices, slice_slots, (const uint32_t *)d.chunk_counts.p,
-                                  n_chunks, regions_per_wg, perm_base, chunk_units, record_kind, d_out, cap, id_map, stream, &tail,
-                                  ext_stop ? ev[2] : nullptr));
-    else
-        HIP_TRY(launch_permute((const ScratchRec *)d.scratch.p, counters, n_slices, slice_slots,
-                               (const uint64_t *)d.offsets.p, perm_base, chunk_units, by_start, record_kind, d_out, cap, id_map,
-                               stream, &tail));
-    d.cclean[1 - cs] = true; // zeroed by the pass just launched
-    d.cset = 1 - cs;
-    if (timed && !ext_stop) HIP_TRY(hipEventRecord(ev[2], stream));
-    // exact record count = grand total of the per-chunk counts (the slot counter also counts reservation holes)
-    if (tk) {
-        tk->shard = *sh;
-        tk->record_kind = record_kind;
-        tk->d_out = d_out;
-        tk->stream = stream;
-        // (the call's last kernel delivered its end to ev[2]: that IS the call's completion -- one marker packet less per step)
-        tk->done_is_ev2 = ext_stop;
-        if (!ext_stop) HIP_TRY(hipEventRecord(tk->done, stream));
-        tk->scanned = scanned;
-        std::snprintf(tk->kname, sizeof(tk->kname), "%s", kname);
-        return ACGPU_OK;
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
-    if ((uint32_t)d.h_counter[1] != 0) // a candidate slice / scratch slice overflowed: fused kernel, one scratch slice
-        return match_all(a, d, sh, record_kind, d_out, cap, n_out, stream, prof, nullptr, true, Tov);
-    *n_out = *d.h_counter;
-    if (!ww) d.all_density = (double)*n_out / (double)own_len;
-    if (prof) {
-        HIP_TRY(hipEventElapsedTime(&prof->scan_ms, d.ev[0], d.ev[1]));
-        HIP_TRY(hipEventElapsedTime(&prof->finalize_ms, d.ev[1], d.ev[2]));
-        HIP_TRY(hipEventElapsedTime(&prof->total_ms, d.ev[0], d.ev[2]));
-        prof->scan_units = scanned;
-        prof->n_matches = *n_out;
-        std::snprintf(prof->scan_kernel, sizeof(prof->scan_kernel), "%s", kname);
-    }
-    return *n_out > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
+    A.slice_slots = A.scratch_cap;
+    A.perm_base = (uint32_t)sh->own_begin;
+    if (ww) rc = setup_ww_scan(a, d, r, A);
+    else if (use_tile_kernel(t)) rc = setup_tile_scan(a, d, r, A);
+    else rc = setup_dfa_scan(a, d, r, A);
+    if (rc) return rc;
+    return order_records(d, r, A);
 }
 
 // Marks the chain k0, nxt[k0], nxt[nxt[k0]], ... (nxt[k] in (k, M], nxt[M] = M; d_mark[k0] = 1 on entry, every other mark 0):
@@ -865,7 +904,7 @@ int mark_chain(DeviceState &d, uint32_t *d_nxt, uint32_t *d_tmp, uint32_t *d_mar
     bool one_pass = M >= one_pass_from && jump_bound <= 60000 && !(tunables().tile_debug & 2097152);
     uint64_t head = ~0ull, max_jump = 0;
     if (one_pass) {
-        // counter words used here: [2] chain head, [3] largest jump (bytes 16..32).  They lie inside match_all's first slot
+        // counter words used here: [2] chain head, [3] largest jump (bytes 16..32).  They lie inside enqueue_all's first slot
         // counter line (word 0 = slot counter, word 1 = workgroup sum, the rest of the 128-byte line is padding), which every
         // caller marks dirty (cclean[0] = false) so that the next AhoCorasick call clears it
         static_assert(kCounterStride >= 4, "mark_chain keeps its head and largest jump in words 2 and 3 of the first counter line");
@@ -919,26 +958,38 @@ int mark_chain(DeviceState &d, uint32_t *d_nxt, uint32_t *d_tmp, uint32_t *d_mar
     return ACGPU_OK;
 }
 
+// A LONGEST shard's own checks (the right halo, a chain entry inside the owned range or behind it); presets sh->chain_exit.
+int check_longest_shard(const HostTables &t, acgpu_shard *sh) {
+    const uint32_t halo = t.max_len > 0 ? t.max_len - 1 : 0;
+    if (!sh->text_end && sh->n_units - sh->own_end < halo) return ACGPU_E_INVALID; // right halo too short
+    if (sh->chain_entry < (int64_t)sh->own_begin) return ACGPU_E_INVALID;
+    sh->chain_exit = (int64_t)std::max<uint64_t>((uint64_t)sh->chain_entry, sh->own_end);
+    return ACGPU_OK;
+}
+
 // LONGEST over a dictionary whose suffix filter is selective: matches are sparse, so leftmost-longest is a selection
 // over the all-matches list (the AhoCorasick tile pipeline into an internal buffer + k_long_next + chain marking)
 // instead of a trie walk from every position.  Returns ACGPU_E_UNSUPPORTED when the haystack turns out to be dense in
 // matches (the caller then takes the walk).
 int match_longest_sparse(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_kind, void *d_out, uint64_t cap,
-                         uint64_t *n_out, hipStream_t stream, acgpu_profile *prof, uint64_t entry) {
+                         uint64_t *n_out, hipStream_t stream, acgpu_profile *prof) {
     const HostTables &t = a->t;
+    int rc;
+    if ((rc = check_longest_shard(t, sh))) return rc;
+    const uint64_t entry = (uint64_t)sh->chain_entry;
+    if (entry >= sh->own_end || t.n_states <= 1) return ACGPU_OK; // (the empty call)
     const uint64_t halo = t.max_len > 0 ? t.max_len - 1 : 0;
     const uint64_t own_len = sh->own_end - sh->own_begin;
     acgpu_shard all = *sh; // every occurrence that ENDS in the owned range or its right halo
     all.own_end = std::min<uint64_t>(sh->n_units, sh->own_end + halo);
     all.text_begin = 1; // occurrences that begin before the buffer begin before own_begin: not ours anyway
-    int rc;
     uint64_t m = 0;
     const uint64_t dense_limit = own_len / 4 + 4096;
     uint64_t acap = std::max<uint64_t>(d.short_recs.bytes > 16 ? (d.short_recs.bytes - 16) / ACGPU_REC_MAP : 0, own_len / 32 + (1 << 16));
     acgpu_profile all_prof;
     for (;;) {
         if ((rc = d.short_recs.ensure(acap * ACGPU_REC_MAP + 16))) return rc;
-        rc = match_all(a, d, &all, ACGPU_REC_MAP, d.short_recs.p, acap, &m, stream, prof ? &all_prof : nullptr);
+        rc = run_sync(enqueue_all, a, d, &all, ACGPU_REC_MAP, d.short_recs.p, acap, &m, stream, prof ? &all_prof : nullptr);
         if (rc == ACGPU_E_OVERFLOW) {
             if (m > dense_limit) return ACGPU_E_UNSUPPORTED;
             acap = m;
@@ -970,7 +1021,7 @@ int match_longest_sparse(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, in
     HIP_TRY(launch_shortest_emit((const int32_t *)d.short_recs.p, M, (const uint32_t *)d.short_mark.p,
                                  (const uint64_t *)d.offsets.p, d_total, record_kind, d_out, cap, (int64_t)entry,
                                  (unsigned long long *)d.counter.p, stream));
-    d.cclean[0] = false; // (the exit position went where match_all's first set of slot counters lives)
+    d.cclean[0] = false; // (the exit position went where enqueue_all's first set of slot counters lives)
     if (prof) HIP_TRY(hipEventRecord(d.ev[1], stream));
     HIP_TRY(hipMemcpyAsync(d.h_counter, d_total, 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipMemcpyAsync(d.h_counter + 1, d.counter.p, 8, hipMemcpyDeviceToHost, stream));
@@ -989,256 +1040,177 @@ int match_longest_sparse(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, in
     return *n_out > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
 }
 
-// LONGEST-mode pipeline on one shard: reverse scan -> chain count -> prefix sum -> chain write.
-// With a ticket (the walk pipeline only: want_async_longest) the call returns after enqueueing; acgpu_match_device_end collects it.
-int match_longest(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_kind, void *d_out, uint64_t cap,
-                  uint64_t *n_out, hipStream_t stream, acgpu_profile *prof, Ticket *tk = nullptr, int bits_level = 0) {
+// A two-letter alphabet in which every letter is a keyword: the text as one bit per unit, the chain's own positions only
+// (k_longest_bits, acgpu_longest_bits.hip) -- no length array, no synchronisation pass; Map records look their keyword ids up
+// by the matched text's own bits when they are written (keywords of up to 32 units; the rare longer ones by a walk).  The kernel checks
+// its own result (every segment's exit against the next one's entry) and raises the bail flag -- also for a unit outside
+// the alphabet --: collect() then redoes the call once more with a run-up of a whole segment (level 1), or by the walk pipeline
+// (level 2).
+int enqueue_longest_bits(acgpu_automaton *a, DeviceState &d, CallRecord &r, uint64_t entry, int bits_level) {
     const HostTables &t = a->t;
-    hipEvent_t *ev = tk ? tk->ev : d.ev;
-    const bool timed = tk ? tk->profiled : prof != nullptr;
-    const uint32_t halo = t.max_len > 0 ? t.max_len - 1 : 0;
-    if (!sh->text_end && sh->n_units - sh->own_end < halo) return ACGPU_E_INVALID; // right halo too short
-    if (sh->chain_entry < (int64_t)sh->own_begin) return ACGPU_E_INVALID;
-    if (prof) std::memset(prof, 0, sizeof(*prof));
-    const uint64_t entry = (uint64_t)sh->chain_entry;
-    sh->chain_exit = (int64_t)std::max<uint64_t>(entry, sh->own_end);
-    if (entry >= sh->own_end || t.n_states <= 1) {
-        *n_out = 0;
-        if (entry < sh->own_end) sh->chain_exit = (int64_t)sh->own_end;
-        if (tk) { // (no kernel will write the slot)
-            tk->h_count[0] = tk->h_count[1] = 0;
-            tk->h_count[2] = (unsigned long long)sh->chain_exit;
-            tk->profiled = false;
-            tk->stream = stream;
-            if (sh->d_result) HIP_TRY(hipMemsetAsync(sh->d_result, 0, sizeof(acgpu_device_result), stream));
-            HIP_TRY(hipEventRecord(tk->done, stream));
-        }
-        return ACGPU_OK;
+    const acgpu_shard *sh = &r.shard;
+    const hipStream_t stream = r.stream;
+    int rc;
+    LongestBitsLaunch Bl{};
+    Bl.d_hay = sh->d_hay;
+    Bl.n_units = (uint32_t)sh->n_units;
+    Bl.own_end = (uint32_t)sh->own_end;
+    Bl.entry = (uint32_t)entry;
+    Bl.g0 = (uint32_t)entry & ~127u; // (bitmap words in groups of four: 16-byte stores)
+    const uint32_t region_units = longest_bits_region_units();
+    Bl.n_regions = (uint32_t)((sh->own_end - Bl.g0 + region_units - 1) / region_units);
+    Bl.runup = bits_level == 0 ? longest_bits_seg_units() / 2 : longest_bits_seg_units();
+    Bl.max_len = t.max_len;
+    Bl.d_out = r.d_out;
+    Bl.cap = r.cap;
+    const size_t n_blk = ((size_t)Bl.n_regions + 63) / 64, state_words = 8 + (size_t)Bl.n_regions + n_blk + 2;
+    // exit / flag / count, a word per region, a word per block of 64 regions, the region counter: zero at the start of a call --
+    // the call's last kernel leaves them so; a memset only for a fresh (or larger) buffer and after a call that failed half way
+    const size_t state_had = d.bits_state.bytes;
+    if ((rc = d.bits_state.ensure(state_words * 8))) return rc;
+    if (d.bits_state.p != d.bits_state_seen || d.bits_state.bytes != state_had) {
+        HIP_TRY(hipMemsetAsync(d.bits_state.p, 0, d.bits_state.bytes, stream));
+        d.bits_state_seen = d.bits_state.p;
     }
-    const uint64_t own_len = sh->own_end - sh->own_begin;
-    if (!tk && filter_is_selective(t) && tunables().force_kernel != 1) { // selective suffix filter: selection over all matches
-        const int src = match_longest_sparse(a, d, sh, record_kind, d_out, cap, n_out, stream, prof, entry);
-        if (src != ACGPU_E_UNSUPPORTED) return src;
-        sh->chain_exit = (int64_t)std::max<uint64_t>(entry, sh->own_end); // dense in matches after all: the walk
+    if ((rc = d.blockmax.ensure((size_t)Bl.n_regions * 8 + 64))) return rc;
+    if ((rc = d.chainbits.ensure((size_t)Bl.n_regions * longest_bits_region_scratch_bytes() + 64))) return rc;
+    Bl.d_exit = (unsigned long long *)d.bits_state.p;
+    Bl.d_agg = Bl.d_exit + 8;
+    Bl.d_blk = Bl.d_agg + Bl.n_regions;
+    Bl.d_next = (uint32_t *)(Bl.d_blk + n_blk);
+    Bl.d_marks = (uint32_t *)d.chainbits.p;
+    Bl.d_xout = Bl.d_marks + (size_t)Bl.n_regions * (region_units / 32);
+    Bl.d_text = nullptr;
+    if (r.record_kind == ACGPU_REC_MAP) { // the regions' text bits, parked for the keyword ids (acgpu_longest_bits.hip)
+        if ((rc = d.lenbuf.ensure((size_t)Bl.n_regions * longest_bits_region_text_bytes() + 64))) return rc;
+        Bl.d_text = (uint32_t *)d.lenbuf.p;
     }
-    // A two-letter alphabet in which every letter is a keyword: the text as one bit per unit, the chain's own positions only
-    // (k_longest_bits, acgpu_longest_bits.hip) -- no length array, no synchronisation pass; Map records look their keyword ids up
-    // by the matched text's own bits when they are written (keywords of up to 32 units; the rare longer ones by a walk).  The kernel checks
-    // its own result (every segment's exit against the next one's entry) and raises the bail flag -- also for a unit outside
-    // the alphabet --: the call is then redone right here, or in acgpu_match_device_end: once more with a run-up of a whole
-    // segment (bits_level 1), then by the walk pipeline below (bits_level 2).
-    // Tunable longest_form, bits: 1 = never, 4 = also for short texts (tests).
-    const int64_t lform = tunables().longest_form;
-    const bool bits_form = bits_level < 2 && (record_kind == ACGPU_REC_SET || d.T.bits_idkeys != nullptr) && d.T.bits_rk != 0 && !(lform & 1) &&
-                           (own_len >= (1ull << 21) || (lform & 4)) && tunables().force_kernel == 0;
-    if (bits_form) {
-        int rc;
-        LongestBitsLaunch Bl{};
-        Bl.d_hay = sh->d_hay;
-        Bl.n_units = (uint32_t)sh->n_units;
-        Bl.own_end = (uint32_t)sh->own_end;
-        Bl.entry = (uint32_t)entry;
-        Bl.g0 = (uint32_t)entry & ~127u; // (bitmap words in groups of four: 16-byte stores)
-        const uint32_t region_units = longest_bits_region_units();
-        Bl.n_regions = (uint32_t)((sh->own_end - Bl.g0 + region_units - 1) / region_units);
-        Bl.runup = bits_level == 0 ? longest_bits_seg_units() / 2 : longest_bits_seg_units();
-        Bl.max_len = t.max_len;
-        Bl.d_out = d_out;
-        Bl.cap = cap;
-        const size_t n_blk = ((size_t)Bl.n_regions + 63) / 64, state_words = 8 + (size_t)Bl.n_regions + n_blk + 2;
-        // exit / flag / count, a word per region, a word per block of 64 regions, the region counter: zero at the start of a call --
-        // the call's last kernel leaves them so; a memset only for a fresh (or larger) buffer and after a call that failed half way
-        const size_t state_had = d.bits_state.bytes;
-        if ((rc = d.bits_state.ensure(state_words * 8))) return rc;
-        if (d.bits_state.p != d.bits_state_seen || d.bits_state.bytes != state_had) {
-            HIP_TRY(hipMemsetAsync(d.bits_state.p, 0, d.bits_state.bytes, stream));
-            d.bits_state_seen = d.bits_state.p;
-        }
-        if ((rc = d.blockmax.ensure((size_t)Bl.n_regions * 8 + 64))) return rc;
-        if ((rc = d.chainbits.ensure((size_t)Bl.n_regions * longest_bits_region_scratch_bytes() + 64))) return rc;
-        Bl.d_exit = (unsigned long long *)d.bits_state.p;
-        Bl.d_agg = Bl.d_exit + 8;
-        Bl.d_blk = Bl.d_agg + Bl.n_regions;
-        Bl.d_next = (uint32_t *)(Bl.d_blk + n_blk);
-        Bl.d_marks = (uint32_t *)d.chainbits.p;
-        Bl.d_xout = Bl.d_marks + (size_t)Bl.n_regions * (region_units / 32);
-        Bl.d_text = nullptr;
-        if (record_kind == ACGPU_REC_MAP) { // the regions' text bits, parked for the keyword ids (acgpu_longest_bits.hip)
-            if ((rc = d.lenbuf.ensure((size_t)Bl.n_regions * longest_bits_region_text_bytes() + 64))) return rc;
-            Bl.d_text = (uint32_t *)d.lenbuf.p;
-        }
-        Bl.d_pred = (uint32_t *)d.blockmax.p;
-        Bl.d_true = Bl.d_pred + Bl.n_regions;
-        Bl.grid = (int)std::min<uint64_t>((uint64_t)d.n_cu, (Bl.n_regions + 15) / 16);
-        Bl.debug = (uint32_t)(tunables().tile_debug >> 32);
-        unsigned long long *h_slot = tk ? tk->h_count : d.h_counter, *d_slot = nullptr;
-        HIP_TRY(hipHostGetDevicePointer((void **)&d_slot, h_slot, 0));
-        void *const seen = d.bits_state_seen;
-        d.bits_state_seen = nullptr; // (until both kernels are enqueued: an error below leaves the words in an unknown state)
-        // the whole pipeline in two launches: text in, records out; then the seams, the result and the state for the next call.
-        // (Profiled calls take the dispatches' own start / stop timestamps: marker packets between the steps cost more than the
-        // second kernel does.)
-        HIP_TRY(launch_longest_bits(d.T, Bl, d_slot, tk ? reinterpret_cast<acgpu_device_result *>(sh->d_result) : nullptr,
-                                    (unsigned long long *)d.bits_state.p, (uint32_t)state_words, stream, timed ? ev[0] : nullptr,
-                                    timed ? ev[1] : nullptr, timed ? ev[2] : nullptr));
-        d.bits_state_seen = seen;
-        if (tk) {
-            tk->stream = stream;
-            tk->shard = *sh;
-            tk->record_kind = record_kind;
-            tk->d_out = d_out;
-            tk->bits_level = bits_level;
-            tk->done_is_ev2 = timed; // (the finish kernel's own end)
-            if (!timed) HIP_TRY(hipEventRecord(tk->done, stream));
-            tk->scanned = own_len;
-            std::snprintf(tk->kname, sizeof(tk->kname), "k_longest_bits");
-            return ACGPU_OK;
-        }
-        HIP_TRY(hipStreamSynchronize(stream));
+    Bl.d_pred = (uint32_t *)d.blockmax.p;
+    Bl.d_true = Bl.d_pred + Bl.n_regions;
+    Bl.grid = (int)std::min<uint64_t>((uint64_t)d.n_cu, (Bl.n_regions + 15) / 16);
+    Bl.debug = (uint32_t)(tunables().tile_debug >> 32);
+    unsigned long long *d_slot = nullptr;
+    if ((rc = slot_on_device(r, &d_slot))) return rc;
+    void *const seen = d.bits_state_seen;
+    d.bits_state_seen = nullptr; // (until both kernels are enqueued: an error below leaves the words in an unknown state)
+    // the whole pipeline in two launches: text in, records out; then the seams, the result and the state for the next call.
+    // (Profiled calls take the dispatches' own start / stop timestamps: marker packets between the steps cost more than the
+    // second kernel does.)
+    const bool timed = r.profiled;
+    HIP_TRY(launch_longest_bits(d.T, Bl, d_slot, reinterpret_cast<acgpu_device_result *>(sh->d_result),
+                                (unsigned long long *)d.bits_state.p, (uint32_t)state_words, stream, timed ? r.ev[0] : nullptr,
+                                timed ? r.ev[1] : nullptr, timed ? r.ev[2] : nullptr));
+    d.bits_state_seen = seen;
 #ifdef ACGPU_ABLATION
-        if (Bl.debug) {
-            unsigned long long mism = 0;
-            (void)hipMemcpy(&mism, (const char *)d.bits_state.p + 24, 8, hipMemcpyDeviceToHost); // (the finish kernel has zeroed it: kept for builds that skip it)
-            fprintf(stderr, "[k_longest_bits debug %u] segments whose assumed entry was not the exit before them: %llu\n", Bl.debug, mism);
-        }
-#endif
-        if (d.h_counter[1] != 0) // (1: a chain that did not merge inside the run-up; 2: a unit outside the alphabet)
-            return match_longest(a, d, sh, record_kind, d_out, cap, n_out, stream, prof, nullptr, d.h_counter[1] == 1 ? bits_level + 1 : 2);
-        *n_out = d.h_counter[0];
-        sh->chain_exit = (int64_t)d.h_counter[2];
-        if (prof) {
-            HIP_TRY(hipEventElapsedTime(&prof->scan_ms, d.ev[0], d.ev[1]));
-            HIP_TRY(hipEventElapsedTime(&prof->finalize_ms, d.ev[1], d.ev[2]));
-            HIP_TRY(hipEventElapsedTime(&prof->total_ms, d.ev[0], d.ev[2]));
-            prof->scan_units = own_len;
-            prof->n_matches = *n_out;
-            std::snprintf(prof->scan_kernel, sizeof(prof->scan_kernel), "k_longest_bits");
-        }
-        return *n_out > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
-    }
-    // Any other dense dictionary with range classes or small class pages, long texts, Set and Map records: the walks of the chain's own
-    // positions only (k_longest_follow, acgpu_longest_follow.hip) in place of the length array, the synchronisation points and the chain
-    // pass; the bitmaps, counts and first positions it leaves are what the prefix sum and k_longest_emit_ends below read.  It checks its
-    // own result like k_longest_bits and is redone the same way.  Tunable longest_form, bits: 2 = never, 4 = also for short texts.
-    const size_t fol_pages = (!t.range_cls && !t.dfa_pages.empty()) ? t.dfa_pages.size() * 2 : 0;
-    const bool fol_classes = t.dense && ((t.range_cls && t.n_cls == t.cls_span + 1) || fol_pages > 0);
-    const uint32_t fol_hot = fol_classes ? longest_follow_hot_rows(t.n_cls, t.n_states, (uint32_t)fol_pages) : 0;
-    if (bits_level < d.fol_level && !bits_form) bits_level = d.fol_level; // (what earlier calls on this pool have learnt about its texts)
-    // (Not where the walk pipeline has its root table -- dictionaries over up to four letters whose first 14 or 7 units one lookup
-    // decides: config 4's dictionary with Map records 3.71 against 5.79 ms per 2^29 units, tools/longest_shapes.py.  Tunable
-    // longest_form bit 8: there too, for A/B.)
-    const bool follow_form = bits_level < 2 && fol_hot > 0 && !(lform & 2) && (own_len >= (1ull << 20) || (lform & 4)) && tunables().force_kernel == 0 &&
-                             (t.root_b == 0 || (lform & 8));
-    if (follow_form) {
-        int rc;
-        LongestFollowLaunch F{};
-        F.d_hay = sh->d_hay;
-        F.n_units = (uint32_t)sh->n_units;
-        F.own_end = (uint32_t)sh->own_end;
-        F.entry = (uint32_t)entry;
-        F.g0 = (uint32_t)entry & ~31u;
-        // a lane walks a segment of 1024 positions behind a run-up.  (Segments of 512 for texts that leave half the chip's lanes
-        // without one were measured: 4.95 against 3.30 ms per 2^28 units of the README word list -- the kernel is bound by the
-        // number of gathers, and a run-up of a whole segment is a third more of them.)  Tunable region_units (64 .. 1024): the first
-        // try's run-up, for A/B.
-        const uint32_t seg_units = longest_follow_seg_units();
-        F.seg_log2 = 10;
-        const uint32_t region_units = 64 * seg_units;
-        F.n_regions = (uint32_t)((sh->own_end - F.g0 + region_units - 1) / region_units);
-        // The first try's run-up is 128 positions: on a text with separators every chain lands on each of them (no keyword goes
-        // across), so chains merge within a word, and the run-up is a fifth of the gathers at 512 (measured on the README word
-        // list: 3.27 ms per 2^28 units at 512, 2.85 at 256, 2.65 at 128).  A text on which that fails -- the kernel notices --
-        // is redone with a whole segment, and this pool remembers it (d.fol_level): the next call starts there, or, if chains
-        // do not merge within 1024 positions either, with the walk pipeline.
-        const int64_t ru = tunables().region_units;
-        F.runup = bits_level == 0 ? (ru >= 64 && ru <= 1024 ? (uint32_t)ru : 128u) : seg_units;
-        F.tile_log2 = 2; // (emit tiles of 4096 positions)
-        F.hot_rows = fol_hot;
-        const uint32_t n_tiles = (F.n_regions * (region_units / seg_units)) >> F.tile_log2;
-        if ((rc = d.counter.ensure(64))) return rc;
-        if ((rc = d.chunk_counts.ensure((size_t)n_tiles * 4))) return rc;
-        if ((rc = d.offsets.ensure((size_t)n_tiles * 8))) return rc;
-        if ((rc = d.scan_tmp.ensure(((size_t)n_tiles / 2048 + 2) * 8))) return rc;
-        if ((rc = d.chain.ensure((size_t)n_tiles * 4 + 64))) return rc;
-        if ((rc = d.blockmax.ensure((size_t)F.n_regions * 8 + 64))) return rc;
-        const size_t bit_bytes = ((size_t)sh->n_units / 128 + 2) * 16;
-        if ((rc = d.chainbits.ensure(bit_bytes * 2))) return rc;
-        F.d_bits = (uint32_t *)d.chainbits.p;
-        F.d_ebits = F.d_bits + bit_bytes / 4;
-        F.d_state = nullptr;
-        if (record_kind == ACGPU_REC_MAP) {
-            if ((rc = d.statebuf.ensure((size_t)sh->n_units * 4 + 64))) return rc;
-            F.d_state = (uint32_t *)d.statebuf.p;
-        }
-        F.d_sync = (uint32_t *)d.chain.p;
-        F.d_counts = (uint32_t *)d.chunk_counts.p;
-        F.d_exit = (unsigned long long *)d.counter.p;
-        F.d_pred = (uint32_t *)d.blockmax.p;
-        F.d_true = F.d_pred + F.n_regions;
-        F.grid = (int)std::min<uint64_t>(2ull * d.n_cu, (F.n_regions + 15) / 16);
-        HIP_TRY(hipMemsetAsync(d.counter.p, 0, 64, stream));
-        d.cclean[0] = false; // (match_all's first set of slot counters lives here)
-        { // the end bits are merged with atomicOr: zeros from the first word the chain can touch to where its last match can end
-            const size_t first = F.g0 >> 5, last = std::min<size_t>(bit_bytes / 4, (((size_t)sh->own_end + t.max_len) >> 5) + 2);
-            if (last > first) HIP_TRY(hipMemsetAsync(F.d_ebits + first, 0, (last - first) * 4, stream));
-        }
-        if (timed) HIP_TRY(hipEventRecord(ev[0], stream));
-        HIP_TRY(launch_longest_follow(d.T, F, t.range_cls, record_kind == ACGPU_REC_MAP, stream));
-        if (timed) HIP_TRY(hipEventRecord(ev[1], stream));
-        LongestChainLaunch Cn{};
-        Cn.d_state = F.d_state;
-        Cn.d_out_id = d.T.term_id;
-        Cn.len_bytes = 1;
-        Cn.own_begin = (uint32_t)sh->own_begin;
-        Cn.own_end = (uint32_t)sh->own_end;
-        Cn.entry = (uint32_t)entry;
-        Cn.tile_units = seg_units << F.tile_log2;
-        Cn.n_tiles = n_tiles;
-        Cn.max_len = t.max_len;
-        Cn.d_counts = F.d_counts;
-        Cn.d_offsets = (const uint64_t *)d.offsets.p;
-        Cn.d_out = d_out;
-        Cn.cap = cap;
-        Cn.record_kind = record_kind;
-        Cn.d_exit = F.d_exit;
-        Cn.len_units = (uint32_t)sh->n_units;
-        Cn.d_bits = F.d_bits;
-        Cn.d_ebits = F.d_ebits;
-        HIP_TRY(launch_exclusive_scan(Cn.d_counts, Cn.n_tiles, (uint64_t *)d.offsets.p, (uint64_t *)d.scan_tmp.p, stream));
-        HIP_TRY(launch_longest_emit(Cn, F.d_sync, stream));
-        if (timed) HIP_TRY(hipEventRecord(ev[2], stream));
-        unsigned long long *h_slot = tk ? tk->h_count : d.h_counter, *d_slot = nullptr;
-        HIP_TRY(hipHostGetDevicePointer((void **)&d_slot, h_slot, 0));
-        HIP_TRY(launch_publish_result((const unsigned long long *)d.scan_tmp.p + scan_tiles_for(Cn.n_tiles), (const unsigned long long *)d.counter.p,
-                                      d_slot, tk ? reinterpret_cast<acgpu_device_result *>(sh->d_result) : nullptr, stream));
-        if (tk) {
-            tk->stream = stream;
-            tk->shard = *sh;
-            tk->record_kind = record_kind;
-            tk->d_out = d_out;
-            tk->bits_level = bits_level;
-            HIP_TRY(hipEventRecord(tk->done, stream));
-            tk->scanned = own_len;
-            std::snprintf(tk->kname, sizeof(tk->kname), "k_longest_follow");
-            return ACGPU_OK;
-        }
+    if (Bl.debug && !r.done) {
         HIP_TRY(hipStreamSynchronize(stream));
-        if (d.h_counter[1] != 0) { // (a chain that did not merge inside the run-up)
-            d.fol_level = std::max(d.fol_level, bits_level + 1);
-            return match_longest(a, d, sh, record_kind, d_out, cap, n_out, stream, prof, nullptr, bits_level + 1);
-        }
-        *n_out = d.h_counter[0];
-        sh->chain_exit = (int64_t)d.h_counter[2];
-        if (prof) {
-            HIP_TRY(hipEventElapsedTime(&prof->scan_ms, d.ev[0], d.ev[1]));
-            HIP_TRY(hipEventElapsedTime(&prof->finalize_ms, d.ev[1], d.ev[2]));
-            HIP_TRY(hipEventElapsedTime(&prof->total_ms, d.ev[0], d.ev[2]));
-            prof->scan_units = own_len;
-            prof->n_matches = *n_out;
-            std::snprintf(prof->scan_kernel, sizeof(prof->scan_kernel), "k_longest_follow");
-        }
-        return *n_out > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
+        unsigned long long mism = 0;
+        (void)hipMemcpy(&mism, (const char *)d.bits_state.p + 24, 8, hipMemcpyDeviceToHost); // (the finish kernel has zeroed it: kept for builds that skip it)
+        fprintf(stderr, "[k_longest_bits debug %u] segments whose assumed entry was not the exit before them: %llu\n", Bl.debug, mism);
     }
+#endif
+    return close_call(r, CallForm::LongestBits, "k_longest_bits", sh->own_end - sh->own_begin, /*done_is_ev2=*/timed); // (the finish kernel's own end)
+}
+
+// Any other dense dictionary with range classes or small class pages, long texts, Set and Map records: the walks of the chain's own
+// positions only (k_longest_follow, acgpu_longest_follow.hip) in place of the length array, the synchronisation points and the chain
+// pass; the bitmaps, counts and first positions it leaves are what the prefix sum and k_longest_emit_ends below read.  It checks its
+// own result like k_longest_bits and is redone the same way.
+int enqueue_longest_follow(acgpu_automaton *a, DeviceState &d, CallRecord &r, uint64_t entry, int bits_level, uint32_t fol_hot) {
+    const HostTables &t = a->t;
+    const acgpu_shard *sh = &r.shard;
+    const hipStream_t stream = r.stream;
+    int rc;
+    LongestFollowLaunch F{};
+    F.d_hay = sh->d_hay;
+    F.n_units = (uint32_t)sh->n_units;
+    F.own_end = (uint32_t)sh->own_end;
+    F.entry = (uint32_t)entry;
+    F.g0 = (uint32_t)entry & ~31u;
+    // a lane walks a segment of 1024 positions behind a run-up.  (Segments of 512 for texts that leave half the chip's lanes
+    // without one were measured: 4.95 against 3.30 ms per 2^28 units of the README word list -- the kernel is bound by the
+    // number of gathers, and a run-up of a whole segment is a third more of them.)  Tunable region_units (64 .. 1024): the first
+    // try's run-up, for A/B.
+    const uint32_t seg_units = longest_follow_seg_units();
+    F.seg_log2 = 10;
+    const uint32_t region_units = 64 * seg_units;
+    F.n_regions = (uint32_t)((sh->own_end - F.g0 + region_units - 1) / region_units);
+    // The first try's run-up is 128 positions: on a text with separators every chain lands on each of them (no keyword goes
+    // across), so chains merge within a word, and the run-up is a fifth of the gathers at 512 (measured on the README word
+    // list: 3.27 ms per 2^28 units at 512, 2.85 at 256, 2.65 at 128).  A text on which that fails -- the kernel notices --
+    // is redone with a whole segment, and this pool remembers it (d.fol_level): the next call starts there, or, if chains
+    // do not merge within 1024 positions either, with the walk pipeline.
+    const int64_t ru = tunables().region_units;
+    F.runup = bits_level == 0 ? (ru >= 64 && ru <= 1024 ? (uint32_t)ru : 128u) : seg_units;
+    F.tile_log2 = 2; // (emit tiles of 4096 positions)
+    F.hot_rows = fol_hot;
+    const uint32_t n_tiles = (F.n_regions * (region_units / seg_units)) >> F.tile_log2;
+    if ((rc = d.counter.ensure(64))) return rc;
+    if ((rc = d.chunk_counts.ensure((size_t)n_tiles * 4))) return rc;
+    if ((rc = d.offsets.ensure((size_t)n_tiles * 8))) return rc;
+    if ((rc = d.scan_tmp.ensure(((size_t)n_tiles / 2048 + 2) * 8))) return rc;
+    if ((rc = d.chain.ensure((size_t)n_tiles * 4 + 64))) return rc;
+    if ((rc = d.blockmax.ensure((size_t)F.n_regions * 8 + 64))) return rc;
+    const size_t bit_bytes = ((size_t)sh->n_units / 128 + 2) * 16;
+    if ((rc = d.chainbits.ensure(bit_bytes * 2))) return rc;
+    F.d_bits = (uint32_t *)d.chainbits.p;
+    F.d_ebits = F.d_bits + bit_bytes / 4;
+    F.d_state = nullptr;
+    if (r.record_kind == ACGPU_REC_MAP) {
+        if ((rc = d.statebuf.ensure((size_t)sh->n_units * 4 + 64))) return rc;
+        F.d_state = (uint32_t *)d.statebuf.p;
+    }
+    F.d_sync = (uint32_t *)d.chain.p;
+    F.d_counts = (uint32_t *)d.chunk_counts.p;
+    F.d_exit = (unsigned long long *)d.counter.p;
+    F.d_pred = (uint32_t *)d.blockmax.p;
+    F.d_true = F.d_pred + F.n_regions;
+    F.grid = (int)std::min<uint64_t>(2ull * d.n_cu, (F.n_regions + 15) / 16);
+    HIP_TRY(hipMemsetAsync(d.counter.p, 0, 64, stream));
+    d.cclean[0] = false; // (enqueue_all's first set of slot counters lives here)
+    { // the end bits are merged with atomicOr: zeros from the first word the chain can touch to where its last match can end
+        const size_t first = F.g0 >> 5, last = std::min<size_t>(bit_bytes / 4, (((size_t)sh->own_end + t.max_len) >> 5) + 2);
+        if (last > first) HIP_TRY(hipMemsetAsync(F.d_ebits + first, 0, (last - first) * 4, stream));
+    }
+    if (r.profiled) HIP_TRY(hipEventRecord(r.ev[0], stream));
+    HIP_TRY(launch_longest_follow(d.T, F, t.range_cls, r.record_kind == ACGPU_REC_MAP, stream));
+    if (r.profiled) HIP_TRY(hipEventRecord(r.ev[1], stream));
+    LongestChainLaunch Cn{};
+    Cn.d_state = F.d_state;
+    Cn.d_out_id = d.T.term_id;
+    Cn.len_bytes = 1;
+    Cn.own_begin = (uint32_t)sh->own_begin;
+    Cn.own_end = (uint32_t)sh->own_end;
+    Cn.entry = (uint32_t)entry;
+    Cn.tile_units = seg_units << F.tile_log2;
+    Cn.n_tiles = n_tiles;
+    Cn.max_len = t.max_len;
+    Cn.d_counts = F.d_counts;
+    Cn.d_offsets = (const uint64_t *)d.offsets.p;
+    Cn.d_out = r.d_out;
+    Cn.cap = r.cap;
+    Cn.record_kind = r.record_kind;
+    Cn.d_exit = F.d_exit;
+    Cn.len_units = (uint32_t)sh->n_units;
+    Cn.d_bits = F.d_bits;
+    Cn.d_ebits = F.d_ebits;
+    HIP_TRY(launch_exclusive_scan(Cn.d_counts, Cn.n_tiles, (uint64_t *)d.offsets.p, (uint64_t *)d.scan_tmp.p, stream));
+    HIP_TRY(launch_longest_emit(Cn, F.d_sync, stream));
+    if (r.profiled) HIP_TRY(hipEventRecord(r.ev[2], stream));
+    unsigned long long *d_slot = nullptr;
+    if ((rc = slot_on_device(r, &d_slot))) return rc;
+    HIP_TRY(launch_publish_result((const unsigned long long *)d.scan_tmp.p + scan_tiles_for(Cn.n_tiles), (const unsigned long long *)d.counter.p,
+                                  d_slot, reinterpret_cast<acgpu_device_result *>(sh->d_result), stream));
+    return close_call(r, CallForm::LongestFollow, "k_longest_follow", sh->own_end - sh->own_begin);
+}
+
+// The walk pipeline: reverse scan -> chain count -> prefix sum -> chain write.
+int enqueue_longest_walk(acgpu_automaton *a, DeviceState &d, CallRecord &r, uint64_t entry) {
+    const HostTables &t = a->t;
+    const acgpu_shard *sh = &r.shard;
+    const hipStream_t stream = r.stream;
+    const int record_kind = r.record_kind;
+    const uint64_t own_len = sh->own_end - sh->own_begin;
     LongestScanLaunch S{};
     S.block = 1024;
     // two workgroups per CU share the LDS (hot trie rows: at most 72 KB each); a short haystack gets fewer (every
@@ -1328,14 +1300,14 @@ int match_longest(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int recor
     Cn.max_len = t.max_len;
     Cn.d_counts = (uint32_t *)d.chunk_counts.p;
     Cn.d_offsets = (const uint64_t *)d.offsets.p;
-    Cn.d_out = d_out;
-    Cn.cap = cap;
+    Cn.d_out = r.d_out;
+    Cn.cap = r.cap;
     Cn.record_kind = record_kind;
     Cn.d_exit = (unsigned long long *)d.counter.p;
 
     HIP_TRY(hipMemsetAsync(d.counter.p, 0, 64, stream));
-    d.cclean[0] = false; // (match_all's first set of slot counters lives here)
-    if (timed) HIP_TRY(hipEventRecord(ev[0], stream));
+    d.cclean[0] = false; // (enqueue_all's first set of slot counters lives here)
+    if (r.profiled) HIP_TRY(hipEventRecord(r.ev[0], stream));
     const char *kname = "";
     if (root_form) {
         LongestScanLaunch Sb = S;
@@ -1347,7 +1319,7 @@ int match_longest(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int recor
     } else {
         HIP_TRY(launch_longest_scan(d.T, S, stream, &kname));
     }
-    if (timed) HIP_TRY(hipEventRecord(ev[1], stream));
+    if (r.profiled) HIP_TRY(hipEventRecord(r.ev[1], stream));
     if ((rc = d.chain.ensure((size_t)Cn.n_tiles * 4 + 64))) return rc;
     uint32_t *d_sync = (uint32_t *)d.chain.p;
     // Chain: synchronisation points, a count pass that also marks the chain's matches in a bitmap, prefix sum, and the
@@ -1375,35 +1347,113 @@ int match_longest(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int recor
     if (!serial_write) HIP_TRY(launch_longest_emit(Cn, d_sync, stream));
     else if (chain_lds) HIP_TRY(launch_longest_chain_lds(Cn, d_sync, /*write_pass=*/true, stream));
     else HIP_TRY(launch_longest_chain(Cn, d_sync, /*write_pass=*/true, stream));
-    if (timed) HIP_TRY(hipEventRecord(ev[2], stream));
+    if (r.profiled) HIP_TRY(hipEventRecord(r.ev[2], stream));
     // {count, 0, exit} into the call's pinned host slot (and the device result) by the pipeline's last kernel
-    unsigned long long *h_slot = tk ? tk->h_count : d.h_counter, *d_slot = nullptr;
-    HIP_TRY(hipHostGetDevicePointer((void **)&d_slot, h_slot, 0));
+    unsigned long long *d_slot = nullptr;
+    if ((rc = slot_on_device(r, &d_slot))) return rc;
     HIP_TRY(launch_publish_result((const unsigned long long *)d.scan_tmp.p + scan_tiles_for(Cn.n_tiles), (const unsigned long long *)d.counter.p,
-                                  d_slot, tk ? reinterpret_cast<acgpu_device_result *>(sh->d_result) : nullptr, stream));
-    if (tk) {
-        tk->stream = stream;
-        HIP_TRY(hipEventRecord(tk->done, stream));
-        tk->scanned = own_len;
-        std::snprintf(tk->kname, sizeof(tk->kname), "%s", kname);
-        return ACGPU_OK;
+                                  d_slot, reinterpret_cast<acgpu_device_result *>(sh->d_result), stream));
+    return close_call(r, CallForm::LongestWalk, kname, own_len);
+}
+
+// LONGEST-mode pipeline on one shard: the checks, the chain's preset exit, the empty call; then the form of this run-up level
+// (bits_level 0: short, 1: a whole segment, 2: the walk pipeline).  The sparse form of a selective suffix filter runs before
+// this, synchronously (match_shard).  Tunable longest_form, bits: 1 = never k_longest_bits, 2 = never k_longest_follow,
+// 4 = also for short texts (tests), 8 = k_longest_follow where the walk pipeline has its root table too.
+int enqueue_longest(acgpu_automaton *a, DeviceState &d, CallRecord &r, int bits_level) {
+    const HostTables &t = a->t;
+    int rc;
+    if ((rc = check_longest_shard(t, &r.shard))) return rc;
+    r.user_shard->chain_exit = r.shard.chain_exit;
+    const acgpu_shard *sh = &r.shard;
+    const uint64_t entry = (uint64_t)sh->chain_entry;
+    if (entry >= sh->own_end || t.n_states <= 1) return enqueue_empty(r, sh->chain_exit);
+    const uint64_t own_len = sh->own_end - sh->own_begin;
+    const int64_t lform = tunables().longest_form;
+    const bool bits_form = bits_level < 2 && (r.record_kind == ACGPU_REC_SET || d.T.bits_idkeys != nullptr) && d.T.bits_rk != 0 && !(lform & 1) &&
+                           (own_len >= (1ull << 21) || (lform & 4)) && tunables().force_kernel == 0;
+    if (bits_form) {
+        r.level = bits_level;
+        return enqueue_longest_bits(a, d, r, entry, bits_level);
     }
-    HIP_TRY(hipStreamSynchronize(stream));
-    *n_out = d.h_counter[0];
-    sh->chain_exit = (int64_t)d.h_counter[2];
-    if (prof) {
-        HIP_TRY(hipEventElapsedTime(&prof->scan_ms, d.ev[0], d.ev[1]));
-        HIP_TRY(hipEventElapsedTime(&prof->finalize_ms, d.ev[1], d.ev[2]));
-        HIP_TRY(hipEventElapsedTime(&prof->total_ms, d.ev[0], d.ev[2]));
-        prof->scan_units = own_len;
+    const size_t fol_pages = (!t.range_cls && !t.dfa_pages.empty()) ? t.dfa_pages.size() * 2 : 0;
+    const bool fol_classes = t.dense && ((t.range_cls && t.n_cls == t.cls_span + 1) || fol_pages > 0);
+    const uint32_t fol_hot = fol_classes ? longest_follow_hot_rows(t.n_cls, t.n_states, (uint32_t)fol_pages) : 0;
+    if (bits_level < d.fol_level) bits_level = d.fol_level; // (what earlier calls on this pool have learnt about its texts)
+    r.level = bits_level;
+    // (Not where the walk pipeline has its root table -- dictionaries over up to four letters whose first 14 or 7 units one lookup
+    // decides: config 4's dictionary with Map records 3.71 against 5.79 ms per 2^29 units, tools/longest_shapes.py.  Tunable
+    // longest_form bit 8: there too, for A/B.)
+    const bool follow_form = bits_level < 2 && fol_hot > 0 && !(lform & 2) && (own_len >= (1ull << 20) || (lform & 4)) && tunables().force_kernel == 0 &&
+                             (t.root_b == 0 || (lform & 8));
+    if (follow_form) return enqueue_longest_follow(a, d, r, entry, bits_level, fol_hot);
+    return enqueue_longest_walk(a, d, r, entry);
+}
+
+// The level a call has to be redone at, or -1.  ALL: an overflow word raised by the scan (a candidate slice of the split form
+// or a scratch slice was too small) -> 1, the fused kernel with one scratch slice.  LONGEST: the bail flag of k_longest_bits /
+// k_longest_follow (1: a chain that did not merge inside the run-up, 2: a unit outside the alphabet) -> the next run-up level,
+// or 2, the walk pipeline.  A redo is always at a higher level, and the forms of the last levels never ask for one.
+int redo_level(const CallRecord &r) {
+    const unsigned long long flag = r.h_slot[1];
+    if (r.form == CallForm::Ordered || r.form == CallForm::FusedTail) return r.level == 0 && (uint32_t)flag != 0 ? 1 : -1;
+    if (r.form == CallForm::LongestBits || r.form == CallForm::LongestFollow) return flag == 0 ? -1 : flag == 1 ? r.level + 1 : 2;
+    return -1;
+}
+
+// Completes a call enqueued into *r: the wait (a synchronous call's; end_ticket waits for a ticket's outside the pool's lock),
+// the redo if the kernels ask for one -- a synchronous call on the pool's own record --, then the chain exit, what the pool
+// learns (the ALL density), the profile and the overflow status.  The caller holds d.mu.
+int collect(acgpu_automaton *a, DeviceState &d, CallRecord *r, uint64_t *n_out, acgpu_profile *prof, bool *redone) {
+    for (;;) {
+        if (!r->done && r->form != CallForm::Complete) HIP_TRY(hipStreamSynchronize(r->stream));
+        const int level = redo_level(*r);
+        if (level < 0) break;
+        const bool longest = r->form != CallForm::Ordered && r->form != CallForm::FusedTail;
+        if (r->form == CallForm::LongestFollow) d.fol_level = std::max(d.fol_level, r->level + 1); // (the pool's later calls start there)
+        // (the redo shares the scratch with the tickets still in flight: same stream, so stream order keeps them apart)
+        acgpu_shard sh = r->shard;
+        if (longest) sh.d_result = nullptr; // (a Longest redo leaves the device result to the first attempt)
+        open_call(d.call, d.ev, nullptr, d.h_counter, sh, r->user_shard, r->record_kind, r->d_out, r->cap, r->stream, prof != nullptr,
+                  r->folded);
+        if (redone) *redone = true;
+        const int rc = longest ? enqueue_longest(a, d, d.call, level) : enqueue_all(a, d, d.call, level);
+        if (rc) return rc;
+        r = &d.call;
+    }
+    *n_out = r->h_slot[0];
+    if (r->form == CallForm::LongestBits || r->form == CallForm::LongestFollow || r->form == CallForm::LongestWalk)
+        r->user_shard->chain_exit = (int64_t)r->h_slot[2];
+    else if (r->form != CallForm::Complete && a->t.mode != ACGPU_MODE_WHOLEWORD) // (what the states form's choice goes by)
+        d.all_density = (double)*n_out / (double)(r->shard.own_end - r->shard.own_begin);
+    if (prof && r->form != CallForm::Complete) {
+        std::memset(prof, 0, sizeof(*prof));
+        if (r->profiled && r->one_kernel) {
+            HIP_TRY(hipEventElapsedTime(&prof->scan_ms, r->ev[0], r->ev[2]));
+            prof->total_ms = prof->scan_ms;
+        } else if (r->profiled) {
+            HIP_TRY(hipEventElapsedTime(&prof->scan_ms, r->ev[0], r->ev[1]));
+            HIP_TRY(hipEventElapsedTime(&prof->finalize_ms, r->ev[1], r->ev[2]));
+            HIP_TRY(hipEventElapsedTime(&prof->total_ms, r->ev[0], r->ev[2]));
+        }
+        prof->scan_units = r->scanned;
         prof->n_matches = *n_out;
-        std::snprintf(prof->scan_kernel, sizeof(prof->scan_kernel), "%s", kname);
+        std::snprintf(prof->scan_kernel, sizeof(prof->scan_kernel), "%s", r->kname);
     }
-    return *n_out > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
+    return *n_out > r->cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
+}
+
+// A synchronous call of an enqueued pipeline: into the pool's own record (events d.ev, slot d.h_counter), then collect().
+int run_sync(EnqueueFn enqueue, acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_kind, void *d_out, uint64_t cap,
+             uint64_t *n_out, hipStream_t stream, acgpu_profile *prof, bool folded) {
+    open_call(d.call, d.ev, nullptr, d.h_counter, *sh, sh, record_kind, d_out, cap, stream, prof != nullptr, folded);
+    if (prof) std::memset(prof, 0, sizeof(*prof));
+    const int rc = enqueue(a, d, d.call, 0);
+    return rc ? rc : collect(a, d, &d.call, n_out, prof, nullptr);
 }
 
 // WHOLEWORD with a word-character table that is not fold-consistent: the reference's mixed folded/raw lookups make
-// token boundaries history dependent -- whole text, one lane (k_ww_sequential).  (Fold-consistent tables: match_all.)
+// token boundaries history dependent -- whole text, one lane (k_ww_sequential).  (Fold-consistent tables: enqueue_all.)
 int match_wholeword_sequential(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_kind, void *d_out, uint64_t cap,
                                uint64_t *n_out, hipStream_t stream, acgpu_profile *prof) {
     const uint64_t own_len = sh->own_end - sh->own_begin;
@@ -1415,7 +1465,7 @@ int match_wholeword_sequential(acgpu_automaton *a, DeviceState &d, acgpu_shard *
     int rc;
     if ((rc = d.counter.ensure(64))) return rc;
     HIP_TRY(hipMemsetAsync(d.counter.p, 0, 64, stream));
-    d.cclean[0] = false; // (match_all's first set of slot counters lives here)
+    d.cclean[0] = false; // (enqueue_all's first set of slot counters lives here)
     if (!sh->text_begin || !sh->text_end || sh->own_begin != 0 || sh->own_end != sh->n_units) return ACGPU_E_UNSUPPORTED;
     if (prof) HIP_TRY(hipEventRecord(d.ev[0], stream));
     HIP_TRY(launch_ww_sequential(d.T, sh->d_hay, (uint32_t)sh->n_units, d_out, cap, record_kind,
@@ -1447,7 +1497,7 @@ int match_shortest(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int reco
     acgpu_profile all_prof;
     for (;;) { // all matches (end ascending, longest first) with keyword ids; retried once with the exact capacity
         if ((rc = d.short_recs.ensure(acap * ACGPU_REC_MAP + 16))) return rc;
-        rc = match_all(a, d, sh, ACGPU_REC_MAP, d.short_recs.p, acap, &m, stream, prof ? &all_prof : nullptr);
+        rc = run_sync(enqueue_all, a, d, sh, ACGPU_REC_MAP, d.short_recs.p, acap, &m, stream, prof ? &all_prof : nullptr);
         if (rc == ACGPU_E_OVERFLOW) {
             acap = m;
             continue;
@@ -1477,7 +1527,7 @@ int match_shortest(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int reco
     HIP_TRY(launch_shortest_emit((const int32_t *)d.short_recs.p, M, (const uint32_t *)d.short_mark.p,
                                  (const uint64_t *)d.offsets.p, d_total, record_kind, d_out, cap, entry,
                                  (unsigned long long *)d.counter.p, stream));
-    d.cclean[0] = false; // (the exit position went where match_all's first set of slot counters lives)
+    d.cclean[0] = false; // (the exit position went where enqueue_all's first set of slot counters lives)
     if (prof) HIP_TRY(hipEventRecord(d.ev[1], stream));
     HIP_TRY(hipMemcpyAsync(d.h_counter, d_total, 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipMemcpyAsync(d.h_counter + 1, d.counter.p, 8, hipMemcpyDeviceToHost, stream));
@@ -1508,7 +1558,7 @@ int match_wwlongest_sequential(acgpu_automaton *a, DeviceState &d, acgpu_shard *
     if (!sh->text_begin || !sh->text_end || sh->own_begin != 0 || sh->own_end != sh->n_units) return ACGPU_E_UNSUPPORTED;
     if (n == 0 || t.n_states <= 1) return ACGPU_OK;
     if ((rc = d.counter.ensure(64))) return rc;
-    d.cclean[0] = false; // (match_all's first set of slot counters lives here)
+    d.cclean[0] = false; // (enqueue_all's first set of slot counters lives here)
     if (prof) HIP_TRY(hipEventRecord(d.ev[0], stream));
     HIP_TRY(launch_wwl_sequential(d.T, sh->d_hay, n, d_out, cap, record_kind, (unsigned long long *)d.counter.p, stream));
     if (prof) HIP_TRY(hipEventRecord(d.ev[1], stream));
@@ -1549,7 +1599,7 @@ int match_wwlongest(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int rec
     if ((rc = d.offsets.ensure((size_t)n_tiles * 8))) return rc;
     if ((rc = d.scan_tmp.ensure(((size_t)n_tiles / 2048 + 2) * 8))) return rc;
     if ((rc = d.counter.ensure(64))) return rc;
-    d.cclean[0] = false; // (match_all's first set of slot counters lives here)
+    d.cclean[0] = false; // (enqueue_all's first set of slot counters lives here)
     if (prof) HIP_TRY(hipEventRecord(d.ev[0], stream));
     HIP_TRY(launch_wwl_starts(T, sh->d_hay, n, d.n_cu, false, (uint32_t *)d.chunk_counts.p, nullptr, nullptr, sh->text_begin, d.start_behind, stream));
     HIP_TRY(launch_exclusive_scan((const uint32_t *)d.chunk_counts.p, n_tiles, (uint64_t *)d.offsets.p, (uint64_t *)d.scan_tmp.p,
@@ -1633,34 +1683,45 @@ int device_for_call(acgpu_automaton *a, DeviceState **d, int lane) {
     return ensure_device(a, d, lane);
 }
 
+// the checks of match_shard and begin_shard (include/acgpu.h), after the call's view of the tunables is refreshed
+int check_shard(acgpu_automaton *a, DeviceState &d, const acgpu_shard *sh, int record_kind, const void *d_out, uint64_t cap,
+                hipStream_t stream) {
+    refresh_call_state(a, d);
+    if (record_kind != ACGPU_REC_SET && record_kind != ACGPU_REC_MAP) return ACGPU_E_INVALID;
+    if (sh->n_units >= (1ull << 31) || sh->own_begin > sh->own_end || sh->own_end > sh->n_units) return ACGPU_E_INVALID;
+    if (sh->n_units && (!sh->d_hay || ((uintptr_t)sh->d_hay & 15))) return ACGPU_E_INVALID;
+    if (cap && (!d_out || ((uintptr_t)d_out & 3))) return ACGPU_E_INVALID;
+    if (sh->d_result && ((uintptr_t)sh->d_result & 15)) return ACGPU_E_INVALID;
+    if (d.inflight > 0 && stream != d.inflight_stream) return ACGPU_E_INVALID; // stream rule (include/acgpu.h)
+    return ACGPU_OK;
+}
+
 // validates a shard and runs the pipeline of the automaton's family; caller holds d.mu.
 // readable: the call stands for match(Readable, ...) (acgpu_stream_feed) -- the word matchers' Readable loops fold in every
 // lookup where their String loops mix folded and raw ones, which only matters for tables that are not fold-consistent.
 int match_shard(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_kind, void *d_out, uint64_t cap,
                 uint64_t *n_out, hipStream_t stream, acgpu_profile *prof, bool readable) {
-    refresh_call_state(a, d);
-    if (record_kind != ACGPU_REC_SET && record_kind != ACGPU_REC_MAP) return ACGPU_E_INVALID;
-    if (sh->n_units >= (1ull << 31)) return ACGPU_E_INVALID;
-    if (sh->own_begin > sh->own_end || sh->own_end > sh->n_units) return ACGPU_E_INVALID;
-    if (sh->n_units && (!sh->d_hay || ((uintptr_t)sh->d_hay & 15))) return ACGPU_E_INVALID;
-    if (cap && (!d_out || ((uintptr_t)d_out & 3))) return ACGPU_E_INVALID;
-    if (sh->d_result && ((uintptr_t)sh->d_result & 15)) return ACGPU_E_INVALID;
-    if (d.inflight > 0 && stream != d.inflight_stream) return ACGPU_E_INVALID; // stream rule (include/acgpu.h)
+    int rc;
+    if ((rc = check_shard(a, d, sh, record_kind, d_out, cap, stream))) return rc;
     *n_out = 0;
+    if (prof) std::memset(prof, 0, sizeof(*prof));
     const HostTables &t = a->t;
     if (t.mode == ACGPU_MODE_ALL || (t.mode == ACGPU_MODE_WHOLEWORD && t.fold_consistent))
-        return match_all(a, d, sh, record_kind, d_out, cap, n_out, stream, prof);
-    if (t.mode == ACGPU_MODE_WHOLEWORD && readable && t.fold_clean) { // the Readable loop: an ordinary scan over w' = word o lower
-        const DevTables Tf = folded_tables(d);
-        return match_all(a, d, sh, record_kind, d_out, cap, n_out, stream, prof, nullptr, false, &Tf);
-    }
+        return run_sync(enqueue_all, a, d, sh, record_kind, d_out, cap, n_out, stream, prof);
+    if (t.mode == ACGPU_MODE_WHOLEWORD && readable && t.fold_clean) // the Readable loop: an ordinary scan over w' = word o lower
+        return run_sync(enqueue_all, a, d, sh, record_kind, d_out, cap, n_out, stream, prof, /*folded=*/true);
     // the other families end with their count on the host (and some run the ALL pipeline inside): the device copy of the
     // result is written behind the pipeline
     acgpu_device_result *d_res = reinterpret_cast<acgpu_device_result *>(sh->d_result);
     sh->d_result = nullptr;
-    int rc;
     switch (t.mode) {
-    case ACGPU_MODE_LONGEST: rc = match_longest(a, d, sh, record_kind, d_out, cap, n_out, stream, prof); break;
+    case ACGPU_MODE_LONGEST:
+        // a selective suffix filter: a selection over all matches, unless the text turns out to be dense in them
+        rc = ACGPU_E_UNSUPPORTED;
+        if (filter_is_selective(t) && tunables().force_kernel != 1)
+            rc = match_longest_sparse(a, d, sh, record_kind, d_out, cap, n_out, stream, prof);
+        if (rc == ACGPU_E_UNSUPPORTED) rc = run_sync(enqueue_longest, a, d, sh, record_kind, d_out, cap, n_out, stream, prof);
+        break;
     case ACGPU_MODE_WHOLEWORD:
         if (readable) { // folded keywords with non-word units: the WholeWordLongest walk without fail matches, unit by unit
             DevTables Tf = folded_tables(d);
@@ -1687,59 +1748,40 @@ int match_shard(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_
     return rc;
 }
 
-// acgpu_match_device_begin on a given scratch pool (the caller holds dd.mu and has made dd's device current)
-int begin_shard(acgpu_automaton *a, DeviceState &dd, acgpu_shard *sh, int record_kind, void *d_out, uint64_t cap, hipStream_t stream,
+// acgpu_match_device_begin on a given scratch pool (the caller holds d.mu and has made d's device current)
+int begin_shard(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_kind, void *d_out, uint64_t cap, hipStream_t stream,
                 int want_profile, acgpu_ticket **ticket) {
     *ticket = nullptr;
     const HostTables &t = a->t;
-    DeviceState *d = &dd;
-    refresh_call_state(a, dd);
     int rc;
-    if (record_kind != ACGPU_REC_SET && record_kind != ACGPU_REC_MAP) return ACGPU_E_INVALID;
-    if (sh->n_units >= (1ull << 31) || sh->own_begin > sh->own_end || sh->own_end > sh->n_units) return ACGPU_E_INVALID;
-    if (sh->n_units && (!sh->d_hay || ((uintptr_t)sh->d_hay & 15))) return ACGPU_E_INVALID;
-    if (cap && (!d_out || ((uintptr_t)d_out & 3))) return ACGPU_E_INVALID;
-    if (sh->d_result && ((uintptr_t)sh->d_result & 15)) return ACGPU_E_INVALID;
-    if (d->inflight > 0 && stream != d->inflight_stream) return ACGPU_E_INVALID; // stream rule (include/acgpu.h)
+    if ((rc = check_shard(a, d, sh, record_kind, d_out, cap, stream))) return rc;
     Ticket *tk = nullptr;
-    for (auto &cand : d->tickets)
+    for (auto &cand : d.tickets)
         if (!cand.busy) { tk = &cand; break; }
     if (!tk) return ACGPU_E_INVALID; // too many calls in flight: collect one first
-    tk->profiled = want_profile != 0;
-    tk->done_is_ev2 = false;
-    tk->one_kernel = false;
-    tk->cap = cap;
-    tk->user_shard = sh;
-    tk->kname[0] = 0;
-    uint64_t dummy = 0;
-    // enqueued without waiting: the AhoCorasick / WholeWord pipeline (one scan + ordering pass) and the LongestMatch walk
-    // pipeline (lengths, synchronisation points, chain count, prefix sum, emit: nothing of it needs the host).  The other
-    // families -- and LongestMatch over a dictionary with a selective suffix filter, whose sparse form falls back to the walk
-    // after looking at the match count -- run their call inside _begin: the ticket is complete when _begin returns.
-    if (t.mode == ACGPU_MODE_ALL || (t.mode == ACGPU_MODE_WHOLEWORD && t.fold_consistent)) {
-        tk->kind = 0;
-        rc = match_all(a, *d, sh, record_kind, d_out, cap, &dummy, stream, nullptr, tk);
-    } else if (t.mode == ACGPU_MODE_LONGEST && !(filter_is_selective(t) && tunables().force_kernel != 1)) {
-        tk->kind = 1;
-        rc = match_longest(a, *d, sh, record_kind, d_out, cap, &dummy, stream, nullptr, tk);
+    // enqueued without waiting: the AhoCorasick / WholeWord pipeline (one scan + ordering pass) and the LongestMatch pipelines
+    // (nothing of them needs the host).  The other families -- and LongestMatch over a dictionary with a selective suffix
+    // filter, whose sparse form falls back to the walk after looking at the match count -- run their call inside _begin: the
+    // ticket is complete when _begin returns (no completion marker: nothing in flight, the stream rule does not apply to it).
+    const bool all = t.mode == ACGPU_MODE_ALL || (t.mode == ACGPU_MODE_WHOLEWORD && t.fold_consistent);
+    const bool enqueued = all || (t.mode == ACGPU_MODE_LONGEST && !(filter_is_selective(t) && tunables().force_kernel != 1));
+    open_call(tk->rec, tk->ev, enqueued ? tk->done : nullptr, tk->h_count, *sh, sh, record_kind, d_out, cap, stream, want_profile != 0,
+              false);
+    std::memset(&tk->sync_prof, 0, sizeof(tk->sync_prof));
+    if (enqueued) {
+        if ((rc = all ? enqueue_all(a, d, tk->rec, 0) : enqueue_longest(a, d, tk->rec, 0))) return rc;
+        d.inflight++;
+        d.inflight_stream = stream;
     } else {
-        tk->kind = 2;
-        tk->sync_n = 0;
-        std::memset(&tk->sync_prof, 0, sizeof(tk->sync_prof));
-        tk->sync_rc = match_shard(a, *d, sh, record_kind, d_out, cap, &tk->sync_n, stream, want_profile ? &tk->sync_prof : nullptr);
-        if (tk->sync_rc != ACGPU_OK && tk->sync_rc != ACGPU_E_OVERFLOW) return tk->sync_rc;
-        tk->busy = true; // (complete: nothing in flight on the device, the stream rule does not apply to it)
-        *ticket = reinterpret_cast<acgpu_ticket *>(tk);
-        return ACGPU_OK;
+        uint64_t n = 0;
+        rc = match_shard(a, d, sh, record_kind, d_out, cap, &n, stream, want_profile ? &tk->sync_prof : nullptr);
+        if (rc != ACGPU_OK && rc != ACGPU_E_OVERFLOW) return rc;
+        tk->h_count[0] = n; // (the record stays complete: the count is all collect() reads)
     }
-    if (rc != ACGPU_OK) return rc;
     tk->busy = true;
-    d->inflight++;
-    d->inflight_stream = stream;
     *ticket = reinterpret_cast<acgpu_ticket *>(tk);
     return ACGPU_OK;
 }
-
 
 } // namespace acgpu
 
@@ -1978,17 +2020,17 @@ int acgpu_match_device_abandon(const acgpu_automaton *ca, acgpu_ticket *ticket) 
     {
         std::lock_guard<std::mutex> lock(own->mu);
         if (!tk->busy) return ACGPU_E_INVALID;
-        if (tk->kind == 2) {
+        if (!tk->rec.done) { // (ran inside _begin)
             tk->busy = false;
             return ACGPU_OK;
         }
-        done = tk->done_is_ev2 ? tk->ev[2] : tk->done;
+        done = completion(tk->rec);
     }
     HIP_TRY(hipEventSynchronize(done)); // (its kernels still write the caller's buffers until then)
     std::lock_guard<std::mutex> lock(own->mu);
     if (!tk->busy) return ACGPU_E_INVALID;
     tk->busy = false;
-    reinterpret_cast<DeviceState *>(tk->owner)->inflight--;
+    own->inflight--;
     return ACGPU_OK;
 }
 
@@ -2005,71 +2047,22 @@ int end_ticket(const acgpu_automaton *ca, acgpu_ticket *ticket, uint64_t *n_out,
     if (!ca || !ticket || !n_out) return ACGPU_E_INVALID;
     acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
     Ticket *tk = reinterpret_cast<Ticket *>(ticket);
-    DeviceState *own = reinterpret_cast<DeviceState *>(tk->owner); // (set when the pool was created)
+    DeviceState *d = reinterpret_cast<DeviceState *>(tk->owner); // (set when the pool was created)
     hipEvent_t done = nullptr;
     {
-        std::lock_guard<std::mutex> lock(own->mu);
+        std::lock_guard<std::mutex> lock(d->mu);
         if (!tk->busy) return ACGPU_E_INVALID;
-        if (tk->kind == 2) { // ran inside _begin
-            tk->busy = false;
-            *n_out = tk->sync_n;
-            if (prof) *prof = tk->sync_prof;
-            return tk->sync_rc;
-        }
-        done = tk->done_is_ev2 ? tk->ev[2] : tk->done;
+        if (tk->rec.done) done = completion(tk->rec);
     }
-    HIP_TRY(hipEventSynchronize(done)); // outside the lock: other calls may be enqueued meanwhile
-    std::lock_guard<std::mutex> lock(own->mu);
+    if (done) HIP_TRY(hipEventSynchronize(done)); // outside the lock: other calls may be enqueued meanwhile
+    std::lock_guard<std::mutex> lock(d->mu);
     if (!tk->busy) return ACGPU_E_INVALID; // (collected by another thread meanwhile)
-    DeviceState *d = reinterpret_cast<DeviceState *>(tk->owner);
-    if (tk->kind == 0 && (uint32_t)tk->h_count[1] != 0) { // a candidate slice / scratch slice was too small: redo with the fused kernel, one slice
-        // (the redo shares the scratch with the tickets still in flight: same stream, so stream order keeps them apart)
-        const int rc = match_all(a, *d, &tk->shard, tk->record_kind, tk->d_out, tk->cap, n_out, tk->stream, prof, nullptr, true);
-        tk->busy = false;
-        d->inflight--;
-        if (redone) *redone = true;
-        return rc;
-    }
-    if (tk->kind == 1 && tk->h_count[1] != 0) { // k_longest_bits / k_longest_follow bailed out (a unit outside the alphabet, a chain that did not merge)
-        if (!std::strcmp(tk->kname, "k_longest_follow")) d->fol_level = std::max(d->fol_level, tk->bits_level + 1);
-        const int rc = match_longest(a, *d, &tk->shard, tk->record_kind, tk->d_out, tk->cap, n_out, tk->stream, prof, nullptr,
-                                     tk->h_count[1] == 1 ? tk->bits_level + 1 : 2);
-        if (tk->user_shard) tk->user_shard->chain_exit = tk->shard.chain_exit;
-        tk->busy = false;
-        d->inflight--;
-        if (redone) *redone = true;
-        return rc;
-    }
-    *n_out = *tk->h_count;
-    if (tk->kind == 1 && tk->user_shard) tk->user_shard->chain_exit = (int64_t)tk->h_count[2];
-    if (tk->kind == 0 && a->t.mode != ACGPU_MODE_WHOLEWORD && tk->shard.own_end > tk->shard.own_begin)
-        d->all_density = (double)*n_out / (double)(tk->shard.own_end - tk->shard.own_begin);
     tk->busy = false; // (whatever happens below, the ticket is collected)
-    d->inflight--;
-    if (prof) {
-        std::memset(prof, 0, sizeof(*prof));
-        if (tk->profiled && tk->one_kernel) {
-            HIP_TRY(hipEventElapsedTime(&prof->scan_ms, tk->ev[0], tk->ev[2]));
-            prof->total_ms = prof->scan_ms;
-        } else if (tk->profiled) {
-            HIP_TRY(hipEventElapsedTime(&prof->scan_ms, tk->ev[0], tk->ev[1]));
-            HIP_TRY(hipEventElapsedTime(&prof->finalize_ms, tk->ev[1], tk->ev[2]));
-            HIP_TRY(hipEventElapsedTime(&prof->total_ms, tk->ev[0], tk->ev[2]));
-        }
-        prof->scan_units = tk->scanned;
-        prof->n_matches = *n_out;
-        std::snprintf(prof->scan_kernel, sizeof(prof->scan_kernel), "%s", tk->kname);
-    }
-    return *n_out > tk->cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
+    if (tk->rec.done) d->inflight--;
+    if (prof && tk->rec.form == CallForm::Complete) *prof = tk->sync_prof;
+    return collect(a, *d, &tk->rec, n_out, prof, redone);
 }
 
-} // namespace acgpu
-
-extern "C" {
-
-} // extern "C"
-
-namespace acgpu {
 
 // acgpu_match_u16 on a long haystack, pipelined: the text goes to the device in chunks -- worker threads copy the caller's
 // (pageable) memory into a ring of pinned staging buffers and enqueue the DMA on a copy stream -- while the chunks that have

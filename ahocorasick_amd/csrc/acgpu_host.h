@@ -46,31 +46,48 @@ struct DevBuf {
     }
 };
 
+// How a call's result is collected (collect(), acgpu_api.hip): the pipeline that was enqueued.
+enum class CallForm : uint8_t {
+    Complete,      // nothing to read from the device: the empty call, or a call that ran inside _begin (count in h_slot[0])
+    States,        // k_ac_states + k_ac_states_out
+    Ordered,       // a scan kernel and its ordering pass (k_permute, k_permute_wg, k_ww_compact), which reports into the slot
+    FusedTail,     // the tile kernel or k_ww_pp with the fused tail: one kernel
+    LongestBits,   // k_longest_bits
+    LongestFollow, // k_longest_follow
+    LongestWalk,   // the LONGEST walk pipeline
+};
+
+// One call on a scratch pool: what enqueueing it decided and what completing it needs.  A ticket carries one; the pool owns one
+// for its synchronous calls (DeviceState::call, on DeviceState::ev and h_counter).
+struct CallRecord {
+    acgpu_shard shard{};               // the shard as it was enqueued: a redo runs on this copy
+    acgpu_shard *user_shard = nullptr; // the caller's: receives chain_exit
+    int record_kind = 0;
+    void *d_out = nullptr;
+    uint64_t cap = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t *ev = nullptr;          // ev[0] .. ev[2]: the profile's events
+    hipEvent_t done = nullptr;         // a ticket's completion marker; null: a synchronous call (or one that ran inside _begin)
+    bool done_is_ev2 = false;          // the completion to wait for is ev[2] (the call's last kernel's own end), not `done`
+    bool one_kernel = false;           // the call was one kernel (the fused tail): ev[0] .. ev[2] is its dispatch, ev[1] is not recorded
+    bool profiled = false;
+    unsigned long long *h_slot = nullptr; // pinned, 64 bytes: {count, overflow word or bail flag, chain exit}
+    CallForm form = CallForm::Complete;
+    int level = 0;                     // ALL: 1 = the redo's form (the fused kernel, one scratch slice); LONGEST: the run-up level
+    bool folded = false;               // WHOLEWORD: the scan saw the folded tables (folded_tables, acgpu_api.hip)
+    uint64_t scanned = 0;
+    char kname[64] = {0};
+};
+
 // One asynchronous call in flight (acgpu_match_device_begin/_end): its own events and pinned count slot.
 struct Ticket {
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     hipEvent_t done = nullptr;
     unsigned long long *h_count = nullptr; // pinned, 64 bytes
-    bool busy = false, profiled = false;
-    bool done_is_ev2 = false; // the completion to wait for is ev[2] (the finalize kernel's own end), not `done`
-    bool one_kernel = false;  // the call was one kernel (the tile kernel with the fused tail): ev[0] .. ev[2] is its dispatch, ev[1] is not recorded
-    // how _end collects it: 0 = the AhoCorasick / WholeWord pipeline (count and overflow word in h_count), 1 = a chain pipeline
-    // that was enqueued (LONGEST walk: count in h_count[0], chain exit in h_count[2]), 2 = the call ran synchronously inside
-    // _begin (the other families): everything is in the fields below
-    int kind = 0;
-    int sync_rc = 0;
-    uint64_t sync_n = 0;
-    acgpu_profile sync_prof{};
-    acgpu_shard *user_shard = nullptr; // receives chain_exit in _end
-    uint64_t cap = 0, scanned = 0;
-    char kname[64] = {0};
+    bool busy = false;
+    CallRecord rec;
+    acgpu_profile sync_prof{}; // the profile of a call that ran inside _begin (zero for the empty call)
     void *owner = nullptr; // the DeviceState it belongs to
-    // what _end needs to redo the call when the split form's candidate slices were too small
-    acgpu_shard shard{};
-    int record_kind = 0;
-    void *d_out = nullptr;
-    hipStream_t stream = nullptr;
-    int bits_level = 0; // LONGEST, k_longest_bits / k_longest_follow: the run-up level the call was enqueued with (0: short, 1: a whole segment)
 };
 
 struct DeviceState {
@@ -121,6 +138,7 @@ struct DeviceState {
     bool cclean[2] = {false, false};
     void *counter_seen = nullptr; // (a re-allocated counter buffer is not clean)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    CallRecord call; // the synchronous calls' record
     Ticket tickets[4];
     // stream rule (include/acgpu.h): while tickets are in flight every call on this automaton and device uses their stream
     int inflight = 0;

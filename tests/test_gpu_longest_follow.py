@@ -155,6 +155,16 @@ def test_follow_form_shards_chains_that_never_merge_and_tickets(words):
     # ... and the pool remembers: its next call does not try again (a fresh automaton does)
     got, kname, _ = _run(a2, run[:200000], False)
     assert kname != "k_longest_follow" and (got == Oracle(FAM_LONGEST, kw2).match(run[:200000])[:, :2]).all()
+    # the enqueued form on a fresh pool: _end learns of the bail-out, redoes the call, and the pool remembers it too
+    a2t = Automaton(N.MODE_LONGEST, kw2, True)
+    d_run = torch.from_numpy(run.view(np.int16)).cuda()
+    out2 = torch.empty((run.size, 2), dtype=torch.int32, device="cuda")
+    tk, rc = a2t.match_device_begin(d_run.data_ptr(), run.size, False, out2.data_ptr(), run.size, stream=st)
+    assert rc == N.OK
+    m, rc, _ = a2t.match_device_end(tk)
+    assert rc == N.OK and m == len(want2) and (out2[:m].cpu().numpy() == want2).all()
+    got, kname, _ = _run(a2t, run[:200000], False)
+    assert kname != "k_longest_follow" and (got == Oracle(FAM_LONGEST, kw2).match(run[:200000])[:, :2]).all()
     run[::1000] = ord("d")
     a3 = Automaton(N.MODE_LONGEST, kw2, True)
     got, kname, _ = _run(a3, run, False)

@@ -1666,7 +1666,7 @@ def test_long_keywords_branching_suffixes_and_planted_matches():
 
 def test_wholeword_scratch_slice_overflow_is_redone_with_one_slice():
     """WholeWord takes record slots from one scratch slice per workgroup as well: all words in the first workgroup's share,
-    exact capacity -> that slice fills up and the call is redone with one slice."""
+    exact capacity -> that slice fills up and the call is redone with one slice -- synchronously and through begin/end."""
     import torch
     words = ["ab", "abc", "b", "cab"]
     a = Automaton(N.MODE_WHOLEWORD, words, True, word_chars=WORD)
@@ -1683,6 +1683,11 @@ def test_wholeword_scratch_slice_overflow_is_redone_with_one_slice():
     d_hay = torch.from_numpy(hay.view(np.int16)).cuda()
     got, _ = _dev_match(a, d_hay, n, True, len(want))
     assert got.shape == want.shape and (got == want).all()
+    out = torch.empty((len(want), 3), dtype=torch.int32, device="cuda")
+    tk, rc = a.match_device_begin(d_hay.data_ptr(), n, True, out.data_ptr(), len(want), stream=torch.cuda.current_stream().cuda_stream)
+    assert rc == N.OK
+    m, rc, _ = a.match_device_end(tk)
+    assert rc == N.OK and m == len(want) and (out[:m].cpu().numpy() == want).all()
 
 
 def test_wholeword_async_begin_end_pipelined_overflow_and_slice_redo():
