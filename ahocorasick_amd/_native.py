@@ -53,6 +53,12 @@ class Profile(ctypes.Structure):
                 ("scan_units", ctypes.c_uint64), ("n_matches", ctypes.c_uint64), ("scan_kernel", ctypes.c_char * 64)]
 
 
+class CursorStats(ctypes.Structure):  # acgpu_cursor_stats
+    _fields_ = [("records_delivered", ctypes.c_uint64), ("records_buffered", ctypes.c_uint64), ("units_scanned", ctypes.c_uint64),
+                ("scan_end", ctypes.c_uint64), ("pieces", ctypes.c_uint32), ("rescans", ctypes.c_uint32), ("done", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
 # every symbol include/acgpu.h declares
 SYMBOLS = ["acgpu_build", "acgpu_free", "acgpu_get_info", "acgpu_match_u16", "acgpu_match_batch_u16", "acgpu_match_device",
            "acgpu_match_device_begin", "acgpu_match_device_end", "acgpu_match_device_abandon", "acgpu_synth_fill", "acgpu_synth_tokens", "acgpu_stream_probe",
@@ -60,7 +66,8 @@ SYMBOLS = ["acgpu_build", "acgpu_free", "acgpu_get_info", "acgpu_match_u16", "ac
            "acgpu_debug_wordhash", "acgpu_debug_wordhash_perfect", "acgpu_stream_open", "acgpu_stream_feed", "acgpu_stream_close",
            "acgpu_match_u16_multi", "acgpu_comm_open", "acgpu_comm_close", "acgpu_comm_transport", "acgpu_comm_stream",
            "acgpu_match_device_allgather", "acgpu_last_rccl_error", "acgpu_gather_slot_bytes",
-           "acgpu_stream_set_pipelined", "acgpu_stream_reserve"]
+           "acgpu_stream_set_pipelined", "acgpu_stream_reserve", "acgpu_cursor_open", "acgpu_cursor_next",
+           "acgpu_cursor_get_stats", "acgpu_cursor_close"]
 
 _lib = None
 
@@ -126,6 +133,14 @@ def lib():
         L.acgpu_stream_set_pipelined.argtypes = [vp, ci]
         L.acgpu_stream_reserve.restype = ci
         L.acgpu_stream_reserve.argtypes = [vp, u64, ctypes.POINTER(vp)]
+        L.acgpu_cursor_open.restype = ci
+        L.acgpu_cursor_open.argtypes = [vp, vp, u64, ci, ctypes.POINTER(vp)]
+        L.acgpu_cursor_next.restype = ci
+        L.acgpu_cursor_next.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
+        L.acgpu_cursor_get_stats.restype = ci
+        L.acgpu_cursor_get_stats.argtypes = [vp, ctypes.POINTER(CursorStats)]
+        L.acgpu_cursor_close.restype = None
+        L.acgpu_cursor_close.argtypes = [vp]
         L.acgpu_debug_wordhash_perfect.restype = ci
         L.acgpu_debug_wordhash_perfect.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.acgpu_debug_wordhash.restype = ci

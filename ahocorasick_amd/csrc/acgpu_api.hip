@@ -1845,6 +1845,9 @@ int64_t acgpu_set_tunable(const char *name, int64_t value) {
     else if (!std::strcmp(name, "no_big_l2")) slot = &t.no_big_l2;
     else if (!std::strcmp(name, "no_class_pages")) slot = &t.no_class_pages;
     else if (!std::strcmp(name, "split_cand_div")) slot = &t.split_cand_div;
+    else if (!std::strcmp(name, "cursor_first_piece")) slot = &t.cursor_first_piece;
+    else if (!std::strcmp(name, "cursor_max_piece")) slot = &t.cursor_max_piece;
+    else if (!std::strcmp(name, "cursor_reservoir_bytes")) slot = &t.cursor_reservoir_bytes;
     if (!slot) return -1;
     return slot->exchange(value, std::memory_order_relaxed);
 }
@@ -1872,6 +1875,7 @@ int acgpu_build(int mode, const uint16_t *kw_units, const uint64_t *kw_off, uint
 }
 
 void acgpu_stream_detach(acgpu_stream *s); // acgpu_stream.hip
+void acgpu_cursor_detach(acgpu_cursor *c); // acgpu_cursor.hip
 
 void acgpu_free(acgpu_automaton *a) {
     if (!a) return;
@@ -1880,6 +1884,8 @@ void acgpu_free(acgpu_automaton *a) {
         std::lock_guard<std::mutex> l(a->mu);
         for (acgpu_stream *s : a->open_streams) acgpu_stream_detach(s);
         a->open_streams.clear();
+        for (acgpu_cursor *c : a->open_cursors) acgpu_cursor_detach(c); // (the same for cursors)
+        a->open_cursors.clear();
     }
     int cur = -1;
     bool have = hipGetDevice(&cur) == hipSuccess;
@@ -2118,7 +2124,8 @@ static bool device_numa_cpus(int dev, cpu_set_t *set) {
 }
 
 int scan_host_range(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack, uint64_t n_units, uint64_t lo, uint64_t hi,
-                    uint64_t own_lo, uint64_t own_hi, int record_kind, uint64_t cap, uint64_t *n_out, int64_t *chain_io) {
+                    uint64_t own_lo, uint64_t own_hi, int record_kind, uint64_t cap, uint64_t *n_out, int64_t *chain_io,
+                    void *d_out) {
     const HostTables &t = a->t;
     const uint64_t C = kHostChunkUnits;
     const uint64_t nb = hi - lo; // units in the device buffer
@@ -2128,7 +2135,10 @@ int scan_host_range(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack
     *n_out = 0;
     int rc;
     if ((rc = d.stage_hay.ensure(nb * 2 + 16))) return rc;
-    if ((rc = d.stage_out.ensure(cap * (uint64_t)record_kind + 16))) return rc;
+    if (!d_out) {
+        if ((rc = d.stage_out.ensure(cap * (uint64_t)record_kind + 16))) return rc;
+        d_out = d.stage_out.p;
+    }
     if (!d.copy_stream) HIP_TRY(hipStreamCreateWithFlags(&d.copy_stream, hipStreamNonBlocking));
     // the ring: as many slots as this buffer has chunks (at most kPinSlots), each as large as its largest chunk -- a share of a
     // few megabytes of a multi-device call, or a 40 MiB haystack, does not pin 8 x 32 MiB
@@ -2228,7 +2238,7 @@ int scan_host_range(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack
         sh.chain_entry = t.mode == ACGPU_MODE_SHORTEST ? chain : std::max<int64_t>(chain, (int64_t)c0);
         uint64_t n_k = 0;
         const uint64_t room = total < cap ? cap - total : 0;
-        rc = match_shard(a, d, &sh, record_kind, (char *)d.stage_out.p + std::min(total, cap) * (uint64_t)record_kind, room, &n_k, stream, nullptr);
+        rc = match_shard(a, d, &sh, record_kind, (char *)d_out + std::min(total, cap) * (uint64_t)record_kind, room, &n_k, stream, nullptr);
         if (rc != ACGPU_OK && rc != ACGPU_E_OVERFLOW) {
             result = rc;
             break;

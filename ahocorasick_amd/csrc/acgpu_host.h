@@ -214,6 +214,7 @@ struct acgpu_automaton {
     acgpu::HostTables t;
     std::vector<acgpu::StreamBufs> stream_cache;                                 // guarded by mu
     std::set<struct acgpu_stream *> open_streams;                                // guarded by mu: acgpu_free detaches them (acgpu_stream::a = nullptr)
+    std::set<struct acgpu_cursor *> open_cursors;                                // guarded by mu: the same for cursors (acgpu_cursor.hip)
     std::mutex mu;                                                               // guards `dev`, `stream_cache` and `open_streams`
     std::map<std::pair<int, int>, std::unique_ptr<acgpu::DeviceState>> dev;      // (HIP device, lane) -> scratch pool + tables
 };
@@ -240,8 +241,10 @@ int end_ticket(const acgpu_automaton *a, acgpu_ticket *ticket, uint64_t *n_out, 
 
 // acgpu_match_u16 on a long haystack, pipelined over chunks (acgpu_api.hip): the units [lo, hi) of `haystack` become the
 // device buffer d.stage_hay (buffer unit 0 = unit lo), the owned range [own_lo, own_hi) is scanned as shards of it on
-// d.call_stream, the records (buffer relative) land in d.stage_out.  chain: in = entry, out = exit (buffer relative).
+// d.call_stream, the records (buffer relative) land in d.stage_out -- or in d_out, a device buffer of cap records, when it is
+// given.  chain: in = entry, out = exit (buffer relative).
 int scan_host_range(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack, uint64_t n_units, uint64_t lo, uint64_t hi,
-                    uint64_t own_lo, uint64_t own_hi, int record_kind, uint64_t cap, uint64_t *n_out, int64_t *chain);
+                    uint64_t own_lo, uint64_t own_hi, int record_kind, uint64_t cap, uint64_t *n_out, int64_t *chain,
+                    void *d_out = nullptr);
 
 } // namespace acgpu

@@ -397,6 +397,9 @@ struct Tunables {
     std::atomic<int64_t> no_bits_trie{0};     // builder: 1 = no path-compressed trie for k_longest_bits (the walk pipeline instead: A/B)
     std::atomic<int64_t> reserve_cus{0};      // CUs left without a scan workgroup (room for a collective's kernels under the scan)
     std::atomic<int64_t> tile_form{0};        // ALL, tile kernel, bits: 1 = never the fused tail (a finalize launch behind the scan: tests, A/B)
+    std::atomic<int64_t> cursor_first_piece{1ll << 20};      // acgpu_cursor: owned units of the first piece
+    std::atomic<int64_t> cursor_max_piece{1ll << 26};        // acgpu_cursor: owned units of the largest piece
+    std::atomic<int64_t> cursor_reservoir_bytes{256ll << 20}; // acgpu_cursor: largest device reservoir of one piece's records
 };
 Tunables &tunables();
 

@@ -38,6 +38,19 @@ public class GpuAhoCorasickMap<T> implements StringMap<T>, AutoCloseable {
     }
 
     public void match(final String haystack, final MapMatchListener<T> listener) {
+        if (automaton.pages(haystack)) { // a long haystack: pages of a cursor (see GpuAhoCorasickSet.match)
+            final long cursor = automaton.openCursor(haystack, true);
+            try {
+                for (int[] r = automaton.nextPage(cursor); r.length > 0; r = automaton.nextPage(cursor)) {
+                    for (int i = 0; i < r.length; i += 3) {
+                        if (!listener.match(haystack, r[i], r[i + 1], values.get(r[i + 2]))) return;
+                    }
+                }
+            } finally {
+                NativeAutomaton.closeCursor(cursor);
+            }
+            return;
+        }
         final int[] r = automaton.match(haystack, true);
         for (int i = 0; i < r.length; i += 3) {
             if (!listener.match(haystack, r[i], r[i + 1], values.get(r[i + 2]))) {

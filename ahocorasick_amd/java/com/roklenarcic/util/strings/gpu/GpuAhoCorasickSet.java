@@ -30,6 +30,19 @@ public class GpuAhoCorasickSet implements StringSet, AutoCloseable {
     }
 
     public void match(final String haystack, final SetMatchListener listener) {
+        if (automaton.pages(haystack)) { // a long haystack: pages of a cursor, scanned only as far as the listener goes
+            final long cursor = automaton.openCursor(haystack, false);
+            try {
+                for (int[] r = automaton.nextPage(cursor); r.length > 0; r = automaton.nextPage(cursor)) {
+                    for (int i = 0; i < r.length; i += 2) {
+                        if (!listener.match(haystack, r[i], r[i + 1])) return;
+                    }
+                }
+            } finally {
+                NativeAutomaton.closeCursor(cursor);
+            }
+            return;
+        }
         final int[] r = automaton.match(haystack, false); // NullPointerException for a null haystack, like the reference
         for (int i = 0; i < r.length; i += 2) {
             if (!listener.match(haystack, r[i], r[i + 1])) {

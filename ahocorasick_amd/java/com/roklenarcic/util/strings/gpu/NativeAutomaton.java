@@ -71,6 +71,34 @@ final class NativeAutomaton implements AutoCloseable {
         streamClose(stream);
     }
 
+    /** match(String, ...) pages through a cursor from this many chars on (shorter haystacks: the one call, whose fixed cost is lower) */
+    static final int CURSOR_MIN_CHARS = 1 << 22;
+
+    /** records per page of a cursor (12 MiB of int[] for Map records) */
+    static final int PAGE_RECORDS = 1 << 20;
+
+    /** whether match(String, ...) takes the cursor for this haystack: long, and no device list (which keeps the single call) */
+    boolean pages(String haystack) {
+        return DEVICES == null && haystack != null && haystack.length() >= CURSOR_MIN_CHARS;
+    }
+
+    /**
+     * acgpu_cursor_*: the records of {@link #match} handed out in pages, scanned only as far as the pages taken require. The
+     * cursor owns a copy of the haystack's chars until {@link #closeCursor}.
+     */
+    long openCursor(String haystack, boolean withIds) {
+        return cursorOpen(handle, haystack, withIds);
+    }
+
+    /** the next page, flattened as {@link #match} returns records; an empty array: every record has been handed out */
+    int[] nextPage(long cursor) {
+        return cursorNext(cursor, PAGE_RECORDS);
+    }
+
+    static void closeCursor(long cursor) {
+        cursorClose(cursor);
+    }
+
     @Override
     public void close() {
         if (handle != 0) {
@@ -94,4 +122,11 @@ final class NativeAutomaton implements AutoCloseable {
     private static native int[] streamFeed(long stream, char[] chunk, int length, boolean last, boolean pipelined);
 
     private static native void streamClose(long stream);
+
+    /** NullPointerException for a null haystack */
+    private static native long cursorOpen(long handle, String haystack, boolean withIds);
+
+    private static native int[] cursorNext(long cursor, int maxRecords);
+
+    private static native void cursorClose(long cursor);
 }

@@ -2,7 +2,7 @@
  * acgpu_jni.c -- JNI glue between com.roklenarcic.util.strings.gpu.NativeAutomaton and the C ABI (include/acgpu.h).
  * Build (on a machine with a JDK; not possible in the build image):
  *   gcc -shared -fPIC -I$JAVA_HOME/include -I$JAVA_HOME/include/linux -I../../../include \
- *       -o libacgpu_jni.so acgpu_jni.c -L../../lib -lacgpu -Wl,-rpath,'$ORIGIN'
+ *       -o libacgpu_jni.so acgpu_jni.c acgpu_jni_cursor.c -L../../lib -lacgpu -Wl,-rpath,'$ORIGIN'
  *
  * Rules this file keeps:
  *  - no JNI critical region is ever open across a call into libacgpu (those calls take a mutex, allocate device memory,
@@ -19,22 +19,7 @@
 #include <string.h>
 
 #include "acgpu.h"
-
-#define REGION_SLICE (32 * 1024 * 1024) /* chars per GetStringRegion call (64 MiB) */
-
-static void throw_new(JNIEnv *env, const char *cls, const char *msg) {
-    if ((*env)->ExceptionCheck(env)) return; /* keep the first one */
-    jclass c = (*env)->FindClass(env, cls);
-    if (c) (*env)->ThrowNew(env, c, msg);
-}
-
-static void throw_oom(JNIEnv *env, const char *what) { throw_new(env, "java/lang/OutOfMemoryError", what); }
-
-static void throw_rc(JNIEnv *env, int rc) {
-    if (rc == ACGPU_E_NOMEM) throw_oom(env, acgpu_strerror(rc));
-    else if (rc == ACGPU_E_UNSUPPORTED) throw_new(env, "java/lang/UnsupportedOperationException", acgpu_strerror(rc));
-    else throw_new(env, "java/lang/IllegalStateException", acgpu_strerror(rc));
-}
+#include "acgpu_jni_common.h"
 
 /* IllegalArgumentException(keyword + " contains non-word characters.") -- the reference's message,
  * S/WholeWordMatchMap.java:265 -- built from the String itself (any characters, any length) */

@@ -205,6 +205,16 @@ class Automaton:
         """acgpu_match_device_abandon: give the ticket up (waits for its kernels, never redoes the call)."""
         return N.lib().acgpu_match_device_abandon(self._h, ticket.handle)
 
+    def pages(self, hay_units, with_ids, page_records=1 << 20):
+        """acgpu_cursor_*: the records of match_host(hay_units) as a generator of (n, 2|3) int32 pages of at most page_records
+        records, scanned only as far as the pages taken so far require.  Closing the generator closes the cursor."""
+        with Cursor(self, hay_units, with_ids) as cur:
+            while True:
+                page = cur.next(page_records)
+                if not len(page):
+                    return
+                yield page
+
 
 class Comm:
     """acgpu_comm: the devices of a single-process multi-GPU job, one stream per device, and the transport of the gather
@@ -322,6 +332,68 @@ class Stream:
     __del__ = close
 
 
+class Cursor:
+    """acgpu_cursor: one match(String) call handed out in pages (include/acgpu.h).  next(cap) returns the next 1 .. cap records
+    as an (n, 2|3) int32 array with haystack positions -- an empty one when every record has been handed out."""
+
+    def __init__(self, automaton, hay_units, with_ids=True):
+        self._auto = automaton  # keeps the handle alive
+        hay = np.ascontiguousarray(hay_units, dtype=np.uint16)
+        self._src = hay if hay.size else np.zeros(1, np.uint16)  # the library reads it until close
+        self._kind = N.REC_MAP if with_ids else N.REC_SET
+        self._out = None
+        h = ctypes.c_void_p()
+        N.check(N.lib().acgpu_cursor_open(automaton.handle, _vp(self._src), int(hay.size), self._kind, ctypes.byref(h)),
+                "acgpu_cursor_open")
+        self._h = h
+
+    def next(self, cap):
+        cap = int(cap)
+        cols = self._kind // 4
+        if self._out is None or self._out.shape[0] < cap:
+            self._out = np.empty((cap, cols), dtype=np.int32)
+        n_out = ctypes.c_uint64(0)
+        N.check(N.lib().acgpu_cursor_next(self._h, _vp(self._out), cap, ctypes.byref(n_out)), "acgpu_cursor_next")
+        return self._out[:n_out.value].copy()
+
+    def stats(self):
+        st = N.CursorStats()
+        N.check(N.lib().acgpu_cursor_get_stats(self._h, ctypes.byref(st)), "acgpu_cursor_get_stats")
+        return {f: getattr(st, f) for f, _ in N.CursorStats._fields_}
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            N.lib().acgpu_cursor_close(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    __del__ = close
+
+
+# match(String, listener) pages through a cursor from this many units on (shorter texts: the one call, whose fixed cost is lower)
+CURSOR_MIN_UNITS = 1 << 22
+
+
+def _listener_records(auto, hay, with_ids):
+    """The records of match(String, listener), as lists of rows: pages of a cursor for long haystacks on the current device,
+    the single call otherwise (and with a device list)."""
+    if hay.size >= CURSOR_MIN_UNITS and configured_devices() is None:
+        pages = auto.pages(hay, with_ids)
+        try:
+            for p in pages:
+                yield p.tolist()
+        finally:
+            pages.close()
+    else:
+        yield auto.match_host(hay, with_ids=with_ids).tolist()
+
+
 class ReadableMatchListener:
     """S/ReadableMatchListener.java:3-9"""
 
@@ -373,11 +445,15 @@ class StringSet:
     def match(self, haystack, listener):
         if haystack is None:
             raise TypeError("haystack is None")  # the reference throws NullPointerException at haystack.length()
-        recs = self._auto.match_host(utf16(haystack), with_ids=False)
         fn = _listener_fn(listener)
-        for s, e in recs.tolist():
-            if not fn(haystack, s, e):
-                break
+        pages = _listener_records(self._auto, utf16(haystack), False)
+        try:
+            for page in pages:
+                for s, e in page:
+                    if not fn(haystack, s, e):
+                        return
+        finally:
+            pages.close()  # (a long haystack's cursor: closed at the first False, the rest is never scanned)
 
     def find_all(self, haystack):
         """Convenience (not in the reference): the (n,2) int32 array of (start, end) records."""
@@ -415,12 +491,16 @@ class StringMap:
             raise TypeError("haystack is None")
         if not isinstance(haystack, (str, np.ndarray)):
             return self.match_readable(haystack, listener)
-        recs = self._auto.match_host(utf16(haystack), with_ids=True)
         fn = _listener_fn(listener)
         vals = self._values
-        for s, e, k in recs.tolist():
-            if not fn(haystack, s, e, vals[k]):
-                break
+        pages = _listener_records(self._auto, utf16(haystack), True)
+        try:
+            for page in pages:
+                for s, e, k in page:
+                    if not fn(haystack, s, e, vals[k]):
+                        return
+        finally:
+            pages.close()
 
     def match_readable(self, readable, listener, chunk_chars=1 << 22):
         """S/AhoCorasickMap.java:208-275, S/LongestMatchMap.java:203-286, S/WholeWordMatchMap.java:55-153: the listener

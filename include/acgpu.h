@@ -50,6 +50,13 @@
  *        -> without room: 20 C + 17 MB (scratch slices + ordering pass)
  *      Shortest / WholeWordLongest              the AhoCorasick / WholeWord form
  *        + 16 bytes per record of the all-matches list / per walk start
+ *    A cursor (acgpu_cursor_open below) needs the pool's scratch for ONE piece
+ *    (N = its units + halo, at most cursor_max_piece = 2^26 + max_len + 1)
+ *    plus buffers of its own:
+ *      reservoir (device)                       up to cursor_reservoir_bytes
+ *                                               (256 MiB): the piece's records
+ *      page staging (pinned, device-mapped)     cap x record_kind of the
+ *                                               largest page handed out
  */
 #ifndef ACGPU_H
 #define ACGPU_H
@@ -410,6 +417,54 @@ int acgpu_stream_set_pipelined(acgpu_stream *s, int on);
 int acgpu_stream_reserve(acgpu_stream *s, uint64_t n_units, uint16_t **buf);
 
 /*
+ * Cursor over ONE match(String, listener) call: the records acgpu_match_u16 would return for the haystack, handed out in the
+ * reference's listener-call order in pages of a size the caller chooses, and scanned only as far as the pages taken so far
+ * require -- a listener that returns false stops the scan where the reference stops (S/AhoCorasickSet.java:223-225), and a text
+ * with more records than one buffer (or one Java int[]) holds is drained page by page.
+ *  open  : haystack in HOST memory, n_units < 2^31; the caller keeps it alive and unchanged until close.  record_kind as for
+ *          acgpu_match_u16.  The cursor's device is the current HIP device at open (the automaton's tables are uploaded there
+ *          then: without a device, open fails as acgpu_match_u16 does).
+ *  next  : copies the next 1 .. cap records (cap >= 1) into `out` (record_kind layout, positions in haystack coordinates) and
+ *          returns ACGPU_OK; *n_out == 0 with ACGPU_OK: every record has been handed out.  Never ACGPU_E_OVERFLOW.  The
+ *          concatenation of all pages is, record for record, what acgpu_match_u16 returns for the same haystack and record_kind
+ *          (every family, both record kinds, fold-consistent word tables or not).
+ *  stats : progress of the scan, see acgpu_cursor_stats.
+ * How it scans: the owned units are cut into PIECES, each scanned by itself with the halo its family needs (as a share of
+ * acgpu_match_u16_multi carries) and the chain handed on from the piece before -- pieces run in sequence, so nothing is
+ * repaired.  The first piece has "cursor_first_piece" units (default 2^20), every further one four times the one before, up to
+ * "cursor_max_piece" (2^26), and never more than the records seen per unit so far predict to fill half of the reservoir: a
+ * device buffer of the cursor's own that holds the records of the current piece and grows up to "cursor_reservoir_bytes"
+ * (256 MiB).  A piece whose records do not fit is scanned again -- in a larger reservoir, or shrunk -- and counted in
+ * `rescans`.  A unit holds at most max_keyword_len records (ALL / SHORTEST) or one (the others), so a piece of one unit always
+ * fits a reservoir of that many records; ACGPU_E_NOMEM only where even that does not.  The loops that exist only as one
+ * sequential scan (word matchers over a table that is not fold-consistent, see above) scan the whole text as one piece.
+ * A next whose reservoir is empty scans pieces until one yields a record or the text ends; nothing is scanned ahead while the
+ * caller holds a page.
+ * Device and lifetime as for acgpu_stream_*: next from a thread whose current device is not the cursor's returns
+ * ACGPU_E_INVALID; close a cursor before acgpu_free of its automaton (one still open then is detached: next returns
+ * ACGPU_E_INVALID, close stays safe); tickets in flight on the automaton and device make next return ACGPU_E_INVALID.
+ * One thread at a time per cursor.  Other cursors and match calls on the same automaton may run between page calls: the scratch
+ * pool is held only inside next.  After a next that failed, only close is valid.
+ * Memory, besides the pool's scratch for one piece (its units plus halo, and the scan's buffers for them): the reservoir (up to
+ * cursor_reservoir_bytes of device memory) and a pinned, device-mapped page staging buffer of the largest page handed out.
+ */
+typedef struct acgpu_cursor acgpu_cursor;
+typedef struct acgpu_cursor_stats {
+    uint64_t records_delivered; /* handed out by the page calls so far                                   */
+    uint64_t records_buffered;  /* scanned, not yet handed out (held in the cursor's device reservoir)   */
+    uint64_t units_scanned;     /* owned haystack units scanned so far, rescans included                  */
+    uint64_t scan_end;          /* haystack units [0, scan_end) have been scanned                         */
+    uint32_t pieces, rescans;   /* piece scans; of those, scans repeated because the reservoir overflowed */
+    uint32_t done;              /* 1: text exhausted and every record handed out                          */
+    uint32_t reserved;
+} acgpu_cursor_stats;
+int acgpu_cursor_open(const acgpu_automaton *a, const uint16_t *haystack, uint64_t n_units, int record_kind,
+                      acgpu_cursor **out);
+int acgpu_cursor_next(acgpu_cursor *c, void *out, uint64_t cap, uint64_t *n_out);
+int acgpu_cursor_get_stats(const acgpu_cursor *c, acgpu_cursor_stats *st);
+void acgpu_cursor_close(acgpu_cursor *c);
+
+/*
  * Synthetic haystack generator of the benchmark: unit i of the stream is
  * table[((z_i >> 32) * table_len) >> 32] with z_i = SplitMix64 output for counter
  * start_index + i of `seed` (see ahocorasick_amd/synth.py).  d_dst: device pointer.
@@ -455,7 +510,8 @@ int acgpu_stream_probe(const void *d_buf, uint64_t n_bytes, void *stream, int re
  * default 4), "ww_no_byte_pages" (units staged as class codes, not as one byte each), "ww_block" (threads of a workgroup,
  * a multiple of 64) and "ww_ramp_pm" (per mille by which the spans of the last workgroups shrink); "longest_form" (bits:
  * 1 no k_longest_bits, 2 no k_longest_follow, 4 both for short texts too, 8 k_longest_follow over alphabets of up to four
- * letters).  Returns the previous value, -1 for an unknown name. */
+ * letters); the cursor's "cursor_first_piece" (units of its first piece, default 2^20), "cursor_max_piece" (largest piece,
+ * 2^26) and "cursor_reservoir_bytes" (largest reservoir, 256 MiB).  Returns the previous value, -1 for an unknown name. */
 int64_t acgpu_set_tunable(const char *name, int64_t value);
 
 const char *acgpu_strerror(int code);
