@@ -1706,10 +1706,9 @@ int match_shard(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_
     *n_out = 0;
     if (prof) std::memset(prof, 0, sizeof(*prof));
     const HostTables &t = a->t;
-    if (t.mode == ACGPU_MODE_ALL || (t.mode == ACGPU_MODE_WHOLEWORD && t.fold_consistent))
-        return run_sync(enqueue_all, a, d, sh, record_kind, d_out, cap, n_out, stream, prof);
-    if (t.mode == ACGPU_MODE_WHOLEWORD && readable && t.fold_clean) // the Readable loop: an ordinary scan over w' = word o lower
-        return run_sync(enqueue_all, a, d, sh, record_kind, d_out, cap, n_out, stream, prof, /*folded=*/true);
+    const ShardRule rule = shard_rule(t, record_kind, readable);
+    if (rule.all_pipeline) // (not fold-consistent: the Readable loop of WholeWord, an ordinary scan over w' = word o lower)
+        return run_sync(enqueue_all, a, d, sh, record_kind, d_out, cap, n_out, stream, prof, /*folded=*/!t.fold_consistent);
     // the other families end with their count on the host (and some run the ALL pipeline inside): the device copy of the
     // result is written behind the pipeline
     acgpu_device_result *d_res = reinterpret_cast<acgpu_device_result *>(sh->d_result);
@@ -1723,12 +1722,12 @@ int match_shard(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_
         if (rc == ACGPU_E_UNSUPPORTED) rc = run_sync(enqueue_longest, a, d, sh, record_kind, d_out, cap, n_out, stream, prof);
         break;
     case ACGPU_MODE_WHOLEWORD:
-        if (readable) { // folded keywords with non-word units: the WholeWordLongest walk without fail matches, unit by unit
+        if (rule.sequential) {
+            rc = match_wholeword_sequential(a, d, sh, record_kind, d_out, cap, n_out, stream, prof);
+        } else { // Readable, folded keywords with non-word units: the WholeWordLongest walk without fail matches, unit by unit
             DevTables Tf = folded_tables(d);
             Tf.ww_fat = nullptr;
             rc = match_wwlongest(a, d, sh, record_kind, d_out, cap, n_out, stream, prof, Tf, true);
-        } else {
-            rc = match_wholeword_sequential(a, d, sh, record_kind, d_out, cap, n_out, stream, prof);
         }
         break;
     case ACGPU_MODE_SHORTEST: rc = match_shortest(a, d, sh, record_kind, d_out, cap, n_out, stream, prof); break;
@@ -1736,10 +1735,8 @@ int match_shard(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_
         // not fold-consistent: the Map class's String loop and both Readable loops fold in every lookup
         // (S/WholeWordLongestMatchMap.java:252-288, :404) -- position parallel over w'; the Set class's String loop mixes
         // raw and folded lookups (S/WholeWordLongestMatchSet.java:126,151,156) -- sequential
-        if (t.fold_consistent) rc = match_wwlongest(a, d, sh, record_kind, d_out, cap, n_out, stream, prof, d.T, false);
-        else if (readable || record_kind == ACGPU_REC_MAP)
-            rc = match_wwlongest(a, d, sh, record_kind, d_out, cap, n_out, stream, prof, folded_tables(d), false);
-        else rc = match_wwlongest_sequential(a, d, sh, record_kind, d_out, cap, n_out, stream, prof);
+        if (rule.sequential) rc = match_wwlongest_sequential(a, d, sh, record_kind, d_out, cap, n_out, stream, prof);
+        else rc = match_wwlongest(a, d, sh, record_kind, d_out, cap, n_out, stream, prof, t.fold_consistent ? d.T : folded_tables(d), false);
         break;
     default: rc = ACGPU_E_UNSUPPORTED;
     }
@@ -1763,7 +1760,7 @@ int begin_shard(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_
     // (nothing of them needs the host).  The other families -- and LongestMatch over a dictionary with a selective suffix
     // filter, whose sparse form falls back to the walk after looking at the match count -- run their call inside _begin: the
     // ticket is complete when _begin returns (no completion marker: nothing in flight, the stream rule does not apply to it).
-    const bool all = t.mode == ACGPU_MODE_ALL || (t.mode == ACGPU_MODE_WHOLEWORD && t.fold_consistent);
+    const bool all = shard_rule(t, record_kind, false).all_pipeline;
     const bool enqueued = all || (t.mode == ACGPU_MODE_LONGEST && !(filter_is_selective(t) && tunables().force_kernel != 1));
     open_call(tk->rec, tk->ev, enqueued ? tk->done : nullptr, tk->h_count, *sh, sh, record_kind, d_out, cap, stream, want_profile != 0,
               false);
@@ -2069,6 +2066,36 @@ int end_ticket(const acgpu_automaton *ca, acgpu_ticket *ticket, uint64_t *n_out,
     return collect(a, *d, &tk->rec, n_out, prof, redone);
 }
 
+// ---- cutting a text into shards ------------------------------------------------------------------------------
+// ALL / SHORTEST: a match belongs to the piece that owns its last unit; LONGEST: to the piece that owns its first unit; the word
+// matchers: a word belongs to the piece that owns its first unit, whose left neighbour decides whether it starts a word.
+ShardRule shard_rule(const HostTables &t, int record_kind, bool readable) {
+    const uint64_t m = t.max_len, h = m ? m - 1 : 0;
+    switch (t.mode) { // ShardRule{left, right, chain, sequential, all_pipeline}
+    case ACGPU_MODE_ALL: return ShardRule{h, 0, Chain::None, false, true};
+    case ACGPU_MODE_SHORTEST: return ShardRule{h, 0, Chain::Restart, false, false};
+    case ACGPU_MODE_LONGEST: return ShardRule{0, h, Chain::Position, false, false};
+    case ACGPU_MODE_WHOLEWORD:
+        // not fold-consistent: the String loop mixes folded and raw lookups (sequential); the Readable loop folds in every
+        // lookup: the pipeline over the folded tables, or the WholeWordLongest walk where folded keywords hold non-word units
+        if (t.fold_consistent || (readable && t.fold_clean)) return ShardRule{1, m + 1, Chain::None, false, true};
+        return readable ? ShardRule{1, m + 1, Chain::Position, false, false} : ShardRule{1, m + 1, Chain::None, true, false};
+    case ACGPU_MODE_WWLONGEST: // (not fold-consistent: only the Set class's String loop mixes folded and raw lookups)
+        return ShardRule{1, m + 1, Chain::Position, !t.fold_consistent && record_kind == ACGPU_REC_SET && !readable, false};
+    default: return ShardRule{};
+    }
+}
+
+int64_t piece_entry(const ShardRule &r, int64_t chain, int64_t origin, uint64_t own_begin) {
+    const int64_t rel = std::max<int64_t>(0, chain - origin); // (a restart left of the buffer restricts nothing more than its start)
+    return r.chain == Chain::Restart ? rel : std::max<int64_t>(rel, (int64_t)own_begin);
+}
+
+int64_t piece_exit(const ShardRule &r, int64_t entry, uint64_t own_end, const acgpu_shard *sh, uint64_t n) {
+    if (r.chain == Chain::Restart) return sh && n ? sh->chain_exit : entry; // (no record: the restart that came in)
+    if (r.chain == Chain::Position && sh) return sh->chain_exit;
+    return std::max<int64_t>(entry, (int64_t)own_end);
+}
 
 // acgpu_match_u16 on a long haystack, pipelined: the text goes to the device in chunks -- worker threads copy the caller's
 // (pageable) memory into a ring of pinned staging buffers and enqueue the DMA on a copy stream -- while the chunks that have
@@ -2079,6 +2106,8 @@ int end_ticket(const acgpu_automaton *ca, acgpu_ticket *ticket, uint64_t *n_out,
 // the text (the share plus its halos), of which [own_lo, own_hi) is owned; positions in the records and in *chain are
 // relative to the buffer.
 constexpr uint64_t kHostChunkUnits = 1ull << 24; // 32 MiB per chunk
+
+bool one_piece(const ShardRule &r, const HostTables &t) { return r.sequential || (uint64_t)t.max_len + 2 >= kHostChunkUnits; }
 
 // The CPUs of the NUMA node a device hangs on (/sys/bus/pci/devices/<bdf>/numa_node, /sys/devices/system/node/node<N>/cpulist):
 // the threads that copy a share's text into pinned memory run there, so that on a two-socket host eight devices are fed by both
@@ -2126,7 +2155,7 @@ static bool device_numa_cpus(int dev, cpu_set_t *set) {
 int scan_host_range(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack, uint64_t n_units, uint64_t lo, uint64_t hi,
                     uint64_t own_lo, uint64_t own_hi, int record_kind, uint64_t cap, uint64_t *n_out, int64_t *chain_io,
                     void *d_out) {
-    const HostTables &t = a->t;
+    const ShardRule rule = shard_rule(a->t, record_kind, false);
     const uint64_t C = kHostChunkUnits;
     const uint64_t nb = hi - lo; // units in the device buffer
     const uint32_t n_chunks = (uint32_t)((nb + C - 1) / C);
@@ -2210,8 +2239,6 @@ int scan_host_range(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack
         for (auto &th : pool) if (th.joinable()) th.join();
     };
     // consumer: shard k once the chunks its right halo reaches into have arrived (the chunks before a shard always have)
-    const uint64_t right = (t.mode == ACGPU_MODE_WHOLEWORD || t.mode == ACGPU_MODE_WWLONGEST) ? (uint64_t)t.max_len + 1
-                           : (t.mode == ACGPU_MODE_LONGEST ? (t.max_len ? t.max_len - 1 : 0) : 0);
     uint64_t total = 0;
     int64_t chain = chain_io ? *chain_io : 0;
     uint32_t waited = 0; // chunks whose arrival the compute stream already waits for
@@ -2219,7 +2246,7 @@ int scan_host_range(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack
     for (uint32_t k = 0; k < n_chunks && result == ACGPU_OK; ++k) {
         const uint64_t c0 = std::max<uint64_t>((uint64_t)k * C, ob), c1 = std::min<uint64_t>({nb, (uint64_t)(k + 1) * C, oe});
         if (c0 >= c1) continue; // a chunk of halo units only
-        const uint32_t need = (uint32_t)std::min<uint64_t>(n_chunks, (std::min<uint64_t>(nb, c1 + right) + C - 1) / C); // chunks [0, need)
+        const uint32_t need = (uint32_t)std::min<uint64_t>(n_chunks, (std::min<uint64_t>(nb, c1 + rule.right) + C - 1) / C); // chunks [0, need)
         for (; waited < need && result == ACGPU_OK; ++waited) {
             while (!ready[waited].load(std::memory_order_acquire)) {
                 if (worker_rc.load() != ACGPU_OK) { result = worker_rc.load(); break; }
@@ -2235,7 +2262,8 @@ int scan_host_range(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack
         sh.own_end = c1;
         sh.text_begin = lo == 0 ? 1 : 0;
         sh.text_end = (sh.n_units == nb && hi == n_units) ? 1 : 0;
-        sh.chain_entry = t.mode == ACGPU_MODE_SHORTEST ? chain : std::max<int64_t>(chain, (int64_t)c0);
+        const int64_t entry = piece_entry(rule, chain, 0, c0);
+        sh.chain_entry = entry;
         uint64_t n_k = 0;
         const uint64_t room = total < cap ? cap - total : 0;
         rc = match_shard(a, d, &sh, record_kind, (char *)d_out + std::min(total, cap) * (uint64_t)record_kind, room, &n_k, stream, nullptr);
@@ -2244,8 +2272,7 @@ int scan_host_range(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack
             break;
         }
         total += n_k; // (beyond cap: the remaining shards only count)
-        if (t.mode == ACGPU_MODE_SHORTEST) chain = n_k ? sh.chain_exit : chain;
-        else chain = sh.chain_exit;
+        chain = piece_exit(rule, entry, c1, &sh, n_k);
     }
     if (result != ACGPU_OK) worker_rc.store(result); // (stops the producers)
     join_all();
@@ -2345,8 +2372,6 @@ int acgpu_match_u16(const acgpu_automaton *ca, const uint16_t *haystack, uint64_
     int rc = device_for_call(a, &d);
     if (rc) return rc;
     std::lock_guard<std::mutex> lock(d->mu); // staging buffers are part of the per-device scratch pool
-    // long haystacks of the families whose shards chain: the pipelined form (the loops that only exist as a sequential kernel
-    // over the whole text -- WholeWord / WholeWordLongestSet with a fold-inconsistent table -- take the plain one)
     const HostTables &t = a->t;
     // short haystacks: one launch, no copies (tunable tile_debug bit 2^41, or a kernel form forced by "force_kernel": the
     // general path -- for A/B, and for the tests that run the scan kernels on the short edge-case inputs)
@@ -2356,10 +2381,10 @@ int acgpu_match_u16(const acgpu_automaton *ca, const uint16_t *haystack, uint64_
         rc = match_small(a, *d, haystack, n_units, record_kind, out, cap, n_out, &handled);
         if (rc != ACGPU_OK || handled) return rc;
     }
-    const bool sequential_only = (t.mode == ACGPU_MODE_WHOLEWORD && !t.fold_consistent) ||
-                                 (t.mode == ACGPU_MODE_WWLONGEST && !t.fold_consistent && record_kind == ACGPU_REC_SET);
-    if (n_units >= 2 * kHostChunkUnits && !sequential_only && d->inflight == 0 && !(tunables().tile_debug & 33554432) &&
-        (uint64_t)t.max_len + 2 < kHostChunkUnits)
+    // long haystacks: the pipelined form, unless the text is one piece (the loops that only exist as a sequential kernel over
+    // the whole text -- WholeWord / WholeWordLongestSet with a fold-inconsistent table -- take the plain one)
+    if (n_units >= 2 * kHostChunkUnits && !one_piece(shard_rule(t, record_kind, false), t) && d->inflight == 0 &&
+        !(tunables().tile_debug & 33554432))
         return match_u16_pipelined(a, *d, haystack, n_units, record_kind, out, cap, n_out);
     if ((rc = d->stage_hay.ensure(n_units * 2 + 16))) return rc;
     if ((rc = d->stage_out.ensure(cap * (uint64_t)record_kind + 16))) return rc;

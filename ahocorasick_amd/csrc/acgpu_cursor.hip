@@ -53,8 +53,6 @@ __global__ void k_cursor_page(const int32_t *__restrict__ src, int32_t *__restri
     }
 }
 
-constexpr uint64_t kWholeTextHalo = 1ull << 24; // halos this long (keywords of ~2^24 units): the text is one piece
-
 } // namespace
 
 struct acgpu_cursor {
@@ -63,11 +61,11 @@ struct acgpu_cursor {
     const uint16_t *hay = nullptr;
     uint64_t n = 0;
     int record_kind = 0;
-    bool whole = false;  // the text is scanned as ONE piece (sequential-only loops)
+    bool whole = false;  // the text is scanned as ONE piece (one_piece)
     bool failed = false; // a next failed: only close is valid
     // the scan
     uint64_t pos = 0;      // owned units [0, pos) have been scanned
-    int64_t chain = 0;     // LONGEST / WWLONGEST / SHORTEST: the chain's entry into the next piece (haystack coordinates)
+    int64_t chain = 0;     // the chain's entry into the next piece (haystack coordinates)
     uint64_t piece = 0;    // owned units of the next piece (before the density cap)
     uint64_t seen_records = 0, seen_units = 0; // what the pieces scanned so far yielded (the density estimate)
     // the reservoir: records [res_r, res_n) of the current piece are not handed out yet; positions relative to res_base
@@ -151,14 +149,9 @@ int scan_whole(acgpu_cursor *c, DeviceState &d) {
 int scan_piece(acgpu_cursor *c, DeviceState &d) {
     if (c->whole) return scan_whole(c, d);
     acgpu_automaton *a = c->a;
-    const HostTables &t = a->t;
+    const ShardRule rule = shard_rule(a->t, c->record_kind, false);
     const uint64_t rk = (uint64_t)c->record_kind;
     const uint64_t budget_recs = std::max<uint64_t>(budget_bytes() / rk, 1);
-    const bool ww = t.mode == ACGPU_MODE_WHOLEWORD || t.mode == ACGPU_MODE_WWLONGEST;
-    const uint64_t ml = t.max_len;
-    const uint64_t left = (t.mode == ACGPU_MODE_ALL || t.mode == ACGPU_MODE_SHORTEST) ? (ml ? ml - 1 : 0) : (ww ? 1 : 0);
-    const uint64_t right = ww ? ml + 1 : (t.mode == ACGPU_MODE_LONGEST ? (ml ? ml - 1 : 0) : 0);
-    const bool chained = t.mode == ACGPU_MODE_LONGEST || t.mode == ACGPU_MODE_SHORTEST || t.mode == ACGPU_MODE_WWLONGEST;
     // the size: the next step of the ramp, capped so that the density seen so far fills at most half the reservoir budget
     uint64_t size = std::min<uint64_t>(c->piece, c->n - c->pos);
     if (c->seen_records && c->seen_units) {
@@ -168,7 +161,7 @@ int scan_piece(acgpu_cursor *c, DeviceState &d) {
     }
     for (;;) {
         const uint64_t own_lo = c->pos, own_hi = own_lo + size;
-        const uint64_t lo = own_lo - std::min(left, own_lo), hi = std::min<uint64_t>(c->n, own_hi + right);
+        const uint64_t lo = own_lo - std::min(rule.left, own_lo), hi = std::min<uint64_t>(c->n, own_hi + rule.right);
         // predicted records: room for them (within the budget) before the scan, so that a steady text is not scanned twice
         if (c->seen_units) {
             const double pred = (double)c->seen_records / (double)c->seen_units * (double)size;
@@ -179,8 +172,7 @@ int scan_piece(acgpu_cursor *c, DeviceState &d) {
             int rc = grow_reservoir(c, std::min<uint64_t>(budget_recs, std::max<uint64_t>(size, 4096)) * rk);
             if (rc) return rc;
         }
-        int64_t chain = 0;
-        if (chained) chain = std::max<int64_t>(0, c->chain - (int64_t)lo);
+        int64_t chain = c->chain - (int64_t)lo; // (buffer relative: scan_host_range takes each shard's entry from it)
         uint64_t cnt = 0;
         int rc = scan_host_range(a, d, c->hay, c->n, lo, hi, own_lo, own_hi, c->record_kind, c->res_bytes / rk, &cnt, &chain, c->res);
         c->st.pieces++;
@@ -199,7 +191,7 @@ int scan_piece(acgpu_cursor *c, DeviceState &d) {
             continue;
         }
         if (rc) return rc;
-        if (chained) c->chain = chain + (int64_t)lo;
+        c->chain = chain + (int64_t)lo;
         c->res_n = cnt;
         c->res_r = 0;
         c->res_base = (int32_t)lo;
@@ -281,9 +273,7 @@ int acgpu_cursor_open(const acgpu_automaton *ca, const uint16_t *haystack, uint6
     c->n = n_units;
     c->record_kind = record_kind;
     const HostTables &t = a->t;
-    c->whole = (t.mode == ACGPU_MODE_WHOLEWORD && !t.fold_consistent) ||
-               (t.mode == ACGPU_MODE_WWLONGEST && !t.fold_consistent && record_kind == ACGPU_REC_SET) ||
-               (uint64_t)t.max_len + 2 >= kWholeTextHalo;
+    c->whole = one_piece(shard_rule(t, record_kind, false), t);
     c->piece = (uint64_t)std::max<int64_t>(1, tunables().cursor_first_piece.load(std::memory_order_relaxed));
     try {
         std::lock_guard<std::mutex> l(a->mu);

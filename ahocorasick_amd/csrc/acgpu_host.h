@@ -221,6 +221,31 @@ struct acgpu_automaton {
 
 namespace acgpu {
 
+// How a text is cut into shards for one call (shard_rule, acgpu_api.hip): the facts of the automaton's family that every host
+// entry which scans a text piece by piece needs.
+enum class Chain : uint8_t {
+    None,     // ALL, WHOLEWORD: nothing passes from piece to piece
+    Position, // LONGEST, WWLONGEST, the WholeWord walk: the position the scan goes on from, at least the piece's own_begin
+    Restart,  // SHORTEST: where matching last restarted -- it passes through a piece that reports nothing
+};
+
+struct ShardRule {
+    uint64_t left = 0, right = 0; // units of left context and of right halo a piece needs
+    Chain chain = Chain::None;
+    bool sequential = false;      // only the sequential kernel over the whole text exists
+    bool all_pipeline = false;    // the ALL / WholeWord enqueued pipeline (enqueue_all; over the folded tables if not fold-consistent)
+};
+
+// readable: the call stands for match(Readable, ...) (acgpu_stream_feed)
+ShardRule shard_rule(const HostTables &t, int record_kind, bool readable);
+// The chain's entry into a piece, buffer relative: `chain` and `origin` (the buffer's first unit) in the caller's coordinates.
+int64_t piece_entry(const ShardRule &r, int64_t chain, int64_t origin, uint64_t own_begin);
+// The chain's exit from a piece that was entered at `entry`, buffer relative: sh = the shard as scanned, which reported n
+// records; nullptr = nothing was scanned.
+int64_t piece_exit(const ShardRule &r, int64_t entry, uint64_t own_end, const acgpu_shard *sh, uint64_t n);
+// A host haystack is scanned as one piece: only the whole-text kernel exists, or the halos would not fit a host chunk.
+bool one_piece(const ShardRule &r, const HostTables &t);
+
 // The scratch pool of `a` on the CURRENT HIP device (created and the tables uploaded on first use).  lane > 0: a further,
 // independent pool on the same device (its own stream), for multi-device calls that list a device more than once.
 int device_for_call(acgpu_automaton *a, DeviceState **d, int lane = 0);

@@ -51,24 +51,6 @@ __global__ void k_record_bound(const int32_t *recs, uint64_t n, int cols, int fi
     *out = lo;
 }
 
-struct Halo {
-    uint64_t left, right;
-};
-
-Halo halos_for(const HostTables &t) {
-    const uint64_t m = t.max_len;
-    switch (t.mode) {
-    case ACGPU_MODE_WHOLEWORD:
-    case ACGPU_MODE_WWLONGEST: return {1, m + 1};
-    case ACGPU_MODE_LONGEST: return {0, m ? m - 1 : 0};
-    default: return {m ? m - 1 : 0, 0}; // ALL, SHORTEST
-    }
-}
-
-bool chain_family(const HostTables &t) {
-    return t.mode == ACGPU_MODE_LONGEST || t.mode == ACGPU_MODE_SHORTEST || t.mode == ACGPU_MODE_WWLONGEST;
-}
-
 uint64_t round_up8(uint64_t v) { return (v + 7) & ~7ull; }
 
 // One share of the haystack on one device.  All positions are relative to the share's device buffer.
@@ -144,8 +126,9 @@ int record_bound(Share &s, const void *recs, uint64_t n, int record_kind, int fi
 // Speculation per family (what the scan phase assumed): LONGEST / WWLONGEST the scan enters at the share's first unit;
 // SHORTEST no restart position restricts anything.
 int repair_chains(acgpu_automaton *a, std::vector<Share> &sh, int record_kind) {
-    const HostTables &t = a->t;
-    const int64_t halo = t.max_len ? (int64_t)t.max_len - 1 : 0;
+    const ShardRule rule = shard_rule(a->t, record_kind, false);
+    const bool restart = rule.chain == Chain::Restart;
+    const int64_t halo = (int64_t)rule.left; // SHORTEST: how far left of a share a match that ends in it can begin
     // share 0's exit is the speculation's (its entry is the text's)
     for (size_t i = 0; i < sh.size(); ++i) {
         Share &s = sh[i];
@@ -154,21 +137,16 @@ int repair_chains(acgpu_automaton *a, std::vector<Share> &sh, int record_kind) {
         s.repaired = false;
         s.keep_from = 0;
         s.n_win = 0;
-        if (t.mode == ACGPU_MODE_SHORTEST) {
-            // the state: the end of the last match reported so far (nothing reported: what came in)
-            // (share 0 scanned from the CALLER's entry, which its chain_exit hands on when it reports nothing: always the truth)
-            s.exit_valid = s.n_spec > 0 || i == 0;
-            s.exit_rel = s.spec_exit - (int64_t)s.own_end;
-        } else {
-            s.exit_valid = true;
-            s.exit_rel = s.spec_exit - (int64_t)s.own_end;
-        }
+        // SHORTEST: the state is the end of the last match reported so far (nothing reported: what came in -- share 0 scanned
+        // from the CALLER's entry, which its chain_exit hands on when it reports nothing: always the truth)
+        s.exit_valid = !restart || s.n_spec > 0 || i == 0;
+        s.exit_rel = s.spec_exit - (int64_t)s.own_end;
         if (i == 0) continue;
         const Share &p = sh[i - 1];
         // the true entry, in this share's coordinates (the previous share's own_end is this share's own_begin)
         int64_t entry;
         bool differs;
-        if (t.mode == ACGPU_MODE_SHORTEST) {
+        if (restart) {
             if (!p.exit_valid) continue; // nothing has been reported yet: the speculation is the truth
             entry = (int64_t)s.own_begin + p.exit_rel;
             differs = entry > (int64_t)s.own_begin - halo; // a restart left of every match that can end in this share forbids nothing
@@ -185,7 +163,7 @@ int repair_chains(acgpu_automaton *a, std::vector<Share> &sh, int record_kind) {
             differs = entry > (int64_t)s.own_begin;
             if (!differs) continue;
         }
-        const int64_t spec_entry = t.mode == ACGPU_MODE_SHORTEST ? 0 : (int64_t)s.own_begin;
+        const int64_t spec_entry = piece_entry(rule, 0, 0, s.own_begin);
         uint64_t w = 4096;
         for (;;) {
             // the window reaches beyond the true entry (a match of the previous share may cover this share's head)
@@ -199,7 +177,7 @@ int repair_chains(acgpu_automaton *a, std::vector<Share> &sh, int record_kind) {
                 s.repaired = true;
                 s.n_win = n_t;
                 s.keep_from = s.n_spec;
-                if (t.mode == ACGPU_MODE_SHORTEST) {
+                if (restart) {
                     s.exit_valid = true;
                     s.exit_rel = (n_t ? ex_t : entry) - (int64_t)s.own_end;
                 } else {
@@ -209,7 +187,7 @@ int repair_chains(acgpu_automaton *a, std::vector<Share> &sh, int record_kind) {
             }
             if ((rc = scan_window(a, s, w_end, spec_entry, s.d->multi_tail, record_kind, &n_s, &ex_s))) return rc;
             bool same;
-            if (t.mode == ACGPU_MODE_SHORTEST) {
+            if (restart) {
                 // a restart at or left of w_end - halo restricts nothing that ends behind the window
                 const int64_t floor = (int64_t)w_end - halo;
                 const int64_t st_t = std::max<int64_t>(n_t ? ex_t : entry, floor), st_s = std::max<int64_t>(n_s ? ex_s : -1, floor);
@@ -221,13 +199,13 @@ int repair_chains(acgpu_automaton *a, std::vector<Share> &sh, int record_kind) {
                 // the speculation's records behind the window: LONGEST / WWLONGEST own by their first unit (start >= w_end),
                 // SHORTEST by their last (end > w_end)
                 uint64_t idx = 0;
-                if (t.mode == ACGPU_MODE_SHORTEST) rc = record_bound(s, s.spec, s.n_spec, record_kind, 1, (int64_t)w_end, true, &idx);
+                if (restart) rc = record_bound(s, s.spec, s.n_spec, record_kind, 1, (int64_t)w_end, true, &idx);
                 else rc = record_bound(s, s.spec, s.n_spec, record_kind, 0, (int64_t)w_end, false, &idx);
                 if (rc) return rc;
                 s.repaired = true;
                 s.n_win = n_t;
                 s.keep_from = idx;
-                if (t.mode == ACGPU_MODE_SHORTEST && idx == s.n_spec) { // no speculative record is left: the window's last one, or what came in
+                if (restart && idx == s.n_spec) { // no speculative record is left: the window's last one, or what came in
                     s.exit_valid = true;
                     s.exit_rel = (n_t ? ex_t : entry) - (int64_t)s.own_end;
                 }
@@ -373,32 +351,29 @@ int acgpu_match_u16_multi(const acgpu_automaton *ca, const uint16_t *haystack, u
     int rc = check_devices(devices, n_devices);
     if (rc) return rc;
     acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
-    const HostTables &t = a->t;
+    const ShardRule rule = shard_rule(a->t, record_kind, false);
     *n_out = 0;
     DeviceRestore restore;
     // the loops that only exist as a sequential kernel over the whole text (word matchers over a table that is not
     // fold-consistent), and texts too short to be worth cutting: one device, the single-device entry
-    const bool sequential_only = (t.mode == ACGPU_MODE_WHOLEWORD && !t.fold_consistent) ||
-                                 (t.mode == ACGPU_MODE_WWLONGEST && !t.fold_consistent && record_kind == ACGPU_REC_SET);
     // A share has to be worth its fixed costs -- a host thread, a staging ring, two extra synchronisations --: 2^22 units (8 MiB)
     // at least, below that fewer devices or the single-device entry (a 100 KB string under -Dacgpu.devices=0..7 is ONE call on
     // one device).  Tunable multi_min_share: the tests cut texts of a few thousand units.
     const uint64_t min_share = (uint64_t)std::max<int64_t>(8, tunables().multi_min_share);
-    const int K = sequential_only ? 1 : (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_devices, n_units / min_share));
+    const int K = rule.sequential ? 1 : (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_devices, n_units / min_share));
     if (K == 1) {
         if ((rc = set_device(devices[0]))) return rc;
         return acgpu_match_u16(ca, haystack, n_units, record_kind, out, cap, n_out);
     }
-    const Halo h = halos_for(t);
     const std::vector<int> lanes = lanes_of(devices, n_devices);
     std::vector<Share> sh((size_t)K);
     std::vector<uint64_t> v0((size_t)K), v1((size_t)K), lo((size_t)K), hi((size_t)K);
     for (int i = 0; i < K; ++i) {
         lo[i] = i == 0 ? 0 : ((uint64_t)i * n_units / (uint64_t)K) & ~7ull;
         hi[i] = i == K - 1 ? n_units : ((uint64_t)(i + 1) * n_units / (uint64_t)K) & ~7ull;
-        const uint64_t lpad = round_up8(h.left);
+        const uint64_t lpad = round_up8(rule.left);
         v0[i] = lo[i] > lpad ? lo[i] - lpad : 0; // (lo and the pad are multiples of 8: the view and the owned range start 16-byte aligned)
-        v1[i] = std::min<uint64_t>(n_units, hi[i] + h.right);
+        v1[i] = std::min<uint64_t>(n_units, hi[i] + rule.right);
         sh[i].device = devices[i];
         sh[i].lane = lanes[i];
     }
@@ -462,7 +437,7 @@ int acgpu_match_u16_multi(const acgpu_automaton *ca, const uint16_t *haystack, u
             return ACGPU_OK;
         }
     });
-    if (rc == ACGPU_OK && chain_family(t)) rc = repair_chains(a, sh, record_kind);
+    if (rc == ACGPU_OK && rule.chain != Chain::None) rc = repair_chains(a, sh, record_kind);
     uint64_t total = 0;
     if (rc == ACGPU_OK) {
         for (auto &s : sh) total += s.n_final();
@@ -565,7 +540,7 @@ int acgpu_match_device_allgather(const acgpu_automaton *ca, acgpu_comm *c, acgpu
     if (!ca || !c || !shards || !d_gather || !counts) return ACGPU_E_INVALID;
     if (record_kind != ACGPU_REC_SET && record_kind != ACGPU_REC_MAP) return ACGPU_E_INVALID;
     acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
-    const HostTables &t = a->t;
+    const ShardRule rule = shard_rule(a->t, record_kind, false);
     const int K = (int)c->devices.size();
     const uint64_t slot_bytes = acgpu_gather_slot_bytes(gcap, record_kind);
     for (int i = 0; i < K; ++i) {
@@ -577,7 +552,6 @@ int acgpu_match_device_allgather(const acgpu_automaton *ca, acgpu_comm *c, acgpu
     int rc = ACGPU_OK;
     auto slot_of = [&](int i) { return (char *)d_gather[i] + (uint64_t)i * slot_bytes; };
     bool over = false;
-    const bool async_family = t.mode == ACGPU_MODE_ALL || (t.mode == ACGPU_MODE_WHOLEWORD && t.fold_consistent);
     std::vector<DeviceState *> pools((size_t)K, nullptr);
     for (int i = 0; i < K; ++i) {
         if ((rc = set_device(c->devices[i]))) return rc;
@@ -585,7 +559,7 @@ int acgpu_match_device_allgather(const acgpu_automaton *ca, acgpu_comm *c, acgpu
     }
     std::vector<acgpu_ticket *> tickets((size_t)K, nullptr);
     std::vector<acgpu_shard> local(shards, shards + K);
-    if (async_family) {
+    if (rule.all_pipeline) {
         // ---- AhoCorasick / WholeWord: scan -> [header | records] of the device's own slot, enqueued on every device without a
         // host round trip; the header is written by the scan's last kernel in stream order, the gather follows on the same stream
         for (int i = 0; i < K && rc == ACGPU_OK; ++i) {
@@ -617,13 +591,13 @@ int acgpu_match_device_allgather(const acgpu_automaton *ca, acgpu_comm *c, acgpu
             s.text_begin = shards[i].text_begin;
             s.text_end = shards[i].text_end;
         }
-        const bool chains = chain_family(t) && K > 1;
+        const bool chains = rule.chain != Chain::None && K > 1;
         rc = on_all_shares(sh, [&](size_t i) -> int {
             Share &s = sh[i];
             acgpu_shard one = shards[i];
             one.d_result = nullptr;
             // speculation (see repair_chains); share 0 takes the caller's entry
-            if (chain_family(t)) one.chain_entry = i == 0 ? shards[0].chain_entry : (t.mode == ACGPU_MODE_SHORTEST ? 0 : (int64_t)s.own_begin);
+            if (rule.chain != Chain::None && i > 0) one.chain_entry = piece_entry(rule, 0, 0, s.own_begin);
             uint64_t n = 0;
             int r = match_shard(a, *s.d, &one, record_kind, slot_of((int)i) + 16, gcap, &n, s.stream, profs ? &profs[i] : nullptr);
             s.spec = slot_of((int)i) + 16;

@@ -42,30 +42,13 @@ struct FeedPlan {
     uint64_t total, own_begin, own_end, keep_from;
 };
 
-int scan_mode(const HostTables &t) {
-    // what the scan carries between feeds: a WHOLEWORD automaton whose folded keywords hold non-word units is scanned by the
-    // WholeWordLongest walk (match_shard), which hands the position of its next word start on
-    return (t.mode == ACGPU_MODE_WHOLEWORD && !t.fold_consistent && !t.fold_clean) ? ACGPU_MODE_WWLONGEST : t.mode;
-}
-
-FeedPlan plan_feed(const HostTables &t, uint64_t n_carry, uint64_t n_units, uint64_t own_from, uint64_t carry_pos, bool final) {
-    const int mode = scan_mode(t);
+FeedPlan plan_feed(const ShardRule &rule, uint64_t n_carry, uint64_t n_units, uint64_t own_from, uint64_t carry_pos, bool final) {
     FeedPlan p{};
     p.total = n_carry + n_units;
     p.own_begin = own_from - carry_pos;
-    p.own_end = p.total;
-    if (mode == ACGPU_MODE_ALL || mode == ACGPU_MODE_SHORTEST) {
-        const uint64_t halo = t.max_len > 0 ? t.max_len - 1 : 0;
-        p.keep_from = p.total > halo ? p.total - halo : 0;
-    } else if (mode == ACGPU_MODE_WHOLEWORD || mode == ACGPU_MODE_WWLONGEST) {
-        const uint64_t hold = (uint64_t)t.max_len + 1; // a word / walk that starts here may still grow
-        if (!final) p.own_end = std::max<uint64_t>(p.own_begin, p.total > hold ? p.total - hold : 0);
-        p.keep_from = p.own_end > 0 ? p.own_end - 1 : 0; // one unit of left context
-    } else {
-        const uint64_t halo = t.max_len > 0 ? t.max_len - 1 : 0;
-        if (!final) p.own_end = std::max<uint64_t>(p.own_begin, p.total > halo ? p.total - halo : 0);
-        p.keep_from = p.own_end;
-    }
+    // the right halo is held back until a later chunk (or the end) brings it; the left context is carried
+    p.own_end = final ? p.total : std::max<uint64_t>(p.own_begin, p.total > rule.right ? p.total - rule.right : 0);
+    p.keep_from = p.own_end - std::min<uint64_t>(rule.left, p.own_end);
     return p;
 }
 
@@ -167,7 +150,7 @@ struct acgpu_stream {
     std::vector<uint16_t> carry; // units a later chunk can still change the answer for (context + held back)
     uint64_t carry_pos = 0;      // global position of carry[0]
     uint64_t own_from = 0;       // global position of the first unit no earlier feed has owned
-    uint64_t chain_entry = 0;    // LONGEST: global position at which the greedy chain continues
+    int64_t chain_entry = 0;     // the chain families: where the chain enters the next feed (global; piece_entry)
     bool finished = false;
     std::vector<uint16_t> buf;
     // ---- pipelined form ----
@@ -215,12 +198,12 @@ namespace {
 // `base`, to out[n_done ..); *n_out = records so far (beyond cap: a count only)
 int scan_slot(acgpu_stream *s, Slot &sl, int record_kind, void *out, uint64_t cap, uint64_t n_done, int64_t base, uint64_t *n_out) {
     acgpu_automaton *a = s->a;
-    const HostTables &t = a->t;
-    const int mode = scan_mode(t);
+    const ShardRule rule = shard_rule(a->t, record_kind, /*readable=*/true);
     const FeedPlan &p = sl.plan;
     const int si = (int)(&sl - s->slot);
     *n_out = n_done;
-    uint64_t chain_exit = mode == ACGPU_MODE_SHORTEST ? s->chain_entry : std::max<uint64_t>(s->chain_entry, sl.carry_pos + p.own_end);
+    const int64_t entry = piece_entry(rule, s->chain_entry, (int64_t)sl.carry_pos, p.own_begin);
+    int64_t chain_exit = piece_exit(rule, entry, p.own_end, nullptr, 0);
     if (p.own_end > p.own_begin) {
         DeviceState *d = nullptr;
         int rc = device_for_call(a, &d);
@@ -246,8 +229,7 @@ int scan_slot(acgpu_stream *s, Slot &sl, int record_kind, void *out, uint64_t ca
             sh.own_end = p.own_end;
             sh.text_begin = sl.carry_pos == 0 ? 1 : 0;
             sh.text_end = sl.final ? 1 : 0;
-            sh.chain_entry = (int64_t)(s->chain_entry > sl.carry_pos ? s->chain_entry - sl.carry_pos : 0);
-            if (mode != ACGPU_MODE_SHORTEST) sh.chain_entry = std::max<int64_t>(sh.chain_entry, (int64_t)p.own_begin);
+            sh.chain_entry = entry;
             rc = match_shard(a, *d, &sh, record_kind, s->b.out_dev.p, scap, &n, nullptr, nullptr, /*readable=*/true);
             if (rc == ACGPU_E_OVERFLOW) {
                 scap = n + n / 8 + 16;
@@ -257,8 +239,7 @@ int scan_slot(acgpu_stream *s, Slot &sl, int record_kind, void *out, uint64_t ca
             break;
         }
         if (trace) fprintf(stderr, ", scanned after %.0f us (%llu records)\n", since(), (unsigned long long)n);
-        if (mode == ACGPU_MODE_LONGEST || mode == ACGPU_MODE_WWLONGEST) chain_exit = sl.carry_pos + (uint64_t)sh.chain_exit;
-        if (mode == ACGPU_MODE_SHORTEST && n) chain_exit = sl.carry_pos + (uint64_t)sh.chain_exit;
+        chain_exit = piece_exit(rule, entry, p.own_end, &sh, n);
         if (n) {
             // positions relative to `base` (the final feed hands over two chunks' records under one base)
             const int64_t delta = (int64_t)sl.carry_pos - base;
@@ -305,7 +286,7 @@ int scan_slot(acgpu_stream *s, Slot &sl, int record_kind, void *out, uint64_t ca
             *n_out = n_done + n;
         }
     }
-    s->chain_entry = chain_exit;
+    s->chain_entry = (int64_t)sl.carry_pos + chain_exit;
     sl.pending = false;
     return ACGPU_OK;
 }
@@ -339,7 +320,6 @@ int feed_pipelined(acgpu_stream *s, const uint16_t *units, uint64_t n_units, int
                    uint64_t *n_out, int64_t *base) {
     acgpu_automaton *a = s->a;
     if (!a) return ACGPU_E_INVALID; // (its automaton has been freed)
-    const HostTables &t = a->t;
     *n_out = 0;
     { const int drc = check_feed_device(s); if (drc) return drc; }
     if (s->redeliver) { // the same feed again, with the capacity the first call reported: its chunk was consumed then
@@ -374,7 +354,7 @@ int feed_pipelined(acgpu_stream *s, const uint16_t *units, uint64_t n_units, int
     Slot &sl = s->slot[s->cur];
     Slot &prev = s->slot[1 - s->cur];
     const int si = s->cur;
-    const FeedPlan p = plan_feed(t, n_carry, n_units, s->own_from, s->carry_pos, final != 0);
+    const FeedPlan p = plan_feed(shard_rule(a->t, record_kind, /*readable=*/true), n_carry, n_units, s->own_from, s->carry_pos, final != 0);
     int rc;
     if (s->b.pin_bytes[si] < p.total * 2 + 64) {
         if (s->b.pin[si]) (void)hipHostFree(s->b.pin[si]);
@@ -516,9 +496,8 @@ int acgpu_stream_feed(acgpu_stream *s, const uint16_t *units, uint64_t n_units, 
     if (!s->a) return ACGPU_E_INVALID; // (its automaton has been freed)
     if (s->pipelined) return feed_pipelined(s, units, n_units, final, record_kind, out, cap, n_out, base);
     acgpu_automaton *a = s->a;
-    const HostTables &t = a->t;
-    const int mode = scan_mode(t);
-    const FeedPlan p = plan_feed(t, s->carry.size(), n_units, s->own_from, s->carry_pos, final != 0);
+    const ShardRule rule = shard_rule(a->t, record_kind, /*readable=*/true);
+    const FeedPlan p = plan_feed(rule, s->carry.size(), n_units, s->own_from, s->carry_pos, final != 0);
     const uint64_t total = p.total, own_begin = p.own_begin, own_end = p.own_end, keep_from = p.keep_from;
     if (total >= (1ull << 31)) return ACGPU_E_INVALID;
     *n_out = 0;
@@ -530,7 +509,8 @@ int acgpu_stream_feed(acgpu_stream *s, const uint16_t *units, uint64_t n_units, 
     }
     if (!s->carry.empty()) std::memcpy(s->buf.data(), s->carry.data(), s->carry.size() * 2);
     if (n_units) std::memcpy(s->buf.data() + s->carry.size(), units, n_units * 2);
-    uint64_t chain_exit = mode == ACGPU_MODE_SHORTEST ? s->chain_entry : std::max<uint64_t>(s->chain_entry, s->carry_pos + own_end);
+    const int64_t entry = piece_entry(rule, s->chain_entry, (int64_t)s->carry_pos, own_begin);
+    int64_t chain_exit = piece_exit(rule, entry, own_end, nullptr, 0);
     if (own_end > own_begin) {
         DeviceState *d = nullptr;
         int rc = device_for_call(a, &d);
@@ -546,18 +526,15 @@ int acgpu_stream_feed(acgpu_stream *s, const uint16_t *units, uint64_t n_units, 
         sh.own_end = own_end;
         sh.text_begin = s->carry_pos == 0 ? 1 : 0;
         sh.text_end = final ? 1 : 0;
-        sh.chain_entry = (int64_t)(s->chain_entry > s->carry_pos ? s->chain_entry - s->carry_pos : 0);
-        if (mode != ACGPU_MODE_SHORTEST) sh.chain_entry = std::max<int64_t>(sh.chain_entry, (int64_t)own_begin);
+        sh.chain_entry = entry;
         rc = match_shard(a, *d, &sh, record_kind, d->stage_out.p, cap, n_out, nullptr, nullptr, /*readable=*/true);
         if (rc != ACGPU_OK) return rc; // ACGPU_E_OVERFLOW: nothing consumed, *n_out = capacity to retry with
         if (*n_out) HIP_TRY(hipMemcpy(out, d->stage_out.p, *n_out * (uint64_t)record_kind, hipMemcpyDeviceToHost));
-        if (mode == ACGPU_MODE_LONGEST || mode == ACGPU_MODE_WWLONGEST) chain_exit = s->carry_pos + (uint64_t)sh.chain_exit;
-        // SHORTEST: the last restart; an exit equal to the relative entry means "no match in this feed"
-        if (mode == ACGPU_MODE_SHORTEST && *n_out) chain_exit = s->carry_pos + (uint64_t)sh.chain_exit;
+        chain_exit = piece_exit(rule, entry, own_end, &sh, *n_out);
     }
     // commit
     s->own_from = s->carry_pos + own_end;
-    s->chain_entry = chain_exit;
+    s->chain_entry = (int64_t)s->carry_pos + chain_exit;
     s->carry.assign(s->buf.begin() + (ptrdiff_t)keep_from, s->buf.end());
     s->carry_pos += keep_from;
     s->finished = final != 0;
