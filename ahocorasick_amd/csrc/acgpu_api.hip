@@ -296,10 +296,30 @@ int close_call(CallRecord &r, CallForm form, const char *kname, uint64_t scanned
 
 // A call with nothing to scan: the device result says so, the slot is written here (no kernel will write it).
 int enqueue_empty(CallRecord &r, int64_t chain_exit) {
-    r.h_slot[0] = r.h_slot[1] = 0;
-    r.h_slot[2] = (unsigned long long)chain_exit;
+    r.h_slot[kSlotCount] = r.h_slot[kSlotFlag] = 0;
+    r.h_slot[kSlotExit] = (unsigned long long)chain_exit;
     if (r.shard.d_result) HIP_TRY(hipMemsetAsync(r.shard.d_result, 0, sizeof(acgpu_device_result), r.stream));
     return close_call(r, CallForm::Complete, "", 0);
+}
+
+// The end of a call that ran on the host: the count and the chain exit from their device words into the record's slot (no
+// d_exit: the pipeline has put the exit there), and the wait.
+int close_host_run(CallRecord &r, const void *d_count, const void *d_exit, const char *kname, uint64_t scanned) {
+    HIP_TRY(hipMemcpyAsync(r.h_slot + kSlotCount, d_count, 8, hipMemcpyDeviceToHost, r.stream));
+    if (d_exit) HIP_TRY(hipMemcpyAsync(r.h_slot + kSlotExit, d_exit, 8, hipMemcpyDeviceToHost, r.stream));
+    HIP_TRY(hipStreamSynchronize(r.stream));
+    return close_call(r, CallForm::HostRun, kname, scanned);
+}
+
+// This call keeps words of its own (an exit position, a count, mark_chain's head and largest jump) in the first 64 bytes of
+// d.counter -- the first slot-counter line of enqueue_all's first set (word 0 = slot counter, word 1 = workgroup sum, the rest
+// of the 128-byte line is padding): the next ALL call must clear that set itself.  clear: the words are zeroed on the stream.
+int borrow_counter_line(DeviceState &d, hipStream_t stream, bool clear) {
+    int rc;
+    if ((rc = d.counter.ensure(64))) return rc;
+    if (clear) HIP_TRY(hipMemsetAsync(d.counter.p, 0, 64, stream));
+    d.cclean[0] = false;
+    return ACGPU_OK;
 }
 
 // ALL-mode pipeline on one shard, the form for texts with dense matches: see enqueue_all.
@@ -325,7 +345,6 @@ int enqueue_states(acgpu_automaton *a, DeviceState &d, CallRecord &r, uint32_t h
     const uint64_t chunks = (span + (1ull << S.chunk_log2) - 1) >> S.chunk_log2;
     S.n_waves = (uint32_t)((chunks + 63) / 64);
     S.n_chunks = (uint32_t)chunks;
-    if ((rc = d.counter.ensure(64))) return rc;
     if (tunables().tile_debug & (1ll << 40)) return ACGPU_E_NOMEM; // (tests: the allocation "fails", the caller falls back)
     if ((rc = d.statebuf.ensure((((size_t)S.n_waves * 64) << S.chunk_log2) * 4 + 64))) return rc;
     if ((rc = d.chunk_counts.ensure((size_t)S.n_chunks * 4))) return rc;
@@ -337,8 +356,7 @@ int enqueue_states(acgpu_automaton *a, DeviceState &d, CallRecord &r, uint32_t h
     S.d_out = r.d_out;
     S.cap = r.cap;
     S.grid = (int)std::min<uint64_t>((uint64_t)d.n_cu * (ac_states_lanes_per_cu() / 1024u), (S.n_waves + 15) / 16);
-    HIP_TRY(hipMemsetAsync(d.counter.p, 0, 64, stream)); // (word 1: the "redo" flag of the result -- never raised here)
-    d.cclean[0] = false; // (enqueue_all's first set of slot counters lives here)
+    if ((rc = borrow_counter_line(d, stream, /*clear=*/true))) return rc; // (word 1: the "redo" flag of the result -- never raised here)
     if (r.profiled) HIP_TRY(hipEventRecord(ev[0], stream));
     HIP_TRY(launch_ac_states(d.T, S, t.range_cls, stream));
     if (r.profiled) HIP_TRY(hipEventRecord(ev[1], stream));
@@ -355,8 +373,6 @@ int enqueue_states(acgpu_automaton *a, DeviceState &d, CallRecord &r, uint32_t h
 int collect(acgpu_automaton *a, DeviceState &d, CallRecord *r, uint64_t *n_out, acgpu_profile *prof, bool *redone);
 int enqueue_all(acgpu_automaton *a, DeviceState &d, CallRecord &r, int level);
 using EnqueueFn = int (*)(acgpu_automaton *, DeviceState &, CallRecord &, int);
-int run_sync(EnqueueFn enqueue, acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_kind, void *d_out, uint64_t cap,
-             uint64_t *n_out, hipStream_t stream, acgpu_profile *prof, bool folded = false);
 
 // Texts in which this dictionary matches densely (natural words in natural text: every filter passes, every verification walk
 // is long): the automaton's state behind every unit (k_ac_states over the compact automaton of acgpu_build.cpp 6d), then the
@@ -904,21 +920,19 @@ int mark_chain(DeviceState &d, uint32_t *d_nxt, uint32_t *d_tmp, uint32_t *d_mar
     bool one_pass = M >= one_pass_from && jump_bound <= 60000 && !(tunables().tile_debug & 2097152);
     uint64_t head = ~0ull, max_jump = 0;
     if (one_pass) {
-        // counter words used here: [2] chain head, [3] largest jump (bytes 16..32).  They lie inside enqueue_all's first slot
-        // counter line (word 0 = slot counter, word 1 = workgroup sum, the rest of the 128-byte line is padding), which every
-        // caller marks dirty (cclean[0] = false) so that the next AhoCorasick call clears it
+        // counter words used here: [2] chain head, [3] largest jump (bytes 16..32) of the line the caller has borrowed
+        // (borrow_counter_line)
         static_assert(kCounterStride >= 4, "mark_chain keeps its head and largest jump in words 2 and 3 of the first counter line");
-        if ((rc = d.counter.ensure(64))) return rc;
         if ((rc = d.lenbuf.ensure((size_t)M * 2 + 128))) return rc;
         if ((rc = d.blockmax.ensure(((size_t)M / 64 + 2) * 4))) return rc;
         HIP_TRY(hipMemsetAsync((char *)d.counter.p + 16, 0xff, 8, stream)); // the chain head's index (none: all ones)
         HIP_TRY(hipMemsetAsync((char *)d.counter.p + 24, 0, 8, stream));    // the largest jump
         HIP_TRY(launch_wwl_jumps(d_nxt, d_mark, M, (uint16_t *)d.lenbuf.p, (uint32_t *)d.blockmax.p,
                                  (unsigned long long *)d.counter.p + 2, jump_bound == 0, stream));
-        HIP_TRY(hipMemcpyAsync(d.h_counter + 3, (const char *)d.counter.p + 16, 16, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(d.h_counter + kPoolChainHead, (const char *)d.counter.p + 16, 16, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
-        head = d.h_counter[3];
-        max_jump = jump_bound ? jump_bound : d.h_counter[4];
+        head = d.h_counter[kPoolChainHead];
+        max_jump = jump_bound ? jump_bound : d.h_counter[kPoolChainHead + 1];
         if (head >= M) return ACGPU_OK; // no head: nothing is marked, nothing to mark
         if (max_jump > 60000) one_pass = false;
     }
@@ -967,77 +981,102 @@ int check_longest_shard(const HostTables &t, acgpu_shard *sh) {
     return ACGPU_OK;
 }
 
-// LONGEST over a dictionary whose suffix filter is selective: matches are sparse, so leftmost-longest is a selection
-// over the all-matches list (the AhoCorasick tile pipeline into an internal buffer + k_long_next + chain marking)
-// instead of a trie walk from every position.  Returns ACGPU_E_UNSUPPORTED when the haystack turns out to be dense in
-// matches (the caller then takes the walk).
-int match_longest_sparse(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_kind, void *d_out, uint64_t cap,
-                         uint64_t *n_out, hipStream_t stream, acgpu_profile *prof) {
-    const HostTables &t = a->t;
+// A pass that a host-run call runs inside itself: a synchronous call of an enqueued pipeline on the pool's own record (events
+// d.ev, slot d.h_counter), enqueued and collected -- that record may be `r`, so r is put back afterwards, with the pass's profile
+// in r.inside.
+int run_inside(EnqueueFn enqueue, acgpu_automaton *a, DeviceState &d, CallRecord &r, acgpu_shard *sh, int record_kind, void *d_out,
+               uint64_t cap, uint64_t *n_out) {
+    const CallRecord outer = r;
+    acgpu_profile inside{};
+    open_call(d.call, d.ev, nullptr, d.h_counter, *sh, sh, record_kind, d_out, cap, outer.stream, outer.profiled, false);
+    int rc = enqueue(a, d, d.call, 0);
+    if (rc == ACGPU_OK) rc = collect(a, d, &d.call, n_out, outer.profiled ? &inside : nullptr, nullptr);
+    r = outer;
+    r.inside = inside;
+    return rc;
+}
+
+// A host-run call whose pass inside was the whole call: what that pass found, and the chain's exit.
+int close_as_inside(CallRecord &r, uint64_t n, int64_t chain_exit) {
+    r.profiled = false; // (no events of its own)
+    r.h_slot[kSlotCount] = n;
+    r.h_slot[kSlotExit] = (unsigned long long)chain_exit;
+    return close_call(r, CallForm::HostRun, r.inside.scan_kernel, r.inside.scan_units);
+}
+
+// SHORTEST, and LONGEST where matches are sparse, as a selection over the all-matches list: the ALL pipeline over `all` into an
+// internal buffer (all matches, end ascending, longest first, with keyword ids; retried once with the exact capacity), every
+// record's successor (k_short_next; leftmost_longest: k_long_next), the chain from `entry` marked, its records written out.
+// More than dense_limit matches: ACGPU_E_UNSUPPORTED.  r.shard.chain_exit: the exit the caller has preset.
+int run_selection(acgpu_automaton *a, DeviceState &d, CallRecord &r, acgpu_shard all, int64_t entry, uint64_t dense_limit,
+                  bool leftmost_longest) {
+    const hipStream_t stream = r.stream;
+    const uint64_t own_len = r.shard.own_end - r.shard.own_begin;
     int rc;
-    if ((rc = check_longest_shard(t, sh))) return rc;
-    const uint64_t entry = (uint64_t)sh->chain_entry;
-    if (entry >= sh->own_end || t.n_states <= 1) return ACGPU_OK; // (the empty call)
-    const uint64_t halo = t.max_len > 0 ? t.max_len - 1 : 0;
-    const uint64_t own_len = sh->own_end - sh->own_begin;
-    acgpu_shard all = *sh; // every occurrence that ENDS in the owned range or its right halo
-    all.own_end = std::min<uint64_t>(sh->n_units, sh->own_end + halo);
-    all.text_begin = 1; // occurrences that begin before the buffer begin before own_begin: not ours anyway
     uint64_t m = 0;
-    const uint64_t dense_limit = own_len / 4 + 4096;
+    // what the buffer already holds (its size includes 16 spare bytes), or a first guess
     uint64_t acap = std::max<uint64_t>(d.short_recs.bytes > 16 ? (d.short_recs.bytes - 16) / ACGPU_REC_MAP : 0, own_len / 32 + (1 << 16));
-    acgpu_profile all_prof;
     for (;;) {
         if ((rc = d.short_recs.ensure(acap * ACGPU_REC_MAP + 16))) return rc;
-        rc = run_sync(enqueue_all, a, d, &all, ACGPU_REC_MAP, d.short_recs.p, acap, &m, stream, prof ? &all_prof : nullptr);
-        if (rc == ACGPU_E_OVERFLOW) {
-            if (m > dense_limit) return ACGPU_E_UNSUPPORTED;
-            acap = m;
-            continue;
-        }
-        if (rc != ACGPU_OK) return rc;
-        break;
+        rc = run_inside(enqueue_all, a, d, r, &all, ACGPU_REC_MAP, d.short_recs.p, acap, &m);
+        if (m > dense_limit && (rc == ACGPU_OK || rc == ACGPU_E_OVERFLOW)) return ACGPU_E_UNSUPPORTED;
+        if (rc == ACGPU_OK) break;
+        if (rc != ACGPU_E_OVERFLOW) return rc;
+        acap = m;
     }
-    if (m > dense_limit) return ACGPU_E_UNSUPPORTED;
-    if (prof) *prof = all_prof;
-    *n_out = 0;
-    sh->chain_exit = (int64_t)std::max<uint64_t>(entry, sh->own_end);
-    if (m == 0) return ACGPU_OK;
+    if (m == 0) return close_as_inside(r, 0, r.shard.chain_exit); // (nothing to select from)
+    if (m >= 0xfffffff0ull) return ACGPU_E_UNSUPPORTED; // (the selection's indices are 32 bits wide)
     const uint32_t M = (uint32_t)m;
     if ((rc = d.short_nxt.ensure(((size_t)M + 1) * 4))) return rc;
     if ((rc = d.short_tmp.ensure(((size_t)M + 1) * 4))) return rc;
     if ((rc = d.short_mark.ensure(((size_t)M + 1) * 4))) return rc;
     if ((rc = d.offsets.ensure((size_t)M * 8))) return rc;
     if ((rc = d.scan_tmp.ensure(((size_t)M / 2048 + 2) * 8))) return rc;
-    if ((rc = d.counter.ensure(64))) return rc;
-    if (prof) HIP_TRY(hipEventRecord(d.ev[0], stream));
-    HIP_TRY(launch_longest_select((const int32_t *)d.short_recs.p, M, (int64_t)entry, (int64_t)sh->own_end, t.max_len,
-                                  (uint32_t *)d.short_nxt.p, (uint32_t *)d.short_tmp.p, (uint32_t *)d.short_mark.p, stream));
+    if ((rc = borrow_counter_line(d, stream, /*clear=*/false))) return rc; // (the exit position; mark_chain's words)
+    if (r.profiled) HIP_TRY(hipEventRecord(r.ev[0], stream));
+    if (leftmost_longest)
+        HIP_TRY(launch_longest_select((const int32_t *)d.short_recs.p, M, entry, (int64_t)r.shard.own_end, a->t.max_len,
+                                      (uint32_t *)d.short_nxt.p, (uint32_t *)d.short_mark.p, stream));
+    else
+        HIP_TRY(launch_shortest_select((const int32_t *)d.short_recs.p, M, entry, (uint32_t *)d.short_nxt.p, (uint32_t *)d.short_mark.p, stream));
     if ((rc = mark_chain(d, (uint32_t *)d.short_nxt.p, (uint32_t *)d.short_tmp.p, (uint32_t *)d.short_mark.p, M, stream, nullptr,
                          nullptr, 0)))
         return rc;
     HIP_TRY(launch_exclusive_scan((const uint32_t *)d.short_mark.p, M, (uint64_t *)d.offsets.p, (uint64_t *)d.scan_tmp.p, stream));
     const uint64_t *d_total = (const uint64_t *)d.scan_tmp.p + scan_tiles_for(M);
-    HIP_TRY(launch_shortest_emit((const int32_t *)d.short_recs.p, M, (const uint32_t *)d.short_mark.p,
-                                 (const uint64_t *)d.offsets.p, d_total, record_kind, d_out, cap, (int64_t)entry,
-                                 (unsigned long long *)d.counter.p, stream));
-    d.cclean[0] = false; // (the exit position went where enqueue_all's first set of slot counters lives)
-    if (prof) HIP_TRY(hipEventRecord(d.ev[1], stream));
-    HIP_TRY(hipMemcpyAsync(d.h_counter, d_total, 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(d.h_counter + 1, d.counter.p, 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    *n_out = d.h_counter[0];
-    // the chain leaves the owned range at the end of its last match, or walks out of it one unit at a time
-    if (*n_out) sh->chain_exit = (int64_t)std::max<uint64_t>(d.h_counter[1], sh->own_end);
-    if (prof) {
-        float sel_ms = 0;
-        HIP_TRY(hipEventElapsedTime(&sel_ms, d.ev[0], d.ev[1]));
-        prof->finalize_ms += sel_ms;
-        prof->total_ms += sel_ms;
-        prof->scan_units = own_len;
-        prof->n_matches = *n_out;
-    }
-    return *n_out > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
+    HIP_TRY(launch_shortest_emit((const int32_t *)d.short_recs.p, M, (const uint32_t *)d.short_mark.p, (const uint64_t *)d.offsets.p,
+                                 d_total, r.record_kind, r.d_out, r.cap, entry, (unsigned long long *)d.counter.p, stream));
+    if (r.profiled) HIP_TRY(hipEventRecord(r.ev[1], stream));
+    r.behind_pass = true; // (the ordering of the all-matches list + the selection)
+    if ((rc = close_host_run(r, d_total, d.counter.p, r.inside.scan_kernel, leftmost_longest ? own_len : r.inside.scan_units))) return rc;
+    // LONGEST: the chain leaves the owned range at the end of its last match, or walks out of it one unit at a time
+    if (leftmost_longest)
+        r.h_slot[kSlotExit] = r.h_slot[kSlotCount] ? std::max<unsigned long long>(r.h_slot[kSlotExit], r.shard.own_end)
+                                                   : (unsigned long long)r.shard.chain_exit;
+    return ACGPU_OK;
+}
+
+// SHORTEST-mode pipeline on one shard: the restart position that came in restricts where the first match may start.
+int run_shortest(acgpu_automaton *a, DeviceState &d, CallRecord &r) {
+    const int64_t entry = r.shard.chain_entry > 0 ? r.shard.chain_entry : 0;
+    r.user_shard->chain_exit = r.shard.chain_exit = entry;
+    return run_selection(a, d, r, r.shard, entry, ~0ull, false);
+}
+
+// LONGEST over a dictionary whose suffix filter is selective: matches are sparse, so leftmost-longest is a selection over the
+// all-matches list instead of a trie walk from every position.  Returns ACGPU_E_UNSUPPORTED when the haystack turns out to be
+// dense in matches (the caller then takes the walk).
+int run_longest_sparse(acgpu_automaton *a, DeviceState &d, CallRecord &r) {
+    const HostTables &t = a->t;
+    int rc;
+    if ((rc = check_longest_shard(t, &r.shard))) return rc;
+    r.user_shard->chain_exit = r.shard.chain_exit;
+    const acgpu_shard &sh = r.shard;
+    if ((uint64_t)sh.chain_entry >= sh.own_end || t.n_states <= 1) return enqueue_empty(r, sh.chain_exit);
+    acgpu_shard all = sh; // every occurrence that ENDS in the owned range or its right halo
+    all.own_end = std::min<uint64_t>(sh.n_units, sh.own_end + (t.max_len > 0 ? t.max_len - 1 : 0));
+    all.text_begin = 1; // occurrences that begin before the buffer begin before own_begin: not ours anyway
+    return run_selection(a, d, r, all, sh.chain_entry, (sh.own_end - sh.own_begin) / 4 + 4096, true);
 }
 
 // A two-letter alphabet in which every letter is a keyword: the text as one bit per unit, the chain's own positions only
@@ -1145,7 +1184,7 @@ int enqueue_longest_follow(acgpu_automaton *a, DeviceState &d, CallRecord &r, ui
     F.tile_log2 = 2; // (emit tiles of 4096 positions)
     F.hot_rows = fol_hot;
     const uint32_t n_tiles = (F.n_regions * (region_units / seg_units)) >> F.tile_log2;
-    if ((rc = d.counter.ensure(64))) return rc;
+    if ((rc = borrow_counter_line(d, stream, /*clear=*/true))) return rc;
     if ((rc = d.chunk_counts.ensure((size_t)n_tiles * 4))) return rc;
     if ((rc = d.offsets.ensure((size_t)n_tiles * 8))) return rc;
     if ((rc = d.scan_tmp.ensure(((size_t)n_tiles / 2048 + 2) * 8))) return rc;
@@ -1166,8 +1205,6 @@ int enqueue_longest_follow(acgpu_automaton *a, DeviceState &d, CallRecord &r, ui
     F.d_pred = (uint32_t *)d.blockmax.p;
     F.d_true = F.d_pred + F.n_regions;
     F.grid = (int)std::min<uint64_t>(2ull * d.n_cu, (F.n_regions + 15) / 16);
-    HIP_TRY(hipMemsetAsync(d.counter.p, 0, 64, stream));
-    d.cclean[0] = false; // (enqueue_all's first set of slot counters lives here)
     { // the end bits are merged with atomicOr: zeros from the first word the chain can touch to where its last match can end
         const size_t first = F.g0 >> 5, last = std::min<size_t>(bit_bytes / 4, (((size_t)sh->own_end + t.max_len) >> 5) + 2);
         if (last > first) HIP_TRY(hipMemsetAsync(F.d_ebits + first, 0, (last - first) * 4, stream));
@@ -1284,7 +1321,7 @@ int enqueue_longest_walk(acgpu_automaton *a, DeviceState &d, CallRecord &r, uint
     const uint64_t T_units = tunables().region_units > 0 ? (uint64_t)tunables().region_units : (own_len >= (1ull << 24) ? 6144 : 1024);
     Cn.tile_units = (uint32_t)T_units;
     Cn.n_tiles = (uint32_t)((sh->own_end - entry + T_units - 1) / T_units);
-    if ((rc = d.counter.ensure(64))) return rc;
+    if ((rc = borrow_counter_line(d, stream, /*clear=*/true))) return rc;
     if ((rc = d.chunk_counts.ensure((size_t)Cn.n_tiles * 4))) return rc;
     if ((rc = d.offsets.ensure((size_t)Cn.n_tiles * 8))) return rc;
     if ((rc = d.scan_tmp.ensure(((size_t)Cn.n_tiles / 2048 + 2) * 8))) return rc;
@@ -1304,9 +1341,6 @@ int enqueue_longest_walk(acgpu_automaton *a, DeviceState &d, CallRecord &r, uint
     Cn.cap = r.cap;
     Cn.record_kind = record_kind;
     Cn.d_exit = (unsigned long long *)d.counter.p;
-
-    HIP_TRY(hipMemsetAsync(d.counter.p, 0, 64, stream));
-    d.cclean[0] = false; // (enqueue_all's first set of slot counters lives here)
     if (r.profiled) HIP_TRY(hipEventRecord(r.ev[0], stream));
     const char *kname = "";
     if (root_form) {
@@ -1358,7 +1392,7 @@ int enqueue_longest_walk(acgpu_automaton *a, DeviceState &d, CallRecord &r, uint
 
 // LONGEST-mode pipeline on one shard: the checks, the chain's preset exit, the empty call; then the form of this run-up level
 // (bits_level 0: short, 1: a whole segment, 2: the walk pipeline).  The sparse form of a selective suffix filter runs before
-// this, synchronously (match_shard).  Tunable longest_form, bits: 1 = never k_longest_bits, 2 = never k_longest_follow,
+// this, on the host (start_call).  Tunable longest_form, bits: 1 = never k_longest_bits, 2 = never k_longest_follow,
 // 4 = also for short texts (tests), 8 = k_longest_follow where the walk pipeline has its root table too.
 int enqueue_longest(acgpu_automaton *a, DeviceState &d, CallRecord &r, int bits_level) {
     const HostTables &t = a->t;
@@ -1395,25 +1429,26 @@ int enqueue_longest(acgpu_automaton *a, DeviceState &d, CallRecord &r, int bits_
 // k_longest_follow (1: a chain that did not merge inside the run-up, 2: a unit outside the alphabet) -> the next run-up level,
 // or 2, the walk pipeline.  A redo is always at a higher level, and the forms of the last levels never ask for one.
 int redo_level(const CallRecord &r) {
-    const unsigned long long flag = r.h_slot[1];
+    const unsigned long long flag = r.h_slot[kSlotFlag];
     if (r.form == CallForm::Ordered || r.form == CallForm::FusedTail) return r.level == 0 && (uint32_t)flag != 0 ? 1 : -1;
     if (r.form == CallForm::LongestBits || r.form == CallForm::LongestFollow) return flag == 0 ? -1 : flag == 1 ? r.level + 1 : 2;
     return -1;
 }
 
-// Completes a call enqueued into *r: the wait (a synchronous call's; end_ticket waits for a ticket's outside the pool's lock),
-// the redo if the kernels ask for one -- a synchronous call on the pool's own record --, then the chain exit, what the pool
-// learns (the ALL density), the profile and the overflow status.  The caller holds d.mu.
+// Completes the call in *r, for every family: the wait (a synchronous call's; end_ticket waits for a ticket's outside the pool's
+// lock; a host-run call has waited itself), the redo if the kernels ask for one -- a synchronous call on the pool's own record --,
+// then the count, the chain exit, what the pool learns (the ALL density), the profile and the overflow status.  The caller
+// holds d.mu.
 int collect(acgpu_automaton *a, DeviceState &d, CallRecord *r, uint64_t *n_out, acgpu_profile *prof, bool *redone) {
     for (;;) {
-        if (!r->done && r->form != CallForm::Complete) HIP_TRY(hipStreamSynchronize(r->stream));
+        if (!r->done && r->form != CallForm::Complete && r->form != CallForm::HostRun) HIP_TRY(hipStreamSynchronize(r->stream));
         const int level = redo_level(*r);
         if (level < 0) break;
         const bool longest = r->form != CallForm::Ordered && r->form != CallForm::FusedTail;
         if (r->form == CallForm::LongestFollow) d.fol_level = std::max(d.fol_level, r->level + 1); // (the pool's later calls start there)
         // (the redo shares the scratch with the tickets still in flight: same stream, so stream order keeps them apart)
         acgpu_shard sh = r->shard;
-        if (longest) sh.d_result = nullptr; // (a Longest redo leaves the device result to the first attempt)
+        if (longest && r->done) sh.d_result = nullptr; // (a ticket's Longest redo leaves the device result to the first attempt, which says "redone")
         open_call(d.call, d.ev, nullptr, d.h_counter, sh, r->user_shard, r->record_kind, r->d_out, r->cap, r->stream, prof != nullptr,
                   r->folded);
         if (redone) *redone = true;
@@ -1421,14 +1456,19 @@ int collect(acgpu_automaton *a, DeviceState &d, CallRecord *r, uint64_t *n_out, 
         if (rc) return rc;
         r = &d.call;
     }
-    *n_out = r->h_slot[0];
-    if (r->form == CallForm::LongestBits || r->form == CallForm::LongestFollow || r->form == CallForm::LongestWalk)
-        r->user_shard->chain_exit = (int64_t)r->h_slot[2];
+    *n_out = r->h_slot[kSlotCount];
+    if (r->form == CallForm::LongestBits || r->form == CallForm::LongestFollow || r->form == CallForm::LongestWalk || r->form == CallForm::HostRun)
+        r->user_shard->chain_exit = (int64_t)r->h_slot[kSlotExit];
     else if (r->form != CallForm::Complete && a->t.mode != ACGPU_MODE_WHOLEWORD) // (what the states form's choice goes by)
         d.all_density = (double)*n_out / (double)(r->shard.own_end - r->shard.own_begin);
+    if (prof) *prof = r->inside; // (zero, but for a host-run call with a pass inside)
     if (prof && r->form != CallForm::Complete) {
-        std::memset(prof, 0, sizeof(*prof));
-        if (r->profiled && r->one_kernel) {
+        if (r->profiled && r->behind_pass) {
+            float behind_ms = 0;
+            HIP_TRY(hipEventElapsedTime(&behind_ms, r->ev[0], r->ev[1]));
+            prof->finalize_ms += behind_ms;
+            prof->total_ms += behind_ms;
+        } else if (r->profiled && r->one_kernel) {
             HIP_TRY(hipEventElapsedTime(&prof->scan_ms, r->ev[0], r->ev[2]));
             prof->total_ms = prof->scan_ms;
         } else if (r->profiled) {
@@ -1443,137 +1483,42 @@ int collect(acgpu_automaton *a, DeviceState &d, CallRecord *r, uint64_t *n_out, 
     return *n_out > r->cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
 }
 
-// A synchronous call of an enqueued pipeline: into the pool's own record (events d.ev, slot d.h_counter), then collect().
-int run_sync(EnqueueFn enqueue, acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_kind, void *d_out, uint64_t cap,
-             uint64_t *n_out, hipStream_t stream, acgpu_profile *prof, bool folded) {
-    open_call(d.call, d.ev, nullptr, d.h_counter, *sh, sh, record_kind, d_out, cap, stream, prof != nullptr, folded);
-    if (prof) std::memset(prof, 0, sizeof(*prof));
-    const int rc = enqueue(a, d, d.call, 0);
-    return rc ? rc : collect(a, d, &d.call, n_out, prof, nullptr);
-}
-
 // WHOLEWORD with a word-character table that is not fold-consistent: the reference's mixed folded/raw lookups make
 // token boundaries history dependent -- whole text, one lane (k_ww_sequential).  (Fold-consistent tables: enqueue_all.)
-int match_wholeword_sequential(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_kind, void *d_out, uint64_t cap,
-                               uint64_t *n_out, hipStream_t stream, acgpu_profile *prof) {
-    const uint64_t own_len = sh->own_end - sh->own_begin;
-    if (prof) std::memset(prof, 0, sizeof(*prof));
-    if (own_len == 0) {
-        *n_out = 0;
-        return ACGPU_OK;
-    }
+int run_wholeword_sequential(acgpu_automaton *, DeviceState &d, CallRecord &r) {
+    const acgpu_shard &sh = r.shard;
+    const uint64_t own_len = sh.own_end - sh.own_begin;
+    if (own_len == 0) return enqueue_empty(r, sh.chain_exit);
     int rc;
-    if ((rc = d.counter.ensure(64))) return rc;
-    HIP_TRY(hipMemsetAsync(d.counter.p, 0, 64, stream));
-    d.cclean[0] = false; // (enqueue_all's first set of slot counters lives here)
-    if (!sh->text_begin || !sh->text_end || sh->own_begin != 0 || sh->own_end != sh->n_units) return ACGPU_E_UNSUPPORTED;
-    if (prof) HIP_TRY(hipEventRecord(d.ev[0], stream));
-    HIP_TRY(launch_ww_sequential(d.T, sh->d_hay, (uint32_t)sh->n_units, d_out, cap, record_kind,
-                                 (unsigned long long *)d.counter.p, stream));
-    if (prof) HIP_TRY(hipEventRecord(d.ev[1], stream));
-    HIP_TRY(hipMemcpyAsync(d.h_counter, d.counter.p, 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    *n_out = *d.h_counter;
-    if (prof) {
-        HIP_TRY(hipEventElapsedTime(&prof->scan_ms, d.ev[0], d.ev[1]));
-        prof->total_ms = prof->scan_ms;
-        prof->scan_units = own_len;
-        prof->n_matches = *n_out;
-        std::snprintf(prof->scan_kernel, sizeof(prof->scan_kernel), "k_ww_sequential");
-    }
-    return *n_out > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
-}
-
-// SHORTEST-mode pipeline on one shard: the AhoCorasick pipeline into an internal buffer, then the greedy selection.
-int match_shortest(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_kind, void *d_out, uint64_t cap,
-                   uint64_t *n_out, hipStream_t stream, acgpu_profile *prof) {
-    const int64_t entry = sh->chain_entry > 0 ? sh->chain_entry : 0;
-    sh->chain_exit = entry;
-    int rc;
-    uint64_t m = 0;
-    // what the buffer already holds (its size includes 16 spare bytes), or a first guess
-    uint64_t acap = std::max<uint64_t>(d.short_recs.bytes > 16 ? (d.short_recs.bytes - 16) / ACGPU_REC_MAP : 0,
-                                       (sh->own_end - sh->own_begin) / 32 + (1 << 16));
-    acgpu_profile all_prof;
-    for (;;) { // all matches (end ascending, longest first) with keyword ids; retried once with the exact capacity
-        if ((rc = d.short_recs.ensure(acap * ACGPU_REC_MAP + 16))) return rc;
-        rc = run_sync(enqueue_all, a, d, sh, ACGPU_REC_MAP, d.short_recs.p, acap, &m, stream, prof ? &all_prof : nullptr);
-        if (rc == ACGPU_E_OVERFLOW) {
-            acap = m;
-            continue;
-        }
-        if (rc != ACGPU_OK) return rc;
-        break;
-    }
-    if (prof) *prof = all_prof;
-    *n_out = 0;
-    if (m == 0) return ACGPU_OK;
-    if (m >= 0xfffffff0ull) return ACGPU_E_UNSUPPORTED;
-    const uint32_t M = (uint32_t)m;
-    if ((rc = d.short_nxt.ensure(((size_t)M + 1) * 4))) return rc;
-    if ((rc = d.short_tmp.ensure(((size_t)M + 1) * 4))) return rc;
-    if ((rc = d.short_mark.ensure(((size_t)M + 1) * 4))) return rc;
-    if ((rc = d.offsets.ensure((size_t)M * 8))) return rc;
-    if ((rc = d.scan_tmp.ensure(((size_t)M / 2048 + 2) * 8))) return rc;
-    if ((rc = d.counter.ensure(64))) return rc;
-    if (prof) HIP_TRY(hipEventRecord(d.ev[0], stream));
-    HIP_TRY(launch_shortest_select((const int32_t *)d.short_recs.p, M, entry, (uint32_t *)d.short_nxt.p,
-                                   (uint32_t *)d.short_tmp.p, (uint32_t *)d.short_mark.p, stream));
-    if ((rc = mark_chain(d, (uint32_t *)d.short_nxt.p, (uint32_t *)d.short_tmp.p, (uint32_t *)d.short_mark.p, M, stream, nullptr,
-                         nullptr, 0)))
-        return rc;
-    HIP_TRY(launch_exclusive_scan((const uint32_t *)d.short_mark.p, M, (uint64_t *)d.offsets.p, (uint64_t *)d.scan_tmp.p, stream));
-    const uint64_t *d_total = (const uint64_t *)d.scan_tmp.p + scan_tiles_for(M);
-    HIP_TRY(launch_shortest_emit((const int32_t *)d.short_recs.p, M, (const uint32_t *)d.short_mark.p,
-                                 (const uint64_t *)d.offsets.p, d_total, record_kind, d_out, cap, entry,
-                                 (unsigned long long *)d.counter.p, stream));
-    d.cclean[0] = false; // (the exit position went where enqueue_all's first set of slot counters lives)
-    if (prof) HIP_TRY(hipEventRecord(d.ev[1], stream));
-    HIP_TRY(hipMemcpyAsync(d.h_counter, d_total, 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(d.h_counter + 1, d.counter.p, 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    *n_out = d.h_counter[0];
-    sh->chain_exit = (int64_t)d.h_counter[1];
-    if (prof) {
-        float sel_ms = 0;
-        HIP_TRY(hipEventElapsedTime(&sel_ms, d.ev[0], d.ev[1]));
-        prof->finalize_ms += sel_ms; // ordering of the all-matches list + the selection
-        prof->total_ms += sel_ms;
-        prof->n_matches = *n_out;
-    }
-    return *n_out > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
+    if ((rc = borrow_counter_line(d, r.stream, /*clear=*/true))) return rc;
+    if (!sh.text_begin || !sh.text_end || sh.own_begin != 0 || sh.own_end != sh.n_units) return ACGPU_E_UNSUPPORTED;
+    if (r.profiled) HIP_TRY(hipEventRecord(r.ev[0], r.stream));
+    HIP_TRY(launch_ww_sequential(d.T, sh.d_hay, (uint32_t)sh.n_units, r.d_out, r.cap, r.record_kind, (unsigned long long *)d.counter.p,
+                                 r.stream));
+    if (r.profiled) HIP_TRY(hipEventRecord(r.ev[2], r.stream));
+    r.one_kernel = true;
+    r.h_slot[kSlotExit] = (unsigned long long)sh.chain_exit; // (no chain: the caller's word stays what it is)
+    return close_host_run(r, d.counter.p, nullptr, "k_ww_sequential", own_len);
 }
 
 // WholeWordLongestMatchSet.match(String) with a word-character table that is not fold-consistent: the reference mixes folded
 // and raw lookups (S/WholeWordLongestMatchSet.java:126 against :151,:156), which makes token boundaries history dependent --
 // whole text, one lane (k_wwl_sequential).
-int match_wwlongest_sequential(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_kind, void *d_out, uint64_t cap,
-                               uint64_t *n_out, hipStream_t stream, acgpu_profile *prof) {
-    const HostTables &t = a->t;
-    if (prof) std::memset(prof, 0, sizeof(*prof));
-    *n_out = 0;
-    const uint32_t n = (uint32_t)sh->n_units;
-    sh->chain_exit = (int64_t)std::max<int64_t>(sh->chain_entry, (int64_t)sh->own_begin);
+int run_wwlongest_sequential(acgpu_automaton *a, DeviceState &d, CallRecord &r) {
+    const acgpu_shard &sh = r.shard;
+    const uint32_t n = (uint32_t)sh.n_units;
+    const int64_t entry = std::max<int64_t>(sh.chain_entry, (int64_t)sh.own_begin);
+    r.user_shard->chain_exit = entry;
     int rc;
-    if (!sh->text_begin || !sh->text_end || sh->own_begin != 0 || sh->own_end != sh->n_units) return ACGPU_E_UNSUPPORTED;
-    if (n == 0 || t.n_states <= 1) return ACGPU_OK;
-    if ((rc = d.counter.ensure(64))) return rc;
-    d.cclean[0] = false; // (enqueue_all's first set of slot counters lives here)
-    if (prof) HIP_TRY(hipEventRecord(d.ev[0], stream));
-    HIP_TRY(launch_wwl_sequential(d.T, sh->d_hay, n, d_out, cap, record_kind, (unsigned long long *)d.counter.p, stream));
-    if (prof) HIP_TRY(hipEventRecord(d.ev[1], stream));
-    HIP_TRY(hipMemcpyAsync(d.h_counter, d.counter.p, 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    *n_out = *d.h_counter;
-    sh->chain_exit = (int64_t)n;
-    if (prof) {
-        HIP_TRY(hipEventElapsedTime(&prof->scan_ms, d.ev[0], d.ev[1]));
-        prof->total_ms = prof->scan_ms;
-        prof->scan_units = n;
-        prof->n_matches = *n_out;
-        std::snprintf(prof->scan_kernel, sizeof(prof->scan_kernel), "k_wwl_sequential");
-    }
-    return *n_out > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
+    if (!sh.text_begin || !sh.text_end || sh.own_begin != 0 || sh.own_end != sh.n_units) return ACGPU_E_UNSUPPORTED;
+    if (n == 0 || a->t.n_states <= 1) return enqueue_empty(r, entry);
+    if ((rc = borrow_counter_line(d, r.stream, /*clear=*/false))) return rc;
+    if (r.profiled) HIP_TRY(hipEventRecord(r.ev[0], r.stream));
+    HIP_TRY(launch_wwl_sequential(d.T, sh.d_hay, n, r.d_out, r.cap, r.record_kind, (unsigned long long *)d.counter.p, r.stream));
+    if (r.profiled) HIP_TRY(hipEventRecord(r.ev[2], r.stream));
+    r.one_kernel = true;
+    r.h_slot[kSlotExit] = n;
+    return close_host_run(r, d.counter.p, nullptr, "k_wwl_sequential", n);
 }
 
 // WWLONGEST-mode pipeline on one shard.  A walk belongs to the shard that owns its first unit; the scan visits the first walk
@@ -1582,33 +1527,31 @@ int match_wwlongest_sequential(acgpu_automaton *a, DeviceState &d, acgpu_shard *
 // plain_words: the walk reports only a whole path that is a keyword and ends at a word boundary -- no carried fail match --
 // and does without the first-word table: WholeWordMatchMap's loop (S/WholeWordMatchMap.java:55-153), which is this walk
 // without fail matches, over a WHOLEWORD automaton whose folded keywords hold non-word units (HostTables::fold_clean).
-int match_wwlongest(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_kind, void *d_out, uint64_t cap,
-                    uint64_t *n_out, hipStream_t stream, acgpu_profile *prof, const DevTables &T, bool plain_words) {
+int run_wwlongest(acgpu_automaton *a, DeviceState &d, CallRecord &r, const DevTables &T, bool plain_words) {
     const HostTables &t = a->t;
-    if (prof) std::memset(prof, 0, sizeof(*prof));
-    *n_out = 0;
+    const acgpu_shard *sh = &r.shard;
+    const hipStream_t stream = r.stream;
     const uint32_t n = (uint32_t)sh->n_units;
     const uint64_t entry = (uint64_t)std::max<int64_t>(sh->chain_entry, (int64_t)sh->own_begin);
-    sh->chain_exit = (int64_t)entry;
+    r.user_shard->chain_exit = (int64_t)entry;
     int rc;
     if (!sh->text_begin && sh->own_begin < 1) return ACGPU_E_INVALID;                              // left context: 1 unit
     if (!sh->text_end && sh->n_units - sh->own_end < (uint64_t)t.max_len + 1) return ACGPU_E_INVALID; // right halo
-    if (n == 0 || t.n_states <= 1 || sh->own_end == sh->own_begin || entry >= sh->own_end) return ACGPU_OK;
+    if (n == 0 || t.n_states <= 1 || sh->own_end == sh->own_begin || entry >= sh->own_end) return enqueue_empty(r, (int64_t)entry);
     const uint32_t n_tiles = wwl_tiles(n);
     if ((rc = d.chunk_counts.ensure((size_t)n_tiles * 4))) return rc;
     if ((rc = d.offsets.ensure((size_t)n_tiles * 8))) return rc;
     if ((rc = d.scan_tmp.ensure(((size_t)n_tiles / 2048 + 2) * 8))) return rc;
-    if ((rc = d.counter.ensure(64))) return rc;
-    d.cclean[0] = false; // (enqueue_all's first set of slot counters lives here)
-    if (prof) HIP_TRY(hipEventRecord(d.ev[0], stream));
+    if ((rc = borrow_counter_line(d, stream, /*clear=*/false))) return rc; // (the exit position; mark_chain's words)
+    if (r.profiled) HIP_TRY(hipEventRecord(r.ev[0], stream));
     HIP_TRY(launch_wwl_starts(T, sh->d_hay, n, d.n_cu, false, (uint32_t *)d.chunk_counts.p, nullptr, nullptr, sh->text_begin, d.start_behind, stream));
     HIP_TRY(launch_exclusive_scan((const uint32_t *)d.chunk_counts.p, n_tiles, (uint64_t *)d.offsets.p, (uint64_t *)d.scan_tmp.p,
                                   stream));
-    HIP_TRY(hipMemcpyAsync(d.h_counter, (const uint64_t *)d.scan_tmp.p + scan_tiles_for(n_tiles), 8, hipMemcpyDeviceToHost,
+    HIP_TRY(hipMemcpyAsync(r.h_slot + kSlotCount, (const uint64_t *)d.scan_tmp.p + scan_tiles_for(n_tiles), 8, hipMemcpyDeviceToHost,
                            stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    const uint32_t M = (uint32_t)*d.h_counter; // walk starts of the buffer (halos included)
-    if (M == 0) return ACGPU_OK;
+    const uint32_t M = (uint32_t)r.h_slot[kSlotCount]; // walk starts of the buffer (halos included)
+    if (M == 0) return enqueue_empty(r, (int64_t)entry);
     if ((rc = d.wwl_rs.ensure(((size_t)M + 1) * 4))) return rc;
     if ((rc = d.wwl_mend.ensure(((size_t)M + 1) * 4))) return rc;
     if ((rc = d.wwl_mid.ensure(((size_t)M + 1) * 4))) return rc;
@@ -1618,15 +1561,15 @@ int match_wwlongest(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int rec
     if ((rc = d.short_tmp.ensure(((size_t)M + 1) * 4))) return rc;
     if ((rc = d.short_mark.ensure(((size_t)M + 1) * 4))) return rc;
     { // the exit position, preset to the entry (no visited walk start: nothing changes hands)
-        d.h_counter[2] = entry;
-        HIP_TRY(hipMemcpyAsync(d.counter.p, d.h_counter + 2, 8, hipMemcpyHostToDevice, stream));
+        r.h_slot[kSlotExit] = entry;
+        HIP_TRY(hipMemcpyAsync(d.counter.p, r.h_slot + kSlotExit, 8, hipMemcpyHostToDevice, stream));
     }
     HIP_TRY(launch_wwl_starts(T, sh->d_hay, n, d.n_cu, true, nullptr, (const uint64_t *)d.offsets.p, (uint32_t *)d.wwl_rs.p,
                               sh->text_begin, d.start_behind, stream));
     HIP_TRY(launch_wwl_walk(T, plain_words, sh->d_hay, n, (const uint32_t *)d.wwl_rs.p, M, (uint32_t *)d.short_nxt.p,
                             (uint32_t *)d.short_mark.p, (int32_t *)d.wwl_mend.p, (int32_t *)d.wwl_mid.p, (uint32_t *)d.wwl_stop.p,
                             (uint32_t)entry, d.n_cu, stream));
-    if (prof) HIP_TRY(hipEventRecord(d.ev[1], stream));
+    if (r.profiled) HIP_TRY(hipEventRecord(r.ev[1], stream));
     // Which starts does the scan visit?  The chain k0, NXT[k0], ... over the start indices: mark_chain (one pass -- a walk
     // runs over few later starts; pointer doubling took 2.5 ms of 8.4 on config 5's text).  The select pass needs the
     // successors afterwards.
@@ -1642,22 +1585,9 @@ int match_wwlongest(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int rec
     if ((rc = d.scan_tmp.ensure(((size_t)M / 2048 + 2) * 8))) return rc;
     HIP_TRY(launch_scan_tile_offsets((const uint32_t *)d.wwl_sel.p, M, (uint64_t *)d.scan_tmp.p, stream));
     HIP_TRY(launch_wwl_emit((const uint32_t *)d.wwl_rs.p, (const uint32_t *)d.wwl_sel.p, (const int32_t *)d.wwl_mend.p,
-                            (const int32_t *)d.wwl_mid.p, (const uint64_t *)d.scan_tmp.p, M, record_kind, d_out, cap, stream));
-    if (prof) HIP_TRY(hipEventRecord(d.ev[2], stream));
-    HIP_TRY(hipMemcpyAsync(d.h_counter, (const uint64_t *)d.scan_tmp.p + scan_tiles_for(M), 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(d.h_counter + 1, d.counter.p, 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    *n_out = *d.h_counter;
-    sh->chain_exit = (int64_t)d.h_counter[1];
-    if (prof) {
-        HIP_TRY(hipEventElapsedTime(&prof->scan_ms, d.ev[0], d.ev[1]));
-        HIP_TRY(hipEventElapsedTime(&prof->finalize_ms, d.ev[1], d.ev[2]));
-        HIP_TRY(hipEventElapsedTime(&prof->total_ms, d.ev[0], d.ev[2]));
-        prof->scan_units = n;
-        prof->n_matches = *n_out;
-        std::snprintf(prof->scan_kernel, sizeof(prof->scan_kernel), "k_wwl_walk");
-    }
-    return *n_out > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
+                            (const int32_t *)d.wwl_mid.p, (const uint64_t *)d.scan_tmp.p, M, r.record_kind, r.d_out, r.cap, stream));
+    if (r.profiled) HIP_TRY(hipEventRecord(r.ev[2], stream));
+    return close_host_run(r, (const uint64_t *)d.scan_tmp.p + scan_tiles_for(M), d.counter.p, "k_wwl_walk", n);
 }
 
 } // namespace
@@ -1696,84 +1626,91 @@ int check_shard(acgpu_automaton *a, DeviceState &d, const acgpu_shard *sh, int r
     return ACGPU_OK;
 }
 
-// validates a shard and runs the pipeline of the automaton's family; caller holds d.mu.
+// One call on a checked shard into its record -- the pool's own (tk null: a synchronous call, which the caller collects at once)
+// or a ticket's -- by the pipeline of the automaton's family.  Enqueued without waiting: the AhoCorasick / WholeWord pipeline
+// (one scan + ordering pass) and the LongestMatch pipelines (nothing of them needs the host).  The other families -- and
+// LongestMatch over a dictionary with a selective suffix filter, whose sparse form falls back to the walk after looking at the
+// match count -- need the host between their launches and run to their end here (CallForm::HostRun): such a ticket is complete
+// when _begin returns (no completion marker: nothing in flight, the stream rule does not apply to it); only its bookkeeping
+// waits for collect().
 // readable: the call stands for match(Readable, ...) (acgpu_stream_feed) -- the word matchers' Readable loops fold in every
 // lookup where their String loops mix folded and raw ones, which only matters for tables that are not fold-consistent.
+static int start_call(acgpu_automaton *a, DeviceState &d, Ticket *tk, acgpu_shard *sh, int record_kind, void *d_out, uint64_t cap,
+                      hipStream_t stream, bool profiled, bool readable) {
+    const HostTables &t = a->t;
+    const ShardRule rule = shard_rule(t, record_kind, readable);
+    const bool enqueued = rule.all_pipeline || (t.mode == ACGPU_MODE_LONGEST && !(filter_is_selective(t) && tunables().force_kernel != 1));
+    CallRecord &r = tk ? tk->rec : d.call;
+    // (all_pipeline over tables that are not fold-consistent: the Readable loop of WholeWord, an ordinary scan over w' = word o lower)
+    open_call(r, tk ? tk->ev : d.ev, tk && enqueued ? tk->done : nullptr, tk ? tk->h_count : d.h_counter, *sh, sh, record_kind, d_out, cap,
+              stream, profiled, rule.all_pipeline && !t.fold_consistent);
+    if (rule.all_pipeline) return enqueue_all(a, d, r, 0);
+    if (enqueued) return enqueue_longest(a, d, r, 0);
+    // a host-run call ends with its count on the host (and some run the ALL pipeline inside): the device copy of the result is
+    // written behind the pipeline
+    r.shard.d_result = nullptr;
+    int rc;
+    switch (t.mode) {
+    case ACGPU_MODE_LONGEST:
+        // a selective suffix filter: a selection over all matches, unless the text turns out to be dense in them -- then the
+        // walk after all, as a pass inside
+        rc = run_longest_sparse(a, d, r);
+        if (rc == ACGPU_E_UNSUPPORTED) {
+            acgpu_shard walk = r.shard;
+            uint64_t n = 0;
+            rc = run_inside(enqueue_longest, a, d, r, &walk, record_kind, d_out, cap, &n);
+            if (rc == ACGPU_OK || rc == ACGPU_E_OVERFLOW) rc = close_as_inside(r, n, walk.chain_exit);
+        }
+        break;
+    case ACGPU_MODE_WHOLEWORD:
+        if (rule.sequential) {
+            rc = run_wholeword_sequential(a, d, r);
+        } else { // Readable, folded keywords with non-word units: the WholeWordLongest walk without fail matches, unit by unit
+            DevTables Tf = folded_tables(d);
+            Tf.ww_fat = nullptr;
+            rc = run_wwlongest(a, d, r, Tf, true);
+        }
+        break;
+    case ACGPU_MODE_SHORTEST: rc = run_shortest(a, d, r); break;
+    case ACGPU_MODE_WWLONGEST:
+        // not fold-consistent: the Map class's String loop and both Readable loops fold in every lookup
+        // (S/WholeWordLongestMatchMap.java:252-288, :404) -- position parallel over w'; the Set class's String loop mixes
+        // raw and folded lookups (S/WholeWordLongestMatchSet.java:126,151,156) -- sequential
+        if (rule.sequential) rc = run_wwlongest_sequential(a, d, r);
+        else rc = run_wwlongest(a, d, r, t.fold_consistent ? d.T : folded_tables(d), false);
+        break;
+    default: rc = ACGPU_E_UNSUPPORTED;
+    }
+    if (rc == ACGPU_OK && sh->d_result)
+        HIP_TRY(launch_write_result(reinterpret_cast<acgpu_device_result *>(sh->d_result), r.h_slot[kSlotCount], stream));
+    return rc;
+}
+
+// validates a shard and runs the pipeline of the automaton's family; caller holds d.mu.
 int match_shard(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_kind, void *d_out, uint64_t cap,
                 uint64_t *n_out, hipStream_t stream, acgpu_profile *prof, bool readable) {
     int rc;
     if ((rc = check_shard(a, d, sh, record_kind, d_out, cap, stream))) return rc;
     *n_out = 0;
     if (prof) std::memset(prof, 0, sizeof(*prof));
-    const HostTables &t = a->t;
-    const ShardRule rule = shard_rule(t, record_kind, readable);
-    if (rule.all_pipeline) // (not fold-consistent: the Readable loop of WholeWord, an ordinary scan over w' = word o lower)
-        return run_sync(enqueue_all, a, d, sh, record_kind, d_out, cap, n_out, stream, prof, /*folded=*/!t.fold_consistent);
-    // the other families end with their count on the host (and some run the ALL pipeline inside): the device copy of the
-    // result is written behind the pipeline
-    acgpu_device_result *d_res = reinterpret_cast<acgpu_device_result *>(sh->d_result);
-    sh->d_result = nullptr;
-    switch (t.mode) {
-    case ACGPU_MODE_LONGEST:
-        // a selective suffix filter: a selection over all matches, unless the text turns out to be dense in them
-        rc = ACGPU_E_UNSUPPORTED;
-        if (filter_is_selective(t) && tunables().force_kernel != 1)
-            rc = match_longest_sparse(a, d, sh, record_kind, d_out, cap, n_out, stream, prof);
-        if (rc == ACGPU_E_UNSUPPORTED) rc = run_sync(enqueue_longest, a, d, sh, record_kind, d_out, cap, n_out, stream, prof);
-        break;
-    case ACGPU_MODE_WHOLEWORD:
-        if (rule.sequential) {
-            rc = match_wholeword_sequential(a, d, sh, record_kind, d_out, cap, n_out, stream, prof);
-        } else { // Readable, folded keywords with non-word units: the WholeWordLongest walk without fail matches, unit by unit
-            DevTables Tf = folded_tables(d);
-            Tf.ww_fat = nullptr;
-            rc = match_wwlongest(a, d, sh, record_kind, d_out, cap, n_out, stream, prof, Tf, true);
-        }
-        break;
-    case ACGPU_MODE_SHORTEST: rc = match_shortest(a, d, sh, record_kind, d_out, cap, n_out, stream, prof); break;
-    case ACGPU_MODE_WWLONGEST:
-        // not fold-consistent: the Map class's String loop and both Readable loops fold in every lookup
-        // (S/WholeWordLongestMatchMap.java:252-288, :404) -- position parallel over w'; the Set class's String loop mixes
-        // raw and folded lookups (S/WholeWordLongestMatchSet.java:126,151,156) -- sequential
-        if (rule.sequential) rc = match_wwlongest_sequential(a, d, sh, record_kind, d_out, cap, n_out, stream, prof);
-        else rc = match_wwlongest(a, d, sh, record_kind, d_out, cap, n_out, stream, prof, t.fold_consistent ? d.T : folded_tables(d), false);
-        break;
-    default: rc = ACGPU_E_UNSUPPORTED;
-    }
-    sh->d_result = d_res;
-    if (d_res && (rc == ACGPU_OK || rc == ACGPU_E_OVERFLOW)) HIP_TRY(launch_write_result(d_res, *n_out, stream));
-    return rc;
+    if ((rc = start_call(a, d, nullptr, sh, record_kind, d_out, cap, stream, prof != nullptr, readable))) return rc;
+    return collect(a, d, &d.call, n_out, prof, nullptr);
 }
 
 // acgpu_match_device_begin on a given scratch pool (the caller holds d.mu and has made d's device current)
 int begin_shard(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_kind, void *d_out, uint64_t cap, hipStream_t stream,
                 int want_profile, acgpu_ticket **ticket) {
     *ticket = nullptr;
-    const HostTables &t = a->t;
     int rc;
     if ((rc = check_shard(a, d, sh, record_kind, d_out, cap, stream))) return rc;
     Ticket *tk = nullptr;
     for (auto &cand : d.tickets)
         if (!cand.busy) { tk = &cand; break; }
     if (!tk) return ACGPU_E_INVALID; // too many calls in flight: collect one first
-    // enqueued without waiting: the AhoCorasick / WholeWord pipeline (one scan + ordering pass) and the LongestMatch pipelines
-    // (nothing of them needs the host).  The other families -- and LongestMatch over a dictionary with a selective suffix
-    // filter, whose sparse form falls back to the walk after looking at the match count -- run their call inside _begin: the
-    // ticket is complete when _begin returns (no completion marker: nothing in flight, the stream rule does not apply to it).
-    const bool all = shard_rule(t, record_kind, false).all_pipeline;
-    const bool enqueued = all || (t.mode == ACGPU_MODE_LONGEST && !(filter_is_selective(t) && tunables().force_kernel != 1));
-    open_call(tk->rec, tk->ev, enqueued ? tk->done : nullptr, tk->h_count, *sh, sh, record_kind, d_out, cap, stream, want_profile != 0,
-              false);
-    std::memset(&tk->sync_prof, 0, sizeof(tk->sync_prof));
-    if (enqueued) {
-        if ((rc = all ? enqueue_all(a, d, tk->rec, 0) : enqueue_longest(a, d, tk->rec, 0))) return rc;
+    if ((rc = start_call(a, d, tk, sh, record_kind, d_out, cap, stream, want_profile != 0, false))) return rc;
+    if (tk->rec.done) { // enqueued: in flight until _end or _abandon
         d.inflight++;
         d.inflight_stream = stream;
-    } else {
-        uint64_t n = 0;
-        rc = match_shard(a, d, sh, record_kind, d_out, cap, &n, stream, want_profile ? &tk->sync_prof : nullptr);
-        if (rc != ACGPU_OK && rc != ACGPU_E_OVERFLOW) return rc;
-        tk->h_count[0] = n; // (the record stays complete: the count is all collect() reads)
     }
     tk->busy = true;
     *ticket = reinterpret_cast<acgpu_ticket *>(tk);
@@ -2023,7 +1960,7 @@ int acgpu_match_device_abandon(const acgpu_automaton *ca, acgpu_ticket *ticket) 
     {
         std::lock_guard<std::mutex> lock(own->mu);
         if (!tk->busy) return ACGPU_E_INVALID;
-        if (!tk->rec.done) { // (ran inside _begin)
+        if (!tk->rec.done) { // (ran to its end inside _begin)
             tk->busy = false;
             return ACGPU_OK;
         }
@@ -2062,7 +1999,6 @@ int end_ticket(const acgpu_automaton *ca, acgpu_ticket *ticket, uint64_t *n_out,
     if (!tk->busy) return ACGPU_E_INVALID; // (collected by another thread meanwhile)
     tk->busy = false; // (whatever happens below, the ticket is collected)
     if (tk->rec.done) d->inflight--;
-    if (prof && tk->rec.form == CallForm::Complete) *prof = tk->sync_prof;
     return collect(a, *d, &tk->rec, n_out, prof, redone);
 }
 

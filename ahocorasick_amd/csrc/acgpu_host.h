@@ -48,13 +48,24 @@ struct DevBuf {
 
 // How a call's result is collected (collect(), acgpu_api.hip): the pipeline that was enqueued.
 enum class CallForm : uint8_t {
-    Complete,      // nothing to read from the device: the empty call, or a call that ran inside _begin (count in h_slot[0])
+    Complete,      // the empty call: nothing found, nothing to report
+    HostRun,       // ran to its end on the host (the families that need the host between their launches): count and chain exit in the slot
     States,        // k_ac_states + k_ac_states_out
     Ordered,       // a scan kernel and its ordering pass (k_permute, k_permute_wg, k_ww_compact), which reports into the slot
     FusedTail,     // the tile kernel or k_ww_pp with the fused tail: one kernel
     LongestBits,   // k_longest_bits
     LongestFollow, // k_longest_follow
     LongestWalk,   // the LONGEST walk pipeline
+};
+
+// The words of a record's pinned slot (CallRecord::h_slot), and the further words of the pool's own slot (DeviceState::h_counter)
+// that a call borrows while it runs.
+enum : int {
+    kSlotCount = 0,     // records found
+    kSlotFlag = 1,      // ALL: the overflow word; LONGEST: the bail flag
+    kSlotExit = 2,      // the chain's exit
+    kPoolChainHead = 3, // mark_chain: the chain head's index, behind it (kPoolChainHead + 1) the largest jump
+    kPoolBound = 5,     // the multi-device driver: record_bound's index
 };
 
 // One call on a scratch pool: what enqueueing it decided and what completing it needs.  A ticket carries one; the pool owns one
@@ -67,11 +78,13 @@ struct CallRecord {
     uint64_t cap = 0;
     hipStream_t stream = nullptr;
     hipEvent_t *ev = nullptr;          // ev[0] .. ev[2]: the profile's events
-    hipEvent_t done = nullptr;         // a ticket's completion marker; null: a synchronous call (or one that ran inside _begin)
+    hipEvent_t done = nullptr;         // a ticket's completion marker; null: a synchronous call (or one that ran to its end inside _begin)
     bool done_is_ev2 = false;          // the completion to wait for is ev[2] (the call's last kernel's own end), not `done`
-    bool one_kernel = false;           // the call was one kernel (the fused tail): ev[0] .. ev[2] is its dispatch, ev[1] is not recorded
-    bool profiled = false;
-    unsigned long long *h_slot = nullptr; // pinned, 64 bytes: {count, overflow word or bail flag, chain exit}
+    bool one_kernel = false;           // the call was one kernel (the fused tail, a sequential kernel): ev[0] .. ev[2] is all of it, ev[1] is not recorded
+    bool profiled = false;             // the events are recorded
+    bool behind_pass = false;          // HostRun: ev[0] .. ev[1] is what ran behind the pass inside the call, accounted as finalizing
+    acgpu_profile inside{};            // HostRun: the profile of a pass that ran inside the call on the pool's own record (run_inside)
+    unsigned long long *h_slot = nullptr; // pinned, 64 bytes: kSlotCount, kSlotFlag, kSlotExit
     CallForm form = CallForm::Complete;
     int level = 0;                     // ALL: 1 = the redo's form (the fused kernel, one scratch slice); LONGEST: the run-up level
     bool folded = false;               // WHOLEWORD: the scan saw the folded tables (folded_tables, acgpu_api.hip)
@@ -86,7 +99,6 @@ struct Ticket {
     unsigned long long *h_count = nullptr; // pinned, 64 bytes
     bool busy = false;
     CallRecord rec;
-    acgpu_profile sync_prof{}; // the profile of a call that ran inside _begin (zero for the empty call)
     void *owner = nullptr; // the DeviceState it belongs to
 };
 
@@ -132,7 +144,7 @@ struct DeviceState {
     void *bits_state_seen = nullptr;                     // (a re-allocated buffer, or a call that failed half way, is zeroed by a memset)
     DevBuf cands, region_cands;                          // ALL, split form: candidate positions, {first, count} per region
     DevBuf wwl_rs, wwl_mend, wwl_mid, wwl_sel, wwl_stop, wwl_nxt0; // WWLONGEST: walk starts, what each would report, where it stops
-    unsigned long long *h_counter = nullptr; // pinned
+    unsigned long long *h_counter = nullptr; // pinned, 64 bytes: the slot of the pool's own record, and the kPool words
     // match_all: two sets of slot counters alternate; the permute pass of a call zeroes the set the next call uses
     int cset = 0;
     bool cclean[2] = {false, false};

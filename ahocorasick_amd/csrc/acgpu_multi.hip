@@ -113,12 +113,12 @@ int record_bound(Share &s, const void *recs, uint64_t n, int record_kind, int fi
         return ACGPU_OK;
     }
     unsigned long long *d_slot = nullptr;
-    HIP_TRY(hipHostGetDevicePointer((void **)&d_slot, s.d->h_counter + 5, 0));
+    HIP_TRY(hipHostGetDevicePointer((void **)&d_slot, s.d->h_counter + kPoolBound, 0));
     hipLaunchKernelGGL(k_record_bound, dim3(1), dim3(1), 0, s.stream, (const int32_t *)recs, n, record_kind / 4, field,
                        (int32_t)std::max<int64_t>(value, -0x7fffffffll), upper ? 1 : 0, d_slot);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s.stream));
-    *idx = s.d->h_counter[5];
+    *idx = s.d->h_counter[kPoolBound];
     return ACGPU_OK;
 }
 

@@ -840,7 +840,8 @@ def test_async_begin_end_matches_synchronous_call():
 def test_async_begin_end_for_the_chain_families():
     """acgpu_match_device_begin/_end beyond AhoCorasick: the LongestMatch walk pipeline is enqueued without a host round trip
     (count and chain exit arrive through the ticket: three calls in flight, shards chained through entry / exit, Set and Map
-    records, overflow); the other families -- and LongestMatch over a selective dictionary -- run inside _begin."""
+    records, overflow); the other families -- and LongestMatch over a selective dictionary -- run inside _begin, and a ticketed
+    call of theirs is the synchronous call in every respect: count, records, chain exit, profile, overflow protocol, device result."""
     import torch
     from ahocorasick_amd.strings import Automaton as A
     from oracle.oracle import FAM_SHORTEST, FAM_WWLONGEST
@@ -909,6 +910,33 @@ def test_async_begin_end_for_the_chain_families():
     tk, rc = sel.match_device_begin(d3.data_ptr(), hay3.size, True, out3.data_ptr(), len(want3) + 8, stream=st)
     n, rc, _ = sel.match_device_end(tk)
     assert rc == N.OK and n == len(want3) and (out3[:n].cpu().numpy() == want3).all()
+    # ... and the same call in every other respect: count, chain exit, what the profile names, the overflow protocol, the device result
+    kw4, hay4 = _wwl_case(146, 150000)
+    wwl = A(N.MODE_WWLONGEST, kw4, False, word_chars=WORD)
+    want4 = Oracle(FAM_WWLONGEST, kw4, case_sensitive=False, lower=LOWER, word_chars=WORD).match(hay4)
+    d4 = torch.from_numpy(hay4.view(np.int16)).cuda()
+    for auto, d_hay, hay, want, kernel in ((sh, d2, hay2, want2, "k_ac"), (sel, d3, hay3, want3, "k_ac"), (wwl, d4, hay4, want4, "k_wwl_walk")):
+        assert len(want) > 5  # (so that a capacity of 5 overflows)
+        room = len(want) + 8
+        for cap_ in (room, 5):
+            bufs = [torch.zeros(4 + room * 3, dtype=torch.int32, device="cuda") for _ in range(2)]  # [device result | records]
+            n_s, rc_s, prof_s, exit_s = auto.match_device(d_hay.data_ptr(), hay.size, True, bufs[0].data_ptr() + 16, cap_, stream=st,
+                                                          profile=True, d_result=bufs[0].data_ptr())
+            tk, rc = auto.match_device_begin(d_hay.data_ptr(), hay.size, True, bufs[1].data_ptr() + 16, cap_, stream=st, profile=True,
+                                             d_result=bufs[1].data_ptr())
+            assert rc == N.OK
+            n_t, rc_t, prof_t = auto.match_device_end(tk, profile=True)
+            torch.cuda.current_stream().synchronize()
+            assert rc_s == rc_t == (N.OK if cap_ == room else N.E_OVERFLOW)
+            assert n_s == n_t == len(want) and exit_s == tk.chain_exit and exit_s >= 0
+            for key in ("scan_kernel", "scan_units", "n_matches"):
+                assert prof_s[key] == prof_t[key], key
+            assert prof_s["n_matches"] == len(want) and prof_s["scan_units"] >= hay.size and prof_s["scan_kernel"].startswith(kernel)
+            assert prof_s["scan_ms"] > 0 and prof_t["scan_ms"] > 0
+            got_s, got_t = (b_.cpu().numpy() for b_ in bufs)
+            k = min(len(want), cap_)
+            assert (got_s[4:4 + 3 * k].reshape(k, 3) == want[:k]).all() and (got_t[4:4 + 3 * k] == got_s[4:4 + 3 * k]).all()
+            assert (got_s[:4] == got_t[:4]).all() and int(got_s[:2].view(np.int64)[0]) == len(want) and got_s[2] == 0
 
 
 @pytest.mark.parametrize("family", ["ac", "wholeword", "longest", "shortest", "wwlongest"])
