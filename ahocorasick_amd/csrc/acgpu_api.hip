@@ -324,7 +324,9 @@ int borrow_counter_line(DeviceState &d, hipStream_t stream, bool clear) {
 
 // ALL-mode pipeline on one shard, the form for texts with dense matches: see enqueue_all.
 constexpr double kStatesFormDensity = 0.05; // records per unit of the pool's last call from which k_ac_states is taken
-int enqueue_states(acgpu_automaton *a, DeviceState &d, CallRecord &r, uint32_t hot_rows) {
+// counting: the direct form of a counting call (acgpu_count.hip) -- k_states_hist adds the owned positions' states to the pool's
+// visit words in place of the prefix sum's consumer, the record pass; the count still comes from the chunks' counts.
+int enqueue_states(acgpu_automaton *a, DeviceState &d, CallRecord &r, uint32_t hot_rows, bool counting = false) {
     const HostTables &t = a->t;
     const acgpu_shard *sh = &r.shard;
     hipEvent_t *ev = r.ev;
@@ -340,8 +342,11 @@ int enqueue_states(acgpu_automaton *a, DeviceState &d, CallRecord &r, uint32_t h
     S.hot_rows = hot_rows;
     const uint64_t span = sh->own_end - S.g0;
     // a lane's chunk: 1024 units, shorter (down to 256) when the text would leave lanes of the chip without one
+    // (development tunable states_chunk_log2: 8 .. 10 forces it -- 1 to 4 steps per chunk of the passes behind the walk on short texts)
     S.chunk_log2 = 10;
-    while (S.chunk_log2 > 8 && (span >> S.chunk_log2) < (uint64_t)ac_states_lanes_per_cu() * d.n_cu) --S.chunk_log2;
+    const int64_t forced_log2 = tunables().states_chunk_log2;
+    if (forced_log2 >= 8 && forced_log2 <= 10) S.chunk_log2 = (uint32_t)forced_log2;
+    else while (S.chunk_log2 > 8 && (span >> S.chunk_log2) < (uint64_t)ac_states_lanes_per_cu() * d.n_cu) --S.chunk_log2;
     const uint64_t chunks = (span + (1ull << S.chunk_log2) - 1) >> S.chunk_log2;
     S.n_waves = (uint32_t)((chunks + 63) / 64);
     S.n_chunks = (uint32_t)chunks;
@@ -357,17 +362,28 @@ int enqueue_states(acgpu_automaton *a, DeviceState &d, CallRecord &r, uint32_t h
     S.cap = r.cap;
     S.grid = (int)std::min<uint64_t>((uint64_t)d.n_cu * (ac_states_lanes_per_cu() / 1024u), (S.n_waves + 15) / 16);
     if ((rc = borrow_counter_line(d, stream, /*clear=*/true))) return rc; // (word 1: the "redo" flag of the result -- never raised here)
+    if (counting) {
+        CountCall &c = *d.count;
+        S.d_visits = (uint32_t *)d.visits.p;
+        S.n_states = t.hy_n_states;
+        const int64_t cform = tunables().count_form;
+        S.hist_hot = (cform & 2) ? 0u : std::min(t.hy_n_states, states_hist_max_hot());
+        S.hist_peel = (cform & 4) ? 0u : 1u;
+        if (!c.visits_zeroed) HIP_TRY(hipMemsetAsync(d.visits.p, 0, (size_t)t.hy_n_states * 4, stream));
+        c.visits_zeroed = true;
+    }
     if (r.profiled) HIP_TRY(hipEventRecord(ev[0], stream));
     HIP_TRY(launch_ac_states(d.T, S, t.range_cls, stream));
     if (r.profiled) HIP_TRY(hipEventRecord(ev[1], stream));
     HIP_TRY(launch_exclusive_scan(S.d_counts, S.n_chunks, (uint64_t *)d.offsets.p, (uint64_t *)d.scan_tmp.p, stream));
-    HIP_TRY(launch_ac_states_out(d.T, S, r.record_kind == ACGPU_REC_MAP, stream));
+    if (counting) HIP_TRY(launch_states_hist(S, d.n_cu, stream));
+    else HIP_TRY(launch_ac_states_out(d.T, S, r.record_kind == ACGPU_REC_MAP, stream));
     if (r.profiled) HIP_TRY(hipEventRecord(ev[2], stream));
     unsigned long long *d_slot = nullptr;
     if ((rc = slot_on_device(r, &d_slot))) return rc;
     HIP_TRY(launch_publish_result((const unsigned long long *)d.scan_tmp.p + scan_tiles_for(S.n_chunks), (const unsigned long long *)d.counter.p, d_slot,
                                   reinterpret_cast<acgpu_device_result *>(sh->d_result), stream));
-    return close_call(r, CallForm::States, "k_ac_states", sh->own_end - sh->own_begin);
+    return close_call(r, counting ? CallForm::StatesCount : CallForm::States, "k_ac_states", sh->own_end - sh->own_begin);
 }
 
 int collect(acgpu_automaton *a, DeviceState &d, CallRecord *r, uint64_t *n_out, acgpu_profile *prof, bool *redone);
@@ -399,6 +415,7 @@ int choose_states_form(acgpu_automaton *a, DeviceState &d, const CallRecord &r, 
         head.shard.d_result = nullptr;
         head.cap = 0;
         head.profiled = false;
+        head.counting = false;
         uint64_t n_head = 0;
         int prc = enqueue_states(a, d, head, st_hot);
         if (prc == ACGPU_OK) prc = collect(a, d, &head, &n_head, nullptr, nullptr);
@@ -863,7 +880,8 @@ int enqueue_all(acgpu_automaton *a, DeviceState &d, CallRecord &r, int level) {
     uint32_t st_hot = 0;
     if ((rc = choose_states_form(a, d, r, &st_hot))) return rc;
     if (st_hot) {
-        rc = enqueue_states(a, d, r, st_hot);
+        // (a counting call: its direct form; without room for the visit words, or with the tunable count_form against it, the records form)
+        rc = enqueue_states(a, d, r, st_hot, r.counting && d.count->direct_ok);
         if (rc != ACGPU_E_NOMEM) return rc; // (no room for 4 bytes of state per unit -- before anything was launched: the tile kernel it is)
     }
     AllScan A;
@@ -1448,9 +1466,11 @@ int collect(acgpu_automaton *a, DeviceState &d, CallRecord *r, uint64_t *n_out, 
         if (r->form == CallForm::LongestFollow) d.fol_level = std::max(d.fol_level, r->level + 1); // (the pool's later calls start there)
         // (the redo shares the scratch with the tickets still in flight: same stream, so stream order keeps them apart)
         acgpu_shard sh = r->shard;
+        const bool counting = r->counting;
         if (longest && r->done) sh.d_result = nullptr; // (a ticket's Longest redo leaves the device result to the first attempt, which says "redone")
         open_call(d.call, d.ev, nullptr, d.h_counter, sh, r->user_shard, r->record_kind, r->d_out, r->cap, r->stream, prof != nullptr,
                   r->folded);
+        d.call.counting = counting;
         if (redone) *redone = true;
         const int rc = longest ? enqueue_longest(a, d, d.call, level) : enqueue_all(a, d, d.call, level);
         if (rc) return rc;
@@ -1480,6 +1500,7 @@ int collect(acgpu_automaton *a, DeviceState &d, CallRecord *r, uint64_t *n_out, 
         prof->n_matches = *n_out;
         std::snprintf(prof->scan_kernel, sizeof(prof->scan_kernel), "%s", r->kname);
     }
+    if (r->counting) return count_collected(d, *r, *n_out);
     return *n_out > r->cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
 }
 
@@ -1644,6 +1665,7 @@ static int start_call(acgpu_automaton *a, DeviceState &d, Ticket *tk, acgpu_shar
     // (all_pipeline over tables that are not fold-consistent: the Readable loop of WholeWord, an ordinary scan over w' = word o lower)
     open_call(r, tk ? tk->ev : d.ev, tk && enqueued ? tk->done : nullptr, tk ? tk->h_count : d.h_counter, *sh, sh, record_kind, d_out, cap,
               stream, profiled, rule.all_pipeline && !t.fold_consistent);
+    r.counting = d.count != nullptr;
     if (rule.all_pipeline) return enqueue_all(a, d, r, 0);
     if (enqueued) return enqueue_longest(a, d, r, 0);
     // a host-run call ends with its count on the host (and some run the ALL pipeline inside): the device copy of the result is
@@ -1782,6 +1804,8 @@ int64_t acgpu_set_tunable(const char *name, int64_t value) {
     else if (!std::strcmp(name, "cursor_first_piece")) slot = &t.cursor_first_piece;
     else if (!std::strcmp(name, "cursor_max_piece")) slot = &t.cursor_max_piece;
     else if (!std::strcmp(name, "cursor_reservoir_bytes")) slot = &t.cursor_reservoir_bytes;
+    else if (!std::strcmp(name, "states_chunk_log2")) slot = &t.states_chunk_log2;
+    else if (!std::strcmp(name, "count_form")) slot = &t.count_form;
     if (!slot) return -1;
     return slot->exchange(value, std::memory_order_relaxed);
 }
@@ -1804,6 +1828,7 @@ int acgpu_build(int mode, const uint16_t *kw_units, const uint64_t *kw_off, uint
         delete a;
         return rc;
     }
+    a->n_given = n_kw;
     *out = a;
     return ACGPU_OK;
 }
@@ -2090,14 +2115,16 @@ static bool device_numa_cpus(int dev, cpu_set_t *set) {
 
 int scan_host_range(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack, uint64_t n_units, uint64_t lo, uint64_t hi,
                     uint64_t own_lo, uint64_t own_hi, int record_kind, uint64_t cap, uint64_t *n_out, int64_t *chain_io,
-                    void *d_out) {
+                    void *d_out, uint64_t *own_done) {
     const ShardRule rule = shard_rule(a->t, record_kind, false);
     const uint64_t C = kHostChunkUnits;
     const uint64_t nb = hi - lo; // units in the device buffer
     const uint32_t n_chunks = (uint32_t)((nb + C - 1) / C);
     const uint64_t ob = own_lo - lo, oe = own_hi - lo; // the owned range in the buffer
     hipStream_t stream = d.call_stream;
+    const bool counting = own_done != nullptr; // (a counting call's scan: a shard's records are consumed when it is collected, see acgpu_host.h)
     *n_out = 0;
+    if (own_done) *own_done = ob;
     int rc;
     if ((rc = d.stage_hay.ensure(nb * 2 + 16))) return rc;
     if (!d_out) {
@@ -2203,23 +2230,26 @@ int scan_host_range(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack
         uint64_t n_k = 0;
         const uint64_t room = total < cap ? cap - total : 0;
         rc = match_shard(a, d, &sh, record_kind, (char *)d_out + std::min(total, cap) * (uint64_t)record_kind, room, &n_k, stream, nullptr);
-        if (rc != ACGPU_OK && rc != ACGPU_E_OVERFLOW) {
+        if (rc != ACGPU_OK && !(rc == ACGPU_E_OVERFLOW && !counting)) {
+            if (rc == ACGPU_E_OVERFLOW) total = n_k; // (a counting call: this shard's records did not fit, what lies before it is counted)
             result = rc;
             break;
         }
-        total += n_k; // (beyond cap: the remaining shards only count)
+        if (!counting) total += n_k; // (beyond cap: the remaining shards only count)
         chain = piece_exit(rule, entry, c1, &sh, n_k);
+        if (own_done) *own_done = c1;
     }
     if (result != ACGPU_OK) worker_rc.store(result); // (stops the producers)
     join_all();
     if (result == ACGPU_OK && worker_rc.load() != ACGPU_OK) result = worker_rc.load();
     (void)hipStreamSynchronize(d.copy_stream); // nothing of this call stays in flight
-    if (result != ACGPU_OK) {
+    if (result != ACGPU_OK && !(result == ACGPU_E_OVERFLOW && counting)) {
         if (result == ACGPU_E_HIP) g_last_hip_error = (int)hipGetLastError();
         return result;
     }
     *n_out = total;
     if (chain_io) *chain_io = chain;
+    if (counting) return result;
     return total > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
 }
 

@@ -55,6 +55,53 @@ __global__ void k_cursor_page(const int32_t *__restrict__ src, int32_t *__restri
 
 } // namespace
 
+namespace acgpu {
+
+uint64_t reservoir_budget_bytes() { return (uint64_t)std::max<int64_t>(tunables().cursor_reservoir_bytes.load(std::memory_order_relaxed), 16); }
+
+void PieceRamp::start() {
+    piece = (uint64_t)std::max<int64_t>(1, tunables().cursor_first_piece.load(std::memory_order_relaxed));
+    seen_records = seen_units = 0;
+}
+
+// the next step of the ramp, capped so that the density seen so far fills at most half the reservoir budget
+uint64_t PieceRamp::next_size(uint64_t left, uint64_t budget_recs) const {
+    uint64_t size = std::min<uint64_t>(piece, left);
+    if (seen_records && seen_units) {
+        const double per_unit = (double)seen_records / (double)seen_units;
+        const double fit = (double)(budget_recs / 2) / per_unit;
+        if (fit < (double)size) size = std::max<uint64_t>(1, (uint64_t)fit);
+    }
+    return size;
+}
+
+uint64_t PieceRamp::predicted_room(uint64_t size, uint64_t budget_recs) const {
+    if (!seen_units) return 0;
+    const double pred = (double)seen_records / (double)seen_units * (double)size;
+    return std::min<uint64_t>(budget_recs, (uint64_t)(pred * 1.25) + 1024);
+}
+
+bool PieceRamp::on_overflow(uint64_t *size, uint64_t cnt, uint64_t budget_recs, uint64_t *room) const {
+    if (cnt <= budget_recs) { // a larger reservoir
+        *room = std::min<uint64_t>(budget_recs, cnt + cnt / 8);
+    } else if (*size > 1) { // a smaller piece: half the budget by this piece's density
+        *size = std::max<uint64_t>(1, (uint64_t)((double)*size * (double)(budget_recs / 2) / (double)cnt));
+        *room = budget_recs;
+    } else {
+        return false;
+    }
+    return true;
+}
+
+void PieceRamp::advance(uint64_t size, uint64_t cnt) {
+    seen_records += cnt;
+    seen_units += size;
+    const uint64_t max_piece = (uint64_t)std::max<int64_t>(1, tunables().cursor_max_piece.load(std::memory_order_relaxed));
+    piece = std::min<uint64_t>(max_piece, std::max<uint64_t>(size, 1) * 4);
+}
+
+} // namespace acgpu
+
 struct acgpu_cursor {
     acgpu_automaton *a = nullptr; // nullptr: detached by acgpu_free
     int device = -1;
@@ -66,8 +113,7 @@ struct acgpu_cursor {
     // the scan
     uint64_t pos = 0;      // owned units [0, pos) have been scanned
     int64_t chain = 0;     // the chain's entry into the next piece (haystack coordinates)
-    uint64_t piece = 0;    // owned units of the next piece (before the density cap)
-    uint64_t seen_records = 0, seen_units = 0; // what the pieces scanned so far yielded (the density estimate)
+    PieceRamp ramp;        // the sizes of the pieces
     // the reservoir: records [res_r, res_n) of the current piece are not handed out yet; positions relative to res_base
     void *res = nullptr;
     uint64_t res_bytes = 0;
@@ -105,7 +151,7 @@ int grow_reservoir(acgpu_cursor *c, uint64_t bytes) {
     return ACGPU_OK;
 }
 
-uint64_t budget_bytes() { return (uint64_t)std::max<int64_t>(tunables().cursor_reservoir_bytes.load(std::memory_order_relaxed), 16); }
+uint64_t budget_bytes() { return reservoir_budget_bytes(); }
 
 // The whole text as one shard (the loops that exist only as one sequential kernel): copied to the pool's staging buffer and
 // scanned into the reservoir, which grows to the exact count -- past the budget if device memory allows.
@@ -152,20 +198,12 @@ int scan_piece(acgpu_cursor *c, DeviceState &d) {
     const ShardRule rule = shard_rule(a->t, c->record_kind, false);
     const uint64_t rk = (uint64_t)c->record_kind;
     const uint64_t budget_recs = std::max<uint64_t>(budget_bytes() / rk, 1);
-    // the size: the next step of the ramp, capped so that the density seen so far fills at most half the reservoir budget
-    uint64_t size = std::min<uint64_t>(c->piece, c->n - c->pos);
-    if (c->seen_records && c->seen_units) {
-        const double per_unit = (double)c->seen_records / (double)c->seen_units;
-        const double fit = (double)(budget_recs / 2) / per_unit;
-        if (fit < (double)size) size = std::max<uint64_t>(1, (uint64_t)fit);
-    }
+    uint64_t size = c->ramp.next_size(c->n - c->pos, budget_recs);
     for (;;) {
         const uint64_t own_lo = c->pos, own_hi = own_lo + size;
         const uint64_t lo = own_lo - std::min(rule.left, own_lo), hi = std::min<uint64_t>(c->n, own_hi + rule.right);
         // predicted records: room for them (within the budget) before the scan, so that a steady text is not scanned twice
-        if (c->seen_units) {
-            const double pred = (double)c->seen_records / (double)c->seen_units * (double)size;
-            const uint64_t want = std::min<uint64_t>(budget_recs, (uint64_t)(pred * 1.25) + 1024);
+        if (const uint64_t want = c->ramp.predicted_room(size, budget_recs)) {
             int rc = grow_reservoir(c, want * rk);
             if (rc) return rc;
         } else if (!c->res) { // (a record per unit: natural text against a word list has 0.8)
@@ -180,14 +218,9 @@ int scan_piece(acgpu_cursor *c, DeviceState &d) {
         c->st.scan_end = std::max<uint64_t>(c->st.scan_end, hi);
         if (rc == ACGPU_E_OVERFLOW) {
             c->st.rescans++;
-            if (cnt <= budget_recs) { // a larger reservoir
-                if ((rc = grow_reservoir(c, std::min<uint64_t>(budget_recs, cnt + cnt / 8) * rk))) return rc;
-            } else if (size > 1) { // a smaller piece: half the budget by this piece's density
-                size = std::max<uint64_t>(1, (uint64_t)((double)size * (double)(budget_recs / 2) / (double)cnt));
-                if ((rc = grow_reservoir(c, budget_recs * rk))) return rc;
-            } else {
-                return ACGPU_E_NOMEM; // one unit's records do not fit the budget
-            }
+            uint64_t room = 0;
+            if (!c->ramp.on_overflow(&size, cnt, budget_recs, &room)) return ACGPU_E_NOMEM; // one unit's records do not fit the budget
+            if ((rc = grow_reservoir(c, room * rk))) return rc;
             continue;
         }
         if (rc) return rc;
@@ -196,10 +229,7 @@ int scan_piece(acgpu_cursor *c, DeviceState &d) {
         c->res_r = 0;
         c->res_base = (int32_t)lo;
         c->pos = own_hi;
-        c->seen_records += cnt;
-        c->seen_units += size;
-        const uint64_t max_piece = (uint64_t)std::max<int64_t>(1, tunables().cursor_max_piece.load(std::memory_order_relaxed));
-        c->piece = std::min<uint64_t>(max_piece, std::max<uint64_t>(size, 1) * 4);
+        c->ramp.advance(size, cnt);
         return ACGPU_OK;
     }
 }
@@ -274,7 +304,7 @@ int acgpu_cursor_open(const acgpu_automaton *ca, const uint16_t *haystack, uint6
     c->record_kind = record_kind;
     const HostTables &t = a->t;
     c->whole = one_piece(shard_rule(t, record_kind, false), t);
-    c->piece = (uint64_t)std::max<int64_t>(1, tunables().cursor_first_piece.load(std::memory_order_relaxed));
+    c->ramp.start();
     try {
         std::lock_guard<std::mutex> l(a->mu);
         a->open_cursors.insert(c);

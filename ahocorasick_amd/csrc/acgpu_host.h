@@ -51,6 +51,7 @@ enum class CallForm : uint8_t {
     Complete,      // the empty call: nothing found, nothing to report
     HostRun,       // ran to its end on the host (the families that need the host between their launches): count and chain exit in the slot
     States,        // k_ac_states + k_ac_states_out
+    StatesCount,   // k_ac_states + k_states_hist: a counting call's direct form, no records (acgpu_count.hip)
     Ordered,       // a scan kernel and its ordering pass (k_permute, k_permute_wg, k_ww_compact), which reports into the slot
     FusedTail,     // the tile kernel or k_ww_pp with the fused tail: one kernel
     LongestBits,   // k_longest_bits
@@ -88,6 +89,7 @@ struct CallRecord {
     CallForm form = CallForm::Complete;
     int level = 0;                     // ALL: 1 = the redo's form (the fused kernel, one scratch slice); LONGEST: the run-up level
     bool folded = false;               // WHOLEWORD: the scan saw the folded tables (folded_tables, acgpu_api.hip)
+    bool counting = false;             // a shard call of acgpu_count_*: collect() hands its result to the pool's CountCall
     uint64_t scanned = 0;
     char kname[64] = {0};
 };
@@ -101,6 +103,35 @@ struct Ticket {
     CallRecord rec;
     void *owner = nullptr; // the DeviceState it belongs to
 };
+
+// One acgpu_count_u16 / acgpu_count_device call (acgpu_count.hip), set in DeviceState::count while it runs: every shard call
+// it makes is a counting call (CallRecord::counting) whose result collect() turns into counts -- the visit words of a direct
+// piece, or the keyword_id column of the records in the call's reservoir -- instead of handing records on.
+struct CountCall {
+    unsigned long long *d_counts = nullptr; // device, n_counts words: added to
+    uint32_t n_counts = 0;
+    bool direct_ok = false;      // the visit words are there (and the tunable count_form allows the direct form)
+    bool visits_zeroed = false;  // ... and zeroed on the call's stream (before the first direct piece)
+    uint64_t through_reservoir = 0; // records counted in the records form
+    acgpu_count_stats st{};
+};
+
+// The sizes of the pieces a text is scanned in when its records go through a reservoir of bounded size (the cursor, the counting
+// calls): a ramp -- "cursor_first_piece", then four times the piece before, up to "cursor_max_piece" -- capped so that the records
+// seen per unit so far fill at most half of the reservoir's budget.
+struct PieceRamp {
+    uint64_t piece = 0;                        // owned units of the next piece (before the density cap)
+    uint64_t seen_records = 0, seen_units = 0; // what the pieces scanned so far yielded (the density estimate)
+    void start();
+    uint64_t next_size(uint64_t left, uint64_t budget_recs) const; // the next piece's owned units
+    // records to have room for before a piece of `size` units is scanned (0: nothing is known yet)
+    uint64_t predicted_room(uint64_t size, uint64_t budget_recs) const;
+    // A piece of `size` units yielded cnt records, more than the reservoir held: *room = the records to make room for, and
+    // `size` shrinks if even the budget does not hold them.  false: one unit's records do not fit the budget.
+    bool on_overflow(uint64_t *size, uint64_t cnt, uint64_t budget_recs, uint64_t *room) const;
+    void advance(uint64_t size, uint64_t cnt);
+};
+uint64_t reservoir_budget_bytes(); // tunable "cursor_reservoir_bytes"
 
 struct DeviceState {
     std::mutex mu;   // one call at a time on this scratch pool (the automaton's own mutex only guards its map of these)
@@ -139,6 +170,8 @@ struct DeviceState {
     DevBuf lenbig, todo;                                 // LONGEST: escaped lengths; root-table form: flagged chunks
     DevBuf chainbits;                                    // LONGEST: one bit per position, set where the chain reports a match
     DevBuf bits_state;                                   // k_longest_bits: exit / flag / count, look-back words, region counter -- zero between calls
+    DevBuf visits, count_res, count_out;                 // acgpu_count_*: visit words (4 bytes per state of the compact automaton), the reservoir, the host entry's counts
+    CountCall *count = nullptr;                          // the counting call that runs on this pool (it holds mu), or nullptr
     double all_density = -1.0;                           // ALL: records per unit of this pool's last call (-1: none yet): k_ac_states or the tile kernel
     int fol_level = 0;                                   // k_longest_follow: 0 = run-up of 128 positions, 1 = of a whole segment (a call's chains had not merged), 2 = not for this pool's texts
     void *bits_state_seen = nullptr;                     // (a re-allocated buffer, or a call that failed half way, is zeroed by a memset)
@@ -170,6 +203,7 @@ struct DeviceState {
         for (auto &q : pin) if (q) (void)hipHostFree(q);
         if (batch_pin) (void)hipHostFree(batch_pin);
         batch_off.release(); batch_out.release();
+        visits.release(); count_res.release(); count_out.release();
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
         for (auto &e : chunk_ev) if (e) (void)hipEventDestroy(e);
         for (auto &e : ev) if (e) (void)hipEventDestroy(e);
@@ -229,6 +263,7 @@ struct acgpu_automaton {
     std::set<struct acgpu_cursor *> open_cursors;                                // guarded by mu: the same for cursors (acgpu_cursor.hip)
     std::mutex mu;                                                               // guards `dev`, `stream_cache` and `open_streams`
     std::map<std::pair<int, int>, std::unique_ptr<acgpu::DeviceState>> dev;      // (HIP device, lane) -> scratch pool + tables
+    uint32_t n_given = 0;                                                        // keywords handed to acgpu_build (empty and duplicate ones included)
 };
 
 namespace acgpu {
@@ -280,8 +315,15 @@ int end_ticket(const acgpu_automaton *a, acgpu_ticket *ticket, uint64_t *n_out, 
 // device buffer d.stage_hay (buffer unit 0 = unit lo), the owned range [own_lo, own_hi) is scanned as shards of it on
 // d.call_stream, the records (buffer relative) land in d.stage_out -- or in d_out, a device buffer of cap records, when it is
 // given.  chain: in = entry, out = exit (buffer relative).
+// own_done given -- a counting call's scan (d.count is set; acgpu_count.hip is the only such caller): every shard's records are consumed when it is collected, so each shard writes to the start of
+// d_out; the scan stops at the first shard whose records do not fit -- *own_done = the buffer position up to which the owned
+// units have been counted (own_hi - lo when all were), *n_out = that shard's records, *chain = the entry into it.
 int scan_host_range(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack, uint64_t n_units, uint64_t lo, uint64_t hi,
                     uint64_t own_lo, uint64_t own_hi, int record_kind, uint64_t cap, uint64_t *n_out, int64_t *chain,
-                    void *d_out = nullptr);
+                    void *d_out = nullptr, uint64_t *own_done = nullptr);
+
+// collect() of a counting shard call that found n records: counts them (acgpu_count.hip).  ACGPU_E_OVERFLOW: they did not fit
+// the reservoir, nothing was counted.
+int count_collected(DeviceState &d, const CallRecord &r, uint64_t n);
 
 } // namespace acgpu

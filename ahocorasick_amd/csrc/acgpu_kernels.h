@@ -317,12 +317,23 @@ struct AcStatesLaunch {
     void *d_out;
     uint64_t cap;
     int grid;
+    // the counting form (k_states_hist in place of the record pass)
+    uint32_t *d_visits;   // per h-id: how often the text stood in that state at an owned position (only states that report matches are counted)
+    uint32_t n_states;    // entries of d_visits
+    uint32_t hist_hot;    // states below this number are counted in LDS and flushed once per workgroup (0: every state by global atomics)
+    uint32_t hist_peel;   // 1: the lanes that share the first active lane's state are added as one
 };
 uint32_t ac_states_chunk_units();
 uint32_t ac_states_lanes_per_cu();
 uint32_t ac_states_hot_rows(uint32_t n_cls, uint32_t n_dense, uint32_t page_bytes); // 0: does not fit
 hipError_t launch_ac_states(const DevTables &t, const AcStatesLaunch &l, bool range, hipStream_t stream);
 hipError_t launch_ac_states_out(const DevTables &t, const AcStatesLaunch &l, bool map, hipStream_t stream);
+// Counting without records (acgpu_count_*): the state words of a k_ac_states launch -> l.d_visits; after the call's last piece the
+// visits -> per-keyword counts (64-bit, added); and the records form: the keyword_id column of n Map records -> the same counts.
+uint32_t states_hist_max_hot(); // the most states k_states_hist counts in LDS
+hipError_t launch_states_hist(const AcStatesLaunch &l, int n_cu, hipStream_t stream);
+hipError_t launch_states_spread(const DevTables &t, const uint32_t *d_visits, unsigned long long *d_counts, uint32_t n_counts, hipStream_t stream);
+hipError_t launch_count_ids(const void *d_map_recs, uint64_t n, unsigned long long *d_counts, uint32_t n_counts, bool peel, hipStream_t stream);
 } // namespace acgpu
 
 namespace acgpu {

@@ -398,6 +398,136 @@ __global__ __launch_bounds__(256) void k_ac_states_out(DevTables T, AcStatesLaun
     }
 }
 
+// ---- counting without records (acgpu_count_*, acgpu_count.hip) -----------------------------------------------------------------
+// The per-keyword counts of a text are a histogram of its state words and one pass over the states: every state lists the
+// keywords that end in it (hy_out / hy_ids, closed over suffixes), so counts[id] = sum over the states s that list id of
+// visits[s].  k_states_hist takes the place of the prefix sum and the record pass; k_states_spread runs once per call.
+constexpr int kHistBlock = 1024;
+constexpr uint32_t kHistMaxHot = 32768; // 128 KiB of LDS counters: one workgroup per CU
+
+// +1 on ctr[key] for every lane with `valid`.  peel: the lanes that hold the first valid lane's key are added as one (a text that
+// stays in one state, or whose records carry one id, is one add per wave instead of 64 on one address).
+template <typename C, typename Add>
+__device__ __forceinline__ void wave_count_key(bool valid, uint32_t key, bool peel, Add add) {
+    if (!peel) {
+        if (valid) add(key, (C)1);
+        return;
+    }
+    const unsigned long long act = __ballot(valid);
+    if (act == 0ull) return; // wave-uniform
+    const uint32_t lead = (uint32_t)__ffsll((long long)act) - 1u;
+    const uint32_t first = (uint32_t)__shfl((int)key, (int)lead);
+    const unsigned long long same = __ballot(valid && key == first);
+    if (lane_id() == lead) add(first, (C)__popcll(same));
+    else if (valid && key != first) add(key, (C)1);
+}
+
+// The state words are read in the order they lie in memory -- quad q of the buffer is group (q / 64) mod 2^(chunk_log2 - 2) of
+// lane q mod 64 of wave q >> (chunk_log2 + 4): st_index backwards, whole lines per wave -- since a histogram does not care for
+// the order of the positions.  Masks as in k_ac_states_out: the up to three positions in front of own_begin do not count, the
+// partial group at own_end is read word by word, nothing beyond own_end (never written) is read.
+__global__ __launch_bounds__(kHistBlock) void k_states_hist(AcStatesLaunch L) {
+    extern __shared__ uint32_t hist[];
+    const uint32_t H = L.hist_hot;
+    for (uint32_t i = threadIdx.x; i < H; i += blockDim.x) hist[i] = 0u;
+    __syncthreads();
+    const uint32_t gl2 = L.chunk_log2 - 2u; // groups per chunk (log2)
+    const uint64_t n_quads = ((uint64_t)L.n_waves * 64u) << gl2;
+    const bool peel = L.hist_peel != 0u;
+    auto add = [&](uint32_t s, uint32_t n) {
+        if (s < H) __hip_atomic_fetch_add(&hist[s], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        else if (s < L.n_states) __hip_atomic_fetch_add(&L.d_visits[s], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    // (q0 is uniform over the workgroup: every wave makes the same number of rounds, the ballots of the peel see whole waves)
+    for (uint64_t q0 = (uint64_t)blockIdx.x * kHistBlock; q0 < n_quads; q0 += (uint64_t)gridDim.x * kHistBlock) {
+        const uint64_t q = q0 + threadIdx.x;
+        const uint32_t l = (uint32_t)(q & 63u), g = (uint32_t)((q >> 6) & ((1u << gl2) - 1u));
+        const uint64_t w = q >> (6u + gl2);
+        const uint64_t p = (uint64_t)L.g0 + (((w << 6) + l) << L.chunk_log2) + g * 4u; // the group's first position
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (q < n_quads && p < L.own_end) {
+            if (p + 4u <= L.own_end) {
+                v = *reinterpret_cast<const uint4 *>(L.d_state + q * 4u);
+            } else {
+                v.x = L.d_state[q * 4u];
+                if (p + 1u < L.own_end) v.y = L.d_state[q * 4u + 1u];
+                if (p + 2u < L.own_end) v.z = L.d_state[q * 4u + 2u];
+            }
+            if (p < L.own_begin) {
+                if (p + 0u < L.own_begin) v.x = 0u;
+                if (p + 1u < L.own_begin) v.y = 0u;
+                if (p + 2u < L.own_begin) v.z = 0u;
+                if (p + 3u < L.own_begin) v.w = 0u;
+            }
+        }
+        wave_count_key<uint32_t>((v.x & kHyOut) != 0u, v.x & kHyIdMask, peel, add);
+        wave_count_key<uint32_t>((v.y & kHyOut) != 0u, v.y & kHyIdMask, peel, add);
+        wave_count_key<uint32_t>((v.z & kHyOut) != 0u, v.z & kHyIdMask, peel, add);
+        wave_count_key<uint32_t>((v.w & kHyOut) != 0u, v.w & kHyIdMask, peel, add);
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < H; i += blockDim.x) {
+        const uint32_t c = hist[i];
+        if (c) __hip_atomic_fetch_add(&L.d_visits[i], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// one lane per state: a visited state's count goes to every keyword it lists
+__global__ __launch_bounds__(256) void k_states_spread(DevTables T, const uint32_t *__restrict__ visits, unsigned long long *counts, uint32_t n_counts) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= T.hy_n_states) return;
+    const unsigned long long v = visits[s];
+    if (v == 0ull) return;
+    const uint2 o = reinterpret_cast<const uint2 *>(T.hy_out)[s]; // {mask, index into hy_ids | bit 31: the id itself}
+    if (o.y & 0x80000000u) {
+        const uint32_t id = o.y & 0x7fffffffu;
+        if (id < n_counts) __hip_atomic_fetch_add(&counts[id], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+    const uint32_t n = (uint32_t)__popc(o.x);
+    for (uint32_t j = 0; j < n; ++j) {
+        const uint32_t id = T.hy_ids[o.y + j];
+        if (id < n_counts) __hip_atomic_fetch_add(&counts[id], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// the records form: the keyword_id column of n Map records
+__global__ __launch_bounds__(256) void k_count_ids(const int32_t *__restrict__ recs, uint64_t n, unsigned long long *counts, uint32_t n_counts, int peel) {
+    auto add = [&](uint32_t id, unsigned long long k) { __hip_atomic_fetch_add(&counts[id], k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    for (uint64_t b = (uint64_t)blockIdx.x * blockDim.x; b < n; b += (uint64_t)gridDim.x * blockDim.x) { // (b: uniform over the workgroup)
+        const uint64_t i = b + threadIdx.x;
+        const uint32_t id = i < n ? (uint32_t)recs[i * 3u + 2u] : ~0u;
+        wave_count_key<unsigned long long>(id < n_counts, id, peel != 0, add);
+    }
+}
+
+uint32_t states_hist_max_hot() { return kHistMaxHot; }
+
+hipError_t launch_states_hist(const AcStatesLaunch &l, int n_cu, hipStream_t stream) {
+    const size_t lds = (size_t)l.hist_hot * 4;
+    // (per launch, as launch_ac_states does: the attribute belongs to the current device's copy of the kernel, and a process may
+    // count on several devices; the value is always the largest a launch can ask for)
+    const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_states_hist), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kHistMaxHot * 4));
+    if (attr != hipSuccess) return attr;
+    const uint64_t n_quads = ((uint64_t)l.n_waves * 64u) << (l.chunk_log2 - 2u);
+    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_cu, (n_quads + kHistBlock - 1) / kHistBlock));
+    hipLaunchKernelGGL(k_states_hist, dim3(grid), dim3(kHistBlock), lds, stream, l);
+    return hipGetLastError();
+}
+
+hipError_t launch_states_spread(const DevTables &t, const uint32_t *d_visits, unsigned long long *d_counts, uint32_t n_counts, hipStream_t stream) {
+    if (!t.hy_n_states) return hipSuccess;
+    hipLaunchKernelGGL(k_states_spread, dim3((t.hy_n_states + 255) / 256), dim3(256), 0, stream, t, d_visits, d_counts, n_counts);
+    return hipGetLastError();
+}
+
+hipError_t launch_count_ids(const void *d_map_recs, uint64_t n, unsigned long long *d_counts, uint32_t n_counts, bool peel, hipStream_t stream) {
+    if (!n) return hipSuccess;
+    const unsigned grid = (unsigned)std::min<uint64_t>((n + 255) / 256, 8192);
+    hipLaunchKernelGGL(k_count_ids, dim3(grid), dim3(256), 0, stream, (const int32_t *)d_map_recs, n, d_counts, n_counts, peel ? 1 : 0);
+    return hipGetLastError();
+}
+
 uint32_t ac_states_chunk_units() { return 1u << kStChunkLog2; }
 uint32_t ac_states_lanes_per_cu() { return (uint32_t)kStWgsPerCu * kStBlock; }
 // rows of the dense group the kernel can keep in LDS next to `page_bytes` of class pages (0: range classes)

@@ -168,6 +168,34 @@ class Automaton:
                       scan_units=prof.scan_units, n_matches=prof.n_matches, scan_kernel=prof.scan_kernel.decode())
         return int(n_out.value), rc, pd, int(sh.chain_exit)
 
+    def count_host(self, hay_units):
+        """acgpu_count_u16: haystack in host memory -> (uint64 array with one count per keyword given to the constructor,
+        stats dict).  No record leaves the device."""
+        hay = np.ascontiguousarray(hay_units, dtype=np.uint16)
+        n = int(hay.size)
+        buf_in = hay if n else np.zeros(1, np.uint16)
+        counts = np.zeros(max(len(self.keywords), 1), dtype=np.uint64)
+        st = N.CountStats()
+        N.check(N.lib().acgpu_count_u16(self._h, _vp(buf_in), n, _vp(counts), len(self.keywords), ctypes.byref(st)), "acgpu_count_u16")
+        return counts[:len(self.keywords)], {f: int(getattr(st, f)) for f, _ in N.CountStats._fields_}
+
+    def count_device(self, d_hay_ptr, n_units, d_counts_ptr, own=None, text_begin=True, text_end=True, chain_entry=None, stream=0):
+        """acgpu_count_device on raw device pointers: ADDS this shard's counts to the uint64 device array d_counts_ptr (one
+        word per keyword given to the constructor, zeroed by the caller).  Returns (rc, stats dict, chain_exit)."""
+        sh = N.Shard()
+        sh.d_result = None
+        sh.d_hay = d_hay_ptr
+        sh.n_units = n_units
+        sh.own_begin, sh.own_end = (0, n_units) if own is None else own
+        sh.text_begin = 1 if text_begin else 0
+        sh.text_end = 1 if text_end else 0
+        sh.chain_entry = sh.own_begin if chain_entry is None else chain_entry
+        sh.chain_exit = -1
+        st = N.CountStats()
+        rc = N.lib().acgpu_count_device(self._h, ctypes.byref(sh), d_counts_ptr, len(self.keywords), ctypes.c_void_p(stream),
+                                        ctypes.byref(st))
+        return rc, {f: int(getattr(st, f)) for f, _ in N.CountStats._fields_}, int(sh.chain_exit)
+
 
     def match_device_begin(self, d_hay_ptr, n_units, with_ids, d_out_ptr, cap, own=None, text_begin=True, text_end=True,
                            stream=0, profile=False, d_result=None, chain_entry=None):
@@ -455,6 +483,14 @@ class StringSet:
         finally:
             pages.close()  # (a long haystack's cursor: closed at the first False, the rest is never scanned)
 
+    def count(self, haystack):
+        """Not in the reference: how often every keyword of the constructor's list is reported for `haystack` -- what a listener
+        doing counts[index_of(keyword)] += 1; return True would hold (a duplicate keyword: its last occurrence in the list
+        counts, for ShortestMatch its first) -- as a uint64 array, computed on the device without a record being handed out."""
+        if haystack is None:
+            raise TypeError("haystack is None")
+        return self._auto.count_host(utf16(haystack))[0]
+
     def find_all(self, haystack):
         """Convenience (not in the reference): the (n,2) int32 array of (start, end) records."""
         return self._auto.match_host(utf16(haystack), with_ids=False)
@@ -518,6 +554,14 @@ class StringMap:
                     return
         finally:
             st.close()
+
+    def count(self, haystack):
+        """Not in the reference: how often the listener of match(String, ...) would be called with each value -- a uint64 array
+        aligned with the constructor's keyword / value lists (a duplicate keyword: the value that won), computed on the
+        device without a record being handed out."""
+        if haystack is None:
+            raise TypeError("haystack is None")
+        return self._auto.count_host(utf16(haystack))[0]
 
     def find_all(self, haystack):
         """Convenience (not in the reference): the (n,3) int32 array of (start, end, keyword_index) records."""

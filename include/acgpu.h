@@ -57,6 +57,10 @@
  *                                               (256 MiB): the piece's records
  *      page staging (pinned, device-mapped)     cap x record_kind of the
  *                                               largest page handed out
+ *    A counting call (acgpu_count_* below) needs the pool's scratch for ONE piece as well, plus, kept by the pool:
+ *      visit words (device)                     4 bytes per state of the compact automaton
+ *      reservoir (device)                       up to cursor_reservoir_bytes: the Map records of a piece
+ *                                               that is not counted directly
  */
 #ifndef ACGPU_H
 #define ACGPU_H
@@ -465,6 +469,52 @@ int acgpu_cursor_get_stats(const acgpu_cursor *c, acgpu_cursor_stats *st);
 void acgpu_cursor_close(acgpu_cursor *c);
 
 /*
+ * Counting: how often every keyword occurs -- what a listener that does nothing but counts[value]++ would hold -- without a
+ * record being handed out.  counts[i] = the number of records with keyword_id == i that acgpu_match_u16 / acgpu_match_device
+ * with ACGPU_REC_MAP would return for the same automaton, text and shard: every family, the word matchers over tables that are
+ * not fold-consistent included; ids as in the Map records: the LAST duplicate of a keyword is counted, for Shortest the FIRST;
+ * the slots of empty keywords and of the other duplicates stay 0.
+ *  n_counts : the number of keywords given to acgpu_build (else ACGPU_E_INVALID).
+ *  acgpu_count_u16    : haystack in HOST memory, n_units < 2^31; OVERWRITES the host array counts[n_counts].  Without a device
+ *                       it fails as acgpu_match_u16 does and leaves counts untouched.
+ *  acgpu_count_device : the shard as for acgpu_match_device (halos, text_begin / text_end, chain_entry in, chain_exit out;
+ *                       d_result is not written); ADDS to the device array d_counts[n_counts] (8-byte aligned), which the caller
+ *                       zeroes -- shards, ranks and steps accumulate into one array (AhoCorasick and WholeWord counts are
+ *                       additive over the shards of a text; the chain families hand chain_exit on to the next shard's
+ *                       chain_entry).  Synchronous: everything is enqueued on `stream`; the call waits for that stream
+ *                       once per piece (for the piece's record count, as acgpu_match_device does) and once at the end.  The
+ *                       STREAM RULE above applies (tickets in flight on another stream: ACGPU_E_INVALID, nothing is added).
+ *                       After any other error d_counts is undefined (pieces already counted have been added, visit tallies of
+ *                       direct pieces have not): zero it before the next use.
+ *  st       : NULL, or receives how the text was counted.
+ * Errors as for the match calls; never ACGPU_E_OVERFLOW (there is no caller capacity).
+ * How it counts: the owned units are cut into pieces as a cursor's are (the same ramp -- cursor_first_piece, x 4,
+ * cursor_max_piece -- density cap and rescan rules; the chain handed on from piece to piece), and a piece is counted
+ *  - directly (ACGPU_MODE_ALL, where a record call would take the states form -- dense matches, a compact automaton): the
+ *    automaton's state behind every owned unit is tallied per state (4-byte visit words), and after the last piece every
+ *    visited state's tally is added to each keyword that ends in it.  No record is written, ordered or copied;
+ *  - or through Map records in a device reservoir of the call's own, whose keyword_id column is added to the counts on the
+ *    device.  Records that do not fit the reservoir: the piece is scanned again (st->rescans), larger reservoir or smaller piece.
+ * A counting call teaches the pool its density as a record call does: on a word list in natural text the first piece goes
+ * through records, the following ones are counted directly.
+ * Memory, besides the pool's scratch for one piece: the visit words (4 bytes per state of the compact automaton; without
+ * room for them every piece goes through records), a reservoir of at most cursor_reservoir_bytes (kept by the pool, grow-only),
+ * and for acgpu_count_u16 the counts on the device (8 bytes per keyword).
+ */
+typedef struct acgpu_count_stats {
+    uint64_t n_records;     /* records the equivalent Map match call would have returned == what this call added to counts[] in total */
+    uint64_t units_direct;  /* owned units counted from the automaton's states: no record written                                      */
+    uint64_t units_records; /* owned units counted through Map records in the call's own device reservoir                              */
+    uint32_t pieces, rescans; /* pieces: scan attempts (a host text's piece may be several shard calls); rescans: of those, attempts
+                                 that ended at a shard whose records did not fit -- the shards in front of it stay counted, the rest
+                                 of the piece is scanned again                                                                      */
+} acgpu_count_stats;
+int acgpu_count_u16(const acgpu_automaton *a, const uint16_t *haystack, uint64_t n_units, uint64_t *counts, uint32_t n_counts,
+                    acgpu_count_stats *st);
+int acgpu_count_device(const acgpu_automaton *a, acgpu_shard *shard, uint64_t *d_counts, uint32_t n_counts, void *stream,
+                       acgpu_count_stats *st);
+
+/*
  * Synthetic haystack generator of the benchmark: unit i of the stream is
  * table[((z_i >> 32) * table_len) >> 32] with z_i = SplitMix64 output for counter
  * start_index + i of `seed` (see ahocorasick_amd/synth.py).  d_dst: device pointer.
@@ -511,7 +561,9 @@ int acgpu_stream_probe(const void *d_buf, uint64_t n_bytes, void *stream, int re
  * a multiple of 64) and "ww_ramp_pm" (per mille by which the spans of the last workgroups shrink); "longest_form" (bits:
  * 1 no k_longest_bits, 2 no k_longest_follow, 4 both for short texts too, 8 k_longest_follow over alphabets of up to four
  * letters); the cursor's "cursor_first_piece" (units of its first piece, default 2^20), "cursor_max_piece" (largest piece,
- * 2^26) and "cursor_reservoir_bytes" (largest reservoir, 256 MiB).  Returns the previous value, -1 for an unknown name. */
+ * 2^26) and "cursor_reservoir_bytes" (largest reservoir, 256 MiB); "states_chunk_log2" (k_ac_states: a lane's chunk, 0 = by the text's
+ * length, 8 .. 10 = forced) and the counting calls' A/B switches "count_form" (bits: 1 never the direct form, 2 no LDS counters
+ * in k_states_hist, 4 no same-key peel in k_states_hist / k_count_ids).  Returns the previous value, -1 for an unknown name. */
 int64_t acgpu_set_tunable(const char *name, int64_t value);
 
 const char *acgpu_strerror(int code);
