@@ -2113,6 +2113,17 @@ static bool device_numa_cpus(int dev, cpu_set_t *set) {
     return n_set > 0;
 }
 
+int stage_whole_text(DeviceState &d, const uint16_t *haystack, uint64_t n_units, acgpu_shard *out) {
+    const int rc = d.stage_hay.ensure(n_units * 2 + 16);
+    if (rc) return rc;
+    if (n_units) HIP_TRY(hipMemcpy(d.stage_hay.p, haystack, n_units * 2, hipMemcpyHostToDevice));
+    *out = acgpu_shard{};
+    out->d_hay = (const uint16_t *)d.stage_hay.p;
+    out->n_units = out->own_end = n_units;
+    out->text_begin = out->text_end = 1;
+    return ACGPU_OK;
+}
+
 int scan_host_range(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack, uint64_t n_units, uint64_t lo, uint64_t hi,
                     uint64_t own_lo, uint64_t own_hi, int record_kind, uint64_t cap, uint64_t *n_out, int64_t *chain_io,
                     void *d_out, uint64_t *own_done) {
@@ -2352,17 +2363,9 @@ int acgpu_match_u16(const acgpu_automaton *ca, const uint16_t *haystack, uint64_
     if (n_units >= 2 * kHostChunkUnits && !one_piece(shard_rule(t, record_kind, false), t) && d->inflight == 0 &&
         !(tunables().tile_debug & 33554432))
         return match_u16_pipelined(a, *d, haystack, n_units, record_kind, out, cap, n_out);
-    if ((rc = d->stage_hay.ensure(n_units * 2 + 16))) return rc;
+    acgpu_shard sh;
     if ((rc = d->stage_out.ensure(cap * (uint64_t)record_kind + 16))) return rc;
-    if (n_units) HIP_TRY(hipMemcpy(d->stage_hay.p, haystack, n_units * 2, hipMemcpyHostToDevice));
-    acgpu_shard sh{};
-    sh.d_hay = (const uint16_t *)d->stage_hay.p;
-    sh.n_units = n_units;
-    sh.own_begin = 0;
-    sh.own_end = n_units;
-    sh.text_begin = 1;
-    sh.text_end = 1;
-    sh.chain_entry = 0;
+    if ((rc = stage_whole_text(*d, haystack, n_units, &sh))) return rc;
     rc = match_shard(a, *d, &sh, record_kind, d->stage_out.p, cap, n_out, nullptr, nullptr);
     if (rc != ACGPU_OK) return rc;
     if (*n_out) HIP_TRY(hipMemcpy(out, d->stage_out.p, *n_out * (uint64_t)record_kind, hipMemcpyDeviceToHost));

@@ -1,10 +1,8 @@
 // acgpu_cursor.hip -- acgpu_cursor_* (include/acgpu.h): one match(String, listener) call handed out in pages, scanned piece by
-// piece only as far as the pages taken so far require.
+// piece (scan_next_piece, acgpu_pieces.hip) only as far as the pages taken so far require.
 //
-// A piece is one scan_host_range call (acgpu_api.hip) over an owned range of the haystack plus the halo its family needs, into
-// the cursor's own device reservoir; the chain of LONGEST / SHORTEST / WWLONGEST is handed from piece to piece in haystack
-// coordinates.  Pages leave the reservoir through k_cursor_page, which shifts the positions from the piece's buffer coordinates
-// to haystack coordinates on the way into pinned, device-mapped staging memory.
+// Pages leave the cursor's own device reservoir through k_cursor_page, which shifts the positions from the piece's buffer
+// coordinates to haystack coordinates on the way into pinned, device-mapped staging memory.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -55,84 +53,30 @@ __global__ void k_cursor_page(const int32_t *__restrict__ src, int32_t *__restri
 
 } // namespace
 
-namespace acgpu {
-
-uint64_t reservoir_budget_bytes() { return (uint64_t)std::max<int64_t>(tunables().cursor_reservoir_bytes.load(std::memory_order_relaxed), 16); }
-
-void PieceRamp::start() {
-    piece = (uint64_t)std::max<int64_t>(1, tunables().cursor_first_piece.load(std::memory_order_relaxed));
-    seen_records = seen_units = 0;
-}
-
-// the next step of the ramp, capped so that the density seen so far fills at most half the reservoir budget
-uint64_t PieceRamp::next_size(uint64_t left, uint64_t budget_recs) const {
-    uint64_t size = std::min<uint64_t>(piece, left);
-    if (seen_records && seen_units) {
-        const double per_unit = (double)seen_records / (double)seen_units;
-        const double fit = (double)(budget_recs / 2) / per_unit;
-        if (fit < (double)size) size = std::max<uint64_t>(1, (uint64_t)fit);
-    }
-    return size;
-}
-
-uint64_t PieceRamp::predicted_room(uint64_t size, uint64_t budget_recs) const {
-    if (!seen_units) return 0;
-    const double pred = (double)seen_records / (double)seen_units * (double)size;
-    return std::min<uint64_t>(budget_recs, (uint64_t)(pred * 1.25) + 1024);
-}
-
-bool PieceRamp::on_overflow(uint64_t *size, uint64_t cnt, uint64_t budget_recs, uint64_t *room) const {
-    if (cnt <= budget_recs) { // a larger reservoir
-        *room = std::min<uint64_t>(budget_recs, cnt + cnt / 8);
-    } else if (*size > 1) { // a smaller piece: half the budget by this piece's density
-        *size = std::max<uint64_t>(1, (uint64_t)((double)*size * (double)(budget_recs / 2) / (double)cnt));
-        *room = budget_recs;
-    } else {
-        return false;
-    }
-    return true;
-}
-
-void PieceRamp::advance(uint64_t size, uint64_t cnt) {
-    seen_records += cnt;
-    seen_units += size;
-    const uint64_t max_piece = (uint64_t)std::max<int64_t>(1, tunables().cursor_max_piece.load(std::memory_order_relaxed));
-    piece = std::min<uint64_t>(max_piece, std::max<uint64_t>(size, 1) * 4);
-}
-
-} // namespace acgpu
-
 struct acgpu_cursor {
     acgpu_automaton *a = nullptr; // nullptr: detached by acgpu_free
     int device = -1;
     const uint16_t *hay = nullptr;
-    uint64_t n = 0;
-    int record_kind = 0;
-    bool whole = false;  // the text is scanned as ONE piece (one_piece)
     bool failed = false; // a next failed: only close is valid
-    // the scan
-    uint64_t pos = 0;      // owned units [0, pos) have been scanned
-    int64_t chain = 0;     // the chain's entry into the next piece (haystack coordinates)
-    PieceRamp ramp;        // the sizes of the pieces
+    PieceDriver p;       // the scan: the text's units [0, p.pos) have been scanned
     // the reservoir: records [res_r, res_n) of the current piece are not handed out yet; positions relative to res_base
-    void *res = nullptr;
-    uint64_t res_bytes = 0;
+    Reservoir res;
     uint64_t res_n = 0, res_r = 0;
     int32_t res_base = 0;
     // page staging: pinned, device-mapped
     void *pin = nullptr, *pin_dev = nullptr;
     uint64_t pin_bytes = 0;
-    acgpu_cursor_stats st{};
+    acgpu_cursor_stats st{}; // done, records_delivered: the rest is the driver's
     ~acgpu_cursor() {
         if (a) {
             std::lock_guard<std::mutex> l(a->mu);
             a->open_cursors.erase(this);
         }
-        if (device >= 0 && (res || pin)) {
+        if (device >= 0 && (res.p || pin)) {
             int cur = -1;
             const bool have = hipGetDevice(&cur) == hipSuccess;
             (void)hipSetDevice(device);
-            if (res) (void)hipFree(res);
+            res.release();
             if (pin) (void)hipHostFree(pin);
             if (have) (void)hipSetDevice(cur);
         }
@@ -141,101 +85,8 @@ struct acgpu_cursor {
 
 namespace {
 
-int grow_reservoir(acgpu_cursor *c, uint64_t bytes) {
-    if (bytes <= c->res_bytes) return ACGPU_OK;
-    if (c->res) (void)hipFree(c->res);
-    c->res = nullptr;
-    c->res_bytes = 0;
-    HIP_TRY(hipMalloc(&c->res, bytes + 64));
-    c->res_bytes = bytes;
-    return ACGPU_OK;
-}
-
-uint64_t budget_bytes() { return reservoir_budget_bytes(); }
-
-// The whole text as one shard (the loops that exist only as one sequential kernel): copied to the pool's staging buffer and
-// scanned into the reservoir, which grows to the exact count -- past the budget if device memory allows.
-int scan_whole(acgpu_cursor *c, DeviceState &d) {
-    acgpu_automaton *a = c->a;
-    const uint64_t rk = (uint64_t)c->record_kind;
-    int rc;
-    if ((rc = d.stage_hay.ensure(c->n * 2 + 16))) return rc;
-    if (c->n) HIP_TRY(hipMemcpy(d.stage_hay.p, c->hay, c->n * 2, hipMemcpyHostToDevice));
-    if ((rc = grow_reservoir(c, std::min<uint64_t>(budget_bytes(), std::max<uint64_t>(c->n / 16, 4096) * rk)))) return rc;
-    for (;;) {
-        acgpu_shard sh{};
-        sh.d_hay = (const uint16_t *)d.stage_hay.p;
-        sh.n_units = c->n;
-        sh.own_begin = 0;
-        sh.own_end = c->n;
-        sh.text_begin = 1;
-        sh.text_end = 1;
-        sh.chain_entry = 0;
-        uint64_t cnt = 0;
-        rc = match_shard(a, d, &sh, c->record_kind, c->res, c->res_bytes / rk, &cnt, d.call_stream, nullptr);
-        c->st.pieces++;
-        c->st.units_scanned += c->n;
-        if (rc == ACGPU_E_OVERFLOW) {
-            c->st.rescans++;
-            if ((rc = grow_reservoir(c, cnt * rk))) return rc;
-            continue;
-        }
-        if (rc) return rc;
-        c->res_n = cnt;
-        c->res_r = 0;
-        c->res_base = 0;
-        c->pos = c->n;
-        c->st.scan_end = c->n;
-        return ACGPU_OK;
-    }
-}
-
-// Scans the next piece into the reservoir (which is empty): its owned range starts at c->pos.  Overflow: a larger reservoir
-// within the budget, else a smaller piece, and the same piece scanned again.
-int scan_piece(acgpu_cursor *c, DeviceState &d) {
-    if (c->whole) return scan_whole(c, d);
-    acgpu_automaton *a = c->a;
-    const ShardRule rule = shard_rule(a->t, c->record_kind, false);
-    const uint64_t rk = (uint64_t)c->record_kind;
-    const uint64_t budget_recs = std::max<uint64_t>(budget_bytes() / rk, 1);
-    uint64_t size = c->ramp.next_size(c->n - c->pos, budget_recs);
-    for (;;) {
-        const uint64_t own_lo = c->pos, own_hi = own_lo + size;
-        const uint64_t lo = own_lo - std::min(rule.left, own_lo), hi = std::min<uint64_t>(c->n, own_hi + rule.right);
-        // predicted records: room for them (within the budget) before the scan, so that a steady text is not scanned twice
-        if (const uint64_t want = c->ramp.predicted_room(size, budget_recs)) {
-            int rc = grow_reservoir(c, want * rk);
-            if (rc) return rc;
-        } else if (!c->res) { // (a record per unit: natural text against a word list has 0.8)
-            int rc = grow_reservoir(c, std::min<uint64_t>(budget_recs, std::max<uint64_t>(size, 4096)) * rk);
-            if (rc) return rc;
-        }
-        int64_t chain = c->chain - (int64_t)lo; // (buffer relative: scan_host_range takes each shard's entry from it)
-        uint64_t cnt = 0;
-        int rc = scan_host_range(a, d, c->hay, c->n, lo, hi, own_lo, own_hi, c->record_kind, c->res_bytes / rk, &cnt, &chain, c->res);
-        c->st.pieces++;
-        c->st.units_scanned += size;
-        c->st.scan_end = std::max<uint64_t>(c->st.scan_end, hi);
-        if (rc == ACGPU_E_OVERFLOW) {
-            c->st.rescans++;
-            uint64_t room = 0;
-            if (!c->ramp.on_overflow(&size, cnt, budget_recs, &room)) return ACGPU_E_NOMEM; // one unit's records do not fit the budget
-            if ((rc = grow_reservoir(c, room * rk))) return rc;
-            continue;
-        }
-        if (rc) return rc;
-        c->chain = chain + (int64_t)lo;
-        c->res_n = cnt;
-        c->res_r = 0;
-        c->res_base = (int32_t)lo;
-        c->pos = own_hi;
-        c->ramp.advance(size, cnt);
-        return ACGPU_OK;
-    }
-}
-
 int page_out(acgpu_cursor *c, DeviceState &d, void *out, uint64_t k) {
-    const uint64_t rk = (uint64_t)c->record_kind, bytes = k * rk;
+    const uint64_t rk = (uint64_t)c->p.record_kind, bytes = k * rk;
     if (c->pin_bytes < bytes) {
         if (c->pin) (void)hipHostFree(c->pin);
         c->pin = c->pin_dev = nullptr;
@@ -248,7 +99,7 @@ int page_out(acgpu_cursor *c, DeviceState &d, void *out, uint64_t k) {
     const uint64_t n_dw = k * (rk / 4), n_q = (n_dw + 3) / 4;
     const unsigned blocks = (unsigned)std::min<uint64_t>((n_q + 255) / 256, 8192);
     hipLaunchKernelGGL(k_cursor_page, dim3(blocks), dim3(256), 0, d.call_stream,
-                       (const int32_t *)((const char *)c->res + c->res_r * rk), (int32_t *)c->pin_dev, n_dw, (int)(rk / 4), c->res_base);
+                       (const int32_t *)((const char *)c->res.p + c->res_r * rk), (int32_t *)c->pin_dev, n_dw, (int)(rk / 4), c->res_base);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(d.call_stream));
     std::memcpy(out, c->pin, bytes);
@@ -265,11 +116,14 @@ int cursor_next(acgpu_cursor *c, void *out, uint64_t cap, uint64_t *n_out) {
     std::lock_guard<std::mutex> lock(d->mu);
     if (d->inflight > 0) return ACGPU_E_INVALID; // (stream rule: tickets of the asynchronous entry are in flight)
     while (c->res_r == c->res_n) { // (an empty reservoir: scan until a piece yields a record or the text ends)
-        if (c->pos >= c->n) {
+        if (c->p.pos >= c->p.end) {
             c->st.done = 1;
             return ACGPU_OK;
         }
-        if ((rc = scan_piece(c, *d))) return rc;
+        uint64_t base = 0;
+        if ((rc = scan_next_piece(c->p, PieceScan{c->a, *d, c->hay, c->p.end, nullptr, nullptr}, &c->res_n, &base))) return rc;
+        c->res_r = 0;
+        c->res_base = (int32_t)base;
     }
     const uint64_t k = std::min<uint64_t>(cap, c->res_n - c->res_r);
     if ((rc = page_out(c, *d, out, k))) return rc;
@@ -300,11 +154,11 @@ int acgpu_cursor_open(const acgpu_automaton *ca, const uint16_t *haystack, uint6
     if (!c) return ACGPU_E_NOMEM;
     c->device = d->device;
     c->hay = haystack;
-    c->n = n_units;
-    c->record_kind = record_kind;
-    const HostTables &t = a->t;
-    c->whole = one_piece(shard_rule(t, record_kind, false), t);
-    c->ramp.start();
+    c->p.end = n_units;
+    c->p.record_kind = record_kind;
+    c->p.whole = one_piece(shard_rule(a->t, record_kind, false), a->t);
+    c->p.ramp.start();
+    c->p.res = &c->res;
     try {
         std::lock_guard<std::mutex> l(a->mu);
         a->open_cursors.insert(c);
@@ -333,6 +187,10 @@ int acgpu_cursor_get_stats(const acgpu_cursor *c, acgpu_cursor_stats *st) {
     if (!c || !st) return ACGPU_E_INVALID;
     *st = c->st;
     st->records_buffered = c->res_n - c->res_r;
+    st->units_scanned = c->p.units_scanned;
+    st->scan_end = c->p.scan_end;
+    st->pieces = (uint32_t)c->p.pieces;
+    st->rescans = (uint32_t)c->p.rescans;
     return ACGPU_OK;
 }
 

@@ -46,6 +46,25 @@ struct DevBuf {
     }
 };
 
+// A device buffer whose capacity is kept in records (the cursor's and the counting calls' reservoir): grow-only, and exactly
+// what was asked for plus 64 bytes of slack -- the tunable "cursor_reservoir_bytes" bounds what the callers ask for.
+struct Reservoir {
+    void *p = nullptr;
+    uint64_t recs = 0;
+    int ensure(uint64_t need, uint64_t record_bytes) {
+        if (need <= recs) return ACGPU_OK;
+        release();
+        HIP_TRY(hipMalloc(&p, need * record_bytes + 64));
+        recs = need;
+        return ACGPU_OK;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        recs = 0;
+    }
+};
+
 // How a call's result is collected (collect(), acgpu_api.hip): the pipeline that was enqueued.
 enum class CallForm : uint8_t {
     Complete,      // the empty call: nothing found, nothing to report
@@ -170,7 +189,8 @@ struct DeviceState {
     DevBuf lenbig, todo;                                 // LONGEST: escaped lengths; root-table form: flagged chunks
     DevBuf chainbits;                                    // LONGEST: one bit per position, set where the chain reports a match
     DevBuf bits_state;                                   // k_longest_bits: exit / flag / count, look-back words, region counter -- zero between calls
-    DevBuf visits, count_res, count_out;                 // acgpu_count_*: visit words (4 bytes per state of the compact automaton), the reservoir, the host entry's counts
+    DevBuf visits, count_out;                            // acgpu_count_*: visit words (4 bytes per state of the compact automaton), the host entry's counts
+    Reservoir count_res;                                 // ... and their reservoir of Map records
     CountCall *count = nullptr;                          // the counting call that runs on this pool (it holds mu), or nullptr
     double all_density = -1.0;                           // ALL: records per unit of this pool's last call (-1: none yet): k_ac_states or the tile kernel
     int fol_level = 0;                                   // k_longest_follow: 0 = run-up of 128 positions, 1 = of a whole segment (a call's chains had not merged), 2 = not for this pool's texts
@@ -321,6 +341,41 @@ int end_ticket(const acgpu_automaton *a, acgpu_ticket *ticket, uint64_t *n_out, 
 int scan_host_range(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack, uint64_t n_units, uint64_t lo, uint64_t hi,
                     uint64_t own_lo, uint64_t own_hi, int record_kind, uint64_t cap, uint64_t *n_out, int64_t *chain,
                     void *d_out = nullptr, uint64_t *own_done = nullptr);
+
+// The whole host text as one shard: copied (blocking) into d.stage_hay; *out = that buffer, all of it owned, the text's begin and
+// end, no chain.  The caller holds d.mu.
+int stage_whole_text(DeviceState &d, const uint16_t *haystack, uint64_t n_units, acgpu_shard *out);
+
+// A text on its way through a reservoir, piece by piece (scan_next_piece, acgpu_pieces.hip): the cursor keeps one from page call
+// to page call, a counting call has one for its duration.
+struct PieceDriver {
+    uint64_t pos = 0, end = 0;         // the owned units [pos, end) have not been scanned yet
+    int64_t chain = 0;                 // the chain's entry into the next piece (the text's coordinates)
+    bool whole = false;                // the text is scanned as ONE piece (one_piece, or a sequential rule)
+    int record_kind = 0;
+    PieceRamp ramp;                    // the sizes of the pieces
+    Reservoir *res = nullptr;          // where a piece's records go
+    const uint64_t *through = nullptr; // a counting call: CountCall::through_reservoir (its shards' records are counted as they are collected)
+    uint64_t pieces = 0, rescans = 0;  // scan attempts; of those, attempts whose records did not fit
+    uint64_t units_scanned = 0, scan_end = 0; // owned units scanned, rescans included; the host text's units [0, scan_end) have been scanned
+};
+
+// The scan of one piece.  Exactly three kinds: a caller's device shard with a moving owned range (`shard`, on `stream`); else a
+// host text (hay, n) -- whole as one staged shard (stage_whole_text + match_shard), or a range of it through scan_host_range.
+struct PieceScan {
+    acgpu_automaton *a;
+    DeviceState &d;
+    const uint16_t *hay;
+    uint64_t n;
+    const acgpu_shard *shard;
+    hipStream_t stream;
+    int operator()(PieceDriver &p, uint64_t size, uint64_t *cnt, uint64_t *done, uint64_t *base) const;
+};
+
+// Scans the next piece to its completion: sizes it, makes room, scans, and on overflow scans again -- in a larger reservoir, as a
+// smaller piece, or not at all (ACGPU_E_NOMEM: one unit's records do not fit the budget; a whole text instead grows the reservoir
+// to the exact count, past the budget).  *n_out = the piece's records, *base = the text position of their buffer's unit 0.
+int scan_next_piece(PieceDriver &p, const PieceScan &scan, uint64_t *n_out, uint64_t *base);
 
 // collect() of a counting shard call that found n records: counts them (acgpu_count.hip).  ACGPU_E_OVERFLOW: they did not fit
 // the reservoir, nothing was counted.

@@ -516,12 +516,9 @@ int acgpu_stream_feed(acgpu_stream *s, const uint16_t *units, uint64_t n_units, 
         int rc = device_for_call(a, &d);
         if (rc) return rc;
         std::lock_guard<std::mutex> lock(d->mu); // staging buffers are part of the per-device scratch pool
-        if ((rc = d->stage_hay.ensure(total * 2 + 16))) return rc;
+        acgpu_shard sh;
         if ((rc = d->stage_out.ensure(cap * (uint64_t)record_kind + 16))) return rc;
-        HIP_TRY(hipMemcpy(d->stage_hay.p, s->buf.data(), total * 2, hipMemcpyHostToDevice));
-        acgpu_shard sh{};
-        sh.d_hay = (const uint16_t *)d->stage_hay.p;
-        sh.n_units = total;
+        if ((rc = stage_whole_text(*d, s->buf.data(), total, &sh))) return rc; // (the carry and the fed units: then the owned range, the ends and the chain)
         sh.own_begin = own_begin;
         sh.own_end = own_end;
         sh.text_begin = s->carry_pos == 0 ? 1 : 0;

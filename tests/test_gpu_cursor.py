@@ -19,7 +19,8 @@ from tests.helpers import LOWER, WORD, rand_case
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEFAULTS = [("cursor_first_piece", 1 << 20), ("cursor_max_piece", 1 << 26), ("cursor_reservoir_bytes", 256 << 20)]
+DEFAULTS = [("cursor_first_piece", 1 << 20), ("cursor_max_piece", 1 << 26), ("cursor_reservoir_bytes", 256 << 20), ("all_form", 0),
+            ("count_form", 0)]
 MODES = {N.MODE_ALL: FAM_AC, N.MODE_LONGEST: FAM_LONGEST, N.MODE_WHOLEWORD: FAM_WHOLEWORD, N.MODE_SHORTEST: FAM_SHORTEST,
          N.MODE_WWLONGEST: FAM_WWLONGEST}
 
@@ -208,6 +209,47 @@ def test_reservoir_pressure_rescans_and_nomem():
         assert e.value.code == N.E_NOMEM
         with pytest.raises(N.AcgpuError):  # after a failed next only close is valid
             c.next(1)
+
+
+def _dense_all():
+    from tests.test_gpu_count import _family_case
+    kws, hay = _family_case(N.MODE_ALL, True, 300 + N.MODE_ALL * 2 + 1, 20000)
+    return lambda: Automaton(N.MODE_ALL, kws, True), hay, len(kws)
+
+
+def _whole_word_not_fold_consistent():
+    rng = np.random.default_rng(9)
+    alpha = np.array([ord(ch) for ch in "abxyABXY ,"], dtype=np.uint16)
+    wc = word_chars_from_list("abcdxyABCD")  # X, Y are not word characters although x, y are
+    hay = alpha[rng.integers(0, len(alpha), 20000)]
+    kws = [alpha[rng.integers(0, 4, int(rng.integers(1, 5)))] for _ in range(12)]
+    kws += [kws[2].copy()]
+    return lambda: Automaton(N.MODE_WHOLEWORD, kws, False, word_chars=wc), hay, len(kws)
+
+
+@pytest.mark.parametrize("case", [_dense_all, _whole_word_not_fold_consistent])
+def test_cursor_and_count_plan_the_same_pieces(case):
+    """A cursor drained in one page per piece and a counting call, each on a fresh automaton (an empty reservoir), pieces of
+    64 .. 4096 units through a reservoir of 500 Map records, every piece through records: the same pieces and the same rescans.
+    The dense ALL text overflows its reservoir at least once; the WholeWord table that is not fold-consistent is one piece."""
+    fresh, hay, n_kw = case()
+    ref = fresh().match_host(hay, True)
+    want = np.bincount(ref[:, 2], minlength=n_kw).astype(np.uint64)
+    pieces(64, 4096)
+    N.set_tunable("cursor_reservoir_bytes", 6000)
+    N.set_tunable("all_form", 1)
+    N.set_tunable("count_form", 1)
+    got, cst = drain(fresh(), hay, True, len(ref) + 1)
+    counts, nst = fresh().count_host(hay)
+    plans = (cst["pieces"], cst["rescans"]), (nst["pieces"], nst["rescans"])
+    print("plan", case.__name__, plans)
+    assert plans[0] == plans[1]
+    assert len(ref) > 100 and got.shape == ref.shape and (got == ref).all()
+    assert (counts == want).all() and nst["units_direct"] == 0
+    if case is _dense_all:
+        assert cst["rescans"] >= 1
+    else:
+        assert cst["pieces"] - cst["rescans"] == 1 and nst["pieces"] - nst["rescans"] == 1
 
 
 def test_more_records_than_a_java_int_array_holds():
