@@ -64,6 +64,10 @@ class CountStats(ctypes.Structure):  # acgpu_count_stats
                 ("pieces", ctypes.c_uint32), ("rescans", ctypes.c_uint32)]
 
 
+class ReplaceStats(ctypes.Structure):  # acgpu_replace_stats
+    _fields_ = [("n_records", ctypes.c_uint64), ("units_out", ctypes.c_uint64), ("pieces", ctypes.c_uint32), ("rescans", ctypes.c_uint32)]
+
+
 # every symbol include/acgpu.h declares
 SYMBOLS = ["acgpu_build", "acgpu_free", "acgpu_get_info", "acgpu_match_u16", "acgpu_match_batch_u16", "acgpu_match_device",
            "acgpu_match_device_begin", "acgpu_match_device_end", "acgpu_match_device_abandon", "acgpu_synth_fill", "acgpu_synth_tokens", "acgpu_stream_probe",
@@ -72,7 +76,8 @@ SYMBOLS = ["acgpu_build", "acgpu_free", "acgpu_get_info", "acgpu_match_u16", "ac
            "acgpu_match_u16_multi", "acgpu_comm_open", "acgpu_comm_close", "acgpu_comm_transport", "acgpu_comm_stream",
            "acgpu_match_device_allgather", "acgpu_last_rccl_error", "acgpu_gather_slot_bytes",
            "acgpu_stream_set_pipelined", "acgpu_stream_reserve", "acgpu_cursor_open", "acgpu_cursor_next",
-           "acgpu_cursor_get_stats", "acgpu_cursor_close", "acgpu_count_u16", "acgpu_count_device"]
+           "acgpu_cursor_get_stats", "acgpu_cursor_close", "acgpu_count_u16", "acgpu_count_device",
+           "acgpu_replace_u16", "acgpu_replace_device"]
 
 _lib = None
 
@@ -150,6 +155,11 @@ def lib():
         L.acgpu_count_u16.argtypes = [vp, vp, u64, vp, u32, ctypes.POINTER(CountStats)]
         L.acgpu_count_device.restype = ci
         L.acgpu_count_device.argtypes = [vp, ctypes.POINTER(Shard), vp, u32, vp, ctypes.POINTER(CountStats)]
+        L.acgpu_replace_u16.restype = ci
+        L.acgpu_replace_u16.argtypes = [vp, vp, u64, vp, vp, u32, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(ReplaceStats)]
+        L.acgpu_replace_device.restype = ci
+        L.acgpu_replace_device.argtypes = [vp, ctypes.POINTER(Shard), vp, vp, u32, vp, u64, ctypes.POINTER(u64), vp,
+                                           ctypes.POINTER(ReplaceStats)]
         L.acgpu_debug_wordhash_perfect.restype = ci
         L.acgpu_debug_wordhash_perfect.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.acgpu_debug_wordhash.restype = ci

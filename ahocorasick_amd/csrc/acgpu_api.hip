@@ -1806,6 +1806,7 @@ int64_t acgpu_set_tunable(const char *name, int64_t value) {
     else if (!std::strcmp(name, "cursor_reservoir_bytes")) slot = &t.cursor_reservoir_bytes;
     else if (!std::strcmp(name, "states_chunk_log2")) slot = &t.states_chunk_log2;
     else if (!std::strcmp(name, "count_form")) slot = &t.count_form;
+    else if (!std::strcmp(name, "replace_slab_units")) slot = &t.replace_slab_units;
     if (!slot) return -1;
     return slot->exchange(value, std::memory_order_relaxed);
 }

@@ -190,7 +190,10 @@ struct DeviceState {
     DevBuf chainbits;                                    // LONGEST: one bit per position, set where the chain reports a match
     DevBuf bits_state;                                   // k_longest_bits: exit / flag / count, look-back words, region counter -- zero between calls
     DevBuf visits, count_out;                            // acgpu_count_*: visit words (4 bytes per state of the compact automaton), the host entry's counts
-    Reservoir count_res;                                 // ... and their reservoir of Map records
+    Reservoir count_res;                                 // ... and their reservoir of Map records (a replace call's too: acgpu_replace.hip)
+    DevBuf replace_tab, replace_plan, replace_slab;      // acgpu_replace_*: the replacement table, the plan {sums, output positions}, the host entry's two slabs
+    void *replace_pin = nullptr;                         // ... pinned, 64 bytes: a piece's output length and last end
+    hipEvent_t replace_ev[4] = {nullptr, nullptr, nullptr, nullptr}; // ... slab b emitted (b), slab b copied out (2 + b)
     CountCall *count = nullptr;                          // the counting call that runs on this pool (it holds mu), or nullptr
     double all_density = -1.0;                           // ALL: records per unit of this pool's last call (-1: none yet): k_ac_states or the tile kernel
     int fol_level = 0;                                   // k_longest_follow: 0 = run-up of 128 positions, 1 = of a whole segment (a call's chains had not merged), 2 = not for this pool's texts
@@ -224,6 +227,9 @@ struct DeviceState {
         if (batch_pin) (void)hipHostFree(batch_pin);
         batch_off.release(); batch_out.release();
         visits.release(); count_res.release(); count_out.release();
+        replace_tab.release(); replace_plan.release(); replace_slab.release();
+        if (replace_pin) (void)hipHostFree(replace_pin);
+        for (auto &e : replace_ev) if (e) (void)hipEventDestroy(e);
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
         for (auto &e : chunk_ev) if (e) (void)hipEventDestroy(e);
         for (auto &e : ev) if (e) (void)hipEventDestroy(e);

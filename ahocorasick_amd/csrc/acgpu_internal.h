@@ -401,6 +401,7 @@ struct Tunables {
     std::atomic<int64_t> cursor_max_piece{1ll << 26};        // acgpu_cursor: owned units of the largest piece
     std::atomic<int64_t> cursor_reservoir_bytes{256ll << 20}; // acgpu_cursor: largest device reservoir of one piece's records
     std::atomic<int64_t> states_chunk_log2{0};  // k_ac_states: a lane's chunk, 0 = by the text's length, 8 .. 10 = forced (tests: 1 to 4 steps per chunk on short texts)
+    std::atomic<int64_t> replace_slab_units{1ll << 25}; // acgpu_replace_u16: units of one of the two device slabs the result leaves through
     std::atomic<int64_t> count_form{0};         // acgpu_count_*, bits: 1 = never the direct form, 2 = no LDS counters in k_states_hist, 4 = no same-key peel (A/B)
 };
 Tunables &tunables();

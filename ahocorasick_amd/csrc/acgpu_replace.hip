@@ -1,0 +1,527 @@
+// acgpu_replace.hip -- acgpu_replace_u16 / acgpu_replace_device (include/acgpu.h): the text with every match of a non-overlapping
+// family replaced, written on the device.
+//
+// A replace call is the third consumer of the piece driver (scan_next_piece, acgpu_pieces.hip): the Map records of a piece stay
+// in the pool's reservoir, the piece's text is on the device already (d.stage_hay, or the caller's buffer), and behind every piece
+//  * the PLAN (k_replace_sums, k_replace_offsets, k_replace_plan: a two-level exclusive scan) turns record i into the output
+//    position of its replacement, pos_i = (s_i - done) + sum over j < i of (rlen[id_j] - (e_j - s_j)), 64-bit;
+//  * the EMIT (k_replace_emit) writes a window of the piece's output -- a workgroup per 2048 output units, a lane per 16-byte
+//    store -- from the text and the replacement table.
+// The host keeps `done`, the text position up to which output exists, and `out_pos`, the units written so far; what a piece may
+// emit, [done, limit), is decided by replace_limit below.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <mutex>
+#include <vector>
+
+#include "acgpu_device.h"
+#include "acgpu_host.h"
+#include "acgpu_internal.h"
+
+using namespace acgpu;
+
+namespace {
+
+typedef uint32_t rp_v4u __attribute__((ext_vector_type(4)));
+
+constexpr int kPlanBlock = 256, kPlanPer = 8, kPlanTile = kPlanBlock * kPlanPer; // records per workgroup of the plan
+constexpr int kEmitBlock = 256, kEmitTile = kEmitBlock * 8;                      // output units per workgroup of the emit
+constexpr int kEmitLds = 3072;                                                   // segments a workgroup stages (16 bytes each)
+
+// The replacement table on the device: n_repl entries {first unit in `units`, length}, then the units.
+struct ReplTable {
+    const uint2 *ent;
+    const uint16_t *units;
+    uint32_t n_repl; // 1: that replacement stands for every keyword
+};
+
+__device__ __forceinline__ uint2 repl_of(const ReplTable &rt, int32_t id) {
+    return rt.ent[rt.n_repl == 1 ? 0u : std::min<uint32_t>((uint32_t)id, rt.n_repl - 1)];
+}
+
+// what record i adds to the output's length: its replacement's units minus the match's
+__device__ __forceinline__ int64_t repl_delta(const int32_t *recs, uint64_t i, const ReplTable &rt) {
+    const int32_t s = recs[3 * i], e = recs[3 * i + 1], id = recs[3 * i + 2];
+    return (int64_t)repl_of(rt, id).y - (int64_t)(e - s);
+}
+
+__device__ __forceinline__ int64_t plan_block_scan(int64_t v, int64_t *total) { // exclusive, kPlanBlock threads
+    __shared__ int64_t wsum[kPlanBlock / kWave];
+    const int64_t inc = wave_inclusive_scan(v);
+    const int w = threadIdx.x / kWave;
+    if (lane_id() == kWave - 1) wsum[w] = inc;
+    __syncthreads();
+    int64_t base = 0, all = 0;
+    for (int i = 0; i < kPlanBlock / kWave; ++i) {
+        if (i < w) base += wsum[i];
+        all += wsum[i];
+    }
+    *total = all;
+    __syncthreads();
+    return base + inc - v;
+}
+
+// plan, level 1: the sum of the deltas of every workgroup's kPlanTile records (a thread takes kPlanPer consecutive ones)
+__global__ __launch_bounds__(kPlanBlock) void k_replace_sums(const int32_t *__restrict__ recs, uint64_t n, ReplTable rt, int64_t *__restrict__ bsum) {
+    const uint64_t first = (uint64_t)blockIdx.x * kPlanTile + (uint64_t)threadIdx.x * kPlanPer;
+    int64_t v = 0;
+    for (int k = 0; k < kPlanPer; ++k)
+        if (first + k < n) v += repl_delta(recs, first + k, rt);
+    int64_t total;
+    plan_block_scan(v, &total);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+}
+
+// plan, level 2: ONE workgroup scans the workgroups' sums in place (exclusive), kPlanBlock per step with a running carry;
+// slot[0] = the sum of all deltas, slot[1] = the end of the last record
+__global__ __launch_bounds__(kPlanBlock) void k_replace_offsets(int64_t *__restrict__ bsum, uint32_t n_blocks, const int32_t *__restrict__ recs, uint64_t n,
+                                                                int64_t *__restrict__ slot) {
+    int64_t carry = 0;
+    for (uint32_t b0 = 0; b0 < n_blocks; b0 += kPlanBlock) {
+        const uint32_t b = b0 + threadIdx.x;
+        const int64_t v = b < n_blocks ? bsum[b] : 0;
+        int64_t total;
+        const int64_t ex = plan_block_scan(v, &total);
+        if (b < n_blocks) bsum[b] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) {
+        slot[0] = carry;
+        slot[1] = n ? (int64_t)recs[3 * (n - 1) + 1] : 0;
+    }
+}
+
+// plan, level 3: pos[i] = (s_i - done) + the deltas in front of record i (done: buffer relative, as the records are)
+__global__ __launch_bounds__(kPlanBlock) void k_replace_plan(const int32_t *__restrict__ recs, uint64_t n, ReplTable rt, const int64_t *__restrict__ bsum,
+                                                             int64_t done, int64_t *__restrict__ pos) {
+    const uint64_t first = (uint64_t)blockIdx.x * kPlanTile + (uint64_t)threadIdx.x * kPlanPer;
+    int64_t dl[kPlanPer], v = 0;
+#pragma unroll
+    for (int k = 0; k < kPlanPer; ++k) {
+        dl[k] = first + k < n ? repl_delta(recs, first + k, rt) : 0;
+        v += dl[k];
+    }
+    int64_t total;
+    int64_t run = plan_block_scan(v, &total) + bsum[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < kPlanPer; ++k) {
+        if (first + k < n) pos[first + k] = (int64_t)recs[3 * (first + k)] - done + run;
+        run += dl[k];
+    }
+}
+
+// The last index i in [lo, hi) with pos[i] <= x, lo - 1 if there is none (pos ascends; equal positions: deleted matches that
+// touch each other).
+__device__ __forceinline__ int64_t last_at_or_before(const int64_t *__restrict__ pos, int64_t lo, int64_t hi, int64_t x) {
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (pos[mid] <= x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo - 1;
+}
+
+// One stretch of the output as a workgroup sees it, u = an output unit relative to the tile: from u = rel on, the units below
+// rend are units rsrc + u of the replacement table, the others units tsrc + u of the text -- up to the next segment's rel.
+// (rsrc, tsrc: modulo 2^32; what they are used for lies below 2^31.)
+struct Seg {
+    int32_t rel, rend;
+    uint32_t rsrc, tsrc;
+};
+
+struct EmitArgs {
+    const uint16_t *hay;  // the piece's buffer
+    const int32_t *recs;  // its Map records, buffer relative
+    const int64_t *pos;   // the plan
+    int64_t n_recs;
+    ReplTable rt;
+    int64_t done;         // buffer relative: output unit 0 of the piece is text unit `done` (if no record starts there)
+    int64_t w0, w1;       // the window of the piece's output to write
+    uint16_t *dst;        // where output unit w0 goes
+};
+
+// segment of record i (-1: the text in front of the first record), t0 = the tile's first output unit
+__device__ __forceinline__ Seg make_seg(const EmitArgs &A, int64_t i, int64_t t0) {
+    Seg s;
+    if (i < 0) {
+        s.rel = -1;
+        s.rend = 0;
+        s.rsrc = 0;
+        s.tsrc = (uint32_t)(A.done + t0);
+        return s;
+    }
+    const int64_t P = A.pos[i] - t0; // < kEmitTile
+    const uint2 r = repl_of(A.rt, A.recs[3 * i + 2]);
+    const int64_t rend = P + (int64_t)r.y;
+    s.rel = (int32_t)std::max<int64_t>(P, -1);
+    s.rend = (int32_t)std::min<int64_t>(std::max<int64_t>(rend, 0), kEmitTile);
+    s.rsrc = r.x - (uint32_t)P;
+    s.tsrc = (uint32_t)A.recs[3 * i + 1] - (uint32_t)rend;
+    return s;
+}
+
+// 8 consecutive units from p (any 2-byte alignment) as one 16-byte value: the two aligned 16-byte words around them and a funnel
+// shift.  Only 16-byte words that hold one of the 8 units are read, so nothing beyond the page of a valid unit.
+__device__ __forceinline__ rp_v4u load8(const uint16_t *p) {
+    const uintptr_t a = (uintptr_t)p;
+    const uint32_t sh = (uint32_t)(a >> 1) & 7u;
+    const rp_v4u *q = reinterpret_cast<const rp_v4u *>(a & ~(uintptr_t)15);
+    const rp_v4u lo = q[0];
+    if (sh == 0) return lo;
+    const rp_v4u hi = q[1];
+    uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    if (sh & 4u) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) w[j] = w[j + 2];
+    }
+    if (sh & 2u) {
+#pragma unroll
+        for (int j = 0; j < 7; ++j) w[j] = w[j + 1];
+    }
+    if (sh & 1u) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[j] = (w[j] >> 16) | (w[j + 1] << 16);
+    }
+    rp_v4u r;
+    r.x = w[0]; r.y = w[1]; r.z = w[2]; r.w = w[3];
+    return r;
+}
+
+// The emit.  Tiles are laid over the DESTINATION's 16-byte grid: v = o - w0 + (dst's misalignment in units), tile b = the v in
+// [b * kEmitTile, + kEmitTile), lane l of it the 8 units of one aligned 16-byte store.  A vector that the window covers only in
+// part (the window's first and last) is written unit by unit, so nothing outside [w0, w1) -- nothing at or beyond the caller's
+// capacity -- is touched.
+// The records that touch a tile are found by two binary searches over pos; their segments go to LDS when they fit (they do unless
+// thousands of deleted matches fall into one tile), else every lane takes them from global memory: the same code over another
+// view.  A lane finds the segment of its first unit by binary search and walks on from there (a few steps, then a search again).
+template <bool kLds>
+__device__ __forceinline__ void emit_tile(const EmitArgs &A, const Seg *lseg, int64_t t0, int64_t i0, int32_t cnt, int64_t cnt_g) {
+    const int64_t n_seg = kLds ? (int64_t)cnt : cnt_g;
+    auto rel_at = [&](int64_t j) -> int64_t {
+        if (kLds) return lseg[j].rel;
+        const int64_t i = i0 + j;
+        return i < 0 ? -1 : std::max<int64_t>(A.pos[i] - t0, -1);
+    };
+    auto seg_at = [&](int64_t j) -> Seg { return kLds ? lseg[j] : make_seg(A, i0 + j, t0); };
+    auto find = [&](int64_t from, int32_t u) -> int64_t { // the last segment j >= from with rel <= u (segment `from` has)
+        int64_t lo = from + 1, hi = n_seg;
+        for (int step = 0; step < 4 && lo < hi; ++step) {
+            if (rel_at(lo) > u) return lo - 1;
+            ++lo;
+        }
+        while (lo < hi) {
+            const int64_t mid = lo + (hi - lo) / 2;
+            if (rel_at(mid) <= u) lo = mid + 1;
+            else hi = mid;
+        }
+        return lo - 1;
+    };
+    const int32_t u0 = (int32_t)threadIdx.x * 8;
+    const int64_t o_first = t0 + u0;
+    if (o_first >= A.w1 || o_first + 8 <= A.w0) return;
+    const int32_t ua = (int32_t)std::max<int64_t>(A.w0 - o_first, 0), ub = (int32_t)std::min<int64_t>(A.w1 - o_first, 8); // the lane's valid units [ua, ub)
+    uint16_t *out = A.dst + (o_first - A.w0);
+    int64_t j = find(0, u0 + ua);
+    Seg s = seg_at(j);
+    const bool full = ua == 0 && ub == 8;
+    if (full && (j + 1 >= n_seg || rel_at(j + 1) > u0 + 7)) { // one segment holds the vector
+        if (u0 >= s.rend) {
+            __builtin_nontemporal_store(load8(A.hay + (uint32_t)(s.tsrc + (uint32_t)u0)), reinterpret_cast<rp_v4u *>(out));
+            return;
+        }
+        if (u0 + 8 <= s.rend) {
+            __builtin_nontemporal_store(load8(A.rt.units + (uint32_t)(s.rsrc + (uint32_t)u0)), reinterpret_cast<rp_v4u *>(out));
+            return;
+        }
+    }
+    uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        if (k >= ua && k < ub) {
+            const int32_t u = u0 + k;
+            if (k > ua) {
+                const int64_t jn = find(j, u);
+                if (jn != j) {
+                    j = jn;
+                    s = seg_at(j);
+                }
+            }
+            const uint32_t x = u < s.rend ? A.rt.units[(uint32_t)(s.rsrc + (uint32_t)u)] : A.hay[(uint32_t)(s.tsrc + (uint32_t)u)];
+            if (full) w[k / 2] |= x << (16 * (k & 1));
+            else out[k] = (uint16_t)x;
+        }
+    }
+    if (full) {
+        rp_v4u v;
+        v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+        __builtin_nontemporal_store(v, reinterpret_cast<rp_v4u *>(out));
+    }
+}
+
+__global__ __launch_bounds__(kEmitBlock) void k_replace_emit(EmitArgs A) {
+    __shared__ Seg lseg[kEmitLds];
+    __shared__ int64_t bounds[2];
+    const int64_t mis = (int64_t)(((uintptr_t)A.dst >> 1) & 7u);
+    const int64_t t0 = A.w0 - mis + (int64_t)blockIdx.x * kEmitTile;
+    const int64_t ov0 = std::max(t0, A.w0), ov1 = std::min(t0 + kEmitTile, A.w1); // the tile's units of the window
+    if (ov0 >= ov1) return;
+    if (threadIdx.x == 0) bounds[0] = last_at_or_before(A.pos, 0, A.n_recs, ov0);
+    if (threadIdx.x == kWave) bounds[1] = last_at_or_before(A.pos, 0, A.n_recs, ov1 - 1);
+    __syncthreads();
+    const int64_t i0 = bounds[0], cnt = bounds[1] - i0 + 1; // segments i0 .. bounds[1]; i0 = -1: the text in front of record 0
+    if (cnt <= kEmitLds) {
+        for (int32_t j = (int32_t)threadIdx.x; j < (int32_t)cnt; j += kEmitBlock) lseg[j] = make_seg(A, i0 + j, t0);
+        __syncthreads();
+        emit_tile<true>(A, lseg, t0, i0, (int32_t)cnt, cnt);
+    } else {
+        emit_tile<false>(A, lseg, t0, i0, 0, cnt);
+    }
+}
+
+// What one call holds while it runs (the caller holds d.mu).
+struct ReplaceCall {
+    acgpu_automaton *a;
+    DeviceState &d;
+    hipStream_t stream;
+    ReplTable rt{};
+    uint16_t *h_out = nullptr; // the host entry's result (through the slabs) ...
+    uint16_t *d_out = nullptr; // ... or the device entry's
+    uint64_t cap = 0;
+    uint64_t n = 0;            // units of the text
+    uint64_t done = 0;         // output exists for the text's units [0, done)
+    uint64_t out_pos = 0;      // units of it (beyond cap: counted, not written)
+    acgpu_replace_stats st{};
+};
+
+int upload_table(ReplaceCall &c, const uint16_t *repl_units, const uint64_t *repl_off, uint32_t n_repl) {
+    const uint64_t r0 = n_repl ? repl_off[0] : 0, total = n_repl ? repl_off[n_repl] - r0 : 0;
+    const size_t ent_bytes = ((size_t)n_repl * 8 + 15) & ~(size_t)15;
+    std::vector<uint64_t> blob;
+    try {
+        blob.assign((ent_bytes + (size_t)total * 2 + 16 + 7) / 8, 0);
+    } catch (...) {
+        return ACGPU_E_NOMEM;
+    }
+    uint32_t *ent = reinterpret_cast<uint32_t *>(blob.data());
+    for (uint32_t i = 0; i < n_repl; ++i) {
+        ent[2 * i] = (uint32_t)(repl_off[i] - r0);
+        ent[2 * i + 1] = (uint32_t)(repl_off[i + 1] - repl_off[i]);
+    }
+    if (total) std::copy(repl_units + r0, repl_units + r0 + total, reinterpret_cast<uint16_t *>(reinterpret_cast<char *>(blob.data()) + ent_bytes));
+    const int rc = c.d.replace_tab.ensure(blob.size() * 8);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(c.d.replace_tab.p, blob.data(), blob.size() * 8, hipMemcpyHostToDevice)); // (blocking: the blob dies here)
+    c.rt.ent = reinterpret_cast<const uint2 *>(c.d.replace_tab.p);
+    c.rt.units = reinterpret_cast<const uint16_t *>(reinterpret_cast<const char *>(c.d.replace_tab.p) + ent_bytes);
+    c.rt.n_repl = n_repl;
+    return ACGPU_OK;
+}
+
+// The text position up to which a piece that owned [.., own_hi) and reported records up to last_end (0: none) may emit.
+//  * last piece, or the text as one piece: the text's end.
+//  * LONGEST, WHOLEWORD, WWLONGEST -- a match belongs to the piece that owns its FIRST unit: every later piece's records start at
+//    or behind own_hi, and, as the records of a text do not overlap and come in position order, at or behind last_end.  So nothing
+//    starts before max(own_hi, last_end).  That lies inside the buffer: a record starts before own_hi and has at most max_len
+//    units, which the right halo (max_len - 1 units and more) holds; and `done`, where the next piece's emit starts, is at least
+//    its own_lo, the buffer's first unit but for the one unit of left context of the word matchers.
+//  * SHORTEST -- a match belongs to the piece that owns its LAST unit: a later record ends behind own_hi, so it starts at or
+//    behind own_hi - (max_len - 1), and at or behind every earlier record's end, which `done` and last_end bound.  The units
+//    withheld, at most max_len - 1 in front of own_hi, are the next piece's left halo: it emits them from there.  The limit never
+//    exceeds own_hi, the buffer's end.
+uint64_t replace_limit(const HostTables &t, bool last_or_whole, uint64_t n, uint64_t own_hi, uint64_t last_end, uint64_t done) {
+    if (last_or_whole) return n;
+    if (t.mode == ACGPU_MODE_SHORTEST) {
+        const uint64_t back = t.max_len ? t.max_len - 1 : 0;
+        return std::max({last_end, done, own_hi > back ? own_hi - back : 0});
+    }
+    return std::max({own_hi, last_end, done});
+}
+
+int launch_emit(ReplaceCall &c, const uint16_t *hay, uint64_t cnt, int64_t done_rel, uint64_t w0, uint64_t w1, uint16_t *dst, hipStream_t stream) {
+    EmitArgs A;
+    A.hay = hay;
+    A.recs = reinterpret_cast<const int32_t *>(c.d.count_res.p);
+    A.pos = reinterpret_cast<const int64_t *>(c.d.replace_plan.p) + 2 + (cnt + kPlanTile - 1) / kPlanTile;
+    A.n_recs = (int64_t)cnt;
+    A.rt = c.rt;
+    A.done = done_rel;
+    A.w0 = (int64_t)w0;
+    A.w1 = (int64_t)w1;
+    A.dst = dst;
+    const uint64_t mis = ((uintptr_t)dst >> 1) & 7u;
+    const uint64_t tiles = (w1 - w0 + mis + kEmitTile - 1) / kEmitTile;
+    hipLaunchKernelGGL(k_replace_emit, dim3((unsigned)tiles), dim3(kEmitBlock), 0, stream, A);
+    HIP_TRY(hipGetLastError());
+    return ACGPU_OK;
+}
+
+// Behind a piece: plan its cnt records (in d.count_res, relative to `base`), then emit [done, limit) of the text `hay` (the
+// piece's buffer, whose unit 0 is the text's unit `base`).
+int replace_piece(ReplaceCall &c, const uint16_t *hay, uint64_t base, uint64_t cnt, uint64_t own_hi, bool last_or_whole) {
+    DeviceState &d = c.d;
+    const int64_t done_rel = (int64_t)(c.done - base);
+    int64_t delta = 0;
+    uint64_t last_end = 0;
+    if (cnt) {
+        const uint32_t n_blocks = (uint32_t)((cnt + kPlanTile - 1) / kPlanTile);
+        int rc = d.replace_plan.ensure((2 + (size_t)n_blocks + cnt) * 8); // {sum of the deltas, last end} | workgroup sums | pos
+        if (rc) return rc;
+        int64_t *slot = reinterpret_cast<int64_t *>(d.replace_plan.p), *bsum = slot + 2, *pos = bsum + n_blocks;
+        const int32_t *recs = reinterpret_cast<const int32_t *>(d.count_res.p);
+        hipLaunchKernelGGL(k_replace_sums, dim3(n_blocks), dim3(kPlanBlock), 0, c.stream, recs, cnt, c.rt, bsum);
+        hipLaunchKernelGGL(k_replace_offsets, dim3(1), dim3(kPlanBlock), 0, c.stream, bsum, n_blocks, recs, cnt, slot);
+        hipLaunchKernelGGL(k_replace_plan, dim3(n_blocks), dim3(kPlanBlock), 0, c.stream, recs, cnt, c.rt, (const int64_t *)bsum, done_rel, pos);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(d.replace_pin, slot, 16, hipMemcpyDeviceToHost, c.stream));
+        HIP_TRY(hipStreamSynchronize(c.stream)); // the piece's output length decides the windows and the next piece's `done`
+        delta = reinterpret_cast<const int64_t *>(d.replace_pin)[0];
+        last_end = base + (uint64_t)reinterpret_cast<const int64_t *>(d.replace_pin)[1];
+    }
+    const uint64_t limit = std::min(c.n, replace_limit(c.a->t, last_or_whole, c.n, own_hi, last_end, c.done));
+    const int64_t total_s = (int64_t)(limit - c.done) + delta;
+    if (limit < c.done || total_s < 0) return ACGPU_E_HIP; // (records that overlap or are out of order: not a family this call serves)
+    const uint64_t total = (uint64_t)total_s;
+    const uint64_t room = c.cap > c.out_pos ? c.cap - c.out_pos : 0, emit_total = std::min(total, room); // beyond cap: planned, not written
+    if (emit_total && c.d_out) {
+        const int rc = launch_emit(c, hay, cnt, done_rel, 0, emit_total, c.d_out + c.out_pos, c.stream);
+        if (rc) return rc;
+    } else if (emit_total) {
+        // through two slabs of the pool: slab k is copied to the caller's memory (on the copy stream) while slab k + 1 is emitted
+        const uint64_t slab = (std::min<uint64_t>((uint64_t)std::max<int64_t>(8, tunables().replace_slab_units.load(std::memory_order_relaxed)), emit_total) + 7) & ~7ull;
+        int rc = d.replace_slab.ensure(slab * 4 + 32);
+        if (rc) return rc;
+        uint16_t *buf[2] = {reinterpret_cast<uint16_t *>(d.replace_slab.p), reinterpret_cast<uint16_t *>(d.replace_slab.p) + slab};
+        bool copied[2] = {false, false};
+        auto copy_out = [&](int b, uint64_t w0, uint64_t w1) -> int {
+            HIP_TRY(hipStreamWaitEvent(d.copy_stream, d.replace_ev[b], 0));
+            HIP_TRY(hipMemcpyAsync(c.h_out + c.out_pos + w0, buf[b], (w1 - w0) * 2, hipMemcpyDeviceToHost, d.copy_stream));
+            HIP_TRY(hipEventRecord(d.replace_ev[2 + b], d.copy_stream));
+            copied[b] = true;
+            return ACGPU_OK;
+        };
+        uint64_t prev0 = 0, prev1 = 0;
+        int k = 0;
+        for (uint64_t w0 = 0; w0 < emit_total; w0 += slab, ++k) {
+            const uint64_t w1 = std::min(emit_total, w0 + slab);
+            const int b = k & 1;
+            if (copied[b]) HIP_TRY(hipStreamWaitEvent(c.stream, d.replace_ev[2 + b], 0)); // (the slab has left for the host)
+            if ((rc = launch_emit(c, hay, cnt, done_rel, w0, w1, buf[b], c.stream))) return rc;
+            HIP_TRY(hipEventRecord(d.replace_ev[b], c.stream));
+            if (k > 0 && (rc = copy_out(b ^ 1, prev0, prev1))) return rc;
+            prev0 = w0;
+            prev1 = w1;
+        }
+        if ((rc = copy_out((k - 1) & 1, prev0, prev1))) return rc;
+        HIP_TRY(hipStreamSynchronize(d.copy_stream));
+        HIP_TRY(hipStreamSynchronize(c.stream)); // (the next piece's text overwrites d.stage_hay from the copy stream)
+    }
+    c.done = limit;
+    c.out_pos += total;
+    c.st.n_records += cnt;
+    return ACGPU_OK;
+}
+
+int replace_pieces(ReplaceCall &c, int64_t chain, bool whole, const PieceScan &scan) {
+    DeviceState &d = c.d;
+    if (!d.replace_pin) HIP_TRY(hipHostMalloc(&d.replace_pin, 64, hipHostMallocDefault));
+    if (!d.copy_stream) HIP_TRY(hipStreamCreateWithFlags(&d.copy_stream, hipStreamNonBlocking));
+    for (auto &e : d.replace_ev)
+        if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    PieceDriver p;
+    p.pos = 0;
+    p.end = c.n;
+    p.chain = chain;
+    p.whole = whole;
+    p.record_kind = ACGPU_REC_MAP;
+    p.ramp.start();
+    p.res = &d.count_res; // the pool's reservoir of Map records (a counting call's too: one call at a time holds the pool)
+    int rc = ACGPU_OK;
+    while (rc == ACGPU_OK && p.pos < p.end) {
+        uint64_t cnt = 0, base = 0;
+        if ((rc = scan_next_piece(p, scan, &cnt, &base))) break;
+        const uint16_t *hay = scan.shard ? scan.shard->d_hay : reinterpret_cast<const uint16_t *>(d.stage_hay.p);
+        rc = replace_piece(c, hay, base, cnt, p.pos, whole || p.pos >= p.end);
+    }
+    c.st.pieces = (uint32_t)p.pieces;
+    c.st.rescans = (uint32_t)p.rescans;
+    c.st.units_out = c.out_pos;
+    return rc;
+}
+
+// the checks both entries share, none of which needs a device
+int check_table(const acgpu_automaton *a, const uint16_t *repl_units, const uint64_t *repl_off, uint32_t n_repl) {
+    if (n_repl != a->n_given && n_repl != 1) return ACGPU_E_INVALID;
+    if (n_repl && !repl_off) return ACGPU_E_INVALID;
+    for (uint32_t i = 0; i < n_repl; ++i)
+        if (repl_off[i] > repl_off[i + 1]) return ACGPU_E_INVALID;
+    const uint64_t total = n_repl ? repl_off[n_repl] - repl_off[0] : 0;
+    if (total > (1ull << 31) || (total && !repl_units)) return ACGPU_E_INVALID;
+    return a->t.mode == ACGPU_MODE_ALL ? ACGPU_E_UNSUPPORTED : ACGPU_OK; // (its records overlap)
+}
+
+} // namespace
+
+extern "C" {
+
+int acgpu_replace_u16(const acgpu_automaton *ca, const uint16_t *haystack, uint64_t n_units, const uint16_t *repl_units,
+                      const uint64_t *repl_off, uint32_t n_repl, uint16_t *out, uint64_t cap, uint64_t *n_out, acgpu_replace_stats *st) {
+    if (!ca || !n_out || (n_units && !haystack) || (cap && !out)) return ACGPU_E_INVALID;
+    if (n_units >= (1ull << 31)) return ACGPU_E_INVALID;
+    acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
+    int rc = check_table(a, repl_units, repl_off, n_repl);
+    if (rc) return rc;
+    DeviceState *dp = nullptr;
+    if ((rc = device_for_call(a, &dp))) return rc; // (no device: fails here, as acgpu_match_u16 does, and out is untouched)
+    DeviceState &d = *dp;
+    std::lock_guard<std::mutex> lock(d.mu);
+    if (d.inflight > 0 && d.call_stream != d.inflight_stream) return ACGPU_E_INVALID; // stream rule (include/acgpu.h)
+    ReplaceCall c{a, d, d.call_stream};
+    c.h_out = out;
+    c.cap = cap;
+    c.n = n_units;
+    if ((rc = upload_table(c, repl_units, repl_off, n_repl))) return rc;
+    const bool whole = one_piece(shard_rule(a->t, ACGPU_REC_MAP, false), a->t);
+    rc = replace_pieces(c, 0, whole, PieceScan{a, d, haystack, n_units, nullptr, d.call_stream});
+    if (rc) {
+        (void)hipStreamSynchronize(d.call_stream); // (nothing of the call stays in flight)
+        if (d.copy_stream) (void)hipStreamSynchronize(d.copy_stream);
+        return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(d.call_stream));
+    if (st) *st = c.st;
+    *n_out = c.out_pos;
+    return c.out_pos > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
+}
+
+int acgpu_replace_device(const acgpu_automaton *ca, acgpu_shard *shard, const uint16_t *repl_units, const uint64_t *repl_off,
+                         uint32_t n_repl, uint16_t *d_out, uint64_t cap, uint64_t *n_out, void *stream_, acgpu_replace_stats *st) {
+    if (!ca || !shard || !n_out || (cap && !d_out) || ((uintptr_t)d_out & 15)) return ACGPU_E_INVALID;
+    if (shard->n_units >= (1ull << 31) || (shard->n_units && !shard->d_hay) || ((uintptr_t)shard->d_hay & 15)) return ACGPU_E_INVALID;
+    acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
+    int rc = check_table(a, repl_units, repl_off, n_repl);
+    if (rc) return rc;
+    // one shard of a sharded text: its rewrite starts at the position up to which the rank before it has emitted -- not built
+    if (shard->own_begin != 0 || shard->own_end != shard->n_units || shard->text_begin != 1 || shard->text_end != 1) return ACGPU_E_UNSUPPORTED;
+    DeviceState *dp = nullptr;
+    if ((rc = device_for_call(a, &dp))) return rc;
+    DeviceState &d = *dp;
+    std::lock_guard<std::mutex> lock(d.mu);
+    const hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (d.inflight > 0 && stream != d.inflight_stream) return ACGPU_E_INVALID; // stream rule (include/acgpu.h)
+    ReplaceCall c{a, d, stream};
+    c.d_out = d_out;
+    c.cap = cap;
+    c.n = shard->n_units;
+    if ((rc = upload_table(c, repl_units, repl_off, n_repl))) return rc;
+    const bool whole = shard_rule(a->t, ACGPU_REC_MAP, false).sequential;
+    rc = replace_pieces(c, shard->chain_entry, whole, PieceScan{a, d, nullptr, 0, shard, stream});
+    const hipError_t e = hipStreamSynchronize(stream); // the final wait
+    if (rc) return rc;
+    HIP_TRY(e);
+    if (st) *st = c.st;
+    *n_out = c.out_pos;
+    return c.out_pos > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
+}
+
+} // extern "C"

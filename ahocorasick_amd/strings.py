@@ -38,6 +38,11 @@ def utf16(s):
     return np.ascontiguousarray(s, dtype=np.uint16)
 
 
+def _to_str(units):
+    """UTF-16 code units -> str (lone surrogates pass through, as in a Java String)"""
+    return np.ascontiguousarray(units, dtype=np.uint16).tobytes().decode("utf-16-le", "surrogatepass")
+
+
 def _pack(keywords):
     parts = [utf16(k) if k is not None else np.zeros(0, np.uint16) for k in keywords]
     off = np.zeros(len(parts) + 1, dtype=np.uint64)
@@ -196,6 +201,54 @@ class Automaton:
                                         ctypes.byref(st))
         return rc, {f: int(getattr(st, f)) for f, _ in N.CountStats._fields_}, int(sh.chain_exit)
 
+    def _replacements(self, replacements):
+        """one str or uint16 array per keyword, or a single str that stands for every keyword -> (units, offsets, n_repl)"""
+        if isinstance(replacements, str):
+            replacements = [replacements]
+        elif len(replacements) != len(self.keywords):
+            raise ValueError("%d replacements for %d keywords" % (len(replacements), len(self.keywords)))
+        units, off = _pack(replacements)
+        return units, off, len(off) - 1
+
+    def replace_host(self, hay_units, replacements, cap=None):
+        """acgpu_replace_u16: haystack in host memory -> (the rewritten text as a uint16 array, stats dict).  `replacements`: a
+        list with one str or uint16 array per keyword given to the constructor, or a single str for all of them.  A result
+        larger than the first buffer (the text's size and a quarter) is fetched by one more call with the size the first reports."""
+        hay = np.ascontiguousarray(hay_units, dtype=np.uint16)
+        n = int(hay.size)
+        buf_in = hay if n else np.zeros(1, np.uint16)
+        units, off, n_repl = self._replacements(replacements)
+        if cap is None:
+            cap = n + n // 4 + 64
+        st = N.ReplaceStats()
+        for attempt in (0, 1):
+            out = np.empty(max(cap, 1), dtype=np.uint16)
+            n_out = ctypes.c_uint64(0)
+            rc = N.lib().acgpu_replace_u16(self._h, _vp(buf_in), n, _vp(units), _vp(off), n_repl, _vp(out), cap, ctypes.byref(n_out),
+                                           ctypes.byref(st))
+            if rc == N.E_OVERFLOW and attempt == 0:
+                cap = int(n_out.value)
+                continue
+            N.check(rc, "acgpu_replace_u16")
+            return out[:n_out.value], {f: int(getattr(st, f)) for f, _ in N.ReplaceStats._fields_}
+
+    def replace_device(self, d_hay_ptr, n_units, replacements, d_out_ptr, cap, stream=0):
+        """acgpu_replace_device on raw device pointers: the whole text d_hay_ptr[0 .. n_units) rewritten into d_out_ptr (cap
+        units, 16-byte aligned).  Returns (n_out, rc, stats dict); rc == E_OVERFLOW: n_out is the capacity to call again with."""
+        sh = N.Shard()
+        sh.d_result = None
+        sh.d_hay = d_hay_ptr
+        sh.n_units = n_units
+        sh.own_begin, sh.own_end = 0, n_units
+        sh.text_begin = sh.text_end = 1
+        sh.chain_entry = 0
+        sh.chain_exit = -1
+        units, off, n_repl = self._replacements(replacements)
+        st = N.ReplaceStats()
+        n_out = ctypes.c_uint64(0)
+        rc = N.lib().acgpu_replace_device(self._h, ctypes.byref(sh), _vp(units), _vp(off), n_repl, d_out_ptr, cap, ctypes.byref(n_out),
+                                          ctypes.c_void_p(stream), ctypes.byref(st))
+        return int(n_out.value), rc, {f: int(getattr(st, f)) for f, _ in N.ReplaceStats._fields_}
 
     def match_device_begin(self, d_hay_ptr, n_units, with_ids, d_out_ptr, cap, own=None, text_begin=True, text_end=True,
                            stream=0, profile=False, d_result=None, chain_entry=None):
@@ -491,6 +544,13 @@ class StringSet:
             raise TypeError("haystack is None")
         return self._auto.count_host(utf16(haystack))[0]
 
+    def replace(self, haystack, replacement):
+        """Not in the reference: `haystack` with every match replaced by the str `replacement` (the empty one deletes the
+        matches), rewritten on the device.  The non-overlapping families only: AhoCorasickSet raises the library's error."""
+        if haystack is None:
+            raise TypeError("haystack is None")
+        return _to_str(self._auto.replace_host(utf16(haystack), str(replacement))[0])
+
     def find_all(self, haystack):
         """Convenience (not in the reference): the (n,2) int32 array of (start, end) records."""
         return self._auto.match_host(utf16(haystack), with_ids=False)
@@ -562,6 +622,20 @@ class StringMap:
         if haystack is None:
             raise TypeError("haystack is None")
         return self._auto.count_host(utf16(haystack))[0]
+
+    def replace(self, haystack, replacements=None):
+        """Not in the reference: `haystack` with every match replaced, rewritten on the device -- by its value (replacements is
+        None: the values must all be str), by the entry of a list aligned with the constructor's keywords, or by one str for
+        every keyword.  The non-overlapping families only: AhoCorasickMap raises the library's error."""
+        if haystack is None:
+            raise TypeError("haystack is None")
+        if replacements is None:
+            replacements = self._values
+            if not all(isinstance(v, str) for v in replacements):
+                raise TypeError("replace() without replacements needs str values")
+        elif not isinstance(replacements, str):
+            replacements = list(replacements)[:len(self._keywords)]
+        return _to_str(self._auto.replace_host(utf16(haystack), replacements)[0])
 
     def find_all(self, haystack):
         """Convenience (not in the reference): the (n,3) int32 array of (start, end, keyword_index) records."""

@@ -61,6 +61,11 @@
  *      visit words (device)                     4 bytes per state of the compact automaton
  *      reservoir (device)                       up to cursor_reservoir_bytes: the Map records of a piece
  *                                               that is not counted directly
+ *    A replace call (acgpu_replace_* below) needs the pool's scratch for ONE piece as well, plus, kept by the pool:
+ *      reservoir (device)                       the counting calls' (up to cursor_reservoir_bytes): the Map records of a piece
+ *      plan (device)                            8 bytes per record of the piece (+ 8 per 2048 records)
+ *      replacement table (device)               8 bytes per replacement + 2 per replacement unit, uploaded per call
+ *      slabs (device, acgpu_replace_u16 only)   2 x replace_slab_units x 2 bytes (2 x 64 MiB), or the result's size if smaller
  */
 #ifndef ACGPU_H
 #define ACGPU_H
@@ -515,6 +520,49 @@ int acgpu_count_device(const acgpu_automaton *a, acgpu_shard *shard, uint64_t *d
                        acgpu_count_stats *st);
 
 /*
+ * Replace: the text with every match substituted -- what a listener doing sb.append(haystack, last, start).append(value);
+ * last = end would build -- written on the device; no record reaches the host.  With r_0 .. r_{k-1} the Map records
+ * acgpu_match_u16 returns for the same automaton and text, in their order, and e_{-1} = 0, the result is
+ *   hay[e_{-1}:s_0] + repl[id_0] + hay[e_0:s_1] + repl[id_1] + ... + hay[e_{k-1}:n]
+ * for the four families whose records never overlap and come in position order: ACGPU_MODE_LONGEST, _SHORTEST, _WHOLEWORD,
+ * _WWLONGEST (word tables that are not fold-consistent included).  ACGPU_MODE_ALL: ACGPU_E_UNSUPPORTED, before any device is
+ * touched (its records overlap, and the listener order does not say which one wins).
+ *  repl_units / repl_off : HOST arrays in the layout of kw_units / kw_off: replacement i is repl_units[repl_off[i] .. repl_off[i+1]),
+ *              indexed by keyword_id exactly as a Map value array is (the LAST duplicate's slot is the one read, for Shortest the
+ *              FIRST; the slots of empty keywords and of the other duplicates are never read).  An empty replacement deletes the
+ *              match.  A case-insensitive automaton replaces whatever case matched.
+ *  n_repl    : the number of keywords given to acgpu_build, or 1: that one replacement stands for every keyword (masking).
+ *              Anything else, or more than 2^31 replacement units in all: ACGPU_E_INVALID.
+ *  cap, *n_out : in UNITS.  A result of more than cap units: ACGPU_E_OVERFLOW with *n_out (and st->units_out) the exact size;
+ *              out[0 .. cap) is then unspecified and nothing at or beyond cap has been written (the rest of the text is still
+ *              scanned and planned, for the size, but neither emitted nor copied).  *n_out may exceed 2^32.
+ *  acgpu_replace_u16    : haystack in HOST memory, n_units < 2^31; `out` is host memory.  Without a device it fails as
+ *              acgpu_match_u16 does and leaves `out` untouched.  Works on the NULL stream (STREAM RULE above), under the pool's lock.
+ *  acgpu_replace_device : the shard must be a WHOLE text (own_begin == 0, own_end == n_units, text_begin == text_end == 1), else
+ *              ACGPU_E_UNSUPPORTED: rewriting one shard of a sharded text needs the position up to which the rank before it has
+ *              emitted handed on between the ranks, which is not built (nor is a multi-device, streaming or batch form).  d_out:
+ *              device memory, 16-byte aligned, written directly (clipped at cap).  Everything is enqueued on `stream`; the call
+ *              waits for it per piece -- for the piece's record count, as acgpu_count_device does, and for its output length -- and
+ *              once at the end.
+ * How it works: the text is cut into pieces as a cursor's are (the same ramp and rescan rules); a piece's Map records go to the
+ * pool's reservoir; a prefix sum over them (the plan) gives every replacement its output position, and one kernel writes the
+ * piece's part of the result from the text and the replacement table, for the host entry slab by slab ("replace_slab_units",
+ * default 2^25 units: a slab is copied out while the next is written).  A piece emits the text up to a position before which no
+ * later record can start: for the families whose match belongs to the piece that owns its first unit, the end of its owned range
+ * or of its last record; for Shortest, max_keyword_len - 1 units less than that (emitted from the next piece's left halo).
+ */
+typedef struct acgpu_replace_stats {
+    uint64_t n_records;       /* matches replaced == records the Map match call returns                      */
+    uint64_t units_out;       /* units of the rewritten text (exact, also on ACGPU_E_OVERFLOW)               */
+    uint32_t pieces, rescans; /* as acgpu_count_stats                                                        */
+} acgpu_replace_stats;
+int acgpu_replace_u16(const acgpu_automaton *a, const uint16_t *haystack, uint64_t n_units, const uint16_t *repl_units,
+                      const uint64_t *repl_off, uint32_t n_repl, uint16_t *out, uint64_t cap, uint64_t *n_out,
+                      acgpu_replace_stats *st);
+int acgpu_replace_device(const acgpu_automaton *a, acgpu_shard *shard, const uint16_t *repl_units, const uint64_t *repl_off,
+                         uint32_t n_repl, uint16_t *d_out, uint64_t cap, uint64_t *n_out, void *stream, acgpu_replace_stats *st);
+
+/*
  * Synthetic haystack generator of the benchmark: unit i of the stream is
  * table[((z_i >> 32) * table_len) >> 32] with z_i = SplitMix64 output for counter
  * start_index + i of `seed` (see ahocorasick_amd/synth.py).  d_dst: device pointer.
@@ -563,7 +611,8 @@ int acgpu_stream_probe(const void *d_buf, uint64_t n_bytes, void *stream, int re
  * letters); the cursor's "cursor_first_piece" (units of its first piece, default 2^20), "cursor_max_piece" (largest piece,
  * 2^26) and "cursor_reservoir_bytes" (largest reservoir, 256 MiB); "states_chunk_log2" (k_ac_states: a lane's chunk, 0 = by the text's
  * length, 8 .. 10 = forced) and the counting calls' A/B switches "count_form" (bits: 1 never the direct form, 2 no LDS counters
- * in k_states_hist, 4 no same-key peel in k_states_hist / k_count_ids).  Returns the previous value, -1 for an unknown name. */
+ * in k_states_hist, 4 no same-key peel in k_states_hist / k_count_ids); "replace_slab_units" (acgpu_replace_u16: units of one of the
+ * two device slabs its result leaves through, default 2^25).  Returns the previous value, -1 for an unknown name. */
 int64_t acgpu_set_tunable(const char *name, int64_t value);
 
 const char *acgpu_strerror(int code);

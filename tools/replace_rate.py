@@ -1,0 +1,73 @@
+"""Development tool: what a rewrite costs beyond the match call it contains, one box, one process --
+  match   : acgpu_match_device with Map records on a device-resident text (the scan inside a rewrite);
+  replace : acgpu_replace_device on the same text (scan + plan + emit);
+  probe   : acgpu_stream_probe pattern 1 over 2 N + 2 N_out bytes (a pure read of what the emit moves).
+Workloads: config 4's dictionary (LongestMatch) over its text; the README word list with WholeWordMatch in synth.readme_text.
+usage: replace_rate.py [--log2 28] [--only c4|readme]"""
+import argparse, ctypes, os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np, torch
+from ahocorasick_amd import _native as N, synth
+from ahocorasick_amd.strings import Automaton
+from ahocorasick_amd.unicode_tables import default_word_chars
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--log2", type=int, default=28)
+ap.add_argument("--only", default=None)
+args = ap.parse_args()
+n = 1 << args.log2
+stream = torch.cuda.current_stream().cuda_stream
+
+
+def timed(fn, reps=3):
+    best = None
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) * 1e3
+        best = dt if best is None else min(best, dt)
+    return best, out
+
+
+def run(label, a, d_hay, rec_cap, repls):
+    d_recs = torch.empty((rec_cap, 3), dtype=torch.int32, device="cuda")
+
+    def match():
+        nm, rc, _, _ = a.match_device(d_hay.data_ptr(), n, True, d_recs.data_ptr(), rec_cap, stream=stream)
+        assert rc == 0, rc
+        return nm
+    ms_match, n_recs = timed(match)
+    need, rc, _ = a.replace_device(d_hay.data_ptr(), n, repls, 0, 0, stream=stream)  # cap 0: the size
+    assert rc in (N.OK, N.E_OVERFLOW), rc
+    d_out = torch.empty(need + 8, dtype=torch.int16, device="cuda")
+
+    def replace():
+        n_out, rc, st = a.replace_device(d_hay.data_ptr(), n, repls, d_out.data_ptr(), need, stream=stream)
+        assert rc == 0 and n_out == need, (rc, n_out)
+        return st
+    ms_repl, st = timed(replace)
+    assert st["n_records"] == n_recs, (st, n_recs)
+    nbytes = 2 * n + 2 * need
+    d_probe = torch.empty(nbytes // 2 + 8, dtype=torch.int16, device="cuda")
+    ms_probe = ctypes.c_float(0)
+    N.check(N.lib().acgpu_stream_probe(d_probe.data_ptr(), nbytes & ~15, ctypes.c_void_p(stream), 5, 1, ctypes.byref(ms_probe)), "stream_probe")
+    print("%-8s N=%d  R=%d  N_out=%d  pieces=%d rescans=%d" % (label, n, n_recs, need, st["pieces"], st["rescans"]))
+    print("%-8s match %.3f ms | replace %.3f ms | beyond the match %.3f ms | pure read of 2N+2N_out %.3f ms (x%.1f)" % (
+        label, ms_match, ms_repl, ms_repl - ms_match, ms_probe.value, (ms_repl - ms_match) / max(ms_probe.value, 1e-6)), flush=True)
+
+
+if args.only in (None, "c4"):
+    kws = synth.config_keywords("C4")
+    d_hay = torch.empty(n, dtype=torch.int16, device="cuda")
+    tab = np.ascontiguousarray(synth.ALPHA_LOWER)
+    N.check(N.lib().acgpu_synth_fill(d_hay.data_ptr(), n, 0, synth.CONFIGS["C4"]["hay_seed"], tab.ctypes.data_as(ctypes.c_void_p), len(tab),
+                                     ctypes.c_void_p(stream)), "synth_fill")
+    run("C4", Automaton(N.MODE_LONGEST, kws, True), d_hay, n // 2 + 1024, "#")
+    del d_hay
+if args.only in (None, "readme"):
+    words = synth.readme_dictionary()
+    block = synth.readme_text(2006, min(n, 1 << 25), words)
+    d_hay = torch.from_numpy(block.view(np.int16)).cuda().repeat(max(1, n // block.size))
+    run("README", Automaton(N.MODE_WHOLEWORD, words, True, word_chars=default_word_chars()), d_hay, n // 2 + 1024, "***")
