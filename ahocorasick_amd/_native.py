@@ -77,7 +77,7 @@ SYMBOLS = ["acgpu_build", "acgpu_free", "acgpu_get_info", "acgpu_match_u16", "ac
            "acgpu_match_device_allgather", "acgpu_last_rccl_error", "acgpu_gather_slot_bytes",
            "acgpu_stream_set_pipelined", "acgpu_stream_reserve", "acgpu_cursor_open", "acgpu_cursor_next",
            "acgpu_cursor_get_stats", "acgpu_cursor_close", "acgpu_count_u16", "acgpu_count_device",
-           "acgpu_replace_u16", "acgpu_replace_device"]
+           "acgpu_replace_u16", "acgpu_replace_device", "acgpu_replace_batch_u16"]
 
 _lib = None
 
@@ -160,6 +160,8 @@ def lib():
         L.acgpu_replace_device.restype = ci
         L.acgpu_replace_device.argtypes = [vp, ctypes.POINTER(Shard), vp, vp, u32, vp, u64, ctypes.POINTER(u64), vp,
                                            ctypes.POINTER(ReplaceStats)]
+        L.acgpu_replace_batch_u16.restype = ci
+        L.acgpu_replace_batch_u16.argtypes = [vp, vp, vp, u32, vp, vp, u32, vp, u64, vp, ctypes.POINTER(u64), ctypes.POINTER(ReplaceStats)]
         L.acgpu_debug_wordhash_perfect.restype = ci
         L.acgpu_debug_wordhash_perfect.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.acgpu_debug_wordhash.restype = ci

@@ -2114,6 +2114,34 @@ static bool device_numa_cpus(int dev, cpu_set_t *set) {
     return n_set > 0;
 }
 
+// the concatenation of the batch calls (acgpu_host.h); the offsets stand 64-byte aligned behind the text
+int batch_concat(DeviceState &d, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks, uint16_t sep, uint16_t **h_cat_out,
+                 uint32_t **h_off_out) {
+    const uint64_t cat = offsets[n_haystacks] - offsets[0] + n_haystacks;
+    const size_t off_bytes = ((size_t)n_haystacks + 1) * 4, pin_need = cat * 2 + 64 + off_bytes;
+    if (d.batch_pin_bytes < pin_need) {
+        if (d.batch_pin) (void)hipHostFree(d.batch_pin);
+        d.batch_pin = nullptr;
+        d.batch_pin_bytes = 0;
+        HIP_TRY(hipHostMalloc(&d.batch_pin, pin_need + pin_need / 4, hipHostMallocDefault));
+        d.batch_pin_bytes = pin_need + pin_need / 4;
+    }
+    uint16_t *h_cat = (uint16_t *)d.batch_pin;
+    uint32_t *h_off = (uint32_t *)((char *)d.batch_pin + ((cat * 2 + 63) & ~(size_t)63));
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n_haystacks; i++) {
+        const uint64_t len = offsets[i + 1] - offsets[i];
+        h_off[i] = (uint32_t)at;
+        if (len) std::memcpy(h_cat + at, units + offsets[i], len * 2);
+        at += len;
+        h_cat[at++] = sep;
+    }
+    h_off[n_haystacks] = (uint32_t)at;
+    *h_cat_out = h_cat;
+    *h_off_out = h_off;
+    return ACGPU_OK;
+}
+
 int stage_whole_text(DeviceState &d, const uint16_t *haystack, uint64_t n_units, acgpu_shard *out) {
     const int rc = d.stage_hay.ensure(n_units * 2 + 16);
     if (rc) return rc;
@@ -2424,27 +2452,10 @@ int acgpu_match_batch_u16(const acgpu_automaton *ca, const uint16_t *units, cons
     if (rc) return rc;
     std::lock_guard<std::mutex> lock(d->mu); // staging buffers are part of the per-device scratch pool
     if (d->inflight > 0) return ACGPU_E_INVALID; // (the NULL stream: see the stream rule)
-    const size_t off_bytes = ((size_t)n_haystacks + 1) * 4, pin_need = cat * 2 + 64 + off_bytes;
-    if (d->batch_pin_bytes < pin_need) {
-        if (d->batch_pin) (void)hipHostFree(d->batch_pin);
-        d->batch_pin = nullptr;
-        d->batch_pin_bytes = 0;
-        HIP_TRY(hipHostMalloc(&d->batch_pin, pin_need + pin_need / 4, hipHostMallocDefault));
-        d->batch_pin_bytes = pin_need + pin_need / 4;
-    }
-    uint16_t *h_cat = (uint16_t *)d->batch_pin;
-    uint32_t *h_off = (uint32_t *)((char *)d->batch_pin + ((cat * 2 + 63) & ~(size_t)63));
-    {
-        uint64_t at = 0;
-        for (uint32_t i = 0; i < n_haystacks; i++) {
-            const uint64_t len = offsets[i + 1] - offsets[i];
-            h_off[i] = (uint32_t)at;
-            if (len) std::memcpy(h_cat + at, units + offsets[i], len * 2);
-            at += len;
-            h_cat[at++] = (uint16_t)t.sep_unit;
-        }
-        h_off[n_haystacks] = (uint32_t)at;
-    }
+    const size_t off_bytes = ((size_t)n_haystacks + 1) * 4;
+    uint16_t *h_cat = nullptr;
+    uint32_t *h_off = nullptr;
+    if ((rc = batch_concat(*d, units, offsets, n_haystacks, (uint16_t)t.sep_unit, &h_cat, &h_off))) return rc;
     if ((rc = d->stage_hay.ensure(cat * 2 + 16))) return rc;
     if ((rc = d->stage_out.ensure(cap * (uint64_t)record_kind + 16))) return rc;
     if ((rc = d->batch_off.ensure(off_bytes + 16))) return rc;

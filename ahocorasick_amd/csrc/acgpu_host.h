@@ -194,6 +194,7 @@ struct DeviceState {
     DevBuf replace_tab, replace_plan, replace_slab;      // acgpu_replace_*: the replacement table, the plan {sums, output positions}, the host entry's two slabs
     void *replace_pin = nullptr;                         // ... pinned, 64 bytes: a piece's output length and last end
     hipEvent_t replace_ev[4] = {nullptr, nullptr, nullptr, nullptr}; // ... slab b emitted (b), slab b copied out (2 + b)
+    DevBuf replace_merged, replace_off;                  // acgpu_replace_batch_u16: a piece's records merged with its separators, the result's offsets
     CountCall *count = nullptr;                          // the counting call that runs on this pool (it holds mu), or nullptr
     double all_density = -1.0;                           // ALL: records per unit of this pool's last call (-1: none yet): k_ac_states or the tile kernel
     int fol_level = 0;                                   // k_longest_follow: 0 = run-up of 128 positions, 1 = of a whole segment (a call's chains had not merged), 2 = not for this pool's texts
@@ -227,7 +228,7 @@ struct DeviceState {
         if (batch_pin) (void)hipHostFree(batch_pin);
         batch_off.release(); batch_out.release();
         visits.release(); count_res.release(); count_out.release();
-        replace_tab.release(); replace_plan.release(); replace_slab.release();
+        replace_tab.release(); replace_plan.release(); replace_slab.release(); replace_merged.release(); replace_off.release();
         if (replace_pin) (void)hipHostFree(replace_pin);
         for (auto &e : replace_ev) if (e) (void)hipEventDestroy(e);
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
@@ -351,6 +352,12 @@ int scan_host_range(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack
 // The whole host text as one shard: copied (blocking) into d.stage_hay; *out = that buffer, all of it owned, the text's begin and
 // end, no chain.  The caller holds d.mu.
 int stage_whole_text(DeviceState &d, const uint16_t *haystack, uint64_t n_units, acgpu_shard *out);
+
+// The haystacks of a batch call as one text in d.batch_pin, a separator `sep` behind every haystack: *h_cat = the text, *h_off =
+// n_haystacks + 1 words behind it, h_off[i] = the first unit of haystack i (separator i stands at h_off[i + 1] - 1).  The caller
+// holds d.mu and has checked the offsets.
+int batch_concat(DeviceState &d, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks, uint16_t sep, uint16_t **h_cat,
+                 uint32_t **h_off);
 
 // A text on its way through a reservoir, piece by piece (scan_next_piece, acgpu_pieces.hip): the cursor keeps one from page call
 // to page call, a counting call has one for its duration.

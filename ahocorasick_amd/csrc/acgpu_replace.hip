@@ -9,6 +9,11 @@
 //    store -- from the text and the replacement table.
 // The host keeps `done`, the text position up to which output exists, and `out_pos`, the units written so far; what a piece may
 // emit, [done, limit), is decided by replace_limit below.
+//
+// acgpu_replace_batch_u16 rewrites many short texts as ONE such text: the haystacks with a separator unit behind each (the batch
+// match call's concatenation), where a separator is a match that is deleted.  Behind every piece k_replace_merge merges the piece's
+// records with the pseudo-records of its separators; plan and emit run over the merged list as they are, so the results come out
+// back to back, and k_replace_batch_offsets reads every result's first output unit off the plan.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -279,6 +284,66 @@ __global__ __launch_bounds__(kEmitBlock) void k_replace_emit(EmitArgs A) {
     }
 }
 
+// The separators a piece of a batch call merges: separator j of them stands at text position cat_off[i0 + j + 1] - 1 (cat_off[i] =
+// the first unit of haystack i in the concatenation), `base` = the text position of the records' buffer's unit 0.
+struct BatchSeps {
+    const uint32_t *cat_off = nullptr;
+    uint32_t i0 = 0, n_sep = 0;
+    int64_t base = 0;
+    int32_t id = 0; // the keyword id of a separator's pseudo-record: the empty slot behind the replacement table
+};
+
+constexpr int kMergeBlock = 256;
+
+__device__ __forceinline__ int64_t sep_at(const BatchSeps &S, uint32_t j) { return (int64_t)S.cat_off[S.i0 + j + 1] - 1 - S.base; } // buffer relative
+
+// the records (ascending starts) that start in front of buffer position p
+__device__ __forceinline__ uint64_t records_before(const int32_t *__restrict__ recs, uint64_t cnt, int64_t p) {
+    uint64_t lo = 0, hi = cnt;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if ((int64_t)recs[3 * mid] < p) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// A piece's cnt records and the pseudo-records {p, p + 1, S.id} of its separators, as one list in position order.  Both lists
+// ascend and cannot tie -- a record neither contains nor starts at a separator -- so an element's place is its index plus the
+// elements of the other list in front of it: a rank merge, one binary search per element.
+__global__ __launch_bounds__(kMergeBlock) void k_replace_merge(const int32_t *__restrict__ recs, uint64_t cnt, BatchSeps S, int32_t *__restrict__ merged) {
+    const uint64_t t = (uint64_t)blockIdx.x * kMergeBlock + threadIdx.x;
+    if (t < cnt) {
+        const int32_t s = recs[3 * t];
+        uint32_t lo = 0, hi = S.n_sep; // the separators in front of s
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (sep_at(S, mid) < (int64_t)s) lo = mid + 1;
+            else hi = mid;
+        }
+        int32_t *o = merged + 3 * (t + lo);
+        o[0] = s;
+        o[1] = recs[3 * t + 1];
+        o[2] = recs[3 * t + 2];
+    } else if (t < cnt + S.n_sep) {
+        const int64_t p = sep_at(S, (uint32_t)(t - cnt));
+        int32_t *o = merged + 3 * (t - cnt + records_before(recs, cnt, p));
+        o[0] = (int32_t)p;
+        o[1] = (int32_t)p + 1;
+        o[2] = S.id;
+    }
+}
+
+// Behind the plan of such a merged list: separator i0 + j ends haystack i0 + j, so the result of haystack i0 + j + 1 begins where
+// the separator's (empty) replacement stands -- out_pos, the output in front of the piece, plus the plan's position of its record.
+__global__ __launch_bounds__(kMergeBlock) void k_replace_batch_offsets(const int32_t *__restrict__ recs, uint64_t cnt, BatchSeps S,
+                                                                       const int64_t *__restrict__ pos, uint64_t out_pos,
+                                                                       uint64_t *__restrict__ out_off) {
+    const uint32_t j = blockIdx.x * kMergeBlock + threadIdx.x;
+    if (j >= S.n_sep) return;
+    out_off[(uint64_t)S.i0 + j + 1] = out_pos + (uint64_t)pos[j + records_before(recs, cnt, sep_at(S, j))];
+}
+
 // What one call holds while it runs (the caller holds d.mu).
 struct ReplaceCall {
     acgpu_automaton *a;
@@ -292,11 +357,21 @@ struct ReplaceCall {
     uint64_t done = 0;         // output exists for the text's units [0, done)
     uint64_t out_pos = 0;      // units of it (beyond cap: counted, not written)
     acgpu_replace_stats st{};
+    // a batch call: the concatenation's offsets on the host (n_hay + 1 words), what the current piece merges (seps.cat_off: the
+    // offsets on the device, set for the whole call), the result's offsets on the device (n_hay + 1 words of 64 bits)
+    const uint32_t *h_cat_off = nullptr;
+    uint32_t n_hay = 0;
+    BatchSeps seps{};
+    uint64_t *d_out_off = nullptr;
 };
 
-int upload_table(ReplaceCall &c, const uint16_t *repl_units, const uint64_t *repl_off, uint32_t n_repl) {
+// full: the table in its full form, whatever n_repl is -- an entry per keyword given to acgpu_build (a single replacement: they
+// share its units) and behind them an empty one, the slot of a batch call's separators; repl_of then never sees n_repl == 1 where
+// there is a keyword.
+int upload_table(ReplaceCall &c, const uint16_t *repl_units, const uint64_t *repl_off, uint32_t n_repl, bool full = false) {
     const uint64_t r0 = n_repl ? repl_off[0] : 0, total = n_repl ? repl_off[n_repl] - r0 : 0;
-    const size_t ent_bytes = ((size_t)n_repl * 8 + 15) & ~(size_t)15;
+    const uint32_t n_ent = full ? c.a->n_given + 1 : n_repl;
+    const size_t ent_bytes = ((size_t)n_ent * 8 + 15) & ~(size_t)15;
     std::vector<uint64_t> blob;
     try {
         blob.assign((ent_bytes + (size_t)total * 2 + 16 + 7) / 8, 0);
@@ -304,9 +379,11 @@ int upload_table(ReplaceCall &c, const uint16_t *repl_units, const uint64_t *rep
         return ACGPU_E_NOMEM;
     }
     uint32_t *ent = reinterpret_cast<uint32_t *>(blob.data());
-    for (uint32_t i = 0; i < n_repl; ++i) {
-        ent[2 * i] = (uint32_t)(repl_off[i] - r0);
-        ent[2 * i + 1] = (uint32_t)(repl_off[i + 1] - repl_off[i]);
+    for (uint32_t i = 0; i < n_ent; ++i) {
+        const uint32_t from = n_repl == 1 ? 0 : i; // (the blob is zeroed: the entries behind the caller's stay empty)
+        if (from >= n_repl || (full && i + 1 == n_ent)) continue;
+        ent[2 * i] = (uint32_t)(repl_off[from] - r0);
+        ent[2 * i + 1] = (uint32_t)(repl_off[from + 1] - repl_off[from]);
     }
     if (total) std::copy(repl_units + r0, repl_units + r0 + total, reinterpret_cast<uint16_t *>(reinterpret_cast<char *>(blob.data()) + ent_bytes));
     const int rc = c.d.replace_tab.ensure(blob.size() * 8);
@@ -314,7 +391,7 @@ int upload_table(ReplaceCall &c, const uint16_t *repl_units, const uint64_t *rep
     HIP_TRY(hipMemcpy(c.d.replace_tab.p, blob.data(), blob.size() * 8, hipMemcpyHostToDevice)); // (blocking: the blob dies here)
     c.rt.ent = reinterpret_cast<const uint2 *>(c.d.replace_tab.p);
     c.rt.units = reinterpret_cast<const uint16_t *>(reinterpret_cast<const char *>(c.d.replace_tab.p) + ent_bytes);
-    c.rt.n_repl = n_repl;
+    c.rt.n_repl = n_ent;
     return ACGPU_OK;
 }
 
@@ -329,6 +406,13 @@ int upload_table(ReplaceCall &c, const uint16_t *repl_units, const uint64_t *rep
 //    behind own_hi - (max_len - 1), and at or behind every earlier record's end, which `done` and last_end bound.  The units
 //    withheld, at most max_len - 1 in front of own_hi, are the next piece's left halo: it emits them from there.  The limit never
 //    exceeds own_hi, the buffer's end.
+//  * A BATCH call's piece merges the separators in [done, own_hi), every family, and last_end is the end of the last element of
+//    the merged list, record or separator.  A first-unit family's record that starts before own_hi cannot reach across a separator
+//    at or behind own_hi, so no separator lies in [own_hi, last_end).  For SHORTEST a later record ends behind own_hi and holds no
+//    separator, so it starts behind the last merged separator: max(last_end, done, own_hi - (max_len - 1)) is still a position no
+//    later record starts before.  And every separator below the limit has been merged: the limit is at most own_hi, or, for the
+//    first-unit families, at most the end of a record that holds no separator.  So the plan's sum holds exactly the elements below
+//    the limit, and every separator is merged by exactly one piece: the one that emits it.
 uint64_t replace_limit(const HostTables &t, bool last_or_whole, uint64_t n, uint64_t own_hi, uint64_t last_end, uint64_t done) {
     if (last_or_whole) return n;
     if (t.mode == ACGPU_MODE_SHORTEST) {
@@ -338,10 +422,10 @@ uint64_t replace_limit(const HostTables &t, bool last_or_whole, uint64_t n, uint
     return std::max({own_hi, last_end, done});
 }
 
-int launch_emit(ReplaceCall &c, const uint16_t *hay, uint64_t cnt, int64_t done_rel, uint64_t w0, uint64_t w1, uint16_t *dst, hipStream_t stream) {
+int launch_emit(ReplaceCall &c, const uint16_t *hay, const int32_t *recs, uint64_t cnt, int64_t done_rel, uint64_t w0, uint64_t w1, uint16_t *dst, hipStream_t stream) {
     EmitArgs A;
     A.hay = hay;
-    A.recs = reinterpret_cast<const int32_t *>(c.d.count_res.p);
+    A.recs = recs;
     A.pos = reinterpret_cast<const int64_t *>(c.d.replace_plan.p) + 2 + (cnt + kPlanTile - 1) / kPlanTile;
     A.n_recs = (int64_t)cnt;
     A.rt = c.rt;
@@ -356,9 +440,31 @@ int launch_emit(ReplaceCall &c, const uint16_t *hay, uint64_t cnt, int64_t done_
     return ACGPU_OK;
 }
 
-// Behind a piece: plan its cnt records (in d.count_res, relative to `base`), then emit [done, limit) of the text `hay` (the
-// piece's buffer, whose unit 0 is the text's unit `base`).
-int replace_piece(ReplaceCall &c, const uint16_t *hay, uint64_t base, uint64_t cnt, uint64_t own_hi, bool last_or_whole) {
+// A batch call's piece: its cnt records (d.count_res) merged with the separators in [done, own_hi) into d.replace_merged.  Which
+// separators those are the host knows from its copy of the offsets, so the plan still gets its n by value.
+int merge_separators(ReplaceCall &c, uint64_t base, uint64_t own_hi, const int32_t **recs, uint64_t *cnt) {
+    const uint32_t *sep_end = c.h_cat_off + 1; // separator i stands at sep_end[i] - 1: at or behind x <=> sep_end[i] > x
+    const uint32_t i0 = (uint32_t)(std::upper_bound(sep_end, sep_end + c.n_hay, c.done) - sep_end);
+    const uint32_t i1 = (uint32_t)(std::upper_bound(sep_end, sep_end + c.n_hay, own_hi) - sep_end);
+    c.seps.i0 = i0;
+    c.seps.n_sep = i1 > i0 ? i1 - i0 : 0;
+    c.seps.base = (int64_t)base;
+    if (!c.seps.n_sep) return ACGPU_OK;
+    const uint64_t n = *cnt + c.seps.n_sep;
+    const int rc = c.d.replace_merged.ensure(n * ACGPU_REC_MAP);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_replace_merge, dim3((unsigned)((n + kMergeBlock - 1) / kMergeBlock)), dim3(kMergeBlock), 0, c.stream, *recs, *cnt, c.seps,
+                       reinterpret_cast<int32_t *>(c.d.replace_merged.p));
+    HIP_TRY(hipGetLastError());
+    *recs = reinterpret_cast<const int32_t *>(c.d.replace_merged.p);
+    *cnt = n;
+    return ACGPU_OK;
+}
+
+// Behind a piece: plan its cnt records `recs` (relative to `base`; a batch call's: n_found records and the piece's separators),
+// then emit [done, limit) of the text `hay` (the piece's buffer, whose unit 0 is the text's unit `base`).
+int replace_piece(ReplaceCall &c, const uint16_t *hay, uint64_t base, const int32_t *recs, uint64_t cnt, uint64_t n_found, uint64_t own_hi,
+                  bool last_or_whole) {
     DeviceState &d = c.d;
     const int64_t done_rel = (int64_t)(c.done - base);
     int64_t delta = 0;
@@ -368,10 +474,12 @@ int replace_piece(ReplaceCall &c, const uint16_t *hay, uint64_t base, uint64_t c
         int rc = d.replace_plan.ensure((2 + (size_t)n_blocks + cnt) * 8); // {sum of the deltas, last end} | workgroup sums | pos
         if (rc) return rc;
         int64_t *slot = reinterpret_cast<int64_t *>(d.replace_plan.p), *bsum = slot + 2, *pos = bsum + n_blocks;
-        const int32_t *recs = reinterpret_cast<const int32_t *>(d.count_res.p);
         hipLaunchKernelGGL(k_replace_sums, dim3(n_blocks), dim3(kPlanBlock), 0, c.stream, recs, cnt, c.rt, bsum);
         hipLaunchKernelGGL(k_replace_offsets, dim3(1), dim3(kPlanBlock), 0, c.stream, bsum, n_blocks, recs, cnt, slot);
         hipLaunchKernelGGL(k_replace_plan, dim3(n_blocks), dim3(kPlanBlock), 0, c.stream, recs, cnt, c.rt, (const int64_t *)bsum, done_rel, pos);
+        if (c.seps.n_sep) // (over the piece's own records: the same search that placed the separators)
+            hipLaunchKernelGGL(k_replace_batch_offsets, dim3((c.seps.n_sep + kMergeBlock - 1) / kMergeBlock), dim3(kMergeBlock), 0, c.stream,
+                               reinterpret_cast<const int32_t *>(d.count_res.p), n_found, c.seps, (const int64_t *)pos, c.out_pos, c.d_out_off);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(d.replace_pin, slot, 16, hipMemcpyDeviceToHost, c.stream));
         HIP_TRY(hipStreamSynchronize(c.stream)); // the piece's output length decides the windows and the next piece's `done`
@@ -384,7 +492,7 @@ int replace_piece(ReplaceCall &c, const uint16_t *hay, uint64_t base, uint64_t c
     const uint64_t total = (uint64_t)total_s;
     const uint64_t room = c.cap > c.out_pos ? c.cap - c.out_pos : 0, emit_total = std::min(total, room); // beyond cap: planned, not written
     if (emit_total && c.d_out) {
-        const int rc = launch_emit(c, hay, cnt, done_rel, 0, emit_total, c.d_out + c.out_pos, c.stream);
+        const int rc = launch_emit(c, hay, recs, cnt, done_rel, 0, emit_total, c.d_out + c.out_pos, c.stream);
         if (rc) return rc;
     } else if (emit_total) {
         // through two slabs of the pool: slab k is copied to the caller's memory (on the copy stream) while slab k + 1 is emitted
@@ -406,7 +514,7 @@ int replace_piece(ReplaceCall &c, const uint16_t *hay, uint64_t base, uint64_t c
             const uint64_t w1 = std::min(emit_total, w0 + slab);
             const int b = k & 1;
             if (copied[b]) HIP_TRY(hipStreamWaitEvent(c.stream, d.replace_ev[2 + b], 0)); // (the slab has left for the host)
-            if ((rc = launch_emit(c, hay, cnt, done_rel, w0, w1, buf[b], c.stream))) return rc;
+            if ((rc = launch_emit(c, hay, recs, cnt, done_rel, w0, w1, buf[b], c.stream))) return rc;
             HIP_TRY(hipEventRecord(d.replace_ev[b], c.stream));
             if (k > 0 && (rc = copy_out(b ^ 1, prev0, prev1))) return rc;
             prev0 = w0;
@@ -418,7 +526,7 @@ int replace_piece(ReplaceCall &c, const uint16_t *hay, uint64_t base, uint64_t c
     }
     c.done = limit;
     c.out_pos += total;
-    c.st.n_records += cnt;
+    c.st.n_records += n_found;
     return ACGPU_OK;
 }
 
@@ -441,7 +549,10 @@ int replace_pieces(ReplaceCall &c, int64_t chain, bool whole, const PieceScan &s
         uint64_t cnt = 0, base = 0;
         if ((rc = scan_next_piece(p, scan, &cnt, &base))) break;
         const uint16_t *hay = scan.shard ? scan.shard->d_hay : reinterpret_cast<const uint16_t *>(d.stage_hay.p);
-        rc = replace_piece(c, hay, base, cnt, p.pos, whole || p.pos >= p.end);
+        const int32_t *recs = reinterpret_cast<const int32_t *>(d.count_res.p);
+        uint64_t n_list = cnt;
+        if (c.h_cat_off && (rc = merge_separators(c, base, p.pos, &recs, &n_list))) break;
+        rc = replace_piece(c, hay, base, recs, n_list, cnt, p.pos, whole || p.pos >= p.end);
     }
     c.st.pieces = (uint32_t)p.pieces;
     c.st.rescans = (uint32_t)p.rescans;
@@ -519,6 +630,84 @@ int acgpu_replace_device(const acgpu_automaton *ca, acgpu_shard *shard, const ui
     const hipError_t e = hipStreamSynchronize(stream); // the final wait
     if (rc) return rc;
     HIP_TRY(e);
+    if (st) *st = c.st;
+    *n_out = c.out_pos;
+    return c.out_pos > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
+}
+
+int acgpu_replace_batch_u16(const acgpu_automaton *ca, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks,
+                            const uint16_t *repl_units, const uint64_t *repl_off, uint32_t n_repl, uint16_t *out, uint64_t cap,
+                            uint64_t *out_offsets, uint64_t *n_out, acgpu_replace_stats *st) {
+    if (!ca || !offsets || !n_out || !out_offsets || (cap && !out)) return ACGPU_E_INVALID;
+    acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
+    int rc = check_table(a, repl_units, repl_off, n_repl);
+    if (rc) return rc;
+    *n_out = 0;
+    out_offsets[0] = 0;
+    if (st) *st = acgpu_replace_stats{};
+    if (n_haystacks == 0) return ACGPU_OK;
+    for (uint32_t i = 0; i < n_haystacks; i++)
+        if (offsets[i] > offsets[i + 1]) return ACGPU_E_INVALID;
+    const uint64_t total = offsets[n_haystacks] - offsets[0];
+    if (total && !units) return ACGPU_E_INVALID;
+    const uint64_t cat = total + n_haystacks; // one separator behind every haystack
+    if (cat >= (1ull << 31)) return ACGPU_E_INVALID;
+    const HostTables &t = a->t;
+    // where acgpu_match_batch_u16 scans haystack by haystack (no unit is free to separate them, or a word matcher over a table that
+    // is not fold-consistent: see there), one replace call per haystack, the results back to back
+    if (t.sep_unit < 0 || ((t.mode == ACGPU_MODE_WHOLEWORD || t.mode == ACGPU_MODE_WWLONGEST) && !t.fold_consistent)) {
+        acgpu_replace_stats sum{};
+        for (uint32_t i = 0; i < n_haystacks; i++) {
+            const uint64_t len = offsets[i + 1] - offsets[i], room = cap > sum.units_out ? cap - sum.units_out : 0;
+            uint64_t got = 0;
+            acgpu_replace_stats one{};
+            rc = acgpu_replace_u16(ca, len ? units + offsets[i] : nullptr, len, repl_units, repl_off, n_repl, room ? out + sum.units_out : nullptr,
+                                   room, &got, &one);
+            if (rc != ACGPU_OK && rc != ACGPU_E_OVERFLOW) return rc;
+            sum.n_records += one.n_records;
+            sum.pieces += one.pieces;
+            sum.rescans += one.rescans;
+            sum.units_out += got;
+            out_offsets[i + 1] = sum.units_out;
+        }
+        if (st) *st = sum;
+        *n_out = sum.units_out;
+        return sum.units_out > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
+    }
+    DeviceState *dp = nullptr;
+    if ((rc = device_for_call(a, &dp))) return rc; // (no device: fails here, and out is untouched)
+    DeviceState &d = *dp;
+    std::lock_guard<std::mutex> lock(d.mu);
+    if (d.inflight > 0) return ACGPU_E_INVALID; // (the NULL stream: see the stream rule)
+    uint16_t *h_cat = nullptr;
+    uint32_t *h_off = nullptr;
+    if ((rc = batch_concat(d, units, offsets, n_haystacks, (uint16_t)t.sep_unit, &h_cat, &h_off))) return rc;
+    const size_t off_bytes = ((size_t)n_haystacks + 1) * 4;
+    if ((rc = d.batch_off.ensure(off_bytes + 16))) return rc;
+    if ((rc = d.replace_off.ensure(((size_t)n_haystacks + 1) * 8))) return rc;
+    HIP_TRY(hipMemcpyAsync(d.batch_off.p, h_off, off_bytes, hipMemcpyHostToDevice, d.call_stream));
+    ReplaceCall c{a, d, d.call_stream};
+    c.h_out = out;
+    c.cap = cap;
+    c.n = cat;
+    c.h_cat_off = h_off;
+    c.n_hay = n_haystacks;
+    c.seps.cat_off = reinterpret_cast<const uint32_t *>(d.batch_off.p);
+    c.seps.id = (int32_t)a->n_given;
+    c.d_out_off = reinterpret_cast<uint64_t *>(d.replace_off.p);
+    if ((rc = upload_table(c, repl_units, repl_off, n_repl, /*full=*/true))) return rc;
+    const bool whole = one_piece(shard_rule(t, ACGPU_REC_MAP, false), t);
+    d.start_behind = t.sep_unit; // (WholeWordLongest: every haystack's first unit is a walk start, also where a piece's left halo is the separator)
+    rc = replace_pieces(c, 0, whole, PieceScan{a, d, h_cat, cat, nullptr, d.call_stream});
+    d.start_behind = -1;
+    if (rc) {
+        (void)hipStreamSynchronize(d.call_stream); // (nothing of the call stays in flight)
+        if (d.copy_stream) (void)hipStreamSynchronize(d.copy_stream);
+        return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(out_offsets + 1, c.d_out_off + 1, (size_t)n_haystacks * 8, hipMemcpyDeviceToHost, d.call_stream)); // (every separator was merged once)
+    HIP_TRY(hipStreamSynchronize(d.call_stream));
+    c.st.units_out = c.out_pos;
     if (st) *st = c.st;
     *n_out = c.out_pos;
     return c.out_pos > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;

@@ -232,6 +232,27 @@ class Automaton:
             N.check(rc, "acgpu_replace_u16")
             return out[:n_out.value], {f: int(getattr(st, f)) for f, _ in N.ReplaceStats._fields_}
 
+    def replace_batch(self, haystacks, replacements, cap=None):
+        """acgpu_replace_batch_u16: many short haystacks (str or uint16 arrays) rewritten in one call -> (units, out_offsets,
+        stats dict): the result of haystack i is units[out_offsets[i]:out_offsets[i + 1]].  `replacements` as for replace_host,
+        and the same one retry with the size the first call reports."""
+        units, off = _pack(haystacks)
+        r_units, r_off, n_repl = self._replacements(replacements)
+        if cap is None:
+            cap = int(off[-1]) + int(off[-1]) // 4 + 64
+        st = N.ReplaceStats()
+        out_off = np.zeros(len(off), dtype=np.uint64)
+        for attempt in (0, 1):
+            out = np.empty(max(cap, 1), dtype=np.uint16)
+            n_out = ctypes.c_uint64(0)
+            rc = N.lib().acgpu_replace_batch_u16(self._h, _vp(units), _vp(off), len(off) - 1, _vp(r_units), _vp(r_off), n_repl, _vp(out), cap,
+                                                 _vp(out_off), ctypes.byref(n_out), ctypes.byref(st))
+            if rc == N.E_OVERFLOW and attempt == 0:
+                cap = int(n_out.value)
+                continue
+            N.check(rc, "acgpu_replace_batch_u16")
+            return out[:n_out.value], out_off, {f: int(getattr(st, f)) for f, _ in N.ReplaceStats._fields_}
+
     def replace_device(self, d_hay_ptr, n_units, replacements, d_out_ptr, cap, stream=0):
         """acgpu_replace_device on raw device pointers: the whole text d_hay_ptr[0 .. n_units) rewritten into d_out_ptr (cap
         units, 16-byte aligned).  Returns (n_out, rc, stats dict); rc == E_OVERFLOW: n_out is the capacity to call again with."""
@@ -515,6 +536,19 @@ def _listener_fn(listener):
     return listener.match if hasattr(listener, "match") else listener
 
 
+def _checked(haystacks):
+    haystacks = list(haystacks)
+    if any(h is None for h in haystacks):
+        raise TypeError("haystack is None")
+    return haystacks
+
+
+def _split_batch(units, out_off):
+    """the result of Automaton.replace_batch -> one str per haystack"""
+    o = out_off.tolist()
+    return [_to_str(units[o[i]:o[i + 1]]) for i in range(len(o) - 1)]
+
+
 class StringSet:
     """S/StringSet.java:3-5"""
     _MODE = None
@@ -550,6 +584,11 @@ class StringSet:
         if haystack is None:
             raise TypeError("haystack is None")
         return _to_str(self._auto.replace_host(utf16(haystack), str(replacement))[0])
+
+    def replace_batch(self, haystacks, replacement):
+        """Not in the reference: [replace(h, replacement) for h in haystacks] in ONE device call (short inputs: a call has tens
+        of microseconds of fixed cost) -> a list of str."""
+        return _split_batch(*self._auto.replace_batch(_checked(haystacks), str(replacement))[:2])
 
     def find_all(self, haystack):
         """Convenience (not in the reference): the (n,2) int32 array of (start, end) records."""
@@ -629,13 +668,19 @@ class StringMap:
         every keyword.  The non-overlapping families only: AhoCorasickMap raises the library's error."""
         if haystack is None:
             raise TypeError("haystack is None")
+        return _to_str(self._auto.replace_host(utf16(haystack), self._replacements_for(replacements))[0])
+
+    def replace_batch(self, haystacks, replacements=None):
+        """Not in the reference: [replace(h, replacements) for h in haystacks] in ONE device call (see
+        StringSet.replace_batch) -> a list of str."""
+        return _split_batch(*self._auto.replace_batch(_checked(haystacks), self._replacements_for(replacements))[:2])
+
+    def _replacements_for(self, replacements):
         if replacements is None:
-            replacements = self._values
-            if not all(isinstance(v, str) for v in replacements):
+            if not all(isinstance(v, str) for v in self._values):
                 raise TypeError("replace() without replacements needs str values")
-        elif not isinstance(replacements, str):
-            replacements = list(replacements)[:len(self._keywords)]
-        return _to_str(self._auto.replace_host(utf16(haystack), replacements)[0])
+            return self._values
+        return replacements if isinstance(replacements, str) else list(replacements)[:len(self._keywords)]
 
     def find_all(self, haystack):
         """Convenience (not in the reference): the (n,3) int32 array of (start, end, keyword_index) records."""

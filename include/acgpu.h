@@ -65,7 +65,13 @@
  *      reservoir (device)                       the counting calls' (up to cursor_reservoir_bytes): the Map records of a piece
  *      plan (device)                            8 bytes per record of the piece (+ 8 per 2048 records)
  *      replacement table (device)               8 bytes per replacement + 2 per replacement unit, uploaded per call
- *      slabs (device, acgpu_replace_u16 only)   2 x replace_slab_units x 2 bytes (2 x 64 MiB), or the result's size if smaller
+ *      slabs (device, the host entries)         2 x replace_slab_units x 2 bytes (2 x 64 MiB), or the result's size if smaller
+ *    acgpu_replace_batch_u16 in addition, kept by the pool (N = the haystacks' units + one per haystack, H = the haystacks):
+ *      concatenation (pinned, shared with       2.5 N + 5 H bytes
+ *        acgpu_match_batch_u16)
+ *      offsets (device)                         4 H in, 8 H out
+ *      merged list (device)                     12 bytes per record and per separator of ONE piece, grow-only
+ *      replacement table                        in its full form: 8 bytes per keyword given to acgpu_build (+ 8), whatever n_repl is
  */
 #ifndef ACGPU_H
 #define ACGPU_H
@@ -540,7 +546,7 @@ int acgpu_count_device(const acgpu_automaton *a, acgpu_shard *shard, uint64_t *d
  *              acgpu_match_u16 does and leaves `out` untouched.  Works on the NULL stream (STREAM RULE above), under the pool's lock.
  *  acgpu_replace_device : the shard must be a WHOLE text (own_begin == 0, own_end == n_units, text_begin == text_end == 1), else
  *              ACGPU_E_UNSUPPORTED: rewriting one shard of a sharded text needs the position up to which the rank before it has
- *              emitted handed on between the ranks, which is not built (nor is a multi-device, streaming or batch form).  d_out:
+ *              emitted handed on between the ranks, which is not built (nor is a multi-device or streaming form).  d_out:
  *              device memory, 16-byte aligned, written directly (clipped at cap).  Everything is enqueued on `stream`; the call
  *              waits for it per piece -- for the piece's record count, as acgpu_count_device does, and for its output length -- and
  *              once at the end.
@@ -561,6 +567,33 @@ int acgpu_replace_u16(const acgpu_automaton *a, const uint16_t *haystack, uint64
                       acgpu_replace_stats *st);
 int acgpu_replace_device(const acgpu_automaton *a, acgpu_shard *shard, const uint16_t *repl_units, const uint64_t *repl_off,
                          uint32_t n_repl, uint16_t *d_out, uint64_t cap, uint64_t *n_out, void *stream, acgpu_replace_stats *st);
+
+/*
+ * Many short texts rewritten in ONE call (a replace call has the fixed cost of a match call, a table upload and its waits on
+ * top): haystack i is units[offsets[i] .. offsets[i+1]) as for acgpu_match_batch_u16, empty ones allowed, and the result is
+ * out[out_offsets[i] .. out_offsets[i+1]), unit for unit what acgpu_replace_u16 returns for haystack i alone.  The results lie
+ * back to back, no separator between them; out_offsets has n_haystacks + 1 entries, out_offsets[0] == 0 and
+ * *n_out == out_offsets[n_haystacks].  repl_units / repl_off / n_repl, cap and *n_out: as for acgpu_replace_u16.
+ *  st        : n_records is the sum over the haystacks, units_out == *n_out; pieces and rescans are those of the one text the
+ *              haystacks are scanned as (of the calls per haystack, summed, where the library makes those).
+ *  errors    : ACGPU_E_UNSUPPORTED for ACGPU_MODE_ALL, before any device is touched.  ACGPU_E_INVALID: NULL offsets, n_out or
+ *              out_offsets; descending offsets; a bad replacement table; offsets[n_haystacks] - offsets[0] + n_haystacks >= 2^31;
+ *              tickets in flight on the pool (the call works on the NULL stream, under the pool's lock, as the batch match call).
+ *              n_haystacks == 0: ACGPU_OK, *n_out = 0, out_offsets[0] = 0, no device needed.
+ *  overflow  : a result of more than cap units gives ACGPU_E_OVERFLOW; *n_out and EVERY entry of out_offsets are exact all the
+ *              same (the plan runs to the end), and nothing at or beyond out[cap] has been written.
+ * How it works: the haystacks are concatenated with a separator unit behind each, as acgpu_match_batch_u16 does, and that text
+ * goes through the pieces of acgpu_replace_u16 -- with a separator treated as a match that is deleted: behind every piece its
+ * records are merged with the pseudo-records of its separators (k_replace_merge), plan and emit run over the merged list
+ * unchanged, and the plan's position of a separator is where the next haystack's result begins (k_replace_batch_offsets).  One
+ * scan, one plan and one emit, no second pass over the output; the waits per piece are those of acgpu_replace_u16.
+ * One acgpu_replace_u16 call per haystack inside the library instead, same results, where acgpu_match_batch_u16 falls back: a
+ * dictionary that uses all 65536 units, and the word matchers over a table that is not fold-consistent.
+ * No device-resident, multi-device or streaming form of this call exists.
+ */
+int acgpu_replace_batch_u16(const acgpu_automaton *a, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks,
+                            const uint16_t *repl_units, const uint64_t *repl_off, uint32_t n_repl, uint16_t *out, uint64_t cap,
+                            uint64_t *out_offsets /* n_haystacks + 1 */, uint64_t *n_out, acgpu_replace_stats *st);
 
 /*
  * Synthetic haystack generator of the benchmark: unit i of the stream is

@@ -3,7 +3,9 @@
   replace : acgpu_replace_device on the same text (scan + plan + emit);
   probe   : acgpu_stream_probe pattern 1 over 2 N + 2 N_out bytes (a pure read of what the emit moves).
 Workloads: config 4's dictionary (LongestMatch) over its text; the README word list with WholeWordMatch in synth.readme_text.
-usage: replace_rate.py [--log2 28] [--only c4|readme]"""
+--batch N instead: N haystacks of the README paragraph's size (400-600 units of synth.readme_text) rewritten by ONE
+acgpu_replace_batch_u16 call and by a loop of acgpu_replace_u16 calls (at most --loop of them) on the same build, per haystack.
+usage: replace_rate.py [--log2 28] [--only c4|readme] | --batch N [--loop 2000]"""
 import argparse, ctypes, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -14,7 +16,41 @@ from ahocorasick_amd.unicode_tables import default_word_chars
 ap = argparse.ArgumentParser()
 ap.add_argument("--log2", type=int, default=28)
 ap.add_argument("--only", default=None)
+ap.add_argument("--batch", type=int, default=0)
+ap.add_argument("--loop", type=int, default=2000)
 args = ap.parse_args()
+
+
+def batch_mode(n_hay, n_loop):
+    words = synth.readme_dictionary()
+    a = Automaton(N.MODE_WHOLEWORD, words, True, word_chars=default_word_chars())
+    rng = np.random.default_rng(5)
+    text = synth.readme_text(2006, n_hay * 600, words)
+    cuts = np.concatenate([[0], np.cumsum(rng.integers(400, 600, n_hay))])
+    hays = [text[cuts[i]:cuts[i + 1]] for i in range(n_hay)]
+    units, off, st = a.replace_batch(hays, "***")  # (warm: the pool's buffers, the size)
+    times = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        units, off, st = a.replace_batch(hays, "***", cap=int(units.size) + 16)
+        times.append(time.perf_counter() - t0)
+    dt = float(np.median(times))
+    print("batch : %d haystacks of ~500 units, %d keywords, %d records, %d pieces: %.3f ms per call = %.3f us per haystack" % (
+        n_hay, len(words), st["n_records"], st["pieces"], dt * 1e3, dt * 1e6 / n_hay))
+    some = hays[:min(n_hay, n_loop)]
+    for h in some[:20]:
+        a.replace_host(h, "***")
+    t0 = time.perf_counter()
+    got = [a.replace_host(h, "***")[0] for h in some]
+    dt = time.perf_counter() - t0
+    print("loop  : acgpu_replace_u16 per haystack, %d calls: %.1f us per haystack" % (len(some), dt / len(some) * 1e6), flush=True)
+    o = off.tolist()
+    assert all((units[o[i]:o[i + 1]] == g).all() for i, g in enumerate(got)), "batch and loop differ"
+
+
+if args.batch:
+    batch_mode(args.batch, args.loop)
+    sys.exit(0)
 n = 1 << args.log2
 stream = torch.cuda.current_stream().cuda_stream
 
