@@ -1,6 +1,7 @@
 """Shared helpers for the parity tests (test code only)."""
 import numpy as np
 
+from ahocorasick_amd.strings import utf16
 from ahocorasick_amd.unicode_tables import default_word_chars, java_lower_table
 
 
@@ -26,6 +27,23 @@ def rand_case(rng, alphabet, n_kw, max_len, hay_len, min_len=1):
         kws.append(alphabet[rng.integers(0, len(alphabet), ln)])
     hay = alphabet[rng.integers(0, len(alphabet), hay_len)]
     return hay, kws
+
+
+def splice(hay, recs, repls):
+    """The text a replace call has to produce: hay[e_{-1}:s_0] + repl[id_0] + hay[e_0:s_1] + ... + hay[e_{k-1}:n] over the (n, 3)
+    records (start, end, keyword index); repls: one entry per keyword, or one str for all of them.  The records must not overlap and must come in position order"""
+    hay = utf16(hay)
+    if isinstance(repls, str):
+        repls = [repls] * (int(recs[:, 2].max()) + 1 if len(recs) else 1)
+    repls = [utf16(r) for r in repls]
+    if len(recs):
+        assert (recs[:, 0] < recs[:, 1]).all() and (recs[1:, 0] >= recs[:-1, 1]).all() and recs[0, 0] >= 0 and recs[-1, 1] <= hay.size
+    parts, last = [], 0
+    for s, e, k in recs.tolist():
+        parts += [hay[last:s], repls[k]]
+        last = e
+    parts.append(hay[last:])
+    return np.concatenate(parts).astype(np.uint16)
 
 
 LOWER = java_lower_table()

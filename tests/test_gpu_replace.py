@@ -10,7 +10,7 @@ from ahocorasick_amd import _native as N
 from ahocorasick_amd.strings import Automaton, WholeWordMatchMap, WholeWordMatchSet, utf16
 from ahocorasick_amd.unicode_tables import word_chars_from_list
 from oracle.oracle import FAM_LONGEST, FAM_SHORTEST, FAM_WHOLEWORD, FAM_WWLONGEST, Oracle
-from tests.helpers import LOWER, WORD, fixture_inputs, rand_case
+from tests.helpers import LOWER, WORD, fixture_inputs, rand_case, splice
 
 pytestmark = pytest.mark.gpu
 
@@ -25,22 +25,6 @@ def _reset_tunables():
     yield
     for k, v in DEFAULTS:
         N.set_tunable(k, v)
-
-
-def splice(hay, recs, repls):
-    """the formula above; the records must not overlap and must come in position order"""
-    hay = utf16(hay)
-    if isinstance(repls, str):
-        repls = [repls] * (int(recs[:, 2].max()) + 1 if len(recs) else 1)
-    repls = [utf16(r) for r in repls]
-    if len(recs):
-        assert (recs[:, 0] < recs[:, 1]).all() and (recs[1:, 0] >= recs[:-1, 1]).all() and recs[0, 0] >= 0 and recs[-1, 1] <= hay.size
-    parts, last = [], 0
-    for s, e, k in recs.tolist():
-        parts += [hay[last:s], repls[k]]
-        last = e
-    parts.append(hay[last:])
-    return np.concatenate(parts).astype(np.uint16)
 
 
 def on_device(hay):
