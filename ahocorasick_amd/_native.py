@@ -68,6 +68,25 @@ class ReplaceStats(ctypes.Structure):  # acgpu_replace_stats
     _fields_ = [("n_records", ctypes.c_uint64), ("units_out", ctypes.c_uint64), ("pieces", ctypes.c_uint32), ("rescans", ctypes.c_uint32)]
 
 
+class BatchSummary(ctypes.Structure):  # acgpu_batch_summary
+    _fields_ = [("n_matches", ctypes.c_uint64), ("start", ctypes.c_int32), ("end", ctypes.c_int32), ("keyword_id", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class SummaryStats(ctypes.Structure):  # acgpu_summary_stats
+    _fields_ = [("n_records", ctypes.c_uint64), ("n_matched", ctypes.c_uint64), ("pieces", ctypes.c_uint32), ("rescans", ctypes.c_uint32)]
+
+
+def _summary_dtype():
+    import numpy as np
+    return np.dtype({"names": ["n_matches", "start", "end", "keyword_id", "reserved"],
+                     "formats": [np.uint64, np.int32, np.int32, np.int32, np.int32],
+                     "offsets": [0, 8, 12, 16, 20], "itemsize": 24})
+
+
+SUMMARY_DTYPE = _summary_dtype()  # one acgpu_batch_summary as a numpy record
+
+
 # every symbol include/acgpu.h declares
 SYMBOLS = ["acgpu_build", "acgpu_free", "acgpu_get_info", "acgpu_match_u16", "acgpu_match_batch_u16", "acgpu_match_device",
            "acgpu_match_device_begin", "acgpu_match_device_end", "acgpu_match_device_abandon", "acgpu_synth_fill", "acgpu_synth_tokens", "acgpu_stream_probe",
@@ -77,7 +96,7 @@ SYMBOLS = ["acgpu_build", "acgpu_free", "acgpu_get_info", "acgpu_match_u16", "ac
            "acgpu_match_device_allgather", "acgpu_last_rccl_error", "acgpu_gather_slot_bytes",
            "acgpu_stream_set_pipelined", "acgpu_stream_reserve", "acgpu_cursor_open", "acgpu_cursor_next",
            "acgpu_cursor_get_stats", "acgpu_cursor_close", "acgpu_count_u16", "acgpu_count_device",
-           "acgpu_replace_u16", "acgpu_replace_device", "acgpu_replace_batch_u16"]
+           "acgpu_replace_u16", "acgpu_replace_device", "acgpu_replace_batch_u16", "acgpu_summary_batch_u16"]
 
 _lib = None
 
@@ -162,6 +181,8 @@ def lib():
                                            ctypes.POINTER(ReplaceStats)]
         L.acgpu_replace_batch_u16.restype = ci
         L.acgpu_replace_batch_u16.argtypes = [vp, vp, vp, u32, vp, vp, u32, vp, u64, vp, ctypes.POINTER(u64), ctypes.POINTER(ReplaceStats)]
+        L.acgpu_summary_batch_u16.restype = ci
+        L.acgpu_summary_batch_u16.argtypes = [vp, vp, vp, u32, vp, ctypes.POINTER(SummaryStats)]
         L.acgpu_debug_wordhash_perfect.restype = ci
         L.acgpu_debug_wordhash_perfect.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.acgpu_debug_wordhash.restype = ci

@@ -195,6 +195,7 @@ struct DeviceState {
     void *replace_pin = nullptr;                         // ... pinned, 64 bytes: a piece's output length and last end
     hipEvent_t replace_ev[4] = {nullptr, nullptr, nullptr, nullptr}; // ... slab b emitted (b), slab b copied out (2 + b)
     DevBuf replace_merged, replace_off;                  // acgpu_replace_batch_u16: a piece's records merged with its separators, the result's offsets
+    DevBuf summary;                                      // acgpu_summary_batch_u16: 24 bytes per haystack, {records, the first of them}
     CountCall *count = nullptr;                          // the counting call that runs on this pool (it holds mu), or nullptr
     double all_density = -1.0;                           // ALL: records per unit of this pool's last call (-1: none yet): k_ac_states or the tile kernel
     int fol_level = 0;                                   // k_longest_follow: 0 = run-up of 128 positions, 1 = of a whole segment (a call's chains had not merged), 2 = not for this pool's texts
@@ -229,6 +230,7 @@ struct DeviceState {
         batch_off.release(); batch_out.release();
         visits.release(); count_res.release(); count_out.release();
         replace_tab.release(); replace_plan.release(); replace_slab.release(); replace_merged.release(); replace_off.release();
+        summary.release();
         if (replace_pin) (void)hipHostFree(replace_pin);
         for (auto &e : replace_ev) if (e) (void)hipEventDestroy(e);
         if (copy_stream) (void)hipStreamDestroy(copy_stream);

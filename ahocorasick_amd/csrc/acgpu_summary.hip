@@ -1,0 +1,210 @@
+// acgpu_summary.hip -- acgpu_summary_batch_u16 (include/acgpu.h): for every haystack of a batch how many records it has and the
+// first of them, reduced on the device.
+//
+// A summary call is the fourth consumer of the piece driver (scan_next_piece, acgpu_pieces.hip): the haystacks are concatenated
+// with a separator unit behind each (batch_concat, as acgpu_replace_batch_u16 does), that text goes through the pieces, the Map
+// records of a piece stay in the pool's reservoir, and behind every piece that completed ONE kernel, k_batch_summary, reduces them
+// into the pool's summaries -- 24 bytes per haystack, the only thing that leaves the device, once, at the end of the call.
+//
+// Why a run-wise reduction is enough: no match, word or walk crosses a separator, and a family's records come in listener order,
+// which within a text is a position order (ALL and SHORTEST: by last unit, the others: by first unit) -- so the records of one
+// haystack are CONTIGUOUS, within a piece and from piece to piece, and a piece's record list is a sequence of runs, one per
+// haystack that has records in it, haystacks ascending.  A piece therefore holds at most one run per haystack; a run that a piece
+// boundary cuts continues as the first run of the next piece.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <mutex>
+#include <vector>
+
+#include "acgpu_device.h"
+#include "acgpu_host.h"
+#include "acgpu_internal.h"
+
+using namespace acgpu;
+
+namespace {
+
+constexpr int kSummaryBlock = 256;
+
+static_assert(sizeof(acgpu_batch_summary) == 24, "the layout include/acgpu.h promises");
+
+// every entry {0, -1, -1, -1, 0}
+__global__ __launch_bounds__(kSummaryBlock) void k_summary_fill(acgpu_batch_summary *__restrict__ out, uint32_t n) {
+    const uint32_t i = blockIdx.x * kSummaryBlock + threadIdx.x;
+    if (i >= n) return;
+    acgpu_batch_summary s;
+    s.n_matches = 0;
+    s.start = s.end = s.keyword_id = -1;
+    s.reserved = 0;
+    out[i] = s;
+}
+
+// the last haystack that begins at or before text position pos (k_batch_tag's search)
+__device__ __forceinline__ uint32_t haystack_of(const uint32_t *__restrict__ cat_off, uint32_t n_hay, uint32_t pos) {
+    uint32_t lo = 0, hi = n_hay;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (cat_off[mid] <= pos) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// A piece's cnt Map records (buffer relative; `base` = the text position of the buffer's unit 0) into the summaries: a lane per
+// record.  The lane's haystack h comes from its record's start; its neighbours' come from the lanes beside it, and only a wave's
+// first and last lane search for a record of another wave (i - 1, i + 1).
+//  * count: the HEAD of a run (i == 0 or h(i - 1) != h(i)) adds -i to n_matches[h], its TAIL (i == cnt - 1 or h(i + 1) != h(i))
+//    adds i + 1 (modulo 2^64; a run of one record adds 1 at once).  A run cut by a piece boundary has its tail in one piece and
+//    its head in the next, and the sums still add up to the run's length.
+//  * first: a head writes its record where the entry's start is still -1.  Only the head at i == 0 can find an entry that an
+//    earlier piece wrote -- an earlier kernel on the same stream; within the kernel one lane at most touches the first-record
+//    words of an entry (one run per haystack), so plain stores do.
+__global__ __launch_bounds__(kSummaryBlock) void k_batch_summary(const int32_t *__restrict__ recs, uint64_t cnt, const uint32_t *__restrict__ cat_off,
+                                                                 uint32_t n_hay, int64_t base, acgpu_batch_summary *__restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * kSummaryBlock + threadIdx.x;
+    const bool live = i < cnt;
+    int32_t s = 0, e = 0, id = 0;
+    uint32_t h = 0xffffffffu;
+    if (live) {
+        s = recs[3 * i];
+        e = recs[3 * i + 1];
+        id = recs[3 * i + 2];
+        h = haystack_of(cat_off, n_hay, (uint32_t)((int64_t)s + base));
+    }
+    const uint32_t lane = lane_id();
+    uint32_t hp = __shfl_up(h, 1), hn = __shfl_down(h, 1); // (every lane of the wave takes part; a live lane's neighbour inside [0, cnt) is live)
+    if (!live) return;
+    bool head = i == 0, tail = i == cnt - 1;
+    if (!head) {
+        if (lane == 0) hp = haystack_of(cat_off, n_hay, (uint32_t)((int64_t)recs[3 * (i - 1)] + base));
+        head = hp != h;
+    }
+    if (!tail) {
+        if (lane == kWave - 1) hn = haystack_of(cat_off, n_hay, (uint32_t)((int64_t)recs[3 * (i + 1)] + base));
+        tail = hn != h;
+    }
+    if (!head && !tail) return;
+    acgpu_batch_summary *o = out + h;
+    unsigned long long *n_matches = reinterpret_cast<unsigned long long *>(&o->n_matches);
+    if (head && tail) atomicAdd(n_matches, 1ull);
+    else if (head) atomicAdd(n_matches, 0ull - (unsigned long long)i);
+    else atomicAdd(n_matches, (unsigned long long)i + 1);
+    if (head && o->start == -1) {
+        const int64_t rel = base - (int64_t)cat_off[h];
+        o->start = (int32_t)((int64_t)s + rel);
+        o->end = (int32_t)((int64_t)e + rel);
+        o->keyword_id = id;
+    }
+}
+
+// Where the records of one driven text go: the entries of the haystacks that begin at cat_off[0 .. n_hay) of a text whose unit 0
+// stands at `origin` in cat_off's coordinates.  The batch as one text: all the offsets, origin 0.  One haystack alone (the calls
+// per haystack): its own offset, n_hay = 1 and origin = that offset, so that every record is its haystack's and positions stay
+// what they are.
+struct SummaryTarget {
+    const uint32_t *cat_off;
+    uint32_t n_hay;
+    uint64_t origin;
+    acgpu_batch_summary *out;
+};
+
+// One text through the pieces; behind every piece that scan_next_piece completed (a piece scanned again for want of room comes
+// back once) the summary kernel on its records.  The host waits for nothing here: the next scan follows on the same stream.
+int summary_pieces(acgpu_automaton *a, DeviceState &d, const PieceScan &scan, bool whole, const SummaryTarget &tg, acgpu_summary_stats *st) {
+    PieceDriver p;
+    p.pos = 0;
+    p.end = scan.n;
+    p.chain = 0;
+    p.whole = whole;
+    p.record_kind = ACGPU_REC_MAP;
+    p.ramp.start();
+    p.res = &d.count_res; // the pool's reservoir of Map records (one call at a time holds the pool)
+    int rc = ACGPU_OK;
+    while (rc == ACGPU_OK && p.pos < p.end) {
+        uint64_t cnt = 0, base = 0;
+        if ((rc = scan_next_piece(p, scan, &cnt, &base))) break;
+        if (!cnt) continue;
+        hipLaunchKernelGGL(k_batch_summary, dim3((unsigned)((cnt + kSummaryBlock - 1) / kSummaryBlock)), dim3(kSummaryBlock), 0, scan.stream,
+                           reinterpret_cast<const int32_t *>(d.count_res.p), cnt, tg.cat_off, tg.n_hay, (int64_t)(base + tg.origin), tg.out);
+        HIP_TRY(hipGetLastError());
+        st->n_records += cnt;
+    }
+    st->pieces += (uint32_t)p.pieces;
+    st->rescans += (uint32_t)p.rescans;
+    return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int acgpu_summary_batch_u16(const acgpu_automaton *ca, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks,
+                            acgpu_batch_summary *out, acgpu_summary_stats *st) {
+    if (!ca || !offsets || (n_haystacks && !out)) return ACGPU_E_INVALID;
+    for (uint32_t i = 0; i < n_haystacks; i++)
+        if (offsets[i] > offsets[i + 1]) return ACGPU_E_INVALID;
+    const uint64_t total = offsets[n_haystacks] - offsets[0];
+    if (total && !units) return ACGPU_E_INVALID;
+    const uint64_t cat = total + n_haystacks; // one separator behind every haystack
+    if (cat >= (1ull << 31)) return ACGPU_E_INVALID;
+    if (n_haystacks == 0) {
+        if (st) *st = acgpu_summary_stats{};
+        return ACGPU_OK;
+    }
+    acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
+    const HostTables &t = a->t;
+    DeviceState *dp = nullptr;
+    int rc = device_for_call(a, &dp); // (no device: fails here, as acgpu_match_batch_u16 does, and out is untouched)
+    if (rc) return rc;
+    DeviceState &d = *dp;
+    std::lock_guard<std::mutex> lock(d.mu);
+    if (d.inflight > 0) return ACGPU_E_INVALID; // (the NULL stream: see the stream rule)
+    const hipStream_t stream = d.call_stream;
+    const size_t off_bytes = ((size_t)n_haystacks + 1) * 4, sum_bytes = (size_t)n_haystacks * sizeof(acgpu_batch_summary);
+    if ((rc = d.batch_off.ensure(off_bytes + 16))) return rc;
+    if ((rc = d.summary.ensure(sum_bytes))) return rc;
+    acgpu_batch_summary *d_sum = reinterpret_cast<acgpu_batch_summary *>(d.summary.p);
+    const uint32_t *d_off = reinterpret_cast<const uint32_t *>(d.batch_off.p);
+    hipLaunchKernelGGL(k_summary_fill, dim3((n_haystacks + kSummaryBlock - 1) / kSummaryBlock), dim3(kSummaryBlock), 0, stream, d_sum, n_haystacks);
+    HIP_TRY(hipGetLastError());
+    acgpu_summary_stats sum{};
+    const bool whole = one_piece(shard_rule(t, ACGPU_REC_MAP, false), t);
+    // where acgpu_match_batch_u16 scans haystack by haystack (no unit is free to separate them, or a word matcher over a table that
+    // is not fold-consistent: see there), every haystack goes through the pieces as a text of its own, into its own entry
+    if (t.sep_unit < 0 || ((t.mode == ACGPU_MODE_WHOLEWORD || t.mode == ACGPU_MODE_WWLONGEST) && !t.fold_consistent)) {
+        std::vector<uint32_t> h_off;
+        try {
+            h_off.resize((size_t)n_haystacks + 1);
+        } catch (...) {
+            return ACGPU_E_NOMEM;
+        }
+        for (uint32_t i = 0; i <= n_haystacks; i++) h_off[i] = (uint32_t)(offsets[i] - offsets[0] + i); // (the concatenation's offsets)
+        HIP_TRY(hipMemcpy(d.batch_off.p, h_off.data(), off_bytes, hipMemcpyHostToDevice));
+        for (uint32_t i = 0; i < n_haystacks && rc == ACGPU_OK; i++) {
+            const uint64_t len = offsets[i + 1] - offsets[i];
+            if (!len) continue;
+            rc = summary_pieces(a, d, PieceScan{a, d, units + offsets[i], len, nullptr, stream}, whole,
+                                SummaryTarget{d_off + i, 1, h_off[i], d_sum + i}, &sum);
+        }
+    } else {
+        uint16_t *h_cat = nullptr;
+        uint32_t *h_off = nullptr;
+        if ((rc = batch_concat(d, units, offsets, n_haystacks, (uint16_t)t.sep_unit, &h_cat, &h_off))) return rc;
+        HIP_TRY(hipMemcpyAsync(d.batch_off.p, h_off, off_bytes, hipMemcpyHostToDevice, stream));
+        d.start_behind = t.sep_unit; // (WholeWordLongest: every haystack's first unit is a walk start, also where a piece's left halo is the separator)
+        rc = summary_pieces(a, d, PieceScan{a, d, h_cat, cat, nullptr, stream}, whole, SummaryTarget{d_off, n_haystacks, 0, d_sum}, &sum);
+        d.start_behind = -1;
+    }
+    if (rc) {
+        (void)hipStreamSynchronize(stream); // (nothing of the call stays in flight)
+        return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(out, d_sum, sum_bytes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (uint32_t i = 0; i < n_haystacks; i++) sum.n_matched += out[i].n_matches != 0;
+    if (st) *st = sum;
+    return ACGPU_OK;
+}
+
+} // extern "C"

@@ -253,6 +253,18 @@ class Automaton:
             N.check(rc, "acgpu_replace_batch_u16")
             return out[:n_out.value], out_off, {f: int(getattr(st, f)) for f, _ in N.ReplaceStats._fields_}
 
+    def summary_batch(self, haystacks):
+        """acgpu_summary_batch_u16: many short haystacks (str or uint16 arrays) decided in one call -> (array of N.SUMMARY_DTYPE
+        with one entry per haystack: n_matches and the first record in listener order, -1s where there is none; stats dict).
+        No record leaves the device and there is no capacity to guess."""
+        units, off = _pack(haystacks)
+        n = len(off) - 1
+        out = np.zeros(n, dtype=N.SUMMARY_DTYPE)
+        st = N.SummaryStats()
+        N.check(N.lib().acgpu_summary_batch_u16(self._h, _vp(units), _vp(off), n, _vp(out) if n else None, ctypes.byref(st)),
+                "acgpu_summary_batch_u16")
+        return out, {f: int(getattr(st, f)) for f, _ in N.SummaryStats._fields_}
+
     def replace_device(self, d_hay_ptr, n_units, replacements, d_out_ptr, cap, stream=0):
         """acgpu_replace_device on raw device pointers: the whole text d_hay_ptr[0 .. n_units) rewritten into d_out_ptr (cap
         units, 16-byte aligned).  Returns (n_out, rc, stats dict); rc == E_OVERFLOW: n_out is the capacity to call again with."""
@@ -549,7 +561,36 @@ def _split_batch(units, out_off):
     return [_to_str(units[o[i]:o[i + 1]]) for i in range(len(o) - 1)]
 
 
-class StringSet:
+class _BatchDecisions:
+    """Not in the reference: what a listener that decides about each text of a list would hold, from ONE device call that returns
+    24 bytes per haystack and no record (Automaton.summary_batch).  An empty list gives empty results without a device."""
+
+    def _summary(self, haystacks):
+        haystacks = _checked(haystacks)
+        if not haystacks:
+            return np.zeros(0, dtype=N.SUMMARY_DTYPE)
+        return self._auto.summary_batch(haystacks)[0]
+
+    def contains_batch(self, haystacks):
+        """[does match(h, listener) call the listener at all for h in haystacks] as a bool array"""
+        return self._summary(haystacks)["n_matches"] > 0
+
+    def count_matches_batch(self, haystacks):
+        """[how often match(h, listener) calls a listener that always returns True for h in haystacks] as a uint64 array"""
+        return self._summary(haystacks)["n_matches"].copy()
+
+    def first_batch(self, haystacks):
+        """[the arguments of the first listener call of match(h, listener), without the haystack, or None for h in haystacks]:
+        (start, end) for a set, (start, end, value) for a map"""
+        s = self._summary(haystacks)
+        vals = getattr(self, "_values", None)
+        rows = zip(s["n_matches"].tolist(), s["start"].tolist(), s["end"].tolist(), s["keyword_id"].tolist())
+        if vals is None:
+            return [(b, e) if n else None for n, b, e, _ in rows]
+        return [(b, e, vals[k]) if n else None for n, b, e, k in rows]
+
+
+class StringSet(_BatchDecisions):
     """S/StringSet.java:3-5"""
     _MODE = None
 
@@ -608,7 +649,7 @@ class StringSet:
         return self._auto
 
 
-class StringMap:
+class StringMap(_BatchDecisions):
     """S/StringMap.java:5-9 (String overload only)"""
     _MODE = None
 

@@ -72,6 +72,12 @@
  *      offsets (device)                         4 H in, 8 H out
  *      merged list (device)                     12 bytes per record and per separator of ONE piece, grow-only
  *      replacement table                        in its full form: 8 bytes per keyword given to acgpu_build (+ 8), whatever n_repl is
+ *    acgpu_summary_batch_u16 needs the pool's scratch for ONE piece and the counting calls' reservoir as well, plus, kept by the
+ *    pool (N and H as above):
+ *      concatenation (pinned, shared with       2.5 N + 5 H bytes
+ *        acgpu_match_batch_u16)
+ *      offsets (device)                         4 H
+ *      summaries (device)                       24 H, grow-only
  */
 #ifndef ACGPU_H
 #define ACGPU_H
@@ -594,6 +600,53 @@ int acgpu_replace_device(const acgpu_automaton *a, acgpu_shard *shard, const uin
 int acgpu_replace_batch_u16(const acgpu_automaton *a, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks,
                             const uint16_t *repl_units, const uint64_t *repl_off, uint32_t n_repl, uint16_t *out, uint64_t cap,
                             uint64_t *out_offsets /* n_haystacks + 1 */, uint64_t *n_out, acgpu_replace_stats *st);
+
+/*
+ * Many short texts DECIDED in one call: for every haystack how many records it has and the first of them -- what a listener that
+ * returns false from its first call, or one that only counts, would hold -- reduced on the device; no record reaches the host.
+ * Haystack i is units[offsets[i] .. offsets[i+1]) as for acgpu_match_batch_u16, empty ones allowed.  out[i] is {count, first
+ * record} of the records with haystack == i that acgpu_match_batch_u16(..., ACGPU_REC_MAP, ...) returns for the same arguments:
+ * every family, ACGPU_MODE_ALL included (nothing here needs records that do not overlap); positions relative to the haystack,
+ * keyword_id as in a Map record (the LAST duplicate of a keyword, for Shortest the FIRST).  "First" is first in the reference's
+ * listener-call order -- for AhoCorasick end ascending, then start ascending, which is not the lowest start: keywords "abc" and
+ * "b" on "abc" give "b".
+ *  out       : HOST array of n_haystacks entries, overwritten; a size that does not depend on the matches, so there is no capacity
+ *              to guess and never ACGPU_E_OVERFLOW.
+ *  st        : NULL, or n_records = the sum of n_matches, n_matched = the haystacks with n_matches > 0; pieces and rescans are those
+ *              of the one text the haystacks are scanned as (of the texts per haystack, summed, where the library scans those).
+ *  errors    : ACGPU_E_INVALID, before any device is touched: NULL a or offsets; NULL out with n_haystacks > 0; descending offsets;
+ *              units to read and no array; offsets[n_haystacks] - offsets[0] + n_haystacks >= 2^31.  ACGPU_E_INVALID as well with
+ *              tickets in flight on the pool (the call works on the NULL stream, under the pool's lock, as the batch match call).
+ *              n_haystacks == 0: ACGPU_OK, nothing but *st is written, no device needed.  Without a device the call fails as
+ *              acgpu_match_batch_u16 does.  After every failure `out` is untouched.
+ * How it works: the haystacks are concatenated with a separator unit behind each, as acgpu_match_batch_u16 does, and that text
+ * goes through the pieces of a counting call (the same ramp and rescan rules; the Map records of a piece stay in the pool's
+ * reservoir).  Behind every piece that completed, k_batch_summary runs over its records, a lane per record: a haystack's records
+ * are contiguous in every family's order, so the piece's list is a sequence of runs, one per haystack; the head of a run adds
+ * minus its index to the haystack's count and the tail its index plus one -- two 64-bit atomics per run and piece, whatever its
+ * length, and a run that a piece boundary cuts still sums to its length -- and a head writes its record as the first one where
+ * none is written yet.  The summaries (24 bytes per haystack) are copied out once, at the end; per piece the host waits only for
+ * what the scan itself waits for.
+ * Haystack by haystack inside the library instead, same results, where acgpu_match_batch_u16 falls back (a dictionary that uses
+ * all 65536 units, and the word matchers over a table that is not fold-consistent): every haystack goes through the pieces as a
+ * text of its own, into its own entry; no host buffer grows with the matches there either.
+ * Not built: a device-resident, multi-device or streaming form of this call; stopping a haystack's scan at its first match (the
+ * scan still finds every record: what is saved is their way to the host); the Java facade.  ACGPU_ABI_VERSION stays as it is:
+ * adding symbols is compatible.
+ */
+typedef struct acgpu_batch_summary {
+    uint64_t n_matches;              /* records acgpu_match_batch_u16 (ACGPU_REC_MAP) returns for this haystack          */
+    int32_t start, end, keyword_id;  /* the FIRST of them in the reference's listener-call order, positions relative to
+                                        the haystack, id as in a Map record; -1, -1, -1 when n_matches == 0             */
+    int32_t reserved;                /* 0 */
+} acgpu_batch_summary;               /* 24 bytes */
+typedef struct acgpu_summary_stats {
+    uint64_t n_records;       /* sum of n_matches                                  */
+    uint64_t n_matched;       /* haystacks with n_matches > 0                      */
+    uint32_t pieces, rescans; /* as acgpu_replace_stats                            */
+} acgpu_summary_stats;
+int acgpu_summary_batch_u16(const acgpu_automaton *a, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks,
+                            acgpu_batch_summary *out /* n_haystacks, host */, acgpu_summary_stats *st /* may be NULL */);
 
 /*
  * Synthetic haystack generator of the benchmark: unit i of the stream is
