@@ -31,10 +31,10 @@ namespace {
 
 template <typename T>
 int upload(DeviceState &d, const std::vector<T> &v, const T **out) {
-    void *p = nullptr;
+    d.table_allocs.emplace_back();
+    void *&p = d.table_allocs.back().h;
     size_t bytes = std::max<size_t>(v.size() * sizeof(T), 16);
     HIP_TRY(hipMalloc(&p, bytes));
-    d.table_allocs.push_back(p);
     if (!v.empty()) HIP_TRY(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     *out = reinterpret_cast<const T *>(p);
     return ACGPU_OK;
@@ -71,7 +71,10 @@ int ensure_device(acgpu_automaton *a, DeviceState **out, int lane) {
     if (!d) return ACGPU_E_NOMEM;
     d->device = dev;
     d->lane = lane;
-    if (lane > 0) HIP_TRY(hipStreamCreateWithFlags(&d->call_stream, hipStreamNonBlocking));
+    if (lane > 0) {
+        HIP_TRY(hipStreamCreateWithFlags(&d->lane_stream.h, hipStreamNonBlocking));
+        d->call_stream = d->lane_stream;
+    }
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, dev));
     d->n_cu = d->n_cu_phys = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -177,12 +180,12 @@ int ensure_device(acgpu_automaton *a, DeviceState **out, int lane) {
     T.cls_base = t.cls_base; T.cls_span = t.cls_span; T.range_cls = t.range_cls; T.cs = t.cs; T.dense = t.dense;
     T.entry_bytes = (int32_t)t.entry_bytes;
     T.lds_entries = lds_states_for(t) * t.n_cls;
-    HIP_TRY(hipHostMalloc((void **)&d->h_counter, 64, hipHostMallocDefault));
-    for (auto &e : d->ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipHostMalloc((void **)&d->h_counter.h, 64, hipHostMallocDefault));
+    for (auto &e : d->ev) HIP_TRY(hipEventCreate(&e.h));
     for (auto &tk : d->tickets) {
-        for (auto &e : tk.ev) HIP_TRY(hipEventCreate(&e));
-        HIP_TRY(hipEventCreateWithFlags(&tk.done, hipEventDisableTiming));
-        HIP_TRY(hipHostMalloc((void **)&tk.h_count, 64, hipHostMallocDefault));
+        for (auto &e : tk.ev) HIP_TRY(hipEventCreate(&e.h));
+        HIP_TRY(hipEventCreateWithFlags(&tk.done.h, hipEventDisableTiming));
+        HIP_TRY(hipHostMalloc((void **)&tk.h_count.h, 64, hipHostMallocDefault));
         tk.owner = d.get();
     }
     *out = d.get();
@@ -267,7 +270,7 @@ DevTables folded_tables(const DeviceState &d) {
 
 // Starts a call in `r`: the call's arguments, the record's events and pinned slot (done: a ticket's completion marker, null for a
 // synchronous call).  Until a form fills it in, the record is complete with nothing found.
-void open_call(CallRecord &r, hipEvent_t *ev, hipEvent_t done, unsigned long long *slot, const acgpu_shard &sh, acgpu_shard *user,
+void open_call(CallRecord &r, const PoolEvent *ev, hipEvent_t done, unsigned long long *slot, const acgpu_shard &sh, acgpu_shard *user,
                int record_kind, void *d_out, uint64_t cap, hipStream_t stream, bool profiled, bool folded) {
     r = CallRecord{};
     r.shard = sh; r.user_shard = user; r.record_kind = record_kind; r.d_out = d_out; r.cap = cap; r.stream = stream;
@@ -329,7 +332,7 @@ constexpr double kStatesFormDensity = 0.05; // records per unit of the pool's la
 int enqueue_states(acgpu_automaton *a, DeviceState &d, CallRecord &r, uint32_t hot_rows, bool counting = false) {
     const HostTables &t = a->t;
     const acgpu_shard *sh = &r.shard;
-    hipEvent_t *ev = r.ev;
+    const PoolEvent *ev = r.ev;
     const hipStream_t stream = r.stream;
     int rc;
     AcStatesLaunch S{};
@@ -1663,7 +1666,7 @@ static int start_call(acgpu_automaton *a, DeviceState &d, Ticket *tk, acgpu_shar
     const bool enqueued = rule.all_pipeline || (t.mode == ACGPU_MODE_LONGEST && !(filter_is_selective(t) && tunables().force_kernel != 1));
     CallRecord &r = tk ? tk->rec : d.call;
     // (all_pipeline over tables that are not fold-consistent: the Readable loop of WholeWord, an ordinary scan over w' = word o lower)
-    open_call(r, tk ? tk->ev : d.ev, tk && enqueued ? tk->done : nullptr, tk ? tk->h_count : d.h_counter, *sh, sh, record_kind, d_out, cap,
+    open_call(r, tk ? tk->ev : d.ev, tk && enqueued ? tk->done.h : nullptr, tk ? tk->h_count : d.h_counter, *sh, sh, record_kind, d_out, cap,
               stream, profiled, rule.all_pipeline && !t.fold_consistent);
     r.counting = d.count != nullptr;
     if (rule.all_pipeline) return enqueue_all(a, d, r, 0);
@@ -1959,11 +1962,9 @@ int acgpu_match_device(const acgpu_automaton *ca, acgpu_shard *sh, int record_ki
                        uint64_t *n_out, void *stream_, acgpu_profile *prof) {
     if (!ca || !sh || !n_out) return ACGPU_E_INVALID;
     acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
-    DeviceState *d = nullptr;
-    int rc = device_for_call(a, &d);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lock(d->mu);
-    return match_shard(a, *d, sh, record_kind, d_out, cap, n_out, reinterpret_cast<hipStream_t>(stream_), prof);
+    PoolCall call(a);
+    if (call.rc) return call.rc;
+    return match_shard(a, *call.d, sh, record_kind, d_out, cap, n_out, reinterpret_cast<hipStream_t>(stream_), prof);
 }
 
 int acgpu_match_device_begin(const acgpu_automaton *ca, acgpu_shard *sh, int record_kind, void *d_out, uint64_t cap,
@@ -1971,11 +1972,9 @@ int acgpu_match_device_begin(const acgpu_automaton *ca, acgpu_shard *sh, int rec
     if (!ca || !sh || !ticket) return ACGPU_E_INVALID;
     *ticket = nullptr;
     acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
-    DeviceState *d = nullptr;
-    int rc = device_for_call(a, &d);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lock(d->mu);
-    return begin_shard(a, *d, sh, record_kind, d_out, cap, reinterpret_cast<hipStream_t>(stream_), want_profile, ticket);
+    PoolCall call(a);
+    if (call.rc) return call.rc;
+    return begin_shard(a, *call.d, sh, record_kind, d_out, cap, reinterpret_cast<hipStream_t>(stream_), want_profile, ticket);
 }
 
 int acgpu_match_device_abandon(const acgpu_automaton *ca, acgpu_ticket *ticket) {
@@ -2070,6 +2069,7 @@ int64_t piece_exit(const ShardRule &r, int64_t entry, uint64_t own_end, const ac
 constexpr uint64_t kHostChunkUnits = 1ull << 24; // 32 MiB per chunk
 
 bool one_piece(const ShardRule &r, const HostTables &t) { return r.sequential || (uint64_t)t.max_len + 2 >= kHostChunkUnits; }
+bool host_one_piece(const HostTables &t, int record_kind) { return one_piece(shard_rule(t, record_kind, false), t); }
 
 // The CPUs of the NUMA node a device hangs on (/sys/bus/pci/devices/<bdf>/numa_node, /sys/devices/system/node/node<N>/cpulist):
 // the threads that copy a share's text into pinned memory run there, so that on a two-socket host eight devices are fed by both
@@ -2114,34 +2114,6 @@ static bool device_numa_cpus(int dev, cpu_set_t *set) {
     return n_set > 0;
 }
 
-// the concatenation of the batch calls (acgpu_host.h); the offsets stand 64-byte aligned behind the text
-int batch_concat(DeviceState &d, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks, uint16_t sep, uint16_t **h_cat_out,
-                 uint32_t **h_off_out) {
-    const uint64_t cat = offsets[n_haystacks] - offsets[0] + n_haystacks;
-    const size_t off_bytes = ((size_t)n_haystacks + 1) * 4, pin_need = cat * 2 + 64 + off_bytes;
-    if (d.batch_pin_bytes < pin_need) {
-        if (d.batch_pin) (void)hipHostFree(d.batch_pin);
-        d.batch_pin = nullptr;
-        d.batch_pin_bytes = 0;
-        HIP_TRY(hipHostMalloc(&d.batch_pin, pin_need + pin_need / 4, hipHostMallocDefault));
-        d.batch_pin_bytes = pin_need + pin_need / 4;
-    }
-    uint16_t *h_cat = (uint16_t *)d.batch_pin;
-    uint32_t *h_off = (uint32_t *)((char *)d.batch_pin + ((cat * 2 + 63) & ~(size_t)63));
-    uint64_t at = 0;
-    for (uint32_t i = 0; i < n_haystacks; i++) {
-        const uint64_t len = offsets[i + 1] - offsets[i];
-        h_off[i] = (uint32_t)at;
-        if (len) std::memcpy(h_cat + at, units + offsets[i], len * 2);
-        at += len;
-        h_cat[at++] = sep;
-    }
-    h_off[n_haystacks] = (uint32_t)at;
-    *h_cat_out = h_cat;
-    *h_off_out = h_off;
-    return ACGPU_OK;
-}
-
 int stage_whole_text(DeviceState &d, const uint16_t *haystack, uint64_t n_units, acgpu_shard *out) {
     const int rc = d.stage_hay.ensure(n_units * 2 + 16);
     if (rc) return rc;
@@ -2171,27 +2143,24 @@ int scan_host_range(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack
         if ((rc = d.stage_out.ensure(cap * (uint64_t)record_kind + 16))) return rc;
         d_out = d.stage_out.p;
     }
-    if (!d.copy_stream) HIP_TRY(hipStreamCreateWithFlags(&d.copy_stream, hipStreamNonBlocking));
+    if (!d.copy_stream) HIP_TRY(hipStreamCreateWithFlags(&d.copy_stream.h, hipStreamNonBlocking));
     // the ring: as many slots as this buffer has chunks (at most kPinSlots), each as large as its largest chunk -- a share of a
     // few megabytes of a multi-device call, or a 40 MiB haystack, does not pin 8 x 32 MiB
     const size_t slot_bytes = (((size_t)std::min<uint64_t>(nb, C) * 2 + (1u << 20) - 1) >> 20) << 20;
     const int slots_needed = (int)std::min<uint32_t>(n_chunks, (uint32_t)DeviceState::kPinSlots);
     if (d.pin_bytes < slot_bytes) {
-        for (auto &q : d.pin) {
-            if (q) (void)hipHostFree(q);
-            q = nullptr;
-        }
+        for (auto &q : d.pin) q.reset();
         d.pin_n = 0;
         d.pin_bytes = slot_bytes;
     }
     while (d.pin_n < slots_needed) {
-        HIP_TRY(hipHostMalloc(&d.pin[d.pin_n], d.pin_bytes, hipHostMallocDefault));
+        HIP_TRY(hipHostMalloc(&d.pin[d.pin_n].h, d.pin_bytes, hipHostMallocDefault));
         d.pin_n++;
     }
     while (d.chunk_ev.size() < n_chunks) {
-        hipEvent_t e = nullptr;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        d.chunk_ev.push_back(e);
+        PoolEvent e;
+        HIP_TRY(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
+        d.chunk_ev.push_back(std::move(e));
     }
     // producers: chunk k -> pinned slot k % kPinSlots (free once chunk k - kPinSlots has been copied to the device) -> DMA
     const int n_workers = (int)std::min<uint32_t>({(uint32_t)DeviceState::kPinSlots - 2, n_chunks, std::max(2u, std::thread::hardware_concurrency() / 2)});
@@ -2293,41 +2262,21 @@ int scan_host_range(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack
     return total > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
 }
 
-} // namespace acgpu
-
-namespace {
-
-int match_u16_pipelined(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack, uint64_t n_units, int record_kind, void *out,
-                        uint64_t cap, uint64_t *n_out) {
-    int64_t chain = 0;
-    const int rc = scan_host_range(a, d, haystack, n_units, 0, n_units, 0, n_units, record_kind, cap, n_out, &chain);
-    if (rc != ACGPU_OK) return rc;
-    if (*n_out) {
-        HIP_TRY(hipMemcpyAsync(out, d.stage_out.p, *n_out * (uint64_t)record_kind, hipMemcpyDeviceToHost, d.call_stream));
-        HIP_TRY(hipStreamSynchronize(d.call_stream));
-    }
-    return ACGPU_OK;
-}
-
-} // namespace
-
-namespace {
-
 // acgpu_match_u16 on a short haystack: ONE launch of one workgroup (acgpu_small.hip) that reads the haystack from, and writes
 // the records to, host-mapped pinned memory; the host waits on a flag in that memory.  *handled = false: the kernel could not
 // hold the call (too many occurrences) -- the general path takes it.
-int match_small(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack, uint64_t n_units, int record_kind, void *out,
+static int match_small(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack, uint64_t n_units, int record_kind, void *out,
                 uint64_t cap, uint64_t *n_out, bool *handled) {
     *handled = false;
     constexpr size_t kHayBytes = (size_t)kSmallMaxUnits * 2 + 64, kOutBytes = (size_t)kSmallMaxRecs * ACGPU_REC_MAP + 64;
     if (!d.small_pin) {
         // fine-grained (coherent) host memory: the device's writes are visible to the host while the kernel is still running
-        HIP_TRY(hipHostMalloc(&d.small_pin, 64 + kHayBytes + kOutBytes, hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_TRY(hipHostMalloc(&d.small_pin.h, 64 + kHayBytes + kOutBytes, hipHostMallocMapped | hipHostMallocCoherent));
         HIP_TRY(hipHostGetDevicePointer(&d.small_pin_dev, d.small_pin, 0));
-        HIP_TRY(hipStreamCreateWithFlags(&d.small_stream, hipStreamNonBlocking));
+        HIP_TRY(hipStreamCreateWithFlags(&d.small_stream.h, hipStreamNonBlocking));
     }
-    volatile unsigned long long *status = reinterpret_cast<volatile unsigned long long *>(d.small_pin);
-    char *h_hay = (char *)d.small_pin + 64, *h_out = h_hay + kHayBytes;
+    volatile unsigned long long *status = static_cast<volatile unsigned long long *>(d.small_pin.h);
+    char *h_hay = (char *)d.small_pin.h + 64, *h_out = h_hay + kHayBytes;
     char *dev = (char *)d.small_pin_dev;
     std::memcpy(h_hay, haystack, n_units * 2);
     std::memset(h_hay + n_units * 2, 0, 8); // (the kernel reads whole 8-byte groups)
@@ -2364,7 +2313,37 @@ int match_small(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack, ui
     return ACGPU_OK;
 }
 
-} // namespace
+int match_host_text(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack, uint64_t n_units, int record_kind, void *out,
+                    uint64_t cap, uint64_t *n_out) {
+    const HostTables &t = a->t;
+    int rc;
+    // short haystacks: one launch, no copies (tunable tile_debug bit 2^41, or a kernel form forced by "force_kernel": the
+    // general path -- for A/B, and for the tests that run the scan kernels on the short edge-case inputs)
+    if (n_units > 0 && n_units <= kSmallMaxUnits && d.inflight == 0 && small_call_supported(t) && !(tunables().tile_debug & (1ll << 41)) &&
+        tunables().force_kernel == 0) {
+        bool handled = false;
+        rc = match_small(a, d, haystack, n_units, record_kind, out, cap, n_out, &handled);
+        if (rc != ACGPU_OK || handled) return rc;
+    }
+    // long haystacks: the pipelined form, unless the text is one piece (the loops that only exist as a sequential kernel over
+    // the whole text -- WholeWord / WholeWordLongestSet with a fold-inconsistent table -- take the plain one)
+    if (n_units >= 2 * kHostChunkUnits && !host_one_piece(t, record_kind) && d.inflight == 0 && !(tunables().tile_debug & 33554432)) {
+        int64_t chain = 0;
+        if ((rc = scan_host_range(a, d, haystack, n_units, 0, n_units, 0, n_units, record_kind, cap, n_out, &chain)) || !*n_out) return rc;
+        HIP_TRY(hipMemcpyAsync(out, d.stage_out.p, *n_out * (uint64_t)record_kind, hipMemcpyDeviceToHost, d.call_stream));
+        HIP_TRY(hipStreamSynchronize(d.call_stream));
+        return ACGPU_OK;
+    }
+    acgpu_shard sh;
+    if ((rc = d.stage_out.ensure(cap * (uint64_t)record_kind + 16))) return rc;
+    if ((rc = stage_whole_text(d, haystack, n_units, &sh))) return rc;
+    rc = match_shard(a, d, &sh, record_kind, d.stage_out.p, cap, n_out, nullptr, nullptr);
+    if (rc != ACGPU_OK) return rc;
+    if (*n_out) HIP_TRY(hipMemcpy(out, d.stage_out.p, *n_out * (uint64_t)record_kind, hipMemcpyDeviceToHost));
+    return ACGPU_OK;
+}
+
+} // namespace acgpu
 
 extern "C" {
 
@@ -2374,111 +2353,9 @@ int acgpu_match_u16(const acgpu_automaton *ca, const uint16_t *haystack, uint64_
     if (record_kind != ACGPU_REC_SET && record_kind != ACGPU_REC_MAP) return ACGPU_E_INVALID;
     if (n_units >= (1ull << 31)) return ACGPU_E_INVALID;
     acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
-    DeviceState *d = nullptr;
-    int rc = device_for_call(a, &d);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lock(d->mu); // staging buffers are part of the per-device scratch pool
-    const HostTables &t = a->t;
-    // short haystacks: one launch, no copies (tunable tile_debug bit 2^41, or a kernel form forced by "force_kernel": the
-    // general path -- for A/B, and for the tests that run the scan kernels on the short edge-case inputs)
-    if (n_units > 0 && n_units <= kSmallMaxUnits && d->inflight == 0 && small_call_supported(t) && !(tunables().tile_debug & (1ll << 41)) &&
-        tunables().force_kernel == 0) {
-        bool handled = false;
-        rc = match_small(a, *d, haystack, n_units, record_kind, out, cap, n_out, &handled);
-        if (rc != ACGPU_OK || handled) return rc;
-    }
-    // long haystacks: the pipelined form, unless the text is one piece (the loops that only exist as a sequential kernel over
-    // the whole text -- WholeWord / WholeWordLongestSet with a fold-inconsistent table -- take the plain one)
-    if (n_units >= 2 * kHostChunkUnits && !one_piece(shard_rule(t, record_kind, false), t) && d->inflight == 0 &&
-        !(tunables().tile_debug & 33554432))
-        return match_u16_pipelined(a, *d, haystack, n_units, record_kind, out, cap, n_out);
-    acgpu_shard sh;
-    if ((rc = d->stage_out.ensure(cap * (uint64_t)record_kind + 16))) return rc;
-    if ((rc = stage_whole_text(*d, haystack, n_units, &sh))) return rc;
-    rc = match_shard(a, *d, &sh, record_kind, d->stage_out.p, cap, n_out, nullptr, nullptr);
-    if (rc != ACGPU_OK) return rc;
-    if (*n_out) HIP_TRY(hipMemcpy(out, d->stage_out.p, *n_out * (uint64_t)record_kind, hipMemcpyDeviceToHost));
-    return ACGPU_OK;
-}
-
-int acgpu_match_batch_u16(const acgpu_automaton *ca, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks,
-                          int record_kind, void *out, uint64_t cap, uint64_t *n_out) {
-    if (!ca || !n_out || !offsets || (cap && !out)) return ACGPU_E_INVALID;
-    if (record_kind != ACGPU_REC_SET && record_kind != ACGPU_REC_MAP) return ACGPU_E_INVALID;
-    *n_out = 0;
-    if (n_haystacks == 0) return ACGPU_OK;
-    for (uint32_t i = 0; i < n_haystacks; i++)
-        if (offsets[i] > offsets[i + 1]) return ACGPU_E_INVALID;
-    const uint64_t total = offsets[n_haystacks] - offsets[0];
-    if (total && !units) return ACGPU_E_INVALID;
-    const uint64_t cat = total + n_haystacks; // one separator behind every haystack
-    if (cat >= (1ull << 31)) return ACGPU_E_INVALID;
-    acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
-    const HostTables &t = a->t;
-    const size_t out_rec = (size_t)record_kind + 4;
-    // no unit can stand between two haystacks (every one of the 65536 is in use), or a word matcher over a table that is not
-    // fold-consistent: one call per haystack.  (Such a table makes some loops sequential kernels over one whole text; and in
-    // the folding scans a keyword's FOLDED first unit need not be a word character, so a walk that begins at position 0 of a
-    // text -- where the scan starts whatever stands there -- is not a walk that begins behind a separator.)
-    const bool per_haystack = (t.mode == ACGPU_MODE_WHOLEWORD || t.mode == ACGPU_MODE_WWLONGEST) && !t.fold_consistent;
-    if (t.sep_unit < 0 || per_haystack) {
-        std::vector<int32_t> tmp;
-        uint64_t n = 0;
-        for (uint32_t i = 0; i < n_haystacks; i++) {
-            const uint64_t len = offsets[i + 1] - offsets[i];
-            uint64_t got = 0, room = cap > n ? cap - n : 0;
-            try {
-                tmp.resize(std::max<size_t>(room * (record_kind / 4), 4));
-            } catch (...) {
-                return ACGPU_E_NOMEM;
-            }
-            const int rc = acgpu_match_u16(ca, units + offsets[i], len, record_kind, tmp.data(), room, &got);
-            if (rc != ACGPU_OK && rc != ACGPU_E_OVERFLOW) return rc;
-            if (rc == ACGPU_OK) {
-                const int W = record_kind / 4;
-                for (uint64_t r = 0; r < got; r++) {
-                    int32_t *o = (int32_t *)((char *)out + (n + r) * out_rec);
-                    o[0] = (int32_t)i;
-                    for (int w = 0; w < W; w++) o[1 + w] = tmp[r * W + w];
-                }
-            }
-            n += got;
-        }
-        *n_out = n;
-        return n > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
-    }
-    DeviceState *d = nullptr;
-    int rc = device_for_call(a, &d);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lock(d->mu); // staging buffers are part of the per-device scratch pool
-    if (d->inflight > 0) return ACGPU_E_INVALID; // (the NULL stream: see the stream rule)
-    const size_t off_bytes = ((size_t)n_haystacks + 1) * 4;
-    uint16_t *h_cat = nullptr;
-    uint32_t *h_off = nullptr;
-    if ((rc = batch_concat(*d, units, offsets, n_haystacks, (uint16_t)t.sep_unit, &h_cat, &h_off))) return rc;
-    if ((rc = d->stage_hay.ensure(cat * 2 + 16))) return rc;
-    if ((rc = d->stage_out.ensure(cap * (uint64_t)record_kind + 16))) return rc;
-    if ((rc = d->batch_off.ensure(off_bytes + 16))) return rc;
-    if ((rc = d->batch_out.ensure(cap * out_rec + 16))) return rc;
-    HIP_TRY(hipMemcpyAsync(d->stage_hay.p, h_cat, cat * 2, hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(hipMemcpyAsync(d->batch_off.p, h_off, off_bytes, hipMemcpyHostToDevice, nullptr));
-    acgpu_shard sh{};
-    sh.d_hay = (const uint16_t *)d->stage_hay.p;
-    sh.n_units = cat;
-    sh.own_begin = 0;
-    sh.own_end = cat;
-    sh.text_begin = 1;
-    sh.text_end = 1;
-    sh.chain_entry = 0;
-    d->start_behind = t.sep_unit; // (WholeWordLongest: every haystack's first unit is a walk start, as position 0 of a text is)
-    rc = match_shard(a, *d, &sh, record_kind, d->stage_out.p, cap, n_out, nullptr, nullptr);
-    d->start_behind = -1;
-    if (rc != ACGPU_OK) return rc; // ACGPU_E_OVERFLOW: *n_out is the capacity to retry with
-    if (*n_out) {
-        HIP_TRY(launch_batch_tag(d->stage_out.p, *n_out, record_kind, (const uint32_t *)d->batch_off.p, n_haystacks, d->batch_out.p, nullptr));
-        HIP_TRY(hipMemcpy(out, d->batch_out.p, *n_out * out_rec, hipMemcpyDeviceToHost));
-    }
-    return ACGPU_OK;
+    PoolCall call(a); // (the staging buffers are part of the per-device scratch pool)
+    if (call.rc) return call.rc;
+    return match_host_text(a, *call.d, haystack, n_units, record_kind, out, cap, n_out);
 }
 
 int acgpu_stream_probe(const void *d_buf, uint64_t n_bytes, void *stream_, int repeats, int pattern, float *ms_median) {

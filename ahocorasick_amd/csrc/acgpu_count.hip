@@ -12,7 +12,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <mutex>
 
 #include "acgpu_host.h"
 #include "acgpu_internal.h"
@@ -54,15 +53,7 @@ int count_pieces(acgpu_automaton *a, DeviceState &d, CountCall &c, uint64_t begi
     c.direct_ok = false;
     if (t.mode == ACGPU_MODE_ALL && t.hy_n_states && !(tunables().count_form & 1))
         c.direct_ok = d.visits.ensure((size_t)t.hy_n_states * 4) == ACGPU_OK; // (no room: every piece takes the records form)
-    PieceDriver p;
-    p.pos = begin;
-    p.end = end;
-    p.chain = *chain;
-    p.whole = whole;
-    p.record_kind = ACGPU_REC_MAP;
-    p.ramp.start();
-    p.res = &d.count_res; // (with what the pool holds from earlier calls)
-    p.through = &c.through_reservoir;
+    PieceDriver p(begin, end, *chain, whole, ACGPU_REC_MAP, &d.count_res, &c.through_reservoir); // (the reservoir with what the pool holds from earlier calls)
     int rc = ACGPU_OK;
     for (uint64_t cnt, base; rc == ACGPU_OK && p.pos < p.end;) rc = scan_next_piece(p, scan, &cnt, &base);
     c.st.pieces = (uint32_t)p.pieces;
@@ -83,26 +74,21 @@ int acgpu_count_u16(const acgpu_automaton *ca, const uint16_t *haystack, uint64_
     if (n_units >= (1ull << 31)) return ACGPU_E_INVALID;
     acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
     if (n_counts != a->n_given) return ACGPU_E_INVALID;
-    DeviceState *dp = nullptr;
-    int rc = device_for_call(a, &dp); // (no device: fails here, as acgpu_match_u16 does, and counts is untouched)
-    if (rc) return rc;
-    DeviceState &d = *dp;
-    std::lock_guard<std::mutex> lock(d.mu);
-    if (d.inflight > 0 && d.call_stream != d.inflight_stream) return ACGPU_E_INVALID; // stream rule (include/acgpu.h)
+    PoolCall call(a); // (no device: fails here, as acgpu_match_u16 does, and counts is untouched)
+    if (call.rc) return call.rc;
+    DeviceState &d = *call.d;
     const hipStream_t stream = d.call_stream;
+    int rc = call.on(stream);
+    if (rc) return rc;
     if ((rc = d.count_out.ensure((size_t)n_counts * 8 + 8))) return rc;
     HIP_TRY(hipMemsetAsync(d.count_out.p, 0, (size_t)n_counts * 8 + 8, stream));
     CountCall c;
     c.d_counts = (unsigned long long *)d.count_out.p;
     c.n_counts = n_counts;
     CountGuard guard(d, &c);
-    const bool whole = one_piece(shard_rule(a->t, ACGPU_REC_MAP, false), a->t);
     int64_t chain = 0;
-    rc = count_pieces(a, d, c, 0, n_units, &chain, whole, PieceScan{a, d, haystack, n_units, nullptr, stream});
-    if (rc) {
-        (void)hipStreamSynchronize(stream); // (nothing of the call stays in flight behind its CountCall)
-        return rc;
-    }
+    rc = count_pieces(a, d, c, 0, n_units, &chain, host_one_piece(a->t, ACGPU_REC_MAP), PieceScan{a, d, haystack, n_units, nullptr, stream});
+    if (rc) return call.fail(rc); // (nothing of the call stays in flight behind its CountCall)
     if (n_counts) HIP_TRY(hipMemcpyAsync(counts, d.count_out.p, (size_t)n_counts * 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     if (st) *st = c.st;
@@ -115,13 +101,12 @@ int acgpu_count_device(const acgpu_automaton *ca, acgpu_shard *shard, uint64_t *
     acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
     if (n_counts != a->n_given) return ACGPU_E_INVALID;
     if (shard->n_units >= (1ull << 31) || shard->own_begin > shard->own_end || shard->own_end > shard->n_units) return ACGPU_E_INVALID;
-    DeviceState *dp = nullptr;
-    int rc = device_for_call(a, &dp);
-    if (rc) return rc;
-    DeviceState &d = *dp;
-    std::lock_guard<std::mutex> lock(d.mu);
+    PoolCall call(a);
+    if (call.rc) return call.rc;
+    DeviceState &d = *call.d;
     const hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    if (d.inflight > 0 && stream != d.inflight_stream) return ACGPU_E_INVALID; // stream rule (include/acgpu.h)
+    int rc = call.on(stream);
+    if (rc) return rc;
     CountCall c;
     c.d_counts = reinterpret_cast<unsigned long long *>(d_counts);
     c.n_counts = n_counts;

@@ -110,11 +110,11 @@ int cursor_next(acgpu_cursor *c, void *out, uint64_t cap, uint64_t *n_out) {
     int cur = -1;
     HIP_TRY(hipGetDevice(&cur));
     if (cur != c->device) return ACGPU_E_INVALID;
-    DeviceState *d = nullptr;
-    int rc = device_for_call(c->a, &d);
+    PoolCall call(c->a);
+    if (call.rc) return call.rc;
+    DeviceState *d = call.d;
+    int rc = call.idle(); // (tickets of the asynchronous entry are in flight)
     if (rc) return rc;
-    std::lock_guard<std::mutex> lock(d->mu);
-    if (d->inflight > 0) return ACGPU_E_INVALID; // (stream rule: tickets of the asynchronous entry are in flight)
     while (c->res_r == c->res_n) { // (an empty reservoir: scan until a piece yields a record or the text ends)
         if (c->p.pos >= c->p.end) {
             c->st.done = 1;
@@ -154,11 +154,7 @@ int acgpu_cursor_open(const acgpu_automaton *ca, const uint16_t *haystack, uint6
     if (!c) return ACGPU_E_NOMEM;
     c->device = d->device;
     c->hay = haystack;
-    c->p.end = n_units;
-    c->p.record_kind = record_kind;
-    c->p.whole = one_piece(shard_rule(a->t, record_kind, false), a->t);
-    c->p.ramp.start();
-    c->p.res = &c->res;
+    c->p = PieceDriver(0, n_units, 0, host_one_piece(a->t, record_kind), record_kind, &c->res);
     try {
         std::lock_guard<std::mutex> l(a->mu);
         a->open_cursors.insert(c);

@@ -65,6 +65,35 @@ struct Reservoir {
     }
 };
 
+// What a scratch pool (DeviceState) owns: released when the pool dies, neither copied nor assigned.  DevBuf and Reservoir
+// themselves stay plain -- StreamBufs is moved by member copy, g_timing is a global, locals release by hand.
+template <class Buf>
+struct Owned : Buf {
+    Owned() = default;
+    Owned(const Owned &) = delete;
+    Owned &operator=(const Owned &) = delete;
+    ~Owned() { this->release(); }
+};
+using PoolBuf = Owned<DevBuf>;
+
+// ... and its pinned blocks, events and streams: reads as the handle, the runtime creates it through &x.h.
+template <class H, auto Free>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    Handle(Handle &&o) noexcept : h(o.h) { o.h = nullptr; } // (no copies: a handle has one owner)
+    ~Handle() { reset(); }
+    void reset() {
+        if (h) (void)Free(h);
+        h = nullptr;
+    }
+    operator H() const { return h; }
+};
+template <class T = void>
+using Pinned = Handle<T *, hipHostFree>;
+using PoolEvent = Handle<hipEvent_t, hipEventDestroy>;
+using PoolStream = Handle<hipStream_t, hipStreamDestroy>;
+
 // How a call's result is collected (collect(), acgpu_api.hip): the pipeline that was enqueued.
 enum class CallForm : uint8_t {
     Complete,      // the empty call: nothing found, nothing to report
@@ -97,7 +126,7 @@ struct CallRecord {
     void *d_out = nullptr;
     uint64_t cap = 0;
     hipStream_t stream = nullptr;
-    hipEvent_t *ev = nullptr;          // ev[0] .. ev[2]: the profile's events
+    const PoolEvent *ev = nullptr;     // ev[0] .. ev[2]: the profile's events
     hipEvent_t done = nullptr;         // a ticket's completion marker; null: a synchronous call (or one that ran to its end inside _begin)
     bool done_is_ev2 = false;          // the completion to wait for is ev[2] (the call's last kernel's own end), not `done`
     bool one_kernel = false;           // the call was one kernel (the fused tail, a sequential kernel): ev[0] .. ev[2] is all of it, ev[1] is not recorded
@@ -115,9 +144,9 @@ struct CallRecord {
 
 // One asynchronous call in flight (acgpu_match_device_begin/_end): its own events and pinned count slot.
 struct Ticket {
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t done = nullptr;
-    unsigned long long *h_count = nullptr; // pinned, 64 bytes
+    PoolEvent ev[3];
+    PoolEvent done;
+    Pinned<unsigned long long> h_count; // 64 bytes
     bool busy = false;
     CallRecord rec;
     void *owner = nullptr; // the DeviceState it belongs to
@@ -156,94 +185,66 @@ struct DeviceState {
     std::mutex mu;   // one call at a time on this scratch pool (the automaton's own mutex only guards its map of these)
     int device = -1;
     int lane = 0;    // 0: what the single-device entries use; > 0: further shards of a multi-device call on the SAME device
-    hipStream_t call_stream = nullptr; // the stream the host-haystack entries work on: the NULL stream for lane 0, its own otherwise
+    hipStream_t call_stream = nullptr; // the stream the host-haystack entries work on: the NULL stream for lane 0, lane_stream otherwise
+    PoolStream lane_stream;            // (acgpu_match_u16_multi points call_stream at multi_stream for the duration of a call)
     int n_cu = 256;      // CUs the scan kernels size their grids for: n_cu_phys minus the tunable reserve_cus
     int n_cu_phys = 256; // multiProcessorCount of the device
     DevTables T{};
     const uint8_t *wflags_f = nullptr; // word-character tables of the loops that fold in every lookup (HostTables::wflags_f)
     const uint32_t *wbits_f = nullptr;
     int start_behind = -1; // set for the duration of a batch call: the separator unit (k_wwl_starts: a haystack's first unit is a walk start)
-    std::vector<void *> table_allocs;
+    std::vector<Handle<void *, hipFree>> table_allocs;
     // scratch pool (one in-flight match per automaton and device)
-    DevBuf counter, chunk_counts, offsets, scan_tmp, scratch, chain, lenbuf, statebuf;
-    DevBuf stage_hay, stage_out; // acgpu_match_u16 staging
+    PoolBuf counter, chunk_counts, offsets, scan_tmp, scratch, chain, lenbuf, statebuf;
+    PoolBuf stage_hay, stage_out; // acgpu_match_u16 staging
     // the one-launch form for short haystacks (acgpu_small.hip): host-mapped pinned block [status | haystack | records], its stream
-    void *small_pin = nullptr, *small_pin_dev = nullptr;
-    hipStream_t small_stream = nullptr;
-    DevBuf multi_win, multi_tail; // multi-device calls, chain families: records of a repair window, the kept tail of the speculation
+    Pinned<> small_pin;
+    void *small_pin_dev = nullptr;
+    PoolStream small_stream;
+    PoolBuf multi_win, multi_tail; // multi-device calls, chain families: records of a repair window, the kept tail of the speculation
     // batch entry: pinned concatenation + offsets, device offsets, tagged records
-    void *batch_pin = nullptr;
+    Pinned<> batch_pin;
     size_t batch_pin_bytes = 0;
-    DevBuf batch_off, batch_out;
+    PoolBuf batch_off, batch_out;
     // pipelined host entry: pinned staging ring (one slot per chunk in flight), its copy stream, one event per chunk
     static constexpr int kPinSlots = 8;
-    void *pin[kPinSlots] = {nullptr};
+    Pinned<> pin[kPinSlots];
     size_t pin_bytes = 0; // bytes per slot
     int pin_n = 0;        // slots allocated
-    hipStream_t multi_stream = nullptr; // acgpu_match_u16_multi: this pool's stream for the duration of such a call (kept between calls)
-    hipStream_t copy_stream = nullptr;
-    std::vector<hipEvent_t> chunk_ev;
-    DevBuf short_recs, short_nxt, short_tmp, short_mark; // SHORTEST: all-matches list + selection scratch
-    DevBuf ww_recs;                                      // WHOLEWORD: region-local record slots (TileLaunch::d_region_recs)
-    DevBuf blockmax;                                     // LONGEST: farthest landing per 64 positions
-    DevBuf lenbig, todo;                                 // LONGEST: escaped lengths; root-table form: flagged chunks
-    DevBuf chainbits;                                    // LONGEST: one bit per position, set where the chain reports a match
-    DevBuf bits_state;                                   // k_longest_bits: exit / flag / count, look-back words, region counter -- zero between calls
-    DevBuf visits, count_out;                            // acgpu_count_*: visit words (4 bytes per state of the compact automaton), the host entry's counts
-    Reservoir count_res;                                 // ... and their reservoir of Map records (a replace call's too: acgpu_replace.hip)
-    DevBuf replace_tab, replace_plan, replace_slab;      // acgpu_replace_*: the replacement table, the plan {sums, output positions}, the host entry's two slabs
-    void *replace_pin = nullptr;                         // ... pinned, 64 bytes: a piece's output length and last end
-    hipEvent_t replace_ev[4] = {nullptr, nullptr, nullptr, nullptr}; // ... slab b emitted (b), slab b copied out (2 + b)
-    DevBuf replace_merged, replace_off;                  // acgpu_replace_batch_u16: a piece's records merged with its separators, the result's offsets
-    DevBuf summary;                                      // acgpu_summary_batch_u16: 24 bytes per haystack, {records, the first of them}
+    PoolStream multi_stream; // acgpu_match_u16_multi: this pool's stream for the duration of such a call (kept between calls)
+    PoolStream copy_stream;
+    std::vector<PoolEvent> chunk_ev;
+    PoolBuf short_recs, short_nxt, short_tmp, short_mark; // SHORTEST: all-matches list + selection scratch
+    PoolBuf ww_recs;                                      // WHOLEWORD: region-local record slots (TileLaunch::d_region_recs)
+    PoolBuf blockmax;                                     // LONGEST: farthest landing per 64 positions
+    PoolBuf lenbig, todo;                                 // LONGEST: escaped lengths; root-table form: flagged chunks
+    PoolBuf chainbits;                                    // LONGEST: one bit per position, set where the chain reports a match
+    PoolBuf bits_state;                                   // k_longest_bits: exit / flag / count, look-back words, region counter -- zero between calls
+    PoolBuf visits, count_out;                            // acgpu_count_*: visit words (4 bytes per state of the compact automaton), the host entry's counts
+    Owned<Reservoir> count_res;                           // ... and their reservoir of Map records (a replace call's too: acgpu_replace.hip)
+    PoolBuf replace_tab, replace_plan, replace_slab;      // acgpu_replace_*: the replacement table, the plan {sums, output positions}, the host entry's two slabs
+    Pinned<> replace_pin;                                 // ... 64 bytes: a piece's output length and last end
+    PoolEvent replace_ev[4];                              // ... slab b emitted (b), slab b copied out (2 + b)
+    PoolBuf replace_merged, replace_off;                  // acgpu_replace_batch_u16: a piece's records merged with its separators, the result's offsets
+    PoolBuf summary;                                      // acgpu_summary_batch_u16: 24 bytes per haystack, {records, the first of them}
     CountCall *count = nullptr;                          // the counting call that runs on this pool (it holds mu), or nullptr
     double all_density = -1.0;                           // ALL: records per unit of this pool's last call (-1: none yet): k_ac_states or the tile kernel
     int fol_level = 0;                                   // k_longest_follow: 0 = run-up of 128 positions, 1 = of a whole segment (a call's chains had not merged), 2 = not for this pool's texts
     void *bits_state_seen = nullptr;                     // (a re-allocated buffer, or a call that failed half way, is zeroed by a memset)
-    DevBuf cands, region_cands;                          // ALL, split form: candidate positions, {first, count} per region
-    DevBuf wwl_rs, wwl_mend, wwl_mid, wwl_sel, wwl_stop, wwl_nxt0; // WWLONGEST: walk starts, what each would report, where it stops
-    unsigned long long *h_counter = nullptr; // pinned, 64 bytes: the slot of the pool's own record, and the kPool words
+    PoolBuf cands, region_cands;                          // ALL, split form: candidate positions, {first, count} per region
+    PoolBuf wwl_rs, wwl_mend, wwl_mid, wwl_sel, wwl_stop, wwl_nxt0; // WWLONGEST: walk starts, what each would report, where it stops
+    Pinned<unsigned long long> h_counter;    // 64 bytes: the slot of the pool's own record, and the kPool words
     // match_all: two sets of slot counters alternate; the permute pass of a call zeroes the set the next call uses
     int cset = 0;
     bool cclean[2] = {false, false};
     void *counter_seen = nullptr; // (a re-allocated counter buffer is not clean)
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    PoolEvent ev[4];
     CallRecord call; // the synchronous calls' record
     Ticket tickets[4];
     // stream rule (include/acgpu.h): while tickets are in flight every call on this automaton and device uses their stream
     int inflight = 0;
     hipStream_t inflight_stream = nullptr;
-    ~DeviceState() {
-        for (void *p : table_allocs) (void)hipFree(p);
-        counter.release(); chunk_counts.release(); offsets.release(); scan_tmp.release(); scratch.release();
-        chain.release(); lenbuf.release(); statebuf.release(); stage_hay.release(); stage_out.release();
-        multi_win.release(); multi_tail.release();
-        if (call_stream) (void)hipStreamDestroy(call_stream);
-        if (multi_stream) (void)hipStreamDestroy(multi_stream);
-        if (small_stream) (void)hipStreamDestroy(small_stream);
-        if (small_pin) (void)hipHostFree(small_pin);
-        short_recs.release(); short_nxt.release(); short_tmp.release(); short_mark.release();
-        wwl_rs.release(); wwl_mend.release(); wwl_mid.release(); wwl_sel.release(); wwl_stop.release(); wwl_nxt0.release(); ww_recs.release(); blockmax.release(); lenbig.release(); todo.release(); chainbits.release(); bits_state.release(); cands.release(); region_cands.release();
-        if (h_counter) (void)hipHostFree(h_counter);
-        for (auto &q : pin) if (q) (void)hipHostFree(q);
-        if (batch_pin) (void)hipHostFree(batch_pin);
-        batch_off.release(); batch_out.release();
-        visits.release(); count_res.release(); count_out.release();
-        replace_tab.release(); replace_plan.release(); replace_slab.release(); replace_merged.release(); replace_off.release();
-        summary.release();
-        if (replace_pin) (void)hipHostFree(replace_pin);
-        for (auto &e : replace_ev) if (e) (void)hipEventDestroy(e);
-        if (copy_stream) (void)hipStreamDestroy(copy_stream);
-        for (auto &e : chunk_ev) if (e) (void)hipEventDestroy(e);
-        for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-        for (auto &tk : tickets) {
-            for (auto &e : tk.ev) if (e) (void)hipEventDestroy(e);
-            if (tk.done) (void)hipEventDestroy(tk.done);
-            if (tk.h_count) (void)hipHostFree(tk.h_count);
-        }
-    }
-};
-
+}; // (no destructor: every member releases itself -- acgpu_free has made the pool's device current)
 
 } // namespace acgpu
 
@@ -321,10 +322,32 @@ int64_t piece_entry(const ShardRule &r, int64_t chain, int64_t origin, uint64_t 
 int64_t piece_exit(const ShardRule &r, int64_t entry, uint64_t own_end, const acgpu_shard *sh, uint64_t n);
 // A host haystack is scanned as one piece: only the whole-text kernel exists, or the halos would not fit a host chunk.
 bool one_piece(const ShardRule &r, const HostTables &t);
+// ... what the host entries that scan piece by piece ask: the rule of the String loop
+bool host_one_piece(const HostTables &t, int record_kind);
 
 // The scratch pool of `a` on the CURRENT HIP device (created and the tables uploaded on first use).  lane > 0: a further,
 // independent pool on the same device (its own stream), for multi-device calls that list a device more than once.
 int device_for_call(acgpu_automaton *a, DeviceState **d, int lane = 0);
+
+// The prologue of a call on the current device's pool: device_for_call, then d->mu for the call's lifetime.  rc != 0: no pool,
+// nothing is locked.  The stream rule (include/acgpu.h) in its two forms, for the entry to apply where its checks have it.
+struct PoolCall {
+    DeviceState *d = nullptr;
+    int rc;
+    std::unique_lock<std::mutex> lock;
+    explicit PoolCall(acgpu_automaton *a) : rc(device_for_call(a, &d)) {
+        if (!rc) lock = std::unique_lock<std::mutex>(d->mu);
+    }
+    // a call that enqueues on `stream`: tickets in flight must be on that stream
+    int on(hipStream_t stream) const { return d->inflight > 0 && stream != d->inflight_stream ? ACGPU_E_INVALID : ACGPU_OK; }
+    // a call that uses the NULL stream or waits on the host: no ticket may be in flight
+    int idle() const { return d->inflight > 0 ? ACGPU_E_INVALID : ACGPU_OK; }
+    int fail(int code) const { // the call failed: nothing of it stays in flight
+        (void)hipStreamSynchronize(d->call_stream);
+        if (d->copy_stream) (void)hipStreamSynchronize(d->copy_stream);
+        return code;
+    }
+};
 
 // Validates a shard and runs the pipeline of the automaton's family on `stream`; the caller holds d.mu.
 // readable: the call stands for match(Readable, ...) (acgpu_stream_feed).
@@ -355,14 +378,38 @@ int scan_host_range(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack
 // end, no chain.  The caller holds d.mu.
 int stage_whole_text(DeviceState &d, const uint16_t *haystack, uint64_t n_units, acgpu_shard *out);
 
-// The haystacks of a batch call as one text in d.batch_pin, a separator `sep` behind every haystack: *h_cat = the text, *h_off =
-// n_haystacks + 1 words behind it, h_off[i] = the first unit of haystack i (separator i stands at h_off[i + 1] - 1).  The caller
-// holds d.mu and has checked the offsets.
-int batch_concat(DeviceState &d, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks, uint16_t sep, uint16_t **h_cat,
-                 uint32_t **h_off);
+// acgpu_match_u16 behind its argument checks; the caller holds d.mu (acgpu_match_batch_u16 calls it per haystack).
+int match_host_text(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack, uint64_t n_units, int record_kind, void *out,
+                    uint64_t cap, uint64_t *n_out);
 
-// A text on its way through a reservoir, piece by piece (scan_next_piece, acgpu_pieces.hip): the cursor keeps one from page call
-// to page call, a counting call has one for its duration.
+// What the batch entries check before they touch a device (check_batch, acgpu_batch.hip).
+struct BatchPlan {
+    uint64_t total = 0, cat = 0; // units of all haystacks; of their concatenation, a separator behind every haystack
+    bool per_haystack = false; // they cannot be concatenated: every haystack is scanned as a text of its own
+};
+int check_batch(const HostTables &t, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks, BatchPlan *plan);
+
+// The haystacks of a batch call staged as ONE text, for as long as the call scans it: the text and its offsets in d.batch_pin
+// (h_off[i] = the first unit of haystack i, separator i stands at h_off[i + 1] - 1; n_haystacks + 1 words), the offsets in
+// d.batch_off as well, and d.start_behind set to the separator.  The caller holds d.mu.
+struct BatchText {
+    DeviceState &d;
+    const uint16_t sep;
+    uint16_t *h_cat = nullptr;
+    uint32_t *h_off = nullptr;
+    uint64_t cat = 0;
+    uint32_t n_haystacks = 0;
+    // (WholeWordLongest: every haystack's first unit is a walk start, also where a piece's left halo is the separator)
+    BatchText(DeviceState &d_, const HostTables &t) : d(d_), sep((uint16_t)t.sep_unit) { d.start_behind = t.sep_unit; }
+    BatchText(const BatchText &) = delete;
+    ~BatchText() { d.start_behind = -1; }
+    const uint32_t *d_off() const { return reinterpret_cast<const uint32_t *>(d.batch_off.p); }
+    // concatenates, and uploads the offsets on `stream` (asynchronously: the scan follows on it)
+    int stage(const uint16_t *units, const uint64_t *offsets, uint32_t n, hipStream_t stream);
+};
+
+// A text on its way through a reservoir, piece by piece (scan_next_piece, acgpu_pieces.hip).  Four consumers: the cursor keeps
+// one from page call to page call; a counting, a replace and a batch summary call have one for each text they drive.
 struct PieceDriver {
     uint64_t pos = 0, end = 0;         // the owned units [pos, end) have not been scanned yet
     int64_t chain = 0;                 // the chain's entry into the next piece (the text's coordinates)
@@ -373,6 +420,9 @@ struct PieceDriver {
     const uint64_t *through = nullptr; // a counting call: CountCall::through_reservoir (its shards' records are counted as they are collected)
     uint64_t pieces = 0, rescans = 0;  // scan attempts; of those, attempts whose records did not fit
     uint64_t units_scanned = 0, scan_end = 0; // owned units scanned, rescans included; the host text's units [0, scan_end) have been scanned
+    PieceDriver() = default;
+    PieceDriver(uint64_t pos_, uint64_t end_, int64_t chain_, bool whole_, int record_kind_, Reservoir *res_, const uint64_t *through_ = nullptr)
+        : pos(pos_), end(end_), chain(chain_), whole(whole_), record_kind(record_kind_), res(res_), through(through_) { ramp.start(); }
 };
 
 // The scan of one piece.  Exactly three kinds: a caller's device shard with a moving owned range (`shard`, on `stream`); else a

@@ -390,7 +390,7 @@ int acgpu_match_u16_multi(const acgpu_automaton *ca, const uint16_t *haystack, u
         if ((rc = device_for_call(a, &sh[i].d, sh[i].lane))) break;
         locks[i] = std::unique_lock<std::mutex>(sh[i].d->mu);
         if (sh[i].d->inflight > 0) rc = ACGPU_E_INVALID; // (stream rule: tickets of the asynchronous entry are in flight)
-        else if (!sh[i].d->multi_stream && hipStreamCreateWithFlags(&sh[i].d->multi_stream, hipStreamNonBlocking) != hipSuccess) rc = ACGPU_E_HIP;
+        else if (!sh[i].d->multi_stream && hipStreamCreateWithFlags(&sh[i].d->multi_stream.h, hipStreamNonBlocking) != hipSuccess) rc = ACGPU_E_HIP;
         else {
             own_stream[i] = sh[i].d->multi_stream; // (the pool's own, created once)
             saved[i] = sh[i].d->call_stream;

@@ -17,7 +17,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <mutex>
 #include <vector>
 
 #include "acgpu_device.h"
@@ -483,8 +482,8 @@ int replace_piece(ReplaceCall &c, const uint16_t *hay, uint64_t base, const int3
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(d.replace_pin, slot, 16, hipMemcpyDeviceToHost, c.stream));
         HIP_TRY(hipStreamSynchronize(c.stream)); // the piece's output length decides the windows and the next piece's `done`
-        delta = reinterpret_cast<const int64_t *>(d.replace_pin)[0];
-        last_end = base + (uint64_t)reinterpret_cast<const int64_t *>(d.replace_pin)[1];
+        delta = static_cast<const int64_t *>(d.replace_pin.h)[0];
+        last_end = base + (uint64_t)static_cast<const int64_t *>(d.replace_pin.h)[1];
     }
     const uint64_t limit = std::min(c.n, replace_limit(c.a->t, last_or_whole, c.n, own_hi, last_end, c.done));
     const int64_t total_s = (int64_t)(limit - c.done) + delta;
@@ -532,18 +531,11 @@ int replace_piece(ReplaceCall &c, const uint16_t *hay, uint64_t base, const int3
 
 int replace_pieces(ReplaceCall &c, int64_t chain, bool whole, const PieceScan &scan) {
     DeviceState &d = c.d;
-    if (!d.replace_pin) HIP_TRY(hipHostMalloc(&d.replace_pin, 64, hipHostMallocDefault));
-    if (!d.copy_stream) HIP_TRY(hipStreamCreateWithFlags(&d.copy_stream, hipStreamNonBlocking));
+    if (!d.replace_pin) HIP_TRY(hipHostMalloc(&d.replace_pin.h, 64, hipHostMallocDefault));
+    if (!d.copy_stream) HIP_TRY(hipStreamCreateWithFlags(&d.copy_stream.h, hipStreamNonBlocking));
     for (auto &e : d.replace_ev)
-        if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    PieceDriver p;
-    p.pos = 0;
-    p.end = c.n;
-    p.chain = chain;
-    p.whole = whole;
-    p.record_kind = ACGPU_REC_MAP;
-    p.ramp.start();
-    p.res = &d.count_res; // the pool's reservoir of Map records (a counting call's too: one call at a time holds the pool)
+        if (!e) HIP_TRY(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
+    PieceDriver p(0, c.n, chain, whole, ACGPU_REC_MAP, &d.count_res); // the pool's reservoir of Map records (a counting call's too: one call at a time holds the pool)
     int rc = ACGPU_OK;
     while (rc == ACGPU_OK && p.pos < p.end) {
         uint64_t cnt = 0, base = 0;
@@ -554,10 +546,28 @@ int replace_pieces(ReplaceCall &c, int64_t chain, bool whole, const PieceScan &s
         if (c.h_cat_off && (rc = merge_separators(c, base, p.pos, &recs, &n_list))) break;
         rc = replace_piece(c, hay, base, recs, n_list, cnt, p.pos, whole || p.pos >= p.end);
     }
-    c.st.pieces = (uint32_t)p.pieces;
-    c.st.rescans = (uint32_t)p.rescans;
+    c.st.pieces += (uint32_t)p.pieces; // (added: a batch call haystack by haystack drives one text after the other)
+    c.st.rescans += (uint32_t)p.rescans;
     c.st.units_out = c.out_pos;
     return rc;
+}
+
+// One host text through the pieces to its end: the body of acgpu_replace_u16, and of every haystack of a batch call that goes
+// haystack by haystack -- c.cap, c.out_pos and the stats carry on from text to text, the table is uploaded once.
+int replace_host_text(ReplaceCall &c, const uint16_t *hay, uint64_t n_units) {
+    c.n = n_units;
+    c.done = 0;
+    const int rc = replace_pieces(c, 0, host_one_piece(c.a->t, ACGPU_REC_MAP), PieceScan{c.a, c.d, hay, n_units, nullptr, c.stream});
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    return ACGPU_OK;
+}
+
+// what every entry returns behind its last piece
+int replace_result(const ReplaceCall &c, uint64_t *n_out, acgpu_replace_stats *st) {
+    if (st) *st = c.st;
+    *n_out = c.out_pos;
+    return c.out_pos > c.cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
 }
 
 // the checks both entries share, none of which needs a device
@@ -582,27 +592,16 @@ int acgpu_replace_u16(const acgpu_automaton *ca, const uint16_t *haystack, uint6
     acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
     int rc = check_table(a, repl_units, repl_off, n_repl);
     if (rc) return rc;
-    DeviceState *dp = nullptr;
-    if ((rc = device_for_call(a, &dp))) return rc; // (no device: fails here, as acgpu_match_u16 does, and out is untouched)
-    DeviceState &d = *dp;
-    std::lock_guard<std::mutex> lock(d.mu);
-    if (d.inflight > 0 && d.call_stream != d.inflight_stream) return ACGPU_E_INVALID; // stream rule (include/acgpu.h)
+    PoolCall call(a); // (no device: fails here, as acgpu_match_u16 does, and out is untouched)
+    if (call.rc) return call.rc;
+    DeviceState &d = *call.d;
+    if ((rc = call.on(d.call_stream))) return rc;
     ReplaceCall c{a, d, d.call_stream};
     c.h_out = out;
     c.cap = cap;
-    c.n = n_units;
     if ((rc = upload_table(c, repl_units, repl_off, n_repl))) return rc;
-    const bool whole = one_piece(shard_rule(a->t, ACGPU_REC_MAP, false), a->t);
-    rc = replace_pieces(c, 0, whole, PieceScan{a, d, haystack, n_units, nullptr, d.call_stream});
-    if (rc) {
-        (void)hipStreamSynchronize(d.call_stream); // (nothing of the call stays in flight)
-        if (d.copy_stream) (void)hipStreamSynchronize(d.copy_stream);
-        return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(d.call_stream));
-    if (st) *st = c.st;
-    *n_out = c.out_pos;
-    return c.out_pos > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
+    if ((rc = replace_host_text(c, haystack, n_units))) return call.fail(rc);
+    return replace_result(c, n_out, st);
 }
 
 int acgpu_replace_device(const acgpu_automaton *ca, acgpu_shard *shard, const uint16_t *repl_units, const uint64_t *repl_off,
@@ -614,12 +613,11 @@ int acgpu_replace_device(const acgpu_automaton *ca, acgpu_shard *shard, const ui
     if (rc) return rc;
     // one shard of a sharded text: its rewrite starts at the position up to which the rank before it has emitted -- not built
     if (shard->own_begin != 0 || shard->own_end != shard->n_units || shard->text_begin != 1 || shard->text_end != 1) return ACGPU_E_UNSUPPORTED;
-    DeviceState *dp = nullptr;
-    if ((rc = device_for_call(a, &dp))) return rc;
-    DeviceState &d = *dp;
-    std::lock_guard<std::mutex> lock(d.mu);
+    PoolCall call(a);
+    if (call.rc) return call.rc;
+    DeviceState &d = *call.d;
     const hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    if (d.inflight > 0 && stream != d.inflight_stream) return ACGPU_E_INVALID; // stream rule (include/acgpu.h)
+    if ((rc = call.on(stream))) return rc;
     ReplaceCall c{a, d, stream};
     c.d_out = d_out;
     c.cap = cap;
@@ -630,9 +628,7 @@ int acgpu_replace_device(const acgpu_automaton *ca, acgpu_shard *shard, const ui
     const hipError_t e = hipStreamSynchronize(stream); // the final wait
     if (rc) return rc;
     HIP_TRY(e);
-    if (st) *st = c.st;
-    *n_out = c.out_pos;
-    return c.out_pos > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
+    return replace_result(c, n_out, st);
 }
 
 int acgpu_replace_batch_u16(const acgpu_automaton *ca, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks,
@@ -646,71 +642,41 @@ int acgpu_replace_batch_u16(const acgpu_automaton *ca, const uint16_t *units, co
     out_offsets[0] = 0;
     if (st) *st = acgpu_replace_stats{};
     if (n_haystacks == 0) return ACGPU_OK;
-    for (uint32_t i = 0; i < n_haystacks; i++)
-        if (offsets[i] > offsets[i + 1]) return ACGPU_E_INVALID;
-    const uint64_t total = offsets[n_haystacks] - offsets[0];
-    if (total && !units) return ACGPU_E_INVALID;
-    const uint64_t cat = total + n_haystacks; // one separator behind every haystack
-    if (cat >= (1ull << 31)) return ACGPU_E_INVALID;
     const HostTables &t = a->t;
-    // where acgpu_match_batch_u16 scans haystack by haystack (no unit is free to separate them, or a word matcher over a table that
-    // is not fold-consistent: see there), one replace call per haystack, the results back to back
-    if (t.sep_unit < 0 || ((t.mode == ACGPU_MODE_WHOLEWORD || t.mode == ACGPU_MODE_WWLONGEST) && !t.fold_consistent)) {
-        acgpu_replace_stats sum{};
-        for (uint32_t i = 0; i < n_haystacks; i++) {
-            const uint64_t len = offsets[i + 1] - offsets[i], room = cap > sum.units_out ? cap - sum.units_out : 0;
-            uint64_t got = 0;
-            acgpu_replace_stats one{};
-            rc = acgpu_replace_u16(ca, len ? units + offsets[i] : nullptr, len, repl_units, repl_off, n_repl, room ? out + sum.units_out : nullptr,
-                                   room, &got, &one);
-            if (rc != ACGPU_OK && rc != ACGPU_E_OVERFLOW) return rc;
-            sum.n_records += one.n_records;
-            sum.pieces += one.pieces;
-            sum.rescans += one.rescans;
-            sum.units_out += got;
-            out_offsets[i + 1] = sum.units_out;
-        }
-        if (st) *st = sum;
-        *n_out = sum.units_out;
-        return sum.units_out > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
-    }
-    DeviceState *dp = nullptr;
-    if ((rc = device_for_call(a, &dp))) return rc; // (no device: fails here, and out is untouched)
-    DeviceState &d = *dp;
-    std::lock_guard<std::mutex> lock(d.mu);
-    if (d.inflight > 0) return ACGPU_E_INVALID; // (the NULL stream: see the stream rule)
-    uint16_t *h_cat = nullptr;
-    uint32_t *h_off = nullptr;
-    if ((rc = batch_concat(d, units, offsets, n_haystacks, (uint16_t)t.sep_unit, &h_cat, &h_off))) return rc;
-    const size_t off_bytes = ((size_t)n_haystacks + 1) * 4;
-    if ((rc = d.batch_off.ensure(off_bytes + 16))) return rc;
-    if ((rc = d.replace_off.ensure(((size_t)n_haystacks + 1) * 8))) return rc;
-    HIP_TRY(hipMemcpyAsync(d.batch_off.p, h_off, off_bytes, hipMemcpyHostToDevice, d.call_stream));
+    BatchPlan plan;
+    if ((rc = check_batch(t, units, offsets, n_haystacks, &plan))) return rc;
+    PoolCall call(a); // (no device: fails here, and out is untouched)
+    if (call.rc) return call.rc;
+    DeviceState &d = *call.d;
     ReplaceCall c{a, d, d.call_stream};
     c.h_out = out;
     c.cap = cap;
-    c.n = cat;
-    c.h_cat_off = h_off;
+    if (plan.per_haystack) { // every haystack as a text of its own, the results back to back
+        if ((rc = call.on(c.stream))) return rc; // (what acgpu_replace_u16 asks)
+        if ((rc = upload_table(c, repl_units, repl_off, n_repl))) return rc;
+        for (uint32_t i = 0; i < n_haystacks; i++) {
+            const uint64_t len = offsets[i + 1] - offsets[i];
+            if ((rc = replace_host_text(c, len ? units + offsets[i] : nullptr, len))) return call.fail(rc);
+            out_offsets[i + 1] = c.out_pos;
+        }
+        return replace_result(c, n_out, st);
+    }
+    if ((rc = call.idle())) return rc; // (the NULL stream: see the stream rule)
+    BatchText text(d, t);
+    if ((rc = text.stage(units, offsets, n_haystacks, c.stream))) return rc;
+    if ((rc = d.replace_off.ensure(((size_t)n_haystacks + 1) * 8))) return rc;
+    c.n = text.cat;
+    c.h_cat_off = text.h_off;
     c.n_hay = n_haystacks;
-    c.seps.cat_off = reinterpret_cast<const uint32_t *>(d.batch_off.p);
+    c.seps.cat_off = text.d_off();
     c.seps.id = (int32_t)a->n_given;
     c.d_out_off = reinterpret_cast<uint64_t *>(d.replace_off.p);
     if ((rc = upload_table(c, repl_units, repl_off, n_repl, /*full=*/true))) return rc;
-    const bool whole = one_piece(shard_rule(t, ACGPU_REC_MAP, false), t);
-    d.start_behind = t.sep_unit; // (WholeWordLongest: every haystack's first unit is a walk start, also where a piece's left halo is the separator)
-    rc = replace_pieces(c, 0, whole, PieceScan{a, d, h_cat, cat, nullptr, d.call_stream});
-    d.start_behind = -1;
-    if (rc) {
-        (void)hipStreamSynchronize(d.call_stream); // (nothing of the call stays in flight)
-        if (d.copy_stream) (void)hipStreamSynchronize(d.copy_stream);
-        return rc;
-    }
+    rc = replace_pieces(c, 0, host_one_piece(t, ACGPU_REC_MAP), PieceScan{a, d, text.h_cat, text.cat, nullptr, c.stream});
+    if (rc) return call.fail(rc);
     HIP_TRY(hipMemcpyAsync(out_offsets + 1, c.d_out_off + 1, (size_t)n_haystacks * 8, hipMemcpyDeviceToHost, d.call_stream)); // (every separator was merged once)
     HIP_TRY(hipStreamSynchronize(d.call_stream));
-    c.st.units_out = c.out_pos;
-    if (st) *st = c.st;
-    *n_out = c.out_pos;
-    return c.out_pos > cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
+    return replace_result(c, n_out, st);
 }
 
 } // extern "C"

@@ -205,10 +205,10 @@ int scan_slot(acgpu_stream *s, Slot &sl, int record_kind, void *out, uint64_t ca
     const int64_t entry = piece_entry(rule, s->chain_entry, (int64_t)sl.carry_pos, p.own_begin);
     int64_t chain_exit = piece_exit(rule, entry, p.own_end, nullptr, 0);
     if (p.own_end > p.own_begin) {
-        DeviceState *d = nullptr;
-        int rc = device_for_call(a, &d);
-        if (rc) return rc;
-        std::lock_guard<std::mutex> lock(d->mu);
+        PoolCall call(a);
+        if (call.rc) return call.rc;
+        DeviceState *d = call.d;
+        int rc;
         const bool trace = (tunables().tile_debug & (1ll << 42)) != 0;
         const auto t0 = std::chrono::steady_clock::now();
         auto since = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); };
@@ -512,10 +512,10 @@ int acgpu_stream_feed(acgpu_stream *s, const uint16_t *units, uint64_t n_units, 
     const int64_t entry = piece_entry(rule, s->chain_entry, (int64_t)s->carry_pos, own_begin);
     int64_t chain_exit = piece_exit(rule, entry, own_end, nullptr, 0);
     if (own_end > own_begin) {
-        DeviceState *d = nullptr;
-        int rc = device_for_call(a, &d);
-        if (rc) return rc;
-        std::lock_guard<std::mutex> lock(d->mu); // staging buffers are part of the per-device scratch pool
+        PoolCall call(a); // (the staging buffers are part of the per-device scratch pool)
+        if (call.rc) return call.rc;
+        DeviceState *d = call.d;
+        int rc;
         acgpu_shard sh;
         if ((rc = d->stage_out.ensure(cap * (uint64_t)record_kind + 16))) return rc;
         if ((rc = stage_whole_text(*d, s->buf.data(), total, &sh))) return rc; // (the carry and the fed units: then the owned range, the ends and the chain)

@@ -2,7 +2,7 @@
 // first of them, reduced on the device.
 //
 // A summary call is the fourth consumer of the piece driver (scan_next_piece, acgpu_pieces.hip): the haystacks are concatenated
-// with a separator unit behind each (batch_concat, as acgpu_replace_batch_u16 does), that text goes through the pieces, the Map
+// with a separator unit behind each (BatchText, as acgpu_replace_batch_u16 does), that text goes through the pieces, the Map
 // records of a piece stay in the pool's reservoir, and behind every piece that completed ONE kernel, k_batch_summary, reduces them
 // into the pool's summaries -- 24 bytes per haystack, the only thing that leaves the device, once, at the end of the call.
 //
@@ -14,7 +14,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <mutex>
 #include <vector>
 
 #include "acgpu_device.h"
@@ -112,14 +111,7 @@ struct SummaryTarget {
 // One text through the pieces; behind every piece that scan_next_piece completed (a piece scanned again for want of room comes
 // back once) the summary kernel on its records.  The host waits for nothing here: the next scan follows on the same stream.
 int summary_pieces(acgpu_automaton *a, DeviceState &d, const PieceScan &scan, bool whole, const SummaryTarget &tg, acgpu_summary_stats *st) {
-    PieceDriver p;
-    p.pos = 0;
-    p.end = scan.n;
-    p.chain = 0;
-    p.whole = whole;
-    p.record_kind = ACGPU_REC_MAP;
-    p.ramp.start();
-    p.res = &d.count_res; // the pool's reservoir of Map records (one call at a time holds the pool)
+    PieceDriver p(0, scan.n, 0, whole, ACGPU_REC_MAP, &d.count_res); // the pool's reservoir of Map records (one call at a time holds the pool)
     int rc = ACGPU_OK;
     while (rc == ACGPU_OK && p.pos < p.end) {
         uint64_t cnt = 0, base = 0;
@@ -142,37 +134,28 @@ extern "C" {
 int acgpu_summary_batch_u16(const acgpu_automaton *ca, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks,
                             acgpu_batch_summary *out, acgpu_summary_stats *st) {
     if (!ca || !offsets || (n_haystacks && !out)) return ACGPU_E_INVALID;
-    for (uint32_t i = 0; i < n_haystacks; i++)
-        if (offsets[i] > offsets[i + 1]) return ACGPU_E_INVALID;
-    const uint64_t total = offsets[n_haystacks] - offsets[0];
-    if (total && !units) return ACGPU_E_INVALID;
-    const uint64_t cat = total + n_haystacks; // one separator behind every haystack
-    if (cat >= (1ull << 31)) return ACGPU_E_INVALID;
+    acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
+    const HostTables &t = a->t;
+    BatchPlan plan;
+    int rc = check_batch(t, units, offsets, n_haystacks, &plan);
+    if (rc) return rc;
     if (n_haystacks == 0) {
         if (st) *st = acgpu_summary_stats{};
         return ACGPU_OK;
     }
-    acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
-    const HostTables &t = a->t;
-    DeviceState *dp = nullptr;
-    int rc = device_for_call(a, &dp); // (no device: fails here, as acgpu_match_batch_u16 does, and out is untouched)
-    if (rc) return rc;
-    DeviceState &d = *dp;
-    std::lock_guard<std::mutex> lock(d.mu);
-    if (d.inflight > 0) return ACGPU_E_INVALID; // (the NULL stream: see the stream rule)
+    PoolCall call(a); // (no device: fails here, as acgpu_match_batch_u16 does, and out is untouched)
+    if (call.rc) return call.rc;
+    DeviceState &d = *call.d;
+    if ((rc = call.idle())) return rc; // (the NULL stream: see the stream rule)
     const hipStream_t stream = d.call_stream;
     const size_t off_bytes = ((size_t)n_haystacks + 1) * 4, sum_bytes = (size_t)n_haystacks * sizeof(acgpu_batch_summary);
-    if ((rc = d.batch_off.ensure(off_bytes + 16))) return rc;
     if ((rc = d.summary.ensure(sum_bytes))) return rc;
     acgpu_batch_summary *d_sum = reinterpret_cast<acgpu_batch_summary *>(d.summary.p);
-    const uint32_t *d_off = reinterpret_cast<const uint32_t *>(d.batch_off.p);
     hipLaunchKernelGGL(k_summary_fill, dim3((n_haystacks + kSummaryBlock - 1) / kSummaryBlock), dim3(kSummaryBlock), 0, stream, d_sum, n_haystacks);
     HIP_TRY(hipGetLastError());
     acgpu_summary_stats sum{};
-    const bool whole = one_piece(shard_rule(t, ACGPU_REC_MAP, false), t);
-    // where acgpu_match_batch_u16 scans haystack by haystack (no unit is free to separate them, or a word matcher over a table that
-    // is not fold-consistent: see there), every haystack goes through the pieces as a text of its own, into its own entry
-    if (t.sep_unit < 0 || ((t.mode == ACGPU_MODE_WHOLEWORD || t.mode == ACGPU_MODE_WWLONGEST) && !t.fold_consistent)) {
+    const bool whole = host_one_piece(t, ACGPU_REC_MAP);
+    if (plan.per_haystack) { // every haystack goes through the pieces as a text of its own, into its own entry
         std::vector<uint32_t> h_off;
         try {
             h_off.resize((size_t)n_haystacks + 1);
@@ -180,6 +163,8 @@ int acgpu_summary_batch_u16(const acgpu_automaton *ca, const uint16_t *units, co
             return ACGPU_E_NOMEM;
         }
         for (uint32_t i = 0; i <= n_haystacks; i++) h_off[i] = (uint32_t)(offsets[i] - offsets[0] + i); // (the concatenation's offsets)
+        if ((rc = d.batch_off.ensure(off_bytes + 16))) return rc;
+        const uint32_t *d_off = reinterpret_cast<const uint32_t *>(d.batch_off.p);
         HIP_TRY(hipMemcpy(d.batch_off.p, h_off.data(), off_bytes, hipMemcpyHostToDevice));
         for (uint32_t i = 0; i < n_haystacks && rc == ACGPU_OK; i++) {
             const uint64_t len = offsets[i + 1] - offsets[i];
@@ -188,18 +173,12 @@ int acgpu_summary_batch_u16(const acgpu_automaton *ca, const uint16_t *units, co
                                 SummaryTarget{d_off + i, 1, h_off[i], d_sum + i}, &sum);
         }
     } else {
-        uint16_t *h_cat = nullptr;
-        uint32_t *h_off = nullptr;
-        if ((rc = batch_concat(d, units, offsets, n_haystacks, (uint16_t)t.sep_unit, &h_cat, &h_off))) return rc;
-        HIP_TRY(hipMemcpyAsync(d.batch_off.p, h_off, off_bytes, hipMemcpyHostToDevice, stream));
-        d.start_behind = t.sep_unit; // (WholeWordLongest: every haystack's first unit is a walk start, also where a piece's left halo is the separator)
-        rc = summary_pieces(a, d, PieceScan{a, d, h_cat, cat, nullptr, stream}, whole, SummaryTarget{d_off, n_haystacks, 0, d_sum}, &sum);
-        d.start_behind = -1;
+        BatchText text(d, t);
+        if ((rc = text.stage(units, offsets, n_haystacks, stream))) return rc;
+        rc = summary_pieces(a, d, PieceScan{a, d, text.h_cat, text.cat, nullptr, stream}, whole, SummaryTarget{text.d_off(), n_haystacks, 0, d_sum},
+                            &sum);
     }
-    if (rc) {
-        (void)hipStreamSynchronize(stream); // (nothing of the call stays in flight)
-        return rc;
-    }
+    if (rc) return call.fail(rc);
     HIP_TRY(hipMemcpyAsync(out, d_sum, sum_bytes, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     for (uint32_t i = 0; i < n_haystacks; i++) sum.n_matched += out[i].n_matches != 0;

@@ -71,3 +71,21 @@ def test_host_builder_under_asan_ubsan_builds_the_product_tables(tmp_path):
             assert (got["dfa"].reshape(dfa.shape) == dfa).all(), name
         n_checked += 1
     assert n_checked >= 9
+
+
+def test_pool_owning_types_under_asan_ubsan(tmp_path):
+    """tests/san_owners.cpp: the owning types of csrc/acgpu_host.h -- construction, a failed ensure, destruction -- as a
+    stand-alone host program over a stub runtime without a device.  The ROCm compiler builds it (the HIP headers need clang)."""
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    clang = os.path.join(rocm, "llvm", "bin", "clang++")
+    if not os.path.exists(clang):
+        pytest.skip("no ROCm clang++")
+    exe = tmp_path / "san_owners"
+    csrc = os.path.join(ROOT, "ahocorasick_amd", "csrc")
+    subprocess.check_call([clang, "-x", "c++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-Wno-c++20-extensions", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"),
+                           "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "-o", str(exe), os.path.join(ROOT, "tests", "san_owners.cpp")])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    p = subprocess.run([str(exe)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
+    out = p.stdout.decode(errors="replace")
+    assert p.returncode == 0 and "san_owners: done" in out and "ERROR: AddressSanitizer" not in out and "runtime error:" not in out, out[-4000:]
