@@ -511,10 +511,15 @@ int timing_report_ww(const TileLaunch &L, bool fused_tail, hipStream_t stream) {
 int timing_report_tile(const TileLaunch &L, hipStream_t stream) {
     std::vector<unsigned long long> h;
     if (int rc = timing_read(L, stream, h)) return rc;
-    double sum[8] = {0}, mx0 = 0, vt[4] = {0, 0, 0, 0}; size_t nw = 0;
+    double sum[8] = {0}, mx0 = 0, vt[4] = {0, 0, 0, 0}, su = 0, su_min = 1e30, su_max = 0; size_t nw = 0;
     for (size_t w = 0; w < h.size() / 8; ++w) {
         if (!h[w * 8]) continue;
         nw++;
+        { // word 4: passes, and above them the start-up (kernel entry to the first filtered tile)
+            const double s = (double)(h[w * 8 + 4] >> 32);
+            h[w * 8 + 4] &= 0xffffffffull;
+            su += s; su_min = std::min(su_min, s); su_max = std::max(su_max, s);
+        }
         for (int i = 0; i < 6; ++i) sum[i] += (double)h[w * 8 + i];
         vt[0] += (double)(h[w * 8 + 6] & 0xffffffffu); vt[1] += (double)(h[w * 8 + 6] >> 32);
         vt[2] += (double)(h[w * 8 + 7] & 0xffffffffu); vt[3] += (double)(h[w * 8 + 7] >> 32);
@@ -539,6 +544,7 @@ int timing_report_tile(const TileLaunch &L, hipStream_t stream) {
         }
         fprintf(stderr, "\n");
     }
+    if (nw) fprintf(stderr, "[timing] start-up (entry to first filtered tile): avg %.0f min %.0f max %.0f\n", su / nw, su_min, su_max);
     if (nw) fprintf(stderr, "[timing] verification: windows %.0f | K-gram nodes %.0f | walks %.0f | emission %.0f\n", vt[0] / nw, vt[1] / nw, vt[2] / nw, vt[3] / nw);
     if (nw) fprintf(stderr, "[timing] waves %zu  total avg %.0f max %.0f | stream wait %.0f | drain %.0f (%.1f calls) | filter+L2 %.0f | passes %.1f  (s_memtime ticks, 100 MHz)\n",
                     nw, sum[0] / nw, mx0, sum[1] / nw, sum[2] / nw, sum[5] / nw, sum[3] / nw, sum[4] / nw);

@@ -132,6 +132,8 @@ __device__ __forceinline__ uint32_t walk_step(const DevTables &T, uint32_t ref, 
 // in text order, are looked up in kg_keys/kg_vals, and every step of the walk goes through the unit-keyed hashed edges.
 // QI: queue entries carry the K-gram index and the left neighbour's class (TileCtx::pos16): no text window is read for them.
 // SHORTS = false: the dictionary has no keyword shorter than K (compiled out: the config-2 form is register- and SGPR-tight)
+// (A second instance with one batch, for drains of 64 or fewer candidates, was measured: the drains got 28 % shorter and the
+// kernel 2 % slower -- EXPERIMENTS.md, "start-up, neighbour classes, one verification batch".)
 template <int K, bool RANGE, bool HASHK = false, bool QI = false, bool SHORTS = true>
 __device__ __forceinline__ void verify_multi(TileCtx &c, uint32_t head, uint32_t n_cand) {
     constexpr int NB = kVerifyBatches;
@@ -564,6 +566,10 @@ template <int K, bool RANGE, bool WIDE, bool SPLIT, bool HASHK = false, bool PK 
           bool BIG = false>
 __global__ __launch_bounds__(kTileBlock) void k_ac_tile(DevTables T, TileLaunch L) {
     static_assert(!BIG || L2, "the large second level is a form of the L2 kernel");
+#ifdef ACGPU_TIMING
+    const unsigned long long tm_entry = clock64(); // the kernel's first instruction: the start-up ends at the first filtered tile
+    unsigned long long tm_startup = 0;
+#endif
     const bool has_short = SHORTS && T.has_short != 0; // (SHORTS = false: the launcher knows there is none)
     // the filter rows are STATIC LDS (offset 0, so a scaled row index is the ds_read address with nothing to add);
     // the candidate queues are the dynamic part behind it
@@ -571,22 +577,38 @@ __global__ __launch_bounds__(kTileBlock) void k_ac_tile(DevTables T, TileLaunch 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ uint32_t wg_words[kFtWords]; // fused tail: the workgroup's number, its slice's fill mark, its waves' records
     const bool FT = !SPLIT && L.fused_tail != 0; // kernel-uniform
-    if (FT && threadIdx.x == 0) ft_take_number(L, wg_words); // (the answer is there when the tables are: the barrier below)
+    // Start-up: every memory round trip that does not depend on another goes out at once.  Every thread loads its share of the
+    // filter rows and of the Bloom words into registers in one batch (at most 7 x 16 bytes at 1024 threads; dead before the main
+    // loop), and behind them thread 0 asks for the workgroup's number (an atomic on one address for the whole grid).  The number
+    // reaches the waves through a barrier of its own, so that the carry and the first tile group are asked for while fifteen of
+    // the sixteen waves' tables are still on their way; the tables go to LDS behind those loads, and the second barrier ends the
+    // start-up.  (The atomic goes LAST in thread 0's batch: the compiler reads an atomic's result back at once -- it aggregates
+    // the wave's lanes, v_readfirstlane -- and a wait in front of the table loads would put the two round trips in series.)
     const unsigned char *rows8 = reinterpret_cast<const unsigned char *>(rows32);
     uint32_t *cand_all = reinterpret_cast<uint32_t *>(smem);
-    { // the filter rows, 16 bytes per thread and step (the kernel does not stream before this is done)
-        const uint32_t n4 = T.filt_words / 4;
-        const uint4 *src4 = reinterpret_cast<const uint4 *>(T.filt_bits);
-        uint4 *dst4 = reinterpret_cast<uint4 *>(rows32);
-        for (uint32_t i = threadIdx.x; i < n4; i += blockDim.x) dst4[i] = src4[i];
-        for (uint32_t i = n4 * 4 + threadIdx.x; i < T.filt_words; i += blockDim.x) rows32[i] = T.filt_bits[i];
+    constexpr uint32_t kRowsPer = (sizeof(rows32) / 16 + kTileBlock - 1) / kTileBlock;               // 16-byte loads per thread: rows
+    constexpr uint32_t kBloomPer = (L2 && !BIG) ? (kL2Words / 4 + kTileBlock - 1) / kTileBlock : 0u; // ... Bloom words
+    const uint32_t n4 = T.filt_words / 4;
+    const uint4 *src4 = reinterpret_cast<const uint4 *>(T.filt_bits);
+    uint4 tab[kRowsPer + kBloomPer];
+#pragma unroll
+    for (uint32_t q = 0; q < kRowsPer; ++q) {
+        const uint32_t i = threadIdx.x + q * blockDim.x;
+        tab[q] = make_uint4(0u, 0u, 0u, 0u);
+        if (i < n4) tab[q] = src4[i];
+    }
+#pragma unroll
+    for (uint32_t q = 0; q < kBloomPer; ++q) { // (the table has kL2Words words: a clamped index, so that the load is unconditional)
+        const uint32_t i = threadIdx.x + q * blockDim.x;
+        tab[kRowsPer + q] = reinterpret_cast<const uint4 *>(T.l2_bloom)[min(i, (uint32_t)kL2Words / 4 - 1)];
+    }
+    if (FT) { // kernel-uniform (the forms without the fused tail take blockIdx.x: no number, no barrier for it)
+        if (threadIdx.x == 0) ft_take_number(L, wg_words);
+        __syncthreads();
     }
     // LUT forms with the scalar filter: the class table as pages behind the rows, when it fits (acgpu_build.cpp 7b)
     const uint32_t pg_off = (T.filt_words * 4u + 15u) & ~15u;
     const bool cls_lds = !RANGE && !PK && T.cls_pages != nullptr && (uint64_t)pg_off + T.cls_pages_bytes <= sizeof(rows32) && !ACGPU_DBG(L, 1u << 15); // (ablation build, tile_debug bit 32768: the class table in global memory on the same tables)
-    if (cls_lds)
-        for (uint32_t i = threadIdx.x; i < T.cls_pages_bytes / 16; i += blockDim.x)
-            reinterpret_cast<uint4 *>(rows32)[pg_off / 16 + i] = reinterpret_cast<const uint4 *>(T.cls_pages)[i];
     const unsigned char *pg8 = rows8 + pg_off;
     constexpr int D2 = K + 2 < 6 ? K + 2 : 6; // depth of the second-level filter
     // tile geometry of this variant (the names hide the namespace-scope defaults)
@@ -606,11 +628,8 @@ __global__ __launch_bounds__(kTileBlock) void k_ac_tile(DevTables T, TileLaunch 
     unsigned char *tb = smem + kWavesPerBlock * kL2Cap * 6 + wave_in_block * kTbBytes;
     uint16_t *fresh = reinterpret_cast<uint16_t *>(smem + kWavesPerBlock * (kL2Cap * 6 + kTbBytes)) + wave_in_block * kL2Fresh;
     uint32_t *bloom = reinterpret_cast<uint32_t *>(smem + (kTileBlock / kWave) * kL2WaveBytes);
-    if (L2 && !BIG) for (uint32_t i = threadIdx.x; i < kL2Words / 4; i += blockDim.x)
-        reinterpret_cast<uint4 *>(bloom)[i] = reinterpret_cast<const uint4 *>(T.l2_bloom)[i];
     uint16_t *bigl = reinterpret_cast<uint16_t *>(bloom) + wave_in_block * kBigFresh; // BIG: the tile's candidates, text order
     static_assert(kL2Words % 4 == 0, "Bloom words are copied 16 bytes at a time");
-    __syncthreads();
 
     const uint32_t lane = lane_id();
     // (the fused tail orders the workgroups by their start, not by blockIdx: the number names span, slice and counters)
@@ -634,7 +653,6 @@ __global__ __launch_bounds__(kTileBlock) void k_ac_tile(DevTables T, TileLaunch 
 
     const uint32_t first_region = wave_global * L.regions_per_wave;
     const bool has_work = first_region < L.n_regions; // wave-uniform
-    if (!has_work && !FT) return; // (fused tail: a wave without a region passes through the loop and joins the workgroup's tail)
     const uint32_t last_region = min(first_region + L.regions_per_wave, L.n_regions);
     const uint32_t base8 = L.own_begin & ~7u;
     const uint32_t R = L.region_units;
@@ -680,6 +698,30 @@ __global__ __launch_bounds__(kTileBlock) void k_ac_tile(DevTables T, TileLaunch 
             for (int u = 0; u < kAcVec; ++u)
                 nxt[d][u] = stream_load(hay, min(tile + d * kAcTileUnits + lane * kAcLaneUnits + u * 8, last_vec));
     }
+    { // the tables, from the registers to LDS (a block of fewer than kTileBlock threads copies the rest in the loops)
+        uint4 *dst4 = reinterpret_cast<uint4 *>(rows32);
+#pragma unroll
+        for (uint32_t q = 0; q < kRowsPer; ++q) {
+            const uint32_t i = threadIdx.x + q * blockDim.x;
+            if (i < n4) dst4[i] = tab[q];
+        }
+        for (uint32_t i = threadIdx.x + kRowsPer * blockDim.x; i < n4; i += blockDim.x) dst4[i] = src4[i];
+        for (uint32_t i = n4 * 4 + threadIdx.x; i < T.filt_words; i += blockDim.x) rows32[i] = T.filt_bits[i];
+#pragma unroll
+        for (uint32_t q = 0; q < kBloomPer; ++q) {
+            const uint32_t i = threadIdx.x + q * blockDim.x;
+            if (i < (uint32_t)kL2Words / 4) reinterpret_cast<uint4 *>(bloom)[i] = tab[kRowsPer + q];
+        }
+        if (L2 && !BIG)
+            for (uint32_t i = threadIdx.x + kBloomPer * blockDim.x; i < (uint32_t)kL2Words / 4; i += blockDim.x)
+                reinterpret_cast<uint4 *>(bloom)[i] = reinterpret_cast<const uint4 *>(T.l2_bloom)[i];
+        // (LUT forms with the class table in LDS: a copy of its own, these forms are not the streaming-bound ones)
+        if (cls_lds)
+            for (uint32_t i = threadIdx.x; i < T.cls_pages_bytes / 16; i += blockDim.x)
+                reinterpret_cast<uint4 *>(rows32)[pg_off / 16 + i] = reinterpret_cast<const uint4 *>(T.cls_pages)[i];
+    }
+    __syncthreads();
+    if (!has_work && !FT) return; // (fused tail: a wave without a region passes through the loop and joins the workgroup's tail)
 
 #ifdef ACGPU_TIMING
     // instrumented build (tools/build_variant.sh timing -DACGPU_TIMING): where a wave's time goes, in s_memtime ticks
@@ -759,6 +801,7 @@ __global__ __launch_bounds__(kTileBlock) void k_ac_tile(DevTables T, TileLaunch 
             }
 #ifdef ACGPU_TIMING
             const unsigned long long tm_f0 = clock64();
+            if (tm_startup == 0) tm_startup = tm_f0 - tm_entry;
 #endif
             // positions a lane may report: inside the region, in the vector part of the buffer, with K units to their
             // left in the buffer.  Only groups at the edges of a region need the per-lane mask.
@@ -1199,6 +1242,7 @@ __global__ __launch_bounds__(kTileBlock) void k_ac_tile(DevTables T, TileLaunch 
     if (lane == 0 && L.d_timing)
     {
         for (int i = 0; i < 8; ++i) L.d_timing[(size_t)wave_global * 8 + i] = tm[i];
+        L.d_timing[(size_t)wave_global * 8 + 4] = tm[4] | (tm_startup << 32); // (passes: far fewer than 2^32)
         L.d_timing[(size_t)wave_global * 8 + 6] = c.vt[0] | (c.vt[1] << 32);
         L.d_timing[(size_t)wave_global * 8 + 7] = c.vt[2] | (c.vt[3] << 32);
     }
