@@ -6,6 +6,7 @@
 #include <atomic>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <cctype>
 #include <pthread.h>
 #include <sched.h>
@@ -13,9 +14,11 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <thread>
 #include <vector>
 
+#include "acgpu_forms.h"
 #include "acgpu_host.h"
 #include "acgpu_internal.h"
 #include "acgpu_kernels.h"
@@ -291,7 +294,7 @@ int slot_on_device(const CallRecord &r, unsigned long long **d_slot) {
 int close_call(CallRecord &r, CallForm form, const char *kname, uint64_t scanned, bool done_is_ev2 = false) {
     r.form = form;
     r.scanned = scanned;
-    std::snprintf(r.kname, sizeof(r.kname), "%s", kname);
+    std::snprintf(r.kname, sizeof(r.kname), "%.*s", (int)sizeof(r.kname) - 1, kname); // (the one cut: acgpu_profile::scan_kernel holds 63 characters)
     r.done_is_ev2 = done_is_ev2;
     if (r.done && !done_is_ev2) HIP_TRY(hipEventRecord(r.done, r.stream));
     return ACGPU_OK;
@@ -353,7 +356,7 @@ int enqueue_states(acgpu_automaton *a, DeviceState &d, CallRecord &r, uint32_t h
     const uint64_t chunks = (span + (1ull << S.chunk_log2) - 1) >> S.chunk_log2;
     S.n_waves = (uint32_t)((chunks + 63) / 64);
     S.n_chunks = (uint32_t)chunks;
-    if (tunables().tile_debug & (1ll << 40)) return ACGPU_E_NOMEM; // (tests: the allocation "fails", the caller falls back)
+    if (tunables().tile_debug & kSelAllocFails) return ACGPU_E_NOMEM; // (tests: the allocation "fails", the caller falls back)
     if ((rc = d.statebuf.ensure((((size_t)S.n_waves * 64) << S.chunk_log2) * 4 + 64))) return rc;
     if ((rc = d.chunk_counts.ensure((size_t)S.n_chunks * 4))) return rc;
     if ((rc = d.offsets.ensure((size_t)S.n_chunks * 8))) return rc;
@@ -443,7 +446,7 @@ struct AllScan {
     uint64_t slice_slots = 0;
     const uint32_t *id_map = nullptr;
     int by_start = 0;
-    const char *kname = "";
+    char kname[kFormNameBytes] = ""; // the whole name (close_call cuts it to the ABI's field)
     uint64_t scanned = 0;
 };
 
@@ -552,45 +555,42 @@ int timing_report_tile(const TileLaunch &L, hipStream_t stream) {
 }
 #endif
 
-// WHOLEWORD (fold-consistent tables): the WholeWord tile kernels over regions -- run starts instead of K-gram candidates, ranks
-// by match start, halos of 1 unit on the left and max_len + 1 on the right.
-int setup_ww_scan(acgpu_automaton *a, DeviceState &d, CallRecord &r, AllScan &A) {
-    const HostTables &t = a->t;
+// The region lay-out of a tile scan (setup_ww_scan, setup_tile_scan; L.block and L.debug are set): regions of sizes[i].units
+// when the shard has at least sizes[i].per_wave units for each of `waves` waves (the last entry: any shard), on long shards
+// (balance_from units per wave) the size that fills the waves evenly (balanced_region_units: r_min, prefer) -- or the tunable
+// region_units -- rounded to whole tile groups and laid out from the shard's 16-byte aligned start; a wave scans regions_per_wave
+// consecutive regions, the grid holds the waves that own one; one scratch slice and slot counter per workgroup (a slice that
+// fills up: the redo takes one slice; kSelOneCounter: A/B); the region counts, their offsets and the prefix sum's words.
+struct RegionSize {
+    uint64_t units, per_wave;
+};
+int lay_out_regions(DeviceState &d, const CallRecord &r, AllScan &A, TileLaunch &L, uint64_t waves, std::initializer_list<RegionSize> sizes,
+                    uint64_t balance_from, uint64_t r_min, uint64_t prefer) {
     const acgpu_shard *sh = &r.shard;
-    const DevTables &T = *A.T;
-    const uint64_t own_len = sh->own_end - sh->own_begin;
+    const uint64_t own_len = sh->own_end - sh->own_begin, g = tile_group_units(), waves_per_block = (uint64_t)L.block / 64;
+    const uint64_t base8 = sh->own_begin & ~7ull;
     int rc;
-    TileLaunch L{};
-    L.block = tile_block_threads();
-    const int waves_per_block = L.block / 64;
-    // regions as large as still gives every wave one (fewer forced drains: 65536 against 16384 units -2 % at config 5's share)
-    const uint64_t ww_waves = (uint64_t)d.n_cu * ww_blocks_per_cu() * waves_per_block;
-    uint64_t R = tunables().region_units > 0 ? (uint64_t)tunables().region_units
-                 : own_len >= 65536 * ww_waves ? 65536 : own_len >= 32768 * ww_waves ? 32768 : 16384;
-    if (tunables().region_units <= 0 && own_len >= 32768 * ww_waves) { // long shards: regions that fill the waves evenly
-        const uint64_t Rb = balanced_region_units(sh->own_end - (sh->own_begin & ~7ull), ww_waves, tile_group_units(), 16384, 16, 65536);
+    uint64_t R = (uint64_t)tunables().region_units;
+    if (tunables().region_units <= 0) {
+        for (const RegionSize &z : sizes)
+            if (own_len >= z.per_wave * waves) { R = z.units; break; }
+        const uint64_t Rb = own_len >= balance_from * waves ? balanced_region_units(sh->own_end - base8, waves, g, r_min, 16, prefer) : 0;
         if (Rb) R = Rb;
     }
-    { const uint64_t g = tile_group_units(); R = std::max<uint64_t>(g, (R + g - 1) / g * g); }
+    R = std::max<uint64_t>(g, (R + g - 1) / g * g);
     L.region_units = (uint32_t)R;
-    const uint64_t base8 = sh->own_begin & ~7ull;
     L.n_regions = (uint32_t)((sh->own_end - base8 + R - 1) / R);
-    L.regions_per_wave = (uint32_t)((L.n_regions + ww_waves - 1) / ww_waves);
+    L.regions_per_wave = (uint32_t)((L.n_regions + waves - 1) / waves);
     const uint64_t waves_used = ((uint64_t)L.n_regions + L.regions_per_wave - 1) / L.regions_per_wave;
     L.grid = (int)((waves_used + waves_per_block - 1) / waves_per_block);
     A.perm_base = (uint32_t)base8;
-    A.by_start = 1;
     L.d_hay = sh->d_hay;
     L.n_units = (uint32_t)sh->n_units;
     L.own_begin = (uint32_t)sh->own_begin;
     L.own_end = (uint32_t)sh->own_end;
     L.cap = A.scratch_cap;
-    L.lds_bytes = ww_lds_bytes(L.block, T);
-    L.debug = (uint32_t)tunables().tile_debug | (tunables().force_kernel == 1 ? 256u : 0u); // 256: trie-walk verification
     L.d_overflow = A.overflow_word;
-    // one scratch slice and slot counter per workgroup (config 5 emits 15 M records per shard: 60 k reservations that one
-    // counter would serve at under 100 per microsecond); a slice that fills up -> redo with one slice
-    if (!A.fused_only && L.grid > 1 && !(L.debug & 16384u)) {
+    if (!A.fused_only && L.grid > 1 && !(L.debug & kSelOneCounter)) {
         A.n_slices = (uint32_t)std::min<int>(L.grid, kMaxSlices);
         A.slice_slots = A.scratch_cap / A.n_slices;
     }
@@ -602,12 +602,57 @@ int setup_ww_scan(acgpu_automaton *a, DeviceState &d, CallRecord &r, AllScan &A)
     L.d_scratch = (ScratchRec *)d.scratch.p;
     L.d_counter = A.counters;
     L.d_region_counts = (uint32_t *)d.chunk_counts.p;
+    return ACGPU_OK;
+}
+
+// The launch of a tile scan and what it leaves for the ordering stage.  own_events: one kernel scans, and a profiled call takes
+// that kernel's own dispatch timestamps (no marker packets around it); fused: the scan is the call's only kernel, its end the call's.
+template <class Launch>
+int launch_regions(TileLaunch &L, CallRecord &r, AllScan &A, bool own_events, bool fused, bool ww, Launch &&launch) {
+    int rc;
+#ifdef ACGPU_TIMING
+    if ((rc = timing_arm(L, r.stream))) return rc;
+#endif
+    if (own_events && r.profiled) {
+        L.ev_start = r.ev[0];
+        L.ev_stop = r.ev[1];
+    }
+    if (own_events && fused) L.ev_stop = (r.profiled || r.done) ? r.ev[2] : nullptr;
+    if ((rc = launch())) return rc;
+#ifdef ACGPU_TIMING
+    if (!r.done && own_events && (rc = ww ? timing_report_ww(L, fused, r.stream) : timing_report_tile(L, r.stream))) return rc;
+#else
+    (void)ww;
+#endif
+    A.n_chunks = L.n_regions;
+    A.chunk_units = L.region_units;
+    A.scanned = r.shard.own_end - r.shard.own_begin;
+    return ACGPU_OK;
+}
+
+// WHOLEWORD (fold-consistent tables): the WholeWord tile kernels over regions -- run starts instead of K-gram candidates, ranks
+// by match start, halos of 1 unit on the left and max_len + 1 on the right.
+int setup_ww_scan(acgpu_automaton *a, DeviceState &d, CallRecord &r, AllScan &A) {
+    const HostTables &t = a->t;
+    const acgpu_shard *sh = &r.shard;
+    const DevTables &T = *A.T;
+    int rc;
+    TileLaunch L{};
+    L.block = tile_block_threads();
+    L.debug = (uint32_t)tunables().tile_debug | (tunables().force_kernel == 1 ? (uint32_t)kSelWwTrieWalk : 0u);
+    // regions as large as still gives every wave one (fewer forced drains: 65536 against 16384 units -2 % at config 5's share);
+    // one scratch slice per workgroup: config 5 emits 15 M records per shard, 60 k reservations that one counter would serve at
+    // under 100 per microsecond
+    const uint64_t ww_waves = (uint64_t)d.n_cu * ww_blocks_per_cu() * (L.block / 64);
+    if ((rc = lay_out_regions(d, r, A, L, ww_waves, {{65536, 65536}, {32768, 32768}, {16384, 0}}, 32768, 16384, 65536))) return rc;
+    A.by_start = 1;
+    const uint64_t R = L.region_units, base8 = A.perm_base;
     // region-local record slots (a region of R units holds at most R/2 + 1 words): no slot reservations in the scan, and a
-    // coalesced copy instead of the permutation (tunable tile_debug bit 134217728: the scratch slices + k_permute, for A/B)
+    // coalesced copy instead of the permutation (kSelWwPermute: the scratch slices + k_permute, for A/B)
     L.d_region_recs = nullptr;
     L.region_cap = (uint32_t)(R / 2 + 1);
     const uint64_t ww_rec_bytes = (uint64_t)L.n_regions * L.region_cap * 12;
-    bool direct = !(tunables().tile_debug & 134217728) && ww_rec_bytes <= (24ull << 30);
+    bool direct = !(tunables().tile_debug & kSelWwPermute) && ww_rec_bytes <= (24ull << 30);
     // The fused tail of k_ww_pp (TileLaunch::fused_tail, ft_total16): no counts, prefix sums or copy pass behind the scan -- a
     // wave's records go to its own area and, when the workgroups with lower numbers are done, from there to their final
     // place.  (Tunable ww_ramp_pm: spans that grow with the workgroup's number, so that copies would run while later
@@ -617,13 +662,15 @@ int setup_ww_scan(acgpu_automaton *a, DeviceState &d, CallRecord &r, AllScan &A)
     bool fused = false;
     int block_ft = L.block;
     uint64_t total16 = 0, G = 0, area_recs = 0;
-    if (direct && !A.fused_only && !(tunables().tile_form & 2) && ww_pp_serves(T, L)) {
+    const WwForm whole = choose_ww_form(T, L, L.block); // (k_ww_pp is the kernel that has the fused tail)
+    if (direct && !A.fused_only && !(tunables().tile_form & 2) && whole.pp) {
         // (tunable ww_block: workgroups of fewer waves, two to a CU when their LDS allows -- A/B)
         const int64_t wb = tunables().ww_block;
         block_ft = (wb >= 64 && wb <= 1024 && wb % 64 == 0) ? (int)wb : L.block;
         const uint64_t wpb = (uint64_t)block_ft / 64;
         // (two workgroups: when each needs at most half the LDS, and for the 16-unit form only -- the 32-unit form's registers allow four waves per SIMD)
-        const uint64_t per_cu = wb > 0 && t.max_len <= 16 && ww_pp_lds_total(T, L, block_ft) <= 80 * 1024 ? 2 : 1;
+        // (block_ft <= L.block: k_ww_pp serves there as well, and the form's LDS is k_ww_pp's)
+        const uint64_t per_cu = wb > 0 && t.max_len <= 16 && choose_ww_form(T, L, block_ft).lds + ww_pp_static_lds(whole.fold) <= 80 * 1024 ? 2 : 1;
         const uint64_t tiles = (sh->own_end - base8 + 511) / 512;
         total16 = (tiles + wpb - 1) / wpb;
         G = std::min<uint64_t>((uint64_t)d.n_cu * per_cu, total16);
@@ -632,8 +679,8 @@ int setup_ww_scan(acgpu_automaton *a, DeviceState &d, CallRecord &r, AllScan &A)
     }
     if (direct) {
         // (about 6 bytes per haystack unit: on a device that cannot spare them the call falls back to the scratch slices +
-        // k_permute instead of failing; tunable tile_debug bit 2^40: the allocation "fails", for the test of that path)
-        rc = (tunables().tile_debug & (1ll << 40)) ? ACGPU_E_NOMEM : d.ww_recs.ensure((fused ? area_recs * 12 : ww_rec_bytes) + 64);
+        // k_permute instead of failing; kSelAllocFails: the allocation "fails", for the test of that path)
+        rc = (tunables().tile_debug & kSelAllocFails) ? ACGPU_E_NOMEM : d.ww_recs.ensure((fused ? area_recs * 12 : ww_rec_bytes) + 64);
         if (rc == ACGPU_E_NOMEM) direct = fused = false;
         else if (rc != ACGPU_OK) return rc;
     }
@@ -652,73 +699,29 @@ int setup_ww_scan(acgpu_automaton *a, DeviceState &d, CallRecord &r, AllScan &A)
     } else {
         HIP_TRY(hipMemsetAsync(d.chunk_counts.p, 0, (size_t)L.n_regions * 4, r.stream));
     }
-#ifdef ACGPU_TIMING
-    if ((rc = timing_arm(L, r.stream))) return rc;
-#endif
-    if (r.profiled) { // (the kernel's own dispatch timestamps: no marker packets around it)
-        L.ev_start = r.ev[0];
-        L.ev_stop = r.ev[1];
-    }
-    if (fused) L.ev_stop = (r.profiled || r.done) ? r.ev[2] : nullptr; // the scan is the call's only kernel: its end is the call's
-    HIP_TRY(launch_ww_tile(T, L, r.stream, &A.kname));
-#ifdef ACGPU_TIMING
-    if (!r.done && (rc = timing_report_ww(L, fused, r.stream))) return rc;
-#endif
-    A.n_chunks = L.n_regions;
-    A.chunk_units = L.region_units;
-    A.scanned = own_len;
-    return ACGPU_OK;
+    const WwForm form = choose_ww_form(T, L, L.block);
+    L.lds_bytes = form.lds;
+    ww_form_name(form, A.kname);
+    return launch_regions(L, r, A, true, fused, true, [&]() -> int {
+        HIP_TRY(launch_ww_tile(T, L, form, r.stream));
+        return ACGPU_OK;
+    });
 }
 
 // ALL: the position-parallel K-gram tile kernel (fused, or the split form: filter + verification) over regions.
 int setup_tile_scan(acgpu_automaton *a, DeviceState &d, CallRecord &r, AllScan &A) {
-    const acgpu_shard *sh = &r.shard;
-    const uint64_t own_len = sh->own_end - sh->own_begin;
     int rc;
     TileLaunch L{};
     L.block = tile_block_threads();
+    L.debug = (uint32_t)tunables().tile_debug;
     const int waves_per_block = L.block / 64;
     // regions of 16384 units, or 32768 when that still leaves every wave two of them (fewer forced drains: -1.1 % at
     // config 2 in interleaved A/B; 65536 was no better)
-    uint64_t R = tunables().region_units > 0 ? (uint64_t)tunables().region_units
-                 : own_len >= 2ull * 32768 * d.n_cu * waves_per_block ? 32768 : 16384;
-    if (tunables().region_units <= 0 && own_len >= 2ull * 16384 * d.n_cu * waves_per_block) { // long shards: regions that fill the waves evenly
-        const uint64_t Rb = balanced_region_units(sh->own_end - (sh->own_begin & ~7ull), (uint64_t)d.n_cu * waves_per_block, tile_group_units(),
-                                                  12288, 16, 32768);
-        if (Rb) R = Rb;
-    }
-    { const uint64_t g = tile_group_units(); R = std::max<uint64_t>(g, (R + g - 1) / g * g); }
-    L.region_units = (uint32_t)R;
-    const uint64_t base8 = sh->own_begin & ~7ull; // regions are laid out from the 16-byte aligned start
-    L.n_regions = (uint32_t)((sh->own_end - base8 + R - 1) / R);
-    const uint64_t waves_max = (uint64_t)d.n_cu * waves_per_block;
-    L.regions_per_wave = (uint32_t)((L.n_regions + waves_max - 1) / waves_max);
+    if ((rc = lay_out_regions(d, r, A, L, (uint64_t)d.n_cu * waves_per_block, {{32768, 2 * 32768}, {16384, 0}}, 2 * 16384, 12288, 32768))) return rc;
+    const uint64_t R = L.region_units;
     const uint64_t waves_used = ((uint64_t)L.n_regions + L.regions_per_wave - 1) / L.regions_per_wave;
-    L.grid = (int)((waves_used + waves_per_block - 1) / waves_per_block);
-    A.perm_base = (uint32_t)base8;
     A.id_map = d.T.rterm;
-    L.d_hay = sh->d_hay;
-    L.n_units = (uint32_t)sh->n_units;
-    L.own_begin = (uint32_t)sh->own_begin;
-    L.own_end = (uint32_t)sh->own_end;
-    L.cap = A.scratch_cap;
-    L.lds_bytes = tile_lds_bytes(d.T, L.block);
-    L.debug = (uint32_t)tunables().tile_debug;
-    L.d_overflow = A.overflow_word;
-    // one scratch slice and slot counter per workgroup (the redo after an overflow takes one slice)
-    if (!A.fused_only && L.grid > 1 && !(L.debug & 16384u)) { // 16384: A/B, one counter
-        A.n_slices = (uint32_t)std::min<int>(L.grid, kMaxSlices);
-        A.slice_slots = A.scratch_cap / A.n_slices;
-    }
-    L.n_slices = A.n_slices;
-    L.slice_slots = (uint32_t)A.slice_slots;
     L.wg_sums = 0;
-    if ((rc = d.chunk_counts.ensure((size_t)L.n_regions * 4))) return rc;
-    if ((rc = d.offsets.ensure((size_t)L.n_regions * 8))) return rc;
-    if ((rc = d.scan_tmp.ensure(((size_t)L.n_regions / 2048 + 2) * 8))) return rc;
-    L.d_scratch = (ScratchRec *)d.scratch.p;
-    L.d_counter = A.counters;
-    L.d_region_counts = (uint32_t *)d.chunk_counts.p;
     // (every region's count is written by the wave that owns the region: no memset)
     bool split = !A.fused_only && use_split_form(d.T);
     if (split) {
@@ -749,9 +752,9 @@ int setup_tile_scan(acgpu_automaton *a, DeviceState &d, CallRecord &r, AllScan &
     }
     // one finalize launch instead of three (prefix-sum kernels + permute) when a scratch slice is a workgroup: the scan
     // kernel leaves every workgroup's record count next to its slot counter and the permute pass (k_permute_wg) derives
-    // its offsets from those and the region counts of its own workgroup.  (tunable tile_debug bit 262144: the old way)
+    // its offsets from those and the region counts of its own workgroup.  (kSelFinalizeLaunches: the old way)
     const bool fused_finalize = !split && A.n_slices == (uint32_t)L.grid && L.grid <= kMaxSlices &&
-                                (uint64_t)waves_per_block * L.regions_per_wave <= kPermuteWgRegions && !(L.debug & 262144u);
+                                (uint64_t)waves_per_block * L.regions_per_wave <= kPermuteWgRegions && !(L.debug & kSelFinalizeLaunches);
     if (fused_finalize) A.order = AllScan::Order::PermuteWg;
     L.wg_sums = fused_finalize ? 1u : 0u;
     A.regions_per_wg = (uint32_t)waves_per_block * L.regions_per_wave;
@@ -763,29 +766,22 @@ int setup_tile_scan(acgpu_automaton *a, DeviceState &d, CallRecord &r, AllScan &
         L.wg_sums = 0; // (the workgroups' sums go through their own LDS)
         if ((rc = set_fused_tail(L, r, A, A.id_map))) return rc;
     }
-#ifdef ACGPU_TIMING
-    if ((rc = timing_arm(L, r.stream))) return rc;
-#endif
-    if (split) {
-        if (r.profiled) HIP_TRY(hipEventRecord(r.ev[0], r.stream));
-        HIP_TRY(launch_ac_filter(d.T, L, r.stream, &A.kname));
-        if (r.profiled) HIP_TRY(hipEventRecord(r.ev[1], r.stream)); // the verification is accounted with the ordering
-        HIP_TRY(launch_ac_verify(d.T, L, r.stream));
-    } else {
-        if (r.profiled) { // (the kernel's own dispatch timestamps: no marker packets around it)
-            L.ev_start = r.ev[0];
-            L.ev_stop = r.ev[1];
+    // the kernel's form, once: its dynamic LDS and its name (the second level's predicate reads L.region_units and L.debug)
+    const std::optional<TileForm> form = choose_tile_form(d.T, L, split);
+    if (!form) HIP_TRY(hipErrorInvalidValue);
+    L.lds_bytes = form->lds;
+    tile_form_name(*form, A.kname);
+    return launch_regions(L, r, A, !split, fused, false, [&]() -> int {
+        if (split) {
+            if (r.profiled) HIP_TRY(hipEventRecord(r.ev[0], r.stream));
+            HIP_TRY(launch_ac_filter(d.T, L, *form, r.stream));
+            if (r.profiled) HIP_TRY(hipEventRecord(r.ev[1], r.stream)); // the verification is accounted with the ordering
+            HIP_TRY(launch_ac_verify(d.T, L, r.stream));
+        } else {
+            HIP_TRY(launch_ac_tile(d.T, L, *form, r.stream));
         }
-        if (fused) L.ev_stop = (r.profiled || r.done) ? r.ev[2] : nullptr; // the scan is the call's only kernel: its end is the call's
-        HIP_TRY(launch_ac_tile(d.T, L, r.stream, &A.kname));
-    }
-#ifdef ACGPU_TIMING
-    if (!r.done && !split && (rc = timing_report_tile(L, r.stream))) return rc;
-#endif
-    A.n_chunks = L.n_regions;
-    A.chunk_units = L.region_units;
-    A.scanned = own_len;
-    return ACGPU_OK;
+        return ACGPU_OK;
+    });
 }
 
 // ALL: the general DFA chunk scan (any alphabet, any keyword lengths).
@@ -800,8 +796,8 @@ int setup_dfa_scan(acgpu_automaton *a, DeviceState &d, CallRecord &r, AllScan &A
     L.grid = d.n_cu * (int)std::max<int64_t>(1, tunables().blocks_per_cu);
     // tile_debug bit 2^43: the one-chain kernel of rounds 1-3 (A/B); bit 2^45 (ablation build): no lookups in global memory
     L.debug = (uint32_t)((tunables().tile_debug >> 43) & 5);
-    if (sh->n_units < 64) L.debug |= 1u; // (k_ac_dfa takes the buffer's last vector whole: the old kernel reads unit by unit)
-    const uint64_t lanes = (uint64_t)L.grid * L.block * (uint64_t)((L.debug & 1u) ? 1 : std::max(1, scan_chains(d.T)));
+    if (sh->n_units < 64) L.debug |= kScanOneChain; // (k_ac_dfa takes the buffer's last vector whole: the old kernel reads unit by unit)
+    const uint64_t lanes = (uint64_t)L.grid * L.block * (uint64_t)((L.debug & kScanOneChain) ? 1 : std::max(1, scan_chains(d.T)));
     uint64_t C = tunables().chunk_units > 0 ? (uint64_t)tunables().chunk_units
                                             : std::max<uint64_t>({(own_len + lanes - 1) / lanes, 256, 16ull * halo});
     C = std::max<uint32_t>(8, round_up8(C));
@@ -821,8 +817,11 @@ int setup_dfa_scan(acgpu_automaton *a, DeviceState &d, CallRecord &r, AllScan &A
     L.d_scratch = (ScratchRec *)d.scratch.p;
     L.d_counter = A.counters;
     L.d_chunk_counts = (uint32_t *)d.chunk_counts.p;
+    const std::optional<DfaForm> form = choose_dfa_form(d.T, L);
+    if (!form) HIP_TRY(hipErrorInvalidValue);
+    dfa_form_name(*form, A.kname);
     if (r.profiled) HIP_TRY(hipEventRecord(r.ev[0], r.stream));
-    HIP_TRY(launch_ac_scan(d.T, L, r.stream, &A.kname));
+    HIP_TRY(launch_ac_scan(d.T, L, *form, r.stream));
     if (r.profiled) HIP_TRY(hipEventRecord(r.ev[1], r.stream));
     A.n_chunks = L.n_chunks;
     A.chunk_units = L.chunk_units;

@@ -6,8 +6,6 @@
 
 namespace acgpu {
 
-constexpr int kWave = 64;
-
 __device__ __forceinline__ uint32_t lane_id() { return __lane_id(); }
 
 __device__ __forceinline__ uint64_t lanemask_lt() {

@@ -10,6 +10,7 @@
 
 namespace acgpu {
 
+constexpr int kWave = 64; // gfx950 runs these kernels in wave64
 constexpr uint64_t kEmptyKey = ~0ull;
 constexpr uint32_t kRefHasChildren = 0x80000000u, kRefTerminal = 0x40000000u, kRefIdMask = 0x00ffffffu;
 constexpr uint32_t kRefHintShift = 24, kRefHintMask = 0x3fu; // class+1 of an only child, 0 = no hint

@@ -27,11 +27,15 @@ struct ScanLaunch {
     uint32_t *d_chunk_counts;      // n_chunks entries
     int grid, block;
     size_t lds_bytes;
-    uint32_t debug; // 1: the one-chain kernel (k_ac_scan_dense) where k_ac_dfa would run
+    uint32_t debug; // kScanOneChain: the one-chain kernel (k_ac_scan_dense) where k_ac_dfa would run
 };
+constexpr uint32_t kScanOneChain = 1u;
 
-// AC-all scan: dense (state x class table, hot rows in LDS) or sparse (hashed goto + fail links).
-hipError_t launch_ac_scan(const DevTables &t, const ScanLaunch &l, hipStream_t stream, const char **kernel_name);
+struct TileForm; // acgpu_forms.h: the kernel forms, their choosers (choose_tile_form ...) and their names
+struct WwForm;
+struct DfaForm;
+// AC-all scan: dense (state x class table, hot rows in LDS) or sparse (hashed goto + fail links); the form: choose_dfa_form
+hipError_t launch_ac_scan(const DevTables &t, const ScanLaunch &l, const DfaForm &f, hipStream_t stream);
 
 // Position-parallel AC-all scan (suffix K-gram filter in LDS + reversed-trie verification).  Ordering unit
 // ("chunk" for the permute pass) = one wave region of region_units owned units.
@@ -106,15 +110,27 @@ struct TileLaunch {
                     // at all (stream + reduce only), 8 = verification without the text-window load, 16 = without the
                     // K-gram node load, 32 = no record emission, 64 = no walk beyond the K-gram node, 128 = records
                     // not stored, 512 = one candidate in eight is kept, 4096 = the second-level filter passes everything.
-                    // Kernel selection (results stay right): 1024 = scalar filter instead of the packed one, 2048 = no
-                    // second-level filter, 16384 = one slot counter.  0 in production.
+                    // Kernel selection (results stay right): the bits of TileSelect.  0 in production.
 };
-hipError_t launch_ac_tile(const DevTables &t, const TileLaunch &l, hipStream_t stream, const char **kernel_name);
+// The kernel-selection bits of TileLaunch::debug and of the tunable tile_debug that host code tests (A/B and tests, which pass the
+// numbers; the ablation bits above are tested inside the kernels, through ACGPU_DBG)
+enum TileSelect : uint64_t {
+    kSelWwTrieWalk = 256,            // WholeWord: the trie-walk verification, which only k_ww_tile has (force_kernel 1 sets it)
+    kSelScalarFilter = 1024,         // the scalar filter instead of the packed one
+    kSelNoSecondLevel = 2048,        // no second-level filter
+    kSelOneCounter = 16384,          // one scratch slice and slot counter
+    kSelFinalizeLaunches = 262144,   // the prefix-sum kernels + k_permute instead of k_permute_wg
+    kSelWwPermute = 134217728,       // WholeWord: the scratch slices + k_permute instead of region-local records
+    kSelWwTile = 268435456,          // WholeWord: k_ww_tile where k_ww_pp would run
+    kSelWwNoPerfectHash = 1u << 29,  // k_ww_pp: the two-choice table behind the Bloom filter
+    kSelNoBigL2 = 1u << 30,          // the second level in LDS where the large one (BIG) would run
+    kSelAllocFails = 1ull << 40,     // the allocation of the region-local records / the state words "fails": the fallback's test
+};
+// (the form: choose_tile_form, with l.region_units and l.debug set; l.lds_bytes is the form's)
+hipError_t launch_ac_tile(const DevTables &t, const TileLaunch &l, const TileForm &f, hipStream_t stream);
 // split form: launch_ac_filter, then launch_ac_verify on the same stream (same TileLaunch)
-hipError_t launch_ac_filter(const DevTables &t, const TileLaunch &l, hipStream_t stream, const char **kernel_name);
+hipError_t launch_ac_filter(const DevTables &t, const TileLaunch &l, const TileForm &f, hipStream_t stream);
 hipError_t launch_ac_verify(const DevTables &t, const TileLaunch &l, hipStream_t stream);
-bool tile_split_supported(const DevTables &t);
-size_t tile_lds_bytes(const DevTables &t, int block_threads);
 int tile_block_threads();
 
 // exclusive prefix sum of d_counts[0..n) into d_offsets (uint64); d_tmp holds >= ceil(n/2048)+1 uint64
@@ -369,12 +385,8 @@ hipError_t launch_wwl_sequential(const DevTables &t, const uint16_t *d_hay, uint
 hipError_t launch_wwl_emit(const uint32_t *d_rs, const uint32_t *d_sel, const int32_t *d_mend, const int32_t *d_mid,
                            const uint64_t *d_offsets, uint32_t M, int record_kind, void *d_out, uint64_t cap, hipStream_t stream);
 
-uint32_t ww_fold_pages_in_lds(const DevTables &t); // 0: the fold table is not staged (case sensitive / too many pages)
-size_t ww_lds_bytes(int block_threads, const DevTables &t);
 int ww_blocks_per_cu();
-hipError_t launch_ww_tile(const DevTables &t, const TileLaunch &l, hipStream_t stream, const char **kernel_name);
-size_t ww_pp_lds_total(const DevTables &t, const TileLaunch &l, int block_threads); // k_ww_pp's LDS, static + dynamic, for a workgroup of that size
-bool ww_pp_serves(const DevTables &t, const TileLaunch &l); // launch_ww_tile would take k_ww_pp (the kernel that has the fused tail)
+hipError_t launch_ww_tile(const DevTables &t, const TileLaunch &l, const WwForm &f, hipStream_t stream); // (the form: choose_ww_form at l.block; l.lds_bytes is the form's)
 hipError_t launch_ww_sequential(const DevTables &t, const uint16_t *d_hay, uint32_t len, void *d_out, uint64_t cap,
                                 int record_kind, unsigned long long *d_counter, hipStream_t stream);
 } // namespace acgpu

@@ -13,9 +13,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
+#include <utility>
 
 #include "acgpu_device.h"
-#include "acgpu_kernels.h"
+#include "acgpu_forms.h"
 
 namespace acgpu {
 
@@ -341,15 +343,7 @@ __global__ __launch_bounds__(kScanBlock) void k_ac_dfa(DevTables T, ScanLaunch L
 }
 
 int scan_chains(const DevTables &t) { // chunks per lane of the dense chunk scan (the host sizes the chunks for it); 0: k_ac_dfa cannot run
-    return t.dense && t.n_states < (1u << 24) && t.n_cls < (1u << 22) && (uint64_t)t.n_states * t.n_cls < (1ull << 30) ? ACGPU_DFA_CHAINS : 0;
-}
-
-template <typename E, bool RANGE, bool GLOB>
-static hipError_t launch_ac_dfa(const DevTables &t, const ScanLaunch &l, hipStream_t stream) {
-    auto *k = &k_ac_dfa<E, RANGE, GLOB, ACGPU_DFA_CHAINS>;
-    if ((uint64_t)t.lds_entries * sizeof(E) > (uint64_t)kDfaLdsBytes) return hipErrorInvalidValue; // (lds_states_for keeps below it)
-    hipLaunchKernelGGL(k, dim3(l.grid), dim3(l.block), 0, stream, t, l);
-    return hipSuccess;
+    return dfa_chains_usable(t) ? ACGPU_DFA_CHAINS : 0;
 }
 
 __global__ __launch_bounds__(kScanBlock) void k_ac_scan_sparse(DevTables T, ScanLaunch L) {
@@ -360,47 +354,30 @@ __global__ __launch_bounds__(kScanBlock) void k_ac_scan_sparse(DevTables T, Scan
     ac_scan_body(T, L, step, wq);
 }
 
-hipError_t launch_ac_scan(const DevTables &t, const ScanLaunch &l, hipStream_t stream, const char **kernel_name) {
-    hipError_t e;
-    if (t.dense && scan_chains(t) > 0 && !(l.debug & 1u)) { // (debug bit 1: the one-chain kernel of rounds 1-3, for A/B)
-        const bool glob = (uint64_t)t.lds_entries < (uint64_t)t.n_states * t.n_cls;
-        const bool u16 = t.entry_bytes == 2;
-#define ACGPU_DFA_CASE(E, R, G, NAME)                                                    \
-    if (u16 == (sizeof(E) == 2) && (t.range_cls != 0) == R && glob == G) {               \
-        e = launch_ac_dfa<E, R, G>(t, l, stream);                                          \
-        if (e != hipSuccess) return e;                                                    \
-        if (kernel_name) *kernel_name = NAME;                                             \
-        return hipGetLastError();                                                         \
-    }
-        ACGPU_DFA_CASE(uint16_t, true, true, "k_ac_dfa<unsigned short, true, true>")
-        ACGPU_DFA_CASE(uint16_t, true, false, "k_ac_dfa<unsigned short, true, false>")
-        ACGPU_DFA_CASE(uint16_t, false, true, "k_ac_dfa<unsigned short, false, true>")
-        ACGPU_DFA_CASE(uint16_t, false, false, "k_ac_dfa<unsigned short, false, false>")
-        ACGPU_DFA_CASE(uint32_t, true, true, "k_ac_dfa<unsigned int, true, true>")
-        ACGPU_DFA_CASE(uint32_t, true, false, "k_ac_dfa<unsigned int, true, false>")
-        ACGPU_DFA_CASE(uint32_t, false, true, "k_ac_dfa<unsigned int, false, true>")
-        ACGPU_DFA_CASE(uint32_t, false, false, "k_ac_dfa<unsigned int, false, false>")
-#undef ACGPU_DFA_CASE
-    }
-    if (t.dense) {
-        if (t.entry_bytes == 2) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ac_scan_dense<uint16_t>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds_bytes);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(k_ac_scan_dense<uint16_t>, dim3(l.grid), dim3(l.block), l.lds_bytes, stream, t, l);
-            if (kernel_name) *kernel_name = "k_ac_scan_dense<unsigned short>";
-        } else {
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ac_scan_dense<uint32_t>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds_bytes);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(k_ac_scan_dense<uint32_t>, dim3(l.grid), dim3(l.block), l.lds_bytes, stream, t, l);
-            if (kernel_name) *kernel_name = "k_ac_scan_dense<unsigned int>";
-        }
+// entry I of kDfaForms (acgpu_forms.h, choose_dfa_form): the one place the chunk-scan kernels are instantiated and launched
+template <size_t I>
+static hipError_t launch_form(const DevTables &t, const ScanLaunch &l, hipStream_t stream) {
+    constexpr DfaForm f = kDfaForms[I];
+    using E = std::conditional_t<f.u16, uint16_t, uint32_t>;
+    if constexpr (f.kernel == DfaForm::Dfa) { // (static LDS only)
+        hipLaunchKernelGGL((k_ac_dfa<E, f.range, f.glob, ACGPU_DFA_CHAINS>), dim3(l.grid), dim3(l.block), 0, stream, t, l);
+    } else if constexpr (f.kernel == DfaForm::Dense) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ac_scan_dense<E>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds_bytes);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_ac_scan_dense<E>, dim3(l.grid), dim3(l.block), l.lds_bytes, stream, t, l);
     } else {
         hipLaunchKernelGGL(k_ac_scan_sparse, dim3(l.grid), dim3(l.block), l.lds_bytes, stream, t, l);
-        if (kernel_name) *kernel_name = "k_ac_scan_sparse";
     }
     return hipGetLastError();
+}
+using ScanLaunchFn = hipError_t (*)(const DevTables &, const ScanLaunch &, hipStream_t);
+template <size_t... I>
+static constexpr std::array<ScanLaunchFn, sizeof...(I)> scan_launchers(std::index_sequence<I...>) { return {{&launch_form<I>...}}; }
+
+hipError_t launch_ac_scan(const DevTables &t, const ScanLaunch &l, const DfaForm &f, hipStream_t stream) {
+    static constexpr auto launchers = scan_launchers(std::make_index_sequence<kDfaFormCount>{});
+    const int i = form_index(kDfaForms, f);
+    return i < 0 ? hipErrorInvalidValue : launchers[(size_t)i](t, l, stream); // (a form that is not in the table was not compiled)
 }
 
 // ---- exclusive prefix sum of per-chunk counts ------------------------------------------------------------

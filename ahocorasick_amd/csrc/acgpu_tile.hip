@@ -25,7 +25,7 @@
 // slots the wave reserves 256 at a time with one atomic.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
+#include <utility>
 
 #include "acgpu_tile_common.h"
 
@@ -33,46 +33,17 @@ namespace acgpu {
 
 int tile_block_threads() { return kTileBlock; }
 uint32_t tile_reserve_slots() { return kReserve; }
-#ifndef ACGPU_VEC
-#define ACGPU_VEC 2
-#endif
-// AhoCorasick tile geometry: a lane holds kAcVec 16-byte vectors = 8*kAcVec consecutive units of a tile, so the per-tile
-// fixed work (prefix sum, cross-lane carry, queue append) is shared by 16 positions per lane instead of 8
-constexpr int kAcVec = ACGPU_VEC;
-constexpr int kAcLaneUnits = 8 * kAcVec;
-constexpr int kAcTileUnits = kWave * kAcLaneUnits;
-constexpr int kAcCandCap = kAcTileUnits + kVerifyBatches * kWave;
 uint32_t tile_group_units() { return kPrefetch * kTileUnits; }
 
 #ifndef ACGPU_FILTER_WORDS
 #define ACGPU_FILTER_WORDS 22016
 #endif
 constexpr int kFilterWordsMax = ACGPU_FILTER_WORDS; // 88064 bytes of static LDS for the filter rows (tunable filter_max_bytes <= 88000)
-constexpr int kFilterWordsSplit = 20224; // the filter-only kernel: 79 KiB, so that two workgroups fit one CU's 160 KiB
-bool tile_split_supported(const DevTables &t) {
-    return t.filt_k >= 1 && t.filt_words <= (uint32_t)kFilterWordsSplit && !(t.hashk && t.fold_range); // (merged ranges: fused only)
-}
 
-// L2 form (second-level filter in LDS, see l2_gram in acgpu_internal.h): smaller static array for the rows, and per wave a
-// queue of SURVIVORS (kL2Cap), a copy of the current tile as packed classes behind an 8-unit halo (kTbBytes) and the list
-// of the tile's first-level candidates (kL2Fresh tile-relative positions); the Bloom words follow
-constexpr int kFilterWordsL2 = 19712;  // 78848 bytes: 27 classes, K = 4
-constexpr int kL2Cap = 256;            // a drain leaves fewer than 128; a tile adds at most 128 through the second level
+// (the geometry of the tile, of the L2 form and of the candidate queues: acgpu_forms.h, where the host sizes the LDS from it)
 static_assert(kVerifyBatches * kWave + 128 <= kL2Cap, "the queue holds what a drain leaves plus a tile's survivors (-DACGPU_NB=4 hangs)");
-constexpr int kL2Fresh = 128;
 constexpr int kBigFresh = 704;          // BIG: candidates of one tile a wave lists (the LDS of the Bloom words: 1440 bytes per wave)
 static_assert(kBigFresh * 2 * (kTileBlock / kWave) <= kL2Words * 4, "the lists of the large second level live where the Bloom words did");
-constexpr int kL2Vec = 4;              // the L2 form takes 32 units per lane: every per-tile cost is shared by 2048 positions
-constexpr int kL2TileUnits = kWave * 8 * kL2Vec;
-constexpr int kTbBytes = 16 + kL2TileUnits; // one BYTE per class: [8 spare][8 classes before the tile][the tile]
-constexpr size_t kL2WaveBytes = kL2Cap * 4 + kL2Cap * 2 + kTbBytes + kL2Fresh * 2; // queue (info + pos16), tile copy, list
-
-// dynamic LDS only: the candidate queues
-size_t tile_lds_bytes(const DevTables &t, int block_threads) {
-    (void)t;
-    return (size_t)(block_threads / kWave) * kAcCandCap * sizeof(uint32_t);
-}
-size_t tile_l2_lds_bytes(int block_threads) { return (size_t)(block_threads / kWave) * kL2WaveBytes + kL2Words * 4; }
 
 struct __attribute__((packed, aligned(2))) Units8 { // 8 UTF-16 units at any unit address (one global_load_dwordx4)
     uint32_t d[4];
@@ -1283,257 +1254,53 @@ __global__ __launch_bounds__(256) void k_ac_verify(DevTables T, TileLaunch L) {
         if (c.res_cur + i < c.slot_limit) store_rec(L, c.res_cur + i, 0, 0, 0, ~0u); // (not into the next slice)
 }
 
-template <int K, bool RANGE, bool WIDE>
-static hipError_t launch_tile_variant(const DevTables &t, const TileLaunch &l, hipStream_t stream) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ac_tile<K, RANGE, WIDE, false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds_bytes);
-    if (e != hipSuccess) return e;
-    ACGPU_LAUNCH_EV((k_ac_tile<K, RANGE, WIDE, false>), dim3(l.grid), dim3(l.block), l.lds_bytes, stream, l.ev_start, l.ev_stop, t, l);
-    return hipGetLastError();
-}
-
-template <int K, bool RANGE, bool WIDE>
-static hipError_t launch_filter_variant(const DevTables &t, const TileLaunch &l, hipStream_t stream) {
-    ACGPU_LAUNCH_EV((k_ac_tile<K, RANGE, WIDE, true>), dim3(l.grid), dim3(l.block), 0, stream, l.ev_start, l.ev_stop, t, l);
-    return hipGetLastError();
-}
-
-template <int K>
-static hipError_t launch_filter_k(const DevTables &t, const TileLaunch &l, hipStream_t stream) {
-    const bool wide = t.filt_row_bytes == 8;
-    if (t.range_cls) return wide ? launch_filter_variant<K, true, true>(t, l, stream) : launch_filter_variant<K, true, false>(t, l, stream);
-    return wide ? launch_filter_variant<K, false, true>(t, l, stream) : launch_filter_variant<K, false, false>(t, l, stream);
-}
-
-template <int K>
-static hipError_t launch_verify_k(const DevTables &t, const TileLaunch &l, hipStream_t stream) {
-    if (t.range_cls) hipLaunchKernelGGL((k_ac_verify<K, true>), dim3(l.verify_grid), dim3(256), 0, stream, t, l);
-    else hipLaunchKernelGGL((k_ac_verify<K, false>), dim3(l.verify_grid), dim3(256), 0, stream, t, l);
-    return hipGetLastError();
-}
-
-// bucketed classes: LUT classes, 8-byte rows, K <= 3
-template <int K, bool SPLIT>
-static hipError_t launch_tile_hashk(const DevTables &t, const TileLaunch &l, hipStream_t stream) {
-    if (!SPLIT) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ac_tile<K, false, true, false, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds_bytes);
+// ---- launch: the forms of acgpu_forms.h -----------------------------------------------------------------------------------
+// entry I of kTileForms / kVerifyForms: the one place a kernel of this file is instantiated and launched
+template <size_t I>
+static hipError_t launch_form(const DevTables &t, const TileLaunch &l, hipStream_t stream) {
+    constexpr TileForm f = kTileForms[I];
+    auto *k = &k_ac_tile<f.k, f.range, f.wide, f.split, f.hashk, f.pk, f.l2, f.nr4, f.shorts, f.big>;
+    if (l.lds_bytes) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds_bytes);
         if (e != hipSuccess) return e;
-        ACGPU_LAUNCH_EV((k_ac_tile<K, false, true, false, true>), dim3(l.grid), dim3(l.block), l.lds_bytes, stream, l.ev_start, l.ev_stop, t, l);
-    } else {
-        ACGPU_LAUNCH_EV((k_ac_tile<K, false, true, true, true>), dim3(l.grid), dim3(l.block), 0, stream, l.ev_start, l.ev_stop, t, l);
     }
+    ACGPU_LAUNCH_EV(k, dim3(l.grid), dim3(l.block), l.lds_bytes, stream, l.ev_start, l.ev_stop, t, l);
     return hipGetLastError();
 }
-
-// the packed 16-bit filter: range classes, 4-byte rows, row index below 2^16 (l.debug & 1024 keeps the scalar filter: A/B)
-static bool tile_pk_usable(const DevTables &t, const TileLaunch &l) {
-    if (!(t.range_cls || t.fold_range) || t.filt_row_bytes != 4 || t.filt_k < 2 || (t.hashk && !t.fold_range) || (l.debug & 1024u)) return false;
-    uint64_t rows = 1;
-    for (uint32_t i = 0; i + 1 < t.filt_k; ++i) rows *= t.filt_n;
-    if (rows > 65536) return false;
-    if (t.fold_range) return t.fr_base + t.fr_span <= 65536 && t.fr_base2 + t.fr_span <= 65536 &&
-                             (t.fr_nr <= 2 || (t.fr_base3 + t.fr_span <= 65536 && t.fr_base4 + t.fr_span <= 65536));
-    return t.cls_base + t.cls_span <= 65536;
-}
-
-// two merged ranges (DevTables::hashk with fold_range): the packed two-range filter, the verification by units; K <= 4
-// the large second level (K = 4, DevTables::l2_big): tile_debug bit 2^30 keeps the LDS form for A/B
-static bool tile_big_usable(const DevTables &t, const TileLaunch &l) { return t.l2_big != nullptr && t.filt_k == 4 && !(l.debug & (1u << 30)); }
-
-template <bool NR4>
-static hipError_t launch_tile_merged_big(const DevTables &t, const TileLaunch &l, hipStream_t stream) {
-    const size_t lds = tile_l2_lds_bytes(l.block);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ac_tile<4, false, false, false, true, true, true, NR4, true, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    ACGPU_LAUNCH_EV((k_ac_tile<4, false, false, false, true, true, true, NR4, true, true>), dim3(l.grid), dim3(l.block), lds, stream, l.ev_start, l.ev_stop, t, l);
+template <size_t I>
+static hipError_t launch_verify_form(const DevTables &t, const TileLaunch &l, hipStream_t stream) {
+    constexpr VerifyForm f = kVerifyForms[I];
+    hipLaunchKernelGGL((k_ac_verify<f.k, f.range, f.hashk>), dim3(l.verify_grid), dim3(256), 0, stream, t, l);
     return hipGetLastError();
 }
+using TileLaunchFn = hipError_t (*)(const DevTables &, const TileLaunch &, hipStream_t);
+template <size_t... I>
+static constexpr std::array<TileLaunchFn, sizeof...(I)> tile_launchers(std::index_sequence<I...>) { return {{&launch_form<I>...}}; }
+template <size_t... I>
+static constexpr std::array<TileLaunchFn, sizeof...(I)> verify_launchers(std::index_sequence<I...>) { return {{&launch_verify_form<I>...}}; }
 
-template <int K, bool L2, bool NR4>
-static hipError_t launch_tile_merged(const DevTables &t, const TileLaunch &l, hipStream_t stream) {
-    const size_t lds = L2 ? tile_l2_lds_bytes(l.block) : l.lds_bytes;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ac_tile<K, false, false, false, true, true, L2, NR4>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    ACGPU_LAUNCH_EV((k_ac_tile<K, false, false, false, true, true, L2, NR4>), dim3(l.grid), dim3(l.block), lds, stream, l.ev_start, l.ev_stop, t, l);
-    return hipGetLastError();
-}
-template <int K>
-static hipError_t launch_tile_merged_k(const DevTables &t, const TileLaunch &l, bool l2, hipStream_t stream) {
-    if (K == 4 && l2 && tile_big_usable(t, l)) return t.fr_nr > 2 ? launch_tile_merged_big<true>(t, l, stream) : launch_tile_merged_big<false>(t, l, stream);
-    if (t.fr_nr > 2) return l2 ? launch_tile_merged<K, true, true>(t, l, stream) : launch_tile_merged<K, false, true>(t, l, stream);
-    return l2 ? launch_tile_merged<K, true, false>(t, l, stream) : launch_tile_merged<K, false, false>(t, l, stream);
+// a form the table does not hold was not compiled: an error, never another kernel in its place
+static hipError_t launch_tile_form(const DevTables &t, const TileLaunch &l, const TileForm &f, bool filter_only, hipStream_t stream) {
+    static constexpr auto launchers = tile_launchers(std::make_index_sequence<kTileFormCount>{});
+    const int i = form_index(kTileForms, f);
+    if (i < 0 || f.filter_only() != filter_only || l.lds_bytes != f.lds) return hipErrorInvalidValue;
+    return launchers[(size_t)i](t, l, stream);
 }
 
-template <int K, bool RANGE>
-static hipError_t launch_tile_pk(const DevTables &t, const TileLaunch &l, hipStream_t stream) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ac_tile<K, RANGE, false, false, false, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds_bytes);
-    if (e != hipSuccess) return e;
-    ACGPU_LAUNCH_EV((k_ac_tile<K, RANGE, false, false, false, true>), dim3(l.grid), dim3(l.block), l.lds_bytes, stream, l.ev_start, l.ev_stop, t, l);
-    return hipGetLastError();
+hipError_t launch_ac_tile(const DevTables &t, const TileLaunch &l, const TileForm &f, hipStream_t stream) {
+    return launch_tile_form(t, l, f, false, stream);
 }
 
-// the PK form with the second-level filter (l.debug & 2048 keeps the one-level form: A/B)
-static bool tile_l2_usable(const DevTables &t, const TileLaunch &l) {
-    uint64_t grams = 1; // queue entries hold the K-gram index in 20 bits and the position in its region in 16
-    for (uint32_t i = 0; i < t.filt_k; ++i) grams *= t.filt_n;
-    return tile_pk_usable(t, l) && t.l2_bloom != nullptr && t.l2_depth != 0 && t.filt_k <= 5 && grams <= (1u << 20) &&
-           l.region_units <= 65536u && t.filt_words <= (uint32_t)kFilterWordsL2 && !(l.debug & 2048u);
-}
-
-template <int K, bool RANGE, bool SHORTS>
-static hipError_t launch_tile_l2s(const DevTables &t, const TileLaunch &l, hipStream_t stream) {
-    const size_t lds = tile_l2_lds_bytes(l.block);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ac_tile<K, RANGE, false, false, false, true, true, false, SHORTS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    ACGPU_LAUNCH_EV((k_ac_tile<K, RANGE, false, false, false, true, true, false, SHORTS>), dim3(l.grid), dim3(l.block), lds, stream, l.ev_start, l.ev_stop, t, l);
-    return hipGetLastError();
-}
-template <bool RANGE, bool SHORTS>
-static hipError_t launch_tile_l2_big(const DevTables &t, const TileLaunch &l, hipStream_t stream) {
-    const size_t lds = tile_l2_lds_bytes(l.block);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ac_tile<4, RANGE, false, false, false, true, true, false, SHORTS, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    ACGPU_LAUNCH_EV((k_ac_tile<4, RANGE, false, false, false, true, true, false, SHORTS, true>), dim3(l.grid), dim3(l.block), lds, stream, l.ev_start, l.ev_stop, t, l);
-    return hipGetLastError();
-}
-template <int K, bool RANGE>
-static hipError_t launch_tile_l2(const DevTables &t, const TileLaunch &l, hipStream_t stream) {
-    if (K == 4 && tile_big_usable(t, l)) return t.has_short ? launch_tile_l2_big<RANGE, true>(t, l, stream) : launch_tile_l2_big<RANGE, false>(t, l, stream);
-    // (short keywords imply K <= 4: the K = 5 form needs no SHORTS instantiation)
-    if (K <= 4 && t.has_short) return launch_tile_l2s<K, RANGE, (K <= 4)>(t, l, stream);
-    return launch_tile_l2s<K, RANGE, false>(t, l, stream);
-}
-
-template <int K>
-static hipError_t launch_tile_k(const DevTables &t, const TileLaunch &l, hipStream_t stream) {
-    const bool wide = t.filt_row_bytes == 8;
-    if (t.range_cls) return wide ? launch_tile_variant<K, true, true>(t, l, stream) : launch_tile_variant<K, true, false>(t, l, stream);
-    return wide ? launch_tile_variant<K, false, true>(t, l, stream) : launch_tile_variant<K, false, false>(t, l, stream);
-}
-
-hipError_t launch_ac_tile(const DevTables &t, const TileLaunch &l, hipStream_t stream, const char **kernel_name) {
-    static thread_local char name[64];
-    if (t.filt_k < 1 || t.filt_k > 8) return hipErrorInvalidValue;
-    std::snprintf(name, sizeof(name), "k_ac_tile<%u, %s, %s, false>", t.filt_k, t.range_cls ? "true" : "false",
-                  t.filt_row_bytes == 8 ? "true" : "false");
-    if (kernel_name) *kernel_name = name;
-    if (t.hashk && t.fold_range) {
-        if (!tile_pk_usable(t, l)) return hipErrorInvalidValue; // (the builder chooses this form only where it is)
-        const bool l2 = tile_l2_usable(t, l);
-        std::snprintf(name, sizeof(name), "k_ac_tile<%u, false, false, false, true, true, %s, %s>", t.filt_k, l2 ? "true" : "false",
-                      t.fr_nr > 2 ? "true" : "false");
-        if (l2 && tile_big_usable(t, l))
-            std::snprintf(name, sizeof(name), "k_ac_tile<4, false, false, false, true, true, true, %s, true, true>", t.fr_nr > 2 ? "true" : "false");
-        switch (t.filt_k) {
-        case 2: return launch_tile_merged_k<2>(t, l, l2, stream);
-        case 3: return launch_tile_merged_k<3>(t, l, l2, stream);
-        case 4: return launch_tile_merged_k<4>(t, l, l2, stream);
-        default: return hipErrorInvalidValue;
-        }
-    }
-    if (t.hashk) {
-        std::snprintf(name, sizeof(name), "k_ac_tile<%u, false, true, false, true>", t.filt_k);
-        switch (t.filt_k) {
-        case 1: return launch_tile_hashk<1, false>(t, l, stream);
-        case 2: return launch_tile_hashk<2, false>(t, l, stream);
-        case 3: return launch_tile_hashk<3, false>(t, l, stream);
-        default: return hipErrorInvalidValue;
-        }
-    }
-    const char *rg = t.range_cls ? "true" : "false";
-    if (tile_l2_usable(t, l)) {
-        std::snprintf(name, sizeof(name), "k_ac_tile<%u, %s, false, false, false, true, true>", t.filt_k, rg);
-        if (tile_big_usable(t, l))
-            std::snprintf(name, sizeof(name), "k_ac_tile<4, %s, false, false, false, true, true, false, %s, true>", rg, t.has_short ? "true" : "false");
-        switch (t.filt_k) {
-        case 2: return t.range_cls ? launch_tile_l2<2, true>(t, l, stream) : launch_tile_l2<2, false>(t, l, stream);
-        case 3: return t.range_cls ? launch_tile_l2<3, true>(t, l, stream) : launch_tile_l2<3, false>(t, l, stream);
-        case 4: return t.range_cls ? launch_tile_l2<4, true>(t, l, stream) : launch_tile_l2<4, false>(t, l, stream);
-        case 5: return t.range_cls ? launch_tile_l2<5, true>(t, l, stream) : launch_tile_l2<5, false>(t, l, stream);
-        default: return hipErrorInvalidValue;
-        }
-    }
-    if (tile_pk_usable(t, l)) {
-        std::snprintf(name, sizeof(name), "k_ac_tile<%u, %s, false, false, false, true>", t.filt_k, rg);
-        switch (t.filt_k) {
-        case 2: return t.range_cls ? launch_tile_pk<2, true>(t, l, stream) : launch_tile_pk<2, false>(t, l, stream);
-        case 3: return t.range_cls ? launch_tile_pk<3, true>(t, l, stream) : launch_tile_pk<3, false>(t, l, stream);
-        case 4: return t.range_cls ? launch_tile_pk<4, true>(t, l, stream) : launch_tile_pk<4, false>(t, l, stream);
-        case 5: return t.range_cls ? launch_tile_pk<5, true>(t, l, stream) : launch_tile_pk<5, false>(t, l, stream);
-        case 6: return t.range_cls ? launch_tile_pk<6, true>(t, l, stream) : launch_tile_pk<6, false>(t, l, stream);
-        case 7: return t.range_cls ? launch_tile_pk<7, true>(t, l, stream) : launch_tile_pk<7, false>(t, l, stream);
-        case 8: return t.range_cls ? launch_tile_pk<8, true>(t, l, stream) : launch_tile_pk<8, false>(t, l, stream);
-        default: return hipErrorInvalidValue;
-        }
-    }
-    switch (t.filt_k) {
-    case 1: return launch_tile_k<1>(t, l, stream);
-    case 2: return launch_tile_k<2>(t, l, stream);
-    case 3: return launch_tile_k<3>(t, l, stream);
-    case 4: return launch_tile_k<4>(t, l, stream);
-    case 5: return launch_tile_k<5>(t, l, stream);
-    case 6: return launch_tile_k<6>(t, l, stream);
-    case 7: return launch_tile_k<7>(t, l, stream);
-    case 8: return launch_tile_k<8>(t, l, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t launch_ac_filter(const DevTables &t, const TileLaunch &l, hipStream_t stream, const char **kernel_name) {
-    static thread_local char name[64];
-    if (!tile_split_supported(t) || t.filt_k > 8) return hipErrorInvalidValue;
-    std::snprintf(name, sizeof(name), "k_ac_tile<%u, %s, %s, true>", t.filt_k, t.range_cls ? "true" : "false",
-                  t.filt_row_bytes == 8 ? "true" : "false");
-    if (kernel_name) *kernel_name = name;
-    if (t.hashk) {
-        std::snprintf(name, sizeof(name), "k_ac_tile<%u, false, true, true, true>", t.filt_k);
-        switch (t.filt_k) {
-        case 1: return launch_tile_hashk<1, true>(t, l, stream);
-        case 2: return launch_tile_hashk<2, true>(t, l, stream);
-        case 3: return launch_tile_hashk<3, true>(t, l, stream);
-        default: return hipErrorInvalidValue;
-        }
-    }
-    switch (t.filt_k) {
-    case 1: return launch_filter_k<1>(t, l, stream);
-    case 2: return launch_filter_k<2>(t, l, stream);
-    case 3: return launch_filter_k<3>(t, l, stream);
-    case 4: return launch_filter_k<4>(t, l, stream);
-    case 5: return launch_filter_k<5>(t, l, stream);
-    case 6: return launch_filter_k<6>(t, l, stream);
-    case 7: return launch_filter_k<7>(t, l, stream);
-    case 8: return launch_filter_k<8>(t, l, stream);
-    default: return hipErrorInvalidValue;
-    }
+hipError_t launch_ac_filter(const DevTables &t, const TileLaunch &l, const TileForm &f, hipStream_t stream) {
+    return launch_tile_form(t, l, f, true, stream);
 }
 
 hipError_t launch_ac_verify(const DevTables &t, const TileLaunch &l, hipStream_t stream) {
-    if (t.hashk) {
-        switch (t.filt_k) {
-        case 1: hipLaunchKernelGGL((k_ac_verify<1, false, true>), dim3(l.verify_grid), dim3(256), 0, stream, t, l); break;
-        case 2: hipLaunchKernelGGL((k_ac_verify<2, false, true>), dim3(l.verify_grid), dim3(256), 0, stream, t, l); break;
-        case 3: hipLaunchKernelGGL((k_ac_verify<3, false, true>), dim3(l.verify_grid), dim3(256), 0, stream, t, l); break;
-        default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (t.filt_k) {
-    case 1: return launch_verify_k<1>(t, l, stream);
-    case 2: return launch_verify_k<2>(t, l, stream);
-    case 3: return launch_verify_k<3>(t, l, stream);
-    case 4: return launch_verify_k<4>(t, l, stream);
-    case 5: return launch_verify_k<5>(t, l, stream);
-    case 6: return launch_verify_k<6>(t, l, stream);
-    case 7: return launch_verify_k<7>(t, l, stream);
-    case 8: return launch_verify_k<8>(t, l, stream);
-    default: return hipErrorInvalidValue;
-    }
+    static constexpr auto launchers = verify_launchers(std::make_index_sequence<kVerifyFormCount>{});
+    const std::optional<VerifyForm> f = choose_verify_form(t);
+    const int i = f ? form_index(kVerifyForms, *f) : -1;
+    return i < 0 ? hipErrorInvalidValue : launchers[(size_t)i](t, l, stream);
 }
+
 
 } // namespace acgpu

@@ -4,19 +4,13 @@
 #include <hip/hip_runtime.h>
 
 #include "acgpu_device.h"
-#include "acgpu_kernels.h"
+#include "acgpu_forms.h" // the geometry the host sizes the LDS from: kTileBlock, kTileUnits, kVerifyBatches, kFtWords ...
 
 namespace acgpu {
 
-constexpr int kTileBlock = 1024;               // 16 waves share one LDS copy of the filter rows
-constexpr int kTileUnits = 512;                // units per wave tile (64 lanes x 8 units)
-#ifndef ACGPU_NB
-#define ACGPU_NB 2
-#endif
 #ifndef ACGPU_PREFETCH
 #define ACGPU_PREFETCH 4
 #endif
-constexpr int kVerifyBatches = ACGPU_NB;              // candidates verified per lane and call (independent load chains in flight)
 constexpr int kCandCap = 1024;                 // candidate queue entries per wave; a tile adds at most 512
 constexpr int kPrefetch = ACGPU_PREFETCH;                   // tiles per group; one group of loads is in flight per wave
 #ifndef ACGPU_RESERVE
@@ -153,7 +147,6 @@ __device__ __forceinline__ SlotRange reserve_slots(TileCtx &c, uint32_t total) {
 
 // ---- fused tail (TileLaunch::fused_tail): what the tile kernels' workgroups hand each other ------------------------------------
 constexpr unsigned long long kFtDone = 1ull << 62; // d_counter[number * kCounterStride + 2]: {done, the workgroup's records}
-constexpr uint32_t kFtWords = 2 + kTileBlock / kWave; // LDS: [0] the workgroup's number (later: the records below it), [1] the slice's fill mark, [2 + w] wave w's records
 __device__ __forceinline__ uint32_t ft_wave_sum(uint32_t x) { return __builtin_amdgcn_readlane(wave_inclusive_scan_dpp(x), kWave - 1); }
 
 // The workgroup's number: workgroups are numbered in the order in which they start, so that every lower number is running or

@@ -19,7 +19,7 @@
 // restatement of the reference loop -- slow, but exact.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
+#include <utility>
 
 #include "acgpu_tile_common.h"
 
@@ -50,10 +50,6 @@ __device__ __forceinline__ uint32_t word_bits8(const uint32_t *wbits, const uint
     else return wm;
 }
 
-#ifndef ACGPU_WW_NB
-#define ACGPU_WW_NB 3
-#endif
-constexpr int kWwBatches = ACGPU_WW_NB;   // run starts verified per lane and call (independent lookup chains in flight)
 #ifndef ACGPU_WW_PREFETCH
 #define ACGPU_WW_PREFETCH 2
 #endif
@@ -62,30 +58,12 @@ constexpr int kWwBatches = ACGPU_WW_NB;   // run starts verified per lane and ca
 #endif
 constexpr int kWwPrefetch = ACGPU_WW_PREFETCH; // tiles per load group (the verification needs the registers)
 constexpr int kWwBlocksPerCu = ACGPU_WW_BLOCKS; // resident blocks per CU the register budget is set for
-// run starts per tile <= 256 (a start needs a non-word unit before it); the queue holds one verification call's worth
-// (kept until the next call) plus one tile
-constexpr int kWwCandCap = kWwBatches * 64 + 256 + 64;
-
+// (kWwBatches, the queue's capacity kWwCandCap, kFoldPagesMax, kBytePagesMax and k_ww_pp's per-wave LDS: acgpu_forms.h)
 int ww_blocks_per_cu() { return kWwBlocksPerCu; }
-#ifndef ACGPU_FOLD_PAGES_MAX
-#define ACGPU_FOLD_PAGES_MAX 64
-#endif
-constexpr uint32_t kFoldPagesMax = ACGPU_FOLD_PAGES_MAX; // 32 KB of LDS; Unicode 13 simple lower-casing needs 18 pages
-constexpr uint32_t kBytePagesMax = 64;                    // k_ww_pp, FOLD 3: 16 KB (acgpu_build.cpp caps HostTables::ww_bp_n at this)
 
-uint32_t ww_fold_pages_in_lds(const DevTables &t) { return (!t.cs && t.fold_n_pages <= kFoldPagesMax) ? t.fold_n_pages : 0u; }
-
-static size_t ww_bloom_bytes(const DevTables &t) { return ((size_t)t.ww_bloom_mask + 1) / 8; }
-
-// dynamic LDS of k_ww_tile: [Bloom words | candidate queues]; the word-character bits (8 KB), the page index (256 B) and
-// the pages of the fold table (32 KB) are STATIC LDS, at addresses the compiler knows: a lookup is then address arithmetic on the unit alone
-// (with everything behind a dynamic base the compiler added the base -- a literal 0 -- to every one of them)
-size_t ww_lds_bytes(int block_threads, const DevTables &t) {
-    const uint32_t fold_pages = ww_fold_pages_in_lds(t);
-    (void)fold_pages; // (the pages are static LDS as well: kFoldPagesMax of them)
-    return ww_bloom_bytes(t) + (size_t)(block_threads / kWave) * kWwCandCap * sizeof(uint32_t);
-}
-
+// k_ww_tile's dynamic LDS is [Bloom words | candidate queues] (choose_ww_form); the word-character bits (8 KB), the page index (256 B)
+// and the pages of the fold table (32 KB) are STATIC LDS, at addresses the compiler knows: a lookup is then address arithmetic on the
+// unit alone (with everything behind a dynamic base the compiler added the base -- a literal 0 -- to every one of them)
 struct __attribute__((packed, aligned(2))) WwUnits8 { // 8 UTF-16 units at any unit address (one global_load_dwordx4)
     uint32_t d[4];
 };
@@ -633,18 +611,8 @@ __global__ __launch_bounds__(kTileBlock, kWwBlocksPerCu * (kTileBlock / 256)) vo
 //                      tile in slot 1 goes on in slot 0)
 //             bits   = the same for the word-character bits, one byte per lane and tile
 //             list   = the run starts of the tile being verified, tile relative, in text order
-constexpr int kPpRingUnits = 2 * kTileUnits + 32;
-constexpr int kPpBitBytes = 2 * (kTileUnits / 8) + 8;
-constexpr int kPpListCap = kTileUnits / 2; // a run start needs a unit that is no word character before it
-constexpr int kPpWaveBytes = (kPpRingUnits * 2 + kPpBitBytes + kPpListCap * 2 + 15) & ~15;
-constexpr uint32_t kPpMaxLen = 32; // longer keywords: k_ww_tile (up to 16 units: the LONG = false form, one 32-byte ring read per run)
-
-// the perfect hash's displacements take the Bloom filter's place in LDS (tile_debug bit 2^29: the two-choice table behind the filter, A/B)
-static bool ww_pp_perfect(const DevTables &t, const TileLaunch &l) { return t.ww_ph != nullptr && !(l.debug & (1u << 29)); }
-static size_t ww_pp_front_bytes(const DevTables &t, bool ph) { return ph ? ((size_t)t.ww_ph_buckets + 7) / 8 * 16 : ww_bloom_bytes(t); }
-static size_t ww_pp_lds_bytes(int block_threads, const DevTables &t, bool ph) {
-    return ww_pp_front_bytes(t, ph) + (size_t)(block_threads / kWave) * kPpWaveBytes;
-}
+// (kPpRingUnits, kPpBitBytes, kPpListCap, kPpWaveBytes: acgpu_forms.h).  The perfect hash's displacements take the Bloom filter's
+// place in LDS.
 
 // One batch of run starts, hashed and ready to probe: everything but the probed slots (registers; PpBatch travels from the
 // pass that computes it to the next pass, which issues its probes, and compares them at its end -- the LOADED registers
@@ -1172,64 +1140,28 @@ __global__ void k_ww_sequential(DevTables T, const uint16_t *hay, uint32_t len, 
     *counter = n;
 }
 
-// the position-parallel form serves keywords of at most 16 units whose fold table (if any) fits LDS, when its LDS fits next
-// to the Bloom filter (tile_debug bit 268435456 keeps k_ww_tile: A/B; bit 256, the trie-walk verification, exists only there)
-// the byte pages serve the scan they were built for (case-insensitive, the automaton's own word bits)
-static bool ww_pp_byte_pages(const DevTables &t) { return !t.cs && t.ww_bp_n != 0 && t.ww_bp_n <= kBytePagesMax && t.wbits == t.ww_bp_wbits; }
-static size_t ww_pp_fixed_lds(const DevTables &t) { // the kernel's static LDS
-    const int fold = t.cs ? 0 : (ww_pp_byte_pages(t) ? 3 : ww_fold_pages_in_lds(t) ? 1 : 2);
-    return (fold == 3 ? 16 + 256 + 16 + kBytePagesMax * 256 + 256 : fold == 1 ? 8192 + 256 + kFoldPagesMax * 512 + 32 : 8192 + 64) + kFtWords * 4;
-}
-size_t ww_pp_lds_total(const DevTables &t, const TileLaunch &l, int block_threads) {
-    return ww_pp_lds_bytes(block_threads, t, ww_pp_perfect(t, l)) + ww_pp_fixed_lds(t);
-}
-static bool ww_pp_usable(const DevTables &t, const TileLaunch &l) {
-    const int fold = t.cs ? 0 : (ww_pp_byte_pages(t) ? 3 : ww_fold_pages_in_lds(t) ? 1 : 2);
-    return fold != 2 && t.max_len <= kPpMaxLen && !(l.debug & (256u | 268435456u)) && ww_pp_lds_total(t, l, l.block) <= 160 * 1024;
-}
-
-bool ww_pp_serves(const DevTables &t, const TileLaunch &l) { return ww_pp_usable(t, l); }
-
-hipError_t launch_ww_tile(const DevTables &t, const TileLaunch &l, hipStream_t stream, const char **kernel_name) {
-    int fold = t.cs ? 0 : (ww_fold_pages_in_lds(t) ? 1 : 2);
-    if (ww_pp_usable(t, l)) {
-        if (ww_pp_byte_pages(t)) fold = 3;
-        const bool ph = ww_pp_perfect(t, l);
-        const size_t lds = ww_pp_lds_bytes(l.block, t, ph);
-        const bool lng = t.max_len > 16;
-        static thread_local char name[48];
-        std::snprintf(name, sizeof(name), "k_ww_pp<%d, %s, %s>", fold, lng ? "true" : "false", ph ? "true" : "false");
-        if (kernel_name) *kernel_name = name;
-#define ACGPU_WW_PP(F, LG, PHV)                                                                                              \
-    do {                                                                                                                     \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ww_pp<F, LG, PHV>),                             \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                            \
-        if (e != hipSuccess) return e;                                                                                       \
-        ACGPU_LAUNCH_EV((k_ww_pp<F, LG, PHV>), dim3(l.grid), dim3(l.block), lds, stream, l.ev_start, l.ev_stop, t, l);       \
-        return hipGetLastError();                                                                                            \
-    } while (0)
-        if (fold == 0) {
-            if (lng) { if (ph) ACGPU_WW_PP(0, true, true); else ACGPU_WW_PP(0, true, false); }
-            else { if (ph) ACGPU_WW_PP(0, false, true); else ACGPU_WW_PP(0, false, false); }
-        } else if (fold == 3) {
-            if (lng) { if (ph) ACGPU_WW_PP(3, true, true); else ACGPU_WW_PP(3, true, false); }
-            else { if (ph) ACGPU_WW_PP(3, false, true); else ACGPU_WW_PP(3, false, false); }
-        } else {
-            if (lng) { if (ph) ACGPU_WW_PP(1, true, true); else ACGPU_WW_PP(1, true, false); }
-            else { if (ph) ACGPU_WW_PP(1, false, true); else ACGPU_WW_PP(1, false, false); }
-        }
-#undef ACGPU_WW_PP
-        fold = t.cs ? 0 : (ww_fold_pages_in_lds(t) ? 1 : 2); // (not reached: every branch above returns)
-    }
-    const void *fn = fold == 0 ? reinterpret_cast<const void *>(&k_ww_tile<0>)
-                   : fold == 1 ? reinterpret_cast<const void *>(&k_ww_tile<1>) : reinterpret_cast<const void *>(&k_ww_tile<2>);
+// ---- launch: the forms of acgpu_forms.h (choose_ww_form) ------------------------------------------------------------------
+template <size_t I>
+static hipError_t launch_form(const DevTables &t, const TileLaunch &l, hipStream_t stream) {
+    constexpr WwForm f = kWwForms[I];
+    const void *fn;
+    if constexpr (f.pp) fn = reinterpret_cast<const void *>(&k_ww_pp<f.fold, f.lng, f.ph>);
+    else fn = reinterpret_cast<const void *>(&k_ww_tile<f.fold>);
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds_bytes);
     if (e != hipSuccess) return e;
-    if (fold == 0) ACGPU_LAUNCH_EV(k_ww_tile<0>, dim3(l.grid), dim3(l.block), l.lds_bytes, stream, l.ev_start, l.ev_stop, t, l);
-    else if (fold == 1) ACGPU_LAUNCH_EV(k_ww_tile<1>, dim3(l.grid), dim3(l.block), l.lds_bytes, stream, l.ev_start, l.ev_stop, t, l);
-    else ACGPU_LAUNCH_EV(k_ww_tile<2>, dim3(l.grid), dim3(l.block), l.lds_bytes, stream, l.ev_start, l.ev_stop, t, l);
-    if (kernel_name) *kernel_name = fold == 0 ? "k_ww_tile<0>" : fold == 1 ? "k_ww_tile<1>" : "k_ww_tile<2>";
+    if constexpr (f.pp) ACGPU_LAUNCH_EV((k_ww_pp<f.fold, f.lng, f.ph>), dim3(l.grid), dim3(l.block), l.lds_bytes, stream, l.ev_start, l.ev_stop, t, l);
+    else ACGPU_LAUNCH_EV(k_ww_tile<f.fold>, dim3(l.grid), dim3(l.block), l.lds_bytes, stream, l.ev_start, l.ev_stop, t, l);
     return hipGetLastError();
+}
+using WwLaunchFn = hipError_t (*)(const DevTables &, const TileLaunch &, hipStream_t);
+template <size_t... I>
+static constexpr std::array<WwLaunchFn, sizeof...(I)> ww_launchers(std::index_sequence<I...>) { return {{&launch_form<I>...}}; }
+
+hipError_t launch_ww_tile(const DevTables &t, const TileLaunch &l, const WwForm &f, hipStream_t stream) {
+    static constexpr auto launchers = ww_launchers(std::make_index_sequence<kWwFormCount>{});
+    const int i = form_index(kWwForms, f);
+    if (i < 0 || l.lds_bytes != f.lds) return hipErrorInvalidValue; // (a form that is not in the table was not compiled)
+    return launchers[(size_t)i](t, l, stream);
 }
 
 hipError_t launch_ww_sequential(const DevTables &t, const uint16_t *d_hay, uint32_t len, void *d_out, uint64_t cap,
