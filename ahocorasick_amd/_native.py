@@ -6,7 +6,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ACGPU_LIB") or os.path.join(_HERE, "lib", "libacgpu.so")  # ACGPU_LIB: A/B builds
 
-OK, E_INVALID, E_NONWORD, E_NOMEM, E_OVERFLOW, E_HIP, E_NODEVICE, E_UNSUPPORTED = 0, -1, -2, -3, -4, -5, -6, -7
+OK, E_INVALID, E_NONWORD, E_NOMEM, E_OVERFLOW, E_HIP, E_NODEVICE, E_UNSUPPORTED, E_ENCODING = 0, -1, -2, -3, -4, -5, -6, -7, -8
 MODE_ALL, MODE_LONGEST, MODE_WHOLEWORD, MODE_SHORTEST, MODE_WWLONGEST = 0, 1, 2, 3, 4
 REC_SET, REC_MAP = 8, 12
 TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_PEER = 0, 1, 2
@@ -24,6 +24,15 @@ class AcgpuError(RuntimeError):
         if code == E_HIP:
             msg += " (hipError_t=%d)" % lib().acgpu_last_hip_error()
         super().__init__("%s: %s [%d]" % (where, msg, code))
+
+
+class Utf8Error(ValueError):
+    """ACGPU_E_ENCODING of acgpu_match_utf8: the haystack is not well-formed UTF-8.  start: the byte offset at which a strict
+    decoder stops -- UnicodeDecodeError.start of bytes.decode("utf-8") on the same buffer."""
+
+    def __init__(self, start):
+        self.start = int(start)
+        super().__init__("haystack is not well-formed UTF-8 at byte %d" % self.start)
 
 
 class Info(ctypes.Structure):
@@ -77,6 +86,10 @@ class SummaryStats(ctypes.Structure):  # acgpu_summary_stats
     _fields_ = [("n_records", ctypes.c_uint64), ("n_matched", ctypes.c_uint64), ("pieces", ctypes.c_uint32), ("rescans", ctypes.c_uint32)]
 
 
+class Utf8Stats(ctypes.Structure):  # acgpu_utf8_stats
+    _fields_ = [("n_units", ctypes.c_uint64), ("first_bad", ctypes.c_int64), ("ascii", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 def _summary_dtype():
     import numpy as np
     return np.dtype({"names": ["n_matches", "start", "end", "keyword_id", "reserved"],
@@ -96,7 +109,8 @@ SYMBOLS = ["acgpu_build", "acgpu_free", "acgpu_get_info", "acgpu_match_u16", "ac
            "acgpu_match_device_allgather", "acgpu_last_rccl_error", "acgpu_gather_slot_bytes",
            "acgpu_stream_set_pipelined", "acgpu_stream_reserve", "acgpu_cursor_open", "acgpu_cursor_next",
            "acgpu_cursor_get_stats", "acgpu_cursor_close", "acgpu_count_u16", "acgpu_count_device",
-           "acgpu_replace_u16", "acgpu_replace_device", "acgpu_replace_batch_u16", "acgpu_summary_batch_u16"]
+           "acgpu_replace_u16", "acgpu_replace_device", "acgpu_replace_batch_u16", "acgpu_summary_batch_u16",
+           "acgpu_match_utf8"]
 
 _lib = None
 
@@ -183,6 +197,8 @@ def lib():
         L.acgpu_replace_batch_u16.argtypes = [vp, vp, vp, u32, vp, vp, u32, vp, u64, vp, ctypes.POINTER(u64), ctypes.POINTER(ReplaceStats)]
         L.acgpu_summary_batch_u16.restype = ci
         L.acgpu_summary_batch_u16.argtypes = [vp, vp, vp, u32, vp, ctypes.POINTER(SummaryStats)]
+        L.acgpu_match_utf8.restype = ci
+        L.acgpu_match_utf8.argtypes = [vp, vp, u64, ci, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(Utf8Stats)]
         L.acgpu_debug_wordhash_perfect.restype = ci
         L.acgpu_debug_wordhash_perfect.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.acgpu_debug_wordhash.restype = ci

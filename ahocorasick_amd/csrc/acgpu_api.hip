@@ -1765,6 +1765,7 @@ const char *acgpu_strerror(int code) {
     case ACGPU_E_HIP: return "HIP runtime error";
     case ACGPU_E_NODEVICE: return "no HIP device";
     case ACGPU_E_UNSUPPORTED: return "unsupported";
+    case ACGPU_E_ENCODING: return "haystack is not well-formed UTF-8";
     default: return "unknown error";
     }
 }

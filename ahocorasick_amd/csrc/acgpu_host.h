@@ -227,6 +227,7 @@ struct DeviceState {
     PoolEvent replace_ev[4];                              // ... slab b emitted (b), slab b copied out (2 + b)
     PoolBuf replace_merged, replace_off;                  // acgpu_replace_batch_u16: a piece's records merged with its separators, the result's offsets
     PoolBuf summary;                                      // acgpu_summary_batch_u16: 24 bytes per haystack, {records, the first of them}
+    PoolBuf utf8_in, utf8_aux;                            // acgpu_match_utf8: the caller's bytes; {n_units, first_bad}, block sums, checkpoints (acgpu_utf8.hip)
     CountCall *count = nullptr;                          // the counting call that runs on this pool (it holds mu), or nullptr
     double all_density = -1.0;                           // ALL: records per unit of this pool's last call (-1: none yet): k_ac_states or the tile kernel
     int fol_level = 0;                                   // k_longest_follow: 0 = run-up of 128 positions, 1 = of a whole segment (a call's chains had not merged), 2 = not for this pool's texts
@@ -377,6 +378,20 @@ int scan_host_range(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack
 // The whole host text as one shard: copied (blocking) into d.stage_hay; *out = that buffer, all of it owned, the text's begin and
 // end, no chain.  The caller holds d.mu.
 int stage_whole_text(DeviceState &d, const uint16_t *haystack, uint64_t n_units, acgpu_shard *out);
+
+// A UTF-8 host text staged as one shard (acgpu_utf8.hip): validated and transcoded on the device.
+struct Utf8Text {
+    acgpu_shard shard{};              // as stage_whole_text builds it: d.stage_hay, all of it owned, the text's begin and end, no chain
+    const uint8_t *d_bytes = nullptr; // the bytes on the device (d.utf8_in)
+    const uint32_t *d_ckpt = nullptr; // checkpoint table, one word per 32 units: the byte offset of the sequence that holds unit 32 i, bit 31
+                                      // set where that unit is its low surrogate; nullptr: an all-ASCII text, unit offsets are byte offsets
+    uint64_t n_units = 0;             // UTF-16 units of the text
+    int64_t first_bad = -1;           // ACGPU_E_ENCODING: where a strict decoder stops
+};
+// bytes -> {device shard, checkpoint table, n_units} on `stream`, which it waits for once (the transcoder's 16-byte result sizes
+// the shard).  ACGPU_E_ENCODING: the text is ill-formed, out->first_bad says where, nothing was transcoded and the stream is
+// idle.  The caller holds d.mu; n_bytes < 2^31.
+int stage_utf8_text(DeviceState &d, const uint8_t *bytes, uint64_t n_bytes, hipStream_t stream, Utf8Text *out);
 
 // acgpu_match_u16 behind its argument checks; the caller holds d.mu (acgpu_match_batch_u16 calls it per haystack).
 int match_host_text(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack, uint64_t n_units, int record_kind, void *out,

@@ -24,6 +24,7 @@ import os
 import numpy as np
 
 from . import _native as N
+from ._native import Utf8Error
 from .unicode_tables import (default_word_chars, java_lower_table, word_chars_from_list, word_chars_with_toggles)
 
 
@@ -36,6 +37,23 @@ def utf16(s):
     if isinstance(s, str):
         return np.frombuffer(s.encode("utf-16-le", "surrogatepass"), dtype=np.uint16).copy()
     return np.ascontiguousarray(s, dtype=np.uint16)
+
+
+def _utf8_bytes(data):
+    """bytes / bytearray / memoryview / uint8 array -> a contiguous uint8 array over the same memory where that is possible"""
+    if isinstance(data, np.ndarray):
+        return np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    return np.frombuffer(data, dtype=np.uint8)
+
+
+def utf8_unit_offsets(data):
+    """The mapping rule of acgpu_match_utf8 (include/acgpu.h) restated on the host, for WELL-FORMED UTF-8: an int64 array with
+    one entry per UTF-16 unit the text decodes to; entry u is the byte offset of the first byte of the code point that holds
+    unit u (both units of a surrogate pair name the same 4-byte sequence).  A record (start, end) in units is
+    (off[start], off[end - 1] + the length of the sequence at off[end - 1]) in bytes.  For tests and tools, not the hot path."""
+    b = _utf8_bytes(data)
+    leads = np.flatnonzero((b & 0xC0) != 0x80)
+    return np.repeat(leads, 1 + (b[leads] >= 0xF0)).astype(np.int64)
 
 
 def _to_str(units):
@@ -130,6 +148,30 @@ class Automaton:
                 cap = int(n_out.value)
                 continue
             N.check(rc, "acgpu_match_u16_multi" if devs is not None else "acgpu_match_u16")
+            return out[:n_out.value]
+
+    def match_utf8(self, data, with_ids, cap=None, stats=None):
+        """acgpu_match_utf8: a UTF-8 haystack (bytes, bytearray, memoryview or uint8 array) in host memory -> (n, 2|3) int32 array
+        in reference call order with BYTE offsets into `data`, end exclusive.  Ill-formed input raises Utf8Error (.start as
+        UnicodeDecodeError.start).  stats: an N.Utf8Stats to fill in, if wanted."""
+        buf = _utf8_bytes(data)
+        n = int(buf.size)
+        kind = N.REC_MAP if with_ids else N.REC_SET
+        cols = kind // 4
+        if cap is None:
+            cap = max(4096, n // 64)
+        buf_in = buf if n else np.zeros(1, np.uint8)
+        st = stats if stats is not None else N.Utf8Stats()
+        while True:
+            out = np.empty((cap, cols), dtype=np.int32)
+            n_out = ctypes.c_uint64(0)
+            rc = N.lib().acgpu_match_utf8(self._h, _vp(buf_in), n, kind, _vp(out), cap, ctypes.byref(n_out), ctypes.byref(st))
+            if rc == N.E_OVERFLOW:
+                cap = int(n_out.value)
+                continue
+            if rc == N.E_ENCODING:
+                raise Utf8Error(st.first_bad)
+            N.check(rc, "acgpu_match_utf8")
             return out[:n_out.value]
 
     def match_batch(self, haystacks, with_ids, cap=None):
@@ -635,6 +677,21 @@ class StringSet(_BatchDecisions):
         """Convenience (not in the reference): the (n,2) int32 array of (start, end) records."""
         return self._auto.match_host(utf16(haystack), with_ids=False)
 
+    def find_all_utf8(self, data):
+        """Not in the reference: the (n,2) int32 array of (start, end) records of a UTF-8 haystack (bytes, bytearray, memoryview
+        or uint8 array), in BYTE offsets into `data` -- decoded, scanned and mapped back on the device.  Utf8Error if ill-formed."""
+        return self._auto.match_utf8(data, with_ids=False)
+
+    def match_utf8(self, data, listener):
+        """Not in the reference: match(data.decode("utf-8"), listener) with the listener receiving `data` itself and byte
+        offsets into it; a listener call that returns False stops the loop."""
+        if data is None:
+            raise TypeError("haystack is None")
+        fn = _listener_fn(listener)
+        for s, e in self._auto.match_utf8(data, with_ids=False).tolist():
+            if not fn(data, s, e):
+                return
+
     def match_batch(self, haystacks, listener):
         """Not in the reference: match(haystack, listener) for every haystack of a list in ONE device call (short inputs: a
         call has tens of microseconds of fixed cost).  A listener call that returns False ends THAT haystack's matches."""
@@ -726,6 +783,22 @@ class StringMap(_BatchDecisions):
     def find_all(self, haystack):
         """Convenience (not in the reference): the (n,3) int32 array of (start, end, keyword_index) records."""
         return self._auto.match_host(utf16(haystack), with_ids=True)
+
+    def find_all_utf8(self, data):
+        """Not in the reference: the (n,3) int32 array of (start, end, keyword_index) records of a UTF-8 haystack, in BYTE
+        offsets into `data` (see StringSet.find_all_utf8)."""
+        return self._auto.match_utf8(data, with_ids=True)
+
+    def match_utf8(self, data, listener):
+        """Not in the reference: match(data.decode("utf-8"), listener) with the listener receiving `data` itself, byte offsets
+        into it and the value; a listener call that returns False stops the loop."""
+        if data is None:
+            raise TypeError("haystack is None")
+        fn = _listener_fn(listener)
+        vals = self._values
+        for s, e, k in self._auto.match_utf8(data, with_ids=True).tolist():
+            if not fn(data, s, e, vals[k]):
+                return
 
     def match_batch(self, haystacks, listener):
         """Not in the reference: match(haystack, listener) for every haystack of a list in ONE device call (see

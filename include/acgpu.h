@@ -78,6 +78,11 @@
  *        acgpu_match_batch_u16)
  *      offsets (device)                         4 H
  *      summaries (device)                       24 H, grow-only
+ *    acgpu_match_utf8 needs what acgpu_match_u16 needs for the decoded text as ONE shard (N = its units, at most B, the bytes
+ *    given: the staged text 2 N, the records cap x record_kind, the scan's form above), plus, kept by the pool:
+ *      the bytes (device)                       B
+ *      block sums (device)                      B/1024  (4 bytes per 4096 bytes)
+ *      checkpoints (device)                     B/8 at most  (4 bytes per 32 units)
  */
 #ifndef ACGPU_H
 #define ACGPU_H
@@ -101,6 +106,7 @@ extern "C" {
 #define ACGPU_E_HIP (-5)         /* HIP runtime error; see acgpu_last_hip_error()                    */
 #define ACGPU_E_NODEVICE (-6)    /* no HIP device visible                                            */
 #define ACGPU_E_UNSUPPORTED (-7) /* combination not implemented by this build                        */
+#define ACGPU_E_ENCODING (-8)    /* the haystack is not well-formed UTF-8; stats->first_bad says where */
 
 /* matcher families (which reference class an automaton replaces) */
 #define ACGPU_MODE_ALL 0       /* AhoCorasickSet / AhoCorasickMap      S/AhoCorasickSet.java:193-252, S/AhoCorasickMap.java:277-336 */
@@ -647,6 +653,48 @@ typedef struct acgpu_summary_stats {
 } acgpu_summary_stats;
 int acgpu_summary_batch_u16(const acgpu_automaton *a, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks,
                             acgpu_batch_summary *out /* n_haystacks, host */, acgpu_summary_stats *st /* may be NULL */);
+
+/*
+ * A haystack in UTF-8 -- text as it lies in a file or in a buffer of a C, Python, Go or Rust caller -- in HOST memory: validated
+ * and transcoded to UTF-16 on the device, scanned there, and the records returned in BYTE offsets of `bytes`.  The call returns
+ * the records acgpu_match_u16 returns for the decoded text (what bytes.decode("utf-8") followed by a Java String of it holds):
+ * their number, order, keyword_id and record_kind are the same, every family; only start and end differ, `end` exclusive.
+ * MAPPING RULE.  start becomes the offset of the first byte of the encoded code point that holds unit `start`; end becomes one
+ * past the last byte of the code point that holds unit `end - 1`.  For a match on code-point boundaries that is the obvious
+ * mapping.  A match that begins or ends between the two units of a surrogate pair -- possible only with keywords that hold
+ * lone surrogates -- gets the smallest byte span that covers it: all four bytes of that code point are inside.
+ * VALIDATION is strict, as in CPython's bytes.decode("utf-8"): stray or missing continuation bytes, a sequence truncated by the
+ * end of the text, overlong forms (leads C0 / C1, E0 80..9F, F0 80..8F), encoded surrogates (ED A0..BF) and anything above
+ * U+10FFFF (F4 90.., leads F5..FF) are ill-formed.  Then the call returns ACGPU_E_ENCODING, *n_out = 0, nothing has been scanned,
+ * and stats->first_bad is the smallest offset that is the lead byte of an ill-formed sequence or a continuation byte that no
+ * lead claims -- the value of CPython's UnicodeDecodeError.start.  A byte order mark is not stripped: U+FEFF is a unit like any
+ * other.
+ *  n_bytes   : < 2^31, else ACGPU_E_INVALID (as NULL a, bytes or n_out, and a bad record_kind: before a device is touched).
+ *              n_bytes == 0: ACGPU_OK, no records, no device needed.
+ *  out, cap, *n_out : as for acgpu_match_u16; on ACGPU_E_OVERFLOW *n_out is the capacity to retry with (cap 0 and out NULL: count).
+ *  stats     : NULL, or what the transcoder found.  ascii == 1: every byte is below 0x80, unit offsets ARE byte offsets and the
+ *              records were not rewritten.
+ * Works on the NULL stream, under the pool's lock (STREAM RULE above: tickets in flight on the pool give ACGPU_E_INVALID).
+ * How it works: the bytes are copied to the device; k_utf8_count validates them, a lane per 16 bytes, and counts the units of
+ * every block of 4096 bytes; the host waits ONCE for 16 bytes (n_units, first_bad) to size the shard; k_utf8_write stores the
+ * units and, per 32 units, the byte offset of the sequence that holds the first of them (the checkpoints); the scan is
+ * match_shard on the whole text as one shard, unchanged; k_utf8_map rewrites start and end - 1 of every record in place from
+ * the nearest checkpoint and a walk of at most 31 units over the lead bytes; one copy brings the records out.
+ * The call is ONE shard through the general path: neither the chunk-pipelined form acgpu_match_u16 takes from 2^25 units on
+ * (a long text is copied whole before the scan begins, nothing overlaps), nor its one-launch form for texts of up to 4096 units
+ * (a short text pays the fixed cost of five launches, two copies and two waits, several times that form's latency: batch short
+ * texts, or decode them on the host).  Not built: count, replace, batch, cursor, stream, device-resident and multi-device forms
+ * for UTF-8; lossy decoding (U+FFFD); CESU-8 / WTF-8; the Java facade (its strings are UTF-16).  ACGPU_ABI_VERSION stays as it
+ * is: adding symbols is compatible.
+ */
+typedef struct acgpu_utf8_stats {
+    uint64_t n_units;    /* UTF-16 units the text decodes to (0 on ACGPU_E_ENCODING)                */
+    int64_t  first_bad;  /* -1, or the byte offset of the first ill-formed sequence                 */
+    uint32_t ascii;      /* 1: every byte < 0x80, offsets were not remapped                         */
+    uint32_t reserved;
+} acgpu_utf8_stats;
+int acgpu_match_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, int record_kind, void *out, uint64_t cap,
+                     uint64_t *n_out, acgpu_utf8_stats *stats /* may be NULL */);
 
 /*
  * Synthetic haystack generator of the benchmark: unit i of the stream is
