@@ -98,6 +98,11 @@ int build_tables(int mode, const uint16_t *kw_units, const uint64_t *kw_off, uin
             }
         }
         if (we <= ws) continue; // null / empty keywords are skipped, S/AhoCorasickSet.java:27
+        for (uint64_t i = ws; i < we; i++) { // (raw units: case folding never touches a surrogate half)
+            const bool high = (w[i] & 0xfc00u) == 0xd800u, low = (w[i] & 0xfc00u) == 0xdc00u;
+            if (high && i + 1 < we && (w[i + 1] & 0xfc00u) == 0xdc00u) i++; // a pair
+            else if (high || low) t.lone_surrogate = true;
+        }
         uint32_t cur = 0;
         for (uint64_t i = ws; i < we; i++) {
             uint16_t u = t.lower[w[i]];

@@ -386,12 +386,19 @@ struct Utf8Text {
     const uint32_t *d_ckpt = nullptr; // checkpoint table, one word per 32 units: the byte offset of the sequence that holds unit 32 i, bit 31
                                       // set where that unit is its low surrogate; nullptr: an all-ASCII text, unit offsets are byte offsets
     uint64_t n_units = 0;             // UTF-16 units of the text
+    uint64_t n_bytes = 0;             // ... and its bytes
     int64_t first_bad = -1;           // ACGPU_E_ENCODING: where a strict decoder stops
 };
 // bytes -> {device shard, checkpoint table, n_units} on `stream`, which it waits for once (the transcoder's 16-byte result sizes
 // the shard).  ACGPU_E_ENCODING: the text is ill-formed, out->first_bad says where, nothing was transcoded and the stream is
 // idle.  The caller holds d.mu; n_bytes < 2^31.
 int stage_utf8_text(DeviceState &d, const uint8_t *bytes, uint64_t n_bytes, hipStream_t stream, Utf8Text *out);
+// The mapping rule of acgpu_match_utf8 over cnt records of `cols` words on the device, in place (k_utf8_map), enqueued on
+// `stream`.  An all-ASCII text (no checkpoints) needs none: nothing is launched.
+int utf8_map_records(const Utf8Text &text, int32_t *d_recs, uint64_t cnt, uint32_t cols, hipStream_t stream);
+// *d_out = the first byte of the code point that holds unit `unit` < n_units, enqueued on `stream` (k_utf8_pos): a position
+// between the two units of a surrogate pair is rounded DOWN.  Not for an all-ASCII text (there the unit is the byte).
+int utf8_map_position(const Utf8Text &text, uint64_t unit, int64_t *d_out, hipStream_t stream);
 
 // acgpu_match_u16 behind its argument checks; the caller holds d.mu (acgpu_match_batch_u16 calls it per haystack).
 int match_host_text(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack, uint64_t n_units, int record_kind, void *out,

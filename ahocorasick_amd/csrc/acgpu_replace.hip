@@ -14,6 +14,11 @@
 // match call's concatenation), where a separator is a match that is deleted.  Behind every piece k_replace_merge merges the piece's
 // records with the pseudo-records of its separators; plan and emit run over the merged list as they are, so the results come out
 // back to back, and k_replace_batch_offsets reads every result's first output unit off the plan.
+//
+// acgpu_replace_utf8 rewrites a UTF-8 text in BYTES: the text is staged by stage_utf8_text (acgpu_utf8.hip) and scanned in UTF-16
+// units as a device shard; behind every piece its records become byte offsets (utf8_map_records) and its boundary a byte position
+// (utf8_map_position), and from there on the driver's bookkeeping, the plan and the emit count bytes: the emit is a template over
+// the element, k_replace_emit<uint16_t> for the entries above and k_replace_emit<uint8_t> for this one.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,14 +35,22 @@ namespace {
 typedef uint32_t rp_v4u __attribute__((ext_vector_type(4)));
 
 constexpr int kPlanBlock = 256, kPlanPer = 8, kPlanTile = kPlanBlock * kPlanPer; // records per workgroup of the plan
-constexpr int kEmitBlock = 256, kEmitTile = kEmitBlock * 8;                      // output units per workgroup of the emit
+constexpr int kEmitBlock = 256;                                                  // lanes of a workgroup of the emit: one 16-byte store each
 constexpr int kEmitLds = 3072;                                                   // segments a workgroup stages (16 bytes each)
+constexpr int kPlanHead = 4; // words in front of the plan's sums: {sum of the deltas, last end, the piece's boundary in bytes (UTF-8), unused}
+
+// An output ELEMENT is what the text is made of as the caller sees it: a UTF-16 unit (T = uint16_t), or a byte of a UTF-8 text
+// (T = uint8_t).  Records, the table's entries, the plan and the windows count elements; "unit" below means element.
+template <class T>
+constexpr int kEmitPer = 16 / (int)sizeof(T); // elements of a lane's store: 8 units or 16 bytes
+template <class T>
+constexpr int kEmitTile = kEmitBlock * kEmitPer<T>; // ... of a workgroup: 2048 units or 4096 bytes
 
 // The replacement table on the device: n_repl entries {first unit in `units`, length}, then the units.
 struct ReplTable {
     const uint2 *ent;
-    const uint16_t *units;
-    uint32_t n_repl; // 1: that replacement stands for every keyword
+    const void *units; // uint16_t or uint8_t: the emit's element
+    uint32_t n_repl;   // 1: that replacement stands for every keyword
 };
 
 __device__ __forceinline__ uint2 repl_of(const ReplTable &rt, int32_t id) {
@@ -134,19 +147,22 @@ struct Seg {
     uint32_t rsrc, tsrc;
 };
 
+template <class T>
 struct EmitArgs {
-    const uint16_t *hay;  // the piece's buffer
+    const T *hay;         // the piece's buffer
     const int32_t *recs;  // its Map records, buffer relative
     const int64_t *pos;   // the plan
     int64_t n_recs;
     ReplTable rt;
     int64_t done;         // buffer relative: output unit 0 of the piece is text unit `done` (if no record starts there)
     int64_t w0, w1;       // the window of the piece's output to write
-    uint16_t *dst;        // where output unit w0 goes
+    T *dst;               // where output unit w0 goes
+    __device__ __forceinline__ const T *repl() const { return static_cast<const T *>(rt.units); }
 };
 
 // segment of record i (-1: the text in front of the first record), t0 = the tile's first output unit
-__device__ __forceinline__ Seg make_seg(const EmitArgs &A, int64_t i, int64_t t0) {
+template <class T>
+__device__ __forceinline__ Seg make_seg(const EmitArgs<T> &A, int64_t i, int64_t t0) {
     Seg s;
     if (i < 0) {
         s.rel = -1;
@@ -155,37 +171,44 @@ __device__ __forceinline__ Seg make_seg(const EmitArgs &A, int64_t i, int64_t t0
         s.tsrc = (uint32_t)(A.done + t0);
         return s;
     }
-    const int64_t P = A.pos[i] - t0; // < kEmitTile
+    const int64_t P = A.pos[i] - t0; // < kEmitTile<T>
     const uint2 r = repl_of(A.rt, A.recs[3 * i + 2]);
     const int64_t rend = P + (int64_t)r.y;
     s.rel = (int32_t)std::max<int64_t>(P, -1);
-    s.rend = (int32_t)std::min<int64_t>(std::max<int64_t>(rend, 0), kEmitTile);
+    s.rend = (int32_t)std::min<int64_t>(std::max<int64_t>(rend, 0), kEmitTile<T>);
     s.rsrc = r.x - (uint32_t)P;
     s.tsrc = (uint32_t)A.recs[3 * i + 1] - (uint32_t)rend;
     return s;
 }
 
-// 8 consecutive units from p (any 2-byte alignment) as one 16-byte value: the two aligned 16-byte words around them and a funnel
-// shift.  Only 16-byte words that hold one of the 8 units are read, so nothing beyond the page of a valid unit.
-__device__ __forceinline__ rp_v4u load8(const uint16_t *p) {
+// The 16 consecutive bytes from p -- 8 units at any 2-byte alignment, or 16 bytes at any address -- as one 16-byte value: the two
+// aligned 16-byte words around them and a funnel shift by sh = p's offset into the first, in bytes (units: even).  Only 16-byte
+// words that hold one of the wanted bytes are read, so nothing beyond the page of a valid element.
+template <class T>
+__device__ __forceinline__ rp_v4u load16(const T *p) {
     const uintptr_t a = (uintptr_t)p;
-    const uint32_t sh = (uint32_t)(a >> 1) & 7u;
+    const uint32_t sh = (uint32_t)a & 15u;
     const rp_v4u *q = reinterpret_cast<const rp_v4u *>(a & ~(uintptr_t)15);
     const rp_v4u lo = q[0];
     if (sh == 0) return lo;
     const rp_v4u hi = q[1];
     uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    if (sh & 4u) {
+    if (sh & 8u) {
 #pragma unroll
         for (int j = 0; j < 6; ++j) w[j] = w[j + 2];
     }
-    if (sh & 2u) {
+    if (sh & 4u) {
 #pragma unroll
         for (int j = 0; j < 7; ++j) w[j] = w[j + 1];
     }
-    if (sh & 1u) {
+    if (sizeof(T) == 2) {
+        if (sh & 2u) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = (w[j] >> 16) | (w[j + 1] << 16);
+            for (int j = 0; j < 4; ++j) w[j] = (w[j] >> 16) | (w[j + 1] << 16);
+        }
+    } else { // the low bytes of the shift: each word from itself and its neighbour, {w[j + 1], w[j]} >> 8 (sh & 3)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[j] = __builtin_amdgcn_alignbyte(w[j + 1], w[j], sh & 3u);
     }
     rp_v4u r;
     r.x = w[0]; r.y = w[1]; r.z = w[2]; r.w = w[3];
@@ -193,14 +216,14 @@ __device__ __forceinline__ rp_v4u load8(const uint16_t *p) {
 }
 
 // The emit.  Tiles are laid over the DESTINATION's 16-byte grid: v = o - w0 + (dst's misalignment in units), tile b = the v in
-// [b * kEmitTile, + kEmitTile), lane l of it the 8 units of one aligned 16-byte store.  A vector that the window covers only in
+// [b * kEmitTile, + kEmitTile), lane l of it the kEmitPer units -- 8 units, or 16 bytes -- of one aligned 16-byte store.  A vector that the window covers only in
 // part (the window's first and last) is written unit by unit, so nothing outside [w0, w1) -- nothing at or beyond the caller's
 // capacity -- is touched.
 // The records that touch a tile are found by two binary searches over pos; their segments go to LDS when they fit (they do unless
 // thousands of deleted matches fall into one tile), else every lane takes them from global memory: the same code over another
 // view.  A lane finds the segment of its first unit by binary search and walks on from there (a few steps, then a search again).
-template <bool kLds>
-__device__ __forceinline__ void emit_tile(const EmitArgs &A, const Seg *lseg, int64_t t0, int64_t i0, int32_t cnt, int64_t cnt_g) {
+template <class T, bool kLds>
+__device__ __forceinline__ void emit_tile(const EmitArgs<T> &A, const Seg *lseg, int64_t t0, int64_t i0, int32_t cnt, int64_t cnt_g) {
     const int64_t n_seg = kLds ? (int64_t)cnt : cnt_g;
     auto rel_at = [&](int64_t j) -> int64_t {
         if (kLds) return lseg[j].rel;
@@ -221,27 +244,28 @@ __device__ __forceinline__ void emit_tile(const EmitArgs &A, const Seg *lseg, in
         }
         return lo - 1;
     };
-    const int32_t u0 = (int32_t)threadIdx.x * 8;
+    constexpr int kPer = kEmitPer<T>, kPerWord = 4 / (int)sizeof(T);
+    const int32_t u0 = (int32_t)threadIdx.x * kPer;
     const int64_t o_first = t0 + u0;
-    if (o_first >= A.w1 || o_first + 8 <= A.w0) return;
-    const int32_t ua = (int32_t)std::max<int64_t>(A.w0 - o_first, 0), ub = (int32_t)std::min<int64_t>(A.w1 - o_first, 8); // the lane's valid units [ua, ub)
-    uint16_t *out = A.dst + (o_first - A.w0);
+    if (o_first >= A.w1 || o_first + kPer <= A.w0) return;
+    const int32_t ua = (int32_t)std::max<int64_t>(A.w0 - o_first, 0), ub = (int32_t)std::min<int64_t>(A.w1 - o_first, kPer); // the lane's valid units [ua, ub)
+    T *out = A.dst + (o_first - A.w0);
     int64_t j = find(0, u0 + ua);
     Seg s = seg_at(j);
-    const bool full = ua == 0 && ub == 8;
-    if (full && (j + 1 >= n_seg || rel_at(j + 1) > u0 + 7)) { // one segment holds the vector
+    const bool full = ua == 0 && ub == kPer;
+    if (full && (j + 1 >= n_seg || rel_at(j + 1) > u0 + kPer - 1)) { // one segment holds the vector
         if (u0 >= s.rend) {
-            __builtin_nontemporal_store(load8(A.hay + (uint32_t)(s.tsrc + (uint32_t)u0)), reinterpret_cast<rp_v4u *>(out));
+            __builtin_nontemporal_store(load16(A.hay + (uint32_t)(s.tsrc + (uint32_t)u0)), reinterpret_cast<rp_v4u *>(out));
             return;
         }
-        if (u0 + 8 <= s.rend) {
-            __builtin_nontemporal_store(load8(A.rt.units + (uint32_t)(s.rsrc + (uint32_t)u0)), reinterpret_cast<rp_v4u *>(out));
+        if (u0 + kPer <= s.rend) {
+            __builtin_nontemporal_store(load16(A.repl() + (uint32_t)(s.rsrc + (uint32_t)u0)), reinterpret_cast<rp_v4u *>(out));
             return;
         }
     }
     uint32_t w[4] = {0, 0, 0, 0};
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
+    for (int k = 0; k < kPer; ++k) {
         if (k >= ua && k < ub) {
             const int32_t u = u0 + k;
             if (k > ua) {
@@ -251,9 +275,9 @@ __device__ __forceinline__ void emit_tile(const EmitArgs &A, const Seg *lseg, in
                     s = seg_at(j);
                 }
             }
-            const uint32_t x = u < s.rend ? A.rt.units[(uint32_t)(s.rsrc + (uint32_t)u)] : A.hay[(uint32_t)(s.tsrc + (uint32_t)u)];
-            if (full) w[k / 2] |= x << (16 * (k & 1));
-            else out[k] = (uint16_t)x;
+            const uint32_t x = u < s.rend ? A.repl()[(uint32_t)(s.rsrc + (uint32_t)u)] : A.hay[(uint32_t)(s.tsrc + (uint32_t)u)];
+            if (full) w[k / kPerWord] |= x << (8 * (int)sizeof(T) * (k % kPerWord));
+            else out[k] = (T)x;
         }
     }
     if (full) {
@@ -263,12 +287,13 @@ __device__ __forceinline__ void emit_tile(const EmitArgs &A, const Seg *lseg, in
     }
 }
 
-__global__ __launch_bounds__(kEmitBlock) void k_replace_emit(EmitArgs A) {
+template <class T>
+__global__ __launch_bounds__(kEmitBlock) void k_replace_emit(EmitArgs<T> A) {
     __shared__ Seg lseg[kEmitLds];
     __shared__ int64_t bounds[2];
-    const int64_t mis = (int64_t)(((uintptr_t)A.dst >> 1) & 7u);
-    const int64_t t0 = A.w0 - mis + (int64_t)blockIdx.x * kEmitTile;
-    const int64_t ov0 = std::max(t0, A.w0), ov1 = std::min(t0 + kEmitTile, A.w1); // the tile's units of the window
+    const int64_t mis = (int64_t)(((uintptr_t)A.dst & 15u) / sizeof(T));
+    const int64_t t0 = A.w0 - mis + (int64_t)blockIdx.x * kEmitTile<T>;
+    const int64_t ov0 = std::max(t0, A.w0), ov1 = std::min(t0 + kEmitTile<T>, A.w1); // the tile's units of the window
     if (ov0 >= ov1) return;
     if (threadIdx.x == 0) bounds[0] = last_at_or_before(A.pos, 0, A.n_recs, ov0);
     if (threadIdx.x == kWave) bounds[1] = last_at_or_before(A.pos, 0, A.n_recs, ov1 - 1);
@@ -277,9 +302,9 @@ __global__ __launch_bounds__(kEmitBlock) void k_replace_emit(EmitArgs A) {
     if (cnt <= kEmitLds) {
         for (int32_t j = (int32_t)threadIdx.x; j < (int32_t)cnt; j += kEmitBlock) lseg[j] = make_seg(A, i0 + j, t0);
         __syncthreads();
-        emit_tile<true>(A, lseg, t0, i0, (int32_t)cnt, cnt);
+        emit_tile<T, true>(A, lseg, t0, i0, (int32_t)cnt, cnt);
     } else {
-        emit_tile<false>(A, lseg, t0, i0, 0, cnt);
+        emit_tile<T, false>(A, lseg, t0, i0, 0, cnt);
     }
 }
 
@@ -349,8 +374,10 @@ struct ReplaceCall {
     DeviceState &d;
     hipStream_t stream;
     ReplTable rt{};
-    uint16_t *h_out = nullptr; // the host entry's result (through the slabs) ...
-    uint16_t *d_out = nullptr; // ... or the device entry's
+    uint32_t esz = 2;          // bytes of an element: 2, a UTF-16 unit; 1, a byte of a UTF-8 text (acgpu_replace_utf8).  What follows counts elements
+    const Utf8Text *u8 = nullptr; // esz == 1: the staged text -- the scan runs over its units, everything below counts its bytes
+    uint8_t *h_out = nullptr;  // the host entry's result (through the slabs) ...
+    uint8_t *d_out = nullptr;  // ... or the device entry's
     uint64_t cap = 0;
     uint64_t n = 0;            // units of the text
     uint64_t done = 0;         // output exists for the text's units [0, done)
@@ -367,13 +394,15 @@ struct ReplaceCall {
 // full: the table in its full form, whatever n_repl is -- an entry per keyword given to acgpu_build (a single replacement: they
 // share its units) and behind them an empty one, the slot of a batch call's separators; repl_of then never sees n_repl == 1 where
 // there is a keyword.
-int upload_table(ReplaceCall &c, const uint16_t *repl_units, const uint64_t *repl_off, uint32_t n_repl, bool full = false) {
+// repl_units: c.esz bytes each; the entries are {first, length} in those.  Behind the units the blob is padded so that an aligned
+// 16-byte load around any of them stays inside it.
+int upload_table(ReplaceCall &c, const void *repl_units, const uint64_t *repl_off, uint32_t n_repl, bool full = false) {
     const uint64_t r0 = n_repl ? repl_off[0] : 0, total = n_repl ? repl_off[n_repl] - r0 : 0;
     const uint32_t n_ent = full ? c.a->n_given + 1 : n_repl;
     const size_t ent_bytes = ((size_t)n_ent * 8 + 15) & ~(size_t)15;
     std::vector<uint64_t> blob;
     try {
-        blob.assign((ent_bytes + (size_t)total * 2 + 16 + 7) / 8, 0);
+        blob.assign((ent_bytes + (size_t)total * c.esz + 16 + 7) / 8, 0);
     } catch (...) {
         return ACGPU_E_NOMEM;
     }
@@ -384,12 +413,12 @@ int upload_table(ReplaceCall &c, const uint16_t *repl_units, const uint64_t *rep
         ent[2 * i] = (uint32_t)(repl_off[from] - r0);
         ent[2 * i + 1] = (uint32_t)(repl_off[from + 1] - repl_off[from]);
     }
-    if (total) std::copy(repl_units + r0, repl_units + r0 + total, reinterpret_cast<uint16_t *>(reinterpret_cast<char *>(blob.data()) + ent_bytes));
+    if (total) std::copy_n(static_cast<const char *>(repl_units) + r0 * c.esz, total * c.esz, reinterpret_cast<char *>(blob.data()) + ent_bytes);
     const int rc = c.d.replace_tab.ensure(blob.size() * 8);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(c.d.replace_tab.p, blob.data(), blob.size() * 8, hipMemcpyHostToDevice)); // (blocking: the blob dies here)
     c.rt.ent = reinterpret_cast<const uint2 *>(c.d.replace_tab.p);
-    c.rt.units = reinterpret_cast<const uint16_t *>(reinterpret_cast<const char *>(c.d.replace_tab.p) + ent_bytes);
+    c.rt.units = reinterpret_cast<const char *>(c.d.replace_tab.p) + ent_bytes;
     c.rt.n_repl = n_ent;
     return ACGPU_OK;
 }
@@ -412,31 +441,49 @@ int upload_table(ReplaceCall &c, const uint16_t *repl_units, const uint64_t *rep
 //    later record starts before.  And every separator below the limit has been merged: the limit is at most own_hi, or, for the
 //    first-unit families, at most the end of a record that holds no separator.  So the plan's sum holds exactly the elements below
 //    the limit, and every separator is merged by exactly one piece: the one that emits it.
-uint64_t replace_limit(const HostTables &t, bool last_or_whole, uint64_t n, uint64_t own_hi, uint64_t last_end, uint64_t done) {
-    if (last_or_whole) return n;
-    if (t.mode == ACGPU_MODE_SHORTEST) {
-        const uint64_t back = t.max_len ? t.max_len - 1 : 0;
-        return std::max({last_end, done, own_hi > back ? own_hi - back : 0});
-    }
-    return std::max({own_hi, last_end, done});
+//  * A UTF-8 call scans in units and keeps n, done, last_end and the limit in BYTES.  Its keywords are well-formed UTF-16
+//    (HostTables::lone_surrogate is refused), so every record begins and ends on a code-point boundary of the text, and the map
+//    from such unit positions to byte positions is exact and monotone: records that neither overlap nor are out of order in units
+//    are neither in bytes.  The piece's boundary (piece_bound, in units) is the one position that need not be a code-point
+//    boundary -- a piece may end between the two units of a surrogate pair -- so it is mapped to the first byte of the code point
+//    that HOLDS it, i.e. rounded down (utf8_map_position).  A later record starts on a code-point boundary at or behind that
+//    unit, therefore at or behind the rounded byte; rounding down only withholds more, and the limit still takes the maximum
+//    with done and last_end, so it never falls behind what has been emitted or inside a record of this piece.  The text is on
+//    the device as a whole, so "inside the buffer" holds trivially.
+// piece_bound: the family's part of the rule, in the scan's coordinates; replace_limit: the maximum, in the driver's.
+uint64_t piece_bound(const HostTables &t, uint64_t own_hi) {
+    if (t.mode != ACGPU_MODE_SHORTEST) return own_hi;
+    const uint64_t back = t.max_len ? t.max_len - 1 : 0;
+    return own_hi > back ? own_hi - back : 0;
 }
 
-int launch_emit(ReplaceCall &c, const uint16_t *hay, const int32_t *recs, uint64_t cnt, int64_t done_rel, uint64_t w0, uint64_t w1, uint16_t *dst, hipStream_t stream) {
-    EmitArgs A;
-    A.hay = hay;
+uint64_t replace_limit(bool last_or_whole, uint64_t n, uint64_t bound, uint64_t last_end, uint64_t done) {
+    return last_or_whole ? n : std::max({bound, last_end, done});
+}
+
+template <class T>
+int launch_emit_as(ReplaceCall &c, const void *hay, const int32_t *recs, uint64_t cnt, int64_t done_rel, uint64_t w0, uint64_t w1, void *dst, hipStream_t stream) {
+    EmitArgs<T> A;
+    A.hay = static_cast<const T *>(hay);
     A.recs = recs;
-    A.pos = reinterpret_cast<const int64_t *>(c.d.replace_plan.p) + 2 + (cnt + kPlanTile - 1) / kPlanTile;
+    A.pos = reinterpret_cast<const int64_t *>(c.d.replace_plan.p) + kPlanHead + (cnt + kPlanTile - 1) / kPlanTile;
     A.n_recs = (int64_t)cnt;
     A.rt = c.rt;
     A.done = done_rel;
     A.w0 = (int64_t)w0;
     A.w1 = (int64_t)w1;
-    A.dst = dst;
-    const uint64_t mis = ((uintptr_t)dst >> 1) & 7u;
-    const uint64_t tiles = (w1 - w0 + mis + kEmitTile - 1) / kEmitTile;
-    hipLaunchKernelGGL(k_replace_emit, dim3((unsigned)tiles), dim3(kEmitBlock), 0, stream, A);
+    A.dst = static_cast<T *>(dst);
+    const uint64_t mis = ((uintptr_t)dst & 15u) / sizeof(T);
+    const uint64_t tiles = (w1 - w0 + mis + kEmitTile<T> - 1) / kEmitTile<T>;
+    hipLaunchKernelGGL(k_replace_emit<T>, dim3((unsigned)tiles), dim3(kEmitBlock), 0, stream, A);
     HIP_TRY(hipGetLastError());
     return ACGPU_OK;
+}
+
+// hay, dst: elements of c.esz bytes
+int launch_emit(ReplaceCall &c, const void *hay, const int32_t *recs, uint64_t cnt, int64_t done_rel, uint64_t w0, uint64_t w1, void *dst, hipStream_t stream) {
+    return c.esz == 1 ? launch_emit_as<uint8_t>(c, hay, recs, cnt, done_rel, w0, w1, dst, stream)
+                      : launch_emit_as<uint16_t>(c, hay, recs, cnt, done_rel, w0, w1, dst, stream);
 }
 
 // A batch call's piece: its cnt records (d.count_res) merged with the separators in [done, own_hi) into d.replace_merged.  Which
@@ -461,48 +508,63 @@ int merge_separators(ReplaceCall &c, uint64_t base, uint64_t own_hi, const int32
 }
 
 // Behind a piece: plan its cnt records `recs` (relative to `base`; a batch call's: n_found records and the piece's separators),
-// then emit [done, limit) of the text `hay` (the piece's buffer, whose unit 0 is the text's unit `base`).
-int replace_piece(ReplaceCall &c, const uint16_t *hay, uint64_t base, const int32_t *recs, uint64_t cnt, uint64_t n_found, uint64_t own_hi,
+// then emit [done, limit) of the text `hay` (the piece's buffer, whose unit 0 is the text's unit `base`).  A UTF-8 call: recs
+// and hay are in bytes (base == 0), own_hi is in units still.
+int replace_piece(ReplaceCall &c, const void *hay, uint64_t base, const int32_t *recs, uint64_t cnt, uint64_t n_found, uint64_t own_hi,
                   bool last_or_whole) {
     DeviceState &d = c.d;
     const int64_t done_rel = (int64_t)(c.done - base);
     int64_t delta = 0;
-    uint64_t last_end = 0;
-    if (cnt) {
+    uint64_t last_end = 0, bound = piece_bound(c.a->t, own_hi);
+    // UTF-8: the boundary goes from units to bytes through the checkpoints (the last piece's limit is the text's end, and in an
+    // all-ASCII text a unit is a byte); the byte rides with what the host reads behind the plan anyway
+    const bool map_bound = c.u8 && c.u8->d_ckpt && !last_or_whole;
+    if (cnt || map_bound) {
         const uint32_t n_blocks = (uint32_t)((cnt + kPlanTile - 1) / kPlanTile);
-        int rc = d.replace_plan.ensure((2 + (size_t)n_blocks + cnt) * 8); // {sum of the deltas, last end} | workgroup sums | pos
+        int rc = d.replace_plan.ensure((kPlanHead + (size_t)n_blocks + cnt) * 8); // {sum of the deltas, last end, boundary, -} | workgroup sums | pos
         if (rc) return rc;
-        int64_t *slot = reinterpret_cast<int64_t *>(d.replace_plan.p), *bsum = slot + 2, *pos = bsum + n_blocks;
-        hipLaunchKernelGGL(k_replace_sums, dim3(n_blocks), dim3(kPlanBlock), 0, c.stream, recs, cnt, c.rt, bsum);
-        hipLaunchKernelGGL(k_replace_offsets, dim3(1), dim3(kPlanBlock), 0, c.stream, bsum, n_blocks, recs, cnt, slot);
-        hipLaunchKernelGGL(k_replace_plan, dim3(n_blocks), dim3(kPlanBlock), 0, c.stream, recs, cnt, c.rt, (const int64_t *)bsum, done_rel, pos);
-        if (c.seps.n_sep) // (over the piece's own records: the same search that placed the separators)
-            hipLaunchKernelGGL(k_replace_batch_offsets, dim3((c.seps.n_sep + kMergeBlock - 1) / kMergeBlock), dim3(kMergeBlock), 0, c.stream,
-                               reinterpret_cast<const int32_t *>(d.count_res.p), n_found, c.seps, (const int64_t *)pos, c.out_pos, c.d_out_off);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(d.replace_pin, slot, 16, hipMemcpyDeviceToHost, c.stream));
+        int64_t *slot = reinterpret_cast<int64_t *>(d.replace_plan.p), *bsum = slot + kPlanHead, *pos = bsum + n_blocks;
+        if (cnt) {
+            hipLaunchKernelGGL(k_replace_sums, dim3(n_blocks), dim3(kPlanBlock), 0, c.stream, recs, cnt, c.rt, bsum);
+            hipLaunchKernelGGL(k_replace_offsets, dim3(1), dim3(kPlanBlock), 0, c.stream, bsum, n_blocks, recs, cnt, slot);
+            hipLaunchKernelGGL(k_replace_plan, dim3(n_blocks), dim3(kPlanBlock), 0, c.stream, recs, cnt, c.rt, (const int64_t *)bsum, done_rel, pos);
+            if (c.seps.n_sep) // (over the piece's own records: the same search that placed the separators)
+                hipLaunchKernelGGL(k_replace_batch_offsets, dim3((c.seps.n_sep + kMergeBlock - 1) / kMergeBlock), dim3(kMergeBlock), 0, c.stream,
+                                   reinterpret_cast<const int32_t *>(d.count_res.p), n_found, c.seps, (const int64_t *)pos, c.out_pos, c.d_out_off);
+            HIP_TRY(hipGetLastError());
+        }
+        if (map_bound && (rc = utf8_map_position(*c.u8, bound, slot + 2, c.stream))) return rc;
+        // (a piece without records reads the boundary alone)
+        const size_t first = cnt ? 0 : 2, words = (map_bound ? 3 : 2) - first;
+        HIP_TRY(hipMemcpyAsync(static_cast<int64_t *>(d.replace_pin.h) + first, slot + first, words * 8, hipMemcpyDeviceToHost, c.stream));
         HIP_TRY(hipStreamSynchronize(c.stream)); // the piece's output length decides the windows and the next piece's `done`
-        delta = static_cast<const int64_t *>(d.replace_pin.h)[0];
-        last_end = base + (uint64_t)static_cast<const int64_t *>(d.replace_pin.h)[1];
+        const int64_t *h = static_cast<const int64_t *>(d.replace_pin.h);
+        if (cnt) {
+            delta = h[0];
+            last_end = base + (uint64_t)h[1];
+        }
+        if (map_bound) bound = (uint64_t)h[2];
     }
-    const uint64_t limit = std::min(c.n, replace_limit(c.a->t, last_or_whole, c.n, own_hi, last_end, c.done));
+    const uint64_t limit = std::min(c.n, replace_limit(last_or_whole, c.n, bound, last_end, c.done));
     const int64_t total_s = (int64_t)(limit - c.done) + delta;
     if (limit < c.done || total_s < 0) return ACGPU_E_HIP; // (records that overlap or are out of order: not a family this call serves)
     const uint64_t total = (uint64_t)total_s;
     const uint64_t room = c.cap > c.out_pos ? c.cap - c.out_pos : 0, emit_total = std::min(total, room); // beyond cap: planned, not written
     if (emit_total && c.d_out) {
-        const int rc = launch_emit(c, hay, recs, cnt, done_rel, 0, emit_total, c.d_out + c.out_pos, c.stream);
+        const int rc = launch_emit(c, hay, recs, cnt, done_rel, 0, emit_total, c.d_out + c.out_pos * c.esz, c.stream);
         if (rc) return rc;
     } else if (emit_total) {
-        // through two slabs of the pool: slab k is copied to the caller's memory (on the copy stream) while slab k + 1 is emitted
-        const uint64_t slab = (std::min<uint64_t>((uint64_t)std::max<int64_t>(8, tunables().replace_slab_units.load(std::memory_order_relaxed)), emit_total) + 7) & ~7ull;
-        int rc = d.replace_slab.ensure(slab * 4 + 32);
+        // through two slabs of the pool: slab k is copied to the caller's memory (on the copy stream) while slab k + 1 is emitted.
+        // A slab is a whole number of 16-byte vectors -- 8 units, or 16 bytes -- so that both slabs start 16-byte aligned.
+        const uint64_t vec = 16 / c.esz;
+        const uint64_t slab = (std::min<uint64_t>((uint64_t)std::max<int64_t>(8, tunables().replace_slab_units.load(std::memory_order_relaxed)), emit_total) + vec - 1) & ~(vec - 1);
+        int rc = d.replace_slab.ensure(slab * 2 * c.esz + 32);
         if (rc) return rc;
-        uint16_t *buf[2] = {reinterpret_cast<uint16_t *>(d.replace_slab.p), reinterpret_cast<uint16_t *>(d.replace_slab.p) + slab};
+        uint8_t *buf[2] = {reinterpret_cast<uint8_t *>(d.replace_slab.p), reinterpret_cast<uint8_t *>(d.replace_slab.p) + slab * c.esz};
         bool copied[2] = {false, false};
         auto copy_out = [&](int b, uint64_t w0, uint64_t w1) -> int {
             HIP_TRY(hipStreamWaitEvent(d.copy_stream, d.replace_ev[b], 0));
-            HIP_TRY(hipMemcpyAsync(c.h_out + c.out_pos + w0, buf[b], (w1 - w0) * 2, hipMemcpyDeviceToHost, d.copy_stream));
+            HIP_TRY(hipMemcpyAsync(c.h_out + (c.out_pos + w0) * c.esz, buf[b], (w1 - w0) * c.esz, hipMemcpyDeviceToHost, d.copy_stream));
             HIP_TRY(hipEventRecord(d.replace_ev[2 + b], d.copy_stream));
             copied[b] = true;
             return ACGPU_OK;
@@ -535,13 +597,15 @@ int replace_pieces(ReplaceCall &c, int64_t chain, bool whole, const PieceScan &s
     if (!d.copy_stream) HIP_TRY(hipStreamCreateWithFlags(&d.copy_stream.h, hipStreamNonBlocking));
     for (auto &e : d.replace_ev)
         if (!e) HIP_TRY(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
-    PieceDriver p(0, c.n, chain, whole, ACGPU_REC_MAP, &d.count_res); // the pool's reservoir of Map records (a counting call's too: one call at a time holds the pool)
+    PieceDriver p(0, c.u8 ? c.u8->n_units : c.n, chain, whole, ACGPU_REC_MAP, &d.count_res); // the pool's reservoir of Map records (a counting call's too: one call at a time holds the pool)
     int rc = ACGPU_OK;
     while (rc == ACGPU_OK && p.pos < p.end) {
         uint64_t cnt = 0, base = 0;
         if ((rc = scan_next_piece(p, scan, &cnt, &base))) break;
-        const uint16_t *hay = scan.shard ? scan.shard->d_hay : reinterpret_cast<const uint16_t *>(d.stage_hay.p);
+        const void *hay = c.u8 ? (const void *)c.u8->d_bytes : scan.shard ? (const void *)scan.shard->d_hay : d.stage_hay.p;
         const int32_t *recs = reinterpret_cast<const int32_t *>(d.count_res.p);
+        // UTF-8: the piece's records go from units to bytes where they lie (text relative: the shard is the whole text)
+        if (c.u8 && (rc = utf8_map_records(*c.u8, reinterpret_cast<int32_t *>(d.count_res.p), cnt, ACGPU_REC_MAP / 4, c.stream))) break;
         uint64_t n_list = cnt;
         if (c.h_cat_off && (rc = merge_separators(c, base, p.pos, &recs, &n_list))) break;
         rc = replace_piece(c, hay, base, recs, n_list, cnt, p.pos, whole || p.pos >= p.end);
@@ -571,7 +635,7 @@ int replace_result(const ReplaceCall &c, uint64_t *n_out, acgpu_replace_stats *s
 }
 
 // the checks both entries share, none of which needs a device
-int check_table(const acgpu_automaton *a, const uint16_t *repl_units, const uint64_t *repl_off, uint32_t n_repl) {
+int check_table(const acgpu_automaton *a, const void *repl_units, const uint64_t *repl_off, uint32_t n_repl) {
     if (n_repl != a->n_given && n_repl != 1) return ACGPU_E_INVALID;
     if (n_repl && !repl_off) return ACGPU_E_INVALID;
     for (uint32_t i = 0; i < n_repl; ++i)
@@ -597,7 +661,7 @@ int acgpu_replace_u16(const acgpu_automaton *ca, const uint16_t *haystack, uint6
     DeviceState &d = *call.d;
     if ((rc = call.on(d.call_stream))) return rc;
     ReplaceCall c{a, d, d.call_stream};
-    c.h_out = out;
+    c.h_out = reinterpret_cast<uint8_t *>(out);
     c.cap = cap;
     if ((rc = upload_table(c, repl_units, repl_off, n_repl))) return rc;
     if ((rc = replace_host_text(c, haystack, n_units))) return call.fail(rc);
@@ -619,7 +683,7 @@ int acgpu_replace_device(const acgpu_automaton *ca, acgpu_shard *shard, const ui
     const hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     if ((rc = call.on(stream))) return rc;
     ReplaceCall c{a, d, stream};
-    c.d_out = d_out;
+    c.d_out = reinterpret_cast<uint8_t *>(d_out);
     c.cap = cap;
     c.n = shard->n_units;
     if ((rc = upload_table(c, repl_units, repl_off, n_repl))) return rc;
@@ -628,6 +692,46 @@ int acgpu_replace_device(const acgpu_automaton *ca, acgpu_shard *shard, const ui
     const hipError_t e = hipStreamSynchronize(stream); // the final wait
     if (rc) return rc;
     HIP_TRY(e);
+    return replace_result(c, n_out, st);
+}
+
+int acgpu_replace_utf8(const acgpu_automaton *ca, const uint8_t *bytes, uint64_t n_bytes, const uint8_t *repl_bytes, const uint64_t *repl_off,
+                       uint32_t n_repl, uint8_t *out, uint64_t cap, uint64_t *n_out, acgpu_replace_stats *st, acgpu_utf8_stats *ust) {
+    if (!ca || !n_out || (n_bytes && !bytes) || (cap && !out)) return ACGPU_E_INVALID;
+    if (n_bytes >= (1ull << 31)) return ACGPU_E_INVALID;
+    acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
+    int rc = check_table(a, repl_bytes, repl_off, n_repl);
+    if (rc) return rc;
+    if (a->t.lone_surrogate) return ACGPU_E_UNSUPPORTED; // (a match inside a surrogate pair: records that overlap in bytes, see replace_limit)
+    *n_out = 0;
+    if (st) *st = acgpu_replace_stats{};
+    acgpu_utf8_stats us{};
+    us.first_bad = -1;
+    us.ascii = 1;
+    if (ust) *ust = us;
+    if (n_bytes == 0) return ACGPU_OK; // (nothing to decode and nothing to rewrite: no device needed)
+    PoolCall call(a); // (no device: fails here, as acgpu_match_utf8 does, and out is untouched)
+    if (call.rc) return call.rc;
+    DeviceState &d = *call.d;
+    if ((rc = call.idle())) return rc; // (the NULL stream: see the stream rule)
+    Utf8Text text;
+    rc = stage_utf8_text(d, bytes, n_bytes, d.call_stream, &text);
+    us.first_bad = text.first_bad;
+    us.n_units = rc == ACGPU_E_ENCODING ? 0 : text.n_units;
+    us.ascii = rc != ACGPU_E_ENCODING && text.n_units == n_bytes;
+    if (ust) *ust = us;
+    if (rc == ACGPU_E_ENCODING) return rc; // (the stream is idle: the pool is as usable as before the call)
+    if (rc) return call.fail(rc);
+    ReplaceCall c{a, d, d.call_stream};
+    c.esz = 1;
+    c.u8 = &text;
+    c.h_out = out;
+    c.cap = cap;
+    c.n = n_bytes;
+    if ((rc = upload_table(c, repl_bytes, repl_off, n_repl))) return call.fail(rc);
+    const bool whole = shard_rule(a->t, ACGPU_REC_MAP, false).sequential;
+    if ((rc = replace_pieces(c, 0, whole, PieceScan{a, d, nullptr, 0, &text.shard, c.stream}))) return call.fail(rc);
+    HIP_TRY(hipStreamSynchronize(c.stream));
     return replace_result(c, n_out, st);
 }
 
@@ -649,7 +753,7 @@ int acgpu_replace_batch_u16(const acgpu_automaton *ca, const uint16_t *units, co
     if (call.rc) return call.rc;
     DeviceState &d = *call.d;
     ReplaceCall c{a, d, d.call_stream};
-    c.h_out = out;
+    c.h_out = reinterpret_cast<uint8_t *>(out);
     c.cap = cap;
     if (plan.per_haystack) { // every haystack as a text of its own, the results back to back
         if ((rc = call.on(c.stream))) return rc; // (what acgpu_replace_u16 asks)

@@ -10,6 +10,8 @@
 //                  that unit's sequence begins -- the checkpoint table, 4 bytes per 32 units;
 //   k_utf8_map   : a lane per record: start and end - 1 go from units to bytes through the nearest checkpoint at or below them
 //                  and a walk of at most 31 units over the lead bytes.
+// For acgpu_replace_utf8 (acgpu_replace.hip) the front end and k_utf8_map are host functions of their own (stage_utf8_text,
+// utf8_map_records), and k_utf8_pos maps one unit position -- a piece's boundary -- the same way (utf8_map_position).
 // What a lane knows about its 16 bytes is eleven bit masks over a window of 24 bytes (the 4 before, its own, the 4 behind), built
 // by one function that both passes over the text share, so they cannot disagree about a count.
 #include <hip/hip_runtime.h>
@@ -231,12 +233,36 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_map(int32_t *__restrict__ r
     r[1] = (int32_t)(s.p + len);
 }
 
+// one lane: *out = the first byte of the code point that holds unit `unit` < n_units -- of a low surrogate, its pair's
+__global__ void k_utf8_pos(uint32_t unit, const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ ckpt, int64_t *__restrict__ out) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    SeqPos s = seek(ckpt, unit);
+    (void)advance(in, n, s, unit);
+    *out = (int64_t)s.p;
+}
+
 } // namespace
 
 namespace acgpu {
 
+int utf8_map_records(const Utf8Text &text, int32_t *d_recs, uint64_t cnt, uint32_t cols, hipStream_t stream) {
+    if (!text.d_ckpt || !cnt) return ACGPU_OK;
+    hipLaunchKernelGGL(k_utf8_map, dim3((unsigned)((cnt + kU8Threads - 1) / kU8Threads)), dim3(kU8Threads), 0, stream, d_recs, cnt, cols,
+                       text.d_bytes, (uint32_t)text.n_bytes, (uint32_t)text.n_units, text.d_ckpt);
+    HIP_TRY(hipGetLastError());
+    return ACGPU_OK;
+}
+
+int utf8_map_position(const Utf8Text &text, uint64_t unit, int64_t *d_out, hipStream_t stream) {
+    if (!text.d_ckpt || unit >= text.n_units) return ACGPU_E_INVALID; // (a checkpoint is written for the text's units only)
+    hipLaunchKernelGGL(k_utf8_pos, dim3(1), dim3(1), 0, stream, (uint32_t)unit, text.d_bytes, (uint32_t)text.n_bytes, text.d_ckpt, d_out);
+    HIP_TRY(hipGetLastError());
+    return ACGPU_OK;
+}
+
 int stage_utf8_text(DeviceState &d, const uint8_t *bytes, uint64_t n_bytes, hipStream_t stream, Utf8Text *out) {
     *out = Utf8Text{};
+    out->n_bytes = n_bytes;
     const uint32_t n = (uint32_t)n_bytes, n_blocks = (n + kU8Block - 1) / kU8Block;
     // aux: [n_units, first_bad | block sums | checkpoints, one per 32 units of a text that has at most n units]
     const size_t sums_off = 64, ckpt_off = sums_off + (((size_t)n_blocks * 4 + 63) & ~(size_t)63);
@@ -312,12 +338,7 @@ int acgpu_match_utf8(const acgpu_automaton *ca, const uint8_t *bytes, uint64_t n
     rc = match_shard(a, d, &text.shard, record_kind, d.stage_out.p, cap, n_out, stream, nullptr);
     if (rc != ACGPU_OK) return rc; // (ACGPU_E_OVERFLOW: *n_out is the capacity to call again with)
     if (!*n_out) return ACGPU_OK;
-    if (text.d_ckpt) {
-        hipLaunchKernelGGL(k_utf8_map, dim3((unsigned)((*n_out + kU8Threads - 1) / kU8Threads)), dim3(kU8Threads), 0, stream,
-                           reinterpret_cast<int32_t *>(d.stage_out.p), *n_out, (uint32_t)record_kind / 4, text.d_bytes, (uint32_t)n_bytes,
-                           (uint32_t)text.n_units, text.d_ckpt);
-        HIP_TRY(hipGetLastError());
-    }
+    if ((rc = utf8_map_records(text, reinterpret_cast<int32_t *>(d.stage_out.p), *n_out, (uint32_t)record_kind / 4, stream))) return call.fail(rc);
     HIP_TRY(hipMemcpyAsync(out, d.stage_out.p, *n_out * (uint64_t)record_kind, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return ACGPU_OK;

@@ -274,6 +274,45 @@ class Automaton:
             N.check(rc, "acgpu_replace_u16")
             return out[:n_out.value], {f: int(getattr(st, f)) for f, _ in N.ReplaceStats._fields_}
 
+    def _replacements_utf8(self, replacements):
+        """as _replacements, in bytes: a str is encoded as UTF-8; bytes, bytearray and uint8 arrays are taken as they are (and
+        not validated) -> (bytes, offsets, n_repl)"""
+        if isinstance(replacements, (str, bytes, bytearray)):
+            replacements = [replacements]
+        elif len(replacements) != len(self.keywords):
+            raise ValueError("%d replacements for %d keywords" % (len(replacements), len(self.keywords)))
+        parts = [_utf8_bytes(r.encode("utf-8") if isinstance(r, str) else r) for r in replacements]
+        off = np.zeros(len(parts) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([p.size for p in parts], dtype=np.uint64)
+        blob = np.concatenate(parts + [np.zeros(1, np.uint8)])  # (never an empty array: its pointer is read as "no table")
+        return np.ascontiguousarray(blob, dtype=np.uint8), off, len(parts)
+
+    def replace_utf8(self, data, replacements, cap=None, stats=None):
+        """acgpu_replace_utf8: a UTF-8 haystack (bytes, bytearray, memoryview or uint8 array) in host memory -> (the rewritten
+        bytes as a uint8 array, stats dict); outside the matches a byte-for-byte copy.  `replacements`: a list with one str
+        (encoded as UTF-8), bytes, bytearray or uint8 array per keyword given to the constructor, or a single one for all of
+        them.  Ill-formed input raises Utf8Error.  The one retry of replace_host; stats: an N.Utf8Stats to fill in, if wanted."""
+        buf = _utf8_bytes(data)
+        n = int(buf.size)
+        buf_in = buf if n else np.zeros(1, np.uint8)
+        r_bytes, off, n_repl = self._replacements_utf8(replacements)
+        if cap is None:
+            cap = n + n // 4 + 64
+        st = N.ReplaceStats()
+        ust = stats if stats is not None else N.Utf8Stats()
+        for attempt in (0, 1):
+            out = np.empty(max(cap, 1), dtype=np.uint8)
+            n_out = ctypes.c_uint64(0)
+            rc = N.lib().acgpu_replace_utf8(self._h, _vp(buf_in), n, _vp(r_bytes), _vp(off), n_repl, _vp(out), cap, ctypes.byref(n_out),
+                                            ctypes.byref(st), ctypes.byref(ust))
+            if rc == N.E_OVERFLOW and attempt == 0:
+                cap = int(n_out.value)
+                continue
+            if rc == N.E_ENCODING:
+                raise Utf8Error(ust.first_bad)
+            N.check(rc, "acgpu_replace_utf8")
+            return out[:n_out.value], {f: int(getattr(st, f)) for f, _ in N.ReplaceStats._fields_}
+
     def replace_batch(self, haystacks, replacements, cap=None):
         """acgpu_replace_batch_u16: many short haystacks (str or uint16 arrays) rewritten in one call -> (units, out_offsets,
         stats dict): the result of haystack i is units[out_offsets[i]:out_offsets[i + 1]].  `replacements` as for replace_host,
@@ -673,6 +712,14 @@ class StringSet(_BatchDecisions):
         of microseconds of fixed cost) -> a list of str."""
         return _split_batch(*self._auto.replace_batch(_checked(haystacks), str(replacement))[:2])
 
+    def replace_utf8(self, data, replacement):
+        """Not in the reference: the UTF-8 haystack `data` (bytes, bytearray, memoryview or uint8 array) with every match
+        replaced by `replacement` (a str, encoded as UTF-8, or bytes taken as they are; empty deletes the matches) -> bytes,
+        rewritten on the device without a decode or an encode on the host.  Utf8Error if `data` is ill-formed."""
+        if data is None:
+            raise TypeError("haystack is None")
+        return self._auto.replace_utf8(data, replacement if isinstance(replacement, (bytes, bytearray)) else str(replacement))[0].tobytes()
+
     def find_all(self, haystack):
         """Convenience (not in the reference): the (n,2) int32 array of (start, end) records."""
         return self._auto.match_host(utf16(haystack), with_ids=False)
@@ -772,6 +819,15 @@ class StringMap(_BatchDecisions):
         """Not in the reference: [replace(h, replacements) for h in haystacks] in ONE device call (see
         StringSet.replace_batch) -> a list of str."""
         return _split_batch(*self._auto.replace_batch(_checked(haystacks), self._replacements_for(replacements))[:2])
+
+    def replace_utf8(self, data, replacements=None):
+        """Not in the reference: the UTF-8 haystack `data` with every match replaced -> bytes (see StringSet.replace_utf8);
+        `replacements` under the rules of replace(), a str encoded as UTF-8, bytes taken as they are."""
+        if data is None:
+            raise TypeError("haystack is None")
+        if not isinstance(replacements, (bytes, bytearray)):
+            replacements = self._replacements_for(replacements)
+        return self._auto.replace_utf8(data, replacements)[0].tobytes()
 
     def _replacements_for(self, replacements):
         if replacements is None:

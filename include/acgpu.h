@@ -683,8 +683,8 @@ int acgpu_summary_batch_u16(const acgpu_automaton *a, const uint16_t *units, con
  * The call is ONE shard through the general path: neither the chunk-pipelined form acgpu_match_u16 takes from 2^25 units on
  * (a long text is copied whole before the scan begins, nothing overlaps), nor its one-launch form for texts of up to 4096 units
  * (a short text pays the fixed cost of five launches, two copies and two waits, several times that form's latency: batch short
- * texts, or decode them on the host).  Not built: count, replace, batch, cursor, stream, device-resident and multi-device forms
- * for UTF-8; lossy decoding (U+FFFD); CESU-8 / WTF-8; the Java facade (its strings are UTF-16).  ACGPU_ABI_VERSION stays as it
+ * texts, or decode them on the host).  Not built: count, batch, cursor, stream, device-resident and multi-device forms
+ * for UTF-8 (replace: acgpu_replace_utf8 below); lossy decoding (U+FFFD); CESU-8 / WTF-8; the Java facade (its strings are UTF-16).  ACGPU_ABI_VERSION stays as it
  * is: adding symbols is compatible.
  */
 typedef struct acgpu_utf8_stats {
@@ -695,6 +695,43 @@ typedef struct acgpu_utf8_stats {
 } acgpu_utf8_stats;
 int acgpu_match_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, int record_kind, void *out, uint64_t cap,
                      uint64_t *n_out, acgpu_utf8_stats *stats /* may be NULL */);
+
+/*
+ * Replace for a UTF-8 text in HOST memory: bytes in, rewritten bytes out, nothing decoded or encoded on the host.  With
+ * r_0 .. r_{k-1} the Map records acgpu_match_utf8 returns for `bytes` (BYTE offsets), in their order, the result is
+ *   bytes[0:s_0] + repl[id_0] + bytes[e_0:s_1] + repl[id_1] + ... + bytes[e_{k-1}:n_bytes]
+ * -- outside the matches a byte-for-byte copy of the caller's buffer; nothing is re-encoded.
+ *  repl_bytes / repl_off / n_repl : the table of acgpu_replace_u16 with BYTES for units: replacement i is
+ *              repl_bytes[repl_off[i] .. repl_off[i+1]), n_repl is the number of keywords given to acgpu_build or 1, an empty
+ *              entry deletes the match.  The bytes are copied as given and NOT validated: the result is well-formed UTF-8 when
+ *              every replacement is.
+ *  cap, *n_out : in BYTES, as for acgpu_replace_u16: a result of more than cap bytes gives ACGPU_E_OVERFLOW with *n_out (and
+ *              st->units_out, which counts bytes here) exact, nothing at or beyond out[cap] written; out == NULL with cap == 0
+ *              counts only.
+ *  families  : ACGPU_MODE_LONGEST, _SHORTEST, _WHOLEWORD, _WWLONGEST.  ACGPU_MODE_ALL: ACGPU_E_UNSUPPORTED.  An automaton one of
+ *              whose keywords holds an UNPAIRED SURROGATE: ACGPU_E_UNSUPPORTED as well -- by the mapping rule a match that begins
+ *              or ends inside a surrogate pair covers all four bytes of the code point, so two records could cover the same
+ *              bytes, and replace rests on records that do not overlap.  With well-formed keywords every record begins and ends
+ *              on a code-point boundary, and records that do not overlap in units do not overlap in bytes.  Both refusals come
+ *              before any device is touched, as do the ACGPU_E_INVALID of NULL a, bytes or n_out, cap without out,
+ *              n_bytes >= 2^31 and a bad replacement table.
+ *  ill-formed input : ACGPU_E_ENCODING with ust->first_bad as for acgpu_match_utf8; *n_out = 0, `out` is untouched, the pool
+ *              stays usable.
+ *  n_bytes == 0 : ACGPU_OK, *n_out = 0, no device needed.
+ *  st, ust   : may be NULL.  st->n_records: matches replaced; st->units_out: bytes of the result; ust as acgpu_match_utf8 fills it.
+ * Works on the NULL stream, under the pool's lock (STREAM RULE above: tickets in flight on the pool give ACGPU_E_INVALID).
+ * How it works: the text is staged as acgpu_match_utf8 stages it (validated, transcoded, checkpoints) and scanned in UNITS
+ * through the pieces of acgpu_replace_device; behind every piece k_utf8_map rewrites its records in the reservoir to byte
+ * offsets, and one lane maps the piece's boundary to the first byte of the code point that holds it (rounded down: that only
+ * withholds more).  From there on everything counts bytes: the plan runs unchanged over byte records and a byte table, and the
+ * byte form of the emit kernel writes 16 output bytes per lane from the caller's bytes on the device and the table, through
+ * the two slabs of acgpu_replace_u16 ("replace_slab_units" counts bytes here).
+ * Not built: batch, device-resident, multi-device and stream forms; validating the replacements; the Java facade.
+ * ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
+ */
+int acgpu_replace_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, const uint8_t *repl_bytes,
+                       const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap, uint64_t *n_out,
+                       acgpu_replace_stats *st /* may be NULL */, acgpu_utf8_stats *ust /* may be NULL */);
 
 /*
  * Synthetic haystack generator of the benchmark: unit i of the stream is
@@ -746,7 +783,7 @@ int acgpu_stream_probe(const void *d_buf, uint64_t n_bytes, void *stream, int re
  * 2^26) and "cursor_reservoir_bytes" (largest reservoir, 256 MiB); "states_chunk_log2" (k_ac_states: a lane's chunk, 0 = by the text's
  * length, 8 .. 10 = forced) and the counting calls' A/B switches "count_form" (bits: 1 never the direct form, 2 no LDS counters
  * in k_states_hist, 4 no same-key peel in k_states_hist / k_count_ids); "replace_slab_units" (acgpu_replace_u16: units of one of the
- * two device slabs its result leaves through, default 2^25).  Returns the previous value, -1 for an unknown name. */
+ * two device slabs its result leaves through, default 2^25; it counts OUTPUT ELEMENTS, so for acgpu_replace_utf8 bytes).  Returns the previous value, -1 for an unknown name. */
 int64_t acgpu_set_tunable(const char *name, int64_t value);
 
 const char *acgpu_strerror(int code);
