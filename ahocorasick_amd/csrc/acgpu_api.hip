@@ -794,8 +794,8 @@ int setup_dfa_scan(acgpu_automaton *a, DeviceState &d, CallRecord &r, AllScan &A
     ScanLaunch L{};
     L.block = scan_block_threads();
     L.grid = d.n_cu * (int)std::max<int64_t>(1, tunables().blocks_per_cu);
-    // tile_debug bit 2^43: the one-chain kernel of rounds 1-3 (A/B); bit 2^45 (ablation build): no lookups in global memory
-    L.debug = (uint32_t)((tunables().tile_debug >> 43) & 5);
+    // kSelDfaOneChain: the one-chain kernel of rounds 1-3 (A/B); kSelDfaNoGlobal (ablation build): no lookups in global memory
+    L.debug = ((tunables().tile_debug & kSelDfaOneChain) ? kScanOneChain : 0u) | ((tunables().tile_debug & kSelDfaNoGlobal) ? 4u : 0u);
     if (sh->n_units < 64) L.debug |= kScanOneChain; // (k_ac_dfa takes the buffer's last vector whole: the old kernel reads unit by unit)
     const uint64_t lanes = (uint64_t)L.grid * L.block * (uint64_t)((L.debug & kScanOneChain) ? 1 : std::max(1, scan_chains(d.T)));
     uint64_t C = tunables().chunk_units > 0 ? (uint64_t)tunables().chunk_units
@@ -932,7 +932,7 @@ int enqueue_all(acgpu_automaton *a, DeviceState &d, CallRecord &r, int level) {
 // "length" this is the greedy chain of LongestMatchSet, and the Longest chain kernels mark it (tiles of indices with
 // synchronisation points, one lane per tile, a bit per visited index; acgpu_longest.hip, acgpu_wwlongest.hip: k_wwl_jumps);
 // pointer doubling -- ceil(log2 M) rounds over all M elements -- otherwise (tiny inputs, jumps beyond 16 bits, tunable
-// tile_debug bit 2097152).  The doubling squares the jump table: *d_nxt_kept is where the successors survive
+// tile_debug bit kSelMarkDoubling).  The doubling squares the jump table: *d_nxt_kept is where the successors survive
 // (d_nxt itself, or d_nxt_copy -- M + 1 words, may be null if the caller does not need them).
 // jump_bound: what the caller knows nxt[k] - k cannot exceed (0: unknown -- the largest jump is measured).  The one pass has a
 // fixed cost (a read-back, four small launches) that 21 doubling rounds over a million elements do not reach: it is taken
@@ -941,9 +941,9 @@ int mark_chain(DeviceState &d, uint32_t *d_nxt, uint32_t *d_tmp, uint32_t *d_mar
                uint32_t *d_nxt_copy, const uint32_t **d_nxt_kept, uint32_t jump_bound) {
     int rc;
     if (d_nxt_kept) *d_nxt_kept = d_nxt;
-    // (tunable tile_debug: bit 2097152 = always the doubling, bit 4194304 = the one pass from 64 elements on -- tests)
-    const uint32_t one_pass_from = (tunables().tile_debug & 4194304) ? 64u : (1u << 22);
-    bool one_pass = M >= one_pass_from && jump_bound <= 60000 && !(tunables().tile_debug & 2097152);
+    // (tunable tile_debug: kSelMarkDoubling = always the doubling, kSelMarkOnePassEarly = the one pass from 64 elements on -- tests)
+    const uint32_t one_pass_from = (tunables().tile_debug & kSelMarkOnePassEarly) ? 64u : (1u << 22);
+    bool one_pass = M >= one_pass_from && jump_bound <= 60000 && !(tunables().tile_debug & kSelMarkDoubling);
     uint64_t head = ~0ull, max_jump = 0;
     if (one_pass) {
         // counter words used here: [2] chain head, [3] largest jump (bytes 16..32) of the line the caller has borrowed
@@ -993,7 +993,7 @@ int mark_chain(DeviceState &d, uint32_t *d_nxt, uint32_t *d_tmp, uint32_t *d_mar
     Cn.record_kind = ACGPU_REC_SET;
     if ((rc = d.chain.ensure((size_t)Cn.n_tiles * 4 + 64))) return rc;
     HIP_TRY(launch_longest_sync(Cn, (uint32_t *)d.chain.p, stream));
-    HIP_TRY(launch_longest_chain_lds(Cn, (const uint32_t *)d.chain.p, /*write_pass=*/false, stream));
+    HIP_TRY(launch_longest_chain_lds(Cn, (const uint32_t *)d.chain.p, stream));
     HIP_TRY(launch_wwl_bits_to_mark((const uint32_t *)d.chainbits.p, M, d_mark, stream));
     return ACGPU_OK;
 }
@@ -1177,6 +1177,37 @@ int enqueue_longest_bits(acgpu_automaton *a, DeviceState &d, CallRecord &r, uint
     return close_call(r, CallForm::LongestBits, "k_longest_bits", sh->own_end - sh->own_begin, /*done_is_ev2=*/timed); // (the finish kernel's own end)
 }
 
+// What the chain stage of a LONGEST call is told whichever pipeline runs in front of it: the shard's bounds and the chain's entry,
+// the per-tile counts and their offsets, the records' place, the chain's exit.  (Called with those buffers allocated; the
+// tiles, the lengths and the bitmaps are the pipeline's own.)
+LongestChainLaunch longest_chain_launch(const HostTables &t, const DeviceState &d, const CallRecord &r, uint64_t entry) {
+    LongestChainLaunch Cn{};
+    Cn.d_out_id = d.T.term_id; // state[] holds the trie node of the longest keyword starting at a position
+    Cn.own_begin = (uint32_t)r.shard.own_begin;
+    Cn.own_end = (uint32_t)r.shard.own_end;
+    Cn.entry = (uint32_t)entry;
+    Cn.max_len = t.max_len;
+    Cn.d_counts = (uint32_t *)d.chunk_counts.p;
+    Cn.d_offsets = (const uint64_t *)d.offsets.p;
+    Cn.d_out = r.d_out;
+    Cn.cap = r.cap;
+    Cn.record_kind = r.record_kind;
+    Cn.d_exit = (unsigned long long *)d.counter.p;
+    Cn.len_units = (uint32_t)r.shard.n_units;
+    return Cn;
+}
+
+// {count, 0, exit} into the call's pinned host slot (and the device result) by the pipeline's last kernel: the count is the
+// grand total the prefix sum over n_tiles counts left, the exit what the count pass wrote into the counter line
+int publish_chain_result(const DeviceState &d, CallRecord &r, uint32_t n_tiles) {
+    int rc;
+    unsigned long long *d_slot = nullptr;
+    if ((rc = slot_on_device(r, &d_slot))) return rc;
+    HIP_TRY(launch_publish_result((const unsigned long long *)d.scan_tmp.p + scan_tiles_for(n_tiles), (const unsigned long long *)d.counter.p,
+                                  d_slot, reinterpret_cast<acgpu_device_result *>(r.shard.d_result), r.stream));
+    return ACGPU_OK;
+}
+
 // Any other dense dictionary with range classes or small class pages, long texts, Set and Map records: the walks of the chain's own
 // positions only (k_longest_follow, acgpu_longest_follow.hip) in place of the length array, the synchronisation points and the chain
 // pass; the bitmaps, counts and first positions it leaves are what the prefix sum and k_longest_emit_ends below read.  It checks its
@@ -1238,36 +1269,21 @@ int enqueue_longest_follow(acgpu_automaton *a, DeviceState &d, CallRecord &r, ui
     if (r.profiled) HIP_TRY(hipEventRecord(r.ev[0], stream));
     HIP_TRY(launch_longest_follow(d.T, F, t.range_cls, r.record_kind == ACGPU_REC_MAP, stream));
     if (r.profiled) HIP_TRY(hipEventRecord(r.ev[1], stream));
-    LongestChainLaunch Cn{};
+    LongestChainLaunch Cn = longest_chain_launch(t, d, r, entry); // (its counts and exit: what F.d_counts and F.d_exit point to)
     Cn.d_state = F.d_state;
-    Cn.d_out_id = d.T.term_id;
-    Cn.len_bytes = 1;
-    Cn.own_begin = (uint32_t)sh->own_begin;
-    Cn.own_end = (uint32_t)sh->own_end;
-    Cn.entry = (uint32_t)entry;
+    Cn.len_bytes = 1; // (no lengths: the emit pass reads the two bitmaps)
     Cn.tile_units = seg_units << F.tile_log2;
     Cn.n_tiles = n_tiles;
-    Cn.max_len = t.max_len;
-    Cn.d_counts = F.d_counts;
-    Cn.d_offsets = (const uint64_t *)d.offsets.p;
-    Cn.d_out = r.d_out;
-    Cn.cap = r.cap;
-    Cn.record_kind = r.record_kind;
-    Cn.d_exit = F.d_exit;
-    Cn.len_units = (uint32_t)sh->n_units;
     Cn.d_bits = F.d_bits;
     Cn.d_ebits = F.d_ebits;
     HIP_TRY(launch_exclusive_scan(Cn.d_counts, Cn.n_tiles, (uint64_t *)d.offsets.p, (uint64_t *)d.scan_tmp.p, stream));
     HIP_TRY(launch_longest_emit(Cn, F.d_sync, stream));
     if (r.profiled) HIP_TRY(hipEventRecord(r.ev[2], stream));
-    unsigned long long *d_slot = nullptr;
-    if ((rc = slot_on_device(r, &d_slot))) return rc;
-    HIP_TRY(launch_publish_result((const unsigned long long *)d.scan_tmp.p + scan_tiles_for(Cn.n_tiles), (const unsigned long long *)d.counter.p,
-                                  d_slot, reinterpret_cast<acgpu_device_result *>(sh->d_result), stream));
+    if ((rc = publish_chain_result(d, r, Cn.n_tiles))) return rc;
     return close_call(r, CallForm::LongestFollow, "k_longest_follow", sh->own_end - sh->own_begin);
 }
 
-// The walk pipeline: reverse scan -> chain count -> prefix sum -> chain write.
+// The walk pipeline: a length for every position (the walk), then the chain: synchronisation points -> count pass -> prefix sum -> emit pass.
 int enqueue_longest_walk(acgpu_automaton *a, DeviceState &d, CallRecord &r, uint64_t entry) {
     const HostTables &t = a->t;
     const acgpu_shard *sh = &r.shard;
@@ -1294,25 +1310,23 @@ int enqueue_longest_walk(acgpu_automaton *a, DeviceState &d, CallRecord &r, uint
     if (t.dense && t.n_cls) lds_rows = (uint32_t)std::min<uint64_t>(t.n_states, (72 * 1024 - walk_pages) / ((uint64_t)t.n_cls * 4));
     // range classes (case sensitive, keyword units within a span of 63) take the lean walk; tunable force_kernel=1
     // keeps the general one
-    S.pairs = t.dense && t.range_cls && t.n_cls == t.cls_span + 1 && tunables().force_kernel != 1 &&
-              (uint64_t)t.n_states * t.n_cls * 4 < (1ull << 31);
-    if (S.pairs) lds_rows = (uint32_t)std::min<uint64_t>(t.n_states, (72 * 1024) / ((uint64_t)t.n_cls * 4) - 2);
+    const bool range = t.dense && t.range_cls && t.n_cls == t.cls_span + 1 && tunables().force_kernel != 1 &&
+                       (uint64_t)t.n_states * t.n_cls * 4 < (1ull << 31);
+    S.form = range ? LongestWalkForm::Range : LongestWalkForm::General;
+    if (range) lds_rows = (uint32_t)std::min<uint64_t>(t.n_states, (72 * 1024) / ((uint64_t)t.n_cls * 4) - 2);
     S.lds_rows = lds_rows;
-    S.lds_bytes = std::max<size_t>((size_t)(lds_rows + (S.pairs ? 2 : 0)) * t.n_cls * 4, 16) + (S.pairs ? 0 : walk_pages);
-    S.pages_bytes = S.pairs ? 0u : (uint32_t)walk_pages; // (0: classes from the table in global memory)
-    // the work-list form of the range-class walk (tunable force_kernel=4 keeps the lock-step form): 16-bit lengths, LDS rows
-    // below 64 KiB (the row offset is the low word of an entry), two workgroups per CU
-    if (S.pairs && S.len_bytes == 2 && t.max_len < 64000 && tunables().force_kernel != 4) {
-        S.pairs = 2;
+    S.lds_bytes = std::max<size_t>((size_t)(lds_rows + (range ? 2 : 0)) * t.n_cls * 4, 16) + (range ? 0 : walk_pages);
+    S.pages_bytes = range ? 0u : (uint32_t)walk_pages; // (0: classes from the table in global memory)
+    int rc;
+    // the work-list form of the range-class walk (tunable force_kernel=4 keeps the lock-step form): keywords below 64000 units,
+    // LDS rows below 64 KiB (the row offset is the low word of an entry), two workgroups per CU.  It stores ONE byte per length,
+    // 255 = "255 or more: see the 16-bit side array" -- half the bytes written by the walk and read back by the chain passes
+    if (range && t.max_len < 64000 && tunables().force_kernel != 4) {
+        S.form = LongestWalkForm::RangeList;
         S.lds_rows = lds_rows = std::min<uint32_t>(t.n_states, longest_list_max_rows(t.n_cls, record_kind == ACGPU_REC_MAP));
         S.lds_bytes = longest_list_lds_bytes(record_kind == ACGPU_REC_MAP);
         // two workgroups per CU (Set records: 60 KiB of rows + 17 KiB of lists each; Map: 52 + 26)
         S.grid = (int)std::min<uint64_t>(2ull * d.n_cu, (own_len + 16 * 1024 - 1) / (16 * 1024));
-    }
-    int rc;
-    // the work-list form stores ONE byte per length, 255 = "255 or more: see the 16-bit side array" (tunable tile_debug bit
-    // 8388608: 16-bit lengths, for A/B) -- half the bytes written by the walk and read back by the chain passes
-    if (S.pairs == 2 && !(tunables().tile_debug & 8388608)) {
         S.len_bytes = 1;
         if ((rc = d.lenbig.ensure((size_t)sh->n_units * 2 + 64))) return rc;
         S.d_len_big = (uint16_t *)d.lenbig.p;
@@ -1327,46 +1341,35 @@ int enqueue_longest_walk(acgpu_automaton *a, DeviceState &d, CallRecord &r, uint
         S.d_state = (uint32_t *)d.statebuf.p;
     }
     // Set records over a small alphabet: k_longest_block (first round through the root table, the live walks through its own
-    // work list), then the general kernel for the chunks it flagged (tunable tile_debug bit 16777216: the general kernel for
-    // everything).  A wave's span must fit the 16-bit lane positions of its queue.
+    // work list), then the general kernel for the chunks it flagged.  A wave's span must fit the 16-bit lane positions of its
+    // queue.
     const uint64_t blk_waves = (uint64_t)S.grid * (S.block / 64), blk_chunks = (own_len + 1023) / 1024;
     const uint64_t blk_span = (blk_chunks + blk_waves - 1) / std::max<uint64_t>(blk_waves, 1);
-    const bool root_form = S.pairs == 2 && S.len_bytes == 1 && record_kind == ACGPU_REC_SET && d.T.root_b != 0 &&
-                           !(tunables().tile_debug & 16777216) && blk_span * 1024 <= (1u << 19) && sh->n_units >= 4096 &&
-                           (sh->own_begin & 7) == 0;
+    const bool root_form = S.form == LongestWalkForm::RangeList && record_kind == ACGPU_REC_SET && d.T.root_b != 0 &&
+                           blk_span * 1024 <= (1u << 19) && sh->n_units >= 4096 && (sh->own_begin & 7) == 0;
     if (root_form) {
         S.span_chunks = (uint32_t)blk_span;
         if ((rc = d.todo.ensure(blk_chunks + 64))) return rc;
         S.d_todo_w = (uint8_t *)d.todo.p;
     }
-    LongestChainLaunch Cn{};
     // positions per chain lane: the synchronisation scan skips 64-position blocks that cannot reach the tile, so tiles
     // can stay small (more lanes, shorter dependent chains) even when keywords are long
     // (measured at config 4: 6144 positions per lane are best with 256-position chunks of one-byte lengths -- 4096: +15 %,
     // 8192: +3 %, 12288: +22 % for the chain passes; small inputs get more, shorter lanes)
     const uint64_t T_units = tunables().region_units > 0 ? (uint64_t)tunables().region_units : (own_len >= (1ull << 24) ? 6144 : 1024);
-    Cn.tile_units = (uint32_t)T_units;
-    Cn.n_tiles = (uint32_t)((sh->own_end - entry + T_units - 1) / T_units);
+    const uint32_t n_tiles = (uint32_t)((sh->own_end - entry + T_units - 1) / T_units);
     if ((rc = borrow_counter_line(d, stream, /*clear=*/true))) return rc;
-    if ((rc = d.chunk_counts.ensure((size_t)Cn.n_tiles * 4))) return rc;
-    if ((rc = d.offsets.ensure((size_t)Cn.n_tiles * 8))) return rc;
-    if ((rc = d.scan_tmp.ensure(((size_t)Cn.n_tiles / 2048 + 2) * 8))) return rc;
+    if ((rc = d.chunk_counts.ensure((size_t)n_tiles * 4))) return rc;
+    if ((rc = d.offsets.ensure((size_t)n_tiles * 8))) return rc;
+    if ((rc = d.scan_tmp.ensure(((size_t)n_tiles / 2048 + 2) * 8))) return rc;
+    LongestChainLaunch Cn = longest_chain_launch(t, d, r, entry);
+    Cn.tile_units = (uint32_t)T_units;
+    Cn.n_tiles = n_tiles;
     Cn.d_len = d.lenbuf.p;
     Cn.d_len_big = S.d_len_big;
     Cn.d_state = S.d_state;
-    Cn.d_out_id = d.T.term_id; // state[] holds the trie node of the longest keyword starting at a position
     Cn.len_bytes = S.len_bytes;
-    Cn.own_begin = (uint32_t)sh->own_begin;
-    Cn.own_end = (uint32_t)sh->own_end;
     Cn.d_blockmax = S.d_blockmax;
-    Cn.entry = (uint32_t)entry;
-    Cn.max_len = t.max_len;
-    Cn.d_counts = (uint32_t *)d.chunk_counts.p;
-    Cn.d_offsets = (const uint64_t *)d.offsets.p;
-    Cn.d_out = r.d_out;
-    Cn.cap = r.cap;
-    Cn.record_kind = record_kind;
-    Cn.d_exit = (unsigned long long *)d.counter.p;
     if (r.profiled) HIP_TRY(hipEventRecord(r.ev[0], stream));
     const char *kname = "";
     if (root_form) {
@@ -1382,37 +1385,22 @@ int enqueue_longest_walk(acgpu_automaton *a, DeviceState &d, CallRecord &r, uint
     if (r.profiled) HIP_TRY(hipEventRecord(r.ev[1], stream));
     if ((rc = d.chain.ensure((size_t)Cn.n_tiles * 4 + 64))) return rc;
     uint32_t *d_sync = (uint32_t *)d.chain.p;
-    // Chain: synchronisation points, a count pass that also marks the chain's matches in a bitmap, prefix sum, and the
-    // records written position-parallel from the bitmap (k_longest_emit).  16-bit lengths take the count pass that reads the
-    // lengths through LDS in chunks (k_longest_chain_lds).  Tunable tile_debug, for A/B: bit 65536 = the serial write pass
-    // instead of bitmap + emit, bit 131072 = the count/write passes that read the lengths from global memory.
-    Cn.d_bits = nullptr;
-    Cn.d_ebits = nullptr;
-    Cn.len_units = (uint32_t)sh->n_units;
-    const bool serial_write = (tunables().tile_debug & 65536) != 0;
-    const bool chain_lds = Cn.len_bytes <= 2 && !(tunables().tile_debug & 131072);
-    if (!serial_write) {
-        const size_t bit_bytes = ((size_t)sh->n_units / 128 + 2) * 16; // whole groups of four words (16-byte stores)
-        // (a second bitmap of match ends for the emit pass; tile_debug bit 524288: without it, the emit pass looks lengths up)
-        const bool end_bits = chain_lds && !(tunables().tile_debug & 524288);
-        if ((rc = d.chainbits.ensure(bit_bytes * (end_bits ? 2 : 1)))) return rc;
-        Cn.d_bits = (uint32_t *)d.chainbits.p;
-        if (end_bits) Cn.d_ebits = Cn.d_bits + bit_bytes / 4;
-        HIP_TRY(hipMemsetAsync(d.chainbits.p, 0, bit_bytes * (end_bits ? 2 : 1), stream));
-    }
+    // Chain: synchronisation points; the count pass, which marks the chain's matches in a bitmap -- through LDS for 1- and 2-byte
+    // lengths (k_longest_chain_lds), which also marks their ends in a second bitmap, from global memory for 4-byte lengths
+    // (k_longest_chain); prefix sum; the records written position-parallel from the bitmaps.
+    const bool lds_pass = Cn.len_bytes <= 2;
+    const size_t bit_bytes = ((size_t)sh->n_units / 128 + 2) * 16; // whole groups of four words (16-byte stores)
+    if ((rc = d.chainbits.ensure(bit_bytes * (lds_pass ? 2 : 1)))) return rc;
+    Cn.d_bits = (uint32_t *)d.chainbits.p;
+    Cn.d_ebits = lds_pass ? Cn.d_bits + bit_bytes / 4 : nullptr;
+    HIP_TRY(hipMemsetAsync(d.chainbits.p, 0, bit_bytes * (lds_pass ? 2 : 1), stream));
     HIP_TRY(launch_longest_sync(Cn, d_sync, stream));
-    if (chain_lds) HIP_TRY(launch_longest_chain_lds(Cn, d_sync, /*write_pass=*/false, stream));
-    else HIP_TRY(launch_longest_chain(Cn, d_sync, /*write_pass=*/false, stream));
+    if (lds_pass) HIP_TRY(launch_longest_chain_lds(Cn, d_sync, stream));
+    else HIP_TRY(launch_longest_chain(Cn, d_sync, stream));
     HIP_TRY(launch_exclusive_scan(Cn.d_counts, Cn.n_tiles, (uint64_t *)d.offsets.p, (uint64_t *)d.scan_tmp.p, stream));
-    if (!serial_write) HIP_TRY(launch_longest_emit(Cn, d_sync, stream));
-    else if (chain_lds) HIP_TRY(launch_longest_chain_lds(Cn, d_sync, /*write_pass=*/true, stream));
-    else HIP_TRY(launch_longest_chain(Cn, d_sync, /*write_pass=*/true, stream));
+    HIP_TRY(launch_longest_emit(Cn, d_sync, stream));
     if (r.profiled) HIP_TRY(hipEventRecord(r.ev[2], stream));
-    // {count, 0, exit} into the call's pinned host slot (and the device result) by the pipeline's last kernel
-    unsigned long long *d_slot = nullptr;
-    if ((rc = slot_on_device(r, &d_slot))) return rc;
-    HIP_TRY(launch_publish_result((const unsigned long long *)d.scan_tmp.p + scan_tiles_for(Cn.n_tiles), (const unsigned long long *)d.counter.p,
-                                  d_slot, reinterpret_cast<acgpu_device_result *>(sh->d_result), stream));
+    if ((rc = publish_chain_result(d, r, Cn.n_tiles))) return rc;
     return close_call(r, CallForm::LongestWalk, kname, own_len);
 }
 
@@ -2323,9 +2311,9 @@ int match_host_text(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack
                     uint64_t cap, uint64_t *n_out) {
     const HostTables &t = a->t;
     int rc;
-    // short haystacks: one launch, no copies (tunable tile_debug bit 2^41, or a kernel form forced by "force_kernel": the
+    // short haystacks: one launch, no copies (tunable tile_debug bit kSelNoSmallCall, or a kernel form forced by "force_kernel": the
     // general path -- for A/B, and for the tests that run the scan kernels on the short edge-case inputs)
-    if (n_units > 0 && n_units <= kSmallMaxUnits && d.inflight == 0 && small_call_supported(t) && !(tunables().tile_debug & (1ll << 41)) &&
+    if (n_units > 0 && n_units <= kSmallMaxUnits && d.inflight == 0 && small_call_supported(t) && !(tunables().tile_debug & kSelNoSmallCall) &&
         tunables().force_kernel == 0) {
         bool handled = false;
         rc = match_small(a, d, haystack, n_units, record_kind, out, cap, n_out, &handled);
@@ -2333,7 +2321,7 @@ int match_host_text(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack
     }
     // long haystacks: the pipelined form, unless the text is one piece (the loops that only exist as a sequential kernel over
     // the whole text -- WholeWord / WholeWordLongestSet with a fold-inconsistent table -- take the plain one)
-    if (n_units >= 2 * kHostChunkUnits && !host_one_piece(t, record_kind) && d.inflight == 0 && !(tunables().tile_debug & 33554432)) {
+    if (n_units >= 2 * kHostChunkUnits && !host_one_piece(t, record_kind) && d.inflight == 0 && !(tunables().tile_debug & kSelNoHostChunks)) {
         int64_t chain = 0;
         if ((rc = scan_host_range(a, d, haystack, n_units, 0, n_units, 0, n_units, record_kind, cap, n_out, &chain)) || !*n_out) return rc;
         HIP_TRY(hipMemcpyAsync(out, d.stage_out.p, *n_out * (uint64_t)record_kind, hipMemcpyDeviceToHost, d.call_stream));

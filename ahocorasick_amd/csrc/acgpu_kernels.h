@@ -122,9 +122,16 @@ enum TileSelect : uint64_t {
     kSelFinalizeLaunches = 262144,   // the prefix-sum kernels + k_permute instead of k_permute_wg
     kSelWwPermute = 134217728,       // WholeWord: the scratch slices + k_permute instead of region-local records
     kSelWwTile = 268435456,          // WholeWord: k_ww_tile where k_ww_pp would run
+    kSelMarkDoubling = 2097152,      // mark_chain: always the pointer doubling
+    kSelMarkOnePassEarly = 4194304,  // mark_chain: the one pass from 64 elements on (tests)
+    kSelNoHostChunks = 33554432,     // a long host text in one piece, not in chunks
     kSelWwNoPerfectHash = 1u << 29,  // k_ww_pp: the two-choice table behind the Bloom filter
     kSelNoBigL2 = 1u << 30,          // the second level in LDS where the large one (BIG) would run
     kSelAllocFails = 1ull << 40,     // the allocation of the region-local records / the state words "fails": the fallback's test
+    kSelNoSmallCall = 1ull << 41,    // a short host text through the enqueued pipeline, not the one-launch form
+    kSelStreamTrace = 1ull << 42,    // acgpu_stream: where a feed's time goes, on stderr (development)
+    kSelDfaOneChain = 1ull << 43,    // the dense DFA scan: the one-chain kernel (A/B)
+    kSelDfaNoGlobal = 1ull << 45,    // the dense DFA scan, ablation build: no lookups in global memory (ScanLaunch::debug bit 4)
 };
 // (the form: choose_tile_form, with l.region_units and l.debug set; l.lds_bytes is the form's)
 hipError_t launch_ac_tile(const DevTables &t, const TileLaunch &l, const TileForm &f, hipStream_t stream);
@@ -204,17 +211,21 @@ size_t scan_queue_bytes(int block_threads);
 
 namespace acgpu {
 // ---- LONGEST (leftmost-longest, non-overlapping) pipeline -------------------------------------------------
+enum class LongestWalkForm : int {
+    General,   // k_longest_walk: any dictionary
+    Range,     // k_longest_walk_range: range classes, lanes in lock step
+    RangeList, // k_longest_walk_list: range classes, per-wave work lists, one-byte lengths (also behind k_longest_block)
+};
 struct LongestScanLaunch {
     const uint16_t *d_hay;
     uint32_t n_units, own_begin, own_end;
     uint32_t chunk_units, n_chunks; // owned START positions per lane chunk (multiple of 8)
-    void *d_len;                    // per unit of the buffer: length of the longest keyword starting there (u16 or u32)
+    void *d_len;                    // per unit of the buffer: length of the longest keyword starting there (len_bytes wide)
     uint32_t *d_state;              // optional: automaton state per unit (for the keyword id), or nullptr
     uint32_t *d_blockmax;           // per 64 owned positions: max(p + max(L[p],1)) -- lets the chain kernels skip
-    int len_bytes;                  // 2 or 4
+    int len_bytes;                  // 1: the work-list form (escape 255: d_len_big); 2; 4: a keyword of 65 536 units or more
     uint32_t lds_rows;              // trie rows staged in LDS
-    int pairs;                      // 1: the lean range-class walk (k_longest_walk_range), 2: its work-list form
-                                    // (k_longest_walk_list: one workgroup per CU, grid-stride over 1024-position chunks)
+    LongestWalkForm form;
     int grid, block;
     size_t lds_bytes;
     uint16_t *d_len_big;            // len_bytes == 1: the lengths of 255 units and more (escape 255 in d_len), sparse
@@ -233,11 +244,11 @@ size_t longest_list_lds_bytes(bool state);       // dynamic LDS of k_longest_wal
 uint32_t longest_list_max_rows(uint32_t n_cls, bool state); // trie rows its static LDS holds
 
 struct LongestChainLaunch {
-    const void *d_len;
+    const void *d_len;         // len_bytes per position
     const uint16_t *d_len_big; // len_bytes == 1: see LongestScanLaunch
     const uint32_t *d_state; // or nullptr (Set records)
     const uint32_t *d_out_id;
-    int len_bytes;
+    int len_bytes;             // 1 or 2: the count pass through LDS (k_longest_chain_lds); 4: the one that reads global memory (k_longest_chain)
     uint32_t own_begin, own_end;
     const uint32_t *d_blockmax; // see LongestScanLaunch
     uint32_t entry;       // first greedy-chain position of this shard
@@ -245,17 +256,19 @@ struct LongestChainLaunch {
     uint32_t n_tiles;
     uint32_t max_len;
     uint32_t *d_counts;         // per tile
-    const uint64_t *d_offsets;  // per tile (write pass)
+    const uint64_t *d_offsets;  // per tile: records before it (the emit pass)
     void *d_out;
     uint64_t cap;
     int record_kind;
     unsigned long long *d_exit; // first chain position >= own_end
     uint32_t len_units;         // entries of d_len that hold lengths (the chain passes through LDS read whole chunks)
     uint32_t *d_bits;           // one bit per buffer position: set by the count pass where a match is reported (zeroed by the
-                                // caller), read by k_longest_emit; nullptr: the serial write pass is used instead
-    uint32_t *d_ebits;          // optional second bitmap (zeroed by the caller): bit end-1 of every reported match.  Matches do
-                                // not overlap, so the k-th set bit of d_bits and the k-th of d_ebits are one record and the
-                                // emit pass needs no length lookups (16-bit lengths through k_longest_chain_lds only)
+                                // caller), read by the emit pass
+    uint32_t *d_ebits;          // the second bitmap (zeroed by the caller): bit end-1 of every reported match.  Matches do not
+                                // overlap, so the k-th set bit of d_bits and the k-th of d_ebits are one record and the emit
+                                // pass (k_longest_emit_ends) looks no length up.  Filled by k_longest_chain_lds (1- and
+                                // 2-byte lengths) or by k_longest_follow; nullptr for 4-byte lengths (k_longest_emit looks the lengths up) and where
+                                // only the marks are wanted (mark_chain)
 };
 // k_longest_bits (acgpu_longest_bits.hip): Set records, two-letter alphabets in which every letter is a keyword
 struct LongestBitsLaunch {
@@ -309,10 +322,11 @@ uint32_t longest_follow_lanes_per_cu();
 uint32_t longest_follow_hot_rows(uint32_t n_cls, uint32_t n_states, uint32_t page_bytes); // 0: does not fit
 hipError_t launch_longest_follow(const DevTables &t, const LongestFollowLaunch &l, bool range, bool state, hipStream_t stream);
 hipError_t launch_longest_sync(const LongestChainLaunch &l, uint32_t *d_sync, hipStream_t stream);
-hipError_t launch_longest_chain(const LongestChainLaunch &l, const uint32_t *d_sync, bool write_pass, hipStream_t stream);
-// count / write pass with the lengths staged through LDS in chunks (16-bit lengths)
-hipError_t launch_longest_chain_lds(const LongestChainLaunch &l, const uint32_t *d_sync, bool write_pass, hipStream_t stream);
-// the records from the bitmap of the count pass (d_bits), one wave per chain segment
+// the count pass (per-tile counts, d_bits, the chain's exit), 4-byte lengths: a length from global memory per step
+hipError_t launch_longest_chain(const LongestChainLaunch &l, const uint32_t *d_sync, hipStream_t stream);
+// the count pass, 1- and 2-byte lengths: staged through LDS in chunks; also fills d_ebits when that is given
+hipError_t launch_longest_chain_lds(const LongestChainLaunch &l, const uint32_t *d_sync, hipStream_t stream);
+// the records from the bitmaps of the count pass, one wave per chain segment
 hipError_t launch_longest_emit(const LongestChainLaunch &l, const uint32_t *d_sync, hipStream_t stream);
 } // namespace acgpu
 

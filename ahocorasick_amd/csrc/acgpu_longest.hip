@@ -10,9 +10,14 @@
 //                    blows 50k trie nodes up to 24M states.)
 //  k_longest_sync  : one synchronisation point per tile -- a position every greedy chain that can enter the tile must
 //                    pass (found by following all candidate chains until they have merged).
-//  k_longest_chain : one lane per tile follows the chain from its synchronisation point to the next tile's, so lanes
-//                    are independent and their records concatenate in position order.  Two passes: count, (prefix
-//                    sum), write.
+//  count pass      : one lane per tile follows the chain from its synchronisation point to the next tile's, so lanes
+//                    are independent and their records concatenate in position order; it counts the tile's matches
+//                    and marks them in a bitmap.  k_longest_chain_lds for one- and two-byte lengths (the lengths
+//                    through LDS, a second bitmap of the match ends), k_longest_chain for four-byte lengths.
+//  emit pass       : after a prefix sum of the counts, the records from the bitmaps, position parallel:
+//                    k_longest_emit_ends (both bitmaps), k_longest_emit (four-byte lengths: the start bitmap + len[]).
+// Lengths are one byte wide behind the work-list walk (k_longest_block, k_longest_walk_list), two bytes behind the other
+// walks, four when a keyword has 65 536 units or more.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -313,16 +318,13 @@ __device__ __forceinline__ uint32_t wl_round(const unsigned char *rows8, const u
 constexpr int kWlRowWordsSet = 13312, kWlRowWordsMap = 13312; // 52 KiB of rows
 
 // One byte per length with an escape: 255 = "255 or more, the value is in d_len_big[p]" (a full-size 16-bit array that is only
-// written -- and read -- for such positions: config 4's keywords go up to 1000 units, its walks die below 40).
+// written -- and read -- for such positions: config 4's keywords go up to 1000 units, its walks die below 40).  Half the bytes
+// of 16-bit lengths, written here and read back by the chain passes, and a chunk of the count pass holds twice the positions:
+// count pass 0.456 -> 0.342 ms at config 4 (EXPERIMENTS.md 4.3, round 3).
 constexpr uint32_t kLenEscape = 255u;
-template <typename LenT>
 __device__ __forceinline__ void store_len(const LongestScanLaunch &L, uint32_t p, uint32_t best) {
-    if (sizeof(LenT) == 1) {
-        reinterpret_cast<uint8_t *>(L.d_len)[p] = (uint8_t)min(best, kLenEscape);
-        if (best >= kLenEscape) L.d_len_big[p] = (uint16_t)best;
-    } else {
-        reinterpret_cast<LenT *>(L.d_len)[p] = (LenT)best;
-    }
+    reinterpret_cast<uint8_t *>(L.d_len)[p] = (uint8_t)min(best, kLenEscape);
+    if (best >= kLenEscape) L.d_len_big[p] = (uint16_t)best;
 }
 
 // ---- the first round through a ROOT TABLE: k_longest_block (Set records, small alphabets) ----------------------------------
@@ -464,7 +466,7 @@ __global__ __launch_bounds__(kLScanBlock, 8) void k_longest_block(DevTables T, L
 #ifdef ACGPU_ABLATION
             if (!(L.debug & 1u))
 #endif
-            store_len<uint8_t>(L, p, best);
+            store_len(L, p, best);
             // (the block maximum was preset to its last position + kBlockMaxSlack: only a longer match raises it)
             const uint32_t blk = (p - L.own_begin) >> 6;
             if (p + best > L.own_begin + (blk << 6) + 63u + kBlockMaxSlack) atomicMax(&L.d_blockmax[blk], p + best);
@@ -601,7 +603,7 @@ __device__ unsigned long long g_wl_timing[8]; // total, text wait, index + root 
 #else
 #define WL_MARK(i)
 #endif
-template <typename LenT, bool STATE>
+template <bool STATE>
 __global__ __launch_bounds__(kLScanBlock, 8) void k_longest_walk_list(DevTables T, LongestScanLaunch L) { // (8 waves per SIMD: two workgroups per CU)
     __shared__ __attribute__((aligned(16))) uint32_t rows[STATE ? kWlRowWordsMap : kWlRowWordsSet];
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[]; // the work lists
@@ -698,7 +700,7 @@ __global__ __launch_bounds__(kLScanBlock, 8) void k_longest_walk_list(DevTables 
                 }
             }
         }
-        store_len<LenT>(L, p, best);
+        store_len(L, p, best);
         if (STATE) L.d_state[p] = best_node;
         const uint32_t reach = p + (best ? best : 1u);
         if (by_atomic) atomicMax(&bm[prel >> 6], reach);
@@ -896,13 +898,13 @@ hipError_t launch_longest_scan(const DevTables &t, const LongestScanLaunch &l, h
         hipLaunchKernelGGL(KERNEL, dim3(l.grid), dim3(l.block), l.lds_bytes, stream, t, l);                             \
         if (kernel_name) *kernel_name = NAME;                                                                           \
     } while (0)
-    if (l.pairs == 2) { // the work-list form (8- or 16-bit lengths, LDS rows below 64 KiB)
-        if (l.len_bytes == 1) {
-            if (l.d_state) ACGPU_LAUNCH((k_longest_walk_list<uint8_t, true>), "k_longest_walk_list<unsigned char, true>");
-            else ACGPU_LAUNCH((k_longest_walk_list<uint8_t, false>), "k_longest_walk_list<unsigned char, false>");
-        } else if (l.d_state) ACGPU_LAUNCH((k_longest_walk_list<uint16_t, true>), "k_longest_walk_list<unsigned short, true>");
-        else ACGPU_LAUNCH((k_longest_walk_list<uint16_t, false>), "k_longest_walk_list<unsigned short, false>");
-    } else if (l.pairs) { // (field name kept: the lean range-class form)
+    if (l.form == LongestWalkForm::RangeList) { // (one-byte lengths, LDS rows below 64 KiB)
+        if (l.len_bytes != 1) return hipErrorInvalidValue;
+        if (l.d_state) ACGPU_LAUNCH((k_longest_walk_list<true>), "k_longest_walk_list<true>");
+        else ACGPU_LAUNCH((k_longest_walk_list<false>), "k_longest_walk_list<false>");
+    } else if (l.len_bytes == 1) { // (one-byte lengths are the work list's)
+        return hipErrorInvalidValue;
+    } else if (l.form == LongestWalkForm::Range) {
         if (l.d_state) {
             if (l.len_bytes == 2) ACGPU_LAUNCH((k_longest_walk_range<uint16_t, true>), "k_longest_walk_range<unsigned short, true>");
             else ACGPU_LAUNCH((k_longest_walk_range<uint32_t, true>), "k_longest_walk_range<unsigned int, true>");
@@ -1055,27 +1057,23 @@ __global__ __launch_bounds__(256) void k_longest_sync(LongestChainLaunch L, uint
     S[t] = (ok && cnt == 1 && set[0] < te) ? set[0] : ~0u;
 }
 
-// One lane per tile with a synchronisation point: follows the chain from S[t] to the next tile's synchronisation point
-// (or out of the owned range), counting or writing the matches met.  The write pass stages a lane's records in LDS and
-// stores them as whole aligned groups (8 Set records = 64 bytes, 4 Map records = 48 bytes, as consecutive 16-byte
-// stores by the same lane), so that the L2 sees full sectors instead of one 8-byte store per line and instruction.
+// The count pass for 4-byte lengths (a keyword of 65 536 units or more): one lane per tile with a synchronisation point
+// follows the chain from S[t] to the next tile's synchronisation point (or out of the owned range), reading a length from
+// global memory per step.  It counts the matches it meets and marks every position at which it reports one in the bitmap
+// L.d_bits -- the records are then written by k_longest_emit, in parallel over all positions, instead of by a second serial
+// pass over the chain.  A segment's first and last bitmap word may be shared with its neighbours (atomicOr); the words
+// between are its own (plain stores into the zeroed bitmap).  (Shorter lengths take k_longest_chain_lds below: this pass
+// waits for global memory at every step of its serial chain.)
 constexpr int kChainBlock = 256;
 
-// BITS (count pass): the lane also marks every position at which it reports a match in the bitmap L.d_bits -- with it
-// the records are written by k_longest_emit, in parallel over all positions, instead of a second serial pass over the
-// chain (WRITE).  A segment's first and last bitmap word may be shared with its neighbours (atomicOr); the words between
-// are its own (plain stores into the zeroed bitmap).
-template <typename LenT, bool WRITE, bool BITS = false>
 __global__ __launch_bounds__(kChainBlock) void k_longest_chain(LongestChainLaunch L, const uint32_t *S) {
-    __shared__ int2 ring_se[WRITE ? 8 : 1][kChainBlock]; // [slot][lane]: conflict-free for a lane's own slots
-    __shared__ int ring_id[WRITE ? 4 : 1][kChainBlock];
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= L.n_tiles) return;
-    const LenT *len = reinterpret_cast<const LenT *>(L.d_len);
+    const uint32_t *len = reinterpret_cast<const uint32_t *>(L.d_len);
     const uint32_t start = S[t];
     if (start == ~0u || start >= L.own_end) {
-        if (!WRITE) L.d_counts[t] = 0;
-        if (t == 0 && !WRITE) *L.d_exit = L.entry; // entry at/after the end of the owned range
+        L.d_counts[t] = 0;
+        if (t == 0) *L.d_exit = L.entry; // entry at/after the end of the owned range
         return;
     }
     uint32_t target = ~0u; // the next synchronisation point on the chain
@@ -1086,51 +1084,10 @@ __global__ __launch_bounds__(kChainBlock) void k_longest_chain(LongestChainLaunc
             break;
         }
     }
-    const bool set_kind = L.record_kind == ACGPU_REC_SET;
-    const uint32_t gmask = set_kind ? 7u : 3u; // records per aligned group - 1
     uint32_t pos = start, count = 0;
-    uint64_t dst = WRITE ? L.d_offsets[t] : 0;
-    uint32_t gfirst = (uint32_t)dst & gmask; // first valid slot of the group being filled
-    const uint32_t lane = threadIdx.x;
-    // stores slots [from, to) of the current group one record at a time (group not complete, or beyond cap)
-    auto flush_scalar = [&](uint64_t gbase, uint32_t from, uint32_t to) {
-        for (uint32_t k = from; k < to; ++k) {
-            const uint64_t d = gbase + k;
-            if (d >= L.cap) break;
-            const int2 se = ring_se[k][lane];
-            if (set_kind) {
-                reinterpret_cast<int2 *>(L.d_out)[d] = se;
-            } else {
-                int32_t *o = reinterpret_cast<int32_t *>(L.d_out) + d * 3;
-                o[0] = se.x; o[1] = se.y; o[2] = ring_id[k][lane];
-            }
-        }
-    };
-    // 16-entry window of len[] in registers (two 16-byte loads): a dense chain (config 4: 6.4 positions per step) then
-    // waits for memory once per 16 positions instead of once per step (a 32-entry window was slower: 3.7 ms against
-    // 1.5 ms for the chain kernels at config 4)
-    uint32_t win[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint32_t wbase = ~0u - 64u; // no window yet
-    auto len_at = [&](uint32_t q) -> uint32_t {
-        if (sizeof(LenT) != 2) return len_full<LenT>(L, q, (uint32_t)len[q]);
-        if (q - wbase >= 16u) { // (also true for q < wbase: the chain only moves forwards)
-            const uint16_t *src = reinterpret_cast<const uint16_t *>(len) + q;
-            const Units8 a = *reinterpret_cast<const Units8 *>(src), b = *reinterpret_cast<const Units8 *>(src + 8);
-            win[0] = a.d[0]; win[1] = a.d[1]; win[2] = a.d[2]; win[3] = a.d[3];
-            win[4] = b.d[0]; win[5] = b.d[1]; win[6] = b.d[2]; win[7] = b.d[3];
-            wbase = q;
-        }
-        const uint32_t k = q - wbase;
-        uint32_t x0 = (k & 8u) ? win[4] : win[0], x1 = (k & 8u) ? win[5] : win[1];
-        uint32_t x2 = (k & 8u) ? win[6] : win[2], x3 = (k & 8u) ? win[7] : win[3];
-        x0 = (k & 4u) ? x2 : x0;
-        x1 = (k & 4u) ? x3 : x1;
-        x0 = (k & 2u) ? x1 : x0;
-        return (k & 1u) ? (x0 >> 16) : (x0 & 0xffffu);
-    };
-    // BITS: the aligned group of four bitmap words (128 positions) being filled.  Stores sit in the lane's in-order vmcnt
-    // stream in front of its next window load (gfx950 counts stores there), so they are few and wide: one 16-byte store per
-    // group; only the first and the last group of a segment can be shared with a neighbour (atomicOr per word).
+    // the aligned group of four bitmap words (128 positions) being filled.  Stores sit in the lane's in-order vmcnt stream in
+    // front of its next length load (gfx950 counts stores there), so they are few and wide: one 16-byte store per group; only
+    // the first and the last group of a segment can be shared with a neighbour (atomicOr per word).
     uint32_t bg = ~0u;
     unsigned long long blo = 0, bhi = 0;
     bool bfirst = true;
@@ -1147,93 +1104,39 @@ __global__ __launch_bounds__(kChainBlock) void k_longest_chain(LongestChainLaunc
         }
     };
     while (pos < target && pos < L.own_end) {
-        const uint32_t l = len_at(pos);
+        const uint32_t l = len[pos];
         if (l > 0) {
-            if (BITS) {
-                const uint32_t g = pos >> 7;
-                if (g != bg) {
-                    flush_bits(bfirst);
-                    bfirst = bg == ~0u; // (still nothing flushed: the next flush is the segment's first)
-                    bg = g;
-                    blo = bhi = 0;
-                }
-                const unsigned long long bit = 1ull << (pos & 63u);
-                if (pos & 64u) bhi |= bit;
-                else blo |= bit;
+            const uint32_t g = pos >> 7;
+            if (g != bg) {
+                flush_bits(bfirst);
+                bfirst = bg == ~0u; // (still nothing flushed: the next flush is the segment's first)
+                bg = g;
+                blo = bhi = 0;
             }
-            if (WRITE) {
-                const uint32_t k = (uint32_t)dst & gmask;
-                ring_se[k][lane] = make_int2((int)pos, (int)(pos + l));
-                if (!set_kind) ring_id[k][lane] = (int)L.d_out_id[L.d_state[pos]];
-                if (k == gmask) { // the group is full up to its last slot
-                    const uint64_t gbase = dst - gmask;
-                    if (gfirst == 0 && dst < L.cap) {
-                        if (set_kind) {
-                            uint4 *o = reinterpret_cast<uint4 *>(reinterpret_cast<int2 *>(L.d_out) + gbase);
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) {
-                                const int2 r0 = ring_se[2 * q][lane], r1 = ring_se[2 * q + 1][lane];
-                                o[q] = make_uint4((uint32_t)r0.x, (uint32_t)r0.y, (uint32_t)r1.x, (uint32_t)r1.y);
-                            }
-                        } else {
-                            uint4 *o = reinterpret_cast<uint4 *>(reinterpret_cast<int32_t *>(L.d_out) + gbase * 3);
-                            const int2 r0 = ring_se[0][lane], r1 = ring_se[1][lane], r2 = ring_se[2][lane], r3 = ring_se[3][lane];
-                            o[0] = make_uint4((uint32_t)r0.x, (uint32_t)r0.y, (uint32_t)ring_id[0][lane], (uint32_t)r1.x);
-                            o[1] = make_uint4((uint32_t)r1.y, (uint32_t)ring_id[1][lane], (uint32_t)r2.x, (uint32_t)r2.y);
-                            o[2] = make_uint4((uint32_t)ring_id[2][lane], (uint32_t)r3.x, (uint32_t)r3.y, (uint32_t)ring_id[3][lane]);
-                        }
-                    } else {
-                        flush_scalar(gbase, gfirst, gmask + 1);
-                    }
-                    gfirst = 0;
-                }
-            }
-            ++dst;
+            const unsigned long long bit = 1ull << (pos & 63u);
+            if (pos & 64u) bhi |= bit;
+            else blo |= bit;
             ++count;
             pos += l;
         } else {
-            // no keyword starts here: skip the run of such positions eight at a time (sparse dictionaries: most of
-            // the haystack), reading 16 bytes of lengths per step
-            ++pos;
-            if (sizeof(LenT) == 2) {
-                const uint32_t limit = min(target, L.own_end);
-                while (pos + 8 <= limit) {
-                    const Units8 z = *reinterpret_cast<const Units8 *>(reinterpret_cast<const uint16_t *>(len) + pos);
-                    const uint32_t any = z.d[0] | z.d[1] | z.d[2] | z.d[3];
-                    if (any) {
-                        // first non-zero 16-bit entry
-                        uint32_t k = 0;
-                        if (z.d[0]) k = (z.d[0] & 0xffffu) ? 0 : 1;
-                        else if (z.d[1]) k = (z.d[1] & 0xffffu) ? 2 : 3;
-                        else if (z.d[2]) k = (z.d[2] & 0xffffu) ? 4 : 5;
-                        else k = (z.d[3] & 0xffffu) ? 6 : 7;
-                        pos += k;
-                        break;
-                    }
-                    pos += 8;
-                }
-            }
+            ++pos; // no keyword starts here
         }
     }
-    if (WRITE) {
-        const uint32_t k = (uint32_t)dst & gmask;
-        if (k > gfirst) flush_scalar(dst - k, gfirst, k);
-    }
-    if (BITS) flush_bits(true);
-    if (!WRITE) {
-        L.d_counts[t] = count;
-        if (pos >= L.own_end) *L.d_exit = pos; // exactly one lane's segment crosses the end of the owned range
-    }
+    flush_bits(true);
+    L.d_counts[t] = count;
+    if (pos >= L.own_end) *L.d_exit = pos; // exactly one lane's segment crosses the end of the owned range
 }
 
 // The records of segment t -- the matches of the chain between the synchronisation points S[t] and the next one -- from
 // the bitmap the count pass left: one wave per segment, 64 bitmap words per step (lane i: word i), a wave prefix sum of
 // the popcounts gives every record its place behind d_offsets[t]; the records are staged in LDS in order and leave as
-// coalesced stores.  Position parallel: this pass runs at memory speed where the serial write pass waited for the chain.
+// coalesced stores.  Position parallel: this pass runs at memory speed where a second, serial pass over the chain that wrote
+// the records (retired: EXPERIMENTS.md 4.3) waited for the chain.  4-byte lengths only, looked up per match: shorter lengths
+// come with the bitmap of ends (k_longest_emit_ends below).
 constexpr int kEmitBlock = 256;
 constexpr int kEmitCap = 1024; // records staged per wave and step (a denser step goes out in several rounds)
 
-template <typename LenT, int REC>
+template <int REC>
 __global__ __launch_bounds__(kEmitBlock) void k_longest_emit(LongestChainLaunch L, const uint32_t *S) {
     __shared__ int2 st_se[kEmitBlock / kWave][kEmitCap];
     __shared__ int st_id[REC == ACGPU_REC_MAP ? kEmitBlock / kWave : 1][REC == ACGPU_REC_MAP ? kEmitCap : 1];
@@ -1251,7 +1154,7 @@ __global__ __launch_bounds__(kEmitBlock) void k_longest_emit(LongestChainLaunch 
             break;
         }
     }
-    const LenT *len = reinterpret_cast<const LenT *>(L.d_len);
+    const uint32_t *len = reinterpret_cast<const uint32_t *>(L.d_len);
     uint64_t base = L.d_offsets[t];
     const uint32_t w_first = start >> 5, w_last = (target - 1u) >> 5;
     int2 *se = st_se[wave];
@@ -1276,7 +1179,7 @@ __global__ __launch_bounds__(kEmitBlock) void k_longest_emit(LongestChainLaunch 
                 const uint32_t p = wi * 32u + (uint32_t)__builtin_ctz(b);
                 b &= b - 1u;
                 if (k >= done && k < done + kEmitCap) {
-                    se[k - done] = make_int2((int)p, (int)(p + len_full<LenT>(L, p, (uint32_t)len[p])));
+                    se[k - done] = make_int2((int)p, (int)(p + len[p]));
                     if (REC == ACGPU_REC_MAP) st_id[wave][k - done] = (int)L.d_out_id[L.d_state[p]];
                 }
                 ++k;
@@ -1386,24 +1289,26 @@ __global__ __launch_bounds__(kEmitBlock, 8) void k_longest_emit_ends(LongestChai
     }
 }
 
-// ---- chain passes through LDS --------------------------------------------------------------------------------------------
-// k_longest_chain waits for global memory once per 16 positions of its (serial) chain: ~250 dependent round trips per lane,
-// 0.46 ms per pass at config 4 with every wave of the grid resident.  Here a lane still follows its own segment, but the
-// lengths come through LDS in chunks of 256 positions: a lane requests its whole chunk at once (32 independent 16-byte
-// loads: one memory latency per 256 positions instead of one per 16) and then walks it with LDS reads.  The walk is cheap
-// enough to run twice -- count, (prefix sum), write -- without the bitmap and the separate emit pass.
+// ---- the count pass through LDS: one- and two-byte lengths ------------------------------------------------------------------
+// Reading the lengths from global memory, a 16-entry register window at a time, the count pass waited for memory once per 16
+// positions of its (serial) chain: ~250 dependent round trips per lane, 0.46 ms per pass at config 4 with every wave of the grid
+// resident (a 32-entry window was slower).  Here a lane still follows its own segment, but the lengths come through LDS in
+// chunks: a lane requests its whole chunk at once (independent 16-byte loads: one memory latency per chunk instead of one per
+// 16 positions) and then walks it with LDS reads.
 // (measured at config 4 with one-byte lengths, whole chain pipeline: 32 pieces / 1 wave per SIMD / 4096-position tiles 0.795 ms;
 // 16 pieces / 2 waves per SIMD: 0.75 at 4096-position tiles, 0.65 at 6144, 0.67 at 8192; 8 pieces / 4 waves: 0.70 / 0.68 / 0.73)
 #ifndef ACGPU_C2PIECES
 #define ACGPU_C2PIECES 16
 #endif
-constexpr int kC2Pieces = ACGPU_C2PIECES; // 16-byte pieces per lane and chunk: 512 bytes, loaded by one half wave of one LDS-DMA instruction
-                              // (global_load_lds_dwordx4: lane i's 16 bytes land at base + 16 i) -- 256 positions of 16-bit
-                              // lengths, 512 positions of one-byte lengths
+constexpr int kC2Pieces = ACGPU_C2PIECES; // 16-byte pieces per lane and chunk: 256 bytes, loaded by a quarter wave of one LDS-DMA instruction
+                              // (global_load_lds_dwordx4: lane i's 16 bytes land at base + 16 i) -- 128 positions of two-byte
+                              // lengths, 256 positions of one-byte lengths
 
-// BITS (count pass): the matches are also marked in the bitmap L.d_bits for k_longest_emit -- collected per chunk in LDS
-// (chunks start on a bitmap word) and merged into the zeroed bitmap with one atomicOr per non-zero word; these stores are
-// issued when a chunk is done and complete under the next chunk's load.
+// The matches are counted and marked in the bitmap L.d_bits -- and their ends (bit end-1) in L.d_ebits when that is given, for
+// k_longest_emit_ends: with both bitmaps the emit pass looks no length up (the lookups were 0.42 ms at config 4, a second read
+// of len[]).  The bits are collected per chunk in LDS (chunks start on a bitmap word) and go to the zeroed bitmaps as plain
+// stores for the words inside the lane's segment and one atomicOr per non-zero word at its ends; these stores are issued
+// when a chunk is done and complete under the next chunk's load.
 #ifndef ACGPU_C2WAVES
 #define ACGPU_C2WAVES 2
 #endif
@@ -1413,22 +1318,20 @@ __device__ unsigned long long g_c2_timing[8]; // total, zero+issue, load wait, w
 #else
 #define C2_MARK(i)
 #endif
-template <typename LenT, bool WRITE, bool BITS = false>
+template <typename LenT>
 __global__ __launch_bounds__(kWave, ACGPU_C2WAVES) void k_longest_chain_lds(LongestChainLaunch L, const uint32_t *S) {
     constexpr uint32_t kPP = 16 / sizeof(LenT);            // lengths per piece: 8 or 16
     constexpr uint32_t kPPLog = sizeof(LenT) == 2 ? 3 : 4;
     constexpr int kC2Chunk = kC2Pieces * (int)kPP;         // positions per lane and chunk
     __shared__ __attribute__((aligned(16))) unsigned char buf[kC2Pieces * kWave * 16]; // [piece][lane][16 bytes of lengths]
-    __shared__ uint32_t lbits[BITS ? kC2Chunk / 32 : 1][kWave];
-    __shared__ uint32_t lebits[BITS ? kC2Chunk / 32 + 1 : 1][kWave]; // the ends (bit end-1), when L.d_ebits is there (+ a dummy word)
-    __shared__ int2 ring_se[WRITE ? 8 : 1][kWave];
-    __shared__ int ring_id[WRITE ? 4 : 1][kWave];
+    __shared__ uint32_t lbits[kC2Chunk / 32][kWave];
+    __shared__ uint32_t lebits[kC2Chunk / 32 + 1][kWave]; // the ends (bit end-1), when L.d_ebits is there (+ a dummy word)
     const uint32_t lane = threadIdx.x;
     const uint32_t t = blockIdx.x * kWave + lane;
     const LenT *len = reinterpret_cast<const LenT *>(L.d_len);
     uint32_t start = t < L.n_tiles ? S[t] : ~0u;
     bool active = start != ~0u && start < L.own_end;
-    if (t < L.n_tiles && !active && !WRITE) {
+    if (t < L.n_tiles && !active) {
         L.d_counts[t] = 0;
         if (t == 0) *L.d_exit = L.entry; // entry at/after the end of the owned range
     }
@@ -1442,24 +1345,7 @@ __global__ __launch_bounds__(kWave, ACGPU_C2WAVES) void k_longest_chain_lds(Long
             }
         }
     const uint32_t limit = min(target, L.own_end);
-    const bool set_kind = L.record_kind == ACGPU_REC_SET;
-    const uint32_t gmask = set_kind ? 7u : 3u; // records per aligned group - 1
     uint32_t pos = active ? start : 0u, count = 0;
-    uint64_t dst = (WRITE && active) ? L.d_offsets[t] : 0;
-    uint32_t gfirst = (uint32_t)dst & gmask;
-    auto flush_scalar = [&](uint64_t gbase, uint32_t from, uint32_t to) {
-        for (uint32_t k = from; k < to; ++k) {
-            const uint64_t d = gbase + k;
-            if (d >= L.cap) break;
-            const int2 se = ring_se[k][lane];
-            if (set_kind) {
-                reinterpret_cast<int2 *>(L.d_out)[d] = se;
-            } else {
-                int32_t *o = reinterpret_cast<int32_t *>(L.d_out) + d * 3;
-                o[0] = se.x; o[1] = se.y; o[2] = ring_id[k][lane];
-            }
-        }
-    };
     // LDS layout: a lane's chunk is contiguous (kC2Chunk * 2 bytes at lane * kC2Chunk * 2), its 16-byte pieces permuted by
     // piece ^ lane -- the lanes walk their chunks at about the same pace, and without the permutation they would all sit in
     // the same banks.  Length x of the lane's chunk: piece x >> 3, entry x & 7.
@@ -1473,21 +1359,19 @@ __global__ __launch_bounds__(kWave, ACGPU_C2WAVES) void k_longest_chain_lds(Long
     // a chunk starts on a 16-byte boundary of len[]; pieces past its end are read from the last whole piece instead (never
     // consulted: the walk stops at limit <= the end of the owned range; the allocation of len[] has 64 bytes of slack)
     const uint32_t last_piece = L.len_units & ~(kPP - 1u);
-    const bool ebits = BITS && L.d_ebits != nullptr;
+    const bool ebits = L.d_ebits != nullptr;
 #ifdef ACGPU_TIMING
     unsigned long long c2t[8] = {0, 0, 0, 0, 0, 0, 0, 0}, c2t0 = clock64();
     const unsigned long long c2start = c2t0;
 #endif
     uint32_t pend = ~0u; // an end beyond the chunk in which its match started: it lies in the first word of the lane's next chunk
     while (__any(active)) {
-        const uint32_t cb = pos & (BITS ? ~31u : ~(kPP - 1u));
-        if (BITS) {
+        const uint32_t cb = pos & ~31u;
 #pragma unroll
-            for (int w = 0; w < kC2Chunk / 32; ++w) lbits[w][lane] = 0;
-            if (ebits) {
+        for (int w = 0; w < kC2Chunk / 32; ++w) lbits[w][lane] = 0;
+        if (ebits) {
 #pragma unroll
-                for (int w = 0; w < kC2Chunk / 32; ++w) lebits[w][lane] = 0;
-            }
+            for (int w = 0; w < kC2Chunk / 32; ++w) lebits[w][lane] = 0;
         }
         if (ebits && active && pend != ~0u) { // (an end beyond its chunk lies in the first word of the lane's next chunk)
             lebits[0][lane] = 1u << (pend & 31u);
@@ -1519,7 +1403,7 @@ __global__ __launch_bounds__(kWave, ACGPU_C2WAVES) void k_longest_chain_lds(Long
         __builtin_amdgcn_wave_barrier();
         if (active) {
             // The chain inside the chunk, on the chunk-relative position `rel` (the loop-carried chain is rel -> address (two
-            // instructions) -> length (one LDS read) -> rel + length).  BITS: chunks start on a bitmap word, so bit numbers are
+            // instructions) -> length (one LDS read) -> rel + length).  Chunks start on a bitmap word, so bit numbers are
             // rel's low five bits; the ors go to LDS without return; only the LAST match of a chunk can end beyond it -- its
             // bit goes to a dummy word and its position into `pend`.
             const uint32_t rel_end = limit > cb ? min(limit - cb, (uint32_t)kC2Chunk) : 0u;
@@ -1528,42 +1412,13 @@ __global__ __launch_bounds__(kWave, ACGPU_C2WAVES) void k_longest_chain_lds(Long
                 uint32_t l = *reinterpret_cast<const LenT *>(at(rel));
                 if (sizeof(LenT) == 1 && l == kLenEscape) l = (uint32_t)L.d_len_big[cb + rel]; // (rare: 255 units and more)
                 if (l > 0) {
-                    if (BITS) atomicOr(&lbits[rel >> 5][lane], 1u << (rel & 31u));
+                    atomicOr(&lbits[rel >> 5][lane], 1u << (rel & 31u));
                     if (ebits) {
                         const uint32_t er = rel + l - 1u;
                         const bool in = er < (uint32_t)kC2Chunk;
                         atomicOr(&lebits[in ? er >> 5 : (uint32_t)(kC2Chunk / 32)][lane], 1u << (er & 31u));
                         pend_rel = in ? pend_rel : er;
                     }
-                    if constexpr (WRITE) {
-                        pos = cb + rel;
-                        const uint32_t k = (uint32_t)dst & gmask;
-                        ring_se[k][lane] = make_int2((int)pos, (int)(pos + l));
-                        if (!set_kind) ring_id[k][lane] = (int)L.d_out_id[L.d_state[pos]];
-                        if (k == gmask) { // the group is full up to its last slot
-                            const uint64_t gbase = dst - gmask;
-                            if (gfirst == 0 && dst < L.cap) {
-                                if (set_kind) {
-                                    uint4 *o = reinterpret_cast<uint4 *>(reinterpret_cast<int2 *>(L.d_out) + gbase);
-#pragma unroll
-                                    for (int q = 0; q < 4; ++q) {
-                                        const int2 r0 = ring_se[2 * q][lane], r1 = ring_se[2 * q + 1][lane];
-                                        o[q] = make_uint4((uint32_t)r0.x, (uint32_t)r0.y, (uint32_t)r1.x, (uint32_t)r1.y);
-                                    }
-                                } else {
-                                    uint4 *o = reinterpret_cast<uint4 *>(reinterpret_cast<int32_t *>(L.d_out) + gbase * 3);
-                                    const int2 r0 = ring_se[0][lane], r1 = ring_se[1][lane], r2 = ring_se[2][lane], r3 = ring_se[3][lane];
-                                    o[0] = make_uint4((uint32_t)r0.x, (uint32_t)r0.y, (uint32_t)ring_id[0][lane], (uint32_t)r1.x);
-                                    o[1] = make_uint4((uint32_t)r1.y, (uint32_t)ring_id[1][lane], (uint32_t)r2.x, (uint32_t)r2.y);
-                                    o[2] = make_uint4((uint32_t)ring_id[2][lane], (uint32_t)r3.x, (uint32_t)r3.y, (uint32_t)ring_id[3][lane]);
-                                }
-                            } else {
-                                flush_scalar(gbase, gfirst, gmask + 1);
-                            }
-                            gfirst = 0;
-                        }
-                    }
-                    ++dst;
                     ++count;
                     rel += l;
                 } else {
@@ -1579,37 +1434,36 @@ __global__ __launch_bounds__(kWave, ACGPU_C2WAVES) void k_longest_chain_lds(Long
             pos = cb + rel;
             if (ebits && pend_rel != ~0u) pend = cb + pend_rel;
             C2_MARK(3)
-            if (BITS) { // words wholly inside the segment are this lane's own (plain stores); the two at its ends may be shared
-                if (ebits && pend != ~0u && ((pend + 1u) & 31u) == 0) { // a word between this lane's chunks: nobody stores it
-                    atomicOr(&L.d_ebits[pend >> 5], 0x80000000u);
-                    pend = ~0u;
-                }
-                auto store_bits = [&](const uint32_t (*lb)[kWave], uint32_t *bitmap) {
-                    uint32_t bw[kC2Chunk / 32];
+            // words wholly inside the segment are this lane's own (plain stores); the two at its ends may be shared
+            if (ebits && pend != ~0u && ((pend + 1u) & 31u) == 0) { // a word between this lane's chunks: nobody stores it
+                atomicOr(&L.d_ebits[pend >> 5], 0x80000000u);
+                pend = ~0u;
+            }
+            auto store_bits = [&](const uint32_t (*lb)[kWave], uint32_t *bitmap) {
+                uint32_t bw[kC2Chunk / 32];
 #pragma unroll
-                    for (int w = 0; w < kC2Chunk / 32; ++w) bw[w] = lb[w][lane];
-                    uint32_t *dstw = bitmap + (cb >> 5);
-                    if (cb >= start && cb + kC2Chunk <= limit) {
-                        uint4 *d4 = reinterpret_cast<uint4 *>(dstw); // (cb is a multiple of 32 positions, not of 128: 4-byte aligned only)
-                        if (kC2Chunk >= 128 && (cb & 127u) == 0) {
+                for (int w = 0; w < kC2Chunk / 32; ++w) bw[w] = lb[w][lane];
+                uint32_t *dstw = bitmap + (cb >> 5);
+                if (cb >= start && cb + kC2Chunk <= limit) {
+                    uint4 *d4 = reinterpret_cast<uint4 *>(dstw); // (cb is a multiple of 32 positions, not of 128: 4-byte aligned only)
+                    if (kC2Chunk >= 128 && (cb & 127u) == 0) {
 #pragma unroll
-                            for (int g = 0; g < kC2Chunk / 128; ++g) d4[g] = make_uint4(bw[4 * g], bw[4 * g + 1], bw[4 * g + 2], bw[4 * g + 3]);
-                        } else {
-#pragma unroll
-                            for (int w = 0; w < kC2Chunk / 32; ++w) dstw[w] = bw[w];
-                        }
+                        for (int g = 0; g < kC2Chunk / 128; ++g) d4[g] = make_uint4(bw[4 * g], bw[4 * g + 1], bw[4 * g + 2], bw[4 * g + 3]);
                     } else {
 #pragma unroll
-                        for (int w = 0; w < kC2Chunk / 32; ++w) {
-                            const uint32_t wp = cb + 32u * w;
-                            if (wp >= start && wp + 32u <= limit) dstw[w] = bw[w];
-                            else if (bw[w]) atomicOr(&dstw[w], bw[w]);
-                        }
+                        for (int w = 0; w < kC2Chunk / 32; ++w) dstw[w] = bw[w];
                     }
-                };
-                store_bits(lbits, L.d_bits);
-                if (ebits) store_bits(lebits, L.d_ebits);
-            }
+                } else {
+#pragma unroll
+                    for (int w = 0; w < kC2Chunk / 32; ++w) {
+                        const uint32_t wp = cb + 32u * w;
+                        if (wp >= start && wp + 32u <= limit) dstw[w] = bw[w];
+                        else if (bw[w]) atomicOr(&dstw[w], bw[w]);
+                    }
+                }
+            };
+            store_bits(lbits, L.d_bits);
+            if (ebits) store_bits(lebits, L.d_ebits);
             if (pos >= limit) active = false;
         }
         __builtin_amdgcn_wave_barrier();
@@ -1626,31 +1480,21 @@ __global__ __launch_bounds__(kWave, ACGPU_C2WAVES) void k_longest_chain_lds(Long
     }
 #endif
     if (t < L.n_tiles && start != ~0u && start < L.own_end) {
-        if (WRITE) {
-            const uint32_t k = (uint32_t)dst & gmask;
-            if (k > gfirst) flush_scalar(dst - k, gfirst, k);
-        } else {
-            L.d_counts[t] = count;
-            if (pos >= L.own_end) *L.d_exit = pos; // exactly one lane's segment crosses the end of the owned range
-            if (ebits && pend != ~0u) atomicOr(&L.d_ebits[pend >> 5], 1u << (pend & 31u)); // (the segment ended before that chunk)
-        }
+        L.d_counts[t] = count;
+        if (pos >= L.own_end) *L.d_exit = pos; // exactly one lane's segment crosses the end of the owned range
+        if (ebits && pend != ~0u) atomicOr(&L.d_ebits[pend >> 5], 1u << (pend & 31u)); // (the segment ended before that chunk)
     }
 }
 
-hipError_t launch_longest_chain_lds(const LongestChainLaunch &l, const uint32_t *d_sync, bool write_pass, hipStream_t stream) {
+// (a call the host cannot construct -- lengths of another width, no bitmap -- is an error, not a silent no-op)
+hipError_t launch_longest_chain_lds(const LongestChainLaunch &l, const uint32_t *d_sync, hipStream_t stream) {
+    if ((l.len_bytes != 1 && l.len_bytes != 2) || l.d_bits == nullptr) return hipErrorInvalidValue;
     if (l.n_tiles == 0) return hipSuccess;
     const dim3 grid((l.n_tiles + kWave - 1) / kWave), block(kWave);
-    if (l.len_bytes == 1) {
-        if (write_pass) hipLaunchKernelGGL((k_longest_chain_lds<uint8_t, true>), grid, block, 0, stream, l, d_sync);
-        else if (l.d_bits) hipLaunchKernelGGL((k_longest_chain_lds<uint8_t, false, true>), grid, block, 0, stream, l, d_sync);
-        else hipLaunchKernelGGL((k_longest_chain_lds<uint8_t, false>), grid, block, 0, stream, l, d_sync);
-    } else {
-        if (write_pass) hipLaunchKernelGGL((k_longest_chain_lds<uint16_t, true>), grid, block, 0, stream, l, d_sync);
-        else if (l.d_bits) hipLaunchKernelGGL((k_longest_chain_lds<uint16_t, false, true>), grid, block, 0, stream, l, d_sync);
-        else hipLaunchKernelGGL((k_longest_chain_lds<uint16_t, false>), grid, block, 0, stream, l, d_sync);
-    }
+    if (l.len_bytes == 1) hipLaunchKernelGGL((k_longest_chain_lds<uint8_t>), grid, block, 0, stream, l, d_sync);
+    else hipLaunchKernelGGL((k_longest_chain_lds<uint16_t>), grid, block, 0, stream, l, d_sync);
 #ifdef ACGPU_TIMING
-    if (!write_pass) {
+    {
         (void)hipStreamSynchronize(stream);
         unsigned long long h[8] = {0};
         (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_c2_timing), sizeof(h));
@@ -1672,41 +1516,26 @@ hipError_t launch_longest_sync(const LongestChainLaunch &l, uint32_t *d_sync, hi
     return hipGetLastError();
 }
 
-hipError_t launch_longest_chain(const LongestChainLaunch &l, const uint32_t *d_sync, bool write_pass, hipStream_t stream) {
+hipError_t launch_longest_chain(const LongestChainLaunch &l, const uint32_t *d_sync, hipStream_t stream) {
+    if (l.len_bytes != 4 || l.d_bits == nullptr) return hipErrorInvalidValue;
     if (l.n_tiles == 0) return hipSuccess;
     const dim3 grid((l.n_tiles + kChainBlock - 1) / kChainBlock), block(kChainBlock);
-    if (l.len_bytes == 1) {
-        if (write_pass) hipLaunchKernelGGL((k_longest_chain<uint8_t, true>), grid, block, 0, stream, l, d_sync);
-        else if (l.d_bits) hipLaunchKernelGGL((k_longest_chain<uint8_t, false, true>), grid, block, 0, stream, l, d_sync);
-        else hipLaunchKernelGGL((k_longest_chain<uint8_t, false>), grid, block, 0, stream, l, d_sync);
-    } else if (l.len_bytes == 2) {
-        if (write_pass) hipLaunchKernelGGL((k_longest_chain<uint16_t, true>), grid, block, 0, stream, l, d_sync);
-        else if (l.d_bits) hipLaunchKernelGGL((k_longest_chain<uint16_t, false, true>), grid, block, 0, stream, l, d_sync);
-        else hipLaunchKernelGGL((k_longest_chain<uint16_t, false>), grid, block, 0, stream, l, d_sync);
-    } else {
-        if (write_pass) hipLaunchKernelGGL((k_longest_chain<uint32_t, true>), grid, block, 0, stream, l, d_sync);
-        else if (l.d_bits) hipLaunchKernelGGL((k_longest_chain<uint32_t, false, true>), grid, block, 0, stream, l, d_sync);
-        else hipLaunchKernelGGL((k_longest_chain<uint32_t, false>), grid, block, 0, stream, l, d_sync);
-    }
+    hipLaunchKernelGGL(k_longest_chain, grid, block, 0, stream, l, d_sync);
     return hipGetLastError();
 }
 
+// both bitmaps (the count pass through LDS): k_longest_emit_ends; the start bitmap and 4-byte lengths: k_longest_emit
 hipError_t launch_longest_emit(const LongestChainLaunch &l, const uint32_t *d_sync, hipStream_t stream) {
+    if (l.d_bits == nullptr || (l.d_ebits == nullptr && l.len_bytes != 4)) return hipErrorInvalidValue;
     if (l.n_tiles == 0) return hipSuccess;
     const dim3 grid((l.n_tiles + kEmitBlock / kWave - 1) / (kEmitBlock / kWave)), block(kEmitBlock);
     const bool set_kind = l.record_kind == ACGPU_REC_SET;
     if (l.d_ebits) {
         if (set_kind) hipLaunchKernelGGL((k_longest_emit_ends<ACGPU_REC_SET>), grid, block, 0, stream, l, d_sync);
         else hipLaunchKernelGGL((k_longest_emit_ends<ACGPU_REC_MAP>), grid, block, 0, stream, l, d_sync);
-    } else if (l.len_bytes == 1) {
-        if (set_kind) hipLaunchKernelGGL((k_longest_emit<uint8_t, ACGPU_REC_SET>), grid, block, 0, stream, l, d_sync);
-        else hipLaunchKernelGGL((k_longest_emit<uint8_t, ACGPU_REC_MAP>), grid, block, 0, stream, l, d_sync);
-    } else if (l.len_bytes == 2) {
-        if (set_kind) hipLaunchKernelGGL((k_longest_emit<uint16_t, ACGPU_REC_SET>), grid, block, 0, stream, l, d_sync);
-        else hipLaunchKernelGGL((k_longest_emit<uint16_t, ACGPU_REC_MAP>), grid, block, 0, stream, l, d_sync);
     } else {
-        if (set_kind) hipLaunchKernelGGL((k_longest_emit<uint32_t, ACGPU_REC_SET>), grid, block, 0, stream, l, d_sync);
-        else hipLaunchKernelGGL((k_longest_emit<uint32_t, ACGPU_REC_MAP>), grid, block, 0, stream, l, d_sync);
+        if (set_kind) hipLaunchKernelGGL((k_longest_emit<ACGPU_REC_SET>), grid, block, 0, stream, l, d_sync);
+        else hipLaunchKernelGGL((k_longest_emit<ACGPU_REC_MAP>), grid, block, 0, stream, l, d_sync);
     }
     return hipGetLastError();
 }

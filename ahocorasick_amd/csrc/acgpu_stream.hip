@@ -209,7 +209,7 @@ int scan_slot(acgpu_stream *s, Slot &sl, int record_kind, void *out, uint64_t ca
         if (call.rc) return call.rc;
         DeviceState *d = call.d;
         int rc;
-        const bool trace = (tunables().tile_debug & (1ll << 42)) != 0;
+        const bool trace = (tunables().tile_debug & kSelStreamTrace) != 0;
         const auto t0 = std::chrono::steady_clock::now();
         auto since = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); };
         if (trace) {
@@ -379,7 +379,7 @@ int feed_pipelined(acgpu_stream *s, const uint16_t *units, uint64_t n_units, int
         const uint64_t o = (uint64_t)i * piece, len = std::min<uint64_t>(piece, n_units - o);
         std::memcpy(h + n_carry + o, units + o, len * 2);
     };
-    const bool trace = (tunables().tile_debug & (1ll << 42)) != 0; // development: where a feed's time goes (stderr)
+    const bool trace = (tunables().tile_debug & kSelStreamTrace) != 0; // development: where a feed's time goes (stderr)
     const auto t_start = std::chrono::steady_clock::now();
     auto since = [&]() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count(); };
     if (n_pieces) s->pool->start(n_pieces, job);

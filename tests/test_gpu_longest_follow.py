@@ -185,3 +185,48 @@ def test_follow_form_two_letter_text_walks_that_run_three_blocks_ahead_of_their_
     N.set_tunable("longest_form", 8)  # ... k_longest_follow there too
     got, kname, _ = _run(a, hay, True)
     assert kname == "k_longest_follow" and got.shape == want.shape and (got == want).all()
+
+
+def test_walk_pipeline_four_byte_lengths_keyword_of_65536_units():
+    """A keyword of 65 536 units makes the lengths four bytes wide: the walk kernels' <unsigned int> forms, k_longest_sync<unsigned int>,
+    k_longest_chain (the count pass that reads the lengths from global memory) and k_longest_emit (the start bitmap + a length
+    lookup per match).  The single letters are keywords, so every position is a match (no selective filter, a dense chain); the
+    long keywords are random letters, so a walk dies after a few steps except where one of them is planted."""
+    rng = np.random.default_rng(65536)
+    def letters(k):
+        return rng.integers(97, 123, k).astype(np.uint16)
+    long_kw, k40000, k1000, k300 = letters(65536), letters(40000), letters(1000), letters(300)
+    kws = [utf16(chr(c)) for c in range(97, 123)] + [long_kw, k300, k1000, k40000]
+    n = 200003
+    hay = letters(n)
+    hay[1000:1000 + 65536] = long_kw
+    hay[70000:70000 + 40000] = k40000
+    hay[120000:120000 + 1000] = k1000
+    hay[n - 30000:] = long_kw[:30000]  # cut off by the end of the buffer
+    a = Automaton(N.MODE_LONGEST, kws, True)
+    info = a.info()
+    assert info["max_keyword_len"] == 65536 and info["tile_kernel"] == 0
+    want = Oracle(FAM_LONGEST, kws).match(hay)
+    lens = set((want[:, 1] - want[:, 0]).tolist())
+    assert {1, 1000, 40000, 65536} <= lens and want[-1, 1] == n
+    import torch
+    d_hay = torch.from_numpy(hay.view(np.int16)).cuda()
+    for force, prefix in ((0, "k_longest_walk"), (1, "k_longest_walk<unsigned int")):
+        N.set_tunable("force_kernel", force)
+        for with_ids in (False, True):
+            w = want if with_ids else want[:, :2]
+            got, kname, ex = _run(a, hay, with_ids, d_hay=d_hay)
+            assert kname.startswith(prefix) and "unsigned int" in kname, kname
+            assert got.shape == w.shape and (got == w).all() and ex == n, (force, with_ids)
+            # three shards, the chain handed on: the first cut falls inside the planted long keyword, so the chain enters the
+            # last shard beyond its first position (and skips the one-unit shard between them)
+            cuts, parts, entry = [0, 66000, 66001, n], [], 0
+            for lo, hi in zip(cuts[:-1], cuts[1:]):
+                if entry >= hi:
+                    continue
+                part, kname, ex = _run(a, hay, with_ids, own=(lo, hi), entry=max(entry, lo), d_hay=d_hay)
+                assert kname.startswith(prefix) and "unsigned int" in kname and ex >= hi, kname
+                parts.append(part)
+                entry = ex
+            got = np.concatenate(parts)
+            assert len(parts) == 2 and got.shape == w.shape and (got == w).all(), (force, with_ids)
