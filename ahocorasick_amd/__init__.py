@@ -6,8 +6,8 @@ This package is the host-side mirror of the reference's API on top of it.  No CP
 from .strings import (AhoCorasickMap, AhoCorasickSet, Automaton, IllegalArgumentException, LongestMatchMap,
                       LongestMatchSet, MapMatchListener, ReadableMatchListener, SetMatchListener, ShortestMatchMap, ShortestMatchSet, Stream, StringMap,
                       StringSet, WholeWordLongestMatchMap, WholeWordLongestMatchSet, WholeWordMatchMap, WholeWordMatchSet,
-                      Utf8Error, utf8_unit_offsets, utf16)
+                      Utf8Error, utf8_line_offsets, utf8_unit_offsets, utf16)
 
 __all__ = ["AhoCorasickSet", "AhoCorasickMap", "LongestMatchSet", "LongestMatchMap", "WholeWordMatchSet",
            "WholeWordMatchMap", "ShortestMatchSet", "ShortestMatchMap", "WholeWordLongestMatchSet", "WholeWordLongestMatchMap", "StringSet", "StringMap", "SetMatchListener", "MapMatchListener", "ReadableMatchListener", "Stream", "Automaton",
-           "IllegalArgumentException", "utf16", "Utf8Error", "utf8_unit_offsets"]
+           "IllegalArgumentException", "utf16", "Utf8Error", "utf8_unit_offsets", "utf8_line_offsets"]

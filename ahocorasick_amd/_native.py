@@ -28,11 +28,16 @@ class AcgpuError(RuntimeError):
 
 class Utf8Error(ValueError):
     """ACGPU_E_ENCODING of acgpu_match_utf8: the haystack is not well-formed UTF-8.  start: the byte offset at which a strict
-    decoder stops -- UnicodeDecodeError.start of bytes.decode("utf-8") on the same buffer."""
+    decoder stops -- UnicodeDecodeError.start of bytes.decode("utf-8") on the same buffer.  haystack: None, or for the batch
+    entries the index of the first ill-formed haystack; start is then an offset inside THAT haystack."""
 
-    def __init__(self, start):
+    def __init__(self, start, haystack=None):
         self.start = int(start)
-        super().__init__("haystack is not well-formed UTF-8 at byte %d" % self.start)
+        self.haystack = None if haystack is None else int(haystack)
+        if haystack is None:
+            super().__init__("haystack is not well-formed UTF-8 at byte %d" % self.start)
+        else:
+            super().__init__("haystack %d is not well-formed UTF-8 at byte %d" % (self.haystack, self.start))
 
 
 class Info(ctypes.Structure):
@@ -90,6 +95,10 @@ class Utf8Stats(ctypes.Structure):  # acgpu_utf8_stats
     _fields_ = [("n_units", ctypes.c_uint64), ("first_bad", ctypes.c_int64), ("ascii", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class Utf8BatchStats(ctypes.Structure):  # acgpu_utf8_batch_stats
+    _fields_ = [("n_units", ctypes.c_uint64), ("first_bad", ctypes.c_int64), ("bad_haystack", ctypes.c_uint32), ("ascii", ctypes.c_uint32)]
+
+
 def _summary_dtype():
     import numpy as np
     return np.dtype({"names": ["n_matches", "start", "end", "keyword_id", "reserved"],
@@ -110,7 +119,7 @@ SYMBOLS = ["acgpu_build", "acgpu_free", "acgpu_get_info", "acgpu_match_u16", "ac
            "acgpu_stream_set_pipelined", "acgpu_stream_reserve", "acgpu_cursor_open", "acgpu_cursor_next",
            "acgpu_cursor_get_stats", "acgpu_cursor_close", "acgpu_count_u16", "acgpu_count_device",
            "acgpu_replace_u16", "acgpu_replace_device", "acgpu_replace_batch_u16", "acgpu_summary_batch_u16",
-           "acgpu_match_utf8", "acgpu_replace_utf8"]
+           "acgpu_match_utf8", "acgpu_replace_utf8", "acgpu_match_batch_utf8", "acgpu_summary_batch_utf8"]
 
 _lib = None
 
@@ -199,6 +208,10 @@ def lib():
         L.acgpu_summary_batch_u16.argtypes = [vp, vp, vp, u32, vp, ctypes.POINTER(SummaryStats)]
         L.acgpu_match_utf8.restype = ci
         L.acgpu_match_utf8.argtypes = [vp, vp, u64, ci, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(Utf8Stats)]
+        L.acgpu_match_batch_utf8.restype = ci
+        L.acgpu_match_batch_utf8.argtypes = [vp, vp, vp, u32, ci, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(Utf8BatchStats)]
+        L.acgpu_summary_batch_utf8.restype = ci
+        L.acgpu_summary_batch_utf8.argtypes = [vp, vp, vp, u32, vp, ctypes.POINTER(SummaryStats), ctypes.POINTER(Utf8BatchStats)]
         L.acgpu_replace_utf8.restype = ci
         L.acgpu_replace_utf8.argtypes = [vp, vp, u64, vp, vp, u32, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(ReplaceStats),
                                          ctypes.POINTER(Utf8Stats)]

@@ -36,4 +36,16 @@ __device__ __forceinline__ uint32_t hashed_goto(const uint64_t *hkeys, const uin
     }
 }
 
+// A batch's text (the haystacks with a separator unit behind each; cat_off[i] = the first unit of haystack i): the last haystack
+// that begins at or before text position pos (k_batch_tag's search)
+__device__ __forceinline__ uint32_t haystack_of(const uint32_t *__restrict__ cat_off, uint32_t n_hay, uint32_t pos) {
+    uint32_t lo = 0, hi = n_hay;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (cat_off[mid] <= pos) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 } // namespace acgpu

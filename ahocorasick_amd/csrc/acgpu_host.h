@@ -400,6 +400,39 @@ int utf8_map_records(const Utf8Text &text, int32_t *d_recs, uint64_t cnt, uint32
 // between the two units of a surrogate pair is rounded DOWN.  Not for an all-ASCII text (there the unit is the byte).
 int utf8_map_position(const Utf8Text &text, uint64_t unit, int64_t *d_out, hipStream_t stream);
 
+// A batch of UTF-8 haystacks staged as ONE shard (acgpu_utf8.hip): the caller's span copied once, every haystack validated on its
+// own, and transcoded into the text a batch call scans -- the haystacks' units with the separator unit behind every haystack.
+struct Utf8Batch {
+    Utf8Text text;                       // shard: d.stage_hay, n_units + n_haystacks units, all owned; n_units: WITHOUT separators; d_ckpt:
+                                         // indexed by the unit without separators (text unit - haystack), nullptr for an all-ASCII batch
+    const uint32_t *d_boff = nullptr;    // n_haystacks + 1 byte offsets relative to the span's first byte (d.utf8_aux)
+    const uint32_t *d_cat_off = nullptr; // n_haystacks + 1: the first unit of every haystack in the shard (d.batch_off), what k_batch_tag,
+                                         // k_batch_summary and haystack_of take
+    uint32_t n_haystacks = 0;
+    uint32_t bad_haystack = 0;           // ACGPU_E_ENCODING: the first ill-formed haystack; text.first_bad is relative to ITS first byte
+};
+// bytes[offsets[0] .. offsets[n]) -> Utf8Batch on `stream`, which it waits for once, as stage_utf8_text does.  offsets: checked
+// (check_batch), the span not empty.  validate_only: no shard is built (the calls that go haystack by haystack stage every
+// haystack with stage_utf8_text afterwards); out->text.n_units is set all the same.  ACGPU_E_ENCODING: nothing was transcoded
+// and the stream is idle.  The caller holds d.mu.
+int stage_utf8_batch(DeviceState &d, const HostTables &t, const uint8_t *bytes, const uint64_t *offsets, uint32_t n, hipStream_t stream,
+                     Utf8Batch *out, bool validate_only = false);
+// cnt records of the scan over b's shard in d_recs -> records tagged with their haystack in d_out, positions in bytes relative to
+// the haystack (k_utf8_batch_tag; an all-ASCII batch: k_batch_tag, there a relative unit is a relative byte)
+int utf8_batch_tag(const Utf8Batch &b, const void *d_recs, uint64_t cnt, int record_kind, void *d_out, hipStream_t stream);
+// The first records of n_entries summaries from units to bytes (k_summary_utf8_bytes): b given, the entries of b's haystacks;
+// else the entries -- one -- of `text` scanned as a text of its own.  Nothing is launched where there are no checkpoints.
+int utf8_summary_bytes(const Utf8Batch *b, const Utf8Text &text, acgpu_batch_summary *d_sum, uint32_t n_entries, hipStream_t stream);
+
+// For as long as a batch's text is scanned: d.start_behind is the separator unit (WholeWordLongest: every haystack's first unit
+// is a walk start).  BatchText does the same for the texts it stages.  The caller holds d.mu.
+struct SeparatorScan {
+    DeviceState &d;
+    SeparatorScan(DeviceState &d_, const HostTables &t) : d(d_) { d.start_behind = t.sep_unit; }
+    SeparatorScan(const SeparatorScan &) = delete;
+    ~SeparatorScan() { d.start_behind = -1; }
+};
+
 // acgpu_match_u16 behind its argument checks; the caller holds d.mu (acgpu_match_batch_u16 calls it per haystack).
 int match_host_text(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack, uint64_t n_units, int record_kind, void *out,
                     uint64_t cap, uint64_t *n_out);

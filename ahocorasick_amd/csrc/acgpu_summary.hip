@@ -11,6 +11,9 @@
 // haystack are CONTIGUOUS, within a piece and from piece to piece, and a piece's record list is a sequence of runs, one per
 // haystack that has records in it, haystacks ascending.  A piece therefore holds at most one run per haystack; a run that a piece
 // boundary cuts continues as the first run of the next piece.
+//
+// acgpu_summary_batch_utf8 is the same call for UTF-8 haystacks: the text comes from stage_utf8_batch (acgpu_utf8.hip) as a device
+// shard, the pieces and k_batch_summary run unchanged, and k_summary_utf8_bytes maps the first records to bytes at the end.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,17 +40,6 @@ __global__ __launch_bounds__(kSummaryBlock) void k_summary_fill(acgpu_batch_summ
     s.start = s.end = s.keyword_id = -1;
     s.reserved = 0;
     out[i] = s;
-}
-
-// the last haystack that begins at or before text position pos (k_batch_tag's search)
-__device__ __forceinline__ uint32_t haystack_of(const uint32_t *__restrict__ cat_off, uint32_t n_hay, uint32_t pos) {
-    uint32_t lo = 0, hi = n_hay;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (cat_off[mid] <= pos) lo = mid;
-        else hi = mid;
-    }
-    return lo;
 }
 
 // A piece's cnt Map records (buffer relative; `base` = the text position of the buffer's unit 0) into the summaries: a lane per
@@ -111,7 +103,8 @@ struct SummaryTarget {
 // One text through the pieces; behind every piece that scan_next_piece completed (a piece scanned again for want of room comes
 // back once) the summary kernel on its records.  The host waits for nothing here: the next scan follows on the same stream.
 int summary_pieces(acgpu_automaton *a, DeviceState &d, const PieceScan &scan, bool whole, const SummaryTarget &tg, acgpu_summary_stats *st) {
-    PieceDriver p(0, scan.n, 0, whole, ACGPU_REC_MAP, &d.count_res); // the pool's reservoir of Map records (one call at a time holds the pool)
+    // the pool's reservoir of Map records (one call at a time holds the pool); a device shard is driven over the units it owns
+    PieceDriver p(0, scan.shard ? scan.shard->own_end : scan.n, 0, whole, ACGPU_REC_MAP, &d.count_res);
     int rc = ACGPU_OK;
     while (rc == ACGPU_OK && p.pos < p.end) {
         uint64_t cnt = 0, base = 0;
@@ -183,6 +176,75 @@ int acgpu_summary_batch_u16(const acgpu_automaton *ca, const uint16_t *units, co
     HIP_TRY(hipStreamSynchronize(stream));
     for (uint32_t i = 0; i < n_haystacks; i++) sum.n_matched += out[i].n_matches != 0;
     if (st) *st = sum;
+    return ACGPU_OK;
+}
+
+int acgpu_summary_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
+                             acgpu_batch_summary *out, acgpu_summary_stats *st, acgpu_utf8_batch_stats *stats) {
+    if (!ca || !offsets || (n_haystacks && !out)) return ACGPU_E_INVALID;
+    acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
+    const HostTables &t = a->t;
+    BatchPlan plan; // (in bytes: bytes >= units, so bytes + haystacks < 2^31 bounds the text the scan sees)
+    int rc = check_batch(t, reinterpret_cast<const uint16_t *>(bytes), offsets, n_haystacks, &plan);
+    if (rc) return rc;
+    acgpu_utf8_batch_stats us{};
+    us.first_bad = -1;
+    us.ascii = 1;
+    if (plan.total == 0) { // (nothing to decode and nothing to find: no device needed)
+        for (uint32_t i = 0; i < n_haystacks; i++) out[i] = acgpu_batch_summary{0, -1, -1, -1, 0};
+        if (st) *st = acgpu_summary_stats{};
+        if (stats) *stats = us;
+        return ACGPU_OK;
+    }
+    PoolCall call(a); // (no device: fails here and out is untouched)
+    if (call.rc) return call.rc;
+    DeviceState &d = *call.d;
+    if ((rc = call.idle())) return rc; // (the NULL stream: see the stream rule)
+    const hipStream_t stream = d.call_stream;
+    Utf8Batch b;
+    rc = stage_utf8_batch(d, t, bytes, offsets, n_haystacks, stream, &b, plan.per_haystack);
+    if (rc == ACGPU_E_ENCODING) { // (the stream is idle: the pool is as usable as before the call)
+        us.first_bad = b.text.first_bad;
+        us.bad_haystack = b.bad_haystack;
+        us.ascii = 0;
+        if (stats) *stats = us;
+        return rc;
+    }
+    if (rc) return call.fail(rc);
+    us.n_units = b.text.n_units;
+    us.ascii = b.text.n_units == plan.total;
+    const size_t sum_bytes = (size_t)n_haystacks * sizeof(acgpu_batch_summary);
+    if ((rc = d.summary.ensure(sum_bytes))) return call.fail(rc);
+    acgpu_batch_summary *d_sum = reinterpret_cast<acgpu_batch_summary *>(d.summary.p);
+    hipLaunchKernelGGL(k_summary_fill, dim3((n_haystacks + kSummaryBlock - 1) / kSummaryBlock), dim3(kSummaryBlock), 0, stream, d_sum, n_haystacks);
+    if (hipGetLastError() != hipSuccess) return call.fail(ACGPU_E_HIP);
+    acgpu_summary_stats sum{};
+    const bool whole = shard_rule(t, ACGPU_REC_MAP, false).sequential; // (a device shard: as acgpu_replace_utf8 drives its pieces)
+    if (plan.per_haystack) { // every haystack staged and driven as a text of its own, into its own entry, mapped before the next is staged
+        // the target of one haystack alone: one offset that is the text's origin as well -- its value does not matter, word 0 of
+        // the batch's offsets table (stage_utf8_batch has made room for it) holds it
+        uint32_t *d_zero = reinterpret_cast<uint32_t *>(d.batch_off.p);
+        if (hipMemsetAsync(d_zero, 0, 4, stream) != hipSuccess) return call.fail(ACGPU_E_HIP);
+        for (uint32_t i = 0; i < n_haystacks && rc == ACGPU_OK; i++) {
+            const uint64_t len = offsets[i + 1] - offsets[i];
+            if (!len) continue;
+            Utf8Text text;
+            if ((rc = stage_utf8_text(d, bytes + offsets[i], len, stream, &text))) break;
+            if ((rc = summary_pieces(a, d, PieceScan{a, d, nullptr, 0, &text.shard, stream}, whole, SummaryTarget{d_zero, 1, 0, d_sum + i}, &sum))) break;
+            rc = utf8_summary_bytes(nullptr, text, d_sum + i, 1, stream);
+        }
+        if (rc == ACGPU_E_ENCODING) rc = ACGPU_E_HIP; // (never: the batch has been validated)
+    } else {
+        SeparatorScan sep(d, t);
+        rc = summary_pieces(a, d, PieceScan{a, d, nullptr, 0, &b.text.shard, stream}, whole, SummaryTarget{b.d_cat_off, n_haystacks, 0, d_sum}, &sum);
+        if (rc == ACGPU_OK) rc = utf8_summary_bytes(&b, b.text, d_sum, n_haystacks, stream);
+    }
+    if (rc) return call.fail(rc);
+    if (hipMemcpyAsync(out, d_sum, sum_bytes, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
+        return call.fail(ACGPU_E_HIP);
+    for (uint32_t i = 0; i < n_haystacks; i++) sum.n_matched += out[i].n_matches != 0;
+    if (st) *st = sum;
+    if (stats) *stats = us;
     return ACGPU_OK;
 }
 

@@ -12,13 +12,22 @@
 //                  and a walk of at most 31 units over the lead bytes.
 // For acgpu_replace_utf8 (acgpu_replace.hip) the front end and k_utf8_map are host functions of their own (stage_utf8_text,
 // utf8_map_records), and k_utf8_pos maps one unit position -- a piece's boundary -- the same way (utf8_map_position).
+// acgpu_match_batch_utf8 (here) and acgpu_summary_batch_utf8 (acgpu_summary.hip) are the batch form: stage_utf8_batch knows where
+// the haystacks begin -- k_utf8_batch_count validates every haystack on its own (lane_view's twelfth mask, the cuts),
+// k_utf8_batch_write stores the separator unit behind every haystack and every haystack's first unit (cat_off), the checkpoints
+// stay those of the buffer read as one text; k_utf8_batch_tag is k_batch_tag and k_utf8_map in one, k_summary_utf8_bytes maps
+// the summaries' first records.
 // What a lane knows about its 16 bytes is eleven bit masks over a window of 24 bytes (the 4 before, its own, the 4 behind), built
 // by one function that both passes over the text share, so they cannot disagree about a count.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <vector>
+
 #include "acgpu_device.h"
 #include "acgpu_host.h"
 #include "acgpu_internal.h"
+#include "acgpu_kernels.h"
 
 using namespace acgpu;
 
@@ -31,6 +40,7 @@ constexpr uint32_t kU8Own = 0x000ffff0u;             // the window's bits of a l
 constexpr uint32_t kCkptLow = 0x80000000u;           // checkpoint flag: the unit is the low surrogate of the sequence named
 
 static_assert(sizeof(acgpu_utf8_stats) == 24, "the layout include/acgpu.h promises");
+static_assert(sizeof(acgpu_utf8_batch_stats) == 24, "the layout include/acgpu.h promises");
 
 // What a lane knows about its bytes.  Bit k of a mask stands for the byte at offset o - 4 + k of the text, o the lane's first.
 struct LaneView {
@@ -38,13 +48,33 @@ struct LaneView {
     uint32_t lead;   // own bytes inside the text that are no continuation bytes: every one begins a sequence
     uint32_t four;   // ... of those, the leads of 4-byte sequences (two units)
     uint32_t bad;    // own bytes at which a strict decoder stops: leads of ill-formed sequences, unclaimed continuation bytes
+    uint32_t cut;    // the batch form: bytes of the window's bits 4..23 that begin a haystack (or are the buffer's end)
+    uint32_t next;   // the batch form: the first boundary j with boff[j] >= o -- until the lane meets it, its bytes are haystack j - 1's
     __device__ __forceinline__ uint32_t byte(int k) const { return (w[k >> 2] >> (8 * (k & 3))) & 0xffu; }
     __device__ __forceinline__ uint32_t units() const { return __popc(lead) + __popc(four); }
 };
 
 // Every lane of the wave takes part (the neighbours' bytes come through cross-lane moves; a wave's first and last lane load
 // theirs).  in: 16-byte aligned, readable up to n rounded up to 16 and 4 bytes more.
-__device__ __forceinline__ LaneView lane_view(const uint8_t *__restrict__ in, uint32_t n, uint32_t o) {
+//
+// BATCH: the buffer is n_hay haystacks, haystack j the bytes [boff[j], boff[j + 1]), boff[0] = 0, boff[n_hay] = n; every haystack
+// has to be well-formed ON ITS OWN.  The twelfth mask, cut, has a bit where a byte begins a haystack, and
+//  * a lead is bad when a byte it needs lies at or behind a cut (the haystack's end truncates its sequence);
+//  * a continuation byte that stands at a cut is unclaimed (nothing of its own haystack can claim it).
+// Why the buffer's smallest flagged offset p is then the first ill-formed haystack's own error position: let h be the first
+// haystack that is ill-formed and e the byte at which a strict decoder of h alone stops.  Every byte before e -- the haystacks
+// before h, and h's bytes before e -- belongs to a sequence that lies whole inside its own haystack; no cut falls behind its lead
+// and no continuation byte of it stands at a cut, so these bytes are judged as the one-text rules judge them, by bytes of their own
+// haystack alone: none is flagged.  At e the decoder stops for one of three reasons.  A lead whose sequence is ill-formed in its
+// bytes: the one-text rules flag it.  A lead whose sequence the end of h truncates: the cut rule flags it, AT THE LEAD, and a
+// lead lies before every byte its sequence could claim in the next haystack, so no flag of a mis-claimed byte comes first.
+// A continuation byte that no sequence of h reaches: if it is h's first byte, it stands at a cut; if not, the byte before it is
+// h's, decoded, and did not claim it -- as in one text.  So p = e.  The cuts come from the offsets themselves: a search for the
+// first boundary at or behind the lane's first byte, then a walk over the boundaries of the window -- haystacks that are empty
+// are several boundaries at one byte, one bit.
+template <bool BATCH>
+__device__ __forceinline__ LaneView lane_view(const uint8_t *__restrict__ in, uint32_t n, uint32_t o, const uint32_t *__restrict__ boff = nullptr,
+                                              uint32_t n_hay = 0) {
     LaneView v;
     uint4 own = make_uint4(0, 0, 0, 0);
     if (o < n) own = *reinterpret_cast<const uint4 *>(in + o);
@@ -84,15 +114,33 @@ __device__ __forceinline__ LaneView lane_view(const uint8_t *__restrict__ in, ui
         f4 |= (uint32_t)(b == 0xf4u) << k;
     }
     const uint32_t own_bits = k_end >= 20 ? kU8Own : (((1u << k_end) - 1u) & kU8Own);
+    uint32_t cut = 0, first = 0;
+    if constexpr (BATCH) {
+        if (o < n) { // (boff[n_hay] = n > o: the search ends inside the table)
+            uint32_t hi = n_hay;
+            while (first < hi) {
+                const uint32_t mid = first + ((hi - first) >> 1);
+                if (boff[mid] < o) first = mid + 1;
+                else hi = mid;
+            }
+            for (uint32_t j = first; j <= n_hay; ++j) {
+                const uint32_t q = boff[j] - o;
+                if (q >= 20u) break;
+                cut |= 1u << (q + 4u);
+            }
+        }
+    }
+    v.cut = cut;
+    v.next = first;
     // a lead validates its own sequence: the bytes it needs are continuation bytes, the second one in the range its lead allows
     // (E0: A0..BF, no overlong form; ED: 80..9F, no surrogate; F0: 90..BF; F4: 80..8F, nothing above U+10FFFF)
     const uint32_t bad_lead = inv | (l2 & ~(cont >> 1)) | (l3 & ~(cont >> 2)) | (l4 & ~(cont >> 3)) | (e0 & ~(gea0 >> 1)) | (ed & (gea0 >> 1)) |
-                              (f0 & ~(ge90 >> 1)) | (f4 & (ge90 >> 1));
+                              (f0 & ~(ge90 >> 1)) | (f4 & (ge90 >> 1)) | (l2 & (cut >> 1)) | (l3 & (cut >> 2)) | (l4 & (cut >> 3));
     // a continuation byte is claimed when the nearest byte before it that is none is a lead long enough to reach it
     const uint32_t claimed = (l2 << 1) | ((l3 << 2) & (cont << 1)) | ((l4 << 3) & (cont << 2) & (cont << 1));
     v.lead = ~cont & own_bits;
     v.four = l4 & own_bits;
-    v.bad = (bad_lead | (cont & ~claimed)) & own_bits;
+    v.bad = (bad_lead | (cont & (~claimed | cut))) & own_bits;
     return v;
 }
 
@@ -118,8 +166,21 @@ __device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t *total) {
 __global__ __launch_bounds__(kU8Threads) void k_utf8_count(const uint8_t *__restrict__ in, uint32_t n, uint32_t *__restrict__ block_sums,
                                                            unsigned long long *__restrict__ res) {
     const uint32_t o = (blockIdx.x * kU8Threads + threadIdx.x) * kU8Lane;
-    const LaneView v = lane_view(in, n, o);
+    const LaneView v = lane_view<false>(in, n, o);
     // lanes are contiguous: the first lane of a wave that saw something holds the wave's smallest offset
+    const unsigned long long offenders = __ballot(v.bad != 0);
+    if (offenders && lane_id() == (uint32_t)__ffsll((long long)offenders) - 1)
+        atomicMin(res + 1, (unsigned long long)(o - 4 + (uint32_t)__ffs((int)v.bad) - 1));
+    uint32_t total;
+    (void)block_scan(v.units(), &total);
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
+}
+
+// k_utf8_count over a batch: the same sums (units of the buffer read as one text, separators not counted), the cut-aware validation
+__global__ __launch_bounds__(kU8Threads) void k_utf8_batch_count(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ boff,
+                                                                 uint32_t n_hay, uint32_t *__restrict__ block_sums, unsigned long long *__restrict__ res) {
+    const uint32_t o = (blockIdx.x * kU8Threads + threadIdx.x) * kU8Lane;
+    const LaneView v = lane_view<true>(in, n, o, boff, n_hay);
     const unsigned long long offenders = __ballot(v.bad != 0);
     if (offenders && lane_id() == (uint32_t)__ffsll((long long)offenders) - 1)
         atomicMin(res + 1, (unsigned long long)(o - 4 + (uint32_t)__ffs((int)v.bad) - 1));
@@ -147,7 +208,7 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_scan(uint32_t *__restrict__
 __global__ __launch_bounds__(kU8Threads) void k_utf8_write(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ block_base,
                                                            uint16_t *__restrict__ out, uint32_t n_units, uint32_t *__restrict__ ckpt) {
     const uint32_t o = (blockIdx.x * kU8Threads + threadIdx.x) * kU8Lane;
-    const LaneView v = lane_view(in, n, o);
+    const LaneView v = lane_view<false>(in, n, o);
     const uint32_t cnt = v.units();
     uint32_t total;
     uint32_t u = block_base[blockIdx.x] + block_scan(cnt, &total);
@@ -184,6 +245,75 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_write(const uint8_t *__rest
             out[u + 1] = (uint16_t)(0xdc00u + (cp & 0x3ffu));
             if (ckpt && ((u + 1) & 31u) == 0) ckpt[(u + 1) >> 5] = pos | kCkptLow;
             u += 2;
+        }
+    }
+}
+
+// k_utf8_write over a batch that is known to be well-formed, haystack by haystack.  out: the text the scan sees, n_units + n_hay
+// units: the haystacks' units with `sep` behind every haystack, empty ones included -- the unit of a lead at byte p of haystack h
+// goes to (units of bytes[0, p)) + h.  cat_off[j] = (units of bytes[0, boff[j])) + j, the first unit of haystack j in that text;
+// the lane that owns byte boff[j] stores it and the separator in front of it, and the lane of the buffer's last byte those of
+// the boundaries at the buffer's end (j = n_hay, and the empty haystacks at the end).  Checkpoints are indexed by the unit WITHOUT
+// separators -- the table of the buffer read as one text, which is well-formed because every haystack is.
+__global__ __launch_bounds__(kU8Threads) void k_utf8_batch_write(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ block_base,
+                                                                 uint16_t *__restrict__ out, uint32_t n_units, uint32_t *__restrict__ ckpt,
+                                                                 const uint32_t *__restrict__ boff, uint32_t n_hay, uint32_t *__restrict__ cat_off,
+                                                                 uint32_t sep) {
+    const uint32_t o = (blockIdx.x * kU8Threads + threadIdx.x) * kU8Lane;
+    const LaneView v = lane_view<true>(in, n, o, boff, n_hay);
+    const uint32_t cnt = v.units();
+    uint32_t total;
+    uint32_t u = block_base[blockIdx.x] + block_scan(cnt, &total);
+    if (o >= n || u + cnt > n_units) return; // (the second: never, the counts are those of k_utf8_batch_count)
+    uint32_t j = v.next;                      // the boundaries [0, j) lie before the byte the lane is at: it is haystack j - 1's
+    if (!(v.cut & kU8Own) && o + kU8Lane < n && v.lead == kU8Own && ((v.w[1] | v.w[2] | v.w[3] | v.w[4]) & 0x80808080u) == 0 &&
+        ((u + j - 1u) & 7u) == 0) {
+        // 16 ASCII bytes of one haystack (j >= 1: byte 0 is a cut) whose units begin on a 16-byte boundary of the output
+        uint32_t p[8];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t x = v.w[1 + i];
+            p[2 * i] = (x & 0xffu) | ((x & 0xff00u) << 8);
+            p[2 * i + 1] = ((x >> 16) & 0xffu) | ((x >> 8) & 0xff0000u);
+        }
+        uint4 *dst = reinterpret_cast<uint4 *>(out + u + j - 1u);
+        dst[0] = make_uint4(p[0], p[1], p[2], p[3]);
+        dst[1] = make_uint4(p[4], p[5], p[6], p[7]);
+        const uint32_t m = (0u - u) & 31u;
+        if (ckpt && m < kU8Lane) ckpt[(u + m) >> 5] = o + m;
+        return;
+    }
+#pragma unroll
+    for (int k = 4; k < 20; ++k) {
+        const uint32_t pos = o + (uint32_t)(k - 4);
+        if ((v.cut >> k) & 1u) {
+            while (j <= n_hay && boff[j] == pos) { // (several: empty haystacks)
+                cat_off[j] = u + j;
+                if (j) out[u + j - 1u] = (uint16_t)sep;
+                ++j;
+            }
+        }
+        if (!((v.lead >> k) & 1u)) continue;
+        const uint32_t b0 = v.byte(k), b1 = v.byte(k + 1) & 0x3fu, b2 = v.byte(k + 2) & 0x3fu, b3 = v.byte(k + 3) & 0x3fu;
+        uint16_t *dst = out + u + j - 1u; // (j >= 1: a lead is a byte of a haystack, whose boundary has been met)
+        if (ckpt && (u & 31u) == 0) ckpt[u >> 5] = pos;
+        if (b0 < 0xf0u) {
+            const uint32_t cp = b0 < 0x80u ? b0 : (b0 < 0xe0u ? ((b0 & 0x1fu) << 6) | b1 : ((b0 & 0x0fu) << 12) | (b1 << 6) | b2);
+            dst[0] = (uint16_t)cp;
+            u += 1;
+        } else {
+            const uint32_t cp = (((b0 & 0x07u) << 18) | (b1 << 12) | (b2 << 6) | b3) - 0x10000u;
+            dst[0] = (uint16_t)(0xd800u + (cp >> 10));
+            dst[1] = (uint16_t)(0xdc00u + (cp & 0x3ffu));
+            if (ckpt && ((u + 1) & 31u) == 0) ckpt[(u + 1) >> 5] = pos | kCkptLow;
+            u += 2;
+        }
+    }
+    if (o + kU8Lane >= n) { // the buffer's last lane: u = n_units, what is left are the boundaries at the buffer's end
+        while (j <= n_hay) {
+            cat_off[j] = u + j;
+            if (j) out[u + j - 1u] = (uint16_t)sep;
+            ++j;
         }
     }
 }
@@ -239,6 +369,53 @@ __global__ void k_utf8_pos(uint32_t unit, const uint8_t *__restrict__ in, uint32
     SeqPos s = seek(ckpt, unit);
     (void)advance(in, n, s, unit);
     *out = (int64_t)s.p;
+}
+
+// The byte offsets, relative to haystack h's first byte, of a record of the scan over a batch's text: its units first .. last
+// WITHOUT separators (text unit - h) through the checkpoints, minus the haystack's byte offset (0 where boff is not given).
+__device__ __forceinline__ void batch_bytes(uint32_t first, uint32_t last, uint32_t hay_byte, const uint8_t *__restrict__ in, uint32_t n,
+                                            const uint32_t *__restrict__ ckpt, int32_t *start, int32_t *end) {
+    SeqPos s = seek(ckpt, first);
+    (void)advance(in, n, s, first);
+    *start = (int32_t)(s.p - hay_byte);
+    if ((last >> 5) != (first >> 5)) s = seek(ckpt, last);
+    const uint32_t len = advance(in, n, s, last);
+    *end = (int32_t)(s.p + len - hay_byte);
+}
+
+// k_batch_tag and k_utf8_map in one, a lane per record: {start, end[, id]} in units of the batch's text -> {haystack, start, end[, id]}
+// in bytes of the haystack
+template <int REC>
+__global__ __launch_bounds__(kU8Threads) void k_utf8_batch_tag(const int32_t *__restrict__ recs, uint64_t cnt, const uint32_t *__restrict__ cat_off,
+                                                               uint32_t n_hay, const uint32_t *__restrict__ boff, const uint8_t *__restrict__ in, uint32_t n,
+                                                               uint32_t n_units, const uint32_t *__restrict__ ckpt, int32_t *__restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * kU8Threads + threadIdx.x;
+    if (i >= cnt) return;
+    constexpr int W = REC / 4;
+    const uint32_t start = (uint32_t)recs[i * W], end = (uint32_t)recs[i * W + 1];
+    const uint32_t h = haystack_of(cat_off, n_hay, start);
+    const uint32_t first = start - h, last = end - 1u - h; // (no match holds a separator: both are units of haystack h)
+    int32_t *o = out + i * (W + 1);
+    o[0] = (int32_t)h;
+    if (W == 3) o[3] = recs[i * W + 2];
+    if (first > last || last >= n_units) return; // (never: the scan's records lie inside the text)
+    batch_bytes(first, last, boff[h], in, n, ckpt, o + 1, o + 2);
+}
+
+// A lane per haystack, behind the last piece of a summary call: the first record of every entry that has one, from units
+// relative to its haystack to bytes relative to it.  cat_off given: entry i is haystack i of a batch's text (its first unit
+// without separators is cat_off[i] - i, its first byte boff[i]); not given: the entries' one text is `in` itself.
+__global__ __launch_bounds__(kU8Threads) void k_summary_utf8_bytes(acgpu_batch_summary *__restrict__ sum, uint32_t n_entries, const uint32_t *__restrict__ cat_off,
+                                                                   const uint32_t *__restrict__ boff, const uint8_t *__restrict__ in, uint32_t n,
+                                                                   uint32_t n_units, const uint32_t *__restrict__ ckpt) {
+    const uint32_t i = blockIdx.x * kU8Threads + threadIdx.x;
+    if (i >= n_entries) return;
+    acgpu_batch_summary *e = sum + i;
+    if (!e->n_matches || e->start < 0 || e->end <= e->start) return;
+    const uint32_t unit0 = cat_off ? cat_off[i] - i : 0u, byte0 = cat_off ? boff[i] : 0u;
+    const uint32_t first = unit0 + (uint32_t)e->start, last = unit0 + (uint32_t)e->end - 1u;
+    if (last >= n_units) return; // (never)
+    batch_bytes(first, last, byte0, in, n, ckpt, &e->start, &e->end);
 }
 
 } // namespace
@@ -299,6 +476,97 @@ int stage_utf8_text(DeviceState &d, const uint8_t *bytes, uint64_t n_bytes, hipS
     return ACGPU_OK;
 }
 
+int stage_utf8_batch(DeviceState &d, const HostTables &t, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_hay, hipStream_t stream,
+                     Utf8Batch *out, bool validate_only) {
+    *out = Utf8Batch{};
+    out->n_haystacks = n_hay;
+    const uint8_t *span = bytes + offsets[0];
+    const uint32_t n = (uint32_t)(offsets[n_hay] - offsets[0]), n_blocks = (n + kU8Block - 1) / kU8Block;
+    out->text.n_bytes = n;
+    // aux: stage_utf8_text's [n_units, first_bad | block sums | checkpoints], and behind them the byte offsets
+    const size_t sums_off = 64, ckpt_off = sums_off + (((size_t)n_blocks * 4 + 63) & ~(size_t)63);
+    const size_t boff_off = ckpt_off + ((((size_t)n / 32 + 1) * 4 + 63) & ~(size_t)63), off_bytes = ((size_t)n_hay + 1) * 4;
+    int rc;
+    if ((rc = d.utf8_in.ensure((size_t)n + 64))) return rc;
+    if ((rc = d.utf8_aux.ensure(boff_off + off_bytes))) return rc;
+    if ((rc = d.batch_off.ensure(off_bytes + 16))) return rc;
+    std::vector<uint32_t> h_boff;
+    try {
+        h_boff.resize((size_t)n_hay + 1);
+    } catch (...) {
+        return ACGPU_E_NOMEM;
+    }
+    for (uint32_t i = 0; i <= n_hay; i++) h_boff[i] = (uint32_t)(offsets[i] - offsets[0]);
+    const uint8_t *d_in = reinterpret_cast<const uint8_t *>(d.utf8_in.p);
+    unsigned long long *d_res = reinterpret_cast<unsigned long long *>(d.utf8_aux.p);
+    uint32_t *d_sums = reinterpret_cast<uint32_t *>((char *)d.utf8_aux.p + sums_off);
+    uint32_t *d_ckpt = reinterpret_cast<uint32_t *>((char *)d.utf8_aux.p + ckpt_off);
+    uint32_t *d_boff = reinterpret_cast<uint32_t *>((char *)d.utf8_aux.p + boff_off);
+    uint32_t *d_cat_off = reinterpret_cast<uint32_t *>(d.batch_off.p);
+    HIP_TRY(hipMemcpyAsync(d.utf8_in.p, span, n, hipMemcpyHostToDevice, stream)); // the caller's span as it lies: one copy
+    HIP_TRY(hipMemcpyAsync(d_boff, h_boff.data(), off_bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(d_res, 0xff, 16, stream));
+    hipLaunchKernelGGL(k_utf8_batch_count, dim3(n_blocks), dim3(kU8Threads), 0, stream, d_in, n, (const uint32_t *)d_boff, n_hay, d_sums, d_res);
+    hipLaunchKernelGGL(k_utf8_scan, dim3(1), dim3(kU8Threads), 0, stream, d_sums, n_blocks, d_res);
+    HIP_TRY(hipGetLastError());
+    unsigned long long h_res[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(h_res, d_res, 16, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream)); // (h_boff has been read by now, too)
+    out->text.n_units = h_res[0];
+    out->text.first_bad = (int64_t)h_res[1];
+    if (out->text.first_bad >= 0) {
+        // the haystack that holds byte p: the LAST j < n_hay with offset <= p (of several at one byte all but the last are empty)
+        const uint32_t p = (uint32_t)h_res[1];
+        const uint32_t j = (uint32_t)(std::upper_bound(h_boff.begin(), h_boff.begin() + n_hay, p) - h_boff.begin()) - 1u;
+        out->bad_haystack = j;
+        out->text.first_bad = (int64_t)(p - h_boff[j]);
+        return ACGPU_E_ENCODING;
+    }
+    if (out->text.n_units > n) return ACGPU_E_HIP; // (never: a sequence has no more units than bytes)
+    const bool ascii = out->text.n_units == n;
+    out->text.d_bytes = d_in;
+    out->d_boff = d_boff;
+    if (validate_only) return ACGPU_OK;
+    const uint64_t cat = out->text.n_units + n_hay;
+    if ((rc = d.stage_hay.ensure(cat * 2 + 16))) return rc;
+    hipLaunchKernelGGL(k_utf8_batch_write, dim3(n_blocks), dim3(kU8Threads), 0, stream, d_in, n, (const uint32_t *)d_sums,
+                       reinterpret_cast<uint16_t *>(d.stage_hay.p), (uint32_t)out->text.n_units, ascii ? nullptr : d_ckpt, (const uint32_t *)d_boff,
+                       n_hay, d_cat_off, (uint32_t)(uint16_t)t.sep_unit);
+    HIP_TRY(hipGetLastError());
+    out->text.shard.d_hay = (const uint16_t *)d.stage_hay.p;
+    out->text.shard.n_units = out->text.shard.own_end = cat;
+    out->text.shard.text_begin = out->text.shard.text_end = 1;
+    out->text.d_ckpt = ascii ? nullptr : d_ckpt;
+    out->d_cat_off = d_cat_off;
+    return ACGPU_OK;
+}
+
+int utf8_batch_tag(const Utf8Batch &b, const void *d_recs, uint64_t cnt, int record_kind, void *d_out, hipStream_t stream) {
+    if (!cnt) return ACGPU_OK;
+    if (!b.text.d_ckpt) {
+        HIP_TRY(launch_batch_tag(d_recs, cnt, record_kind, b.d_cat_off, b.n_haystacks, d_out, stream));
+        return ACGPU_OK;
+    }
+    const dim3 grid((unsigned)((cnt + kU8Threads - 1) / kU8Threads)), block(kU8Threads);
+    const uint32_t n = (uint32_t)b.text.n_bytes, n_units = (uint32_t)b.text.n_units;
+    if (record_kind == ACGPU_REC_SET)
+        hipLaunchKernelGGL(k_utf8_batch_tag<ACGPU_REC_SET>, grid, block, 0, stream, (const int32_t *)d_recs, cnt, b.d_cat_off, b.n_haystacks, b.d_boff,
+                           b.text.d_bytes, n, n_units, b.text.d_ckpt, (int32_t *)d_out);
+    else
+        hipLaunchKernelGGL(k_utf8_batch_tag<ACGPU_REC_MAP>, grid, block, 0, stream, (const int32_t *)d_recs, cnt, b.d_cat_off, b.n_haystacks, b.d_boff,
+                           b.text.d_bytes, n, n_units, b.text.d_ckpt, (int32_t *)d_out);
+    HIP_TRY(hipGetLastError());
+    return ACGPU_OK;
+}
+
+int utf8_summary_bytes(const Utf8Batch *b, const Utf8Text &text, acgpu_batch_summary *d_sum, uint32_t n_entries, hipStream_t stream) {
+    if (!text.d_ckpt || !n_entries) return ACGPU_OK;
+    hipLaunchKernelGGL(k_summary_utf8_bytes, dim3((n_entries + kU8Threads - 1) / kU8Threads), dim3(kU8Threads), 0, stream, d_sum, n_entries,
+                       b ? b->d_cat_off : nullptr, b ? b->d_boff : nullptr, text.d_bytes, (uint32_t)text.n_bytes, (uint32_t)text.n_units, text.d_ckpt);
+    HIP_TRY(hipGetLastError());
+    return ACGPU_OK;
+}
+
 } // namespace acgpu
 
 extern "C" {
@@ -341,6 +609,88 @@ int acgpu_match_utf8(const acgpu_automaton *ca, const uint8_t *bytes, uint64_t n
     if ((rc = utf8_map_records(text, reinterpret_cast<int32_t *>(d.stage_out.p), *n_out, (uint32_t)record_kind / 4, stream))) return call.fail(rc);
     HIP_TRY(hipMemcpyAsync(out, d.stage_out.p, *n_out * (uint64_t)record_kind, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
+    return ACGPU_OK;
+}
+
+int acgpu_match_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks, int record_kind,
+                           void *out, uint64_t cap, uint64_t *n_out, acgpu_utf8_batch_stats *stats) {
+    if (!ca || !n_out || !offsets || (cap && !out)) return ACGPU_E_INVALID;
+    if (record_kind != ACGPU_REC_SET && record_kind != ACGPU_REC_MAP) return ACGPU_E_INVALID;
+    acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
+    const HostTables &t = a->t;
+    BatchPlan plan; // (in bytes: bytes >= units, so bytes + haystacks < 2^31 bounds the text the scan sees)
+    int rc = check_batch(t, reinterpret_cast<const uint16_t *>(bytes), offsets, n_haystacks, &plan);
+    if (rc) return rc;
+    *n_out = 0;
+    acgpu_utf8_batch_stats st{};
+    st.first_bad = -1;
+    st.ascii = 1;
+    if (stats) *stats = st;
+    if (plan.total == 0) return ACGPU_OK; // (nothing to decode and nothing to find: no device needed)
+    PoolCall call(a);
+    if (call.rc) return call.rc;
+    DeviceState &d = *call.d;
+    if ((rc = call.idle())) return rc; // (the NULL stream: see the stream rule)
+    const hipStream_t stream = d.call_stream;
+    Utf8Batch b;
+    rc = stage_utf8_batch(d, t, bytes, offsets, n_haystacks, stream, &b, plan.per_haystack);
+    if (rc == ACGPU_E_ENCODING) { // (the stream is idle: the pool is as usable as before the call)
+        st.first_bad = b.text.first_bad;
+        st.bad_haystack = b.bad_haystack;
+        st.ascii = 0;
+        if (stats) *stats = st;
+        return rc;
+    }
+    if (rc) return call.fail(rc);
+    st.n_units = b.text.n_units;
+    st.ascii = b.text.n_units == plan.total;
+    if (stats) *stats = st;
+    const uint64_t W = (uint64_t)record_kind / 4, out_rec = (uint64_t)record_kind + 4;
+    if (plan.per_haystack) { // every haystack by the route acgpu_match_utf8 takes, tagged on the host
+        std::vector<int32_t> tmp;
+        uint64_t n = 0;
+        for (uint32_t i = 0; i < n_haystacks; i++) {
+            const uint64_t len = offsets[i + 1] - offsets[i];
+            if (!len) continue;
+            uint64_t got = 0;
+            const uint64_t room = cap > n ? cap - n : 0;
+            Utf8Text text;
+            if ((rc = stage_utf8_text(d, bytes + offsets[i], len, stream, &text))) return call.fail(rc == ACGPU_E_ENCODING ? ACGPU_E_HIP : rc);
+            if ((rc = d.stage_out.ensure(room * (uint64_t)record_kind + 16))) return call.fail(rc);
+            rc = match_shard(a, d, &text.shard, record_kind, d.stage_out.p, room, &got, stream, nullptr);
+            if (rc != ACGPU_OK && rc != ACGPU_E_OVERFLOW) return call.fail(rc);
+            if (rc == ACGPU_OK && got) {
+                if ((rc = utf8_map_records(text, reinterpret_cast<int32_t *>(d.stage_out.p), got, (uint32_t)W, stream))) return call.fail(rc);
+                try {
+                    tmp.resize(got * W);
+                } catch (...) {
+                    return call.fail(ACGPU_E_NOMEM);
+                }
+                if (hipMemcpyAsync(tmp.data(), d.stage_out.p, got * (uint64_t)record_kind, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                    hipStreamSynchronize(stream) != hipSuccess)
+                    return call.fail(ACGPU_E_HIP);
+                for (uint64_t r = 0; r < got; r++) {
+                    int32_t *o = (int32_t *)((char *)out + (n + r) * out_rec);
+                    o[0] = (int32_t)i;
+                    for (uint64_t w = 0; w < W; w++) o[1 + w] = tmp[r * W + w];
+                }
+            }
+            n += got;
+        }
+        *n_out = n;
+        return n > cap ? call.fail(ACGPU_E_OVERFLOW) : ACGPU_OK;
+    }
+    if ((rc = d.stage_out.ensure(cap * (uint64_t)record_kind + 16))) return call.fail(rc);
+    if ((rc = d.batch_out.ensure(cap * out_rec + 16))) return call.fail(rc);
+    {
+        SeparatorScan sep(d, t);
+        rc = match_shard(a, d, &b.text.shard, record_kind, d.stage_out.p, cap, n_out, stream, nullptr);
+    }
+    if (rc != ACGPU_OK) return call.fail(rc); // (ACGPU_E_OVERFLOW: *n_out is the capacity to call again with)
+    if (!*n_out) return ACGPU_OK;
+    if ((rc = utf8_batch_tag(b, d.stage_out.p, *n_out, record_kind, d.batch_out.p, stream))) return call.fail(rc);
+    if (hipMemcpyAsync(out, d.batch_out.p, *n_out * out_rec, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
+        return call.fail(ACGPU_E_HIP);
     return ACGPU_OK;
 }
 

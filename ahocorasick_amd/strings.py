@@ -56,6 +56,35 @@ def utf8_unit_offsets(data):
     return np.repeat(leads, 1 + (b[leads] >= 0xF0)).astype(np.int64)
 
 
+def utf8_line_offsets(data):
+    """The offsets of the lines of a UTF-8 buffer for the offsets= form of the batch entries: every line with its "\\n", a last
+    line without one if the buffer does not end in "\\n" -- bytes.splitlines(keepends=True) of a text whose only line break is
+    "\\n" -- as a uint64 array of (lines + 1) entries.  A log file goes in as it is:
+    contains_batch_utf8(buf, offsets=utf8_line_offsets(buf))."""
+    b = _utf8_bytes(data)
+    ends = np.flatnonzero(b == 0x0A).astype(np.uint64) + np.uint64(1)
+    tail = [b.size] if b.size and (not ends.size or int(ends[-1]) != b.size) else []
+    return np.concatenate([np.zeros(1, np.uint64), ends, np.array(tail, np.uint64)])
+
+
+def _pack_utf8(data, offsets):
+    """-> (uint8 buffer, uint64 offsets): a sequence of bytes-like haystacks joined once, or with `offsets` ONE buffer used in place"""
+    if offsets is not None:
+        off = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if off.size < 1:
+            raise ValueError("offsets needs at least one entry")
+        buf = _utf8_bytes(data)
+        if int(off[-1]) > buf.size:
+            raise ValueError("offsets reach past the end of the buffer")
+        return buf, off
+    parts = [_utf8_bytes(h) for h in data]
+    off = np.zeros(len(parts) + 1, dtype=np.uint64)
+    if parts:
+        off[1:] = np.cumsum([p.size for p in parts], dtype=np.uint64)
+    buf = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+    return np.ascontiguousarray(buf, dtype=np.uint8), off
+
+
 def _to_str(units):
     """UTF-16 code units -> str (lone surrogates pass through, as in a Java String)"""
     return np.ascontiguousarray(units, dtype=np.uint16).tobytes().decode("utf-16-le", "surrogatepass")
@@ -191,6 +220,48 @@ class Automaton:
                 continue
             N.check(rc, "acgpu_match_batch_u16")
             return out[:n_out.value]
+
+    def match_batch_utf8(self, data, with_ids, cap=None, stats=None, offsets=None):
+        """acgpu_match_batch_utf8: many short UTF-8 haystacks in one call -> (n, 3|4) int32 array of (haystack index, start,
+        end[, keyword index]) records, haystack by haystack in reference call order, start and end in BYTES relative to the
+        haystack.  data: a sequence of bytes-like objects, joined once on the host; with offsets= (n + 1 ascending byte
+        offsets) ONE buffer, used in place.  An ill-formed haystack raises Utf8Error (.haystack, and .start inside it).
+        stats: an N.Utf8BatchStats to fill in, if wanted."""
+        buf, off = _pack_utf8(data, offsets)
+        kind = N.REC_MAP if with_ids else N.REC_SET
+        cols = kind // 4 + 1
+        if cap is None:
+            cap = max(4096, int(off[-1] - off[0]) // 16)
+        buf_in = buf if buf.size else np.zeros(1, np.uint8)
+        st = stats if stats is not None else N.Utf8BatchStats()
+        while True:
+            out = np.empty((cap, cols), dtype=np.int32)
+            n_out = ctypes.c_uint64(0)
+            rc = N.lib().acgpu_match_batch_utf8(self._h, _vp(buf_in), _vp(off), len(off) - 1, kind, _vp(out), cap, ctypes.byref(n_out),
+                                                ctypes.byref(st))
+            if rc == N.E_OVERFLOW:
+                cap = int(n_out.value)
+                continue
+            if rc == N.E_ENCODING:
+                raise Utf8Error(st.first_bad, haystack=st.bad_haystack)
+            N.check(rc, "acgpu_match_batch_utf8")
+            return out[:n_out.value]
+
+    def summary_batch_utf8(self, data, stats=None, offsets=None):
+        """acgpu_summary_batch_utf8: many short UTF-8 haystacks decided in one call -> (array of N.SUMMARY_DTYPE with one entry
+        per haystack: n_matches and the first record in listener order in BYTES relative to the haystack, -1s where there is
+        none; stats dict).  data and offsets as for match_batch_utf8; an ill-formed haystack raises Utf8Error."""
+        buf, off = _pack_utf8(data, offsets)
+        n = len(off) - 1
+        out = np.zeros(n, dtype=N.SUMMARY_DTYPE)
+        buf_in = buf if buf.size else np.zeros(1, np.uint8)
+        st = N.SummaryStats()
+        ust = stats if stats is not None else N.Utf8BatchStats()
+        rc = N.lib().acgpu_summary_batch_utf8(self._h, _vp(buf_in), _vp(off), n, _vp(out) if n else None, ctypes.byref(st), ctypes.byref(ust))
+        if rc == N.E_ENCODING:
+            raise Utf8Error(ust.first_bad, haystack=ust.bad_haystack)
+        N.check(rc, "acgpu_summary_batch_utf8")
+        return out, {f: int(getattr(st, f)) for f, _ in N.SummaryStats._fields_}
 
     def match_device(self, d_hay_ptr, n_units, with_ids, d_out_ptr, cap, own=None, text_begin=True, text_end=True,
                      chain_entry=None, stream=0, profile=False, d_result=None):
@@ -663,12 +734,34 @@ class _BatchDecisions:
     def first_batch(self, haystacks):
         """[the arguments of the first listener call of match(h, listener), without the haystack, or None for h in haystacks]:
         (start, end) for a set, (start, end, value) for a map"""
-        s = self._summary(haystacks)
+        return self._first_rows(self._summary(haystacks))
+
+    def _first_rows(self, s):
         vals = getattr(self, "_values", None)
         rows = zip(s["n_matches"].tolist(), s["start"].tolist(), s["end"].tolist(), s["keyword_id"].tolist())
         if vals is None:
             return [(b, e) if n else None for n, b, e, _ in rows]
         return [(b, e, vals[k]) if n else None for n, b, e, k in rows]
+
+    def _summary_utf8(self, datas, offsets):
+        if offsets is None:
+            datas = _checked(datas)
+        elif datas is None:
+            raise TypeError("haystack is None")
+        return self._auto.summary_batch_utf8(datas, offsets=offsets)[0]
+
+    def contains_batch_utf8(self, datas, offsets=None):
+        """contains_batch for UTF-8 haystacks: a sequence of bytes-like objects, or with offsets= one buffer in place (a log
+        file: offsets=utf8_line_offsets(buf)).  Utf8Error (.haystack, .start) if one of them is ill-formed."""
+        return self._summary_utf8(datas, offsets)["n_matches"] > 0
+
+    def count_matches_batch_utf8(self, datas, offsets=None):
+        """count_matches_batch for UTF-8 haystacks (see contains_batch_utf8)"""
+        return self._summary_utf8(datas, offsets)["n_matches"].copy()
+
+    def first_batch_utf8(self, datas, offsets=None):
+        """first_batch for UTF-8 haystacks (see contains_batch_utf8): start and end in BYTES relative to the haystack"""
+        return self._first_rows(self._summary_utf8(datas, offsets))
 
 
 class StringSet(_BatchDecisions):
@@ -746,6 +839,22 @@ class StringSet(_BatchDecisions):
         skip = -1
         for h, s, e in self._auto.match_batch(haystacks, with_ids=False).tolist():
             if h != skip and not fn(haystacks[h], s, e):
+                skip = h
+
+    def find_all_batch_utf8(self, datas, offsets=None):
+        """Not in the reference: the (n,3) int32 array of (haystack index, start, end) records of many UTF-8 haystacks (a
+        sequence of bytes-like objects, or with offsets= one buffer in place) from ONE device call, start and end in BYTES
+        relative to the haystack.  Utf8Error (.haystack, .start) if one of them is ill-formed."""
+        return self._auto.match_batch_utf8(datas if offsets is not None else _checked(datas), with_ids=False, offsets=offsets)
+
+    def match_batch_utf8(self, datas, listener):
+        """Not in the reference: match_utf8(data, listener) for every haystack of a list in ONE device call: the listener
+        gets the haystack's own bytes and byte offsets into them.  A listener call that returns False ends THAT haystack's matches."""
+        datas = _checked(datas)
+        fn = _listener_fn(listener)
+        skip = -1
+        for h, s, e in self._auto.match_batch_utf8(datas, with_ids=False).tolist():
+            if h != skip and not fn(datas[h], s, e):
                 skip = h
 
     @property
@@ -864,6 +973,22 @@ class StringMap(_BatchDecisions):
         skip = -1
         for h, s, e, k in self._auto.match_batch(haystacks, with_ids=True).tolist():
             if h != skip and not fn(haystacks[h], s, e, vals[k]):
+                skip = h
+
+    def find_all_batch_utf8(self, datas, offsets=None):
+        """Not in the reference: the (n,4) int32 array of (haystack index, start, end, keyword index) records of many UTF-8
+        haystacks from ONE device call (see StringSet.find_all_batch_utf8)."""
+        return self._auto.match_batch_utf8(datas if offsets is not None else _checked(datas), with_ids=True, offsets=offsets)
+
+    def match_batch_utf8(self, datas, listener):
+        """Not in the reference: match_utf8(data, listener) for every haystack of a list in ONE device call (see
+        StringSet.match_batch_utf8)."""
+        datas = _checked(datas)
+        fn = _listener_fn(listener)
+        vals = self._values
+        skip = -1
+        for h, s, e, k in self._auto.match_batch_utf8(datas, with_ids=True).tolist():
+            if h != skip and not fn(datas[h], s, e, vals[k]):
                 skip = h
 
     @property

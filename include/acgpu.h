@@ -83,6 +83,11 @@
  *      the bytes (device)                       B
  *      block sums (device)                      B/1024  (4 bytes per 4096 bytes)
  *      checkpoints (device)                     B/8 at most  (4 bytes per 32 units)
+ *    acgpu_match_batch_utf8 / acgpu_summary_batch_utf8 need that for the span of B bytes and a staged text of N + H units (H = the
+ *    haystacks, a separator unit behind each), plus, kept by the pool:
+ *      byte offsets, haystacks' first units     4 H + 4 H (device)
+ *      tagged records (match)                   cap x (record_kind + 4)
+ *      summaries (summary)                      24 H, and the counting calls' reservoir
  */
 #ifndef ACGPU_H
 #define ACGPU_H
@@ -683,9 +688,9 @@ int acgpu_summary_batch_u16(const acgpu_automaton *a, const uint16_t *units, con
  * The call is ONE shard through the general path: neither the chunk-pipelined form acgpu_match_u16 takes from 2^25 units on
  * (a long text is copied whole before the scan begins, nothing overlaps), nor its one-launch form for texts of up to 4096 units
  * (a short text pays the fixed cost of five launches, two copies and two waits, several times that form's latency: batch short
- * texts, or decode them on the host).  Not built: count, batch, cursor, stream, device-resident and multi-device forms
- * for UTF-8 (replace: acgpu_replace_utf8 below); lossy decoding (U+FFFD); CESU-8 / WTF-8; the Java facade (its strings are UTF-16).  ACGPU_ABI_VERSION stays as it
- * is: adding symbols is compatible.
+ * texts with acgpu_match_batch_utf8 / acgpu_summary_batch_utf8 below).  Not built: count, batch replace, cursor, stream,
+ * device-resident and multi-device forms for UTF-8 (replace: acgpu_replace_utf8 below); lossy decoding (U+FFFD); CESU-8 / WTF-8;
+ * the Java facade (its strings are UTF-16).  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
  */
 typedef struct acgpu_utf8_stats {
     uint64_t n_units;    /* UTF-16 units the text decodes to (0 on ACGPU_E_ENCODING)                */
@@ -726,12 +731,60 @@ int acgpu_match_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_
  * withholds more).  From there on everything counts bytes: the plan runs unchanged over byte records and a byte table, and the
  * byte form of the emit kernel writes 16 output bytes per lane from the caller's bytes on the device and the table, through
  * the two slabs of acgpu_replace_u16 ("replace_slab_units" counts bytes here).
- * Not built: batch, device-resident, multi-device and stream forms; validating the replacements; the Java facade.
+ * Not built: batch (acgpu_replace_batch_utf8), device-resident, multi-device and stream forms; validating the replacements; the
+ * Java facade.
  * ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
  */
 int acgpu_replace_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, const uint8_t *repl_bytes,
                        const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap, uint64_t *n_out,
                        acgpu_replace_stats *st /* may be NULL */, acgpu_utf8_stats *ust /* may be NULL */);
+
+/*
+ * Batches of UTF-8 haystacks in HOST memory: acgpu_match_batch_u16 and acgpu_summary_batch_u16 for texts as they lie in files --
+ * log lines, JSON records, form fields -- in ONE device call.  Haystack i is bytes[offsets[i] .. offsets[i+1]) (the offsets
+ * convention of acgpu_match_batch_u16: n_haystacks + 1 ascending offsets, empty haystacks allowed anywhere); the haystacks are
+ * contiguous in the caller's buffer, which is copied to the device as it lies, once.
+ *  acgpu_match_batch_utf8 returns the records acgpu_match_batch_u16 returns for the haystacks decoded one by one --
+ *              acgpu_batch_set_match / acgpu_batch_map_match, the same count, order, haystack index and keyword_id, every
+ *              family -- with start and end as BYTE offsets relative to the haystack's first byte, by acgpu_match_utf8's MAPPING
+ *              RULE (the case inside a surrogate pair included).  On ACGPU_E_OVERFLOW *n_out is the capacity to retry with.
+ *  acgpu_summary_batch_utf8 returns out[i] = {count, first record} of those records for haystack i, the first record in byte
+ *              offsets relative to the haystack; all five families; never ACGPU_E_OVERFLOW.  st as acgpu_summary_batch_u16 fills it.
+ * VALIDATION is strict and PER HAYSTACK: every haystack must be well-formed on its own, as
+ * bytes[offsets[i]:offsets[i+1]].decode("utf-8") in CPython.  A sequence that a haystack boundary cuts is ill-formed, also where
+ * the next haystack's first bytes would complete it: "a\xc3" | "\xa9b" is refused at haystack 0, offset 1, although the buffer
+ * as a whole is valid.  Then the call returns ACGPU_E_ENCODING; stats->bad_haystack is the first ill-formed haystack and
+ * stats->first_bad the offset inside it at which a strict decoder stops (UnicodeDecodeError.start of that haystack); *n_out = 0,
+ * `out` is untouched, nothing has been scanned, the stream is idle and the pool is usable.
+ * ACGPU_E_INVALID, before a device is touched and with out and stats untouched: NULL a, offsets or n_out, cap without out (the
+ * summary: haystacks without out), a bad record_kind, descending offsets, bytes NULL with a byte to read, and
+ * offsets[n] - offsets[0] + n_haystacks >= 2^31 (bytes >= units, so this bounds the text the scan sees as well).
+ * n_haystacks == 0, or all haystacks empty: ACGPU_OK without a device; the summary fills {0, -1, -1, -1, 0}.
+ * Both work on the NULL stream, under the pool's lock (STREAM RULE above: tickets in flight on the pool give ACGPU_E_INVALID).
+ * How it works: k_utf8_batch_count is k_utf8_count with a twelfth mask, `cut`, a bit where a byte begins a haystack: a lead is
+ * bad when a byte it needs lies at or behind a cut, a continuation byte at a cut is unclaimed; the smallest flagged offset of the
+ * buffer is then the first ill-formed haystack's own error position, and the host turns it into (bad_haystack, first_bad).
+ * k_utf8_batch_write stores the units with the builder's separator unit behind every haystack -- the text acgpu_match_batch_u16
+ * scans -- and every haystack's first unit in it; the checkpoints stay indexed by the unit WITHOUT separators.  The scan is
+ * match_shard on that one shard (the summary: the pieces of acgpu_summary_batch_u16 over it, k_batch_summary behind each);
+ * k_utf8_batch_tag, a lane per record, finds the haystack and maps start and end - 1 to bytes relative to it
+ * (k_summary_utf8_bytes, a lane per haystack, the summaries' first records).  An all-ASCII batch writes no checkpoints and maps
+ * nothing.  Where acgpu_match_batch_u16 goes haystack by haystack (no free separator unit, a word matcher over a table that is
+ * not fold-consistent) these do too, after the same validation of the whole batch: one acgpu_match_utf8-style pass per haystack.
+ * Not built: acgpu_replace_batch_utf8, acgpu_count_utf8; device-resident, multi-device, stream and cursor forms; the one-launch
+ * form for tiny batches; the Java facade.  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
+ */
+typedef struct acgpu_utf8_batch_stats {
+    uint64_t n_units;      /* UTF-16 units of all haystacks, separators not counted (0 on ACGPU_E_ENCODING) */
+    int64_t  first_bad;    /* -1, or the offset INSIDE haystack bad_haystack at which a strict decoder stops */
+    uint32_t bad_haystack; /* the first haystack that is ill-formed (0 when first_bad == -1)                 */
+    uint32_t ascii;        /* 1: every byte < 0x80                                                           */
+} acgpu_utf8_batch_stats;  /* 24 bytes */
+int acgpu_match_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks, int record_kind,
+                           void *out, uint64_t cap, uint64_t *n_out, acgpu_utf8_batch_stats *stats /* may be NULL */);
+int acgpu_summary_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
+                             acgpu_batch_summary *out /* n_haystacks, host */, acgpu_summary_stats *st /* may be NULL */,
+                             acgpu_utf8_batch_stats *stats /* may be NULL */);
 
 /*
  * Synthetic haystack generator of the benchmark: unit i of the stream is
