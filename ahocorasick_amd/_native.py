@@ -119,7 +119,8 @@ SYMBOLS = ["acgpu_build", "acgpu_free", "acgpu_get_info", "acgpu_match_u16", "ac
            "acgpu_stream_set_pipelined", "acgpu_stream_reserve", "acgpu_cursor_open", "acgpu_cursor_next",
            "acgpu_cursor_get_stats", "acgpu_cursor_close", "acgpu_count_u16", "acgpu_count_device",
            "acgpu_replace_u16", "acgpu_replace_device", "acgpu_replace_batch_u16", "acgpu_summary_batch_u16",
-           "acgpu_match_utf8", "acgpu_replace_utf8", "acgpu_match_batch_utf8", "acgpu_summary_batch_utf8"]
+           "acgpu_match_utf8", "acgpu_replace_utf8", "acgpu_match_batch_utf8", "acgpu_summary_batch_utf8",
+           "acgpu_replace_batch_utf8"]
 
 _lib = None
 
@@ -215,6 +216,9 @@ def lib():
         L.acgpu_replace_utf8.restype = ci
         L.acgpu_replace_utf8.argtypes = [vp, vp, u64, vp, vp, u32, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(ReplaceStats),
                                          ctypes.POINTER(Utf8Stats)]
+        L.acgpu_replace_batch_utf8.restype = ci
+        L.acgpu_replace_batch_utf8.argtypes = [vp, vp, vp, u32, vp, vp, u32, vp, u64, vp, ctypes.POINTER(u64), ctypes.POINTER(ReplaceStats),
+                                               ctypes.POINTER(Utf8BatchStats)]
         L.acgpu_debug_wordhash_perfect.restype = ci
         L.acgpu_debug_wordhash_perfect.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.acgpu_debug_wordhash.restype = ci

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <map>
 #include <set>
 #include <memory>
@@ -225,7 +226,7 @@ struct DeviceState {
     PoolBuf replace_tab, replace_plan, replace_slab;      // acgpu_replace_*: the replacement table, the plan {sums, output positions}, the host entry's two slabs
     Pinned<> replace_pin;                                 // ... 64 bytes: a piece's output length and last end
     PoolEvent replace_ev[4];                              // ... slab b emitted (b), slab b copied out (2 + b)
-    PoolBuf replace_merged, replace_off;                  // acgpu_replace_batch_u16: a piece's records merged with its separators, the result's offsets
+    PoolBuf replace_merged, replace_off;                  // acgpu_replace_batch_u16: a piece's records merged with its separators, the result's offsets (acgpu_replace_batch_utf8's too)
     PoolBuf summary;                                      // acgpu_summary_batch_u16: 24 bytes per haystack, {records, the first of them}
     PoolBuf utf8_in, utf8_aux;                            // acgpu_match_utf8: the caller's bytes; {n_units, first_bad}, block sums, checkpoints (acgpu_utf8.hip)
     CountCall *count = nullptr;                          // the counting call that runs on this pool (it holds mu), or nullptr
@@ -408,6 +409,7 @@ struct Utf8Batch {
     const uint32_t *d_boff = nullptr;    // n_haystacks + 1 byte offsets relative to the span's first byte (d.utf8_aux)
     const uint32_t *d_cat_off = nullptr; // n_haystacks + 1: the first unit of every haystack in the shard (d.batch_off), what k_batch_tag,
                                          // k_batch_summary and haystack_of take
+    std::vector<uint32_t> h_boff;        // ... and on the host (what d_boff was uploaded from)
     uint32_t n_haystacks = 0;
     uint32_t bad_haystack = 0;           // ACGPU_E_ENCODING: the first ill-formed haystack; text.first_bad is relative to ITS first byte
 };
@@ -420,9 +422,27 @@ int stage_utf8_batch(DeviceState &d, const HostTables &t, const uint8_t *bytes, 
 // cnt records of the scan over b's shard in d_recs -> records tagged with their haystack in d_out, positions in bytes relative to
 // the haystack (k_utf8_batch_tag; an all-ASCII batch: k_batch_tag, there a relative unit is a relative byte)
 int utf8_batch_tag(const Utf8Batch &b, const void *d_recs, uint64_t cnt, int record_kind, void *d_out, hipStream_t stream);
+// A piece's cnt records of the scan over b's shard, in place in d_recs: units of the shard -> bytes relative to the SPAN
+// (k_utf8_batch_map).  An all-ASCII batch is mapped too: a record of haystack h stands h separators behind its byte.
+int utf8_batch_map_records(const Utf8Batch &b, int32_t *d_recs, uint64_t cnt, uint32_t cols, hipStream_t stream);
+// *d_out = the span's byte for unit `unit` of b's shard, enqueued on `stream` (k_utf8_batch_pos): a separator, the last one
+// included, maps to the byte where the next haystack begins (n_bytes behind the last); any other unit to the first byte of the
+// code point that holds it, rounded DOWN as utf8_map_position does.
+int utf8_batch_map_position(const Utf8Batch &b, uint64_t unit, int64_t *d_out, hipStream_t stream);
 // The first records of n_entries summaries from units to bytes (k_summary_utf8_bytes): b given, the entries of b's haystacks;
 // else the entries -- one -- of `text` scanned as a text of its own.  Nothing is launched where there are no checkpoints.
 int utf8_summary_bytes(const Utf8Batch *b, const Utf8Text &text, acgpu_batch_summary *d_sum, uint32_t n_entries, hipStream_t stream);
+
+// acgpu_replace_batch_utf8, behind a piece that emits the span's bytes [done, limit): the haystack boundaries whose output offset
+// that piece writes are [*j0, *j1) of boff (n_hay + 1 ascending byte offsets, boff[n_hay] = the span's bytes) -- those with
+// done <= boff[j] < limit, and behind the LAST piece (limit = the span's end) those at the end as well.  The pieces' [done, limit)
+// tile the span, so every boundary is taken by exactly one piece; a run of empty haystacks is a run of equal offsets, taken whole.
+inline void span_boundaries(const uint32_t *boff, uint32_t n_hay, uint64_t done, uint64_t limit, bool last, uint32_t *j0, uint32_t *j1) {
+    const uint32_t *end = boff + n_hay + 1;
+    auto below = [](uint32_t b, uint64_t x) { return (uint64_t)b < x; };
+    *j0 = (uint32_t)(std::lower_bound(boff, end, done, below) - boff);
+    *j1 = last ? n_hay + 1 : std::max(*j0, (uint32_t)(std::lower_bound(boff, end, limit, below) - boff));
+}
 
 // For as long as a batch's text is scanned: d.start_behind is the separator unit (WholeWordLongest: every haystack's first unit
 // is a walk start).  BatchText does the same for the texts it stages.  The caller holds d.mu.

@@ -19,6 +19,12 @@
 // units as a device shard; behind every piece its records become byte offsets (utf8_map_records) and its boundary a byte position
 // (utf8_map_position), and from there on the driver's bookkeeping, the plan and the emit count bytes: the emit is a template over
 // the element, k_replace_emit<uint16_t> for the entries above and k_replace_emit<uint8_t> for this one.
+//
+// acgpu_replace_batch_utf8 rewrites many UTF-8 texts as ONE span of bytes: stage_utf8_batch stages them as the device shard the
+// batch match call scans (a separator unit behind every haystack), and behind every piece its records become bytes of the span
+// (utf8_batch_map_records) and its boundary a byte of it (utf8_batch_map_position).  The span itself has NO separators, so nothing
+// is merged and nothing deleted: plan and emit run over the records alone, and the results lie back to back because the
+// haystacks do.  Where each result begins is computed behind the plan by k_replace_span_offsets, a lane per haystack boundary.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -368,6 +374,25 @@ __global__ __launch_bounds__(kMergeBlock) void k_replace_batch_offsets(const int
     out_off[(uint64_t)S.i0 + j + 1] = out_pos + (uint64_t)pos[j + records_before(recs, cnt, sep_at(S, j))];
 }
 
+// A UTF-8 batch call, behind a piece's plan: the output offset of the n_b haystack boundaries j0 .. j0 + n_b - 1 that the piece
+// emits (span_boundaries, acgpu_host.h), a lane per boundary.  b = boff[j] is a byte of the span with done <= b <= limit, and with
+// k = the piece's records that start before b (records and `done` in bytes of the span):
+//   k == 0 : out_off[j] = out_pos + (b - done)                                       -- text only in front of b
+//   k  > 0 : out_off[j] = out_pos + pos[k - 1] + rlen[id_{k-1}] + (b - e_{k-1})      -- record k - 1's replacement, then text
+// No record crosses a haystack boundary (in the scan's text a separator stands there), so e_{k-1} <= b; and the records in
+// front of b are the first k of the list because starts ascend.  A run of empty haystacks is several lanes with the same b.
+__global__ __launch_bounds__(kMergeBlock) void k_replace_span_offsets(const int32_t *__restrict__ recs, uint64_t cnt, ReplTable rt,
+                                                                      const int64_t *__restrict__ pos, const uint32_t *__restrict__ boff, uint32_t j0,
+                                                                      uint32_t n_b, int64_t done, uint64_t out_pos, uint64_t *__restrict__ out_off) {
+    const uint32_t t = blockIdx.x * kMergeBlock + threadIdx.x;
+    if (t >= n_b) return;
+    const int64_t b = (int64_t)boff[j0 + t];
+    const uint64_t k = records_before(recs, cnt, b);
+    int64_t at = b - done;
+    if (k) at = pos[k - 1] + (int64_t)repl_of(rt, recs[3 * (k - 1) + 2]).y + (b - (int64_t)recs[3 * (k - 1) + 1]);
+    out_off[j0 + t] = out_pos + (uint64_t)at;
+}
+
 // What one call holds while it runs (the caller holds d.mu).
 struct ReplaceCall {
     acgpu_automaton *a;
@@ -376,6 +401,8 @@ struct ReplaceCall {
     ReplTable rt{};
     uint32_t esz = 2;          // bytes of an element: 2, a UTF-16 unit; 1, a byte of a UTF-8 text (acgpu_replace_utf8).  What follows counts elements
     const Utf8Text *u8 = nullptr; // esz == 1: the staged text -- the scan runs over its units, everything below counts its bytes
+    const Utf8Batch *ub = nullptr; // ... a batch of them staged as one shard (u8 == &ub->text): n, done and the records count bytes of the SPAN;
+                                   // n_hay haystacks, d_out_off as below
     uint8_t *h_out = nullptr;  // the host entry's result (through the slabs) ...
     uint8_t *d_out = nullptr;  // ... or the device entry's
     uint64_t cap = 0;
@@ -450,6 +477,20 @@ int upload_table(ReplaceCall &c, const void *repl_units, const uint64_t *repl_of
 //    unit, therefore at or behind the rounded byte; rounding down only withholds more, and the limit still takes the maximum
 //    with done and last_end, so it never falls behind what has been emitted or inside a record of this piece.  The text is on
 //    the device as a whole, so "inside the buffer" holds trivially.
+//  * A UTF-8 BATCH call scans the haystacks' units with a separator behind each and keeps n, done, last_end and the limit in bytes
+//    of the caller's SPAN, which has no separators.  The map unit -> span byte (k_utf8_batch_map for records, k_utf8_batch_pos
+//    for the boundary) drops the h separators in front of haystack h and is monotone; a boundary that IS a separator maps to the
+//    byte where the next haystack begins.  A later record starts at or behind the boundary's unit x (first-unit families: at or
+//    behind own_hi; SHORTEST: at or behind own_hi - (max_len - 1), as above, and no record holds a separator): if x is a unit of
+//    a haystack, on a code-point boundary at or behind it, so at or behind the rounded byte; if x is haystack h's separator, in a
+//    haystack behind h, so at or behind boff[h + 1].  The rest is the UTF-8 argument.  Two facts that k_replace_span_offsets
+//    rests on follow.  (1) Every record of a piece's list lies below the piece's limit: the limit is at least last_end, the end
+//    of the list's last record, and the records ascend without overlapping -- so for a boundary b < limit, or any b on the last
+//    piece, the records counted in front of b are all planned by THIS piece, and the plan's sum is over exactly the list.
+//    (2) `done` never exceeds the first record's start: done is the previous piece's limit, a position no later record starts
+//    before -- for the first-unit families because such a record starts at or behind that piece's own_hi and last_end, for
+//    SHORTEST because it ends behind that piece's own_hi, hence starts at or behind own_hi - (max_len - 1), and behind every
+//    earlier record's end.  So b - done and pos[] (which are relative to done) are not negative for the boundaries a piece takes.
 // piece_bound: the family's part of the rule, in the scan's coordinates; replace_limit: the maximum, in the driver's.
 uint64_t piece_bound(const HostTables &t, uint64_t own_hi) {
     if (t.mode != ACGPU_MODE_SHORTEST) return own_hi;
@@ -518,7 +559,8 @@ int replace_piece(ReplaceCall &c, const void *hay, uint64_t base, const int32_t 
     uint64_t last_end = 0, bound = piece_bound(c.a->t, own_hi);
     // UTF-8: the boundary goes from units to bytes through the checkpoints (the last piece's limit is the text's end, and in an
     // all-ASCII text a unit is a byte); the byte rides with what the host reads behind the plan anyway
-    const bool map_bound = c.u8 && c.u8->d_ckpt && !last_or_whole;
+    // a batch's boundary always goes through the kernel: also in an all-ASCII batch a unit stands h separators behind its byte
+    const bool map_bound = !last_or_whole && (c.ub || (c.u8 && c.u8->d_ckpt));
     if (cnt || map_bound) {
         const uint32_t n_blocks = (uint32_t)((cnt + kPlanTile - 1) / kPlanTile);
         int rc = d.replace_plan.ensure((kPlanHead + (size_t)n_blocks + cnt) * 8); // {sum of the deltas, last end, boundary, -} | workgroup sums | pos
@@ -533,7 +575,8 @@ int replace_piece(ReplaceCall &c, const void *hay, uint64_t base, const int32_t 
                                    reinterpret_cast<const int32_t *>(d.count_res.p), n_found, c.seps, (const int64_t *)pos, c.out_pos, c.d_out_off);
             HIP_TRY(hipGetLastError());
         }
-        if (map_bound && (rc = utf8_map_position(*c.u8, bound, slot + 2, c.stream))) return rc;
+        if (map_bound && (rc = c.ub ? utf8_batch_map_position(*c.ub, bound, slot + 2, c.stream) : utf8_map_position(*c.u8, bound, slot + 2, c.stream)))
+            return rc;
         // (a piece without records reads the boundary alone)
         const size_t first = cnt ? 0 : 2, words = (map_bound ? 3 : 2) - first;
         HIP_TRY(hipMemcpyAsync(static_cast<int64_t *>(d.replace_pin.h) + first, slot + first, words * 8, hipMemcpyDeviceToHost, c.stream));
@@ -549,6 +592,16 @@ int replace_piece(ReplaceCall &c, const void *hay, uint64_t base, const int32_t 
     const int64_t total_s = (int64_t)(limit - c.done) + delta;
     if (limit < c.done || total_s < 0) return ACGPU_E_HIP; // (records that overlap or are out of order: not a family this call serves)
     const uint64_t total = (uint64_t)total_s;
+    if (c.ub) { // where the results of the haystacks that begin in [done, limit) begin: behind the plan, before the emit, no wait
+        uint32_t j0, j1;
+        span_boundaries(c.ub->h_boff.data(), c.n_hay, c.done, limit, last_or_whole, &j0, &j1);
+        if (j1 > j0) {
+            const int64_t *pos = cnt ? reinterpret_cast<const int64_t *>(d.replace_plan.p) + kPlanHead + (cnt + kPlanTile - 1) / kPlanTile : nullptr;
+            hipLaunchKernelGGL(k_replace_span_offsets, dim3((j1 - j0 + kMergeBlock - 1) / kMergeBlock), dim3(kMergeBlock), 0, c.stream, recs, cnt, c.rt,
+                               pos, c.ub->d_boff, j0, j1 - j0, done_rel, c.out_pos, c.d_out_off);
+            HIP_TRY(hipGetLastError());
+        }
+    }
     const uint64_t room = c.cap > c.out_pos ? c.cap - c.out_pos : 0, emit_total = std::min(total, room); // beyond cap: planned, not written
     if (emit_total && c.d_out) {
         const int rc = launch_emit(c, hay, recs, cnt, done_rel, 0, emit_total, c.d_out + c.out_pos * c.esz, c.stream);
@@ -597,7 +650,8 @@ int replace_pieces(ReplaceCall &c, int64_t chain, bool whole, const PieceScan &s
     if (!d.copy_stream) HIP_TRY(hipStreamCreateWithFlags(&d.copy_stream.h, hipStreamNonBlocking));
     for (auto &e : d.replace_ev)
         if (!e) HIP_TRY(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
-    PieceDriver p(0, c.u8 ? c.u8->n_units : c.n, chain, whole, ACGPU_REC_MAP, &d.count_res); // the pool's reservoir of Map records (a counting call's too: one call at a time holds the pool)
+    // (driven over the units the scan sees: a UTF-8 text's units, a UTF-8 batch's units and separators)
+    PieceDriver p(0, c.u8 ? c.u8->shard.n_units : c.n, chain, whole, ACGPU_REC_MAP, &d.count_res); // the pool's reservoir of Map records (a counting call's too: one call at a time holds the pool)
     int rc = ACGPU_OK;
     while (rc == ACGPU_OK && p.pos < p.end) {
         uint64_t cnt = 0, base = 0;
@@ -605,7 +659,11 @@ int replace_pieces(ReplaceCall &c, int64_t chain, bool whole, const PieceScan &s
         const void *hay = c.u8 ? (const void *)c.u8->d_bytes : scan.shard ? (const void *)scan.shard->d_hay : d.stage_hay.p;
         const int32_t *recs = reinterpret_cast<const int32_t *>(d.count_res.p);
         // UTF-8: the piece's records go from units to bytes where they lie (text relative: the shard is the whole text)
-        if (c.u8 && (rc = utf8_map_records(*c.u8, reinterpret_cast<int32_t *>(d.count_res.p), cnt, ACGPU_REC_MAP / 4, c.stream))) break;
+        // (a batch: span relative, and an all-ASCII one is mapped too)
+        int32_t *own = reinterpret_cast<int32_t *>(d.count_res.p);
+        if (c.ub) rc = utf8_batch_map_records(*c.ub, own, cnt, ACGPU_REC_MAP / 4, c.stream);
+        else if (c.u8) rc = utf8_map_records(*c.u8, own, cnt, ACGPU_REC_MAP / 4, c.stream);
+        if (rc) break;
         uint64_t n_list = cnt;
         if (c.h_cat_off && (rc = merge_separators(c, base, p.pos, &recs, &n_list))) break;
         rc = replace_piece(c, hay, base, recs, n_list, cnt, p.pos, whole || p.pos >= p.end);
@@ -732,6 +790,86 @@ int acgpu_replace_utf8(const acgpu_automaton *ca, const uint8_t *bytes, uint64_t
     const bool whole = shard_rule(a->t, ACGPU_REC_MAP, false).sequential;
     if ((rc = replace_pieces(c, 0, whole, PieceScan{a, d, nullptr, 0, &text.shard, c.stream}))) return call.fail(rc);
     HIP_TRY(hipStreamSynchronize(c.stream));
+    return replace_result(c, n_out, st);
+}
+
+int acgpu_replace_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
+                             const uint8_t *repl_bytes, const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap,
+                             uint64_t *out_offsets, uint64_t *n_out, acgpu_replace_stats *st, acgpu_utf8_batch_stats *ust) {
+    if (!ca || !offsets || !n_out || !out_offsets || (cap && !out)) return ACGPU_E_INVALID;
+    acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
+    const HostTables &t = a->t;
+    int rc = check_table(a, repl_bytes, repl_off, n_repl);
+    if (rc) return rc;
+    if (t.lone_surrogate) return ACGPU_E_UNSUPPORTED; // (as acgpu_replace_utf8)
+    BatchPlan plan; // (in bytes: bytes >= units, so bytes + haystacks < 2^31 bounds the text the scan sees)
+    if ((rc = check_batch(t, reinterpret_cast<const uint16_t *>(bytes), offsets, n_haystacks, &plan))) return rc;
+    *n_out = 0;
+    out_offsets[0] = 0;
+    if (st) *st = acgpu_replace_stats{};
+    acgpu_utf8_batch_stats us{};
+    us.first_bad = -1;
+    us.ascii = 1;
+    if (ust) *ust = us;
+    if (plan.total == 0) { // (nothing to decode and nothing to rewrite: no device needed)
+        for (uint32_t i = 0; i < n_haystacks; i++) out_offsets[i + 1] = 0;
+        return ACGPU_OK;
+    }
+    PoolCall call(a); // (no device: fails here, and out is untouched)
+    if (call.rc) return call.rc;
+    DeviceState &d = *call.d;
+    if ((rc = call.idle())) return rc; // (the NULL stream: see the stream rule)
+    // the whole batch is validated first, whichever way it is scanned, so that what is refused does not depend on the route
+    Utf8Batch b;
+    rc = stage_utf8_batch(d, t, bytes, offsets, n_haystacks, d.call_stream, &b, plan.per_haystack);
+    if (rc == ACGPU_E_ENCODING) { // (the stream is idle: the pool is as usable as before the call; out_offsets[1..] untouched)
+        us.first_bad = b.text.first_bad;
+        us.bad_haystack = b.bad_haystack;
+        us.ascii = 0;
+        if (ust) *ust = us;
+        return rc;
+    }
+    if (rc) return call.fail(rc);
+    us.n_units = b.text.n_units;
+    us.ascii = b.text.n_units == plan.total;
+    if (ust) *ust = us;
+    ReplaceCall c{a, d, d.call_stream};
+    c.esz = 1;
+    c.h_out = out;
+    c.cap = cap;
+    if ((rc = upload_table(c, repl_bytes, repl_off, n_repl))) return call.fail(rc);
+    const bool whole = shard_rule(t, ACGPU_REC_MAP, false).sequential; // (a device shard: as acgpu_replace_utf8 drives its pieces)
+    if (plan.per_haystack) { // every haystack by the route acgpu_replace_utf8 takes, the results back to back
+        for (uint32_t i = 0; i < n_haystacks; i++) {
+            const uint64_t len = offsets[i + 1] - offsets[i];
+            if (len) {
+                Utf8Text text;
+                if ((rc = stage_utf8_text(d, bytes + offsets[i], len, c.stream, &text))) return call.fail(rc == ACGPU_E_ENCODING ? ACGPU_E_HIP : rc); // (never ill-formed: validated)
+                c.u8 = &text;
+                c.n = len;
+                c.done = 0;
+                if ((rc = replace_pieces(c, 0, whole, PieceScan{a, d, nullptr, 0, &text.shard, c.stream}))) return call.fail(rc);
+                if (hipStreamSynchronize(c.stream) != hipSuccess) return call.fail(ACGPU_E_HIP); // (the next haystack is staged over this one)
+            }
+            out_offsets[i + 1] = c.out_pos;
+        }
+        return replace_result(c, n_out, st);
+    }
+    if ((rc = d.replace_off.ensure(((size_t)n_haystacks + 1) * 8))) return call.fail(rc);
+    c.u8 = &b.text;
+    c.ub = &b;
+    c.n = plan.total;
+    c.n_hay = n_haystacks;
+    c.d_out_off = reinterpret_cast<uint64_t *>(d.replace_off.p);
+    {
+        SeparatorScan sep(d, t);
+        rc = replace_pieces(c, 0, whole, PieceScan{a, d, nullptr, 0, &b.text.shard, c.stream});
+    }
+    if (rc) return call.fail(rc);
+    // (every boundary was written by exactly one piece, boundary 0 -- offset 0 -- included)
+    if (hipMemcpyAsync(out_offsets, c.d_out_off, ((size_t)n_haystacks + 1) * 8, hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
+        hipStreamSynchronize(c.stream) != hipSuccess)
+        return call.fail(ACGPU_E_HIP);
     return replace_result(c, n_out, st);
 }
 

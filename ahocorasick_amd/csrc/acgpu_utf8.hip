@@ -16,7 +16,8 @@
 // the haystacks begin -- k_utf8_batch_count validates every haystack on its own (lane_view's twelfth mask, the cuts),
 // k_utf8_batch_write stores the separator unit behind every haystack and every haystack's first unit (cat_off), the checkpoints
 // stay those of the buffer read as one text; k_utf8_batch_tag is k_batch_tag and k_utf8_map in one, k_summary_utf8_bytes maps
-// the summaries' first records.
+// the summaries' first records.  For acgpu_replace_batch_utf8 (acgpu_replace.hip) k_utf8_batch_map rewrites a piece's records to
+// bytes of the SPAN (utf8_batch_map_records) and k_utf8_batch_pos maps a piece's boundary (utf8_batch_map_position).
 // What a lane knows about its 16 bytes is eleven bit masks over a window of 24 bytes (the 4 before, its own, the 4 behind), built
 // by one function that both passes over the text share, so they cannot disagree about a count.
 #include <hip/hip_runtime.h>
@@ -402,6 +403,58 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_batch_tag(const int32_t *__
     batch_bytes(first, last, boff[h], in, n, ckpt, o + 1, o + 2);
 }
 
+// A lane per record of the scan over a batch's text, in place (acgpu_replace_batch_utf8): {start, end} in units of that text ->
+// bytes relative to the SPAN's first byte, not the haystack's -- plan and emit work on the span, which has no separators.  The
+// record's haystack h is also the number of separators in front of it, so its units in the buffer read as one text are
+// start - h .. end - 1 - h: with checkpoints they go through batch_bytes, and in an all-ASCII batch (ckpt == nullptr), where a
+// unit of the buffer is its byte, the shift is all there is to do -- but it is still to do.
+__global__ __launch_bounds__(kU8Threads) void k_utf8_batch_map(int32_t *__restrict__ recs, uint64_t cnt, uint32_t cols, const uint32_t *__restrict__ cat_off,
+                                                               uint32_t n_hay, const uint8_t *__restrict__ in, uint32_t n, uint32_t n_units,
+                                                               const uint32_t *__restrict__ ckpt) {
+    const uint64_t i = (uint64_t)blockIdx.x * kU8Threads + threadIdx.x;
+    if (i >= cnt) return;
+    int32_t *r = recs + i * cols;
+    const uint32_t start = (uint32_t)r[0], end = (uint32_t)r[1];
+    const uint32_t h = haystack_of(cat_off, n_hay, start);
+    const uint32_t first = start - h, last = end - 1u - h; // (no match holds a separator: both are units of haystack h)
+    if (first > last || last >= n_units) return;           // (never: the scan's records lie inside the text)
+    if (!ckpt) {
+        r[0] = (int32_t)first;
+        r[1] = (int32_t)(last + 1u);
+        return;
+    }
+    batch_bytes(first, last, 0u, in, n, ckpt, r, r + 1);
+}
+
+// One lane: unit x of a batch's text -> *out, a byte of the span (a piece's boundary, see replace_limit in acgpu_replace.hip).
+// With h the haystack that holds x (cat_off[h] <= x < cat_off[h + 1]):
+//  * x is haystack h's separator, the last unit before cat_off[h + 1]: the byte where haystack h + 1 begins, boff[h + 1] -- for
+//    the batch's last separator that is n, the span's end.  (The checkpoint table has no entry for a separator: x - h would be
+//    the first unit of the next haystack, or n_units.)  A unit at or behind the text's end maps to n as well;
+//  * any other unit: the first byte of the code point that holds unit x - h of the buffer read as one text -- between the two
+//    units of a surrogate pair that rounds down, as k_utf8_pos does; all-ASCII (ckpt == nullptr): the byte x - h itself.
+__global__ void k_utf8_batch_pos(uint32_t x, const uint32_t *__restrict__ cat_off, uint32_t n_hay, const uint32_t *__restrict__ boff,
+                                 const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ ckpt, int64_t *__restrict__ out) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    if (x >= cat_off[n_hay]) {
+        *out = (int64_t)n;
+        return;
+    }
+    const uint32_t h = haystack_of(cat_off, n_hay, x);
+    if (x + 1u == cat_off[h + 1u]) {
+        *out = (int64_t)boff[h + 1u];
+        return;
+    }
+    const uint32_t u = x - h;
+    if (!ckpt) {
+        *out = (int64_t)u;
+        return;
+    }
+    SeqPos s = seek(ckpt, u);
+    (void)advance(in, n, s, u);
+    *out = (int64_t)s.p;
+}
+
 // A lane per haystack, behind the last piece of a summary call: the first record of every entry that has one, from units
 // relative to its haystack to bytes relative to it.  cat_off given: entry i is haystack i of a batch's text (its first unit
 // without separators is cat_off[i] - i, its first byte boff[i]); not given: the entries' one text is `in` itself.
@@ -433,6 +486,22 @@ int utf8_map_records(const Utf8Text &text, int32_t *d_recs, uint64_t cnt, uint32
 int utf8_map_position(const Utf8Text &text, uint64_t unit, int64_t *d_out, hipStream_t stream) {
     if (!text.d_ckpt || unit >= text.n_units) return ACGPU_E_INVALID; // (a checkpoint is written for the text's units only)
     hipLaunchKernelGGL(k_utf8_pos, dim3(1), dim3(1), 0, stream, (uint32_t)unit, text.d_bytes, (uint32_t)text.n_bytes, text.d_ckpt, d_out);
+    HIP_TRY(hipGetLastError());
+    return ACGPU_OK;
+}
+
+int utf8_batch_map_records(const Utf8Batch &b, int32_t *d_recs, uint64_t cnt, uint32_t cols, hipStream_t stream) {
+    if (!cnt) return ACGPU_OK;
+    hipLaunchKernelGGL(k_utf8_batch_map, dim3((unsigned)((cnt + kU8Threads - 1) / kU8Threads)), dim3(kU8Threads), 0, stream, d_recs, cnt, cols,
+                       b.d_cat_off, b.n_haystacks, b.text.d_bytes, (uint32_t)b.text.n_bytes, (uint32_t)b.text.n_units, b.text.d_ckpt);
+    HIP_TRY(hipGetLastError());
+    return ACGPU_OK;
+}
+
+int utf8_batch_map_position(const Utf8Batch &b, uint64_t unit, int64_t *d_out, hipStream_t stream) {
+    if (!b.d_cat_off || !b.n_haystacks || unit >= (1ull << 32)) return ACGPU_E_INVALID;
+    hipLaunchKernelGGL(k_utf8_batch_pos, dim3(1), dim3(1), 0, stream, (uint32_t)unit, b.d_cat_off, b.n_haystacks, b.d_boff, b.text.d_bytes,
+                       (uint32_t)b.text.n_bytes, b.text.d_ckpt, d_out);
     HIP_TRY(hipGetLastError());
     return ACGPU_OK;
 }
@@ -490,7 +559,7 @@ int stage_utf8_batch(DeviceState &d, const HostTables &t, const uint8_t *bytes, 
     if ((rc = d.utf8_in.ensure((size_t)n + 64))) return rc;
     if ((rc = d.utf8_aux.ensure(boff_off + off_bytes))) return rc;
     if ((rc = d.batch_off.ensure(off_bytes + 16))) return rc;
-    std::vector<uint32_t> h_boff;
+    std::vector<uint32_t> &h_boff = out->h_boff;
     try {
         h_boff.resize((size_t)n_hay + 1);
     } catch (...) {

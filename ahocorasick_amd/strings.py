@@ -384,6 +384,33 @@ class Automaton:
             N.check(rc, "acgpu_replace_utf8")
             return out[:n_out.value], {f: int(getattr(st, f)) for f, _ in N.ReplaceStats._fields_}
 
+    def replace_batch_utf8(self, data, replacements, cap=None, stats=None, offsets=None):
+        """acgpu_replace_batch_utf8: many short UTF-8 haystacks rewritten in one call -> (uint8 array, out_offsets, stats dict):
+        the result of haystack i is out[out_offsets[i]:out_offsets[i + 1]], byte for byte what replace_utf8 returns for it.
+        data and offsets as for match_batch_utf8, `replacements` as for replace_utf8, the one retry of replace_batch.  An
+        ill-formed haystack raises Utf8Error (.haystack, and .start inside it); stats: an N.Utf8BatchStats to fill in, if wanted."""
+        buf, off = _pack_utf8(data, offsets)
+        r_bytes, r_off, n_repl = self._replacements_utf8(replacements)
+        n = int(off[-1] - off[0])
+        if cap is None:
+            cap = n + n // 4 + 64
+        buf_in = buf if buf.size else np.zeros(1, np.uint8)
+        st = N.ReplaceStats()
+        ust = stats if stats is not None else N.Utf8BatchStats()
+        out_off = np.zeros(len(off), dtype=np.uint64)
+        for attempt in (0, 1):
+            out = np.empty(max(cap, 1), dtype=np.uint8)
+            n_out = ctypes.c_uint64(0)
+            rc = N.lib().acgpu_replace_batch_utf8(self._h, _vp(buf_in), _vp(off), len(off) - 1, _vp(r_bytes), _vp(r_off), n_repl, _vp(out), cap,
+                                                  _vp(out_off), ctypes.byref(n_out), ctypes.byref(st), ctypes.byref(ust))
+            if rc == N.E_OVERFLOW and attempt == 0:
+                cap = int(n_out.value)
+                continue
+            if rc == N.E_ENCODING:
+                raise Utf8Error(ust.first_bad, haystack=ust.bad_haystack)
+            N.check(rc, "acgpu_replace_batch_utf8")
+            return out[:n_out.value], out_off, {f: int(getattr(st, f)) for f, _ in N.ReplaceStats._fields_}
+
     def replace_batch(self, haystacks, replacements, cap=None):
         """acgpu_replace_batch_u16: many short haystacks (str or uint16 arrays) rewritten in one call -> (units, out_offsets,
         stats dict): the result of haystack i is units[out_offsets[i]:out_offsets[i + 1]].  `replacements` as for replace_host,
@@ -713,6 +740,12 @@ def _split_batch(units, out_off):
     return [_to_str(units[o[i]:o[i + 1]]) for i in range(len(o) - 1)]
 
 
+def _split_batch_utf8(out, out_off):
+    """the result of Automaton.replace_batch_utf8 -> one bytes object per haystack"""
+    o = out_off.tolist()
+    return [out[o[i]:o[i + 1]].tobytes() for i in range(len(o) - 1)]
+
+
 class _BatchDecisions:
     """Not in the reference: what a listener that decides about each text of a list would hold, from ONE device call that returns
     24 bytes per haystack and no record (Automaton.summary_batch).  An empty list gives empty results without a device."""
@@ -812,6 +845,13 @@ class StringSet(_BatchDecisions):
         if data is None:
             raise TypeError("haystack is None")
         return self._auto.replace_utf8(data, replacement if isinstance(replacement, (bytes, bytearray)) else str(replacement))[0].tobytes()
+
+    def replace_batch_utf8(self, datas, replacement, offsets=None):
+        """Not in the reference: [replace_utf8(d, replacement) for d in datas] in ONE device call -> a list of bytes, one per
+        haystack.  datas: a sequence of bytes-like objects, or with offsets= ONE buffer used in place -- a log file line by line:
+        replace_batch_utf8(buf, "***", offsets=utf8_line_offsets(buf)).  Utf8Error (.haystack, .start) if one is ill-formed."""
+        r = replacement if isinstance(replacement, (bytes, bytearray)) else str(replacement)
+        return _split_batch_utf8(*self._auto.replace_batch_utf8(datas if offsets is not None else _checked(datas), r, offsets=offsets)[:2])
 
     def find_all(self, haystack):
         """Convenience (not in the reference): the (n,2) int32 array of (start, end) records."""
@@ -937,6 +977,13 @@ class StringMap(_BatchDecisions):
         if not isinstance(replacements, (bytes, bytearray)):
             replacements = self._replacements_for(replacements)
         return self._auto.replace_utf8(data, replacements)[0].tobytes()
+
+    def replace_batch_utf8(self, datas, replacements=None, offsets=None):
+        """Not in the reference: [replace_utf8(d, replacements) for d in datas] in ONE device call -> a list of bytes (see
+        StringSet.replace_batch_utf8); `replacements` under the rules of replace_utf8()."""
+        if not isinstance(replacements, (bytes, bytearray)):
+            replacements = self._replacements_for(replacements)
+        return _split_batch_utf8(*self._auto.replace_batch_utf8(datas if offsets is not None else _checked(datas), replacements, offsets=offsets)[:2])
 
     def _replacements_for(self, replacements):
         if replacements is None:

@@ -688,8 +688,8 @@ int acgpu_summary_batch_u16(const acgpu_automaton *a, const uint16_t *units, con
  * The call is ONE shard through the general path: neither the chunk-pipelined form acgpu_match_u16 takes from 2^25 units on
  * (a long text is copied whole before the scan begins, nothing overlaps), nor its one-launch form for texts of up to 4096 units
  * (a short text pays the fixed cost of five launches, two copies and two waits, several times that form's latency: batch short
- * texts with acgpu_match_batch_utf8 / acgpu_summary_batch_utf8 below).  Not built: count, batch replace, cursor, stream,
- * device-resident and multi-device forms for UTF-8 (replace: acgpu_replace_utf8 below); lossy decoding (U+FFFD); CESU-8 / WTF-8;
+ * texts with acgpu_match_batch_utf8 / acgpu_summary_batch_utf8 below).  Not built: count, cursor, stream,
+ * device-resident and multi-device forms for UTF-8 (replace: acgpu_replace_utf8 and acgpu_replace_batch_utf8 below); lossy decoding (U+FFFD); CESU-8 / WTF-8;
  * the Java facade (its strings are UTF-16).  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
  */
 typedef struct acgpu_utf8_stats {
@@ -731,8 +731,8 @@ int acgpu_match_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_
  * withholds more).  From there on everything counts bytes: the plan runs unchanged over byte records and a byte table, and the
  * byte form of the emit kernel writes 16 output bytes per lane from the caller's bytes on the device and the table, through
  * the two slabs of acgpu_replace_u16 ("replace_slab_units" counts bytes here).
- * Not built: batch (acgpu_replace_batch_utf8), device-resident, multi-device and stream forms; validating the replacements; the
- * Java facade.
+ * Many short texts in one call: acgpu_replace_batch_utf8 below.  Not built: device-resident, multi-device and stream forms;
+ * validating the replacements; the Java facade.
  * ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
  */
 int acgpu_replace_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, const uint8_t *repl_bytes,
@@ -771,7 +771,7 @@ int acgpu_replace_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t 
  * (k_summary_utf8_bytes, a lane per haystack, the summaries' first records).  An all-ASCII batch writes no checkpoints and maps
  * nothing.  Where acgpu_match_batch_u16 goes haystack by haystack (no free separator unit, a word matcher over a table that is
  * not fold-consistent) these do too, after the same validation of the whole batch: one acgpu_match_utf8-style pass per haystack.
- * Not built: acgpu_replace_batch_utf8, acgpu_count_utf8; device-resident, multi-device, stream and cursor forms; the one-launch
+ * Batch replace: acgpu_replace_batch_utf8 below.  Not built: acgpu_count_utf8; device-resident, multi-device, stream and cursor forms; the one-launch
  * form for tiny batches; the Java facade.  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
  */
 typedef struct acgpu_utf8_batch_stats {
@@ -785,6 +785,50 @@ int acgpu_match_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, const
 int acgpu_summary_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
                              acgpu_batch_summary *out /* n_haystacks, host */, acgpu_summary_stats *st /* may be NULL */,
                              acgpu_utf8_batch_stats *stats /* may be NULL */);
+
+/*
+ * Many short UTF-8 texts rewritten in ONE call: acgpu_replace_utf8 for a batch, the conjunction of acgpu_match_batch_utf8 and
+ * acgpu_replace_batch_u16.  Haystack i is bytes[offsets[i] .. offsets[i+1]) as for acgpu_match_batch_utf8 (contiguous in the
+ * caller's buffer, empty ones allowed anywhere), and out[out_offsets[i] .. out_offsets[i+1]) is byte for byte what
+ * acgpu_replace_utf8 returns for haystack i alone.  The results lie back to back; out_offsets has n_haystacks + 1 entries,
+ * out_offsets[0] == 0 and *n_out == out_offsets[n_haystacks].
+ *  repl_bytes / repl_off / n_repl, cap, *n_out, st : in BYTES, as for acgpu_replace_utf8; the replacements are not validated.
+ *              st->n_records is the sum over the haystacks, st->units_out == *n_out.
+ *  refusals  : before any device is touched.  The replacement table is checked first (ACGPU_E_INVALID; ACGPU_E_UNSUPPORTED for
+ *              ACGPU_MODE_ALL), then ACGPU_E_UNSUPPORTED for a dictionary with an unpaired surrogate (see acgpu_replace_utf8), then
+ *              ACGPU_E_INVALID for descending offsets, a byte to read and no `bytes`, and
+ *              offsets[n_haystacks] - offsets[0] + n_haystacks >= 2^31.  NULL a, offsets, n_out or out_offsets and cap without out
+ *              are ACGPU_E_INVALID before all of these.  After such a refusal out and out_offsets are untouched.
+ *  no device : n_haystacks == 0, or every haystack empty: ACGPU_OK, *n_out = 0, every entry of out_offsets 0, *ust = {0, -1, 0, 1}.
+ *  VALIDATION: strict and PER HAYSTACK, exactly as in acgpu_match_batch_utf8 -- a sequence that a haystack boundary cuts is
+ *              ill-formed.  ACGPU_E_ENCODING with ust->bad_haystack / ust->first_bad; *n_out = 0, out and out_offsets[1..] are
+ *              untouched, the stream is idle and the pool usable.
+ *  overflow  : a result of more than cap bytes gives ACGPU_E_OVERFLOW; *n_out and EVERY entry of out_offsets are exact all the
+ *              same (the plan runs to the end), and nothing at or beyond out[cap] has been written.  out == NULL with cap == 0
+ *              only counts.
+ * Works on the NULL stream, under the pool's lock (STREAM RULE above: tickets in flight on the pool give ACGPU_E_INVALID).
+ * How it works: the batch is staged as acgpu_match_batch_utf8 stages it -- validated with the cuts, transcoded with a separator
+ * unit behind every haystack -- and that shard goes through the pieces of acgpu_replace_utf8.  The caller's bytes have NO
+ * separator, so, unlike acgpu_replace_batch_u16, nothing is merged and nothing deleted; three mappings take the scan's
+ * coordinates to bytes of the span instead.  (1) Behind every piece k_utf8_batch_map rewrites its records in the reservoir: a
+ * record of haystack h stands h separators behind its units in the checkpoint table, so units start - h and end - 1 - h go
+ * through the checkpoints -- in an all-ASCII batch, which has none, the shift alone remains and is still applied.  (2) One lane,
+ * k_utf8_batch_pos, maps the piece's boundary: a separator (the batch's last one included) to the byte where the next haystack
+ * begins, any other unit to the first byte of the code point that holds it, rounded down.  (3) Behind the plan
+ * k_replace_span_offsets, a lane per haystack boundary that the piece emits, computes where that haystack's result begins from
+ * the plan's position of the last record in front of it; every boundary is written by exactly one piece, and the offsets leave
+ * the device once, at the end.  Plan and the byte form of the emit run as they are.
+ * Haystack by haystack inside the library instead, same results, where acgpu_match_batch_utf8 falls back (no free separator unit,
+ * a word matcher over a table that is not fold-consistent): the whole batch is validated first, so what is refused does not
+ * depend on the route, then every haystack takes acgpu_replace_utf8's route with cap, the output position and the stats carried
+ * across and the table uploaded once.
+ * Not built: device-resident, multi-device, stream and cursor forms; validating the replacements; lossy decoding (U+FFFD); a
+ * one-launch form for tiny batches; the Java facade.  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
+ */
+int acgpu_replace_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
+                             const uint8_t *repl_bytes, const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap,
+                             uint64_t *out_offsets /* n_haystacks + 1 */, uint64_t *n_out,
+                             acgpu_replace_stats *st /* may be NULL */, acgpu_utf8_batch_stats *ust /* may be NULL */);
 
 /*
  * Synthetic haystack generator of the benchmark: unit i of the stream is

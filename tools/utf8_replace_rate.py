@@ -6,17 +6,23 @@
   today        : what the same caller does without it: data.decode() -> utf16() -> Automaton.replace_host -> str -> encode().
 All on the mixed text of tools/utf8_rate.py (restated here) and its automaton (WholeWordMatch over the README word list), one
 replacement for every keyword, capacity known (no overflow retry timed), the results compared.
-usage: utf8_replace_rate.py [--log2 24] [--repl "[redacted]"]"""
+--batch N: N lines of that text, about 12 words a line, rewritten line by line through three routes instead --
+  batch    : acgpu_replace_batch_utf8 on the one buffer and its line offsets (offsets=): one device call;
+  per line : one acgpu_replace_utf8 call per line (on the first --per-line lines; the figure is scaled to N);
+  decode   : every line decoded on the host, Automaton.replace_batch on the str lines, every result encoded again.
+usage: utf8_replace_rate.py [--log2 24] [--repl "[redacted]"] [--batch 20000 [--per-line 2000]]"""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from ahocorasick_amd import _native as N, synth
-from ahocorasick_amd.strings import Automaton, _to_str, utf16
+from ahocorasick_amd.strings import Automaton, _split_batch, _to_str, utf8_line_offsets, utf16
 from ahocorasick_amd.unicode_tables import default_word_chars
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--log2", type=int, default=24, help="bytes of the text, about")
 ap.add_argument("--repl", default="[redacted]")
+ap.add_argument("--batch", type=int, default=0, help="lines of a batch; 0: the one-text measurement")
+ap.add_argument("--per-line", type=int, default=2000)
 args = ap.parse_args()
 
 EXTRA = ["Zürich", "naïve", "straße", "λόγος", "Москва", "東京", "데이터", "😀", "𝒜𝓃𝓈"]
@@ -38,6 +44,52 @@ def timed(fn, reps=5):
         ts.append(time.perf_counter() - t0)
     return float(np.median(ts)) * 1e3, out
 
+
+WORDS_PER_LINE = 12
+
+
+def make_lines(n_lines):
+    words = synth.readme_dictionary()
+    toks = _to_str(synth.readme_text(2006, n_lines * WORDS_PER_LINE * 8, words)).split(" ")
+    toks = [t if i % 6 else t + " " + EXTRA[(i // 6) % len(EXTRA)] for i, t in enumerate(toks)]
+    lines = [" ".join(toks[i * WORDS_PER_LINE:(i + 1) * WORDS_PER_LINE]) for i in range(n_lines)]
+    return words, ("\n".join(lines) + "\n").encode("utf-8")
+
+
+def batch_routes():
+    words, buf = make_lines(args.batch)
+    a = Automaton(N.MODE_WHOLEWORD, words + EXTRA[:7], True, word_chars=default_word_chars())
+    off = utf8_line_offsets(buf)
+    n = len(off) - 1
+    ust = N.Utf8BatchStats()
+    out, out_off, st = a.replace_batch_utf8(buf, args.repl, offsets=off, stats=ust)
+    cap_out = out.size + 64
+    print("%d lines, %d bytes -> %d units, ascii=%d, %d records replaced by %r, %d bytes out, %d pieces" % (
+        n, len(buf), ust.n_units, ust.ascii, st["n_records"], args.repl, out.size, st["pieces"]))
+    ms_batch, (got, got_off, _) = timed(lambda: a.replace_batch_utf8(buf, args.repl, cap=cap_out, offsets=off))
+    o = off.tolist()
+    ms_split, raw_lines = timed(lambda: [buf[o[i]:o[i + 1]] for i in range(n)])
+    ms_dec, lines = timed(lambda: [ln.decode("utf-8") for ln in raw_lines])
+    ms_u16, (units, u_off, _) = timed(lambda: a.replace_batch(lines, args.repl, cap=cap_out))
+    ms_enc, want = timed(lambda: [s.encode("utf-8") for s in _split_batch(units, u_off)])
+    go = got_off.tolist()
+    assert [got[go[i]:go[i + 1]].tobytes() for i in range(n)] == want, "the routes differ"
+    decode = ms_split + ms_dec + ms_u16 + ms_enc
+    k = min(n, args.per_line)
+    t0 = time.perf_counter()
+    per = [a.replace_utf8(ln, args.repl)[0].tobytes() for ln in raw_lines[:k]]
+    ms_line = (time.perf_counter() - t0) * 1e3
+    assert per == want[:k], "the per-line route differs"
+    print("batch    : %8.3f ms = %6.3f us a line = %6.2f GB/s of input bytes (one call, no host step)" % (ms_batch, ms_batch * 1e3 / n, len(buf) / ms_batch / 1e6))
+    print("per line : %8.3f ms for %d lines = %6.3f us a line, %8.3f ms scaled to %d lines" % (ms_line, k, ms_line * 1e3 / k, ms_line * n / k, n))
+    print("decode   : %8.3f ms (host: slice %.3f + decode %.3f + str, encode %.3f; replace_batch, its UTF-16 packing included, %.3f)" % (
+        decode, ms_split, ms_dec, ms_enc, ms_u16))
+    print("ratios   : per line / batch = %.2f, decode / batch = %.2f" % (ms_line * n / k / ms_batch, decode / ms_batch), flush=True)
+
+
+if args.batch:
+    batch_routes()
+    sys.exit(0)
 
 words, data = mixed_text(1 << args.log2)
 a = Automaton(N.MODE_WHOLEWORD, words + EXTRA[:7], True, word_chars=default_word_chars())
