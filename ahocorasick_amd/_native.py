@@ -99,6 +99,10 @@ class Utf8BatchStats(ctypes.Structure):  # acgpu_utf8_batch_stats
     _fields_ = [("n_units", ctypes.c_uint64), ("first_bad", ctypes.c_int64), ("bad_haystack", ctypes.c_uint32), ("ascii", ctypes.c_uint32)]
 
 
+class Utf8StreamStats(ctypes.Structure):  # acgpu_utf8_stream_stats
+    _fields_ = [("n_units", ctypes.c_uint64), ("first_bad", ctypes.c_int64), ("ascii", ctypes.c_uint32), ("held", ctypes.c_uint32)]
+
+
 def _summary_dtype():
     import numpy as np
     return np.dtype({"names": ["n_matches", "start", "end", "keyword_id", "reserved"],
@@ -120,7 +124,7 @@ SYMBOLS = ["acgpu_build", "acgpu_free", "acgpu_get_info", "acgpu_match_u16", "ac
            "acgpu_cursor_get_stats", "acgpu_cursor_close", "acgpu_count_u16", "acgpu_count_device",
            "acgpu_replace_u16", "acgpu_replace_device", "acgpu_replace_batch_u16", "acgpu_summary_batch_u16",
            "acgpu_match_utf8", "acgpu_replace_utf8", "acgpu_match_batch_utf8", "acgpu_summary_batch_utf8",
-           "acgpu_replace_batch_utf8"]
+           "acgpu_replace_batch_utf8", "acgpu_stream_feed_utf8"]
 
 _lib = None
 
@@ -180,6 +184,9 @@ def lib():
         L.acgpu_stream_open.argtypes = [vp, ctypes.POINTER(vp)]
         L.acgpu_stream_feed.restype = ci
         L.acgpu_stream_feed.argtypes = [vp, vp, u64, ci, ci, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(i64)]
+        L.acgpu_stream_feed_utf8.restype = ci
+        L.acgpu_stream_feed_utf8.argtypes = [vp, vp, u64, ci, ci, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(i64),
+                                             ctypes.POINTER(Utf8StreamStats)]
         L.acgpu_stream_close.restype = None
         L.acgpu_stream_close.argtypes = [vp]
         L.acgpu_stream_set_pipelined.restype = ci

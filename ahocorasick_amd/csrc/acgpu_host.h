@@ -387,13 +387,20 @@ struct Utf8Text {
     const uint32_t *d_ckpt = nullptr; // checkpoint table, one word per 32 units: the byte offset of the sequence that holds unit 32 i, bit 31
                                       // set where that unit is its low surrogate; nullptr: an all-ASCII text, unit offsets are byte offsets
     uint64_t n_units = 0;             // UTF-16 units of the text
-    uint64_t n_bytes = 0;             // ... and its bytes
+    uint64_t n_bytes = 0;             // ... and its bytes (the open form: without the held prefix)
+    uint32_t tail = 0;                // the open form: bytes at the buffer's end that begin a sequence the next buffer completes, 0..3
     int64_t first_bad = -1;           // ACGPU_E_ENCODING: where a strict decoder stops
 };
 // bytes -> {device shard, checkpoint table, n_units} on `stream`, which it waits for once (the transcoder's 16-byte result sizes
 // the shard).  ACGPU_E_ENCODING: the text is ill-formed, out->first_bad says where, nothing was transcoded and the stream is
 // idle.  The caller holds d.mu; n_bytes < 2^31.
 int stage_utf8_text(DeviceState &d, const uint8_t *bytes, uint64_t n_bytes, hipStream_t stream, Utf8Text *out);
+// The same for a buffer that lies in two parts on the host, head | bytes (acgpu_stream_feed_utf8: the carried bytes and the
+// caller's chunk; n_head + n_rest < 2^31, not 0), each copied from where it is.  open: the text goes on behind the buffer -- a
+// sequence that the buffer's end cuts and that is well-formed so far is held back: out->tail bytes, and the shard, the
+// checkpoints, n_units and n_bytes are those of the bytes before them (k_utf8_open_count).
+int stage_utf8_parts(DeviceState &d, const uint8_t *head, uint64_t n_head, const uint8_t *bytes, uint64_t n_rest, bool open, hipStream_t stream,
+                     Utf8Text *out);
 // The mapping rule of acgpu_match_utf8 over cnt records of `cols` words on the device, in place (k_utf8_map), enqueued on
 // `stream`.  An all-ASCII text (no checkpoints) needs none: nothing is launched.
 int utf8_map_records(const Utf8Text &text, int32_t *d_recs, uint64_t cnt, uint32_t cols, hipStream_t stream);

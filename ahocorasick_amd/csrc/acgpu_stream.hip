@@ -10,6 +10,10 @@
 //    several threads made the launches of the scan slow): copy, transfer and scan of neighbouring chunks overlap, a feed
 //    costs the slowest of them instead of their sum.  The last feed (final != 0) returns the records
 //    of both the previous and its own chunk.  The concatenation over all feeds is the same in both forms.
+// acgpu_stream_feed_utf8 is the synchronous form for a text that arrives as UTF-8 bytes: the stream carries BYTES, whole code points
+// and behind them the prefix of a sequence that a chunk's end has cut; every feed transcodes [carried bytes | chunk] on the
+// device (stage_utf8_parts, open at the end unless the feed is the last), scans it by the same plan in units and maps the
+// records to bytes of that buffer.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -153,6 +157,13 @@ struct acgpu_stream {
     int64_t chain_entry = 0;     // the chain families: where the chain enters the next feed (global; piece_entry)
     bool finished = false;
     std::vector<uint16_t> buf;
+    // ---- a stream of UTF-8 bytes (acgpu_stream_feed_utf8): carry_pos, own_from and chain_entry stay in units ----
+    enum Fed : uint8_t { kFedNone, kFedUnits, kFedBytes };
+    Fed fed = kFedNone;          // what the first feed, of whatever length, made of the stream
+    std::vector<uint8_t> carry8; // the carried text's bytes, whole code points, then the held prefix
+    uint32_t held = 0;           // bytes at carry8's end that begin a sequence the next feed must complete, 0..3
+    uint64_t carry_units = 0;    // units that carry8 without the held prefix decodes to
+    uint64_t carry_byte = 0;     // global byte position of carry8[0]
     // ---- pipelined form ----
     bool pipelined = false, started = false;
     int device = -1;
@@ -465,6 +476,7 @@ void acgpu_stream_detach(acgpu_stream *s) { s->a = nullptr; }
 
 int acgpu_stream_set_pipelined(acgpu_stream *s, int on) {
     if (!s || s->started || s->carry_pos != 0 || !s->carry.empty() || s->own_from != 0) return ACGPU_E_INVALID; // before the first feed
+    if (s->fed == acgpu_stream::kFedBytes) return ACGPU_E_INVALID;                                              // (of bytes as well)
     s->pipelined = on != 0;
     return ACGPU_OK;
 }
@@ -494,6 +506,8 @@ int acgpu_stream_feed(acgpu_stream *s, const uint16_t *units, uint64_t n_units, 
     if (!s || !n_out || !base || (n_units && !units) || (cap && !out) || s->finished) return ACGPU_E_INVALID;
     if (record_kind != ACGPU_REC_SET && record_kind != ACGPU_REC_MAP) return ACGPU_E_INVALID;
     if (!s->a) return ACGPU_E_INVALID; // (its automaton has been freed)
+    if (s->fed == acgpu_stream::kFedBytes) return ACGPU_E_INVALID; // (a stream of bytes: acgpu_stream_feed_utf8)
+    s->fed = acgpu_stream::kFedUnits;
     if (s->pipelined) return feed_pipelined(s, units, n_units, final, record_kind, out, cap, n_out, base);
     acgpu_automaton *a = s->a;
     const ShardRule rule = shard_rule(a->t, record_kind, /*readable=*/true);
@@ -534,6 +548,104 @@ int acgpu_stream_feed(acgpu_stream *s, const uint16_t *units, uint64_t n_units, 
     s->chain_entry = (int64_t)s->carry_pos + chain_exit;
     s->carry.assign(s->buf.begin() + (ptrdiff_t)keep_from, s->buf.end());
     s->carry_pos += keep_from;
+    s->finished = final != 0;
+    return ACGPU_OK;
+}
+
+int acgpu_stream_feed_utf8(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, int record_kind, void *out, uint64_t cap,
+                           uint64_t *n_out, int64_t *base, acgpu_utf8_stream_stats *stats) {
+    static_assert(sizeof(acgpu_utf8_stream_stats) == 24, "the layout include/acgpu.h promises");
+    if (!s || !n_out || !base || (n_bytes && !bytes) || (cap && !out) || s->finished) return ACGPU_E_INVALID;
+    if (record_kind != ACGPU_REC_SET && record_kind != ACGPU_REC_MAP) return ACGPU_E_INVALID;
+    if (!s->a) return ACGPU_E_INVALID; // (its automaton has been freed)
+    if (s->pipelined) return ACGPU_E_UNSUPPORTED;
+    if (s->fed == acgpu_stream::kFedUnits) return ACGPU_E_INVALID; // (a stream of units: acgpu_stream_feed)
+    const uint64_t n_c8 = s->carry8.size(), total_bytes = n_c8 + n_bytes;
+    if (n_bytes >= (1ull << 31) || total_bytes >= (1ull << 31)) return ACGPU_E_INVALID;
+    s->fed = acgpu_stream::kFedBytes;
+    *n_out = 0;
+    *base = (int64_t)s->carry_byte;
+    acgpu_utf8_stream_stats st{};
+    st.first_bad = -1;
+    st.held = s->held;
+    st.ascii = 1;
+    for (uint8_t b : s->carry8) st.ascii &= b < 0x80u ? 1u : 0u;
+    if (stats) *stats = st;
+    if (n_bytes == 0 && !final) return ACGPU_OK; // (nothing new to decode or to decide: no device needed)
+    if (total_bytes == 0) {                      // (the end of a stream that holds nothing: neither)
+        s->finished = true;
+        return ACGPU_OK;
+    }
+    acgpu_automaton *a = s->a;
+    PoolCall call(a);
+    if (call.rc) return call.rc;
+    DeviceState &d = *call.d;
+    int rc;
+    if ((rc = call.idle())) return rc; // (the call stream, waited for: see the stream rule)
+    const hipStream_t stream = d.call_stream;
+    Utf8Text text;
+    rc = stage_utf8_parts(d, s->carry8.data(), n_c8, bytes, n_bytes, /*open=*/!final, stream, &text);
+    if (rc == ACGPU_E_ENCODING) { // (the stream is idle: the pool is as usable as before the call)
+        st.first_bad = (int64_t)s->carry_byte + text.first_bad; // (in an earlier feed's bytes: the lead of the held prefix)
+        st.ascii = 0;
+        st.held = 0;
+        if (stats) *stats = st;
+        s->finished = true;
+        return rc;
+    }
+    if (rc) return call.fail(rc);
+    if (text.n_units < s->carry_units) return call.fail(ACGPU_E_HIP); // (never: the carried code points decode as they did)
+    st.n_units = text.n_units - s->carry_units;
+    st.ascii = text.n_units == total_bytes;
+    st.held = text.tail;
+    if (stats) *stats = st;
+    const ShardRule rule = shard_rule(a->t, record_kind, /*readable=*/true);
+    const FeedPlan p = plan_feed(rule, s->carry_units, text.n_units - s->carry_units, s->own_from, s->carry_pos, final != 0);
+    const int64_t entry = piece_entry(rule, s->chain_entry, (int64_t)s->carry_pos, p.own_begin);
+    int64_t chain_exit = piece_exit(rule, entry, p.own_end, nullptr, 0);
+    if (p.own_end > p.own_begin) {
+        if ((rc = d.stage_out.ensure(cap * (uint64_t)record_kind + 16))) return call.fail(rc);
+        acgpu_shard &sh = text.shard; // (all the buffer's units: then the owned range, the ends and the chain)
+        sh.own_begin = p.own_begin;
+        sh.own_end = p.own_end;
+        sh.text_begin = s->carry_pos == 0 ? 1 : 0;
+        sh.text_end = final ? 1 : 0;
+        sh.chain_entry = entry;
+        rc = match_shard(a, d, &sh, record_kind, d.stage_out.p, cap, n_out, stream, nullptr, /*readable=*/true);
+        if (rc != ACGPU_OK) return rc; // ACGPU_E_OVERFLOW: nothing consumed, *n_out = capacity to retry with
+        if (*n_out) {
+            if ((rc = utf8_map_records(text, reinterpret_cast<int32_t *>(d.stage_out.p), *n_out, (uint32_t)record_kind / 4, stream))) return call.fail(rc);
+            if (hipMemcpyAsync(out, d.stage_out.p, *n_out * (uint64_t)record_kind, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                hipStreamSynchronize(stream) != hipSuccess)
+                return call.fail(ACGPU_E_HIP);
+        }
+        chain_exit = piece_exit(rule, entry, p.own_end, &sh, *n_out);
+    }
+    // The byte to cut the carry at, on the host: back from the end of the decoded bytes over the leads -- every byte that is no
+    // continuation byte begins a code point of one unit, of two from F0 up -- until at least total - keep_from units are
+    // covered.  That is a code-point boundary; where keep_from names a low surrogate, one unit more is carried than the plan asks.
+    auto at = [&](uint64_t i) { return i < n_c8 ? s->carry8[i] : bytes[i - n_c8]; };
+    const uint64_t need = p.total - p.keep_from;
+    uint64_t cut = text.n_bytes, kept = 0;
+    while (kept < need && cut > 0) {
+        const uint8_t b = at(--cut);
+        if ((b & 0xc0u) != 0x80u) kept += b >= 0xf0u ? 2u : 1u;
+    }
+    std::vector<uint8_t> next;
+    try {
+        next.resize(total_bytes - cut);
+    } catch (...) {
+        return ACGPU_E_NOMEM;
+    }
+    for (uint64_t i = cut; i < total_bytes; ++i) next[i - cut] = at(i);
+    // commit
+    s->own_from = s->carry_pos + p.own_end;
+    s->chain_entry = (int64_t)s->carry_pos + chain_exit;
+    s->carry8.swap(next);
+    s->held = text.tail;
+    s->carry_pos += p.total - kept;
+    s->carry_units = kept;
+    s->carry_byte += cut;
     s->finished = final != 0;
     return ACGPU_OK;
 }

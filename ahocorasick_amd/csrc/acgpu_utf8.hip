@@ -18,6 +18,8 @@
 // stay those of the buffer read as one text; k_utf8_batch_tag is k_batch_tag and k_utf8_map in one, k_summary_utf8_bytes maps
 // the summaries' first records.  For acgpu_replace_batch_utf8 (acgpu_replace.hip) k_utf8_batch_map rewrites a piece's records to
 // bytes of the SPAN (utf8_batch_map_records) and k_utf8_batch_pos maps a piece's boundary (utf8_batch_map_position).
+// acgpu_stream_feed_utf8 (acgpu_stream.hip) stages [carried bytes | chunk] through stage_utf8_parts; unless the feed is the last,
+// k_utf8_open_count validates with lane_view's OPEN form: a sequence that the buffer's end cuts is held back, not refused.
 // What a lane knows about its 16 bytes is eleven bit masks over a window of 24 bytes (the 4 before, its own, the 4 behind), built
 // by one function that both passes over the text share, so they cannot disagree about a count.
 #include <hip/hip_runtime.h>
@@ -51,6 +53,7 @@ struct LaneView {
     uint32_t bad;    // own bytes at which a strict decoder stops: leads of ill-formed sequences, unclaimed continuation bytes
     uint32_t cut;    // the batch form: bytes of the window's bits 4..23 that begin a haystack (or are the buffer's end)
     uint32_t next;   // the batch form: the first boundary j with boff[j] >= o -- until the lane meets it, its bytes are haystack j - 1's
+    uint32_t tail;   // the open form: the own byte (at most one) that begins a sequence which the buffer's end cuts, so far well-formed
     __device__ __forceinline__ uint32_t byte(int k) const { return (w[k >> 2] >> (8 * (k & 3))) & 0xffu; }
     __device__ __forceinline__ uint32_t units() const { return __popc(lead) + __popc(four); }
 };
@@ -73,9 +76,21 @@ struct LaneView {
 // h's, decoded, and did not claim it -- as in one text.  So p = e.  The cuts come from the offsets themselves: a search for the
 // first boundary at or behind the lane's first byte, then a walk over the boundaries of the window -- haystacks that are empty
 // are several boundaries at one byte, one bit.
-template <bool BATCH>
+//
+// OPEN: the buffer is a text that GOES ON behind byte n (a feed of acgpu_stream_feed_utf8 that is not the last).  A lead in the
+// last three bytes whose sequence reaches behind the buffer's end is judged by the bytes that are there alone -- the lead byte
+// itself, the second byte against the range its lead allows, a third byte as a continuation byte: what
+// codecs.getincrementaldecoder("utf-8") holds back.  If they pass, the lead is neither bad nor counted (lead, four): it is the
+// `tail`, and the units are those of the n - tail bytes before it, which end on a sequence's end and are well-formed as a text
+// of their own.  Its continuation bytes are claimed as ever.  If they do not pass, the lead is bad NOW, as for a decoder that no
+// later byte can satisfy.  One prefix is held although it is none: ED A0..BF as the last two bytes (bad_open).
+// At most one tail exists in a buffer: let p < q be two leads of the last three bytes that both reach behind the end.  Then q
+// is one of the bytes p + 1 .. n - 1 that p's sequence needs and that are there, and q is a lead, no continuation byte: p does
+// not pass.  So of such leads only the last can pass, and the one lane that owns it stores n - position without a race.
+template <bool BATCH, bool OPEN = false>
 __device__ __forceinline__ LaneView lane_view(const uint8_t *__restrict__ in, uint32_t n, uint32_t o, const uint32_t *__restrict__ boff = nullptr,
                                               uint32_t n_hay = 0) {
+    static_assert(!(BATCH && OPEN), "a batch's haystacks end where they end");
     LaneView v;
     uint4 own = make_uint4(0, 0, 0, 0);
     if (o < n) own = *reinterpret_cast<const uint4 *>(in + o);
@@ -142,6 +157,21 @@ __device__ __forceinline__ LaneView lane_view(const uint8_t *__restrict__ in, ui
     v.lead = ~cont & own_bits;
     v.four = l4 & own_bits;
     v.bad = (bad_lead | (cont & (~claimed | cut))) & own_bits;
+    v.tail = 0;
+    if constexpr (OPEN) {
+        // `behind`: the window's bytes at and behind the buffer's end -- they are not there YET, so whatever a lead asks of them holds
+        // (what a lead forbids, ED A0.. and F4 90.., is asked of bytes that are there: the plain masks, zero behind the end)
+        const uint32_t behind = k_end >= 24 ? 0u : ~((1u << k_end) - 1u);
+        const uint32_t cont_o = cont | behind, gea0_o = gea0 | behind, ge90_o = ge90 | behind;
+        // (ED A0..BF as the buffer's LAST two bytes is held all the same, as CPython's incremental decoder holds it -- "a truncated
+        // surrogate" -- although no third byte can complete it: the next buffer, or the end, reports it, at the same lead)
+        const uint32_t bad_open = inv | (l2 & ~(cont_o >> 1)) | (l3 & ~(cont_o >> 2)) | (l4 & ~(cont_o >> 3)) | (e0 & ~(gea0_o >> 1)) |
+                                  (ed & (gea0 >> 1) & ~(behind >> 2)) | (f0 & ~(ge90_o >> 1)) | (f4 & (ge90 >> 1));
+        v.tail = ((l2 & (behind >> 1)) | (l3 & (behind >> 2)) | (l4 & (behind >> 3))) & ~bad_open & own_bits;
+        v.lead &= ~v.tail; // the held prefix's lead begins no unit of THIS buffer
+        v.four &= ~v.tail;
+        v.bad = (bad_open | (cont & ~claimed)) & own_bits;
+    }
     return v;
 }
 
@@ -172,6 +202,21 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_count(const uint8_t *__rest
     const unsigned long long offenders = __ballot(v.bad != 0);
     if (offenders && lane_id() == (uint32_t)__ffsll((long long)offenders) - 1)
         atomicMin(res + 1, (unsigned long long)(o - 4 + (uint32_t)__ffs((int)v.bad) - 1));
+    uint32_t total;
+    (void)block_scan(v.units(), &total);
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
+}
+
+// k_utf8_count over a buffer whose text goes on behind it (lane_view's OPEN form).  res[2] (preset to 0): the bytes at the
+// buffer's end that begin a sequence a later buffer has to complete, 1 .. 3; the sums are those of the n - res[2] bytes before them
+__global__ __launch_bounds__(kU8Threads) void k_utf8_open_count(const uint8_t *__restrict__ in, uint32_t n, uint32_t *__restrict__ block_sums,
+                                                                unsigned long long *__restrict__ res) {
+    const uint32_t o = (blockIdx.x * kU8Threads + threadIdx.x) * kU8Lane;
+    const LaneView v = lane_view<false, true>(in, n, o);
+    const unsigned long long offenders = __ballot(v.bad != 0);
+    if (offenders && lane_id() == (uint32_t)__ffsll((long long)offenders) - 1)
+        atomicMin(res + 1, (unsigned long long)(o - 4 + (uint32_t)__ffs((int)v.bad) - 1));
+    if (v.tail) res[2] = (unsigned long long)(n - (o - 4 + (uint32_t)__ffs((int)v.tail) - 1));
     uint32_t total;
     (void)block_scan(v.units(), &total);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
@@ -507,10 +552,16 @@ int utf8_batch_map_position(const Utf8Batch &b, uint64_t unit, int64_t *d_out, h
 }
 
 int stage_utf8_text(DeviceState &d, const uint8_t *bytes, uint64_t n_bytes, hipStream_t stream, Utf8Text *out) {
+    return stage_utf8_parts(d, nullptr, 0, bytes, n_bytes, /*open=*/false, stream, out);
+}
+
+int stage_utf8_parts(DeviceState &d, const uint8_t *head, uint64_t n_head, const uint8_t *bytes, uint64_t n_rest, bool open, hipStream_t stream,
+                     Utf8Text *out) {
     *out = Utf8Text{};
+    const uint64_t n_bytes = n_head + n_rest;
     out->n_bytes = n_bytes;
     const uint32_t n = (uint32_t)n_bytes, n_blocks = (n + kU8Block - 1) / kU8Block;
-    // aux: [n_units, first_bad | block sums | checkpoints, one per 32 units of a text that has at most n units]
+    // aux: [n_units, first_bad, tail | block sums | checkpoints, one per 32 units of a text that has at most n units]
     const size_t sums_off = 64, ckpt_off = sums_off + (((size_t)n_blocks * 4 + 63) & ~(size_t)63);
     int rc;
     if ((rc = d.utf8_in.ensure((size_t)n + 64))) return rc; // (a lane's 16-byte load, and 4 bytes behind it)
@@ -519,23 +570,35 @@ int stage_utf8_text(DeviceState &d, const uint8_t *bytes, uint64_t n_bytes, hipS
     unsigned long long *d_res = reinterpret_cast<unsigned long long *>(d.utf8_aux.p);
     uint32_t *d_sums = reinterpret_cast<uint32_t *>((char *)d.utf8_aux.p + sums_off);
     uint32_t *d_ckpt = reinterpret_cast<uint32_t *>((char *)d.utf8_aux.p + ckpt_off);
-    HIP_TRY(hipMemcpyAsync(d.utf8_in.p, bytes, n, hipMemcpyHostToDevice, stream));
+    if (n_head) HIP_TRY(hipMemcpyAsync(d.utf8_in.p, head, n_head, hipMemcpyHostToDevice, stream));
+    if (n_rest) HIP_TRY(hipMemcpyAsync((char *)d.utf8_in.p + n_head, bytes, n_rest, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemsetAsync(d_res, 0xff, 16, stream));
-    hipLaunchKernelGGL(k_utf8_count, dim3(n_blocks), dim3(kU8Threads), 0, stream, d_in, n, d_sums, d_res);
+    if (open) {
+        HIP_TRY(hipMemsetAsync(d_res + 2, 0, 8, stream));
+        hipLaunchKernelGGL(k_utf8_open_count, dim3(n_blocks), dim3(kU8Threads), 0, stream, d_in, n, d_sums, d_res);
+    } else {
+        hipLaunchKernelGGL(k_utf8_count, dim3(n_blocks), dim3(kU8Threads), 0, stream, d_in, n, d_sums, d_res);
+    }
     hipLaunchKernelGGL(k_utf8_scan, dim3(1), dim3(kU8Threads), 0, stream, d_sums, n_blocks, d_res);
     HIP_TRY(hipGetLastError());
     // the one wait this front end adds: the shard cannot be sized, nor the scan begun, before the text is known to be well-formed
-    unsigned long long h_res[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(h_res, d_res, 16, hipMemcpyDeviceToHost, stream));
+    unsigned long long h_res[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h_res, d_res, open ? 24 : 16, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     out->n_units = h_res[0];
     out->first_bad = (int64_t)h_res[1];
     if (out->first_bad >= 0) return ACGPU_E_ENCODING;
-    if (out->n_units > n) return ACGPU_E_HIP; // (never: a sequence has no more units than bytes)
-    const bool ascii = out->n_units == n;
+    if (h_res[2] > 3 || h_res[2] > n) return ACGPU_E_HIP; // (never: a held prefix is one to three bytes of the buffer)
+    out->tail = (uint32_t)h_res[2];
+    // the text that is transcoded: the bytes before the held prefix -- they end where a sequence ends, well-formed on their own
+    const uint32_t n_text = n - out->tail, n_text_blocks = (n_text + kU8Block - 1) / kU8Block;
+    out->n_bytes = n_text;
+    if (out->n_units > n_text) return ACGPU_E_HIP; // (never: a sequence has no more units than bytes)
+    const bool ascii = out->n_units == n_text;
     if ((rc = d.stage_hay.ensure(out->n_units * 2 + 16))) return rc;
-    hipLaunchKernelGGL(k_utf8_write, dim3(n_blocks), dim3(kU8Threads), 0, stream, d_in, n, (const uint32_t *)d_sums,
-                       reinterpret_cast<uint16_t *>(d.stage_hay.p), (uint32_t)out->n_units, ascii ? nullptr : d_ckpt);
+    if (n_text_blocks) // (a buffer that is a held prefix and nothing else has no unit to write)
+        hipLaunchKernelGGL(k_utf8_write, dim3(n_text_blocks), dim3(kU8Threads), 0, stream, d_in, n_text, (const uint32_t *)d_sums,
+                           reinterpret_cast<uint16_t *>(d.stage_hay.p), (uint32_t)out->n_units, ascii ? nullptr : d_ckpt);
     HIP_TRY(hipGetLastError());
     out->shard.d_hay = (const uint16_t *)d.stage_hay.p;
     out->shard.n_units = out->shard.own_end = out->n_units;

@@ -617,12 +617,65 @@ class Stream:
             r[:, :2] += base.value
             return r
 
+    def feed_utf8(self, data, final=False, cap=None, stats=None):
+        """acgpu_stream_feed_utf8: the next bytes of a UTF-8 text (bytes-like or a uint8 array; a chunk may end inside a
+        sequence) -> the records that have become decidable as an (n, 2|3) int64 array with GLOBAL BYTE offsets (bytes since the
+        first feed), end exclusive.  Ill-formed input raises Utf8Error (.start: the global offset) and finishes the stream.
+        A stream is fed either units or bytes.  stats: an N.Utf8StreamStats to fill in, if wanted."""
+        buf = _utf8_bytes(data)
+        n = int(buf.size)
+        cols = self._kind // 4
+        if cap is None:
+            cap = max(4096, n // 64)
+        src = buf if n else np.zeros(1, np.uint8)
+        st = stats if stats is not None else N.Utf8StreamStats()
+        while True:
+            out = getattr(self, "_out", None)  # (one record buffer per stream, as feed)
+            if out is None or out.shape != (cap, cols):
+                out = self._out = np.empty((cap, cols), dtype=np.int32)
+            n_out, base = ctypes.c_uint64(0), ctypes.c_int64(0)
+            rc = N.lib().acgpu_stream_feed_utf8(self._h, _vp(src), n, 1 if final else 0, self._kind, _vp(out), cap,
+                                                ctypes.byref(n_out), ctypes.byref(base), ctypes.byref(st))
+            if rc == N.E_OVERFLOW:  # nothing was consumed: same feed, larger buffer
+                cap = int(n_out.value)
+                continue
+            if rc == N.E_ENCODING:
+                raise Utf8Error(st.first_bad)
+            N.check(rc, "acgpu_stream_feed_utf8")
+            r = out[:n_out.value].astype(np.int64)
+            r[:, :2] += base.value
+            return r
+
     def close(self):
         h, self._h = getattr(self, "_h", None), None
         if h:
             N.lib().acgpu_stream_close(h)
 
     __del__ = close
+
+
+def _byte_chunks(readable, chunk_bytes):
+    """A binary file object (read(n) -> bytes, b"" at the end) or any iterable of bytes-like chunks."""
+    if hasattr(readable, "read"):
+        while True:
+            c = readable.read(chunk_bytes)
+            if not c:
+                return
+            yield c
+    else:
+        yield from readable
+
+
+def _utf8_stream_pages(auto, readable, chunk_bytes, with_ids):
+    """The records of a UTF-8 text that is read chunk by chunk, as one int64 array of global byte offsets per feed; closing the
+    generator closes the stream, and no chunk is read before the records of the one before it have been taken."""
+    st = Stream(auto, with_ids=with_ids)
+    try:
+        for chunk in _byte_chunks(readable, chunk_bytes):
+            yield st.feed_utf8(chunk)
+        yield st.feed_utf8(b"", final=True)
+    finally:
+        st.close()
 
 
 class Cursor:
@@ -872,6 +925,27 @@ class StringSet(_BatchDecisions):
             if not fn(data, s, e):
                 return
 
+    def match_utf8_readable(self, readable, listener, chunk_bytes=1 << 22):
+        """Not in the reference: match_utf8 for a text that is read as it goes -- a binary file object (read(n)) or an iterable
+        of bytes-like chunks, cut anywhere, inside a sequence too.  The listener gets (start, end) in GLOBAL byte offsets (there
+        is no one haystack object to hand over); a call that returns False stops the feeding AND the reading.  Utf8Error
+        (.start: the global offset) if the text is ill-formed."""
+        fn = _listener_fn(listener)
+        pages = _utf8_stream_pages(self._auto, readable, chunk_bytes, False)
+        try:
+            for page in pages:
+                for s, e in page.tolist():
+                    if not fn(s, e):
+                        return
+        finally:
+            pages.close()
+
+    def find_all_utf8_readable(self, readable, chunk_bytes=1 << 22):
+        """Not in the reference: the (n,2) int64 array of (start, end) records of a UTF-8 text read chunk by chunk, in GLOBAL
+        byte offsets -- find_all_utf8 of the whole text, which may be longer than 2^31 bytes."""
+        pages = list(_utf8_stream_pages(self._auto, readable, chunk_bytes, False))
+        return np.concatenate(pages) if pages else np.zeros((0, 2), np.int64)
+
     def match_batch(self, haystacks, listener):
         """Not in the reference: match(haystack, listener) for every haystack of a list in ONE device call (short inputs: a
         call has tens of microseconds of fixed cost).  A listener call that returns False ends THAT haystack's matches."""
@@ -1011,6 +1085,26 @@ class StringMap(_BatchDecisions):
         for s, e, k in self._auto.match_utf8(data, with_ids=True).tolist():
             if not fn(data, s, e, vals[k]):
                 return
+
+    def match_utf8_readable(self, readable, listener, chunk_bytes=1 << 22):
+        """Not in the reference: match_utf8 for a text that is read as it goes (see StringSet.match_utf8_readable); the listener
+        gets (start, end, value) in GLOBAL byte offsets."""
+        fn = _listener_fn(listener)
+        vals = self._values
+        pages = _utf8_stream_pages(self._auto, readable, chunk_bytes, True)
+        try:
+            for page in pages:
+                for s, e, k in page.tolist():
+                    if not fn(s, e, vals[k]):
+                        return
+        finally:
+            pages.close()
+
+    def find_all_utf8_readable(self, readable, chunk_bytes=1 << 22):
+        """Not in the reference: the (n,3) int64 array of (start, end, keyword_index) records of a UTF-8 text read chunk by
+        chunk, in GLOBAL byte offsets (see StringSet.find_all_utf8_readable)."""
+        pages = list(_utf8_stream_pages(self._auto, readable, chunk_bytes, True))
+        return np.concatenate(pages) if pages else np.zeros((0, 3), np.int64)
 
     def match_batch(self, haystacks, listener):
         """Not in the reference: match(haystack, listener) for every haystack of a list in ONE device call (see

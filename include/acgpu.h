@@ -688,7 +688,8 @@ int acgpu_summary_batch_u16(const acgpu_automaton *a, const uint16_t *units, con
  * The call is ONE shard through the general path: neither the chunk-pipelined form acgpu_match_u16 takes from 2^25 units on
  * (a long text is copied whole before the scan begins, nothing overlaps), nor its one-launch form for texts of up to 4096 units
  * (a short text pays the fixed cost of five launches, two copies and two waits, several times that form's latency: batch short
- * texts with acgpu_match_batch_utf8 / acgpu_summary_batch_utf8 below).  Not built: count, cursor, stream,
+ * texts with acgpu_match_batch_utf8 / acgpu_summary_batch_utf8 below).  A text that arrives in chunks, or is longer than 2^31
+ * bytes: acgpu_stream_feed_utf8 below.  Not built: count, cursor, the pipelined stream,
  * device-resident and multi-device forms for UTF-8 (replace: acgpu_replace_utf8 and acgpu_replace_batch_utf8 below); lossy decoding (U+FFFD); CESU-8 / WTF-8;
  * the Java facade (its strings are UTF-16).  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
  */
@@ -731,8 +732,8 @@ int acgpu_match_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_
  * withholds more).  From there on everything counts bytes: the plan runs unchanged over byte records and a byte table, and the
  * byte form of the emit kernel writes 16 output bytes per lane from the caller's bytes on the device and the table, through
  * the two slabs of acgpu_replace_u16 ("replace_slab_units" counts bytes here).
- * Many short texts in one call: acgpu_replace_batch_utf8 below.  Not built: device-resident, multi-device and stream forms;
- * validating the replacements; the Java facade.
+ * Many short texts in one call: acgpu_replace_batch_utf8 below.  Not built: device-resident and multi-device forms, replace over
+ * a stream (matching over one: acgpu_stream_feed_utf8); validating the replacements; the Java facade.
  * ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
  */
 int acgpu_replace_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, const uint8_t *repl_bytes,
@@ -771,8 +772,8 @@ int acgpu_replace_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t 
  * (k_summary_utf8_bytes, a lane per haystack, the summaries' first records).  An all-ASCII batch writes no checkpoints and maps
  * nothing.  Where acgpu_match_batch_u16 goes haystack by haystack (no free separator unit, a word matcher over a table that is
  * not fold-consistent) these do too, after the same validation of the whole batch: one acgpu_match_utf8-style pass per haystack.
- * Batch replace: acgpu_replace_batch_utf8 below.  Not built: acgpu_count_utf8; device-resident, multi-device, stream and cursor forms; the one-launch
- * form for tiny batches; the Java facade.  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
+ * Batch replace: acgpu_replace_batch_utf8 below.  One long text in chunks: acgpu_stream_feed_utf8 below.  Not built:
+ * acgpu_count_utf8; device-resident, multi-device and cursor forms; the one-launch form for tiny batches; the Java facade.  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
  */
 typedef struct acgpu_utf8_batch_stats {
     uint64_t n_units;      /* UTF-16 units of all haystacks, separators not counted (0 on ACGPU_E_ENCODING) */
@@ -822,13 +823,64 @@ int acgpu_summary_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, con
  * a word matcher over a table that is not fold-consistent): the whole batch is validated first, so what is refused does not
  * depend on the route, then every haystack takes acgpu_replace_utf8's route with cap, the output position and the stats carried
  * across and the table uploaded once.
- * Not built: device-resident, multi-device, stream and cursor forms; validating the replacements; lossy decoding (U+FFFD); a
- * one-launch form for tiny batches; the Java facade.  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
+ * Not built: device-resident, multi-device and cursor forms, replace over a stream (matching over one: acgpu_stream_feed_utf8
+ * below); validating the replacements; lossy decoding (U+FFFD); a one-launch form for tiny batches; the Java facade.  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
  */
 int acgpu_replace_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
                              const uint8_t *repl_bytes, const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap,
                              uint64_t *out_offsets /* n_haystacks + 1 */, uint64_t *n_out,
                              acgpu_replace_stats *st /* may be NULL */, acgpu_utf8_batch_stats *ust /* may be NULL */);
+
+/*
+ * The chunked feed for UTF-8: match(Readable, ...) over a file, a dump or a socket as its BYTES arrive, records in byte offsets.
+ * A stream opened with acgpu_stream_open is fed bytes instead of units; the concatenation of the records over all feeds is,
+ * record for record, what acgpu_match_utf8 returns for the concatenation of all bytes fed -- count, order, keyword_id and
+ * record kind, all five families (the Readable rule for word tables that are not fold-consistent, as acgpu_stream_feed) -- and
+ * a feed returns the records that have become decidable, as acgpu_stream_feed does.
+ *  out    : cap records of record_kind; start / end follow acgpu_match_utf8's MAPPING RULE (inside a surrogate pair included) as
+ *           int32 relative to *base, a GLOBAL BYTE position (bytes since the first feed, int64: a stream may run past 2^31 bytes).
+ *  CUT SEQUENCES.  A feed may end inside a sequence.  If its last 1..3 bytes are a proper prefix of a well-formed sequence --
+ *           the lead is valid and every byte present satisfies the rule that names it: the second byte lies in the range its lead
+ *           allows (E0 A0..BF, ED 80..9F, F0 90..BF, F4 80..8F), the third is a continuation byte -- they are held back
+ *           (stats->held) and decoded with the next feed.  Anything else is ill-formed NOW.  With final != 0 nothing is held: a
+ *           truncated sequence is ill-formed at its lead.  This is codecs.getincrementaldecoder("utf-8")().decode(chunk, final)
+ *           of CPython: the same feed fails, at the same place.  That includes its one exception to the rule above: a feed that
+ *           is not final and ENDS with the two bytes ED A0..BF (an encoded surrogate, cut) holds them too, although no third byte
+ *           completes them; the next feed, or the final one, then reports the same offset, that of the ED.
+ *  ACGPU_E_ENCODING : *n_out = 0, `out` is untouched, nothing of this feed was scanned; stats->first_bad is the GLOBAL offset (it
+ *           may lie in an earlier feed's bytes: the lead of a held prefix that the new bytes fail to complete).  The stream is
+ *           finished, only close is valid; the pool is as usable as before.
+ *  ACGPU_E_OVERFLOW : nothing was consumed; *n_out is the capacity to call the SAME feed again with (cap == 0, out == NULL: count).
+ *  ACGPU_E_INVALID, before a device is touched: NULL s, n_out or base; bytes NULL with a byte to read; cap without out; a bad
+ *           record_kind; a finished or detached stream; carried bytes + n_bytes >= 2^31; a stream that has been fed through
+ *           acgpu_stream_feed -- and acgpu_stream_feed on a stream that has been fed bytes.  The first feed of either kind, a feed
+ *           of length 0 included, decides which kind the stream is.
+ *  ACGPU_E_UNSUPPORTED : a stream switched to the pipelined form (acgpu_stream_set_pipelined, which in turn refuses a stream of bytes).
+ *  no device : an empty feed that is not final, and an empty final feed on a stream that holds nothing: ACGPU_OK, no records.
+ *  stats  : may be NULL.
+ * Device and lifetime as for acgpu_stream_feed.  Works on the pool's call stream, under the pool's lock (STREAM RULE above:
+ * tickets in flight on the pool give ACGPU_E_INVALID).
+ * How it works: the stream carries BYTES on code-point boundaries -- the carried text and behind it the held prefix -- with the
+ * units they decode to, and its positions in both measures.  A feed stages [carried bytes | chunk] as acgpu_match_utf8 stages a
+ * text, through the OPEN form of the validator unless it is the last (k_utf8_open_count: a lead in the last three bytes whose
+ * sequence reaches behind the buffer is judged by the bytes that are there; if they pass it is not counted and the host reads
+ * {n_units, first_bad, tail} in the one wait; k_utf8_write runs over the n - tail bytes before it).  The shard is cut by the
+ * plan of acgpu_stream_feed in units, scanned by match_shard, and k_utf8_map rewrites the records to bytes of the buffer (an
+ * all-ASCII buffer: nothing to map).  The byte at which the carry is cut for the next feed is found on the host, walking back
+ * from the end of the decoded bytes over the lead bytes; it is a code-point boundary, so where the plan's unit is a low
+ * surrogate one unit more is carried -- left context that is longer than needed changes no record.
+ * Not built: the pipelined and reserved forms for bytes; cursor, count, device-resident and multi-device forms; lossy decoding
+ * (U+FFFD); the Java facade (its Readable hands out UTF-16).  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
+ */
+typedef struct acgpu_utf8_stream_stats {
+    uint64_t n_units;    /* UTF-16 units the bytes newly decoded by this feed came to (0 on ACGPU_E_ENCODING)                      */
+    int64_t  first_bad;  /* -1, or the GLOBAL byte offset (bytes since the first feed) at which a strict decoder stops             */
+    uint32_t ascii;      /* 1: every byte of this feed's buffer (carry included) < 0x80, nothing was remapped                      */
+    uint32_t held;       /* 0..3: bytes at the end of this feed that begin a sequence the next feed must complete                  */
+} acgpu_utf8_stream_stats;   /* 24 bytes */
+int acgpu_stream_feed_utf8(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, int record_kind,
+                           void *out, uint64_t cap, uint64_t *n_out, int64_t *base,
+                           acgpu_utf8_stream_stats *stats /* may be NULL */);
 
 /*
  * Synthetic haystack generator of the benchmark: unit i of the stream is
