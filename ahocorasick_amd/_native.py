@@ -124,7 +124,8 @@ SYMBOLS = ["acgpu_build", "acgpu_free", "acgpu_get_info", "acgpu_match_u16", "ac
            "acgpu_cursor_get_stats", "acgpu_cursor_close", "acgpu_count_u16", "acgpu_count_device",
            "acgpu_replace_u16", "acgpu_replace_device", "acgpu_replace_batch_u16", "acgpu_summary_batch_u16",
            "acgpu_match_utf8", "acgpu_replace_utf8", "acgpu_match_batch_utf8", "acgpu_summary_batch_utf8",
-           "acgpu_replace_batch_utf8", "acgpu_stream_feed_utf8"]
+           "acgpu_replace_batch_utf8", "acgpu_stream_feed_utf8", "acgpu_stream_replace_u16",
+           "acgpu_stream_replace_utf8"]
 
 _lib = None
 
@@ -187,6 +188,11 @@ def lib():
         L.acgpu_stream_feed_utf8.restype = ci
         L.acgpu_stream_feed_utf8.argtypes = [vp, vp, u64, ci, ci, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(i64),
                                              ctypes.POINTER(Utf8StreamStats)]
+        L.acgpu_stream_replace_u16.restype = ci
+        L.acgpu_stream_replace_u16.argtypes = [vp, vp, u64, ci, vp, vp, u32, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(ReplaceStats)]
+        L.acgpu_stream_replace_utf8.restype = ci
+        L.acgpu_stream_replace_utf8.argtypes = [vp, vp, u64, ci, vp, vp, u32, vp, u64, ctypes.POINTER(u64),
+                                                ctypes.POINTER(Utf8StreamStats), ctypes.POINTER(ReplaceStats)]
         L.acgpu_stream_close.restype = None
         L.acgpu_stream_close.argtypes = [vp]
         L.acgpu_stream_set_pipelined.restype = ci

@@ -516,6 +516,7 @@ struct PieceScan {
     uint64_t n;
     const acgpu_shard *shard;
     hipStream_t stream;
+    bool readable = false; // a shard scanned as match(Readable, ...) scans it (shard_rule, match_shard): a stream's buffer
     int operator()(PieceDriver &p, uint64_t size, uint64_t *cnt, uint64_t *done, uint64_t *base) const;
 };
 
@@ -523,6 +524,25 @@ struct PieceScan {
 // smaller piece, or not at all (ACGPU_E_NOMEM: one unit's records do not fit the budget; a whole text instead grows the reservoir
 // to the exact count, past the budget).  *n_out = the piece's records, *base = the text position of their buffer's unit 0.
 int scan_next_piece(PieceDriver &p, const PieceScan &scan, uint64_t *n_out, uint64_t *base);
+
+// ---- a replace stream's feed (acgpu_replace.hip, for acgpu_stream.hip) ----
+// check_table of the replace entries: ACGPU_E_INVALID for a bad table, ACGPU_E_UNSUPPORTED for ACGPU_MODE_ALL; no device.
+int replace_check_table(const acgpu_automaton *a, const void *repl, const uint64_t *repl_off, uint32_t n_repl);
+// The buffer [carry | chunk] of one feed, on the device.  Positions are buffer relative; done counts ELEMENTS -- units, or
+// bytes of u8 -- and chain units.
+struct ReplaceFeed {
+    acgpu_shard shard{};         // the buffer's units with the feed's owned range, text_begin and text_end set
+    const Utf8Text *u8 = nullptr; // a stream of bytes: the staged buffer `shard` is the units of
+    bool final = false;          // the buffer's end is the text's end
+    uint64_t done = 0;           // in: output exists for the elements in front of it; out: the same behind this feed
+    int64_t chain = 0;           // in: the chain's entry; out: its exit
+    acgpu_replace_stats st{};    // out: this feed alone
+};
+// Rewrites [f->done, new done) of the buffer into out (host, cap elements) through the pieces of the replace entries, scanned by
+// the Readable rule.  ACGPU_E_OVERFLOW: *n_out and f->st are exact, nothing at or beyond out[cap] was written.  The caller holds
+// d.mu, no ticket is in flight, and on an error it waits for the streams (PoolCall::fail).
+int replace_feed(acgpu_automaton *a, DeviceState &d, ReplaceFeed *f, const void *repl, const uint64_t *repl_off, uint32_t n_repl, void *out,
+                 uint64_t cap, uint64_t *n_out);
 
 // collect() of a counting shard call that found n records: counts them (acgpu_count.hip).  ACGPU_E_OVERFLOW: they did not fit
 // the reservoir, nothing was counted.

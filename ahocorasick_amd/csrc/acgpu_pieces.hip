@@ -58,17 +58,17 @@ void PieceRamp::advance(uint64_t size, uint64_t cnt) {
 // ACGPU_E_OVERFLOW: *cnt is what did not fit, and a counting host range has moved *done to the position up to which the piece is
 // counted all the same (p.chain: the entry into the rest).  *base: the text position of the buffer's unit 0.
 int PieceScan::operator()(PieceDriver &p, uint64_t size, uint64_t *cnt, uint64_t *done, uint64_t *base) const {
-    const ShardRule rule = shard_rule(a->t, p.record_kind, false);
+    const ShardRule rule = shard_rule(a->t, p.record_kind, shard && readable);
     const uint64_t own_hi = p.pos + size;
     *base = 0;
-    if (shard) { // the caller's buffer, a moving owned range
+    if (shard) { // the caller's buffer, a moving owned range (readable: a stream's, by the rule of the Readable loops)
         acgpu_shard sh = *shard;
         sh.own_begin = p.pos;
         sh.own_end = own_hi;
         sh.d_result = nullptr;
         const int64_t entry = rule.chain == Chain::None ? shard->chain_entry : piece_entry(rule, p.chain, 0, p.pos);
         sh.chain_entry = entry;
-        const int rc = match_shard(a, d, &sh, p.record_kind, p.res->p, p.res->recs, cnt, stream, nullptr);
+        const int rc = match_shard(a, d, &sh, p.record_kind, p.res->p, p.res->recs, cnt, stream, nullptr, readable);
         if (rc == ACGPU_OK) p.chain = piece_exit(rule, entry, own_hi, &sh, *cnt);
         return rc;
     }

@@ -560,7 +560,13 @@ int replace_piece(ReplaceCall &c, const void *hay, uint64_t base, const int32_t 
     // UTF-8: the boundary goes from units to bytes through the checkpoints (the last piece's limit is the text's end, and in an
     // all-ASCII text a unit is a byte); the byte rides with what the host reads behind the plan anyway
     // a batch's boundary always goes through the kernel: also in an all-ASCII batch a unit stands h separators behind its byte
-    const bool map_bound = !last_or_whole && (c.ub || (c.u8 && c.u8->d_ckpt));
+    bool map_bound = !last_or_whole && (c.ub || (c.u8 && c.u8->d_ckpt));
+    // a stream's feed whose right halo is empty (SHORTEST; LONGEST over one-unit keywords) ends its last piece at the buffer's
+    // end, which is no unit of the text (utf8_map_position wants unit < n_units): its byte is the end of the decoded bytes
+    if (map_bound && !c.ub && bound >= c.u8->n_units) {
+        bound = c.u8->n_bytes;
+        map_bound = false;
+    }
     if (cnt || map_bound) {
         const uint32_t n_blocks = (uint32_t)((cnt + kPlanTile - 1) / kPlanTile);
         int rc = d.replace_plan.ensure((kPlanHead + (size_t)n_blocks + cnt) * 8); // {sum of the deltas, last end, boundary, -} | workgroup sums | pos
@@ -644,19 +650,25 @@ int replace_piece(ReplaceCall &c, const void *hay, uint64_t base, const int32_t 
     return ACGPU_OK;
 }
 
-int replace_pieces(ReplaceCall &c, int64_t chain, bool whole, const PieceScan &scan) {
+// The pieces of the owned units [own_begin, own_end) of the scan's text, behind c.done (set by the caller: the position up to
+// which output exists).  last: the range's end is the text's end, so its last piece emits everything; else every piece emits
+// up to replace_limit and c.done is where the next range's emit starts (a stream's feed, acgpu_stream.hip).  A whole text is
+// (0, n, c.done = 0, last = true).  chain: the chain's entry; *chain_exit: its exit, if a piece was scanned.
+int replace_pieces(ReplaceCall &c, int64_t chain, bool whole, const PieceScan &scan, uint64_t own_begin, uint64_t own_end, bool last = true,
+                   int64_t *chain_exit = nullptr) {
     DeviceState &d = c.d;
     if (!d.replace_pin) HIP_TRY(hipHostMalloc(&d.replace_pin.h, 64, hipHostMallocDefault));
     if (!d.copy_stream) HIP_TRY(hipStreamCreateWithFlags(&d.copy_stream.h, hipStreamNonBlocking));
     for (auto &e : d.replace_ev)
         if (!e) HIP_TRY(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
     // (driven over the units the scan sees: a UTF-8 text's units, a UTF-8 batch's units and separators)
-    PieceDriver p(0, c.u8 ? c.u8->shard.n_units : c.n, chain, whole, ACGPU_REC_MAP, &d.count_res); // the pool's reservoir of Map records (a counting call's too: one call at a time holds the pool)
+    PieceDriver p(own_begin, own_end, chain, whole, ACGPU_REC_MAP, &d.count_res); // the pool's reservoir of Map records (a counting call's too: one call at a time holds the pool)
     int rc = ACGPU_OK;
+    const void *hay = c.u8 ? (const void *)c.u8->d_bytes : scan.shard ? (const void *)scan.shard->d_hay : d.stage_hay.p;
     while (rc == ACGPU_OK && p.pos < p.end) {
         uint64_t cnt = 0, base = 0;
         if ((rc = scan_next_piece(p, scan, &cnt, &base))) break;
-        const void *hay = c.u8 ? (const void *)c.u8->d_bytes : scan.shard ? (const void *)scan.shard->d_hay : d.stage_hay.p;
+        if (!c.u8 && !scan.shard) hay = d.stage_hay.p; // (a host text's buffer may have grown under the piece)
         const int32_t *recs = reinterpret_cast<const int32_t *>(d.count_res.p);
         // UTF-8: the piece's records go from units to bytes where they lie (text relative: the shard is the whole text)
         // (a batch: span relative, and an all-ASCII one is mapped too)
@@ -666,8 +678,11 @@ int replace_pieces(ReplaceCall &c, int64_t chain, bool whole, const PieceScan &s
         if (rc) break;
         uint64_t n_list = cnt;
         if (c.h_cat_off && (rc = merge_separators(c, base, p.pos, &recs, &n_list))) break;
-        rc = replace_piece(c, hay, base, recs, n_list, cnt, p.pos, whole || p.pos >= p.end);
+        rc = replace_piece(c, hay, base, recs, n_list, cnt, p.pos, last && p.pos >= p.end); // (a whole text's one piece ends at p.end)
     }
+    // a stream's last feed that owns nothing new: what the feeds before it withheld, text without a record
+    if (rc == ACGPU_OK && last && scan.shard && c.done < c.n) rc = replace_piece(c, hay, 0, reinterpret_cast<const int32_t *>(d.count_res.p), 0, 0, p.end, true);
+    if (chain_exit && p.pieces) *chain_exit = p.chain;
     c.st.pieces += (uint32_t)p.pieces; // (added: a batch call haystack by haystack drives one text after the other)
     c.st.rescans += (uint32_t)p.rescans;
     c.st.units_out = c.out_pos;
@@ -679,7 +694,7 @@ int replace_pieces(ReplaceCall &c, int64_t chain, bool whole, const PieceScan &s
 int replace_host_text(ReplaceCall &c, const uint16_t *hay, uint64_t n_units) {
     c.n = n_units;
     c.done = 0;
-    const int rc = replace_pieces(c, 0, host_one_piece(c.a->t, ACGPU_REC_MAP), PieceScan{c.a, c.d, hay, n_units, nullptr, c.stream});
+    const int rc = replace_pieces(c, 0, host_one_piece(c.a->t, ACGPU_REC_MAP), PieceScan{c.a, c.d, hay, n_units, nullptr, c.stream}, 0, n_units);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c.stream));
     return ACGPU_OK;
@@ -704,6 +719,44 @@ int check_table(const acgpu_automaton *a, const void *repl_units, const uint64_t
 }
 
 } // namespace
+
+namespace acgpu {
+
+int replace_check_table(const acgpu_automaton *a, const void *repl, const uint64_t *repl_off, uint32_t n_repl) {
+    return check_table(a, repl, repl_off, n_repl);
+}
+
+// One feed of a replace stream: the pieces of the buffer's owned range behind f->done, as a text's pieces are driven -- the
+// table is uploaded per feed, so nothing of the stream stays on the device between two feeds.
+int replace_feed(acgpu_automaton *a, DeviceState &d, ReplaceFeed *f, const void *repl, const uint64_t *repl_off, uint32_t n_repl, void *out,
+                 uint64_t cap, uint64_t *n_out) {
+    ReplaceCall c{a, d, d.call_stream};
+    c.esz = f->u8 ? 1 : 2;
+    c.u8 = f->u8;
+    c.h_out = static_cast<uint8_t *>(out);
+    c.cap = cap;
+    c.n = f->u8 ? f->u8->n_bytes : f->shard.n_units;
+    c.done = f->done;
+    if (c.done > c.n) return ACGPU_E_HIP; // (never: the carry reaches back to `done`, the stream checks it)
+    int rc = upload_table(c, repl, repl_off, n_repl);
+    if (rc) return rc;
+    const ShardRule rule = shard_rule(a->t, ACGPU_REC_MAP, /*readable=*/true);
+    const int64_t entry = piece_entry(rule, f->chain, 0, f->shard.own_begin);
+    int64_t chain_exit = piece_exit(rule, entry, f->shard.own_end, nullptr, 0); // (nothing owned: nothing scanned)
+    acgpu_shard sh = f->shard;
+    sh.chain_entry = entry;
+    rc = replace_pieces(c, f->chain, rule.sequential, PieceScan{a, d, nullptr, 0, &sh, c.stream, /*readable=*/true}, sh.own_begin, sh.own_end, f->final,
+                        &chain_exit);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    f->done = c.done;
+    f->chain = chain_exit;
+    f->st = c.st;
+    *n_out = c.out_pos;
+    return c.out_pos > c.cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
+}
+
+} // namespace acgpu
 
 extern "C" {
 
@@ -746,7 +799,7 @@ int acgpu_replace_device(const acgpu_automaton *ca, acgpu_shard *shard, const ui
     c.n = shard->n_units;
     if ((rc = upload_table(c, repl_units, repl_off, n_repl))) return rc;
     const bool whole = shard_rule(a->t, ACGPU_REC_MAP, false).sequential;
-    rc = replace_pieces(c, shard->chain_entry, whole, PieceScan{a, d, nullptr, 0, shard, stream});
+    rc = replace_pieces(c, shard->chain_entry, whole, PieceScan{a, d, nullptr, 0, shard, stream}, 0, shard->n_units);
     const hipError_t e = hipStreamSynchronize(stream); // the final wait
     if (rc) return rc;
     HIP_TRY(e);
@@ -788,7 +841,7 @@ int acgpu_replace_utf8(const acgpu_automaton *ca, const uint8_t *bytes, uint64_t
     c.n = n_bytes;
     if ((rc = upload_table(c, repl_bytes, repl_off, n_repl))) return call.fail(rc);
     const bool whole = shard_rule(a->t, ACGPU_REC_MAP, false).sequential;
-    if ((rc = replace_pieces(c, 0, whole, PieceScan{a, d, nullptr, 0, &text.shard, c.stream}))) return call.fail(rc);
+    if ((rc = replace_pieces(c, 0, whole, PieceScan{a, d, nullptr, 0, &text.shard, c.stream}, 0, text.shard.n_units))) return call.fail(rc);
     HIP_TRY(hipStreamSynchronize(c.stream));
     return replace_result(c, n_out, st);
 }
@@ -848,7 +901,7 @@ int acgpu_replace_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, co
                 c.u8 = &text;
                 c.n = len;
                 c.done = 0;
-                if ((rc = replace_pieces(c, 0, whole, PieceScan{a, d, nullptr, 0, &text.shard, c.stream}))) return call.fail(rc);
+                if ((rc = replace_pieces(c, 0, whole, PieceScan{a, d, nullptr, 0, &text.shard, c.stream}, 0, text.shard.n_units))) return call.fail(rc);
                 if (hipStreamSynchronize(c.stream) != hipSuccess) return call.fail(ACGPU_E_HIP); // (the next haystack is staged over this one)
             }
             out_offsets[i + 1] = c.out_pos;
@@ -863,7 +916,7 @@ int acgpu_replace_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, co
     c.d_out_off = reinterpret_cast<uint64_t *>(d.replace_off.p);
     {
         SeparatorScan sep(d, t);
-        rc = replace_pieces(c, 0, whole, PieceScan{a, d, nullptr, 0, &b.text.shard, c.stream});
+        rc = replace_pieces(c, 0, whole, PieceScan{a, d, nullptr, 0, &b.text.shard, c.stream}, 0, b.text.shard.n_units);
     }
     if (rc) return call.fail(rc);
     // (every boundary was written by exactly one piece, boundary 0 -- offset 0 -- included)
@@ -914,7 +967,7 @@ int acgpu_replace_batch_u16(const acgpu_automaton *ca, const uint16_t *units, co
     c.seps.id = (int32_t)a->n_given;
     c.d_out_off = reinterpret_cast<uint64_t *>(d.replace_off.p);
     if ((rc = upload_table(c, repl_units, repl_off, n_repl, /*full=*/true))) return rc;
-    rc = replace_pieces(c, 0, host_one_piece(t, ACGPU_REC_MAP), PieceScan{a, d, text.h_cat, text.cat, nullptr, c.stream});
+    rc = replace_pieces(c, 0, host_one_piece(t, ACGPU_REC_MAP), PieceScan{a, d, text.h_cat, text.cat, nullptr, c.stream}, 0, text.cat);
     if (rc) return call.fail(rc);
     HIP_TRY(hipMemcpyAsync(out_offsets + 1, c.d_out_off + 1, (size_t)n_haystacks * 8, hipMemcpyDeviceToHost, d.call_stream)); // (every separator was merged once)
     HIP_TRY(hipStreamSynchronize(d.call_stream));

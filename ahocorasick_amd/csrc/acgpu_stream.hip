@@ -14,6 +14,9 @@
 // and behind them the prefix of a sequence that a chunk's end has cut; every feed transcodes [carried bytes | chunk] on the
 // device (stage_utf8_parts, open at the end unless the feed is the last), scans it by the same plan in units and maps the
 // records to bytes of that buffer.
+// acgpu_stream_replace_u16 / acgpu_stream_replace_utf8 rewrite the text instead of reporting its records: the same buffers and the
+// same plan, and over a feed's owned range the pieces of the replace entries (replace_feed, acgpu_replace.hip); the stream keeps
+// `done`, the global position up to which output has been delivered.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -158,8 +161,10 @@ struct acgpu_stream {
     bool finished = false;
     std::vector<uint16_t> buf;
     // ---- a stream of UTF-8 bytes (acgpu_stream_feed_utf8): carry_pos, own_from and chain_entry stay in units ----
-    enum Fed : uint8_t { kFedNone, kFedUnits, kFedBytes };
-    Fed fed = kFedNone;          // what the first feed, of whatever length, made of the stream
+    enum Fed : uint8_t { kFedNone, kFedUnits, kFedBytes, kFedReplaceUnits, kFedReplaceBytes };
+    Fed fed = kFedNone;          // what the first feed, of whatever length, made of the stream: every other entry refuses it
+    uint64_t done = 0;           // a replace stream: output has been delivered for the text in front of this global position, in
+                                 // units (kFedReplaceUnits) or bytes (kFedReplaceBytes); never in front of the carry's first
     std::vector<uint8_t> carry8; // the carried text's bytes, whole code points, then the held prefix
     uint32_t held = 0;           // bytes at carry8's end that begin a sequence the next feed must complete, 0..3
     uint64_t carry_units = 0;    // units that carry8 without the held prefix decodes to
@@ -476,7 +481,7 @@ void acgpu_stream_detach(acgpu_stream *s) { s->a = nullptr; }
 
 int acgpu_stream_set_pipelined(acgpu_stream *s, int on) {
     if (!s || s->started || s->carry_pos != 0 || !s->carry.empty() || s->own_from != 0) return ACGPU_E_INVALID; // before the first feed
-    if (s->fed == acgpu_stream::kFedBytes) return ACGPU_E_INVALID;                                              // (of bytes as well)
+    if (s->fed != acgpu_stream::kFedNone && s->fed != acgpu_stream::kFedUnits) return ACGPU_E_INVALID;          // (of bytes or a replace stream as well)
     s->pipelined = on != 0;
     return ACGPU_OK;
 }
@@ -506,7 +511,7 @@ int acgpu_stream_feed(acgpu_stream *s, const uint16_t *units, uint64_t n_units, 
     if (!s || !n_out || !base || (n_units && !units) || (cap && !out) || s->finished) return ACGPU_E_INVALID;
     if (record_kind != ACGPU_REC_SET && record_kind != ACGPU_REC_MAP) return ACGPU_E_INVALID;
     if (!s->a) return ACGPU_E_INVALID; // (its automaton has been freed)
-    if (s->fed == acgpu_stream::kFedBytes) return ACGPU_E_INVALID; // (a stream of bytes: acgpu_stream_feed_utf8)
+    if (s->fed != acgpu_stream::kFedNone && s->fed != acgpu_stream::kFedUnits) return ACGPU_E_INVALID; // (a stream of another kind: bytes, or a replace stream)
     s->fed = acgpu_stream::kFedUnits;
     if (s->pipelined) return feed_pipelined(s, units, n_units, final, record_kind, out, cap, n_out, base);
     acgpu_automaton *a = s->a;
@@ -559,7 +564,7 @@ int acgpu_stream_feed_utf8(acgpu_stream *s, const uint8_t *bytes, uint64_t n_byt
     if (record_kind != ACGPU_REC_SET && record_kind != ACGPU_REC_MAP) return ACGPU_E_INVALID;
     if (!s->a) return ACGPU_E_INVALID; // (its automaton has been freed)
     if (s->pipelined) return ACGPU_E_UNSUPPORTED;
-    if (s->fed == acgpu_stream::kFedUnits) return ACGPU_E_INVALID; // (a stream of units: acgpu_stream_feed)
+    if (s->fed != acgpu_stream::kFedNone && s->fed != acgpu_stream::kFedBytes) return ACGPU_E_INVALID; // (a stream of another kind: units, or a replace stream)
     const uint64_t n_c8 = s->carry8.size(), total_bytes = n_c8 + n_bytes;
     if (n_bytes >= (1ull << 31) || total_bytes >= (1ull << 31)) return ACGPU_E_INVALID;
     s->fed = acgpu_stream::kFedBytes;
@@ -641,6 +646,170 @@ int acgpu_stream_feed_utf8(acgpu_stream *s, const uint8_t *bytes, uint64_t n_byt
     // commit
     s->own_from = s->carry_pos + p.own_end;
     s->chain_entry = (int64_t)s->carry_pos + chain_exit;
+    s->carry8.swap(next);
+    s->held = text.tail;
+    s->carry_pos += p.total - kept;
+    s->carry_units = kept;
+    s->carry_byte += cut;
+    s->finished = final != 0;
+    return ACGPU_OK;
+}
+
+int acgpu_stream_replace_u16(acgpu_stream *s, const uint16_t *units, uint64_t n_units, int final, const uint16_t *repl_units,
+                             const uint64_t *repl_off, uint32_t n_repl, uint16_t *out, uint64_t cap, uint64_t *n_out, acgpu_replace_stats *st) {
+    if (!s || !n_out || (n_units && !units) || (cap && !out) || s->finished) return ACGPU_E_INVALID;
+    if (!s->a) return ACGPU_E_INVALID; // (its automaton has been freed)
+    if (s->fed != acgpu_stream::kFedNone && s->fed != acgpu_stream::kFedReplaceUnits) return ACGPU_E_INVALID; // (a stream of another kind)
+    acgpu_automaton *a = s->a;
+    int rc = replace_check_table(a, repl_units, repl_off, n_repl);
+    if (rc) return rc;
+    if (s->pipelined) return ACGPU_E_UNSUPPORTED;
+    const ShardRule rule = shard_rule(a->t, ACGPU_REC_MAP, /*readable=*/true);
+    const FeedPlan p = plan_feed(rule, s->carry.size(), n_units, s->own_from, s->carry_pos, final != 0);
+    if (n_units >= (1ull << 31) || p.total >= (1ull << 31)) return ACGPU_E_INVALID;
+    s->fed = acgpu_stream::kFedReplaceUnits;
+    *n_out = 0;
+    if (st) *st = acgpu_replace_stats{};
+    if (n_units == 0 && !final) return ACGPU_OK; // (nothing new to decide: no device needed)
+    if (p.total == 0) {                          // (the end of a stream that holds nothing: neither)
+        s->finished = true;
+        return ACGPU_OK;
+    }
+    if (s->done < s->carry_pos) return ACGPU_E_HIP; // (never: the carry invariant, checked at every commit)
+    try {
+        s->buf.resize(p.total);
+    } catch (...) {
+        return ACGPU_E_NOMEM;
+    }
+    if (!s->carry.empty()) std::memcpy(s->buf.data(), s->carry.data(), s->carry.size() * 2);
+    if (n_units) std::memcpy(s->buf.data() + s->carry.size(), units, n_units * 2);
+    ReplaceFeed f;
+    f.final = final != 0;
+    f.done = s->done - s->carry_pos;
+    f.chain = s->chain_entry - (int64_t)s->carry_pos;
+    if (p.own_end > p.own_begin || (final && f.done < p.total)) {
+        PoolCall call(a);
+        if (call.rc) return call.rc;
+        DeviceState &d = *call.d;
+        if ((rc = call.idle())) return rc; // (the call stream, waited for: see the stream rule)
+        if ((rc = stage_whole_text(d, s->buf.data(), p.total, &f.shard))) return rc; // (the carry and the fed units: then the owned range and the ends)
+        f.shard.own_begin = p.own_begin;
+        f.shard.own_end = p.own_end;
+        f.shard.text_begin = s->carry_pos == 0 ? 1 : 0;
+        f.shard.text_end = final ? 1 : 0;
+        rc = replace_feed(a, d, &f, repl_units, repl_off, n_repl, out, cap, n_out);
+        if (rc == ACGPU_OK || rc == ACGPU_E_OVERFLOW) {
+            if (st) *st = f.st;
+        }
+        if (rc == ACGPU_E_OVERFLOW) return rc; // nothing committed: the same feed again, with *n_out units of room
+        if (rc) return call.fail(rc);
+    } else { // (nothing owned yet: the chain passes through)
+        f.chain = piece_exit(rule, piece_entry(rule, f.chain, 0, p.own_begin), p.own_end, nullptr, 0);
+    }
+    // the carry must reach back to `done`: keep_from <= own_end - left <= done by the limit rule
+    if (!final && f.done < p.keep_from) return ACGPU_E_HIP;
+    // commit
+    s->done = s->carry_pos + f.done;
+    s->own_from = s->carry_pos + p.own_end;
+    s->chain_entry = (int64_t)s->carry_pos + f.chain;
+    s->carry.assign(s->buf.begin() + (ptrdiff_t)p.keep_from, s->buf.end());
+    s->carry_pos += p.keep_from;
+    s->finished = final != 0;
+    return ACGPU_OK;
+}
+
+int acgpu_stream_replace_utf8(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, const uint8_t *repl_bytes,
+                              const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap, uint64_t *n_out,
+                              acgpu_utf8_stream_stats *ust, acgpu_replace_stats *rst) {
+    if (!s || !n_out || (n_bytes && !bytes) || (cap && !out) || s->finished) return ACGPU_E_INVALID;
+    if (!s->a) return ACGPU_E_INVALID; // (its automaton has been freed)
+    if (s->fed != acgpu_stream::kFedNone && s->fed != acgpu_stream::kFedReplaceBytes) return ACGPU_E_INVALID; // (a stream of another kind)
+    acgpu_automaton *a = s->a;
+    int rc = replace_check_table(a, repl_bytes, repl_off, n_repl);
+    if (rc) return rc;
+    if (s->pipelined || a->t.lone_surrogate) return ACGPU_E_UNSUPPORTED; // (the latter: as acgpu_replace_utf8)
+    const uint64_t n_c8 = s->carry8.size(), total_bytes = n_c8 + n_bytes;
+    if (n_bytes >= (1ull << 31) || total_bytes >= (1ull << 31)) return ACGPU_E_INVALID;
+    s->fed = acgpu_stream::kFedReplaceBytes;
+    *n_out = 0;
+    if (rst) *rst = acgpu_replace_stats{};
+    acgpu_utf8_stream_stats st{};
+    st.first_bad = -1;
+    st.held = s->held;
+    st.ascii = 1;
+    for (uint8_t b : s->carry8) st.ascii &= b < 0x80u ? 1u : 0u;
+    if (ust) *ust = st;
+    if (n_bytes == 0 && !final) return ACGPU_OK; // (nothing new to decode or to decide: no device needed)
+    if (total_bytes == 0) {                      // (the end of a stream that holds nothing: neither)
+        s->finished = true;
+        return ACGPU_OK;
+    }
+    if (s->done < s->carry_byte) return ACGPU_E_HIP; // (never: the carry invariant, checked at every commit)
+    PoolCall call(a);
+    if (call.rc) return call.rc;
+    DeviceState &d = *call.d;
+    if ((rc = call.idle())) return rc; // (the call stream, waited for: see the stream rule)
+    const hipStream_t stream = d.call_stream;
+    Utf8Text text;
+    rc = stage_utf8_parts(d, s->carry8.data(), n_c8, bytes, n_bytes, /*open=*/!final, stream, &text);
+    if (rc == ACGPU_E_ENCODING) { // (the stream is idle: the pool is as usable as before the call; what was withheld stays undelivered)
+        st.first_bad = (int64_t)s->carry_byte + text.first_bad;
+        st.ascii = 0;
+        st.held = 0;
+        if (ust) *ust = st;
+        s->finished = true;
+        return rc;
+    }
+    if (rc) return call.fail(rc);
+    if (text.n_units < s->carry_units) return call.fail(ACGPU_E_HIP); // (never: the carried code points decode as they did)
+    st.n_units = text.n_units - s->carry_units;
+    st.ascii = text.n_units == total_bytes;
+    st.held = text.tail;
+    if (ust) *ust = st;
+    const ShardRule rule = shard_rule(a->t, ACGPU_REC_MAP, /*readable=*/true);
+    const FeedPlan p = plan_feed(rule, s->carry_units, text.n_units - s->carry_units, s->own_from, s->carry_pos, final != 0);
+    ReplaceFeed f;
+    f.u8 = &text;
+    f.final = final != 0;
+    f.done = s->done - s->carry_byte; // (bytes of the buffer)
+    f.chain = s->chain_entry - (int64_t)s->carry_pos;
+    if (p.own_end > p.own_begin || (final && f.done < text.n_bytes)) {
+        f.shard = text.shard; // (all the buffer's units: then the owned range and the ends)
+        f.shard.own_begin = p.own_begin;
+        f.shard.own_end = p.own_end;
+        f.shard.text_begin = s->carry_pos == 0 ? 1 : 0;
+        f.shard.text_end = final ? 1 : 0;
+        rc = replace_feed(a, d, &f, repl_bytes, repl_off, n_repl, out, cap, n_out);
+        if (rc == ACGPU_OK || rc == ACGPU_E_OVERFLOW) {
+            if (rst) *rst = f.st;
+        }
+        if (rc == ACGPU_E_OVERFLOW) return rc; // nothing committed: the same feed again, with *n_out bytes of room
+        if (rc) return call.fail(rc);
+    } else { // (nothing owned yet: the chain passes through)
+        f.chain = piece_exit(rule, piece_entry(rule, f.chain, 0, p.own_begin), p.own_end, nullptr, 0);
+    }
+    // the byte to cut the carry at: as acgpu_stream_feed_utf8 finds it
+    auto at = [&](uint64_t i) { return i < n_c8 ? s->carry8[i] : bytes[i - n_c8]; };
+    const uint64_t need = p.total - p.keep_from;
+    uint64_t cut = text.n_bytes, kept = 0;
+    while (kept < need && cut > 0) {
+        const uint8_t b = at(--cut);
+        if ((b & 0xc0u) != 0x80u) kept += b >= 0xf0u ? 2u : 1u;
+    }
+    // the carry must reach back to `done`: the cut is the first byte of the code point that holds unit keep_from, or of the one
+    // before it, and `done` is at least the byte that keep_from <= own_end - left rounds down to
+    if (!final && f.done < cut) return ACGPU_E_HIP;
+    std::vector<uint8_t> next;
+    try {
+        next.resize(total_bytes - cut);
+    } catch (...) {
+        return ACGPU_E_NOMEM;
+    }
+    for (uint64_t i = cut; i < total_bytes; ++i) next[i - cut] = at(i);
+    // commit
+    s->done = s->carry_byte + f.done;
+    s->own_from = s->carry_pos + p.own_end;
+    s->chain_entry = (int64_t)s->carry_pos + f.chain;
     s->carry8.swap(next);
     s->held = text.tail;
     s->carry_pos += p.total - kept;

@@ -646,12 +646,88 @@ class Stream:
             r[:, :2] += base.value
             return r
 
+    def replace_feed(self, units, replacements, final=False, cap=None, stats=None):
+        """acgpu_stream_replace_u16: the next units of a text that is REWRITTEN as it arrives -> the units of the result that have
+        become decidable, a uint16 array (the concatenation over all feeds: the whole text with every match replaced).
+        `replacements` as for Automaton.replace_host, the same at every feed.  A stream is fed through one entry only.
+        stats: an N.ReplaceStats to fill in, if wanted (this feed alone)."""
+        u = utf16(units)
+        n = int(u.size)
+        src = u if n else np.zeros(1, np.uint16)
+        r_units, off, n_repl = self._auto._replacements(replacements)
+        if cap is None:
+            cap = n + n // 4 + 64
+        st = stats if stats is not None else N.ReplaceStats()
+        while True:
+            out = np.empty(max(cap, 1), dtype=np.uint16)
+            n_out = ctypes.c_uint64(0)
+            rc = N.lib().acgpu_stream_replace_u16(self._h, _vp(src), n, 1 if final else 0, _vp(r_units), _vp(off), n_repl, _vp(out), cap,
+                                                  ctypes.byref(n_out), ctypes.byref(st))
+            if rc == N.E_OVERFLOW and int(n_out.value) > cap:  # nothing was committed: same feed, the room it asks for
+                cap = int(n_out.value)
+                continue
+            N.check(rc, "acgpu_stream_replace_u16")
+            return out[:n_out.value]
+
+    def replace_feed_utf8(self, data, replacements, final=False, stats=None, cap=None, replace_stats=None):
+        """acgpu_stream_replace_utf8: the next bytes of a UTF-8 text that is rewritten as it arrives (a chunk may end inside a
+        sequence) -> the bytes of the result that have become decidable.  `replacements` as for Automaton.replace_utf8, the same
+        at every feed.  Ill-formed input raises Utf8Error (.start: the global offset) and finishes the stream; what had been
+        withheld is not delivered.  stats: an N.Utf8StreamStats, replace_stats: an N.ReplaceStats to fill in, if wanted."""
+        buf = _utf8_bytes(data)
+        n = int(buf.size)
+        src = buf if n else np.zeros(1, np.uint8)
+        r_bytes, off, n_repl = self._auto._replacements_utf8(replacements)
+        if cap is None:
+            cap = n + n // 4 + 64
+        ust = stats if stats is not None else N.Utf8StreamStats()
+        st = replace_stats if replace_stats is not None else N.ReplaceStats()
+        while True:
+            out = np.empty(max(cap, 1), dtype=np.uint8)
+            n_out = ctypes.c_uint64(0)
+            rc = N.lib().acgpu_stream_replace_utf8(self._h, _vp(src), n, 1 if final else 0, _vp(r_bytes), _vp(off), n_repl, _vp(out), cap,
+                                                   ctypes.byref(n_out), ctypes.byref(ust), ctypes.byref(st))
+            if rc == N.E_OVERFLOW and int(n_out.value) > cap:  # nothing was committed: same feed, the room it asks for
+                cap = int(n_out.value)
+                continue
+            if rc == N.E_ENCODING:
+                raise Utf8Error(ust.first_bad)
+            N.check(rc, "acgpu_stream_replace_utf8")
+            return out[:n_out.value].tobytes()
+
     def close(self):
         h, self._h = getattr(self, "_h", None), None
         if h:
             N.lib().acgpu_stream_close(h)
 
     __del__ = close
+
+
+def _replace_stream(auto, chunks, feed, replacements, empty):
+    """The rewritten text of a stream of chunks, one piece of it per feed; closing the generator closes the stream, and no chunk is
+    read before the result of the one before it has been taken.  The stream is opened, and the families that replace refuses are
+    refused, at the first next()."""
+    st = Stream(auto)
+    try:
+        for chunk in chunks:
+            yield feed(st, chunk, replacements)
+        yield feed(st, empty, replacements, final=True)
+    finally:
+        st.close()
+
+
+def _str_feed():
+    """Stream.replace_feed as a feed of _replace_stream that yields str: a feed's output may end between the two units of a
+    surrogate pair (the position it ends at is one of the TEXT's, any unit), and two str that hold half a pair each do not
+    join to the pair -- the high surrogate waits for the next feed's output."""
+    held = [np.zeros(0, np.uint16)]
+
+    def feed(st, chunk, r, final=False):
+        out = np.concatenate([held[0], st.replace_feed(utf16(chunk), r, final=final)])
+        cut = out.size - 1 if not final and out.size and 0xD800 <= int(out[-1]) < 0xDC00 else out.size
+        held[0] = out[cut:]
+        return _to_str(out[:cut])
+    return feed
 
 
 def _byte_chunks(readable, chunk_bytes):
@@ -906,6 +982,20 @@ class StringSet(_BatchDecisions):
         r = replacement if isinstance(replacement, (bytes, bytearray)) else str(replacement)
         return _split_batch_utf8(*self._auto.replace_batch_utf8(datas if offsets is not None else _checked(datas), r, offsets=offsets)[:2])
 
+    def replace_readable(self, readable, replacement, chunk_chars=1 << 22):
+        """Not in the reference: replace() for a text that is read as it goes -- an object with read(n) -> str, or an iterable of
+        str / uint16 arrays, cut anywhere, inside a keyword too -> a generator of str whose concatenation is replace() of the
+        whole text; a feed yields what no later chunk can change.  Closing the generator closes the stream."""
+        return _replace_stream(self._auto, _chunks(readable, chunk_chars), _str_feed(), str(replacement), "")
+
+    def replace_utf8_readable(self, readable, replacement, chunk_bytes=1 << 22):
+        """Not in the reference: replace_utf8() for a text that is read as it goes -- a binary file object or an iterable of
+        bytes-like chunks, cut anywhere, inside a sequence too (see match_utf8_readable) -> a generator of bytes whose
+        concatenation is replace_utf8() of the whole text.  Utf8Error (.start: the global offset) if the text is ill-formed."""
+        r = replacement if isinstance(replacement, (bytes, bytearray)) else str(replacement)
+        feed = lambda st, chunk, r, final=False: st.replace_feed_utf8(chunk, r, final=final)
+        return _replace_stream(self._auto, _byte_chunks(readable, chunk_bytes), feed, r, b"")
+
     def find_all(self, haystack):
         """Convenience (not in the reference): the (n,2) int32 array of (start, end) records."""
         return self._auto.match_host(utf16(haystack), with_ids=False)
@@ -1058,6 +1148,19 @@ class StringMap(_BatchDecisions):
         if not isinstance(replacements, (bytes, bytearray)):
             replacements = self._replacements_for(replacements)
         return _split_batch_utf8(*self._auto.replace_batch_utf8(datas if offsets is not None else _checked(datas), replacements, offsets=offsets)[:2])
+
+    def replace_readable(self, readable, replacements=None, chunk_chars=1 << 22):
+        """Not in the reference: replace() for a text that is read as it goes -> a generator of str (see
+        StringSet.replace_readable); `replacements` under the rules of replace()."""
+        return _replace_stream(self._auto, _chunks(readable, chunk_chars), _str_feed(), self._replacements_for(replacements), "")
+
+    def replace_utf8_readable(self, readable, replacements=None, chunk_bytes=1 << 22):
+        """Not in the reference: replace_utf8() for a text that is read as it goes -> a generator of bytes (see
+        StringSet.replace_utf8_readable); `replacements` under the rules of replace_utf8()."""
+        if not isinstance(replacements, (bytes, bytearray)):
+            replacements = self._replacements_for(replacements)
+        feed = lambda st, chunk, r, final=False: st.replace_feed_utf8(chunk, r, final=final)
+        return _replace_stream(self._auto, _byte_chunks(readable, chunk_bytes), feed, replacements, b"")
 
     def _replacements_for(self, replacements):
         if replacements is None:

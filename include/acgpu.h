@@ -563,7 +563,8 @@ int acgpu_count_device(const acgpu_automaton *a, acgpu_shard *shard, uint64_t *d
  *              acgpu_match_u16 does and leaves `out` untouched.  Works on the NULL stream (STREAM RULE above), under the pool's lock.
  *  acgpu_replace_device : the shard must be a WHOLE text (own_begin == 0, own_end == n_units, text_begin == text_end == 1), else
  *              ACGPU_E_UNSUPPORTED: rewriting one shard of a sharded text needs the position up to which the rank before it has
- *              emitted handed on between the ranks, which is not built (nor is a multi-device or streaming form).  d_out:
+ *              emitted handed on between the ranks, which is not built (nor is a multi-device form; a text in chunks:
+ *              acgpu_stream_replace_u16 below).  d_out:
  *              device memory, 16-byte aligned, written directly (clipped at cap).  Everything is enqueued on `stream`; the call
  *              waits for it per piece -- for the piece's record count, as acgpu_count_device does, and for its output length -- and
  *              once at the end.
@@ -606,7 +607,8 @@ int acgpu_replace_device(const acgpu_automaton *a, acgpu_shard *shard, const uin
  * scan, one plan and one emit, no second pass over the output; the waits per piece are those of acgpu_replace_u16.
  * One acgpu_replace_u16 call per haystack inside the library instead, same results, where acgpu_match_batch_u16 falls back: a
  * dictionary that uses all 65536 units, and the word matchers over a table that is not fold-consistent.
- * No device-resident, multi-device or streaming form of this call exists.
+ * No device-resident or multi-device form of this call exists, nor a stream of batches (one long text in chunks:
+ * acgpu_stream_replace_u16 below).
  */
 int acgpu_replace_batch_u16(const acgpu_automaton *a, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks,
                             const uint16_t *repl_units, const uint64_t *repl_off, uint32_t n_repl, uint16_t *out, uint64_t cap,
@@ -732,8 +734,8 @@ int acgpu_match_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_
  * withholds more).  From there on everything counts bytes: the plan runs unchanged over byte records and a byte table, and the
  * byte form of the emit kernel writes 16 output bytes per lane from the caller's bytes on the device and the table, through
  * the two slabs of acgpu_replace_u16 ("replace_slab_units" counts bytes here).
- * Many short texts in one call: acgpu_replace_batch_utf8 below.  Not built: device-resident and multi-device forms, replace over
- * a stream (matching over one: acgpu_stream_feed_utf8); validating the replacements; the Java facade.
+ * Many short texts in one call: acgpu_replace_batch_utf8 below.  One long text in chunks: acgpu_stream_replace_utf8 below.
+ * Not built: device-resident and multi-device forms; validating the replacements; the Java facade.
  * ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
  */
 int acgpu_replace_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, const uint8_t *repl_bytes,
@@ -823,8 +825,8 @@ int acgpu_summary_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, con
  * a word matcher over a table that is not fold-consistent): the whole batch is validated first, so what is refused does not
  * depend on the route, then every haystack takes acgpu_replace_utf8's route with cap, the output position and the stats carried
  * across and the table uploaded once.
- * Not built: device-resident, multi-device and cursor forms, replace over a stream (matching over one: acgpu_stream_feed_utf8
- * below); validating the replacements; lossy decoding (U+FFFD); a one-launch form for tiny batches; the Java facade.  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
+ * Not built: device-resident, multi-device and cursor forms, a stream of batches (one long text in chunks:
+ * acgpu_stream_replace_utf8 below); validating the replacements; lossy decoding (U+FFFD); a one-launch form for tiny batches; the Java facade.  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
  */
 int acgpu_replace_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
                              const uint8_t *repl_bytes, const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap,
@@ -853,8 +855,9 @@ int acgpu_replace_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, con
  *  ACGPU_E_OVERFLOW : nothing was consumed; *n_out is the capacity to call the SAME feed again with (cap == 0, out == NULL: count).
  *  ACGPU_E_INVALID, before a device is touched: NULL s, n_out or base; bytes NULL with a byte to read; cap without out; a bad
  *           record_kind; a finished or detached stream; carried bytes + n_bytes >= 2^31; a stream that has been fed through
- *           acgpu_stream_feed -- and acgpu_stream_feed on a stream that has been fed bytes.  The first feed of either kind, a feed
- *           of length 0 included, decides which kind the stream is.
+ *           acgpu_stream_feed -- and acgpu_stream_feed on a stream that has been fed bytes.  The first feed of any kind, a feed
+ *           of length 0 included, decides which of the four kinds the stream is (match units, match bytes, and the two replace
+ *           kinds below); every other entry then returns ACGPU_E_INVALID.
  *  ACGPU_E_UNSUPPORTED : a stream switched to the pipelined form (acgpu_stream_set_pipelined, which in turn refuses a stream of bytes).
  *  no device : an empty feed that is not final, and an empty final feed on a stream that holds nothing: ACGPU_OK, no records.
  *  stats  : may be NULL.
@@ -881,6 +884,56 @@ typedef struct acgpu_utf8_stream_stats {
 int acgpu_stream_feed_utf8(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, int record_kind,
                            void *out, uint64_t cap, uint64_t *n_out, int64_t *base,
                            acgpu_utf8_stream_stats *stats /* may be NULL */);
+
+/*
+ * Stream replace: acgpu_replace_u16 / acgpu_replace_utf8 for a text that arrives in chunks of any size and may be longer than
+ * 2^31 elements -- a log file, a dump, a socket.  A stream opened with acgpu_stream_open is fed through ONE of these two entries;
+ * the first feed of any kind, an empty one included, decides what the stream is, and every other entry then returns
+ * ACGPU_E_INVALID.  "Element" below: a UTF-16 unit for acgpu_stream_replace_u16, a byte for acgpu_stream_replace_utf8.
+ *  result : let T be the concatenation of everything fed and r_0 .. r_{k-1} the Map records that acgpu_stream_feed /
+ *           acgpu_stream_feed_utf8 deliver for T over all feeds.  The concatenation of out[0 .. *n_out) over all feeds is
+ *             T[0:s_0] + repl[id_0] + T[e_0:s_1] + ... + T[e_{k-1}:]
+ *           whatever the chunking.  For a fold-consistent word table that is element for element what acgpu_replace_u16 /
+ *           acgpu_replace_utf8 return for T; over a word table that is not fold-consistent the STREAM's records are meant (the
+ *           Readable loops, which fold in every lookup), not those of the String loop.
+ *  a feed : delivers the rewrite of T[done_before : done_after).  done_after is the position before which no later record can
+ *           start, by the rule of the replace pieces applied to the feed's owned range (what acgpu_stream_feed would decide now):
+ *           LONGEST, WHOLEWORD, WWLONGEST: max(end of the owned range, end of the feed's last record); SHORTEST: max(last
+ *           record's end, done_before, end of the owned range - (max_keyword_len - 1)); final != 0: the end of the text -- for
+ *           bytes the end of the decoded bytes: a held prefix (acgpu_stream_feed_utf8, CUT SEQUENCES) is never delivered before
+ *           the bytes that complete it.  So without matches a feed that is not final withholds at most max_keyword_len + 1 units
+ *           (in bytes: at most 4 * (max_keyword_len + 2) + 3), a match that begins in the owned range is delivered whole, by that
+ *           feed, however many chunks it took to arrive, and final flushes everything.
+ *  repl_* / n_repl : the table of acgpu_replace_u16 / acgpu_replace_utf8.  The table of the feed that delivers a record applies;
+ *           pass the same one every time.
+ *  cap, *n_out : in elements.  ACGPU_E_OVERFLOW: nothing was committed, *n_out (and st->units_out) is the exact size of THIS
+ *           feed's output, out[0 .. cap) is unspecified and nothing at or beyond cap has been written; call the SAME feed again.
+ *  st     : may be NULL; this feed alone, st->units_out == *n_out.  ust (bytes): may be NULL, as acgpu_stream_feed_utf8 fills it.
+ *  ACGPU_E_UNSUPPORTED, before any device is touched: ACGPU_MODE_ALL; a pipelined stream; for bytes a dictionary with an unpaired
+ *           surrogate (see acgpu_replace_utf8).
+ *  ACGPU_E_INVALID, before any device is touched and with out, st and ust untouched: NULL s or n_out, data without a buffer, cap
+ *           without out, a finished or detached stream, a stream of another kind, a bad replacement table, n >= 2^31 or carried
+ *           + n >= 2^31.  Tickets in flight on the pool: ACGPU_E_INVALID as well (STREAM RULE above).
+ *  ACGPU_E_ENCODING (bytes): as acgpu_stream_feed_utf8 -- ust->first_bad is the GLOBAL offset, *n_out = 0, `out` is untouched,
+ *           the stream is finished and the pool usable.  What earlier feeds had withheld is NOT delivered: the output so far ends
+ *           where the last successful feed ended.
+ *  no device : an empty feed that is not final, and an empty final feed on a stream that holds nothing: ACGPU_OK, *n_out = 0.
+ * Device and lifetime as for acgpu_stream_feed.  Nothing of the stream lives on the device between two feeds (the table is
+ * uploaded per feed), so any other call on the automaton -- other streams and replace calls with other tables included -- may
+ * run between them.
+ * How it works: no kernel of its own.  A feed builds [carry | chunk] as the match feeds do, cuts it by their plan, and drives the
+ * pieces of the replace entries over the owned range (the reservoir, the ramp and the rescans; plan and emit; the slabs), scanned
+ * by the Readable rule; `done`, 64 bits and global, travels from feed to feed on the host.  The carry always reaches back to
+ * `done` (keep_from <= owned end - left context <= done); a feed that finds otherwise returns ACGPU_E_HIP.
+ * Not built: pipelined and reserved forms, ACGPU_MODE_ALL, device-resident and multi-device forms, the Java facade.
+ * ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
+ */
+int acgpu_stream_replace_u16(acgpu_stream *s, const uint16_t *units, uint64_t n_units, int final, const uint16_t *repl_units,
+                             const uint64_t *repl_off, uint32_t n_repl, uint16_t *out, uint64_t cap, uint64_t *n_out,
+                             acgpu_replace_stats *st /* may be NULL */);
+int acgpu_stream_replace_utf8(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, const uint8_t *repl_bytes,
+                              const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap, uint64_t *n_out,
+                              acgpu_utf8_stream_stats *ust /* may be NULL */, acgpu_replace_stats *st /* may be NULL */);
 
 /*
  * Synthetic haystack generator of the benchmark: unit i of the stream is

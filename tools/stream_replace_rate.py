@@ -1,0 +1,149 @@
+"""Development tool: what a caller pays who rewrites a UTF-8 text that is read in chunks, one box, one process --
+  stream : one Stream fed the chunks through Stream.replace_feed_utf8 (acgpu_stream_replace_utf8: carry + chunk copied, validated
+           + transcoded, the owned range scanned piece by piece, plan, byte emit, the feed's part of the result copied out);
+           `calls` beside it: the same feeds through the C entry alone, into one buffer that is large enough;
+  whole  : acgpu_replace_utf8 on the whole text in one call (what the chunked form is measured against; needs the text in one
+           piece and below 2^31 bytes);
+  host   : what the same caller does without the entry: codecs' incremental decoder per chunk -> utf16() -> Stream.feed -> the
+           records' unit positions mapped to bytes and the result spliced on the host (one table of byte offsets for the whole
+           text, built chunk by chunk from strings.utf8_unit_offsets, and one splice at the end -- a caller that has to write as
+           it goes pays more).
+All three on the 19.4 MB mixed text of tools/utf8_replace_rate.py and its automaton (WholeWordMatch over the README word list), one
+replacement for every keyword, the three results compared.  Chunks are cut at multiples of the chunk size, wherever that falls in
+a sequence.
+usage: stream_replace_rate.py [--log2 24] [--chunks 4194304,1048576,65536] [--reps 3] [--repl "[redacted]"]"""
+import argparse, codecs, ctypes, json, os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+from ahocorasick_amd import _native as N, synth
+from ahocorasick_amd.strings import Automaton, Stream, _to_str, utf16, utf8_unit_offsets
+from ahocorasick_amd.unicode_tables import default_word_chars
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--log2", type=int, default=24, help="bytes of the text before the non-ASCII tokens go in, about")
+ap.add_argument("--chunks", default="4194304,1048576,65536")
+ap.add_argument("--reps", type=int, default=3)
+ap.add_argument("--repl", default="[redacted]")
+args = ap.parse_args()
+
+EXTRA = ["Zürich", "naïve", "straße", "λόγος", "Москва", "東京", "데이터", "😀", "𝒜𝓃𝓈"]  # (tools/utf8_replace_rate.py)
+
+
+def mixed_text(n_bytes):
+    words = synth.readme_dictionary()
+    toks = _to_str(synth.readme_text(2006, n_bytes, words)).split(" ")
+    mixed = " ".join(t if i % 6 else t + " " + EXTRA[(i // 6) % len(EXTRA)] for i, t in enumerate(toks))
+    return words, mixed.encode("utf-8")
+
+
+def timed(fn, reps):
+    fn()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        out = fn()
+        ts.append(time.perf_counter() - t0)
+    return float(np.median(ts)) * 1e3, out
+
+
+def stream_bytes(a, data, chunk):
+    st = Stream(a)
+    try:
+        parts = [st.replace_feed_utf8(data[i:i + chunk], args.repl, final=i + chunk >= len(data)) for i in range(0, len(data), chunk)]
+    finally:
+        st.close()
+    return b"".join(parts)
+
+
+def stream_calls(a, data, chunk, out):
+    """the feeds of stream_bytes through acgpu_stream_replace_utf8 itself, back to back into `out` -> the bytes written"""
+    L, h = N.lib(), ctypes.c_void_p()
+    N.check(L.acgpu_stream_open(a.handle, ctypes.byref(h)), "acgpu_stream_open")
+    buf = np.frombuffer(data, np.uint8)
+    r_bytes, r_off, n_repl = a._replacements_utf8(args.repl)
+    vp = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+    total, m = 0, ctypes.c_uint64(0)
+    try:
+        for i in range(0, len(data), chunk):
+            piece, room = buf[i:i + chunk], out[total:]
+            N.check(L.acgpu_stream_replace_utf8(h, vp(piece), piece.size, 1 if i + chunk >= len(data) else 0, vp(r_bytes), vp(r_off), n_repl,
+                                                vp(room), room.size, ctypes.byref(m), None, None), "acgpu_stream_replace_utf8")
+            total += m.value
+    finally:
+        L.acgpu_stream_close(h)
+    return total
+
+
+def stream_host(a, data, chunk, cap, split):
+    """-> the rewritten bytes; split: a dict that receives the host steps' seconds"""
+    dec = codecs.getincrementaldecoder("utf-8")()
+    st = Stream(a, with_ids=True)
+    pages, offs, pos = [], [], 0
+    t = dict(decode=0.0, utf16=0.0, feed=0.0, splice=0.0)
+    try:
+        for i in range(0, len(data), chunk):
+            piece, final = data[i:i + chunk], i + chunk >= len(data)
+            t0 = time.perf_counter()
+            pending = len(dec.getstate()[0])
+            text = dec.decode(piece, final)
+            t1 = time.perf_counter()
+            units = utf16(text)
+            t2 = time.perf_counter()
+            pages.append(st.feed(units, final=final, cap=cap))
+            t3 = time.perf_counter()
+            consumed = pending + len(piece) - len(dec.getstate()[0])
+            offs.append(utf8_unit_offsets(data[pos:pos + consumed]) + pos)
+            pos += consumed
+            t4 = time.perf_counter()
+            t["decode"] += t1 - t0
+            t["utf16"] += t2 - t1
+            t["feed"] += t3 - t2
+            t["splice"] += t4 - t3
+    finally:
+        st.close()
+    t0 = time.perf_counter()
+    recs, off, b = np.concatenate(pages), np.concatenate(offs), np.frombuffer(data, np.uint8)
+    last = off[recs[:, 1] - 1]
+    lead = b[last]
+    start = off[recs[:, 0]]
+    end = last + 1 + (lead >= 0xC0) + (lead >= 0xE0) + (lead >= 0xF0)
+    # the splice: the text between the matches copied run by run, the one replacement between the runs
+    repl = args.repl.encode("utf-8")
+    gaps = np.concatenate([[0], end]), np.concatenate([start, [len(data)]])
+    parts = [None] * (2 * len(recs) + 1)
+    parts[0::2] = [data[s:e] for s, e in zip(gaps[0].tolist(), gaps[1].tolist())]
+    parts[1::2] = [repl] * len(recs)
+    out = b"".join(parts)
+    t["splice"] += time.perf_counter() - t0
+    split.update(t)
+    return out
+
+
+words, data = mixed_text(1 << args.log2)
+a = Automaton(N.MODE_WHOLEWORD, words + EXTRA[:7], True, word_chars=default_word_chars())
+n = len(data)
+n_recs = len(a.match_utf8(data, with_ids=True))
+want = a.replace_utf8(data, args.repl)[0].tobytes()
+cap_out = len(want) + 64
+ms_whole, (got, st) = timed(lambda: a.replace_utf8(data, args.repl, cap=cap_out), args.reps)
+assert got.tobytes() == want and st["n_records"] == n_recs
+print("text  %d bytes, %d records replaced by %r, %d bytes out" % (n, n_recs, args.repl, len(want)))
+print("whole          : %8.3f ms = %6.2f GB/s of input bytes (acgpu_replace_utf8, one call)" % (ms_whole, n / ms_whole / 1e6), flush=True)
+result = {"bytes": n, "records": n_recs, "bytes_out": len(want), "whole_ms": round(ms_whole, 3), "chunks": []}
+room = np.empty(cap_out, np.uint8)
+for chunk in [int(c) for c in args.chunks.split(",")]:
+    feeds = -(-n // chunk)
+    ms_stream, got = timed(lambda: stream_bytes(a, data, chunk), args.reps)
+    assert got == want, "replace_feed_utf8 and replace_utf8 differ"
+    ms_calls, total = timed(lambda: stream_calls(a, data, chunk, room), args.reps)
+    assert total == len(want) and room[:total].tobytes() == want
+    split = {}
+    ms_host, got = timed(lambda: stream_host(a, data, chunk, n_recs + 16, split), args.reps)
+    assert got == want, "the host route and replace_utf8 differ"
+    print("chunk %8d : stream %8.3f ms = %6.2f GB/s (%d feeds, %.3f ms a feed; calls alone %.3f ms) | host %8.3f ms = %6.2f GB/s (decode %.1f + utf-16 %.1f "
+          "+ offsets and splice %.1f ms around %.1f ms of Stream.feed) | host / stream = %.1f, stream / whole = %.2f" % (
+              chunk, ms_stream, n / ms_stream / 1e6, feeds, ms_stream / feeds, ms_calls, ms_host, n / ms_host / 1e6, split["decode"] * 1e3,
+              split["utf16"] * 1e3, split["splice"] * 1e3, split["feed"] * 1e3, ms_host / ms_stream, ms_stream / ms_whole), flush=True)
+    result["chunks"].append({"chunk_bytes": chunk, "feeds": feeds, "stream_ms": round(ms_stream, 3), "calls_ms": round(ms_calls, 3), "host_ms": round(ms_host, 3),
+                             "host_split_ms": {k: round(v * 1e3, 3) for k, v in split.items()}})
+print(json.dumps(result))
