@@ -228,7 +228,7 @@ struct DeviceState {
     PoolEvent replace_ev[4];                              // ... slab b emitted (b), slab b copied out (2 + b)
     PoolBuf replace_merged, replace_off;                  // acgpu_replace_batch_u16: a piece's records merged with its separators, the result's offsets (acgpu_replace_batch_utf8's too)
     PoolBuf summary;                                      // acgpu_summary_batch_u16: 24 bytes per haystack, {records, the first of them}
-    PoolBuf utf8_in, utf8_aux;                            // acgpu_match_utf8: the caller's bytes; {n_units, first_bad}, block sums, checkpoints (acgpu_utf8.hip)
+    PoolBuf utf8_in, utf8_aux;                            // the UTF-8 entries: the caller's bytes; {n_units, first_bad, tail}, block sums, checkpoints, a batch's byte offsets (Utf8Aux, acgpu_utf8.hip)
     CountCall *count = nullptr;                          // the counting call that runs on this pool (it holds mu), or nullptr
     double all_density = -1.0;                           // ALL: records per unit of this pool's last call (-1: none yet): k_ac_states or the tile kernel
     int fol_level = 0;                                   // k_longest_follow: 0 = run-up of 128 positions, 1 = of a whole segment (a call's chains had not merged), 2 = not for this pool's texts
@@ -401,13 +401,6 @@ int stage_utf8_text(DeviceState &d, const uint8_t *bytes, uint64_t n_bytes, hipS
 // checkpoints, n_units and n_bytes are those of the bytes before them (k_utf8_open_count).
 int stage_utf8_parts(DeviceState &d, const uint8_t *head, uint64_t n_head, const uint8_t *bytes, uint64_t n_rest, bool open, hipStream_t stream,
                      Utf8Text *out);
-// The mapping rule of acgpu_match_utf8 over cnt records of `cols` words on the device, in place (k_utf8_map), enqueued on
-// `stream`.  An all-ASCII text (no checkpoints) needs none: nothing is launched.
-int utf8_map_records(const Utf8Text &text, int32_t *d_recs, uint64_t cnt, uint32_t cols, hipStream_t stream);
-// *d_out = the first byte of the code point that holds unit `unit` < n_units, enqueued on `stream` (k_utf8_pos): a position
-// between the two units of a surrogate pair is rounded DOWN.  Not for an all-ASCII text (there the unit is the byte).
-int utf8_map_position(const Utf8Text &text, uint64_t unit, int64_t *d_out, hipStream_t stream);
-
 // A batch of UTF-8 haystacks staged as ONE shard (acgpu_utf8.hip): the caller's span copied once, every haystack validated on its
 // own, and transcoded into the text a batch call scans -- the haystacks' units with the separator unit behind every haystack.
 struct Utf8Batch {
@@ -429,16 +422,40 @@ int stage_utf8_batch(DeviceState &d, const HostTables &t, const uint8_t *bytes, 
 // cnt records of the scan over b's shard in d_recs -> records tagged with their haystack in d_out, positions in bytes relative to
 // the haystack (k_utf8_batch_tag; an all-ASCII batch: k_batch_tag, there a relative unit is a relative byte)
 int utf8_batch_tag(const Utf8Batch &b, const void *d_recs, uint64_t cnt, int record_kind, void *d_out, hipStream_t stream);
-// A piece's cnt records of the scan over b's shard, in place in d_recs: units of the shard -> bytes relative to the SPAN
-// (k_utf8_batch_map).  An all-ASCII batch is mapped too: a record of haystack h stands h separators behind its byte.
-int utf8_batch_map_records(const Utf8Batch &b, int32_t *d_recs, uint64_t cnt, uint32_t cols, hipStream_t stream);
-// *d_out = the span's byte for unit `unit` of b's shard, enqueued on `stream` (k_utf8_batch_pos): a separator, the last one
-// included, maps to the byte where the next haystack begins (n_bytes behind the last); any other unit to the first byte of the
-// code point that holds it, rounded DOWN as utf8_map_position does.
-int utf8_batch_map_position(const Utf8Batch &b, uint64_t unit, int64_t *d_out, hipStream_t stream);
+// cnt records of `cols` words of the scan over text's shard, in place in d_recs, enqueued on `stream` (k_utf8_batch_map): start ->
+// the first byte of the code point that holds unit start, end -> one past the last byte of the one that holds unit end - 1.
+// b == nullptr: the shard is the text's own units, bytes of the text; an all-ASCII text (no checkpoints) needs no map, nothing is
+// launched.  b given (text is b->text): units of the batch's shard -> bytes relative to the SPAN; an all-ASCII batch is mapped
+// too, a record of haystack h stands h separators behind its byte.
+int utf8_map_records(const Utf8Text &text, const Utf8Batch *b, int32_t *d_recs, uint64_t cnt, uint32_t cols, hipStream_t stream);
+// *d_out = the byte for unit `unit` of the shard, enqueued on `stream` (k_utf8_batch_pos).  b == nullptr: the first byte of the
+// code point that holds unit `unit` < n_units -- a position between the two units of a surrogate pair is rounded DOWN; not for
+// an all-ASCII text (there the unit is the byte).  b given: a byte of the span -- a separator, the last one included, maps to the
+// byte where the next haystack begins (n_bytes behind the last), as does a unit at or behind the shard's end; any other unit as
+// above.
+int utf8_map_position(const Utf8Text &text, const Utf8Batch *b, uint64_t unit, int64_t *d_out, hipStream_t stream);
 // The first records of n_entries summaries from units to bytes (k_summary_utf8_bytes): b given, the entries of b's haystacks;
 // else the entries -- one -- of `text` scanned as a text of its own.  Nothing is launched where there are no checkpoints.
 int utf8_summary_bytes(const Utf8Batch *b, const Utf8Text &text, acgpu_batch_summary *d_sum, uint32_t n_entries, hipStream_t stream);
+
+// The stats of the UTF-8 entries.  No argument: the preset, what an entry writes before it touches a device.  With the staged
+// text and the front end's rc: ACGPU_E_ENCODING -> where the decoder stops, no units, not ASCII; any other rc -> what was decoded.
+inline acgpu_utf8_stats utf8_stats(const Utf8Text *text = nullptr, int rc = ACGPU_OK) {
+    acgpu_utf8_stats st{};
+    st.first_bad = text ? text->first_bad : -1;
+    st.n_units = text && rc != ACGPU_E_ENCODING ? text->n_units : 0;
+    st.ascii = text ? rc != ACGPU_E_ENCODING && text->n_units == text->n_bytes : 1;
+    return st;
+}
+inline acgpu_utf8_batch_stats utf8_batch_stats(const Utf8Batch *b = nullptr, int rc = ACGPU_OK) {
+    acgpu_utf8_batch_stats st{};
+    const bool bad = b && rc == ACGPU_E_ENCODING;
+    st.first_bad = bad ? b->text.first_bad : -1;
+    st.bad_haystack = bad ? b->bad_haystack : 0;
+    st.n_units = b && !bad ? b->text.n_units : 0;
+    st.ascii = b ? !bad && b->text.n_units == b->text.n_bytes : 1;
+    return st;
+}
 
 // acgpu_replace_batch_utf8, behind a piece that emits the span's bytes [done, limit): the haystack boundaries whose output offset
 // that piece writes are [*j0, *j1) of boff (n_hay + 1 ascending byte offsets, boff[n_hay] = the span's bytes) -- those with

@@ -22,7 +22,7 @@
 //
 // acgpu_replace_batch_utf8 rewrites many UTF-8 texts as ONE span of bytes: stage_utf8_batch stages them as the device shard the
 // batch match call scans (a separator unit behind every haystack), and behind every piece its records become bytes of the span
-// (utf8_batch_map_records) and its boundary a byte of it (utf8_batch_map_position).  The span itself has NO separators, so nothing
+// (utf8_map_records with the batch) and its boundary a byte of it (utf8_map_position with the batch).  The span itself has NO separators, so nothing
 // is merged and nothing deleted: plan and emit run over the records alone, and the results lie back to back because the
 // haystacks do.  Where each result begins is computed behind the plan by k_replace_span_offsets, a lane per haystack boundary.
 #include <hip/hip_runtime.h>
@@ -581,8 +581,7 @@ int replace_piece(ReplaceCall &c, const void *hay, uint64_t base, const int32_t 
                                    reinterpret_cast<const int32_t *>(d.count_res.p), n_found, c.seps, (const int64_t *)pos, c.out_pos, c.d_out_off);
             HIP_TRY(hipGetLastError());
         }
-        if (map_bound && (rc = c.ub ? utf8_batch_map_position(*c.ub, bound, slot + 2, c.stream) : utf8_map_position(*c.u8, bound, slot + 2, c.stream)))
-            return rc;
+        if (map_bound && (rc = utf8_map_position(*c.u8, c.ub, bound, slot + 2, c.stream))) return rc;
         // (a piece without records reads the boundary alone)
         const size_t first = cnt ? 0 : 2, words = (map_bound ? 3 : 2) - first;
         HIP_TRY(hipMemcpyAsync(static_cast<int64_t *>(d.replace_pin.h) + first, slot + first, words * 8, hipMemcpyDeviceToHost, c.stream));
@@ -673,9 +672,7 @@ int replace_pieces(ReplaceCall &c, int64_t chain, bool whole, const PieceScan &s
         // UTF-8: the piece's records go from units to bytes where they lie (text relative: the shard is the whole text)
         // (a batch: span relative, and an all-ASCII one is mapped too)
         int32_t *own = reinterpret_cast<int32_t *>(d.count_res.p);
-        if (c.ub) rc = utf8_batch_map_records(*c.ub, own, cnt, ACGPU_REC_MAP / 4, c.stream);
-        else if (c.u8) rc = utf8_map_records(*c.u8, own, cnt, ACGPU_REC_MAP / 4, c.stream);
-        if (rc) break;
+        if (c.u8 && (rc = utf8_map_records(*c.u8, c.ub, own, cnt, ACGPU_REC_MAP / 4, c.stream))) break;
         uint64_t n_list = cnt;
         if (c.h_cat_off && (rc = merge_separators(c, base, p.pos, &recs, &n_list))) break;
         rc = replace_piece(c, hay, base, recs, n_list, cnt, p.pos, last && p.pos >= p.end); // (a whole text's one piece ends at p.end)
@@ -816,10 +813,7 @@ int acgpu_replace_utf8(const acgpu_automaton *ca, const uint8_t *bytes, uint64_t
     if (a->t.lone_surrogate) return ACGPU_E_UNSUPPORTED; // (a match inside a surrogate pair: records that overlap in bytes, see replace_limit)
     *n_out = 0;
     if (st) *st = acgpu_replace_stats{};
-    acgpu_utf8_stats us{};
-    us.first_bad = -1;
-    us.ascii = 1;
-    if (ust) *ust = us;
+    if (ust) *ust = utf8_stats();
     if (n_bytes == 0) return ACGPU_OK; // (nothing to decode and nothing to rewrite: no device needed)
     PoolCall call(a); // (no device: fails here, as acgpu_match_utf8 does, and out is untouched)
     if (call.rc) return call.rc;
@@ -827,10 +821,7 @@ int acgpu_replace_utf8(const acgpu_automaton *ca, const uint8_t *bytes, uint64_t
     if ((rc = call.idle())) return rc; // (the NULL stream: see the stream rule)
     Utf8Text text;
     rc = stage_utf8_text(d, bytes, n_bytes, d.call_stream, &text);
-    us.first_bad = text.first_bad;
-    us.n_units = rc == ACGPU_E_ENCODING ? 0 : text.n_units;
-    us.ascii = rc != ACGPU_E_ENCODING && text.n_units == n_bytes;
-    if (ust) *ust = us;
+    if (ust) *ust = utf8_stats(&text, rc);
     if (rc == ACGPU_E_ENCODING) return rc; // (the stream is idle: the pool is as usable as before the call)
     if (rc) return call.fail(rc);
     ReplaceCall c{a, d, d.call_stream};
@@ -860,10 +851,7 @@ int acgpu_replace_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, co
     *n_out = 0;
     out_offsets[0] = 0;
     if (st) *st = acgpu_replace_stats{};
-    acgpu_utf8_batch_stats us{};
-    us.first_bad = -1;
-    us.ascii = 1;
-    if (ust) *ust = us;
+    if (ust) *ust = utf8_batch_stats();
     if (plan.total == 0) { // (nothing to decode and nothing to rewrite: no device needed)
         for (uint32_t i = 0; i < n_haystacks; i++) out_offsets[i + 1] = 0;
         return ACGPU_OK;
@@ -875,17 +863,9 @@ int acgpu_replace_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, co
     // the whole batch is validated first, whichever way it is scanned, so that what is refused does not depend on the route
     Utf8Batch b;
     rc = stage_utf8_batch(d, t, bytes, offsets, n_haystacks, d.call_stream, &b, plan.per_haystack);
-    if (rc == ACGPU_E_ENCODING) { // (the stream is idle: the pool is as usable as before the call; out_offsets[1..] untouched)
-        us.first_bad = b.text.first_bad;
-        us.bad_haystack = b.bad_haystack;
-        us.ascii = 0;
-        if (ust) *ust = us;
-        return rc;
-    }
-    if (rc) return call.fail(rc);
-    us.n_units = b.text.n_units;
-    us.ascii = b.text.n_units == plan.total;
-    if (ust) *ust = us;
+    if (rc && rc != ACGPU_E_ENCODING) return call.fail(rc);
+    if (ust) *ust = utf8_batch_stats(&b, rc);
+    if (rc) return rc; // (ACGPU_E_ENCODING.  The stream is idle: the pool is as usable as before the call; out_offsets[1..] untouched)
     ReplaceCall c{a, d, d.call_stream};
     c.esz = 1;
     c.h_out = out;

@@ -27,6 +27,7 @@
 #include <cstring>
 #include <functional>
 #include <new>
+#include <optional>
 #include <thread>
 #include <vector>
 
@@ -57,6 +58,16 @@ FeedPlan plan_feed(const ShardRule &rule, uint64_t n_carry, uint64_t n_units, ui
     p.own_end = final ? p.total : std::max<uint64_t>(p.own_begin, p.total > rule.right ? p.total - rule.right : 0);
     p.keep_from = p.own_end - std::min<uint64_t>(rule.left, p.own_end);
     return p;
+}
+
+// a feed's shard: sh names the buffer (d_hay, n_units); its owned range, the text's ends -- carry_pos is the global position of
+// buffer unit 0 -- and where the chain enters it (a replace feed enters the chain itself: replace_feed)
+void plan_shard(acgpu_shard *sh, const FeedPlan &p, uint64_t carry_pos, bool final, int64_t chain_entry = 0) {
+    sh->own_begin = p.own_begin;
+    sh->own_end = p.own_end;
+    sh->text_begin = carry_pos == 0 ? 1 : 0;
+    sh->text_end = final ? 1 : 0;
+    sh->chain_entry = chain_entry;
 }
 
 // a few persistent host threads that copy pieces of a chunk (thread start-up costs as much as copying a megabyte)
@@ -241,11 +252,7 @@ int scan_slot(acgpu_stream *s, Slot &sl, int record_kind, void *out, uint64_t ca
             sh = acgpu_shard{};
             sh.d_hay = (const uint16_t *)s->b.dev[si].p;
             sh.n_units = p.total;
-            sh.own_begin = p.own_begin;
-            sh.own_end = p.own_end;
-            sh.text_begin = sl.carry_pos == 0 ? 1 : 0;
-            sh.text_end = sl.final ? 1 : 0;
-            sh.chain_entry = entry;
+            plan_shard(&sh, p, sl.carry_pos, sl.final, entry);
             rc = match_shard(a, *d, &sh, record_kind, s->b.out_dev.p, scap, &n, nullptr, nullptr, /*readable=*/true);
             if (rc == ACGPU_E_OVERFLOW) {
                 scap = n + n / 8 + 16;
@@ -448,6 +455,120 @@ int feed_pipelined(acgpu_stream *s, const uint16_t *units, uint64_t n_units, int
     return ACGPU_OK;
 }
 
+// ---- what the synchronous feeds share (each entry keeps its argument checks and its middle) ----
+
+// s->buf = [carry | chunk], p.total units
+int join_units(acgpu_stream *s, const uint16_t *units, uint64_t n_units, const FeedPlan &p) {
+    try {
+        s->buf.resize(p.total);
+    } catch (...) {
+        return ACGPU_E_NOMEM;
+    }
+    if (!s->carry.empty()) std::memcpy(s->buf.data(), s->carry.data(), s->carry.size() * 2);
+    if (n_units) std::memcpy(s->buf.data() + s->carry.size(), units, n_units * 2);
+    return ACGPU_OK;
+}
+
+// the commit of a feed of units; chain_exit: buffer relative
+void commit_units(acgpu_stream *s, const FeedPlan &p, int64_t chain_exit, bool final) {
+    s->own_from = s->carry_pos + p.own_end;
+    s->chain_entry = (int64_t)s->carry_pos + chain_exit;
+    s->carry.assign(s->buf.begin() + (ptrdiff_t)p.keep_from, s->buf.end());
+    s->carry_pos += p.keep_from;
+    s->finished = final;
+}
+
+// A feed of bytes between its entry's argument checks and its commit.
+struct ByteFeed {
+    const uint8_t *bytes;
+    uint64_t n_bytes;
+    bool final;
+    acgpu_utf8_stream_stats *stats; // the caller's, may be NULL
+    uint64_t n_c8 = 0, total_bytes = 0;
+    bool go = false;                // begin: there is something to decode, the pool is held and the buffer staged
+    std::optional<PoolCall> call;   // ... from begin to the entry's return
+    Utf8Text text;                  // [carried bytes | chunk] on the device
+    ShardRule rule{};
+    FeedPlan p{};
+    uint8_t at(const acgpu_stream *s, uint64_t i) const { return i < n_c8 ? s->carry8[i] : bytes[i - n_c8]; }
+};
+
+// The prologue of the byte feeds, from the stats' preset through plan_feed: returns what the entry returns where !f->go -- an
+// empty feed, a failure, or ill-formed bytes (ACGPU_E_ENCODING, which finishes the stream).
+int byte_feed_begin(acgpu_stream *s, int record_kind, ByteFeed *f) {
+    static_assert(sizeof(acgpu_utf8_stream_stats) == 24, "the layout include/acgpu.h promises");
+    f->n_c8 = s->carry8.size();
+    f->total_bytes = f->n_c8 + f->n_bytes;
+    acgpu_utf8_stream_stats st{};
+    st.first_bad = -1;
+    st.held = s->held;
+    st.ascii = 1;
+    for (uint8_t b : s->carry8) st.ascii &= b < 0x80u ? 1u : 0u;
+    if (f->stats) *f->stats = st;
+    if (f->n_bytes == 0 && !f->final) return ACGPU_OK; // (nothing new to decode or to decide: no device needed)
+    if (f->total_bytes == 0) {                         // (the end of a stream that holds nothing: neither)
+        s->finished = true;
+        return ACGPU_OK;
+    }
+    PoolCall &call = f->call.emplace(s->a);
+    if (call.rc) return call.rc;
+    int rc;
+    if ((rc = call.idle())) return rc; // (the call stream, waited for: see the stream rule)
+    rc = stage_utf8_parts(*call.d, s->carry8.data(), f->n_c8, f->bytes, f->n_bytes, /*open=*/!f->final, call.d->call_stream, &f->text);
+    if (rc == ACGPU_E_ENCODING) { // (the stream is idle: the pool is as usable as before the call; what a replace stream withheld stays undelivered)
+        st.first_bad = (int64_t)s->carry_byte + f->text.first_bad; // (in an earlier feed's bytes: the lead of the held prefix)
+        st.ascii = 0;
+        st.held = 0;
+        if (f->stats) *f->stats = st;
+        s->finished = true;
+        return rc;
+    }
+    if (rc) return call.fail(rc);
+    if (f->text.n_units < s->carry_units) return call.fail(ACGPU_E_HIP); // (never: the carried code points decode as they did)
+    st.n_units = f->text.n_units - s->carry_units;
+    st.ascii = f->text.n_units == f->total_bytes;
+    st.held = f->text.tail;
+    if (f->stats) *f->stats = st;
+    f->rule = shard_rule(s->a->t, record_kind, /*readable=*/true);
+    f->p = plan_feed(f->rule, s->carry_units, f->text.n_units - s->carry_units, s->own_from, s->carry_pos, f->final);
+    f->go = true;
+    return ACGPU_OK;
+}
+
+// The epilogue of the byte feeds: the byte to cut the carry at, the next carry, the commit.  chain_exit: buffer relative.
+// done: a replace stream's -- output exists for the buffer's bytes in front of *done, and the carry must reach back to it.
+int byte_feed_commit(acgpu_stream *s, const ByteFeed &f, int64_t chain_exit, const uint64_t *done = nullptr) {
+    // The cut is found on the host: back from the end of the decoded bytes over the leads -- every byte that is no continuation
+    // byte begins a code point of one unit, of two from F0 up -- until at least total - keep_from units are covered.  That is a
+    // code-point boundary; where keep_from names a low surrogate, one unit more is carried than the plan asks.
+    const uint64_t need = f.p.total - f.p.keep_from;
+    uint64_t cut = f.text.n_bytes, kept = 0;
+    while (kept < need && cut > 0) {
+        const uint8_t b = f.at(s, --cut);
+        if ((b & 0xc0u) != 0x80u) kept += b >= 0xf0u ? 2u : 1u;
+    }
+    // the cut is the first byte of the code point that holds unit keep_from, or of the one before it, and `done` is at least the
+    // byte that keep_from <= own_end - left rounds down to
+    if (done && !f.final && *done < cut) return ACGPU_E_HIP;
+    std::vector<uint8_t> next;
+    try {
+        next.resize(f.total_bytes - cut);
+    } catch (...) {
+        return ACGPU_E_NOMEM;
+    }
+    for (uint64_t i = cut; i < f.total_bytes; ++i) next[i - cut] = f.at(s, i);
+    if (done) s->done = s->carry_byte + *done;
+    s->own_from = s->carry_pos + f.p.own_end;
+    s->chain_entry = (int64_t)s->carry_pos + chain_exit;
+    s->carry8.swap(next);
+    s->held = f.text.tail;
+    s->carry_pos += f.p.total - kept;
+    s->carry_units = kept;
+    s->carry_byte += cut;
+    s->finished = f.final;
+    return ACGPU_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -517,142 +638,66 @@ int acgpu_stream_feed(acgpu_stream *s, const uint16_t *units, uint64_t n_units, 
     acgpu_automaton *a = s->a;
     const ShardRule rule = shard_rule(a->t, record_kind, /*readable=*/true);
     const FeedPlan p = plan_feed(rule, s->carry.size(), n_units, s->own_from, s->carry_pos, final != 0);
-    const uint64_t total = p.total, own_begin = p.own_begin, own_end = p.own_end, keep_from = p.keep_from;
-    if (total >= (1ull << 31)) return ACGPU_E_INVALID;
+    if (p.total >= (1ull << 31)) return ACGPU_E_INVALID;
     *n_out = 0;
     *base = (int64_t)s->carry_pos;
-    try {
-        s->buf.resize(total);
-    } catch (...) {
-        return ACGPU_E_NOMEM;
-    }
-    if (!s->carry.empty()) std::memcpy(s->buf.data(), s->carry.data(), s->carry.size() * 2);
-    if (n_units) std::memcpy(s->buf.data() + s->carry.size(), units, n_units * 2);
-    const int64_t entry = piece_entry(rule, s->chain_entry, (int64_t)s->carry_pos, own_begin);
-    int64_t chain_exit = piece_exit(rule, entry, own_end, nullptr, 0);
-    if (own_end > own_begin) {
+    int rc;
+    if ((rc = join_units(s, units, n_units, p))) return rc;
+    const int64_t entry = piece_entry(rule, s->chain_entry, (int64_t)s->carry_pos, p.own_begin);
+    int64_t chain_exit = piece_exit(rule, entry, p.own_end, nullptr, 0);
+    if (p.own_end > p.own_begin) {
         PoolCall call(a); // (the staging buffers are part of the per-device scratch pool)
         if (call.rc) return call.rc;
         DeviceState *d = call.d;
-        int rc;
         acgpu_shard sh;
         if ((rc = d->stage_out.ensure(cap * (uint64_t)record_kind + 16))) return rc;
-        if ((rc = stage_whole_text(*d, s->buf.data(), total, &sh))) return rc; // (the carry and the fed units: then the owned range, the ends and the chain)
-        sh.own_begin = own_begin;
-        sh.own_end = own_end;
-        sh.text_begin = s->carry_pos == 0 ? 1 : 0;
-        sh.text_end = final ? 1 : 0;
-        sh.chain_entry = entry;
+        if ((rc = stage_whole_text(*d, s->buf.data(), p.total, &sh))) return rc; // (the carry and the fed units: then the owned range, the ends and the chain)
+        plan_shard(&sh, p, s->carry_pos, final != 0, entry);
         rc = match_shard(a, *d, &sh, record_kind, d->stage_out.p, cap, n_out, nullptr, nullptr, /*readable=*/true);
         if (rc != ACGPU_OK) return rc; // ACGPU_E_OVERFLOW: nothing consumed, *n_out = capacity to retry with
         if (*n_out) HIP_TRY(hipMemcpy(out, d->stage_out.p, *n_out * (uint64_t)record_kind, hipMemcpyDeviceToHost));
-        chain_exit = piece_exit(rule, entry, own_end, &sh, *n_out);
+        chain_exit = piece_exit(rule, entry, p.own_end, &sh, *n_out);
     }
-    // commit
-    s->own_from = s->carry_pos + own_end;
-    s->chain_entry = (int64_t)s->carry_pos + chain_exit;
-    s->carry.assign(s->buf.begin() + (ptrdiff_t)keep_from, s->buf.end());
-    s->carry_pos += keep_from;
-    s->finished = final != 0;
+    commit_units(s, p, chain_exit, final != 0);
     return ACGPU_OK;
 }
 
 int acgpu_stream_feed_utf8(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, int record_kind, void *out, uint64_t cap,
                            uint64_t *n_out, int64_t *base, acgpu_utf8_stream_stats *stats) {
-    static_assert(sizeof(acgpu_utf8_stream_stats) == 24, "the layout include/acgpu.h promises");
     if (!s || !n_out || !base || (n_bytes && !bytes) || (cap && !out) || s->finished) return ACGPU_E_INVALID;
     if (record_kind != ACGPU_REC_SET && record_kind != ACGPU_REC_MAP) return ACGPU_E_INVALID;
     if (!s->a) return ACGPU_E_INVALID; // (its automaton has been freed)
     if (s->pipelined) return ACGPU_E_UNSUPPORTED;
     if (s->fed != acgpu_stream::kFedNone && s->fed != acgpu_stream::kFedBytes) return ACGPU_E_INVALID; // (a stream of another kind: units, or a replace stream)
-    const uint64_t n_c8 = s->carry8.size(), total_bytes = n_c8 + n_bytes;
-    if (n_bytes >= (1ull << 31) || total_bytes >= (1ull << 31)) return ACGPU_E_INVALID;
+    if (n_bytes >= (1ull << 31) || s->carry8.size() + n_bytes >= (1ull << 31)) return ACGPU_E_INVALID;
     s->fed = acgpu_stream::kFedBytes;
     *n_out = 0;
     *base = (int64_t)s->carry_byte;
-    acgpu_utf8_stream_stats st{};
-    st.first_bad = -1;
-    st.held = s->held;
-    st.ascii = 1;
-    for (uint8_t b : s->carry8) st.ascii &= b < 0x80u ? 1u : 0u;
-    if (stats) *stats = st;
-    if (n_bytes == 0 && !final) return ACGPU_OK; // (nothing new to decode or to decide: no device needed)
-    if (total_bytes == 0) {                      // (the end of a stream that holds nothing: neither)
-        s->finished = true;
-        return ACGPU_OK;
-    }
+    ByteFeed f{bytes, n_bytes, final != 0, stats};
+    int rc = byte_feed_begin(s, record_kind, &f);
+    if (!f.go) return rc;
     acgpu_automaton *a = s->a;
-    PoolCall call(a);
-    if (call.rc) return call.rc;
+    const PoolCall &call = *f.call;
     DeviceState &d = *call.d;
-    int rc;
-    if ((rc = call.idle())) return rc; // (the call stream, waited for: see the stream rule)
     const hipStream_t stream = d.call_stream;
-    Utf8Text text;
-    rc = stage_utf8_parts(d, s->carry8.data(), n_c8, bytes, n_bytes, /*open=*/!final, stream, &text);
-    if (rc == ACGPU_E_ENCODING) { // (the stream is idle: the pool is as usable as before the call)
-        st.first_bad = (int64_t)s->carry_byte + text.first_bad; // (in an earlier feed's bytes: the lead of the held prefix)
-        st.ascii = 0;
-        st.held = 0;
-        if (stats) *stats = st;
-        s->finished = true;
-        return rc;
-    }
-    if (rc) return call.fail(rc);
-    if (text.n_units < s->carry_units) return call.fail(ACGPU_E_HIP); // (never: the carried code points decode as they did)
-    st.n_units = text.n_units - s->carry_units;
-    st.ascii = text.n_units == total_bytes;
-    st.held = text.tail;
-    if (stats) *stats = st;
-    const ShardRule rule = shard_rule(a->t, record_kind, /*readable=*/true);
-    const FeedPlan p = plan_feed(rule, s->carry_units, text.n_units - s->carry_units, s->own_from, s->carry_pos, final != 0);
-    const int64_t entry = piece_entry(rule, s->chain_entry, (int64_t)s->carry_pos, p.own_begin);
-    int64_t chain_exit = piece_exit(rule, entry, p.own_end, nullptr, 0);
+    const FeedPlan &p = f.p;
+    const int64_t entry = piece_entry(f.rule, s->chain_entry, (int64_t)s->carry_pos, p.own_begin);
+    int64_t chain_exit = piece_exit(f.rule, entry, p.own_end, nullptr, 0);
     if (p.own_end > p.own_begin) {
         if ((rc = d.stage_out.ensure(cap * (uint64_t)record_kind + 16))) return call.fail(rc);
-        acgpu_shard &sh = text.shard; // (all the buffer's units: then the owned range, the ends and the chain)
-        sh.own_begin = p.own_begin;
-        sh.own_end = p.own_end;
-        sh.text_begin = s->carry_pos == 0 ? 1 : 0;
-        sh.text_end = final ? 1 : 0;
-        sh.chain_entry = entry;
+        acgpu_shard &sh = f.text.shard; // (all the buffer's units: then the owned range, the ends and the chain)
+        plan_shard(&sh, p, s->carry_pos, f.final, entry);
         rc = match_shard(a, d, &sh, record_kind, d.stage_out.p, cap, n_out, stream, nullptr, /*readable=*/true);
         if (rc != ACGPU_OK) return rc; // ACGPU_E_OVERFLOW: nothing consumed, *n_out = capacity to retry with
         if (*n_out) {
-            if ((rc = utf8_map_records(text, reinterpret_cast<int32_t *>(d.stage_out.p), *n_out, (uint32_t)record_kind / 4, stream))) return call.fail(rc);
+            if ((rc = utf8_map_records(f.text, nullptr, reinterpret_cast<int32_t *>(d.stage_out.p), *n_out, (uint32_t)record_kind / 4, stream))) return call.fail(rc);
             if (hipMemcpyAsync(out, d.stage_out.p, *n_out * (uint64_t)record_kind, hipMemcpyDeviceToHost, stream) != hipSuccess ||
                 hipStreamSynchronize(stream) != hipSuccess)
                 return call.fail(ACGPU_E_HIP);
         }
-        chain_exit = piece_exit(rule, entry, p.own_end, &sh, *n_out);
+        chain_exit = piece_exit(f.rule, entry, p.own_end, &sh, *n_out);
     }
-    // The byte to cut the carry at, on the host: back from the end of the decoded bytes over the leads -- every byte that is no
-    // continuation byte begins a code point of one unit, of two from F0 up -- until at least total - keep_from units are
-    // covered.  That is a code-point boundary; where keep_from names a low surrogate, one unit more is carried than the plan asks.
-    auto at = [&](uint64_t i) { return i < n_c8 ? s->carry8[i] : bytes[i - n_c8]; };
-    const uint64_t need = p.total - p.keep_from;
-    uint64_t cut = text.n_bytes, kept = 0;
-    while (kept < need && cut > 0) {
-        const uint8_t b = at(--cut);
-        if ((b & 0xc0u) != 0x80u) kept += b >= 0xf0u ? 2u : 1u;
-    }
-    std::vector<uint8_t> next;
-    try {
-        next.resize(total_bytes - cut);
-    } catch (...) {
-        return ACGPU_E_NOMEM;
-    }
-    for (uint64_t i = cut; i < total_bytes; ++i) next[i - cut] = at(i);
-    // commit
-    s->own_from = s->carry_pos + p.own_end;
-    s->chain_entry = (int64_t)s->carry_pos + chain_exit;
-    s->carry8.swap(next);
-    s->held = text.tail;
-    s->carry_pos += p.total - kept;
-    s->carry_units = kept;
-    s->carry_byte += cut;
-    s->finished = final != 0;
-    return ACGPU_OK;
+    return byte_feed_commit(s, f, chain_exit);
 }
 
 int acgpu_stream_replace_u16(acgpu_stream *s, const uint16_t *units, uint64_t n_units, int final, const uint16_t *repl_units,
@@ -676,13 +721,7 @@ int acgpu_stream_replace_u16(acgpu_stream *s, const uint16_t *units, uint64_t n_
         return ACGPU_OK;
     }
     if (s->done < s->carry_pos) return ACGPU_E_HIP; // (never: the carry invariant, checked at every commit)
-    try {
-        s->buf.resize(p.total);
-    } catch (...) {
-        return ACGPU_E_NOMEM;
-    }
-    if (!s->carry.empty()) std::memcpy(s->buf.data(), s->carry.data(), s->carry.size() * 2);
-    if (n_units) std::memcpy(s->buf.data() + s->carry.size(), units, n_units * 2);
+    if ((rc = join_units(s, units, n_units, p))) return rc;
     ReplaceFeed f;
     f.final = final != 0;
     f.done = s->done - s->carry_pos;
@@ -693,10 +732,7 @@ int acgpu_stream_replace_u16(acgpu_stream *s, const uint16_t *units, uint64_t n_
         DeviceState &d = *call.d;
         if ((rc = call.idle())) return rc; // (the call stream, waited for: see the stream rule)
         if ((rc = stage_whole_text(d, s->buf.data(), p.total, &f.shard))) return rc; // (the carry and the fed units: then the owned range and the ends)
-        f.shard.own_begin = p.own_begin;
-        f.shard.own_end = p.own_end;
-        f.shard.text_begin = s->carry_pos == 0 ? 1 : 0;
-        f.shard.text_end = final ? 1 : 0;
+        plan_shard(&f.shard, p, s->carry_pos, f.final);
         rc = replace_feed(a, d, &f, repl_units, repl_off, n_repl, out, cap, n_out);
         if (rc == ACGPU_OK || rc == ACGPU_E_OVERFLOW) {
             if (st) *st = f.st;
@@ -708,13 +744,8 @@ int acgpu_stream_replace_u16(acgpu_stream *s, const uint16_t *units, uint64_t n_
     }
     // the carry must reach back to `done`: keep_from <= own_end - left <= done by the limit rule
     if (!final && f.done < p.keep_from) return ACGPU_E_HIP;
-    // commit
     s->done = s->carry_pos + f.done;
-    s->own_from = s->carry_pos + p.own_end;
-    s->chain_entry = (int64_t)s->carry_pos + f.chain;
-    s->carry.assign(s->buf.begin() + (ptrdiff_t)p.keep_from, s->buf.end());
-    s->carry_pos += p.keep_from;
-    s->finished = final != 0;
+    commit_units(s, p, f.chain, f.final);
     return ACGPU_OK;
 }
 
@@ -728,95 +759,34 @@ int acgpu_stream_replace_utf8(acgpu_stream *s, const uint8_t *bytes, uint64_t n_
     int rc = replace_check_table(a, repl_bytes, repl_off, n_repl);
     if (rc) return rc;
     if (s->pipelined || a->t.lone_surrogate) return ACGPU_E_UNSUPPORTED; // (the latter: as acgpu_replace_utf8)
-    const uint64_t n_c8 = s->carry8.size(), total_bytes = n_c8 + n_bytes;
-    if (n_bytes >= (1ull << 31) || total_bytes >= (1ull << 31)) return ACGPU_E_INVALID;
+    if (n_bytes >= (1ull << 31) || s->carry8.size() + n_bytes >= (1ull << 31)) return ACGPU_E_INVALID;
     s->fed = acgpu_stream::kFedReplaceBytes;
     *n_out = 0;
     if (rst) *rst = acgpu_replace_stats{};
-    acgpu_utf8_stream_stats st{};
-    st.first_bad = -1;
-    st.held = s->held;
-    st.ascii = 1;
-    for (uint8_t b : s->carry8) st.ascii &= b < 0x80u ? 1u : 0u;
-    if (ust) *ust = st;
-    if (n_bytes == 0 && !final) return ACGPU_OK; // (nothing new to decode or to decide: no device needed)
-    if (total_bytes == 0) {                      // (the end of a stream that holds nothing: neither)
-        s->finished = true;
-        return ACGPU_OK;
-    }
-    if (s->done < s->carry_byte) return ACGPU_E_HIP; // (never: the carry invariant, checked at every commit)
-    PoolCall call(a);
-    if (call.rc) return call.rc;
-    DeviceState &d = *call.d;
-    if ((rc = call.idle())) return rc; // (the call stream, waited for: see the stream rule)
-    const hipStream_t stream = d.call_stream;
-    Utf8Text text;
-    rc = stage_utf8_parts(d, s->carry8.data(), n_c8, bytes, n_bytes, /*open=*/!final, stream, &text);
-    if (rc == ACGPU_E_ENCODING) { // (the stream is idle: the pool is as usable as before the call; what was withheld stays undelivered)
-        st.first_bad = (int64_t)s->carry_byte + text.first_bad;
-        st.ascii = 0;
-        st.held = 0;
-        if (ust) *ust = st;
-        s->finished = true;
-        return rc;
-    }
-    if (rc) return call.fail(rc);
-    if (text.n_units < s->carry_units) return call.fail(ACGPU_E_HIP); // (never: the carried code points decode as they did)
-    st.n_units = text.n_units - s->carry_units;
-    st.ascii = text.n_units == total_bytes;
-    st.held = text.tail;
-    if (ust) *ust = st;
-    const ShardRule rule = shard_rule(a->t, ACGPU_REC_MAP, /*readable=*/true);
-    const FeedPlan p = plan_feed(rule, s->carry_units, text.n_units - s->carry_units, s->own_from, s->carry_pos, final != 0);
+    ByteFeed bf{bytes, n_bytes, final != 0, ust};
+    rc = byte_feed_begin(s, ACGPU_REC_MAP, &bf);
+    if (!bf.go) return rc;
+    const PoolCall &call = *bf.call;
+    const FeedPlan &p = bf.p;
+    if (s->done < s->carry_byte) return call.fail(ACGPU_E_HIP); // (never: the carry invariant, checked at every commit)
     ReplaceFeed f;
-    f.u8 = &text;
-    f.final = final != 0;
+    f.u8 = &bf.text;
+    f.final = bf.final;
     f.done = s->done - s->carry_byte; // (bytes of the buffer)
     f.chain = s->chain_entry - (int64_t)s->carry_pos;
-    if (p.own_end > p.own_begin || (final && f.done < text.n_bytes)) {
-        f.shard = text.shard; // (all the buffer's units: then the owned range and the ends)
-        f.shard.own_begin = p.own_begin;
-        f.shard.own_end = p.own_end;
-        f.shard.text_begin = s->carry_pos == 0 ? 1 : 0;
-        f.shard.text_end = final ? 1 : 0;
-        rc = replace_feed(a, d, &f, repl_bytes, repl_off, n_repl, out, cap, n_out);
+    if (p.own_end > p.own_begin || (final && f.done < bf.text.n_bytes)) {
+        f.shard = bf.text.shard; // (all the buffer's units: then the owned range and the ends)
+        plan_shard(&f.shard, p, s->carry_pos, f.final);
+        rc = replace_feed(a, *call.d, &f, repl_bytes, repl_off, n_repl, out, cap, n_out);
         if (rc == ACGPU_OK || rc == ACGPU_E_OVERFLOW) {
             if (rst) *rst = f.st;
         }
         if (rc == ACGPU_E_OVERFLOW) return rc; // nothing committed: the same feed again, with *n_out bytes of room
         if (rc) return call.fail(rc);
     } else { // (nothing owned yet: the chain passes through)
-        f.chain = piece_exit(rule, piece_entry(rule, f.chain, 0, p.own_begin), p.own_end, nullptr, 0);
+        f.chain = piece_exit(bf.rule, piece_entry(bf.rule, f.chain, 0, p.own_begin), p.own_end, nullptr, 0);
     }
-    // the byte to cut the carry at: as acgpu_stream_feed_utf8 finds it
-    auto at = [&](uint64_t i) { return i < n_c8 ? s->carry8[i] : bytes[i - n_c8]; };
-    const uint64_t need = p.total - p.keep_from;
-    uint64_t cut = text.n_bytes, kept = 0;
-    while (kept < need && cut > 0) {
-        const uint8_t b = at(--cut);
-        if ((b & 0xc0u) != 0x80u) kept += b >= 0xf0u ? 2u : 1u;
-    }
-    // the carry must reach back to `done`: the cut is the first byte of the code point that holds unit keep_from, or of the one
-    // before it, and `done` is at least the byte that keep_from <= own_end - left rounds down to
-    if (!final && f.done < cut) return ACGPU_E_HIP;
-    std::vector<uint8_t> next;
-    try {
-        next.resize(total_bytes - cut);
-    } catch (...) {
-        return ACGPU_E_NOMEM;
-    }
-    for (uint64_t i = cut; i < total_bytes; ++i) next[i - cut] = at(i);
-    // commit
-    s->done = s->carry_byte + f.done;
-    s->own_from = s->carry_pos + p.own_end;
-    s->chain_entry = (int64_t)s->carry_pos + f.chain;
-    s->carry8.swap(next);
-    s->held = text.tail;
-    s->carry_pos += p.total - kept;
-    s->carry_units = kept;
-    s->carry_byte += cut;
-    s->finished = final != 0;
-    return ACGPU_OK;
+    return byte_feed_commit(s, bf, f.chain, &f.done);
 }
 
 } // extern "C"

@@ -187,13 +187,10 @@ int acgpu_summary_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, co
     BatchPlan plan; // (in bytes: bytes >= units, so bytes + haystacks < 2^31 bounds the text the scan sees)
     int rc = check_batch(t, reinterpret_cast<const uint16_t *>(bytes), offsets, n_haystacks, &plan);
     if (rc) return rc;
-    acgpu_utf8_batch_stats us{};
-    us.first_bad = -1;
-    us.ascii = 1;
     if (plan.total == 0) { // (nothing to decode and nothing to find: no device needed)
         for (uint32_t i = 0; i < n_haystacks; i++) out[i] = acgpu_batch_summary{0, -1, -1, -1, 0};
         if (st) *st = acgpu_summary_stats{};
-        if (stats) *stats = us;
+        if (stats) *stats = utf8_batch_stats();
         return ACGPU_OK;
     }
     PoolCall call(a); // (no device: fails here and out is untouched)
@@ -204,15 +201,10 @@ int acgpu_summary_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, co
     Utf8Batch b;
     rc = stage_utf8_batch(d, t, bytes, offsets, n_haystacks, stream, &b, plan.per_haystack);
     if (rc == ACGPU_E_ENCODING) { // (the stream is idle: the pool is as usable as before the call)
-        us.first_bad = b.text.first_bad;
-        us.bad_haystack = b.bad_haystack;
-        us.ascii = 0;
-        if (stats) *stats = us;
+        if (stats) *stats = utf8_batch_stats(&b, rc);
         return rc;
     }
     if (rc) return call.fail(rc);
-    us.n_units = b.text.n_units;
-    us.ascii = b.text.n_units == plan.total;
     const size_t sum_bytes = (size_t)n_haystacks * sizeof(acgpu_batch_summary);
     if ((rc = d.summary.ensure(sum_bytes))) return call.fail(rc);
     acgpu_batch_summary *d_sum = reinterpret_cast<acgpu_batch_summary *>(d.summary.p);
@@ -244,7 +236,7 @@ int acgpu_summary_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, co
         return call.fail(ACGPU_E_HIP);
     for (uint32_t i = 0; i < n_haystacks; i++) sum.n_matched += out[i].n_matches != 0;
     if (st) *st = sum;
-    if (stats) *stats = us;
+    if (stats) *stats = utf8_batch_stats(&b);
     return ACGPU_OK;
 }
 

@@ -8,20 +8,26 @@
 //   k_utf8_write : the same lanes again (after the host has seen n_units and that nothing offends): every lead byte decodes its
 //                  code point and stores one or two units, and the lane of a unit whose index is a multiple of 32 stores where
 //                  that unit's sequence begins -- the checkpoint table, 4 bytes per 32 units;
-//   k_utf8_map   : a lane per record: start and end - 1 go from units to bytes through the nearest checkpoint at or below them
-//                  and a walk of at most 31 units over the lead bytes.
-// For acgpu_replace_utf8 (acgpu_replace.hip) the front end and k_utf8_map are host functions of their own (stage_utf8_text,
-// utf8_map_records), and k_utf8_pos maps one unit position -- a piece's boundary -- the same way (utf8_map_position).
-// acgpu_match_batch_utf8 (here) and acgpu_summary_batch_utf8 (acgpu_summary.hip) are the batch form: stage_utf8_batch knows where
-// the haystacks begin -- k_utf8_batch_count validates every haystack on its own (lane_view's twelfth mask, the cuts),
-// k_utf8_batch_write stores the separator unit behind every haystack and every haystack's first unit (cat_off), the checkpoints
-// stay those of the buffer read as one text; k_utf8_batch_tag is k_batch_tag and k_utf8_map in one, k_summary_utf8_bytes maps
-// the summaries' first records.  For acgpu_replace_batch_utf8 (acgpu_replace.hip) k_utf8_batch_map rewrites a piece's records to
-// bytes of the SPAN (utf8_batch_map_records) and k_utf8_batch_pos maps a piece's boundary (utf8_batch_map_position).
-// acgpu_stream_feed_utf8 (acgpu_stream.hip) stages [carried bytes | chunk] through stage_utf8_parts; unless the feed is the last,
-// k_utf8_open_count validates with lane_view's OPEN form: a sequence that the buffer's end cuts is held back, not refused.
+//   k_utf8_batch_map : a lane per record: start and end - 1 go from units to bytes through the nearest checkpoint at or below
+//                  them and a walk of at most 31 units over the lead bytes (locate, batch_bytes).
+// Every form of the entry is these four with one more argument, and each piece of logic stands once:
+//  * count: count_units<BATCH, OPEN> is the body of k_utf8_count, k_utf8_batch_count (acgpu_match_batch_utf8 here,
+//    acgpu_summary_batch_utf8 in acgpu_summary.hip: every haystack validated on its own -- lane_view's twelfth mask, the cuts) and
+//    k_utf8_open_count (acgpu_stream_feed_utf8, acgpu_stream.hip: unless the feed is the last, a sequence that the buffer's end
+//    cuts is held back, not refused);
+//  * write: k_utf8_write and k_utf8_batch_write store through store_ascii16 and store_lead; the batch's writer also stores the
+//    separator unit behind every haystack and every haystack's first unit (cat_off), the checkpoints stay those of the buffer read
+//    as one text;
+//  * map: locate is the rule from a unit to its byte, batch_bytes a record's.  k_utf8_batch_map rewrites records in place -- a
+//    text's (utf8_map_records without a batch) or, for acgpu_replace_batch_utf8 (acgpu_replace.hip), a batch's to bytes of the
+//    SPAN; k_utf8_batch_pos maps one unit position, a piece's boundary, of either (utf8_map_position); k_utf8_batch_tag is
+//    k_batch_tag and the map in one, k_summary_utf8_bytes maps the summaries' first records;
+//  * staging: Utf8Aux lays out the device buffers and utf8_validate runs count, scan and the one wait for stage_utf8_parts (a
+//    text in two host parts: acgpu_stream_feed_utf8's carried bytes and chunk; stage_utf8_text is its one-part, closed case) and
+//    for stage_utf8_batch.
 // What a lane knows about its 16 bytes is eleven bit masks over a window of 24 bytes (the 4 before, its own, the 4 behind), built
-// by one function that both passes over the text share, so they cannot disagree about a count.
+// by one function that both passes over the text share, so they cannot disagree about a count; the two writers share the
+// decoder, so they cannot disagree about a unit.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -193,46 +199,40 @@ __device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t *total) {
     return base + inc - v;
 }
 
-// res[1]: the smallest offending offset (preset to ~0); block_sums[b] = the units of block b's bytes
-__global__ __launch_bounds__(kU8Threads) void k_utf8_count(const uint8_t *__restrict__ in, uint32_t n, uint32_t *__restrict__ block_sums,
-                                                           unsigned long long *__restrict__ res) {
+// The body of the three count kernels, one per form of lane_view.  res[1]: the smallest offending offset (preset to ~0);
+// block_sums[b] = the units of block b's bytes.  OPEN: res[2] (preset to 0) = the bytes at the buffer's end that begin a sequence
+// a later buffer has to complete, 1 .. 3, and the sums are those of the n - res[2] bytes before them.
+template <bool BATCH, bool OPEN>
+__device__ __forceinline__ void count_units(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ boff, uint32_t n_hay,
+                                            uint32_t *__restrict__ block_sums, unsigned long long *__restrict__ res) {
     const uint32_t o = (blockIdx.x * kU8Threads + threadIdx.x) * kU8Lane;
-    const LaneView v = lane_view<false>(in, n, o);
+    const LaneView v = lane_view<BATCH, OPEN>(in, n, o, boff, n_hay);
     // lanes are contiguous: the first lane of a wave that saw something holds the wave's smallest offset
     const unsigned long long offenders = __ballot(v.bad != 0);
     if (offenders && lane_id() == (uint32_t)__ffsll((long long)offenders) - 1)
         atomicMin(res + 1, (unsigned long long)(o - 4 + (uint32_t)__ffs((int)v.bad) - 1));
+    if constexpr (OPEN)
+        if (v.tail) res[2] = (unsigned long long)(n - (o - 4 + (uint32_t)__ffs((int)v.tail) - 1));
     uint32_t total;
     (void)block_scan(v.units(), &total);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
 }
 
-// k_utf8_count over a buffer whose text goes on behind it (lane_view's OPEN form).  res[2] (preset to 0): the bytes at the
-// buffer's end that begin a sequence a later buffer has to complete, 1 .. 3; the sums are those of the n - res[2] bytes before them
+__global__ __launch_bounds__(kU8Threads) void k_utf8_count(const uint8_t *__restrict__ in, uint32_t n, uint32_t *__restrict__ block_sums,
+                                                           unsigned long long *__restrict__ res) {
+    count_units<false, false>(in, n, nullptr, 0, block_sums, res);
+}
+
+// ... over a buffer whose text goes on behind it (lane_view's OPEN form)
 __global__ __launch_bounds__(kU8Threads) void k_utf8_open_count(const uint8_t *__restrict__ in, uint32_t n, uint32_t *__restrict__ block_sums,
                                                                 unsigned long long *__restrict__ res) {
-    const uint32_t o = (blockIdx.x * kU8Threads + threadIdx.x) * kU8Lane;
-    const LaneView v = lane_view<false, true>(in, n, o);
-    const unsigned long long offenders = __ballot(v.bad != 0);
-    if (offenders && lane_id() == (uint32_t)__ffsll((long long)offenders) - 1)
-        atomicMin(res + 1, (unsigned long long)(o - 4 + (uint32_t)__ffs((int)v.bad) - 1));
-    if (v.tail) res[2] = (unsigned long long)(n - (o - 4 + (uint32_t)__ffs((int)v.tail) - 1));
-    uint32_t total;
-    (void)block_scan(v.units(), &total);
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
+    count_units<false, true>(in, n, nullptr, 0, block_sums, res);
 }
 
-// k_utf8_count over a batch: the same sums (units of the buffer read as one text, separators not counted), the cut-aware validation
+// ... over a batch: the same sums (units of the buffer read as one text, separators not counted), the cut-aware validation
 __global__ __launch_bounds__(kU8Threads) void k_utf8_batch_count(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ boff,
                                                                  uint32_t n_hay, uint32_t *__restrict__ block_sums, unsigned long long *__restrict__ res) {
-    const uint32_t o = (blockIdx.x * kU8Threads + threadIdx.x) * kU8Lane;
-    const LaneView v = lane_view<true>(in, n, o, boff, n_hay);
-    const unsigned long long offenders = __ballot(v.bad != 0);
-    if (offenders && lane_id() == (uint32_t)__ffsll((long long)offenders) - 1)
-        atomicMin(res + 1, (unsigned long long)(o - 4 + (uint32_t)__ffs((int)v.bad) - 1));
-    uint32_t total;
-    (void)block_scan(v.units(), &total);
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
+    count_units<true, false>(in, n, boff, n_hay, block_sums, res);
 }
 
 // one workgroup, 256 block sums a round with a running carry (at most 2^19 blocks: 2048 rounds): block_sums become exclusive
@@ -250,6 +250,41 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_scan(uint32_t *__restrict__
     if (threadIdx.x == 0) res[0] = carry;
 }
 
+// The lane's 16 bytes are ASCII and `dst`, where their units go, is 16-byte aligned: two vector stores.  u: the index of the
+// first of them among the units that the checkpoints count, o: the lane's first byte.
+__device__ __forceinline__ void store_ascii16(const LaneView &v, uint16_t *__restrict__ dst, uint32_t u, uint32_t o, uint32_t *__restrict__ ckpt) {
+    uint32_t p[8];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t x = v.w[1 + j];
+        p[2 * j] = (x & 0xffu) | ((x & 0xff00u) << 8);
+        p[2 * j + 1] = ((x >> 16) & 0xffu) | ((x >> 8) & 0xff0000u);
+    }
+    uint4 *d4 = reinterpret_cast<uint4 *>(dst);
+    d4[0] = make_uint4(p[0], p[1], p[2], p[3]);
+    d4[1] = make_uint4(p[4], p[5], p[6], p[7]);
+    const uint32_t m = (0u - u) & 31u; // the first of the lane's units whose index is a multiple of 32
+    if (ckpt && m < kU8Lane) ckpt[(u + m) >> 5] = o + m;
+}
+
+// The lead at bit k of the lane's window, byte `pos` of the buffer: decodes its code point, stores its one or two units at dst,
+// and the checkpoint of whichever of them has an index that is a multiple of 32 -- u is the index of the first, among the units
+// that the checkpoints count.  Returns the number of units.
+__device__ __forceinline__ uint32_t store_lead(const LaneView &v, int k, uint32_t pos, uint16_t *__restrict__ dst, uint32_t u, uint32_t *__restrict__ ckpt) {
+    const uint32_t b0 = v.byte(k), b1 = v.byte(k + 1) & 0x3fu, b2 = v.byte(k + 2) & 0x3fu, b3 = v.byte(k + 3) & 0x3fu;
+    if (ckpt && (u & 31u) == 0) ckpt[u >> 5] = pos;
+    if (b0 < 0xf0u) {
+        const uint32_t cp = b0 < 0x80u ? b0 : (b0 < 0xe0u ? ((b0 & 0x1fu) << 6) | b1 : ((b0 & 0x0fu) << 12) | (b1 << 6) | b2);
+        dst[0] = (uint16_t)cp;
+        return 1;
+    }
+    const uint32_t cp = (((b0 & 0x07u) << 18) | (b1 << 12) | (b2 << 6) | b3) - 0x10000u;
+    dst[0] = (uint16_t)(0xd800u + (cp >> 10));
+    dst[1] = (uint16_t)(0xdc00u + (cp & 0x3ffu));
+    if (ckpt && ((u + 1) & 31u) == 0) ckpt[(u + 1) >> 5] = pos | kCkptLow;
+    return 2;
+}
+
 // The text is known to be well-formed.  out: n_units units; ckpt: one word per 32 units, or nullptr (an all-ASCII text needs none).
 __global__ __launch_bounds__(kU8Threads) void k_utf8_write(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ block_base,
                                                            uint16_t *__restrict__ out, uint32_t n_units, uint32_t *__restrict__ ckpt) {
@@ -260,39 +295,12 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_write(const uint8_t *__rest
     uint32_t u = block_base[blockIdx.x] + block_scan(cnt, &total);
     if (!cnt || u + cnt > n_units) return; // (the second: never, the counts are those of k_utf8_count)
     if (v.lead == kU8Own && !v.four && cnt == kU8Lane && ((v.w[1] | v.w[2] | v.w[3] | v.w[4]) & 0x80808080u) == 0 && (u & 7u) == 0) {
-        // 16 ASCII bytes whose units begin on a 16-byte boundary of the output: two vector stores
-        uint32_t p[8];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t x = v.w[1 + j];
-            p[2 * j] = (x & 0xffu) | ((x & 0xff00u) << 8);
-            p[2 * j + 1] = ((x >> 16) & 0xffu) | ((x >> 8) & 0xff0000u);
-        }
-        uint4 *dst = reinterpret_cast<uint4 *>(out + u);
-        dst[0] = make_uint4(p[0], p[1], p[2], p[3]);
-        dst[1] = make_uint4(p[4], p[5], p[6], p[7]);
-        const uint32_t m = (0u - u) & 31u; // the first of the lane's units whose index is a multiple of 32
-        if (ckpt && m < kU8Lane) ckpt[(u + m) >> 5] = o + m;
+        store_ascii16(v, out + u, u, o, ckpt); // (their units begin on a 16-byte boundary of the output)
         return;
     }
 #pragma unroll
-    for (int k = 4; k < 20; ++k) {
-        if (!((v.lead >> k) & 1u)) continue;
-        const uint32_t pos = o + (uint32_t)(k - 4);
-        const uint32_t b0 = v.byte(k), b1 = v.byte(k + 1) & 0x3fu, b2 = v.byte(k + 2) & 0x3fu, b3 = v.byte(k + 3) & 0x3fu;
-        if (ckpt && (u & 31u) == 0) ckpt[u >> 5] = pos;
-        if (b0 < 0xf0u) {
-            const uint32_t cp = b0 < 0x80u ? b0 : (b0 < 0xe0u ? ((b0 & 0x1fu) << 6) | b1 : ((b0 & 0x0fu) << 12) | (b1 << 6) | b2);
-            out[u] = (uint16_t)cp;
-            u += 1;
-        } else {
-            const uint32_t cp = (((b0 & 0x07u) << 18) | (b1 << 12) | (b2 << 6) | b3) - 0x10000u;
-            out[u] = (uint16_t)(0xd800u + (cp >> 10));
-            out[u + 1] = (uint16_t)(0xdc00u + (cp & 0x3ffu));
-            if (ckpt && ((u + 1) & 31u) == 0) ckpt[(u + 1) >> 5] = pos | kCkptLow;
-            u += 2;
-        }
-    }
+    for (int k = 4; k < 20; ++k)
+        if ((v.lead >> k) & 1u) u += store_lead(v, k, o + (uint32_t)(k - 4), out + u, u, ckpt);
 }
 
 // k_utf8_write over a batch that is known to be well-formed, haystack by haystack.  out: the text the scan sees, n_units + n_hay
@@ -300,7 +308,8 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_write(const uint8_t *__rest
 // goes to (units of bytes[0, p)) + h.  cat_off[j] = (units of bytes[0, boff[j])) + j, the first unit of haystack j in that text;
 // the lane that owns byte boff[j] stores it and the separator in front of it, and the lane of the buffer's last byte those of
 // the boundaries at the buffer's end (j = n_hay, and the empty haystacks at the end).  Checkpoints are indexed by the unit WITHOUT
-// separators -- the table of the buffer read as one text, which is well-formed because every haystack is.
+// separators -- the table of the buffer read as one text, which is well-formed because every haystack is: the two helpers store
+// to out + u + j - 1 and count checkpoints by u.
 __global__ __launch_bounds__(kU8Threads) void k_utf8_batch_write(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ block_base,
                                                                  uint16_t *__restrict__ out, uint32_t n_units, uint32_t *__restrict__ ckpt,
                                                                  const uint32_t *__restrict__ boff, uint32_t n_hay, uint32_t *__restrict__ cat_off,
@@ -315,18 +324,7 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_batch_write(const uint8_t *
     if (!(v.cut & kU8Own) && o + kU8Lane < n && v.lead == kU8Own && ((v.w[1] | v.w[2] | v.w[3] | v.w[4]) & 0x80808080u) == 0 &&
         ((u + j - 1u) & 7u) == 0) {
         // 16 ASCII bytes of one haystack (j >= 1: byte 0 is a cut) whose units begin on a 16-byte boundary of the output
-        uint32_t p[8];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint32_t x = v.w[1 + i];
-            p[2 * i] = (x & 0xffu) | ((x & 0xff00u) << 8);
-            p[2 * i + 1] = ((x >> 16) & 0xffu) | ((x >> 8) & 0xff0000u);
-        }
-        uint4 *dst = reinterpret_cast<uint4 *>(out + u + j - 1u);
-        dst[0] = make_uint4(p[0], p[1], p[2], p[3]);
-        dst[1] = make_uint4(p[4], p[5], p[6], p[7]);
-        const uint32_t m = (0u - u) & 31u;
-        if (ckpt && m < kU8Lane) ckpt[(u + m) >> 5] = o + m;
+        store_ascii16(v, out + u + j - 1u, u, o, ckpt);
         return;
     }
 #pragma unroll
@@ -339,21 +337,8 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_batch_write(const uint8_t *
                 ++j;
             }
         }
-        if (!((v.lead >> k) & 1u)) continue;
-        const uint32_t b0 = v.byte(k), b1 = v.byte(k + 1) & 0x3fu, b2 = v.byte(k + 2) & 0x3fu, b3 = v.byte(k + 3) & 0x3fu;
-        uint16_t *dst = out + u + j - 1u; // (j >= 1: a lead is a byte of a haystack, whose boundary has been met)
-        if (ckpt && (u & 31u) == 0) ckpt[u >> 5] = pos;
-        if (b0 < 0xf0u) {
-            const uint32_t cp = b0 < 0x80u ? b0 : (b0 < 0xe0u ? ((b0 & 0x1fu) << 6) | b1 : ((b0 & 0x0fu) << 12) | (b1 << 6) | b2);
-            dst[0] = (uint16_t)cp;
-            u += 1;
-        } else {
-            const uint32_t cp = (((b0 & 0x07u) << 18) | (b1 << 12) | (b2 << 6) | b3) - 0x10000u;
-            dst[0] = (uint16_t)(0xd800u + (cp >> 10));
-            dst[1] = (uint16_t)(0xdc00u + (cp & 0x3ffu));
-            if (ckpt && ((u + 1) & 31u) == 0) ckpt[(u + 1) >> 5] = pos | kCkptLow;
-            u += 2;
-        }
+        // (j >= 1: a lead is a byte of a haystack, whose boundary has been met)
+        if ((v.lead >> k) & 1u) u += store_lead(v, k, pos, out + u + j - 1u, u, ckpt);
     }
     if (o + kU8Lane >= n) { // the buffer's last lane: u = n_units, what is left are the boundaries at the buffer's end
         while (j <= n_hay) {
@@ -371,16 +356,17 @@ struct SeqPos {
     uint32_t p, u;
 };
 
-__device__ __forceinline__ SeqPos seek(const uint32_t *__restrict__ ckpt, uint32_t unit) {
-    const uint32_t c = ckpt[unit >> 5];
-    SeqPos s;
-    s.p = c & ~kCkptLow;
-    s.u = (unit & ~31u) - (c >> 31);
-    return s;
-}
-
-// moves s (s.u <= unit) to the sequence that holds `unit`; returns that sequence's length in bytes
-__device__ __forceinline__ uint32_t advance(const uint8_t *__restrict__ in, uint32_t n, SeqPos &s, uint32_t unit) {
+// THE rule from a unit to its byte: s = the sequence that holds `unit` -- s.p the first byte of its code point; of a low
+// surrogate, its pair's -- reached from the checkpoint at or below `unit` by a walk of at most 31 units over the lead bytes.
+// resume: s stands at a unit of the same 32 that is not behind `unit`, the walk goes on from there.  Returns the sequence's
+// length in bytes.
+__device__ __forceinline__ uint32_t locate(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ ckpt, uint32_t unit, SeqPos &s,
+                                           bool resume = false) {
+    if (!resume) {
+        const uint32_t c = ckpt[unit >> 5];
+        s.p = c & ~kCkptLow;
+        s.u = (unit & ~31u) - (c >> 31);
+    }
     uint32_t len = 1;
     while (s.p < n) {
         len = seq_len(in[s.p]);
@@ -392,44 +378,26 @@ __device__ __forceinline__ uint32_t advance(const uint8_t *__restrict__ in, uint
     return len;
 }
 
-// recs: cnt records of `cols` words in place: start -> the first byte of the code point that holds unit start, end -> one past the
-// last byte of the code point that holds unit end - 1 (a match has at least one unit)
-__global__ __launch_bounds__(kU8Threads) void k_utf8_map(int32_t *__restrict__ recs, uint64_t cnt, uint32_t cols, const uint8_t *__restrict__ in,
-                                                         uint32_t n, uint32_t n_units, const uint32_t *__restrict__ ckpt) {
-    const uint64_t i = (uint64_t)blockIdx.x * kU8Threads + threadIdx.x;
-    if (i >= cnt) return;
-    int32_t *r = recs + i * cols;
-    const uint32_t first = (uint32_t)r[0], last = (uint32_t)r[1] - 1u;
-    if (first > last || last >= n_units) return; // (never: the scan's records lie inside the text)
-    SeqPos s = seek(ckpt, first);
-    (void)advance(in, n, s, first);
-    r[0] = (int32_t)s.p;
-    if ((last >> 5) != (first >> 5)) s = seek(ckpt, last);
-    const uint32_t len = advance(in, n, s, last);
-    r[1] = (int32_t)(s.p + len);
-}
-
-// one lane: *out = the first byte of the code point that holds unit `unit` < n_units -- of a low surrogate, its pair's
-__global__ void k_utf8_pos(uint32_t unit, const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ ckpt, int64_t *__restrict__ out) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    SeqPos s = seek(ckpt, unit);
-    (void)advance(in, n, s, unit);
-    *out = (int64_t)s.p;
-}
-
-// The byte offsets, relative to haystack h's first byte, of a record of the scan over a batch's text: its units first .. last
-// WITHOUT separators (text unit - h) through the checkpoints, minus the haystack's byte offset (0 where boff is not given).
-__device__ __forceinline__ void batch_bytes(uint32_t first, uint32_t last, uint32_t hay_byte, const uint8_t *__restrict__ in, uint32_t n,
+// A record's units first .. last of the buffer read as one text (n_units of them, WITHOUT separators) -> *start, the first byte
+// of the code point that holds unit first, and *end, one past the last byte of the one that holds unit last (a match has at
+// least one unit), both minus `base`: a haystack's first byte, or 0.  A range that is none is left alone (never: the scan's
+// records lie inside the text).  ckpt == nullptr: an all-ASCII buffer, where a unit is its byte.
+__device__ __forceinline__ void batch_bytes(uint32_t first, uint32_t last, uint32_t base, const uint8_t *__restrict__ in, uint32_t n, uint32_t n_units,
                                             const uint32_t *__restrict__ ckpt, int32_t *start, int32_t *end) {
-    SeqPos s = seek(ckpt, first);
-    (void)advance(in, n, s, first);
-    *start = (int32_t)(s.p - hay_byte);
-    if ((last >> 5) != (first >> 5)) s = seek(ckpt, last);
-    const uint32_t len = advance(in, n, s, last);
-    *end = (int32_t)(s.p + len - hay_byte);
+    if (first > last || last >= n_units) return;
+    if (!ckpt) {
+        *start = (int32_t)(first - base);
+        *end = (int32_t)(last + 1u - base);
+        return;
+    }
+    SeqPos s;
+    (void)locate(in, n, ckpt, first, s);
+    *start = (int32_t)(s.p - base);
+    const uint32_t len = locate(in, n, ckpt, last, s, (last >> 5) == (first >> 5));
+    *end = (int32_t)(s.p + len - base);
 }
 
-// k_batch_tag and k_utf8_map in one, a lane per record: {start, end[, id]} in units of the batch's text -> {haystack, start, end[, id]}
+// k_batch_tag and the map in one, a lane per record: {start, end[, id]} in units of the batch's text -> {haystack, start, end[, id]}
 // in bytes of the haystack
 template <int REC>
 __global__ __launch_bounds__(kU8Threads) void k_utf8_batch_tag(const int32_t *__restrict__ recs, uint64_t cnt, const uint32_t *__restrict__ cat_off,
@@ -440,19 +408,18 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_batch_tag(const int32_t *__
     constexpr int W = REC / 4;
     const uint32_t start = (uint32_t)recs[i * W], end = (uint32_t)recs[i * W + 1];
     const uint32_t h = haystack_of(cat_off, n_hay, start);
-    const uint32_t first = start - h, last = end - 1u - h; // (no match holds a separator: both are units of haystack h)
     int32_t *o = out + i * (W + 1);
     o[0] = (int32_t)h;
     if (W == 3) o[3] = recs[i * W + 2];
-    if (first > last || last >= n_units) return; // (never: the scan's records lie inside the text)
-    batch_bytes(first, last, boff[h], in, n, ckpt, o + 1, o + 2);
+    // (no match holds a separator: both ends are units of haystack h)
+    batch_bytes(start - h, end - 1u - h, boff[h], in, n, n_units, ckpt, o + 1, o + 2);
 }
 
-// A lane per record of the scan over a batch's text, in place (acgpu_replace_batch_utf8): {start, end} in units of that text ->
-// bytes relative to the SPAN's first byte, not the haystack's -- plan and emit work on the span, which has no separators.  The
-// record's haystack h is also the number of separators in front of it, so its units in the buffer read as one text are
-// start - h .. end - 1 - h: with checkpoints they go through batch_bytes, and in an all-ASCII batch (ckpt == nullptr), where a
-// unit of the buffer is its byte, the shift is all there is to do -- but it is still to do.
+// A lane per record of `cols` words, in place: {start, end} in units of the scan's text -> bytes of the buffer.  The text is a
+// batch's (acgpu_replace_batch_utf8) or, n_hay == 0, the buffer's own units (acgpu_match_utf8 and what shares its map): the
+// record's haystack h -- 0 then -- is also the number of separators in front of it, so its units in the buffer read as one text
+// are start - h .. end - 1 - h.  The bytes are relative to the SPAN's first byte, not the haystack's -- plan and emit work on the
+// span, which has no separators.  In an all-ASCII batch the shift is all there is to do -- but it is still to do.
 __global__ __launch_bounds__(kU8Threads) void k_utf8_batch_map(int32_t *__restrict__ recs, uint64_t cnt, uint32_t cols, const uint32_t *__restrict__ cat_off,
                                                                uint32_t n_hay, const uint8_t *__restrict__ in, uint32_t n, uint32_t n_units,
                                                                const uint32_t *__restrict__ ckpt) {
@@ -460,43 +427,40 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_batch_map(int32_t *__restri
     if (i >= cnt) return;
     int32_t *r = recs + i * cols;
     const uint32_t start = (uint32_t)r[0], end = (uint32_t)r[1];
-    const uint32_t h = haystack_of(cat_off, n_hay, start);
-    const uint32_t first = start - h, last = end - 1u - h; // (no match holds a separator: both are units of haystack h)
-    if (first > last || last >= n_units) return;           // (never: the scan's records lie inside the text)
-    if (!ckpt) {
-        r[0] = (int32_t)first;
-        r[1] = (int32_t)(last + 1u);
-        return;
-    }
-    batch_bytes(first, last, 0u, in, n, ckpt, r, r + 1);
+    const uint32_t h = haystack_of(cat_off, n_hay, start); // (n_hay == 0: 0, and cat_off is not read)
+    batch_bytes(start - h, end - 1u - h, 0u, in, n, n_units, ckpt, r, r + 1);
 }
 
-// One lane: unit x of a batch's text -> *out, a byte of the span (a piece's boundary, see replace_limit in acgpu_replace.hip).
-// With h the haystack that holds x (cat_off[h] <= x < cat_off[h + 1]):
+// One lane: unit x of the scan's text -> *out, a byte of the buffer (a piece's boundary, see replace_limit in acgpu_replace.hip).
+// cat_off == nullptr: the text is the buffer's own units, x < n_units, and *out is the first byte of the code point that holds
+// unit x -- between the two units of a surrogate pair that rounds down.  Else the text is a batch's, and with h the haystack
+// that holds x (cat_off[h] <= x < cat_off[h + 1]):
 //  * x is haystack h's separator, the last unit before cat_off[h + 1]: the byte where haystack h + 1 begins, boff[h + 1] -- for
 //    the batch's last separator that is n, the span's end.  (The checkpoint table has no entry for a separator: x - h would be
 //    the first unit of the next haystack, or n_units.)  A unit at or behind the text's end maps to n as well;
-//  * any other unit: the first byte of the code point that holds unit x - h of the buffer read as one text -- between the two
-//    units of a surrogate pair that rounds down, as k_utf8_pos does; all-ASCII (ckpt == nullptr): the byte x - h itself.
+//  * any other unit: as above for unit x - h of the buffer read as one text; all-ASCII (ckpt == nullptr): the byte x - h itself.
 __global__ void k_utf8_batch_pos(uint32_t x, const uint32_t *__restrict__ cat_off, uint32_t n_hay, const uint32_t *__restrict__ boff,
                                  const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ ckpt, int64_t *__restrict__ out) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    if (x >= cat_off[n_hay]) {
-        *out = (int64_t)n;
-        return;
+    uint32_t u = x;
+    if (cat_off) {
+        if (x >= cat_off[n_hay]) {
+            *out = (int64_t)n;
+            return;
+        }
+        const uint32_t h = haystack_of(cat_off, n_hay, x);
+        if (x + 1u == cat_off[h + 1u]) {
+            *out = (int64_t)boff[h + 1u];
+            return;
+        }
+        u = x - h;
     }
-    const uint32_t h = haystack_of(cat_off, n_hay, x);
-    if (x + 1u == cat_off[h + 1u]) {
-        *out = (int64_t)boff[h + 1u];
-        return;
-    }
-    const uint32_t u = x - h;
     if (!ckpt) {
         *out = (int64_t)u;
         return;
     }
-    SeqPos s = seek(ckpt, u);
-    (void)advance(in, n, s, u);
+    SeqPos s;
+    (void)locate(in, n, ckpt, u, s);
     *out = (int64_t)s.p;
 }
 
@@ -511,45 +475,100 @@ __global__ __launch_bounds__(kU8Threads) void k_summary_utf8_bytes(acgpu_batch_s
     acgpu_batch_summary *e = sum + i;
     if (!e->n_matches || e->start < 0 || e->end <= e->start) return;
     const uint32_t unit0 = cat_off ? cat_off[i] - i : 0u, byte0 = cat_off ? boff[i] : 0u;
-    const uint32_t first = unit0 + (uint32_t)e->start, last = unit0 + (uint32_t)e->end - 1u;
-    if (last >= n_units) return; // (never)
-    batch_bytes(first, last, byte0, in, n, ckpt, &e->start, &e->end);
+    batch_bytes(unit0 + (uint32_t)e->start, unit0 + (uint32_t)e->end - 1u, byte0, in, n, n_units, ckpt, &e->start, &e->end);
 }
 
 } // namespace
 
 namespace acgpu {
 
-int utf8_map_records(const Utf8Text &text, int32_t *d_recs, uint64_t cnt, uint32_t cols, hipStream_t stream) {
-    if (!text.d_ckpt || !cnt) return ACGPU_OK;
-    hipLaunchKernelGGL(k_utf8_map, dim3((unsigned)((cnt + kU8Threads - 1) / kU8Threads)), dim3(kU8Threads), 0, stream, d_recs, cnt, cols,
-                       text.d_bytes, (uint32_t)text.n_bytes, (uint32_t)text.n_units, text.d_ckpt);
-    HIP_TRY(hipGetLastError());
-    return ACGPU_OK;
-}
-
-int utf8_map_position(const Utf8Text &text, uint64_t unit, int64_t *d_out, hipStream_t stream) {
-    if (!text.d_ckpt || unit >= text.n_units) return ACGPU_E_INVALID; // (a checkpoint is written for the text's units only)
-    hipLaunchKernelGGL(k_utf8_pos, dim3(1), dim3(1), 0, stream, (uint32_t)unit, text.d_bytes, (uint32_t)text.n_bytes, text.d_ckpt, d_out);
-    HIP_TRY(hipGetLastError());
-    return ACGPU_OK;
-}
-
-int utf8_batch_map_records(const Utf8Batch &b, int32_t *d_recs, uint64_t cnt, uint32_t cols, hipStream_t stream) {
-    if (!cnt) return ACGPU_OK;
+int utf8_map_records(const Utf8Text &text, const Utf8Batch *b, int32_t *d_recs, uint64_t cnt, uint32_t cols, hipStream_t stream) {
+    if (!cnt || (!b && !text.d_ckpt)) return ACGPU_OK; // (a batch is mapped also when it is all ASCII: its records stand behind separators)
     hipLaunchKernelGGL(k_utf8_batch_map, dim3((unsigned)((cnt + kU8Threads - 1) / kU8Threads)), dim3(kU8Threads), 0, stream, d_recs, cnt, cols,
-                       b.d_cat_off, b.n_haystacks, b.text.d_bytes, (uint32_t)b.text.n_bytes, (uint32_t)b.text.n_units, b.text.d_ckpt);
+                       b ? b->d_cat_off : nullptr, b ? b->n_haystacks : 0u, text.d_bytes, (uint32_t)text.n_bytes, (uint32_t)text.n_units, text.d_ckpt);
     HIP_TRY(hipGetLastError());
     return ACGPU_OK;
 }
 
-int utf8_batch_map_position(const Utf8Batch &b, uint64_t unit, int64_t *d_out, hipStream_t stream) {
-    if (!b.d_cat_off || !b.n_haystacks || unit >= (1ull << 32)) return ACGPU_E_INVALID;
-    hipLaunchKernelGGL(k_utf8_batch_pos, dim3(1), dim3(1), 0, stream, (uint32_t)unit, b.d_cat_off, b.n_haystacks, b.d_boff, b.text.d_bytes,
-                       (uint32_t)b.text.n_bytes, b.text.d_ckpt, d_out);
+int utf8_map_position(const Utf8Text &text, const Utf8Batch *b, uint64_t unit, int64_t *d_out, hipStream_t stream) {
+    if (b ? !b->d_cat_off || !b->n_haystacks || unit >= (1ull << 32)
+          : !text.d_ckpt || unit >= text.n_units) // (a checkpoint is written for the text's units only)
+        return ACGPU_E_INVALID;
+    hipLaunchKernelGGL(k_utf8_batch_pos, dim3(1), dim3(1), 0, stream, (uint32_t)unit, b ? b->d_cat_off : nullptr, b ? b->n_haystacks : 0u,
+                       b ? b->d_boff : nullptr, text.d_bytes, (uint32_t)text.n_bytes, text.d_ckpt, d_out);
     HIP_TRY(hipGetLastError());
     return ACGPU_OK;
 }
+
+namespace {
+
+// What the front ends keep on the device around the scan's text: the caller's bytes in d.utf8_in, with room for a lane's 16-byte
+// load and the 4 bytes behind it, and in d.utf8_aux, each part 64-byte aligned,
+//   [n_units, first_bad, tail | block sums | checkpoints, one per 32 units of a text that has at most n units | a batch's byte offsets]
+struct Utf8Aux {
+    uint32_t n = 0, n_blocks = 0; // the buffer's bytes, and its blocks of 4096
+    const uint8_t *in = nullptr;
+    unsigned long long *res = nullptr;
+    uint32_t *sums = nullptr, *ckpt = nullptr, *boff = nullptr; // boff: n_off words
+    int ensure(DeviceState &d, uint32_t n_bytes, size_t n_off = 0) {
+        auto up64 = [](size_t x) { return (x + 63) & ~(size_t)63; };
+        n = n_bytes;
+        n_blocks = (n + kU8Block - 1) / kU8Block;
+        const size_t sums_off = 64, ckpt_off = sums_off + up64((size_t)n_blocks * 4), boff_off = ckpt_off + up64(((size_t)n / 32 + 1) * 4);
+        int rc;
+        if ((rc = d.utf8_in.ensure((size_t)n + 64))) return rc;
+        if ((rc = d.utf8_aux.ensure(boff_off + n_off * 4))) return rc;
+        char *aux = (char *)d.utf8_aux.p;
+        in = reinterpret_cast<const uint8_t *>(d.utf8_in.p);
+        res = reinterpret_cast<unsigned long long *>(aux);
+        sums = reinterpret_cast<uint32_t *>(aux + sums_off);
+        ckpt = reinterpret_cast<uint32_t *>(aux + ckpt_off);
+        boff = reinterpret_cast<uint32_t *>(aux + boff_off);
+        return ACGPU_OK;
+    }
+};
+
+// The validate phase of both front ends, behind the copies: the result words preset, the count kernel of the buffer's form
+// (n_hay != 0: a batch with its offsets in x.boff; open: a text that goes on), the scan of the block sums, and the one wait this
+// front end adds -- the shard cannot be sized, nor the scan begun, before the text is known to be well-formed.  Fills in
+// n_units, first_bad, tail, n_bytes (the bytes before the held prefix), d_bytes and d_ckpt, the table the write kernel is to fill.
+int utf8_validate(const Utf8Aux &x, uint32_t n_hay, bool open, hipStream_t stream, Utf8Text *text) {
+    const dim3 grid(x.n_blocks), block(kU8Threads);
+    HIP_TRY(hipMemsetAsync(x.res, 0xff, 16, stream));
+    if (n_hay) {
+        hipLaunchKernelGGL(k_utf8_batch_count, grid, block, 0, stream, x.in, x.n, (const uint32_t *)x.boff, n_hay, x.sums, x.res);
+    } else if (open) {
+        HIP_TRY(hipMemsetAsync(x.res + 2, 0, 8, stream));
+        hipLaunchKernelGGL(k_utf8_open_count, grid, block, 0, stream, x.in, x.n, x.sums, x.res);
+    } else {
+        hipLaunchKernelGGL(k_utf8_count, grid, block, 0, stream, x.in, x.n, x.sums, x.res);
+    }
+    hipLaunchKernelGGL(k_utf8_scan, dim3(1), block, 0, stream, x.sums, x.n_blocks, x.res);
+    HIP_TRY(hipGetLastError());
+    unsigned long long h_res[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h_res, x.res, open ? 24 : 16, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream)); // (what the copies in front read on the host has been read by now, too)
+    text->n_units = h_res[0];
+    text->first_bad = (int64_t)h_res[1];
+    if (text->first_bad >= 0) return ACGPU_E_ENCODING;
+    if (h_res[2] > 3 || h_res[2] > x.n) return ACGPU_E_HIP; // (never: a held prefix is one to three bytes of the buffer)
+    text->tail = (uint32_t)h_res[2];
+    // the text that is transcoded: the bytes before the held prefix -- they end where a sequence ends, well-formed on their own
+    text->n_bytes = x.n - text->tail;
+    if (text->n_units > text->n_bytes) return ACGPU_E_HIP; // (never: a sequence has no more units than bytes)
+    text->d_bytes = x.in;
+    text->d_ckpt = text->n_units == text->n_bytes ? nullptr : x.ckpt; // (an all-ASCII text needs none)
+    return ACGPU_OK;
+}
+
+// the scan's text behind the write kernel: d.stage_hay as one shard, all of it owned, the text's begin and end, no chain
+void whole_shard(const DeviceState &d, uint64_t n_units, acgpu_shard *sh) {
+    sh->d_hay = (const uint16_t *)d.stage_hay.p;
+    sh->n_units = sh->own_end = n_units;
+    sh->text_begin = sh->text_end = 1;
+}
+
+} // namespace
 
 int stage_utf8_text(DeviceState &d, const uint8_t *bytes, uint64_t n_bytes, hipStream_t stream, Utf8Text *out) {
     return stage_utf8_parts(d, nullptr, 0, bytes, n_bytes, /*open=*/false, stream, out);
@@ -558,53 +577,20 @@ int stage_utf8_text(DeviceState &d, const uint8_t *bytes, uint64_t n_bytes, hipS
 int stage_utf8_parts(DeviceState &d, const uint8_t *head, uint64_t n_head, const uint8_t *bytes, uint64_t n_rest, bool open, hipStream_t stream,
                      Utf8Text *out) {
     *out = Utf8Text{};
-    const uint64_t n_bytes = n_head + n_rest;
-    out->n_bytes = n_bytes;
-    const uint32_t n = (uint32_t)n_bytes, n_blocks = (n + kU8Block - 1) / kU8Block;
-    // aux: [n_units, first_bad, tail | block sums | checkpoints, one per 32 units of a text that has at most n units]
-    const size_t sums_off = 64, ckpt_off = sums_off + (((size_t)n_blocks * 4 + 63) & ~(size_t)63);
+    out->n_bytes = n_head + n_rest;
+    Utf8Aux x;
     int rc;
-    if ((rc = d.utf8_in.ensure((size_t)n + 64))) return rc; // (a lane's 16-byte load, and 4 bytes behind it)
-    if ((rc = d.utf8_aux.ensure(ckpt_off + ((size_t)n / 32 + 1) * 4))) return rc;
-    const uint8_t *d_in = reinterpret_cast<const uint8_t *>(d.utf8_in.p);
-    unsigned long long *d_res = reinterpret_cast<unsigned long long *>(d.utf8_aux.p);
-    uint32_t *d_sums = reinterpret_cast<uint32_t *>((char *)d.utf8_aux.p + sums_off);
-    uint32_t *d_ckpt = reinterpret_cast<uint32_t *>((char *)d.utf8_aux.p + ckpt_off);
+    if ((rc = x.ensure(d, (uint32_t)(n_head + n_rest)))) return rc;
     if (n_head) HIP_TRY(hipMemcpyAsync(d.utf8_in.p, head, n_head, hipMemcpyHostToDevice, stream));
     if (n_rest) HIP_TRY(hipMemcpyAsync((char *)d.utf8_in.p + n_head, bytes, n_rest, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemsetAsync(d_res, 0xff, 16, stream));
-    if (open) {
-        HIP_TRY(hipMemsetAsync(d_res + 2, 0, 8, stream));
-        hipLaunchKernelGGL(k_utf8_open_count, dim3(n_blocks), dim3(kU8Threads), 0, stream, d_in, n, d_sums, d_res);
-    } else {
-        hipLaunchKernelGGL(k_utf8_count, dim3(n_blocks), dim3(kU8Threads), 0, stream, d_in, n, d_sums, d_res);
-    }
-    hipLaunchKernelGGL(k_utf8_scan, dim3(1), dim3(kU8Threads), 0, stream, d_sums, n_blocks, d_res);
-    HIP_TRY(hipGetLastError());
-    // the one wait this front end adds: the shard cannot be sized, nor the scan begun, before the text is known to be well-formed
-    unsigned long long h_res[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h_res, d_res, open ? 24 : 16, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    out->n_units = h_res[0];
-    out->first_bad = (int64_t)h_res[1];
-    if (out->first_bad >= 0) return ACGPU_E_ENCODING;
-    if (h_res[2] > 3 || h_res[2] > n) return ACGPU_E_HIP; // (never: a held prefix is one to three bytes of the buffer)
-    out->tail = (uint32_t)h_res[2];
-    // the text that is transcoded: the bytes before the held prefix -- they end where a sequence ends, well-formed on their own
-    const uint32_t n_text = n - out->tail, n_text_blocks = (n_text + kU8Block - 1) / kU8Block;
-    out->n_bytes = n_text;
-    if (out->n_units > n_text) return ACGPU_E_HIP; // (never: a sequence has no more units than bytes)
-    const bool ascii = out->n_units == n_text;
+    if ((rc = utf8_validate(x, 0, open, stream, out))) return rc;
     if ((rc = d.stage_hay.ensure(out->n_units * 2 + 16))) return rc;
+    const uint32_t n_text = (uint32_t)out->n_bytes, n_text_blocks = (n_text + kU8Block - 1) / kU8Block;
     if (n_text_blocks) // (a buffer that is a held prefix and nothing else has no unit to write)
-        hipLaunchKernelGGL(k_utf8_write, dim3(n_text_blocks), dim3(kU8Threads), 0, stream, d_in, n_text, (const uint32_t *)d_sums,
-                           reinterpret_cast<uint16_t *>(d.stage_hay.p), (uint32_t)out->n_units, ascii ? nullptr : d_ckpt);
+        hipLaunchKernelGGL(k_utf8_write, dim3(n_text_blocks), dim3(kU8Threads), 0, stream, x.in, n_text, (const uint32_t *)x.sums,
+                           reinterpret_cast<uint16_t *>(d.stage_hay.p), (uint32_t)out->n_units, out->d_ckpt ? x.ckpt : nullptr);
     HIP_TRY(hipGetLastError());
-    out->shard.d_hay = (const uint16_t *)d.stage_hay.p;
-    out->shard.n_units = out->shard.own_end = out->n_units;
-    out->shard.text_begin = out->shard.text_end = 1;
-    out->d_bytes = d_in;
-    out->d_ckpt = ascii ? nullptr : d_ckpt;
+    whole_shard(d, out->n_units, &out->shard);
     return ACGPU_OK;
 }
 
@@ -612,15 +598,12 @@ int stage_utf8_batch(DeviceState &d, const HostTables &t, const uint8_t *bytes, 
                      Utf8Batch *out, bool validate_only) {
     *out = Utf8Batch{};
     out->n_haystacks = n_hay;
-    const uint8_t *span = bytes + offsets[0];
-    const uint32_t n = (uint32_t)(offsets[n_hay] - offsets[0]), n_blocks = (n + kU8Block - 1) / kU8Block;
+    const uint32_t n = (uint32_t)(offsets[n_hay] - offsets[0]);
     out->text.n_bytes = n;
-    // aux: stage_utf8_text's [n_units, first_bad | block sums | checkpoints], and behind them the byte offsets
-    const size_t sums_off = 64, ckpt_off = sums_off + (((size_t)n_blocks * 4 + 63) & ~(size_t)63);
-    const size_t boff_off = ckpt_off + ((((size_t)n / 32 + 1) * 4 + 63) & ~(size_t)63), off_bytes = ((size_t)n_hay + 1) * 4;
+    const size_t off_bytes = ((size_t)n_hay + 1) * 4;
+    Utf8Aux x;
     int rc;
-    if ((rc = d.utf8_in.ensure((size_t)n + 64))) return rc;
-    if ((rc = d.utf8_aux.ensure(boff_off + off_bytes))) return rc;
+    if ((rc = x.ensure(d, n, (size_t)n_hay + 1))) return rc;
     if ((rc = d.batch_off.ensure(off_bytes + 16))) return rc;
     std::vector<uint32_t> &h_boff = out->h_boff;
     try {
@@ -629,46 +612,30 @@ int stage_utf8_batch(DeviceState &d, const HostTables &t, const uint8_t *bytes, 
         return ACGPU_E_NOMEM;
     }
     for (uint32_t i = 0; i <= n_hay; i++) h_boff[i] = (uint32_t)(offsets[i] - offsets[0]);
-    const uint8_t *d_in = reinterpret_cast<const uint8_t *>(d.utf8_in.p);
-    unsigned long long *d_res = reinterpret_cast<unsigned long long *>(d.utf8_aux.p);
-    uint32_t *d_sums = reinterpret_cast<uint32_t *>((char *)d.utf8_aux.p + sums_off);
-    uint32_t *d_ckpt = reinterpret_cast<uint32_t *>((char *)d.utf8_aux.p + ckpt_off);
-    uint32_t *d_boff = reinterpret_cast<uint32_t *>((char *)d.utf8_aux.p + boff_off);
-    uint32_t *d_cat_off = reinterpret_cast<uint32_t *>(d.batch_off.p);
-    HIP_TRY(hipMemcpyAsync(d.utf8_in.p, span, n, hipMemcpyHostToDevice, stream)); // the caller's span as it lies: one copy
-    HIP_TRY(hipMemcpyAsync(d_boff, h_boff.data(), off_bytes, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemsetAsync(d_res, 0xff, 16, stream));
-    hipLaunchKernelGGL(k_utf8_batch_count, dim3(n_blocks), dim3(kU8Threads), 0, stream, d_in, n, (const uint32_t *)d_boff, n_hay, d_sums, d_res);
-    hipLaunchKernelGGL(k_utf8_scan, dim3(1), dim3(kU8Threads), 0, stream, d_sums, n_blocks, d_res);
-    HIP_TRY(hipGetLastError());
-    unsigned long long h_res[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(h_res, d_res, 16, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream)); // (h_boff has been read by now, too)
-    out->text.n_units = h_res[0];
-    out->text.first_bad = (int64_t)h_res[1];
-    if (out->text.first_bad >= 0) {
+    HIP_TRY(hipMemcpyAsync(d.utf8_in.p, bytes + offsets[0], n, hipMemcpyHostToDevice, stream)); // the caller's span as it lies: one copy
+    HIP_TRY(hipMemcpyAsync(x.boff, h_boff.data(), off_bytes, hipMemcpyHostToDevice, stream));
+    rc = utf8_validate(x, n_hay, /*open=*/false, stream, &out->text);
+    if (rc == ACGPU_E_ENCODING) {
         // the haystack that holds byte p: the LAST j < n_hay with offset <= p (of several at one byte all but the last are empty)
-        const uint32_t p = (uint32_t)h_res[1];
+        const uint32_t p = (uint32_t)out->text.first_bad;
         const uint32_t j = (uint32_t)(std::upper_bound(h_boff.begin(), h_boff.begin() + n_hay, p) - h_boff.begin()) - 1u;
         out->bad_haystack = j;
         out->text.first_bad = (int64_t)(p - h_boff[j]);
-        return ACGPU_E_ENCODING;
     }
-    if (out->text.n_units > n) return ACGPU_E_HIP; // (never: a sequence has no more units than bytes)
-    const bool ascii = out->text.n_units == n;
-    out->text.d_bytes = d_in;
-    out->d_boff = d_boff;
-    if (validate_only) return ACGPU_OK;
+    if (rc) return rc;
+    out->d_boff = x.boff;
+    if (validate_only) {
+        out->text.d_ckpt = nullptr; // (no table is written)
+        return ACGPU_OK;
+    }
     const uint64_t cat = out->text.n_units + n_hay;
+    uint32_t *d_cat_off = reinterpret_cast<uint32_t *>(d.batch_off.p);
     if ((rc = d.stage_hay.ensure(cat * 2 + 16))) return rc;
-    hipLaunchKernelGGL(k_utf8_batch_write, dim3(n_blocks), dim3(kU8Threads), 0, stream, d_in, n, (const uint32_t *)d_sums,
-                       reinterpret_cast<uint16_t *>(d.stage_hay.p), (uint32_t)out->text.n_units, ascii ? nullptr : d_ckpt, (const uint32_t *)d_boff,
-                       n_hay, d_cat_off, (uint32_t)(uint16_t)t.sep_unit);
+    hipLaunchKernelGGL(k_utf8_batch_write, dim3(x.n_blocks), dim3(kU8Threads), 0, stream, x.in, n, (const uint32_t *)x.sums,
+                       reinterpret_cast<uint16_t *>(d.stage_hay.p), (uint32_t)out->text.n_units, out->text.d_ckpt ? x.ckpt : nullptr,
+                       (const uint32_t *)x.boff, n_hay, d_cat_off, (uint32_t)(uint16_t)t.sep_unit);
     HIP_TRY(hipGetLastError());
-    out->text.shard.d_hay = (const uint16_t *)d.stage_hay.p;
-    out->text.shard.n_units = out->text.shard.own_end = cat;
-    out->text.shard.text_begin = out->text.shard.text_end = 1;
-    out->text.d_ckpt = ascii ? nullptr : d_ckpt;
+    whole_shard(d, cat, &out->text.shard);
     out->d_cat_off = d_cat_off;
     return ACGPU_OK;
 }
@@ -709,10 +676,7 @@ int acgpu_match_utf8(const acgpu_automaton *ca, const uint8_t *bytes, uint64_t n
     if (record_kind != ACGPU_REC_SET && record_kind != ACGPU_REC_MAP) return ACGPU_E_INVALID;
     if (n_bytes >= (1ull << 31)) return ACGPU_E_INVALID;
     *n_out = 0;
-    acgpu_utf8_stats st{};
-    st.first_bad = -1;
-    st.ascii = 1;
-    if (stats) *stats = st;
+    if (stats) *stats = utf8_stats();
     if (n_bytes == 0) return ACGPU_OK; // (nothing to decode and nothing to find: no device needed)
     acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
     PoolCall call(a);
@@ -723,22 +687,14 @@ int acgpu_match_utf8(const acgpu_automaton *ca, const uint8_t *bytes, uint64_t n
     const hipStream_t stream = d.call_stream;
     Utf8Text text;
     rc = stage_utf8_text(d, bytes, n_bytes, stream, &text);
-    st.n_units = text.n_units;
-    st.first_bad = text.first_bad;
-    st.ascii = text.n_units == n_bytes;
-    if (rc == ACGPU_E_ENCODING) { // (the stream is idle: the pool is as usable as before the call)
-        st.n_units = 0;
-        st.ascii = 0;
-        if (stats) *stats = st;
-        return rc;
-    }
-    if (rc) return call.fail(rc);
-    if (stats) *stats = st;
+    if (rc && rc != ACGPU_E_ENCODING) return call.fail(rc);
+    if (stats) *stats = utf8_stats(&text, rc);
+    if (rc) return rc; // (ACGPU_E_ENCODING.  The stream is idle: the pool is as usable as before the call)
     if ((rc = d.stage_out.ensure(cap * (uint64_t)record_kind + 16))) return call.fail(rc);
     rc = match_shard(a, d, &text.shard, record_kind, d.stage_out.p, cap, n_out, stream, nullptr);
     if (rc != ACGPU_OK) return rc; // (ACGPU_E_OVERFLOW: *n_out is the capacity to call again with)
     if (!*n_out) return ACGPU_OK;
-    if ((rc = utf8_map_records(text, reinterpret_cast<int32_t *>(d.stage_out.p), *n_out, (uint32_t)record_kind / 4, stream))) return call.fail(rc);
+    if ((rc = utf8_map_records(text, nullptr, reinterpret_cast<int32_t *>(d.stage_out.p), *n_out, (uint32_t)record_kind / 4, stream))) return call.fail(rc);
     HIP_TRY(hipMemcpyAsync(out, d.stage_out.p, *n_out * (uint64_t)record_kind, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return ACGPU_OK;
@@ -754,10 +710,7 @@ int acgpu_match_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, cons
     int rc = check_batch(t, reinterpret_cast<const uint16_t *>(bytes), offsets, n_haystacks, &plan);
     if (rc) return rc;
     *n_out = 0;
-    acgpu_utf8_batch_stats st{};
-    st.first_bad = -1;
-    st.ascii = 1;
-    if (stats) *stats = st;
+    if (stats) *stats = utf8_batch_stats();
     if (plan.total == 0) return ACGPU_OK; // (nothing to decode and nothing to find: no device needed)
     PoolCall call(a);
     if (call.rc) return call.rc;
@@ -766,17 +719,9 @@ int acgpu_match_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, cons
     const hipStream_t stream = d.call_stream;
     Utf8Batch b;
     rc = stage_utf8_batch(d, t, bytes, offsets, n_haystacks, stream, &b, plan.per_haystack);
-    if (rc == ACGPU_E_ENCODING) { // (the stream is idle: the pool is as usable as before the call)
-        st.first_bad = b.text.first_bad;
-        st.bad_haystack = b.bad_haystack;
-        st.ascii = 0;
-        if (stats) *stats = st;
-        return rc;
-    }
-    if (rc) return call.fail(rc);
-    st.n_units = b.text.n_units;
-    st.ascii = b.text.n_units == plan.total;
-    if (stats) *stats = st;
+    if (rc && rc != ACGPU_E_ENCODING) return call.fail(rc);
+    if (stats) *stats = utf8_batch_stats(&b, rc);
+    if (rc) return rc; // (ACGPU_E_ENCODING.  The stream is idle: the pool is as usable as before the call)
     const uint64_t W = (uint64_t)record_kind / 4, out_rec = (uint64_t)record_kind + 4;
     if (plan.per_haystack) { // every haystack by the route acgpu_match_utf8 takes, tagged on the host
         std::vector<int32_t> tmp;
@@ -792,7 +737,7 @@ int acgpu_match_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, cons
             rc = match_shard(a, d, &text.shard, record_kind, d.stage_out.p, room, &got, stream, nullptr);
             if (rc != ACGPU_OK && rc != ACGPU_E_OVERFLOW) return call.fail(rc);
             if (rc == ACGPU_OK && got) {
-                if ((rc = utf8_map_records(text, reinterpret_cast<int32_t *>(d.stage_out.p), got, (uint32_t)W, stream))) return call.fail(rc);
+                if ((rc = utf8_map_records(text, nullptr, reinterpret_cast<int32_t *>(d.stage_out.p), got, (uint32_t)W, stream))) return call.fail(rc);
                 try {
                     tmp.resize(got * W);
                 } catch (...) {

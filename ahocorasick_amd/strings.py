@@ -595,27 +595,34 @@ class Stream:
         N.check(N.lib().acgpu_stream_reserve(self._h, int(n_units), ctypes.byref(p)), "acgpu_stream_reserve")
         return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint16)), shape=(int(n_units),))
 
-    def feed(self, units, final=False, cap=None):
-        u = np.ascontiguousarray(units, dtype=np.uint16)  # (a view of the reserved staging memory stays where it is)
-        n = int(u.size)
+    def _feed(self, entry, src, n, final, cap, stats=None):
+        """The body of feed and feed_utf8: one record buffer per stream (a fresh one per feed costs more than the feed), the same
+        feed again where the capacity was too small, the records as int64 with GLOBAL positions.  stats: the entry's last argument,
+        where it has one -- then ACGPU_E_ENCODING raises Utf8Error."""
         cols = self._kind // 4
         if cap is None:
             cap = max(4096, n // 64)
-        src = u if n else np.zeros(1, np.uint16)
+        tail = () if stats is None else (ctypes.byref(stats),)
         while True:
-            out = getattr(self, "_out", None)  # (one record buffer per stream: a fresh one per feed costs more than the feed)
+            out = getattr(self, "_out", None)
             if out is None or out.shape != (cap, cols):
                 out = self._out = np.empty((cap, cols), dtype=np.int32)
             n_out, base = ctypes.c_uint64(0), ctypes.c_int64(0)
-            rc = N.lib().acgpu_stream_feed(self._h, _vp(src), n, 1 if final else 0, self._kind, _vp(out), cap,
-                                           ctypes.byref(n_out), ctypes.byref(base))
+            rc = getattr(N.lib(), entry)(self._h, _vp(src), n, 1 if final else 0, self._kind, _vp(out), cap,
+                                         ctypes.byref(n_out), ctypes.byref(base), *tail)
             if rc == N.E_OVERFLOW:  # nothing was consumed: same feed, larger buffer
                 cap = int(n_out.value)
                 continue
-            N.check(rc, "acgpu_stream_feed")
+            if rc == N.E_ENCODING and stats is not None:
+                raise Utf8Error(stats.first_bad)
+            N.check(rc, entry)
             r = out[:n_out.value].astype(np.int64)
             r[:, :2] += base.value
             return r
+
+    def feed(self, units, final=False, cap=None):
+        u = np.ascontiguousarray(units, dtype=np.uint16)  # (a view of the reserved staging memory stays where it is)
+        return self._feed("acgpu_stream_feed", u if u.size else np.zeros(1, np.uint16), int(u.size), final, cap)
 
     def feed_utf8(self, data, final=False, cap=None, stats=None):
         """acgpu_stream_feed_utf8: the next bytes of a UTF-8 text (bytes-like or a uint8 array; a chunk may end inside a
@@ -623,77 +630,47 @@ class Stream:
         first feed), end exclusive.  Ill-formed input raises Utf8Error (.start: the global offset) and finishes the stream.
         A stream is fed either units or bytes.  stats: an N.Utf8StreamStats to fill in, if wanted."""
         buf = _utf8_bytes(data)
-        n = int(buf.size)
-        cols = self._kind // 4
+        return self._feed("acgpu_stream_feed_utf8", buf if buf.size else np.zeros(1, np.uint8), int(buf.size), final, cap,
+                          stats if stats is not None else N.Utf8StreamStats())
+
+    def _replace_feed(self, entry, src, table, final, cap, stats):
+        """The body of replace_feed and replace_feed_utf8: the same feed again with the room it asks for, the result as an array of
+        src's type.  table: (replacements, offsets, n).  stats: the entry's last arguments; a Utf8StreamStats comes first."""
+        n = int(src.size)
+        r, off, n_repl = table
         if cap is None:
-            cap = max(4096, n // 64)
-        src = buf if n else np.zeros(1, np.uint8)
-        st = stats if stats is not None else N.Utf8StreamStats()
+            cap = n + n // 4 + 64
+        if not n:
+            src = np.zeros(1, src.dtype)
         while True:
-            out = getattr(self, "_out", None)  # (one record buffer per stream, as feed)
-            if out is None or out.shape != (cap, cols):
-                out = self._out = np.empty((cap, cols), dtype=np.int32)
-            n_out, base = ctypes.c_uint64(0), ctypes.c_int64(0)
-            rc = N.lib().acgpu_stream_feed_utf8(self._h, _vp(src), n, 1 if final else 0, self._kind, _vp(out), cap,
-                                                ctypes.byref(n_out), ctypes.byref(base), ctypes.byref(st))
-            if rc == N.E_OVERFLOW:  # nothing was consumed: same feed, larger buffer
+            out = np.empty(max(cap, 1), dtype=src.dtype)
+            n_out = ctypes.c_uint64(0)
+            rc = getattr(N.lib(), entry)(self._h, _vp(src), n, 1 if final else 0, _vp(r), _vp(off), n_repl, _vp(out), cap,
+                                         ctypes.byref(n_out), *[ctypes.byref(s) for s in stats])
+            if rc == N.E_OVERFLOW and int(n_out.value) > cap:  # nothing was committed: same feed, the room it asks for
                 cap = int(n_out.value)
                 continue
-            if rc == N.E_ENCODING:
-                raise Utf8Error(st.first_bad)
-            N.check(rc, "acgpu_stream_feed_utf8")
-            r = out[:n_out.value].astype(np.int64)
-            r[:, :2] += base.value
-            return r
+            if rc == N.E_ENCODING and len(stats) == 2:
+                raise Utf8Error(stats[0].first_bad)
+            N.check(rc, entry)
+            return out[:n_out.value]
 
     def replace_feed(self, units, replacements, final=False, cap=None, stats=None):
         """acgpu_stream_replace_u16: the next units of a text that is REWRITTEN as it arrives -> the units of the result that have
         become decidable, a uint16 array (the concatenation over all feeds: the whole text with every match replaced).
         `replacements` as for Automaton.replace_host, the same at every feed.  A stream is fed through one entry only.
         stats: an N.ReplaceStats to fill in, if wanted (this feed alone)."""
-        u = utf16(units)
-        n = int(u.size)
-        src = u if n else np.zeros(1, np.uint16)
-        r_units, off, n_repl = self._auto._replacements(replacements)
-        if cap is None:
-            cap = n + n // 4 + 64
-        st = stats if stats is not None else N.ReplaceStats()
-        while True:
-            out = np.empty(max(cap, 1), dtype=np.uint16)
-            n_out = ctypes.c_uint64(0)
-            rc = N.lib().acgpu_stream_replace_u16(self._h, _vp(src), n, 1 if final else 0, _vp(r_units), _vp(off), n_repl, _vp(out), cap,
-                                                  ctypes.byref(n_out), ctypes.byref(st))
-            if rc == N.E_OVERFLOW and int(n_out.value) > cap:  # nothing was committed: same feed, the room it asks for
-                cap = int(n_out.value)
-                continue
-            N.check(rc, "acgpu_stream_replace_u16")
-            return out[:n_out.value]
+        return self._replace_feed("acgpu_stream_replace_u16", utf16(units), self._auto._replacements(replacements), final, cap,
+                                  [stats if stats is not None else N.ReplaceStats()])
 
     def replace_feed_utf8(self, data, replacements, final=False, stats=None, cap=None, replace_stats=None):
         """acgpu_stream_replace_utf8: the next bytes of a UTF-8 text that is rewritten as it arrives (a chunk may end inside a
         sequence) -> the bytes of the result that have become decidable.  `replacements` as for Automaton.replace_utf8, the same
         at every feed.  Ill-formed input raises Utf8Error (.start: the global offset) and finishes the stream; what had been
         withheld is not delivered.  stats: an N.Utf8StreamStats, replace_stats: an N.ReplaceStats to fill in, if wanted."""
-        buf = _utf8_bytes(data)
-        n = int(buf.size)
-        src = buf if n else np.zeros(1, np.uint8)
-        r_bytes, off, n_repl = self._auto._replacements_utf8(replacements)
-        if cap is None:
-            cap = n + n // 4 + 64
-        ust = stats if stats is not None else N.Utf8StreamStats()
-        st = replace_stats if replace_stats is not None else N.ReplaceStats()
-        while True:
-            out = np.empty(max(cap, 1), dtype=np.uint8)
-            n_out = ctypes.c_uint64(0)
-            rc = N.lib().acgpu_stream_replace_utf8(self._h, _vp(src), n, 1 if final else 0, _vp(r_bytes), _vp(off), n_repl, _vp(out), cap,
-                                                   ctypes.byref(n_out), ctypes.byref(ust), ctypes.byref(st))
-            if rc == N.E_OVERFLOW and int(n_out.value) > cap:  # nothing was committed: same feed, the room it asks for
-                cap = int(n_out.value)
-                continue
-            if rc == N.E_ENCODING:
-                raise Utf8Error(ust.first_bad)
-            N.check(rc, "acgpu_stream_replace_utf8")
-            return out[:n_out.value].tobytes()
+        return self._replace_feed("acgpu_stream_replace_utf8", _utf8_bytes(data), self._auto._replacements_utf8(replacements), final, cap,
+                                  [stats if stats is not None else N.Utf8StreamStats(),
+                                   replace_stats if replace_stats is not None else N.ReplaceStats()]).tobytes()
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None

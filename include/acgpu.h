@@ -685,7 +685,7 @@ int acgpu_summary_batch_u16(const acgpu_automaton *a, const uint16_t *units, con
  * How it works: the bytes are copied to the device; k_utf8_count validates them, a lane per 16 bytes, and counts the units of
  * every block of 4096 bytes; the host waits ONCE for 16 bytes (n_units, first_bad) to size the shard; k_utf8_write stores the
  * units and, per 32 units, the byte offset of the sequence that holds the first of them (the checkpoints); the scan is
- * match_shard on the whole text as one shard, unchanged; k_utf8_map rewrites start and end - 1 of every record in place from
+ * match_shard on the whole text as one shard, unchanged; k_utf8_batch_map rewrites start and end - 1 of every record in place from
  * the nearest checkpoint and a walk of at most 31 units over the lead bytes; one copy brings the records out.
  * The call is ONE shard through the general path: neither the chunk-pipelined form acgpu_match_u16 takes from 2^25 units on
  * (a long text is copied whole before the scan begins, nothing overlaps), nor its one-launch form for texts of up to 4096 units
@@ -729,7 +729,7 @@ int acgpu_match_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_
  *  st, ust   : may be NULL.  st->n_records: matches replaced; st->units_out: bytes of the result; ust as acgpu_match_utf8 fills it.
  * Works on the NULL stream, under the pool's lock (STREAM RULE above: tickets in flight on the pool give ACGPU_E_INVALID).
  * How it works: the text is staged as acgpu_match_utf8 stages it (validated, transcoded, checkpoints) and scanned in UNITS
- * through the pieces of acgpu_replace_device; behind every piece k_utf8_map rewrites its records in the reservoir to byte
+ * through the pieces of acgpu_replace_device; behind every piece k_utf8_batch_map rewrites its records in the reservoir to byte
  * offsets, and one lane maps the piece's boundary to the first byte of the code point that holds it (rounded down: that only
  * withholds more).  From there on everything counts bytes: the plan runs unchanged over byte records and a byte table, and the
  * byte form of the emit kernel writes 16 output bytes per lane from the caller's bytes on the device and the table, through
@@ -868,7 +868,7 @@ int acgpu_replace_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, con
  * text, through the OPEN form of the validator unless it is the last (k_utf8_open_count: a lead in the last three bytes whose
  * sequence reaches behind the buffer is judged by the bytes that are there; if they pass it is not counted and the host reads
  * {n_units, first_bad, tail} in the one wait; k_utf8_write runs over the n - tail bytes before it).  The shard is cut by the
- * plan of acgpu_stream_feed in units, scanned by match_shard, and k_utf8_map rewrites the records to bytes of the buffer (an
+ * plan of acgpu_stream_feed in units, scanned by match_shard, and k_utf8_batch_map rewrites the records to bytes of the buffer (an
  * all-ASCII buffer: nothing to map).  The byte at which the carry is cut for the next feed is found on the host, walking back
  * from the end of the decoded bytes over the lead bytes; it is a code-point boundary, so where the plan's unit is a low
  * surrogate one unit more is carried -- left context that is longer than needed changes no record.

@@ -1,5 +1,5 @@
 """GPU tests of the UTF-8 replace entry (include/acgpu.h: acgpu_replace_utf8; csrc/acgpu_replace.hip: k_replace_emit<uint8_t> behind
-the unchanged plan, csrc/acgpu_utf8.hip: k_utf8_map over a piece's records and k_utf8_pos for its boundary).  Every expected
+the unchanged plan, csrc/acgpu_utf8.hip: k_utf8_batch_map over a piece's records and k_utf8_batch_pos for its boundary, both without a batch).  Every expected
 result is the Python splice, over the BYTES, of the CPU oracle's records on utf16(data.decode()), mapped to byte offsets by the
 header's rule restated here over the text's code points; equality is exact: content, n_out and st.n_records.  Every call writes
 into a buffer with a canary behind its capacity."""

@@ -1,5 +1,5 @@
 """GPU tests of the UTF-8 entry (include/acgpu.h: acgpu_match_utf8; csrc/acgpu_utf8.hip: k_utf8_count, k_utf8_scan, k_utf8_write,
-k_utf8_map around the unchanged scan).  Every expected record comes from the CPU oracle on utf16(data.decode()), its positions
+k_utf8_batch_map around the unchanged scan).  Every expected record comes from the CPU oracle on utf16(data.decode()), its positions
 mapped to bytes by the header's rule, restated here over the text's code points (not through the product's own
 utf8_unit_offsets); equality is exact.  Expected error positions are CPython's UnicodeDecodeError.start."""
 import ctypes
