@@ -99,6 +99,11 @@ class Utf8BatchStats(ctypes.Structure):  # acgpu_utf8_batch_stats
     _fields_ = [("n_units", ctypes.c_uint64), ("first_bad", ctypes.c_int64), ("bad_haystack", ctypes.c_uint32), ("ascii", ctypes.c_uint32)]
 
 
+class Utf8LossyStats(ctypes.Structure):  # acgpu_utf8_lossy_stats
+    _fields_ = [("n_units", ctypes.c_uint64), ("n_replaced", ctypes.c_uint64), ("first_replaced", ctypes.c_int64),
+                ("first_haystack", ctypes.c_uint32), ("ascii", ctypes.c_uint32)]
+
+
 class Utf8StreamStats(ctypes.Structure):  # acgpu_utf8_stream_stats
     _fields_ = [("n_units", ctypes.c_uint64), ("first_bad", ctypes.c_int64), ("ascii", ctypes.c_uint32), ("held", ctypes.c_uint32)]
 
@@ -125,7 +130,8 @@ SYMBOLS = ["acgpu_build", "acgpu_free", "acgpu_get_info", "acgpu_match_u16", "ac
            "acgpu_replace_u16", "acgpu_replace_device", "acgpu_replace_batch_u16", "acgpu_summary_batch_u16",
            "acgpu_match_utf8", "acgpu_replace_utf8", "acgpu_match_batch_utf8", "acgpu_summary_batch_utf8",
            "acgpu_replace_batch_utf8", "acgpu_stream_feed_utf8", "acgpu_stream_replace_u16",
-           "acgpu_stream_replace_utf8"]
+           "acgpu_stream_replace_utf8", "acgpu_match_utf8_lossy", "acgpu_match_batch_utf8_lossy",
+           "acgpu_summary_batch_utf8_lossy"]
 
 _lib = None
 
@@ -226,6 +232,12 @@ def lib():
         L.acgpu_match_batch_utf8.argtypes = [vp, vp, vp, u32, ci, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(Utf8BatchStats)]
         L.acgpu_summary_batch_utf8.restype = ci
         L.acgpu_summary_batch_utf8.argtypes = [vp, vp, vp, u32, vp, ctypes.POINTER(SummaryStats), ctypes.POINTER(Utf8BatchStats)]
+        L.acgpu_match_utf8_lossy.restype = ci
+        L.acgpu_match_utf8_lossy.argtypes = [vp, vp, u64, ci, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(Utf8LossyStats)]
+        L.acgpu_match_batch_utf8_lossy.restype = ci
+        L.acgpu_match_batch_utf8_lossy.argtypes = [vp, vp, vp, u32, ci, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(Utf8LossyStats)]
+        L.acgpu_summary_batch_utf8_lossy.restype = ci
+        L.acgpu_summary_batch_utf8_lossy.argtypes = [vp, vp, vp, u32, vp, ctypes.POINTER(SummaryStats), ctypes.POINTER(Utf8LossyStats)]
         L.acgpu_replace_utf8.restype = ci
         L.acgpu_replace_utf8.argtypes = [vp, vp, u64, vp, vp, u32, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(ReplaceStats),
                                          ctypes.POINTER(Utf8Stats)]

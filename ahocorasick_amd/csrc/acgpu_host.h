@@ -228,7 +228,7 @@ struct DeviceState {
     PoolEvent replace_ev[4];                              // ... slab b emitted (b), slab b copied out (2 + b)
     PoolBuf replace_merged, replace_off;                  // acgpu_replace_batch_u16: a piece's records merged with its separators, the result's offsets (acgpu_replace_batch_utf8's too)
     PoolBuf summary;                                      // acgpu_summary_batch_u16: 24 bytes per haystack, {records, the first of them}
-    PoolBuf utf8_in, utf8_aux;                            // the UTF-8 entries: the caller's bytes; {n_units, first_bad, tail}, block sums, checkpoints, a batch's byte offsets (Utf8Aux, acgpu_utf8.hip)
+    PoolBuf utf8_in, utf8_aux;                            // the UTF-8 entries: the caller's bytes; {n_units, first_bad, tail, n_replaced}, block sums, checkpoints, a batch's byte offsets, a lossy text's start bitmap (Utf8Aux, acgpu_utf8.hip)
     CountCall *count = nullptr;                          // the counting call that runs on this pool (it holds mu), or nullptr
     double all_density = -1.0;                           // ALL: records per unit of this pool's last call (-1: none yet): k_ac_states or the tile kernel
     int fol_level = 0;                                   // k_longest_follow: 0 = run-up of 128 positions, 1 = of a whole segment (a call's chains had not merged), 2 = not for this pool's texts
@@ -380,6 +380,10 @@ int scan_host_range(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack
 // end, no chain.  The caller holds d.mu.
 int stage_whole_text(DeviceState &d, const uint16_t *haystack, uint64_t n_units, acgpu_shard *out);
 
+// What a UTF-8 entry does with ill-formed bytes: refuse the text (ACGPU_E_ENCODING), or scan every maximal ill-formed subpart as
+// one U+FFFD, as bytes.decode("utf-8", "replace") does (the *_lossy entries).
+enum class Utf8Errors { strict, replace };
+
 // A UTF-8 host text staged as one shard (acgpu_utf8.hip): validated and transcoded on the device.
 struct Utf8Text {
     acgpu_shard shard{};              // as stage_whole_text builds it: d.stage_hay, all of it owned, the text's begin and end, no chain
@@ -389,18 +393,22 @@ struct Utf8Text {
     uint64_t n_units = 0;             // UTF-16 units of the text
     uint64_t n_bytes = 0;             // ... and its bytes (the open form: without the held prefix)
     uint32_t tail = 0;                // the open form: bytes at the buffer's end that begin a sequence the next buffer completes, 0..3
-    int64_t first_bad = -1;           // ACGPU_E_ENCODING: where a strict decoder stops
+    int64_t first_bad = -1;           // ACGPU_E_ENCODING: where a strict decoder stops; lossy: -1, or the first replaced subpart's first byte
+    bool lossy = false;               // staged with Utf8Errors::replace: the maps walk d_starts, not the bytes
+    const uint32_t *d_starts = nullptr; // lossy, with d_ckpt: the start bitmap, a bit per byte set where a sequence or a subpart begins (d.utf8_aux)
+    uint64_t n_replaced = 0;          // lossy: the U+FFFD units that stand for ill-formed subparts
 };
 // bytes -> {device shard, checkpoint table, n_units} on `stream`, which it waits for once (the transcoder's 16-byte result sizes
 // the shard).  ACGPU_E_ENCODING: the text is ill-formed, out->first_bad says where, nothing was transcoded and the stream is
 // idle.  The caller holds d.mu; n_bytes < 2^31.
-int stage_utf8_text(DeviceState &d, const uint8_t *bytes, uint64_t n_bytes, hipStream_t stream, Utf8Text *out);
+// errors == replace: never ACGPU_E_ENCODING; out->n_replaced and out->first_bad say what was replaced.
+int stage_utf8_text(DeviceState &d, const uint8_t *bytes, uint64_t n_bytes, hipStream_t stream, Utf8Text *out, Utf8Errors errors = Utf8Errors::strict);
 // The same for a buffer that lies in two parts on the host, head | bytes (acgpu_stream_feed_utf8: the carried bytes and the
 // caller's chunk; n_head + n_rest < 2^31, not 0), each copied from where it is.  open: the text goes on behind the buffer -- a
 // sequence that the buffer's end cuts and that is well-formed so far is held back: out->tail bytes, and the shard, the
 // checkpoints, n_units and n_bytes are those of the bytes before them (k_utf8_open_count).
 int stage_utf8_parts(DeviceState &d, const uint8_t *head, uint64_t n_head, const uint8_t *bytes, uint64_t n_rest, bool open, hipStream_t stream,
-                     Utf8Text *out);
+                     Utf8Text *out, Utf8Errors errors = Utf8Errors::strict); // (open and replace: not built)
 // A batch of UTF-8 haystacks staged as ONE shard (acgpu_utf8.hip): the caller's span copied once, every haystack validated on its
 // own, and transcoded into the text a batch call scans -- the haystacks' units with the separator unit behind every haystack.
 struct Utf8Batch {
@@ -412,13 +420,14 @@ struct Utf8Batch {
     std::vector<uint32_t> h_boff;        // ... and on the host (what d_boff was uploaded from)
     uint32_t n_haystacks = 0;
     uint32_t bad_haystack = 0;           // ACGPU_E_ENCODING: the first ill-formed haystack; text.first_bad is relative to ITS first byte
+                                         // (lossy: the haystack of the first replaced subpart, likewise)
 };
 // bytes[offsets[0] .. offsets[n]) -> Utf8Batch on `stream`, which it waits for once, as stage_utf8_text does.  offsets: checked
 // (check_batch), the span not empty.  validate_only: no shard is built (the calls that go haystack by haystack stage every
 // haystack with stage_utf8_text afterwards); out->text.n_units is set all the same.  ACGPU_E_ENCODING: nothing was transcoded
-// and the stream is idle.  The caller holds d.mu.
+// and the stream is idle.  errors == replace: every haystack decoded on its own, never ACGPU_E_ENCODING.  The caller holds d.mu.
 int stage_utf8_batch(DeviceState &d, const HostTables &t, const uint8_t *bytes, const uint64_t *offsets, uint32_t n, hipStream_t stream,
-                     Utf8Batch *out, bool validate_only = false);
+                     Utf8Batch *out, bool validate_only = false, Utf8Errors errors = Utf8Errors::strict);
 // cnt records of the scan over b's shard in d_recs -> records tagged with their haystack in d_out, positions in bytes relative to
 // the haystack (k_utf8_batch_tag; an all-ASCII batch: k_batch_tag, there a relative unit is a relative byte)
 int utf8_batch_tag(const Utf8Batch &b, const void *d_recs, uint64_t cnt, int record_kind, void *d_out, hipStream_t stream);
@@ -456,6 +465,39 @@ inline acgpu_utf8_batch_stats utf8_batch_stats(const Utf8Batch *b = nullptr, int
     st.ascii = b ? !bad && b->text.n_units == b->text.n_bytes : 1;
     return st;
 }
+
+inline acgpu_utf8_lossy_stats utf8_lossy_stats(const Utf8Text *text = nullptr, uint32_t first_haystack = 0) {
+    acgpu_utf8_lossy_stats st{};
+    st.n_units = text ? text->n_units : 0;
+    st.n_replaced = text ? text->n_replaced : 0;
+    st.first_replaced = text ? text->first_bad : -1;
+    st.first_haystack = first_haystack;
+    st.ascii = text ? text->n_units == text->n_bytes && !text->n_replaced : 1;
+    return st;
+}
+
+// The policy of an entry's body: how its texts are staged and what its stats argument is.  One body serves the strict entry and
+// the lossy one (acgpu_utf8.hip, acgpu_summary.hip).
+struct Utf8StrictText {
+    using Stats = acgpu_utf8_stats;
+    static constexpr Utf8Errors errors = Utf8Errors::strict;
+    static Stats stats(const Utf8Text *text = nullptr, int rc = ACGPU_OK) { return utf8_stats(text, rc); }
+};
+struct Utf8LossyText {
+    using Stats = acgpu_utf8_lossy_stats;
+    static constexpr Utf8Errors errors = Utf8Errors::replace;
+    static Stats stats(const Utf8Text *text = nullptr, int = ACGPU_OK) { return utf8_lossy_stats(text); }
+};
+struct Utf8StrictBatch {
+    using Stats = acgpu_utf8_batch_stats;
+    static constexpr Utf8Errors errors = Utf8Errors::strict;
+    static Stats stats(const Utf8Batch *b = nullptr, int rc = ACGPU_OK) { return utf8_batch_stats(b, rc); }
+};
+struct Utf8LossyBatch {
+    using Stats = acgpu_utf8_lossy_stats;
+    static constexpr Utf8Errors errors = Utf8Errors::replace;
+    static Stats stats(const Utf8Batch *b = nullptr, int = ACGPU_OK) { return utf8_lossy_stats(b ? &b->text : nullptr, b ? b->bad_haystack : 0); }
+};
 
 // acgpu_replace_batch_utf8, behind a piece that emits the span's bytes [done, limit): the haystack boundaries whose output offset
 // that piece writes are [*j0, *j1) of boff (n_hay + 1 ascending byte offsets, boff[n_hay] = the span's bytes) -- those with

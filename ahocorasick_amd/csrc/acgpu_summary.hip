@@ -14,6 +14,7 @@
 //
 // acgpu_summary_batch_utf8 is the same call for UTF-8 haystacks: the text comes from stage_utf8_batch (acgpu_utf8.hip) as a device
 // shard, the pieces and k_batch_summary run unchanged, and k_summary_utf8_bytes maps the first records to bytes at the end.
+// acgpu_summary_batch_utf8_lossy is that body with the lossy policy (summary_batch_utf8<P>): ill-formed bytes are staged as U+FFFD.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -120,6 +121,69 @@ int summary_pieces(acgpu_automaton *a, DeviceState &d, const PieceScan &scan, bo
     return rc;
 }
 
+// The body of acgpu_summary_batch_utf8 and acgpu_summary_batch_utf8_lossy.  P (acgpu_host.h): how the batch is staged, and the entry's stats.
+template <class P>
+int summary_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks, acgpu_batch_summary *out,
+                       acgpu_summary_stats *st, typename P::Stats *stats) {
+    if (!ca || !offsets || (n_haystacks && !out)) return ACGPU_E_INVALID;
+    acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
+    const HostTables &t = a->t;
+    BatchPlan plan; // (in bytes: bytes >= units, so bytes + haystacks < 2^31 bounds the text the scan sees)
+    int rc = check_batch(t, reinterpret_cast<const uint16_t *>(bytes), offsets, n_haystacks, &plan);
+    if (rc) return rc;
+    if (plan.total == 0) { // (nothing to decode and nothing to find: no device needed)
+        for (uint32_t i = 0; i < n_haystacks; i++) out[i] = acgpu_batch_summary{0, -1, -1, -1, 0};
+        if (st) *st = acgpu_summary_stats{};
+        if (stats) *stats = P::stats();
+        return ACGPU_OK;
+    }
+    PoolCall call(a); // (no device: fails here and out is untouched)
+    if (call.rc) return call.rc;
+    DeviceState &d = *call.d;
+    if ((rc = call.idle())) return rc; // (the NULL stream: see the stream rule)
+    const hipStream_t stream = d.call_stream;
+    Utf8Batch b;
+    rc = stage_utf8_batch(d, t, bytes, offsets, n_haystacks, stream, &b, plan.per_haystack, P::errors);
+    if (rc == ACGPU_E_ENCODING) { // (the stream is idle: the pool is as usable as before the call)
+        if (stats) *stats = P::stats(&b, rc);
+        return rc;
+    }
+    if (rc) return call.fail(rc);
+    const size_t sum_bytes = (size_t)n_haystacks * sizeof(acgpu_batch_summary);
+    if ((rc = d.summary.ensure(sum_bytes))) return call.fail(rc);
+    acgpu_batch_summary *d_sum = reinterpret_cast<acgpu_batch_summary *>(d.summary.p);
+    hipLaunchKernelGGL(k_summary_fill, dim3((n_haystacks + kSummaryBlock - 1) / kSummaryBlock), dim3(kSummaryBlock), 0, stream, d_sum, n_haystacks);
+    if (hipGetLastError() != hipSuccess) return call.fail(ACGPU_E_HIP);
+    acgpu_summary_stats sum{};
+    const bool whole = shard_rule(t, ACGPU_REC_MAP, false).sequential; // (a device shard: as acgpu_replace_utf8 drives its pieces)
+    if (plan.per_haystack) { // every haystack staged and driven as a text of its own, into its own entry, mapped before the next is staged
+        // the target of one haystack alone: one offset that is the text's origin as well -- its value does not matter, word 0 of
+        // the batch's offsets table (stage_utf8_batch has made room for it) holds it
+        uint32_t *d_zero = reinterpret_cast<uint32_t *>(d.batch_off.p);
+        if (hipMemsetAsync(d_zero, 0, 4, stream) != hipSuccess) return call.fail(ACGPU_E_HIP);
+        for (uint32_t i = 0; i < n_haystacks && rc == ACGPU_OK; i++) {
+            const uint64_t len = offsets[i + 1] - offsets[i];
+            if (!len) continue;
+            Utf8Text text;
+            if ((rc = stage_utf8_text(d, bytes + offsets[i], len, stream, &text, P::errors))) break;
+            if ((rc = summary_pieces(a, d, PieceScan{a, d, nullptr, 0, &text.shard, stream}, whole, SummaryTarget{d_zero, 1, 0, d_sum + i}, &sum))) break;
+            rc = utf8_summary_bytes(nullptr, text, d_sum + i, 1, stream);
+        }
+        if (rc == ACGPU_E_ENCODING) rc = ACGPU_E_HIP; // (never: the batch has been validated)
+    } else {
+        SeparatorScan sep(d, t);
+        rc = summary_pieces(a, d, PieceScan{a, d, nullptr, 0, &b.text.shard, stream}, whole, SummaryTarget{b.d_cat_off, n_haystacks, 0, d_sum}, &sum);
+        if (rc == ACGPU_OK) rc = utf8_summary_bytes(&b, b.text, d_sum, n_haystacks, stream);
+    }
+    if (rc) return call.fail(rc);
+    if (hipMemcpyAsync(out, d_sum, sum_bytes, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
+        return call.fail(ACGPU_E_HIP);
+    for (uint32_t i = 0; i < n_haystacks; i++) sum.n_matched += out[i].n_matches != 0;
+    if (st) *st = sum;
+    if (stats) *stats = P::stats(&b);
+    return ACGPU_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -179,65 +243,14 @@ int acgpu_summary_batch_u16(const acgpu_automaton *ca, const uint16_t *units, co
     return ACGPU_OK;
 }
 
-int acgpu_summary_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
+int acgpu_summary_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
                              acgpu_batch_summary *out, acgpu_summary_stats *st, acgpu_utf8_batch_stats *stats) {
-    if (!ca || !offsets || (n_haystacks && !out)) return ACGPU_E_INVALID;
-    acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
-    const HostTables &t = a->t;
-    BatchPlan plan; // (in bytes: bytes >= units, so bytes + haystacks < 2^31 bounds the text the scan sees)
-    int rc = check_batch(t, reinterpret_cast<const uint16_t *>(bytes), offsets, n_haystacks, &plan);
-    if (rc) return rc;
-    if (plan.total == 0) { // (nothing to decode and nothing to find: no device needed)
-        for (uint32_t i = 0; i < n_haystacks; i++) out[i] = acgpu_batch_summary{0, -1, -1, -1, 0};
-        if (st) *st = acgpu_summary_stats{};
-        if (stats) *stats = utf8_batch_stats();
-        return ACGPU_OK;
-    }
-    PoolCall call(a); // (no device: fails here and out is untouched)
-    if (call.rc) return call.rc;
-    DeviceState &d = *call.d;
-    if ((rc = call.idle())) return rc; // (the NULL stream: see the stream rule)
-    const hipStream_t stream = d.call_stream;
-    Utf8Batch b;
-    rc = stage_utf8_batch(d, t, bytes, offsets, n_haystacks, stream, &b, plan.per_haystack);
-    if (rc == ACGPU_E_ENCODING) { // (the stream is idle: the pool is as usable as before the call)
-        if (stats) *stats = utf8_batch_stats(&b, rc);
-        return rc;
-    }
-    if (rc) return call.fail(rc);
-    const size_t sum_bytes = (size_t)n_haystacks * sizeof(acgpu_batch_summary);
-    if ((rc = d.summary.ensure(sum_bytes))) return call.fail(rc);
-    acgpu_batch_summary *d_sum = reinterpret_cast<acgpu_batch_summary *>(d.summary.p);
-    hipLaunchKernelGGL(k_summary_fill, dim3((n_haystacks + kSummaryBlock - 1) / kSummaryBlock), dim3(kSummaryBlock), 0, stream, d_sum, n_haystacks);
-    if (hipGetLastError() != hipSuccess) return call.fail(ACGPU_E_HIP);
-    acgpu_summary_stats sum{};
-    const bool whole = shard_rule(t, ACGPU_REC_MAP, false).sequential; // (a device shard: as acgpu_replace_utf8 drives its pieces)
-    if (plan.per_haystack) { // every haystack staged and driven as a text of its own, into its own entry, mapped before the next is staged
-        // the target of one haystack alone: one offset that is the text's origin as well -- its value does not matter, word 0 of
-        // the batch's offsets table (stage_utf8_batch has made room for it) holds it
-        uint32_t *d_zero = reinterpret_cast<uint32_t *>(d.batch_off.p);
-        if (hipMemsetAsync(d_zero, 0, 4, stream) != hipSuccess) return call.fail(ACGPU_E_HIP);
-        for (uint32_t i = 0; i < n_haystacks && rc == ACGPU_OK; i++) {
-            const uint64_t len = offsets[i + 1] - offsets[i];
-            if (!len) continue;
-            Utf8Text text;
-            if ((rc = stage_utf8_text(d, bytes + offsets[i], len, stream, &text))) break;
-            if ((rc = summary_pieces(a, d, PieceScan{a, d, nullptr, 0, &text.shard, stream}, whole, SummaryTarget{d_zero, 1, 0, d_sum + i}, &sum))) break;
-            rc = utf8_summary_bytes(nullptr, text, d_sum + i, 1, stream);
-        }
-        if (rc == ACGPU_E_ENCODING) rc = ACGPU_E_HIP; // (never: the batch has been validated)
-    } else {
-        SeparatorScan sep(d, t);
-        rc = summary_pieces(a, d, PieceScan{a, d, nullptr, 0, &b.text.shard, stream}, whole, SummaryTarget{b.d_cat_off, n_haystacks, 0, d_sum}, &sum);
-        if (rc == ACGPU_OK) rc = utf8_summary_bytes(&b, b.text, d_sum, n_haystacks, stream);
-    }
-    if (rc) return call.fail(rc);
-    if (hipMemcpyAsync(out, d_sum, sum_bytes, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
-        return call.fail(ACGPU_E_HIP);
-    for (uint32_t i = 0; i < n_haystacks; i++) sum.n_matched += out[i].n_matches != 0;
-    if (st) *st = sum;
-    if (stats) *stats = utf8_batch_stats(&b);
-    return ACGPU_OK;
+    return summary_batch_utf8<Utf8StrictBatch>(a, bytes, offsets, n_haystacks, out, st, stats);
+}
+
+int acgpu_summary_batch_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
+                                   acgpu_batch_summary *out, acgpu_summary_stats *st, acgpu_utf8_lossy_stats *stats) {
+    return summary_batch_utf8<Utf8LossyBatch>(a, bytes, offsets, n_haystacks, out, st, stats);
 }
 
 } // extern "C"

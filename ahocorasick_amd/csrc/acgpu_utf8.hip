@@ -24,7 +24,11 @@
 //    k_batch_tag and the map in one, k_summary_utf8_bytes maps the summaries' first records;
 //  * staging: Utf8Aux lays out the device buffers and utf8_validate runs count, scan and the one wait for stage_utf8_parts (a
 //    text in two host parts: acgpu_stream_feed_utf8's carried bytes and chunk; stage_utf8_text is its one-part, closed case) and
-//    for stage_utf8_batch.
+//    for stage_utf8_batch;
+//  * lossy: acgpu_match_utf8_lossy and acgpu_match_batch_utf8_lossy (acgpu_summary_batch_utf8_lossy in acgpu_summary.hip) are the
+//    same bodies with another policy (match_utf8<P>, match_batch_utf8<P>; Utf8Errors::replace down to utf8_validate) over the LOSSY
+//    instantiations of lane_view, count_units, the writers and locate: nothing is refused, a maximal ill-formed subpart is one
+//    U+FFFD, and the maps walk a start bitmap that the lossy writers store beside the checkpoints.
 // What a lane knows about its 16 bytes is eleven bit masks over a window of 24 bytes (the 4 before, its own, the 4 behind), built
 // by one function that both passes over the text share, so they cannot disagree about a count; the two writers share the
 // decoder, so they cannot disagree about a unit.
@@ -50,6 +54,7 @@ constexpr uint32_t kCkptLow = 0x80000000u;           // checkpoint flag: the uni
 
 static_assert(sizeof(acgpu_utf8_stats) == 24, "the layout include/acgpu.h promises");
 static_assert(sizeof(acgpu_utf8_batch_stats) == 24, "the layout include/acgpu.h promises");
+static_assert(sizeof(acgpu_utf8_lossy_stats) == 32, "the layout include/acgpu.h promises");
 
 // What a lane knows about its bytes.  Bit k of a mask stands for the byte at offset o - 4 + k of the text, o the lane's first.
 struct LaneView {
@@ -93,10 +98,22 @@ struct LaneView {
 // At most one tail exists in a buffer: let p < q be two leads of the last three bytes that both reach behind the end.  Then q
 // is one of the bytes p + 1 .. n - 1 that p's sequence needs and that are there, and q is a lead, no continuation byte: p does
 // not pass.  So of such leads only the last can pass, and the one lane that owns it stores n - position without a race.
-template <bool BATCH, bool OPEN = false>
+//
+// LOSSY: nothing is refused.  The masks are those of a decoder that puts one U+FFFD for every MAXIMAL ILL-FORMED SUBPART, as
+// bytes.decode("utf-8", "replace") does: a lead claims the byte behind it only if that is a continuation byte in the range the
+// lead allows, the one behind that only if it claimed the first and it is a continuation byte, a third likewise (4-byte leads
+// only); it never claims a byte at or behind a cut, and C0, C1, F5..FF claim nothing (claimed_lossy).  Then
+//  * lead: every byte that is no claimed continuation byte begins a unit -- a sequence, or a subpart of one to three bytes;
+//  * bad:  of those, the REPLACED ones: a lead that did not claim all it needs, an unclaimed continuation byte;
+//  * four: the 4-byte leads that are not replaced.
+// On well-formed input each equals its strict counterpart (a lead claims all it needs, which is what the strict rules ask).
+// A continuation byte looks at most 3 bytes back for the lead that claims it, and whether that lead does depends on the cuts
+// BETWEEN them: the batch form's cut mask reaches down to bit 1 here, `next` stays the first boundary at or behind o.
+template <bool BATCH, bool OPEN = false, bool LOSSY = false>
 __device__ __forceinline__ LaneView lane_view(const uint8_t *__restrict__ in, uint32_t n, uint32_t o, const uint32_t *__restrict__ boff = nullptr,
                                               uint32_t n_hay = 0) {
     static_assert(!(BATCH && OPEN), "a batch's haystacks end where they end");
+    static_assert(!(LOSSY && OPEN), "the feeds are strict");
     LaneView v;
     uint4 own = make_uint4(0, 0, 0, 0);
     if (o < n) own = *reinterpret_cast<const uint4 *>(in + o);
@@ -140,11 +157,14 @@ __device__ __forceinline__ LaneView lane_view(const uint8_t *__restrict__ in, ui
     if constexpr (BATCH) {
         if (o < n) { // (boff[n_hay] = n > o: the search ends inside the table)
             uint32_t hi = n_hay;
+            const uint32_t from = LOSSY && o ? o - 3u : o;
             while (first < hi) {
                 const uint32_t mid = first + ((hi - first) >> 1);
-                if (boff[mid] < o) first = mid + 1;
+                if (boff[mid] < from) first = mid + 1;
                 else hi = mid;
             }
+            if constexpr (LOSSY)
+                for (; boff[first] < o; ++first) cut |= 1u << (boff[first] + 4u - o); // (bits 1..3; ends: boff[n_hay] = n > o)
             for (uint32_t j = first; j <= n_hay; ++j) {
                 const uint32_t q = boff[j] - o;
                 if (q >= 20u) break;
@@ -164,6 +184,18 @@ __device__ __forceinline__ LaneView lane_view(const uint8_t *__restrict__ in, ui
     v.four = l4 & own_bits;
     v.bad = (bad_lead | (cont & (~claimed | cut))) & own_bits;
     v.tail = 0;
+    if constexpr (LOSSY) {
+        const uint32_t second = (cont >> 1) & ~(e0 & ~(gea0 >> 1)) & ~(ed & (gea0 >> 1)) & ~(f0 & ~(ge90 >> 1)) & ~(f4 & (ge90 >> 1));
+        const uint32_t c1 = l2 & ~inv & second & ~(cut >> 1);  // leads that claim the byte behind them
+        const uint32_t c2 = c1 & l3 & (cont >> 2) & ~(cut >> 2); // ... and the second
+        const uint32_t c3 = c2 & l4 & (cont >> 3) & ~(cut >> 3); // ... and the third
+        const uint32_t claimed_lossy = (c1 << 1) | (c2 << 2) | (c3 << 3);
+        const uint32_t whole = (c1 & ~l3) | (c2 & ~l4) | c3; // leads that claimed all they need
+        const uint32_t bad_lossy = l2 & ~whole;
+        v.lead = (~cont | (cont & ~claimed_lossy)) & own_bits;
+        v.four = l4 & ~bad_lossy & own_bits;
+        v.bad = (bad_lossy | (cont & ~claimed_lossy)) & own_bits;
+    }
     if constexpr (OPEN) {
         // `behind`: the window's bytes at and behind the buffer's end -- they are not there YET, so whatever a lead asks of them holds
         // (what a lead forbids, ED A0.. and F4 90.., is asked of bytes that are there: the plain masks, zero behind the end)
@@ -202,15 +234,22 @@ __device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t *total) {
 // The body of the three count kernels, one per form of lane_view.  res[1]: the smallest offending offset (preset to ~0);
 // block_sums[b] = the units of block b's bytes.  OPEN: res[2] (preset to 0) = the bytes at the buffer's end that begin a sequence
 // a later buffer has to complete, 1 .. 3, and the sums are those of the n - res[2] bytes before them.
-template <bool BATCH, bool OPEN>
+// LOSSY: res[1] is the first REPLACED offset, and res[3] (preset to 0) the number of replaced units: one 64-bit add per wave that
+// has any.
+template <bool BATCH, bool OPEN, bool LOSSY = false>
 __device__ __forceinline__ void count_units(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ boff, uint32_t n_hay,
                                             uint32_t *__restrict__ block_sums, unsigned long long *__restrict__ res) {
     const uint32_t o = (blockIdx.x * kU8Threads + threadIdx.x) * kU8Lane;
-    const LaneView v = lane_view<BATCH, OPEN>(in, n, o, boff, n_hay);
+    const LaneView v = lane_view<BATCH, OPEN, LOSSY>(in, n, o, boff, n_hay);
     // lanes are contiguous: the first lane of a wave that saw something holds the wave's smallest offset
     const unsigned long long offenders = __ballot(v.bad != 0);
     if (offenders && lane_id() == (uint32_t)__ffsll((long long)offenders) - 1)
         atomicMin(res + 1, (unsigned long long)(o - 4 + (uint32_t)__ffs((int)v.bad) - 1));
+    if constexpr (LOSSY)
+        if (offenders) { // (wave-uniform)
+            const uint32_t replaced = wave_inclusive_scan((uint32_t)__popc(v.bad));
+            if (lane_id() == kWave - 1) atomicAdd(res + 3, (unsigned long long)replaced);
+        }
     if constexpr (OPEN)
         if (v.tail) res[2] = (unsigned long long)(n - (o - 4 + (uint32_t)__ffs((int)v.tail) - 1));
     uint32_t total;
@@ -233,6 +272,17 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_open_count(const uint8_t *_
 __global__ __launch_bounds__(kU8Threads) void k_utf8_batch_count(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ boff,
                                                                  uint32_t n_hay, uint32_t *__restrict__ block_sums, unsigned long long *__restrict__ res) {
     count_units<true, false>(in, n, boff, n_hay, block_sums, res);
+}
+
+// ... that refuse nothing (lane_view's LOSSY form): a text's, a batch's
+__global__ __launch_bounds__(kU8Threads) void k_utf8_lossy_count(const uint8_t *__restrict__ in, uint32_t n, uint32_t *__restrict__ block_sums,
+                                                                 unsigned long long *__restrict__ res) {
+    count_units<false, false, true>(in, n, nullptr, 0, block_sums, res);
+}
+__global__ __launch_bounds__(kU8Threads) void k_utf8_lossy_batch_count(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ boff,
+                                                                       uint32_t n_hay, uint32_t *__restrict__ block_sums,
+                                                                       unsigned long long *__restrict__ res) {
+    count_units<true, false, true>(in, n, boff, n_hay, block_sums, res);
 }
 
 // one workgroup, 256 block sums a round with a running carry (at most 2^19 blocks: 2048 rounds): block_sums become exclusive
@@ -269,10 +319,16 @@ __device__ __forceinline__ void store_ascii16(const LaneView &v, uint16_t *__res
 
 // The lead at bit k of the lane's window, byte `pos` of the buffer: decodes its code point, stores its one or two units at dst,
 // and the checkpoint of whichever of them has an index that is a multiple of 32 -- u is the index of the first, among the units
-// that the checkpoints count.  Returns the number of units.
+// that the checkpoints count.  Returns the number of units.  LOSSY: a replaced start (v.bad) is one unit, U+FFFD.
+template <bool LOSSY = false>
 __device__ __forceinline__ uint32_t store_lead(const LaneView &v, int k, uint32_t pos, uint16_t *__restrict__ dst, uint32_t u, uint32_t *__restrict__ ckpt) {
     const uint32_t b0 = v.byte(k), b1 = v.byte(k + 1) & 0x3fu, b2 = v.byte(k + 2) & 0x3fu, b3 = v.byte(k + 3) & 0x3fu;
     if (ckpt && (u & 31u) == 0) ckpt[u >> 5] = pos;
+    if constexpr (LOSSY)
+        if ((v.bad >> k) & 1u) {
+            dst[0] = (uint16_t)0xfffdu;
+            return 1;
+        }
     if (b0 < 0xf0u) {
         const uint32_t cp = b0 < 0x80u ? b0 : (b0 < 0xe0u ? ((b0 & 0x1fu) << 6) | b1 : ((b0 & 0x0fu) << 12) | (b1 << 6) | b2);
         dst[0] = (uint16_t)cp;
@@ -286,13 +342,20 @@ __device__ __forceinline__ uint32_t store_lead(const LaneView &v, int k, uint32_
 }
 
 // The text is known to be well-formed.  out: n_units units; ckpt: one word per 32 units, or nullptr (an all-ASCII text needs none).
-__global__ __launch_bounds__(kU8Threads) void k_utf8_write(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ block_base,
-                                                           uint16_t *__restrict__ out, uint32_t n_units, uint32_t *__restrict__ ckpt) {
+//
+// LOSSY (nothing is known about the text; `starts` given): the START BITMAP as well, one bit per byte, set where a sequence or a
+// subpart begins -- what locate's lossy form walks.  Every lane of the grid stores the 16 bits of its own bytes with one 2-byte
+// store, lanes behind the text zeros: the bitmap has 512 bytes per block, and no bit at or behind n is set.
+template <bool LOSSY>
+__device__ __forceinline__ void write_units(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ block_base, uint16_t *__restrict__ out,
+                                            uint32_t n_units, uint32_t *__restrict__ ckpt, uint16_t *__restrict__ starts) {
     const uint32_t o = (blockIdx.x * kU8Threads + threadIdx.x) * kU8Lane;
-    const LaneView v = lane_view<false>(in, n, o);
+    const LaneView v = lane_view<false, false, LOSSY>(in, n, o);
     const uint32_t cnt = v.units();
     uint32_t total;
     uint32_t u = block_base[blockIdx.x] + block_scan(cnt, &total);
+    if constexpr (LOSSY)
+        if (starts) starts[o / kU8Lane] = (uint16_t)(v.lead >> 4);
     if (!cnt || u + cnt > n_units) return; // (the second: never, the counts are those of k_utf8_count)
     if (v.lead == kU8Own && !v.four && cnt == kU8Lane && ((v.w[1] | v.w[2] | v.w[3] | v.w[4]) & 0x80808080u) == 0 && (u & 7u) == 0) {
         store_ascii16(v, out + u, u, o, ckpt); // (their units begin on a 16-byte boundary of the output)
@@ -300,7 +363,17 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_write(const uint8_t *__rest
     }
 #pragma unroll
     for (int k = 4; k < 20; ++k)
-        if ((v.lead >> k) & 1u) u += store_lead(v, k, o + (uint32_t)(k - 4), out + u, u, ckpt);
+        if ((v.lead >> k) & 1u) u += store_lead<LOSSY>(v, k, o + (uint32_t)(k - 4), out + u, u, ckpt);
+}
+
+__global__ __launch_bounds__(kU8Threads) void k_utf8_write(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ block_base,
+                                                           uint16_t *__restrict__ out, uint32_t n_units, uint32_t *__restrict__ ckpt) {
+    write_units<false>(in, n, block_base, out, n_units, ckpt, nullptr);
+}
+__global__ __launch_bounds__(kU8Threads) void k_utf8_lossy_write(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ block_base,
+                                                                 uint16_t *__restrict__ out, uint32_t n_units, uint32_t *__restrict__ ckpt,
+                                                                 uint16_t *__restrict__ starts) {
+    write_units<true>(in, n, block_base, out, n_units, ckpt, starts);
 }
 
 // k_utf8_write over a batch that is known to be well-formed, haystack by haystack.  out: the text the scan sees, n_units + n_hay
@@ -310,15 +383,19 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_write(const uint8_t *__rest
 // the boundaries at the buffer's end (j = n_hay, and the empty haystacks at the end).  Checkpoints are indexed by the unit WITHOUT
 // separators -- the table of the buffer read as one text, which is well-formed because every haystack is: the two helpers store
 // to out + u + j - 1 and count checkpoints by u.
-__global__ __launch_bounds__(kU8Threads) void k_utf8_batch_write(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ block_base,
-                                                                 uint16_t *__restrict__ out, uint32_t n_units, uint32_t *__restrict__ ckpt,
-                                                                 const uint32_t *__restrict__ boff, uint32_t n_hay, uint32_t *__restrict__ cat_off,
-                                                                 uint32_t sep) {
+// LOSSY: as write_units, the start bitmap of the buffer -- the cuts are in it: a byte at a cut is no claimed byte, so it is a start.
+template <bool LOSSY>
+__device__ __forceinline__ void batch_write_units(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ block_base,
+                                                  uint16_t *__restrict__ out, uint32_t n_units, uint32_t *__restrict__ ckpt,
+                                                  const uint32_t *__restrict__ boff, uint32_t n_hay, uint32_t *__restrict__ cat_off, uint32_t sep,
+                                                  uint16_t *__restrict__ starts) {
     const uint32_t o = (blockIdx.x * kU8Threads + threadIdx.x) * kU8Lane;
-    const LaneView v = lane_view<true>(in, n, o, boff, n_hay);
+    const LaneView v = lane_view<true, false, LOSSY>(in, n, o, boff, n_hay);
     const uint32_t cnt = v.units();
     uint32_t total;
     uint32_t u = block_base[blockIdx.x] + block_scan(cnt, &total);
+    if constexpr (LOSSY)
+        if (starts) starts[o / kU8Lane] = (uint16_t)(v.lead >> 4);
     if (o >= n || u + cnt > n_units) return; // (the second: never, the counts are those of k_utf8_batch_count)
     uint32_t j = v.next;                      // the boundaries [0, j) lie before the byte the lane is at: it is haystack j - 1's
     if (!(v.cut & kU8Own) && o + kU8Lane < n && v.lead == kU8Own && ((v.w[1] | v.w[2] | v.w[3] | v.w[4]) & 0x80808080u) == 0 &&
@@ -338,7 +415,7 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_batch_write(const uint8_t *
             }
         }
         // (j >= 1: a lead is a byte of a haystack, whose boundary has been met)
-        if ((v.lead >> k) & 1u) u += store_lead(v, k, pos, out + u + j - 1u, u, ckpt);
+        if ((v.lead >> k) & 1u) u += store_lead<LOSSY>(v, k, pos, out + u + j - 1u, u, ckpt);
     }
     if (o + kU8Lane >= n) { // the buffer's last lane: u = n_units, what is left are the boundaries at the buffer's end
         while (j <= n_hay) {
@@ -347,6 +424,19 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_batch_write(const uint8_t *
             ++j;
         }
     }
+}
+
+__global__ __launch_bounds__(kU8Threads) void k_utf8_batch_write(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ block_base,
+                                                                 uint16_t *__restrict__ out, uint32_t n_units, uint32_t *__restrict__ ckpt,
+                                                                 const uint32_t *__restrict__ boff, uint32_t n_hay, uint32_t *__restrict__ cat_off,
+                                                                 uint32_t sep) {
+    batch_write_units<false>(in, n, block_base, out, n_units, ckpt, boff, n_hay, cat_off, sep, nullptr);
+}
+__global__ __launch_bounds__(kU8Threads) void k_utf8_lossy_batch_write(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ block_base,
+                                                                       uint16_t *__restrict__ out, uint32_t n_units, uint32_t *__restrict__ ckpt,
+                                                                       const uint32_t *__restrict__ boff, uint32_t n_hay, uint32_t *__restrict__ cat_off,
+                                                                       uint32_t sep, uint16_t *__restrict__ starts) {
+    batch_write_units<true>(in, n, block_base, out, n_units, ckpt, boff, n_hay, cat_off, sep, starts);
 }
 
 __device__ __forceinline__ uint32_t seq_len(uint32_t lead) { return lead < 0x80u ? 1u : (lead < 0xe0u ? 2u : (lead < 0xf0u ? 3u : 4u)); }
@@ -360,6 +450,21 @@ struct SeqPos {
 // surrogate, its pair's -- reached from the checkpoint at or below `unit` by a walk of at most 31 units over the lead bytes.
 // resume: s stands at a unit of the same 32 that is not behind `unit`, the walk goes on from there.  Returns the sequence's
 // length in bytes.
+//
+// LOSSY: `in` is the START BITMAP of the buffer instead (k_utf8_lossy_write), no byte is read.  The length of the start at p is
+// the distance to the next set bit, clamped to n: 4 for a well-formed 4-byte sequence and for nothing else (a subpart has at most
+// 3 bytes), so that is where a start has two units.  Cuts need no thought here: a walk that begins in an earlier haystack passes
+// them as starts like any other -- "E2 82 | AC" is two starts, never a euro sign.
+__device__ __forceinline__ uint32_t start_len(const uint32_t *__restrict__ starts, uint32_t n, uint32_t p) {
+    if (p + 1u >= n) return n - p;
+    const uint32_t w = (p + 1u) >> 5, sh = (p + 1u) & 31u;
+    const uint32_t lo = starts[w], hi = (sh > 29u && ((w + 1u) << 5) < n) ? starts[w + 1u] : 0u; // (a word behind the text's bits is not read)
+    const uint32_t bits = (uint32_t)((((uint64_t)hi << 32) | lo) >> sh) & 7u;                    // the starts at p + 1 .. p + 3
+    const uint32_t len = bits ? (uint32_t)__ffs((int)bits) : 4u;
+    return len < n - p ? len : n - p;
+}
+
+template <bool LOSSY = false>
 __device__ __forceinline__ uint32_t locate(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ ckpt, uint32_t unit, SeqPos &s,
                                            bool resume = false) {
     if (!resume) {
@@ -369,7 +474,8 @@ __device__ __forceinline__ uint32_t locate(const uint8_t *__restrict__ in, uint3
     }
     uint32_t len = 1;
     while (s.p < n) {
-        len = seq_len(in[s.p]);
+        if constexpr (LOSSY) len = start_len(reinterpret_cast<const uint32_t *>(in), n, s.p);
+        else len = seq_len(in[s.p]);
         const uint32_t nu = len == 4 ? 2u : 1u;
         if (unit < s.u + nu) break;
         s.u += nu;
@@ -381,7 +487,8 @@ __device__ __forceinline__ uint32_t locate(const uint8_t *__restrict__ in, uint3
 // A record's units first .. last of the buffer read as one text (n_units of them, WITHOUT separators) -> *start, the first byte
 // of the code point that holds unit first, and *end, one past the last byte of the one that holds unit last (a match has at
 // least one unit), both minus `base`: a haystack's first byte, or 0.  A range that is none is left alone (never: the scan's
-// records lie inside the text).  ckpt == nullptr: an all-ASCII buffer, where a unit is its byte.
+// records lie inside the text).  ckpt == nullptr: an all-ASCII buffer, where a unit is its byte.  LOSSY: locate's, `in` the bitmap.
+template <bool LOSSY = false>
 __device__ __forceinline__ void batch_bytes(uint32_t first, uint32_t last, uint32_t base, const uint8_t *__restrict__ in, uint32_t n, uint32_t n_units,
                                             const uint32_t *__restrict__ ckpt, int32_t *start, int32_t *end) {
     if (first > last || last >= n_units) return;
@@ -391,15 +498,15 @@ __device__ __forceinline__ void batch_bytes(uint32_t first, uint32_t last, uint3
         return;
     }
     SeqPos s;
-    (void)locate(in, n, ckpt, first, s);
+    (void)locate<LOSSY>(in, n, ckpt, first, s);
     *start = (int32_t)(s.p - base);
-    const uint32_t len = locate(in, n, ckpt, last, s, (last >> 5) == (first >> 5));
+    const uint32_t len = locate<LOSSY>(in, n, ckpt, last, s, (last >> 5) == (first >> 5));
     *end = (int32_t)(s.p + len - base);
 }
 
 // k_batch_tag and the map in one, a lane per record: {start, end[, id]} in units of the batch's text -> {haystack, start, end[, id]}
 // in bytes of the haystack
-template <int REC>
+template <int REC, bool LOSSY = false>
 __global__ __launch_bounds__(kU8Threads) void k_utf8_batch_tag(const int32_t *__restrict__ recs, uint64_t cnt, const uint32_t *__restrict__ cat_off,
                                                                uint32_t n_hay, const uint32_t *__restrict__ boff, const uint8_t *__restrict__ in, uint32_t n,
                                                                uint32_t n_units, const uint32_t *__restrict__ ckpt, int32_t *__restrict__ out) {
@@ -412,7 +519,7 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_batch_tag(const int32_t *__
     o[0] = (int32_t)h;
     if (W == 3) o[3] = recs[i * W + 2];
     // (no match holds a separator: both ends are units of haystack h)
-    batch_bytes(start - h, end - 1u - h, boff[h], in, n, n_units, ckpt, o + 1, o + 2);
+    batch_bytes<LOSSY>(start - h, end - 1u - h, boff[h], in, n, n_units, ckpt, o + 1, o + 2);
 }
 
 // A lane per record of `cols` words, in place: {start, end} in units of the scan's text -> bytes of the buffer.  The text is a
@@ -420,6 +527,7 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_batch_tag(const int32_t *__
 // record's haystack h -- 0 then -- is also the number of separators in front of it, so its units in the buffer read as one text
 // are start - h .. end - 1 - h.  The bytes are relative to the SPAN's first byte, not the haystack's -- plan and emit work on the
 // span, which has no separators.  In an all-ASCII batch the shift is all there is to do -- but it is still to do.
+template <bool LOSSY = false>
 __global__ __launch_bounds__(kU8Threads) void k_utf8_batch_map(int32_t *__restrict__ recs, uint64_t cnt, uint32_t cols, const uint32_t *__restrict__ cat_off,
                                                                uint32_t n_hay, const uint8_t *__restrict__ in, uint32_t n, uint32_t n_units,
                                                                const uint32_t *__restrict__ ckpt) {
@@ -428,7 +536,7 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_batch_map(int32_t *__restri
     int32_t *r = recs + i * cols;
     const uint32_t start = (uint32_t)r[0], end = (uint32_t)r[1];
     const uint32_t h = haystack_of(cat_off, n_hay, start); // (n_hay == 0: 0, and cat_off is not read)
-    batch_bytes(start - h, end - 1u - h, 0u, in, n, n_units, ckpt, r, r + 1);
+    batch_bytes<LOSSY>(start - h, end - 1u - h, 0u, in, n, n_units, ckpt, r, r + 1);
 }
 
 // One lane: unit x of the scan's text -> *out, a byte of the buffer (a piece's boundary, see replace_limit in acgpu_replace.hip).
@@ -467,6 +575,7 @@ __global__ void k_utf8_batch_pos(uint32_t x, const uint32_t *__restrict__ cat_of
 // A lane per haystack, behind the last piece of a summary call: the first record of every entry that has one, from units
 // relative to its haystack to bytes relative to it.  cat_off given: entry i is haystack i of a batch's text (its first unit
 // without separators is cat_off[i] - i, its first byte boff[i]); not given: the entries' one text is `in` itself.
+template <bool LOSSY = false>
 __global__ __launch_bounds__(kU8Threads) void k_summary_utf8_bytes(acgpu_batch_summary *__restrict__ sum, uint32_t n_entries, const uint32_t *__restrict__ cat_off,
                                                                    const uint32_t *__restrict__ boff, const uint8_t *__restrict__ in, uint32_t n,
                                                                    uint32_t n_units, const uint32_t *__restrict__ ckpt) {
@@ -475,22 +584,28 @@ __global__ __launch_bounds__(kU8Threads) void k_summary_utf8_bytes(acgpu_batch_s
     acgpu_batch_summary *e = sum + i;
     if (!e->n_matches || e->start < 0 || e->end <= e->start) return;
     const uint32_t unit0 = cat_off ? cat_off[i] - i : 0u, byte0 = cat_off ? boff[i] : 0u;
-    batch_bytes(unit0 + (uint32_t)e->start, unit0 + (uint32_t)e->end - 1u, byte0, in, n, n_units, ckpt, &e->start, &e->end);
+    batch_bytes<LOSSY>(unit0 + (uint32_t)e->start, unit0 + (uint32_t)e->end - 1u, byte0, in, n, n_units, ckpt, &e->start, &e->end);
 }
 
 } // namespace
 
 namespace acgpu {
 
+// what locate walks from a checkpoint: the bytes, or a lossy text's start bitmap
+static const uint8_t *walked(const Utf8Text &text) { return text.lossy ? reinterpret_cast<const uint8_t *>(text.d_starts) : text.d_bytes; }
+
 int utf8_map_records(const Utf8Text &text, const Utf8Batch *b, int32_t *d_recs, uint64_t cnt, uint32_t cols, hipStream_t stream) {
     if (!cnt || (!b && !text.d_ckpt)) return ACGPU_OK; // (a batch is mapped also when it is all ASCII: its records stand behind separators)
-    hipLaunchKernelGGL(k_utf8_batch_map, dim3((unsigned)((cnt + kU8Threads - 1) / kU8Threads)), dim3(kU8Threads), 0, stream, d_recs, cnt, cols,
-                       b ? b->d_cat_off : nullptr, b ? b->n_haystacks : 0u, text.d_bytes, (uint32_t)text.n_bytes, (uint32_t)text.n_units, text.d_ckpt);
+    // (lossy: the walk reads the start bitmap where the strict one reads the bytes)
+    hipLaunchKernelGGL(text.lossy ? k_utf8_batch_map<true> : k_utf8_batch_map<false>, dim3((unsigned)((cnt + kU8Threads - 1) / kU8Threads)),
+                       dim3(kU8Threads), 0, stream, d_recs, cnt, cols, b ? b->d_cat_off : nullptr, b ? b->n_haystacks : 0u, walked(text),
+                       (uint32_t)text.n_bytes, (uint32_t)text.n_units, text.d_ckpt);
     HIP_TRY(hipGetLastError());
     return ACGPU_OK;
 }
 
 int utf8_map_position(const Utf8Text &text, const Utf8Batch *b, uint64_t unit, int64_t *d_out, hipStream_t stream) {
+    if (text.lossy) return ACGPU_E_INVALID; // (replace is not built in lossy form)
     if (b ? !b->d_cat_off || !b->n_haystacks || unit >= (1ull << 32)
           : !text.d_ckpt || unit >= text.n_units) // (a checkpoint is written for the text's units only)
         return ACGPU_E_INVALID;
@@ -504,26 +619,30 @@ namespace {
 
 // What the front ends keep on the device around the scan's text: the caller's bytes in d.utf8_in, with room for a lane's 16-byte
 // load and the 4 bytes behind it, and in d.utf8_aux, each part 64-byte aligned,
-//   [n_units, first_bad, tail | block sums | checkpoints, one per 32 units of a text that has at most n units | a batch's byte offsets]
+//   [n_units, first_bad, tail, n_replaced | block sums | checkpoints, one per 32 units of a text that has at most n units |
+//    a batch's byte offsets | lossy: the start bitmap, 512 bytes per block]
 struct Utf8Aux {
     uint32_t n = 0, n_blocks = 0; // the buffer's bytes, and its blocks of 4096
     const uint8_t *in = nullptr;
     unsigned long long *res = nullptr;
     uint32_t *sums = nullptr, *ckpt = nullptr, *boff = nullptr; // boff: n_off words
-    int ensure(DeviceState &d, uint32_t n_bytes, size_t n_off = 0) {
+    uint16_t *starts = nullptr;                                  // lossy: 16 bits per lane of the write kernel's grid
+    int ensure(DeviceState &d, uint32_t n_bytes, size_t n_off = 0, bool lossy = false) {
         auto up64 = [](size_t x) { return (x + 63) & ~(size_t)63; };
         n = n_bytes;
         n_blocks = (n + kU8Block - 1) / kU8Block;
         const size_t sums_off = 64, ckpt_off = sums_off + up64((size_t)n_blocks * 4), boff_off = ckpt_off + up64(((size_t)n / 32 + 1) * 4);
         int rc;
         if ((rc = d.utf8_in.ensure((size_t)n + 64))) return rc;
-        if ((rc = d.utf8_aux.ensure(boff_off + n_off * 4))) return rc;
+        const size_t starts_off = boff_off + up64(n_off * 4);
+        if ((rc = d.utf8_aux.ensure(lossy ? starts_off + (size_t)n_blocks * (kU8Block / 8) : boff_off + n_off * 4))) return rc;
         char *aux = (char *)d.utf8_aux.p;
         in = reinterpret_cast<const uint8_t *>(d.utf8_in.p);
         res = reinterpret_cast<unsigned long long *>(aux);
         sums = reinterpret_cast<uint32_t *>(aux + sums_off);
         ckpt = reinterpret_cast<uint32_t *>(aux + ckpt_off);
         boff = reinterpret_cast<uint32_t *>(aux + boff_off);
+        starts = lossy ? reinterpret_cast<uint16_t *>(aux + starts_off) : nullptr;
         return ACGPU_OK;
     }
 };
@@ -532,10 +651,20 @@ struct Utf8Aux {
 // (n_hay != 0: a batch with its offsets in x.boff; open: a text that goes on), the scan of the block sums, and the one wait this
 // front end adds -- the shard cannot be sized, nor the scan begun, before the text is known to be well-formed.  Fills in
 // n_units, first_bad, tail, n_bytes (the bytes before the held prefix), d_bytes and d_ckpt, the table the write kernel is to fill.
-int utf8_validate(const Utf8Aux &x, uint32_t n_hay, bool open, hipStream_t stream, Utf8Text *text) {
+// errors == replace (not open): the lossy count kernels, n_replaced with the rest in the one wait, and the call goes on whatever
+// they saw; d_starts with d_ckpt, the bitmap the write kernel is to fill.
+int utf8_validate(const Utf8Aux &x, uint32_t n_hay, bool open, Utf8Errors errors, hipStream_t stream, Utf8Text *text) {
     const dim3 grid(x.n_blocks), block(kU8Threads);
+    const bool lossy = errors == Utf8Errors::replace;
+    if (lossy && open) return ACGPU_E_INVALID;
     HIP_TRY(hipMemsetAsync(x.res, 0xff, 16, stream));
-    if (n_hay) {
+    if (lossy) {
+        HIP_TRY(hipMemsetAsync(x.res + 3, 0, 8, stream));
+        if (n_hay)
+            hipLaunchKernelGGL(k_utf8_lossy_batch_count, grid, block, 0, stream, x.in, x.n, (const uint32_t *)x.boff, n_hay, x.sums, x.res);
+        else
+            hipLaunchKernelGGL(k_utf8_lossy_count, grid, block, 0, stream, x.in, x.n, x.sums, x.res);
+    } else if (n_hay) {
         hipLaunchKernelGGL(k_utf8_batch_count, grid, block, 0, stream, x.in, x.n, (const uint32_t *)x.boff, n_hay, x.sums, x.res);
     } else if (open) {
         HIP_TRY(hipMemsetAsync(x.res + 2, 0, 8, stream));
@@ -545,19 +674,29 @@ int utf8_validate(const Utf8Aux &x, uint32_t n_hay, bool open, hipStream_t strea
     }
     hipLaunchKernelGGL(k_utf8_scan, dim3(1), block, 0, stream, x.sums, x.n_blocks, x.res);
     HIP_TRY(hipGetLastError());
-    unsigned long long h_res[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h_res, x.res, open ? 24 : 16, hipMemcpyDeviceToHost, stream));
+    unsigned long long h_res[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h_res, x.res, lossy ? 32 : (open ? 24 : 16), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream)); // (what the copies in front read on the host has been read by now, too)
     text->n_units = h_res[0];
     text->first_bad = (int64_t)h_res[1];
-    if (text->first_bad >= 0) return ACGPU_E_ENCODING;
+    text->lossy = lossy;
+    if (lossy) {
+        h_res[2] = 0; // (no held prefix; the word was not preset)
+        text->n_replaced = h_res[3];
+        if ((text->first_bad >= 0) != (text->n_replaced != 0) || text->n_replaced > x.n) return ACGPU_E_HIP; // (never)
+    } else if (text->first_bad >= 0) {
+        return ACGPU_E_ENCODING;
+    }
     if (h_res[2] > 3 || h_res[2] > x.n) return ACGPU_E_HIP; // (never: a held prefix is one to three bytes of the buffer)
     text->tail = (uint32_t)h_res[2];
     // the text that is transcoded: the bytes before the held prefix -- they end where a sequence ends, well-formed on their own
     text->n_bytes = x.n - text->tail;
     if (text->n_units > text->n_bytes) return ACGPU_E_HIP; // (never: a sequence has no more units than bytes)
     text->d_bytes = x.in;
-    text->d_ckpt = text->n_units == text->n_bytes ? nullptr : x.ckpt; // (an all-ASCII text needs none)
+    // an all-ASCII text needs none -- nor does a lossy text with as many units as bytes: then every start is one byte and one unit
+    // ("a\x80b"), the map is the identity, and no bitmap is written either
+    text->d_ckpt = text->n_units == text->n_bytes ? nullptr : x.ckpt;
+    text->d_starts = lossy && text->d_ckpt ? reinterpret_cast<const uint32_t *>(x.starts) : nullptr;
     return ACGPU_OK;
 }
 
@@ -570,23 +709,28 @@ void whole_shard(const DeviceState &d, uint64_t n_units, acgpu_shard *sh) {
 
 } // namespace
 
-int stage_utf8_text(DeviceState &d, const uint8_t *bytes, uint64_t n_bytes, hipStream_t stream, Utf8Text *out) {
-    return stage_utf8_parts(d, nullptr, 0, bytes, n_bytes, /*open=*/false, stream, out);
+int stage_utf8_text(DeviceState &d, const uint8_t *bytes, uint64_t n_bytes, hipStream_t stream, Utf8Text *out, Utf8Errors errors) {
+    return stage_utf8_parts(d, nullptr, 0, bytes, n_bytes, /*open=*/false, stream, out, errors);
 }
 
 int stage_utf8_parts(DeviceState &d, const uint8_t *head, uint64_t n_head, const uint8_t *bytes, uint64_t n_rest, bool open, hipStream_t stream,
-                     Utf8Text *out) {
+                     Utf8Text *out, Utf8Errors errors) {
     *out = Utf8Text{};
     out->n_bytes = n_head + n_rest;
+    const bool lossy = errors == Utf8Errors::replace;
     Utf8Aux x;
     int rc;
-    if ((rc = x.ensure(d, (uint32_t)(n_head + n_rest)))) return rc;
+    if ((rc = x.ensure(d, (uint32_t)(n_head + n_rest), 0, lossy))) return rc;
     if (n_head) HIP_TRY(hipMemcpyAsync(d.utf8_in.p, head, n_head, hipMemcpyHostToDevice, stream));
     if (n_rest) HIP_TRY(hipMemcpyAsync((char *)d.utf8_in.p + n_head, bytes, n_rest, hipMemcpyHostToDevice, stream));
-    if ((rc = utf8_validate(x, 0, open, stream, out))) return rc;
+    if ((rc = utf8_validate(x, 0, open, errors, stream, out))) return rc;
     if ((rc = d.stage_hay.ensure(out->n_units * 2 + 16))) return rc;
     const uint32_t n_text = (uint32_t)out->n_bytes, n_text_blocks = (n_text + kU8Block - 1) / kU8Block;
-    if (n_text_blocks) // (a buffer that is a held prefix and nothing else has no unit to write)
+    if (lossy) // (n_text = n: nothing is held, the grid is the one the bitmap was sized for)
+        hipLaunchKernelGGL(k_utf8_lossy_write, dim3(n_text_blocks), dim3(kU8Threads), 0, stream, x.in, n_text, (const uint32_t *)x.sums,
+                           reinterpret_cast<uint16_t *>(d.stage_hay.p), (uint32_t)out->n_units, out->d_ckpt ? x.ckpt : nullptr,
+                           out->d_starts ? x.starts : nullptr);
+    else if (n_text_blocks) // (a buffer that is a held prefix and nothing else has no unit to write)
         hipLaunchKernelGGL(k_utf8_write, dim3(n_text_blocks), dim3(kU8Threads), 0, stream, x.in, n_text, (const uint32_t *)x.sums,
                            reinterpret_cast<uint16_t *>(d.stage_hay.p), (uint32_t)out->n_units, out->d_ckpt ? x.ckpt : nullptr);
     HIP_TRY(hipGetLastError());
@@ -595,7 +739,7 @@ int stage_utf8_parts(DeviceState &d, const uint8_t *head, uint64_t n_head, const
 }
 
 int stage_utf8_batch(DeviceState &d, const HostTables &t, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_hay, hipStream_t stream,
-                     Utf8Batch *out, bool validate_only) {
+                     Utf8Batch *out, bool validate_only, Utf8Errors errors) {
     *out = Utf8Batch{};
     out->n_haystacks = n_hay;
     const uint32_t n = (uint32_t)(offsets[n_hay] - offsets[0]);
@@ -603,7 +747,8 @@ int stage_utf8_batch(DeviceState &d, const HostTables &t, const uint8_t *bytes, 
     const size_t off_bytes = ((size_t)n_hay + 1) * 4;
     Utf8Aux x;
     int rc;
-    if ((rc = x.ensure(d, n, (size_t)n_hay + 1))) return rc;
+    const bool lossy = errors == Utf8Errors::replace;
+    if ((rc = x.ensure(d, n, (size_t)n_hay + 1, lossy))) return rc;
     if ((rc = d.batch_off.ensure(off_bytes + 16))) return rc;
     std::vector<uint32_t> &h_boff = out->h_boff;
     try {
@@ -614,8 +759,8 @@ int stage_utf8_batch(DeviceState &d, const HostTables &t, const uint8_t *bytes, 
     for (uint32_t i = 0; i <= n_hay; i++) h_boff[i] = (uint32_t)(offsets[i] - offsets[0]);
     HIP_TRY(hipMemcpyAsync(d.utf8_in.p, bytes + offsets[0], n, hipMemcpyHostToDevice, stream)); // the caller's span as it lies: one copy
     HIP_TRY(hipMemcpyAsync(x.boff, h_boff.data(), off_bytes, hipMemcpyHostToDevice, stream));
-    rc = utf8_validate(x, n_hay, /*open=*/false, stream, &out->text);
-    if (rc == ACGPU_E_ENCODING) {
+    rc = utf8_validate(x, n_hay, /*open=*/false, errors, stream, &out->text);
+    if (rc == ACGPU_E_ENCODING || (rc == ACGPU_OK && out->text.first_bad >= 0)) { // (the second: a lossy batch that had something replaced)
         // the haystack that holds byte p: the LAST j < n_hay with offset <= p (of several at one byte all but the last are empty)
         const uint32_t p = (uint32_t)out->text.first_bad;
         const uint32_t j = (uint32_t)(std::upper_bound(h_boff.begin(), h_boff.begin() + n_hay, p) - h_boff.begin()) - 1u;
@@ -626,14 +771,20 @@ int stage_utf8_batch(DeviceState &d, const HostTables &t, const uint8_t *bytes, 
     out->d_boff = x.boff;
     if (validate_only) {
         out->text.d_ckpt = nullptr; // (no table is written)
+        out->text.d_starts = nullptr;
         return ACGPU_OK;
     }
     const uint64_t cat = out->text.n_units + n_hay;
     uint32_t *d_cat_off = reinterpret_cast<uint32_t *>(d.batch_off.p);
     if ((rc = d.stage_hay.ensure(cat * 2 + 16))) return rc;
-    hipLaunchKernelGGL(k_utf8_batch_write, dim3(x.n_blocks), dim3(kU8Threads), 0, stream, x.in, n, (const uint32_t *)x.sums,
-                       reinterpret_cast<uint16_t *>(d.stage_hay.p), (uint32_t)out->text.n_units, out->text.d_ckpt ? x.ckpt : nullptr,
-                       (const uint32_t *)x.boff, n_hay, d_cat_off, (uint32_t)(uint16_t)t.sep_unit);
+    if (lossy)
+        hipLaunchKernelGGL(k_utf8_lossy_batch_write, dim3(x.n_blocks), dim3(kU8Threads), 0, stream, x.in, n, (const uint32_t *)x.sums,
+                           reinterpret_cast<uint16_t *>(d.stage_hay.p), (uint32_t)out->text.n_units, out->text.d_ckpt ? x.ckpt : nullptr,
+                           (const uint32_t *)x.boff, n_hay, d_cat_off, (uint32_t)(uint16_t)t.sep_unit, out->text.d_starts ? x.starts : nullptr);
+    else
+        hipLaunchKernelGGL(k_utf8_batch_write, dim3(x.n_blocks), dim3(kU8Threads), 0, stream, x.in, n, (const uint32_t *)x.sums,
+                           reinterpret_cast<uint16_t *>(d.stage_hay.p), (uint32_t)out->text.n_units, out->text.d_ckpt ? x.ckpt : nullptr,
+                           (const uint32_t *)x.boff, n_hay, d_cat_off, (uint32_t)(uint16_t)t.sep_unit);
     HIP_TRY(hipGetLastError());
     whole_shard(d, cat, &out->text.shard);
     out->d_cat_off = d_cat_off;
@@ -648,35 +799,37 @@ int utf8_batch_tag(const Utf8Batch &b, const void *d_recs, uint64_t cnt, int rec
     }
     const dim3 grid((unsigned)((cnt + kU8Threads - 1) / kU8Threads)), block(kU8Threads);
     const uint32_t n = (uint32_t)b.text.n_bytes, n_units = (uint32_t)b.text.n_units;
-    if (record_kind == ACGPU_REC_SET)
-        hipLaunchKernelGGL(k_utf8_batch_tag<ACGPU_REC_SET>, grid, block, 0, stream, (const int32_t *)d_recs, cnt, b.d_cat_off, b.n_haystacks, b.d_boff,
-                           b.text.d_bytes, n, n_units, b.text.d_ckpt, (int32_t *)d_out);
-    else
-        hipLaunchKernelGGL(k_utf8_batch_tag<ACGPU_REC_MAP>, grid, block, 0, stream, (const int32_t *)d_recs, cnt, b.d_cat_off, b.n_haystacks, b.d_boff,
-                           b.text.d_bytes, n, n_units, b.text.d_ckpt, (int32_t *)d_out);
+    const bool set = record_kind == ACGPU_REC_SET;
+    const auto kernel = b.text.lossy ? (set ? k_utf8_batch_tag<ACGPU_REC_SET, true> : k_utf8_batch_tag<ACGPU_REC_MAP, true>)
+                                     : (set ? k_utf8_batch_tag<ACGPU_REC_SET, false> : k_utf8_batch_tag<ACGPU_REC_MAP, false>);
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, (const int32_t *)d_recs, cnt, b.d_cat_off, b.n_haystacks, b.d_boff, walked(b.text), n, n_units,
+                       b.text.d_ckpt, (int32_t *)d_out);
     HIP_TRY(hipGetLastError());
     return ACGPU_OK;
 }
 
 int utf8_summary_bytes(const Utf8Batch *b, const Utf8Text &text, acgpu_batch_summary *d_sum, uint32_t n_entries, hipStream_t stream) {
     if (!text.d_ckpt || !n_entries) return ACGPU_OK;
-    hipLaunchKernelGGL(k_summary_utf8_bytes, dim3((n_entries + kU8Threads - 1) / kU8Threads), dim3(kU8Threads), 0, stream, d_sum, n_entries,
-                       b ? b->d_cat_off : nullptr, b ? b->d_boff : nullptr, text.d_bytes, (uint32_t)text.n_bytes, (uint32_t)text.n_units, text.d_ckpt);
+    hipLaunchKernelGGL(text.lossy ? k_summary_utf8_bytes<true> : k_summary_utf8_bytes<false>, dim3((n_entries + kU8Threads - 1) / kU8Threads),
+                       dim3(kU8Threads), 0, stream, d_sum, n_entries, b ? b->d_cat_off : nullptr, b ? b->d_boff : nullptr, walked(text),
+                       (uint32_t)text.n_bytes, (uint32_t)text.n_units, text.d_ckpt);
     HIP_TRY(hipGetLastError());
     return ACGPU_OK;
 }
 
 } // namespace acgpu
 
-extern "C" {
+namespace {
 
-int acgpu_match_utf8(const acgpu_automaton *ca, const uint8_t *bytes, uint64_t n_bytes, int record_kind, void *out, uint64_t cap,
-                     uint64_t *n_out, acgpu_utf8_stats *stats) {
+// The body of acgpu_match_utf8 and acgpu_match_utf8_lossy.  P (acgpu_host.h): how the text is staged, and the entry's stats.
+template <class P>
+int match_utf8(const acgpu_automaton *ca, const uint8_t *bytes, uint64_t n_bytes, int record_kind, void *out, uint64_t cap, uint64_t *n_out,
+               typename P::Stats *stats) {
     if (!ca || !n_out || (n_bytes && !bytes) || (cap && !out)) return ACGPU_E_INVALID;
     if (record_kind != ACGPU_REC_SET && record_kind != ACGPU_REC_MAP) return ACGPU_E_INVALID;
     if (n_bytes >= (1ull << 31)) return ACGPU_E_INVALID;
     *n_out = 0;
-    if (stats) *stats = utf8_stats();
+    if (stats) *stats = P::stats();
     if (n_bytes == 0) return ACGPU_OK; // (nothing to decode and nothing to find: no device needed)
     acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
     PoolCall call(a);
@@ -686,9 +839,9 @@ int acgpu_match_utf8(const acgpu_automaton *ca, const uint8_t *bytes, uint64_t n
     if ((rc = call.idle())) return rc; // (the NULL stream: see the stream rule)
     const hipStream_t stream = d.call_stream;
     Utf8Text text;
-    rc = stage_utf8_text(d, bytes, n_bytes, stream, &text);
+    rc = stage_utf8_text(d, bytes, n_bytes, stream, &text, P::errors);
     if (rc && rc != ACGPU_E_ENCODING) return call.fail(rc);
-    if (stats) *stats = utf8_stats(&text, rc);
+    if (stats) *stats = P::stats(&text, rc);
     if (rc) return rc; // (ACGPU_E_ENCODING.  The stream is idle: the pool is as usable as before the call)
     if ((rc = d.stage_out.ensure(cap * (uint64_t)record_kind + 16))) return call.fail(rc);
     rc = match_shard(a, d, &text.shard, record_kind, d.stage_out.p, cap, n_out, stream, nullptr);
@@ -700,8 +853,10 @@ int acgpu_match_utf8(const acgpu_automaton *ca, const uint8_t *bytes, uint64_t n
     return ACGPU_OK;
 }
 
-int acgpu_match_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks, int record_kind,
-                           void *out, uint64_t cap, uint64_t *n_out, acgpu_utf8_batch_stats *stats) {
+// The body of acgpu_match_batch_utf8 and acgpu_match_batch_utf8_lossy
+template <class P>
+int match_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks, int record_kind, void *out,
+                     uint64_t cap, uint64_t *n_out, typename P::Stats *stats) {
     if (!ca || !n_out || !offsets || (cap && !out)) return ACGPU_E_INVALID;
     if (record_kind != ACGPU_REC_SET && record_kind != ACGPU_REC_MAP) return ACGPU_E_INVALID;
     acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
@@ -710,7 +865,7 @@ int acgpu_match_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, cons
     int rc = check_batch(t, reinterpret_cast<const uint16_t *>(bytes), offsets, n_haystacks, &plan);
     if (rc) return rc;
     *n_out = 0;
-    if (stats) *stats = utf8_batch_stats();
+    if (stats) *stats = P::stats();
     if (plan.total == 0) return ACGPU_OK; // (nothing to decode and nothing to find: no device needed)
     PoolCall call(a);
     if (call.rc) return call.rc;
@@ -718,9 +873,9 @@ int acgpu_match_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, cons
     if ((rc = call.idle())) return rc; // (the NULL stream: see the stream rule)
     const hipStream_t stream = d.call_stream;
     Utf8Batch b;
-    rc = stage_utf8_batch(d, t, bytes, offsets, n_haystacks, stream, &b, plan.per_haystack);
+    rc = stage_utf8_batch(d, t, bytes, offsets, n_haystacks, stream, &b, plan.per_haystack, P::errors);
     if (rc && rc != ACGPU_E_ENCODING) return call.fail(rc);
-    if (stats) *stats = utf8_batch_stats(&b, rc);
+    if (stats) *stats = P::stats(&b, rc);
     if (rc) return rc; // (ACGPU_E_ENCODING.  The stream is idle: the pool is as usable as before the call)
     const uint64_t W = (uint64_t)record_kind / 4, out_rec = (uint64_t)record_kind + 4;
     if (plan.per_haystack) { // every haystack by the route acgpu_match_utf8 takes, tagged on the host
@@ -732,7 +887,7 @@ int acgpu_match_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, cons
             uint64_t got = 0;
             const uint64_t room = cap > n ? cap - n : 0;
             Utf8Text text;
-            if ((rc = stage_utf8_text(d, bytes + offsets[i], len, stream, &text))) return call.fail(rc == ACGPU_E_ENCODING ? ACGPU_E_HIP : rc);
+            if ((rc = stage_utf8_text(d, bytes + offsets[i], len, stream, &text, P::errors))) return call.fail(rc == ACGPU_E_ENCODING ? ACGPU_E_HIP : rc);
             if ((rc = d.stage_out.ensure(room * (uint64_t)record_kind + 16))) return call.fail(rc);
             rc = match_shard(a, d, &text.shard, record_kind, d.stage_out.p, room, &got, stream, nullptr);
             if (rc != ACGPU_OK && rc != ACGPU_E_OVERFLOW) return call.fail(rc);
@@ -769,6 +924,30 @@ int acgpu_match_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, cons
     if (hipMemcpyAsync(out, d.batch_out.p, *n_out * out_rec, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
         return call.fail(ACGPU_E_HIP);
     return ACGPU_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int acgpu_match_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, int record_kind, void *out, uint64_t cap, uint64_t *n_out,
+                     acgpu_utf8_stats *stats) {
+    return match_utf8<Utf8StrictText>(a, bytes, n_bytes, record_kind, out, cap, n_out, stats);
+}
+
+int acgpu_match_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, int record_kind, void *out, uint64_t cap,
+                           uint64_t *n_out, acgpu_utf8_lossy_stats *stats) {
+    return match_utf8<Utf8LossyText>(a, bytes, n_bytes, record_kind, out, cap, n_out, stats);
+}
+
+int acgpu_match_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks, int record_kind, void *out,
+                           uint64_t cap, uint64_t *n_out, acgpu_utf8_batch_stats *stats) {
+    return match_batch_utf8<Utf8StrictBatch>(a, bytes, offsets, n_haystacks, record_kind, out, cap, n_out, stats);
+}
+
+int acgpu_match_batch_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks, int record_kind,
+                                 void *out, uint64_t cap, uint64_t *n_out, acgpu_utf8_lossy_stats *stats) {
+    return match_batch_utf8<Utf8LossyBatch>(a, bytes, offsets, n_haystacks, record_kind, out, cap, n_out, stats);
 }
 
 } // extern "C"

@@ -67,6 +67,16 @@ def utf8_line_offsets(data):
     return np.concatenate([np.zeros(1, np.uint64), ends, np.array(tail, np.uint64)])
 
 
+def _utf8_entry(name, strict_stats, errors):
+    """(the native entry, its stats type) for errors="strict" | "replace" -- the lossy entries scan every maximal ill-formed
+    subpart as one U+FFFD, as bytes.decode("utf-8", "replace") does; anything else is refused before a native call"""
+    if errors == "strict":
+        return getattr(N.lib(), name), strict_stats
+    if errors == "replace":
+        return getattr(N.lib(), name + "_lossy"), N.Utf8LossyStats
+    raise ValueError("errors must be 'strict' or 'replace', not %r" % (errors,))
+
+
 def _pack_utf8(data, offsets):
     """-> (uint8 buffer, uint64 offsets): a sequence of bytes-like haystacks joined once, or with `offsets` ONE buffer used in place"""
     if offsets is not None:
@@ -179,10 +189,13 @@ class Automaton:
             N.check(rc, "acgpu_match_u16_multi" if devs is not None else "acgpu_match_u16")
             return out[:n_out.value]
 
-    def match_utf8(self, data, with_ids, cap=None, stats=None):
+    def match_utf8(self, data, with_ids, cap=None, stats=None, errors="strict"):
         """acgpu_match_utf8: a UTF-8 haystack (bytes, bytearray, memoryview or uint8 array) in host memory -> (n, 2|3) int32 array
         in reference call order with BYTE offsets into `data`, end exclusive.  Ill-formed input raises Utf8Error (.start as
-        UnicodeDecodeError.start).  stats: an N.Utf8Stats to fill in, if wanted."""
+        UnicodeDecodeError.start).  stats: an N.Utf8Stats to fill in, if wanted.  errors="replace": acgpu_match_utf8_lossy --
+        the records of data.decode("utf-8", "replace"), a replaced subpart's U+FFFD mapped to its bytes; nothing is raised, and
+        stats is an N.Utf8LossyStats."""
+        entry, stats_type = _utf8_entry("acgpu_match_utf8", N.Utf8Stats, errors)
         buf = _utf8_bytes(data)
         n = int(buf.size)
         kind = N.REC_MAP if with_ids else N.REC_SET
@@ -190,17 +203,17 @@ class Automaton:
         if cap is None:
             cap = max(4096, n // 64)
         buf_in = buf if n else np.zeros(1, np.uint8)
-        st = stats if stats is not None else N.Utf8Stats()
+        st = stats if stats is not None else stats_type()
         while True:
             out = np.empty((cap, cols), dtype=np.int32)
             n_out = ctypes.c_uint64(0)
-            rc = N.lib().acgpu_match_utf8(self._h, _vp(buf_in), n, kind, _vp(out), cap, ctypes.byref(n_out), ctypes.byref(st))
+            rc = entry(self._h, _vp(buf_in), n, kind, _vp(out), cap, ctypes.byref(n_out), ctypes.byref(st))
             if rc == N.E_OVERFLOW:
                 cap = int(n_out.value)
                 continue
             if rc == N.E_ENCODING:
                 raise Utf8Error(st.first_bad)
-            N.check(rc, "acgpu_match_utf8")
+            N.check(rc, entry.__name__)
             return out[:n_out.value]
 
     def match_batch(self, haystacks, with_ids, cap=None):
@@ -221,46 +234,49 @@ class Automaton:
             N.check(rc, "acgpu_match_batch_u16")
             return out[:n_out.value]
 
-    def match_batch_utf8(self, data, with_ids, cap=None, stats=None, offsets=None):
+    def match_batch_utf8(self, data, with_ids, cap=None, stats=None, offsets=None, errors="strict"):
         """acgpu_match_batch_utf8: many short UTF-8 haystacks in one call -> (n, 3|4) int32 array of (haystack index, start,
         end[, keyword index]) records, haystack by haystack in reference call order, start and end in BYTES relative to the
         haystack.  data: a sequence of bytes-like objects, joined once on the host; with offsets= (n + 1 ascending byte
         offsets) ONE buffer, used in place.  An ill-formed haystack raises Utf8Error (.haystack, and .start inside it).
-        stats: an N.Utf8BatchStats to fill in, if wanted."""
+        stats: an N.Utf8BatchStats to fill in, if wanted.  errors="replace": acgpu_match_batch_utf8_lossy -- every haystack as
+        its own .decode("utf-8", "replace"); nothing is raised, and stats is an N.Utf8LossyStats."""
+        entry, stats_type = _utf8_entry("acgpu_match_batch_utf8", N.Utf8BatchStats, errors)
         buf, off = _pack_utf8(data, offsets)
         kind = N.REC_MAP if with_ids else N.REC_SET
         cols = kind // 4 + 1
         if cap is None:
             cap = max(4096, int(off[-1] - off[0]) // 16)
         buf_in = buf if buf.size else np.zeros(1, np.uint8)
-        st = stats if stats is not None else N.Utf8BatchStats()
+        st = stats if stats is not None else stats_type()
         while True:
             out = np.empty((cap, cols), dtype=np.int32)
             n_out = ctypes.c_uint64(0)
-            rc = N.lib().acgpu_match_batch_utf8(self._h, _vp(buf_in), _vp(off), len(off) - 1, kind, _vp(out), cap, ctypes.byref(n_out),
-                                                ctypes.byref(st))
+            rc = entry(self._h, _vp(buf_in), _vp(off), len(off) - 1, kind, _vp(out), cap, ctypes.byref(n_out), ctypes.byref(st))
             if rc == N.E_OVERFLOW:
                 cap = int(n_out.value)
                 continue
             if rc == N.E_ENCODING:
                 raise Utf8Error(st.first_bad, haystack=st.bad_haystack)
-            N.check(rc, "acgpu_match_batch_utf8")
+            N.check(rc, entry.__name__)
             return out[:n_out.value]
 
-    def summary_batch_utf8(self, data, stats=None, offsets=None):
+    def summary_batch_utf8(self, data, stats=None, offsets=None, errors="strict"):
         """acgpu_summary_batch_utf8: many short UTF-8 haystacks decided in one call -> (array of N.SUMMARY_DTYPE with one entry
         per haystack: n_matches and the first record in listener order in BYTES relative to the haystack, -1s where there is
-        none; stats dict).  data and offsets as for match_batch_utf8; an ill-formed haystack raises Utf8Error."""
+        none; stats dict).  data and offsets as for match_batch_utf8; an ill-formed haystack raises Utf8Error.
+        errors="replace": acgpu_summary_batch_utf8_lossy, as for match_batch_utf8."""
+        entry, stats_type = _utf8_entry("acgpu_summary_batch_utf8", N.Utf8BatchStats, errors)
         buf, off = _pack_utf8(data, offsets)
         n = len(off) - 1
         out = np.zeros(n, dtype=N.SUMMARY_DTYPE)
         buf_in = buf if buf.size else np.zeros(1, np.uint8)
         st = N.SummaryStats()
-        ust = stats if stats is not None else N.Utf8BatchStats()
-        rc = N.lib().acgpu_summary_batch_utf8(self._h, _vp(buf_in), _vp(off), n, _vp(out) if n else None, ctypes.byref(st), ctypes.byref(ust))
+        ust = stats if stats is not None else stats_type()
+        rc = entry(self._h, _vp(buf_in), _vp(off), n, _vp(out) if n else None, ctypes.byref(st), ctypes.byref(ust))
         if rc == N.E_ENCODING:
             raise Utf8Error(ust.first_bad, haystack=ust.bad_haystack)
-        N.check(rc, "acgpu_summary_batch_utf8")
+        N.check(rc, entry.__name__)
         return out, {f: int(getattr(st, f)) for f, _ in N.SummaryStats._fields_}
 
     def match_device(self, d_hay_ptr, n_units, with_ids, d_out_ptr, cap, own=None, text_begin=True, text_end=True,
@@ -882,25 +898,26 @@ class _BatchDecisions:
             return [(b, e) if n else None for n, b, e, _ in rows]
         return [(b, e, vals[k]) if n else None for n, b, e, k in rows]
 
-    def _summary_utf8(self, datas, offsets):
+    def _summary_utf8(self, datas, offsets, errors="strict"):
         if offsets is None:
             datas = _checked(datas)
         elif datas is None:
             raise TypeError("haystack is None")
-        return self._auto.summary_batch_utf8(datas, offsets=offsets)[0]
+        return self._auto.summary_batch_utf8(datas, offsets=offsets, errors=errors)[0]
 
-    def contains_batch_utf8(self, datas, offsets=None):
+    def contains_batch_utf8(self, datas, offsets=None, errors="strict"):
         """contains_batch for UTF-8 haystacks: a sequence of bytes-like objects, or with offsets= one buffer in place (a log
-        file: offsets=utf8_line_offsets(buf)).  Utf8Error (.haystack, .start) if one of them is ill-formed."""
-        return self._summary_utf8(datas, offsets)["n_matches"] > 0
+        file: offsets=utf8_line_offsets(buf)).  Utf8Error (.haystack, .start) if one of them is ill-formed -- unless
+        errors="replace": then every haystack is scanned as its .decode("utf-8", "replace"), offsets still those of its bytes."""
+        return self._summary_utf8(datas, offsets, errors)["n_matches"] > 0
 
-    def count_matches_batch_utf8(self, datas, offsets=None):
+    def count_matches_batch_utf8(self, datas, offsets=None, errors="strict"):
         """count_matches_batch for UTF-8 haystacks (see contains_batch_utf8)"""
-        return self._summary_utf8(datas, offsets)["n_matches"].copy()
+        return self._summary_utf8(datas, offsets, errors)["n_matches"].copy()
 
-    def first_batch_utf8(self, datas, offsets=None):
+    def first_batch_utf8(self, datas, offsets=None, errors="strict"):
         """first_batch for UTF-8 haystacks (see contains_batch_utf8): start and end in BYTES relative to the haystack"""
-        return self._first_rows(self._summary_utf8(datas, offsets))
+        return self._first_rows(self._summary_utf8(datas, offsets, errors))
 
 
 class StringSet(_BatchDecisions):
@@ -977,18 +994,18 @@ class StringSet(_BatchDecisions):
         """Convenience (not in the reference): the (n,2) int32 array of (start, end) records."""
         return self._auto.match_host(utf16(haystack), with_ids=False)
 
-    def find_all_utf8(self, data):
+    def find_all_utf8(self, data, errors="strict"):
         """Not in the reference: the (n,2) int32 array of (start, end) records of a UTF-8 haystack (bytes, bytearray, memoryview
         or uint8 array), in BYTE offsets into `data` -- decoded, scanned and mapped back on the device.  Utf8Error if ill-formed."""
-        return self._auto.match_utf8(data, with_ids=False)
+        return self._auto.match_utf8(data, with_ids=False, errors=errors)
 
-    def match_utf8(self, data, listener):
+    def match_utf8(self, data, listener, errors="strict"):
         """Not in the reference: match(data.decode("utf-8"), listener) with the listener receiving `data` itself and byte
         offsets into it; a listener call that returns False stops the loop."""
         if data is None:
             raise TypeError("haystack is None")
         fn = _listener_fn(listener)
-        for s, e in self._auto.match_utf8(data, with_ids=False).tolist():
+        for s, e in self._auto.match_utf8(data, with_ids=False, errors=errors).tolist():
             if not fn(data, s, e):
                 return
 
@@ -1022,19 +1039,19 @@ class StringSet(_BatchDecisions):
             if h != skip and not fn(haystacks[h], s, e):
                 skip = h
 
-    def find_all_batch_utf8(self, datas, offsets=None):
+    def find_all_batch_utf8(self, datas, offsets=None, errors="strict"):
         """Not in the reference: the (n,3) int32 array of (haystack index, start, end) records of many UTF-8 haystacks (a
         sequence of bytes-like objects, or with offsets= one buffer in place) from ONE device call, start and end in BYTES
         relative to the haystack.  Utf8Error (.haystack, .start) if one of them is ill-formed."""
-        return self._auto.match_batch_utf8(datas if offsets is not None else _checked(datas), with_ids=False, offsets=offsets)
+        return self._auto.match_batch_utf8(datas if offsets is not None else _checked(datas), with_ids=False, offsets=offsets, errors=errors)
 
-    def match_batch_utf8(self, datas, listener):
+    def match_batch_utf8(self, datas, listener, errors="strict"):
         """Not in the reference: match_utf8(data, listener) for every haystack of a list in ONE device call: the listener
         gets the haystack's own bytes and byte offsets into them.  A listener call that returns False ends THAT haystack's matches."""
         datas = _checked(datas)
         fn = _listener_fn(listener)
         skip = -1
-        for h, s, e in self._auto.match_batch_utf8(datas, with_ids=False).tolist():
+        for h, s, e in self._auto.match_batch_utf8(datas, with_ids=False, errors=errors).tolist():
             if h != skip and not fn(datas[h], s, e):
                 skip = h
 
@@ -1150,19 +1167,19 @@ class StringMap(_BatchDecisions):
         """Convenience (not in the reference): the (n,3) int32 array of (start, end, keyword_index) records."""
         return self._auto.match_host(utf16(haystack), with_ids=True)
 
-    def find_all_utf8(self, data):
+    def find_all_utf8(self, data, errors="strict"):
         """Not in the reference: the (n,3) int32 array of (start, end, keyword_index) records of a UTF-8 haystack, in BYTE
         offsets into `data` (see StringSet.find_all_utf8)."""
-        return self._auto.match_utf8(data, with_ids=True)
+        return self._auto.match_utf8(data, with_ids=True, errors=errors)
 
-    def match_utf8(self, data, listener):
+    def match_utf8(self, data, listener, errors="strict"):
         """Not in the reference: match(data.decode("utf-8"), listener) with the listener receiving `data` itself, byte offsets
         into it and the value; a listener call that returns False stops the loop."""
         if data is None:
             raise TypeError("haystack is None")
         fn = _listener_fn(listener)
         vals = self._values
-        for s, e, k in self._auto.match_utf8(data, with_ids=True).tolist():
+        for s, e, k in self._auto.match_utf8(data, with_ids=True, errors=errors).tolist():
             if not fn(data, s, e, vals[k]):
                 return
 
@@ -1196,19 +1213,19 @@ class StringMap(_BatchDecisions):
             if h != skip and not fn(haystacks[h], s, e, vals[k]):
                 skip = h
 
-    def find_all_batch_utf8(self, datas, offsets=None):
+    def find_all_batch_utf8(self, datas, offsets=None, errors="strict"):
         """Not in the reference: the (n,4) int32 array of (haystack index, start, end, keyword index) records of many UTF-8
         haystacks from ONE device call (see StringSet.find_all_batch_utf8)."""
-        return self._auto.match_batch_utf8(datas if offsets is not None else _checked(datas), with_ids=True, offsets=offsets)
+        return self._auto.match_batch_utf8(datas if offsets is not None else _checked(datas), with_ids=True, offsets=offsets, errors=errors)
 
-    def match_batch_utf8(self, datas, listener):
+    def match_batch_utf8(self, datas, listener, errors="strict"):
         """Not in the reference: match_utf8(data, listener) for every haystack of a list in ONE device call (see
         StringSet.match_batch_utf8)."""
         datas = _checked(datas)
         fn = _listener_fn(listener)
         vals = self._values
         skip = -1
-        for h, s, e, k in self._auto.match_batch_utf8(datas, with_ids=True).tolist():
+        for h, s, e, k in self._auto.match_batch_utf8(datas, with_ids=True, errors=errors).tolist():
             if h != skip and not fn(datas[h], s, e, vals[k]):
                 skip = h
 

@@ -88,6 +88,8 @@
  *      byte offsets, haystacks' first units     4 H + 4 H (device)
  *      tagged records (match)                   cap x (record_kind + 4)
  *      summaries (summary)                      24 H, and the counting calls' reservoir
+ *    The *_lossy forms of these three need the same, plus, kept by the pool:
+ *      start bitmap (device)                    B/8, rounded up to 512 bytes per 4096  (a bit per byte)
  */
 #ifndef ACGPU_H
 #define ACGPU_H
@@ -692,7 +694,8 @@ int acgpu_summary_batch_u16(const acgpu_automaton *a, const uint16_t *units, con
  * (a short text pays the fixed cost of five launches, two copies and two waits, several times that form's latency: batch short
  * texts with acgpu_match_batch_utf8 / acgpu_summary_batch_utf8 below).  A text that arrives in chunks, or is longer than 2^31
  * bytes: acgpu_stream_feed_utf8 below.  Not built: count, cursor, the pipelined stream,
- * device-resident and multi-device forms for UTF-8 (replace: acgpu_replace_utf8 and acgpu_replace_batch_utf8 below); lossy decoding (U+FFFD); CESU-8 / WTF-8;
+ * device-resident and multi-device forms for UTF-8 (replace: acgpu_replace_utf8 and acgpu_replace_batch_utf8 below; lossy decoding,
+ * ill-formed bytes scanned as U+FFFD: acgpu_match_utf8_lossy below); CESU-8 / WTF-8;
  * the Java facade (its strings are UTF-16).  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
  */
 typedef struct acgpu_utf8_stats {
@@ -790,6 +793,56 @@ int acgpu_summary_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, con
                              acgpu_utf8_batch_stats *stats /* may be NULL */);
 
 /*
+ * LOSSY UTF-8: acgpu_match_utf8, acgpu_match_batch_utf8 and acgpu_summary_batch_utf8 for bytes that need not be well-formed -- log
+ * files, crash dumps, scraped text, truncated lines.  Nothing is refused: the call returns the records its strict counterpart
+ * would return for bytes.decode("utf-8", errors="replace") of the text (a batch: of every haystack on its own) -- the same count,
+ * order and keyword_id, every family -- with start and end as BYTE offsets of the caller's own, unmodified buffer.
+ * REPLACEMENT is CPython's: every MAXIMAL ILL-FORMED SUBPART becomes ONE U+FFFD.  A subpart is one to three bytes: a lead byte
+ * with the longest run of following bytes that is still a valid prefix for that lead (the second byte in the range the lead
+ * allows -- E0: A0..BF, ED: 80..9F, F0: 90..BF, F4: 80..8F -- the others continuation bytes), or a single byte that can begin
+ * nothing: a continuation byte that no lead claims, C0, C1, F5..FF.  So E0 80 80 is three U+FFFD, F0 9F 28 is one (two bytes)
+ * and "(", F0 9F 98 at the end of the text is one of three bytes.
+ * MAPPING RULE.  A U+FFFD that stands for a subpart maps to that subpart's bytes: start is its first byte, end one past its
+ * last.  Everything else follows acgpu_match_utf8's MAPPING RULE.  A keyword that holds U+FFFD matches a genuine EF BF BD and a
+ * replaced subpart alike, as on the decoded string.
+ * BATCH.  Haystack i is decoded alone, as bytes[offsets[i]:offsets[i+1]].decode("utf-8", "replace"): a sequence that a haystack
+ * boundary cuts is a subpart that ends at the boundary, and the continuation bytes at the begin of the next haystack are one
+ * U+FFFD each -- "a\xc3" | "\xa9b" is a, U+FFFD | U+FFFD, b.
+ * Everything else is the strict counterpart's, whose body these share: ACGPU_E_INVALID before a device is touched, the empty text
+ * and the all-empty batch without a device, ACGPU_E_OVERFLOW, the NULL stream under the pool's lock, and the haystack-by-haystack
+ * route where acgpu_match_batch_utf8 takes it.  ACGPU_E_ENCODING is never returned.
+ *  stats     : NULL, or what the decoder found.  ascii == 1: every byte is below 0x80.  A text with as many units as bytes
+ *              ("a\x80b": every start one byte and one unit) is mapped by the identity as an ASCII text is, but ascii is 0 as soon
+ *              as anything was replaced.
+ * How it works: the LOSSY forms of the strict kernels.  The masks of a lane come from claimed_lossy -- a lead claims the byte
+ * behind it only in the range it allows, the next ones only behind a claimed one, never a byte at or behind a haystack boundary --
+ * so a start is every byte that is no claimed continuation byte, and a replaced start is a lead that did not claim all it needs or
+ * an unclaimed continuation byte; on well-formed bytes every mask equals the strict one.  k_utf8_lossy_count adds the replaced
+ * starts of a wave with one 64-bit atomic where there are any, the first of them goes through the strict kernels' atomicMin, and
+ * the one wait brings n_replaced with n_units.  k_utf8_lossy_write stores 0xFFFD for a replaced start and, beside the checkpoints,
+ * a START BITMAP: a bit per byte, set where a sequence or a subpart begins, 16 bits per lane in one store.  The maps walk that
+ * bitmap from the checkpoint, not the bytes: a start's length is the distance to the next set bit, and it has two units exactly
+ * when that is 4 (a subpart has at most 3 bytes).  The bitmap holds the haystack boundaries, so a walk that begins in an earlier
+ * haystack needs to know nothing about them.
+ * Not built in lossy form: replace and batch replace, the stream feeds and stream replace, errors="ignore" (drop the bytes),
+ * the Java facade.  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
+ */
+typedef struct acgpu_utf8_lossy_stats {
+    uint64_t n_units;         /* units the text decodes to, replacements included; batch: separators not counted */
+    uint64_t n_replaced;      /* U+FFFD units that stand for ill-formed subparts (exact)                           */
+    int64_t  first_replaced;  /* -1, or the byte offset of the first of them; batch: inside haystack first_haystack */
+    uint32_t first_haystack;  /* batch: the haystack that holds it (0 otherwise)                                   */
+    uint32_t ascii;           /* 1: every byte < 0x80 (then n_replaced == 0)                                       */
+} acgpu_utf8_lossy_stats;     /* 32 bytes */
+int acgpu_match_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, int record_kind, void *out, uint64_t cap,
+                           uint64_t *n_out, acgpu_utf8_lossy_stats *stats /* may be NULL */);
+int acgpu_match_batch_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
+                                 int record_kind, void *out, uint64_t cap, uint64_t *n_out, acgpu_utf8_lossy_stats *stats /* may be NULL */);
+int acgpu_summary_batch_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
+                                   acgpu_batch_summary *out /* n_haystacks, host */, acgpu_summary_stats *st /* may be NULL */,
+                                   acgpu_utf8_lossy_stats *stats /* may be NULL */);
+
+/*
  * Many short UTF-8 texts rewritten in ONE call: acgpu_replace_utf8 for a batch, the conjunction of acgpu_match_batch_utf8 and
  * acgpu_replace_batch_u16.  Haystack i is bytes[offsets[i] .. offsets[i+1]) as for acgpu_match_batch_utf8 (contiguous in the
  * caller's buffer, empty ones allowed anywhere), and out[out_offsets[i] .. out_offsets[i+1]) is byte for byte what
@@ -826,7 +879,7 @@ int acgpu_summary_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, con
  * depend on the route, then every haystack takes acgpu_replace_utf8's route with cap, the output position and the stats carried
  * across and the table uploaded once.
  * Not built: device-resident, multi-device and cursor forms, a stream of batches (one long text in chunks:
- * acgpu_stream_replace_utf8 below); validating the replacements; lossy decoding (U+FFFD); a one-launch form for tiny batches; the Java facade.  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
+ * acgpu_stream_replace_utf8 below); validating the replacements; a lossy form (acgpu_match_utf8_lossy: what is built); a one-launch form for tiny batches; the Java facade.  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
  */
 int acgpu_replace_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
                              const uint8_t *repl_bytes, const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap,

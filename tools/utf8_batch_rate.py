@@ -7,7 +7,10 @@
 The same automaton (WholeWordMatch over the README word list), Map records, capacity known (no overflow retry timed), the routes'
 results compared.  A host clock around each step; the kernels' own share is what rocprofv3 --kernel-trace --stats shows, in a run
 of its own.
-usage: utf8_batch_rate.py [--lines 20000] [--per-line 2000]"""
+--errors replace: the lossy entries (acgpu_summary_batch_utf8_lossy / acgpu_match_batch_utf8_lossy) on the same buffer
+and offsets, beside the strict ones where the buffer is well-formed (results compared); --damage overwrites about one byte per KB
+with a random byte from 0x80..0xFF (never a line feed: the lines stay the lines), which the strict entries refuse.
+usage: utf8_batch_rate.py [--lines 20000] [--per-line 2000] [--errors strict|replace] [--damage]"""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -18,6 +21,8 @@ from ahocorasick_amd.unicode_tables import default_word_chars
 ap = argparse.ArgumentParser()
 ap.add_argument("--lines", type=int, default=20000)
 ap.add_argument("--per-line", type=int, default=2000)
+ap.add_argument("--errors", default="strict", choices=["strict", "replace"])
+ap.add_argument("--damage", action="store_true", help="with --errors replace: overwrite about one byte per KB")
 args = ap.parse_args()
 
 EXTRA = ["Zürich", "naïve", "straße", "λόγος", "Москва", "東京", "데이터", "😀", "𝒜𝓃𝓈"]
@@ -63,6 +68,28 @@ words, buf = make_lines(args.lines)
 a = Automaton(N.MODE_WHOLEWORD, words + EXTRA[:7], True, word_chars=default_word_chars())
 off = utf8_line_offsets(buf)
 n = len(off) - 1
+if args.errors == "replace":
+    if args.damage:
+        rng = np.random.default_rng(7)
+        b = np.frombuffer(buf, np.uint8).copy()
+        at = np.arange(0, b.size, 1024) + rng.integers(0, 1024, (b.size + 1023) // 1024)
+        at = at[at < b.size]
+        at = at[b[at] != 0x0A]
+        b[at] = rng.integers(0x80, 0x100, at.size)
+        buf = b.tobytes()
+    st = N.Utf8LossyStats()
+    cap = len(a.match_batch_utf8(buf, with_ids=True, offsets=off, stats=st, errors="replace")) + 16
+    print("%d lines, %d bytes -> %d units, %d replaced (first in line %d at %d), ascii=%d, %d records" % (
+        n, len(buf), st.n_units, st.n_replaced, st.first_haystack, st.first_replaced, st.ascii, cap - 16))
+    ms_sum, (sum_l, _) = timed(lambda: a.summary_batch_utf8(buf, offsets=off, errors="replace"))
+    ms_rec, rec_l = timed(lambda: a.match_batch_utf8(buf, with_ids=True, cap=cap, offsets=off, errors="replace"))
+    print("lossy    : summary %8.3f ms = %6.3f us a line | match %8.3f ms = %6.3f us a line" % (ms_sum, ms_sum * 1e3 / n, ms_rec, ms_rec * 1e3 / n))
+    if not st.n_replaced:
+        ms_sum8, (sum8, _) = timed(lambda: a.summary_batch_utf8(buf, offsets=off))
+        ms_rec8, rec8 = timed(lambda: a.match_batch_utf8(buf, with_ids=True, cap=cap, offsets=off))
+        assert (sum8 == sum_l).all() and rec8.shape == rec_l.shape and (rec8 == rec_l).all(), "lossy and strict differ on well-formed bytes"
+        print("strict   : summary %8.3f ms | match %8.3f ms | ratios lossy / strict = %.3f, %.3f" % (ms_sum8, ms_rec8, ms_sum / ms_sum8, ms_rec / ms_rec8), flush=True)
+    sys.exit(0)
 st = N.Utf8BatchStats()
 cap = len(a.match_batch_utf8(buf, with_ids=True, offsets=off, stats=st)) + 16
 print("%d lines, %d bytes -> %d units, ascii=%d, %d records" % (n, len(buf), st.n_units, st.ascii, cap - 16))

@@ -7,7 +7,10 @@ timed), the results compared.  The split host / device: `today` prints its three
 match_host call; `utf8` is one library call with no host step -- its kernels' share is what rocprofv3 --kernel-trace --stats shows
 for k_utf8_* and the scan, in a run of its own.  Texts: a natural-language-like mix (synth.readme_text words, every sixth followed
 by a non-ASCII token) and the same words as pure ASCII.
-usage: utf8_rate.py [--log2 24] [--only mix|ascii]"""
+--errors replace: acgpu_match_utf8_lossy on the same buffer instead -- beside the strict call where the buffer is
+well-formed (the records compared), and with --damage on a copy in which about one byte per KB is overwritten with a random byte
+from 0x80..0xFF (the strict call refuses that one); beside both, the host's data.decode("utf-8", "replace") alone.
+usage: utf8_rate.py [--log2 24] [--only mix|ascii] [--errors strict|replace] [--damage]"""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -18,6 +21,8 @@ from ahocorasick_amd.unicode_tables import default_word_chars
 ap = argparse.ArgumentParser()
 ap.add_argument("--log2", type=int, default=24, help="bytes of the text, about")
 ap.add_argument("--only", default=None)
+ap.add_argument("--errors", default="strict", choices=["strict", "replace"])
+ap.add_argument("--damage", action="store_true", help="with --errors replace: overwrite about one byte per KB")
 args = ap.parse_args()
 
 EXTRA = ["Zürich", "naïve", "straße", "λόγος", "Москва", "東京", "데이터", "😀", "𝒜𝓃𝓈"]
@@ -70,8 +75,36 @@ def run(label, a, data):
     print("%-5s ratio today / utf8 = %.2f" % (label, today / ms_utf8), flush=True)
 
 
+def damage(data, seed=7):
+    """a copy with about one byte per KB overwritten by a byte from 0x80..0xFF"""
+    rng = np.random.default_rng(seed)
+    b = np.frombuffer(data, np.uint8).copy()
+    at = np.arange(0, b.size, 1024) + rng.integers(0, 1024, (b.size + 1023) // 1024)
+    at = at[at < b.size]
+    b[at] = rng.integers(0x80, 0x100, at.size)
+    return b.tobytes()
+
+
+def run_lossy(label, a, data):
+    n = len(data)
+    st = N.Utf8LossyStats()
+    cap = len(a.match_utf8(data, with_ids=True, errors="replace")) + 16
+    ms_lossy, got = timed(lambda: a.match_utf8(data, with_ids=True, cap=cap, stats=st, errors="replace"))
+    ms_dec, _ = timed(lambda: data.decode("utf-8", "replace"))
+    print("%-5s %d bytes -> %d units, %d replaced (first at %d), ascii=%d, %d records" % (
+        label, n, st.n_units, st.n_replaced, st.first_replaced, st.ascii, len(got)))
+    print("%-5s lossy : %8.3f ms = %6.2f GB/s of bytes | host decode(errors='replace') alone: %.3f ms" % (label, ms_lossy, n / ms_lossy / 1e6, ms_dec))
+    if not st.n_replaced:
+        ms_strict, want = timed(lambda: a.match_utf8(data, with_ids=True, cap=cap))
+        assert got.shape == want.shape and (got == want).all(), "lossy and strict differ on well-formed bytes"
+        print("%-5s strict: %8.3f ms = %6.2f GB/s of bytes | ratio lossy / strict = %.3f" % (label, ms_strict, n / ms_strict / 1e6, ms_lossy / ms_strict), flush=True)
+
+
 words, tx = texts(1 << args.log2)
 a = Automaton(N.MODE_WHOLEWORD, words + EXTRA[:7], True, word_chars=default_word_chars())
 for label in ("mix", "ascii"):
     if args.only in (None, label):
-        run(label, a, tx[label])
+        if args.errors == "replace":
+            run_lossy(label + ("*" if args.damage else ""), a, damage(tx[label]) if args.damage else tx[label])
+        else:
+            run(label, a, tx[label])
