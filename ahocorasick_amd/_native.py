@@ -108,6 +108,10 @@ class Utf8StreamStats(ctypes.Structure):  # acgpu_utf8_stream_stats
     _fields_ = [("n_units", ctypes.c_uint64), ("first_bad", ctypes.c_int64), ("ascii", ctypes.c_uint32), ("held", ctypes.c_uint32)]
 
 
+class Utf8LossyStreamStats(ctypes.Structure):  # acgpu_utf8_lossy_stream_stats
+    _fields_ = [("n_units", ctypes.c_uint64), ("n_replaced", ctypes.c_uint64), ("ascii", ctypes.c_uint32), ("held", ctypes.c_uint32)]
+
+
 def _summary_dtype():
     import numpy as np
     return np.dtype({"names": ["n_matches", "start", "end", "keyword_id", "reserved"],
@@ -131,7 +135,8 @@ SYMBOLS = ["acgpu_build", "acgpu_free", "acgpu_get_info", "acgpu_match_u16", "ac
            "acgpu_match_utf8", "acgpu_replace_utf8", "acgpu_match_batch_utf8", "acgpu_summary_batch_utf8",
            "acgpu_replace_batch_utf8", "acgpu_stream_feed_utf8", "acgpu_stream_replace_u16",
            "acgpu_stream_replace_utf8", "acgpu_match_utf8_lossy", "acgpu_match_batch_utf8_lossy",
-           "acgpu_summary_batch_utf8_lossy"]
+           "acgpu_summary_batch_utf8_lossy", "acgpu_replace_utf8_lossy", "acgpu_replace_batch_utf8_lossy",
+           "acgpu_stream_feed_utf8_lossy", "acgpu_stream_replace_utf8_lossy"]
 
 _lib = None
 
@@ -238,6 +243,18 @@ def lib():
         L.acgpu_match_batch_utf8_lossy.argtypes = [vp, vp, vp, u32, ci, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(Utf8LossyStats)]
         L.acgpu_summary_batch_utf8_lossy.restype = ci
         L.acgpu_summary_batch_utf8_lossy.argtypes = [vp, vp, vp, u32, vp, ctypes.POINTER(SummaryStats), ctypes.POINTER(Utf8LossyStats)]
+        L.acgpu_replace_utf8_lossy.restype = ci
+        L.acgpu_replace_utf8_lossy.argtypes = [vp, vp, u64, vp, vp, u32, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(ReplaceStats),
+                                               ctypes.POINTER(Utf8LossyStats)]
+        L.acgpu_replace_batch_utf8_lossy.restype = ci
+        L.acgpu_replace_batch_utf8_lossy.argtypes = [vp, vp, vp, u32, vp, vp, u32, vp, u64, vp, ctypes.POINTER(u64), ctypes.POINTER(ReplaceStats),
+                                                     ctypes.POINTER(Utf8LossyStats)]
+        L.acgpu_stream_feed_utf8_lossy.restype = ci
+        L.acgpu_stream_feed_utf8_lossy.argtypes = [vp, vp, u64, ci, ci, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(i64),
+                                                   ctypes.POINTER(Utf8LossyStreamStats)]
+        L.acgpu_stream_replace_utf8_lossy.restype = ci
+        L.acgpu_stream_replace_utf8_lossy.argtypes = [vp, vp, u64, ci, vp, vp, u32, vp, u64, ctypes.POINTER(u64),
+                                                      ctypes.POINTER(Utf8LossyStreamStats), ctypes.POINTER(ReplaceStats)]
         L.acgpu_replace_utf8.restype = ci
         L.acgpu_replace_utf8.argtypes = [vp, vp, u64, vp, vp, u32, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(ReplaceStats),
                                          ctypes.POINTER(Utf8Stats)]

@@ -406,9 +406,11 @@ int stage_utf8_text(DeviceState &d, const uint8_t *bytes, uint64_t n_bytes, hipS
 // The same for a buffer that lies in two parts on the host, head | bytes (acgpu_stream_feed_utf8: the carried bytes and the
 // caller's chunk; n_head + n_rest < 2^31, not 0), each copied from where it is.  open: the text goes on behind the buffer -- a
 // sequence that the buffer's end cuts and that is well-formed so far is held back: out->tail bytes, and the shard, the
-// checkpoints, n_units and n_bytes are those of the bytes before them (k_utf8_open_count).
+// checkpoints, n_units and n_bytes are those of the bytes before them (k_utf8_open_count).  open and replace
+// (acgpu_stream_feed_utf8_lossy): held is a lead with what it has claimed so far, where that reaches the buffer's end
+// (k_utf8_lossy_open_count); n_replaced and first_bad are those of the bytes before it, too.
 int stage_utf8_parts(DeviceState &d, const uint8_t *head, uint64_t n_head, const uint8_t *bytes, uint64_t n_rest, bool open, hipStream_t stream,
-                     Utf8Text *out, Utf8Errors errors = Utf8Errors::strict); // (open and replace: not built)
+                     Utf8Text *out, Utf8Errors errors = Utf8Errors::strict);
 // A batch of UTF-8 haystacks staged as ONE shard (acgpu_utf8.hip): the caller's span copied once, every haystack validated on its
 // own, and transcoded into the text a batch call scans -- the haystacks' units with the separator unit behind every haystack.
 struct Utf8Batch {
@@ -439,7 +441,8 @@ int utf8_batch_tag(const Utf8Batch &b, const void *d_recs, uint64_t cnt, int rec
 int utf8_map_records(const Utf8Text &text, const Utf8Batch *b, int32_t *d_recs, uint64_t cnt, uint32_t cols, hipStream_t stream);
 // *d_out = the byte for unit `unit` of the shard, enqueued on `stream` (k_utf8_batch_pos).  b == nullptr: the first byte of the
 // code point that holds unit `unit` < n_units -- a position between the two units of a surrogate pair is rounded DOWN; not for
-// an all-ASCII text (there the unit is the byte).  b given: a byte of the span -- a separator, the last one included, maps to the
+// an all-ASCII text (there the unit is the byte).  A lossy text: the first byte of the START that holds the unit -- a replaced
+// subpart is one unit, so it is never entered, and only a surrogate pair rounds down; not for a text without checkpoints.  b given: a byte of the span -- a separator, the last one included, maps to the
 // byte where the next haystack begins (n_bytes behind the last), as does a unit at or behind the shard's end; any other unit as
 // above.
 int utf8_map_position(const Utf8Text &text, const Utf8Batch *b, uint64_t unit, int64_t *d_out, hipStream_t stream);
@@ -477,7 +480,7 @@ inline acgpu_utf8_lossy_stats utf8_lossy_stats(const Utf8Text *text = nullptr, u
 }
 
 // The policy of an entry's body: how its texts are staged and what its stats argument is.  One body serves the strict entry and
-// the lossy one (acgpu_utf8.hip, acgpu_summary.hip).
+// the lossy one (acgpu_utf8.hip, acgpu_summary.hip, acgpu_replace.hip).
 struct Utf8StrictText {
     using Stats = acgpu_utf8_stats;
     static constexpr Utf8Errors errors = Utf8Errors::strict;

@@ -491,6 +491,19 @@ int upload_table(ReplaceCall &c, const void *repl_units, const uint64_t *repl_of
 //    before -- for the first-unit families because such a record starts at or behind that piece's own_hi and last_end, for
 //    SHORTEST because it ends behind that piece's own_hi, hence starts at or behind own_hi - (max_len - 1), and behind every
 //    earlier record's end.  So b - done and pos[] (which are relative to done) are not negative for the boundaries a piece takes.
+//  * A LOSSY UTF-8 call (text, batch or a stream's feed) scans the units of the text decoded with errors="replace" and keeps n,
+//    done, last_end and the limit in bytes of the caller's buffer as it is.  The units tile the bytes in order: a unit is a
+//    START of the bitmap -- a well-formed sequence (two units where it has four bytes) or a maximal ill-formed subpart of one
+//    to three bytes, which is ONE unit, U+FFFD.  The decoded text is well-formed UTF-16 and so are the keywords, so every
+//    record begins and ends between two starts; the map from such unit positions to bytes (locate's lossy form, over the
+//    bitmap) is exact and monotone, and a record that holds a subpart's U+FFFD covers all the subpart's bytes and nothing
+//    else of it -- records that do not overlap in units do not overlap in bytes.  The piece's boundary is rounded down to the
+//    first byte of the START that holds it: for a subpart that IS the unit's own first byte -- a boundary never falls inside
+//    a subpart, which has one unit -- and only between the two units of a surrogate pair does rounding withhold anything.  A
+//    boundary on, directly before or directly behind a subpart is therefore a byte between two starts, and a later record
+//    starts at a start at or behind it.  In a batch the haystack boundaries are starts of the bitmap (a byte at a cut is never
+//    claimed), so the separator rule above holds as it stands.  A text with as many units as bytes has no checkpoints and no
+//    bitmap: every start is one byte and one unit, and the unit is the byte, as in an ASCII text.
 // piece_bound: the family's part of the rule, in the scan's coordinates; replace_limit: the maximum, in the driver's.
 uint64_t piece_bound(const HostTables &t, uint64_t own_hi) {
     if (t.mode != ACGPU_MODE_SHORTEST) return own_hi;
@@ -803,8 +816,17 @@ int acgpu_replace_device(const acgpu_automaton *ca, acgpu_shard *shard, const ui
     return replace_result(c, n_out, st);
 }
 
-int acgpu_replace_utf8(const acgpu_automaton *ca, const uint8_t *bytes, uint64_t n_bytes, const uint8_t *repl_bytes, const uint64_t *repl_off,
-                       uint32_t n_repl, uint8_t *out, uint64_t cap, uint64_t *n_out, acgpu_replace_stats *st, acgpu_utf8_stats *ust) {
+} // extern "C"
+
+namespace {
+
+// The body of acgpu_replace_utf8 and acgpu_replace_utf8_lossy.  P (acgpu_host.h): how the text is staged, and the entry's stats.
+// Lossy: the scan runs over the units of the text decoded with errors="replace", the records are mapped to bytes through the
+// start bitmap, and plan and emit work on the caller's bytes as they lie on the device -- outside the matches the result is a
+// copy of them, ill-formed ones included; a record that covers a replaced subpart removes the subpart's bytes.
+template <class P>
+int replace_utf8(const acgpu_automaton *ca, const uint8_t *bytes, uint64_t n_bytes, const uint8_t *repl_bytes, const uint64_t *repl_off,
+                 uint32_t n_repl, uint8_t *out, uint64_t cap, uint64_t *n_out, acgpu_replace_stats *st, typename P::Stats *ust) {
     if (!ca || !n_out || (n_bytes && !bytes) || (cap && !out)) return ACGPU_E_INVALID;
     if (n_bytes >= (1ull << 31)) return ACGPU_E_INVALID;
     acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
@@ -813,15 +835,15 @@ int acgpu_replace_utf8(const acgpu_automaton *ca, const uint8_t *bytes, uint64_t
     if (a->t.lone_surrogate) return ACGPU_E_UNSUPPORTED; // (a match inside a surrogate pair: records that overlap in bytes, see replace_limit)
     *n_out = 0;
     if (st) *st = acgpu_replace_stats{};
-    if (ust) *ust = utf8_stats();
+    if (ust) *ust = P::stats();
     if (n_bytes == 0) return ACGPU_OK; // (nothing to decode and nothing to rewrite: no device needed)
     PoolCall call(a); // (no device: fails here, as acgpu_match_utf8 does, and out is untouched)
     if (call.rc) return call.rc;
     DeviceState &d = *call.d;
     if ((rc = call.idle())) return rc; // (the NULL stream: see the stream rule)
     Utf8Text text;
-    rc = stage_utf8_text(d, bytes, n_bytes, d.call_stream, &text);
-    if (ust) *ust = utf8_stats(&text, rc);
+    rc = stage_utf8_text(d, bytes, n_bytes, d.call_stream, &text, P::errors);
+    if (ust) *ust = P::stats(&text, rc);
     if (rc == ACGPU_E_ENCODING) return rc; // (the stream is idle: the pool is as usable as before the call)
     if (rc) return call.fail(rc);
     ReplaceCall c{a, d, d.call_stream};
@@ -837,9 +859,11 @@ int acgpu_replace_utf8(const acgpu_automaton *ca, const uint8_t *bytes, uint64_t
     return replace_result(c, n_out, st);
 }
 
-int acgpu_replace_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
-                             const uint8_t *repl_bytes, const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap,
-                             uint64_t *out_offsets, uint64_t *n_out, acgpu_replace_stats *st, acgpu_utf8_batch_stats *ust) {
+// The body of acgpu_replace_batch_utf8 and acgpu_replace_batch_utf8_lossy
+template <class P>
+int replace_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
+                       const uint8_t *repl_bytes, const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap,
+                       uint64_t *out_offsets, uint64_t *n_out, acgpu_replace_stats *st, typename P::Stats *ust) {
     if (!ca || !offsets || !n_out || !out_offsets || (cap && !out)) return ACGPU_E_INVALID;
     acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
     const HostTables &t = a->t;
@@ -851,7 +875,7 @@ int acgpu_replace_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, co
     *n_out = 0;
     out_offsets[0] = 0;
     if (st) *st = acgpu_replace_stats{};
-    if (ust) *ust = utf8_batch_stats();
+    if (ust) *ust = P::stats();
     if (plan.total == 0) { // (nothing to decode and nothing to rewrite: no device needed)
         for (uint32_t i = 0; i < n_haystacks; i++) out_offsets[i + 1] = 0;
         return ACGPU_OK;
@@ -862,9 +886,9 @@ int acgpu_replace_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, co
     if ((rc = call.idle())) return rc; // (the NULL stream: see the stream rule)
     // the whole batch is validated first, whichever way it is scanned, so that what is refused does not depend on the route
     Utf8Batch b;
-    rc = stage_utf8_batch(d, t, bytes, offsets, n_haystacks, d.call_stream, &b, plan.per_haystack);
+    rc = stage_utf8_batch(d, t, bytes, offsets, n_haystacks, d.call_stream, &b, plan.per_haystack, P::errors);
     if (rc && rc != ACGPU_E_ENCODING) return call.fail(rc);
-    if (ust) *ust = utf8_batch_stats(&b, rc);
+    if (ust) *ust = P::stats(&b, rc);
     if (rc) return rc; // (ACGPU_E_ENCODING.  The stream is idle: the pool is as usable as before the call; out_offsets[1..] untouched)
     ReplaceCall c{a, d, d.call_stream};
     c.esz = 1;
@@ -877,7 +901,7 @@ int acgpu_replace_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, co
             const uint64_t len = offsets[i + 1] - offsets[i];
             if (len) {
                 Utf8Text text;
-                if ((rc = stage_utf8_text(d, bytes + offsets[i], len, c.stream, &text))) return call.fail(rc == ACGPU_E_ENCODING ? ACGPU_E_HIP : rc); // (never ill-formed: validated)
+                if ((rc = stage_utf8_text(d, bytes + offsets[i], len, c.stream, &text, P::errors))) return call.fail(rc == ACGPU_E_ENCODING ? ACGPU_E_HIP : rc); // (never ill-formed: validated)
                 c.u8 = &text;
                 c.n = len;
                 c.done = 0;
@@ -904,6 +928,32 @@ int acgpu_replace_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, co
         hipStreamSynchronize(c.stream) != hipSuccess)
         return call.fail(ACGPU_E_HIP);
     return replace_result(c, n_out, st);
+}
+
+} // namespace
+
+extern "C" {
+
+int acgpu_replace_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, const uint8_t *repl_bytes, const uint64_t *repl_off,
+                       uint32_t n_repl, uint8_t *out, uint64_t cap, uint64_t *n_out, acgpu_replace_stats *st, acgpu_utf8_stats *ust) {
+    return replace_utf8<Utf8StrictText>(a, bytes, n_bytes, repl_bytes, repl_off, n_repl, out, cap, n_out, st, ust);
+}
+
+int acgpu_replace_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, const uint8_t *repl_bytes, const uint64_t *repl_off,
+                             uint32_t n_repl, uint8_t *out, uint64_t cap, uint64_t *n_out, acgpu_replace_stats *st, acgpu_utf8_lossy_stats *ust) {
+    return replace_utf8<Utf8LossyText>(a, bytes, n_bytes, repl_bytes, repl_off, n_repl, out, cap, n_out, st, ust);
+}
+
+int acgpu_replace_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
+                             const uint8_t *repl_bytes, const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap,
+                             uint64_t *out_offsets, uint64_t *n_out, acgpu_replace_stats *st, acgpu_utf8_batch_stats *ust) {
+    return replace_batch_utf8<Utf8StrictBatch>(a, bytes, offsets, n_haystacks, repl_bytes, repl_off, n_repl, out, cap, out_offsets, n_out, st, ust);
+}
+
+int acgpu_replace_batch_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
+                                   const uint8_t *repl_bytes, const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap,
+                                   uint64_t *out_offsets, uint64_t *n_out, acgpu_replace_stats *st, acgpu_utf8_lossy_stats *ust) {
+    return replace_batch_utf8<Utf8LossyBatch>(a, bytes, offsets, n_haystacks, repl_bytes, repl_off, n_repl, out, cap, out_offsets, n_out, st, ust);
 }
 
 int acgpu_replace_batch_u16(const acgpu_automaton *ca, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks,

@@ -17,6 +17,10 @@
 // acgpu_stream_replace_u16 / acgpu_stream_replace_utf8 rewrite the text instead of reporting its records: the same buffers and the
 // same plan, and over a feed's owned range the pieces of the replace entries (replace_feed, acgpu_replace.hip); the stream keeps
 // `done`, the global position up to which output has been delivered.
+// acgpu_stream_feed_utf8_lossy / acgpu_stream_replace_utf8_lossy are the two byte entries' bodies with the other error policy
+// (feed_utf8, stream_replace_utf8): nothing is refused, the buffer is staged through the validator that is both lossy and open,
+// the carry is cut at a START found by the claim rule restated on the host (lossy_start, lossy_span), and the stream keeps the
+// replaced count of what it carries.  The policy is part of the stream's kind.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -172,13 +176,15 @@ struct acgpu_stream {
     bool finished = false;
     std::vector<uint16_t> buf;
     // ---- a stream of UTF-8 bytes (acgpu_stream_feed_utf8): carry_pos, own_from and chain_entry stay in units ----
-    enum Fed : uint8_t { kFedNone, kFedUnits, kFedBytes, kFedReplaceUnits, kFedReplaceBytes };
+    enum Fed : uint8_t { kFedNone, kFedUnits, kFedBytes, kFedReplaceUnits, kFedReplaceBytes, kFedBytesLossy, kFedReplaceBytesLossy };
     Fed fed = kFedNone;          // what the first feed, of whatever length, made of the stream: every other entry refuses it
+                                 // (the error policy of a stream of bytes is part of its kind: a strict feed on a lossy stream, and the reverse)
     uint64_t done = 0;           // a replace stream: output has been delivered for the text in front of this global position, in
                                  // units (kFedReplaceUnits) or bytes (kFedReplaceBytes); never in front of the carry's first
     std::vector<uint8_t> carry8; // the carried text's bytes, whole code points, then the held prefix
     uint32_t held = 0;           // bytes at carry8's end that begin a sequence the next feed must complete, 0..3
     uint64_t carry_units = 0;    // units that carry8 without the held prefix decodes to
+    uint64_t carry_replaced = 0; // a lossy stream: of those, the U+FFFD that stand for ill-formed subparts (an earlier feed has reported them)
     uint64_t carry_byte = 0;     // global byte position of carry8[0]
     // ---- pipelined form ----
     bool pipelined = false, started = false;
@@ -484,6 +490,8 @@ struct ByteFeed {
     uint64_t n_bytes;
     bool final;
     acgpu_utf8_stream_stats *stats; // the caller's, may be NULL
+    acgpu_utf8_lossy_stream_stats *lossy_stats = nullptr; // a lossy feed's instead (lossy), may be NULL
+    bool lossy = false;             // the stream's error policy: Utf8Errors::replace
     uint64_t n_c8 = 0, total_bytes = 0;
     bool go = false;                // begin: there is something to decode, the pool is held and the buffer staged
     std::optional<PoolCall> call;   // ... from begin to the entry's return
@@ -493,10 +501,51 @@ struct ByteFeed {
     uint8_t at(const acgpu_stream *s, uint64_t i) const { return i < n_c8 ? s->carry8[i] : bytes[i - n_c8]; }
 };
 
+// The claim rule of lane_view's LOSSY form (acgpu_utf8.hip) restated on the host, for the few bytes byte_feed_commit walks.
+// at(i): byte i of a text of `end` bytes; p: a START of it.  Returns the bytes of that start -- a lead with what it claims (the
+// second byte in the range the lead allows, the later ones continuation bytes, never a byte at or behind `end`), or one byte that
+// claims nothing (ASCII, a continuation byte, C0, C1, F5..FF) -- and *replaced: it is an ill-formed subpart, one U+FFFD.  4 bytes
+// are a well-formed 4-byte sequence and nothing else: two units.
+template <class At>
+uint32_t lossy_span(const At &at, uint64_t p, uint64_t end, bool *replaced) {
+    const uint32_t b0 = at(p);
+    *replaced = b0 >= 0x80u;
+    if (b0 < 0xc2u || b0 > 0xf4u) return 1;
+    const uint32_t need = b0 < 0xe0u ? 1u : (b0 < 0xf0u ? 2u : 3u);
+    const uint32_t lo = b0 == 0xe0u ? 0xa0u : (b0 == 0xf0u ? 0x90u : 0x80u), hi = b0 == 0xedu ? 0x9fu : (b0 == 0xf4u ? 0x8fu : 0xbfu);
+    uint32_t got = 0;
+    if (p + 1 < end && at(p + 1) >= lo && at(p + 1) <= hi) {
+        got = 1;
+        while (got < need && p + 1 + got < end && (at(p + 1 + got) & 0xc0u) == 0x80u) ++got;
+    }
+    *replaced = got < need;
+    return 1 + got;
+}
+
+// ... byte i of that text is a start: no continuation byte, or one that the nearest byte before it that is none -- it looks at
+// most 3 bytes back -- does not claim.  The text begins at a start (a stream's carry does, see byte_feed_commit): bytes before
+// byte 0 claim nothing.
+template <class At>
+bool lossy_start(const At &at, uint64_t i, uint64_t end) {
+    if ((at(i) & 0xc0u) != 0x80u) return true;
+    for (uint64_t k = 1; k <= 3 && k <= i; ++k) {
+        if ((at(i - k) & 0xc0u) == 0x80u) continue;
+        bool replaced;
+        return lossy_span(at, i - k, end, &replaced) <= k;
+    }
+    return true;
+}
+
 // The prologue of the byte feeds, from the stats' preset through plan_feed: returns what the entry returns where !f->go -- an
-// empty feed, a failure, or ill-formed bytes (ACGPU_E_ENCODING, which finishes the stream).
+// empty feed, a failure, or ill-formed bytes (ACGPU_E_ENCODING, which finishes the stream; never on a lossy stream).
 int byte_feed_begin(acgpu_stream *s, int record_kind, ByteFeed *f) {
     static_assert(sizeof(acgpu_utf8_stream_stats) == 24, "the layout include/acgpu.h promises");
+    static_assert(sizeof(acgpu_utf8_lossy_stream_stats) == 24, "the layout include/acgpu.h promises");
+    // the caller's stats, whichever the entry has: a lossy feed has n_replaced where a strict one has first_bad
+    auto put = [f](const acgpu_utf8_stream_stats &st, uint64_t n_replaced) {
+        if (f->stats) *f->stats = st;
+        if (f->lossy_stats) *f->lossy_stats = acgpu_utf8_lossy_stream_stats{st.n_units, n_replaced, st.ascii, st.held};
+    };
     f->n_c8 = s->carry8.size();
     f->total_bytes = f->n_c8 + f->n_bytes;
     acgpu_utf8_stream_stats st{};
@@ -504,7 +553,7 @@ int byte_feed_begin(acgpu_stream *s, int record_kind, ByteFeed *f) {
     st.held = s->held;
     st.ascii = 1;
     for (uint8_t b : s->carry8) st.ascii &= b < 0x80u ? 1u : 0u;
-    if (f->stats) *f->stats = st;
+    put(st, 0);
     if (f->n_bytes == 0 && !f->final) return ACGPU_OK; // (nothing new to decode or to decide: no device needed)
     if (f->total_bytes == 0) {                         // (the end of a stream that holds nothing: neither)
         s->finished = true;
@@ -514,21 +563,25 @@ int byte_feed_begin(acgpu_stream *s, int record_kind, ByteFeed *f) {
     if (call.rc) return call.rc;
     int rc;
     if ((rc = call.idle())) return rc; // (the call stream, waited for: see the stream rule)
-    rc = stage_utf8_parts(*call.d, s->carry8.data(), f->n_c8, f->bytes, f->n_bytes, /*open=*/!f->final, call.d->call_stream, &f->text);
+    rc = stage_utf8_parts(*call.d, s->carry8.data(), f->n_c8, f->bytes, f->n_bytes, /*open=*/!f->final, call.d->call_stream, &f->text,
+                          f->lossy ? Utf8Errors::replace : Utf8Errors::strict);
     if (rc == ACGPU_E_ENCODING) { // (the stream is idle: the pool is as usable as before the call; what a replace stream withheld stays undelivered)
         st.first_bad = (int64_t)s->carry_byte + f->text.first_bad; // (in an earlier feed's bytes: the lead of the held prefix)
         st.ascii = 0;
         st.held = 0;
-        if (f->stats) *f->stats = st;
+        put(st, 0);
         s->finished = true;
         return rc;
     }
     if (rc) return call.fail(rc);
     if (f->text.n_units < s->carry_units) return call.fail(ACGPU_E_HIP); // (never: the carried code points decode as they did)
+    // (lossy: nor were they replaced otherwise -- byte_feed_commit shows both; the carry's count makes the feeds' n_replaced sum
+    // to the whole text's)
+    if (f->text.n_replaced < s->carry_replaced) return call.fail(ACGPU_E_HIP);
     st.n_units = f->text.n_units - s->carry_units;
-    st.ascii = f->text.n_units == f->total_bytes;
+    st.ascii = f->text.n_units == f->total_bytes && !f->text.n_replaced; // ("a\x80b" has as many units as bytes)
     st.held = f->text.tail;
-    if (f->stats) *f->stats = st;
+    put(st, f->text.n_replaced - s->carry_replaced);
     f->rule = shard_rule(s->a->t, record_kind, /*readable=*/true);
     f->p = plan_feed(f->rule, s->carry_units, f->text.n_units - s->carry_units, s->own_from, s->carry_pos, f->final);
     f->go = true;
@@ -541,11 +594,35 @@ int byte_feed_commit(acgpu_stream *s, const ByteFeed &f, int64_t chain_exit, con
     // The cut is found on the host: back from the end of the decoded bytes over the leads -- every byte that is no continuation
     // byte begins a code point of one unit, of two from F0 up -- until at least total - keep_from units are covered.  That is a
     // code-point boundary; where keep_from names a low surrogate, one unit more is carried than the plan asks.
+    //
+    // A LOSSY stream cuts at a START: a lead, or a continuation byte nobody claimed -- a byte that is no continuation byte is not
+    // enough to look for, "a 80 80" has three starts.  The walk restates the claim rule (lossy_start, lossy_span) over the bytes
+    // it passes, at most 3 more behind each: back to the nearest start, which is one unit, or two where it is a well-formed
+    // 4-byte sequence, and replaced where lossy_span says so.  These are the units the device counted: the decoded bytes
+    // [0, n_bytes) were judged as a closed text of n_bytes bytes (lane_view, LOSSY and OPEN), which is what `end` says here.
+    // Why a carry that begins at a start c decodes, with nothing before it, to the units it decoded to before -- the "never"
+    // checks of byte_feed_begin: a claim is a run of continuation bytes directly behind its lead, so a lead before c that claimed
+    // a byte at or behind c would have claimed c, and c is a start.  Which bytes from c on are claimed, by which lead, and
+    // whether that lead got all it needs is therefore decided by bytes from c on alone.  And the units of the carried bytes
+    // BEFORE the held prefix do not depend on what the next feed brings: those bytes were decoded as a text that ends where
+    // the held lead stands, or at the buffer's end where nothing was held, and a lead among them whose claim reached that end
+    // while it needed more IS the held lead -- every other start was decided by bytes that were there.
     const uint64_t need = f.p.total - f.p.keep_from;
-    uint64_t cut = f.text.n_bytes, kept = 0;
-    while (kept < need && cut > 0) {
-        const uint8_t b = f.at(s, --cut);
-        if ((b & 0xc0u) != 0x80u) kept += b >= 0xf0u ? 2u : 1u;
+    uint64_t cut = f.text.n_bytes, kept = 0, kept_replaced = 0;
+    if (f.lossy) {
+        auto at = [&](uint64_t i) { return (uint32_t)f.at(s, i); };
+        while (kept < need && cut > 0) {
+            --cut;
+            while (cut > 0 && !lossy_start(at, cut, f.text.n_bytes)) --cut; // (byte 0 is a start)
+            bool replaced;
+            kept += lossy_span(at, cut, f.text.n_bytes, &replaced) == 4 ? 2u : 1u;
+            kept_replaced += replaced ? 1u : 0u;
+        }
+    } else {
+        while (kept < need && cut > 0) {
+            const uint8_t b = f.at(s, --cut);
+            if ((b & 0xc0u) != 0x80u) kept += b >= 0xf0u ? 2u : 1u;
+        }
     }
     // the cut is the first byte of the code point that holds unit keep_from, or of the one before it, and `done` is at least the
     // byte that keep_from <= own_end - left rounds down to
@@ -564,6 +641,7 @@ int byte_feed_commit(acgpu_stream *s, const ByteFeed &f, int64_t chain_exit, con
     s->held = f.text.tail;
     s->carry_pos += f.p.total - kept;
     s->carry_units = kept;
+    s->carry_replaced = kept_replaced;
     s->carry_byte += cut;
     s->finished = f.final;
     return ACGPU_OK;
@@ -662,18 +740,25 @@ int acgpu_stream_feed(acgpu_stream *s, const uint16_t *units, uint64_t n_units, 
     return ACGPU_OK;
 }
 
-int acgpu_stream_feed_utf8(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, int record_kind, void *out, uint64_t cap,
-                           uint64_t *n_out, int64_t *base, acgpu_utf8_stream_stats *stats) {
+} // extern "C"
+
+namespace {
+
+// The body of acgpu_stream_feed_utf8 and acgpu_stream_feed_utf8_lossy: exactly one of stats and lossy_stats is the entry's (either
+// may be NULL).  The policy is part of the stream's kind.
+int feed_utf8(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, int record_kind, void *out, uint64_t cap, uint64_t *n_out,
+              int64_t *base, bool lossy, acgpu_utf8_stream_stats *stats, acgpu_utf8_lossy_stream_stats *lossy_stats) {
     if (!s || !n_out || !base || (n_bytes && !bytes) || (cap && !out) || s->finished) return ACGPU_E_INVALID;
     if (record_kind != ACGPU_REC_SET && record_kind != ACGPU_REC_MAP) return ACGPU_E_INVALID;
     if (!s->a) return ACGPU_E_INVALID; // (its automaton has been freed)
     if (s->pipelined) return ACGPU_E_UNSUPPORTED;
-    if (s->fed != acgpu_stream::kFedNone && s->fed != acgpu_stream::kFedBytes) return ACGPU_E_INVALID; // (a stream of another kind: units, or a replace stream)
+    const acgpu_stream::Fed kind = lossy ? acgpu_stream::kFedBytesLossy : acgpu_stream::kFedBytes;
+    if (s->fed != acgpu_stream::kFedNone && s->fed != kind) return ACGPU_E_INVALID; // (a stream of another kind: units, a replace stream, bytes under the other policy)
     if (n_bytes >= (1ull << 31) || s->carry8.size() + n_bytes >= (1ull << 31)) return ACGPU_E_INVALID;
-    s->fed = acgpu_stream::kFedBytes;
+    s->fed = kind;
     *n_out = 0;
     *base = (int64_t)s->carry_byte;
-    ByteFeed f{bytes, n_bytes, final != 0, stats};
+    ByteFeed f{bytes, n_bytes, final != 0, stats, lossy_stats, lossy};
     int rc = byte_feed_begin(s, record_kind, &f);
     if (!f.go) return rc;
     acgpu_automaton *a = s->a;
@@ -698,6 +783,20 @@ int acgpu_stream_feed_utf8(acgpu_stream *s, const uint8_t *bytes, uint64_t n_byt
         chain_exit = piece_exit(f.rule, entry, p.own_end, &sh, *n_out);
     }
     return byte_feed_commit(s, f, chain_exit);
+}
+
+} // namespace
+
+extern "C" {
+
+int acgpu_stream_feed_utf8(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, int record_kind, void *out, uint64_t cap,
+                           uint64_t *n_out, int64_t *base, acgpu_utf8_stream_stats *stats) {
+    return feed_utf8(s, bytes, n_bytes, final, record_kind, out, cap, n_out, base, /*lossy=*/false, stats, nullptr);
+}
+
+int acgpu_stream_feed_utf8_lossy(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, int record_kind, void *out, uint64_t cap,
+                                 uint64_t *n_out, int64_t *base, acgpu_utf8_lossy_stream_stats *stats) {
+    return feed_utf8(s, bytes, n_bytes, final, record_kind, out, cap, n_out, base, /*lossy=*/true, nullptr, stats);
 }
 
 int acgpu_stream_replace_u16(acgpu_stream *s, const uint16_t *units, uint64_t n_units, int final, const uint16_t *repl_units,
@@ -749,21 +848,30 @@ int acgpu_stream_replace_u16(acgpu_stream *s, const uint16_t *units, uint64_t n_
     return ACGPU_OK;
 }
 
-int acgpu_stream_replace_utf8(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, const uint8_t *repl_bytes,
-                              const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap, uint64_t *n_out,
-                              acgpu_utf8_stream_stats *ust, acgpu_replace_stats *rst) {
+} // extern "C"
+
+namespace {
+
+// The body of acgpu_stream_replace_utf8 and acgpu_stream_replace_utf8_lossy (ust or lossy_ust: as feed_utf8's stats).  Lossy: the
+// feed's buffer is staged with the other policy and that is all -- the pieces map records and boundaries through the start
+// bitmap, and the emit copies the caller's bytes as they are, so a held prefix (the bytes behind text.n_bytes) stays undelivered
+// until the bytes that complete it, or fail to, or the final feed decide what it is.
+int stream_replace_utf8(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, const uint8_t *repl_bytes, const uint64_t *repl_off,
+                        uint32_t n_repl, uint8_t *out, uint64_t cap, uint64_t *n_out, bool lossy, acgpu_utf8_stream_stats *ust,
+                        acgpu_utf8_lossy_stream_stats *lossy_ust, acgpu_replace_stats *rst) {
     if (!s || !n_out || (n_bytes && !bytes) || (cap && !out) || s->finished) return ACGPU_E_INVALID;
     if (!s->a) return ACGPU_E_INVALID; // (its automaton has been freed)
-    if (s->fed != acgpu_stream::kFedNone && s->fed != acgpu_stream::kFedReplaceBytes) return ACGPU_E_INVALID; // (a stream of another kind)
+    const acgpu_stream::Fed kind = lossy ? acgpu_stream::kFedReplaceBytesLossy : acgpu_stream::kFedReplaceBytes;
+    if (s->fed != acgpu_stream::kFedNone && s->fed != kind) return ACGPU_E_INVALID; // (a stream of another kind)
     acgpu_automaton *a = s->a;
     int rc = replace_check_table(a, repl_bytes, repl_off, n_repl);
     if (rc) return rc;
     if (s->pipelined || a->t.lone_surrogate) return ACGPU_E_UNSUPPORTED; // (the latter: as acgpu_replace_utf8)
     if (n_bytes >= (1ull << 31) || s->carry8.size() + n_bytes >= (1ull << 31)) return ACGPU_E_INVALID;
-    s->fed = acgpu_stream::kFedReplaceBytes;
+    s->fed = kind;
     *n_out = 0;
     if (rst) *rst = acgpu_replace_stats{};
-    ByteFeed bf{bytes, n_bytes, final != 0, ust};
+    ByteFeed bf{bytes, n_bytes, final != 0, ust, lossy_ust, lossy};
     rc = byte_feed_begin(s, ACGPU_REC_MAP, &bf);
     if (!bf.go) return rc;
     const PoolCall &call = *bf.call;
@@ -787,6 +895,22 @@ int acgpu_stream_replace_utf8(acgpu_stream *s, const uint8_t *bytes, uint64_t n_
         f.chain = piece_exit(bf.rule, piece_entry(bf.rule, f.chain, 0, p.own_begin), p.own_end, nullptr, 0);
     }
     return byte_feed_commit(s, bf, f.chain, &f.done);
+}
+
+} // namespace
+
+extern "C" {
+
+int acgpu_stream_replace_utf8(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, const uint8_t *repl_bytes,
+                              const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap, uint64_t *n_out,
+                              acgpu_utf8_stream_stats *ust, acgpu_replace_stats *rst) {
+    return stream_replace_utf8(s, bytes, n_bytes, final, repl_bytes, repl_off, n_repl, out, cap, n_out, /*lossy=*/false, ust, nullptr, rst);
+}
+
+int acgpu_stream_replace_utf8_lossy(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, const uint8_t *repl_bytes,
+                                    const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap, uint64_t *n_out,
+                                    acgpu_utf8_lossy_stream_stats *ust, acgpu_replace_stats *rst) {
+    return stream_replace_utf8(s, bytes, n_bytes, final, repl_bytes, repl_off, n_repl, out, cap, n_out, /*lossy=*/true, nullptr, ust, rst);
 }
 
 } // extern "C"

@@ -28,7 +28,9 @@
 //  * lossy: acgpu_match_utf8_lossy and acgpu_match_batch_utf8_lossy (acgpu_summary_batch_utf8_lossy in acgpu_summary.hip) are the
 //    same bodies with another policy (match_utf8<P>, match_batch_utf8<P>; Utf8Errors::replace down to utf8_validate) over the LOSSY
 //    instantiations of lane_view, count_units, the writers and locate: nothing is refused, a maximal ill-formed subpart is one
-//    U+FFFD, and the maps walk a start bitmap that the lossy writers store beside the checkpoints.
+//    U+FFFD, and the maps walk a start bitmap that the lossy writers store beside the checkpoints.  The lossy replace entries
+//    (acgpu_replace.hip) and the lossy feeds (acgpu_stream.hip) stage through the same two functions with that policy; the feeds'
+//    validator is k_utf8_lossy_open_count, lane_view's LOSSY and OPEN form.
 // What a lane knows about its 16 bytes is eleven bit masks over a window of 24 bytes (the 4 before, its own, the 4 behind), built
 // by one function that both passes over the text share, so they cannot disagree about a count; the two writers share the
 // decoder, so they cannot disagree about a unit.
@@ -109,11 +111,24 @@ struct LaneView {
 // On well-formed input each equals its strict counterpart (a lead claims all it needs, which is what the strict rules ask).
 // A continuation byte looks at most 3 bytes back for the lead that claims it, and whether that lead does depends on the cuts
 // BETWEEN them: the batch form's cut mask reaches down to bit 1 here, `next` stays the first boundary at or behind o.
+//
+// LOSSY and OPEN (a feed of acgpu_stream_feed_utf8_lossy that is not the last): the last 1..3 bytes are held back exactly when
+// they are a lead with everything it has claimed so far under claimed_lossy, and that claim reaches the buffer's end while the
+// lead still needs more.  Everything else is decided now -- a lead whose PRESENT bytes fail is a subpart now, whatever follows
+// (so ED A0 at the end is two U+FFFD now: the strict form's exception is not mirrored, only chunking invariance is promised).
+// The held lead is the `tail`: neither a start (lead) nor replaced (bad) in this buffer, the bytes it claimed are claimed as ever.
+// At most one tail exists in a buffer: let p < q be two leads of the last three bytes.  For p to be a tail its claim reaches the
+// end, so it claimed q -- but a claimed byte is a continuation byte and q is a lead.  So only the last such lead can pass, and the
+// one lane that owns it stores n - position without a race.
+// The bytes before the tail p decode as a CLOSED text of p bytes exactly as they do here: a claim is a run of continuation bytes
+// directly behind its lead, and p is none, so no lead before p claims p or anything behind it -- which bytes before p are claimed,
+// and which leads before p claimed all they need, is decided by bytes before p alone, and in the closed text the window reads
+// zero from p on, no continuation byte either.  So the sums are those of the n - tail bytes, and k_utf8_lossy_write runs
+// unchanged over them.
 template <bool BATCH, bool OPEN = false, bool LOSSY = false>
 __device__ __forceinline__ LaneView lane_view(const uint8_t *__restrict__ in, uint32_t n, uint32_t o, const uint32_t *__restrict__ boff = nullptr,
                                               uint32_t n_hay = 0) {
     static_assert(!(BATCH && OPEN), "a batch's haystacks end where they end");
-    static_assert(!(LOSSY && OPEN), "the feeds are strict");
     LaneView v;
     uint4 own = make_uint4(0, 0, 0, 0);
     if (o < n) own = *reinterpret_cast<const uint4 *>(in + o);
@@ -195,8 +210,17 @@ __device__ __forceinline__ LaneView lane_view(const uint8_t *__restrict__ in, ui
         v.lead = (~cont | (cont & ~claimed_lossy)) & own_bits;
         v.four = l4 & ~bad_lossy & own_bits;
         v.bad = (bad_lossy | (cont & ~claimed_lossy)) & own_bits;
+        if constexpr (OPEN) {
+            // the lead whose claim reaches the buffer's end while it still needs more: a 2..4-byte lead as the last byte, a 3- or
+            // 4-byte lead that claimed the last byte, a 4-byte lead that claimed the last two (behind the end the window reads as
+            // zero, which nobody claims: c1 of the last byte and c2 of the last two are 0, so the three terms exclude each other)
+            const uint32_t behind = k_end >= 24 ? 0u : ~((1u << k_end) - 1u);
+            v.tail = ((l2 & ~inv & (behind >> 1)) | (c1 & l3 & (behind >> 2)) | (c2 & l4 & (behind >> 3))) & own_bits;
+            v.lead &= ~v.tail; // the held prefix's lead begins no unit of THIS buffer ...
+            v.bad &= ~v.tail;  // ... and is no replaced one: it did not claim all it needs YET (four: clear already, it is in bad_lossy)
+        }
     }
-    if constexpr (OPEN) {
+    if constexpr (OPEN && !LOSSY) {
         // `behind`: the window's bytes at and behind the buffer's end -- they are not there YET, so whatever a lead asks of them holds
         // (what a lead forbids, ED A0.. and F4 90.., is asked of bytes that are there: the plain masks, zero behind the end)
         const uint32_t behind = k_end >= 24 ? 0u : ~((1u << k_end) - 1u);
@@ -235,7 +259,8 @@ __device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t *total) {
 // block_sums[b] = the units of block b's bytes.  OPEN: res[2] (preset to 0) = the bytes at the buffer's end that begin a sequence
 // a later buffer has to complete, 1 .. 3, and the sums are those of the n - res[2] bytes before them.
 // LOSSY: res[1] is the first REPLACED offset, and res[3] (preset to 0) the number of replaced units: one 64-bit add per wave that
-// has any.
+// has any.  LOSSY and OPEN: all four -- res[0] the units, res[1] the first replaced offset and res[3] the replaced units of the
+// n - res[2] bytes before the held prefix (its lead is in neither v.bad nor v.lead), res[2] the held bytes.
 template <bool BATCH, bool OPEN, bool LOSSY = false>
 __device__ __forceinline__ void count_units(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ boff, uint32_t n_hay,
                                             uint32_t *__restrict__ block_sums, unsigned long long *__restrict__ res) {
@@ -278,6 +303,11 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_batch_count(const uint8_t *
 __global__ __launch_bounds__(kU8Threads) void k_utf8_lossy_count(const uint8_t *__restrict__ in, uint32_t n, uint32_t *__restrict__ block_sums,
                                                                  unsigned long long *__restrict__ res) {
     count_units<false, false, true>(in, n, nullptr, 0, block_sums, res);
+}
+// ... of a text that goes on behind the buffer (lane_view's LOSSY and OPEN form): the held prefix is neither counted nor replaced
+__global__ __launch_bounds__(kU8Threads) void k_utf8_lossy_open_count(const uint8_t *__restrict__ in, uint32_t n, uint32_t *__restrict__ block_sums,
+                                                                      unsigned long long *__restrict__ res) {
+    count_units<false, true, true>(in, n, nullptr, 0, block_sums, res);
 }
 __global__ __launch_bounds__(kU8Threads) void k_utf8_lossy_batch_count(const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ boff,
                                                                        uint32_t n_hay, uint32_t *__restrict__ block_sums,
@@ -547,6 +577,9 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_batch_map(int32_t *__restri
 //    the batch's last separator that is n, the span's end.  (The checkpoint table has no entry for a separator: x - h would be
 //    the first unit of the next haystack, or n_units.)  A unit at or behind the text's end maps to n as well;
 //  * any other unit: as above for unit x - h of the buffer read as one text; all-ASCII (ckpt == nullptr): the byte x - h itself.
+// LOSSY: locate's, `in` the start bitmap -- the unit of a replaced subpart is the whole subpart, so *out is its first byte, and
+// only a surrogate pair rounds down.
+template <bool LOSSY = false>
 __global__ void k_utf8_batch_pos(uint32_t x, const uint32_t *__restrict__ cat_off, uint32_t n_hay, const uint32_t *__restrict__ boff,
                                  const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ ckpt, int64_t *__restrict__ out) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
@@ -568,7 +601,7 @@ __global__ void k_utf8_batch_pos(uint32_t x, const uint32_t *__restrict__ cat_of
         return;
     }
     SeqPos s;
-    (void)locate(in, n, ckpt, u, s);
+    (void)locate<LOSSY>(in, n, ckpt, u, s);
     *out = (int64_t)s.p;
 }
 
@@ -605,12 +638,14 @@ int utf8_map_records(const Utf8Text &text, const Utf8Batch *b, int32_t *d_recs, 
 }
 
 int utf8_map_position(const Utf8Text &text, const Utf8Batch *b, uint64_t unit, int64_t *d_out, hipStream_t stream) {
-    if (text.lossy) return ACGPU_E_INVALID; // (replace is not built in lossy form)
     if (b ? !b->d_cat_off || !b->n_haystacks || unit >= (1ull << 32)
           : !text.d_ckpt || unit >= text.n_units) // (a checkpoint is written for the text's units only)
         return ACGPU_E_INVALID;
-    hipLaunchKernelGGL(k_utf8_batch_pos, dim3(1), dim3(1), 0, stream, (uint32_t)unit, b ? b->d_cat_off : nullptr, b ? b->n_haystacks : 0u,
-                       b ? b->d_boff : nullptr, text.d_bytes, (uint32_t)text.n_bytes, text.d_ckpt, d_out);
+    // (lossy: the walk reads the start bitmap; without checkpoints -- an all-ASCII batch, or one with as many units as bytes --
+    // neither is read)
+    hipLaunchKernelGGL(text.lossy ? k_utf8_batch_pos<true> : k_utf8_batch_pos<false>, dim3(1), dim3(1), 0, stream, (uint32_t)unit,
+                       b ? b->d_cat_off : nullptr, b ? b->n_haystacks : 0u, b ? b->d_boff : nullptr, walked(text), (uint32_t)text.n_bytes, text.d_ckpt,
+                       d_out);
     HIP_TRY(hipGetLastError());
     return ACGPU_OK;
 }
@@ -651,18 +686,20 @@ struct Utf8Aux {
 // (n_hay != 0: a batch with its offsets in x.boff; open: a text that goes on), the scan of the block sums, and the one wait this
 // front end adds -- the shard cannot be sized, nor the scan begun, before the text is known to be well-formed.  Fills in
 // n_units, first_bad, tail, n_bytes (the bytes before the held prefix), d_bytes and d_ckpt, the table the write kernel is to fill.
-// errors == replace (not open): the lossy count kernels, n_replaced with the rest in the one wait, and the call goes on whatever
-// they saw; d_starts with d_ckpt, the bitmap the write kernel is to fill.
+// errors == replace: the lossy count kernels, n_replaced with the rest in the one wait, and the call goes on whatever they saw;
+// d_starts with d_ckpt, the bitmap the write kernel is to fill.  Open as well: the held prefix comes in the same 32 bytes.
 int utf8_validate(const Utf8Aux &x, uint32_t n_hay, bool open, Utf8Errors errors, hipStream_t stream, Utf8Text *text) {
     const dim3 grid(x.n_blocks), block(kU8Threads);
     const bool lossy = errors == Utf8Errors::replace;
-    if (lossy && open) return ACGPU_E_INVALID;
     HIP_TRY(hipMemsetAsync(x.res, 0xff, 16, stream));
     if (lossy) {
         HIP_TRY(hipMemsetAsync(x.res + 3, 0, 8, stream));
         if (n_hay)
             hipLaunchKernelGGL(k_utf8_lossy_batch_count, grid, block, 0, stream, x.in, x.n, (const uint32_t *)x.boff, n_hay, x.sums, x.res);
-        else
+        else if (open) {
+            HIP_TRY(hipMemsetAsync(x.res + 2, 0, 8, stream));
+            hipLaunchKernelGGL(k_utf8_lossy_open_count, grid, block, 0, stream, x.in, x.n, x.sums, x.res);
+        } else
             hipLaunchKernelGGL(k_utf8_lossy_count, grid, block, 0, stream, x.in, x.n, x.sums, x.res);
     } else if (n_hay) {
         hipLaunchKernelGGL(k_utf8_batch_count, grid, block, 0, stream, x.in, x.n, (const uint32_t *)x.boff, n_hay, x.sums, x.res);
@@ -681,7 +718,7 @@ int utf8_validate(const Utf8Aux &x, uint32_t n_hay, bool open, Utf8Errors errors
     text->first_bad = (int64_t)h_res[1];
     text->lossy = lossy;
     if (lossy) {
-        h_res[2] = 0; // (no held prefix; the word was not preset)
+        if (!open) h_res[2] = 0; // (no held prefix; the word was not preset)
         text->n_replaced = h_res[3];
         if ((text->first_bad >= 0) != (text->n_replaced != 0) || text->n_replaced > x.n) return ACGPU_E_HIP; // (never)
     } else if (text->first_bad >= 0) {
@@ -726,11 +763,11 @@ int stage_utf8_parts(DeviceState &d, const uint8_t *head, uint64_t n_head, const
     if ((rc = utf8_validate(x, 0, open, errors, stream, out))) return rc;
     if ((rc = d.stage_hay.ensure(out->n_units * 2 + 16))) return rc;
     const uint32_t n_text = (uint32_t)out->n_bytes, n_text_blocks = (n_text + kU8Block - 1) / kU8Block;
-    if (lossy) // (n_text = n: nothing is held, the grid is the one the bitmap was sized for)
+    if (lossy && n_text_blocks) // (n_text <= n: the grid is at most the one the bitmap was sized for, and no word behind n_text's is read)
         hipLaunchKernelGGL(k_utf8_lossy_write, dim3(n_text_blocks), dim3(kU8Threads), 0, stream, x.in, n_text, (const uint32_t *)x.sums,
                            reinterpret_cast<uint16_t *>(d.stage_hay.p), (uint32_t)out->n_units, out->d_ckpt ? x.ckpt : nullptr,
                            out->d_starts ? x.starts : nullptr);
-    else if (n_text_blocks) // (a buffer that is a held prefix and nothing else has no unit to write)
+    else if (!lossy && n_text_blocks) // (a buffer that is a held prefix and nothing else has no unit to write)
         hipLaunchKernelGGL(k_utf8_write, dim3(n_text_blocks), dim3(kU8Threads), 0, stream, x.in, n_text, (const uint32_t *)x.sums,
                            reinterpret_cast<uint16_t *>(d.stage_hay.p), (uint32_t)out->n_units, out->d_ckpt ? x.ckpt : nullptr);
     HIP_TRY(hipGetLastError());

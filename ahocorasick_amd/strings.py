@@ -67,14 +67,20 @@ def utf8_line_offsets(data):
     return np.concatenate([np.zeros(1, np.uint64), ends, np.array(tail, np.uint64)])
 
 
-def _utf8_entry(name, strict_stats, errors):
+def _utf8_entry(name, strict_stats, errors, lossy_stats=N.Utf8LossyStats):
     """(the native entry, its stats type) for errors="strict" | "replace" -- the lossy entries scan every maximal ill-formed
     subpart as one U+FFFD, as bytes.decode("utf-8", "replace") does; anything else is refused before a native call"""
-    if errors == "strict":
+    if _check_errors(errors) == "strict":
         return getattr(N.lib(), name), strict_stats
-    if errors == "replace":
-        return getattr(N.lib(), name + "_lossy"), N.Utf8LossyStats
-    raise ValueError("errors must be 'strict' or 'replace', not %r" % (errors,))
+    return getattr(N.lib(), name + "_lossy"), lossy_stats
+
+
+def _check_errors(errors):
+    """errors= of a method that reaches its native entry later (a generator's first next(), a stream's first feed): the same
+    ValueError, now"""
+    if errors not in ("strict", "replace"):
+        raise ValueError("errors must be 'strict' or 'replace', not %r" % (errors,))
+    return errors
 
 
 def _pack_utf8(data, offsets):
@@ -374,11 +380,14 @@ class Automaton:
         blob = np.concatenate(parts + [np.zeros(1, np.uint8)])  # (never an empty array: its pointer is read as "no table")
         return np.ascontiguousarray(blob, dtype=np.uint8), off, len(parts)
 
-    def replace_utf8(self, data, replacements, cap=None, stats=None):
+    def replace_utf8(self, data, replacements, cap=None, stats=None, errors="strict"):
         """acgpu_replace_utf8: a UTF-8 haystack (bytes, bytearray, memoryview or uint8 array) in host memory -> (the rewritten
         bytes as a uint8 array, stats dict); outside the matches a byte-for-byte copy.  `replacements`: a list with one str
         (encoded as UTF-8), bytes, bytearray or uint8 array per keyword given to the constructor, or a single one for all of
-        them.  Ill-formed input raises Utf8Error.  The one retry of replace_host; stats: an N.Utf8Stats to fill in, if wanted."""
+        them.  Ill-formed input raises Utf8Error.  The one retry of replace_host; stats: an N.Utf8Stats to fill in, if wanted.
+        errors="replace": acgpu_replace_utf8_lossy -- the matches are those of match_utf8(errors="replace"), outside them the
+        result is still a copy of `data`, ill-formed bytes included; nothing is raised, and stats is an N.Utf8LossyStats."""
+        entry, stats_type = _utf8_entry("acgpu_replace_utf8", N.Utf8Stats, errors)
         buf = _utf8_bytes(data)
         n = int(buf.size)
         buf_in = buf if n else np.zeros(1, np.uint8)
@@ -386,25 +395,28 @@ class Automaton:
         if cap is None:
             cap = n + n // 4 + 64
         st = N.ReplaceStats()
-        ust = stats if stats is not None else N.Utf8Stats()
+        ust = stats if stats is not None else stats_type()
         for attempt in (0, 1):
             out = np.empty(max(cap, 1), dtype=np.uint8)
             n_out = ctypes.c_uint64(0)
-            rc = N.lib().acgpu_replace_utf8(self._h, _vp(buf_in), n, _vp(r_bytes), _vp(off), n_repl, _vp(out), cap, ctypes.byref(n_out),
-                                            ctypes.byref(st), ctypes.byref(ust))
+            rc = entry(self._h, _vp(buf_in), n, _vp(r_bytes), _vp(off), n_repl, _vp(out), cap, ctypes.byref(n_out),
+                       ctypes.byref(st), ctypes.byref(ust))
             if rc == N.E_OVERFLOW and attempt == 0:
                 cap = int(n_out.value)
                 continue
-            if rc == N.E_ENCODING:
+            if rc == N.E_ENCODING and errors == "strict":
                 raise Utf8Error(ust.first_bad)
             N.check(rc, "acgpu_replace_utf8")
             return out[:n_out.value], {f: int(getattr(st, f)) for f, _ in N.ReplaceStats._fields_}
 
-    def replace_batch_utf8(self, data, replacements, cap=None, stats=None, offsets=None):
+    def replace_batch_utf8(self, data, replacements, cap=None, stats=None, offsets=None, errors="strict"):
         """acgpu_replace_batch_utf8: many short UTF-8 haystacks rewritten in one call -> (uint8 array, out_offsets, stats dict):
         the result of haystack i is out[out_offsets[i]:out_offsets[i + 1]], byte for byte what replace_utf8 returns for it.
         data and offsets as for match_batch_utf8, `replacements` as for replace_utf8, the one retry of replace_batch.  An
-        ill-formed haystack raises Utf8Error (.haystack, and .start inside it); stats: an N.Utf8BatchStats to fill in, if wanted."""
+        ill-formed haystack raises Utf8Error (.haystack, and .start inside it); stats: an N.Utf8BatchStats to fill in, if wanted.
+        errors="replace": acgpu_replace_batch_utf8_lossy -- every haystack as replace_utf8(errors="replace") rewrites it alone;
+        nothing is raised, and stats is an N.Utf8LossyStats."""
+        entry, stats_type = _utf8_entry("acgpu_replace_batch_utf8", N.Utf8BatchStats, errors)
         buf, off = _pack_utf8(data, offsets)
         r_bytes, r_off, n_repl = self._replacements_utf8(replacements)
         n = int(off[-1] - off[0])
@@ -412,17 +424,17 @@ class Automaton:
             cap = n + n // 4 + 64
         buf_in = buf if buf.size else np.zeros(1, np.uint8)
         st = N.ReplaceStats()
-        ust = stats if stats is not None else N.Utf8BatchStats()
+        ust = stats if stats is not None else stats_type()
         out_off = np.zeros(len(off), dtype=np.uint64)
         for attempt in (0, 1):
             out = np.empty(max(cap, 1), dtype=np.uint8)
             n_out = ctypes.c_uint64(0)
-            rc = N.lib().acgpu_replace_batch_utf8(self._h, _vp(buf_in), _vp(off), len(off) - 1, _vp(r_bytes), _vp(r_off), n_repl, _vp(out), cap,
-                                                  _vp(out_off), ctypes.byref(n_out), ctypes.byref(st), ctypes.byref(ust))
+            rc = entry(self._h, _vp(buf_in), _vp(off), len(off) - 1, _vp(r_bytes), _vp(r_off), n_repl, _vp(out), cap,
+                       _vp(out_off), ctypes.byref(n_out), ctypes.byref(st), ctypes.byref(ust))
             if rc == N.E_OVERFLOW and attempt == 0:
                 cap = int(n_out.value)
                 continue
-            if rc == N.E_ENCODING:
+            if rc == N.E_ENCODING and errors == "strict":
                 raise Utf8Error(ust.first_bad, haystack=ust.bad_haystack)
             N.check(rc, "acgpu_replace_batch_utf8")
             return out[:n_out.value], out_off, {f: int(getattr(st, f)) for f, _ in N.ReplaceStats._fields_}
@@ -599,6 +611,7 @@ class Stream:
         host copy, transfer and scan of neighbouring chunks overlap."""
         self._auto = automaton  # keeps the handle alive
         self._kind = N.REC_MAP if with_ids else N.REC_SET
+        self._errors = None  # the policy of a stream of bytes: its first byte feed's, every later one's
         h = ctypes.c_void_p()
         N.check(N.lib().acgpu_stream_open(automaton.handle, ctypes.byref(h)), "acgpu_stream_open")
         self._h = h
@@ -610,6 +623,16 @@ class Stream:
         p = ctypes.c_void_p()
         N.check(N.lib().acgpu_stream_reserve(self._h, int(n_units), ctypes.byref(p)), "acgpu_stream_reserve")
         return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint16)), shape=(int(n_units),))
+
+    def _utf8_policy(self, name, strict_stats, errors):
+        """_utf8_entry for a feed of bytes -> (the entry's name, its stats type): the first byte feed fixes the stream's policy,
+        and a feed with the other one is refused here as the library would refuse it (ACGPU_E_INVALID), without a native call."""
+        entry, stats_type = _utf8_entry(name, strict_stats, errors, N.Utf8LossyStreamStats)
+        if self._errors is None:
+            self._errors = errors
+        elif self._errors != errors:
+            raise ValueError("errors=%r on a stream that is fed with errors=%r" % (errors, self._errors))
+        return entry.__name__, stats_type
 
     def _feed(self, entry, src, n, final, cap, stats=None):
         """The body of feed and feed_utf8: one record buffer per stream (a fresh one per feed costs more than the feed), the same
@@ -629,7 +652,7 @@ class Stream:
             if rc == N.E_OVERFLOW:  # nothing was consumed: same feed, larger buffer
                 cap = int(n_out.value)
                 continue
-            if rc == N.E_ENCODING and stats is not None:
+            if rc == N.E_ENCODING and hasattr(stats, "first_bad"):
                 raise Utf8Error(stats.first_bad)
             N.check(rc, entry)
             r = out[:n_out.value].astype(np.int64)
@@ -640,14 +663,17 @@ class Stream:
         u = np.ascontiguousarray(units, dtype=np.uint16)  # (a view of the reserved staging memory stays where it is)
         return self._feed("acgpu_stream_feed", u if u.size else np.zeros(1, np.uint16), int(u.size), final, cap)
 
-    def feed_utf8(self, data, final=False, cap=None, stats=None):
+    def feed_utf8(self, data, final=False, cap=None, stats=None, errors="strict"):
         """acgpu_stream_feed_utf8: the next bytes of a UTF-8 text (bytes-like or a uint8 array; a chunk may end inside a
         sequence) -> the records that have become decidable as an (n, 2|3) int64 array with GLOBAL BYTE offsets (bytes since the
         first feed), end exclusive.  Ill-formed input raises Utf8Error (.start: the global offset) and finishes the stream.
-        A stream is fed either units or bytes.  stats: an N.Utf8StreamStats to fill in, if wanted."""
+        A stream is fed either units or bytes.  stats: an N.Utf8StreamStats to fill in, if wanted.
+        errors="replace": acgpu_stream_feed_utf8_lossy -- the records of match_utf8(errors="replace") on everything fed, whatever
+        the chunking; nothing is raised, and stats is an N.Utf8LossyStreamStats.  The first feed fixes the stream's policy."""
+        entry, stats_type = self._utf8_policy("acgpu_stream_feed_utf8", N.Utf8StreamStats, errors)
         buf = _utf8_bytes(data)
-        return self._feed("acgpu_stream_feed_utf8", buf if buf.size else np.zeros(1, np.uint8), int(buf.size), final, cap,
-                          stats if stats is not None else N.Utf8StreamStats())
+        return self._feed(entry, buf if buf.size else np.zeros(1, np.uint8), int(buf.size), final, cap,
+                          stats if stats is not None else stats_type())
 
     def _replace_feed(self, entry, src, table, final, cap, stats):
         """The body of replace_feed and replace_feed_utf8: the same feed again with the room it asks for, the result as an array of
@@ -666,7 +692,7 @@ class Stream:
             if rc == N.E_OVERFLOW and int(n_out.value) > cap:  # nothing was committed: same feed, the room it asks for
                 cap = int(n_out.value)
                 continue
-            if rc == N.E_ENCODING and len(stats) == 2:
+            if rc == N.E_ENCODING and hasattr(stats[0], "first_bad"):
                 raise Utf8Error(stats[0].first_bad)
             N.check(rc, entry)
             return out[:n_out.value]
@@ -679,13 +705,16 @@ class Stream:
         return self._replace_feed("acgpu_stream_replace_u16", utf16(units), self._auto._replacements(replacements), final, cap,
                                   [stats if stats is not None else N.ReplaceStats()])
 
-    def replace_feed_utf8(self, data, replacements, final=False, stats=None, cap=None, replace_stats=None):
+    def replace_feed_utf8(self, data, replacements, final=False, stats=None, cap=None, replace_stats=None, errors="strict"):
         """acgpu_stream_replace_utf8: the next bytes of a UTF-8 text that is rewritten as it arrives (a chunk may end inside a
         sequence) -> the bytes of the result that have become decidable.  `replacements` as for Automaton.replace_utf8, the same
         at every feed.  Ill-formed input raises Utf8Error (.start: the global offset) and finishes the stream; what had been
-        withheld is not delivered.  stats: an N.Utf8StreamStats, replace_stats: an N.ReplaceStats to fill in, if wanted."""
-        return self._replace_feed("acgpu_stream_replace_utf8", _utf8_bytes(data), self._auto._replacements_utf8(replacements), final, cap,
-                                  [stats if stats is not None else N.Utf8StreamStats(),
+        withheld is not delivered.  stats: an N.Utf8StreamStats, replace_stats: an N.ReplaceStats to fill in, if wanted.
+        errors="replace": acgpu_stream_replace_utf8_lossy -- replace_utf8(errors="replace") of everything fed, whatever the
+        chunking; nothing is raised, and stats is an N.Utf8LossyStreamStats.  The first feed fixes the stream's policy."""
+        entry, stats_type = self._utf8_policy("acgpu_stream_replace_utf8", N.Utf8StreamStats, errors)
+        return self._replace_feed(entry, _utf8_bytes(data), self._auto._replacements_utf8(replacements), final, cap,
+                                  [stats if stats is not None else stats_type(),
                                    replace_stats if replace_stats is not None else N.ReplaceStats()]).tobytes()
 
     def close(self):
@@ -735,14 +764,14 @@ def _byte_chunks(readable, chunk_bytes):
         yield from readable
 
 
-def _utf8_stream_pages(auto, readable, chunk_bytes, with_ids):
+def _utf8_stream_pages(auto, readable, chunk_bytes, with_ids, errors="strict"):
     """The records of a UTF-8 text that is read chunk by chunk, as one int64 array of global byte offsets per feed; closing the
     generator closes the stream, and no chunk is read before the records of the one before it have been taken."""
     st = Stream(auto, with_ids=with_ids)
     try:
         for chunk in _byte_chunks(readable, chunk_bytes):
-            yield st.feed_utf8(chunk)
-        yield st.feed_utf8(b"", final=True)
+            yield st.feed_utf8(chunk, errors=errors)
+        yield st.feed_utf8(b"", final=True, errors=errors)
     finally:
         st.close()
 
@@ -961,20 +990,25 @@ class StringSet(_BatchDecisions):
         of microseconds of fixed cost) -> a list of str."""
         return _split_batch(*self._auto.replace_batch(_checked(haystacks), str(replacement))[:2])
 
-    def replace_utf8(self, data, replacement):
+    def replace_utf8(self, data, replacement, errors="strict"):
         """Not in the reference: the UTF-8 haystack `data` (bytes, bytearray, memoryview or uint8 array) with every match
         replaced by `replacement` (a str, encoded as UTF-8, or bytes taken as they are; empty deletes the matches) -> bytes,
-        rewritten on the device without a decode or an encode on the host.  Utf8Error if `data` is ill-formed."""
+        rewritten on the device without a decode or an encode on the host.  Utf8Error if `data` is ill-formed -- unless
+        errors="replace": then the matches are those of find_all_utf8(data, errors="replace"), and every byte outside them,
+        ill-formed ones included, is copied as it is."""
+        _check_errors(errors)
         if data is None:
             raise TypeError("haystack is None")
-        return self._auto.replace_utf8(data, replacement if isinstance(replacement, (bytes, bytearray)) else str(replacement))[0].tobytes()
+        return self._auto.replace_utf8(data, replacement if isinstance(replacement, (bytes, bytearray)) else str(replacement), errors=errors)[0].tobytes()
 
-    def replace_batch_utf8(self, datas, replacement, offsets=None):
+    def replace_batch_utf8(self, datas, replacement, offsets=None, errors="strict"):
         """Not in the reference: [replace_utf8(d, replacement) for d in datas] in ONE device call -> a list of bytes, one per
         haystack.  datas: a sequence of bytes-like objects, or with offsets= ONE buffer used in place -- a log file line by line:
-        replace_batch_utf8(buf, "***", offsets=utf8_line_offsets(buf)).  Utf8Error (.haystack, .start) if one is ill-formed."""
+        replace_batch_utf8(buf, "***", offsets=utf8_line_offsets(buf)).  Utf8Error (.haystack, .start) if one is ill-formed --
+        unless errors="replace" (see replace_utf8)."""
+        _check_errors(errors)
         r = replacement if isinstance(replacement, (bytes, bytearray)) else str(replacement)
-        return _split_batch_utf8(*self._auto.replace_batch_utf8(datas if offsets is not None else _checked(datas), r, offsets=offsets)[:2])
+        return _split_batch_utf8(*self._auto.replace_batch_utf8(datas if offsets is not None else _checked(datas), r, offsets=offsets, errors=errors)[:2])
 
     def replace_readable(self, readable, replacement, chunk_chars=1 << 22):
         """Not in the reference: replace() for a text that is read as it goes -- an object with read(n) -> str, or an iterable of
@@ -982,12 +1016,14 @@ class StringSet(_BatchDecisions):
         whole text; a feed yields what no later chunk can change.  Closing the generator closes the stream."""
         return _replace_stream(self._auto, _chunks(readable, chunk_chars), _str_feed(), str(replacement), "")
 
-    def replace_utf8_readable(self, readable, replacement, chunk_bytes=1 << 22):
+    def replace_utf8_readable(self, readable, replacement, chunk_bytes=1 << 22, errors="strict"):
         """Not in the reference: replace_utf8() for a text that is read as it goes -- a binary file object or an iterable of
         bytes-like chunks, cut anywhere, inside a sequence too (see match_utf8_readable) -> a generator of bytes whose
-        concatenation is replace_utf8() of the whole text.  Utf8Error (.start: the global offset) if the text is ill-formed."""
+        concatenation is replace_utf8() of the whole text.  Utf8Error (.start: the global offset) if the text is ill-formed --
+        unless errors="replace": then nothing is raised, and the concatenation is replace_utf8(errors="replace") of the whole."""
+        _check_errors(errors)
         r = replacement if isinstance(replacement, (bytes, bytearray)) else str(replacement)
-        feed = lambda st, chunk, r, final=False: st.replace_feed_utf8(chunk, r, final=final)
+        feed = lambda st, chunk, r, final=False: st.replace_feed_utf8(chunk, r, final=final, errors=errors)
         return _replace_stream(self._auto, _byte_chunks(readable, chunk_bytes), feed, r, b"")
 
     def find_all(self, haystack):
@@ -1009,13 +1045,15 @@ class StringSet(_BatchDecisions):
             if not fn(data, s, e):
                 return
 
-    def match_utf8_readable(self, readable, listener, chunk_bytes=1 << 22):
+    def match_utf8_readable(self, readable, listener, chunk_bytes=1 << 22, errors="strict"):
         """Not in the reference: match_utf8 for a text that is read as it goes -- a binary file object (read(n)) or an iterable
         of bytes-like chunks, cut anywhere, inside a sequence too.  The listener gets (start, end) in GLOBAL byte offsets (there
         is no one haystack object to hand over); a call that returns False stops the feeding AND the reading.  Utf8Error
-        (.start: the global offset) if the text is ill-formed."""
+        (.start: the global offset) if the text is ill-formed -- unless errors="replace": the records of
+        match_utf8(errors="replace") on the whole text, whatever the chunking."""
+        _check_errors(errors)
         fn = _listener_fn(listener)
-        pages = _utf8_stream_pages(self._auto, readable, chunk_bytes, False)
+        pages = _utf8_stream_pages(self._auto, readable, chunk_bytes, False, errors)
         try:
             for page in pages:
                 for s, e in page.tolist():
@@ -1024,10 +1062,11 @@ class StringSet(_BatchDecisions):
         finally:
             pages.close()
 
-    def find_all_utf8_readable(self, readable, chunk_bytes=1 << 22):
+    def find_all_utf8_readable(self, readable, chunk_bytes=1 << 22, errors="strict"):
         """Not in the reference: the (n,2) int64 array of (start, end) records of a UTF-8 text read chunk by chunk, in GLOBAL
-        byte offsets -- find_all_utf8 of the whole text, which may be longer than 2^31 bytes."""
-        pages = list(_utf8_stream_pages(self._auto, readable, chunk_bytes, False))
+        byte offsets -- find_all_utf8 of the whole text, which may be longer than 2^31 bytes (errors: as find_all_utf8)."""
+        _check_errors(errors)
+        pages = list(_utf8_stream_pages(self._auto, readable, chunk_bytes, False, errors))
         return np.concatenate(pages) if pages else np.zeros((0, 2), np.int64)
 
     def match_batch(self, haystacks, listener):
@@ -1127,33 +1166,36 @@ class StringMap(_BatchDecisions):
         StringSet.replace_batch) -> a list of str."""
         return _split_batch(*self._auto.replace_batch(_checked(haystacks), self._replacements_for(replacements))[:2])
 
-    def replace_utf8(self, data, replacements=None):
+    def replace_utf8(self, data, replacements=None, errors="strict"):
         """Not in the reference: the UTF-8 haystack `data` with every match replaced -> bytes (see StringSet.replace_utf8);
         `replacements` under the rules of replace(), a str encoded as UTF-8, bytes taken as they are."""
+        _check_errors(errors)
         if data is None:
             raise TypeError("haystack is None")
         if not isinstance(replacements, (bytes, bytearray)):
             replacements = self._replacements_for(replacements)
-        return self._auto.replace_utf8(data, replacements)[0].tobytes()
+        return self._auto.replace_utf8(data, replacements, errors=errors)[0].tobytes()
 
-    def replace_batch_utf8(self, datas, replacements=None, offsets=None):
+    def replace_batch_utf8(self, datas, replacements=None, offsets=None, errors="strict"):
         """Not in the reference: [replace_utf8(d, replacements) for d in datas] in ONE device call -> a list of bytes (see
         StringSet.replace_batch_utf8); `replacements` under the rules of replace_utf8()."""
+        _check_errors(errors)
         if not isinstance(replacements, (bytes, bytearray)):
             replacements = self._replacements_for(replacements)
-        return _split_batch_utf8(*self._auto.replace_batch_utf8(datas if offsets is not None else _checked(datas), replacements, offsets=offsets)[:2])
+        return _split_batch_utf8(*self._auto.replace_batch_utf8(datas if offsets is not None else _checked(datas), replacements, offsets=offsets, errors=errors)[:2])
 
     def replace_readable(self, readable, replacements=None, chunk_chars=1 << 22):
         """Not in the reference: replace() for a text that is read as it goes -> a generator of str (see
         StringSet.replace_readable); `replacements` under the rules of replace()."""
         return _replace_stream(self._auto, _chunks(readable, chunk_chars), _str_feed(), self._replacements_for(replacements), "")
 
-    def replace_utf8_readable(self, readable, replacements=None, chunk_bytes=1 << 22):
+    def replace_utf8_readable(self, readable, replacements=None, chunk_bytes=1 << 22, errors="strict"):
         """Not in the reference: replace_utf8() for a text that is read as it goes -> a generator of bytes (see
         StringSet.replace_utf8_readable); `replacements` under the rules of replace_utf8()."""
+        _check_errors(errors)
         if not isinstance(replacements, (bytes, bytearray)):
             replacements = self._replacements_for(replacements)
-        feed = lambda st, chunk, r, final=False: st.replace_feed_utf8(chunk, r, final=final)
+        feed = lambda st, chunk, r, final=False: st.replace_feed_utf8(chunk, r, final=final, errors=errors)
         return _replace_stream(self._auto, _byte_chunks(readable, chunk_bytes), feed, replacements, b"")
 
     def _replacements_for(self, replacements):
@@ -1183,12 +1225,13 @@ class StringMap(_BatchDecisions):
             if not fn(data, s, e, vals[k]):
                 return
 
-    def match_utf8_readable(self, readable, listener, chunk_bytes=1 << 22):
+    def match_utf8_readable(self, readable, listener, chunk_bytes=1 << 22, errors="strict"):
         """Not in the reference: match_utf8 for a text that is read as it goes (see StringSet.match_utf8_readable); the listener
         gets (start, end, value) in GLOBAL byte offsets."""
+        _check_errors(errors)
         fn = _listener_fn(listener)
         vals = self._values
-        pages = _utf8_stream_pages(self._auto, readable, chunk_bytes, True)
+        pages = _utf8_stream_pages(self._auto, readable, chunk_bytes, True, errors)
         try:
             for page in pages:
                 for s, e, k in page.tolist():
@@ -1197,10 +1240,11 @@ class StringMap(_BatchDecisions):
         finally:
             pages.close()
 
-    def find_all_utf8_readable(self, readable, chunk_bytes=1 << 22):
+    def find_all_utf8_readable(self, readable, chunk_bytes=1 << 22, errors="strict"):
         """Not in the reference: the (n,3) int64 array of (start, end, keyword_index) records of a UTF-8 text read chunk by
         chunk, in GLOBAL byte offsets (see StringSet.find_all_utf8_readable)."""
-        pages = list(_utf8_stream_pages(self._auto, readable, chunk_bytes, True))
+        _check_errors(errors)
+        pages = list(_utf8_stream_pages(self._auto, readable, chunk_bytes, True, errors))
         return np.concatenate(pages) if pages else np.zeros((0, 3), np.int64)
 
     def match_batch(self, haystacks, listener):

@@ -824,8 +824,10 @@ int acgpu_summary_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, con
  * bitmap from the checkpoint, not the bytes: a start's length is the distance to the next set bit, and it has two units exactly
  * when that is 4 (a subpart has at most 3 bytes).  The bitmap holds the haystack boundaries, so a walk that begins in an earlier
  * haystack needs to know nothing about them.
- * Not built in lossy form: replace and batch replace, the stream feeds and stream replace, errors="ignore" (drop the bytes),
- * the Java facade.  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
+ * Replace, batch replace, the stream feed and stream replace in lossy form: acgpu_replace_utf8_lossy,
+ * acgpu_replace_batch_utf8_lossy, acgpu_stream_feed_utf8_lossy and acgpu_stream_replace_utf8_lossy below.
+ * Not built in lossy form: errors="ignore" (drop the bytes), the Java facade.  ACGPU_ABI_VERSION stays as it is: adding symbols
+ * is compatible.
  */
 typedef struct acgpu_utf8_lossy_stats {
     uint64_t n_units;         /* units the text decodes to, replacements included; batch: separators not counted */
@@ -879,7 +881,7 @@ int acgpu_summary_batch_utf8_lossy(const acgpu_automaton *a, const uint8_t *byte
  * depend on the route, then every haystack takes acgpu_replace_utf8's route with cap, the output position and the stats carried
  * across and the table uploaded once.
  * Not built: device-resident, multi-device and cursor forms, a stream of batches (one long text in chunks:
- * acgpu_stream_replace_utf8 below); validating the replacements; a lossy form (acgpu_match_utf8_lossy: what is built); a one-launch form for tiny batches; the Java facade.  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
+ * acgpu_stream_replace_utf8 below); validating the replacements; a one-launch form for tiny batches; the Java facade.  Lossy form: acgpu_replace_batch_utf8_lossy below.  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
  */
 int acgpu_replace_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
                              const uint8_t *repl_bytes, const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap,
@@ -925,8 +927,9 @@ int acgpu_replace_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, con
  * all-ASCII buffer: nothing to map).  The byte at which the carry is cut for the next feed is found on the host, walking back
  * from the end of the decoded bytes over the lead bytes; it is a code-point boundary, so where the plan's unit is a low
  * surrogate one unit more is carried -- left context that is longer than needed changes no record.
- * Not built: the pipelined and reserved forms for bytes; cursor, count, device-resident and multi-device forms; lossy decoding
- * (U+FFFD); the Java facade (its Readable hands out UTF-16).  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
+ * Lossy decoding (U+FFFD): acgpu_stream_feed_utf8_lossy below.
+ * Not built: the pipelined and reserved forms for bytes; cursor, count, device-resident and multi-device forms; the Java facade
+ * (its Readable hands out UTF-16).  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
  */
 typedef struct acgpu_utf8_stream_stats {
     uint64_t n_units;    /* UTF-16 units the bytes newly decoded by this feed came to (0 on ACGPU_E_ENCODING)                      */
@@ -987,6 +990,78 @@ int acgpu_stream_replace_u16(acgpu_stream *s, const uint16_t *units, uint64_t n_
 int acgpu_stream_replace_utf8(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, const uint8_t *repl_bytes,
                               const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap, uint64_t *n_out,
                               acgpu_utf8_stream_stats *ust /* may be NULL */, acgpu_replace_stats *st /* may be NULL */);
+
+/*
+ * LOSSY replace and LOSSY streams: acgpu_replace_utf8, acgpu_replace_batch_utf8, acgpu_stream_feed_utf8 and acgpu_stream_replace_utf8
+ * for bytes that need not be well-formed.  Nothing is refused and ACGPU_E_ENCODING is never returned; the decoding is that of the
+ * lossy match entries above (every MAXIMAL ILL-FORMED SUBPART is one U+FFFD, and maps to the subpart's bytes).
+ *
+ * acgpu_replace_utf8_lossy, acgpu_replace_batch_utf8_lossy.  RESULT RULE: let r_0 .. r_{k-1} be the Map records that
+ * acgpu_match_utf8_lossy returns for the buffer (a batch: those of acgpu_match_batch_utf8_lossy, haystack by haystack), in BYTE
+ * offsets.  The result is
+ *   T[0:s_0] + repl[id_0] + T[e_0:s_1] + ... + T[e_{k-1}:]
+ * over the CALLER'S bytes T.  Outside the matches it is a byte-for-byte copy of the input, ILL-FORMED BYTES INCLUDED: nothing is
+ * normalised to EF BF BD, and no byte the dictionary did not name is altered -- the rule of every replace entry here.  A keyword
+ * that holds U+FFFD matches a replaced subpart (and a genuine EF BF BD); the subpart's bytes are then what is removed.  On
+ * well-formed input the result is byte for byte that of the strict entry.  The result is well-formed UTF-8 only where the input
+ * outside the matches and the replacements are.
+ * Everything else is the strict counterpart's, whose body these share: the four families (ACGPU_MODE_ALL and a dictionary with an
+ * unpaired surrogate: ACGPU_E_UNSUPPORTED), every ACGPU_E_INVALID before a device is touched and in the same order, the empty
+ * text and the all-empty batch without a device, the overflow contract (exact *n_out and out_offsets, nothing at or beyond
+ * out[cap] written), the NULL stream under the pool's lock, and the haystack-by-haystack route of the batch form.  ust: as
+ * acgpu_match_utf8_lossy / acgpu_match_batch_utf8_lossy fill it (a batch: first_haystack and first_replaced inside it); preset
+ * {0, 0, -1, 0, 1} where no device is needed.
+ * How it works: the text is staged with the lossy kernels, the pieces scan its units, k_utf8_batch_map and k_utf8_batch_pos walk
+ * the start bitmap for a piece's records and its boundary (rounded down to the first byte of the START that holds it: a subpart
+ * is one unit, so only a surrogate pair rounds), and plan and emit run unchanged over the caller's bytes on the device.  No
+ * kernel of their own but the lossy form of k_utf8_batch_pos.
+ *
+ * acgpu_stream_feed_utf8_lossy.  The records of all feeds together are those of acgpu_match_utf8_lossy on the concatenation of
+ * everything fed, in GLOBAL byte offsets (start / end relative to *base), all five families, whatever the chunking.  Arguments,
+ * ACGPU_E_OVERFLOW, ACGPU_E_INVALID, ACGPU_E_UNSUPPORTED and the feeds that need no device: as acgpu_stream_feed_utf8.
+ *  CUT SEQUENCES, lossy.  A feed that is not final holds back its last 1..3 bytes exactly when they are a lead together with
+ *           everything it has claimed so far (the second byte in the range its lead allows, later ones continuation bytes) AND
+ *           that claim reaches the buffer's end while the lead still needs more.  Anything else is decided now: a lead whose
+ *           present bytes already fail is a subpart now.  So ED A0 at the end of a feed is two U+FFFD at once -- the strict
+ *           feed's exception, taken from CPython's incremental decoder, is not mirrored; what is promised is that the chunking
+ *           changes nothing.  With final != 0 nothing is held: a held prefix becomes ONE U+FFFD of 1..3 bytes, as
+ *           bytes.decode("utf-8", "replace") gives for a truncated tail.
+ *  STREAM KIND.  The error policy is part of the stream's kind, fixed by its first byte feed (an empty one included): a strict
+ *           byte feed on a lossy stream returns ACGPU_E_INVALID before any device is touched, and so does the reverse, for the
+ *           match feeds and the replace feeds alike -- six kinds in all.
+ *  stats  : may be NULL.  Summed over the feeds, n_units and n_replaced are those of acgpu_match_utf8_lossy on the whole text (the
+ *           stream keeps the replaced count of the bytes it carries, so none is reported twice).
+ * How it works: k_utf8_lossy_open_count, the validator that is both LOSSY and OPEN -- the held lead is neither a start nor
+ * replaced, the bytes before it decode as a closed text exactly as they do open, so k_utf8_lossy_write runs unchanged over them.
+ * One wait brings four words: res[0] n_units, res[1] the first replaced offset, res[2] the held bytes, res[3] n_replaced.  The
+ * carry is cut at a START -- a lead, or a continuation byte nobody claimed -- which the host finds by restating the claim rule
+ * over the few bytes it walks back from the end; the claim rule looks at most 3 bytes back.
+ *
+ * acgpu_stream_replace_utf8_lossy.  acgpu_stream_replace_utf8 over the lossy feed: the RESULT RULE above applied to the whole
+ * stream, with the records of acgpu_stream_feed_utf8_lossy, and the strict entry's rule for what a feed delivers and withholds; a
+ * held prefix is never delivered before the bytes that complete it (or fail to) or the final feed.  No kernel of its own.
+ * Not built: errors="ignore"; normalising unmatched ill-formed bytes to EF BF BD; pipelined or reserved byte streams; the Java
+ * facade; ACGPU_MODE_ALL.  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
+ */
+typedef struct acgpu_utf8_lossy_stream_stats {
+    uint64_t n_units;     /* units newly decoded by this feed, replacements included */
+    uint64_t n_replaced;  /* of those, U+FFFD that stand for ill-formed subparts     */
+    uint32_t ascii;       /* as acgpu_utf8_stream_stats; 0 as soon as the buffer holds anything replaced */
+    uint32_t held;        /* 0..3                                                    */
+} acgpu_utf8_lossy_stream_stats;   /* 24 bytes */
+int acgpu_replace_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, const uint8_t *repl_bytes,
+                             const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap, uint64_t *n_out,
+                             acgpu_replace_stats *st /* may be NULL */, acgpu_utf8_lossy_stats *ust /* may be NULL */);
+int acgpu_replace_batch_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
+                                   const uint8_t *repl_bytes, const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap,
+                                   uint64_t *out_offsets /* n_haystacks + 1 */, uint64_t *n_out,
+                                   acgpu_replace_stats *st /* may be NULL */, acgpu_utf8_lossy_stats *ust /* may be NULL */);
+int acgpu_stream_feed_utf8_lossy(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, int record_kind,
+                                 void *out, uint64_t cap, uint64_t *n_out, int64_t *base,
+                                 acgpu_utf8_lossy_stream_stats *stats /* may be NULL */);
+int acgpu_stream_replace_utf8_lossy(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, const uint8_t *repl_bytes,
+                                    const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap, uint64_t *n_out,
+                                    acgpu_utf8_lossy_stream_stats *ust /* may be NULL */, acgpu_replace_stats *st /* may be NULL */);
 
 /*
  * Synthetic haystack generator of the benchmark: unit i of the stream is

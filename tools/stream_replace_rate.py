@@ -11,7 +11,10 @@
 All three on the 19.4 MB mixed text of tools/utf8_replace_rate.py and its automaton (WholeWordMatch over the README word list), one
 replacement for every keyword, the three results compared.  Chunks are cut at multiples of the chunk size, wherever that falls in
 a sequence.
-usage: stream_replace_rate.py [--log2 24] [--chunks 4194304,1048576,65536] [--reps 3] [--repl "[redacted]"]"""
+--errors replace: the stream fed through acgpu_stream_replace_utf8_lossy against acgpu_replace_utf8_lossy on the
+whole text -- beside the strict stream where the text is well-formed, and with --damage on a copy in which about one byte per KB
+is overwritten with a random byte from 0x80..0xFF (the strict entries refuse that one).
+usage: stream_replace_rate.py [--log2 24] [--chunks 4194304,1048576,65536] [--reps 3] [--repl "[redacted]"] [--errors strict|replace] [--damage]"""
 import argparse, codecs, ctypes, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -24,6 +27,8 @@ ap.add_argument("--log2", type=int, default=24, help="bytes of the text before t
 ap.add_argument("--chunks", default="4194304,1048576,65536")
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--repl", default="[redacted]")
+ap.add_argument("--errors", default="strict", choices=["strict", "replace"])
+ap.add_argument("--damage", action="store_true", help="with --errors replace: overwrite about one byte per KB")
 args = ap.parse_args()
 
 EXTRA = ["Zürich", "naïve", "straße", "λόγος", "Москва", "東京", "데이터", "😀", "𝒜𝓃𝓈"]  # (tools/utf8_replace_rate.py)
@@ -46,10 +51,10 @@ def timed(fn, reps):
     return float(np.median(ts)) * 1e3, out
 
 
-def stream_bytes(a, data, chunk):
+def stream_bytes(a, data, chunk, errors="strict"):
     st = Stream(a)
     try:
-        parts = [st.replace_feed_utf8(data[i:i + chunk], args.repl, final=i + chunk >= len(data)) for i in range(0, len(data), chunk)]
+        parts = [st.replace_feed_utf8(data[i:i + chunk], args.repl, final=i + chunk >= len(data), errors=errors) for i in range(0, len(data), chunk)]
     finally:
         st.close()
     return b"".join(parts)
@@ -119,8 +124,42 @@ def stream_host(a, data, chunk, cap, split):
     return out
 
 
+def damage(data, seed=7):
+    """a copy with about one byte per KB overwritten by a byte from 0x80..0xFF (tools/utf8_rate.py)"""
+    rng = np.random.default_rng(seed)
+    b = np.frombuffer(data, np.uint8).copy()
+    at = np.arange(0, b.size, 1024) + rng.integers(0, 1024, (b.size + 1023) // 1024)
+    at = at[at < b.size]
+    b[at] = rng.integers(0x80, 0x100, at.size)
+    return b.tobytes()
+
+
+def lossy_routes(a, data):
+    label = "text*" if args.damage else "text"
+    ust = N.Utf8LossyStats()
+    want = a.replace_utf8(data, args.repl, stats=ust, errors="replace")[0].tobytes()
+    cap_out = len(want) + 64
+    ms_whole, _ = timed(lambda: a.replace_utf8(data, args.repl, cap=cap_out, errors="replace"), args.reps)
+    print("%s %d bytes, %d replaced, %d bytes out" % (label, len(data), ust.n_replaced, len(want)))
+    print("whole lossy    : %8.3f ms = %6.2f GB/s of input bytes (acgpu_replace_utf8_lossy, one call)" % (ms_whole, len(data) / ms_whole / 1e6), flush=True)
+    for chunk in [int(c) for c in args.chunks.split(",")]:
+        feeds = -(-len(data) // chunk)
+        ms_lossy, got = timed(lambda: stream_bytes(a, data, chunk, "replace"), args.reps)
+        assert got == want, "the lossy feeds and the lossy call differ"
+        line = "chunk %8d : lossy stream %8.3f ms = %6.2f GB/s (%d feeds, %.3f ms a feed), stream / whole = %.2f" % (
+            chunk, ms_lossy, len(data) / ms_lossy / 1e6, feeds, ms_lossy / feeds, ms_lossy / ms_whole)
+        if not ust.n_replaced:
+            ms_strict, strict = timed(lambda: stream_bytes(a, data, chunk), args.reps)
+            assert strict == want, "lossy and strict differ on well-formed bytes"
+            line += " | strict stream %8.3f ms, lossy / strict = %.3f" % (ms_strict, ms_lossy / ms_strict)
+        print(line, flush=True)
+
+
 words, data = mixed_text(1 << args.log2)
 a = Automaton(N.MODE_WHOLEWORD, words + EXTRA[:7], True, word_chars=default_word_chars())
+if args.errors == "replace":
+    lossy_routes(a, damage(data) if args.damage else data)
+    sys.exit(0)
 n = len(data)
 n_recs = len(a.match_utf8(data, with_ids=True))
 want = a.replace_utf8(data, args.repl)[0].tobytes()

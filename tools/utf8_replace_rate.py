@@ -10,7 +10,10 @@ replacement for every keyword, capacity known (no overflow retry timed), the res
   batch    : acgpu_replace_batch_utf8 on the one buffer and its line offsets (offsets=): one device call;
   per line : one acgpu_replace_utf8 call per line (on the first --per-line lines; the figure is scaled to N);
   decode   : every line decoded on the host, Automaton.replace_batch on the str lines, every result encoded again.
-usage: utf8_replace_rate.py [--log2 24] [--repl "[redacted]"] [--batch 20000 [--per-line 2000]]"""
+--errors replace: acgpu_replace_utf8_lossy on the same buffer (with --batch: acgpu_replace_batch_utf8_lossy) --
+beside the strict call where the buffer is well-formed (the results compared), and with --damage on a copy in which about one byte
+per KB is overwritten with a random byte from 0x80..0xFF (the strict call refuses that one).
+usage: utf8_replace_rate.py [--log2 24] [--repl "[redacted]"] [--batch 20000 [--per-line 2000]] [--errors strict|replace] [--damage]"""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -23,6 +26,8 @@ ap.add_argument("--log2", type=int, default=24, help="bytes of the text, about")
 ap.add_argument("--repl", default="[redacted]")
 ap.add_argument("--batch", type=int, default=0, help="lines of a batch; 0: the one-text measurement")
 ap.add_argument("--per-line", type=int, default=2000)
+ap.add_argument("--errors", default="strict", choices=["strict", "replace"])
+ap.add_argument("--damage", action="store_true", help="with --errors replace: overwrite about one byte per KB")
 args = ap.parse_args()
 
 EXTRA = ["Zürich", "naïve", "straße", "λόγος", "Москва", "東京", "데이터", "😀", "𝒜𝓃𝓈"]
@@ -46,6 +51,33 @@ def timed(fn, reps=5):
 
 
 WORDS_PER_LINE = 12
+def damage(data, seed=7):
+    """a copy with about one byte per KB overwritten by a byte from 0x80..0xFF (tools/utf8_rate.py)"""
+    rng = np.random.default_rng(seed)
+    b = np.frombuffer(data, np.uint8).copy()
+    at = np.arange(0, b.size, 1024) + rng.integers(0, 1024, (b.size + 1023) // 1024)
+    at = at[at < b.size]
+    b[at] = rng.integers(0x80, 0x100, at.size)
+    return b.tobytes()
+
+
+def lossy_routes(a, data, batch_off=None):
+    """the lossy entry on `data` (a batch: with its line offsets) beside the strict one where that takes the buffer"""
+    label = "mix*" if args.damage else "mix"
+    ust = N.Utf8LossyStats()
+    call = (lambda e, **kw: a.replace_batch_utf8(data, args.repl, offsets=batch_off, errors=e, **kw)) if batch_off is not None else (
+        lambda e, **kw: a.replace_utf8(data, args.repl, errors=e, **kw))
+    first = call("replace", stats=ust)
+    cap_out = first[0].size + 64
+    ms_lossy, got = timed(lambda: call("replace", cap=cap_out))
+    print("%-4s %d bytes -> %d units, %d replaced (first at %d), %d records replaced by %r, %d bytes out, %d pieces" % (
+        label, len(data), ust.n_units, ust.n_replaced, ust.first_replaced, got[-1]["n_records"], args.repl, got[0].size, got[-1]["pieces"]))
+    print("%-4s lossy  : %8.3f ms = %6.2f GB/s of input bytes" % (label, ms_lossy, len(data) / ms_lossy / 1e6))
+    if not ust.n_replaced:
+        ms_strict, want = timed(lambda: call("strict", cap=cap_out))
+        assert got[0].tobytes() == want[0].tobytes() and got[-1] == want[-1], "lossy and strict differ on well-formed bytes"
+        print("%-4s strict : %8.3f ms = %6.2f GB/s | ratio lossy / strict = %.3f" % (label, ms_strict, len(data) / ms_strict / 1e6, ms_lossy / ms_strict), flush=True)
+
 
 
 def make_lines(n_lines):
@@ -87,6 +119,12 @@ def batch_routes():
     print("ratios   : per line / batch = %.2f, decode / batch = %.2f" % (ms_line * n / k / ms_batch, decode / ms_batch), flush=True)
 
 
+if args.errors == "replace":
+    words, data = make_lines(args.batch) if args.batch else mixed_text(1 << args.log2)
+    data = damage(data) if args.damage else data
+    lossy_routes(Automaton(N.MODE_WHOLEWORD, words + EXTRA[:7], True, word_chars=default_word_chars()), data,
+                 utf8_line_offsets(data) if args.batch else None)
+    sys.exit(0)
 if args.batch:
     batch_routes()
     sys.exit(0)

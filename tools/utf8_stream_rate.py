@@ -10,7 +10,10 @@
 All three on the 19.4 MB mixed text of tools/utf8_rate.py and its automaton (WholeWordMatch over the README word list), Map records,
 capacity known (no overflow retry timed), the three results compared.  Chunks are cut at multiples of the chunk size, wherever
 that falls in a sequence.
-usage: utf8_stream_rate.py [--log2 24] [--chunks 65536,1048576,4194304] [--reps 3]"""
+--errors replace: the stream fed through acgpu_stream_feed_utf8_lossy against acgpu_match_utf8_lossy on the whole
+text -- beside the strict stream where the text is well-formed, and with --damage on a copy in which about one byte per KB is
+overwritten with a random byte from 0x80..0xFF (the strict entries refuse that one).
+usage: utf8_stream_rate.py [--log2 24] [--chunks 65536,1048576,4194304] [--reps 3] [--errors strict|replace] [--damage]"""
 import argparse, codecs, ctypes, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -22,6 +25,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--log2", type=int, default=24, help="bytes of the text before the non-ASCII tokens go in, about")
 ap.add_argument("--chunks", default="65536,1048576,4194304")
 ap.add_argument("--reps", type=int, default=3)
+ap.add_argument("--errors", default="strict", choices=["strict", "replace"])
+ap.add_argument("--damage", action="store_true", help="with --errors replace: overwrite about one byte per KB")
 args = ap.parse_args()
 
 EXTRA = ["Zürich", "naïve", "straße", "λόγος", "Москва", "東京", "데이터", "😀", "𝒜𝓃𝓈"]  # (tools/utf8_rate.py)
@@ -44,10 +49,10 @@ def timed(fn, reps):
     return float(np.median(ts)) * 1e3, out
 
 
-def stream_bytes(a, data, chunk, cap):
+def stream_bytes(a, data, chunk, cap, errors="strict"):
     st = Stream(a, with_ids=True)
     try:
-        pages = [st.feed_utf8(data[i:i + chunk], final=i + chunk >= len(data), cap=cap) for i in range(0, len(data), chunk)]
+        pages = [st.feed_utf8(data[i:i + chunk], final=i + chunk >= len(data), cap=cap, errors=errors) for i in range(0, len(data), chunk)]
     finally:
         st.close()
     return np.concatenate(pages)
@@ -109,8 +114,42 @@ def stream_host(a, data, chunk, cap, split):
     return out
 
 
+def damage(data, seed=7):
+    """a copy with about one byte per KB overwritten by a byte from 0x80..0xFF (tools/utf8_rate.py)"""
+    rng = np.random.default_rng(seed)
+    b = np.frombuffer(data, np.uint8).copy()
+    at = np.arange(0, b.size, 1024) + rng.integers(0, 1024, (b.size + 1023) // 1024)
+    at = at[at < b.size]
+    b[at] = rng.integers(0x80, 0x100, at.size)
+    return b.tobytes()
+
+
+def lossy_routes(a, data):
+    label = "text*" if args.damage else "text"
+    ust = N.Utf8LossyStats()
+    want = a.match_utf8(data, with_ids=True, stats=ust, errors="replace")
+    cap = len(want) + 16
+    ms_whole, _ = timed(lambda: a.match_utf8(data, with_ids=True, cap=cap, errors="replace"), args.reps)
+    print("%s %d bytes, %d replaced, %d records" % (label, len(data), ust.n_replaced, len(want)))
+    print("whole lossy    : %8.3f ms = %6.2f GB/s of bytes (acgpu_match_utf8_lossy, one call)" % (ms_whole, len(data) / ms_whole / 1e6), flush=True)
+    for chunk in [int(c) for c in args.chunks.split(",")]:
+        feeds = -(-len(data) // chunk)
+        ms_lossy, got = timed(lambda: stream_bytes(a, data, chunk, cap, "replace"), args.reps)
+        assert got.shape == want.shape and (got == want).all(), "the lossy feeds and the lossy call differ"
+        line = "chunk %8d : lossy stream %8.3f ms = %6.2f GB/s (%d feeds, %.3f ms a feed), stream / whole = %.2f" % (
+            chunk, ms_lossy, len(data) / ms_lossy / 1e6, feeds, ms_lossy / feeds, ms_lossy / ms_whole)
+        if not ust.n_replaced:
+            ms_strict, strict = timed(lambda: stream_bytes(a, data, chunk, cap), args.reps)
+            assert (strict == want).all(), "lossy and strict differ on well-formed bytes"
+            line += " | strict stream %8.3f ms, lossy / strict = %.3f" % (ms_strict, ms_lossy / ms_strict)
+        print(line, flush=True)
+
+
 words, data = mixed_text(1 << args.log2)
 a = Automaton(N.MODE_WHOLEWORD, words + EXTRA[:7], True, word_chars=default_word_chars())
+if args.errors == "replace":
+    lossy_routes(a, damage(data) if args.damage else data)
+    sys.exit(0)
 n = len(data)
 want = a.match_utf8(data, with_ids=True)
 cap = len(want) + 16
