@@ -122,21 +122,81 @@ def _summary_dtype():
 SUMMARY_DTYPE = _summary_dtype()  # one acgpu_batch_summary as a numpy record
 
 
-# every symbol include/acgpu.h declares
-SYMBOLS = ["acgpu_build", "acgpu_free", "acgpu_get_info", "acgpu_match_u16", "acgpu_match_batch_u16", "acgpu_match_device",
-           "acgpu_match_device_begin", "acgpu_match_device_end", "acgpu_match_device_abandon", "acgpu_synth_fill", "acgpu_synth_tokens", "acgpu_stream_probe",
-           "acgpu_set_tunable", "acgpu_strerror", "acgpu_last_hip_error", "acgpu_abi_version", "acgpu_debug_tables", "acgpu_debug_states",
-           "acgpu_debug_wordhash", "acgpu_debug_wordhash_perfect", "acgpu_stream_open", "acgpu_stream_feed", "acgpu_stream_close",
-           "acgpu_match_u16_multi", "acgpu_comm_open", "acgpu_comm_close", "acgpu_comm_transport", "acgpu_comm_stream",
-           "acgpu_match_device_allgather", "acgpu_last_rccl_error", "acgpu_gather_slot_bytes",
-           "acgpu_stream_set_pipelined", "acgpu_stream_reserve", "acgpu_cursor_open", "acgpu_cursor_next",
-           "acgpu_cursor_get_stats", "acgpu_cursor_close", "acgpu_count_u16", "acgpu_count_device",
-           "acgpu_replace_u16", "acgpu_replace_device", "acgpu_replace_batch_u16", "acgpu_summary_batch_u16",
-           "acgpu_match_utf8", "acgpu_replace_utf8", "acgpu_match_batch_utf8", "acgpu_summary_batch_utf8",
-           "acgpu_replace_batch_utf8", "acgpu_stream_feed_utf8", "acgpu_stream_replace_u16",
-           "acgpu_stream_replace_utf8", "acgpu_match_utf8_lossy", "acgpu_match_batch_utf8_lossy",
-           "acgpu_summary_batch_utf8_lossy", "acgpu_replace_utf8_lossy", "acgpu_replace_batch_utf8_lossy",
-           "acgpu_stream_feed_utf8_lossy", "acgpu_stream_replace_utf8_lossy"]
+# the struct a strict UTF-8 entry reports in -> the one its _lossy twin fills instead
+_LOSSY_STATS = {Utf8Stats: Utf8LossyStats, Utf8BatchStats: Utf8LossyStats, Utf8StreamStats: Utf8LossyStreamStats}
+_UTF8_STATS = set(_LOSSY_STATS) | set(_LOSSY_STATS.values())
+
+
+def _signatures():
+    """The C ABI of include/acgpu.h, once: symbol -> (restype, argtypes); argtypes None: ctypes is told nothing about them.  The
+    seven _lossy entries are their strict twins with another stats struct (_LOSSY_STATS) and are derived, not written out."""
+    vp, u64, i64, u32, ci, P = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER
+    sig = {
+        "acgpu_build": (ci, [ci, vp, vp, u32, ci, vp, vp, P(vp), P(i64)]),
+        "acgpu_free": (None, [vp]),
+        "acgpu_get_info": (ci, [vp, P(Info)]),
+        "acgpu_match_u16": (ci, [vp, vp, u64, ci, vp, u64, P(u64)]),
+        "acgpu_match_batch_u16": (ci, [vp, vp, vp, u32, ci, vp, u64, P(u64)]),
+        "acgpu_match_device": (ci, [vp, P(Shard), ci, vp, u64, P(u64), vp, P(Profile)]),
+        "acgpu_match_device_begin": (ci, [vp, P(Shard), ci, vp, u64, vp, ci, P(vp)]),
+        "acgpu_match_device_end": (ci, [vp, vp, P(u64), P(Profile)]),
+        "acgpu_match_device_abandon": (ci, [vp, vp]),
+        "acgpu_synth_fill": (ci, [vp, u64, u64, u64, vp, u32, vp]),
+        "acgpu_synth_tokens": (ci, [vp, u64, u64, vp, vp, u32, vp, vp]),
+        "acgpu_stream_probe": (ci, [vp, u64, vp, ci, ci, P(ctypes.c_float)]),
+        "acgpu_set_tunable": (i64, [ctypes.c_char_p, i64]),
+        "acgpu_strerror": (ctypes.c_char_p, [ci]),
+        "acgpu_last_hip_error": (ci, None),
+        "acgpu_abi_version": (u32, None),
+        "acgpu_debug_states": (ci, [vp, vp, vp, vp, vp, vp, vp]),
+        "acgpu_debug_tables": (ci, [vp, vp, vp, vp, vp, vp, vp, P(u32)]),
+        "acgpu_debug_wordhash_perfect": (ci, [vp, vp, vp, vp, vp, vp, vp]),
+        "acgpu_debug_wordhash": (ci, [vp, P(u32), vp, P(u64), vp, vp, P(u32), vp, P(u32)]),
+        "acgpu_stream_open": (ci, [vp, P(vp)]),
+        "acgpu_stream_feed": (ci, [vp, vp, u64, ci, ci, vp, u64, P(u64), P(i64)]),
+        "acgpu_stream_feed_utf8": (ci, [vp, vp, u64, ci, ci, vp, u64, P(u64), P(i64), P(Utf8StreamStats)]),
+        "acgpu_stream_replace_u16": (ci, [vp, vp, u64, ci, vp, vp, u32, vp, u64, P(u64), P(ReplaceStats)]),
+        "acgpu_stream_replace_utf8": (ci, [vp, vp, u64, ci, vp, vp, u32, vp, u64, P(u64), P(Utf8StreamStats), P(ReplaceStats)]),
+        "acgpu_stream_close": (None, [vp]),
+        "acgpu_stream_set_pipelined": (ci, [vp, ci]),
+        "acgpu_stream_reserve": (ci, [vp, u64, P(vp)]),
+        "acgpu_cursor_open": (ci, [vp, vp, u64, ci, P(vp)]),
+        "acgpu_cursor_next": (ci, [vp, vp, u64, P(u64)]),
+        "acgpu_cursor_get_stats": (ci, [vp, P(CursorStats)]),
+        "acgpu_cursor_close": (None, [vp]),
+        "acgpu_count_u16": (ci, [vp, vp, u64, vp, u32, P(CountStats)]),
+        "acgpu_count_device": (ci, [vp, P(Shard), vp, u32, vp, P(CountStats)]),
+        "acgpu_replace_u16": (ci, [vp, vp, u64, vp, vp, u32, vp, u64, P(u64), P(ReplaceStats)]),
+        "acgpu_replace_device": (ci, [vp, P(Shard), vp, vp, u32, vp, u64, P(u64), vp, P(ReplaceStats)]),
+        "acgpu_replace_batch_u16": (ci, [vp, vp, vp, u32, vp, vp, u32, vp, u64, vp, P(u64), P(ReplaceStats)]),
+        "acgpu_summary_batch_u16": (ci, [vp, vp, vp, u32, vp, P(SummaryStats)]),
+        "acgpu_match_utf8": (ci, [vp, vp, u64, ci, vp, u64, P(u64), P(Utf8Stats)]),
+        "acgpu_match_batch_utf8": (ci, [vp, vp, vp, u32, ci, vp, u64, P(u64), P(Utf8BatchStats)]),
+        "acgpu_summary_batch_utf8": (ci, [vp, vp, vp, u32, vp, P(SummaryStats), P(Utf8BatchStats)]),
+        "acgpu_replace_utf8": (ci, [vp, vp, u64, vp, vp, u32, vp, u64, P(u64), P(ReplaceStats), P(Utf8Stats)]),
+        "acgpu_replace_batch_utf8": (ci, [vp, vp, vp, u32, vp, vp, u32, vp, u64, vp, P(u64), P(ReplaceStats), P(Utf8BatchStats)]),
+        "acgpu_match_u16_multi": (ci, [vp, vp, u64, P(ci), ci, ci, vp, u64, P(u64)]),
+        "acgpu_comm_open": (ci, [P(ci), ci, ci, P(vp)]),
+        "acgpu_comm_close": (None, [vp]),
+        "acgpu_comm_transport": (ci, [vp]),
+        "acgpu_comm_stream": (vp, [vp, ci]),
+        "acgpu_match_device_allgather": (ci, [vp, vp, P(Shard), ci, P(vp), u64, P(u64), P(Profile)]),
+        "acgpu_last_rccl_error": (ci, None),
+        "acgpu_gather_slot_bytes": (u64, [u64, ci]),
+    }
+    for name, (restype, argtypes) in list(sig.items()):
+        twin = [P(_LOSSY_STATS[t._type_]) if getattr(t, "_type_", None) in _LOSSY_STATS else t for t in argtypes or ()]
+        if twin != (argtypes or []):
+            sig[name + "_lossy"] = (restype, twin)
+    return sig
+
+
+SIGNATURES = _signatures()
+SYMBOLS = list(SIGNATURES)  # every symbol include/acgpu.h declares
+
+
+# entry -> the UTF-8 stats struct it fills, for the entries that have one: a key of _LOSSY_STATS for a strict entry, a value for its twin
+UTF8_STATS = {name: t._type_ for name, (_, argtypes) in SIGNATURES.items() for t in argtypes or () if getattr(t, "_type_", None) in _UTF8_STATS}
 
 _lib = None
 
@@ -156,132 +216,11 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        vp, u64, i64, u32, ci = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint32, ctypes.c_int
-        L.acgpu_build.restype = ci
-        L.acgpu_build.argtypes = [ci, vp, vp, u32, ci, vp, vp, ctypes.POINTER(vp), ctypes.POINTER(i64)]
-        L.acgpu_free.restype = None
-        L.acgpu_free.argtypes = [vp]
-        L.acgpu_get_info.restype = ci
-        L.acgpu_get_info.argtypes = [vp, ctypes.POINTER(Info)]
-        L.acgpu_match_u16.restype = ci
-        L.acgpu_match_u16.argtypes = [vp, vp, u64, ci, vp, u64, ctypes.POINTER(u64)]
-        L.acgpu_match_batch_u16.restype = ci
-        L.acgpu_match_batch_u16.argtypes = [vp, vp, vp, u32, ci, vp, u64, ctypes.POINTER(u64)]
-        L.acgpu_match_device.restype = ci
-        L.acgpu_match_device.argtypes = [vp, ctypes.POINTER(Shard), ci, vp, u64, ctypes.POINTER(u64), vp,
-                                         ctypes.POINTER(Profile)]
-        L.acgpu_match_device_begin.restype = ci
-        L.acgpu_match_device_begin.argtypes = [vp, ctypes.POINTER(Shard), ci, vp, u64, vp, ci, ctypes.POINTER(vp)]
-        L.acgpu_match_device_end.restype = ci
-        L.acgpu_match_device_end.argtypes = [vp, vp, ctypes.POINTER(u64), ctypes.POINTER(Profile)]
-        L.acgpu_match_device_abandon.restype = ci
-        L.acgpu_match_device_abandon.argtypes = [vp, vp]
-        L.acgpu_synth_fill.restype = ci
-        L.acgpu_synth_fill.argtypes = [vp, u64, u64, u64, vp, u32, vp]
-        L.acgpu_synth_tokens.restype = ci
-        L.acgpu_synth_tokens.argtypes = [vp, u64, u64, vp, vp, u32, vp, vp]
-        L.acgpu_stream_probe.restype = ci
-        L.acgpu_stream_probe.argtypes = [vp, u64, vp, ci, ci, ctypes.POINTER(ctypes.c_float)]
-        L.acgpu_set_tunable.restype = i64
-        L.acgpu_set_tunable.argtypes = [ctypes.c_char_p, i64]
-        L.acgpu_strerror.restype = ctypes.c_char_p
-        L.acgpu_strerror.argtypes = [ci]
-        L.acgpu_last_hip_error.restype = ci
-        L.acgpu_abi_version.restype = u32
-        L.acgpu_debug_states.restype = ci
-        L.acgpu_debug_states.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-        L.acgpu_debug_tables.restype = ci
-        L.acgpu_debug_tables.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(u32)]
-        L.acgpu_stream_open.restype = ci
-        L.acgpu_stream_open.argtypes = [vp, ctypes.POINTER(vp)]
-        L.acgpu_stream_feed.restype = ci
-        L.acgpu_stream_feed.argtypes = [vp, vp, u64, ci, ci, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(i64)]
-        L.acgpu_stream_feed_utf8.restype = ci
-        L.acgpu_stream_feed_utf8.argtypes = [vp, vp, u64, ci, ci, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(i64),
-                                             ctypes.POINTER(Utf8StreamStats)]
-        L.acgpu_stream_replace_u16.restype = ci
-        L.acgpu_stream_replace_u16.argtypes = [vp, vp, u64, ci, vp, vp, u32, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(ReplaceStats)]
-        L.acgpu_stream_replace_utf8.restype = ci
-        L.acgpu_stream_replace_utf8.argtypes = [vp, vp, u64, ci, vp, vp, u32, vp, u64, ctypes.POINTER(u64),
-                                                ctypes.POINTER(Utf8StreamStats), ctypes.POINTER(ReplaceStats)]
-        L.acgpu_stream_close.restype = None
-        L.acgpu_stream_close.argtypes = [vp]
-        L.acgpu_stream_set_pipelined.restype = ci
-        L.acgpu_stream_set_pipelined.argtypes = [vp, ci]
-        L.acgpu_stream_reserve.restype = ci
-        L.acgpu_stream_reserve.argtypes = [vp, u64, ctypes.POINTER(vp)]
-        L.acgpu_cursor_open.restype = ci
-        L.acgpu_cursor_open.argtypes = [vp, vp, u64, ci, ctypes.POINTER(vp)]
-        L.acgpu_cursor_next.restype = ci
-        L.acgpu_cursor_next.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
-        L.acgpu_cursor_get_stats.restype = ci
-        L.acgpu_cursor_get_stats.argtypes = [vp, ctypes.POINTER(CursorStats)]
-        L.acgpu_cursor_close.restype = None
-        L.acgpu_cursor_close.argtypes = [vp]
-        L.acgpu_count_u16.restype = ci
-        L.acgpu_count_u16.argtypes = [vp, vp, u64, vp, u32, ctypes.POINTER(CountStats)]
-        L.acgpu_count_device.restype = ci
-        L.acgpu_count_device.argtypes = [vp, ctypes.POINTER(Shard), vp, u32, vp, ctypes.POINTER(CountStats)]
-        L.acgpu_replace_u16.restype = ci
-        L.acgpu_replace_u16.argtypes = [vp, vp, u64, vp, vp, u32, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(ReplaceStats)]
-        L.acgpu_replace_device.restype = ci
-        L.acgpu_replace_device.argtypes = [vp, ctypes.POINTER(Shard), vp, vp, u32, vp, u64, ctypes.POINTER(u64), vp,
-                                           ctypes.POINTER(ReplaceStats)]
-        L.acgpu_replace_batch_u16.restype = ci
-        L.acgpu_replace_batch_u16.argtypes = [vp, vp, vp, u32, vp, vp, u32, vp, u64, vp, ctypes.POINTER(u64), ctypes.POINTER(ReplaceStats)]
-        L.acgpu_summary_batch_u16.restype = ci
-        L.acgpu_summary_batch_u16.argtypes = [vp, vp, vp, u32, vp, ctypes.POINTER(SummaryStats)]
-        L.acgpu_match_utf8.restype = ci
-        L.acgpu_match_utf8.argtypes = [vp, vp, u64, ci, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(Utf8Stats)]
-        L.acgpu_match_batch_utf8.restype = ci
-        L.acgpu_match_batch_utf8.argtypes = [vp, vp, vp, u32, ci, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(Utf8BatchStats)]
-        L.acgpu_summary_batch_utf8.restype = ci
-        L.acgpu_summary_batch_utf8.argtypes = [vp, vp, vp, u32, vp, ctypes.POINTER(SummaryStats), ctypes.POINTER(Utf8BatchStats)]
-        L.acgpu_match_utf8_lossy.restype = ci
-        L.acgpu_match_utf8_lossy.argtypes = [vp, vp, u64, ci, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(Utf8LossyStats)]
-        L.acgpu_match_batch_utf8_lossy.restype = ci
-        L.acgpu_match_batch_utf8_lossy.argtypes = [vp, vp, vp, u32, ci, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(Utf8LossyStats)]
-        L.acgpu_summary_batch_utf8_lossy.restype = ci
-        L.acgpu_summary_batch_utf8_lossy.argtypes = [vp, vp, vp, u32, vp, ctypes.POINTER(SummaryStats), ctypes.POINTER(Utf8LossyStats)]
-        L.acgpu_replace_utf8_lossy.restype = ci
-        L.acgpu_replace_utf8_lossy.argtypes = [vp, vp, u64, vp, vp, u32, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(ReplaceStats),
-                                               ctypes.POINTER(Utf8LossyStats)]
-        L.acgpu_replace_batch_utf8_lossy.restype = ci
-        L.acgpu_replace_batch_utf8_lossy.argtypes = [vp, vp, vp, u32, vp, vp, u32, vp, u64, vp, ctypes.POINTER(u64), ctypes.POINTER(ReplaceStats),
-                                                     ctypes.POINTER(Utf8LossyStats)]
-        L.acgpu_stream_feed_utf8_lossy.restype = ci
-        L.acgpu_stream_feed_utf8_lossy.argtypes = [vp, vp, u64, ci, ci, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(i64),
-                                                   ctypes.POINTER(Utf8LossyStreamStats)]
-        L.acgpu_stream_replace_utf8_lossy.restype = ci
-        L.acgpu_stream_replace_utf8_lossy.argtypes = [vp, vp, u64, ci, vp, vp, u32, vp, u64, ctypes.POINTER(u64),
-                                                      ctypes.POINTER(Utf8LossyStreamStats), ctypes.POINTER(ReplaceStats)]
-        L.acgpu_replace_utf8.restype = ci
-        L.acgpu_replace_utf8.argtypes = [vp, vp, u64, vp, vp, u32, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(ReplaceStats),
-                                         ctypes.POINTER(Utf8Stats)]
-        L.acgpu_replace_batch_utf8.restype = ci
-        L.acgpu_replace_batch_utf8.argtypes = [vp, vp, vp, u32, vp, vp, u32, vp, u64, vp, ctypes.POINTER(u64), ctypes.POINTER(ReplaceStats),
-                                               ctypes.POINTER(Utf8BatchStats)]
-        L.acgpu_debug_wordhash_perfect.restype = ci
-        L.acgpu_debug_wordhash_perfect.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-        L.acgpu_debug_wordhash.restype = ci
-        L.acgpu_debug_wordhash.argtypes = [vp, ctypes.POINTER(u32), vp, ctypes.POINTER(u64), vp, vp, ctypes.POINTER(u32), vp,
-                                           ctypes.POINTER(u32)]
-        L.acgpu_match_u16_multi.restype = ci
-        L.acgpu_match_u16_multi.argtypes = [vp, vp, u64, ctypes.POINTER(ci), ci, ci, vp, u64, ctypes.POINTER(u64)]
-        L.acgpu_comm_open.restype = ci
-        L.acgpu_comm_open.argtypes = [ctypes.POINTER(ci), ci, ci, ctypes.POINTER(vp)]
-        L.acgpu_comm_close.restype = None
-        L.acgpu_comm_close.argtypes = [vp]
-        L.acgpu_comm_transport.restype = ci
-        L.acgpu_comm_transport.argtypes = [vp]
-        L.acgpu_comm_stream.restype = vp
-        L.acgpu_comm_stream.argtypes = [vp, ci]
-        L.acgpu_match_device_allgather.restype = ci
-        L.acgpu_match_device_allgather.argtypes = [vp, vp, ctypes.POINTER(Shard), ci, ctypes.POINTER(vp), u64, ctypes.POINTER(u64),
-                                                   ctypes.POINTER(Profile)]
-        L.acgpu_last_rccl_error.restype = ci
-        L.acgpu_gather_slot_bytes.restype = u64
-        L.acgpu_gather_slot_bytes.argtypes = [u64, ci]
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = restype
+            if argtypes is not None:
+                fn.argtypes = argtypes
         if L.acgpu_abi_version() != ABI_VERSION:
             raise ImportError("ahocorasick_amd: %s has ABI version %d, this package binds version %d -- rebuild it"
                               % (LIB_PATH, L.acgpu_abi_version(), ABI_VERSION))

@@ -17,8 +17,13 @@ stops at the first listener call that returns False -- which is observationally 
 (S/AhoCorasickSet.java:223-225).  The Thresholder constructor argument of the reference is accepted and ignored
 (results-neutral node-representation knob).  StringMap.match also takes a Readable (an object with read(n), or an
 iterable of chunks) with a value-only ReadableMatchListener, S/StringMap.java:6-8: match_readable over acgpu_stream_*.
+
+Every native call goes through one body per call shape: _records_call (records into a buffer that grows until they fit),
+_rewrite_call (a rewritten text, retried by the caller's rule), _fill_shard (the acgpu_shard of a device call).  StringSet and
+StringMap are _Matcher with the two listener loops and the replacement rule of their flavour.
 """
 import ctypes
+import itertools
 import os
 
 import numpy as np
@@ -67,12 +72,12 @@ def utf8_line_offsets(data):
     return np.concatenate([np.zeros(1, np.uint64), ends, np.array(tail, np.uint64)])
 
 
-def _utf8_entry(name, strict_stats, errors, lossy_stats=N.Utf8LossyStats):
-    """(the native entry, its stats type) for errors="strict" | "replace" -- the lossy entries scan every maximal ill-formed
-    subpart as one U+FFFD, as bytes.decode("utf-8", "replace") does; anything else is refused before a native call"""
-    if _check_errors(errors) == "strict":
-        return getattr(N.lib(), name), strict_stats
-    return getattr(N.lib(), name + "_lossy"), lossy_stats
+def _utf8_entry(name, errors):
+    """(the native entry, the stats type it fills) for errors="strict" | "replace" -- the lossy entries scan every maximal
+    ill-formed subpart as one U+FFFD, as bytes.decode("utf-8", "replace") does; anything else is refused before a native call"""
+    if _check_errors(errors) == "replace":
+        name += "_lossy"
+    return getattr(N.lib(), name), N.UTF8_STATS[name]
 
 
 def _check_errors(errors):
@@ -118,7 +123,101 @@ def _pack(keywords):
 
 
 def _vp(a):
+    """array -> void* (None -> NULL); the pointer object keeps a reference to the array (numpy: ndarray.ctypes.data_as)"""
     return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+
+
+def _readable(a):
+    """the text of a native call: never an empty array, whose pointer the library would refuse even for n = 0"""
+    return a if a.size else np.zeros(1, a.dtype)
+
+
+def _kind(with_ids):
+    return N.REC_MAP if with_ids else N.REC_SET
+
+
+def _stats_dict(st):
+    """a stats struct of integers (N.CountStats, N.ReplaceStats, N.SummaryStats, N.CursorStats) -> dict"""
+    return {f: int(getattr(st, f)) for f, _ in st._fields_}
+
+
+def _profile_dict(prof):
+    """N.Profile -> dict"""
+    return dict(scan_ms=prof.scan_ms, finalize_ms=prof.finalize_ms, total_ms=prof.total_ms,
+                scan_units=prof.scan_units, n_matches=prof.n_matches, scan_kernel=prof.scan_kernel.decode())
+
+
+def _fill_shard(sh, d_hay, n_units, own=None, text_begin=True, text_end=True, chain_entry=None, d_result=None):
+    """The acgpu_shard of a device call, filled in place.  own: (begin, end), None: the whole of d_hay; chain_entry None: the
+    chain enters where the owned range begins."""
+    sh.d_hay = d_hay
+    sh.n_units = n_units
+    sh.own_begin, sh.own_end = (0, n_units) if own is None else own
+    sh.text_begin = 1 if text_begin else 0
+    sh.text_end = 1 if text_end else 0
+    sh.chain_entry = sh.own_begin if chain_entry is None else chain_entry
+    sh.chain_exit = -1
+    sh.d_result = d_result
+    return sh
+
+
+def _raise_for(rc, entry, stats=()):
+    """The error mapping of every call with a return code: ACGPU_E_ENCODING with a stats struct that names the place ->
+    Utf8Error, anything else but OK -> AcgpuError whose `where` is the entry that was called."""
+    if rc == N.E_ENCODING:
+        for st in stats:
+            if hasattr(st, "first_bad"):
+                raise Utf8Error(st.first_bad, haystack=getattr(st, "bad_haystack", None))
+    N.check(rc, entry.__name__)
+
+
+def _new_records(cap, cols):
+    return np.empty((cap, cols), dtype=np.int32)
+
+
+def _records_call(entry, head, kind, cols, cap, tail=(), stats=None, alloc=_new_records):
+    """The records call: entry(*head, kind, out, cap, &n_out, *tail[, &stats]) into a (cap, cols) int32 buffer from alloc ->
+    the rows that were written.  ACGPU_E_OVERFLOW consumed nothing and reports the capacity that is needed in n_out: the same
+    call again with exactly that, as often as the entry asks.  stats: the UTF-8 stats struct of an entry that has one."""
+    extra = tail if stats is None else tail + (ctypes.byref(stats),)
+    while True:
+        out = alloc(cap, cols)
+        n_out = ctypes.c_uint64(0)
+        rc = entry(*head, kind, _vp(out), cap, ctypes.byref(n_out), *extra)
+        if rc != N.E_OVERFLOW:
+            break
+        cap = int(n_out.value)
+    _raise_for(rc, entry, (stats,))
+    return out[:n_out.value]
+
+
+def _retry_once(attempt, asked, cap):
+    """the rule of Automaton's rewrite calls: the first call reports the size, the second has it; a second overflow is an error"""
+    return attempt == 0
+
+
+def _retry_while_more(attempt, asked, cap):
+    """the rule of a stream's rewrite feeds: again as long as the entry asks for more room than it was given"""
+    return asked > cap
+
+
+def _rewrite_call(entry, head, dtype, n, cap, stats, retry, mid=()):
+    """The rewrite call: entry(*head, out, cap, *mid, &n_out, *&stats) into a buffer of cap elements of dtype -> the elements
+    that were written.  cap None: the text's size n and a quarter.  ACGPU_E_OVERFLOW committed nothing and reports the size that is
+    needed in n_out; retry(attempt, that size, cap) says whether the call is made again with it, otherwise it is an error."""
+    if cap is None:
+        cap = n + n // 4 + 64
+    tail = [ctypes.byref(s) for s in stats]
+    attempt = 0
+    while True:
+        out = np.empty(max(cap, 1), dtype=dtype)
+        n_out = ctypes.c_uint64(0)
+        rc = entry(*head, _vp(out), cap, *mid, ctypes.byref(n_out), *tail)
+        if rc != N.E_OVERFLOW or not retry(attempt, int(n_out.value), cap):
+            break
+        cap, attempt = int(n_out.value), attempt + 1
+    _raise_for(rc, entry, stats)
+    return out[:n_out.value]
 
 
 def configured_devices():
@@ -174,26 +273,15 @@ class Automaton:
         memory -> (n, 2|3) int32 array in reference call order."""
         hay = np.ascontiguousarray(hay_units, dtype=np.uint16)
         n = int(hay.size)
-        kind = N.REC_MAP if with_ids else N.REC_SET
-        cols = kind // 4
-        if cap is None:
-            cap = max(4096, n // 64)
-        buf_in = hay if n else np.zeros(1, np.uint16)
+        kind = _kind(with_ids)
+        head = (self._h, _vp(_readable(hay)), n)
         if devices is None:
             devices = configured_devices()
-        devs = (ctypes.c_int * len(devices))(*devices) if devices else None
-        while True:
-            out = np.empty((cap, cols), dtype=np.int32)
-            n_out = ctypes.c_uint64(0)
-            if devs is not None:
-                rc = N.lib().acgpu_match_u16_multi(self._h, _vp(buf_in), n, devs, len(devices), kind, _vp(out), cap, ctypes.byref(n_out))
-            else:
-                rc = N.lib().acgpu_match_u16(self._h, _vp(buf_in), n, kind, _vp(out), cap, ctypes.byref(n_out))
-            if rc == N.E_OVERFLOW:
-                cap = int(n_out.value)
-                continue
-            N.check(rc, "acgpu_match_u16_multi" if devs is not None else "acgpu_match_u16")
-            return out[:n_out.value]
+        if devices:
+            entry, head = N.lib().acgpu_match_u16_multi, head + ((ctypes.c_int * len(devices))(*devices), len(devices))
+        else:
+            entry = N.lib().acgpu_match_u16
+        return _records_call(entry, head, kind, kind // 4, max(4096, n // 64) if cap is None else cap)
 
     def match_utf8(self, data, with_ids, cap=None, stats=None, errors="strict"):
         """acgpu_match_utf8: a UTF-8 haystack (bytes, bytearray, memoryview or uint8 array) in host memory -> (n, 2|3) int32 array
@@ -201,44 +289,20 @@ class Automaton:
         UnicodeDecodeError.start).  stats: an N.Utf8Stats to fill in, if wanted.  errors="replace": acgpu_match_utf8_lossy --
         the records of data.decode("utf-8", "replace"), a replaced subpart's U+FFFD mapped to its bytes; nothing is raised, and
         stats is an N.Utf8LossyStats."""
-        entry, stats_type = _utf8_entry("acgpu_match_utf8", N.Utf8Stats, errors)
+        entry, stats_type = _utf8_entry("acgpu_match_utf8", errors)
         buf = _utf8_bytes(data)
         n = int(buf.size)
-        kind = N.REC_MAP if with_ids else N.REC_SET
-        cols = kind // 4
-        if cap is None:
-            cap = max(4096, n // 64)
-        buf_in = buf if n else np.zeros(1, np.uint8)
-        st = stats if stats is not None else stats_type()
-        while True:
-            out = np.empty((cap, cols), dtype=np.int32)
-            n_out = ctypes.c_uint64(0)
-            rc = entry(self._h, _vp(buf_in), n, kind, _vp(out), cap, ctypes.byref(n_out), ctypes.byref(st))
-            if rc == N.E_OVERFLOW:
-                cap = int(n_out.value)
-                continue
-            if rc == N.E_ENCODING:
-                raise Utf8Error(st.first_bad)
-            N.check(rc, entry.__name__)
-            return out[:n_out.value]
+        kind = _kind(with_ids)
+        return _records_call(entry, (self._h, _vp(_readable(buf)), n), kind, kind // 4, max(4096, n // 64) if cap is None else cap,
+                             stats=stats if stats is not None else stats_type())
 
     def match_batch(self, haystacks, with_ids, cap=None):
         """acgpu_match_batch_u16: many short haystacks (str or uint16 arrays) in one call -> (n, 3|4) int32 array of
         (haystack index, start, end[, keyword index]) records, haystack by haystack in reference call order."""
         units, off = _pack(haystacks)
-        kind = N.REC_MAP if with_ids else N.REC_SET
-        cols = kind // 4 + 1
-        if cap is None:
-            cap = max(4096, int(off[-1]) // 16)
-        while True:
-            out = np.empty((cap, cols), dtype=np.int32)
-            n_out = ctypes.c_uint64(0)
-            rc = N.lib().acgpu_match_batch_u16(self._h, _vp(units), _vp(off), len(off) - 1, kind, _vp(out), cap, ctypes.byref(n_out))
-            if rc == N.E_OVERFLOW:
-                cap = int(n_out.value)
-                continue
-            N.check(rc, "acgpu_match_batch_u16")
-            return out[:n_out.value]
+        kind = _kind(with_ids)
+        return _records_call(N.lib().acgpu_match_batch_u16, (self._h, _vp(units), _vp(off), len(off) - 1), kind, kind // 4 + 1,
+                             max(4096, int(off[-1]) // 16) if cap is None else cap)
 
     def match_batch_utf8(self, data, with_ids, cap=None, stats=None, offsets=None, errors="strict"):
         """acgpu_match_batch_utf8: many short UTF-8 haystacks in one call -> (n, 3|4) int32 array of (haystack index, start,
@@ -247,94 +311,56 @@ class Automaton:
         offsets) ONE buffer, used in place.  An ill-formed haystack raises Utf8Error (.haystack, and .start inside it).
         stats: an N.Utf8BatchStats to fill in, if wanted.  errors="replace": acgpu_match_batch_utf8_lossy -- every haystack as
         its own .decode("utf-8", "replace"); nothing is raised, and stats is an N.Utf8LossyStats."""
-        entry, stats_type = _utf8_entry("acgpu_match_batch_utf8", N.Utf8BatchStats, errors)
+        entry, stats_type = _utf8_entry("acgpu_match_batch_utf8", errors)
         buf, off = _pack_utf8(data, offsets)
-        kind = N.REC_MAP if with_ids else N.REC_SET
-        cols = kind // 4 + 1
-        if cap is None:
-            cap = max(4096, int(off[-1] - off[0]) // 16)
-        buf_in = buf if buf.size else np.zeros(1, np.uint8)
-        st = stats if stats is not None else stats_type()
-        while True:
-            out = np.empty((cap, cols), dtype=np.int32)
-            n_out = ctypes.c_uint64(0)
-            rc = entry(self._h, _vp(buf_in), _vp(off), len(off) - 1, kind, _vp(out), cap, ctypes.byref(n_out), ctypes.byref(st))
-            if rc == N.E_OVERFLOW:
-                cap = int(n_out.value)
-                continue
-            if rc == N.E_ENCODING:
-                raise Utf8Error(st.first_bad, haystack=st.bad_haystack)
-            N.check(rc, entry.__name__)
-            return out[:n_out.value]
+        kind = _kind(with_ids)
+        return _records_call(entry, (self._h, _vp(_readable(buf)), _vp(off), len(off) - 1), kind, kind // 4 + 1,
+                             max(4096, int(off[-1] - off[0]) // 16) if cap is None else cap,
+                             stats=stats if stats is not None else stats_type())
 
     def summary_batch_utf8(self, data, stats=None, offsets=None, errors="strict"):
         """acgpu_summary_batch_utf8: many short UTF-8 haystacks decided in one call -> (array of N.SUMMARY_DTYPE with one entry
         per haystack: n_matches and the first record in listener order in BYTES relative to the haystack, -1s where there is
         none; stats dict).  data and offsets as for match_batch_utf8; an ill-formed haystack raises Utf8Error.
         errors="replace": acgpu_summary_batch_utf8_lossy, as for match_batch_utf8."""
-        entry, stats_type = _utf8_entry("acgpu_summary_batch_utf8", N.Utf8BatchStats, errors)
+        entry, stats_type = _utf8_entry("acgpu_summary_batch_utf8", errors)
         buf, off = _pack_utf8(data, offsets)
         n = len(off) - 1
         out = np.zeros(n, dtype=N.SUMMARY_DTYPE)
-        buf_in = buf if buf.size else np.zeros(1, np.uint8)
         st = N.SummaryStats()
         ust = stats if stats is not None else stats_type()
-        rc = entry(self._h, _vp(buf_in), _vp(off), n, _vp(out) if n else None, ctypes.byref(st), ctypes.byref(ust))
-        if rc == N.E_ENCODING:
-            raise Utf8Error(ust.first_bad, haystack=ust.bad_haystack)
-        N.check(rc, entry.__name__)
-        return out, {f: int(getattr(st, f)) for f, _ in N.SummaryStats._fields_}
+        _raise_for(entry(self._h, _vp(_readable(buf)), _vp(off), n, _vp(out) if n else None, ctypes.byref(st), ctypes.byref(ust)),
+                   entry, (ust,))
+        return out, _stats_dict(st)
 
     def match_device(self, d_hay_ptr, n_units, with_ids, d_out_ptr, cap, own=None, text_begin=True, text_end=True,
                      chain_entry=None, stream=0, profile=False, d_result=None):
         """acgpu_match_device on raw device pointers.  Returns (n_out, rc, profile_dict|None, chain_exit)."""
-        sh = N.Shard()
-        sh.d_result = d_result
-        sh.d_hay = d_hay_ptr
-        sh.n_units = n_units
-        sh.own_begin, sh.own_end = (0, n_units) if own is None else own
-        sh.text_begin = 1 if text_begin else 0
-        sh.text_end = 1 if text_end else 0
-        sh.chain_entry = sh.own_begin if chain_entry is None else chain_entry
-        sh.chain_exit = -1
+        sh = _fill_shard(N.Shard(), d_hay_ptr, n_units, own, text_begin, text_end, chain_entry, d_result)
         prof = N.Profile() if profile else None
         n_out = ctypes.c_uint64(0)
-        rc = N.lib().acgpu_match_device(self._h, ctypes.byref(sh), N.REC_MAP if with_ids else N.REC_SET, d_out_ptr, cap,
-                                        ctypes.byref(n_out), ctypes.c_void_p(stream),
-                                        ctypes.byref(prof) if profile else None)
-        pd = None
-        if profile:
-            pd = dict(scan_ms=prof.scan_ms, finalize_ms=prof.finalize_ms, total_ms=prof.total_ms,
-                      scan_units=prof.scan_units, n_matches=prof.n_matches, scan_kernel=prof.scan_kernel.decode())
-        return int(n_out.value), rc, pd, int(sh.chain_exit)
+        rc = N.lib().acgpu_match_device(self._h, ctypes.byref(sh), N.REC_MAP if with_ids else N.REC_SET, d_out_ptr, cap, ctypes.byref(n_out),
+                                        ctypes.c_void_p(stream), ctypes.byref(prof) if profile else None)
+        return int(n_out.value), rc, _profile_dict(prof) if profile else None, int(sh.chain_exit)
 
     def count_host(self, hay_units):
         """acgpu_count_u16: haystack in host memory -> (uint64 array with one count per keyword given to the constructor,
         stats dict).  No record leaves the device."""
         hay = np.ascontiguousarray(hay_units, dtype=np.uint16)
-        n = int(hay.size)
-        buf_in = hay if n else np.zeros(1, np.uint16)
         counts = np.zeros(max(len(self.keywords), 1), dtype=np.uint64)
         st = N.CountStats()
-        N.check(N.lib().acgpu_count_u16(self._h, _vp(buf_in), n, _vp(counts), len(self.keywords), ctypes.byref(st)), "acgpu_count_u16")
-        return counts[:len(self.keywords)], {f: int(getattr(st, f)) for f, _ in N.CountStats._fields_}
+        N.check(N.lib().acgpu_count_u16(self._h, _vp(_readable(hay)), int(hay.size), _vp(counts), len(self.keywords), ctypes.byref(st)),
+                "acgpu_count_u16")
+        return counts[:len(self.keywords)], _stats_dict(st)
 
     def count_device(self, d_hay_ptr, n_units, d_counts_ptr, own=None, text_begin=True, text_end=True, chain_entry=None, stream=0):
         """acgpu_count_device on raw device pointers: ADDS this shard's counts to the uint64 device array d_counts_ptr (one
         word per keyword given to the constructor, zeroed by the caller).  Returns (rc, stats dict, chain_exit)."""
-        sh = N.Shard()
-        sh.d_result = None
-        sh.d_hay = d_hay_ptr
-        sh.n_units = n_units
-        sh.own_begin, sh.own_end = (0, n_units) if own is None else own
-        sh.text_begin = 1 if text_begin else 0
-        sh.text_end = 1 if text_end else 0
-        sh.chain_entry = sh.own_begin if chain_entry is None else chain_entry
-        sh.chain_exit = -1
+        sh = _fill_shard(N.Shard(), d_hay_ptr, n_units, own, text_begin, text_end, chain_entry)
         st = N.CountStats()
         rc = N.lib().acgpu_count_device(self._h, ctypes.byref(sh), d_counts_ptr, len(self.keywords), ctypes.c_void_p(stream),
                                         ctypes.byref(st))
-        return rc, {f: int(getattr(st, f)) for f, _ in N.CountStats._fields_}, int(sh.chain_exit)
+        return rc, _stats_dict(st), int(sh.chain_exit)
 
     def _replacements(self, replacements):
         """one str or uint16 array per keyword, or a single str that stands for every keyword -> (units, offsets, n_repl)"""
@@ -351,21 +377,11 @@ class Automaton:
         larger than the first buffer (the text's size and a quarter) is fetched by one more call with the size the first reports."""
         hay = np.ascontiguousarray(hay_units, dtype=np.uint16)
         n = int(hay.size)
-        buf_in = hay if n else np.zeros(1, np.uint16)
         units, off, n_repl = self._replacements(replacements)
-        if cap is None:
-            cap = n + n // 4 + 64
         st = N.ReplaceStats()
-        for attempt in (0, 1):
-            out = np.empty(max(cap, 1), dtype=np.uint16)
-            n_out = ctypes.c_uint64(0)
-            rc = N.lib().acgpu_replace_u16(self._h, _vp(buf_in), n, _vp(units), _vp(off), n_repl, _vp(out), cap, ctypes.byref(n_out),
-                                           ctypes.byref(st))
-            if rc == N.E_OVERFLOW and attempt == 0:
-                cap = int(n_out.value)
-                continue
-            N.check(rc, "acgpu_replace_u16")
-            return out[:n_out.value], {f: int(getattr(st, f)) for f, _ in N.ReplaceStats._fields_}
+        out = _rewrite_call(N.lib().acgpu_replace_u16, (self._h, _vp(_readable(hay)), n, _vp(units), _vp(off), n_repl), np.uint16, n, cap,
+                            (st,), _retry_once)
+        return out, _stats_dict(st)
 
     def _replacements_utf8(self, replacements):
         """as _replacements, in bytes: a str is encoded as UTF-8; bytes, bytearray and uint8 arrays are taken as they are (and
@@ -387,27 +403,14 @@ class Automaton:
         them.  Ill-formed input raises Utf8Error.  The one retry of replace_host; stats: an N.Utf8Stats to fill in, if wanted.
         errors="replace": acgpu_replace_utf8_lossy -- the matches are those of match_utf8(errors="replace"), outside them the
         result is still a copy of `data`, ill-formed bytes included; nothing is raised, and stats is an N.Utf8LossyStats."""
-        entry, stats_type = _utf8_entry("acgpu_replace_utf8", N.Utf8Stats, errors)
+        entry, stats_type = _utf8_entry("acgpu_replace_utf8", errors)
         buf = _utf8_bytes(data)
         n = int(buf.size)
-        buf_in = buf if n else np.zeros(1, np.uint8)
         r_bytes, off, n_repl = self._replacements_utf8(replacements)
-        if cap is None:
-            cap = n + n // 4 + 64
         st = N.ReplaceStats()
-        ust = stats if stats is not None else stats_type()
-        for attempt in (0, 1):
-            out = np.empty(max(cap, 1), dtype=np.uint8)
-            n_out = ctypes.c_uint64(0)
-            rc = entry(self._h, _vp(buf_in), n, _vp(r_bytes), _vp(off), n_repl, _vp(out), cap, ctypes.byref(n_out),
-                       ctypes.byref(st), ctypes.byref(ust))
-            if rc == N.E_OVERFLOW and attempt == 0:
-                cap = int(n_out.value)
-                continue
-            if rc == N.E_ENCODING and errors == "strict":
-                raise Utf8Error(ust.first_bad)
-            N.check(rc, "acgpu_replace_utf8")
-            return out[:n_out.value], {f: int(getattr(st, f)) for f, _ in N.ReplaceStats._fields_}
+        out = _rewrite_call(entry, (self._h, _vp(_readable(buf)), n, _vp(r_bytes), _vp(off), n_repl), np.uint8, n, cap,
+                            (st, stats if stats is not None else stats_type()), _retry_once)
+        return out, _stats_dict(st)
 
     def replace_batch_utf8(self, data, replacements, cap=None, stats=None, offsets=None, errors="strict"):
         """acgpu_replace_batch_utf8: many short UTF-8 haystacks rewritten in one call -> (uint8 array, out_offsets, stats dict):
@@ -416,28 +419,14 @@ class Automaton:
         ill-formed haystack raises Utf8Error (.haystack, and .start inside it); stats: an N.Utf8BatchStats to fill in, if wanted.
         errors="replace": acgpu_replace_batch_utf8_lossy -- every haystack as replace_utf8(errors="replace") rewrites it alone;
         nothing is raised, and stats is an N.Utf8LossyStats."""
-        entry, stats_type = _utf8_entry("acgpu_replace_batch_utf8", N.Utf8BatchStats, errors)
+        entry, stats_type = _utf8_entry("acgpu_replace_batch_utf8", errors)
         buf, off = _pack_utf8(data, offsets)
         r_bytes, r_off, n_repl = self._replacements_utf8(replacements)
-        n = int(off[-1] - off[0])
-        if cap is None:
-            cap = n + n // 4 + 64
-        buf_in = buf if buf.size else np.zeros(1, np.uint8)
         st = N.ReplaceStats()
-        ust = stats if stats is not None else stats_type()
         out_off = np.zeros(len(off), dtype=np.uint64)
-        for attempt in (0, 1):
-            out = np.empty(max(cap, 1), dtype=np.uint8)
-            n_out = ctypes.c_uint64(0)
-            rc = entry(self._h, _vp(buf_in), _vp(off), len(off) - 1, _vp(r_bytes), _vp(r_off), n_repl, _vp(out), cap,
-                       _vp(out_off), ctypes.byref(n_out), ctypes.byref(st), ctypes.byref(ust))
-            if rc == N.E_OVERFLOW and attempt == 0:
-                cap = int(n_out.value)
-                continue
-            if rc == N.E_ENCODING and errors == "strict":
-                raise Utf8Error(ust.first_bad, haystack=ust.bad_haystack)
-            N.check(rc, "acgpu_replace_batch_utf8")
-            return out[:n_out.value], out_off, {f: int(getattr(st, f)) for f, _ in N.ReplaceStats._fields_}
+        out = _rewrite_call(entry, (self._h, _vp(_readable(buf)), _vp(off), len(off) - 1, _vp(r_bytes), _vp(r_off), n_repl), np.uint8,
+                            int(off[-1] - off[0]), cap, (st, stats if stats is not None else stats_type()), _retry_once, mid=(_vp(out_off),))
+        return out, out_off, _stats_dict(st)
 
     def replace_batch(self, haystacks, replacements, cap=None):
         """acgpu_replace_batch_u16: many short haystacks (str or uint16 arrays) rewritten in one call -> (units, out_offsets,
@@ -445,20 +434,11 @@ class Automaton:
         and the same one retry with the size the first call reports."""
         units, off = _pack(haystacks)
         r_units, r_off, n_repl = self._replacements(replacements)
-        if cap is None:
-            cap = int(off[-1]) + int(off[-1]) // 4 + 64
         st = N.ReplaceStats()
         out_off = np.zeros(len(off), dtype=np.uint64)
-        for attempt in (0, 1):
-            out = np.empty(max(cap, 1), dtype=np.uint16)
-            n_out = ctypes.c_uint64(0)
-            rc = N.lib().acgpu_replace_batch_u16(self._h, _vp(units), _vp(off), len(off) - 1, _vp(r_units), _vp(r_off), n_repl, _vp(out), cap,
-                                                 _vp(out_off), ctypes.byref(n_out), ctypes.byref(st))
-            if rc == N.E_OVERFLOW and attempt == 0:
-                cap = int(n_out.value)
-                continue
-            N.check(rc, "acgpu_replace_batch_u16")
-            return out[:n_out.value], out_off, {f: int(getattr(st, f)) for f, _ in N.ReplaceStats._fields_}
+        out = _rewrite_call(N.lib().acgpu_replace_batch_u16, (self._h, _vp(units), _vp(off), len(off) - 1, _vp(r_units), _vp(r_off), n_repl),
+                            np.uint16, int(off[-1]), cap, (st,), _retry_once, mid=(_vp(out_off),))
+        return out, out_off, _stats_dict(st)
 
     def summary_batch(self, haystacks):
         """acgpu_summary_batch_u16: many short haystacks (str or uint16 arrays) decided in one call -> (array of N.SUMMARY_DTYPE
@@ -470,40 +450,25 @@ class Automaton:
         st = N.SummaryStats()
         N.check(N.lib().acgpu_summary_batch_u16(self._h, _vp(units), _vp(off), n, _vp(out) if n else None, ctypes.byref(st)),
                 "acgpu_summary_batch_u16")
-        return out, {f: int(getattr(st, f)) for f, _ in N.SummaryStats._fields_}
+        return out, _stats_dict(st)
 
     def replace_device(self, d_hay_ptr, n_units, replacements, d_out_ptr, cap, stream=0):
         """acgpu_replace_device on raw device pointers: the whole text d_hay_ptr[0 .. n_units) rewritten into d_out_ptr (cap
         units, 16-byte aligned).  Returns (n_out, rc, stats dict); rc == E_OVERFLOW: n_out is the capacity to call again with."""
-        sh = N.Shard()
-        sh.d_result = None
-        sh.d_hay = d_hay_ptr
-        sh.n_units = n_units
-        sh.own_begin, sh.own_end = 0, n_units
-        sh.text_begin = sh.text_end = 1
-        sh.chain_entry = 0
-        sh.chain_exit = -1
+        sh = _fill_shard(N.Shard(), d_hay_ptr, n_units)
         units, off, n_repl = self._replacements(replacements)
         st = N.ReplaceStats()
         n_out = ctypes.c_uint64(0)
         rc = N.lib().acgpu_replace_device(self._h, ctypes.byref(sh), _vp(units), _vp(off), n_repl, d_out_ptr, cap, ctypes.byref(n_out),
                                           ctypes.c_void_p(stream), ctypes.byref(st))
-        return int(n_out.value), rc, {f: int(getattr(st, f)) for f, _ in N.ReplaceStats._fields_}
+        return int(n_out.value), rc, _stats_dict(st)
 
     def match_device_begin(self, d_hay_ptr, n_units, with_ids, d_out_ptr, cap, own=None, text_begin=True, text_end=True,
                            stream=0, profile=False, d_result=None, chain_entry=None):
         """acgpu_match_device_begin: enqueue without waiting (AhoCorasick, WholeWord with fold-consistent tables, the LongestMatch
         walk pipeline; the other families run inside the call).  Returns (ticket, rc); the ticket keeps the acgpu_shard alive
         (the library writes chain_exit into it when the ticket is collected)."""
-        sh = N.Shard()
-        sh.d_result = d_result
-        sh.d_hay = d_hay_ptr
-        sh.n_units = n_units
-        sh.own_begin, sh.own_end = (0, n_units) if own is None else own
-        sh.text_begin = 1 if text_begin else 0
-        sh.text_end = 1 if text_end else 0
-        sh.chain_entry = sh.own_begin if chain_entry is None else chain_entry
-        sh.chain_exit = -1
+        sh = _fill_shard(N.Shard(), d_hay_ptr, n_units, own, text_begin, text_end, chain_entry, d_result)
         tk = ctypes.c_void_p()
         rc = N.lib().acgpu_match_device_begin(self._h, ctypes.byref(sh), N.REC_MAP if with_ids else N.REC_SET, d_out_ptr, cap,
                                               ctypes.c_void_p(stream), 1 if profile else 0, ctypes.byref(tk))
@@ -515,12 +480,7 @@ class Automaton:
         prof = N.Profile() if profile else None
         n_out = ctypes.c_uint64(0)
         rc = N.lib().acgpu_match_device_end(self._h, ticket.handle, ctypes.byref(n_out), ctypes.byref(prof) if profile else None)
-        pd = None
-        if profile:
-            pd = dict(scan_ms=prof.scan_ms, finalize_ms=prof.finalize_ms, total_ms=prof.total_ms,
-                      scan_units=prof.scan_units, n_matches=prof.n_matches, scan_kernel=prof.scan_kernel.decode())
-        return int(n_out.value), rc, pd
-
+        return int(n_out.value), rc, _profile_dict(prof) if profile else None
 
     def match_device_abandon(self, ticket):
         """acgpu_match_device_abandon: give the ticket up (waits for its kernels, never redoes the call)."""
@@ -562,24 +522,13 @@ class Comm:
         k = len(self.devices)
         arr = (N.Shard * k)()
         for i, sd in enumerate(shards):
-            sh = arr[i]
-            sh.d_hay = sd["d_hay"]
-            sh.n_units = sd["n_units"]
-            sh.own_begin, sh.own_end = sd.get("own", (0, sd["n_units"]))
-            sh.text_begin = 1 if sd.get("text_begin", i == 0) else 0
-            sh.text_end = 1 if sd.get("text_end", i == k - 1) else 0
-            sh.chain_entry = sd.get("chain_entry", sh.own_begin)
-            sh.chain_exit = -1
-            sh.d_result = None
+            _fill_shard(arr[i], sd["d_hay"], sd["n_units"], sd.get("own"), sd.get("text_begin", i == 0), sd.get("text_end", i == k - 1),
+                        sd.get("chain_entry"))
         ptrs = (ctypes.c_void_p * k)(*gather_ptrs)
         counts = (ctypes.c_uint64 * k)()
         profs = (N.Profile * k)() if profile else None
-        rc = N.lib().acgpu_match_device_allgather(automaton.handle, self._h, arr, N.REC_MAP if with_ids else N.REC_SET, ptrs, gcap,
-                                                  counts, profs)
-        pd = None
-        if profile:
-            pd = [dict(scan_ms=p.scan_ms, finalize_ms=p.finalize_ms, total_ms=p.total_ms, scan_units=p.scan_units,
-                       n_matches=p.n_matches, scan_kernel=p.scan_kernel.decode()) for p in profs]
+        rc = N.lib().acgpu_match_device_allgather(automaton.handle, self._h, arr, _kind(with_ids), ptrs, gcap, counts, profs)
+        pd = [_profile_dict(p) for p in profs] if profile else None
         return rc, [int(c) for c in counts], [int(arr[i].chain_exit) for i in range(k)], pd
 
     def close(self):
@@ -610,7 +559,7 @@ class Stream:
         """pipelined: acgpu_stream_set_pipelined -- a feed returns the records of the PREVIOUS feed's chunk (the final feed both),
         host copy, transfer and scan of neighbouring chunks overlap."""
         self._auto = automaton  # keeps the handle alive
-        self._kind = N.REC_MAP if with_ids else N.REC_SET
+        self._kind = _kind(with_ids)
         self._errors = None  # the policy of a stream of bytes: its first byte feed's, every later one's
         h = ctypes.c_void_p()
         N.check(N.lib().acgpu_stream_open(automaton.handle, ctypes.byref(h)), "acgpu_stream_open")
@@ -624,44 +573,36 @@ class Stream:
         N.check(N.lib().acgpu_stream_reserve(self._h, int(n_units), ctypes.byref(p)), "acgpu_stream_reserve")
         return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint16)), shape=(int(n_units),))
 
-    def _utf8_policy(self, name, strict_stats, errors):
-        """_utf8_entry for a feed of bytes -> (the entry's name, its stats type): the first byte feed fixes the stream's policy,
-        and a feed with the other one is refused here as the library would refuse it (ACGPU_E_INVALID), without a native call."""
-        entry, stats_type = _utf8_entry(name, strict_stats, errors, N.Utf8LossyStreamStats)
+    def _utf8_policy(self, name, errors):
+        """_utf8_entry for a feed of bytes: the first byte feed fixes the stream's policy, and a feed with the other one is
+        refused here as the library would refuse it (ACGPU_E_INVALID), without a native call."""
+        entry, stats_type = _utf8_entry(name, errors)
         if self._errors is None:
             self._errors = errors
         elif self._errors != errors:
             raise ValueError("errors=%r on a stream that is fed with errors=%r" % (errors, self._errors))
-        return entry.__name__, stats_type
+        return entry, stats_type
 
-    def _feed(self, entry, src, n, final, cap, stats=None):
-        """The body of feed and feed_utf8: one record buffer per stream (a fresh one per feed costs more than the feed), the same
-        feed again where the capacity was too small, the records as int64 with GLOBAL positions.  stats: the entry's last argument,
-        where it has one -- then ACGPU_E_ENCODING raises Utf8Error."""
-        cols = self._kind // 4
-        if cap is None:
-            cap = max(4096, n // 64)
-        tail = () if stats is None else (ctypes.byref(stats),)
-        while True:
-            out = getattr(self, "_out", None)
-            if out is None or out.shape != (cap, cols):
-                out = self._out = np.empty((cap, cols), dtype=np.int32)
-            n_out, base = ctypes.c_uint64(0), ctypes.c_int64(0)
-            rc = getattr(N.lib(), entry)(self._h, _vp(src), n, 1 if final else 0, self._kind, _vp(out), cap,
-                                         ctypes.byref(n_out), ctypes.byref(base), *tail)
-            if rc == N.E_OVERFLOW:  # nothing was consumed: same feed, larger buffer
-                cap = int(n_out.value)
-                continue
-            if rc == N.E_ENCODING and hasattr(stats, "first_bad"):
-                raise Utf8Error(stats.first_bad)
-            N.check(rc, entry)
-            r = out[:n_out.value].astype(np.int64)
-            r[:, :2] += base.value
-            return r
+    def _record_buffer(self, cap, cols):
+        """one record buffer per stream: a fresh one per feed costs more than the feed"""
+        out = getattr(self, "_out", None)
+        if out is None or out.shape != (cap, cols):
+            out = self._out = _new_records(cap, cols)
+        return out
+
+    def _feed(self, entry, src, final, cap, stats=None):
+        """The body of feed and feed_utf8: the records call into the stream's own buffer (an overflow consumed nothing: the same
+        feed again), the records as int64 with GLOBAL positions.  stats: the entry's last argument, where it has one."""
+        n = int(src.size)
+        base = ctypes.c_int64(0)
+        r = _records_call(entry, (self._h, _vp(_readable(src)), n, 1 if final else 0), self._kind, self._kind // 4,
+                          max(4096, n // 64) if cap is None else cap, (ctypes.byref(base),), stats, self._record_buffer).astype(np.int64)
+        r[:, :2] += base.value
+        return r
 
     def feed(self, units, final=False, cap=None):
-        u = np.ascontiguousarray(units, dtype=np.uint16)  # (a view of the reserved staging memory stays where it is)
-        return self._feed("acgpu_stream_feed", u if u.size else np.zeros(1, np.uint16), int(u.size), final, cap)
+        # (a view of the reserved staging memory stays where it is)
+        return self._feed(N.lib().acgpu_stream_feed, np.ascontiguousarray(units, dtype=np.uint16), final, cap)
 
     def feed_utf8(self, data, final=False, cap=None, stats=None, errors="strict"):
         """acgpu_stream_feed_utf8: the next bytes of a UTF-8 text (bytes-like or a uint8 array; a chunk may end inside a
@@ -670,39 +611,23 @@ class Stream:
         A stream is fed either units or bytes.  stats: an N.Utf8StreamStats to fill in, if wanted.
         errors="replace": acgpu_stream_feed_utf8_lossy -- the records of match_utf8(errors="replace") on everything fed, whatever
         the chunking; nothing is raised, and stats is an N.Utf8LossyStreamStats.  The first feed fixes the stream's policy."""
-        entry, stats_type = self._utf8_policy("acgpu_stream_feed_utf8", N.Utf8StreamStats, errors)
-        buf = _utf8_bytes(data)
-        return self._feed(entry, buf if buf.size else np.zeros(1, np.uint8), int(buf.size), final, cap,
-                          stats if stats is not None else stats_type())
+        entry, stats_type = self._utf8_policy("acgpu_stream_feed_utf8", errors)
+        return self._feed(entry, _utf8_bytes(data), final, cap, stats if stats is not None else stats_type())
 
     def _replace_feed(self, entry, src, table, final, cap, stats):
-        """The body of replace_feed and replace_feed_utf8: the same feed again with the room it asks for, the result as an array of
-        src's type.  table: (replacements, offsets, n).  stats: the entry's last arguments; a Utf8StreamStats comes first."""
+        """The body of replace_feed and replace_feed_utf8: the rewrite call, made again while it asks for more room (nothing was
+        committed), the result as an array of src's type.  table: (replacements, offsets, n).  stats: the entry's last arguments."""
         n = int(src.size)
         r, off, n_repl = table
-        if cap is None:
-            cap = n + n // 4 + 64
-        if not n:
-            src = np.zeros(1, src.dtype)
-        while True:
-            out = np.empty(max(cap, 1), dtype=src.dtype)
-            n_out = ctypes.c_uint64(0)
-            rc = getattr(N.lib(), entry)(self._h, _vp(src), n, 1 if final else 0, _vp(r), _vp(off), n_repl, _vp(out), cap,
-                                         ctypes.byref(n_out), *[ctypes.byref(s) for s in stats])
-            if rc == N.E_OVERFLOW and int(n_out.value) > cap:  # nothing was committed: same feed, the room it asks for
-                cap = int(n_out.value)
-                continue
-            if rc == N.E_ENCODING and hasattr(stats[0], "first_bad"):
-                raise Utf8Error(stats[0].first_bad)
-            N.check(rc, entry)
-            return out[:n_out.value]
+        return _rewrite_call(entry, (self._h, _vp(_readable(src)), n, 1 if final else 0, _vp(r), _vp(off), n_repl), src.dtype, n, cap, stats,
+                             _retry_while_more)
 
     def replace_feed(self, units, replacements, final=False, cap=None, stats=None):
         """acgpu_stream_replace_u16: the next units of a text that is REWRITTEN as it arrives -> the units of the result that have
         become decidable, a uint16 array (the concatenation over all feeds: the whole text with every match replaced).
         `replacements` as for Automaton.replace_host, the same at every feed.  A stream is fed through one entry only.
         stats: an N.ReplaceStats to fill in, if wanted (this feed alone)."""
-        return self._replace_feed("acgpu_stream_replace_u16", utf16(units), self._auto._replacements(replacements), final, cap,
+        return self._replace_feed(N.lib().acgpu_stream_replace_u16, utf16(units), self._auto._replacements(replacements), final, cap,
                                   [stats if stats is not None else N.ReplaceStats()])
 
     def replace_feed_utf8(self, data, replacements, final=False, stats=None, cap=None, replace_stats=None, errors="strict"):
@@ -712,7 +637,7 @@ class Stream:
         withheld is not delivered.  stats: an N.Utf8StreamStats, replace_stats: an N.ReplaceStats to fill in, if wanted.
         errors="replace": acgpu_stream_replace_utf8_lossy -- replace_utf8(errors="replace") of everything fed, whatever the
         chunking; nothing is raised, and stats is an N.Utf8LossyStreamStats.  The first feed fixes the stream's policy."""
-        entry, stats_type = self._utf8_policy("acgpu_stream_replace_utf8", N.Utf8StreamStats, errors)
+        entry, stats_type = self._utf8_policy("acgpu_stream_replace_utf8", errors)
         return self._replace_feed(entry, _utf8_bytes(data), self._auto._replacements_utf8(replacements), final, cap,
                                   [stats if stats is not None else stats_type(),
                                    replace_stats if replace_stats is not None else N.ReplaceStats()]).tobytes()
@@ -783,8 +708,8 @@ class Cursor:
     def __init__(self, automaton, hay_units, with_ids=True):
         self._auto = automaton  # keeps the handle alive
         hay = np.ascontiguousarray(hay_units, dtype=np.uint16)
-        self._src = hay if hay.size else np.zeros(1, np.uint16)  # the library reads it until close
-        self._kind = N.REC_MAP if with_ids else N.REC_SET
+        self._src = _readable(hay)  # the library reads it until close
+        self._kind = _kind(with_ids)
         self._out = None
         h = ctypes.c_void_p()
         N.check(N.lib().acgpu_cursor_open(automaton.handle, _vp(self._src), int(hay.size), self._kind, ctypes.byref(h)),
@@ -795,7 +720,7 @@ class Cursor:
         cap = int(cap)
         cols = self._kind // 4
         if self._out is None or self._out.shape[0] < cap:
-            self._out = np.empty((cap, cols), dtype=np.int32)
+            self._out = _new_records(cap, cols)
         n_out = ctypes.c_uint64(0)
         N.check(N.lib().acgpu_cursor_next(self._h, _vp(self._out), cap, ctypes.byref(n_out)), "acgpu_cursor_next")
         return self._out[:n_out.value].copy()
@@ -803,7 +728,7 @@ class Cursor:
     def stats(self):
         st = N.CursorStats()
         N.check(N.lib().acgpu_cursor_get_stats(self._h, ctypes.byref(st)), "acgpu_cursor_get_stats")
-        return {f: getattr(st, f) for f, _ in N.CursorStats._fields_}
+        return _stats_dict(st)
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None
@@ -885,6 +810,12 @@ def _checked(haystacks):
     return haystacks
 
 
+def _not_none(haystack):
+    if haystack is None:
+        raise TypeError("haystack is None")  # the reference throws NullPointerException at haystack.length()
+    return haystack
+
+
 def _split_batch(units, out_off):
     """the result of Automaton.replace_batch -> one str per haystack"""
     o = out_off.tolist()
@@ -897,9 +828,135 @@ def _split_batch_utf8(out, out_off):
     return [out[o[i]:o[i + 1]].tobytes() for i in range(len(o) - 1)]
 
 
-class _BatchDecisions:
-    """Not in the reference: what a listener that decides about each text of a list would hold, from ONE device call that returns
-    24 bytes per haystack and no record (Automaton.summary_batch).  An empty list gives empty results without a device."""
+_NO_HAYSTACK = object()  # _emit without a haystack argument for the listener: a text that is read as it goes has no one object
+
+
+class _Matcher:
+    """What StringSet and StringMap share: every public method that both have, written once.  A flavour contributes
+      _WITH_IDS              whether its records carry the keyword index (and its listener gets a value),
+      _replacement(r)        a replacement argument as Automaton takes it,
+      _emit(fn, rows[, h])   rows to the listener until it returns False -> whether every row was delivered,
+      _emit_batch(fn, hs, rows)   the same per haystack: a False ends THAT haystack's rows,
+    and its public replace* methods, whose replacement parameter is named and defaulted differently (S/StringMap has values to
+    fall back on); their bodies are the _replace* methods here.
+
+    The *_batch decisions are not in the reference: what a listener that decides about each text of a list would hold, from ONE
+    device call that returns 24 bytes per haystack and no record (Automaton.summary_batch).  An empty list gives empty results
+    without a device."""
+    _MODE = None
+
+    def match(self, haystack, listener):
+        """match(String, listener): the listener is called for every match in reference order -- (haystack, start, end) for a
+        set, (haystack, start, end, value) for a map -- until it returns False."""
+        fn = _listener_fn(listener)
+        pages = _listener_records(self._auto, utf16(_not_none(haystack)), self._WITH_IDS)
+        try:
+            for page in pages:
+                if not self._emit(fn, page, haystack):
+                    return
+        finally:
+            pages.close()  # (a long haystack's cursor: closed at the first False, the rest is never scanned)
+
+    def count(self, haystack):
+        """Not in the reference: how often every keyword of the constructor's list is reported for `haystack` -- what a listener
+        doing counts[index_of(keyword)] += 1; return True would hold (a duplicate keyword: its last occurrence in the list
+        counts, for ShortestMatch its first) -- as a uint64 array, computed on the device without a record being handed out.
+        For a map: how often the listener of match(String, ...) would be called with each value, aligned with the constructor's
+        keyword / value lists (a duplicate keyword: the value that won)."""
+        return self._auto.count_host(utf16(_not_none(haystack)))[0]
+
+    def _replacement_utf8(self, r):
+        """a replacement argument of the byte forms: bytes are taken as they are, anything else under the rules of _replacement"""
+        return r if isinstance(r, (bytes, bytearray)) else self._replacement(r)
+
+    def _replace(self, haystack, r):
+        return _to_str(self._auto.replace_host(utf16(_not_none(haystack)), self._replacement(r))[0])
+
+    def _replace_batch(self, haystacks, r):
+        return _split_batch(*self._auto.replace_batch(_checked(haystacks), self._replacement(r))[:2])
+
+    def _replace_utf8(self, data, r, errors):
+        _check_errors(errors)
+        return self._auto.replace_utf8(_not_none(data), self._replacement_utf8(r), errors=errors)[0].tobytes()
+
+    def _replace_batch_utf8(self, datas, r, offsets, errors):
+        _check_errors(errors)
+        r = self._replacement_utf8(r)
+        return _split_batch_utf8(*self._auto.replace_batch_utf8(datas if offsets is not None else _checked(datas), r, offsets=offsets,
+                                                                errors=errors)[:2])
+
+    def _replace_readable(self, readable, r, chunk_chars):
+        return _replace_stream(self._auto, _chunks(readable, chunk_chars), _str_feed(), self._replacement(r), "")
+
+    def _replace_utf8_readable(self, readable, r, chunk_bytes, errors):
+        _check_errors(errors)
+        feed = lambda st, chunk, r, final=False: st.replace_feed_utf8(chunk, r, final=final, errors=errors)
+        return _replace_stream(self._auto, _byte_chunks(readable, chunk_bytes), feed, self._replacement_utf8(r), b"")
+
+    def find_all(self, haystack):
+        """Convenience (not in the reference): the (n,2) int32 array of (start, end) records; for a map the (n,3) array of
+        (start, end, keyword_index) records."""
+        return self._auto.match_host(utf16(haystack), with_ids=self._WITH_IDS)
+
+    def find_all_utf8(self, data, errors="strict"):
+        """Not in the reference: the (n,2) int32 array of (start, end) records of a UTF-8 haystack (bytes, bytearray, memoryview
+        or uint8 array) -- for a map the (n,3) array of (start, end, keyword_index) records -- in BYTE offsets into `data`:
+        decoded, scanned and mapped back on the device.  Utf8Error if ill-formed."""
+        return self._auto.match_utf8(data, with_ids=self._WITH_IDS, errors=errors)
+
+    def match_utf8(self, data, listener, errors="strict"):
+        """Not in the reference: match(data.decode("utf-8"), listener) with the listener receiving `data` itself and byte
+        offsets into it (a map's listener the value as well); a listener call that returns False stops the loop."""
+        fn = _listener_fn(listener)
+        self._emit(fn, self._auto.match_utf8(_not_none(data), with_ids=self._WITH_IDS, errors=errors).tolist(), data)
+
+    def match_utf8_readable(self, readable, listener, chunk_bytes=1 << 22, errors="strict"):
+        """Not in the reference: match_utf8 for a text that is read as it goes -- a binary file object (read(n)) or an iterable
+        of bytes-like chunks, cut anywhere, inside a sequence too.  The listener gets (start, end) -- for a map (start, end,
+        value) -- in GLOBAL byte offsets (there is no one haystack object to hand over); a call that returns False stops the
+        feeding AND the reading.  Utf8Error (.start: the global offset) if the text is ill-formed -- unless errors="replace":
+        the records of match_utf8(errors="replace") on the whole text, whatever the chunking."""
+        _check_errors(errors)
+        fn = _listener_fn(listener)
+        pages = _utf8_stream_pages(self._auto, readable, chunk_bytes, self._WITH_IDS, errors)
+        try:
+            for page in pages:
+                if not self._emit(fn, page.tolist()):
+                    return
+        finally:
+            pages.close()
+
+    def find_all_utf8_readable(self, readable, chunk_bytes=1 << 22, errors="strict"):
+        """Not in the reference: the (n,2) int64 array of (start, end) records -- for a map the (n,3) array of (start, end,
+        keyword_index) records -- of a UTF-8 text read chunk by chunk, in GLOBAL byte offsets: find_all_utf8 of the whole
+        text, which may be longer than 2^31 bytes (errors: as find_all_utf8)."""
+        _check_errors(errors)
+        pages = list(_utf8_stream_pages(self._auto, readable, chunk_bytes, self._WITH_IDS, errors))
+        return np.concatenate(pages) if pages else np.zeros((0, 3 if self._WITH_IDS else 2), np.int64)
+
+    def match_batch(self, haystacks, listener):
+        """Not in the reference: match(haystack, listener) for every haystack of a list in ONE device call (short inputs: a
+        call has tens of microseconds of fixed cost).  A listener call that returns False ends THAT haystack's matches."""
+        self._emit_batch(_listener_fn(listener), haystacks, self._auto.match_batch(haystacks, with_ids=self._WITH_IDS).tolist())
+
+    def find_all_batch_utf8(self, datas, offsets=None, errors="strict"):
+        """Not in the reference: the (n,3) int32 array of (haystack index, start, end) records -- for a map the (n,4) array of
+        (haystack index, start, end, keyword index) records -- of many UTF-8 haystacks (a sequence of bytes-like objects, or
+        with offsets= one buffer in place) from ONE device call, start and end in BYTES relative to the haystack.  Utf8Error
+        (.haystack, .start) if one of them is ill-formed."""
+        return self._auto.match_batch_utf8(datas if offsets is not None else _checked(datas), with_ids=self._WITH_IDS, offsets=offsets,
+                                           errors=errors)
+
+    def match_batch_utf8(self, datas, listener, errors="strict"):
+        """Not in the reference: match_utf8(data, listener) for every haystack of a list in ONE device call: the listener
+        gets the haystack's own bytes and byte offsets into them (a map's listener the value as well).  A listener call that
+        returns False ends THAT haystack's matches."""
+        datas = _checked(datas)
+        self._emit_batch(_listener_fn(listener), datas, self._auto.match_batch_utf8(datas, with_ids=self._WITH_IDS, errors=errors).tolist())
+
+    @property
+    def automaton(self):
+        return self._auto
 
     def _summary(self, haystacks):
         haystacks = _checked(haystacks)
@@ -949,46 +1006,43 @@ class _BatchDecisions:
         return self._first_rows(self._summary_utf8(datas, offsets, errors))
 
 
-class StringSet(_BatchDecisions):
+class StringSet(_Matcher):
     """S/StringSet.java:3-5"""
-    _MODE = None
+    _WITH_IDS = False
 
     def _init(self, keywords, case_sensitive, word_chars=None):
         self._keywords = list(keywords)
         self._auto = Automaton(self._MODE, self._keywords, bool(case_sensitive), word_chars=word_chars)
 
-    def match(self, haystack, listener):
-        if haystack is None:
-            raise TypeError("haystack is None")  # the reference throws NullPointerException at haystack.length()
-        fn = _listener_fn(listener)
-        pages = _listener_records(self._auto, utf16(haystack), False)
-        try:
-            for page in pages:
-                for s, e in page:
-                    if not fn(haystack, s, e):
-                        return
-        finally:
-            pages.close()  # (a long haystack's cursor: closed at the first False, the rest is never scanned)
+    def _emit(self, fn, rows, haystack=_NO_HAYSTACK):
+        if haystack is _NO_HAYSTACK:
+            for s, e in rows:
+                if not fn(s, e):
+                    return False
+        else:
+            for s, e in rows:
+                if not fn(haystack, s, e):
+                    return False
+        return True
 
-    def count(self, haystack):
-        """Not in the reference: how often every keyword of the constructor's list is reported for `haystack` -- what a listener
-        doing counts[index_of(keyword)] += 1; return True would hold (a duplicate keyword: its last occurrence in the list
-        counts, for ShortestMatch its first) -- as a uint64 array, computed on the device without a record being handed out."""
-        if haystack is None:
-            raise TypeError("haystack is None")
-        return self._auto.count_host(utf16(haystack))[0]
+    def _emit_batch(self, fn, haystacks, rows):
+        skip = -1
+        for h, s, e in rows:
+            if h != skip and not fn(haystacks[h], s, e):
+                skip = h
+
+    def _replacement(self, r):
+        return str(r)
 
     def replace(self, haystack, replacement):
         """Not in the reference: `haystack` with every match replaced by the str `replacement` (the empty one deletes the
         matches), rewritten on the device.  The non-overlapping families only: AhoCorasickSet raises the library's error."""
-        if haystack is None:
-            raise TypeError("haystack is None")
-        return _to_str(self._auto.replace_host(utf16(haystack), str(replacement))[0])
+        return self._replace(haystack, replacement)
 
     def replace_batch(self, haystacks, replacement):
         """Not in the reference: [replace(h, replacement) for h in haystacks] in ONE device call (short inputs: a call has tens
         of microseconds of fixed cost) -> a list of str."""
-        return _split_batch(*self._auto.replace_batch(_checked(haystacks), str(replacement))[:2])
+        return self._replace_batch(haystacks, replacement)
 
     def replace_utf8(self, data, replacement, errors="strict"):
         """Not in the reference: the UTF-8 haystack `data` (bytes, bytearray, memoryview or uint8 array) with every match
@@ -996,112 +1050,32 @@ class StringSet(_BatchDecisions):
         rewritten on the device without a decode or an encode on the host.  Utf8Error if `data` is ill-formed -- unless
         errors="replace": then the matches are those of find_all_utf8(data, errors="replace"), and every byte outside them,
         ill-formed ones included, is copied as it is."""
-        _check_errors(errors)
-        if data is None:
-            raise TypeError("haystack is None")
-        return self._auto.replace_utf8(data, replacement if isinstance(replacement, (bytes, bytearray)) else str(replacement), errors=errors)[0].tobytes()
+        return self._replace_utf8(data, replacement, errors)
 
     def replace_batch_utf8(self, datas, replacement, offsets=None, errors="strict"):
         """Not in the reference: [replace_utf8(d, replacement) for d in datas] in ONE device call -> a list of bytes, one per
         haystack.  datas: a sequence of bytes-like objects, or with offsets= ONE buffer used in place -- a log file line by line:
         replace_batch_utf8(buf, "***", offsets=utf8_line_offsets(buf)).  Utf8Error (.haystack, .start) if one is ill-formed --
         unless errors="replace" (see replace_utf8)."""
-        _check_errors(errors)
-        r = replacement if isinstance(replacement, (bytes, bytearray)) else str(replacement)
-        return _split_batch_utf8(*self._auto.replace_batch_utf8(datas if offsets is not None else _checked(datas), r, offsets=offsets, errors=errors)[:2])
+        return self._replace_batch_utf8(datas, replacement, offsets, errors)
 
     def replace_readable(self, readable, replacement, chunk_chars=1 << 22):
         """Not in the reference: replace() for a text that is read as it goes -- an object with read(n) -> str, or an iterable of
         str / uint16 arrays, cut anywhere, inside a keyword too -> a generator of str whose concatenation is replace() of the
         whole text; a feed yields what no later chunk can change.  Closing the generator closes the stream."""
-        return _replace_stream(self._auto, _chunks(readable, chunk_chars), _str_feed(), str(replacement), "")
+        return self._replace_readable(readable, replacement, chunk_chars)
 
     def replace_utf8_readable(self, readable, replacement, chunk_bytes=1 << 22, errors="strict"):
         """Not in the reference: replace_utf8() for a text that is read as it goes -- a binary file object or an iterable of
         bytes-like chunks, cut anywhere, inside a sequence too (see match_utf8_readable) -> a generator of bytes whose
         concatenation is replace_utf8() of the whole text.  Utf8Error (.start: the global offset) if the text is ill-formed --
         unless errors="replace": then nothing is raised, and the concatenation is replace_utf8(errors="replace") of the whole."""
-        _check_errors(errors)
-        r = replacement if isinstance(replacement, (bytes, bytearray)) else str(replacement)
-        feed = lambda st, chunk, r, final=False: st.replace_feed_utf8(chunk, r, final=final, errors=errors)
-        return _replace_stream(self._auto, _byte_chunks(readable, chunk_bytes), feed, r, b"")
-
-    def find_all(self, haystack):
-        """Convenience (not in the reference): the (n,2) int32 array of (start, end) records."""
-        return self._auto.match_host(utf16(haystack), with_ids=False)
-
-    def find_all_utf8(self, data, errors="strict"):
-        """Not in the reference: the (n,2) int32 array of (start, end) records of a UTF-8 haystack (bytes, bytearray, memoryview
-        or uint8 array), in BYTE offsets into `data` -- decoded, scanned and mapped back on the device.  Utf8Error if ill-formed."""
-        return self._auto.match_utf8(data, with_ids=False, errors=errors)
-
-    def match_utf8(self, data, listener, errors="strict"):
-        """Not in the reference: match(data.decode("utf-8"), listener) with the listener receiving `data` itself and byte
-        offsets into it; a listener call that returns False stops the loop."""
-        if data is None:
-            raise TypeError("haystack is None")
-        fn = _listener_fn(listener)
-        for s, e in self._auto.match_utf8(data, with_ids=False, errors=errors).tolist():
-            if not fn(data, s, e):
-                return
-
-    def match_utf8_readable(self, readable, listener, chunk_bytes=1 << 22, errors="strict"):
-        """Not in the reference: match_utf8 for a text that is read as it goes -- a binary file object (read(n)) or an iterable
-        of bytes-like chunks, cut anywhere, inside a sequence too.  The listener gets (start, end) in GLOBAL byte offsets (there
-        is no one haystack object to hand over); a call that returns False stops the feeding AND the reading.  Utf8Error
-        (.start: the global offset) if the text is ill-formed -- unless errors="replace": the records of
-        match_utf8(errors="replace") on the whole text, whatever the chunking."""
-        _check_errors(errors)
-        fn = _listener_fn(listener)
-        pages = _utf8_stream_pages(self._auto, readable, chunk_bytes, False, errors)
-        try:
-            for page in pages:
-                for s, e in page.tolist():
-                    if not fn(s, e):
-                        return
-        finally:
-            pages.close()
-
-    def find_all_utf8_readable(self, readable, chunk_bytes=1 << 22, errors="strict"):
-        """Not in the reference: the (n,2) int64 array of (start, end) records of a UTF-8 text read chunk by chunk, in GLOBAL
-        byte offsets -- find_all_utf8 of the whole text, which may be longer than 2^31 bytes (errors: as find_all_utf8)."""
-        _check_errors(errors)
-        pages = list(_utf8_stream_pages(self._auto, readable, chunk_bytes, False, errors))
-        return np.concatenate(pages) if pages else np.zeros((0, 2), np.int64)
-
-    def match_batch(self, haystacks, listener):
-        """Not in the reference: match(haystack, listener) for every haystack of a list in ONE device call (short inputs: a
-        call has tens of microseconds of fixed cost).  A listener call that returns False ends THAT haystack's matches."""
-        fn = _listener_fn(listener)
-        skip = -1
-        for h, s, e in self._auto.match_batch(haystacks, with_ids=False).tolist():
-            if h != skip and not fn(haystacks[h], s, e):
-                skip = h
-
-    def find_all_batch_utf8(self, datas, offsets=None, errors="strict"):
-        """Not in the reference: the (n,3) int32 array of (haystack index, start, end) records of many UTF-8 haystacks (a
-        sequence of bytes-like objects, or with offsets= one buffer in place) from ONE device call, start and end in BYTES
-        relative to the haystack.  Utf8Error (.haystack, .start) if one of them is ill-formed."""
-        return self._auto.match_batch_utf8(datas if offsets is not None else _checked(datas), with_ids=False, offsets=offsets, errors=errors)
-
-    def match_batch_utf8(self, datas, listener, errors="strict"):
-        """Not in the reference: match_utf8(data, listener) for every haystack of a list in ONE device call: the listener
-        gets the haystack's own bytes and byte offsets into them.  A listener call that returns False ends THAT haystack's matches."""
-        datas = _checked(datas)
-        fn = _listener_fn(listener)
-        skip = -1
-        for h, s, e in self._auto.match_batch_utf8(datas, with_ids=False, errors=errors).tolist():
-            if h != skip and not fn(datas[h], s, e):
-                skip = h
-
-    @property
-    def automaton(self):
-        return self._auto
+        return self._replace_utf8_readable(readable, replacement, chunk_bytes, errors)
 
 
-class StringMap(_BatchDecisions):
+class StringMap(_Matcher):
     """S/StringMap.java:5-9 (String overload only)"""
-    _MODE = None
+    _WITH_IDS = True
 
     def _init(self, keywords, values, case_sensitive, word_chars=None):
         # the reference consumes keywords and values pairwise and stops at the shorter one (S/AhoCorasickMap.java:32)
@@ -1110,23 +1084,38 @@ class StringMap(_BatchDecisions):
         self._values = [v for _, v in pairs]
         self._auto = Automaton(self._MODE, self._keywords, bool(case_sensitive), word_chars=word_chars)
 
+    def _emit(self, fn, rows, haystack=_NO_HAYSTACK):
+        vals = self._values
+        if haystack is _NO_HAYSTACK:
+            for s, e, k in rows:
+                if not fn(s, e, vals[k]):
+                    return False
+        else:
+            for s, e, k in rows:
+                if not fn(haystack, s, e, vals[k]):
+                    return False
+        return True
+
+    def _emit_batch(self, fn, haystacks, rows):
+        vals = self._values
+        skip = -1
+        for h, s, e, k in rows:
+            if h != skip and not fn(haystacks[h], s, e, vals[k]):
+                skip = h
+
+    def _replacement(self, replacements):
+        if replacements is None:
+            if not all(isinstance(v, str) for v in self._values):
+                raise TypeError("replace() without replacements needs str values")
+            return self._values
+        return replacements if isinstance(replacements, str) else list(replacements)[:len(self._keywords)]
+
     def match(self, haystack, listener):
         """match(String, MapMatchListener<T>) -- or, when `haystack` has read() / is an iterable of chunks,
         match(Readable, ReadableMatchListener<T>) (S/StringMap.java:6-8)."""
-        if haystack is None:
-            raise TypeError("haystack is None")
-        if not isinstance(haystack, (str, np.ndarray)):
+        if haystack is not None and not isinstance(haystack, (str, np.ndarray)):
             return self.match_readable(haystack, listener)
-        fn = _listener_fn(listener)
-        vals = self._values
-        pages = _listener_records(self._auto, utf16(haystack), True)
-        try:
-            for page in pages:
-                for s, e, k in page:
-                    if not fn(haystack, s, e, vals[k]):
-                        return
-        finally:
-            pages.close()
+        return _Matcher.match(self, haystack, listener)
 
     def match_readable(self, readable, listener, chunk_chars=1 << 22):
         """S/AhoCorasickMap.java:208-275, S/LongestMatchMap.java:203-286, S/WholeWordMatchMap.java:55-153: the listener
@@ -1135,147 +1124,44 @@ class StringMap(_BatchDecisions):
         vals = self._values
         st = Stream(self._auto, with_ids=True)
         try:
-            for chunk in _chunks(readable, chunk_chars):
-                for k in st.feed(utf16(chunk))[:, 2].tolist():
+            feeds = itertools.chain(((chunk, False) for chunk in _chunks(readable, chunk_chars)), [("", True)])
+            for chunk, final in feeds:  # (the value-only listener of this flavour's one Readable form: its loop is here)
+                for k in st.feed(utf16(chunk), final=final)[:, 2].tolist():
                     if not fn(vals[k]):
                         return
-            for k in st.feed(np.zeros(0, np.uint16), final=True)[:, 2].tolist():
-                if not fn(vals[k]):
-                    return
         finally:
             st.close()
-
-    def count(self, haystack):
-        """Not in the reference: how often the listener of match(String, ...) would be called with each value -- a uint64 array
-        aligned with the constructor's keyword / value lists (a duplicate keyword: the value that won), computed on the
-        device without a record being handed out."""
-        if haystack is None:
-            raise TypeError("haystack is None")
-        return self._auto.count_host(utf16(haystack))[0]
 
     def replace(self, haystack, replacements=None):
         """Not in the reference: `haystack` with every match replaced, rewritten on the device -- by its value (replacements is
         None: the values must all be str), by the entry of a list aligned with the constructor's keywords, or by one str for
         every keyword.  The non-overlapping families only: AhoCorasickMap raises the library's error."""
-        if haystack is None:
-            raise TypeError("haystack is None")
-        return _to_str(self._auto.replace_host(utf16(haystack), self._replacements_for(replacements))[0])
+        return self._replace(haystack, replacements)
 
     def replace_batch(self, haystacks, replacements=None):
         """Not in the reference: [replace(h, replacements) for h in haystacks] in ONE device call (see
         StringSet.replace_batch) -> a list of str."""
-        return _split_batch(*self._auto.replace_batch(_checked(haystacks), self._replacements_for(replacements))[:2])
+        return self._replace_batch(haystacks, replacements)
 
     def replace_utf8(self, data, replacements=None, errors="strict"):
         """Not in the reference: the UTF-8 haystack `data` with every match replaced -> bytes (see StringSet.replace_utf8);
         `replacements` under the rules of replace(), a str encoded as UTF-8, bytes taken as they are."""
-        _check_errors(errors)
-        if data is None:
-            raise TypeError("haystack is None")
-        if not isinstance(replacements, (bytes, bytearray)):
-            replacements = self._replacements_for(replacements)
-        return self._auto.replace_utf8(data, replacements, errors=errors)[0].tobytes()
+        return self._replace_utf8(data, replacements, errors)
 
     def replace_batch_utf8(self, datas, replacements=None, offsets=None, errors="strict"):
         """Not in the reference: [replace_utf8(d, replacements) for d in datas] in ONE device call -> a list of bytes (see
         StringSet.replace_batch_utf8); `replacements` under the rules of replace_utf8()."""
-        _check_errors(errors)
-        if not isinstance(replacements, (bytes, bytearray)):
-            replacements = self._replacements_for(replacements)
-        return _split_batch_utf8(*self._auto.replace_batch_utf8(datas if offsets is not None else _checked(datas), replacements, offsets=offsets, errors=errors)[:2])
+        return self._replace_batch_utf8(datas, replacements, offsets, errors)
 
     def replace_readable(self, readable, replacements=None, chunk_chars=1 << 22):
         """Not in the reference: replace() for a text that is read as it goes -> a generator of str (see
         StringSet.replace_readable); `replacements` under the rules of replace()."""
-        return _replace_stream(self._auto, _chunks(readable, chunk_chars), _str_feed(), self._replacements_for(replacements), "")
+        return self._replace_readable(readable, replacements, chunk_chars)
 
     def replace_utf8_readable(self, readable, replacements=None, chunk_bytes=1 << 22, errors="strict"):
         """Not in the reference: replace_utf8() for a text that is read as it goes -> a generator of bytes (see
         StringSet.replace_utf8_readable); `replacements` under the rules of replace_utf8()."""
-        _check_errors(errors)
-        if not isinstance(replacements, (bytes, bytearray)):
-            replacements = self._replacements_for(replacements)
-        feed = lambda st, chunk, r, final=False: st.replace_feed_utf8(chunk, r, final=final, errors=errors)
-        return _replace_stream(self._auto, _byte_chunks(readable, chunk_bytes), feed, replacements, b"")
-
-    def _replacements_for(self, replacements):
-        if replacements is None:
-            if not all(isinstance(v, str) for v in self._values):
-                raise TypeError("replace() without replacements needs str values")
-            return self._values
-        return replacements if isinstance(replacements, str) else list(replacements)[:len(self._keywords)]
-
-    def find_all(self, haystack):
-        """Convenience (not in the reference): the (n,3) int32 array of (start, end, keyword_index) records."""
-        return self._auto.match_host(utf16(haystack), with_ids=True)
-
-    def find_all_utf8(self, data, errors="strict"):
-        """Not in the reference: the (n,3) int32 array of (start, end, keyword_index) records of a UTF-8 haystack, in BYTE
-        offsets into `data` (see StringSet.find_all_utf8)."""
-        return self._auto.match_utf8(data, with_ids=True, errors=errors)
-
-    def match_utf8(self, data, listener, errors="strict"):
-        """Not in the reference: match(data.decode("utf-8"), listener) with the listener receiving `data` itself, byte offsets
-        into it and the value; a listener call that returns False stops the loop."""
-        if data is None:
-            raise TypeError("haystack is None")
-        fn = _listener_fn(listener)
-        vals = self._values
-        for s, e, k in self._auto.match_utf8(data, with_ids=True, errors=errors).tolist():
-            if not fn(data, s, e, vals[k]):
-                return
-
-    def match_utf8_readable(self, readable, listener, chunk_bytes=1 << 22, errors="strict"):
-        """Not in the reference: match_utf8 for a text that is read as it goes (see StringSet.match_utf8_readable); the listener
-        gets (start, end, value) in GLOBAL byte offsets."""
-        _check_errors(errors)
-        fn = _listener_fn(listener)
-        vals = self._values
-        pages = _utf8_stream_pages(self._auto, readable, chunk_bytes, True, errors)
-        try:
-            for page in pages:
-                for s, e, k in page.tolist():
-                    if not fn(s, e, vals[k]):
-                        return
-        finally:
-            pages.close()
-
-    def find_all_utf8_readable(self, readable, chunk_bytes=1 << 22, errors="strict"):
-        """Not in the reference: the (n,3) int64 array of (start, end, keyword_index) records of a UTF-8 text read chunk by
-        chunk, in GLOBAL byte offsets (see StringSet.find_all_utf8_readable)."""
-        _check_errors(errors)
-        pages = list(_utf8_stream_pages(self._auto, readable, chunk_bytes, True, errors))
-        return np.concatenate(pages) if pages else np.zeros((0, 3), np.int64)
-
-    def match_batch(self, haystacks, listener):
-        """Not in the reference: match(haystack, listener) for every haystack of a list in ONE device call (see
-        StringSet.match_batch)."""
-        fn = _listener_fn(listener)
-        vals = self._values
-        skip = -1
-        for h, s, e, k in self._auto.match_batch(haystacks, with_ids=True).tolist():
-            if h != skip and not fn(haystacks[h], s, e, vals[k]):
-                skip = h
-
-    def find_all_batch_utf8(self, datas, offsets=None, errors="strict"):
-        """Not in the reference: the (n,4) int32 array of (haystack index, start, end, keyword index) records of many UTF-8
-        haystacks from ONE device call (see StringSet.find_all_batch_utf8)."""
-        return self._auto.match_batch_utf8(datas if offsets is not None else _checked(datas), with_ids=True, offsets=offsets, errors=errors)
-
-    def match_batch_utf8(self, datas, listener, errors="strict"):
-        """Not in the reference: match_utf8(data, listener) for every haystack of a list in ONE device call (see
-        StringSet.match_batch_utf8)."""
-        datas = _checked(datas)
-        fn = _listener_fn(listener)
-        vals = self._values
-        skip = -1
-        for h, s, e, k in self._auto.match_batch_utf8(datas, with_ids=True, errors=errors).tolist():
-            if h != skip and not fn(datas[h], s, e, vals[k]):
-                skip = h
-
-    @property
-    def automaton(self):
-        return self._auto
+        return self._replace_utf8_readable(readable, replacements, chunk_bytes, errors)
 
 
 def _word_chars(word_characters, toggle_flags):
