@@ -198,7 +198,9 @@ __device__ __forceinline__ void verify_multi(TileCtx &c, uint32_t head, uint32_t
         } else if (!ACGPU_DBG(L, 16u)) {
             ent = act[b] ? reinterpret_cast<const uint2 *>(T.kgram_node)[idx] : make_uint2(0u, 0u);
         }
-        if (!act[b]) ent = make_uint2(0u, 0u);
+        // (fewer than K units in front of e: the window's zeros before the buffer are no text -- with U+0000 in a keyword they
+        // would spell its beginning; keywords of fewer than K units that end here come from the short-keyword tables below)
+        if (!act[b] || e[b] < (uint32_t)K) ent = make_uint2(0u, 0u);
         ref[b] = ent.x;
         ref0[b] = ent.x;
         child0[b] = ent.y; // the depth-K node's only child, travelling with it

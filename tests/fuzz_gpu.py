@@ -2,7 +2,9 @@
 """Randomised GPU-vs-oracle soak test (development tool; the pytest suite holds the fixed regression cases).
 
 Draws random dictionaries / haystacks / tunables / shard splits for all three matcher families and compares the
-device records with oracle/ac_oracle.c bit for bit.  Usage: python tests/fuzz_gpu.py [seconds] [seed]"""
+device records with oracle/ac_oracle.c bit for bit.  Usage: python tests/fuzz_gpu.py [seconds] [seed] [--fold-table NAME]
+(--fold-table java | wide | huge | scatter | rotate: a fold table of tests/fold_tables.py, with its word table, for the automaton and
+the oracle alike, and alphabets drawn from the preimages of the units the table's rule folds to; default: the shipped table)"""
 import os
 import sys
 import time
@@ -33,6 +35,18 @@ ALPHABETS = [
 ]
 DEFAULTS = {"chunk_units": 0, "lds_table_bytes": 127 * 1024, "force_sparse": 0, "force_kernel": 0, "region_units": 0,
             "rdense_budget_bytes": 256 << 20, "tile_debug": 0, "longest_form": 0, "all_form": 0, "tile_form": 0, "ww_block": 0, "ww_ramp_pm": -1}
+
+
+def table_alphabets(lower):
+    """alphabets of raw units for a table of tests/fold_tables.py: every preimage (up to 12) of some of the units its rule folds to"""
+    from tests.fold_tables import preimages
+    own = np.unique(lower[np.flatnonzero(lower != java_lower_table())])
+    if not len(own):
+        return ALPHABETS
+    pre = preimages(lower)
+    raw = lambda folded: sorted({int(r) for f in folded for r in pre[int(f)][:12].tolist()})
+    return [raw(own[:2]), raw(own[:3]), raw(own[:8]), raw(own[::max(1, len(own) // 40)][:40]), raw(own[-5:]) + [ord(c) for c in "ab -_.,9"],
+            raw(own[:6]) + [ord(c) for c in "abAB 019-"] + [0x00E9, 0x00C9, 0x0130, 0x212A], raw(own) if len(own) > 64 else raw(own[:4]) + list(range(0x4E00, 0x4E00 + 300))]
 
 
 def dev_match(a, d_hay, n, cap, with_ids=True, **kw):
@@ -125,7 +139,7 @@ def one_case(rng, it):
     for k, v in ww_build.items():
         N.set_tunable(k, v)
     try:
-        a = Automaton(mode, kws, cs, word_chars=wc)
+        a = Automaton(mode, kws, cs, word_chars=wc, lower=LOWER)
     finally:
         N.set_tunable("no_class_pages", 0)
         for k in ww_build:
@@ -192,8 +206,20 @@ def one_case(rng, it):
 
 
 def main():
-    budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 12345
+    global LOWER, WORD, ALPHABETS
+    argv = list(sys.argv[1:])
+    table = "java"
+    if "--fold-table" in argv:
+        at = argv.index("--fold-table")
+        table = argv[at + 1]
+        if table not in ("java", "wide", "huge", "scatter", "rotate"):
+            sys.exit("--fold-table: java, wide, huge, scatter or rotate")
+        del argv[at:at + 2]
+        from tests.fold_tables import fold_table
+        lower, word = fold_table(table)
+        LOWER, WORD, ALPHABETS = np.array(lower), np.array(word), table_alphabets(np.array(lower))
+    budget = float(argv[0]) if len(argv) > 0 else 60.0
+    seed = int(argv[1]) if len(argv) > 1 else 12345
     rng = np.random.default_rng(seed)
     t0 = time.time()
     counts = [0, 0, 0, 0, 0]
@@ -205,8 +231,8 @@ def main():
         if time.time() - t_said > 30:  # a long soak keeps talking (a silent run is taken to be hung)
             t_said = time.time()
             print("  ... %d cases after %.0f s" % (it, t_said - t0), flush=True)
-    print("fuzz ok: %d cases (AC %d, Longest %d, WholeWord %d, Shortest %d, WholeWordLongest %d) in %.0f s, seed %d" % (
-        it, *counts, time.time() - t0, seed))
+    print("fuzz ok: %d cases (AC %d, Longest %d, WholeWord %d, Shortest %d, WholeWordLongest %d) in %.0f s, seed %d, fold table %s" % (
+        it, *counts, time.time() - t0, seed, table))
 
 
 if __name__ == "__main__":
