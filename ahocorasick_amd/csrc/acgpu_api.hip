@@ -1940,7 +1940,7 @@ int acgpu_debug_wordhash(const acgpu_automaton *a, uint32_t *n_slots, uint32_t *
                          uint8_t *fold_pgidx, uint32_t *n_pages, uint16_t *fold_pages, uint32_t *seed) {
     if (!a) return ACGPU_E_INVALID;
     const HostTables &t = a->t;
-    if (t.mode != ACGPU_MODE_WHOLEWORD) return ACGPU_E_UNSUPPORTED;
+    if (t.mode != ACGPU_MODE_WHOLEWORD && t.mode != ACGPU_MODE_WWLONGEST) return ACGPU_E_UNSUPPORTED;
     if (n_slots) *n_slots = (uint32_t)(t.ww_fat.size() / 8);
     if (slots) std::memcpy(slots, t.ww_fat.data(), t.ww_fat.size() * sizeof(uint32_t));
     if (n_rec_words) *n_rec_words = t.ww_recs.size();

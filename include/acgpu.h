@@ -1136,8 +1136,8 @@ int acgpu_debug_tables(const acgpu_automaton *a, uint16_t *cls_lut /*65536*/, ui
 int acgpu_debug_states(const acgpu_automaton *a, uint64_t sizes[6], uint32_t *rows, uint32_t *nodes, uint32_t *mask, uint32_t *out,
                        uint32_t *ids);
 
-/* Test hook (ACGPU_MODE_WHOLEWORD): the whole-keyword hash table the device kernel probes.  Sizes and the seed are always
- * written; arrays are copied when the pointer is non-NULL.
+/* Test hook (ACGPU_MODE_WHOLEWORD, ACGPU_MODE_WWLONGEST): the whole-keyword hash table the device kernel probes.  Sizes and
+ * the seed are always written; arrays are copied when the pointer is non-NULL.
  * Hashes of a folded keyword over its max(8, ceil(length/2)) packed words w (two units per word, zero beyond the keyword):
  *   h = seed; h = h*33 + w            ... then the murmur3 32-bit finaliser        (hash)
  *   g = seed; g = rotl(g, 5) ^ w                                                    (second hash)
@@ -1147,7 +1147,12 @@ int acgpu_debug_states(const acgpu_automaton *a, uint64_t sizes[6], uint32_t *ro
  * more than 12 units hold their record's offset (in 16-byte units) in place of the id.
  * recs: uint32 words, record = {keyword id, length, folded units packed two per word, zero padded to 16 bytes}.
  * fold_pgidx[256] / fold_pages[n_pages*256]: lower[u] = (u + fold_pages[fold_pgidx[u>>8]*256 + (u&255)]) & 0xffff;
- * page 0 is all zero. */
+ * page 0 is all zero.
+ * ACGPU_MODE_WWLONGEST: the same table over the FIRST WORDS a walk can end or go on from -- the trie paths of word
+ * characters only, of at most 12 units, that are a (trimmed, folded) keyword or go on with a non-word unit.  The id field
+ * (and a record's first word) is then a payload: bit 31 set = the path goes on with a non-word unit, the low 31 bits are the
+ * number of its trie node (the walk goes on from there, unit by unit); bit 31 clear = the walk ends on this keyword, the
+ * payload is its id (the last one given, among duplicates).  No path of more than 12 units is in the table. */
 int acgpu_debug_wordhash(const acgpu_automaton *a, uint32_t *n_slots, uint32_t *slots, uint64_t *n_rec_words, uint32_t *recs,
                          uint8_t *fold_pgidx, uint32_t *n_pages, uint16_t *fold_pages, uint32_t *seed);
 
