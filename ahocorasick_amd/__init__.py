@@ -7,7 +7,10 @@ from .strings import (AhoCorasickMap, AhoCorasickSet, Automaton, IllegalArgument
                       LongestMatchSet, MapMatchListener, ReadableMatchListener, SetMatchListener, ShortestMatchMap, ShortestMatchSet, Stream, StringMap,
                       StringSet, WholeWordLongestMatchMap, WholeWordLongestMatchSet, WholeWordMatchMap, WholeWordMatchSet,
                       Utf8Error, utf8_line_offsets, utf8_unit_offsets, utf16)
+from . import terms
+from .terms import count_batch, count_batch_utf8
 
 __all__ = ["AhoCorasickSet", "AhoCorasickMap", "LongestMatchSet", "LongestMatchMap", "WholeWordMatchSet",
            "WholeWordMatchMap", "ShortestMatchSet", "ShortestMatchMap", "WholeWordLongestMatchSet", "WholeWordLongestMatchMap", "StringSet", "StringMap", "SetMatchListener", "MapMatchListener", "ReadableMatchListener", "Stream", "Automaton",
-           "IllegalArgumentException", "utf16", "Utf8Error", "utf8_unit_offsets", "utf8_line_offsets"]
+           "IllegalArgumentException", "utf16", "Utf8Error", "utf8_unit_offsets", "utf8_line_offsets",
+           "terms", "count_batch", "count_batch_utf8"]

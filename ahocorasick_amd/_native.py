@@ -91,6 +91,14 @@ class SummaryStats(ctypes.Structure):  # acgpu_summary_stats
     _fields_ = [("n_records", ctypes.c_uint64), ("n_matched", ctypes.c_uint64), ("pieces", ctypes.c_uint32), ("rescans", ctypes.c_uint32)]
 
 
+class CountBatchStats(ctypes.Structure):  # acgpu_count_batch_stats
+    _fields_ = [("n_records", ctypes.c_uint64), ("n_entries", ctypes.c_uint64), ("n_terms", ctypes.c_uint64), ("pieces", ctypes.c_uint32),
+                ("rescans", ctypes.c_uint32), ("rows_cut", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+TERMS_BLOCK = 2048  # kTermsBlock (csrc/acgpu_terms.hip): the records a workgroup of k_terms_block sorts and reduces
+
+
 class Utf8Stats(ctypes.Structure):  # acgpu_utf8_stats
     _fields_ = [("n_units", ctypes.c_uint64), ("first_bad", ctypes.c_int64), ("ascii", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
@@ -129,7 +137,7 @@ _UTF8_STATS = set(_LOSSY_STATS) | set(_LOSSY_STATS.values())
 
 def _signatures():
     """The C ABI of include/acgpu.h, once: symbol -> (restype, argtypes); argtypes None: ctypes is told nothing about them.  The
-    seven _lossy entries are their strict twins with another stats struct (_LOSSY_STATS) and are derived, not written out."""
+    eight _lossy entries are their strict twins with another stats struct (_LOSSY_STATS) and are derived, not written out."""
     vp, u64, i64, u32, ci, P = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER
     sig = {
         "acgpu_build": (ci, [ci, vp, vp, u32, ci, vp, vp, P(vp), P(i64)]),
@@ -173,6 +181,9 @@ def _signatures():
         "acgpu_match_utf8": (ci, [vp, vp, u64, ci, vp, u64, P(u64), P(Utf8Stats)]),
         "acgpu_match_batch_utf8": (ci, [vp, vp, vp, u32, ci, vp, u64, P(u64), P(Utf8BatchStats)]),
         "acgpu_summary_batch_utf8": (ci, [vp, vp, vp, u32, vp, P(SummaryStats), P(Utf8BatchStats)]),
+        "acgpu_count_batch_u16": (ci, [vp, vp, vp, u32, vp, vp, vp, u64, P(u64), P(CountBatchStats)]),
+        "acgpu_count_batch_utf8": (ci, [vp, vp, vp, u32, vp, vp, vp, u64, P(u64), P(CountBatchStats), P(Utf8BatchStats)]),
+        "acgpu_debug_count_batch_finish": (ci, [vp, u64, u32, vp, vp, vp, P(u64), P(u32)]),
         "acgpu_replace_utf8": (ci, [vp, vp, u64, vp, vp, u32, vp, u64, P(u64), P(ReplaceStats), P(Utf8Stats)]),
         "acgpu_replace_batch_utf8": (ci, [vp, vp, vp, u32, vp, vp, u32, vp, u64, vp, P(u64), P(ReplaceStats), P(Utf8BatchStats)]),
         "acgpu_match_u16_multi": (ci, [vp, vp, u64, P(ci), ci, ci, vp, u64, P(u64)]),

@@ -228,6 +228,7 @@ struct DeviceState {
     PoolEvent replace_ev[4];                              // ... slab b emitted (b), slab b copied out (2 + b)
     PoolBuf replace_merged, replace_off;                  // acgpu_replace_batch_u16: a piece's records merged with its separators, the result's offsets (acgpu_replace_batch_utf8's too)
     PoolBuf summary;                                      // acgpu_summary_batch_u16: 24 bytes per haystack, {records, the first of them}
+    PoolBuf terms_entries, terms_stage, terms_aux, terms_count; // acgpu_count_batch_*: the call's entry list {h, id, count}, a piece's entries block by block, {block_base, n_distinct} per block, the running entry count (acgpu_terms.hip)
     PoolBuf utf8_in, utf8_aux;                            // the UTF-8 entries: the caller's bytes; {n_units, first_bad, tail, n_replaced}, block sums, checkpoints, a batch's byte offsets, a lossy text's start bitmap (Utf8Aux, acgpu_utf8.hip)
     CountCall *count = nullptr;                          // the counting call that runs on this pool (it holds mu), or nullptr
     double all_density = -1.0;                           // ALL: records per unit of this pool's last call (-1: none yet): k_ac_states or the tile kernel
@@ -552,8 +553,8 @@ struct BatchText {
     int stage(const uint16_t *units, const uint64_t *offsets, uint32_t n, hipStream_t stream);
 };
 
-// A text on its way through a reservoir, piece by piece (scan_next_piece, acgpu_pieces.hip).  Four consumers: the cursor keeps
-// one from page call to page call; a counting, a replace and a batch summary call have one for each text they drive.
+// A text on its way through a reservoir, piece by piece (scan_next_piece, acgpu_pieces.hip).  Five consumers: the cursor keeps
+// one from page call to page call; a counting, a replace, a batch summary and a count-batch call have one for each text they drive.
 struct PieceDriver {
     uint64_t pos = 0, end = 0;         // the owned units [pos, end) have not been scanned yet
     int64_t chain = 0;                 // the chain's entry into the next piece (the text's coordinates)

@@ -78,6 +78,9 @@
  *        acgpu_match_batch_u16)
  *      offsets (device)                         4 H
  *      summaries (device)                       24 H, grow-only
+ *    acgpu_count_batch_u16 needs the same without the summaries, plus, kept by the pool and grow-only:
+ *      entry list (device)                      12 bytes per entry, at most cap entries
+ *      staging (device)                         12 bytes per record of ONE piece (+ 12 per 2048 records)
  *    acgpu_match_utf8 needs what acgpu_match_u16 needs for the decoded text as ONE shard (N = its units, at most B, the bytes
  *    given: the staged text 2 N, the records cap x record_kind, the scan's form above), plus, kept by the pool:
  *      the bytes (device)                       B
@@ -845,6 +848,78 @@ int acgpu_summary_batch_utf8_lossy(const acgpu_automaton *a, const uint8_t *byte
                                    acgpu_utf8_lossy_stats *stats /* may be NULL */);
 
 /*
+ * Many short texts COUNTED PER KEYWORD in one call: the document-term matrix of a batch -- which keywords of the dictionary occur
+ * in every haystack, and how often -- reduced on the device, in CSR form.  Row i holds the distinct keyword_ids of the records with
+ * haystack == i that acgpu_match_batch_u16(..., ACGPU_REC_MAP, ...) returns for the same arguments, ascending, each with the
+ * number of such records: numpy's unique(ids, return_counts=True) per haystack.  Every family, ACGPU_MODE_ALL included.  Ids
+ * index the list given to acgpu_build, as in acgpu_count_u16: the matrix has as many columns as keywords were given, and a
+ * duplicate keyword reports the index that wins in the match call.  No positions are returned, so the UTF-8 forms map nothing: they
+ * return what acgpu_count_batch_u16 returns for the haystacks decoded one by one (the lossy form: decoded with errors="replace").
+ * A single text is a batch of one haystack: that is also how a UTF-8 text gets sparse counts per keyword.
+ *  row_ptr     : HOST, n_haystacks + 1 entries; row i is [row_ptr[i], row_ptr[i + 1]) of keyword_ids and counts; row_ptr[0] == 0.
+ *  keyword_ids : HOST, cap entries (NULL allowed with cap == 0); ascending and distinct within a row.
+ *  counts      : HOST, cap entries (NULL allowed with cap == 0).  32 bits suffice: one keyword ends at most once per unit, and a
+ *                batch has fewer than 2^31 units.
+ *  *n_out      : on success the stored entries, n_terms == row_ptr[n_haystacks].
+ *  st          : NULL, or the call's numbers (written on success and on ACGPU_E_OVERFLOW).
+ * CAPACITY.  The device produces ENTRIES {haystack, keyword, count}, and a haystack whose records are cut -- see below -- has
+ * the same keyword in more than one of them until the host has merged them: n_terms <= n_entries <= n_records.  cap is compared
+ * with n_entries.  If n_entries > cap the call returns ACGPU_E_OVERFLOW with *n_out = n_entries -- exact, counting goes on where
+ * writes are dropped -- and nothing is written to the three arrays.  The same call again (the same automaton, batch and tunables)
+ * with cap >= that *n_out succeeds: the pieces and blocks of a call depend on nothing else, so it produces the same entries.
+ * cap = the batch's record count always suffices.
+ *  errors    : ACGPU_E_INVALID, before any device is touched: NULL a, offsets, row_ptr or n_out; cap > 0 with NULL keyword_ids or
+ *              counts; descending offsets; units to read and no array; offsets[n_haystacks] - offsets[0] + n_haystacks >= 2^31 (the
+ *              UTF-8 forms: in bytes).  ACGPU_E_INVALID as well with tickets in flight on the pool (the call works on the NULL
+ *              stream, under the pool's lock, as acgpu_summary_batch_u16 does).  ACGPU_E_ENCODING (acgpu_count_batch_utf8 only): as
+ *              acgpu_summary_batch_utf8 reports it, stats->bad_haystack and stats->first_bad; *n_out = 0.  n_haystacks == 0, or all
+ *              haystacks empty: ACGPU_OK with an empty matrix, no device needed.  Without a device the call fails as
+ *              acgpu_match_batch_u16 does.  After every failure the three arrays are untouched.
+ * How it works: the haystacks go through the pieces as acgpu_summary_batch_u16 drives them (one text with a separator unit behind
+ * every haystack; the Map records of a piece stay in the pool's reservoir; a piece scanned again for want of room is reduced
+ * once).  A family's records come in listener order and no match crosses a separator, so the haystack index of the records never
+ * descends.  Behind every piece three kernels run, with no host wait: k_terms_block -- a workgroup of 256 lanes per block of 2048
+ * consecutive records sorts the keys (haystack << 32) | id in LDS with a bitonic network, marks the heads of the runs of equal
+ * keys, and writes its distinct {haystack, id, count} to its own region of a staging buffer; k_terms_place -- one workgroup scans
+ * the blocks' numbers of distinct keys behind the call's running entry count; k_terms_gather -- every block copies its entries to
+ * their place in the call's entry list, where that is below cap.  The list has the haystacks ascending, and within one block's
+ * entries of one haystack the ids ascending and distinct.  A haystack whose run of records is CUT by a block boundary or a piece
+ * boundary, or that has more than 2048 records, has several such sub-rows in a row.  At the end the list is copied to the host
+ * once (12 bytes per entry) and finished in one linear pass: row_ptr is filled, and only the cut rows -- one per 2048 records
+ * where haystacks are short -- are sorted and their equal ids summed (st->rows_cut).
+ * THE LIMIT of this form: one huge haystack is one row cut into as many sub-rows as it has blocks, and the host then sorts all of
+ * its entries on one thread; short texts are the contract of the batch calls.
+ * Haystack by haystack inside the library instead, same results, where acgpu_match_batch_u16 falls back (a dictionary that uses
+ * all 65536 units, and the word matchers over a table that is not fold-consistent): every haystack goes through the pieces as a
+ * text of its own and the same kernels.
+ * Memory, kept by the pool and grow-only: the entry list, 12 bytes per entry up to cap (it grows with the records seen, never past
+ * cap); the staging buffer, 12 bytes per record of ONE piece rounded up to 2048 records, plus 12 bytes per block; the counting
+ * calls' reservoir; and what acgpu_summary_batch_u16 (the UTF-8 forms: acgpu_summary_batch_utf8) needs without the summaries.
+ * Not built: a dense per-keyword count of a UTF-8 text; device-resident, multi-device, cursor or streaming forms; a merge of the
+ * cut rows on the device; document frequency and other reductions of the matrix; the Java facade.  ACGPU_ABI_VERSION stays as it
+ * is: adding symbols is compatible.
+ */
+typedef struct acgpu_count_batch_stats {
+    uint64_t n_records;       /* records of the batch: the sum of all counts                                    */
+    uint64_t n_entries;       /* entries the device produced, before cut rows are merged: what cap is compared with */
+    uint64_t n_terms;         /* entries of the matrix (0 on ACGPU_E_OVERFLOW)                                    */
+    uint32_t pieces, rescans; /* as acgpu_summary_stats                                                           */
+    uint32_t rows_cut;        /* rows the host had to sort and merge                                              */
+    uint32_t reserved;        /* 0 */
+} acgpu_count_batch_stats;    /* 40 bytes */
+int acgpu_count_batch_u16(const acgpu_automaton *a, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks,
+                          uint64_t *row_ptr /* n_haystacks + 1, host */, uint32_t *keyword_ids /* cap, host */, uint32_t *counts /* cap, host */,
+                          uint64_t cap, uint64_t *n_out, acgpu_count_batch_stats *st /* may be NULL */);
+int acgpu_count_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
+                           uint64_t *row_ptr /* n_haystacks + 1, host */, uint32_t *keyword_ids /* cap, host */, uint32_t *counts /* cap, host */,
+                           uint64_t cap, uint64_t *n_out, acgpu_count_batch_stats *st /* may be NULL */,
+                           acgpu_utf8_batch_stats *stats /* may be NULL */);
+int acgpu_count_batch_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
+                                 uint64_t *row_ptr /* n_haystacks + 1, host */, uint32_t *keyword_ids /* cap, host */,
+                                 uint32_t *counts /* cap, host */, uint64_t cap, uint64_t *n_out, acgpu_count_batch_stats *st /* may be NULL */,
+                                 acgpu_utf8_lossy_stats *stats /* may be NULL */);
+
+/*
  * Many short UTF-8 texts rewritten in ONE call: acgpu_replace_utf8 for a batch, the conjunction of acgpu_match_batch_utf8 and
  * acgpu_replace_batch_u16.  Haystack i is bytes[offsets[i] .. offsets[i+1]) as for acgpu_match_batch_utf8 (contiguous in the
  * caller's buffer, empty ones allowed anywhere), and out[out_offsets[i] .. out_offsets[i+1]) is byte for byte what
@@ -1168,6 +1243,14 @@ int acgpu_debug_wordhash(const acgpu_automaton *a, uint32_t *n_slots, uint32_t *
  * word character = e & 1, lower[u] = (u + delta[e >> 1]) & 0xffff (delta: 128 entries). */
 int acgpu_debug_wordhash_perfect(const acgpu_automaton *a, uint32_t sizes[3], uint32_t *slots, uint16_t *disp, uint8_t *bp_idx,
                                  uint8_t *bp_pages, uint16_t *bp_delta);
+
+/* Test hook: the host's finishing pass of acgpu_count_batch_u16 on an entry list given by the caller -- no automaton, no device.
+ * entries: 3 words {haystack, keyword_id, count} per entry, the haystacks never descending and below n_haystacks; the entries of
+ * one haystack are sub-rows of ascending, distinct ids.  Out: the CSR matrix (row_ptr: n_haystacks + 1 entries; ids and counts:
+ * room for n_entries), *n_terms its entries, *rows_cut the rows that had more than one sub-row and were sorted and merged.
+ * ACGPU_E_HIP for a haystack index that descends or is out of range, with nothing written; ACGPU_E_INVALID for a NULL pointer. */
+int acgpu_debug_count_batch_finish(const uint32_t *entries /* 3 per entry */, uint64_t n_entries, uint32_t n_haystacks, uint64_t *row_ptr,
+                                   uint32_t *ids, uint32_t *counts, uint64_t *n_terms, uint32_t *rows_cut);
 
 #ifdef __cplusplus
 }
