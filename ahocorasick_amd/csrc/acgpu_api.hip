@@ -2312,13 +2312,15 @@ int match_host_text(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack
     const HostTables &t = a->t;
     int rc;
     // short haystacks: one launch, no copies (tunable tile_debug bit kSelNoSmallCall, or a kernel form forced by "force_kernel": the
-    // general path -- for A/B, and for the tests that run the scan kernels on the short edge-case inputs)
+    // general path -- for A/B, and for the tests that run the scan kernels on the short edge-case inputs; bit kSelOnlySmallCall:
+    // no general path -- a call the one launch does not answer itself is ACGPU_E_UNSUPPORTED, which tells a test who answered)
     if (n_units > 0 && n_units <= kSmallMaxUnits && d.inflight == 0 && small_call_supported(t) && !(tunables().tile_debug & kSelNoSmallCall) &&
         tunables().force_kernel == 0) {
         bool handled = false;
         rc = match_small(a, d, haystack, n_units, record_kind, out, cap, n_out, &handled);
         if (rc != ACGPU_OK || handled) return rc;
     }
+    if (tunables().tile_debug & kSelOnlySmallCall) return ACGPU_E_UNSUPPORTED;
     // long haystacks: the pipelined form, unless the text is one piece (the loops that only exist as a sequential kernel over
     // the whole text -- WholeWord / WholeWordLongestSet with a fold-inconsistent table -- take the plain one)
     if (n_units >= 2 * kHostChunkUnits && !host_one_piece(t, record_kind) && d.inflight == 0 && !(tunables().tile_debug & kSelNoHostChunks)) {

@@ -131,6 +131,7 @@ enum TileSelect : uint64_t {
     kSelNoSmallCall = 1ull << 41,    // a short host text through the enqueued pipeline, not the one-launch form
     kSelStreamTrace = 1ull << 42,    // acgpu_stream: where a feed's time goes, on stderr (development)
     kSelDfaOneChain = 1ull << 43,    // the dense DFA scan: the one-chain kernel (A/B)
+    kSelOnlySmallCall = 1ull << 44,  // a short host text the one-launch form does not answer itself: ACGPU_E_UNSUPPORTED (tests)
     kSelDfaNoGlobal = 1ull << 45,    // the dense DFA scan, ablation build: no lookups in global memory (ScanLaunch::debug bit 4)
 };
 // (the form: choose_tile_form, with l.region_units and l.debug set; l.lds_bytes is the form's)
