@@ -1,4 +1,4 @@
-// acgpu_host.h -- host-side state shared by the C ABI glue (acgpu_api.hip) and the multi-device driver (acgpu_multi.hip):
+// acgpu_host.h -- host-side state shared by the units of the C ABI (acgpu_call.hip and the entries around it; acgpu_multi.hip):
 // grow-only device buffers, tickets, the per-automaton per-device scratch pool, the automaton handle.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -95,7 +95,7 @@ using Pinned = Handle<T *, hipHostFree>;
 using PoolEvent = Handle<hipEvent_t, hipEventDestroy>;
 using PoolStream = Handle<hipStream_t, hipStreamDestroy>;
 
-// How a call's result is collected (collect(), acgpu_api.hip): the pipeline that was enqueued.
+// How a call's result is collected (collect(), acgpu_call.hip): the pipeline that was enqueued.
 enum class CallForm : uint8_t {
     Complete,      // the empty call: nothing found, nothing to report
     HostRun,       // ran to its end on the host (the families that need the host between their launches): count and chain exit in the slot
@@ -137,7 +137,7 @@ struct CallRecord {
     unsigned long long *h_slot = nullptr; // pinned, 64 bytes: kSlotCount, kSlotFlag, kSlotExit
     CallForm form = CallForm::Complete;
     int level = 0;                     // ALL: 1 = the redo's form (the fused kernel, one scratch slice); LONGEST: the run-up level
-    bool folded = false;               // WHOLEWORD: the scan saw the folded tables (folded_tables, acgpu_api.hip)
+    bool folded = false;               // WHOLEWORD: the scan saw the folded tables (folded_tables, acgpu_tables.hip)
     bool counting = false;             // a shard call of acgpu_count_*: collect() hands its result to the pool's CountCall
     uint64_t scanned = 0;
     char kname[64] = {0};
@@ -289,6 +289,10 @@ struct StreamBufs {
 };
 } // namespace acgpu
 
+// what acgpu_free does with the streams and cursors still open on an automaton (open_streams, open_cursors below)
+extern "C" void acgpu_stream_detach(acgpu_stream *s); // acgpu_stream.hip
+extern "C" void acgpu_cursor_detach(acgpu_cursor *c); // acgpu_cursor.hip
+
 struct acgpu_automaton {
     acgpu::HostTables t;
     std::vector<acgpu::StreamBufs> stream_cache;                                 // guarded by mu
@@ -301,7 +305,7 @@ struct acgpu_automaton {
 
 namespace acgpu {
 
-// How a text is cut into shards for one call (shard_rule, acgpu_api.hip): the facts of the automaton's family that every host
+// How a text is cut into shards for one call (shard_rule, acgpu_call.hip): the facts of the automaton's family that every host
 // entry which scans a text piece by piece needs.
 enum class Chain : uint8_t {
     None,     // ALL, WHOLEWORD: nothing passes from piece to piece
@@ -366,7 +370,7 @@ int begin_shard(acgpu_automaton *a, DeviceState &d, acgpu_shard *sh, int record_
 // result were written a second time, AFTER whatever the caller had enqueued behind the first attempt.
 int end_ticket(const acgpu_automaton *a, acgpu_ticket *ticket, uint64_t *n_out, acgpu_profile *prof, bool *redone);
 
-// acgpu_match_u16 on a long haystack, pipelined over chunks (acgpu_api.hip): the units [lo, hi) of `haystack` become the
+// acgpu_match_u16 on a long haystack, pipelined over chunks (acgpu_hosttext.hip): the units [lo, hi) of `haystack` become the
 // device buffer d.stage_hay (buffer unit 0 = unit lo), the owned range [own_lo, own_hi) is scanned as shards of it on
 // d.call_stream, the records (buffer relative) land in d.stage_out -- or in d_out, a device buffer of cap records, when it is
 // given.  chain: in = entry, out = exit (buffer relative).

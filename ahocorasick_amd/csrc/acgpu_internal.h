@@ -365,46 +365,51 @@ struct DevTables {
     uint32_t hy_n_dense, hy_n_states;
 };
 
-// development/test knobs (acgpu_set_tunable): relaxed atomics, read when a call is enqueued
-struct Tunables {
-    std::atomic<int64_t> chunk_units{0};      // 0 = auto
-    std::atomic<int64_t> blocks_per_cu{1};
-    std::atomic<int64_t> lds_table_bytes{127 * 1024};
-    std::atomic<int64_t> force_sparse{0};
-    std::atomic<int64_t> dense_budget_bytes{1ll << 30};
-    std::atomic<int64_t> force_kernel{0};     // 0 auto, 1 = DFA chunk scan, 2 = k-gram tile scan (when the filter exists)
-    std::atomic<int64_t> region_units{0};     // tile kernel: owned units per wave region (0 = auto)
-    std::atomic<int64_t> rdense_budget_bytes{256ll << 20};
-    std::atomic<int64_t> tile_debug{0};       // ablation switches of the tile kernel (see TileLaunch::debug); 0 in production
+// development/test knobs (acgpu_set_tunable): relaxed atomics, read when a call is enqueued.  Every knob stands here once, as
+// X(name, default): the members of struct Tunables and the names acgpu_set_tunable knows both come from this list.
 #ifndef ACGPU_FILTER_MAX_BYTES
 #define ACGPU_FILTER_MAX_BYTES 88000
 #endif
-    std::atomic<int64_t> filter_max_bytes{ACGPU_FILTER_MAX_BYTES};  // the filter rows must fit LDS next to the candidate queues
-    std::atomic<int64_t> no_short_keywords{0}; // builder: 1 = the filter's K stays at most the shortest keyword (A/B)
-    std::atomic<int64_t> no_merged_ranges{0}; // builder: 1 = mixed-case dictionaries keep the 8-byte-row scalar filter (A/B)
-    std::atomic<int64_t> ww_block{0};         // k_ww_pp, fused tail: threads per workgroup (0 = 1024; a multiple of 64 -- two workgroups share a CU when their LDS allows: A/B)
-    std::atomic<int64_t> ww_ramp_pm{-1};      // k_ww_pp, fused tail: the spans' ramp in thousandths of the average span (-1 = the default)
-    std::atomic<int64_t> ww_no_byte_pages{0}; // WHOLEWORD builder: 1 = no combined word-bit / fold pages (A/B, tests)
-    std::atomic<int64_t> ww_no_ph{0};         // WHOLEWORD builder: 1 = no perfect hash (the two-choice table behind the Bloom filter: A/B, tests)
-    std::atomic<int64_t> ww_ph_lambda{0};     // WHOLEWORD builder: keywords per bucket of the perfect hash (0 = 4; tests: large buckets, many displacements tried)
-    std::atomic<int64_t> ww_no_bloom{0};      // WHOLEWORD builder: 1 = no Bloom filter in front of the keyword table (every run of keyword length probes it)
-    std::atomic<int64_t> ww_first_seed{0};    // WHOLEWORD builder: first hash seed tried (tests: the fallback seeds end to end)
-    std::atomic<int64_t> split_cand_div{8};   // split form: a wave's candidate slice holds one candidate per this many units of its span
-    std::atomic<int64_t> no_class_pages{0};   // builder: 1 = the tile kernel's LUT forms look classes up in global memory (A/B)
-    std::atomic<int64_t> no_big_l2{0};        // builder: 1 = large dictionaries keep the (saturated) second level in LDS (A/B)
-    std::atomic<int64_t> multi_min_share{1ll << 22}; // acgpu_match_u16_multi: a share is at least this many units (tests: 1024)
-    std::atomic<int64_t> longest_form{0};     // LONGEST, bits: 1 = never k_longest_bits, 2 = never k_longest_follow, 4 = both also for short texts (tests, A/B)
-    std::atomic<int64_t> all_form{0};         // ALL, bits: 1 = never k_ac_states, 2 = always (where its tables exist), 4 = also for short texts (tests, A/B)
-    std::atomic<int64_t> no_state_form{0};    // builder: 1 = no compact automaton for k_ac_states (A/B)
-    std::atomic<int64_t> no_bits_trie{0};     // builder: 1 = no path-compressed trie for k_longest_bits (the walk pipeline instead: A/B)
-    std::atomic<int64_t> reserve_cus{0};      // CUs left without a scan workgroup (room for a collective's kernels under the scan)
-    std::atomic<int64_t> tile_form{0};        // ALL, tile kernel, bits: 1 = never the fused tail (a finalize launch behind the scan: tests, A/B)
-    std::atomic<int64_t> cursor_first_piece{1ll << 20};      // acgpu_cursor: owned units of the first piece
-    std::atomic<int64_t> cursor_max_piece{1ll << 26};        // acgpu_cursor: owned units of the largest piece
-    std::atomic<int64_t> cursor_reservoir_bytes{256ll << 20}; // acgpu_cursor: largest device reservoir of one piece's records
-    std::atomic<int64_t> states_chunk_log2{0};  // k_ac_states: a lane's chunk, 0 = by the text's length, 8 .. 10 = forced (tests: 1 to 4 steps per chunk on short texts)
-    std::atomic<int64_t> replace_slab_units{1ll << 25}; // acgpu_replace_u16: units of one of the two device slabs the result leaves through
-    std::atomic<int64_t> count_form{0};         // acgpu_count_*, bits: 1 = never the direct form, 2 = no LDS counters in k_states_hist, 4 = no same-key peel (A/B)
+#define ACGPU_TUNABLES(X) \
+    X(chunk_units, 0) /* 0 = auto */ \
+    X(blocks_per_cu, 1) \
+    X(lds_table_bytes, 127 * 1024) \
+    X(force_sparse, 0) \
+    X(dense_budget_bytes, 1ll << 30) \
+    X(force_kernel, 0) /* 0 auto, 1 = DFA chunk scan, 2 = k-gram tile scan (when the filter exists) */ \
+    X(region_units, 0) /* tile kernel: owned units per wave region (0 = auto) */ \
+    X(rdense_budget_bytes, 256ll << 20) \
+    X(tile_debug, 0) /* ablation switches of the tile kernel (see TileLaunch::debug); 0 in production */ \
+    X(filter_max_bytes, ACGPU_FILTER_MAX_BYTES) /* the filter rows must fit LDS next to the candidate queues */ \
+    X(no_short_keywords, 0) /* builder: 1 = the filter's K stays at most the shortest keyword (A/B) */ \
+    X(no_merged_ranges, 0) /* builder: 1 = mixed-case dictionaries keep the 8-byte-row scalar filter (A/B) */ \
+    X(ww_block, 0) /* k_ww_pp, fused tail: threads per workgroup (0 = 1024; a multiple of 64 -- two workgroups share a CU when their LDS allows: A/B) */ \
+    X(ww_ramp_pm, -1) /* k_ww_pp, fused tail: the spans' ramp in thousandths of the average span (-1 = the default) */ \
+    X(ww_no_byte_pages, 0) /* WHOLEWORD builder: 1 = no combined word-bit / fold pages (A/B, tests) */ \
+    X(ww_no_ph, 0) /* WHOLEWORD builder: 1 = no perfect hash (the two-choice table behind the Bloom filter: A/B, tests) */ \
+    X(ww_ph_lambda, 0) /* WHOLEWORD builder: keywords per bucket of the perfect hash (0 = 4; tests: large buckets, many displacements tried) */ \
+    X(ww_no_bloom, 0) /* WHOLEWORD builder: 1 = no Bloom filter in front of the keyword table (every run of keyword length probes it) */ \
+    X(ww_first_seed, 0) /* WHOLEWORD builder: first hash seed tried (tests: the fallback seeds end to end) */ \
+    X(split_cand_div, 8) /* split form: a wave's candidate slice holds one candidate per this many units of its span */ \
+    X(no_class_pages, 0) /* builder: 1 = the tile kernel's LUT forms look classes up in global memory (A/B) */ \
+    X(no_big_l2, 0) /* builder: 1 = large dictionaries keep the (saturated) second level in LDS (A/B) */ \
+    X(multi_min_share, 1ll << 22) /* acgpu_match_u16_multi: a share is at least this many units (tests: 1024) */ \
+    X(longest_form, 0) /* LONGEST, bits: 1 = never k_longest_bits, 2 = never k_longest_follow, 4 = both also for short texts (tests, A/B) */ \
+    X(all_form, 0) /* ALL, bits: 1 = never k_ac_states, 2 = always (where its tables exist), 4 = also for short texts (tests, A/B) */ \
+    X(no_state_form, 0) /* builder: 1 = no compact automaton for k_ac_states (A/B) */ \
+    X(no_bits_trie, 0) /* builder: 1 = no path-compressed trie for k_longest_bits (the walk pipeline instead: A/B) */ \
+    X(reserve_cus, 0) /* CUs left without a scan workgroup (room for a collective's kernels under the scan) */ \
+    X(tile_form, 0) /* ALL, tile kernel, bits: 1 = never the fused tail (a finalize launch behind the scan: tests, A/B) */ \
+    X(cursor_first_piece, 1ll << 20) /* acgpu_cursor: owned units of the first piece */ \
+    X(cursor_max_piece, 1ll << 26) /* acgpu_cursor: owned units of the largest piece */ \
+    X(cursor_reservoir_bytes, 256ll << 20) /* acgpu_cursor: largest device reservoir of one piece's records */ \
+    X(states_chunk_log2, 0) /* k_ac_states: a lane's chunk, 0 = by the text's length, 8 .. 10 = forced (tests: 1 to 4 steps per chunk on short texts) */ \
+    X(replace_slab_units, 1ll << 25) /* acgpu_replace_u16: units of one of the two device slabs the result leaves through */ \
+    X(count_form, 0) /* acgpu_count_*, bits: 1 = never the direct form, 2 = no LDS counters in k_states_hist, 4 = no same-key peel (A/B) */
+struct Tunables {
+#define ACGPU_TUNABLE_MEMBER(name, dflt) std::atomic<int64_t> name{dflt};
+    ACGPU_TUNABLES(ACGPU_TUNABLE_MEMBER)
+#undef ACGPU_TUNABLE_MEMBER
 };
 Tunables &tunables();
 

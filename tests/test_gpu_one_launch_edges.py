@@ -1,5 +1,5 @@
 """GPU tests of the one-launch form of acgpu_match_u16 (k_small<MODE>, csrc/acgpu_small.hip; the gate in match_host_text,
-csrc/acgpu_api.hip) at the edges of its lists, every record against the CPU oracle, bit for bit.  The inputs and the proof that each
+csrc/acgpu_hosttext.hip) at the edges of its lists, every record against the CPU oracle, bit for bit.  The inputs and the proof that each
 reaches its edge are tests/small_edges.py (checked without a device by tests/test_one_launch_inputs_cpu.py):
 
   a. `m > kSmallMaxRecs` at 4095, 4096 and 4097 occurrences, ALL and SHORTEST; the counting sort with `recs` and `sorted` full;

@@ -1,5 +1,5 @@
 """GPU tests of WholeWordLongestMatchSet/Map at the edges of its own kernels (csrc/acgpu_wwlongest.hip, driven by run_wwlongest in
-csrc/acgpu_api.hip), every record against the CPU oracle, bit for bit:
+csrc/acgpu_hostrun.hip), every record against the CPU oracle, bit for bit:
 
   1. k_wwl_walk's first-word table (`T.ww_fat && ws + 16 <= n`, `r >= 1 && r <= kWwInlineUnits`) on both sides of 12 units;
   2. k_wwl_walk's last 15 units of the buffer (`have < 8`, `at_end`), a text cut at every distance from its last walk start;
