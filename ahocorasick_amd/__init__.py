@@ -9,8 +9,9 @@ from .strings import (AhoCorasickMap, AhoCorasickSet, Automaton, IllegalArgument
                       Utf8Error, utf8_line_offsets, utf8_unit_offsets, utf16)
 from . import terms
 from .terms import count_batch, count_batch_utf8
+from .spans import spans, spans_device, spans_utf8  # (the name `spans` of this package is the function; the module: ahocorasick_amd.spans in sys.modules)
 
 __all__ = ["AhoCorasickSet", "AhoCorasickMap", "LongestMatchSet", "LongestMatchMap", "WholeWordMatchSet",
            "WholeWordMatchMap", "ShortestMatchSet", "ShortestMatchMap", "WholeWordLongestMatchSet", "WholeWordLongestMatchMap", "StringSet", "StringMap", "SetMatchListener", "MapMatchListener", "ReadableMatchListener", "Stream", "Automaton",
            "IllegalArgumentException", "utf16", "Utf8Error", "utf8_unit_offsets", "utf8_line_offsets",
-           "terms", "count_batch", "count_batch_utf8"]
+           "terms", "count_batch", "count_batch_utf8", "spans", "spans_utf8", "spans_device"]

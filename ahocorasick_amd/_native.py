@@ -96,6 +96,12 @@ class CountBatchStats(ctypes.Structure):  # acgpu_count_batch_stats
                 ("rescans", ctypes.c_uint32), ("rows_cut", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class SpansStats(ctypes.Structure):  # acgpu_spans_stats
+    _fields_ = [("n_records", ctypes.c_uint64), ("n_spans", ctypes.c_uint64), ("pieces", ctypes.c_uint32), ("rescans", ctypes.c_uint32),
+                ("max_carry", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+SPAN_TILE = 2048  # kSpanTile (csrc/acgpu_spans.hip): the intervals a workgroup of the merge's scans takes
 TERMS_BLOCK = 2048  # kTermsBlock (csrc/acgpu_terms.hip): the records a workgroup of k_terms_block sorts and reduces
 
 
@@ -186,6 +192,9 @@ def _signatures():
         "acgpu_debug_count_batch_finish": (ci, [vp, u64, u32, vp, vp, vp, P(u64), P(u32)]),
         "acgpu_replace_utf8": (ci, [vp, vp, u64, vp, vp, u32, vp, u64, P(u64), P(ReplaceStats), P(Utf8Stats)]),
         "acgpu_replace_batch_utf8": (ci, [vp, vp, vp, u32, vp, vp, u32, vp, u64, vp, P(u64), P(ReplaceStats), P(Utf8BatchStats)]),
+        "acgpu_spans_u16": (ci, [vp, vp, u64, vp, u64, P(u64), P(SpansStats)]),
+        "acgpu_spans_device": (ci, [vp, P(Shard), vp, u64, P(u64), vp, P(SpansStats)]),
+        "acgpu_spans_utf8": (ci, [vp, vp, u64, vp, u64, P(u64), P(SpansStats), P(Utf8Stats)]),
         "acgpu_match_u16_multi": (ci, [vp, vp, u64, P(ci), ci, ci, vp, u64, P(u64)]),
         "acgpu_comm_open": (ci, [P(ci), ci, ci, P(vp)]),
         "acgpu_comm_close": (None, [vp]),

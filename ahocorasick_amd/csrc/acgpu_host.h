@@ -49,10 +49,15 @@ struct DevBuf {
 
 // A device buffer whose capacity is kept in records (the cursor's and the counting calls' reservoir): grow-only, and exactly
 // what was asked for plus 64 bytes of slack -- the tunable "cursor_reservoir_bytes" bounds what the callers ask for.
+// The capacity is in records of the kind it was last asked for (kind = the record's bytes): the pool's reservoir holds Map records
+// for one call and Set records for the next (acgpu_spans.hip), and what is there is counted anew in the kind that is asked for.
 struct Reservoir {
     void *p = nullptr;
     uint64_t recs = 0;
+    uint64_t kind = 0; // bytes of the records `recs` counts
     int ensure(uint64_t need, uint64_t record_bytes) {
+        if (kind && kind != record_bytes) recs = recs * kind / record_bytes;
+        kind = record_bytes;
         if (need <= recs) return ACGPU_OK;
         release();
         HIP_TRY(hipMalloc(&p, need * record_bytes + 64));
@@ -229,7 +234,9 @@ struct DeviceState {
     PoolBuf replace_merged, replace_off;                  // acgpu_replace_batch_u16: a piece's records merged with its separators, the result's offsets (acgpu_replace_batch_utf8's too)
     PoolBuf summary;                                      // acgpu_summary_batch_u16: 24 bytes per haystack, {records, the first of them}
     PoolBuf terms_entries, terms_stage, terms_aux, terms_count; // acgpu_count_batch_*: the call's entry list {h, id, count}, a piece's entries block by block, {block_base, n_distinct} per block, the running entry count (acgpu_terms.hip)
-    PoolBuf utf8_in, utf8_aux;                            // the UTF-8 entries: the caller's bytes; {n_units, first_bad, tail, n_replaced}, block sums, checkpoints, a batch's byte offsets, a lossy text's start bitmap (Utf8Aux, acgpu_utf8.hip)
+    PoolBuf spans_work, spans_carry, spans_out;        // acgpu_spans_*: {n_final, n_carry, bound} and the tiles' minima and counts, the two carry buffers, the host entry's final spans of a piece (acgpu_spans.hip)
+    Pinned<> spans_pin;                                   // ... 64 bytes: a piece's {n_final, n_carry}
+    PoolBuf utf8_in, utf8_aux;                          // the UTF-8 entries: the caller's bytes; {n_units, first_bad, tail, n_replaced}, block sums, checkpoints, a batch's byte offsets, a lossy text's start bitmap (Utf8Aux, acgpu_utf8.hip)
     CountCall *count = nullptr;                          // the counting call that runs on this pool (it holds mu), or nullptr
     double all_density = -1.0;                           // ALL: records per unit of this pool's last call (-1: none yet): k_ac_states or the tile kernel
     int fol_level = 0;                                   // k_longest_follow: 0 = run-up of 128 positions, 1 = of a whole segment (a call's chains had not merged), 2 = not for this pool's texts
@@ -557,8 +564,9 @@ struct BatchText {
     int stage(const uint16_t *units, const uint64_t *offsets, uint32_t n, hipStream_t stream);
 };
 
-// A text on its way through a reservoir, piece by piece (scan_next_piece, acgpu_pieces.hip).  Five consumers: the cursor keeps
-// one from page call to page call; a counting, a replace, a batch summary and a count-batch call have one for each text they drive.
+// A text on its way through a reservoir, piece by piece (scan_next_piece, acgpu_pieces.hip).  Six consumers: the cursor keeps
+// one from page call to page call; a counting, a replace, a batch summary, a count-batch and a spans call have one for each text
+// they drive.
 struct PieceDriver {
     uint64_t pos = 0, end = 0;         // the owned units [pos, end) have not been scanned yet
     int64_t chain = 0;                 // the chain's entry into the next piece (the text's coordinates)

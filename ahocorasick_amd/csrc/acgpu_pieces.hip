@@ -1,7 +1,7 @@
 // acgpu_pieces.hip -- how a text is scanned piece by piece into a record reservoir of bounded size: the sizes of the pieces
-// (PieceRamp), the reservoir's budget, and the ONE driver (scan_next_piece) behind its five consumers: the cursor
+// (PieceRamp), the reservoir's budget, and the ONE driver (scan_next_piece) behind its six consumers: the cursor
 // (acgpu_cursor.hip), the counting entries (acgpu_count.hip), the replace entries (acgpu_replace.hip), the batch summary
-// (acgpu_summary.hip) and the batch counts per haystack (acgpu_terms.hip).
+// (acgpu_summary.hip), the batch counts per haystack (acgpu_terms.hip) and the spans entries (acgpu_spans.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -1139,6 +1139,55 @@ int acgpu_stream_replace_utf8_lossy(acgpu_stream *s, const uint8_t *bytes, uint6
                                     acgpu_utf8_lossy_stream_stats *ust /* may be NULL */, acgpu_replace_stats *st /* may be NULL */);
 
 /*
+ * Spans: which parts of a text are covered by a match -- the records of a text merged into covered runs on the device, for ALL
+ * FIVE families (ACGPU_MODE_ALL included: the answer the replace entries refuse it).  With R the Set records acgpu_match_u16
+ * returns for the same automaton and text, the SPANS are the maximal runs of consecutive positions p with s <= p < e for some
+ * record {s, e} of R: ascending, each {start, end} as two int32 (the layout of ACGPU_REC_SET).  Overlapping, nested AND touching
+ * records fall into one span -- [1,5) and [5,8) give [1,8) -- so two consecutive spans have at least one uncovered position
+ * between them.  The records of the four non-overlapping families can touch, so their spans are not their records either.
+ *  cap, *n_out : in SPANS.  More than cap spans: ACGPU_E_OVERFLOW with *n_out (and st->n_spans) the exact number; out[0 .. cap)
+ *              then holds the first cap spans and nothing at or beyond cap has been written (the rest of the text is still
+ *              scanned and merged, for the number).  The same call with cap = *n_out succeeds.
+ *  st        : may be NULL.
+ *  acgpu_spans_u16    : haystack in HOST memory, n_units < 2^31; `out` is host memory.  Without a device it fails as
+ *              acgpu_match_u16 does and leaves `out` untouched.  Works on the NULL stream (STREAM RULE above), under the pool's lock.
+ *  acgpu_spans_device : the shard must be a WHOLE text (own_begin == 0, own_end == n_units, text_begin == text_end == 1), else
+ *              ACGPU_E_UNSUPPORTED: one shard of a sharded text would have to hand the spans it withholds to the rank behind it,
+ *              which is not built.  d_out: device memory, 16-byte aligned, written directly (clipped at cap).  Everything is
+ *              enqueued on `stream`; the call waits for it per piece -- for the piece's record count and for its span count --
+ *              and once at the end.
+ *  acgpu_spans_utf8 / acgpu_spans_utf8_lossy : the spans of the records acgpu_match_utf8 / acgpu_match_utf8_lossy returns, in BYTE
+ *              offsets of the caller's buffer; n_bytes < 2^31; ust and ACGPU_E_ENCODING as for those entries.  An empty text:
+ *              ACGPU_OK, *n_out = 0, no device needed.  Keywords that hold an unpaired surrogate are accepted (their widened
+ *              records may overlap in bytes, which a merge does not mind).
+ * How it works: the text is cut into pieces as a cursor's are (the same ramp and rescan rules); a piece's Set records go to the
+ * pool's reservoir, and five small launches behind the piece merge them -- a suffix minimum of the starts finds where a span
+ * begins, a prefix count gives the span its index, the first and the last interval of a span write its two words (no atomics,
+ * the result is deterministic).  A piece delivers the spans that end before a position no later record starts at or before; the
+ * others -- at most max_keyword_len / 2 + 2 of them -- wait on the device for the next piece (st->max_carry: the most that did).
+ * Scratch, per automaton and device: the reservoir the counting and replace calls use, 12 bytes per 2048 records of a piece, the
+ * carry, and for the host entries 8 bytes per span of a piece.  The host reads 16 bytes per piece.
+ * Not built: mask, highlight and replace for ACGPU_MODE_ALL on top of spans; a record-free form for ACGPU_MODE_ALL from the
+ * state words of k_ac_states (the analogue of the counting calls' direct form); batch, stream and multi-device forms; the Java
+ * facade.  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
+ */
+typedef struct acgpu_spans_stats {
+    uint64_t n_records;       /* records merged == records the Set match call returns                        */
+    uint64_t n_spans;         /* spans of the text (exact, also on ACGPU_E_OVERFLOW)                         */
+    uint32_t pieces, rescans; /* as acgpu_count_stats                                                        */
+    uint32_t max_carry;       /* the largest number of spans a piece withheld for the next one               */
+    uint32_t reserved;
+} acgpu_spans_stats;   /* 32 bytes */
+int acgpu_spans_u16(const acgpu_automaton *a, const uint16_t *haystack, uint64_t n_units, int32_t *out, uint64_t cap, uint64_t *n_out,
+                    acgpu_spans_stats *st);
+int acgpu_spans_device(const acgpu_automaton *a, acgpu_shard *shard, int32_t *d_out, uint64_t cap, uint64_t *n_out, void *stream,
+                       acgpu_spans_stats *st);
+int acgpu_spans_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, int32_t *out, uint64_t cap, uint64_t *n_out,
+                     acgpu_spans_stats *st, acgpu_utf8_stats *ust /* may be NULL */);
+int acgpu_spans_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, int32_t *out, uint64_t cap, uint64_t *n_out,
+                           acgpu_spans_stats *st, acgpu_utf8_lossy_stats *ust /* may be NULL */);
+
+/*
  * Synthetic haystack generator of the benchmark: unit i of the stream is
  * table[((z_i >> 32) * table_len) >> 32] with z_i = SplitMix64 output for counter
  * start_index + i of `seed` (see ahocorasick_amd/synth.py).  d_dst: device pointer.
