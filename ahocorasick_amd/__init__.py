@@ -10,8 +10,10 @@ from .strings import (AhoCorasickMap, AhoCorasickSet, Automaton, IllegalArgument
 from . import terms
 from .terms import count_batch, count_batch_utf8
 from .spans import spans, spans_device, spans_utf8  # (the name `spans` of this package is the function; the module: ahocorasick_amd.spans in sys.modules)
+from .cover import cover, cover_device, cover_utf8, highlight, highlight_utf8, mask, mask_utf8, redact, redact_utf8  # (as for spans: the name `cover` is the function)
 
 __all__ = ["AhoCorasickSet", "AhoCorasickMap", "LongestMatchSet", "LongestMatchMap", "WholeWordMatchSet",
            "WholeWordMatchMap", "ShortestMatchSet", "ShortestMatchMap", "WholeWordLongestMatchSet", "WholeWordLongestMatchMap", "StringSet", "StringMap", "SetMatchListener", "MapMatchListener", "ReadableMatchListener", "Stream", "Automaton",
            "IllegalArgumentException", "utf16", "Utf8Error", "utf8_unit_offsets", "utf8_line_offsets",
-           "terms", "count_batch", "count_batch_utf8", "spans", "spans_utf8", "spans_device"]
+           "terms", "count_batch", "count_batch_utf8", "spans", "spans_utf8", "spans_device",
+           "cover", "cover_utf8", "cover_device", "mask", "mask_utf8", "highlight", "highlight_utf8", "redact", "redact_utf8"]

@@ -101,6 +101,19 @@ class SpansStats(ctypes.Structure):  # acgpu_spans_stats
                 ("max_carry", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class CoverSpec(ctypes.Structure):  # acgpu_cover_spec
+    _fields_ = [("open", ctypes.c_void_p), ("open_len", ctypes.c_uint32), ("close", ctypes.c_void_p), ("close_len", ctypes.c_uint32),
+                ("body", ctypes.c_uint32), ("fill", ctypes.c_uint32)]
+
+
+class CoverStats(ctypes.Structure):  # acgpu_cover_stats
+    _fields_ = [("n_records", ctypes.c_uint64), ("n_spans", ctypes.c_uint64), ("units_out", ctypes.c_uint64), ("pieces", ctypes.c_uint32),
+                ("rescans", ctypes.c_uint32), ("max_carry", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+COVER_KEEP, COVER_FILL, COVER_DROP = 0, 1, 2
+COVER_TILE_UNITS, COVER_TILE_BYTES = 2048, 4096  # kEmitTile (csrc/acgpu_emit.h): the output elements a workgroup of k_cover_emit writes
+COVER_LDS_SEGMENTS = 1536  # kCoverLds (csrc/acgpu_cover.hip): the segments of a tile k_cover_emit stages in LDS at most; tunable "cover_lds_segments"
 SPAN_TILE = 2048  # kSpanTile (csrc/acgpu_spans.hip): the intervals a workgroup of the merge's scans takes
 TERMS_BLOCK = 2048  # kTermsBlock (csrc/acgpu_terms.hip): the records a workgroup of k_terms_block sorts and reduces
 
@@ -195,6 +208,9 @@ def _signatures():
         "acgpu_spans_u16": (ci, [vp, vp, u64, vp, u64, P(u64), P(SpansStats)]),
         "acgpu_spans_device": (ci, [vp, P(Shard), vp, u64, P(u64), vp, P(SpansStats)]),
         "acgpu_spans_utf8": (ci, [vp, vp, u64, vp, u64, P(u64), P(SpansStats), P(Utf8Stats)]),
+        "acgpu_cover_u16": (ci, [vp, vp, u64, P(CoverSpec), vp, u64, P(u64), P(CoverStats)]),
+        "acgpu_cover_device": (ci, [vp, P(Shard), P(CoverSpec), vp, u64, P(u64), vp, P(CoverStats)]),
+        "acgpu_cover_utf8": (ci, [vp, vp, u64, P(CoverSpec), vp, u64, P(u64), P(CoverStats), P(Utf8Stats)]),
         "acgpu_match_u16_multi": (ci, [vp, vp, u64, P(ci), ci, ci, vp, u64, P(u64)]),
         "acgpu_comm_open": (ci, [P(ci), ci, ci, P(vp)]),
         "acgpu_comm_close": (None, [vp]),

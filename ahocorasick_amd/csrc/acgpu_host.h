@@ -235,7 +235,8 @@ struct DeviceState {
     PoolBuf summary;                                      // acgpu_summary_batch_u16: 24 bytes per haystack, {records, the first of them}
     PoolBuf terms_entries, terms_stage, terms_aux, terms_count; // acgpu_count_batch_*: the call's entry list {h, id, count}, a piece's entries block by block, {block_base, n_distinct} per block, the running entry count (acgpu_terms.hip)
     PoolBuf spans_work, spans_carry, spans_out;        // acgpu_spans_*: {n_final, n_carry, bound} and the tiles' minima and counts, the two carry buffers, the host entry's final spans of a piece (acgpu_spans.hip)
-    Pinned<> spans_pin;                                   // ... 64 bytes: a piece's {n_final, n_carry}
+    Pinned<> spans_pin;                                   // ... 64 bytes: a piece's {n_final, n_carry} and, for a cover call, the rest of the head (acgpu_spans.h)
+    PoolBuf cover_spans, cover_tab, cover_plan;           // acgpu_cover_*: a piece's spans, the call's open and close elements, a DROP call's plan {sums, output positions} (acgpu_cover.hip)
     PoolBuf utf8_in, utf8_aux;                          // the UTF-8 entries: the caller's bytes; {n_units, first_bad, tail, n_replaced}, block sums, checkpoints, a batch's byte offsets, a lossy text's start bitmap (Utf8Aux, acgpu_utf8.hip)
     CountCall *count = nullptr;                          // the counting call that runs on this pool (it holds mu), or nullptr
     double all_density = -1.0;                           // ALL: records per unit of this pool's last call (-1: none yet): k_ac_states or the tile kernel

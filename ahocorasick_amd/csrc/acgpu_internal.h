@@ -405,7 +405,8 @@ struct DevTables {
     X(cursor_reservoir_bytes, 256ll << 20) /* acgpu_cursor: largest device reservoir of one piece's records */ \
     X(states_chunk_log2, 0) /* k_ac_states: a lane's chunk, 0 = by the text's length, 8 .. 10 = forced (tests: 1 to 4 steps per chunk on short texts) */ \
     X(replace_slab_units, 1ll << 25) /* acgpu_replace_u16: units of one of the two device slabs the result leaves through */ \
-    X(count_form, 0) /* acgpu_count_*, bits: 1 = never the direct form, 2 = no LDS counters in k_states_hist, 4 = no same-key peel (A/B) */
+    X(count_form, 0) /* acgpu_count_*, bits: 1 = never the direct form, 2 = no LDS counters in k_states_hist, 4 = no same-key peel (A/B) */ \
+    X(cover_lds_segments, 1536) /* k_cover_emit: segments of a tile staged in LDS at most (0 .. 1536; tests: 0 = every tile through global memory) */
 struct Tunables {
 #define ACGPU_TUNABLE_MEMBER(name, dflt) std::atomic<int64_t> name{dflt};
     ACGPU_TUNABLES(ACGPU_TUNABLE_MEMBER)

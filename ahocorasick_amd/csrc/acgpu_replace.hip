@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "acgpu_device.h"
+#include "acgpu_emit.h"
 #include "acgpu_host.h"
 #include "acgpu_internal.h"
 
@@ -38,19 +39,11 @@ using namespace acgpu;
 
 namespace {
 
-typedef uint32_t rp_v4u __attribute__((ext_vector_type(4)));
-
-constexpr int kPlanBlock = 256, kPlanPer = 8, kPlanTile = kPlanBlock * kPlanPer; // records per workgroup of the plan
-constexpr int kEmitBlock = 256;                                                  // lanes of a workgroup of the emit: one 16-byte store each
 constexpr int kEmitLds = 3072;                                                   // segments a workgroup stages (16 bytes each)
 constexpr int kPlanHead = 4; // words in front of the plan's sums: {sum of the deltas, last end, the piece's boundary in bytes (UTF-8), unused}
 
-// An output ELEMENT is what the text is made of as the caller sees it: a UTF-16 unit (T = uint16_t), or a byte of a UTF-8 text
-// (T = uint8_t).  Records, the table's entries, the plan and the windows count elements; "unit" below means element.
-template <class T>
-constexpr int kEmitPer = 16 / (int)sizeof(T); // elements of a lane's store: 8 units or 16 bytes
-template <class T>
-constexpr int kEmitTile = kEmitBlock * kEmitPer<T>; // ... of a workgroup: 2048 units or 4096 bytes
+// (the tile shape, kEmitPer<T> and kEmitTile<T>, load16, last_at_or_before and plan_block_scan: acgpu_emit.h.  Records, the table's
+// entries, the plan and the windows count elements; "unit" below means element.)
 
 // The replacement table on the device: n_repl entries {first unit in `units`, length}, then the units.
 struct ReplTable {
@@ -67,22 +60,6 @@ __device__ __forceinline__ uint2 repl_of(const ReplTable &rt, int32_t id) {
 __device__ __forceinline__ int64_t repl_delta(const int32_t *recs, uint64_t i, const ReplTable &rt) {
     const int32_t s = recs[3 * i], e = recs[3 * i + 1], id = recs[3 * i + 2];
     return (int64_t)repl_of(rt, id).y - (int64_t)(e - s);
-}
-
-__device__ __forceinline__ int64_t plan_block_scan(int64_t v, int64_t *total) { // exclusive, kPlanBlock threads
-    __shared__ int64_t wsum[kPlanBlock / kWave];
-    const int64_t inc = wave_inclusive_scan(v);
-    const int w = threadIdx.x / kWave;
-    if (lane_id() == kWave - 1) wsum[w] = inc;
-    __syncthreads();
-    int64_t base = 0, all = 0;
-    for (int i = 0; i < kPlanBlock / kWave; ++i) {
-        if (i < w) base += wsum[i];
-        all += wsum[i];
-    }
-    *total = all;
-    __syncthreads();
-    return base + inc - v;
 }
 
 // plan, level 1: the sum of the deltas of every workgroup's kPlanTile records (a thread takes kPlanPer consecutive ones)
@@ -134,17 +111,6 @@ __global__ __launch_bounds__(kPlanBlock) void k_replace_plan(const int32_t *__re
     }
 }
 
-// The last index i in [lo, hi) with pos[i] <= x, lo - 1 if there is none (pos ascends; equal positions: deleted matches that
-// touch each other).
-__device__ __forceinline__ int64_t last_at_or_before(const int64_t *__restrict__ pos, int64_t lo, int64_t hi, int64_t x) {
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (pos[mid] <= x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo - 1;
-}
-
 // One stretch of the output as a workgroup sees it, u = an output unit relative to the tile: from u = rel on, the units below
 // rend are units rsrc + u of the replacement table, the others units tsrc + u of the text -- up to the next segment's rel.
 // (rsrc, tsrc: modulo 2^32; what they are used for lies below 2^31.)
@@ -185,40 +151,6 @@ __device__ __forceinline__ Seg make_seg(const EmitArgs<T> &A, int64_t i, int64_t
     s.rsrc = r.x - (uint32_t)P;
     s.tsrc = (uint32_t)A.recs[3 * i + 1] - (uint32_t)rend;
     return s;
-}
-
-// The 16 consecutive bytes from p -- 8 units at any 2-byte alignment, or 16 bytes at any address -- as one 16-byte value: the two
-// aligned 16-byte words around them and a funnel shift by sh = p's offset into the first, in bytes (units: even).  Only 16-byte
-// words that hold one of the wanted bytes are read, so nothing beyond the page of a valid element.
-template <class T>
-__device__ __forceinline__ rp_v4u load16(const T *p) {
-    const uintptr_t a = (uintptr_t)p;
-    const uint32_t sh = (uint32_t)a & 15u;
-    const rp_v4u *q = reinterpret_cast<const rp_v4u *>(a & ~(uintptr_t)15);
-    const rp_v4u lo = q[0];
-    if (sh == 0) return lo;
-    const rp_v4u hi = q[1];
-    uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    if (sh & 8u) {
-#pragma unroll
-        for (int j = 0; j < 6; ++j) w[j] = w[j + 2];
-    }
-    if (sh & 4u) {
-#pragma unroll
-        for (int j = 0; j < 7; ++j) w[j] = w[j + 1];
-    }
-    if (sizeof(T) == 2) {
-        if (sh & 2u) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) w[j] = (w[j] >> 16) | (w[j + 1] << 16);
-        }
-    } else { // the low bytes of the shift: each word from itself and its neighbour, {w[j + 1], w[j]} >> 8 (sh & 3)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = __builtin_amdgcn_alignbyte(w[j + 1], w[j], sh & 3u);
-    }
-    rp_v4u r;
-    r.x = w[0]; r.y = w[1]; r.z = w[2]; r.w = w[3];
-    return r;
 }
 
 // The emit.  Tiles are laid over the DESTINATION's 16-byte grid: v = o - w0 + (dst's misalignment in units), tile b = the v in
@@ -625,36 +557,11 @@ int replace_piece(ReplaceCall &c, const void *hay, uint64_t base, const int32_t 
         const int rc = launch_emit(c, hay, recs, cnt, done_rel, 0, emit_total, c.d_out + c.out_pos * c.esz, c.stream);
         if (rc) return rc;
     } else if (emit_total) {
-        // through two slabs of the pool: slab k is copied to the caller's memory (on the copy stream) while slab k + 1 is emitted.
-        // A slab is a whole number of 16-byte vectors -- 8 units, or 16 bytes -- so that both slabs start 16-byte aligned.
-        const uint64_t vec = 16 / c.esz;
-        const uint64_t slab = (std::min<uint64_t>((uint64_t)std::max<int64_t>(8, tunables().replace_slab_units.load(std::memory_order_relaxed)), emit_total) + vec - 1) & ~(vec - 1);
-        int rc = d.replace_slab.ensure(slab * 2 * c.esz + 32);
+        // through the pool's two slabs (emit_through_slabs, acgpu_emit.h)
+        const int rc = emit_through_slabs(d, c.stream, c.esz, c.h_out + c.out_pos * c.esz, emit_total, [&](uint64_t w0, uint64_t w1, void *dst) {
+            return launch_emit(c, hay, recs, cnt, done_rel, w0, w1, dst, c.stream);
+        });
         if (rc) return rc;
-        uint8_t *buf[2] = {reinterpret_cast<uint8_t *>(d.replace_slab.p), reinterpret_cast<uint8_t *>(d.replace_slab.p) + slab * c.esz};
-        bool copied[2] = {false, false};
-        auto copy_out = [&](int b, uint64_t w0, uint64_t w1) -> int {
-            HIP_TRY(hipStreamWaitEvent(d.copy_stream, d.replace_ev[b], 0));
-            HIP_TRY(hipMemcpyAsync(c.h_out + (c.out_pos + w0) * c.esz, buf[b], (w1 - w0) * c.esz, hipMemcpyDeviceToHost, d.copy_stream));
-            HIP_TRY(hipEventRecord(d.replace_ev[2 + b], d.copy_stream));
-            copied[b] = true;
-            return ACGPU_OK;
-        };
-        uint64_t prev0 = 0, prev1 = 0;
-        int k = 0;
-        for (uint64_t w0 = 0; w0 < emit_total; w0 += slab, ++k) {
-            const uint64_t w1 = std::min(emit_total, w0 + slab);
-            const int b = k & 1;
-            if (copied[b]) HIP_TRY(hipStreamWaitEvent(c.stream, d.replace_ev[2 + b], 0)); // (the slab has left for the host)
-            if ((rc = launch_emit(c, hay, recs, cnt, done_rel, w0, w1, buf[b], c.stream))) return rc;
-            HIP_TRY(hipEventRecord(d.replace_ev[b], c.stream));
-            if (k > 0 && (rc = copy_out(b ^ 1, prev0, prev1))) return rc;
-            prev0 = w0;
-            prev1 = w1;
-        }
-        if ((rc = copy_out((k - 1) & 1, prev0, prev1))) return rc;
-        HIP_TRY(hipStreamSynchronize(d.copy_stream));
-        HIP_TRY(hipStreamSynchronize(c.stream)); // (the next piece's text overwrites d.stage_hay from the copy stream)
     }
     c.done = limit;
     c.out_pos += total;
@@ -670,12 +577,10 @@ int replace_pieces(ReplaceCall &c, int64_t chain, bool whole, const PieceScan &s
                    int64_t *chain_exit = nullptr) {
     DeviceState &d = c.d;
     if (!d.replace_pin) HIP_TRY(hipHostMalloc(&d.replace_pin.h, 64, hipHostMallocDefault));
-    if (!d.copy_stream) HIP_TRY(hipStreamCreateWithFlags(&d.copy_stream.h, hipStreamNonBlocking));
-    for (auto &e : d.replace_ev)
-        if (!e) HIP_TRY(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
+    int rc = emit_slabs_ready(d);
+    if (rc) return rc;
     // (driven over the units the scan sees: a UTF-8 text's units, a UTF-8 batch's units and separators)
     PieceDriver p(own_begin, own_end, chain, whole, ACGPU_REC_MAP, &d.count_res); // the pool's reservoir of Map records (a counting call's too: one call at a time holds the pool)
-    int rc = ACGPU_OK;
     const void *hay = c.u8 ? (const void *)c.u8->d_bytes : scan.shard ? (const void *)scan.shard->d_hay : d.stage_hay.p;
     while (rc == ACGPU_OK && p.pos < p.end) {
         uint64_t cnt = 0, base = 0;

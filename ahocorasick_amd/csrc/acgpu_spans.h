@@ -1,0 +1,47 @@
+// acgpu_spans.h -- the merge behind a piece (acgpu_spans.hip) as its two callers see it: the spans entries, whose final spans
+// go to the caller, and the cover entries (acgpu_cover.hip), whose final spans stay in the pool for the plan and the emit.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "acgpu_host.h"
+
+namespace acgpu {
+
+// 64-bit words in front of the tiles' values in d.spans_work: {n_final, n_carry, the piece's bound in bytes (UTF-8), and for a
+// cover call: the settled position L, the elements of the piece's final spans (written by the plan of a DROP call), unused}
+constexpr int kSpanHead = 6;
+constexpr int kSpanSettled = 3, kSpanDropped = 4;
+
+// What one call holds while it runs (the caller holds d.mu).  Positions are ELEMENTS of the text as the caller sees it: units, or
+// bytes of a UTF-8 text.
+struct SpansCall {
+    acgpu_automaton *a;
+    DeviceState &d;
+    hipStream_t stream;
+    const Utf8Text *u8 = nullptr; // a UTF-8 text: the scan runs over its units, the merge over bytes
+    int32_t *h_out = nullptr;     // the host entry's result (through d.spans_out) ...
+    int32_t *d_out = nullptr;     // ... or the device entry's
+    uint64_t cap = 0;
+    uint64_t out_pos = 0;         // final spans so far (beyond cap: counted, not written)
+    uint32_t n_carry = 0;         // spans the piece before withheld, in carry buffer `cur`
+    uint32_t carry_cap = 0;
+    int cur = 0;
+    acgpu_spans_stats st{};
+    // A cover call: a piece's final spans go to d.cover_spans (all of them, text coordinates), and the piece's settled position
+    // and whatever `planned` adds ride with {n_final, n_carry} in the piece's one wait.
+    bool to_pool = false;
+    // ... called behind the scatter and before that wait, with the head of d.spans_work (device), the piece's spans (device; the
+    // first slot[0] of them are final) and m, the intervals merged, which bounds their number
+    int (*planned)(void *ctx, uint64_t *d_slot, const int2 *d_spans, uint64_t m) = nullptr;
+    void *ctx = nullptr;
+    uint64_t piece_final = 0;     // out: the piece's final spans
+    int64_t piece_settled = 0;    // out, not on the last piece: L = min(B, start of the first carried span)
+    uint64_t piece_dropped = 0;   // out: slot[kSpanDropped] if `planned` is set
+};
+
+// before the first piece: the pinned words and the two carry buffers
+int spans_begin(SpansCall &c);
+// Behind a piece: merge the carry and the piece's cnt records (in d.count_res, relative to `base`; a UTF-8 call's: in bytes).
+int spans_piece(SpansCall &c, uint64_t base, uint64_t cnt, uint64_t own_hi, bool last_or_whole);
+
+} // namespace acgpu

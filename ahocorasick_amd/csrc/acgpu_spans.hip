@@ -33,6 +33,11 @@
 // text scanned as one piece, finalise everything.  The host reads 16 bytes per piece, {n_final, n_carry}: one wait beside the
 // scan's own.
 //
+// A SECOND CALLER.  The cover entries (acgpu_cover.hip) run the same merge through acgpu_spans.h: SpansCall::to_pool sends a
+// piece's spans to d.cover_spans instead of the caller, k_span_settled adds the position up to which the text is settled, and
+// SpansCall::planned enqueues the caller's plan in front of the wait -- which then reads the whole head, 48 bytes, still once.
+// What the spans entries compute, read back and return is untouched by that.
+//
 // UTF-8: the text is staged by stage_utf8_text and scanned in units; a piece's records become byte offsets where they lie
 // (utf8_map_records, two words per record) BEFORE the merge -- the map is monotone, so the order by end survives -- and `bound`
 // goes through utf8_map_position, rounded down, into the slot the kernels read it from.  Keywords with an unpaired surrogate are
@@ -45,13 +50,13 @@
 #include "acgpu_device.h"
 #include "acgpu_host.h"
 #include "acgpu_internal.h"
+#include "acgpu_spans.h"
 
 using namespace acgpu;
 
 namespace {
 
 constexpr int kSpanBlock = 256, kSpanPer = 8, kSpanTile = kSpanBlock * kSpanPer; // intervals per workgroup: a thread takes kSpanPer consecutive ones
-constexpr int kSpanHead = 4; // 64-bit words in front of the tiles' values: {n_final, n_carry, the piece's bound in bytes (UTF-8), unused}
 constexpr int32_t kNoStart = INT_MAX;
 
 // The list a piece merges: n_carry spans in text coordinates, then the piece's records, relative to `base`.
@@ -272,22 +277,15 @@ __global__ __launch_bounds__(kSpanBlock) void k_span_scatter(SpanList L, const i
     }
 }
 
-// What one call holds while it runs (the caller holds d.mu).  Positions are ELEMENTS of the text as the caller sees it: units, or
-// bytes of a UTF-8 text.
-struct SpansCall {
-    acgpu_automaton *a;
-    DeviceState &d;
-    hipStream_t stream;
-    const Utf8Text *u8 = nullptr; // a UTF-8 text: the scan runs over its units, the merge over bytes
-    int32_t *h_out = nullptr;     // the host entry's result (through d.spans_out) ...
-    int32_t *d_out = nullptr;     // ... or the device entry's
-    uint64_t cap = 0;
-    uint64_t out_pos = 0;         // final spans so far (beyond cap: counted, not written)
-    uint32_t n_carry = 0;         // spans the piece before withheld, in carry buffer `cur`
-    uint32_t carry_cap = 0;
-    int cur = 0;
-    acgpu_spans_stats st{};
-};
+// A cover call (acgpu_cover.hip), behind the scatter: the settled position L = min(B, start of the first carried span) -- every
+// position below it is inside a final span or will never be covered -- into slot[kSpanSettled]; one thread.  empty: a piece
+// without intervals, whose other launches did not run.
+__global__ void k_span_settled(SpanList L, SpanBound Bd, const int2 *__restrict__ carry_out, uint64_t *__restrict__ slot, int empty) {
+    if (empty) slot[0] = slot[1] = slot[kSpanDropped] = 0;
+    int64_t at = final_below(L, Bd);
+    if (slot[1]) at = std::min<int64_t>(at, carry_out[0].x);
+    slot[kSpanSettled] = (uint64_t)at;
+}
 
 bool first_unit_family(const HostTables &t) { return t.mode != ACGPU_MODE_ALL && t.mode != ACGPU_MODE_SHORTEST; }
 
@@ -298,14 +296,25 @@ uint64_t spans_bound(const HostTables &t, uint64_t own_hi) {
     return own_hi > back ? own_hi - back : 0;
 }
 
-// Behind a piece: merge the carry and the piece's cnt records (in d.count_res, relative to `base`; a UTF-8 call's: in bytes).
+} // namespace
+
+namespace acgpu {
+
+int spans_begin(SpansCall &c) {
+    DeviceState &d = c.d;
+    if (!d.spans_pin) HIP_TRY(hipHostMalloc(&d.spans_pin.h, 64, hipHostMallocDefault));
+    c.carry_cap = c.a->t.max_len / 2 + 2;
+    return d.spans_carry.ensure((size_t)c.carry_cap * 2 * 8);
+}
+
 int spans_piece(SpansCall &c, uint64_t base, uint64_t cnt, uint64_t own_hi, bool last_or_whole) {
     DeviceState &d = c.d;
     c.st.n_records += cnt;
     const uint64_t m = c.n_carry + cnt;
-    if (!m) return ACGPU_OK;
+    c.piece_final = c.piece_dropped = 0;
+    if (!m && !c.to_pool) return ACGPU_OK;
     const uint32_t n_tiles = (uint32_t)((m + kSpanTile - 1) / kSpanTile);
-    int rc = d.spans_work.ensure(kSpanHead * 8 + (size_t)n_tiles * 12); // {n_final, n_carry, bound, -} | tile minima | tile counts | tile final counts
+    int rc = d.spans_work.ensure(kSpanHead * 8 + (size_t)n_tiles * 12); // the head (acgpu_spans.h) | tile minima | tile counts | tile final counts
     if (rc) return rc;
     uint64_t *slot = reinterpret_cast<uint64_t *>(d.spans_work.p);
     int32_t *tmin = reinterpret_cast<int32_t *>(slot + kSpanHead);
@@ -338,7 +347,12 @@ int spans_piece(SpansCall &c, uint64_t base, uint64_t cnt, uint64_t own_hi, bool
 
     SpanOut O;
     const uint64_t room = c.cap > c.out_pos ? c.cap - c.out_pos : 0;
-    if (c.d_out) {
+    if (c.to_pool) { // every span of the piece has a slot: the plan and the emit read the final ones from there
+        if ((rc = d.cover_spans.ensure((size_t)m * 8 + 16))) return rc;
+        O.out = reinterpret_cast<int2 *>(d.cover_spans.p);
+        O.out_first = 0;
+        O.room = m;
+    } else if (c.d_out) {
         O.out = reinterpret_cast<int2 *>(c.d_out);
         O.out_first = c.out_pos;
         O.room = room;
@@ -350,6 +364,16 @@ int spans_piece(SpansCall &c, uint64_t base, uint64_t cnt, uint64_t own_hi, bool
     }
     O.carry = carry + (size_t)(c.cur ^ 1) * c.carry_cap;
     O.carry_cap = c.carry_cap;
+    if (!m) { // (a cover call's piece without intervals: its settled position is the bound)
+        c.piece_settled = (int64_t)bound;
+        if (!Bd.d_bound) return ACGPU_OK;
+        hipLaunchKernelGGL(k_span_settled, dim3(1), dim3(1), 0, c.stream, L, Bd, (const int2 *)O.carry, slot, 1);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(d.spans_pin.h, slot, kSpanHead * 8, hipMemcpyDeviceToHost, c.stream));
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        c.piece_settled = (int64_t) static_cast<const uint64_t *>(d.spans_pin.h)[kSpanSettled];
+        return ACGPU_OK;
+    }
 
     hipLaunchKernelGGL(k_span_mins, dim3(n_tiles), dim3(kSpanBlock), 0, c.stream, L, tmin);
     hipLaunchKernelGGL(k_span_scan_mins, dim3(1), dim3(kSpanBlock), 0, c.stream, tmin, n_tiles);
@@ -357,8 +381,11 @@ int spans_piece(SpansCall &c, uint64_t base, uint64_t cnt, uint64_t own_hi, bool
     hipLaunchKernelGGL(k_span_offsets, dim3(1), dim3(kSpanBlock), 0, c.stream, tcnt, (const uint32_t *)tfin, n_tiles, slot);
     hipLaunchKernelGGL(k_span_scatter, dim3(n_tiles), dim3(kSpanBlock), 0, c.stream, L, (const int32_t *)tmin, (const uint32_t *)tcnt,
                        (const uint64_t *)slot, O);
+    if (c.to_pool && !last_or_whole)
+        hipLaunchKernelGGL(k_span_settled, dim3(1), dim3(1), 0, c.stream, L, Bd, (const int2 *)O.carry, slot, 0);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(d.spans_pin.h, slot, 16, hipMemcpyDeviceToHost, c.stream));
+    if (c.planned && (rc = c.planned(c.ctx, slot, O.out, m))) return rc;
+    HIP_TRY(hipMemcpyAsync(d.spans_pin.h, slot, c.to_pool ? kSpanHead * 8 : 16, hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream)); // how many spans left for the output decides out_pos and the next piece's list
     const uint64_t *h = static_cast<const uint64_t *>(d.spans_pin.h);
     const uint64_t n_final = h[0], n_carry = h[1];
@@ -369,15 +396,20 @@ int spans_piece(SpansCall &c, uint64_t base, uint64_t cnt, uint64_t own_hi, bool
     c.n_carry = (uint32_t)n_carry;
     c.cur ^= 1;
     c.st.max_carry = std::max(c.st.max_carry, (uint32_t)n_carry);
+    c.piece_final = n_final;
+    c.piece_settled = (int64_t)h[kSpanSettled];
+    c.piece_dropped = h[kSpanDropped];
     return ACGPU_OK;
 }
+
+} // namespace acgpu
+
+namespace {
 
 // The pieces of a whole text: chain = the chain's entry, whole = the text is scanned as one piece.
 int spans_pieces(SpansCall &c, int64_t chain, bool whole, const PieceScan &scan, uint64_t n_units) {
     DeviceState &d = c.d;
-    if (!d.spans_pin) HIP_TRY(hipHostMalloc(&d.spans_pin.h, 64, hipHostMallocDefault));
-    c.carry_cap = c.a->t.max_len / 2 + 2;
-    int rc = d.spans_carry.ensure((size_t)c.carry_cap * 2 * 8);
+    int rc = spans_begin(c);
     if (rc) return rc;
     PieceDriver p(0, n_units, chain, whole, ACGPU_REC_SET, &d.count_res); // the pool's reservoir, here of Set records: one call at a time holds the pool
     while (p.pos < p.end) {

@@ -1167,7 +1167,7 @@ int acgpu_stream_replace_utf8_lossy(acgpu_stream *s, const uint8_t *bytes, uint6
  * others -- at most max_keyword_len / 2 + 2 of them -- wait on the device for the next piece (st->max_carry: the most that did).
  * Scratch, per automaton and device: the reservoir the counting and replace calls use, 12 bytes per 2048 records of a piece, the
  * carry, and for the host entries 8 bytes per span of a piece.  The host reads 16 bytes per piece.
- * Not built: mask, highlight and replace for ACGPU_MODE_ALL on top of spans; a record-free form for ACGPU_MODE_ALL from the
+ * Not built (mask, highlight and redaction on top of spans: the cover entries below): a record-free form for ACGPU_MODE_ALL from the
  * state words of k_ac_states (the analogue of the counting calls' direct form); batch, stream and multi-device forms; the Java
  * facade.  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
  */
@@ -1186,6 +1186,67 @@ int acgpu_spans_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_
                      acgpu_spans_stats *st, acgpu_utf8_stats *ust /* may be NULL */);
 int acgpu_spans_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, int32_t *out, uint64_t cap, uint64_t *n_out,
                            acgpu_spans_stats *st, acgpu_utf8_lossy_stats *ust /* may be NULL */);
+
+/*
+ * Cover: mask, highlight or redact every covered run of a text, on the device, for ALL FIVE families.  Every span [s, e) of the
+ * text -- exactly the spans the spans entries above report for the same automaton and text -- becomes open ++ body ++ close, and
+ * everything outside the spans is copied as it is.  body is one of
+ *   ACGPU_COVER_KEEP : the covered text itself (highlight, tagging: open = "<b>", close = "</b>")
+ *   ACGPU_COVER_FILL : `fill` once per covered element, so with empty open and close the length is preserved (mask)
+ *   ACGPU_COVER_DROP : nothing (open = "***": redaction; everything empty: deletion)
+ * ELEMENTS are what the caller's text is made of: UTF-16 units for acgpu_cover_u16 and acgpu_cover_device, bytes for the UTF-8
+ * entries (whose spans are in bytes, and which serve keywords with an unpaired surrogate as the spans entries do).  open and close
+ * are HOST pointers in elements, uploaded once per call; the byte entries take them as they are, without validating them.
+ *  not replace : overlapping, nested and TOUCHING records are one span, so DROP with open = r is the result of the replace entries
+ *              with the single replacement r only where no two matches touch: two touching matches give one r, not two.
+ *  fill      : a unit (<= 0xFFFF) in the unit entries, so a surrogate pair becomes two.  In the byte entries it must be below 0x80
+ *              and is written once per covered BYTE: the result stays well-formed and every byte offset computed on the input
+ *              holds on the output.  Lossy input: stray bytes inside a span are filled, outside the spans the output is a
+ *              byte-for-byte copy, stray bytes included.  (fill is only looked at with ACGPU_COVER_FILL.)
+ *  cap, *n_out : in ELEMENTS, as for the replace entries: a result of more than cap elements gives ACGPU_E_OVERFLOW with *n_out (and
+ *              st->units_out) the exact size -- the text is scanned and planned to its end, out[0 .. cap) holds the result's
+ *              first cap elements, nothing at or beyond cap has been written.  The same call with cap = *n_out succeeds.
+ *  errors    : ACGPU_E_INVALID, before a device is touched: NULL a, spec or n_out; body > 2; a NULL pointer with a non-zero length
+ *              (the text, out with cap, open, close); 2^31 or more elements of text, open or close; a fill that the entry's
+ *              element does not hold (see above); acgpu_cover_device: d_hay not 16-byte aligned, d_out not aligned to a unit.
+ *              ACGPU_E_UNSUPPORTED: a shard that is not a WHOLE text, as for acgpu_spans_device.  Ill-formed UTF-8, ust, the empty
+ *              UTF-8 text (ACGPU_OK, *n_out = 0, no device) and the STREAM RULE: as for the spans entries.
+ *  acgpu_cover_u16 : text and out in HOST memory.  The whole text is copied to the device in front of the first piece (one blocking
+ *              copy): a span can reach across every piece, and KEEP copies its body long after the piece that first saw it.
+ *  acgpu_cover_device : d_out is device memory of cap units at ANY unit address, written directly.
+ * How it works: behind every piece the spans merge runs as for the spans entries, its final spans stay on the device, and with
+ * their number the host reads the position up to which the text is settled -- in the one wait per piece that the spans entries
+ * have.  A span's place in the output is closed form for KEEP and FILL and a 64-bit scan for DROP; one emit kernel writes the
+ * piece's output in aligned 16-byte stores (st->pieces, rescans, max_carry: as acgpu_spans_stats).  Host output leaves through
+ * the two slabs of the replace entries ("replace_slab_units").
+ * Not built: batch, stream and multi-device forms, per-keyword open / close, the Java facade.  ACGPU_ABI_VERSION stays as it is.
+ */
+enum { ACGPU_COVER_KEEP = 0, ACGPU_COVER_FILL = 1, ACGPU_COVER_DROP = 2 };
+typedef struct acgpu_cover_spec {
+    const void *open;         /* open_len elements in HOST memory (NULL if open_len == 0)                    */
+    uint32_t open_len;
+    const void *close;        /* close_len elements in HOST memory (NULL if close_len == 0)                  */
+    uint32_t close_len;
+    uint32_t body;            /* ACGPU_COVER_KEEP, _FILL or _DROP                                            */
+    uint32_t fill;            /* ACGPU_COVER_FILL: the element written once per covered element              */
+} acgpu_cover_spec;
+typedef struct acgpu_cover_stats {
+    uint64_t n_records;       /* records merged == records the Set match call returns                        */
+    uint64_t n_spans;         /* spans of the text                                                           */
+    uint64_t units_out;       /* elements of the result (exact, also on ACGPU_E_OVERFLOW)                    */
+    uint32_t pieces, rescans; /* as acgpu_count_stats                                                        */
+    uint32_t max_carry;       /* as acgpu_spans_stats                                                        */
+    uint32_t reserved;
+} acgpu_cover_stats;   /* 40 bytes */
+int acgpu_cover_u16(const acgpu_automaton *a, const uint16_t *haystack, uint64_t n_units, const acgpu_cover_spec *spec, uint16_t *out,
+                    uint64_t cap, uint64_t *n_out, acgpu_cover_stats *st /* may be NULL */);
+int acgpu_cover_device(const acgpu_automaton *a, acgpu_shard *shard, const acgpu_cover_spec *spec, uint16_t *d_out, uint64_t cap,
+                       uint64_t *n_out, void *stream, acgpu_cover_stats *st /* may be NULL */);
+int acgpu_cover_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, const acgpu_cover_spec *spec, uint8_t *out,
+                     uint64_t cap, uint64_t *n_out, acgpu_cover_stats *st /* may be NULL */, acgpu_utf8_stats *ust /* may be NULL */);
+int acgpu_cover_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, const acgpu_cover_spec *spec, uint8_t *out,
+                           uint64_t cap, uint64_t *n_out, acgpu_cover_stats *st /* may be NULL */,
+                           acgpu_utf8_lossy_stats *ust /* may be NULL */);
 
 /*
  * Synthetic haystack generator of the benchmark: unit i of the stream is
@@ -1237,7 +1298,9 @@ int acgpu_stream_probe(const void *d_buf, uint64_t n_bytes, void *stream, int re
  * 2^26) and "cursor_reservoir_bytes" (largest reservoir, 256 MiB); "states_chunk_log2" (k_ac_states: a lane's chunk, 0 = by the text's
  * length, 8 .. 10 = forced) and the counting calls' A/B switches "count_form" (bits: 1 never the direct form, 2 no LDS counters
  * in k_states_hist, 4 no same-key peel in k_states_hist / k_count_ids); "replace_slab_units" (acgpu_replace_u16: units of one of the
- * two device slabs its result leaves through, default 2^25; it counts OUTPUT ELEMENTS, so for acgpu_replace_utf8 bytes).  Returns the previous value, -1 for an unknown name. */
+ * two device slabs its result leaves through, default 2^25; it counts OUTPUT ELEMENTS, so for acgpu_replace_utf8 bytes; the cover entries' host output
+ * leaves through the same slabs); "cover_lds_segments" (k_cover_emit: the segments of a tile it stages in LDS at most, default and
+ * maximum 1536; 0 sends every tile through the global-memory view -- tests).  Returns the previous value, -1 for an unknown name. */
 int64_t acgpu_set_tunable(const char *name, int64_t value);
 
 const char *acgpu_strerror(int code);
