@@ -115,6 +115,9 @@ COVER_KEEP, COVER_FILL, COVER_DROP = 0, 1, 2
 COVER_TILE_UNITS, COVER_TILE_BYTES = 2048, 4096  # kEmitTile (csrc/acgpu_emit.h): the output elements a workgroup of k_cover_emit writes
 COVER_LDS_SEGMENTS = 1536  # kCoverLds (csrc/acgpu_cover.hip): the segments of a tile k_cover_emit stages in LDS at most; tunable "cover_lds_segments"
 SPAN_TILE = 2048  # kSpanTile (csrc/acgpu_spans.hip): the intervals a workgroup of the merge's scans takes
+SPAN_BLOCK = 256  # kSpanBlock (csrc/acgpu_spans.hip): the tiles one step of the merge's level-2 scans (k_span_scan_mins, k_span_offsets) takes
+SPAN_CHUNK = SPAN_BLOCK * SPAN_TILE  # the intervals behind one such step: kSpanBlock * kSpanTile, beyond which the level-2 scans carry
+PLAN_TILE = 2048  # kPlanTile (csrc/acgpu_emit.h): the spans a workgroup of a DROP call's plan takes; k_cover_offsets scans kPlanBlock = 256 of their sums per step
 TERMS_BLOCK = 2048  # kTermsBlock (csrc/acgpu_terms.hip): the records a workgroup of k_terms_block sorts and reduces
 
 

@@ -147,9 +147,9 @@ def test_one_span_of_all_records_at_the_tile_seams(count):
     assert st.n_records == count and want.tolist() == [[0, len(hay)]]
 
 
-@pytest.fixture(scope="module")
-def random_case():
-    rng = np.random.default_rng(4306)  # (a seed under which the conditions asserted below hold)
+def random_dense(n_units):
+    """20 keywords of 1 .. 6 units over "ab." and a random text of n_units over the same three -> (automaton, oracle, text, records)"""
+    rng = np.random.default_rng(4306)  # (a seed under which the conditions asserted by the callers hold)
     kws, seen = [], set()
     while len(kws) < 20:
         k = "".join(rng.choice(list("ab."), int(rng.integers(1, 7))))
@@ -157,10 +157,15 @@ def random_case():
             seen.add(k)
             kws.append(k)
     assert {len(k) for k in kws} == set(range(1, 7))
-    hay = np.array([ord(c) for c in "ab."], np.uint16)[rng.choice(3, 12000, p=[0.3, 0.3, 0.4])]
+    hay = np.array([ord(c) for c in "ab."], np.uint16)[rng.choice(3, n_units, p=[0.3, 0.3, 0.4])]
     a, orc = pair(N.MODE_ALL, kws)
     recs = orc.match(hay, cap=hay.size * 8)
     return a, orc, hay, recs
+
+
+@pytest.fixture(scope="module")
+def random_case():
+    return random_dense(12000)
 
 
 def test_random_text_with_heads_on_every_lane_and_tile_position(random_case):
