@@ -3,8 +3,8 @@
 // body is the covered text itself (KEEP: highlight, tagging), one fill element per covered element (FILL: mask) or nothing (DROP:
 // redaction, deletion); everything outside the spans is copied.
 //
-// A cover call is a consumer of the spans merge (spans_piece, acgpu_spans.hip): behind every piece the five launches of the merge
-// run as they do for the spans entries, but the piece's final spans stay in the pool (d.cover_spans), and with {n_final, n_carry}
+// A cover call is a consumer of the spans piece loop (spans_pieces, acgpu_spans.h): behind every piece the five launches of the
+// merge run as they do for the spans entries, but the piece's final spans stay in the pool (d.cover_spans), and with {n_final, n_carry}
 // the host reads in the same wait
 //   L, the SETTLED POSITION: the text's end on the last piece, else min(B, start of the first carried span), B as final_below has
 //      it (k_span_settled).  Every position below L is inside a final span or will never be covered: a later record starts at or
@@ -14,16 +14,15 @@
 //      front of every span this piece finalises, and the final spans of a piece lie in [done, L): they end before B and before
 //      the first carried span.
 //   and for DROP the elements the piece's final spans hold (the plan's sum).
-// The piece then emits the text's elements [done, L) with its final spans rewritten:
-//  * the PLAN.  With w = open_len + close_len, final span k of the piece begins at output position
+// The piece then emits the text's elements [done, L) with its final spans rewritten (cover_piece, the loop's step behind the
+// merge), by the plan and the emit of acgpu_emit.h:
+//  * the plan's ITEMS are the piece's final spans.  With w = open_len + close_len, span k begins at output position
 //    pos_k = (s_k - done) + k w - D_k of the piece's output, D_k = 0 for KEEP and FILL -- closed form, no scan, no array -- and the
-//    elements of the piece's spans in front of k for DROP: a 64-bit two-level exclusive scan (k_cover_sums, k_cover_offsets,
-//    k_cover_plan) that takes its n from the merge's slot on the device, so it runs BEFORE the piece's one wait.  The positions
+//    elements of the piece's spans in front of k for DROP: the plan over the spans' lengths (k_cover_sums, k_cover_offsets,
+//    k_cover_plan), which takes its n from the merge's slot on the device, so it runs BEFORE the piece's one wait.  The positions
 //    ascend strictly: two spans do not touch, so pos_{k+1} - pos_k >= 1 + w.
-//  * the EMIT (k_cover_emit<T, BODY>): k_replace_emit's shape -- tiles over the destination's 16-byte grid, a lane per aligned
-//    16-byte non-temporal store, the window's first and last vectors element by element, the spans of a tile by two binary
-//    searches, their segments in LDS or, where they do not fit, read through the same code from global memory -- with up to four
-//    sources per segment: open, the body, close, and the text behind the span up to the next one.
+//  * the emit's SOURCE (CoverArgs, k_cover_emit<T, BODY>) has up to four sources per segment: open, the body, close, and the text
+//    behind the span up to the next one.
 // The running output position and the running span count travel from piece to piece on the host (CoverCall).
 //
 // The text stays on the device for the whole call: a carried span can be as long as the text (keyword "aa" on "aaaa..."), and
@@ -47,9 +46,20 @@ namespace {
 
 constexpr int kCoverLds = 1536; // segments a workgroup stages (32 bytes each)
 
-// What the emit reads besides the text: the piece's final spans (text coordinates, elements), for DROP their output positions.
-template <class T>
+// A segment of four sources: from u = rel on, the elements below a_end are elements osrc + u of open, those below b_end the body
+// (elements bsrc + u of the text, or the fill element), those below c_end elements csrc + u of close, the others elements
+// tsrc + u of the text.
+struct CSeg {
+    int32_t rel, a_end, b_end, c_end;
+    uint32_t osrc, bsrc, csrc, tsrc;
+};
+
+// The emit's source (acgpu_emit.h): the text with a piece's final spans (text coordinates, elements) rewritten.
+template <class T, int BODY>
 struct CoverArgs {
+    using Elem = T;
+    using Seg = CSeg;
+    static constexpr int kLds = kCoverLds;
     const T *hay;        // the whole text
     const int2 *spans;
     const int64_t *pos;  // DROP: the plan; else nullptr, the positions are closed form
@@ -58,223 +68,83 @@ struct CoverArgs {
     uint32_t ol, cl;
     uint32_t fill;
     int64_t done;        // output element 0 of the piece is text element `done` (if no span starts there)
-    int64_t w0, w1;      // the window of the piece's output to write
-    T *dst;              // where output element w0 goes
-    int32_t lds_cap;     // segments to stage at most (tunable "cover_lds_segments")
-};
-
-// the output position of span i, relative to the piece's output
-template <class T, int BODY>
-__device__ __forceinline__ int64_t pos_at(const CoverArgs<T> &A, int64_t i) {
-    if (BODY == ACGPU_COVER_DROP) return A.pos[i];
-    return (int64_t)A.spans[i].x - A.done + i * ((int64_t)A.ol + (int64_t)A.cl);
-}
-
-// The last span i in [0, n_spans) with pos_at(i) <= x, -1 if there is none (the positions ascend strictly).
-template <class T, int BODY>
-__device__ __forceinline__ int64_t span_at_or_before(const CoverArgs<T> &A, int64_t x) {
-    int64_t lo = 0, hi = A.n_spans;
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (pos_at<T, BODY>(A, mid) <= x) lo = mid + 1;
-        else hi = mid;
+    int64_t w0, w1;
+    T *dst;
+    int32_t cap;         // segments to stage at most (tunable "cover_lds_segments")
+    __device__ __forceinline__ int32_t lds_cap() const { return cap; }
+    __device__ __forceinline__ int64_t n() const { return n_spans; }
+    __device__ __forceinline__ int64_t pos_at(int64_t i) const {
+        if (BODY == ACGPU_COVER_DROP) return pos[i];
+        return (int64_t)spans[i].x - done + i * ((int64_t)ol + (int64_t)cl);
     }
-    return lo - 1;
-}
-
-// One stretch of the output as a workgroup sees it, u = an output element relative to the tile: from u = rel on, the elements below
-// a_end are elements osrc + u of open, those below b_end the body (elements bsrc + u of the text, or the fill element), those
-// below c_end elements csrc + u of close, the others elements tsrc + u of the text -- up to the next segment's rel.
-// (the sources: modulo 2^32; what they are used for lies below 2^31.)
-struct CSeg {
-    int32_t rel, a_end, b_end, c_end;
-    uint32_t osrc, bsrc, csrc, tsrc;
-};
-
-// segment of span i (-1: the text in front of the first span), t0 = the tile's first output element
-template <class T, int BODY>
-__device__ __forceinline__ CSeg make_seg(const CoverArgs<T> &A, int64_t i, int64_t t0) {
-    CSeg s;
-    if (i < 0) {
-        s.rel = -1;
-        s.a_end = s.b_end = s.c_end = 0;
-        s.osrc = s.bsrc = s.csrc = 0;
-        s.tsrc = (uint32_t)(A.done + t0);
+    __device__ __forceinline__ CSeg make_seg(int64_t i, int64_t t0) const {
+        CSeg s;
+        if (i < 0) {
+            s.rel = -1;
+            s.a_end = s.b_end = s.c_end = 0;
+            s.osrc = s.bsrc = s.csrc = 0;
+            s.tsrc = (uint32_t)(done + t0);
+            return s;
+        }
+        const int2 sp = spans[i];
+        const int64_t P = pos_at(i) - t0; // < kEmitTile<T>
+        const int64_t a = P + (int64_t)ol, b = a + (BODY == ACGPU_COVER_DROP ? 0 : (int64_t)(sp.y - sp.x)), c = b + (int64_t)cl;
+        auto in_tile = [](int64_t x) { return (int32_t)std::min<int64_t>(std::max<int64_t>(x, 0), kEmitTile<T>); };
+        s.rel = (int32_t)std::max<int64_t>(P, -1);
+        s.a_end = in_tile(a);
+        s.b_end = in_tile(b);
+        s.c_end = in_tile(c);
+        s.osrc = (uint32_t)0 - (uint32_t)P;
+        s.bsrc = (uint32_t)sp.x - (uint32_t)a;
+        s.csrc = (uint32_t)0 - (uint32_t)b;
+        s.tsrc = (uint32_t)sp.y - (uint32_t)c;
         return s;
     }
-    const int2 sp = A.spans[i];
-    const int64_t P = pos_at<T, BODY>(A, i) - t0; // < kEmitTile<T>
-    const int64_t a = P + (int64_t)A.ol, b = a + (BODY == ACGPU_COVER_DROP ? 0 : (int64_t)(sp.y - sp.x)), c = b + (int64_t)A.cl;
-    auto in_tile = [](int64_t x) { return (int32_t)std::min<int64_t>(std::max<int64_t>(x, 0), kEmitTile<T>); };
-    s.rel = (int32_t)std::max<int64_t>(P, -1);
-    s.a_end = in_tile(a);
-    s.b_end = in_tile(b);
-    s.c_end = in_tile(c);
-    s.osrc = (uint32_t)0 - (uint32_t)P;
-    s.bsrc = (uint32_t)sp.x - (uint32_t)a;
-    s.csrc = (uint32_t)0 - (uint32_t)b;
-    s.tsrc = (uint32_t)sp.y - (uint32_t)c;
-    return s;
-}
-
-template <class T>
-__device__ __forceinline__ uint32_t fill_word(uint32_t fill) {
-    return sizeof(T) == 2 ? (fill | (fill << 16)) : fill * 0x01010101u;
-}
-
-// The emit of one tile: k_replace_emit's emit_tile (acgpu_replace.hip) over segments of four sources.  A vector that one source of
-// one segment holds is one load16 and one store -- or, inside a FILL body, a constant and one store; any other vector, and the
-// window's first and last, goes element by element.
-template <class T, int BODY, bool kLds>
-__device__ __forceinline__ void cover_tile(const CoverArgs<T> &A, const CSeg *lseg, int64_t t0, int64_t i0, int64_t cnt) {
-    const int64_t n_seg = cnt;
-    auto rel_at = [&](int64_t j) -> int64_t {
-        if (kLds) return lseg[j].rel;
-        const int64_t i = i0 + j;
-        return i < 0 ? -1 : std::max<int64_t>(pos_at<T, BODY>(A, i) - t0, -1);
-    };
-    auto seg_at = [&](int64_t j) -> CSeg { return kLds ? lseg[j] : make_seg<T, BODY>(A, i0 + j, t0); };
-    auto find = [&](int64_t from, int32_t u) -> int64_t { // the last segment j >= from with rel <= u (segment `from` has)
-        int64_t lo = from + 1, hi = n_seg;
-        for (int step = 0; step < 4 && lo < hi; ++step) {
-            if (rel_at(lo) > u) return lo - 1;
-            ++lo;
-        }
-        while (lo < hi) {
-            const int64_t mid = lo + (hi - lo) / 2;
-            if (rel_at(mid) <= u) lo = mid + 1;
-            else hi = mid;
-        }
-        return lo - 1;
-    };
-    constexpr int kPer = kEmitPer<T>, kPerWord = 4 / (int)sizeof(T);
-    const int32_t u0 = (int32_t)threadIdx.x * kPer;
-    const int64_t o_first = t0 + u0;
-    if (o_first >= A.w1 || o_first + kPer <= A.w0) return;
-    const int32_t ua = (int32_t)std::max<int64_t>(A.w0 - o_first, 0), ub = (int32_t)std::min<int64_t>(A.w1 - o_first, kPer); // the lane's valid elements [ua, ub)
-    T *out = A.dst + (o_first - A.w0);
-    int64_t j = find(0, u0 + ua);
-    CSeg s = seg_at(j);
-    const bool full = ua == 0 && ub == kPer;
-    if (full && (j + 1 >= n_seg || rel_at(j + 1) > u0 + kPer - 1)) { // one segment holds the vector
-        if (u0 >= s.c_end) {
-            __builtin_nontemporal_store(load16(A.hay + (uint32_t)(s.tsrc + (uint32_t)u0)), reinterpret_cast<rp_v4u *>(out));
-            return;
-        }
-        if (u0 >= s.a_end && u0 + kPer <= s.b_end) {
-            rp_v4u v;
-            if (BODY == ACGPU_COVER_FILL) v.x = v.y = v.z = v.w = fill_word<T>(A.fill);
-            else v = load16(A.hay + (uint32_t)(s.bsrc + (uint32_t)u0));
-            __builtin_nontemporal_store(v, reinterpret_cast<rp_v4u *>(out));
-            return;
-        }
-        if (u0 + kPer <= s.a_end) {
-            __builtin_nontemporal_store(load16(A.open + (uint32_t)(s.osrc + (uint32_t)u0)), reinterpret_cast<rp_v4u *>(out));
-            return;
-        }
-        if (u0 >= s.b_end && u0 + kPer <= s.c_end) {
-            __builtin_nontemporal_store(load16(A.close + (uint32_t)(s.csrc + (uint32_t)u0)), reinterpret_cast<rp_v4u *>(out));
-            return;
-        }
+    // (inside a FILL body the vector is a constant and needs no load)
+    __device__ __forceinline__ bool whole(const CSeg &s, int32_t u0, rp_v4u *v) const {
+        constexpr int kPer = kEmitPer<T>;
+        if (u0 >= s.c_end) *v = load16(hay + (uint32_t)(s.tsrc + (uint32_t)u0));
+        else if (u0 >= s.a_end && u0 + kPer <= s.b_end) {
+            if (BODY == ACGPU_COVER_FILL) v->x = v->y = v->z = v->w = sizeof(T) == 2 ? (fill | (fill << 16)) : fill * 0x01010101u;
+            else *v = load16(hay + (uint32_t)(s.bsrc + (uint32_t)u0));
+        } else if (u0 + kPer <= s.a_end) *v = load16(open + (uint32_t)(s.osrc + (uint32_t)u0));
+        else if (u0 >= s.b_end && u0 + kPer <= s.c_end) *v = load16(close + (uint32_t)(s.csrc + (uint32_t)u0));
+        else return false;
+        return true;
     }
-    uint32_t w[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-        if (k >= ua && k < ub) {
-            const int32_t u = u0 + k;
-            if (k > ua) {
-                const int64_t jn = find(j, u);
-                if (jn != j) {
-                    j = jn;
-                    s = seg_at(j);
-                }
-            }
-            uint32_t x;
-            if (u < s.a_end) x = A.open[(uint32_t)(s.osrc + (uint32_t)u)];
-            else if (u < s.b_end) x = BODY == ACGPU_COVER_FILL ? A.fill : (uint32_t)A.hay[(uint32_t)(s.bsrc + (uint32_t)u)];
-            else if (u < s.c_end) x = A.close[(uint32_t)(s.csrc + (uint32_t)u)];
-            else x = A.hay[(uint32_t)(s.tsrc + (uint32_t)u)];
-            if (full) w[k / kPerWord] |= x << (8 * (int)sizeof(T) * (k % kPerWord));
-            else out[k] = (T)x;
-        }
+    __device__ __forceinline__ uint32_t element(const CSeg &s, int32_t u) const {
+        if (u < s.a_end) return open[(uint32_t)(s.osrc + (uint32_t)u)];
+        if (u < s.b_end) return BODY == ACGPU_COVER_FILL ? fill : (uint32_t)hay[(uint32_t)(s.bsrc + (uint32_t)u)];
+        if (u < s.c_end) return close[(uint32_t)(s.csrc + (uint32_t)u)];
+        return hay[(uint32_t)(s.tsrc + (uint32_t)u)];
     }
-    if (full) {
-        rp_v4u v;
-        v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
-        __builtin_nontemporal_store(v, reinterpret_cast<rp_v4u *>(out));
-    }
-}
+};
 
-// The emit.  Tiles are laid over the DESTINATION's 16-byte grid exactly as k_replace_emit lays them: v = o - w0 + (dst's
-// misalignment in elements), tile b = the v in [b * kEmitTile, + kEmitTile), lane l of it the kEmitPer elements of one aligned
-// 16-byte store; nothing outside [w0, w1) -- nothing at or beyond the caller's capacity -- is touched.
 template <class T, int BODY>
-__global__ __launch_bounds__(kEmitBlock) void k_cover_emit(CoverArgs<T> A) {
-    __shared__ CSeg lseg[kCoverLds];
-    __shared__ int64_t bounds[2];
-    const int64_t mis = (int64_t)(((uintptr_t)A.dst & 15u) / sizeof(T));
-    const int64_t t0 = A.w0 - mis + (int64_t)blockIdx.x * kEmitTile<T>;
-    const int64_t ov0 = std::max(t0, A.w0), ov1 = std::min(t0 + kEmitTile<T>, A.w1); // the tile's elements of the window
-    if (ov0 >= ov1) return;
-    if (threadIdx.x == 0) bounds[0] = span_at_or_before<T, BODY>(A, ov0);
-    if (threadIdx.x == kWave) bounds[1] = span_at_or_before<T, BODY>(A, ov1 - 1);
-    __syncthreads();
-    const int64_t i0 = bounds[0], cnt = bounds[1] - i0 + 1; // segments i0 .. bounds[1]; i0 = -1: the text in front of span 0
-    if (cnt <= (int64_t)A.lds_cap) {
-        for (int32_t j = (int32_t)threadIdx.x; j < (int32_t)cnt; j += kEmitBlock) lseg[j] = make_seg<T, BODY>(A, i0 + j, t0);
-        __syncthreads();
-        cover_tile<T, BODY, true>(A, lseg, t0, i0, cnt);
-    } else {
-        cover_tile<T, BODY, false>(A, lseg, t0, i0, cnt);
-    }
+__global__ __launch_bounds__(kEmitBlock) void k_cover_emit(CoverArgs<T, BODY> A) {
+    emit_block(A);
 }
 
-// ---- the plan of a DROP call: n = slot[0], the piece's final spans, is on the device; the grids are sized by m >= n ----
+// ---- the plan (acgpu_emit.h) of a DROP call over the elements of a piece's final spans: their number n = slot[0] is on the
+// device; the grids are sized by m >= n ----
 
-// level 1: the elements of every workgroup's kPlanTile spans (a thread takes kPlanPer consecutive ones)
+__device__ __forceinline__ int64_t span_len(const int2 *spans, uint64_t i) { return (int64_t)(spans[i].y - spans[i].x); }
+
 __global__ __launch_bounds__(kPlanBlock) void k_cover_sums(const int2 *__restrict__ spans, const uint64_t *__restrict__ slot, int64_t *__restrict__ bsum) {
-    const uint64_t n = slot[0];
-    const uint64_t first = (uint64_t)blockIdx.x * kPlanTile + (uint64_t)threadIdx.x * kPlanPer;
-    int64_t v = 0;
-    for (int k = 0; k < kPlanPer; ++k)
-        if (first + k < n) v += (int64_t)(spans[first + k].y - spans[first + k].x);
-    int64_t total;
-    plan_block_scan(v, &total);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+    plan_sums([=](uint64_t i) { return span_len(spans, i); }, slot[0], bsum);
 }
 
-// level 2: ONE workgroup scans the workgroups' sums in place (exclusive); slot[kSpanDropped] = the elements of all final spans
+// slot[kSpanDropped] = the elements of all final spans
 __global__ __launch_bounds__(kPlanBlock) void k_cover_offsets(int64_t *__restrict__ bsum, uint32_t n_blocks, uint64_t *__restrict__ slot) {
-    int64_t carry = 0;
-    for (uint32_t b0 = 0; b0 < n_blocks; b0 += kPlanBlock) {
-        const uint32_t b = b0 + threadIdx.x;
-        const int64_t v = b < n_blocks ? bsum[b] : 0;
-        int64_t total;
-        const int64_t ex = plan_block_scan(v, &total);
-        if (b < n_blocks) bsum[b] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) slot[kSpanDropped] = (uint64_t)carry;
+    const int64_t sum = plan_offsets(bsum, n_blocks);
+    if (threadIdx.x == 0) slot[kSpanDropped] = (uint64_t)sum;
 }
 
-// level 3: pos[k] = (s_k - done) + k w - the elements of the spans in front of k
+// pos[k] = (s_k - done) + k w - the elements of the spans in front of k
 __global__ __launch_bounds__(kPlanBlock) void k_cover_plan(const int2 *__restrict__ spans, const uint64_t *__restrict__ slot, const int64_t *__restrict__ bsum,
                                                            int64_t done, int64_t w, int64_t *__restrict__ pos) {
-    const uint64_t n = slot[0];
-    const uint64_t first = (uint64_t)blockIdx.x * kPlanTile + (uint64_t)threadIdx.x * kPlanPer;
-    int64_t len[kPlanPer], v = 0;
-#pragma unroll
-    for (int k = 0; k < kPlanPer; ++k) {
-        len[k] = first + k < n ? (int64_t)(spans[first + k].y - spans[first + k].x) : 0;
-        v += len[k];
-    }
-    int64_t total;
-    int64_t run = plan_block_scan(v, &total) + bsum[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < kPlanPer; ++k) {
-        if (first + k < n) pos[first + k] = (int64_t)spans[first + k].x - done + (int64_t)(first + k) * w - run;
-        run += len[k];
-    }
+    plan_positions([=](uint64_t i) { return span_len(spans, i); }, slot[0], bsum,
+                   [&](uint64_t k, int64_t front) { pos[k] = (int64_t)spans[k].x - done + (int64_t)k * w - front; });
 }
 
 // What one call holds while it runs (the caller holds d.mu).  Positions and lengths are ELEMENTS: units, or bytes of a UTF-8 text.
@@ -337,7 +207,7 @@ int plan_dropped(void *ctx, uint64_t *d_slot, const int2 *d_spans, uint64_t m) {
 template <class T, int BODY>
 int launch_emit_as(CoverCall &c, uint64_t n_final, uint64_t m, uint64_t w0, uint64_t w1, void *dst) {
     DeviceState &d = c.sc.d;
-    CoverArgs<T> A;
+    CoverArgs<T, BODY> A;
     A.hay = static_cast<const T *>(c.hay);
     A.spans = reinterpret_cast<const int2 *>(d.cover_spans.p);
     A.pos = BODY == ACGPU_COVER_DROP && m ? reinterpret_cast<const int64_t *>(d.cover_plan.p) + (m + kPlanTile - 1) / kPlanTile : nullptr;
@@ -348,15 +218,8 @@ int launch_emit_as(CoverCall &c, uint64_t n_final, uint64_t m, uint64_t w0, uint
     A.cl = c.cl;
     A.fill = c.fill;
     A.done = (int64_t)c.done;
-    A.w0 = (int64_t)w0;
-    A.w1 = (int64_t)w1;
-    A.dst = static_cast<T *>(dst);
-    A.lds_cap = (int32_t)std::min<int64_t>(std::max<int64_t>(tunables().cover_lds_segments.load(std::memory_order_relaxed), 0), kCoverLds);
-    const uint64_t mis = ((uintptr_t)dst & 15u) / sizeof(T);
-    const uint64_t tiles = (w1 - w0 + mis + kEmitTile<T> - 1) / kEmitTile<T>;
-    hipLaunchKernelGGL((k_cover_emit<T, BODY>), dim3((unsigned)tiles), dim3(kEmitBlock), 0, c.sc.stream, A);
-    HIP_TRY(hipGetLastError());
-    return ACGPU_OK;
+    A.cap = (int32_t)std::min<int64_t>(std::max<int64_t>(tunables().cover_lds_segments.load(std::memory_order_relaxed), 0), kCoverLds);
+    return launch_emit_kernel(k_cover_emit<T, BODY>, A, w0, w1, dst, c.sc.stream);
 }
 
 template <class T>
@@ -366,58 +229,34 @@ int launch_emit_body(CoverCall &c, uint64_t n_final, uint64_t m, uint64_t w0, ui
                                         : launch_emit_as<T, ACGPU_COVER_DROP>(c, n_final, m, w0, w1, dst);
 }
 
-int launch_emit(CoverCall &c, uint64_t n_final, uint64_t m, uint64_t w0, uint64_t w1, void *dst) {
-    return c.esz == 1 ? launch_emit_body<uint8_t>(c, n_final, m, w0, w1, dst) : launch_emit_body<uint16_t>(c, n_final, m, w0, w1, dst);
-}
-
-// Behind a piece's merge: emit the text's elements [done, L) with the piece's n_final spans rewritten.
-int cover_piece(CoverCall &c, uint64_t n_final, uint64_t m, uint64_t L, uint64_t dropped) {
-    DeviceState &d = c.sc.d;
-    L = std::min(L, c.n);
+// SpansCall::merged: behind a piece's merge of m intervals, emit the text's elements [done, L) with the piece's final spans rewritten
+int cover_piece(void *ctx, uint64_t m, bool last) {
+    CoverCall &c = *static_cast<CoverCall *>(ctx);
+    const uint64_t n_final = c.sc.piece_final, L = last ? c.n : std::min((uint64_t)std::max<int64_t>(c.sc.piece_settled, 0), c.n);
     if (L < c.done) return ACGPU_E_HIP; // (never: the settled position does not move backwards)
-    if (c.body != ACGPU_COVER_DROP) dropped = 0;
+    const uint64_t dropped = c.body == ACGPU_COVER_DROP ? c.sc.piece_dropped : 0;
     const uint64_t added = n_final * ((uint64_t)c.ol + c.cl);
     if (dropped > L - c.done) return ACGPU_E_HIP; // (never: the final spans lie in [done, L))
     const uint64_t total = (L - c.done) + added - dropped;
-    const uint64_t room = c.cap > c.out_pos ? c.cap - c.out_pos : 0, emit_total = std::min(total, room); // beyond cap: planned, not written
-    if (emit_total && c.d_out) {
-        const int rc = launch_emit(c, n_final, m, 0, emit_total, c.d_out + c.out_pos * c.esz);
-        if (rc) return rc;
-    } else if (emit_total) {
-        const int rc = emit_through_slabs(d, c.sc.stream, c.esz, c.h_out + c.out_pos * c.esz, emit_total,
-                                          [&](uint64_t w0, uint64_t w1, void *dst) { return launch_emit(c, n_final, m, w0, w1, dst); });
-        if (rc) return rc;
-    }
+    const int rc = emit_piece(c.sc.d, c.sc.stream, c.esz, c.d_out, c.h_out, c.cap, c.out_pos, total, [&](uint64_t w0, uint64_t w1, void *dst) {
+        return c.esz == 1 ? launch_emit_body<uint8_t>(c, n_final, m, w0, w1, dst) : launch_emit_body<uint16_t>(c, n_final, m, w0, w1, dst);
+    });
+    if (rc) return rc;
     c.done = L;
     c.out_pos += total;
     return ACGPU_OK;
 }
 
-// The pieces of the whole text on the device, c.hay: chain = the chain's entry, whole = the text is scanned as one piece.
-int cover_pieces(CoverCall &c, int64_t chain, bool whole, const PieceScan &scan, uint64_t n_units) {
+// The pieces of the whole text on the device, c.hay (spans_pieces, acgpu_spans.h), each merged, planned and emitted.
+int cover_text(CoverCall &c, int64_t chain, bool whole, const PieceScan &scan, uint64_t n_units) {
     SpansCall &sc = c.sc;
-    DeviceState &d = sc.d;
-    int rc = spans_begin(sc);
-    if (rc) return rc;
-    if (c.h_out && (rc = emit_slabs_ready(d))) return rc;
+    int rc;
+    if (c.h_out && (rc = emit_slabs_ready(sc.d))) return rc;
     sc.to_pool = true;
-    if (c.body == ACGPU_COVER_DROP) {
-        sc.planned = plan_dropped;
-        sc.ctx = &c;
-    }
-    PieceDriver p(0, n_units, chain, whole, ACGPU_REC_SET, &d.count_res); // the pool's reservoir of Set records, as a spans call's
-    while (p.pos < p.end) {
-        uint64_t cnt = 0, base = 0;
-        if ((rc = scan_next_piece(p, scan, &cnt, &base))) return rc;
-        if (sc.u8 && (rc = utf8_map_records(*sc.u8, nullptr, reinterpret_cast<int32_t *>(d.count_res.p), cnt, ACGPU_REC_SET / 4, sc.stream))) return rc;
-        const bool last = p.pos >= p.end; // (a whole text's one piece ends at p.end)
-        const uint64_t m = sc.n_carry + cnt;
-        if ((rc = spans_piece(sc, base, cnt, p.pos, last))) return rc;
-        if ((rc = cover_piece(c, sc.piece_final, m, last ? c.n : (uint64_t)std::max<int64_t>(sc.piece_settled, 0), sc.piece_dropped))) return rc;
-    }
-    sc.st.pieces = (uint32_t)p.pieces;
-    sc.st.rescans = (uint32_t)p.rescans;
-    return ACGPU_OK;
+    sc.ctx = &c;
+    sc.merged = cover_piece;
+    if (c.body == ACGPU_COVER_DROP) sc.planned = plan_dropped;
+    return spans_pieces(sc, chain, whole, scan, n_units);
 }
 
 // what every entry returns behind its last piece
@@ -475,7 +314,7 @@ int cover_utf8(const acgpu_automaton *ca, const uint8_t *bytes, uint64_t n_bytes
     c.cap = cap;
     if ((rc = upload_spec(c, *spec))) return call.fail(rc);
     const bool whole = shard_rule(a->t, ACGPU_REC_SET, false).sequential;
-    if ((rc = cover_pieces(c, 0, whole, PieceScan{a, d, nullptr, 0, &text.shard, c.sc.stream}, text.shard.n_units))) return call.fail(rc);
+    if ((rc = cover_text(c, 0, whole, PieceScan{a, d, nullptr, 0, &text.shard, c.sc.stream}, text.shard.n_units))) return call.fail(rc);
     if (hipStreamSynchronize(c.sc.stream) != hipSuccess) return call.fail(ACGPU_E_HIP);
     return cover_result(c, n_out, st);
 }
@@ -504,7 +343,7 @@ int acgpu_cover_u16(const acgpu_automaton *ca, const uint16_t *haystack, uint64_
     c.cap = cap;
     if ((rc = upload_spec(c, *spec))) return call.fail(rc);
     const bool whole = shard_rule(a->t, ACGPU_REC_SET, false).sequential;
-    if ((rc = cover_pieces(c, 0, whole, PieceScan{a, d, nullptr, 0, &sh, c.sc.stream}, n_units))) return call.fail(rc);
+    if ((rc = cover_text(c, 0, whole, PieceScan{a, d, nullptr, 0, &sh, c.sc.stream}, n_units))) return call.fail(rc);
     if (hipStreamSynchronize(c.sc.stream) != hipSuccess) return call.fail(ACGPU_E_HIP);
     return cover_result(c, n_out, st);
 }
@@ -516,7 +355,7 @@ int acgpu_cover_device(const acgpu_automaton *ca, acgpu_shard *shard, const acgp
     int rc = check_spec(spec, 2);
     if (rc) return rc;
     // one shard of a sharded text: the spans it withholds would have to travel to the rank behind it -- not built
-    if (shard->own_begin != 0 || shard->own_end != shard->n_units || shard->text_begin != 1 || shard->text_end != 1) return ACGPU_E_UNSUPPORTED;
+    if (!shard_is_whole_text(*shard)) return ACGPU_E_UNSUPPORTED;
     acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
     PoolCall call(a);
     if (call.rc) return call.rc;
@@ -530,7 +369,7 @@ int acgpu_cover_device(const acgpu_automaton *ca, acgpu_shard *shard, const acgp
     c.cap = cap;
     if ((rc = upload_spec(c, *spec))) return rc;
     const bool whole = shard_rule(a->t, ACGPU_REC_SET, false).sequential;
-    rc = cover_pieces(c, shard->chain_entry, whole, PieceScan{a, d, nullptr, 0, shard, stream}, shard->n_units);
+    rc = cover_text(c, shard->chain_entry, whole, PieceScan{a, d, nullptr, 0, shard, stream}, shard->n_units);
     const hipError_t e = hipStreamSynchronize(stream); // the final wait
     if (rc) return rc;
     HIP_TRY(e);

@@ -393,6 +393,11 @@ int scan_host_range(acgpu_automaton *a, DeviceState &d, const uint16_t *haystack
 // end, no chain.  The caller holds d.mu.
 int stage_whole_text(DeviceState &d, const uint16_t *haystack, uint64_t n_units, acgpu_shard *out);
 
+// the shard is one whole text: all of it owned, the text's begin and end (what the device entries of spans, cover and replace serve)
+inline bool shard_is_whole_text(const acgpu_shard &sh) {
+    return sh.own_begin == 0 && sh.own_end == sh.n_units && sh.text_begin == 1 && sh.text_end == 1;
+}
+
 // What a UTF-8 entry does with ill-formed bytes: refuse the text (ACGPU_E_ENCODING), or scan every maximal ill-formed subpart as
 // one U+FFFD, as bytes.decode("utf-8", "replace") does (the *_lossy entries).
 enum class Utf8Errors { strict, replace };

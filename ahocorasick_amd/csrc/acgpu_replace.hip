@@ -3,10 +3,11 @@
 //
 // A replace call is the third consumer of the piece driver (scan_next_piece, acgpu_pieces.hip): the Map records of a piece stay
 // in the pool's reservoir, the piece's text is on the device already (d.stage_hay, or the caller's buffer), and behind every piece
-//  * the PLAN (k_replace_sums, k_replace_offsets, k_replace_plan: a two-level exclusive scan) turns record i into the output
-//    position of its replacement, pos_i = (s_i - done) + sum over j < i of (rlen[id_j] - (e_j - s_j)), 64-bit;
-//  * the EMIT (k_replace_emit) writes a window of the piece's output -- a workgroup per 2048 output units, a lane per 16-byte
-//    store -- from the text and the replacement table.
+//  * the PLAN (acgpu_emit.h; k_replace_sums, k_replace_offsets, k_replace_plan), whose items are the records' deltas, turns record
+//    i into the output position of its replacement, pos_i = (s_i - done) + sum over j < i of (rlen[id_j] - (e_j - s_j)), 64-bit.
+//    The positions ascend weakly: deleted matches that touch each other share one;
+//  * the EMIT (acgpu_emit.h; k_replace_emit) writes a window of the piece's output from its SOURCE (EmitArgs): segments of two
+//    sources, a record's replacement and the text behind the record up to the next one.
 // The host keeps `done`, the text position up to which output exists, and `out_pos`, the units written so far; what a piece may
 // emit, [done, limit), is decided by replace_limit below.
 //
@@ -39,11 +40,10 @@ using namespace acgpu;
 
 namespace {
 
-constexpr int kEmitLds = 3072;                                                   // segments a workgroup stages (16 bytes each)
-constexpr int kPlanHead = 4; // words in front of the plan's sums: {sum of the deltas, last end, the piece's boundary in bytes (UTF-8), unused}
+constexpr int kEmitLds = 3072; // segments a workgroup stages (16 bytes each)
+constexpr int kPlanHead = 4;   // words in front of the plan's sums: {sum of the deltas, last end, the piece's boundary in bytes (UTF-8), unused}
 
-// (the tile shape, kEmitPer<T> and kEmitTile<T>, load16, last_at_or_before and plan_block_scan: acgpu_emit.h.  Records, the table's
-// entries, the plan and the windows count elements; "unit" below means element.)
+// (Records, the table's entries, the plan and the windows count elements; "unit" below means element.)
 
 // The replacement table on the device: n_repl entries {first unit in `units`, length}, then the units.
 struct ReplTable {
@@ -56,194 +56,91 @@ __device__ __forceinline__ uint2 repl_of(const ReplTable &rt, int32_t id) {
     return rt.ent[rt.n_repl == 1 ? 0u : std::min<uint32_t>((uint32_t)id, rt.n_repl - 1)];
 }
 
-// what record i adds to the output's length: its replacement's units minus the match's
+// The plan's item: what record i adds to the output's length, its replacement's units minus the match's
 __device__ __forceinline__ int64_t repl_delta(const int32_t *recs, uint64_t i, const ReplTable &rt) {
     const int32_t s = recs[3 * i], e = recs[3 * i + 1], id = recs[3 * i + 2];
     return (int64_t)repl_of(rt, id).y - (int64_t)(e - s);
 }
 
-// plan, level 1: the sum of the deltas of every workgroup's kPlanTile records (a thread takes kPlanPer consecutive ones)
+// the plan (acgpu_emit.h) over a piece's n records
 __global__ __launch_bounds__(kPlanBlock) void k_replace_sums(const int32_t *__restrict__ recs, uint64_t n, ReplTable rt, int64_t *__restrict__ bsum) {
-    const uint64_t first = (uint64_t)blockIdx.x * kPlanTile + (uint64_t)threadIdx.x * kPlanPer;
-    int64_t v = 0;
-    for (int k = 0; k < kPlanPer; ++k)
-        if (first + k < n) v += repl_delta(recs, first + k, rt);
-    int64_t total;
-    plan_block_scan(v, &total);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+    plan_sums([=](uint64_t i) { return repl_delta(recs, i, rt); }, n, bsum);
 }
 
-// plan, level 2: ONE workgroup scans the workgroups' sums in place (exclusive), kPlanBlock per step with a running carry;
 // slot[0] = the sum of all deltas, slot[1] = the end of the last record
 __global__ __launch_bounds__(kPlanBlock) void k_replace_offsets(int64_t *__restrict__ bsum, uint32_t n_blocks, const int32_t *__restrict__ recs, uint64_t n,
                                                                 int64_t *__restrict__ slot) {
-    int64_t carry = 0;
-    for (uint32_t b0 = 0; b0 < n_blocks; b0 += kPlanBlock) {
-        const uint32_t b = b0 + threadIdx.x;
-        const int64_t v = b < n_blocks ? bsum[b] : 0;
-        int64_t total;
-        const int64_t ex = plan_block_scan(v, &total);
-        if (b < n_blocks) bsum[b] = carry + ex;
-        carry += total;
-    }
+    const int64_t sum = plan_offsets(bsum, n_blocks);
     if (threadIdx.x == 0) {
-        slot[0] = carry;
+        slot[0] = sum;
         slot[1] = n ? (int64_t)recs[3 * (n - 1) + 1] : 0;
     }
 }
 
-// plan, level 3: pos[i] = (s_i - done) + the deltas in front of record i (done: buffer relative, as the records are)
+// pos[i] = (s_i - done) + the deltas in front of record i (done: buffer relative, as the records are)
 __global__ __launch_bounds__(kPlanBlock) void k_replace_plan(const int32_t *__restrict__ recs, uint64_t n, ReplTable rt, const int64_t *__restrict__ bsum,
                                                              int64_t done, int64_t *__restrict__ pos) {
-    const uint64_t first = (uint64_t)blockIdx.x * kPlanTile + (uint64_t)threadIdx.x * kPlanPer;
-    int64_t dl[kPlanPer], v = 0;
-#pragma unroll
-    for (int k = 0; k < kPlanPer; ++k) {
-        dl[k] = first + k < n ? repl_delta(recs, first + k, rt) : 0;
-        v += dl[k];
-    }
-    int64_t total;
-    int64_t run = plan_block_scan(v, &total) + bsum[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < kPlanPer; ++k) {
-        if (first + k < n) pos[first + k] = (int64_t)recs[3 * (first + k)] - done + run;
-        run += dl[k];
-    }
+    plan_positions([=](uint64_t i) { return repl_delta(recs, i, rt); }, n, bsum,
+                   [&](uint64_t i, int64_t front) { pos[i] = (int64_t)recs[3 * i] - done + front; });
 }
 
-// One stretch of the output as a workgroup sees it, u = an output unit relative to the tile: from u = rel on, the units below
-// rend are units rsrc + u of the replacement table, the others units tsrc + u of the text -- up to the next segment's rel.
-// (rsrc, tsrc: modulo 2^32; what they are used for lies below 2^31.)
+// A segment of two sources: from u = rel on, the units below rend are units rsrc + u of the replacement table, the others units
+// tsrc + u of the text.
 struct Seg {
     int32_t rel, rend;
     uint32_t rsrc, tsrc;
 };
 
+// The emit's source (acgpu_emit.h): the text with a piece's records replaced.
 template <class T>
 struct EmitArgs {
+    using Elem = T;
+    using Seg = ::Seg;
+    static constexpr int kLds = kEmitLds;
     const T *hay;         // the piece's buffer
     const int32_t *recs;  // its Map records, buffer relative
     const int64_t *pos;   // the plan
     int64_t n_recs;
     ReplTable rt;
     int64_t done;         // buffer relative: output unit 0 of the piece is text unit `done` (if no record starts there)
-    int64_t w0, w1;       // the window of the piece's output to write
-    T *dst;               // where output unit w0 goes
+    int64_t w0, w1;
+    T *dst;
     __device__ __forceinline__ const T *repl() const { return static_cast<const T *>(rt.units); }
-};
-
-// segment of record i (-1: the text in front of the first record), t0 = the tile's first output unit
-template <class T>
-__device__ __forceinline__ Seg make_seg(const EmitArgs<T> &A, int64_t i, int64_t t0) {
-    Seg s;
-    if (i < 0) {
-        s.rel = -1;
-        s.rend = 0;
-        s.rsrc = 0;
-        s.tsrc = (uint32_t)(A.done + t0);
+    __device__ __forceinline__ int32_t lds_cap() const { return kLds; }
+    __device__ __forceinline__ int64_t n() const { return n_recs; }
+    __device__ __forceinline__ int64_t pos_at(int64_t i) const { return pos[i]; }
+    __device__ __forceinline__ Seg make_seg(int64_t i, int64_t t0) const {
+        Seg s;
+        if (i < 0) {
+            s.rel = -1;
+            s.rend = 0;
+            s.rsrc = 0;
+            s.tsrc = (uint32_t)(done + t0);
+            return s;
+        }
+        const int64_t P = pos[i] - t0; // < kEmitTile<T>
+        const uint2 r = repl_of(rt, recs[3 * i + 2]);
+        const int64_t rend = P + (int64_t)r.y;
+        s.rel = (int32_t)std::max<int64_t>(P, -1);
+        s.rend = (int32_t)std::min<int64_t>(std::max<int64_t>(rend, 0), kEmitTile<T>);
+        s.rsrc = r.x - (uint32_t)P;
+        s.tsrc = (uint32_t)recs[3 * i + 1] - (uint32_t)rend;
         return s;
     }
-    const int64_t P = A.pos[i] - t0; // < kEmitTile<T>
-    const uint2 r = repl_of(A.rt, A.recs[3 * i + 2]);
-    const int64_t rend = P + (int64_t)r.y;
-    s.rel = (int32_t)std::max<int64_t>(P, -1);
-    s.rend = (int32_t)std::min<int64_t>(std::max<int64_t>(rend, 0), kEmitTile<T>);
-    s.rsrc = r.x - (uint32_t)P;
-    s.tsrc = (uint32_t)A.recs[3 * i + 1] - (uint32_t)rend;
-    return s;
-}
-
-// The emit.  Tiles are laid over the DESTINATION's 16-byte grid: v = o - w0 + (dst's misalignment in units), tile b = the v in
-// [b * kEmitTile, + kEmitTile), lane l of it the kEmitPer units -- 8 units, or 16 bytes -- of one aligned 16-byte store.  A vector that the window covers only in
-// part (the window's first and last) is written unit by unit, so nothing outside [w0, w1) -- nothing at or beyond the caller's
-// capacity -- is touched.
-// The records that touch a tile are found by two binary searches over pos; their segments go to LDS when they fit (they do unless
-// thousands of deleted matches fall into one tile), else every lane takes them from global memory: the same code over another
-// view.  A lane finds the segment of its first unit by binary search and walks on from there (a few steps, then a search again).
-template <class T, bool kLds>
-__device__ __forceinline__ void emit_tile(const EmitArgs<T> &A, const Seg *lseg, int64_t t0, int64_t i0, int32_t cnt, int64_t cnt_g) {
-    const int64_t n_seg = kLds ? (int64_t)cnt : cnt_g;
-    auto rel_at = [&](int64_t j) -> int64_t {
-        if (kLds) return lseg[j].rel;
-        const int64_t i = i0 + j;
-        return i < 0 ? -1 : std::max<int64_t>(A.pos[i] - t0, -1);
-    };
-    auto seg_at = [&](int64_t j) -> Seg { return kLds ? lseg[j] : make_seg(A, i0 + j, t0); };
-    auto find = [&](int64_t from, int32_t u) -> int64_t { // the last segment j >= from with rel <= u (segment `from` has)
-        int64_t lo = from + 1, hi = n_seg;
-        for (int step = 0; step < 4 && lo < hi; ++step) {
-            if (rel_at(lo) > u) return lo - 1;
-            ++lo;
-        }
-        while (lo < hi) {
-            const int64_t mid = lo + (hi - lo) / 2;
-            if (rel_at(mid) <= u) lo = mid + 1;
-            else hi = mid;
-        }
-        return lo - 1;
-    };
-    constexpr int kPer = kEmitPer<T>, kPerWord = 4 / (int)sizeof(T);
-    const int32_t u0 = (int32_t)threadIdx.x * kPer;
-    const int64_t o_first = t0 + u0;
-    if (o_first >= A.w1 || o_first + kPer <= A.w0) return;
-    const int32_t ua = (int32_t)std::max<int64_t>(A.w0 - o_first, 0), ub = (int32_t)std::min<int64_t>(A.w1 - o_first, kPer); // the lane's valid units [ua, ub)
-    T *out = A.dst + (o_first - A.w0);
-    int64_t j = find(0, u0 + ua);
-    Seg s = seg_at(j);
-    const bool full = ua == 0 && ub == kPer;
-    if (full && (j + 1 >= n_seg || rel_at(j + 1) > u0 + kPer - 1)) { // one segment holds the vector
-        if (u0 >= s.rend) {
-            __builtin_nontemporal_store(load16(A.hay + (uint32_t)(s.tsrc + (uint32_t)u0)), reinterpret_cast<rp_v4u *>(out));
-            return;
-        }
-        if (u0 + kPer <= s.rend) {
-            __builtin_nontemporal_store(load16(A.repl() + (uint32_t)(s.rsrc + (uint32_t)u0)), reinterpret_cast<rp_v4u *>(out));
-            return;
-        }
+    __device__ __forceinline__ bool whole(const Seg &s, int32_t u0, rp_v4u *v) const {
+        if (u0 >= s.rend) *v = load16(hay + (uint32_t)(s.tsrc + (uint32_t)u0));
+        else if (u0 + kEmitPer<T> <= s.rend) *v = load16(repl() + (uint32_t)(s.rsrc + (uint32_t)u0));
+        else return false;
+        return true;
     }
-    uint32_t w[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-        if (k >= ua && k < ub) {
-            const int32_t u = u0 + k;
-            if (k > ua) {
-                const int64_t jn = find(j, u);
-                if (jn != j) {
-                    j = jn;
-                    s = seg_at(j);
-                }
-            }
-            const uint32_t x = u < s.rend ? A.repl()[(uint32_t)(s.rsrc + (uint32_t)u)] : A.hay[(uint32_t)(s.tsrc + (uint32_t)u)];
-            if (full) w[k / kPerWord] |= x << (8 * (int)sizeof(T) * (k % kPerWord));
-            else out[k] = (T)x;
-        }
+    __device__ __forceinline__ uint32_t element(const Seg &s, int32_t u) const {
+        return u < s.rend ? repl()[(uint32_t)(s.rsrc + (uint32_t)u)] : hay[(uint32_t)(s.tsrc + (uint32_t)u)];
     }
-    if (full) {
-        rp_v4u v;
-        v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
-        __builtin_nontemporal_store(v, reinterpret_cast<rp_v4u *>(out));
-    }
-}
+};
 
 template <class T>
 __global__ __launch_bounds__(kEmitBlock) void k_replace_emit(EmitArgs<T> A) {
-    __shared__ Seg lseg[kEmitLds];
-    __shared__ int64_t bounds[2];
-    const int64_t mis = (int64_t)(((uintptr_t)A.dst & 15u) / sizeof(T));
-    const int64_t t0 = A.w0 - mis + (int64_t)blockIdx.x * kEmitTile<T>;
-    const int64_t ov0 = std::max(t0, A.w0), ov1 = std::min(t0 + kEmitTile<T>, A.w1); // the tile's units of the window
-    if (ov0 >= ov1) return;
-    if (threadIdx.x == 0) bounds[0] = last_at_or_before(A.pos, 0, A.n_recs, ov0);
-    if (threadIdx.x == kWave) bounds[1] = last_at_or_before(A.pos, 0, A.n_recs, ov1 - 1);
-    __syncthreads();
-    const int64_t i0 = bounds[0], cnt = bounds[1] - i0 + 1; // segments i0 .. bounds[1]; i0 = -1: the text in front of record 0
-    if (cnt <= kEmitLds) {
-        for (int32_t j = (int32_t)threadIdx.x; j < (int32_t)cnt; j += kEmitBlock) lseg[j] = make_seg(A, i0 + j, t0);
-        __syncthreads();
-        emit_tile<T, true>(A, lseg, t0, i0, (int32_t)cnt, cnt);
-    } else {
-        emit_tile<T, false>(A, lseg, t0, i0, 0, cnt);
-    }
+    emit_block(A);
 }
 
 // The separators a piece of a batch call merges: separator j of them stands at text position cat_off[i0 + j + 1] - 1 (cat_off[i] =
@@ -448,7 +345,7 @@ uint64_t replace_limit(bool last_or_whole, uint64_t n, uint64_t bound, uint64_t 
 }
 
 template <class T>
-int launch_emit_as(ReplaceCall &c, const void *hay, const int32_t *recs, uint64_t cnt, int64_t done_rel, uint64_t w0, uint64_t w1, void *dst, hipStream_t stream) {
+int launch_emit_as(ReplaceCall &c, const void *hay, const int32_t *recs, uint64_t cnt, int64_t done_rel, uint64_t w0, uint64_t w1, void *dst) {
     EmitArgs<T> A;
     A.hay = static_cast<const T *>(hay);
     A.recs = recs;
@@ -456,20 +353,7 @@ int launch_emit_as(ReplaceCall &c, const void *hay, const int32_t *recs, uint64_
     A.n_recs = (int64_t)cnt;
     A.rt = c.rt;
     A.done = done_rel;
-    A.w0 = (int64_t)w0;
-    A.w1 = (int64_t)w1;
-    A.dst = static_cast<T *>(dst);
-    const uint64_t mis = ((uintptr_t)dst & 15u) / sizeof(T);
-    const uint64_t tiles = (w1 - w0 + mis + kEmitTile<T> - 1) / kEmitTile<T>;
-    hipLaunchKernelGGL(k_replace_emit<T>, dim3((unsigned)tiles), dim3(kEmitBlock), 0, stream, A);
-    HIP_TRY(hipGetLastError());
-    return ACGPU_OK;
-}
-
-// hay, dst: elements of c.esz bytes
-int launch_emit(ReplaceCall &c, const void *hay, const int32_t *recs, uint64_t cnt, int64_t done_rel, uint64_t w0, uint64_t w1, void *dst, hipStream_t stream) {
-    return c.esz == 1 ? launch_emit_as<uint8_t>(c, hay, recs, cnt, done_rel, w0, w1, dst, stream)
-                      : launch_emit_as<uint16_t>(c, hay, recs, cnt, done_rel, w0, w1, dst, stream);
+    return launch_emit_kernel(k_replace_emit<T>, A, w0, w1, dst, c.stream);
 }
 
 // A batch call's piece: its cnt records (d.count_res) merged with the separators in [done, own_hi) into d.replace_merged.  Which
@@ -552,17 +436,12 @@ int replace_piece(ReplaceCall &c, const void *hay, uint64_t base, const int32_t 
             HIP_TRY(hipGetLastError());
         }
     }
-    const uint64_t room = c.cap > c.out_pos ? c.cap - c.out_pos : 0, emit_total = std::min(total, room); // beyond cap: planned, not written
-    if (emit_total && c.d_out) {
-        const int rc = launch_emit(c, hay, recs, cnt, done_rel, 0, emit_total, c.d_out + c.out_pos * c.esz, c.stream);
-        if (rc) return rc;
-    } else if (emit_total) {
-        // through the pool's two slabs (emit_through_slabs, acgpu_emit.h)
-        const int rc = emit_through_slabs(d, c.stream, c.esz, c.h_out + c.out_pos * c.esz, emit_total, [&](uint64_t w0, uint64_t w1, void *dst) {
-            return launch_emit(c, hay, recs, cnt, done_rel, w0, w1, dst, c.stream);
-        });
-        if (rc) return rc;
-    }
+    // (hay, dst: elements of c.esz bytes)
+    const int rc = emit_piece(d, c.stream, c.esz, c.d_out, c.h_out, c.cap, c.out_pos, total, [&](uint64_t w0, uint64_t w1, void *dst) {
+        return c.esz == 1 ? launch_emit_as<uint8_t>(c, hay, recs, cnt, done_rel, w0, w1, dst)
+                          : launch_emit_as<uint16_t>(c, hay, recs, cnt, done_rel, w0, w1, dst);
+    });
+    if (rc) return rc;
     c.done = limit;
     c.out_pos += total;
     c.st.n_records += n_found;
@@ -702,7 +581,7 @@ int acgpu_replace_device(const acgpu_automaton *ca, acgpu_shard *shard, const ui
     int rc = check_table(a, repl_units, repl_off, n_repl);
     if (rc) return rc;
     // one shard of a sharded text: its rewrite starts at the position up to which the rank before it has emitted -- not built
-    if (shard->own_begin != 0 || shard->own_end != shard->n_units || shard->text_begin != 1 || shard->text_end != 1) return ACGPU_E_UNSUPPORTED;
+    if (!shard_is_whole_text(*shard)) return ACGPU_E_UNSUPPORTED;
     PoolCall call(a);
     if (call.rc) return call.rc;
     DeviceState &d = *call.d;

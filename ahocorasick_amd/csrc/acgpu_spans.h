@@ -1,5 +1,6 @@
-// acgpu_spans.h -- the merge behind a piece (acgpu_spans.hip) as its two callers see it: the spans entries, whose final spans
-// go to the caller, and the cover entries (acgpu_cover.hip), whose final spans stay in the pool for the plan and the emit.
+// acgpu_spans.h -- the piece loop with the merge behind every piece (acgpu_spans.hip) as its two callers see it: the spans entries,
+// whose final spans go to the caller, and the cover entries (acgpu_cover.hip), whose final spans stay in the pool for the plan and
+// the emit.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,15 +34,15 @@ struct SpansCall {
     // ... called behind the scatter and before that wait, with the head of d.spans_work (device), the piece's spans (device; the
     // first slot[0] of them are final) and m, the intervals merged, which bounds their number
     int (*planned)(void *ctx, uint64_t *d_slot, const int2 *d_spans, uint64_t m) = nullptr;
+    // ... called behind the piece's wait, with m again and whether the piece was the last: the caller's step behind the merge
+    int (*merged)(void *ctx, uint64_t m, bool last) = nullptr;
     void *ctx = nullptr;
     uint64_t piece_final = 0;     // out: the piece's final spans
     int64_t piece_settled = 0;    // out, not on the last piece: L = min(B, start of the first carried span)
     uint64_t piece_dropped = 0;   // out: slot[kSpanDropped] if `planned` is set
 };
 
-// before the first piece: the pinned words and the two carry buffers
-int spans_begin(SpansCall &c);
-// Behind a piece: merge the carry and the piece's cnt records (in d.count_res, relative to `base`; a UTF-8 call's: in bytes).
-int spans_piece(SpansCall &c, uint64_t base, uint64_t cnt, uint64_t own_hi, bool last_or_whole);
+// The pieces of a whole text, each merged behind its scan: chain = the chain's entry, whole = the text is scanned as one piece.
+int spans_pieces(SpansCall &c, int64_t chain, bool whole, const PieceScan &scan, uint64_t n_units);
 
 } // namespace acgpu

@@ -33,10 +33,11 @@
 // text scanned as one piece, finalise everything.  The host reads 16 bytes per piece, {n_final, n_carry}: one wait beside the
 // scan's own.
 //
-// A SECOND CALLER.  The cover entries (acgpu_cover.hip) run the same merge through acgpu_spans.h: SpansCall::to_pool sends a
-// piece's spans to d.cover_spans instead of the caller, k_span_settled adds the position up to which the text is settled, and
-// SpansCall::planned enqueues the caller's plan in front of the wait -- which then reads the whole head, 48 bytes, still once.
-// What the spans entries compute, read back and return is untouched by that.
+// A SECOND CALLER.  The cover entries (acgpu_cover.hip) run the same piece loop and merge through acgpu_spans.h (spans_pieces):
+// SpansCall::to_pool sends a piece's spans to d.cover_spans instead of the caller, k_span_settled adds the position up to which the
+// text is settled, SpansCall::planned enqueues the caller's plan in front of the wait -- which then reads the whole head, 48 bytes,
+// still once -- and SpansCall::merged is the caller's step behind it, the piece's emit.  What the spans entries compute, read back
+// and return is untouched by that.
 //
 // UTF-8: the text is staged by stage_utf8_text and scanned in units; a piece's records become byte offsets where they lie
 // (utf8_map_records, two words per record) BEFORE the merge -- the map is monotone, so the order by end survives -- and `bound`
@@ -296,10 +297,7 @@ uint64_t spans_bound(const HostTables &t, uint64_t own_hi) {
     return own_hi > back ? own_hi - back : 0;
 }
 
-} // namespace
-
-namespace acgpu {
-
+// before the first piece: the pinned words and the two carry buffers
 int spans_begin(SpansCall &c) {
     DeviceState &d = c.d;
     if (!d.spans_pin) HIP_TRY(hipHostMalloc(&d.spans_pin.h, 64, hipHostMallocDefault));
@@ -307,6 +305,7 @@ int spans_begin(SpansCall &c) {
     return d.spans_carry.ensure((size_t)c.carry_cap * 2 * 8);
 }
 
+// Behind a piece: merge the carry and the piece's cnt records (in d.count_res, relative to `base`; a UTF-8 call's: in bytes).
 int spans_piece(SpansCall &c, uint64_t base, uint64_t cnt, uint64_t own_hi, bool last_or_whole) {
     DeviceState &d = c.d;
     c.st.n_records += cnt;
@@ -402,11 +401,10 @@ int spans_piece(SpansCall &c, uint64_t base, uint64_t cnt, uint64_t own_hi, bool
     return ACGPU_OK;
 }
 
-} // namespace acgpu
+} // namespace
 
-namespace {
+namespace acgpu {
 
-// The pieces of a whole text: chain = the chain's entry, whole = the text is scanned as one piece.
 int spans_pieces(SpansCall &c, int64_t chain, bool whole, const PieceScan &scan, uint64_t n_units) {
     DeviceState &d = c.d;
     int rc = spans_begin(c);
@@ -417,12 +415,19 @@ int spans_pieces(SpansCall &c, int64_t chain, bool whole, const PieceScan &scan,
         if ((rc = scan_next_piece(p, scan, &cnt, &base))) return rc;
         // UTF-8: the piece's records go from units to bytes where they lie (text relative: the shard is the whole text)
         if (c.u8 && (rc = utf8_map_records(*c.u8, nullptr, reinterpret_cast<int32_t *>(d.count_res.p), cnt, ACGPU_REC_SET / 4, c.stream))) return rc;
-        if ((rc = spans_piece(c, base, cnt, p.pos, p.pos >= p.end))) return rc; // (a whole text's one piece ends at p.end)
+        const bool last = p.pos >= p.end; // (a whole text's one piece ends at p.end)
+        const uint64_t m = c.n_carry + cnt;
+        if ((rc = spans_piece(c, base, cnt, p.pos, last))) return rc;
+        if (c.merged && (rc = c.merged(c.ctx, m, last))) return rc;
     }
     c.st.pieces = (uint32_t)p.pieces;
     c.st.rescans = (uint32_t)p.rescans;
     return ACGPU_OK;
 }
+
+} // namespace acgpu
+
+namespace {
 
 // what every entry returns behind its last piece
 int spans_result(SpansCall &c, uint64_t *n_out, acgpu_spans_stats *st) {
@@ -490,7 +495,7 @@ int acgpu_spans_device(const acgpu_automaton *ca, acgpu_shard *shard, int32_t *d
     if (!ca || !shard || !n_out || (cap && !d_out) || ((uintptr_t)d_out & 15)) return ACGPU_E_INVALID;
     if (shard->n_units >= (1ull << 31) || (shard->n_units && !shard->d_hay) || ((uintptr_t)shard->d_hay & 15)) return ACGPU_E_INVALID;
     // one shard of a sharded text: the spans it withholds would have to travel to the rank behind it -- not built
-    if (shard->own_begin != 0 || shard->own_end != shard->n_units || shard->text_begin != 1 || shard->text_end != 1) return ACGPU_E_UNSUPPORTED;
+    if (!shard_is_whole_text(*shard)) return ACGPU_E_UNSUPPORTED;
     acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
     PoolCall call(a);
     if (call.rc) return call.rc;

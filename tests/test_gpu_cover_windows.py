@@ -98,7 +98,7 @@ ORDINARY = "ab.bcd..b.abab..bcdb.b..ab.b.bcdd.dd...." * 130  # tests/test_gpu_co
 @pytest.mark.parametrize("body,open,close", V.USES)
 def test_an_ordinary_text_through_slabs(body, open, close, slab, lds_cap):
     """The first to reach k_cover_emit with A.w0 != 0: `t0 = A.w0 - mis + blockIdx.x * kEmitTile` and `bounds[0] =
-    span_at_or_before(A, ov0)` with ov0 = w0 > 0, so that segment i0 is a span in the middle of the list whose position lies in
+    last_at_or_before(A, ov0)` with ov0 = w0 > 0, so that segment i0 is a span in the middle of the list whose position lies in
     front of the window (make_seg: P < 0, rel = -1).  Slab 8: every window is one vector of one lane; slab 1000: a window is half
     a tile and ends inside a vector's worth of elements."""
     a, orc = V.pair(N.MODE_ALL, ["ab", "b", "bcd", "dd"])
@@ -136,7 +136,7 @@ def inside_regime(name, spans, body):
 
 @pytest.mark.parametrize("name,body", [(name, body) for name in sorted(INSIDE) for body in INSIDE[name][5]])  # (DROP has no body to start inside)
 def test_windows_that_start_inside_each_source(name, body):
-    """The first to reach cover_tile with a window's first lane inside an open (`u < s.a_end`, s.osrc = -P with P < 0 by thousands
+    """The first to reach emit_tile with a window's first lane inside an open (`u < s.a_end`, s.osrc = -P with P < 0 by thousands
     of units), inside a KEEP / FILL body (`u < s.b_end`, s.bsrc), inside a close (`u < s.c_end`, s.csrc) and inside uncovered text
     (`s.tsrc`), each at an output offset that is no multiple of a tile -- the sources are addressed modulo 2^32 from a negative
     P, which one window from 0 never has for its first tile."""
@@ -160,7 +160,7 @@ def test_the_windows_of_the_cases_above_start_inside_all_four_sources():
 @pytest.mark.parametrize("lds_cap", [None, 0])
 @pytest.mark.parametrize("open", ["", "|"])
 def test_one_unit_spans_alternating_with_one_uncovered_unit_through_slabs(open, lds_cap):
-    """The first to reach span_at_or_before<DROP> -- a search of A.pos -- for a window that begins in the middle of the plan: with
+    """The first to reach last_at_or_before over a DROP source -- a search of A.pos -- for a window that begins in the middle of the plan: with
     no open a window of 1000 units holds 1000 spans (its first is span w0, pos[w0] == w0), with "|" 500."""
     a, orc = V.pair(N.MODE_ALL, ["a"])
     hay = "a." * (3 * T + 5) + "a"
@@ -196,7 +196,7 @@ def test_slabs_of_8_units_in_pieces_of_16_every_family(mode, body, open, close):
 # ---- B5. capacity inside a later slab -------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("body,open,close", V.USES)
 def test_capacity_that_ends_inside_a_later_slab(body, open, close):
-    """The first to reach cover_piece's `emit_total = std::min(total, room)` as the end of a window that is not the first: the last
+    """The first to reach emit_piece's `emit_total = std::min(total, room)` from a cover call as the end of a window that is not the first: the last
     window [w0, cap) is shorter than a slab, or one element long (cap = 1001)."""
     a, orc = V.pair(N.MODE_ALL, ["ab", "b", "bcd", "dd"])
     hay = utf16(ORDINARY)
