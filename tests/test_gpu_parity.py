@@ -1788,7 +1788,10 @@ def test_wholeword_async_begin_end_pipelined_overflow_and_slice_redo():
 def test_chain_marking_in_one_pass_equals_pointer_doubling():
     """Shortest, the sparse form of Longest and WholeWordLongest select a chain k0, nxt[k0], ... over their candidates.  From
     4 M candidates on the chain is marked in one pass by the Longest chain kernels, below that by pointer doubling; the test
-    hook (tile_debug bit 4194304) takes the one pass from 64 candidates on, bit 2097152 forces the doubling: same records."""
+    hook (tile_debug bit 4194304) takes the one pass from 64 candidates on, bit 2097152 forces the doubling: same records.
+    The Longest case here does NOT run the selection: keywords of 2 to 9 letters over six letters have no selective suffix
+    filter (asserted below), so it is the walk under the three settings.  The sparse Longest under both markers is
+    tests/test_gpu_selection_edges.py."""
     from oracle.oracle import FAM_SHORTEST, FAM_WWLONGEST
     kws = synth.random_keywords(21, 400, 2, 9, table=synth.ALPHA_LOWER[:6])
     hay = synth.haystack(77, 400000, table=synth.ALPHA_LOWER[:6])
@@ -1803,6 +1806,7 @@ def test_chain_marking_in_one_pass_equals_pointer_doubling():
             a = Automaton(mode, k, okw.get("case_sensitive", True), word_chars=okw.get("word_chars"))
             got = a.match_host(h, True)
             assert got.shape == want.shape and (got == want).all(), (mode, bits)
+            assert mode != N.MODE_LONGEST or a.info()["tile_kernel"] == 0  # (the walk: see the docstring)
         N.set_tunable("tile_debug", 0)
 
 
