@@ -210,9 +210,11 @@ def _signatures():
         "acgpu_replace_batch_utf8": (ci, [vp, vp, vp, u32, vp, vp, u32, vp, u64, vp, P(u64), P(ReplaceStats), P(Utf8BatchStats)]),
         "acgpu_spans_u16": (ci, [vp, vp, u64, vp, u64, P(u64), P(SpansStats)]),
         "acgpu_spans_device": (ci, [vp, P(Shard), vp, u64, P(u64), vp, P(SpansStats)]),
+        "acgpu_spans_batch_u16": (ci, [vp, vp, vp, u32, vp, u64, P(u64), P(SpansStats)]),
         "acgpu_spans_utf8": (ci, [vp, vp, u64, vp, u64, P(u64), P(SpansStats), P(Utf8Stats)]),
         "acgpu_cover_u16": (ci, [vp, vp, u64, P(CoverSpec), vp, u64, P(u64), P(CoverStats)]),
         "acgpu_cover_device": (ci, [vp, P(Shard), P(CoverSpec), vp, u64, P(u64), vp, P(CoverStats)]),
+        "acgpu_cover_batch_u16": (ci, [vp, vp, vp, u32, P(CoverSpec), vp, u64, vp, P(u64), P(CoverStats)]),
         "acgpu_cover_utf8": (ci, [vp, vp, u64, P(CoverSpec), vp, u64, P(u64), P(CoverStats), P(Utf8Stats)]),
         "acgpu_match_u16_multi": (ci, [vp, vp, u64, P(ci), ci, ci, vp, u64, P(u64)]),
         "acgpu_comm_open": (ci, [P(ci), ci, ci, P(vp)]),

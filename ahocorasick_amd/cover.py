@@ -1,10 +1,11 @@
-"""Mask, highlight or redact every covered run of a text on the device (include/acgpu.h: acgpu_cover_u16, acgpu_cover_device,
+"""Mask, highlight or redact every covered run of a text on the device (include/acgpu.h: acgpu_cover_u16, acgpu_cover_batch_u16, acgpu_cover_device,
 acgpu_cover_utf8, acgpu_cover_utf8_lossy): every span of the text -- the spans of ahocorasick_amd.spans, for all five families,
 AhoCorasick's overlapping records included -- becomes open + body + close, everything else is copied.
 
     mask(AhoCorasickSet(names, False), text)                    # "call **** or ***" -- the length is preserved
     highlight(AhoCorasickSet(names, False), text, "<b>", "</b>")
     redact(AhoCorasickSet(names, False), text, "[name]")
+    mask_batch(AhoCorasickSet(names, False), lines)             # many short texts: ONE device call, a list of str
 
 Not replace: overlapping, nested and TOUCHING matches are one span, so two matches that touch give ONE replacement, not two.
 No span and no record reaches the host.
@@ -15,9 +16,10 @@ import numpy as np
 
 from . import _native as N
 from .spans import _automaton
-from .strings import _fill_shard, _not_none, _raise_for, _readable, _stats_dict, _to_str, _utf8_bytes, _utf8_entry, _vp, utf16
+from .strings import _fill_shard, _not_none, _pack, _raise_for, _readable, _stats_dict, _to_str, _utf8_bytes, _utf8_entry, _vp, utf16
 
-__all__ = ["cover", "cover_utf8", "cover_device", "mask", "mask_utf8", "highlight", "highlight_utf8", "redact", "redact_utf8"]
+__all__ = ["cover", "cover_utf8", "cover_device", "mask", "mask_utf8", "highlight", "highlight_utf8", "redact", "redact_utf8",
+           "cover_batch", "cover_batch_units", "mask_batch", "highlight_batch", "redact_batch"]
 
 BODIES = {"keep": 0, "fill": 1, "drop": 2}  # ACGPU_COVER_KEEP, _FILL, _DROP
 
@@ -61,16 +63,17 @@ def _fill_byte(fill):
     return int(f[0])
 
 
-def _cover_call(entry, head, spec, dtype, n, stats, tail=()):
-    """entry(*head, &spec, out, cap, &n_out, &stats, *tail) -> the elements written.  The first capacity is the text's size and a
+def _cover_call(entry, head, spec, dtype, n, stats, tail=(), mid=(), cap=None):
+    """entry(*head, &spec, out, cap, *mid, &n_out, &stats, *tail) -> the elements written.  The first capacity is the text's size and a
     quarter plus one open and one close; ACGPU_E_OVERFLOW reports the result's size, and the same call with exactly that capacity
     succeeds (include/acgpu.h): ONE retry, a second overflow is an error."""
     st = stats if stats is not None else N.CoverStats()
-    cap = n + n // 4 + int(spec.open_len) + int(spec.close_len)
+    if cap is None:
+        cap = n + n // 4 + int(spec.open_len) + int(spec.close_len)
     for attempt in range(2):
         out = np.empty(max(cap, 1), dtype=dtype)
         n_out = ctypes.c_uint64(0)
-        rc = entry(*head, ctypes.byref(spec), _vp(out), cap, ctypes.byref(n_out), ctypes.byref(st), *tail)
+        rc = entry(*head, ctypes.byref(spec), _vp(out), cap, *mid, ctypes.byref(n_out), ctypes.byref(st), *tail)
         if rc != N.E_OVERFLOW:
             break
         cap = int(n_out.value)
@@ -111,6 +114,43 @@ def cover_device(matcher, d_hay, n_units, d_out, cap, open="", close="", body="k
     rc = N.lib().acgpu_cover_device(_automaton(matcher).handle, ctypes.byref(sh), ctypes.byref(spec), d_out, cap, ctypes.byref(n_out),
                                     ctypes.c_void_p(stream), ctypes.byref(st))
     return int(n_out.value), rc, _stats_dict(st)
+
+
+def cover_batch_units(matcher, haystacks, open="", close="", body="keep", fill="*", cap=None):
+    """acgpu_cover_batch_u16: many short haystacks (str or uint16 arrays) rewritten in ONE device call -> (units, out_offsets, stats
+    dict): the result of haystack i is units[out_offsets[i]:out_offsets[i + 1]], unit for unit what cover returns for it alone.
+    cap None: the first capacity of cover, over the batch's units; one retry with the size the first call reports."""
+    units, off = _pack([_not_none(h) for h in haystacks])
+    spec, keep = _spec(_units("open", open), _units("close", close), _body(body), _fill_unit(fill))
+    st = N.CoverStats()
+    out_off = np.zeros(len(off), dtype=np.uint64)
+    out = _cover_call(N.lib().acgpu_cover_batch_u16, (_automaton(matcher).handle, _vp(units), _vp(off), len(off) - 1), spec, np.uint16, int(off[-1]),
+                      st, mid=(_vp(out_off),), cap=cap)
+    return out, out_off, _stats_dict(st)
+
+
+def cover_batch(matcher, haystacks, open="", close="", body="keep", fill="*"):
+    """[cover(matcher, h, open, close, body, fill) for h in haystacks] in ONE device call (short inputs: a call has tens of
+    microseconds of fixed cost) -> a list of str.  A span never reaches across two haystacks: "xab", "abx" with keyword ab is
+    rewritten twice, where the joined text "xababx" has one span."""
+    units, out_off, _ = cover_batch_units(matcher, haystacks, open, close, body, fill)
+    whole = _to_str(units)  # (a unit is two bytes of UTF-16: unit offsets cut the str only where no surrogate pair is split)
+    if len(whole) == units.size:
+        return [whole[int(out_off[i]):int(out_off[i + 1])] for i in range(len(out_off) - 1)]
+    return [_to_str(units[int(out_off[i]):int(out_off[i + 1])]) for i in range(len(out_off) - 1)]
+
+
+def mask_batch(matcher, haystacks, fill="*"):
+    """mask for many short haystacks in one device call: every result has its haystack's length"""
+    return cover_batch(matcher, haystacks, body="fill", fill=fill)
+
+
+def highlight_batch(matcher, haystacks, open, close):
+    return cover_batch(matcher, haystacks, open=open, close=close, body="keep")
+
+
+def redact_batch(matcher, haystacks, replacement):
+    return cover_batch(matcher, haystacks, open=replacement, body="drop")
 
 
 def mask(matcher, haystack, fill="*"):

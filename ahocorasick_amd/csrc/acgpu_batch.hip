@@ -1,5 +1,6 @@
 // acgpu_batch.hip -- the front end of the batch entries (acgpu_match_batch_u16 here, acgpu_replace_batch_u16 in
-// acgpu_replace.hip, acgpu_summary_batch_u16 in acgpu_summary.hip): the checks they share and the decision how the batch is
+// acgpu_replace.hip, acgpu_summary_batch_u16 in acgpu_summary.hip, acgpu_spans_batch_u16 in acgpu_spans.hip, acgpu_cover_batch_u16
+// in acgpu_cover.hip): the checks they share and the decision how the batch is
 // scanned (check_batch), the haystacks staged as one text (BatchText), and acgpu_match_batch_u16 itself.
 //
 // A batch is scanned as ONE text, the haystacks with a separator unit behind each, or, where that cannot be done, haystack by

@@ -1,4 +1,4 @@
-// acgpu_cover.hip -- acgpu_cover_u16 / acgpu_cover_device / acgpu_cover_utf8 / acgpu_cover_utf8_lossy (include/acgpu.h): the text
+// acgpu_cover.hip -- acgpu_cover_u16 / acgpu_cover_batch_u16 / acgpu_cover_device / acgpu_cover_utf8 / acgpu_cover_utf8_lossy (include/acgpu.h): the text
 // with every span [s, e) -- the spans of acgpu_spans_* -- rewritten as open ++ body ++ close, on the device, for all five families.
 // body is the covered text itself (KEEP: highlight, tagging), one fill element per covered element (FILL: mask) or nothing (DROP:
 // redaction, deletion); everything outside the spans is copied.
@@ -29,6 +29,11 @@
 // KEEP copies its body long after the piece that first saw it.  The UTF-8 entries hold the caller's bytes anyway; acgpu_cover_u16
 // stages the whole text once (stage_whole_text: one blocking copy in front, not hidden behind the scan) and drives the pieces
 // over it as a device shard.
+//
+// acgpu_cover_batch_u16 rewrites many short texts as ONE such text: the haystacks with a separator unit behind each (BatchText),
+// staged whole like acgpu_cover_u16's text.  No record holds a separator, so the spans of that text are the haystacks' spans; a
+// separator is an item of the plan that emits nothing and skips one element, so the results come out back to back (see "a batch
+// call" below, and DESIGN.md 4.24).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -55,14 +60,20 @@ struct CSeg {
 };
 
 // The emit's source (acgpu_emit.h): the text with a piece's final spans (text coordinates, elements) rewritten.
-template <class T, int BODY>
+// BATCH (acgpu_cover_batch_u16): `spans` is the piece's ITEM list -- its final spans and, as {p, p}, the separators at p -- and
+// `pos` the plan over it, whatever the body.  A separator has neither open nor body nor close, and the text behind it begins at
+// p + 1: it emits nothing and skips one element.  Its segment is empty where the next item touches it, and so is a DROP span's
+// with an empty open and close: positions ascend WEAKLY, which is all the emit asks (emit_block takes the last of equal ones).
+// make_seg assumes nothing about the next item: P may lie anywhere at or below the tile's last element, and what it adds to P is
+// clamped to the tile.
+template <class T, int BODY, bool BATCH = false>
 struct CoverArgs {
     using Elem = T;
     using Seg = CSeg;
     static constexpr int kLds = kCoverLds;
     const T *hay;        // the whole text
     const int2 *spans;
-    const int64_t *pos;  // DROP: the plan; else nullptr, the positions are closed form
+    const int64_t *pos;  // DROP, and every BATCH call: the plan; else nullptr, the positions are closed form
     int64_t n_spans;
     const T *open, *close;
     uint32_t ol, cl;
@@ -74,7 +85,7 @@ struct CoverArgs {
     __device__ __forceinline__ int32_t lds_cap() const { return cap; }
     __device__ __forceinline__ int64_t n() const { return n_spans; }
     __device__ __forceinline__ int64_t pos_at(int64_t i) const {
-        if (BODY == ACGPU_COVER_DROP) return pos[i];
+        if (BODY == ACGPU_COVER_DROP || BATCH) return pos[i];
         return (int64_t)spans[i].x - done + i * ((int64_t)ol + (int64_t)cl);
     }
     __device__ __forceinline__ CSeg make_seg(int64_t i, int64_t t0) const {
@@ -88,7 +99,8 @@ struct CoverArgs {
         }
         const int2 sp = spans[i];
         const int64_t P = pos_at(i) - t0; // < kEmitTile<T>
-        const int64_t a = P + (int64_t)ol, b = a + (BODY == ACGPU_COVER_DROP ? 0 : (int64_t)(sp.y - sp.x)), c = b + (int64_t)cl;
+        const bool sep = BATCH && sp.y == sp.x;
+        const int64_t a = P + (sep ? 0 : (int64_t)ol), b = a + (BODY == ACGPU_COVER_DROP ? 0 : (int64_t)(sp.y - sp.x)), c = b + (sep ? 0 : (int64_t)cl);
         auto in_tile = [](int64_t x) { return (int32_t)std::min<int64_t>(std::max<int64_t>(x, 0), kEmitTile<T>); };
         s.rel = (int32_t)std::max<int64_t>(P, -1);
         s.a_end = in_tile(a);
@@ -97,7 +109,7 @@ struct CoverArgs {
         s.osrc = (uint32_t)0 - (uint32_t)P;
         s.bsrc = (uint32_t)sp.x - (uint32_t)a;
         s.csrc = (uint32_t)0 - (uint32_t)b;
-        s.tsrc = (uint32_t)sp.y - (uint32_t)c;
+        s.tsrc = (uint32_t)sp.y + (uint32_t)sep - (uint32_t)c;
         return s;
     }
     // (inside a FILL body the vector is a constant and needs no load)
@@ -122,6 +134,11 @@ struct CoverArgs {
 
 template <class T, int BODY>
 __global__ __launch_bounds__(kEmitBlock) void k_cover_emit(CoverArgs<T, BODY> A) {
+    emit_block(A);
+}
+
+template <int BODY>
+__global__ __launch_bounds__(kEmitBlock) void k_cover_batch_emit(CoverArgs<uint16_t, BODY, true> A) {
     emit_block(A);
 }
 
@@ -160,6 +177,13 @@ struct CoverCall {
     uint64_t cap = 0;
     uint64_t done = 0;        // output exists for the text's elements [0, done)
     uint64_t out_pos = 0;     // elements of it (beyond cap: counted, not written)
+    // a batch call over the concatenation: its offsets on the host and on the device (n_hay + 1 words), the result's offsets on the
+    // device (n_hay + 1 words of 64 bits), and what the current piece's plan was sized for
+    const uint32_t *h_cat_off = nullptr, *d_cat_off = nullptr;
+    uint32_t n_hay = 0;
+    uint64_t *d_out_off = nullptr;
+    uint64_t piece_items = 0;   // m + piece_max_sep: the items the plan has room for
+    uint32_t piece_max_sep = 0; // the separators in [done, own_hi)
 };
 
 // open and close on the device, each padded so that an aligned 16-byte load around any of their elements stays inside the blob
@@ -203,6 +227,184 @@ int plan_dropped(void *ctx, uint64_t *d_slot, const int2 *d_spans, uint64_t m) {
     return ACGPU_OK;
 }
 
+// ---- a batch call (acgpu_cover_batch_u16): the text is the haystacks' concatenation, a separator behind each, and a separator is
+// an ITEM of the plan that emits nothing and skips one element.  Behind a piece's merge its final spans and the separators in
+// [done, L) become one ascending list (k_cover_batch_merge: a rank merge, one binary search per element -- the two lists cannot
+// tie, a separator is never covered), the plan runs over that list for every body (an item's delta: -1 for a separator, else
+// w minus, for DROP, the span's elements), and k_cover_batch_offsets reads every result's first output element off the plan.
+// All of it is enqueued BEFORE the piece's wait, where n_final and L are on the device only: k_cover_batch_head reads them from
+// the merge's head, counts the separators below L in cat_off and leaves {n_final, n_sep} for the other kernels; the grids are
+// sized by what the host does know, m and the separators in [done, own_hi) -- L <= own_hi, see DESIGN.md 4.24. ----
+
+constexpr int kBatchHead = 2;    // words in front of a batch plan's sums: {n_final, n_sep}
+constexpr int kBatchBlock = 256; // lanes of the merge's and the offsets' workgroups
+
+// The separators a piece may emit: separator i0 + j stands at text position cat_off[i0 + j + 1] - 1 (cat_off[i] = the first unit
+// of haystack i in the concatenation), j < max_sep.
+struct CoverSeps {
+    const uint32_t *cat_off;
+    uint32_t n_hay, i0, max_sep;
+};
+
+// Where a piece's n_final and L come from: the merge's head on the device (acgpu_spans.h); slot == nullptr: a piece without
+// intervals, which has no final span and whose L the host knows.
+struct CoverPieceIn {
+    const uint64_t *slot;
+    uint64_t m;      // the intervals the piece merged: n_final is at most that
+    int64_t L;       // L where the head does not hold it: without a slot, and on the last piece
+    int32_t slot_L;  // L is slot[kSpanSettled]
+};
+
+__device__ __forceinline__ int64_t cover_sep_at(const CoverSeps &S, uint32_t j) { return (int64_t)S.cat_off[S.i0 + j + 1] - 1; }
+
+// the first n of the ascending `spans` that start in front of p
+__device__ __forceinline__ uint64_t spans_before(const int2 *__restrict__ spans, uint64_t n, int64_t p) {
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if ((int64_t)spans[mid].x < p) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// one thread: head = {n_final, the separators in [done, L)}, both counts clamped to what the grids and buffers are sized for
+__global__ void k_cover_batch_head(CoverPieceIn in, CoverSeps S, uint64_t *__restrict__ head) {
+    const uint64_t n_final = in.slot ? std::min<uint64_t>(in.slot[0], in.m) : 0;
+    const int64_t L = in.slot && in.slot_L ? (int64_t)in.slot[kSpanSettled] : in.L;
+    uint32_t lo = S.i0, hi = S.n_hay; // the first separator at or behind L: cat_off[j + 1] - 1 >= L
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if ((int64_t)S.cat_off[mid + 1] <= L) lo = mid + 1;
+        else hi = mid;
+    }
+    head[0] = n_final;
+    head[1] = std::min(lo - S.i0, S.max_sep);
+}
+
+// items = the piece's final spans and, as {p, p}, its separators, in position order; a thread per span (t < m) or separator
+__global__ __launch_bounds__(kBatchBlock) void k_cover_batch_merge(const int2 *__restrict__ spans, const uint64_t *__restrict__ head, CoverSeps S, uint64_t m,
+                                                                   int2 *__restrict__ items) {
+    const uint64_t t = (uint64_t)blockIdx.x * kBatchBlock + threadIdx.x;
+    const uint64_t n_final = head[0];
+    const uint32_t n_sep = (uint32_t)head[1];
+    if (t < m) {
+        if (t >= n_final) return;
+        const int2 sp = spans[t];
+        uint32_t lo = 0, hi = n_sep; // the separators in front of the span
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (cover_sep_at(S, mid) < (int64_t)sp.x) lo = mid + 1;
+            else hi = mid;
+        }
+        items[t + lo] = sp;
+    } else if (t - m < n_sep) {
+        const int32_t p = (int32_t)cover_sep_at(S, (uint32_t)(t - m));
+        items[(t - m) + spans_before(spans, n_final, p)] = make_int2(p, p);
+    }
+}
+
+// The plan's item: what item i adds to the output's length beyond the text it stands for
+__device__ __forceinline__ int64_t batch_delta(const int2 *items, uint64_t i, int64_t w, int drop) {
+    const int64_t len = (int64_t)(items[i].y - items[i].x);
+    return len == 0 ? -1 : w - (drop ? len : 0);
+}
+
+__global__ __launch_bounds__(kPlanBlock) void k_cover_batch_sums(const int2 *__restrict__ items, const uint64_t *__restrict__ head, int64_t w, int drop,
+                                                                 int64_t *__restrict__ bsum) {
+    plan_sums([=](uint64_t i) { return batch_delta(items, i, w, drop); }, head[0] + head[1], bsum);
+}
+
+// *dropped (the merge's slot[kSpanDropped], or nullptr) = the elements of the text in [done, L) that have no output of their own:
+// the separators, and a DROP call's covered elements
+__global__ __launch_bounds__(kPlanBlock) void k_cover_batch_plan_offsets(int64_t *__restrict__ bsum, uint32_t n_blocks, const uint64_t *__restrict__ head, int64_t w,
+                                                                         uint64_t *__restrict__ dropped) {
+    const int64_t sum = plan_offsets(bsum, n_blocks);
+    if (threadIdx.x == 0 && dropped) *dropped = (uint64_t)((int64_t)head[0] * w - sum);
+}
+
+__global__ __launch_bounds__(kPlanBlock) void k_cover_batch_plan(const int2 *__restrict__ items, const uint64_t *__restrict__ head, const int64_t *__restrict__ bsum,
+                                                                 int64_t done, int64_t w, int drop, int64_t *__restrict__ pos) {
+    plan_positions([=](uint64_t i) { return batch_delta(items, i, w, drop); }, head[0] + head[1], bsum,
+                   [&](uint64_t k, int64_t front) { pos[k] = (int64_t)items[k].x - done + front; });
+}
+
+// Separator i0 + j ends haystack i0 + j: the result of haystack i0 + j + 1 begins where the separator's item stands
+__global__ __launch_bounds__(kBatchBlock) void k_cover_batch_offsets(const int2 *__restrict__ spans, const uint64_t *__restrict__ head, CoverSeps S,
+                                                                     const int64_t *__restrict__ pos, uint64_t out_pos, uint64_t *__restrict__ out_off) {
+    const uint32_t j = blockIdx.x * kBatchBlock + threadIdx.x;
+    if (j >= (uint32_t)head[1]) return;
+    out_off[(uint64_t)S.i0 + j + 1] = out_pos + (uint64_t)pos[j + spans_before(spans, head[0], cover_sep_at(S, j))];
+}
+
+// separator i stands at cat_off[i + 1] - 1: the separators in [lo, hi) are [*i0, *i1)
+void separators_in(const uint32_t *h_cat_off, uint32_t n_hay, uint64_t lo, uint64_t hi, uint32_t *i0, uint32_t *i1) {
+    const uint32_t *sep_end = h_cat_off + 1; // at or behind x <=> sep_end[i] > x
+    *i0 = (uint32_t)(std::upper_bound(sep_end, sep_end + n_hay, lo) - sep_end);
+    *i1 = std::max(*i0, (uint32_t)(std::upper_bound(sep_end, sep_end + n_hay, hi) - sep_end));
+}
+
+// The item list and the plan of a batch call's piece that merged m intervals and owned [.., own_hi): enqueued, no wait.
+int plan_batch(CoverCall &c, const CoverPieceIn &in, const int2 *d_spans, uint64_t own_hi, uint64_t *d_dropped) {
+    DeviceState &d = c.sc.d;
+    CoverSeps S;
+    uint32_t i1;
+    separators_in(c.h_cat_off, c.n_hay, c.done, own_hi, &S.i0, &i1);
+    S.cat_off = c.d_cat_off;
+    S.n_hay = c.n_hay;
+    S.max_sep = i1 - S.i0;
+    const uint64_t M = in.m + S.max_sep;
+    c.piece_items = M;
+    c.piece_max_sep = S.max_sep;
+    if (!M) return ACGPU_OK;
+    const uint32_t n_blocks = (uint32_t)((M + kPlanTile - 1) / kPlanTile);
+    int rc = d.cover_items.ensure((size_t)M * 8 + 16);
+    if (rc || (rc = d.cover_plan.ensure((kBatchHead + (size_t)n_blocks + M) * 8))) return rc; // head | workgroup sums | pos
+    uint64_t *head = reinterpret_cast<uint64_t *>(d.cover_plan.p);
+    int64_t *bsum = reinterpret_cast<int64_t *>(head + kBatchHead), *pos = bsum + n_blocks;
+    int2 *items = reinterpret_cast<int2 *>(d.cover_items.p);
+    const hipStream_t stream = c.sc.stream;
+    const int64_t w = (int64_t)c.ol + (int64_t)c.cl;
+    const int drop = c.body == ACGPU_COVER_DROP;
+    hipLaunchKernelGGL(k_cover_batch_head, dim3(1), dim3(1), 0, stream, in, S, head);
+    hipLaunchKernelGGL(k_cover_batch_merge, dim3((unsigned)((M + kBatchBlock - 1) / kBatchBlock)), dim3(kBatchBlock), 0, stream, d_spans, (const uint64_t *)head, S,
+                       in.m, items);
+    hipLaunchKernelGGL(k_cover_batch_sums, dim3(n_blocks), dim3(kPlanBlock), 0, stream, (const int2 *)items, (const uint64_t *)head, w, drop, bsum);
+    hipLaunchKernelGGL(k_cover_batch_plan_offsets, dim3(1), dim3(kPlanBlock), 0, stream, bsum, n_blocks, (const uint64_t *)head, w, d_dropped);
+    hipLaunchKernelGGL(k_cover_batch_plan, dim3(n_blocks), dim3(kPlanBlock), 0, stream, (const int2 *)items, (const uint64_t *)head, (const int64_t *)bsum,
+                       (int64_t)c.done, w, drop, pos);
+    if (S.max_sep)
+        hipLaunchKernelGGL(k_cover_batch_offsets, dim3((S.max_sep + kBatchBlock - 1) / kBatchBlock), dim3(kBatchBlock), 0, stream, d_spans, (const uint64_t *)head, S,
+                           (const int64_t *)pos, c.out_pos, c.d_out_off);
+    HIP_TRY(hipGetLastError());
+    return ACGPU_OK;
+}
+
+// SpansCall::planned of a batch call: in front of the piece's wait, n_final and L read from the merge's head
+int plan_batch_piece(void *ctx, uint64_t *d_slot, const int2 *d_spans, uint64_t m) {
+    CoverCall &c = *static_cast<CoverCall *>(ctx);
+    const CoverPieceIn in{d_slot, m, (int64_t)c.n, !c.sc.piece_last};
+    return plan_batch(c, in, d_spans, c.sc.piece_own_hi, d_slot + kSpanDropped);
+}
+
+template <int BODY>
+int launch_emit_batch(CoverCall &c, uint64_t n_items, uint64_t w0, uint64_t w1, void *dst) {
+    DeviceState &d = c.sc.d;
+    CoverArgs<uint16_t, BODY, true> A;
+    A.hay = static_cast<const uint16_t *>(c.hay);
+    A.spans = reinterpret_cast<const int2 *>(d.cover_items.p);
+    A.pos = n_items ? reinterpret_cast<const int64_t *>(d.cover_plan.p) + kBatchHead + (c.piece_items + kPlanTile - 1) / kPlanTile : nullptr;
+    A.n_spans = (int64_t)n_items;
+    A.open = static_cast<const uint16_t *>(c.d_open);
+    A.close = static_cast<const uint16_t *>(c.d_close);
+    A.ol = c.ol;
+    A.cl = c.cl;
+    A.fill = c.fill;
+    A.done = (int64_t)c.done;
+    A.cap = (int32_t)std::min<int64_t>(std::max<int64_t>(tunables().cover_lds_segments.load(std::memory_order_relaxed), 0), kCoverLds);
+    return launch_emit_kernel(k_cover_batch_emit<BODY>, A, w0, w1, dst, c.sc.stream);
+}
+
 // m: the intervals the piece merged (where the plan's positions begin in d.cover_plan)
 template <class T, int BODY>
 int launch_emit_as(CoverCall &c, uint64_t n_final, uint64_t m, uint64_t w0, uint64_t w1, void *dst) {
@@ -234,11 +436,29 @@ int cover_piece(void *ctx, uint64_t m, bool last) {
     CoverCall &c = *static_cast<CoverCall *>(ctx);
     const uint64_t n_final = c.sc.piece_final, L = last ? c.n : std::min((uint64_t)std::max<int64_t>(c.sc.piece_settled, 0), c.n);
     if (L < c.done) return ACGPU_E_HIP; // (never: the settled position does not move backwards)
-    const uint64_t dropped = c.body == ACGPU_COVER_DROP ? c.sc.piece_dropped : 0;
+    uint64_t dropped = c.body == ACGPU_COVER_DROP ? c.sc.piece_dropped : 0;
+    uint64_t n_items = n_final;
+    int rc;
+    if (c.h_cat_off) { // a batch call: the separators in [done, L) are items, and none of them has output
+        uint32_t i0, i1;
+        separators_in(c.h_cat_off, c.n_hay, c.done, L, &i0, &i1);
+        n_items += i1 - i0;
+        if (m) { // planned in front of the wait (plan_batch_piece)
+            if (i1 - i0 > c.piece_max_sep) return ACGPU_E_HIP; // (never: L <= own_hi)
+            dropped = c.sc.piece_dropped;
+        } else { // a piece without intervals has no launches of its own: its separators are planned here, n_final and L by value
+            if ((rc = plan_batch(c, CoverPieceIn{nullptr, 0, (int64_t)L, 0}, nullptr, L, nullptr))) return rc;
+            dropped = i1 - i0;
+        }
+    }
     const uint64_t added = n_final * ((uint64_t)c.ol + c.cl);
     if (dropped > L - c.done) return ACGPU_E_HIP; // (never: the final spans lie in [done, L))
     const uint64_t total = (L - c.done) + added - dropped;
-    const int rc = emit_piece(c.sc.d, c.sc.stream, c.esz, c.d_out, c.h_out, c.cap, c.out_pos, total, [&](uint64_t w0, uint64_t w1, void *dst) {
+    rc = emit_piece(c.sc.d, c.sc.stream, c.esz, c.d_out, c.h_out, c.cap, c.out_pos, total, [&](uint64_t w0, uint64_t w1, void *dst) {
+        if (c.h_cat_off)
+            return c.body == ACGPU_COVER_KEEP   ? launch_emit_batch<ACGPU_COVER_KEEP>(c, n_items, w0, w1, dst)
+                   : c.body == ACGPU_COVER_FILL ? launch_emit_batch<ACGPU_COVER_FILL>(c, n_items, w0, w1, dst)
+                                                : launch_emit_batch<ACGPU_COVER_DROP>(c, n_items, w0, w1, dst);
         return c.esz == 1 ? launch_emit_body<uint8_t>(c, n_final, m, w0, w1, dst) : launch_emit_body<uint16_t>(c, n_final, m, w0, w1, dst);
     });
     if (rc) return rc;
@@ -255,7 +475,7 @@ int cover_text(CoverCall &c, int64_t chain, bool whole, const PieceScan &scan, u
     sc.to_pool = true;
     sc.ctx = &c;
     sc.merged = cover_piece;
-    if (c.body == ACGPU_COVER_DROP) sc.planned = plan_dropped;
+    sc.planned = c.h_cat_off ? plan_batch_piece : c.body == ACGPU_COVER_DROP ? plan_dropped : nullptr;
     return spans_pieces(sc, chain, whole, scan, n_units);
 }
 
@@ -373,6 +593,62 @@ int acgpu_cover_device(const acgpu_automaton *ca, acgpu_shard *shard, const acgp
     const hipError_t e = hipStreamSynchronize(stream); // the final wait
     if (rc) return rc;
     HIP_TRY(e);
+    return cover_result(c, n_out, st);
+}
+
+int acgpu_cover_batch_u16(const acgpu_automaton *ca, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks, const acgpu_cover_spec *spec,
+                          uint16_t *out, uint64_t cap, uint64_t *out_offsets, uint64_t *n_out, acgpu_cover_stats *st) {
+    if (!ca || !offsets || !n_out || !out_offsets || (cap && !out)) return ACGPU_E_INVALID;
+    int rc = check_spec(spec, 2);
+    if (rc) return rc;
+    acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
+    const HostTables &t = a->t;
+    BatchPlan plan;
+    if ((rc = check_batch(t, units, offsets, n_haystacks, &plan))) return rc;
+    *n_out = 0;
+    out_offsets[0] = 0;
+    if (st) *st = acgpu_cover_stats{};
+    if (n_haystacks == 0) return ACGPU_OK;
+    PoolCall call(a); // (no device: fails here, and out is untouched)
+    if (call.rc) return call.rc;
+    DeviceState &d = *call.d;
+    if ((rc = call.idle())) return rc; // (the text is staged by a blocking copy: the NULL stream, see the stream rule)
+    CoverCall c{SpansCall{a, d, d.call_stream}};
+    c.h_out = reinterpret_cast<uint8_t *>(out);
+    c.cap = cap;
+    if ((rc = upload_spec(c, *spec))) return call.fail(rc);
+    const bool whole = shard_rule(t, ACGPU_REC_SET, false).sequential;
+    acgpu_shard sh;
+    if (plan.per_haystack) { // every haystack by the route acgpu_cover_u16 takes, the results back to back
+        for (uint32_t i = 0; i < n_haystacks; i++) {
+            const uint64_t len = offsets[i + 1] - offsets[i];
+            if (len) {
+                if ((rc = stage_whole_text(d, units + offsets[i], len, &sh))) return call.fail(rc);
+                c.hay = sh.d_hay;
+                c.n = len;
+                c.done = 0;
+                if ((rc = cover_text(c, 0, whole, PieceScan{a, d, nullptr, 0, &sh, c.sc.stream}, len))) return call.fail(rc);
+                if (hipStreamSynchronize(c.sc.stream) != hipSuccess) return call.fail(ACGPU_E_HIP); // (the next haystack is staged over this one)
+            }
+            out_offsets[i + 1] = c.out_pos;
+        }
+        return cover_result(c, n_out, st);
+    }
+    BatchText text(d, t); // (d.start_behind is the separator until this returns, whichever way)
+    if ((rc = text.stage(units, offsets, n_haystacks, c.sc.stream))) return call.fail(rc);
+    if ((rc = stage_whole_text(d, text.h_cat, text.cat, &sh))) return call.fail(rc); // the whole concatenation, once: as acgpu_cover_u16
+    if ((rc = d.replace_off.ensure(((size_t)n_haystacks + 1) * 8))) return call.fail(rc);
+    c.hay = sh.d_hay;
+    c.n = text.cat;
+    c.h_cat_off = text.h_off;
+    c.d_cat_off = text.d_off();
+    c.n_hay = n_haystacks;
+    c.d_out_off = reinterpret_cast<uint64_t *>(d.replace_off.p);
+    if ((rc = cover_text(c, 0, whole, PieceScan{a, d, nullptr, 0, &sh, c.sc.stream}, text.cat))) return call.fail(rc);
+    // (every separator was an item of exactly one piece: the pieces' [done, L) tile the text)
+    if (hipMemcpyAsync(out_offsets + 1, c.d_out_off + 1, (size_t)n_haystacks * 8, hipMemcpyDeviceToHost, c.sc.stream) != hipSuccess ||
+        hipStreamSynchronize(c.sc.stream) != hipSuccess)
+        return call.fail(ACGPU_E_HIP);
     return cover_result(c, n_out, st);
 }
 

@@ -231,12 +231,13 @@ struct DeviceState {
     PoolBuf replace_tab, replace_plan, replace_slab;      // acgpu_replace_*: the replacement table, the plan {sums, output positions}, the host entry's two slabs
     Pinned<> replace_pin;                                 // ... 64 bytes: a piece's output length and last end
     PoolEvent replace_ev[4];                              // ... slab b emitted (b), slab b copied out (2 + b)
-    PoolBuf replace_merged, replace_off;                  // acgpu_replace_batch_u16: a piece's records merged with its separators, the result's offsets (acgpu_replace_batch_utf8's too)
+    PoolBuf replace_merged, replace_off;                  // acgpu_replace_batch_u16: a piece's records merged with its separators, the result's offsets (acgpu_replace_batch_utf8's and acgpu_cover_batch_u16's too)
     PoolBuf summary;                                      // acgpu_summary_batch_u16: 24 bytes per haystack, {records, the first of them}
     PoolBuf terms_entries, terms_stage, terms_aux, terms_count; // acgpu_count_batch_*: the call's entry list {h, id, count}, a piece's entries block by block, {block_base, n_distinct} per block, the running entry count (acgpu_terms.hip)
     PoolBuf spans_work, spans_carry, spans_out;        // acgpu_spans_*: {n_final, n_carry, bound} and the tiles' minima and counts, the two carry buffers, the host entry's final spans of a piece (acgpu_spans.hip)
     Pinned<> spans_pin;                                   // ... 64 bytes: a piece's {n_final, n_carry} and, for a cover call, the rest of the head (acgpu_spans.h)
     PoolBuf cover_spans, cover_tab, cover_plan;           // acgpu_cover_*: a piece's spans, the call's open and close elements, a DROP call's plan {sums, output positions} (acgpu_cover.hip)
+    PoolBuf cover_items;                                  // acgpu_cover_batch_u16: a piece's final spans merged with its separators (its result's offsets: replace_off)
     PoolBuf utf8_in, utf8_aux;                          // the UTF-8 entries: the caller's bytes; {n_units, first_bad, tail, n_replaced}, block sums, checkpoints, a batch's byte offsets, a lossy text's start bitmap (Utf8Aux, acgpu_utf8.hip)
     CountCall *count = nullptr;                          // the counting call that runs on this pool (it holds mu), or nullptr
     double all_density = -1.0;                           // ALL: records per unit of this pool's last call (-1: none yet): k_ac_states or the tile kernel
@@ -572,7 +573,8 @@ struct BatchText {
 
 // A text on its way through a reservoir, piece by piece (scan_next_piece, acgpu_pieces.hip).  Six consumers: the cursor keeps
 // one from page call to page call; a counting, a replace, a batch summary, a count-batch and a spans call have one for each text
-// they drive.
+// they drive -- a spans call being every call through spans_pieces (acgpu_spans.h): the spans and the cover entries, their batch
+// entries over the concatenation, and, haystack by haystack, a batch that cannot be concatenated.
 struct PieceDriver {
     uint64_t pos = 0, end = 0;         // the owned units [pos, end) have not been scanned yet
     int64_t chain = 0;                 // the chain's entry into the next piece (the text's coordinates)

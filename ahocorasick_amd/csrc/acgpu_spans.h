@@ -37,6 +37,16 @@ struct SpansCall {
     // ... called behind the piece's wait, with m again and whether the piece was the last: the caller's step behind the merge
     int (*merged)(void *ctx, uint64_t m, bool last) = nullptr;
     void *ctx = nullptr;
+    // A batch call (acgpu_spans_batch_u16): the text is the haystacks' concatenation, a separator behind each; cat_off (device,
+    // n_hay + 1 words) = every haystack's first unit in it.  A piece's final spans are tagged with their haystack and rebased to
+    // it in d.batch_out, and 12 bytes per span leave for h_out.  cat_off == nullptr with tag_all: a batch that goes haystack by
+    // haystack -- the text is haystack `tag`.
+    const uint32_t *cat_off = nullptr;
+    uint32_t n_hay = 0;
+    bool tag_all = false;
+    int32_t tag = 0;
+    uint64_t piece_own_hi = 0;    // in, for `planned`: the piece owned [.., piece_own_hi) ...
+    bool piece_last = false;      // ... and was the last, or the text as one piece
     uint64_t piece_final = 0;     // out: the piece's final spans
     int64_t piece_settled = 0;    // out, not on the last piece: L = min(B, start of the first carried span)
     uint64_t piece_dropped = 0;   // out: slot[kSpanDropped] if `planned` is set

@@ -1,4 +1,4 @@
-// acgpu_spans.hip -- acgpu_spans_u16 / acgpu_spans_device / acgpu_spans_utf8 / acgpu_spans_utf8_lossy (include/acgpu.h): the
+// acgpu_spans.hip -- acgpu_spans_u16 / acgpu_spans_batch_u16 / acgpu_spans_device / acgpu_spans_utf8 / acgpu_spans_utf8_lossy (include/acgpu.h): the
 // records of a text merged into its covered runs, on the device, for all five families.
 //
 // A spans call is the sixth consumer of the piece driver (scan_next_piece, acgpu_pieces.hip): the Set records of a piece stay in
@@ -38,6 +38,11 @@
 // text is settled, SpansCall::planned enqueues the caller's plan in front of the wait -- which then reads the whole head, 48 bytes,
 // still once -- and SpansCall::merged is the caller's step behind it, the piece's emit.  What the spans entries compute, read back
 // and return is untouched by that.
+//
+// A BATCH (acgpu_spans_batch_u16): the haystacks are merged as one text, a separator unit behind each.  No record holds a
+// separator, so a separator's position is never covered, and a span that ends at it and one that starts behind it do not touch:
+// the merge is unchanged and its spans are the haystacks' spans, shifted.  Behind the piece's wait k_span_tag turns the piece's final
+// spans into {haystack, start, end} relative to the haystack, and 12 bytes per span leave for the caller.
 //
 // UTF-8: the text is staged by stage_utf8_text and scanned in units; a piece's records become byte offsets where they lie
 // (utf8_map_records, two words per record) BEFORE the merge -- the map is monotone, so the order by end survives -- and `bound`
@@ -288,6 +293,29 @@ __global__ void k_span_settled(SpanList L, SpanBound Bd, const int2 *__restrict_
     slot[kSpanSettled] = (uint64_t)at;
 }
 
+// A batch call's final spans of a piece -> {haystack, start, end} relative to the haystack: the layout of k_batch_tag's Set
+// records.  cat_off == nullptr: the text is haystack `tag`, whose spans are relative to it already.
+__global__ __launch_bounds__(kSpanBlock) void k_span_tag(const int2 *__restrict__ spans, uint64_t n, const uint32_t *__restrict__ cat_off, uint32_t n_hay,
+                                                         int32_t tag, int32_t *__restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * kSpanBlock + threadIdx.x;
+    if (i >= n) return;
+    const int2 sp = spans[i];
+    int32_t h = tag, base = 0;
+    if (cat_off) {
+        uint32_t lo = 0, hi = n_hay; // the last haystack that begins at or before the span's start
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (cat_off[mid] <= (uint32_t)sp.x) lo = mid;
+            else hi = mid;
+        }
+        h = (int32_t)lo;
+        base = (int32_t)cat_off[lo];
+    }
+    out[3 * i] = h;
+    out[3 * i + 1] = sp.x - base;
+    out[3 * i + 2] = sp.y - base;
+}
+
 bool first_unit_family(const HostTables &t) { return t.mode != ACGPU_MODE_ALL && t.mode != ACGPU_MODE_SHORTEST; }
 
 // `bound` of THE CARRY, in the scan's units: piece_bound of the replace entries, with ALL on SHORTEST's side
@@ -311,6 +339,8 @@ int spans_piece(SpansCall &c, uint64_t base, uint64_t cnt, uint64_t own_hi, bool
     c.st.n_records += cnt;
     const uint64_t m = c.n_carry + cnt;
     c.piece_final = c.piece_dropped = 0;
+    c.piece_own_hi = own_hi;
+    c.piece_last = last_or_whole;
     if (!m && !c.to_pool) return ACGPU_OK;
     const uint32_t n_tiles = (uint32_t)((m + kSpanTile - 1) / kSpanTile);
     int rc = d.spans_work.ensure(kSpanHead * 8 + (size_t)n_tiles * 12); // the head (acgpu_spans.h) | tile minima | tile counts | tile final counts
@@ -389,8 +419,18 @@ int spans_piece(SpansCall &c, uint64_t base, uint64_t cnt, uint64_t own_hi, bool
     const uint64_t *h = static_cast<const uint64_t *>(d.spans_pin.h);
     const uint64_t n_final = h[0], n_carry = h[1];
     if (n_carry > c.carry_cap || (last_or_whole && n_carry)) return ACGPU_E_HIP; // (never: see THE CARRY)
-    if (c.h_out && n_final && room) // (the next piece's scatter follows it on the stream; the call waits for the stream at its end)
-        HIP_TRY(hipMemcpyAsync(c.h_out + 2 * c.out_pos, O.out, (size_t)std::min(n_final, room) * 8, hipMemcpyDeviceToHost, c.stream));
+    if (c.h_out && n_final && room) { // (the next piece's scatter follows it on the stream; the call waits for the stream at its end)
+        const uint64_t n_put = std::min(n_final, room);
+        if (c.cat_off || c.tag_all) { // a batch call: tagged and rebased in the pool, then 12 bytes per span
+            if ((rc = d.batch_out.ensure((size_t)n_put * 12 + 16))) return rc;
+            hipLaunchKernelGGL(k_span_tag, dim3((unsigned)((n_put + kSpanBlock - 1) / kSpanBlock)), dim3(kSpanBlock), 0, c.stream, (const int2 *)O.out, n_put,
+                               c.cat_off, c.n_hay, c.tag, reinterpret_cast<int32_t *>(d.batch_out.p));
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(c.h_out + 3 * c.out_pos, d.batch_out.p, (size_t)n_put * 12, hipMemcpyDeviceToHost, c.stream));
+        } else {
+            HIP_TRY(hipMemcpyAsync(c.h_out + 2 * c.out_pos, O.out, (size_t)n_put * 8, hipMemcpyDeviceToHost, c.stream));
+        }
+    }
     c.out_pos += n_final;
     c.n_carry = (uint32_t)n_carry;
     c.cur ^= 1;
@@ -420,8 +460,8 @@ int spans_pieces(SpansCall &c, int64_t chain, bool whole, const PieceScan &scan,
         if ((rc = spans_piece(c, base, cnt, p.pos, last))) return rc;
         if (c.merged && (rc = c.merged(c.ctx, m, last))) return rc;
     }
-    c.st.pieces = (uint32_t)p.pieces;
-    c.st.rescans = (uint32_t)p.rescans;
+    c.st.pieces += (uint32_t)p.pieces; // (added: a batch call haystack by haystack drives one text after the other)
+    c.st.rescans += (uint32_t)p.rescans;
     return ACGPU_OK;
 }
 
@@ -511,6 +551,45 @@ int acgpu_spans_device(const acgpu_automaton *ca, acgpu_shard *shard, int32_t *d
     const hipError_t e = hipStreamSynchronize(stream); // the final wait
     if (rc) return rc;
     HIP_TRY(e);
+    return spans_result(c, n_out, st);
+}
+
+int acgpu_spans_batch_u16(const acgpu_automaton *ca, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks, int32_t *out, uint64_t cap,
+                          uint64_t *n_out, acgpu_spans_stats *st) {
+    if (!ca || !offsets || !n_out || (cap && !out)) return ACGPU_E_INVALID;
+    *n_out = 0;
+    if (st) *st = acgpu_spans_stats{};
+    if (n_haystacks == 0) return ACGPU_OK;
+    acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
+    const HostTables &t = a->t;
+    BatchPlan plan;
+    int rc = check_batch(t, units, offsets, n_haystacks, &plan);
+    if (rc) return rc;
+    PoolCall call(a); // (no device: fails here, and out is untouched)
+    if (call.rc) return call.rc;
+    DeviceState &d = *call.d;
+    SpansCall c{a, d, d.call_stream};
+    c.h_out = out;
+    c.cap = cap;
+    if (plan.per_haystack) { // every haystack as a text of its own, by the route acgpu_spans_u16 takes
+        if ((rc = call.on(c.stream))) return rc;
+        c.tag_all = true;
+        for (uint32_t i = 0; i < n_haystacks; i++) {
+            const uint64_t len = offsets[i + 1] - offsets[i];
+            if (!len) continue;
+            c.tag = (int32_t)i;
+            const uint16_t *hay = units + offsets[i];
+            if ((rc = spans_pieces(c, 0, host_one_piece(t, ACGPU_REC_SET), PieceScan{a, d, hay, len, nullptr, c.stream}, len))) return call.fail(rc);
+        }
+    } else {
+        if ((rc = call.idle())) return rc; // (the NULL stream: see the stream rule)
+        BatchText text(d, t);
+        if ((rc = text.stage(units, offsets, n_haystacks, c.stream))) return call.fail(rc);
+        c.cat_off = text.d_off();
+        c.n_hay = n_haystacks;
+        if ((rc = spans_pieces(c, 0, host_one_piece(t, ACGPU_REC_SET), PieceScan{a, d, text.h_cat, text.cat, nullptr, c.stream}, text.cat))) return call.fail(rc);
+    } // (every scan has been waited for: what is left on the stream are the copies of the last piece's spans)
+    if (hipStreamSynchronize(c.stream) != hipSuccess) return call.fail(ACGPU_E_HIP);
     return spans_result(c, n_out, st);
 }
 

@@ -1,5 +1,5 @@
 """Which parts of a text a dictionary covers: the records of a match call merged into covered runs on the device (include/acgpu.h:
-acgpu_spans_u16, acgpu_spans_device, acgpu_spans_utf8, acgpu_spans_utf8_lossy) -- what redaction, highlighting and PII tagging
+acgpu_spans_u16, acgpu_spans_batch_u16, acgpu_spans_device, acgpu_spans_utf8, acgpu_spans_utf8_lossy) -- what redaction, highlighting and PII tagging
 ask, for all five families, AhoCorasick's overlapping records included.
 
 A span is a maximal run of positions that some record covers: overlapping, nested and touching records fall into one span, so
@@ -13,9 +13,9 @@ import ctypes
 import numpy as np
 
 from . import _native as N
-from .strings import Automaton, _fill_shard, _not_none, _raise_for, _readable, _stats_dict, _utf8_bytes, _utf8_entry, _vp, utf16
+from .strings import Automaton, _fill_shard, _not_none, _pack, _raise_for, _readable, _stats_dict, _utf8_bytes, _utf8_entry, _vp, utf16
 
-__all__ = ["spans", "spans_utf8", "spans_device"]
+__all__ = ["spans", "spans_batch", "spans_utf8", "spans_device"]
 
 
 def _automaton(matcher):
@@ -23,14 +23,14 @@ def _automaton(matcher):
     return matcher if isinstance(matcher, Automaton) else matcher.automaton
 
 
-def _spans_call(entry, head, n, stats, tail=()):
-    """entry(*head, out, cap, &n_out, &stats, *tail) -> the (n_out, 2) int32 array.  The first capacity is a guess from the text's
+def _spans_call(entry, head, n, stats, tail=(), cols=2):
+    """entry(*head, out, cap, &n_out, &stats, *tail) -> the (n_out, cols) int32 array.  The first capacity is a guess from the text's
     size; ACGPU_E_OVERFLOW reports the spans the text has, and the same call with exactly that capacity succeeds (include/acgpu.h):
     ONE retry, a second overflow is an error."""
     st = stats if stats is not None else N.SpansStats()
     cap = max(4096, n // 4)
     for attempt in range(2):
-        out = np.empty((cap, 2), dtype=np.int32)
+        out = np.empty((cap, cols), dtype=np.int32)
         n_out = ctypes.c_uint64(0)
         rc = entry(*head, _vp(out), cap, ctypes.byref(n_out), ctypes.byref(st), *tail)
         if rc != N.E_OVERFLOW:
@@ -46,6 +46,14 @@ def spans(matcher, haystack, stats=None):
     an N.SpansStats to fill in, if wanted."""
     hay = utf16(_not_none(haystack))
     return _spans_call(N.lib().acgpu_spans_u16, (_automaton(matcher).handle, _vp(_readable(hay)), int(hay.size)), int(hay.size), stats)
+
+
+def spans_batch(matcher, haystacks, stats=None):
+    """The spans of many short haystacks (str or uint16 arrays) in ONE device call -> (n, 3) int32 array of (haystack, start, end),
+    ordered by haystack and ascending within it, start and end relative to the haystack: the rows of haystack i are spans(matcher,
+    haystacks[i]).  Spans never reach across two haystacks: "xab", "abx" with keyword ab gives two."""
+    units, off = _pack([_not_none(h) for h in haystacks])
+    return _spans_call(N.lib().acgpu_spans_batch_u16, (_automaton(matcher).handle, _vp(units), _vp(off), len(off) - 1), int(off[-1]), stats, cols=3)
 
 
 def spans_utf8(matcher, data, errors="strict", stats=None):

@@ -1167,8 +1167,20 @@ int acgpu_stream_replace_utf8_lossy(acgpu_stream *s, const uint8_t *bytes, uint6
  * others -- at most max_keyword_len / 2 + 2 of them -- wait on the device for the next piece (st->max_carry: the most that did).
  * Scratch, per automaton and device: the reservoir the counting and replace calls use, 12 bytes per 2048 records of a piece, the
  * carry, and for the host entries 8 bytes per span of a piece.  The host reads 16 bytes per piece.
+ *  acgpu_spans_batch_u16 : many short texts in one call.  Haystack i is units[offsets[i] .. offsets[i + 1]) as for
+ *              acgpu_match_batch_u16 (empty haystacks allowed, the same ACGPU_E_INVALID: NULL a, offsets or n_out, descending
+ *              offsets, a concatenation of 2^31 units or more, a cap without a buffer; n_haystacks == 0: ACGPU_OK, *n_out = 0, no
+ *              device).  The result is {haystack, start, end} triples of int32 -- the layout of acgpu_match_batch_u16's Set
+ *              records -- ordered by haystack and ascending within it, start and end relative to the haystack: the triples of
+ *              haystack i are exactly the spans acgpu_spans_u16 returns for it alone.  cap, *n_out, overflow: in spans, as above.
+ *              The haystacks are scanned as one text with a separator unit behind each; no record holds a separator and a
+ *              separator is never covered, so the spans of that text are the haystacks' spans, shifted -- two spans that meet
+ *              at a seam stay two.  A piece's final spans are tagged and rebased in the pool and leave 12 bytes each; no wait
+ *              is added.  Where there is no free separator unit, or a word matcher's table is not fold-consistent, every
+ *              haystack is scanned as a text of its own under the one lock (st->pieces then counts them all).  Works on the
+ *              NULL stream, tickets in flight are refused (STREAM RULE), as acgpu_replace_batch_u16.
  * Not built (mask, highlight and redaction on top of spans: the cover entries below): a record-free form for ACGPU_MODE_ALL from the
- * state words of k_ac_states (the analogue of the counting calls' direct form); batch, stream and multi-device forms; the Java
+ * state words of k_ac_states (the analogue of the counting calls' direct form); stream and multi-device forms; the Java
  * facade.  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
  */
 typedef struct acgpu_spans_stats {
@@ -1182,6 +1194,8 @@ int acgpu_spans_u16(const acgpu_automaton *a, const uint16_t *haystack, uint64_t
                     acgpu_spans_stats *st);
 int acgpu_spans_device(const acgpu_automaton *a, acgpu_shard *shard, int32_t *d_out, uint64_t cap, uint64_t *n_out, void *stream,
                        acgpu_spans_stats *st);
+int acgpu_spans_batch_u16(const acgpu_automaton *a, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks,
+                          int32_t *out /* 3 words per span */, uint64_t cap, uint64_t *n_out, acgpu_spans_stats *st /* may be NULL */);
 int acgpu_spans_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, int32_t *out, uint64_t cap, uint64_t *n_out,
                      acgpu_spans_stats *st, acgpu_utf8_stats *ust /* may be NULL */);
 int acgpu_spans_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, int32_t *out, uint64_t cap, uint64_t *n_out,
@@ -1219,7 +1233,27 @@ int acgpu_spans_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, uint6
  * have.  A span's place in the output is closed form for KEEP and FILL and a 64-bit scan for DROP; one emit kernel writes the
  * piece's output in aligned 16-byte stores (st->pieces, rescans, max_carry: as acgpu_spans_stats).  Host output leaves through
  * the two slabs of the replace entries ("replace_slab_units").
- * Not built: batch, stream and multi-device forms, per-keyword open / close, the Java facade.  ACGPU_ABI_VERSION stays as it is.
+ *  acgpu_cover_batch_u16 : many short texts in one call.  Haystack i is units[offsets[i] .. offsets[i + 1]) as for
+ *              acgpu_match_batch_u16, empty haystacks allowed.  out[out_offsets[i] .. out_offsets[i + 1]) is, unit for unit, what
+ *              acgpu_cover_u16 returns for haystack i alone with the same spec; the results lie back to back, out_offsets[0] == 0
+ *              and *n_out == out_offsets[n_haystacks] (out_offsets: n_haystacks + 1 words in host memory).  More than cap units:
+ *              ACGPU_E_OVERFLOW, *n_out and EVERY entry of out_offsets exact, nothing at or beyond out[cap] written.
+ *              st->n_records and n_spans are sums over the haystacks.  ACGPU_E_INVALID, before a device is touched: NULL a,
+ *              offsets, n_out, spec or out_offsets; descending offsets; a concatenation of 2^31 units or more; a cap without a
+ *              buffer; what the spec checks above refuse.  n_haystacks == 0: ACGPU_OK, *n_out = 0, out_offsets[0] = 0, no
+ *              device.  Works on the NULL stream under the pool's lock, tickets in flight are refused (STREAM RULE), as
+ *              acgpu_replace_batch_u16.
+ *              How: the haystacks are staged once as one text with a separator unit behind each and go through the pieces as
+ *              acgpu_cover_u16's text does.  A span that ends at a separator and one that starts behind it have the separator's
+ *              uncovered position between them, so they stay two spans with two opens -- where cover of the JOINED text
+ *              ("..ab" ++ "ab..") gives one.  Behind a piece's merge its final spans and its separators become one item list; a
+ *              separator is an item that emits nothing and skips one unit, so the results come out back to back, and every
+ *              result's first unit is read off the plan on the device (one copy of out_offsets at the end).  The plan, a
+ *              64-bit scan for every body here, runs in front of the piece's one wait: NO wait is added per piece.  Where
+ *              there is no free separator unit, or a word matcher's table is not fold-consistent, every haystack runs as a
+ *              text of its own under the one lock, open and close uploaded once (st->pieces then counts them all).
+ * Not built: stream and multi-device forms, batches of UTF-8 texts, per-keyword open / close, the Java facade.  ACGPU_ABI_VERSION
+ * stays as it is.
  */
 enum { ACGPU_COVER_KEEP = 0, ACGPU_COVER_FILL = 1, ACGPU_COVER_DROP = 2 };
 typedef struct acgpu_cover_spec {
@@ -1242,6 +1276,9 @@ int acgpu_cover_u16(const acgpu_automaton *a, const uint16_t *haystack, uint64_t
                     uint64_t cap, uint64_t *n_out, acgpu_cover_stats *st /* may be NULL */);
 int acgpu_cover_device(const acgpu_automaton *a, acgpu_shard *shard, const acgpu_cover_spec *spec, uint16_t *d_out, uint64_t cap,
                        uint64_t *n_out, void *stream, acgpu_cover_stats *st /* may be NULL */);
+int acgpu_cover_batch_u16(const acgpu_automaton *a, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks,
+                          const acgpu_cover_spec *spec, uint16_t *out, uint64_t cap, uint64_t *out_offsets /* n_haystacks + 1 */,
+                          uint64_t *n_out, acgpu_cover_stats *st /* may be NULL */);
 int acgpu_cover_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, const acgpu_cover_spec *spec, uint8_t *out,
                      uint64_t cap, uint64_t *n_out, acgpu_cover_stats *st /* may be NULL */, acgpu_utf8_stats *ust /* may be NULL */);
 int acgpu_cover_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, const acgpu_cover_spec *spec, uint8_t *out,
