@@ -9,13 +9,15 @@ from .strings import (AhoCorasickMap, AhoCorasickSet, Automaton, IllegalArgument
                       Utf8Error, utf8_line_offsets, utf8_unit_offsets, utf16)
 from . import terms
 from .terms import count_batch, count_batch_utf8
-from .spans import spans, spans_batch, spans_device, spans_utf8  # (the name `spans` of this package is the function; the module: ahocorasick_amd.spans in sys.modules)
+from .spans import spans, spans_batch, spans_batch_utf8, spans_device, spans_utf8  # (the name `spans` of this package is the function; the module: ahocorasick_amd.spans in sys.modules)
 from .cover import (cover, cover_batch, cover_batch_units, cover_device, cover_utf8, highlight, highlight_batch, highlight_utf8, mask, mask_batch,
-                    mask_utf8, redact, redact_batch, redact_utf8)  # (as for spans: the name `cover` is the function)
+                    mask_utf8, redact, redact_batch, redact_utf8, cover_batch_bytes, cover_batch_utf8, highlight_batch_utf8, mask_batch_utf8,
+                    redact_batch_utf8)  # (as for spans: the name `cover` is the function)
 
 __all__ = ["AhoCorasickSet", "AhoCorasickMap", "LongestMatchSet", "LongestMatchMap", "WholeWordMatchSet",
            "WholeWordMatchMap", "ShortestMatchSet", "ShortestMatchMap", "WholeWordLongestMatchSet", "WholeWordLongestMatchMap", "StringSet", "StringMap", "SetMatchListener", "MapMatchListener", "ReadableMatchListener", "Stream", "Automaton",
            "IllegalArgumentException", "utf16", "Utf8Error", "utf8_unit_offsets", "utf8_line_offsets",
            "terms", "count_batch", "count_batch_utf8", "spans", "spans_batch", "spans_utf8", "spans_device",
            "cover", "cover_utf8", "cover_device", "mask", "mask_utf8", "highlight", "highlight_utf8", "redact", "redact_utf8",
-           "cover_batch", "cover_batch_units", "mask_batch", "highlight_batch", "redact_batch"]
+           "cover_batch", "cover_batch_units", "mask_batch", "highlight_batch", "redact_batch",
+           "spans_batch_utf8", "cover_batch_utf8", "cover_batch_bytes", "mask_batch_utf8", "highlight_batch_utf8", "redact_batch_utf8"]

@@ -216,6 +216,8 @@ def _signatures():
         "acgpu_cover_device": (ci, [vp, P(Shard), P(CoverSpec), vp, u64, P(u64), vp, P(CoverStats)]),
         "acgpu_cover_batch_u16": (ci, [vp, vp, vp, u32, P(CoverSpec), vp, u64, vp, P(u64), P(CoverStats)]),
         "acgpu_cover_utf8": (ci, [vp, vp, u64, P(CoverSpec), vp, u64, P(u64), P(CoverStats), P(Utf8Stats)]),
+        "acgpu_spans_batch_utf8": (ci, [vp, vp, vp, u32, vp, u64, P(u64), P(SpansStats), P(Utf8BatchStats)]),
+        "acgpu_cover_batch_utf8": (ci, [vp, vp, vp, u32, P(CoverSpec), vp, u64, vp, P(u64), P(CoverStats), P(Utf8BatchStats)]),
         "acgpu_match_u16_multi": (ci, [vp, vp, u64, P(ci), ci, ci, vp, u64, P(u64)]),
         "acgpu_comm_open": (ci, [P(ci), ci, ci, P(vp)]),
         "acgpu_comm_close": (None, [vp]),

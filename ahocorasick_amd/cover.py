@@ -1,11 +1,12 @@
 """Mask, highlight or redact every covered run of a text on the device (include/acgpu.h: acgpu_cover_u16, acgpu_cover_batch_u16, acgpu_cover_device,
-acgpu_cover_utf8, acgpu_cover_utf8_lossy): every span of the text -- the spans of ahocorasick_amd.spans, for all five families,
+acgpu_cover_utf8, acgpu_cover_utf8_lossy, acgpu_cover_batch_utf8, acgpu_cover_batch_utf8_lossy): every span of the text -- the spans of ahocorasick_amd.spans, for all five families,
 AhoCorasick's overlapping records included -- becomes open + body + close, everything else is copied.
 
     mask(AhoCorasickSet(names, False), text)                    # "call **** or ***" -- the length is preserved
     highlight(AhoCorasickSet(names, False), text, "<b>", "</b>")
     redact(AhoCorasickSet(names, False), text, "[name]")
     mask_batch(AhoCorasickSet(names, False), lines)             # many short texts: ONE device call, a list of str
+    mask_batch_utf8(AhoCorasickSet(names, False), log, offsets=utf8_line_offsets(log))  # ... of bytes, the buffer used in place
 
 Not replace: overlapping, nested and TOUCHING matches are one span, so two matches that touch give ONE replacement, not two.
 No span and no record reaches the host.
@@ -16,10 +17,11 @@ import numpy as np
 
 from . import _native as N
 from .spans import _automaton
-from .strings import _fill_shard, _not_none, _pack, _raise_for, _readable, _stats_dict, _to_str, _utf8_bytes, _utf8_entry, _vp, utf16
+from .strings import _fill_shard, _not_none, _pack, _pack_utf8, _raise_for, _readable, _stats_dict, _to_str, _utf8_bytes, _utf8_entry, _vp, utf16
 
 __all__ = ["cover", "cover_utf8", "cover_device", "mask", "mask_utf8", "highlight", "highlight_utf8", "redact", "redact_utf8",
-           "cover_batch", "cover_batch_units", "mask_batch", "highlight_batch", "redact_batch"]
+           "cover_batch", "cover_batch_units", "mask_batch", "highlight_batch", "redact_batch",
+           "cover_batch_utf8", "cover_batch_bytes", "mask_batch_utf8", "highlight_batch_utf8", "redact_batch_utf8"]
 
 BODIES = {"keep": 0, "fill": 1, "drop": 2}  # ACGPU_COVER_KEEP, _FILL, _DROP
 
@@ -151,6 +153,44 @@ def highlight_batch(matcher, haystacks, open, close):
 
 def redact_batch(matcher, haystacks, replacement):
     return cover_batch(matcher, haystacks, open=replacement, body="drop")
+
+
+def cover_batch_bytes(matcher, datas, open=b"", close=b"", body="keep", fill=b"*", offsets=None, errors="strict", cap=None):
+    """acgpu_cover_batch_utf8: many short UTF-8 haystacks rewritten in ONE device call -> (uint8 array, out_offsets, stats dict): the
+    result of haystack i is out[out_offsets[i]:out_offsets[i + 1]], byte for byte what cover_utf8 returns for it alone.  datas: a
+    sequence of bytes-like objects, or with offsets= ONE buffer used in place (utf8_line_offsets: a log file line by line).  open,
+    close, fill as for cover_utf8.  An ill-formed haystack raises Utf8Error (.haystack, and .start inside it) -- unless
+    errors="replace" (acgpu_cover_batch_utf8_lossy).  cap None: the first capacity of cover_utf8, over the batch's bytes; one retry
+    with the size the first call reports."""
+    entry, stats_type = _utf8_entry("acgpu_cover_batch_utf8", errors)
+    buf, off = _pack_utf8(datas if offsets is not None else [_not_none(h) for h in datas], offsets)
+    spec, keep = _spec(_bytes("open", open), _bytes("close", close), _body(body), _fill_byte(fill))
+    st = N.CoverStats()
+    out_off = np.zeros(len(off), dtype=np.uint64)
+    out = _cover_call(entry, (_automaton(matcher).handle, _vp(_readable(buf)), _vp(off), len(off) - 1), spec, np.uint8, int(off[-1] - off[0]), st,
+                      tail=(ctypes.byref(stats_type()),), mid=(_vp(out_off),), cap=cap)
+    return out, out_off, _stats_dict(st)
+
+
+def cover_batch_utf8(matcher, datas, open=b"", close=b"", body="keep", fill=b"*", offsets=None, errors="strict"):
+    """[cover_utf8(matcher, d, open, close, body, fill, errors) for d in datas] in ONE device call -> a list of bytes.  A span never
+    reaches across two haystacks: b"xab", b"abx" with keyword ab is rewritten twice."""
+    out, out_off, _ = cover_batch_bytes(matcher, datas, open, close, body, fill, offsets, errors)
+    whole = out.tobytes()
+    return [whole[int(out_off[i]):int(out_off[i + 1])] for i in range(len(out_off) - 1)]
+
+
+def mask_batch_utf8(matcher, datas, fill=b"*", offsets=None, errors="strict"):
+    """mask_utf8 for many short haystacks in one device call: every result has its haystack's length and byte offsets"""
+    return cover_batch_utf8(matcher, datas, body="fill", fill=fill, offsets=offsets, errors=errors)
+
+
+def highlight_batch_utf8(matcher, datas, open, close, offsets=None, errors="strict"):
+    return cover_batch_utf8(matcher, datas, open=open, close=close, body="keep", offsets=offsets, errors=errors)
+
+
+def redact_batch_utf8(matcher, datas, replacement, offsets=None, errors="strict"):
+    return cover_batch_utf8(matcher, datas, open=replacement, body="drop", offsets=offsets, errors=errors)
 
 
 def mask(matcher, haystack, fill="*"):

@@ -1,4 +1,5 @@
-// acgpu_cover.hip -- acgpu_cover_u16 / acgpu_cover_batch_u16 / acgpu_cover_device / acgpu_cover_utf8 / acgpu_cover_utf8_lossy (include/acgpu.h): the text
+// acgpu_cover.hip -- acgpu_cover_u16 / acgpu_cover_batch_u16 / acgpu_cover_device / acgpu_cover_utf8 / acgpu_cover_utf8_lossy /
+// acgpu_cover_batch_utf8 / acgpu_cover_batch_utf8_lossy (include/acgpu.h): the text
 // with every span [s, e) -- the spans of acgpu_spans_* -- rewritten as open ++ body ++ close, on the device, for all five families.
 // body is the covered text itself (KEEP: highlight, tagging), one fill element per covered element (FILL: mask) or nothing (DROP:
 // redaction, deletion); everything outside the spans is copied.
@@ -33,7 +34,8 @@
 // acgpu_cover_batch_u16 rewrites many short texts as ONE such text: the haystacks with a separator unit behind each (BatchText),
 // staged whole like acgpu_cover_u16's text.  No record holds a separator, so the spans of that text are the haystacks' spans; a
 // separator is an item of the plan that emits nothing and skips one element, so the results come out back to back (see "a batch
-// call" below, and DESIGN.md 4.24).
+// call" below, and DESIGN.md 4.24).  acgpu_cover_batch_utf8 does the same for bytes over virtual coordinates, the caller's bytes
+// with a phantom element behind every haystack in the separator's place (cover_batch_utf8 below).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -66,8 +68,24 @@ struct CSeg {
 // with an empty open and close: positions ascend WEAKLY, which is all the emit asks (emit_block takes the last of equal ones).
 // make_seg assumes nothing about the next item: P may lie anywhere at or below the tile's last element, and what it adds to P is
 // clamped to the tile.
+// A byte batch (acgpu_cover_batch_utf8) works in VIRTUAL COORDINATES, the caller's bytes with a phantom element behind every
+// haystack (voff[j] = haystack j's first element): items and `done` are v, and an element v of haystack h is byte
+// v - h of `hay`.  An item is a segment and every phantom is an item, so h is constant within a segment: make_seg finds it once
+// per segment (haystack_of over voff) and the segment's text sources carry the shift; whole() and element() read them as ever.
+template <bool VIRT>
+struct CoverShift {
+    __device__ __forceinline__ uint32_t hay_of(int64_t) const { return 0; }
+};
+template <>
+struct CoverShift<true> {
+    const uint32_t *voff;
+    uint32_t n_hay;
+    __device__ __forceinline__ uint32_t hay_of(int64_t v) const { return haystack_of(voff, n_hay, (uint32_t)v); }
+};
+
 template <class T, int BODY, bool BATCH = false>
-struct CoverArgs {
+struct CoverArgs : CoverShift<BATCH && sizeof(T) == 1> {
+    static constexpr bool VIRT = BATCH && sizeof(T) == 1;
     using Elem = T;
     using Seg = CSeg;
     static constexpr int kLds = kCoverLds;
@@ -94,12 +112,15 @@ struct CoverArgs {
             s.rel = -1;
             s.a_end = s.b_end = s.c_end = 0;
             s.osrc = s.bsrc = s.csrc = 0;
-            s.tsrc = (uint32_t)(done + t0);
+            s.tsrc = (uint32_t)(done + t0) - this->hay_of(done); // (VIRT: up to the first item the text is the haystack's that holds `done`)
             return s;
         }
         const int2 sp = spans[i];
         const int64_t P = pos_at(i) - t0; // < kEmitTile<T>
         const bool sep = BATCH && sp.y == sp.x;
+        // VIRT: the item's haystack.  A span's body and the text behind it are bytes v - h; the text behind haystack h's phantom p
+        // begins at p + 1 in haystack h + 1, which is byte p - h.
+        const uint32_t h = this->hay_of(sp.x);
         const int64_t a = P + (sep ? 0 : (int64_t)ol), b = a + (BODY == ACGPU_COVER_DROP ? 0 : (int64_t)(sp.y - sp.x)), c = b + (sep ? 0 : (int64_t)cl);
         auto in_tile = [](int64_t x) { return (int32_t)std::min<int64_t>(std::max<int64_t>(x, 0), kEmitTile<T>); };
         s.rel = (int32_t)std::max<int64_t>(P, -1);
@@ -107,9 +128,9 @@ struct CoverArgs {
         s.b_end = in_tile(b);
         s.c_end = in_tile(c);
         s.osrc = (uint32_t)0 - (uint32_t)P;
-        s.bsrc = (uint32_t)sp.x - (uint32_t)a;
+        s.bsrc = (uint32_t)sp.x - h - (uint32_t)a;
         s.csrc = (uint32_t)0 - (uint32_t)b;
-        s.tsrc = (uint32_t)sp.y + (uint32_t)sep - (uint32_t)c;
+        s.tsrc = (uint32_t)sp.y + (VIRT ? 0u : (uint32_t)sep) - h - (uint32_t)c;
         return s;
     }
     // (inside a FILL body the vector is a constant and needs no load)
@@ -125,6 +146,16 @@ struct CoverArgs {
         return true;
     }
     __device__ __forceinline__ uint32_t element(const CSeg &s, int32_t u) const {
+        if constexpr (VIRT) {
+            // (the sources read up front, by value: left in the branches, the compiler made a choice between the body's, close's and
+            // the text's source a choice between the ADDRESSES of s.bsrc, s.csrc and s.tsrc in k_cover_batch_emit<uint8_t, KEEP> and
+            // <.., DROP>, and kept the segment in 36 bytes of private memory for it)
+            const uint32_t bs = s.bsrc + (uint32_t)u, cs = s.csrc + (uint32_t)u, ts = s.tsrc + (uint32_t)u;
+            if (u < s.a_end) return open[(uint32_t)(s.osrc + (uint32_t)u)];
+            if (u < s.b_end) return BODY == ACGPU_COVER_FILL ? fill : (uint32_t)hay[bs];
+            if (u < s.c_end) return close[cs];
+            return hay[ts];
+        }
         if (u < s.a_end) return open[(uint32_t)(s.osrc + (uint32_t)u)];
         if (u < s.b_end) return BODY == ACGPU_COVER_FILL ? fill : (uint32_t)hay[(uint32_t)(s.bsrc + (uint32_t)u)];
         if (u < s.c_end) return close[(uint32_t)(s.csrc + (uint32_t)u)];
@@ -137,8 +168,8 @@ __global__ __launch_bounds__(kEmitBlock) void k_cover_emit(CoverArgs<T, BODY> A)
     emit_block(A);
 }
 
-template <int BODY>
-__global__ __launch_bounds__(kEmitBlock) void k_cover_batch_emit(CoverArgs<uint16_t, BODY, true> A) {
+template <class T, int BODY>
+__global__ __launch_bounds__(kEmitBlock) void k_cover_batch_emit(CoverArgs<T, BODY, true> A) {
     emit_block(A);
 }
 
@@ -384,25 +415,40 @@ int plan_batch(CoverCall &c, const CoverPieceIn &in, const int2 *d_spans, uint64
 int plan_batch_piece(void *ctx, uint64_t *d_slot, const int2 *d_spans, uint64_t m) {
     CoverCall &c = *static_cast<CoverCall *>(ctx);
     const CoverPieceIn in{d_slot, m, (int64_t)c.n, !c.sc.piece_last};
-    return plan_batch(c, in, d_spans, c.sc.piece_own_hi, d_slot + kSpanDropped);
+    // A byte batch that is not all ASCII: own_hi is a unit of the shard, and the host has no map from units to v.  The plan is sized
+    // by ALL phantoms not yet emitted -- L never exceeds the text's end -- at the price of at most 8 n_hay bytes of items and idle
+    // lanes, and no wait.  (All ASCII: a unit is its v, and 4.24's bound holds as it stands.)
+    const uint64_t own_hi = c.sc.ub && c.sc.u8->d_ckpt ? c.n : c.sc.piece_own_hi;
+    return plan_batch(c, in, d_spans, own_hi, d_slot + kSpanDropped);
 }
 
-template <int BODY>
+template <class T, int BODY>
 int launch_emit_batch(CoverCall &c, uint64_t n_items, uint64_t w0, uint64_t w1, void *dst) {
     DeviceState &d = c.sc.d;
-    CoverArgs<uint16_t, BODY, true> A;
-    A.hay = static_cast<const uint16_t *>(c.hay);
+    CoverArgs<T, BODY, true> A;
+    if constexpr (sizeof(T) == 1) { // a byte batch: cat_off is voff
+        A.voff = c.d_cat_off;
+        A.n_hay = c.n_hay;
+    }
+    A.hay = static_cast<const T *>(c.hay);
     A.spans = reinterpret_cast<const int2 *>(d.cover_items.p);
     A.pos = n_items ? reinterpret_cast<const int64_t *>(d.cover_plan.p) + kBatchHead + (c.piece_items + kPlanTile - 1) / kPlanTile : nullptr;
     A.n_spans = (int64_t)n_items;
-    A.open = static_cast<const uint16_t *>(c.d_open);
-    A.close = static_cast<const uint16_t *>(c.d_close);
+    A.open = static_cast<const T *>(c.d_open);
+    A.close = static_cast<const T *>(c.d_close);
     A.ol = c.ol;
     A.cl = c.cl;
     A.fill = c.fill;
     A.done = (int64_t)c.done;
     A.cap = (int32_t)std::min<int64_t>(std::max<int64_t>(tunables().cover_lds_segments.load(std::memory_order_relaxed), 0), kCoverLds);
-    return launch_emit_kernel(k_cover_batch_emit<BODY>, A, w0, w1, dst, c.sc.stream);
+    return launch_emit_kernel(k_cover_batch_emit<T, BODY>, A, w0, w1, dst, c.sc.stream);
+}
+
+template <class T>
+int launch_emit_batch_body(CoverCall &c, uint64_t n_items, uint64_t w0, uint64_t w1, void *dst) {
+    return c.body == ACGPU_COVER_KEEP   ? launch_emit_batch<T, ACGPU_COVER_KEEP>(c, n_items, w0, w1, dst)
+           : c.body == ACGPU_COVER_FILL ? launch_emit_batch<T, ACGPU_COVER_FILL>(c, n_items, w0, w1, dst)
+                                        : launch_emit_batch<T, ACGPU_COVER_DROP>(c, n_items, w0, w1, dst);
 }
 
 // m: the intervals the piece merged (where the plan's positions begin in d.cover_plan)
@@ -455,10 +501,7 @@ int cover_piece(void *ctx, uint64_t m, bool last) {
     if (dropped > L - c.done) return ACGPU_E_HIP; // (never: the final spans lie in [done, L))
     const uint64_t total = (L - c.done) + added - dropped;
     rc = emit_piece(c.sc.d, c.sc.stream, c.esz, c.d_out, c.h_out, c.cap, c.out_pos, total, [&](uint64_t w0, uint64_t w1, void *dst) {
-        if (c.h_cat_off)
-            return c.body == ACGPU_COVER_KEEP   ? launch_emit_batch<ACGPU_COVER_KEEP>(c, n_items, w0, w1, dst)
-                   : c.body == ACGPU_COVER_FILL ? launch_emit_batch<ACGPU_COVER_FILL>(c, n_items, w0, w1, dst)
-                                                : launch_emit_batch<ACGPU_COVER_DROP>(c, n_items, w0, w1, dst);
+        if (c.h_cat_off) return c.esz == 1 ? launch_emit_batch_body<uint8_t>(c, n_items, w0, w1, dst) : launch_emit_batch_body<uint16_t>(c, n_items, w0, w1, dst);
         return c.esz == 1 ? launch_emit_body<uint8_t>(c, n_final, m, w0, w1, dst) : launch_emit_body<uint16_t>(c, n_final, m, w0, w1, dst);
     });
     if (rc) return rc;
@@ -536,6 +579,87 @@ int cover_utf8(const acgpu_automaton *ca, const uint8_t *bytes, uint64_t n_bytes
     const bool whole = shard_rule(a->t, ACGPU_REC_SET, false).sequential;
     if ((rc = cover_text(c, 0, whole, PieceScan{a, d, nullptr, 0, &text.shard, c.sc.stream}, text.shard.n_units))) return call.fail(rc);
     if (hipStreamSynchronize(c.sc.stream) != hipSuccess) return call.fail(ACGPU_E_HIP);
+    return cover_result(c, n_out, st);
+}
+
+// The body of acgpu_cover_batch_utf8 and acgpu_cover_batch_utf8_lossy.  The batch is staged as acgpu_replace_batch_utf8 stages it
+// and scanned as ONE device shard, whose units have a separator behind every haystack; the caller's bytes have none.  Merge, plan
+// and emit therefore run over VIRTUAL COORDINATES -- v = byte of the span + index of the haystack: the bytes with a phantom
+// element behind every haystack.  With voff in the place of cat_off everything of "a batch call" above runs
+// unchanged: a phantom is an item {p, p} with delta -1 that emits nothing and skips one element, and a result's first output
+// byte is read off the plan at its phantom.  Only the emit's source knows that the phantoms are not there (CoverShift).
+template <class P>
+int cover_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks, const acgpu_cover_spec *spec,
+                     uint8_t *out, uint64_t cap, uint64_t *out_offsets, uint64_t *n_out, acgpu_cover_stats *st, typename P::Stats *ust) {
+    if (!ca || !offsets || !n_out || !out_offsets || (cap && !out)) return ACGPU_E_INVALID;
+    int rc = check_spec(spec, 1);
+    if (rc) return rc;
+    acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
+    const HostTables &t = a->t;
+    BatchPlan plan; // (in bytes: bytes >= units, so bytes + haystacks < 2^31 bounds the text the scan sees, and the virtual text)
+    if ((rc = check_batch(t, reinterpret_cast<const uint16_t *>(bytes), offsets, n_haystacks, &plan))) return rc;
+    *n_out = 0;
+    out_offsets[0] = 0;
+    if (st) *st = acgpu_cover_stats{};
+    if (ust) *ust = P::stats();
+    if (plan.total == 0) { // (nothing to decode and nothing to rewrite: no device needed)
+        for (uint32_t i = 0; i < n_haystacks; i++) out_offsets[i + 1] = 0;
+        return ACGPU_OK;
+    }
+    PoolCall call(a); // (no device: fails here, and out is untouched)
+    if (call.rc) return call.rc;
+    DeviceState &d = *call.d;
+    if ((rc = call.idle())) return rc; // (the NULL stream: see the stream rule)
+    // the whole batch is validated first, whichever way it is scanned, so that what is refused does not depend on the route
+    Utf8Batch b;
+    rc = stage_utf8_batch(d, t, bytes, offsets, n_haystacks, d.call_stream, &b, plan.per_haystack, P::errors);
+    if (rc && rc != ACGPU_E_ENCODING) return call.fail(rc);
+    if (ust) *ust = P::stats(&b, rc);
+    if (rc) return rc; // (ACGPU_E_ENCODING.  The stream is idle: the pool is as usable as before the call; out and out_offsets[1..] untouched)
+    CoverCall c{SpansCall{a, d, d.call_stream}};
+    c.esz = 1;
+    c.h_out = out;
+    c.cap = cap;
+    if ((rc = upload_spec(c, *spec))) return call.fail(rc);
+    const bool whole = shard_rule(t, ACGPU_REC_SET, false).sequential;
+    if (plan.per_haystack) { // every haystack by the route acgpu_cover_utf8 takes, the results back to back
+        for (uint32_t i = 0; i < n_haystacks; i++) {
+            const uint64_t len = offsets[i + 1] - offsets[i];
+            if (len) {
+                Utf8Text text;
+                if ((rc = stage_utf8_text(d, bytes + offsets[i], len, c.sc.stream, &text, P::errors))) return call.fail(rc == ACGPU_E_ENCODING ? ACGPU_E_HIP : rc); // (never ill-formed: validated)
+                c.sc.u8 = &text;
+                c.hay = text.d_bytes;
+                c.n = len;
+                c.done = 0;
+                rc = cover_text(c, 0, whole, PieceScan{a, d, nullptr, 0, &text.shard, c.sc.stream}, text.shard.n_units);
+                c.sc.u8 = nullptr;
+                if (rc) return call.fail(rc);
+                if (hipStreamSynchronize(c.sc.stream) != hipSuccess) return call.fail(ACGPU_E_HIP); // (the next haystack is staged over this one)
+            }
+            out_offsets[i + 1] = c.out_pos;
+        }
+        return cover_result(c, n_out, st);
+    }
+    std::vector<uint32_t> h_voff;
+    if ((rc = utf8_virtual_offsets(d, b, c.sc.stream, &h_voff, &c.d_cat_off))) return call.fail(rc);
+    if ((rc = d.replace_off.ensure(((size_t)n_haystacks + 1) * 8))) return call.fail(rc);
+    c.sc.u8 = &b.text;
+    c.sc.ub = &b;
+    c.hay = b.text.d_bytes;
+    c.n = plan.total + n_haystacks;
+    c.h_cat_off = h_voff.data();
+    c.n_hay = n_haystacks;
+    c.d_out_off = reinterpret_cast<uint64_t *>(d.replace_off.p);
+    {
+        SeparatorScan sep(d, t);
+        rc = cover_text(c, 0, whole, PieceScan{a, d, nullptr, 0, &b.text.shard, c.sc.stream}, b.text.shard.n_units);
+    }
+    if (rc) return call.fail(rc);
+    // (every phantom was an item of exactly one piece: the pieces' [done, L) tile the virtual text)
+    if (hipMemcpyAsync(out_offsets + 1, c.d_out_off + 1, (size_t)n_haystacks * 8, hipMemcpyDeviceToHost, c.sc.stream) != hipSuccess ||
+        hipStreamSynchronize(c.sc.stream) != hipSuccess)
+        return call.fail(ACGPU_E_HIP);
     return cover_result(c, n_out, st);
 }
 
@@ -660,6 +784,17 @@ int acgpu_cover_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_
 int acgpu_cover_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, const acgpu_cover_spec *spec, uint8_t *out, uint64_t cap,
                            uint64_t *n_out, acgpu_cover_stats *st, acgpu_utf8_lossy_stats *ust) {
     return cover_utf8<Utf8LossyText>(a, bytes, n_bytes, spec, out, cap, n_out, st, ust);
+}
+
+int acgpu_cover_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks, const acgpu_cover_spec *spec,
+                           uint8_t *out, uint64_t cap, uint64_t *out_offsets, uint64_t *n_out, acgpu_cover_stats *st, acgpu_utf8_batch_stats *ust) {
+    return cover_batch_utf8<Utf8StrictBatch>(a, bytes, offsets, n_haystacks, spec, out, cap, out_offsets, n_out, st, ust);
+}
+
+int acgpu_cover_batch_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
+                                 const acgpu_cover_spec *spec, uint8_t *out, uint64_t cap, uint64_t *out_offsets, uint64_t *n_out, acgpu_cover_stats *st,
+                                 acgpu_utf8_lossy_stats *ust) {
+    return cover_batch_utf8<Utf8LossyBatch>(a, bytes, offsets, n_haystacks, spec, out, cap, out_offsets, n_out, st, ust);
 }
 
 } // extern "C"

@@ -239,6 +239,7 @@ struct DeviceState {
     PoolBuf cover_spans, cover_tab, cover_plan;           // acgpu_cover_*: a piece's spans, the call's open and close elements, a DROP call's plan {sums, output positions} (acgpu_cover.hip)
     PoolBuf cover_items;                                  // acgpu_cover_batch_u16: a piece's final spans merged with its separators (its result's offsets: replace_off)
     PoolBuf utf8_in, utf8_aux;                          // the UTF-8 entries: the caller's bytes; {n_units, first_bad, tail, n_replaced}, block sums, checkpoints, a batch's byte offsets, a lossy text's start bitmap (Utf8Aux, acgpu_utf8.hip)
+    PoolBuf utf8_voff;                                   // acgpu_spans_batch_utf8, acgpu_cover_batch_utf8: a batch's offsets in virtual coordinates (utf8_virtual_offsets)
     CountCall *count = nullptr;                          // the counting call that runs on this pool (it holds mu), or nullptr
     double all_density = -1.0;                           // ALL: records per unit of this pool's last call (-1: none yet): k_ac_states or the tile kernel
     int fol_level = 0;                                   // k_longest_follow: 0 = run-up of 128 positions, 1 = of a whole segment (a call's chains had not merged), 2 = not for this pool's texts
@@ -465,6 +466,16 @@ int utf8_map_records(const Utf8Text &text, const Utf8Batch *b, int32_t *d_recs, 
 // byte where the next haystack begins (n_bytes behind the last), as does a unit at or behind the shard's end; any other unit as
 // above.
 int utf8_map_position(const Utf8Text &text, const Utf8Batch *b, uint64_t unit, int64_t *d_out, hipStream_t stream);
+// A batch in VIRTUAL COORDINATES (acgpu_spans_batch_utf8, acgpu_cover_batch_utf8): v = (byte of the span) + (index of the
+// haystack), the caller's bytes with one phantom element behind every haystack; n_bytes + n_haystacks elements in all.
+// voff[j] = boff[j] + j, n_haystacks + 1 words: on the host from b.h_boff, on the device (d.utf8_voff, enqueued) from b.d_boff.
+int utf8_virtual_offsets(DeviceState &d, const Utf8Batch &b, hipStream_t stream, std::vector<uint32_t> *h_voff, const uint32_t **d_voff);
+// cnt Set records of the scan over b's shard, in place in d_recs, enqueued (k_utf8_batch_vmap): units of the shard -> v.  An
+// all-ASCII batch needs no map: there a unit of the shard is its v.
+int utf8_vmap_records(const Utf8Batch &b, int32_t *d_recs, uint64_t cnt, hipStream_t stream);
+// *d_out = a v that no record starting at or behind unit `unit` of b's shard starts before, enqueued (k_utf8_batch_vpos): a
+// separator maps to its phantom, a unit at or behind the shard's end to the text's end; not for an all-ASCII batch (the unit itself).
+int utf8_vmap_position(const Utf8Batch &b, uint64_t unit, int64_t *d_out, hipStream_t stream);
 // The first records of n_entries summaries from units to bytes (k_summary_utf8_bytes): b given, the entries of b's haystacks;
 // else the entries -- one -- of `text` scanned as a text of its own.  Nothing is launched where there are no checkpoints.
 int utf8_summary_bytes(const Utf8Batch *b, const Utf8Text &text, acgpu_batch_summary *d_sum, uint32_t n_entries, hipStream_t stream);

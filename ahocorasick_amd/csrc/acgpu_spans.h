@@ -20,6 +20,9 @@ struct SpansCall {
     DeviceState &d;
     hipStream_t stream;
     const Utf8Text *u8 = nullptr; // a UTF-8 text: the scan runs over its units, the merge over bytes
+    // a batch of UTF-8 texts staged as one shard (u8 == &ub->text): the merge runs over VIRTUAL COORDINATES, the span's bytes with
+    // one phantom element behind every haystack (utf8_virtual_offsets, acgpu_host.h), and cat_off below is voff
+    const Utf8Batch *ub = nullptr;
     int32_t *h_out = nullptr;     // the host entry's result (through d.spans_out) ...
     int32_t *d_out = nullptr;     // ... or the device entry's
     uint64_t cap = 0;

@@ -1,4 +1,5 @@
-// acgpu_spans.hip -- acgpu_spans_u16 / acgpu_spans_batch_u16 / acgpu_spans_device / acgpu_spans_utf8 / acgpu_spans_utf8_lossy (include/acgpu.h): the
+// acgpu_spans.hip -- acgpu_spans_u16 / acgpu_spans_batch_u16 / acgpu_spans_device / acgpu_spans_utf8 / acgpu_spans_utf8_lossy /
+// acgpu_spans_batch_utf8 / acgpu_spans_batch_utf8_lossy (include/acgpu.h): the
 // records of a text merged into its covered runs, on the device, for all five families.
 //
 // A spans call is the sixth consumer of the piece driver (scan_next_piece, acgpu_pieces.hip): the Set records of a piece stay in
@@ -48,6 +49,12 @@
 // (utf8_map_records, two words per record) BEFORE the merge -- the map is monotone, so the order by end survives -- and `bound`
 // goes through utf8_map_position, rounded down, into the slot the kernels read it from.  Keywords with an unpaired surrogate are
 // served: their widened records may overlap in bytes, which a merge does not mind.
+//
+// A BATCH OF UTF-8 TEXTS (acgpu_spans_batch_utf8): the scan's text has a separator unit behind every haystack, the caller's bytes
+// have none, and the records of a lone-surrogate keyword may touch in bytes only -- so the merge runs over VIRTUAL COORDINATES,
+// v = byte of the buffer + index of the haystack: the bytes with one phantom element behind every haystack, which no record
+// covers.  A piece's records become v where they lie (utf8_vmap_records), `bound` becomes a v (utf8_vmap_position), and with
+// voff in the place of cat_off merge, carry and k_span_tag run as for a UTF-16 batch.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -364,7 +371,12 @@ int spans_piece(SpansCall &c, uint64_t base, uint64_t cnt, uint64_t own_hi, bool
     uint64_t bound = spans_bound(c.a->t, own_hi);
     // UTF-8: the bound goes from units to bytes through the checkpoints, rounded down, and stays on the device (an all-ASCII
     // text: a unit is a byte; a bound at the text's end: the text's bytes)
-    if (!last_or_whole && c.u8 && c.u8->d_ckpt) {
+    if (c.ub) { // a batch in virtual coordinates: a unit of an all-ASCII batch's shard is its v; else the device maps it, a separator to its phantom
+        if (!last_or_whole && c.u8->d_ckpt) {
+            if ((rc = utf8_vmap_position(*c.ub, bound, reinterpret_cast<int64_t *>(slot + 2), c.stream))) return rc;
+            Bd.d_bound = reinterpret_cast<const int64_t *>(slot + 2);
+        }
+    } else if (!last_or_whole && c.u8 && c.u8->d_ckpt) {
         if (bound >= c.u8->n_units) {
             bound = c.u8->n_bytes;
         } else {
@@ -454,7 +466,11 @@ int spans_pieces(SpansCall &c, int64_t chain, bool whole, const PieceScan &scan,
         uint64_t cnt = 0, base = 0;
         if ((rc = scan_next_piece(p, scan, &cnt, &base))) return rc;
         // UTF-8: the piece's records go from units to bytes where they lie (text relative: the shard is the whole text)
-        if (c.u8 && (rc = utf8_map_records(*c.u8, nullptr, reinterpret_cast<int32_t *>(d.count_res.p), cnt, ACGPU_REC_SET / 4, c.stream))) return rc;
+        // (a batch of them: to virtual coordinates, the haystack's index added)
+        int32_t *recs = reinterpret_cast<int32_t *>(d.count_res.p);
+        if (c.ub) rc = utf8_vmap_records(*c.ub, recs, cnt, c.stream);
+        else if (c.u8) rc = utf8_map_records(*c.u8, nullptr, recs, cnt, ACGPU_REC_SET / 4, c.stream);
+        if (rc) return rc;
         const bool last = p.pos >= p.end; // (a whole text's one piece ends at p.end)
         const uint64_t m = c.n_carry + cnt;
         if ((rc = spans_piece(c, base, cnt, p.pos, last))) return rc;
@@ -504,6 +520,67 @@ int spans_utf8(const acgpu_automaton *ca, const uint8_t *bytes, uint64_t n_bytes
     c.cap = cap;
     const bool whole = shard_rule(a->t, ACGPU_REC_SET, false).sequential;
     if ((rc = spans_pieces(c, 0, whole, PieceScan{a, d, nullptr, 0, &text.shard, c.stream}, text.shard.n_units))) return call.fail(rc);
+    if (hipStreamSynchronize(c.stream) != hipSuccess) return call.fail(ACGPU_E_HIP);
+    return spans_result(c, n_out, st);
+}
+
+// The body of acgpu_spans_batch_utf8 and acgpu_spans_batch_utf8_lossy.  The batch is staged as acgpu_match_batch_utf8 stages it
+// and scanned as ONE device shard; a piece's records become VIRTUAL COORDINATES where they lie -- v = byte of the span + index of
+// the haystack, the caller's bytes with a phantom element behind every haystack -- and the merge, the carry and
+// k_span_tag run over v as they run over a UTF-16 batch's units: no record covers a phantom, so no span reaches across two
+// haystacks, and a span minus voff[haystack] is in bytes of its haystack.
+template <class P>
+int spans_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks, int32_t *out, uint64_t cap,
+                     uint64_t *n_out, acgpu_spans_stats *st, typename P::Stats *ust) {
+    if (!ca || !offsets || !n_out || (cap && !out)) return ACGPU_E_INVALID;
+    acgpu_automaton *a = const_cast<acgpu_automaton *>(ca);
+    const HostTables &t = a->t;
+    BatchPlan plan; // (in bytes: bytes >= units, so bytes + haystacks < 2^31 bounds the text the scan sees, and the virtual text)
+    int rc = check_batch(t, reinterpret_cast<const uint16_t *>(bytes), offsets, n_haystacks, &plan);
+    if (rc) return rc;
+    *n_out = 0;
+    if (st) *st = acgpu_spans_stats{};
+    if (ust) *ust = P::stats();
+    if (plan.total == 0) return ACGPU_OK; // (nothing to decode and nothing to merge: no device needed)
+    PoolCall call(a); // (no device: fails here, and out is untouched)
+    if (call.rc) return call.rc;
+    DeviceState &d = *call.d;
+    if ((rc = call.idle())) return rc; // (the NULL stream: see the stream rule)
+    // the whole batch is validated first, whichever way it is scanned, so that what is refused does not depend on the route
+    Utf8Batch b;
+    rc = stage_utf8_batch(d, t, bytes, offsets, n_haystacks, d.call_stream, &b, plan.per_haystack, P::errors);
+    if (rc && rc != ACGPU_E_ENCODING) return call.fail(rc);
+    if (ust) *ust = P::stats(&b, rc);
+    if (rc) return rc; // (ACGPU_E_ENCODING.  The stream is idle: the pool is as usable as before the call)
+    SpansCall c{a, d, d.call_stream};
+    c.h_out = out;
+    c.cap = cap;
+    const bool whole = shard_rule(t, ACGPU_REC_SET, false).sequential; // (a device shard: as acgpu_spans_utf8 drives its pieces)
+    if (plan.per_haystack) { // every haystack as a text of its own, by the route acgpu_spans_utf8 takes
+        c.tag_all = true;
+        for (uint32_t i = 0; i < n_haystacks; i++) {
+            const uint64_t len = offsets[i + 1] - offsets[i];
+            if (!len) continue;
+            Utf8Text text; // (staged on the call's stream, behind the copies of the haystack before)
+            if ((rc = stage_utf8_text(d, bytes + offsets[i], len, c.stream, &text, P::errors))) return call.fail(rc == ACGPU_E_ENCODING ? ACGPU_E_HIP : rc); // (never ill-formed: validated)
+            c.u8 = &text;
+            c.tag = (int32_t)i;
+            rc = spans_pieces(c, 0, whole, PieceScan{a, d, nullptr, 0, &text.shard, c.stream}, text.shard.n_units);
+            c.u8 = nullptr;
+            if (rc) return call.fail(rc);
+        }
+    } else {
+        std::vector<uint32_t> h_voff;
+        if ((rc = utf8_virtual_offsets(d, b, c.stream, &h_voff, &c.cat_off))) return call.fail(rc);
+        c.u8 = &b.text;
+        c.ub = &b;
+        c.n_hay = n_haystacks;
+        {
+            SeparatorScan sep(d, t);
+            rc = spans_pieces(c, 0, whole, PieceScan{a, d, nullptr, 0, &b.text.shard, c.stream}, b.text.shard.n_units);
+        }
+        if (rc) return call.fail(rc);
+    }
     if (hipStreamSynchronize(c.stream) != hipSuccess) return call.fail(ACGPU_E_HIP);
     return spans_result(c, n_out, st);
 }
@@ -601,6 +678,16 @@ int acgpu_spans_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_
 int acgpu_spans_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, int32_t *out, uint64_t cap, uint64_t *n_out,
                            acgpu_spans_stats *st, acgpu_utf8_lossy_stats *ust) {
     return spans_utf8<Utf8LossyText>(a, bytes, n_bytes, out, cap, n_out, st, ust);
+}
+
+int acgpu_spans_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks, int32_t *out, uint64_t cap,
+                           uint64_t *n_out, acgpu_spans_stats *st, acgpu_utf8_batch_stats *ust) {
+    return spans_batch_utf8<Utf8StrictBatch>(a, bytes, offsets, n_haystacks, out, cap, n_out, st, ust);
+}
+
+int acgpu_spans_batch_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks, int32_t *out,
+                                 uint64_t cap, uint64_t *n_out, acgpu_spans_stats *st, acgpu_utf8_lossy_stats *ust) {
+    return spans_batch_utf8<Utf8LossyBatch>(a, bytes, offsets, n_haystacks, out, cap, n_out, st, ust);
 }
 
 } // extern "C"

@@ -605,6 +605,63 @@ __global__ void k_utf8_batch_pos(uint32_t x, const uint32_t *__restrict__ cat_of
     *out = (int64_t)s.p;
 }
 
+// ---- VIRTUAL COORDINATES of a batch (acgpu_spans_batch_utf8, acgpu_cover_batch_utf8): v = (byte of the span) +
+// (index of the haystack), the caller's bytes with one PHANTOM element behind every haystack.  voff[j] = boff[j] + j is haystack j's
+// first element, its phantom stands at voff[j + 1] - 1, and the text has n + n_hay elements.  The map unit -> v is monotone. ----
+
+// A lane per word: voff[j] = boff[j] + j, j <= n_hay
+__global__ __launch_bounds__(kU8Threads) void k_utf8_batch_voff(const uint32_t *__restrict__ boff, uint32_t n_words, uint32_t *__restrict__ voff) {
+    const uint32_t j = blockIdx.x * kU8Threads + threadIdx.x;
+    if (j < n_words) voff[j] = boff[j] + j;
+}
+
+// The Set-record form of k_utf8_batch_map for virtual coordinates, a lane per record, in place: {start, end} in units of the
+// batch's text -> v.  Both ends are units of the record's haystack h (no match holds a separator), so its bytes are those of
+// units start - h .. end - 1 - h of the buffer read as one text, and h is added to both.  (An all-ASCII batch needs no launch:
+// there a unit without separators is its byte, and unit - h + h is the unit itself -- utf8_vmap_records.)
+template <bool LOSSY = false>
+__global__ __launch_bounds__(kU8Threads) void k_utf8_batch_vmap(int32_t *__restrict__ recs, uint64_t cnt, const uint32_t *__restrict__ cat_off, uint32_t n_hay,
+                                                                const uint8_t *__restrict__ in, uint32_t n, uint32_t n_units,
+                                                                const uint32_t *__restrict__ ckpt) {
+    const uint64_t i = (uint64_t)blockIdx.x * kU8Threads + threadIdx.x;
+    if (i >= cnt) return;
+    int32_t *r = recs + i * 2;
+    const uint32_t start = (uint32_t)r[0], end = (uint32_t)r[1];
+    const uint32_t h = haystack_of(cat_off, n_hay, start);
+    int32_t s = (int32_t)(start - h), e = (int32_t)(end - h); // (what a range that is none keeps: the record as it was)
+    batch_bytes<LOSSY>(start - h, end - 1u - h, 0u, in, n, n_units, ckpt, &s, &e);
+    r[0] = s + (int32_t)h;
+    r[1] = e + (int32_t)h;
+}
+
+// The form of k_utf8_batch_pos for virtual coordinates, one lane: unit x of the batch's text -> *out, a v no record that starts at
+// or behind unit x starts before (a piece's bound, acgpu_spans.hip).  With h the haystack that holds x:
+//  * x is haystack h's separator: ITS OWN PHANTOM, boff[h + 1] + h.  The position behind it, voff[h + 1], would do as well -- a
+//    record at or behind unit x starts in haystack h + 1 or later, at or behind voff[h + 1], and nothing starts at a phantom.  The
+//    phantom is chosen because it is what the all-ASCII branch computes without a launch (there cat_off == voff and v is the unit,
+//    so a separator IS its phantom): both branches then cut a batch's pieces at the same places, and what is tested on the one
+//    holds on the other.  The price: a span that ends at the haystack's last byte is carried into the next piece (end < B fails).
+//  * a unit at or behind the shard's end: n + n_hay, the text's end;
+//  * any other unit: the first byte of the code point (lossy: of the start) that holds unit x - h of the buffer read as one text --
+//    between the two units of a surrogate pair that rounds down, as utf8_map_position does -- plus h.
+template <bool LOSSY = false>
+__global__ void k_utf8_batch_vpos(uint32_t x, const uint32_t *__restrict__ cat_off, uint32_t n_hay, const uint32_t *__restrict__ boff,
+                                  const uint8_t *__restrict__ in, uint32_t n, const uint32_t *__restrict__ ckpt, int64_t *__restrict__ out) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    if (x >= cat_off[n_hay]) {
+        *out = (int64_t)n + (int64_t)n_hay;
+        return;
+    }
+    const uint32_t h = haystack_of(cat_off, n_hay, x);
+    if (x + 1u == cat_off[h + 1u]) {
+        *out = (int64_t)boff[h + 1u] + (int64_t)h;
+        return;
+    }
+    SeqPos s;
+    (void)locate<LOSSY>(in, n, ckpt, x - h, s);
+    *out = (int64_t)s.p + (int64_t)h;
+}
+
 // A lane per haystack, behind the last piece of a summary call: the first record of every entry that has one, from units
 // relative to its haystack to bytes relative to it.  cat_off given: entry i is haystack i of a batch's text (its first unit
 // without separators is cat_off[i] - i, its first byte boff[i]); not given: the entries' one text is `in` itself.
@@ -646,6 +703,42 @@ int utf8_map_position(const Utf8Text &text, const Utf8Batch *b, uint64_t unit, i
     hipLaunchKernelGGL(text.lossy ? k_utf8_batch_pos<true> : k_utf8_batch_pos<false>, dim3(1), dim3(1), 0, stream, (uint32_t)unit,
                        b ? b->d_cat_off : nullptr, b ? b->n_haystacks : 0u, b ? b->d_boff : nullptr, walked(text), (uint32_t)text.n_bytes, text.d_ckpt,
                        d_out);
+    HIP_TRY(hipGetLastError());
+    return ACGPU_OK;
+}
+
+int utf8_virtual_offsets(DeviceState &d, const Utf8Batch &b, hipStream_t stream, std::vector<uint32_t> *h_voff, const uint32_t **d_voff) {
+    const uint32_t n_words = b.n_haystacks + 1u;
+    try {
+        h_voff->resize(n_words);
+    } catch (...) {
+        return ACGPU_E_NOMEM;
+    }
+    for (uint32_t j = 0; j < n_words; j++) (*h_voff)[j] = b.h_boff[j] + j;
+    const int rc = d.utf8_voff.ensure((size_t)n_words * 4 + 16);
+    if (rc) return rc;
+    uint32_t *voff = reinterpret_cast<uint32_t *>(d.utf8_voff.p);
+    hipLaunchKernelGGL(k_utf8_batch_voff, dim3((n_words + kU8Threads - 1) / kU8Threads), dim3(kU8Threads), 0, stream, b.d_boff, n_words, voff);
+    HIP_TRY(hipGetLastError());
+    *d_voff = voff;
+    return ACGPU_OK;
+}
+
+int utf8_vmap_records(const Utf8Batch &b, int32_t *d_recs, uint64_t cnt, hipStream_t stream) {
+    // an all-ASCII batch: a record's start and end are v as they are -- a unit of haystack h stands h separators behind its byte,
+    // and v adds those h back.  Nothing is to do, so nothing is launched.
+    if (!cnt || !b.text.d_ckpt) return ACGPU_OK;
+    hipLaunchKernelGGL(b.text.lossy ? k_utf8_batch_vmap<true> : k_utf8_batch_vmap<false>, dim3((unsigned)((cnt + kU8Threads - 1) / kU8Threads)),
+                       dim3(kU8Threads), 0, stream, d_recs, cnt, b.d_cat_off, b.n_haystacks, walked(b.text), (uint32_t)b.text.n_bytes,
+                       (uint32_t)b.text.n_units, b.text.d_ckpt);
+    HIP_TRY(hipGetLastError());
+    return ACGPU_OK;
+}
+
+int utf8_vmap_position(const Utf8Batch &b, uint64_t unit, int64_t *d_out, hipStream_t stream) {
+    if (!b.d_cat_off || !b.n_haystacks || !b.text.d_ckpt || unit >= (1ull << 32)) return ACGPU_E_INVALID;
+    hipLaunchKernelGGL(b.text.lossy ? k_utf8_batch_vpos<true> : k_utf8_batch_vpos<false>, dim3(1), dim3(1), 0, stream, (uint32_t)unit, b.d_cat_off,
+                       b.n_haystacks, b.d_boff, walked(b.text), (uint32_t)b.text.n_bytes, b.text.d_ckpt, d_out);
     HIP_TRY(hipGetLastError());
     return ACGPU_OK;
 }

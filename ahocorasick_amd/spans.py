@@ -1,5 +1,6 @@
 """Which parts of a text a dictionary covers: the records of a match call merged into covered runs on the device (include/acgpu.h:
-acgpu_spans_u16, acgpu_spans_batch_u16, acgpu_spans_device, acgpu_spans_utf8, acgpu_spans_utf8_lossy) -- what redaction, highlighting and PII tagging
+acgpu_spans_u16, acgpu_spans_batch_u16, acgpu_spans_device, acgpu_spans_utf8, acgpu_spans_utf8_lossy, acgpu_spans_batch_utf8,
+acgpu_spans_batch_utf8_lossy) -- what redaction, highlighting and PII tagging
 ask, for all five families, AhoCorasick's overlapping records included.
 
 A span is a maximal run of positions that some record covers: overlapping, nested and touching records fall into one span, so
@@ -13,9 +14,9 @@ import ctypes
 import numpy as np
 
 from . import _native as N
-from .strings import Automaton, _fill_shard, _not_none, _pack, _raise_for, _readable, _stats_dict, _utf8_bytes, _utf8_entry, _vp, utf16
+from .strings import Automaton, _fill_shard, _not_none, _pack, _pack_utf8, _raise_for, _readable, _stats_dict, _utf8_bytes, _utf8_entry, _vp, utf16
 
-__all__ = ["spans", "spans_batch", "spans_utf8", "spans_device"]
+__all__ = ["spans", "spans_batch", "spans_batch_utf8", "spans_utf8", "spans_device"]
 
 
 def _automaton(matcher):
@@ -64,6 +65,18 @@ def spans_utf8(matcher, data, errors="strict", stats=None):
     buf = _utf8_bytes(_not_none(data))
     return _spans_call(entry, (_automaton(matcher).handle, _vp(_readable(buf)), int(buf.size)), int(buf.size), stats,
                        tail=(ctypes.byref(stats_type()),))
+
+
+def spans_batch_utf8(matcher, datas, offsets=None, errors="strict", stats=None):
+    """The spans of many short UTF-8 haystacks in ONE device call -> (n, 3) int32 array of (haystack, start, end), start and end in
+    BYTES relative to the haystack: the rows of haystack i are spans_utf8(matcher, datas[i]).  datas: a sequence of bytes-like
+    objects, or with offsets= ONE buffer used in place (utf8_line_offsets: a log file line by line).  Spans never reach across two
+    haystacks.  An ill-formed haystack raises Utf8Error (.haystack, and .start inside it) as find_all_batch_utf8 does -- unless
+    errors="replace": every haystack as its .decode("utf-8", "replace")."""
+    entry, stats_type = _utf8_entry("acgpu_spans_batch_utf8", errors)
+    buf, off = _pack_utf8(datas if offsets is not None else [_not_none(h) for h in datas], offsets)
+    return _spans_call(entry, (_automaton(matcher).handle, _vp(_readable(buf)), _vp(off), len(off) - 1), int(off[-1] - off[0]), stats,
+                       tail=(ctypes.byref(stats_type()),), cols=3)
 
 
 def spans_device(matcher, d_hay, n_units, d_out, cap, stream=0):

@@ -1179,6 +1179,18 @@ int acgpu_stream_replace_utf8_lossy(acgpu_stream *s, const uint8_t *bytes, uint6
  *              is added.  Where there is no free separator unit, or a word matcher's table is not fold-consistent, every
  *              haystack is scanned as a text of its own under the one lock (st->pieces then counts them all).  Works on the
  *              NULL stream, tickets in flight are refused (STREAM RULE), as acgpu_replace_batch_u16.
+ *  acgpu_spans_batch_utf8, acgpu_spans_batch_utf8_lossy : the same for haystacks of BYTES: haystack i is
+ *              bytes[offsets[i] .. offsets[i + 1]) of one buffer, as for acgpu_match_batch_utf8 (offsets[0] need not be 0; bytes
+ *              plus haystacks below 2^31).  start and end are bytes relative to the haystack, and the triples of haystack i are
+ *              the rows acgpu_spans_utf8 (_lossy) returns for it alone; keywords with an unpaired surrogate are served.  A batch
+ *              without a byte: ACGPU_OK, *n_out = 0, no device.  Strict: every haystack must be well-formed on its own (a
+ *              sequence cut by a boundary is ill-formed); ACGPU_E_ENCODING comes plainly after the transcoder's one wait with
+ *              ust->bad_haystack and first_bad as acgpu_match_batch_utf8 sets them, *n_out = 0, out untouched and the stream
+ *              idle, whichever way the batch would have been scanned.  Lossy: never ACGPU_E_ENCODING, every haystack decoded
+ *              on its own.  How: the batch is staged once and scanned in units with a separator behind every haystack; a
+ *              piece's records become positions in the caller's bytes with one phantom element behind every haystack (byte of
+ *              the buffer + index of the haystack) where they lie, and the merge runs over those -- no record covers a phantom,
+ *              so two spans that meet at a seam stay two, also where a keyword with an unpaired surrogate widens them.
  * Not built (mask, highlight and redaction on top of spans: the cover entries below): a record-free form for ACGPU_MODE_ALL from the
  * state words of k_ac_states (the analogue of the counting calls' direct form); stream and multi-device forms; the Java
  * facade.  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
@@ -1196,6 +1208,12 @@ int acgpu_spans_device(const acgpu_automaton *a, acgpu_shard *shard, int32_t *d_
                        acgpu_spans_stats *st);
 int acgpu_spans_batch_u16(const acgpu_automaton *a, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks,
                           int32_t *out /* 3 words per span */, uint64_t cap, uint64_t *n_out, acgpu_spans_stats *st /* may be NULL */);
+int acgpu_spans_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
+                           int32_t *out /* 3 words per span */, uint64_t cap, uint64_t *n_out, acgpu_spans_stats *st /* may be NULL */,
+                           acgpu_utf8_batch_stats *ust /* may be NULL */);
+int acgpu_spans_batch_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
+                                 int32_t *out /* 3 words per span */, uint64_t cap, uint64_t *n_out, acgpu_spans_stats *st /* may be NULL */,
+                                 acgpu_utf8_lossy_stats *ust /* may be NULL */);
 int acgpu_spans_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, int32_t *out, uint64_t cap, uint64_t *n_out,
                      acgpu_spans_stats *st, acgpu_utf8_stats *ust /* may be NULL */);
 int acgpu_spans_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, int32_t *out, uint64_t cap, uint64_t *n_out,
@@ -1252,8 +1270,29 @@ int acgpu_spans_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, uint6
  *              64-bit scan for every body here, runs in front of the piece's one wait: NO wait is added per piece.  Where
  *              there is no free separator unit, or a word matcher's table is not fold-consistent, every haystack runs as a
  *              text of its own under the one lock, open and close uploaded once (st->pieces then counts them all).
- * Not built: stream and multi-device forms, batches of UTF-8 texts, per-keyword open / close, the Java facade.  ACGPU_ABI_VERSION
- * stays as it is.
+ *  acgpu_cover_batch_utf8, acgpu_cover_batch_utf8_lossy : the same for haystacks of BYTES, haystack i being
+ *              bytes[offsets[i] .. offsets[i + 1]) of one buffer as for acgpu_match_batch_utf8 (offsets[0] need not be 0).
+ *              out[out_offsets[i] .. out_offsets[i + 1]) is, byte for byte, what acgpu_cover_utf8 (_lossy) returns for haystack i
+ *              alone; out_offsets[0] == 0, out_offsets[n_haystacks] == *n_out; on ACGPU_E_OVERFLOW *n_out and every offset are
+ *              exact and nothing at or beyond out[cap] is written.  All five families, keywords with an unpaired surrogate
+ *              included; fill is one ASCII byte per covered byte.  The checks come in this order, none needing a device: the
+ *              arguments (NULL a, offsets, n_out, out_offsets; a cap without a buffer), the spec as for acgpu_cover_utf8, the
+ *              offsets as for acgpu_match_batch_utf8 (bytes plus haystacks below 2^31).  A batch without a byte: ACGPU_OK, every
+ *              offset 0, no device.  Strict, ill-formed input (a sequence cut by a haystack boundary is ill-formed):
+ *              ACGPU_E_ENCODING plainly after the transcoder's one wait, ust->bad_haystack and first_bad exactly what
+ *              acgpu_match_batch_utf8 reports for the buffer, *n_out = 0, out and out_offsets[1 ..] untouched, the stream idle.
+ *              Lossy: never ACGPU_E_ENCODING; every haystack is decoded on its own, outside the spans the output is a
+ *              byte-for-byte copy, stray bytes included, and inside a FILL span they are filled.
+ *              How: the scan sees units with a separator behind every haystack, the caller's bytes have none.  Merge, plan and
+ *              emit work on the bytes with one PHANTOM element behind every haystack (position = byte of the buffer + index of
+ *              the haystack): no record covers a phantom, so spans never reach across a seam -- also not the widened records of
+ *              a keyword with an unpaired surrogate, which may touch only in bytes; a phantom is an item that emits nothing
+ *              and skips one element, exactly as the separator of acgpu_cover_batch_u16; only the emit's source knows that the
+ *              phantoms are not in the buffer and subtracts the haystack's index, which is constant within a segment.  No
+ *              wait is added per piece.  The fallback (no free separator unit; a word matcher's table that is not
+ *              fold-consistent) validates the whole batch first, so what is refused does not depend on the route.
+ * Not built: stream, device-resident and multi-device forms, per-keyword open / close, a one-launch form for tiny batches, the Java
+ * facade.  ACGPU_ABI_VERSION stays as it is.
  */
 enum { ACGPU_COVER_KEEP = 0, ACGPU_COVER_FILL = 1, ACGPU_COVER_DROP = 2 };
 typedef struct acgpu_cover_spec {
@@ -1284,6 +1323,12 @@ int acgpu_cover_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_
 int acgpu_cover_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, const acgpu_cover_spec *spec, uint8_t *out,
                            uint64_t cap, uint64_t *n_out, acgpu_cover_stats *st /* may be NULL */,
                            acgpu_utf8_lossy_stats *ust /* may be NULL */);
+int acgpu_cover_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
+                           const acgpu_cover_spec *spec, uint8_t *out, uint64_t cap, uint64_t *out_offsets /* n_haystacks + 1 */,
+                           uint64_t *n_out, acgpu_cover_stats *st /* may be NULL */, acgpu_utf8_batch_stats *ust /* may be NULL */);
+int acgpu_cover_batch_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
+                                 const acgpu_cover_spec *spec, uint8_t *out, uint64_t cap, uint64_t *out_offsets /* n_haystacks + 1 */,
+                                 uint64_t *n_out, acgpu_cover_stats *st /* may be NULL */, acgpu_utf8_lossy_stats *ust /* may be NULL */);
 
 /*
  * Synthetic haystack generator of the benchmark: unit i of the stream is
