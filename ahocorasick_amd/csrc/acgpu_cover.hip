@@ -19,11 +19,11 @@
 // merge), by the plan and the emit of acgpu_emit.h:
 //  * the plan's ITEMS are the piece's final spans.  With w = open_len + close_len, span k begins at output position
 //    pos_k = (s_k - done) + k w - D_k of the piece's output, D_k = 0 for KEEP and FILL -- closed form, no scan, no array -- and the
-//    elements of the piece's spans in front of k for DROP: the plan over the spans' lengths (k_cover_sums, k_cover_offsets,
-//    k_cover_plan), which takes its n from the merge's slot on the device, so it runs BEFORE the piece's one wait.  The positions
-//    ascend strictly: two spans do not touch, so pos_{k+1} - pos_k >= 1 + w.
-//  * the emit's SOURCE (CoverArgs, k_cover_emit<T, BODY>) has up to four sources per segment: open, the body, close, and the text
-//    behind the span up to the next one.
+//    elements of the piece's spans in front of k for DROP: THE PLAN below (k_cover_sums, k_cover_plan_offsets, k_cover_plan) over
+//    what a span adds, w minus its elements, which takes its n from the merge's slot on the device, so it runs BEFORE the piece's
+//    one wait.  The positions ascend strictly: two spans do not touch, so pos_{k+1} - pos_k >= 1 + w.
+//  * the emit's SOURCE (CoverArgs, k_cover_emit<T, BODY, BATCH>) has up to four sources per segment: open, the body, close, and
+//    the text behind the span up to the next one.
 // The running output position and the running span count travel from piece to piece on the host (CoverCall).
 //
 // The text stays on the device for the whole call: a carried span can be as long as the text (keyword "aa" on "aaaa..."), and
@@ -33,9 +33,13 @@
 //
 // acgpu_cover_batch_u16 rewrites many short texts as ONE such text: the haystacks with a separator unit behind each (BatchText),
 // staged whole like acgpu_cover_u16's text.  No record holds a separator, so the spans of that text are the haystacks' spans; a
-// separator is an item of the plan that emits nothing and skips one element, so the results come out back to back (see "a batch
-// call" below, and DESIGN.md 4.24).  acgpu_cover_batch_utf8 does the same for bytes over virtual coordinates, the caller's bytes
-// with a phantom element behind every haystack in the separator's place (cover_batch_utf8 below).
+// separator is an item of the same plan that emits nothing and skips one element, so the results come out back to back (see "a
+// batch call" below, and DESIGN.md 4.24).  acgpu_cover_batch_utf8 does the same for bytes over virtual coordinates, the caller's
+// bytes with a phantom element behind every haystack in the separator's place (cover_batch_utf8 below).
+//
+// One plan, one emit launch (launch_emit<T, BODY, BATCH>, twelve kernels) and one piece step (cover_piece) serve all of them; the
+// separators' descriptor and searches are acgpu_emit.h's, shared with the replace entries; the entries' bodies share
+// cover_staged_text (one staged text to its end), cover_batch_result and the UTF-8 batch front and loop of acgpu_host.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -148,8 +152,8 @@ struct CoverArgs : CoverShift<BATCH && sizeof(T) == 1> {
     __device__ __forceinline__ uint32_t element(const CSeg &s, int32_t u) const {
         if constexpr (VIRT) {
             // (the sources read up front, by value: left in the branches, the compiler made a choice between the body's, close's and
-            // the text's source a choice between the ADDRESSES of s.bsrc, s.csrc and s.tsrc in k_cover_batch_emit<uint8_t, KEEP> and
-            // <.., DROP>, and kept the segment in 36 bytes of private memory for it)
+            // the text's source a choice between the ADDRESSES of s.bsrc, s.csrc and s.tsrc in k_cover_emit<uint8_t, KEEP, true> and
+            // <.., DROP, true>, and kept the segment in 36 bytes of private memory for it)
             const uint32_t bs = s.bsrc + (uint32_t)u, cs = s.csrc + (uint32_t)u, ts = s.tsrc + (uint32_t)u;
             if (u < s.a_end) return open[(uint32_t)(s.osrc + (uint32_t)u)];
             if (u < s.b_end) return BODY == ACGPU_COVER_FILL ? fill : (uint32_t)hay[bs];
@@ -163,36 +167,45 @@ struct CoverArgs : CoverShift<BATCH && sizeof(T) == 1> {
     }
 };
 
-template <class T, int BODY>
-__global__ __launch_bounds__(kEmitBlock) void k_cover_emit(CoverArgs<T, BODY> A) {
+template <class T, int BODY, bool BATCH>
+__global__ __launch_bounds__(kEmitBlock) void k_cover_emit(CoverArgs<T, BODY, BATCH> A) {
     emit_block(A);
 }
 
-template <class T, int BODY>
-__global__ __launch_bounds__(kEmitBlock) void k_cover_batch_emit(CoverArgs<T, BODY, true> A) {
-    emit_block(A);
+// ---- THE PLAN (acgpu_emit.h) of a piece whose positions have no closed form: a DROP call's, over the piece's final spans, and
+// every batch call's, over its items -- final spans and, as {p, p}, separators.  Their number is on the device only, the plan runs
+// in front of the piece's wait: n_final[0] final spans and, n_sep given, n_sep[0] separators; the grids are sized by what the host
+// does know, M >= that number.  d.cover_plan holds {n_final, n_sep} of a batch call | the workgroups' sums | the positions. ----
+
+constexpr int kPlanHead = 2; // words in front of the plan's sums: a batch call's {n_final, n_sep}
+
+__device__ __forceinline__ uint64_t plan_items(const uint64_t *n_final, const uint64_t *n_sep) { return n_final[0] + (n_sep ? n_sep[0] : 0); }
+
+// The plan's item: what item i adds to the output's length beyond the text it stands for -- -1 for a separator (the one item
+// without elements), else w = open + close minus, for DROP, the span's elements
+__device__ __forceinline__ int64_t item_delta(const int2 *items, uint64_t i, int64_t w, int drop) {
+    const int64_t len = (int64_t)(items[i].y - items[i].x);
+    return len == 0 ? -1 : w - (drop ? len : 0);
 }
 
-// ---- the plan (acgpu_emit.h) of a DROP call over the elements of a piece's final spans: their number n = slot[0] is on the
-// device; the grids are sized by m >= n ----
-
-__device__ __forceinline__ int64_t span_len(const int2 *spans, uint64_t i) { return (int64_t)(spans[i].y - spans[i].x); }
-
-__global__ __launch_bounds__(kPlanBlock) void k_cover_sums(const int2 *__restrict__ spans, const uint64_t *__restrict__ slot, int64_t *__restrict__ bsum) {
-    plan_sums([=](uint64_t i) { return span_len(spans, i); }, slot[0], bsum);
+__global__ __launch_bounds__(kPlanBlock) void k_cover_sums(const int2 *__restrict__ items, const uint64_t *__restrict__ n_final, const uint64_t *__restrict__ n_sep,
+                                                           int64_t w, int drop, int64_t *__restrict__ bsum) {
+    plan_sums([=](uint64_t i) { return item_delta(items, i, w, drop); }, plan_items(n_final, n_sep), bsum);
 }
 
-// slot[kSpanDropped] = the elements of all final spans
-__global__ __launch_bounds__(kPlanBlock) void k_cover_offsets(int64_t *__restrict__ bsum, uint32_t n_blocks, uint64_t *__restrict__ slot) {
+// *dropped (the merge's slot[kSpanDropped], or nullptr) = the elements of the text in [done, L) that have no output of their own:
+// the separators, and a DROP call's covered elements -- n_final w minus the sum of the deltas
+__global__ __launch_bounds__(kPlanBlock) void k_cover_plan_offsets(int64_t *__restrict__ bsum, uint32_t n_blocks, const uint64_t *__restrict__ n_final, int64_t w,
+                                                                   uint64_t *__restrict__ dropped) {
     const int64_t sum = plan_offsets(bsum, n_blocks);
-    if (threadIdx.x == 0) slot[kSpanDropped] = (uint64_t)sum;
+    if (threadIdx.x == 0 && dropped) *dropped = (uint64_t)((int64_t)n_final[0] * w - sum);
 }
 
-// pos[k] = (s_k - done) + k w - the elements of the spans in front of k
-__global__ __launch_bounds__(kPlanBlock) void k_cover_plan(const int2 *__restrict__ spans, const uint64_t *__restrict__ slot, const int64_t *__restrict__ bsum,
-                                                           int64_t done, int64_t w, int64_t *__restrict__ pos) {
-    plan_positions([=](uint64_t i) { return span_len(spans, i); }, slot[0], bsum,
-                   [&](uint64_t k, int64_t front) { pos[k] = (int64_t)spans[k].x - done + (int64_t)k * w - front; });
+// pos[k] = (s_k - done) + the deltas in front of item k
+__global__ __launch_bounds__(kPlanBlock) void k_cover_plan(const int2 *__restrict__ items, const uint64_t *__restrict__ n_final, const uint64_t *__restrict__ n_sep,
+                                                           const int64_t *__restrict__ bsum, int64_t done, int64_t w, int drop, int64_t *__restrict__ pos) {
+    plan_positions([=](uint64_t i) { return item_delta(items, i, w, drop); }, plan_items(n_final, n_sep), bsum,
+                   [&](uint64_t k, int64_t front) { pos[k] = (int64_t)items[k].x - done + front; });
 }
 
 // What one call holds while it runs (the caller holds d.mu).  Positions and lengths are ELEMENTS: units, or bytes of a UTF-8 text.
@@ -241,19 +254,32 @@ int upload_spec(CoverCall &c, const acgpu_cover_spec &spec) {
     return ACGPU_OK;
 }
 
-// SpansCall::planned of a DROP call: the plan over the piece's final spans, enqueued in front of the piece's wait
+// d.cover_plan with room for a plan over M items
+int plan_room(DeviceState &d, uint64_t M) { return d.cover_plan.ensure((kPlanHead + (size_t)((M + kPlanTile - 1) / kPlanTile) + M) * 8); }
+uint64_t *plan_head(DeviceState &d) { return reinterpret_cast<uint64_t *>(d.cover_plan.p); }
+int64_t *plan_pos(DeviceState &d, uint64_t M) { return reinterpret_cast<int64_t *>(plan_head(d) + kPlanHead) + (M + kPlanTile - 1) / kPlanTile; }
+
+// the plan's three launches over `items`, sized for M of them (plan_room has made the room)
+void launch_plan(CoverCall &c, const int2 *items, uint64_t M, const uint64_t *n_final, const uint64_t *n_sep, uint64_t *d_dropped) {
+    const uint32_t n_blocks = (uint32_t)((M + kPlanTile - 1) / kPlanTile);
+    int64_t *bsum = reinterpret_cast<int64_t *>(plan_head(c.sc.d) + kPlanHead);
+    const hipStream_t stream = c.sc.stream;
+    const int64_t w = (int64_t)c.ol + (int64_t)c.cl;
+    const int drop = c.body == ACGPU_COVER_DROP;
+    hipLaunchKernelGGL(k_cover_sums, dim3(n_blocks), dim3(kPlanBlock), 0, stream, items, n_final, n_sep, w, drop, bsum);
+    hipLaunchKernelGGL(k_cover_plan_offsets, dim3(1), dim3(kPlanBlock), 0, stream, bsum, n_blocks, n_final, w, d_dropped);
+    hipLaunchKernelGGL(k_cover_plan, dim3(n_blocks), dim3(kPlanBlock), 0, stream, items, n_final, n_sep, (const int64_t *)bsum, (int64_t)c.done, w, drop,
+                       plan_pos(c.sc.d, M));
+}
+
+// SpansCall::planned of a DROP call that is no batch: the plan over the piece's final spans, whose number is the merge's slot[0],
+// enqueued in front of the piece's wait.  A span is never empty, so no item passes for a separator: pos[k] = (s_k - done) + k w -
+// the elements of the spans in front of k, and slot[kSpanDropped] = the elements of all final spans.
 int plan_dropped(void *ctx, uint64_t *d_slot, const int2 *d_spans, uint64_t m) {
     CoverCall &c = *static_cast<CoverCall *>(ctx);
-    DeviceState &d = c.sc.d;
-    const uint32_t n_blocks = (uint32_t)((m + kPlanTile - 1) / kPlanTile);
-    const int rc = d.cover_plan.ensure(((size_t)n_blocks + m) * 8); // workgroup sums | pos
+    const int rc = plan_room(c.sc.d, m);
     if (rc) return rc;
-    int64_t *bsum = reinterpret_cast<int64_t *>(d.cover_plan.p), *pos = bsum + n_blocks;
-    const hipStream_t stream = c.sc.stream;
-    hipLaunchKernelGGL(k_cover_sums, dim3(n_blocks), dim3(kPlanBlock), 0, stream, d_spans, (const uint64_t *)d_slot, bsum);
-    hipLaunchKernelGGL(k_cover_offsets, dim3(1), dim3(kPlanBlock), 0, stream, bsum, n_blocks, d_slot);
-    hipLaunchKernelGGL(k_cover_plan, dim3(n_blocks), dim3(kPlanBlock), 0, stream, d_spans, (const uint64_t *)d_slot, (const int64_t *)bsum, (int64_t)c.done,
-                       (int64_t)c.ol + (int64_t)c.cl, pos);
+    launch_plan(c, d_spans, m, d_slot, nullptr, d_slot + kSpanDropped);
     HIP_TRY(hipGetLastError());
     return ACGPU_OK;
 }
@@ -267,15 +293,10 @@ int plan_dropped(void *ctx, uint64_t *d_slot, const int2 *d_spans, uint64_t m) {
 // the merge's head, counts the separators below L in cat_off and leaves {n_final, n_sep} for the other kernels; the grids are
 // sized by what the host does know, m and the separators in [done, own_hi) -- L <= own_hi, see DESIGN.md 4.24. ----
 
-constexpr int kBatchHead = 2;    // words in front of a batch plan's sums: {n_final, n_sep}
 constexpr int kBatchBlock = 256; // lanes of the merge's and the offsets' workgroups
 
-// The separators a piece may emit: separator i0 + j stands at text position cat_off[i0 + j + 1] - 1 (cat_off[i] = the first unit
-// of haystack i in the concatenation), j < max_sep.
-struct CoverSeps {
-    const uint32_t *cat_off;
-    uint32_t n_hay, i0, max_sep;
-};
+// (The separators a piece may emit are a BatchSeps of acgpu_emit.h in text coordinates, base = 0; its n_sep is the host's bound,
+// the separators in [done, own_hi), and what the kernels take for the count is head[1].)
 
 // Where a piece's n_final and L come from: the merge's head on the device (acgpu_spans.h); slot == nullptr: a piece without
 // intervals, which has no final span and whose L the host knows.
@@ -286,127 +307,75 @@ struct CoverPieceIn {
     int32_t slot_L;  // L is slot[kSpanSettled]
 };
 
-__device__ __forceinline__ int64_t cover_sep_at(const CoverSeps &S, uint32_t j) { return (int64_t)S.cat_off[S.i0 + j + 1] - 1; }
-
-// the first n of the ascending `spans` that start in front of p
+// a piece's spans: ascending starts
 __device__ __forceinline__ uint64_t spans_before(const int2 *__restrict__ spans, uint64_t n, int64_t p) {
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if ((int64_t)spans[mid].x < p) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
+    return starts_before([=](uint64_t i) { return spans[i].x; }, n, p);
 }
 
 // one thread: head = {n_final, the separators in [done, L)}, both counts clamped to what the grids and buffers are sized for
-__global__ void k_cover_batch_head(CoverPieceIn in, CoverSeps S, uint64_t *__restrict__ head) {
+__global__ void k_cover_batch_head(CoverPieceIn in, BatchSeps S, uint32_t n_hay, uint64_t *__restrict__ head) {
     const uint64_t n_final = in.slot ? std::min<uint64_t>(in.slot[0], in.m) : 0;
     const int64_t L = in.slot && in.slot_L ? (int64_t)in.slot[kSpanSettled] : in.L;
-    uint32_t lo = S.i0, hi = S.n_hay; // the first separator at or behind L: cat_off[j + 1] - 1 >= L
+    uint32_t lo = S.i0, hi = n_hay; // the first separator at or behind L: cat_off[j + 1] - 1 >= L
     while (lo < hi) {
         const uint32_t mid = lo + (hi - lo) / 2;
         if ((int64_t)S.cat_off[mid + 1] <= L) lo = mid + 1;
         else hi = mid;
     }
     head[0] = n_final;
-    head[1] = std::min(lo - S.i0, S.max_sep);
+    head[1] = std::min(lo - S.i0, S.n_sep);
 }
 
-// items = the piece's final spans and, as {p, p}, its separators, in position order; a thread per span (t < m) or separator
-__global__ __launch_bounds__(kBatchBlock) void k_cover_batch_merge(const int2 *__restrict__ spans, const uint64_t *__restrict__ head, CoverSeps S, uint64_t m,
+// items = the piece's final spans and, as {p, p}, its separators, in position order (THE SEPARATORS, acgpu_emit.h: a separator
+// is never covered); a thread per span (t < m) or separator
+__global__ __launch_bounds__(kBatchBlock) void k_cover_batch_merge(const int2 *__restrict__ spans, const uint64_t *__restrict__ head, BatchSeps S, uint64_t m,
                                                                    int2 *__restrict__ items) {
+    S.base = 0; // (text coordinates, as plan_batch sets it: said here, the subtraction is compiled away)
     const uint64_t t = (uint64_t)blockIdx.x * kBatchBlock + threadIdx.x;
     const uint64_t n_final = head[0];
     const uint32_t n_sep = (uint32_t)head[1];
     if (t < m) {
         if (t >= n_final) return;
         const int2 sp = spans[t];
-        uint32_t lo = 0, hi = n_sep; // the separators in front of the span
-        while (lo < hi) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (cover_sep_at(S, mid) < (int64_t)sp.x) lo = mid + 1;
-            else hi = mid;
-        }
-        items[t + lo] = sp;
+        items[t + seps_before(S, n_sep, sp.x)] = sp;
     } else if (t - m < n_sep) {
-        const int32_t p = (int32_t)cover_sep_at(S, (uint32_t)(t - m));
+        const int32_t p = (int32_t)sep_at(S, (uint32_t)(t - m));
         items[(t - m) + spans_before(spans, n_final, p)] = make_int2(p, p);
     }
 }
 
-// The plan's item: what item i adds to the output's length beyond the text it stands for
-__device__ __forceinline__ int64_t batch_delta(const int2 *items, uint64_t i, int64_t w, int drop) {
-    const int64_t len = (int64_t)(items[i].y - items[i].x);
-    return len == 0 ? -1 : w - (drop ? len : 0);
-}
-
-__global__ __launch_bounds__(kPlanBlock) void k_cover_batch_sums(const int2 *__restrict__ items, const uint64_t *__restrict__ head, int64_t w, int drop,
-                                                                 int64_t *__restrict__ bsum) {
-    plan_sums([=](uint64_t i) { return batch_delta(items, i, w, drop); }, head[0] + head[1], bsum);
-}
-
-// *dropped (the merge's slot[kSpanDropped], or nullptr) = the elements of the text in [done, L) that have no output of their own:
-// the separators, and a DROP call's covered elements
-__global__ __launch_bounds__(kPlanBlock) void k_cover_batch_plan_offsets(int64_t *__restrict__ bsum, uint32_t n_blocks, const uint64_t *__restrict__ head, int64_t w,
-                                                                         uint64_t *__restrict__ dropped) {
-    const int64_t sum = plan_offsets(bsum, n_blocks);
-    if (threadIdx.x == 0 && dropped) *dropped = (uint64_t)((int64_t)head[0] * w - sum);
-}
-
-__global__ __launch_bounds__(kPlanBlock) void k_cover_batch_plan(const int2 *__restrict__ items, const uint64_t *__restrict__ head, const int64_t *__restrict__ bsum,
-                                                                 int64_t done, int64_t w, int drop, int64_t *__restrict__ pos) {
-    plan_positions([=](uint64_t i) { return batch_delta(items, i, w, drop); }, head[0] + head[1], bsum,
-                   [&](uint64_t k, int64_t front) { pos[k] = (int64_t)items[k].x - done + front; });
-}
-
 // Separator i0 + j ends haystack i0 + j: the result of haystack i0 + j + 1 begins where the separator's item stands
-__global__ __launch_bounds__(kBatchBlock) void k_cover_batch_offsets(const int2 *__restrict__ spans, const uint64_t *__restrict__ head, CoverSeps S,
+__global__ __launch_bounds__(kBatchBlock) void k_cover_batch_offsets(const int2 *__restrict__ spans, const uint64_t *__restrict__ head, BatchSeps S,
                                                                      const int64_t *__restrict__ pos, uint64_t out_pos, uint64_t *__restrict__ out_off) {
+    S.base = 0; // (as in k_cover_batch_merge)
     const uint32_t j = blockIdx.x * kBatchBlock + threadIdx.x;
     if (j >= (uint32_t)head[1]) return;
-    out_off[(uint64_t)S.i0 + j + 1] = out_pos + (uint64_t)pos[j + spans_before(spans, head[0], cover_sep_at(S, j))];
-}
-
-// separator i stands at cat_off[i + 1] - 1: the separators in [lo, hi) are [*i0, *i1)
-void separators_in(const uint32_t *h_cat_off, uint32_t n_hay, uint64_t lo, uint64_t hi, uint32_t *i0, uint32_t *i1) {
-    const uint32_t *sep_end = h_cat_off + 1; // at or behind x <=> sep_end[i] > x
-    *i0 = (uint32_t)(std::upper_bound(sep_end, sep_end + n_hay, lo) - sep_end);
-    *i1 = std::max(*i0, (uint32_t)(std::upper_bound(sep_end, sep_end + n_hay, hi) - sep_end));
+    out_off[(uint64_t)S.i0 + j + 1] = out_pos + (uint64_t)pos[j + spans_before(spans, head[0], sep_at(S, j))];
 }
 
 // The item list and the plan of a batch call's piece that merged m intervals and owned [.., own_hi): enqueued, no wait.
 int plan_batch(CoverCall &c, const CoverPieceIn &in, const int2 *d_spans, uint64_t own_hi, uint64_t *d_dropped) {
     DeviceState &d = c.sc.d;
-    CoverSeps S;
+    BatchSeps S;
     uint32_t i1;
     separators_in(c.h_cat_off, c.n_hay, c.done, own_hi, &S.i0, &i1);
     S.cat_off = c.d_cat_off;
-    S.n_hay = c.n_hay;
-    S.max_sep = i1 - S.i0;
-    const uint64_t M = in.m + S.max_sep;
+    S.n_sep = i1 - S.i0;
+    const uint64_t M = in.m + S.n_sep;
     c.piece_items = M;
-    c.piece_max_sep = S.max_sep;
+    c.piece_max_sep = S.n_sep;
     if (!M) return ACGPU_OK;
-    const uint32_t n_blocks = (uint32_t)((M + kPlanTile - 1) / kPlanTile);
     int rc = d.cover_items.ensure((size_t)M * 8 + 16);
-    if (rc || (rc = d.cover_plan.ensure((kBatchHead + (size_t)n_blocks + M) * 8))) return rc; // head | workgroup sums | pos
-    uint64_t *head = reinterpret_cast<uint64_t *>(d.cover_plan.p);
-    int64_t *bsum = reinterpret_cast<int64_t *>(head + kBatchHead), *pos = bsum + n_blocks;
+    if (rc || (rc = plan_room(d, M))) return rc;
+    uint64_t *head = plan_head(d);
     int2 *items = reinterpret_cast<int2 *>(d.cover_items.p);
     const hipStream_t stream = c.sc.stream;
-    const int64_t w = (int64_t)c.ol + (int64_t)c.cl;
-    const int drop = c.body == ACGPU_COVER_DROP;
-    hipLaunchKernelGGL(k_cover_batch_head, dim3(1), dim3(1), 0, stream, in, S, head);
-    hipLaunchKernelGGL(k_cover_batch_merge, dim3((unsigned)((M + kBatchBlock - 1) / kBatchBlock)), dim3(kBatchBlock), 0, stream, d_spans, (const uint64_t *)head, S,
-                       in.m, items);
-    hipLaunchKernelGGL(k_cover_batch_sums, dim3(n_blocks), dim3(kPlanBlock), 0, stream, (const int2 *)items, (const uint64_t *)head, w, drop, bsum);
-    hipLaunchKernelGGL(k_cover_batch_plan_offsets, dim3(1), dim3(kPlanBlock), 0, stream, bsum, n_blocks, (const uint64_t *)head, w, d_dropped);
-    hipLaunchKernelGGL(k_cover_batch_plan, dim3(n_blocks), dim3(kPlanBlock), 0, stream, (const int2 *)items, (const uint64_t *)head, (const int64_t *)bsum,
-                       (int64_t)c.done, w, drop, pos);
-    if (S.max_sep)
-        hipLaunchKernelGGL(k_cover_batch_offsets, dim3((S.max_sep + kBatchBlock - 1) / kBatchBlock), dim3(kBatchBlock), 0, stream, d_spans, (const uint64_t *)head, S,
-                           (const int64_t *)pos, c.out_pos, c.d_out_off);
+    hipLaunchKernelGGL(k_cover_batch_head, dim3(1), dim3(1), 0, stream, in, S, c.n_hay, head);
+    hipLaunchKernelGGL(k_cover_batch_merge, dim3((unsigned)((M + kBatchBlock - 1) / kBatchBlock)), dim3(kBatchBlock), 0, stream, d_spans, head, S, in.m, items);
+    launch_plan(c, items, M, head, head + 1, d_dropped);
+    if (S.n_sep)
+        hipLaunchKernelGGL(k_cover_batch_offsets, dim3((S.n_sep + kBatchBlock - 1) / kBatchBlock), dim3(kBatchBlock), 0, stream, d_spans, head, S,
+                           (const int64_t *)plan_pos(d, M), c.out_pos, c.d_out_off);
     HIP_TRY(hipGetLastError());
     return ACGPU_OK;
 }
@@ -422,17 +391,19 @@ int plan_batch_piece(void *ctx, uint64_t *d_slot, const int2 *d_spans, uint64_t 
     return plan_batch(c, in, d_spans, own_hi, d_slot + kSpanDropped);
 }
 
-template <class T, int BODY>
-int launch_emit_batch(CoverCall &c, uint64_t n_items, uint64_t w0, uint64_t w1, void *dst) {
+// The emit of a window of a piece's output over n_items items: the piece's final spans in d.cover_spans, or, BATCH, its item list
+// in d.cover_items.  M: the items the piece's plan was sized for (where its positions begin in d.cover_plan), 0: there is none.
+template <class T, int BODY, bool BATCH>
+int launch_emit(CoverCall &c, uint64_t n_items, uint64_t M, uint64_t w0, uint64_t w1, void *dst) {
     DeviceState &d = c.sc.d;
-    CoverArgs<T, BODY, true> A;
-    if constexpr (sizeof(T) == 1) { // a byte batch: cat_off is voff
+    CoverArgs<T, BODY, BATCH> A;
+    if constexpr (BATCH && sizeof(T) == 1) { // a byte batch: cat_off is voff
         A.voff = c.d_cat_off;
         A.n_hay = c.n_hay;
     }
     A.hay = static_cast<const T *>(c.hay);
-    A.spans = reinterpret_cast<const int2 *>(d.cover_items.p);
-    A.pos = n_items ? reinterpret_cast<const int64_t *>(d.cover_plan.p) + kBatchHead + (c.piece_items + kPlanTile - 1) / kPlanTile : nullptr;
+    A.spans = reinterpret_cast<const int2 *>(BATCH ? d.cover_items.p : d.cover_spans.p);
+    A.pos = (BATCH || BODY == ACGPU_COVER_DROP) && M ? plan_pos(d, M) : nullptr;
     A.n_spans = (int64_t)n_items;
     A.open = static_cast<const T *>(c.d_open);
     A.close = static_cast<const T *>(c.d_close);
@@ -441,40 +412,20 @@ int launch_emit_batch(CoverCall &c, uint64_t n_items, uint64_t w0, uint64_t w1, 
     A.fill = c.fill;
     A.done = (int64_t)c.done;
     A.cap = (int32_t)std::min<int64_t>(std::max<int64_t>(tunables().cover_lds_segments.load(std::memory_order_relaxed), 0), kCoverLds);
-    return launch_emit_kernel(k_cover_batch_emit<T, BODY>, A, w0, w1, dst, c.sc.stream);
+    return launch_emit_kernel(k_cover_emit<T, BODY, BATCH>, A, w0, w1, dst, c.sc.stream);
 }
 
-template <class T>
-int launch_emit_batch_body(CoverCall &c, uint64_t n_items, uint64_t w0, uint64_t w1, void *dst) {
-    return c.body == ACGPU_COVER_KEEP   ? launch_emit_batch<T, ACGPU_COVER_KEEP>(c, n_items, w0, w1, dst)
-           : c.body == ACGPU_COVER_FILL ? launch_emit_batch<T, ACGPU_COVER_FILL>(c, n_items, w0, w1, dst)
-                                        : launch_emit_batch<T, ACGPU_COVER_DROP>(c, n_items, w0, w1, dst);
-}
-
-// m: the intervals the piece merged (where the plan's positions begin in d.cover_plan)
-template <class T, int BODY>
-int launch_emit_as(CoverCall &c, uint64_t n_final, uint64_t m, uint64_t w0, uint64_t w1, void *dst) {
-    DeviceState &d = c.sc.d;
-    CoverArgs<T, BODY> A;
-    A.hay = static_cast<const T *>(c.hay);
-    A.spans = reinterpret_cast<const int2 *>(d.cover_spans.p);
-    A.pos = BODY == ACGPU_COVER_DROP && m ? reinterpret_cast<const int64_t *>(d.cover_plan.p) + (m + kPlanTile - 1) / kPlanTile : nullptr;
-    A.n_spans = (int64_t)n_final;
-    A.open = static_cast<const T *>(c.d_open);
-    A.close = static_cast<const T *>(c.d_close);
-    A.ol = c.ol;
-    A.cl = c.cl;
-    A.fill = c.fill;
-    A.done = (int64_t)c.done;
-    A.cap = (int32_t)std::min<int64_t>(std::max<int64_t>(tunables().cover_lds_segments.load(std::memory_order_relaxed), 0), kCoverLds);
-    return launch_emit_kernel(k_cover_emit<T, BODY>, A, w0, w1, dst, c.sc.stream);
-}
-
-template <class T>
-int launch_emit_body(CoverCall &c, uint64_t n_final, uint64_t m, uint64_t w0, uint64_t w1, void *dst) {
-    return c.body == ACGPU_COVER_KEEP   ? launch_emit_as<T, ACGPU_COVER_KEEP>(c, n_final, m, w0, w1, dst)
-           : c.body == ACGPU_COVER_FILL ? launch_emit_as<T, ACGPU_COVER_FILL>(c, n_final, m, w0, w1, dst)
-                                        : launch_emit_as<T, ACGPU_COVER_DROP>(c, n_final, m, w0, w1, dst);
+// ... as the call's element, body and kind have it: one of the twelve
+int launch_emit_for(CoverCall &c, uint64_t n_items, uint64_t M, uint64_t w0, uint64_t w1, void *dst) {
+    auto as = [&](auto elem, auto batch) {
+        using T = decltype(elem);
+        constexpr bool B = decltype(batch)::value;
+        return c.body == ACGPU_COVER_KEEP   ? launch_emit<T, ACGPU_COVER_KEEP, B>(c, n_items, M, w0, w1, dst)
+               : c.body == ACGPU_COVER_FILL ? launch_emit<T, ACGPU_COVER_FILL, B>(c, n_items, M, w0, w1, dst)
+                                            : launch_emit<T, ACGPU_COVER_DROP, B>(c, n_items, M, w0, w1, dst);
+    };
+    if (c.h_cat_off) return c.esz == 1 ? as(uint8_t{}, std::true_type{}) : as(uint16_t{}, std::true_type{});
+    return c.esz == 1 ? as(uint8_t{}, std::false_type{}) : as(uint16_t{}, std::false_type{});
 }
 
 // SpansCall::merged: behind a piece's merge of m intervals, emit the text's elements [done, L) with the piece's final spans rewritten
@@ -500,18 +451,18 @@ int cover_piece(void *ctx, uint64_t m, bool last) {
     const uint64_t added = n_final * ((uint64_t)c.ol + c.cl);
     if (dropped > L - c.done) return ACGPU_E_HIP; // (never: the final spans lie in [done, L))
     const uint64_t total = (L - c.done) + added - dropped;
-    rc = emit_piece(c.sc.d, c.sc.stream, c.esz, c.d_out, c.h_out, c.cap, c.out_pos, total, [&](uint64_t w0, uint64_t w1, void *dst) {
-        if (c.h_cat_off) return c.esz == 1 ? launch_emit_batch_body<uint8_t>(c, n_items, w0, w1, dst) : launch_emit_batch_body<uint16_t>(c, n_items, w0, w1, dst);
-        return c.esz == 1 ? launch_emit_body<uint8_t>(c, n_final, m, w0, w1, dst) : launch_emit_body<uint16_t>(c, n_final, m, w0, w1, dst);
-    });
+    const uint64_t M = c.h_cat_off ? c.piece_items : m; // what the piece's plan, if it has one, was sized for
+    rc = emit_piece(c.sc.d, c.sc.stream, c.esz, c.d_out, c.h_out, c.cap, c.out_pos, total,
+                    [&](uint64_t w0, uint64_t w1, void *dst) { return launch_emit_for(c, n_items, M, w0, w1, dst); });
     if (rc) return rc;
     c.done = L;
     c.out_pos += total;
     return ACGPU_OK;
 }
 
-// The pieces of the whole text on the device, c.hay (spans_pieces, acgpu_spans.h), each merged, planned and emitted.
-int cover_text(CoverCall &c, int64_t chain, bool whole, const PieceScan &scan, uint64_t n_units) {
+// The pieces of the whole text on the device, c.hay, scanned as the device shard `shard`, its units (spans_pieces, acgpu_spans.h),
+// each merged, planned and emitted: what follows the last piece's wait is enqueued, not waited for.
+int cover_text(CoverCall &c, const acgpu_shard &shard) {
     SpansCall &sc = c.sc;
     int rc;
     if (c.h_out && (rc = emit_slabs_ready(sc.d))) return rc;
@@ -519,7 +470,20 @@ int cover_text(CoverCall &c, int64_t chain, bool whole, const PieceScan &scan, u
     sc.ctx = &c;
     sc.merged = cover_piece;
     sc.planned = c.h_cat_off ? plan_batch_piece : c.body == ACGPU_COVER_DROP ? plan_dropped : nullptr;
-    return spans_pieces(sc, chain, whole, scan, n_units);
+    const bool whole = shard_rule(sc.a->t, ACGPU_REC_SET, false).sequential;
+    return spans_pieces(sc, shard.chain_entry, whole, PieceScan{sc.a, sc.d, nullptr, 0, &shard, sc.stream}, shard.n_units);
+}
+
+// One text that a host entry has staged -- `hay`, n elements, on the device; `shard`, its units -- through its pieces to its end.
+// c.cap, c.out_pos and the stats carry on from text to text (a batch call haystack by haystack: the next text is staged over
+// this one, hence the wait).
+int cover_staged_text(CoverCall &c, const void *hay, uint64_t n, const acgpu_shard &shard) {
+    c.hay = hay;
+    c.n = n;
+    c.done = 0;
+    const int rc = cover_text(c, shard);
+    if (rc) return rc;
+    return hipStreamSynchronize(c.sc.stream) != hipSuccess ? ACGPU_E_HIP : ACGPU_OK;
 }
 
 // what every entry returns behind its last piece
@@ -535,6 +499,15 @@ int cover_result(const CoverCall &c, uint64_t *n_out, acgpu_cover_stats *st) {
     }
     *n_out = c.out_pos;
     return c.out_pos > c.cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
+}
+
+// ... and a batch call over one text behind its cover_text: the results' offsets come back, with the call's one final wait.
+// (Every separator, or phantom, was an item of exactly one piece: the pieces' [done, L) tile the text.)
+int cover_batch_result(const PoolCall &call, const CoverCall &c, uint64_t *out_offsets, uint64_t *n_out, acgpu_cover_stats *st) {
+    if (hipMemcpyAsync(out_offsets + 1, c.d_out_off + 1, (size_t)c.n_hay * 8, hipMemcpyDeviceToHost, c.sc.stream) != hipSuccess ||
+        hipStreamSynchronize(c.sc.stream) != hipSuccess)
+        return call.fail(ACGPU_E_HIP);
+    return cover_result(c, n_out, st);
 }
 
 // the checks all entries share, none of which needs a device; esz: bytes of an element
@@ -571,14 +544,10 @@ int cover_utf8(const acgpu_automaton *ca, const uint8_t *bytes, uint64_t n_bytes
     CoverCall c{SpansCall{a, d, d.call_stream}};
     c.sc.u8 = &text;
     c.esz = 1;
-    c.hay = text.d_bytes;
-    c.n = n_bytes;
     c.h_out = out;
     c.cap = cap;
     if ((rc = upload_spec(c, *spec))) return call.fail(rc);
-    const bool whole = shard_rule(a->t, ACGPU_REC_SET, false).sequential;
-    if ((rc = cover_text(c, 0, whole, PieceScan{a, d, nullptr, 0, &text.shard, c.sc.stream}, text.shard.n_units))) return call.fail(rc);
-    if (hipStreamSynchronize(c.sc.stream) != hipSuccess) return call.fail(ACGPU_E_HIP);
+    if ((rc = cover_staged_text(c, text.d_bytes, n_bytes, text.shard))) return call.fail(rc);
     return cover_result(c, n_out, st);
 }
 
@@ -609,36 +578,24 @@ int cover_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, const uint
     PoolCall call(a); // (no device: fails here, and out is untouched)
     if (call.rc) return call.rc;
     DeviceState &d = *call.d;
-    if ((rc = call.idle())) return rc; // (the NULL stream: see the stream rule)
-    // the whole batch is validated first, whichever way it is scanned, so that what is refused does not depend on the route
     Utf8Batch b;
-    rc = stage_utf8_batch(d, t, bytes, offsets, n_haystacks, d.call_stream, &b, plan.per_haystack, P::errors);
-    if (rc && rc != ACGPU_E_ENCODING) return call.fail(rc);
-    if (ust) *ust = P::stats(&b, rc);
-    if (rc) return rc; // (ACGPU_E_ENCODING.  The stream is idle: the pool is as usable as before the call; out and out_offsets[1..] untouched)
+    if ((rc = utf8_batch_front<P>(call, t, bytes, offsets, n_haystacks, plan, &b, ust))) return rc; // (ACGPU_E_ENCODING: out and out_offsets[1..] untouched)
     CoverCall c{SpansCall{a, d, d.call_stream}};
     c.esz = 1;
     c.h_out = out;
     c.cap = cap;
     if ((rc = upload_spec(c, *spec))) return call.fail(rc);
-    const bool whole = shard_rule(t, ACGPU_REC_SET, false).sequential;
     if (plan.per_haystack) { // every haystack by the route acgpu_cover_utf8 takes, the results back to back
-        for (uint32_t i = 0; i < n_haystacks; i++) {
-            const uint64_t len = offsets[i + 1] - offsets[i];
-            if (len) {
-                Utf8Text text;
-                if ((rc = stage_utf8_text(d, bytes + offsets[i], len, c.sc.stream, &text, P::errors))) return call.fail(rc == ACGPU_E_ENCODING ? ACGPU_E_HIP : rc); // (never ill-formed: validated)
+        rc = utf8_each_haystack<P>(
+            d, bytes, offsets, n_haystacks, c.sc.stream,
+            [&](uint32_t i, const Utf8Text &text) {
                 c.sc.u8 = &text;
-                c.hay = text.d_bytes;
-                c.n = len;
-                c.done = 0;
-                rc = cover_text(c, 0, whole, PieceScan{a, d, nullptr, 0, &text.shard, c.sc.stream}, text.shard.n_units);
+                const int prc = cover_staged_text(c, text.d_bytes, offsets[i + 1] - offsets[i], text.shard);
                 c.sc.u8 = nullptr;
-                if (rc) return call.fail(rc);
-                if (hipStreamSynchronize(c.sc.stream) != hipSuccess) return call.fail(ACGPU_E_HIP); // (the next haystack is staged over this one)
-            }
-            out_offsets[i + 1] = c.out_pos;
-        }
+                return prc;
+            },
+            [&](uint32_t i) { out_offsets[i + 1] = c.out_pos; });
+        if (rc) return call.fail(rc);
         return cover_result(c, n_out, st);
     }
     std::vector<uint32_t> h_voff;
@@ -653,14 +610,10 @@ int cover_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, const uint
     c.d_out_off = reinterpret_cast<uint64_t *>(d.replace_off.p);
     {
         SeparatorScan sep(d, t);
-        rc = cover_text(c, 0, whole, PieceScan{a, d, nullptr, 0, &b.text.shard, c.sc.stream}, b.text.shard.n_units);
+        rc = cover_text(c, b.text.shard);
     }
     if (rc) return call.fail(rc);
-    // (every phantom was an item of exactly one piece: the pieces' [done, L) tile the virtual text)
-    if (hipMemcpyAsync(out_offsets + 1, c.d_out_off + 1, (size_t)n_haystacks * 8, hipMemcpyDeviceToHost, c.sc.stream) != hipSuccess ||
-        hipStreamSynchronize(c.sc.stream) != hipSuccess)
-        return call.fail(ACGPU_E_HIP);
-    return cover_result(c, n_out, st);
+    return cover_batch_result(call, c, out_offsets, n_out, st);
 }
 
 } // namespace
@@ -681,14 +634,10 @@ int acgpu_cover_u16(const acgpu_automaton *ca, const uint16_t *haystack, uint64_
     acgpu_shard sh;
     if ((rc = stage_whole_text(d, haystack, n_units, &sh))) return call.fail(rc); // the whole text, once: see the head of this file
     CoverCall c{SpansCall{a, d, d.call_stream}};
-    c.hay = sh.d_hay;
-    c.n = n_units;
     c.h_out = reinterpret_cast<uint8_t *>(out);
     c.cap = cap;
     if ((rc = upload_spec(c, *spec))) return call.fail(rc);
-    const bool whole = shard_rule(a->t, ACGPU_REC_SET, false).sequential;
-    if ((rc = cover_text(c, 0, whole, PieceScan{a, d, nullptr, 0, &sh, c.sc.stream}, n_units))) return call.fail(rc);
-    if (hipStreamSynchronize(c.sc.stream) != hipSuccess) return call.fail(ACGPU_E_HIP);
+    if ((rc = cover_staged_text(c, sh.d_hay, n_units, sh))) return call.fail(rc);
     return cover_result(c, n_out, st);
 }
 
@@ -712,8 +661,7 @@ int acgpu_cover_device(const acgpu_automaton *ca, acgpu_shard *shard, const acgp
     c.d_out = reinterpret_cast<uint8_t *>(d_out);
     c.cap = cap;
     if ((rc = upload_spec(c, *spec))) return rc;
-    const bool whole = shard_rule(a->t, ACGPU_REC_SET, false).sequential;
-    rc = cover_text(c, shard->chain_entry, whole, PieceScan{a, d, nullptr, 0, shard, stream}, shard->n_units);
+    rc = cover_text(c, *shard);
     const hipError_t e = hipStreamSynchronize(stream); // the final wait
     if (rc) return rc;
     HIP_TRY(e);
@@ -741,18 +689,13 @@ int acgpu_cover_batch_u16(const acgpu_automaton *ca, const uint16_t *units, cons
     c.h_out = reinterpret_cast<uint8_t *>(out);
     c.cap = cap;
     if ((rc = upload_spec(c, *spec))) return call.fail(rc);
-    const bool whole = shard_rule(t, ACGPU_REC_SET, false).sequential;
     acgpu_shard sh;
     if (plan.per_haystack) { // every haystack by the route acgpu_cover_u16 takes, the results back to back
         for (uint32_t i = 0; i < n_haystacks; i++) {
             const uint64_t len = offsets[i + 1] - offsets[i];
             if (len) {
                 if ((rc = stage_whole_text(d, units + offsets[i], len, &sh))) return call.fail(rc);
-                c.hay = sh.d_hay;
-                c.n = len;
-                c.done = 0;
-                if ((rc = cover_text(c, 0, whole, PieceScan{a, d, nullptr, 0, &sh, c.sc.stream}, len))) return call.fail(rc);
-                if (hipStreamSynchronize(c.sc.stream) != hipSuccess) return call.fail(ACGPU_E_HIP); // (the next haystack is staged over this one)
+                if ((rc = cover_staged_text(c, sh.d_hay, len, sh))) return call.fail(rc);
             }
             out_offsets[i + 1] = c.out_pos;
         }
@@ -768,12 +711,8 @@ int acgpu_cover_batch_u16(const acgpu_automaton *ca, const uint16_t *units, cons
     c.d_cat_off = text.d_off();
     c.n_hay = n_haystacks;
     c.d_out_off = reinterpret_cast<uint64_t *>(d.replace_off.p);
-    if ((rc = cover_text(c, 0, whole, PieceScan{a, d, nullptr, 0, &sh, c.sc.stream}, text.cat))) return call.fail(rc);
-    // (every separator was an item of exactly one piece: the pieces' [done, L) tile the text)
-    if (hipMemcpyAsync(out_offsets + 1, c.d_out_off + 1, (size_t)n_haystacks * 8, hipMemcpyDeviceToHost, c.sc.stream) != hipSuccess ||
-        hipStreamSynchronize(c.sc.stream) != hipSuccess)
-        return call.fail(ACGPU_E_HIP);
-    return cover_result(c, n_out, st);
+    if ((rc = cover_text(c, sh))) return call.fail(rc);
+    return cover_batch_result(call, c, out_offsets, n_out, st);
 }
 
 int acgpu_cover_utf8(const acgpu_automaton *a, const uint8_t *bytes, uint64_t n_bytes, const acgpu_cover_spec *spec, uint8_t *out, uint64_t cap,

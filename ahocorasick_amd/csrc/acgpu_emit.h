@@ -1,7 +1,8 @@
 // acgpu_emit.h -- the rewrite family's device and host code that does not depend on what an output is made of: the 64-bit plan
 // over a piece's items, the emit of a window of a piece's output from a SOURCE, and a piece's way out, straight to the caller's
 // device memory or to the host through two slabs.  k_replace_emit (acgpu_replace.hip) and k_cover_emit (acgpu_cover.hip) are this
-// emit over their sources; the six plan kernels are the three levels below over their items.
+// emit over their sources; the six plan kernels are the three levels below over their items.  And the separators of a batch call,
+// which both merge into a piece's list: their descriptor, the two searches of the rank merge, the host's range of them.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -86,6 +87,51 @@ __device__ __forceinline__ void plan_positions(Item item, uint64_t n, const int6
         if (first + k < n) put(first + k, run);
         run += it[k];
     }
+}
+
+// THE SEPARATORS of a batch call, whose text is the haystacks' concatenation with a separator element behind each (cat_off[i] =
+// the first element of haystack i in it; a byte batch: the phantoms, voff).  A piece merges those in a range of the text with its
+// own list -- replace: records, the separator a match that is deleted (k_replace_merge); cover: final spans, the separator an item
+// that emits nothing (k_cover_batch_merge) -- by rank: both lists ascend and cannot tie, so an element's place is its index plus
+// the elements of the other list in front of it, one binary search per element.
+// Separator j of a piece is separator i0 + j of the text and stands at text position cat_off[i0 + j + 1] - 1; `base` = the text
+// position of element 0 of the buffer the piece's list is relative to.
+struct BatchSeps {
+    const uint32_t *cat_off = nullptr;
+    uint32_t i0 = 0, n_sep = 0;
+    int64_t base = 0;
+};
+
+__device__ __forceinline__ int64_t sep_at(const BatchSeps &S, uint32_t j) { return (int64_t)S.cat_off[S.i0 + j + 1] - 1 - S.base; } // buffer relative
+
+// the first n separators of S that stand in front of buffer position x
+__device__ __forceinline__ uint32_t seps_before(const BatchSeps &S, uint32_t n, int64_t x) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (sep_at(S, mid) < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// the first n elements of a list of ascending starts -- start(i) -- that start in front of p
+template <class Start>
+__device__ __forceinline__ uint64_t starts_before(Start start, uint64_t n, int64_t p) {
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if ((int64_t)start(mid) < p) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// on the host: separator i stands at h_cat_off[i + 1] - 1, and the separators in the text's [lo, hi) are [*i0, *i1)
+inline void separators_in(const uint32_t *h_cat_off, uint32_t n_hay, uint64_t lo, uint64_t hi, uint32_t *i0, uint32_t *i1) {
+    const uint32_t *sep_end = h_cat_off + 1; // at or behind x <=> sep_end[i] > x
+    *i0 = (uint32_t)(std::upper_bound(sep_end, sep_end + n_hay, lo) - sep_end);
+    *i1 = std::max(*i0, (uint32_t)(std::upper_bound(sep_end, sep_end + n_hay, hi) - sep_end));
 }
 
 // The 16 consecutive bytes from p -- 8 units at any 2-byte alignment, or 16 bytes at any address -- as one 16-byte value: the two

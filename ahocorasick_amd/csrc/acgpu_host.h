@@ -563,6 +563,41 @@ struct BatchPlan {
 };
 int check_batch(const HostTables &t, const uint16_t *units, const uint64_t *offsets, uint32_t n_haystacks, BatchPlan *plan);
 
+// The front of the UTF-8 batch entries of spans, cover and replace, behind their checks, preset outputs and PoolCall; P =
+// Utf8StrictBatch or Utf8LossyBatch.  The stream rule (idle: the NULL stream), then the whole batch is staged -- validated
+// whichever way it is scanned (plan.per_haystack: validated only), so that what is refused does not depend on the route -- and
+// *ust says what was decoded.  ACGPU_OK: go on.  Any other code is the entry's to return as it is: ACGPU_E_ENCODING (and the stream
+// rule's ACGPU_E_INVALID) with the stream idle and the pool as usable as before the call; the rest behind call.fail.
+// (The summary, count-batch and match entries could follow; what they write on an encoding error differs in ways that tests pin.)
+template <class P>
+int utf8_batch_front(const PoolCall &call, const HostTables &t, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks, const BatchPlan &plan,
+                     Utf8Batch *b, typename P::Stats *ust) {
+    int rc = call.idle();
+    if (rc) return rc;
+    rc = stage_utf8_batch(*call.d, t, bytes, offsets, n_haystacks, call.d->call_stream, b, plan.per_haystack, P::errors);
+    if (rc && rc != ACGPU_E_ENCODING) return call.fail(rc);
+    if (ust) *ust = P::stats(b, rc);
+    return rc;
+}
+
+// ... and the route haystack by haystack of those entries: every non-empty haystack staged as a text of its own on `stream`
+// (never ill-formed: the front has validated it) and handed to text(i, staged); after(i) behind every haystack, the empty ones too.
+// Whether the stream is waited for before the next haystack is staged over this one is text's business.
+template <class P, class Text, class After>
+int utf8_each_haystack(DeviceState &d, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks, hipStream_t stream, Text text, After after) {
+    for (uint32_t i = 0; i < n_haystacks; i++) {
+        const uint64_t len = offsets[i + 1] - offsets[i];
+        if (len) {
+            Utf8Text staged;
+            int rc = stage_utf8_text(d, bytes + offsets[i], len, stream, &staged, P::errors);
+            if (rc) return rc == ACGPU_E_ENCODING ? ACGPU_E_HIP : rc;
+            if ((rc = text(i, staged))) return rc;
+        }
+        after(i);
+    }
+    return ACGPU_OK;
+}
+
 // The haystacks of a batch call staged as ONE text, for as long as the call scans it: the text and its offsets in d.batch_pin
 // (h_off[i] = the first unit of haystack i, separator i stands at h_off[i + 1] - 1; n_haystacks + 1 words), the offsets in
 // d.batch_off as well, and d.start_behind set to the separator.  The caller holds d.mu.

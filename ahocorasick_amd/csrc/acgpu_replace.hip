@@ -14,7 +14,8 @@
 // acgpu_replace_batch_u16 rewrites many short texts as ONE such text: the haystacks with a separator unit behind each (the batch
 // match call's concatenation), where a separator is a match that is deleted.  Behind every piece k_replace_merge merges the piece's
 // records with the pseudo-records of its separators; plan and emit run over the merged list as they are, so the results come out
-// back to back, and k_replace_batch_offsets reads every result's first output unit off the plan.
+// back to back, and k_replace_batch_offsets reads every result's first output unit off the plan.  The separators' descriptor, the
+// two searches of the merge and the host's range of them (separators_in) are acgpu_emit.h's, shared with the cover entries.
 //
 // acgpu_replace_utf8 rewrites a UTF-8 text in BYTES: the text is staged by stage_utf8_text (acgpu_utf8.hip) and scanned in UTF-16
 // units as a device shard; behind every piece its records become byte offsets (utf8_map_records) and its boundary a byte position
@@ -26,6 +27,8 @@
 // (utf8_map_records with the batch) and its boundary a byte of it (utf8_map_position with the batch).  The span itself has NO separators, so nothing
 // is merged and nothing deleted: plan and emit run over the records alone, and the results lie back to back because the
 // haystacks do.  Where each result begins is computed behind the plan by k_replace_span_offsets, a lane per haystack boundary.
+// Its front (staging, stats, what an encoding error leaves) and its route haystack by haystack are utf8_batch_front and
+// utf8_each_haystack of acgpu_host.h, shared with the spans and cover entries.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -143,44 +146,21 @@ __global__ __launch_bounds__(kEmitBlock) void k_replace_emit(EmitArgs<T> A) {
     emit_block(A);
 }
 
-// The separators a piece of a batch call merges: separator j of them stands at text position cat_off[i0 + j + 1] - 1 (cat_off[i] =
-// the first unit of haystack i in the concatenation), `base` = the text position of the records' buffer's unit 0.
-struct BatchSeps {
-    const uint32_t *cat_off = nullptr;
-    uint32_t i0 = 0, n_sep = 0;
-    int64_t base = 0;
-    int32_t id = 0; // the keyword id of a separator's pseudo-record: the empty slot behind the replacement table
-};
-
 constexpr int kMergeBlock = 256;
 
-__device__ __forceinline__ int64_t sep_at(const BatchSeps &S, uint32_t j) { return (int64_t)S.cat_off[S.i0 + j + 1] - 1 - S.base; } // buffer relative
-
-// the records (ascending starts) that start in front of buffer position p
+// a piece's records: three words each, ascending starts
 __device__ __forceinline__ uint64_t records_before(const int32_t *__restrict__ recs, uint64_t cnt, int64_t p) {
-    uint64_t lo = 0, hi = cnt;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if ((int64_t)recs[3 * mid] < p) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
+    return starts_before([=](uint64_t i) { return recs[3 * i]; }, cnt, p);
 }
 
-// A piece's cnt records and the pseudo-records {p, p + 1, S.id} of its separators, as one list in position order.  Both lists
-// ascend and cannot tie -- a record neither contains nor starts at a separator -- so an element's place is its index plus the
-// elements of the other list in front of it: a rank merge, one binary search per element.
-__global__ __launch_bounds__(kMergeBlock) void k_replace_merge(const int32_t *__restrict__ recs, uint64_t cnt, BatchSeps S, int32_t *__restrict__ merged) {
+// A batch call's piece (THE SEPARATORS, acgpu_emit.h): its cnt records and the pseudo-records {p, p + 1, id} of its separators as
+// one list in position order -- a record neither contains nor starts at a separator.  id: the keyword id of a pseudo-record, the
+// empty slot behind the replacement table.
+__global__ __launch_bounds__(kMergeBlock) void k_replace_merge(const int32_t *__restrict__ recs, uint64_t cnt, BatchSeps S, int32_t id, int32_t *__restrict__ merged) {
     const uint64_t t = (uint64_t)blockIdx.x * kMergeBlock + threadIdx.x;
     if (t < cnt) {
         const int32_t s = recs[3 * t];
-        uint32_t lo = 0, hi = S.n_sep; // the separators in front of s
-        while (lo < hi) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (sep_at(S, mid) < (int64_t)s) lo = mid + 1;
-            else hi = mid;
-        }
-        int32_t *o = merged + 3 * (t + lo);
+        int32_t *o = merged + 3 * (t + seps_before(S, S.n_sep, s));
         o[0] = s;
         o[1] = recs[3 * t + 1];
         o[2] = recs[3 * t + 2];
@@ -189,7 +169,7 @@ __global__ __launch_bounds__(kMergeBlock) void k_replace_merge(const int32_t *__
         int32_t *o = merged + 3 * (t - cnt + records_before(recs, cnt, p));
         o[0] = (int32_t)p;
         o[1] = (int32_t)p + 1;
-        o[2] = S.id;
+        o[2] = id;
     }
 }
 
@@ -244,6 +224,7 @@ struct ReplaceCall {
     const uint32_t *h_cat_off = nullptr;
     uint32_t n_hay = 0;
     BatchSeps seps{};
+    int32_t sep_id = 0; // the keyword id of a separator's pseudo-record
     uint64_t *d_out_off = nullptr;
 };
 
@@ -359,18 +340,16 @@ int launch_emit_as(ReplaceCall &c, const void *hay, const int32_t *recs, uint64_
 // A batch call's piece: its cnt records (d.count_res) merged with the separators in [done, own_hi) into d.replace_merged.  Which
 // separators those are the host knows from its copy of the offsets, so the plan still gets its n by value.
 int merge_separators(ReplaceCall &c, uint64_t base, uint64_t own_hi, const int32_t **recs, uint64_t *cnt) {
-    const uint32_t *sep_end = c.h_cat_off + 1; // separator i stands at sep_end[i] - 1: at or behind x <=> sep_end[i] > x
-    const uint32_t i0 = (uint32_t)(std::upper_bound(sep_end, sep_end + c.n_hay, c.done) - sep_end);
-    const uint32_t i1 = (uint32_t)(std::upper_bound(sep_end, sep_end + c.n_hay, own_hi) - sep_end);
-    c.seps.i0 = i0;
-    c.seps.n_sep = i1 > i0 ? i1 - i0 : 0;
+    uint32_t i1;
+    separators_in(c.h_cat_off, c.n_hay, c.done, own_hi, &c.seps.i0, &i1);
+    c.seps.n_sep = i1 - c.seps.i0;
     c.seps.base = (int64_t)base;
     if (!c.seps.n_sep) return ACGPU_OK;
     const uint64_t n = *cnt + c.seps.n_sep;
     const int rc = c.d.replace_merged.ensure(n * ACGPU_REC_MAP);
     if (rc) return rc;
     hipLaunchKernelGGL(k_replace_merge, dim3((unsigned)((n + kMergeBlock - 1) / kMergeBlock)), dim3(kMergeBlock), 0, c.stream, *recs, *cnt, c.seps,
-                       reinterpret_cast<int32_t *>(c.d.replace_merged.p));
+                       c.sep_id, reinterpret_cast<int32_t *>(c.d.replace_merged.p));
     HIP_TRY(hipGetLastError());
     *recs = reinterpret_cast<const int32_t *>(c.d.replace_merged.p);
     *cnt = n;
@@ -667,13 +646,8 @@ int replace_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, const ui
     PoolCall call(a); // (no device: fails here, and out is untouched)
     if (call.rc) return call.rc;
     DeviceState &d = *call.d;
-    if ((rc = call.idle())) return rc; // (the NULL stream: see the stream rule)
-    // the whole batch is validated first, whichever way it is scanned, so that what is refused does not depend on the route
     Utf8Batch b;
-    rc = stage_utf8_batch(d, t, bytes, offsets, n_haystacks, d.call_stream, &b, plan.per_haystack, P::errors);
-    if (rc && rc != ACGPU_E_ENCODING) return call.fail(rc);
-    if (ust) *ust = P::stats(&b, rc);
-    if (rc) return rc; // (ACGPU_E_ENCODING.  The stream is idle: the pool is as usable as before the call; out_offsets[1..] untouched)
+    if ((rc = utf8_batch_front<P>(call, t, bytes, offsets, n_haystacks, plan, &b, ust))) return rc; // (ACGPU_E_ENCODING: out_offsets[1..] untouched)
     ReplaceCall c{a, d, d.call_stream};
     c.esz = 1;
     c.h_out = out;
@@ -681,19 +655,18 @@ int replace_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, const ui
     if ((rc = upload_table(c, repl_bytes, repl_off, n_repl))) return call.fail(rc);
     const bool whole = shard_rule(t, ACGPU_REC_MAP, false).sequential; // (a device shard: as acgpu_replace_utf8 drives its pieces)
     if (plan.per_haystack) { // every haystack by the route acgpu_replace_utf8 takes, the results back to back
-        for (uint32_t i = 0; i < n_haystacks; i++) {
-            const uint64_t len = offsets[i + 1] - offsets[i];
-            if (len) {
-                Utf8Text text;
-                if ((rc = stage_utf8_text(d, bytes + offsets[i], len, c.stream, &text, P::errors))) return call.fail(rc == ACGPU_E_ENCODING ? ACGPU_E_HIP : rc); // (never ill-formed: validated)
+        rc = utf8_each_haystack<P>(
+            d, bytes, offsets, n_haystacks, c.stream,
+            [&](uint32_t i, const Utf8Text &text) {
                 c.u8 = &text;
-                c.n = len;
+                c.n = offsets[i + 1] - offsets[i];
                 c.done = 0;
-                if ((rc = replace_pieces(c, 0, whole, PieceScan{a, d, nullptr, 0, &text.shard, c.stream}, 0, text.shard.n_units))) return call.fail(rc);
-                if (hipStreamSynchronize(c.stream) != hipSuccess) return call.fail(ACGPU_E_HIP); // (the next haystack is staged over this one)
-            }
-            out_offsets[i + 1] = c.out_pos;
-        }
+                const int prc = replace_pieces(c, 0, whole, PieceScan{a, d, nullptr, 0, &text.shard, c.stream}, 0, text.shard.n_units);
+                if (prc) return prc;
+                return hipStreamSynchronize(c.stream) != hipSuccess ? (int)ACGPU_E_HIP : (int)ACGPU_OK; // (the next haystack is staged over this one)
+            },
+            [&](uint32_t i) { out_offsets[i + 1] = c.out_pos; });
+        if (rc) return call.fail(rc);
         return replace_result(c, n_out, st);
     }
     if ((rc = d.replace_off.ensure(((size_t)n_haystacks + 1) * 8))) return call.fail(rc);
@@ -778,7 +751,7 @@ int acgpu_replace_batch_u16(const acgpu_automaton *ca, const uint16_t *units, co
     c.h_cat_off = text.h_off;
     c.n_hay = n_haystacks;
     c.seps.cat_off = text.d_off();
-    c.seps.id = (int32_t)a->n_given;
+    c.sep_id = (int32_t)a->n_given;
     c.d_out_off = reinterpret_cast<uint64_t *>(d.replace_off.p);
     if ((rc = upload_table(c, repl_units, repl_off, n_repl, /*full=*/true))) return rc;
     rc = replace_pieces(c, 0, host_one_piece(t, ACGPU_REC_MAP), PieceScan{a, d, text.h_cat, text.cat, nullptr, c.stream}, 0, text.cat);

@@ -54,7 +54,8 @@
 // have none, and the records of a lone-surrogate keyword may touch in bytes only -- so the merge runs over VIRTUAL COORDINATES,
 // v = byte of the buffer + index of the haystack: the bytes with one phantom element behind every haystack, which no record
 // covers.  A piece's records become v where they lie (utf8_vmap_records), `bound` becomes a v (utf8_vmap_position), and with
-// voff in the place of cat_off merge, carry and k_span_tag run as for a UTF-16 batch.
+// voff in the place of cat_off merge, carry and k_span_tag run as for a UTF-16 batch.  The entry's front and its
+// route haystack by haystack are utf8_batch_front and utf8_each_haystack (acgpu_host.h), shared with the cover and replace entries.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -545,30 +546,25 @@ int spans_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, const uint
     PoolCall call(a); // (no device: fails here, and out is untouched)
     if (call.rc) return call.rc;
     DeviceState &d = *call.d;
-    if ((rc = call.idle())) return rc; // (the NULL stream: see the stream rule)
-    // the whole batch is validated first, whichever way it is scanned, so that what is refused does not depend on the route
     Utf8Batch b;
-    rc = stage_utf8_batch(d, t, bytes, offsets, n_haystacks, d.call_stream, &b, plan.per_haystack, P::errors);
-    if (rc && rc != ACGPU_E_ENCODING) return call.fail(rc);
-    if (ust) *ust = P::stats(&b, rc);
-    if (rc) return rc; // (ACGPU_E_ENCODING.  The stream is idle: the pool is as usable as before the call)
+    if ((rc = utf8_batch_front<P>(call, t, bytes, offsets, n_haystacks, plan, &b, ust))) return rc;
     SpansCall c{a, d, d.call_stream};
     c.h_out = out;
     c.cap = cap;
     const bool whole = shard_rule(t, ACGPU_REC_SET, false).sequential; // (a device shard: as acgpu_spans_utf8 drives its pieces)
     if (plan.per_haystack) { // every haystack as a text of its own, by the route acgpu_spans_utf8 takes
         c.tag_all = true;
-        for (uint32_t i = 0; i < n_haystacks; i++) {
-            const uint64_t len = offsets[i + 1] - offsets[i];
-            if (!len) continue;
-            Utf8Text text; // (staged on the call's stream, behind the copies of the haystack before)
-            if ((rc = stage_utf8_text(d, bytes + offsets[i], len, c.stream, &text, P::errors))) return call.fail(rc == ACGPU_E_ENCODING ? ACGPU_E_HIP : rc); // (never ill-formed: validated)
-            c.u8 = &text;
-            c.tag = (int32_t)i;
-            rc = spans_pieces(c, 0, whole, PieceScan{a, d, nullptr, 0, &text.shard, c.stream}, text.shard.n_units);
-            c.u8 = nullptr;
-            if (rc) return call.fail(rc);
-        }
+        rc = utf8_each_haystack<P>(
+            d, bytes, offsets, n_haystacks, c.stream,
+            [&](uint32_t i, const Utf8Text &text) { // (staged on the call's stream, behind the copies of the haystack before: no wait)
+                c.u8 = &text;
+                c.tag = (int32_t)i;
+                const int prc = spans_pieces(c, 0, whole, PieceScan{a, d, nullptr, 0, &text.shard, c.stream}, text.shard.n_units);
+                c.u8 = nullptr;
+                return prc;
+            },
+            [](uint32_t) {});
+        if (rc) return call.fail(rc);
     } else {
         std::vector<uint32_t> h_voff;
         if ((rc = utf8_virtual_offsets(d, b, c.stream, &h_voff, &c.cat_off))) return call.fail(rc);

@@ -250,6 +250,24 @@ def test_one_span_carried_through_every_piece(p):
     check_both(a, hay, match(orc, hay), "<", ">", "drop")
 
 
+@pytest.mark.parametrize("body", ["drop", "keep"])
+def test_pieces_that_merge_intervals_and_finalise_none(body):
+    """Every piece but the last carries its one span: it merges m > 0 intervals and finalises none.  A DROP call that is no batch
+    then runs the plan with grids sized by m while the count it reads from the merge's head is 0 (k_cover_sums, k_cover_plan:
+    `first + k < n` false for every item; k_cover_plan_offsets: dropped = 0), and emits a piece without output."""
+    a, orc = pair(N.MODE_ALL, ["aa"])
+    hay = "a" * 600 + "b"
+    try:
+        N.set_tunable("cursor_first_piece", 64)
+        N.set_tunable("cursor_max_piece", 64)
+        want, st = check_both(a, hay, match(orc, hay), "[", "]", body)
+    finally:
+        for k, v in DEFAULTS:
+            N.set_tunable(k, v)
+    assert want.tobytes().decode("utf-16-le") == {"drop": "[]b", "keep": "[" + "a" * 600 + "]b"}[body]
+    assert st.pieces > 1 and st.n_spans == 1 and st.max_carry == 1, (st.pieces, st.n_spans, st.max_carry)
+
+
 # ---- 7. alignment -----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("body,open,close", USES)
 def test_device_output_at_every_unit_offset_of_a_vector(body, open, close):

@@ -1,5 +1,5 @@
 """GPU tests of the batch cover entry (include/acgpu.h: acgpu_cover_batch_u16; csrc/acgpu_cover.hip: k_cover_batch_head,
-k_cover_batch_merge, the plan over spans and separators, k_cover_batch_offsets, k_cover_batch_emit).  Every expected value is
+k_cover_batch_merge, the plan over spans and separators, k_cover_batch_offsets, k_cover_emit<.., true>).  Every expected value is
 tests/cover_batch_ref.py -- tests/cover_ref.cover_ref over tests/spans_ref.merge of the CPU oracle's records, haystack by haystack --
 never the code under test; as a second assertion only, a haystack's part of the result equals acgpu_cover_u16 on it alone.  Every
 call has a sentinel behind cap.  The cases are shared with tests/test_gpu_spans_batch.py."""

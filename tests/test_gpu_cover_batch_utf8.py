@@ -1,5 +1,5 @@
 """GPU tests of acgpu_cover_batch_utf8 / acgpu_cover_batch_utf8_lossy (include/acgpu.h; csrc/acgpu_cover.hip: the batch plan over
-virtual coordinates, k_cover_batch_emit<uint8_t, BODY>; csrc/acgpu_utf8.hip: k_utf8_batch_vmap, k_utf8_batch_vpos, k_utf8_batch_voff).
+virtual coordinates, k_cover_emit<uint8_t, BODY, true>; csrc/acgpu_utf8.hip: k_utf8_batch_vmap, k_utf8_batch_vpos, k_utf8_batch_voff).
 Every expected value is the reference of DESIGN.md 4.25's tests: for every haystack ON ITS OWN the CPU oracle's records on the
 decoded text (lossy: decoded with "replace"), mapped to bytes by tests/test_gpu_utf8.expected / tests/test_gpu_utf8_lossy.expected,
 then tests/spans_ref.merge and tests/cover_ref.cover_ref on the haystack's bytes, back to back -- never the code under test.  As a

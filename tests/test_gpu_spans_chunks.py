@@ -1,7 +1,7 @@
 """GPU tests of the spans merge (csrc/acgpu_spans.hip) and of the cover entries behind it (csrc/acgpu_cover.hip) where the SECOND
 level of their two-level scans does real work, and where the reservoir is full:
 
- * k_span_scan_mins, k_span_offsets and k_cover_offsets are ONE workgroup each over the tiles' values, N.SPAN_BLOCK = 256 of them
+ * k_span_scan_mins, k_span_offsets and k_cover_plan_offsets are ONE workgroup each over the tiles' values, N.SPAN_BLOCK = 256 of them
    per step with a running carry.  Up to 64 tiles only wave 0 of that workgroup holds a value; from 65 on block_suffix_min /
    block_prefix_sum / plan_block_scan combine waves; from 257 on -- N.SPAN_CHUNK + 1 = 524 289 intervals in one piece -- the step
    loop runs twice and its carry is read.
@@ -145,12 +145,13 @@ def test_random_dense_text_whose_first_merge_is_not_the_last():
     assert st.pieces - st.rescans == 2 and st.max_carry >= 1, (st.pieces, st.rescans, st.max_carry)
 
 
-@pytest.mark.parametrize("body,open,close", [("drop", "#", ""), ("keep", "(", ")")])
+@pytest.mark.parametrize("body,open,close", [("drop", "#", ""), ("drop", "##", ""), ("keep", "(", ")")])
 def test_cover_of_one_more_span_than_a_chunk(body, open, close):
-    """C + 1 spans of one unit in one piece.  DROP is the first to reach k_cover_offsets' `bsum[b] = carry + ex` with carry != 0
-    (plan block 256: pos[C] = C * (1 + len(open)) only with the 262 144 dropped units of the first step) and plan_block_scan's
-    `if (i < w) base += wsum[i]`; KEEP is pos_at()'s closed form `i * (ol + cl)` with i past 2^19.  A position too small sends the
-    emit's segment searches to the wrong span: the text is wrong from output unit pos[C] on."""
+    """C + 1 spans of one unit in one piece.  DROP reaches k_cover_plan_offsets' second step, `bsum[b] = carry + ex` for plan
+    block 256, and plan_block_scan's `if (i < w) base += wsum[i]`.  The plan sums what an item adds, len(open) minus the span's one
+    unit: nothing under "#", where pos[C] = 2 C must come out of sums that are all zero, and one unit per span under "##", where
+    pos[C] = 3 C only with the carry of the first step, 262 144.  KEEP is pos_at()'s closed form `i * (ol + cl)` with i past 2^19.
+    A position too small sends the emit's segment searches to the wrong span: the text is wrong from output unit pos[C] on."""
     one_large_piece()
     a, orc = S.pair(N.MODE_ALL, ["a"])
     count = C + 1
@@ -165,7 +166,7 @@ def test_cover_of_one_more_span_than_a_chunk(body, open, close):
 def test_cover_drop_of_the_random_dense_text():
     """The 63 564 spans of the 600 000-unit text under DROP: the plan's grid is sized by m = 654 008 intervals, 320 blocks of which
     all but 32 lie wholly beyond n = slot[0].  The first to reach k_cover_sums' and k_cover_plan's `first + k < n` false for whole
-    blocks, and k_cover_offsets' second step over sums that are all zero."""
+    blocks, and k_cover_plan_offsets' second step over sums that are all zero."""
     a, orc, hay, recs, spans_want = dense(600_000)
     assert (len(recs) + N.PLAN_TILE - 1) // N.PLAN_TILE > N.SPAN_BLOCK and (len(spans_want) + N.PLAN_TILE - 1) // N.PLAN_TILE < 64
     want, st = V.check_both(a, hay, recs, "***", "", "drop")
