@@ -159,7 +159,7 @@ _UTF8_STATS = set(_LOSSY_STATS) | set(_LOSSY_STATS.values())
 
 def _signatures():
     """The C ABI of include/acgpu.h, once: symbol -> (restype, argtypes); argtypes None: ctypes is told nothing about them.  The
-    eight _lossy entries are their strict twins with another stats struct (_LOSSY_STATS) and are derived, not written out."""
+    _lossy entries are their strict twins with another stats struct (_LOSSY_STATS) and are derived, not written out."""
     vp, u64, i64, u32, ci, P = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER
     sig = {
         "acgpu_build": (ci, [ci, vp, vp, u32, ci, vp, vp, P(vp), P(i64)]),
@@ -187,6 +187,8 @@ def _signatures():
         "acgpu_stream_feed_utf8": (ci, [vp, vp, u64, ci, ci, vp, u64, P(u64), P(i64), P(Utf8StreamStats)]),
         "acgpu_stream_replace_u16": (ci, [vp, vp, u64, ci, vp, vp, u32, vp, u64, P(u64), P(ReplaceStats)]),
         "acgpu_stream_replace_utf8": (ci, [vp, vp, u64, ci, vp, vp, u32, vp, u64, P(u64), P(Utf8StreamStats), P(ReplaceStats)]),
+        "acgpu_stream_cover_u16": (ci, [vp, vp, u64, ci, P(CoverSpec), vp, u64, P(u64), P(CoverStats)]),
+        "acgpu_stream_cover_utf8": (ci, [vp, vp, u64, ci, P(CoverSpec), vp, u64, P(u64), P(Utf8StreamStats), P(CoverStats)]),
         "acgpu_stream_close": (None, [vp]),
         "acgpu_stream_set_pipelined": (ci, [vp, ci]),
         "acgpu_stream_reserve": (ci, [vp, u64, P(vp)]),

@@ -1,5 +1,6 @@
 """Mask, highlight or redact every covered run of a text on the device (include/acgpu.h: acgpu_cover_u16, acgpu_cover_batch_u16, acgpu_cover_device,
-acgpu_cover_utf8, acgpu_cover_utf8_lossy, acgpu_cover_batch_utf8, acgpu_cover_batch_utf8_lossy): every span of the text -- the spans of ahocorasick_amd.spans, for all five families,
+acgpu_cover_utf8, acgpu_cover_utf8_lossy, acgpu_cover_batch_utf8, acgpu_cover_batch_utf8_lossy, acgpu_stream_cover_u16, acgpu_stream_cover_utf8,
+acgpu_stream_cover_utf8_lossy): every span of the text -- the spans of ahocorasick_amd.spans, for all five families,
 AhoCorasick's overlapping records included -- becomes open + body + close, everything else is copied.
 
     mask(AhoCorasickSet(names, False), text)                    # "call **** or ***" -- the length is preserved
@@ -7,6 +8,8 @@ AhoCorasick's overlapping records included -- becomes open + body + close, every
     redact(AhoCorasickSet(names, False), text, "[name]")
     mask_batch(AhoCorasickSet(names, False), lines)             # many short texts: ONE device call, a list of str
     mask_batch_utf8(AhoCorasickSet(names, False), log, offsets=utf8_line_offsets(log))  # ... of bytes, the buffer used in place
+    for piece in mask_utf8_readable(AhoCorasickSet(names, False), open("app.log", "rb")):  # a text of any length, chunk by chunk
+        sink.write(piece)
 
 Not replace: overlapping, nested and TOUCHING matches are one span, so two matches that touch give ONE replacement, not two.
 No span and no record reaches the host.
@@ -17,11 +20,14 @@ import numpy as np
 
 from . import _native as N
 from .spans import _automaton
-from .strings import _fill_shard, _not_none, _pack, _pack_utf8, _raise_for, _readable, _stats_dict, _to_str, _utf8_bytes, _utf8_entry, _vp, utf16
+from .strings import (_byte_chunks, _check_errors, _chunks, _fill_shard, _not_none, _pack, _pack_utf8, _raise_for, _readable, _retry_while_more,
+                      _rewrite_call, _stats_dict, _to_str, _utf8_bytes, _utf8_entry, _vp, utf16)
 
 __all__ = ["cover", "cover_utf8", "cover_device", "mask", "mask_utf8", "highlight", "highlight_utf8", "redact", "redact_utf8",
            "cover_batch", "cover_batch_units", "mask_batch", "highlight_batch", "redact_batch",
-           "cover_batch_utf8", "cover_batch_bytes", "mask_batch_utf8", "highlight_batch_utf8", "redact_batch_utf8"]
+           "cover_batch_utf8", "cover_batch_bytes", "mask_batch_utf8", "highlight_batch_utf8", "redact_batch_utf8",
+           "CoverStream", "cover_readable", "cover_utf8_readable", "mask_readable", "mask_utf8_readable", "highlight_readable",
+           "highlight_utf8_readable", "redact_readable", "redact_utf8_readable"]
 
 BODIES = {"keep": 0, "fill": 1, "drop": 2}  # ACGPU_COVER_KEEP, _FILL, _DROP
 
@@ -219,3 +225,135 @@ def redact(matcher, haystack, replacement):
 
 def redact_utf8(matcher, data, replacement, errors="strict"):
     return cover_utf8(matcher, data, open=replacement, body="drop", errors=errors)
+
+
+class CoverStream:
+    """acgpu_stream_cover_u16 / _utf8 / _utf8_lossy: cover for a text that arrives in chunks of any size -- a log of 40 GB, a socket.
+    The concatenation of what the feeds return is cover (cover_utf8) of everything fed, whatever the chunking; a feed returns what
+    no later chunk can change, and withholds at most a keyword's length however long a span is: a span that is still open at a
+    feed's end gets its open and the body so far now, and its close from the feed that sees it end.  open, close, fill: str, or for
+    a stream of bytes bytes-like as well (cover_utf8's rules).  A stream is fed either units (feed) or bytes (feed_utf8)."""
+
+    def __init__(self, matcher, open="", close="", body="keep", fill="*"):
+        self._auto = _automaton(matcher)  # keeps the handle alive
+        self._args = (_not_none(open), _not_none(close), _body(body), _not_none(fill))
+        self._spec = {}  # per element size: (N.CoverSpec, the arrays it points into)
+        self._errors = None
+        h = ctypes.c_void_p()
+        N.check(N.lib().acgpu_stream_open(self._auto.handle, ctypes.byref(h)), "acgpu_stream_open")
+        self._h = h
+
+    def _spec_for(self, esz):
+        if esz not in self._spec:
+            o, c, body, fill = self._args
+            if esz == 2:
+                self._spec[esz] = _spec(_units("open", o), _units("close", c), body, _fill_unit(fill))
+            else:
+                self._spec[esz] = _spec(_bytes("open", o), _bytes("close", c), body, _fill_byte(fill))
+        return self._spec[esz][0]
+
+    def _feed(self, entry, src, final, cap, stats):
+        """the rewrite call, made again while it asks for more room (an overflow committed nothing) -> an array of src's type"""
+        if self._h is None:
+            raise ValueError("the stream is closed")
+        spec = self._spec_for(src.dtype.itemsize)
+        n = int(src.size)
+        if cap is None:
+            cap = n + n // 4 + 64 + int(spec.open_len) + int(spec.close_len)
+        return _rewrite_call(entry, (self._h, _vp(_readable(src)), n, 1 if final else 0, ctypes.byref(spec)), src.dtype, n, cap, stats,
+                             _retry_while_more)
+
+    def feed(self, units, final=False, cap=None, stats=None):
+        """the next units (str or uint16 array) -> the units of the result that have become decidable, a uint16 array.
+        stats: an N.CoverStats to fill in, if wanted (this feed alone; n_spans: the spans whose open it delivered)."""
+        return self._feed(N.lib().acgpu_stream_cover_u16, utf16(_not_none(units)), final, cap, [stats if stats is not None else N.CoverStats()])
+
+    def feed_utf8(self, data, final=False, errors="strict", stats=None, cap=None, cover_stats=None):
+        """the next bytes of a UTF-8 text (a chunk may end inside a sequence) -> the bytes of the result that have become decidable.
+        Ill-formed input raises Utf8Error (.start: the GLOBAL offset) and finishes the stream; what had been withheld is not
+        delivered -- unless errors="replace": nothing is raised, and the concatenation is cover_utf8(errors="replace") of everything
+        fed.  The first feed fixes the stream's policy.  stats: an N.Utf8StreamStats (errors="replace": N.Utf8LossyStreamStats),
+        cover_stats: an N.CoverStats to fill in, if wanted."""
+        entry, stats_type = _utf8_entry("acgpu_stream_cover_utf8", errors)
+        if self._errors is None:
+            self._errors = errors
+        elif self._errors != errors:
+            raise ValueError("errors=%r on a stream that is fed with errors=%r" % (errors, self._errors))
+        return self._feed(entry, _utf8_bytes(_not_none(data)), final, cap,
+                          [stats if stats is not None else stats_type(), cover_stats if cover_stats is not None else N.CoverStats()]).tobytes()
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            N.lib().acgpu_stream_close(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    __del__ = close
+
+
+def cover_readable(matcher, readable, open="", close="", body="keep", fill="*", chunk_chars=1 << 22):
+    """cover for a text that is read as it goes -- an object with read(n) -> str, or an iterable of str / uint16 arrays, cut
+    anywhere, inside a keyword or a span too -> a generator of str whose concatenation is cover() of the whole text.  A piece never
+    ends between the two units of a surrogate pair: a trailing high surrogate waits for the next piece.  Closing the generator
+    closes the stream; the stream is opened at the first next()."""
+    st = CoverStream(matcher, open, close, body, fill)
+    held = np.zeros(0, np.uint16)
+    try:
+        for final, chunk in _with_final(_chunks(readable, chunk_chars), ""):
+            out = np.concatenate([held, st.feed(chunk, final=final)])
+            cut = out.size - 1 if not final and out.size and 0xD800 <= int(out[-1]) < 0xDC00 else out.size
+            held = out[cut:]
+            yield _to_str(out[:cut])
+    finally:
+        st.close()
+
+
+def cover_utf8_readable(matcher, readable, open=b"", close=b"", body="keep", fill=b"*", chunk_bytes=1 << 22, errors="strict"):
+    """cover_utf8 for a text that is read as it goes -- a binary file object or an iterable of bytes-like chunks, cut anywhere,
+    inside a sequence too -> a generator of bytes whose concatenation is cover_utf8() of the whole text.  Utf8Error (.start: the
+    global offset) if the text is ill-formed -- unless errors="replace".  Closing the generator closes the stream."""
+    _check_errors(errors)
+    st = CoverStream(matcher, open, close, body, fill)
+    try:
+        for final, chunk in _with_final(_byte_chunks(readable, chunk_bytes), b""):
+            yield st.feed_utf8(chunk, final=final, errors=errors)
+    finally:
+        st.close()
+
+
+def _with_final(chunks, empty):
+    """(False, chunk) for every chunk, then (True, empty): the feed that ends the text"""
+    for chunk in chunks:
+        yield False, chunk
+    yield True, empty
+
+
+def mask_readable(matcher, readable, fill="*", chunk_chars=1 << 22):
+    return cover_readable(matcher, readable, body="fill", fill=fill, chunk_chars=chunk_chars)
+
+
+def mask_utf8_readable(matcher, readable, fill=b"*", chunk_bytes=1 << 22, errors="strict"):
+    """mask_utf8 of a file of any length, bytes in, bytes out: every piece has its chunk's byte offsets, shifted by what is withheld"""
+    return cover_utf8_readable(matcher, readable, body="fill", fill=fill, chunk_bytes=chunk_bytes, errors=errors)
+
+
+def highlight_readable(matcher, readable, open, close, chunk_chars=1 << 22):
+    return cover_readable(matcher, readable, open=open, close=close, body="keep", chunk_chars=chunk_chars)
+
+
+def highlight_utf8_readable(matcher, readable, open, close, chunk_bytes=1 << 22, errors="strict"):
+    return cover_utf8_readable(matcher, readable, open=open, close=close, body="keep", chunk_bytes=chunk_bytes, errors=errors)
+
+
+def redact_readable(matcher, readable, replacement, chunk_chars=1 << 22):
+    return cover_readable(matcher, readable, open=replacement, body="drop", chunk_chars=chunk_chars)
+
+
+def redact_utf8_readable(matcher, readable, replacement, chunk_bytes=1 << 22, errors="strict"):
+    return cover_utf8_readable(matcher, readable, open=replacement, body="drop", chunk_bytes=chunk_bytes, errors=errors)

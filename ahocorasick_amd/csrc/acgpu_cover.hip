@@ -37,6 +37,10 @@
 // batch call" below, and DESIGN.md 4.24).  acgpu_cover_batch_utf8 does the same for bytes over virtual coordinates, the caller's
 // bytes with a phantom element behind every haystack in the separator's place (cover_batch_utf8 below).
 //
+// acgpu_stream_cover_* (acgpu_stream.hip) cover a text that arrives in chunks: cover_feed below drives the same pieces over the owned
+// range of a feed's buffer, and there the text does NOT stay -- a feed may end inside a span, which the emit's source serves with
+// two kinds of item that no whole text has (A FEED below, CoverArgs::cut and ::head).
+//
 // One plan, one emit launch (launch_emit<T, BODY, BATCH>, twelve kernels) and one piece step (cover_piece) serve all of them; the
 // separators' descriptor and searches are acgpu_emit.h's, shared with the replace entries; the entries' bodies share
 // cover_staged_text (one staged text to its end), cover_batch_result and the UTF-8 batch front and loop of acgpu_host.h.
@@ -101,6 +105,14 @@ struct CoverArgs : CoverShift<BATCH && sizeof(T) == 1> {
     uint32_t ol, cl;
     uint32_t fill;
     int64_t done;        // output element 0 of the piece is text element `done` (if no span starts there)
+    // A FEED of a cover stream (cover_feed below; no batch call) has two kinds of item that a whole text has not:
+    //  * item 0 is HEADLESS iff spans[0].x < done -- a span that an earlier feed opened and cut at `done`: no open, and its body
+    //    begins at `done` (its true start, in front of the buffer if need be, is kept so that the item is never empty: where its
+    //    end equals `done` it is close alone).  head = ol then, else 0: what the closed form takes off every later position;
+    //  * the last item is TAILLESS iff its end is at or behind `cut`, where the feed's output ends: no close, the body ends at cut.
+    //    cut = INT64_MAX: no feed, or a piece that cuts nothing.
+    // Both are clipped here and nowhere else: text in front of `done` or behind `cut` is never read for a body.
+    int64_t cut, head;
     int64_t w0, w1;
     T *dst;
     int32_t cap;         // segments to stage at most (tunable "cover_lds_segments")
@@ -108,7 +120,7 @@ struct CoverArgs : CoverShift<BATCH && sizeof(T) == 1> {
     __device__ __forceinline__ int64_t n() const { return n_spans; }
     __device__ __forceinline__ int64_t pos_at(int64_t i) const {
         if (BODY == ACGPU_COVER_DROP || BATCH) return pos[i];
-        return (int64_t)spans[i].x - done + i * ((int64_t)ol + (int64_t)cl);
+        return std::max<int64_t>(spans[i].x, done) - done + i * ((int64_t)ol + (int64_t)cl) - (i ? head : 0);
     }
     __device__ __forceinline__ CSeg make_seg(int64_t i, int64_t t0) const {
         CSeg s;
@@ -125,6 +137,21 @@ struct CoverArgs : CoverShift<BATCH && sizeof(T) == 1> {
         // VIRT: the item's haystack.  A span's body and the text behind it are bytes v - h; the text behind haystack h's phantom p
         // begins at p + 1 in haystack h + 1, which is byte p - h.
         const uint32_t h = this->hay_of(sp.x);
+        if constexpr (!BATCH) { // (a feed's items: see `cut` above; for every other call s0 = sp.x, e0 = sp.y and both flags are false)
+            const bool headless = (int64_t)sp.x < done, tailless = (int64_t)sp.y >= cut;
+            const int64_t s0 = headless ? done : (int64_t)sp.x, e0 = tailless ? cut : (int64_t)sp.y;
+            const int64_t a = P + (headless ? 0 : (int64_t)ol), b = a + (BODY == ACGPU_COVER_DROP ? 0 : e0 - s0), c = b + (tailless ? 0 : (int64_t)cl);
+            auto in_tile = [](int64_t x) { return (int32_t)std::min<int64_t>(std::max<int64_t>(x, 0), kEmitTile<T>); };
+            s.rel = (int32_t)std::max<int64_t>(P, -1);
+            s.a_end = in_tile(a);
+            s.b_end = in_tile(b);
+            s.c_end = in_tile(c);
+            s.osrc = (uint32_t)0 - (uint32_t)P;
+            s.bsrc = (uint32_t)s0 - (uint32_t)a;
+            s.csrc = (uint32_t)0 - (uint32_t)b;
+            s.tsrc = (uint32_t)e0 - (uint32_t)c;
+            return s;
+        }
         const int64_t a = P + (sep ? 0 : (int64_t)ol), b = a + (BODY == ACGPU_COVER_DROP ? 0 : (int64_t)(sp.y - sp.x)), c = b + (sep ? 0 : (int64_t)cl);
         auto in_tile = [](int64_t x) { return (int32_t)std::min<int64_t>(std::max<int64_t>(x, 0), kEmitTile<T>); };
         s.rel = (int32_t)std::max<int64_t>(P, -1);
@@ -182,30 +209,41 @@ constexpr int kPlanHead = 2; // words in front of the plan's sums: a batch call'
 __device__ __forceinline__ uint64_t plan_items(const uint64_t *n_final, const uint64_t *n_sep) { return n_final[0] + (n_sep ? n_sep[0] : 0); }
 
 // The plan's item: what item i adds to the output's length beyond the text it stands for -- -1 for a separator (the one item
-// without elements), else w = open + close minus, for DROP, the span's elements
-__device__ __forceinline__ int64_t item_delta(const int2 *items, uint64_t i, int64_t w, int drop) {
-    const int64_t len = (int64_t)(items[i].y - items[i].x);
-    return len == 0 ? -1 : w - (drop ? len : 0);
+// without elements), else w = open + close minus, for DROP, the span's elements.  A feed's HEADLESS item (CoverArgs: it starts in
+// front of `done`) has no open and only its elements from `done` on; no other call has an item in front of its `done`.
+__device__ __forceinline__ int64_t item_delta(const int2 *items, uint64_t i, int64_t w, int drop, int64_t done, int64_t ol) {
+    const int2 it = items[i];
+    if (it.y == it.x) return -1;
+    const bool headless = (int64_t)it.x < done;
+    return w - (headless ? ol : 0) - (drop ? (int64_t)it.y - (headless ? done : (int64_t)it.x) : 0);
 }
 
 __global__ __launch_bounds__(kPlanBlock) void k_cover_sums(const int2 *__restrict__ items, const uint64_t *__restrict__ n_final, const uint64_t *__restrict__ n_sep,
-                                                           int64_t w, int drop, int64_t *__restrict__ bsum) {
-    plan_sums([=](uint64_t i) { return item_delta(items, i, w, drop); }, plan_items(n_final, n_sep), bsum);
+                                                           int64_t w, int drop, int64_t done, int64_t ol, int64_t *__restrict__ bsum) {
+    plan_sums([=](uint64_t i) { return item_delta(items, i, w, drop, done, ol); }, plan_items(n_final, n_sep), bsum);
 }
 
 // *dropped (the merge's slot[kSpanDropped], or nullptr) = the elements of the text in [done, L) that have no output of their own:
-// the separators, and a DROP call's covered elements -- n_final w minus the sum of the deltas
+// the separators, and a DROP call's covered elements -- n_final w minus the sum of the deltas (a feed with a headless item: plus
+// open's length, which the host takes off again)
 __global__ __launch_bounds__(kPlanBlock) void k_cover_plan_offsets(int64_t *__restrict__ bsum, uint32_t n_blocks, const uint64_t *__restrict__ n_final, int64_t w,
                                                                    uint64_t *__restrict__ dropped) {
     const int64_t sum = plan_offsets(bsum, n_blocks);
     if (threadIdx.x == 0 && dropped) *dropped = (uint64_t)((int64_t)n_final[0] * w - sum);
 }
 
-// pos[k] = (s_k - done) + the deltas in front of item k
+// pos[k] = (s_k - done) + the deltas in front of item k (a headless item: at 0)
 __global__ __launch_bounds__(kPlanBlock) void k_cover_plan(const int2 *__restrict__ items, const uint64_t *__restrict__ n_final, const uint64_t *__restrict__ n_sep,
-                                                           const int64_t *__restrict__ bsum, int64_t done, int64_t w, int drop, int64_t *__restrict__ pos) {
-    plan_positions([=](uint64_t i) { return item_delta(items, i, w, drop); }, plan_items(n_final, n_sep), bsum,
-                   [&](uint64_t k, int64_t front) { pos[k] = (int64_t)items[k].x - done + front; });
+                                                           const int64_t *__restrict__ bsum, int64_t done, int64_t w, int64_t ol, int drop, int64_t *__restrict__ pos) {
+    plan_positions([=](uint64_t i) { return item_delta(items, i, w, drop, done, ol); }, plan_items(n_final, n_sep), bsum,
+                   [&](uint64_t k, int64_t front) { pos[k] = std::max<int64_t>(items[k].x, done) - done + front; });
+}
+
+// A feed's TAILLESS item (CoverArgs), which the merge withheld and the feed's last piece emits all the same up to `cut`: item `at`
+// of the piece's list, behind its final spans, and for DROP its position behind their plan.  One thread.
+__global__ void k_cover_tail_item(int2 *__restrict__ items, int64_t *__restrict__ pos, uint64_t at, int2 span, int64_t p) {
+    items[at] = span;
+    if (pos) pos[at] = p;
 }
 
 // What one call holds while it runs (the caller holds d.mu).  Positions and lengths are ELEMENTS: units, or bytes of a UTF-8 text.
@@ -228,6 +266,11 @@ struct CoverCall {
     uint64_t *d_out_off = nullptr;
     uint64_t piece_items = 0;   // m + piece_max_sep: the items the plan has room for
     uint32_t piece_max_sep = 0; // the separators in [done, own_hi)
+    // a FEED of a cover stream (cover_feed): hay is the feed's buffer, and `done` may stand inside a span
+    bool feed = false;
+    bool in_span = false;       // element done - 1 is covered by a span that has not been closed: the list's first span is HEADLESS
+    uint64_t opens = 0;         // the spans whose open the feed has emitted
+    int64_t piece_cut = INT64_MAX, piece_head = 0; // CoverArgs::cut and ::head of the piece being emitted
 };
 
 // open and close on the device, each padded so that an aligned 16-byte load around any of their elements stays inside the blob
@@ -266,10 +309,10 @@ void launch_plan(CoverCall &c, const int2 *items, uint64_t M, const uint64_t *n_
     const hipStream_t stream = c.sc.stream;
     const int64_t w = (int64_t)c.ol + (int64_t)c.cl;
     const int drop = c.body == ACGPU_COVER_DROP;
-    hipLaunchKernelGGL(k_cover_sums, dim3(n_blocks), dim3(kPlanBlock), 0, stream, items, n_final, n_sep, w, drop, bsum);
+    hipLaunchKernelGGL(k_cover_sums, dim3(n_blocks), dim3(kPlanBlock), 0, stream, items, n_final, n_sep, w, drop, (int64_t)c.done, (int64_t)c.ol, bsum);
     hipLaunchKernelGGL(k_cover_plan_offsets, dim3(1), dim3(kPlanBlock), 0, stream, bsum, n_blocks, n_final, w, d_dropped);
-    hipLaunchKernelGGL(k_cover_plan, dim3(n_blocks), dim3(kPlanBlock), 0, stream, items, n_final, n_sep, (const int64_t *)bsum, (int64_t)c.done, w, drop,
-                       plan_pos(c.sc.d, M));
+    hipLaunchKernelGGL(k_cover_plan, dim3(n_blocks), dim3(kPlanBlock), 0, stream, items, n_final, n_sep, (const int64_t *)bsum, (int64_t)c.done, w, (int64_t)c.ol,
+                       drop, plan_pos(c.sc.d, M));
 }
 
 // SpansCall::planned of a DROP call that is no batch: the plan over the piece's final spans, whose number is the merge's slot[0],
@@ -411,6 +454,8 @@ int launch_emit(CoverCall &c, uint64_t n_items, uint64_t M, uint64_t w0, uint64_
     A.cl = c.cl;
     A.fill = c.fill;
     A.done = (int64_t)c.done;
+    A.cut = c.piece_cut;
+    A.head = c.piece_head;
     A.cap = (int32_t)std::min<int64_t>(std::max<int64_t>(tunables().cover_lds_segments.load(std::memory_order_relaxed), 0), kCoverLds);
     return launch_emit_kernel(k_cover_emit<T, BODY, BATCH>, A, w0, w1, dst, c.sc.stream);
 }
@@ -428,14 +473,68 @@ int launch_emit_for(CoverCall &c, uint64_t n_items, uint64_t M, uint64_t w0, uin
     return c.esz == 1 ? as(uint8_t{}, std::false_type{}) : as(uint16_t{}, std::false_type{});
 }
 
+// ---- A FEED of a cover stream (cover_feed; acgpu_stream_cover_*, acgpu_stream.hip).  The text is the feed's buffer [carry | chunk],
+// the pieces run over its owned range, and the stream cannot withhold a span that is still open at the feed's end -- the carry would
+// have to reach back to its start.  So the feed's last piece, unless it is the text's, settles at B itself, L = max(done, B), and
+// the first span it withheld is CUT there if it starts in front of L: it becomes the piece's last item, TAILLESS, emitted as open
+// ++ body up to L.  The span stays in the carry with its true start, so the next feed's merge sees it whole; `done` then stands
+// inside it (in_span), the merge's first span starts in front of `done`, and the piece that finalises it -- or cuts it again --
+// emits it HEADLESS: no second open, the body from `done` on.  A carried span whose end EQUALS done (nothing touched it after
+// all) is a headless item of close alone: never an empty one.  Inside a feed the pieces keep their L rule, min(B, first carried
+// start), clamped to `done` while `done` stands in that very span.  What the items cost the emit: CoverArgs::cut and ::head. ----
+
+// the emit of a feed's piece that merged m intervals and settles at L
+int cover_feed_piece(CoverCall &c, uint64_t m, uint64_t L, bool cutting) {
+    DeviceState &d = c.sc.d;
+    const uint64_t n_final = c.sc.piece_final;
+    const int2 first = c.sc.piece_carry0;
+    const bool tail = cutting && c.sc.piece_carried && (int64_t)first.x < (int64_t)L;
+    if (tail && (int64_t)first.y < (int64_t)L) return ACGPU_E_HIP; // (never: a withheld span ends at or behind B, and behind the `done` that cut it)
+    const uint64_t n_items = n_final + (tail ? 1 : 0);
+    const bool headless = c.in_span && n_items;
+    if (n_items > m) return ACGPU_E_HIP; // (never: m intervals merge to at most m spans)
+    const uint64_t opens = n_items - (headless ? 1 : 0), closes = n_final;
+    uint64_t dropped = 0;
+    if (c.body == ACGPU_COVER_DROP) {
+        const uint64_t raw = m ? c.sc.piece_dropped : 0; // the plan's: the final spans' elements from `done` on, plus open's length for a headless one
+        const uint64_t off = headless && n_final ? c.ol : 0;
+        if (raw < off) return ACGPU_E_HIP;
+        dropped = raw - off;
+        if (tail) dropped += L - (uint64_t)std::max<int64_t>(first.x, (int64_t)c.done);
+    }
+    if (dropped > L - c.done) return ACGPU_E_HIP; // (never: the items lie in [done, L))
+    const uint64_t total = (L - c.done) + opens * c.ol + closes * c.cl - dropped;
+    if (tail) { // behind the final spans: their deltas sum to n_final w - raw
+        int64_t *pos = c.body == ACGPU_COVER_DROP ? plan_pos(d, m) : nullptr;
+        const int64_t at = std::max<int64_t>(first.x, (int64_t)c.done) - (int64_t)c.done + (int64_t)(n_final * ((uint64_t)c.ol + c.cl)) - (int64_t)c.sc.piece_dropped;
+        hipLaunchKernelGGL(k_cover_tail_item, dim3(1), dim3(1), 0, c.sc.stream, reinterpret_cast<int2 *>(d.cover_spans.p), pos, n_final, first, at);
+        HIP_TRY(hipGetLastError());
+    }
+    c.piece_cut = tail ? (int64_t)L : INT64_MAX;
+    c.piece_head = headless ? (int64_t)c.ol : 0;
+    const int rc = emit_piece(d, c.sc.stream, c.esz, c.d_out, c.h_out, c.cap, c.out_pos, total,
+                              [&](uint64_t w0, uint64_t w1, void *dst) { return launch_emit_for(c, n_items, m, w0, w1, dst); });
+    if (rc) return rc;
+    c.done = L;
+    c.out_pos += total;
+    c.opens += opens;
+    if (n_items) c.in_span = tail;
+    return ACGPU_OK;
+}
+
 // SpansCall::merged: behind a piece's merge of m intervals, emit the text's elements [done, L) with the piece's final spans rewritten
 int cover_piece(void *ctx, uint64_t m, bool last) {
     CoverCall &c = *static_cast<CoverCall *>(ctx);
-    const uint64_t n_final = c.sc.piece_final, L = last ? c.n : std::min((uint64_t)std::max<int64_t>(c.sc.piece_settled, 0), c.n);
+    // (a feed's last piece that is not the text's settles at B itself and cuts the span that reaches it: A FEED below)
+    const bool cutting = c.feed && c.sc.piece_range_last;
+    const uint64_t n_final = c.sc.piece_final;
+    uint64_t L = last ? c.n : std::min((uint64_t)std::max<int64_t>(cutting ? c.sc.piece_below : c.sc.piece_settled, 0), c.n);
+    if (c.feed) L = std::max(L, c.done); // (the first carried span may be the one `done` stands in: nothing is settled then)
     if (L < c.done) return ACGPU_E_HIP; // (never: the settled position does not move backwards)
     uint64_t dropped = c.body == ACGPU_COVER_DROP ? c.sc.piece_dropped : 0;
     uint64_t n_items = n_final;
     int rc;
+    if (c.feed) return cover_feed_piece(c, m, L, cutting);
     if (c.h_cat_off) { // a batch call: the separators in [done, L) are items, and none of them has output
         uint32_t i0, i1;
         separators_in(c.h_cat_off, c.n_hay, c.done, L, &i0, &i1);
@@ -617,6 +716,87 @@ int cover_batch_utf8(const acgpu_automaton *ca, const uint8_t *bytes, const uint
 }
 
 } // namespace
+
+namespace acgpu {
+
+int cover_check_spec(const acgpu_cover_spec *spec, uint32_t esz) { return check_spec(spec, esz); }
+
+// One feed of a cover stream (A FEED above): the pieces of the buffer's owned range behind f->done, as a text's pieces are driven
+// -- the spec is uploaded per feed and the carried spans come from and go back to the host, so nothing of the stream stays on the
+// device between two feeds.
+int cover_feed(acgpu_automaton *a, DeviceState &d, CoverFeed *f, const acgpu_cover_spec *spec, void *out, uint64_t cap, uint64_t *n_out) {
+    CoverCall c{SpansCall{a, d, d.call_stream}};
+    c.esz = f->u8 ? 1 : 2;
+    c.sc.u8 = f->u8;
+    c.hay = f->u8 ? static_cast<const void *>(f->u8->d_bytes) : static_cast<const void *>(f->shard.d_hay);
+    c.n = f->u8 ? f->u8->n_bytes : f->shard.n_units;
+    c.h_out = static_cast<uint8_t *>(out);
+    c.cap = cap;
+    c.done = f->done;
+    c.feed = true;
+    c.in_span = f->in_span;
+    if (c.done > c.n) return ACGPU_E_HIP; // (never: the carry reaches back to `done`, the stream checks it)
+    int rc = upload_spec(c, *spec);
+    if (rc || (rc = emit_slabs_ready(d))) return rc;
+    // the carried spans, buffer relative.  A start far in front of the buffer is clamped: all that a span which began in an
+    // earlier feed is asked for is that it starts in front of `done`, and its end.
+    constexpr int64_t kFarFront = -(1ll << 30);
+    std::vector<int2> carry_in;
+    try {
+        carry_in.resize(f->carried.size() / 2);
+    } catch (...) {
+        return ACGPU_E_NOMEM;
+    }
+    for (size_t i = 0; i < carry_in.size(); ++i) {
+        const int64_t s = f->carried[2 * i] - (int64_t)f->origin, e = f->carried[2 * i + 1] - (int64_t)f->origin;
+        if (e < 0 || e > (int64_t)c.n || s >= e) return ACGPU_E_HIP; // (never: a carried span ends inside the carried text)
+        carry_in[i] = make_int2((int32_t)std::max(s, kFarFront), (int32_t)e);
+    }
+    const ShardRule rule = shard_rule(a->t, ACGPU_REC_SET, /*readable=*/true);
+    const int64_t entry = piece_entry(rule, f->chain, 0, f->shard.own_begin);
+    const int64_t idle_exit = piece_exit(rule, entry, f->shard.own_end, nullptr, 0); // (nothing owned: nothing scanned)
+    acgpu_shard sh = f->shard;
+    sh.chain_entry = entry;
+    SpansRange range;
+    range.own_begin = sh.own_begin;
+    range.own_end = sh.own_end;
+    range.text_end = f->final;
+    range.carry_in = carry_in.data();
+    range.n_carry_in = (uint32_t)carry_in.size();
+    SpansCall &sc = c.sc;
+    sc.to_pool = true;
+    sc.ctx = &c;
+    sc.merged = cover_piece;
+    sc.planned = c.body == ACGPU_COVER_DROP ? plan_dropped : nullptr;
+    rc = spans_pieces(sc, f->chain, rule.sequential, PieceScan{a, d, nullptr, 0, &sh, sc.stream, /*readable=*/true}, sh.n_units, &range);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(sc.stream));
+    std::vector<int64_t> carried;
+    try {
+        carried.reserve(range.carry_out.size() * 2);
+    } catch (...) {
+        return ACGPU_E_NOMEM;
+    }
+    for (const int2 &sp : range.carry_out) {
+        carried.push_back((int64_t)sp.x + (int64_t)f->origin);
+        carried.push_back((int64_t)sp.y + (int64_t)f->origin);
+    }
+    f->carried.swap(carried);
+    f->done = c.done;
+    f->in_span = c.in_span;
+    f->chain = range.scanned ? range.chain_exit : idle_exit;
+    f->st = acgpu_cover_stats{};
+    f->st.n_records = sc.st.n_records;
+    f->st.n_spans = c.opens;
+    f->st.units_out = c.out_pos;
+    f->st.pieces = sc.st.pieces;
+    f->st.rescans = sc.st.rescans;
+    f->st.max_carry = sc.st.max_carry;
+    *n_out = c.out_pos;
+    return c.out_pos > c.cap ? ACGPU_E_OVERFLOW : ACGPU_OK;
+}
+
+} // namespace acgpu
 
 extern "C" {
 

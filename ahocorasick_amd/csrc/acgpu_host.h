@@ -673,6 +673,27 @@ struct ReplaceFeed {
 int replace_feed(acgpu_automaton *a, DeviceState &d, ReplaceFeed *f, const void *repl, const uint64_t *repl_off, uint32_t n_repl, void *out,
                  uint64_t cap, uint64_t *n_out);
 
+// ---- a cover stream's feed (acgpu_cover.hip, for acgpu_stream.hip) ----
+// check_spec of the cover entries (esz: bytes of an element): ACGPU_E_INVALID for a bad spec; no device.
+int cover_check_spec(const acgpu_cover_spec *spec, uint32_t esz);
+// The buffer [carry | chunk] of one feed, on the device.  done counts ELEMENTS of the buffer -- units, or bytes of u8 -- and chain
+// units; the carried spans are GLOBAL, in elements since the first feed: `origin` is the global position of the buffer's element 0.
+struct CoverFeed {
+    acgpu_shard shard{};           // the buffer's units with the feed's owned range, text_begin and text_end set
+    const Utf8Text *u8 = nullptr;  // a stream of bytes: the staged buffer `shard` is the units of
+    bool final = false;            // the buffer's end is the text's end
+    uint64_t done = 0;             // in: output exists for the elements in front of it; out: the same behind this feed
+    bool in_span = false;          // in / out: element done - 1 is covered by a span whose close has not been delivered
+    uint64_t origin = 0;
+    std::vector<int64_t> carried;  // in / out: {start, end} of the spans the merge withheld, ascending (at most max_len / 2 + 2)
+    int64_t chain = 0;             // in: the chain's entry; out: its exit
+    acgpu_cover_stats st{};        // out: this feed alone
+};
+// Rewrites [f->done, new done) of the buffer into out (host, cap elements) through the pieces of the cover entries over the owned
+// range, scanned by the Readable rule.  ACGPU_E_OVERFLOW: *n_out and f->st are exact, nothing at or beyond out[cap] was written.
+// The caller holds d.mu, no ticket is in flight, and on an error it waits for the streams (PoolCall::fail).
+int cover_feed(acgpu_automaton *a, DeviceState &d, CoverFeed *f, const acgpu_cover_spec *spec, void *out, uint64_t cap, uint64_t *n_out);
+
 // collect() of a counting shard call that found n records: counts them (acgpu_count.hip).  ACGPU_E_OVERFLOW: they did not fit
 // the reservoir, nothing was counted.
 int count_collected(DeviceState &d, const CallRecord &r, uint64_t n);

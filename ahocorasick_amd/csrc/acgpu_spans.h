@@ -4,14 +4,31 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
 #include "acgpu_host.h"
 
 namespace acgpu {
 
 // 64-bit words in front of the tiles' values in d.spans_work: {n_final, n_carry, the piece's bound in bytes (UTF-8), and for a
-// cover call: the settled position L, the elements of the piece's final spans (written by the plan of a DROP call), unused}
-constexpr int kSpanHead = 6;
-constexpr int kSpanSettled = 3, kSpanDropped = 4;
+// cover call: the settled position L, the elements of the piece's final spans (written by the plan of a DROP call), and B itself
+// (final_below), which the last piece of a RANGE settles at, the first span the piece withheld as {start, end}}
+constexpr int kSpanHead = 7;
+constexpr int kSpanSettled = 3, kSpanDropped = 4, kSpanBelow = 5, kSpanCarry0 = 6;
+
+// A RANGE of a buffer instead of a whole text (a cover stream's feed, acgpu_stream.hip): the pieces run over the owned units
+// [own_begin, own_end) of the scan's shard, the first piece's list begins with the spans an earlier range withheld, whether the
+// range's end is the text's end comes from outside, and what the range's last piece withholds goes back to the host.  Spans are
+// in elements of the buffer; a carried span may begin in front of it (start < 0: only its end and "it began earlier" matter).
+struct SpansRange {
+    uint64_t own_begin = 0, own_end = 0;
+    bool text_end = true;           // the range's last piece finalises everything, as a whole text's
+    const int2 *carry_in = nullptr; // host
+    uint32_t n_carry_in = 0;
+    std::vector<int2> carry_out;    // out: the spans the range's last piece withheld
+    int64_t chain_exit = 0;         // out, if scanned: where the chain leaves the range
+    bool scanned = false;           // out: a piece was scanned
+};
 
 // What one call holds while it runs (the caller holds d.mu).  Positions are ELEMENTS of the text as the caller sees it: units, or
 // bytes of a UTF-8 text.
@@ -53,9 +70,16 @@ struct SpansCall {
     uint64_t piece_final = 0;     // out: the piece's final spans
     int64_t piece_settled = 0;    // out, not on the last piece: L = min(B, start of the first carried span)
     uint64_t piece_dropped = 0;   // out: slot[kSpanDropped] if `planned` is set
+    // a RANGE whose end is not the text's: the piece was the range's last, which nothing finalises but which SETTLES at
+    // piece_below = B itself -- a carried span may begin in front of it (the caller cuts it there)
+    bool piece_range_last = false; // in, for `merged`
+    int64_t piece_below = 0;      // out, with piece_range_last
+    int2 piece_carry0{0, 0};      // out, with piece_range_last: the first span the piece withheld, if piece_carried
+    uint32_t piece_carried = 0;   // out: the spans the piece withheld
 };
 
 // The pieces of a whole text, each merged behind its scan: chain = the chain's entry, whole = the text is scanned as one piece.
-int spans_pieces(SpansCall &c, int64_t chain, bool whole, const PieceScan &scan, uint64_t n_units);
+// range given: the pieces of that range of the scan's shard instead (SpansRange above).
+int spans_pieces(SpansCall &c, int64_t chain, bool whole, const PieceScan &scan, uint64_t n_units, SpansRange *range = nullptr);
 
 } // namespace acgpu

@@ -36,9 +36,15 @@
 //
 // A SECOND CALLER.  The cover entries (acgpu_cover.hip) run the same piece loop and merge through acgpu_spans.h (spans_pieces):
 // SpansCall::to_pool sends a piece's spans to d.cover_spans instead of the caller, k_span_settled adds the position up to which the
-// text is settled, SpansCall::planned enqueues the caller's plan in front of the wait -- which then reads the whole head, 48 bytes,
+// text is settled, SpansCall::planned enqueues the caller's plan in front of the wait -- which then reads the whole head, 56 bytes,
 // still once -- and SpansCall::merged is the caller's step behind it, the piece's emit.  What the spans entries compute, read back
 // and return is untouched by that.
+//
+// A RANGE (SpansRange, acgpu_spans.h; the feed of a cover stream): the same loop over the owned units of a buffer [carry | chunk].
+// The first piece's carry is uploaded from the host, the range's last piece finalises everything only if the caller says the
+// range ends the text -- otherwise it is a piece like any other, after which the caller reads B and the first withheld span from
+// the head (kSpanBelow, kSpanCarry0) -- and what it withholds goes back to the host.  Carried spans may start in front of the
+// buffer: starts are only compared.
 //
 // A BATCH (acgpu_spans_batch_u16): the haystacks are merged as one text, a separator unit behind each.  No record holds a
 // separator, so a separator's position is never covered, and a span that ends at it and one that starts behind it do not touch:
@@ -294,11 +300,20 @@ __global__ __launch_bounds__(kSpanBlock) void k_span_scatter(SpanList L, const i
 // A cover call (acgpu_cover.hip), behind the scatter: the settled position L = min(B, start of the first carried span) -- every
 // position below it is inside a final span or will never be covered -- into slot[kSpanSettled]; one thread.  empty: a piece
 // without intervals, whose other launches did not run.
+// slot[kSpanBelow] = B itself and slot[kSpanCarry0] = the first carried span, {start, end}: what the last piece of a RANGE (a cover
+// stream's feed, acgpu_spans.h) settles at instead, and the span it cuts there.
 __global__ void k_span_settled(SpanList L, SpanBound Bd, const int2 *__restrict__ carry_out, uint64_t *__restrict__ slot, int empty) {
     if (empty) slot[0] = slot[1] = slot[kSpanDropped] = 0;
-    int64_t at = final_below(L, Bd);
-    if (slot[1]) at = std::min<int64_t>(at, carry_out[0].x);
+    const int64_t below = final_below(L, Bd);
+    int64_t at = below;
+    int2 first = make_int2(0, 0);
+    if (slot[1]) {
+        first = carry_out[0];
+        at = std::min<int64_t>(at, first.x);
+    }
     slot[kSpanSettled] = (uint64_t)at;
+    slot[kSpanBelow] = (uint64_t)below;
+    slot[kSpanCarry0] = (uint64_t)(uint32_t)first.x | ((uint64_t)(uint32_t)first.y << 32);
 }
 
 // A batch call's final spans of a piece -> {haystack, start, end} relative to the haystack: the layout of k_batch_tag's Set
@@ -334,21 +349,33 @@ uint64_t spans_bound(const HostTables &t, uint64_t own_hi) {
 }
 
 // before the first piece: the pinned words and the two carry buffers
-int spans_begin(SpansCall &c) {
+// (a range: the spans an earlier range withheld are the first piece's carry)
+int spans_begin(SpansCall &c, const SpansRange *range) {
     DeviceState &d = c.d;
+    static_assert(kSpanHead * 8 <= 64, "the head fits the pinned words");
     if (!d.spans_pin) HIP_TRY(hipHostMalloc(&d.spans_pin.h, 64, hipHostMallocDefault));
     c.carry_cap = c.a->t.max_len / 2 + 2;
-    return d.spans_carry.ensure((size_t)c.carry_cap * 2 * 8);
+    const int rc = d.spans_carry.ensure((size_t)c.carry_cap * 2 * 8);
+    if (rc || !range || !range->n_carry_in) return rc;
+    if (range->n_carry_in > c.carry_cap) return ACGPU_E_HIP; // (never: what a range hands back fits)
+    HIP_TRY(hipMemcpyAsync(reinterpret_cast<int2 *>(d.spans_carry.p) + (size_t)c.cur * c.carry_cap, range->carry_in, (size_t)range->n_carry_in * 8,
+                           hipMemcpyHostToDevice, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream)); // (the caller's memory is pageable)
+    c.n_carry = range->n_carry_in;
+    return ACGPU_OK;
 }
 
 // Behind a piece: merge the carry and the piece's cnt records (in d.count_res, relative to `base`; a UTF-8 call's: in bytes).
-int spans_piece(SpansCall &c, uint64_t base, uint64_t cnt, uint64_t own_hi, bool last_or_whole) {
+// range_last: the last piece of a range whose end is not the text's (acgpu_spans.h).
+int spans_piece(SpansCall &c, uint64_t base, uint64_t cnt, uint64_t own_hi, bool last_or_whole, bool range_last = false) {
     DeviceState &d = c.d;
     c.st.n_records += cnt;
     const uint64_t m = c.n_carry + cnt;
     c.piece_final = c.piece_dropped = 0;
     c.piece_own_hi = own_hi;
     c.piece_last = last_or_whole;
+    c.piece_range_last = range_last;
+    c.piece_carried = 0;
     if (!m && !c.to_pool) return ACGPU_OK;
     const uint32_t n_tiles = (uint32_t)((m + kSpanTile - 1) / kSpanTile);
     int rc = d.spans_work.ensure(kSpanHead * 8 + (size_t)n_tiles * 12); // the head (acgpu_spans.h) | tile minima | tile counts | tile final counts
@@ -407,13 +434,13 @@ int spans_piece(SpansCall &c, uint64_t base, uint64_t cnt, uint64_t own_hi, bool
     O.carry = carry + (size_t)(c.cur ^ 1) * c.carry_cap;
     O.carry_cap = c.carry_cap;
     if (!m) { // (a cover call's piece without intervals: its settled position is the bound)
-        c.piece_settled = (int64_t)bound;
+        c.piece_settled = c.piece_below = (int64_t)bound;
         if (!Bd.d_bound) return ACGPU_OK;
         hipLaunchKernelGGL(k_span_settled, dim3(1), dim3(1), 0, c.stream, L, Bd, (const int2 *)O.carry, slot, 1);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(d.spans_pin.h, slot, kSpanHead * 8, hipMemcpyDeviceToHost, c.stream));
         HIP_TRY(hipStreamSynchronize(c.stream));
-        c.piece_settled = (int64_t) static_cast<const uint64_t *>(d.spans_pin.h)[kSpanSettled];
+        c.piece_settled = c.piece_below = (int64_t) static_cast<const uint64_t *>(d.spans_pin.h)[kSpanSettled];
         return ACGPU_OK;
     }
 
@@ -451,6 +478,9 @@ int spans_piece(SpansCall &c, uint64_t base, uint64_t cnt, uint64_t own_hi, bool
     c.piece_final = n_final;
     c.piece_settled = (int64_t)h[kSpanSettled];
     c.piece_dropped = h[kSpanDropped];
+    c.piece_below = (int64_t)h[kSpanBelow];
+    c.piece_carry0 = make_int2((int32_t)(uint32_t)h[kSpanCarry0], (int32_t)(uint32_t)(h[kSpanCarry0] >> 32));
+    c.piece_carried = (uint32_t)n_carry;
     return ACGPU_OK;
 }
 
@@ -458,11 +488,13 @@ int spans_piece(SpansCall &c, uint64_t base, uint64_t cnt, uint64_t own_hi, bool
 
 namespace acgpu {
 
-int spans_pieces(SpansCall &c, int64_t chain, bool whole, const PieceScan &scan, uint64_t n_units) {
+int spans_pieces(SpansCall &c, int64_t chain, bool whole, const PieceScan &scan, uint64_t n_units, SpansRange *range) {
     DeviceState &d = c.d;
-    int rc = spans_begin(c);
+    int rc = spans_begin(c, range);
     if (rc) return rc;
-    PieceDriver p(0, n_units, chain, whole, ACGPU_REC_SET, &d.count_res); // the pool's reservoir, here of Set records: one call at a time holds the pool
+    const bool text_end = !range || range->text_end;
+    // the pool's reservoir, here of Set records: one call at a time holds the pool
+    PieceDriver p(range ? range->own_begin : 0, range ? range->own_end : n_units, chain, whole, ACGPU_REC_SET, &d.count_res);
     while (p.pos < p.end) {
         uint64_t cnt = 0, base = 0;
         if ((rc = scan_next_piece(p, scan, &cnt, &base))) return rc;
@@ -472,10 +504,33 @@ int spans_pieces(SpansCall &c, int64_t chain, bool whole, const PieceScan &scan,
         if (c.ub) rc = utf8_vmap_records(*c.ub, recs, cnt, c.stream);
         else if (c.u8) rc = utf8_map_records(*c.u8, nullptr, recs, cnt, ACGPU_REC_SET / 4, c.stream);
         if (rc) return rc;
-        const bool last = p.pos >= p.end; // (a whole text's one piece ends at p.end)
+        const bool at_end = p.pos >= p.end, last = at_end && text_end; // (a whole text's one piece ends at p.end)
         const uint64_t m = c.n_carry + cnt;
-        if ((rc = spans_piece(c, base, cnt, p.pos, last))) return rc;
+        if ((rc = spans_piece(c, base, cnt, p.pos, last, at_end && !text_end))) return rc;
         if (c.merged && (rc = c.merged(c.ctx, m, last))) return rc;
+    }
+    if (range) {
+        // a text's last range that owns nothing new: what the ranges before it withheld is finalised by a piece without records
+        if (!p.pieces && text_end) {
+            const uint64_t m = c.n_carry;
+            if ((rc = spans_piece(c, 0, 0, p.end, true))) return rc;
+            if (c.merged && (rc = c.merged(c.ctx, m, true))) return rc;
+        }
+        range->scanned = p.pieces != 0;
+        range->chain_exit = p.chain;
+        // what the range withheld, for the next one: the carry buffer the last piece wrote (c.cur names it now)
+        try {
+            range->carry_out.resize(c.n_carry);
+        } catch (...) {
+            return ACGPU_E_NOMEM;
+        }
+        if (c.n_carry == 1 && c.piece_carried == 1) {
+            range->carry_out[0] = c.piece_carry0;
+        } else if (c.n_carry) {
+            HIP_TRY(hipMemcpyAsync(range->carry_out.data(), reinterpret_cast<const int2 *>(d.spans_carry.p) + (size_t)c.cur * c.carry_cap, (size_t)c.n_carry * 8,
+                                   hipMemcpyDeviceToHost, c.stream));
+            HIP_TRY(hipStreamSynchronize(c.stream));
+        }
     }
     c.st.pieces += (uint32_t)p.pieces; // (added: a batch call haystack by haystack drives one text after the other)
     c.st.rescans += (uint32_t)p.rescans;

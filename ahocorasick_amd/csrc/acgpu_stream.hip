@@ -17,6 +17,9 @@
 // acgpu_stream_replace_u16 / acgpu_stream_replace_utf8 rewrite the text instead of reporting its records: the same buffers and the
 // same plan, and over a feed's owned range the pieces of the replace entries (replace_feed, acgpu_replace.hip); the stream keeps
 // `done`, the global position up to which output has been delivered.
+// acgpu_stream_cover_u16 / acgpu_stream_cover_utf8 / acgpu_stream_cover_utf8_lossy cover the text instead (mask, highlight, redact):
+// the same buffers and plan again, and over a feed's owned range the pieces of the cover entries (cover_feed, acgpu_cover.hip); the
+// stream keeps `done`, whether it stands inside a span, and the few spans the merge withheld.
 // acgpu_stream_feed_utf8_lossy / acgpu_stream_replace_utf8_lossy are the two byte entries' bodies with the other error policy
 // (feed_utf8, stream_replace_utf8): nothing is refused, the buffer is staged through the validator that is both lossy and open,
 // the carry is cut at a START found by the claim rule restated on the host (lossy_start, lossy_span), and the stream keeps the
@@ -176,11 +179,16 @@ struct acgpu_stream {
     bool finished = false;
     std::vector<uint16_t> buf;
     // ---- a stream of UTF-8 bytes (acgpu_stream_feed_utf8): carry_pos, own_from and chain_entry stay in units ----
-    enum Fed : uint8_t { kFedNone, kFedUnits, kFedBytes, kFedReplaceUnits, kFedReplaceBytes, kFedBytesLossy, kFedReplaceBytesLossy };
+    enum Fed : uint8_t {
+        kFedNone, kFedUnits, kFedBytes, kFedReplaceUnits, kFedReplaceBytes, kFedBytesLossy, kFedReplaceBytesLossy,
+        kFedCoverUnits, kFedCoverBytes, kFedCoverBytesLossy
+    };
     Fed fed = kFedNone;          // what the first feed, of whatever length, made of the stream: every other entry refuses it
                                  // (the error policy of a stream of bytes is part of its kind: a strict feed on a lossy stream, and the reverse)
-    uint64_t done = 0;           // a replace stream: output has been delivered for the text in front of this global position, in
-                                 // units (kFedReplaceUnits) or bytes (kFedReplaceBytes); never in front of the carry's first
+    uint64_t done = 0;           // a replace or cover stream: output has been delivered for the text in front of this global position,
+                                 // in units (kFedReplaceUnits, kFedCoverUnits) or bytes; never in front of the carry's first
+    bool in_span = false;        // a cover stream: `done` stands inside a span whose close has not been delivered
+    std::vector<int64_t> spans;  // ... and the spans the merge withheld, {start, end} in the coordinates of `done` (CoverFeed::carried)
     std::vector<uint8_t> carry8; // the carried text's bytes, whole code points, then the held prefix
     uint32_t held = 0;           // bytes at carry8's end that begin a sequence the next feed must complete, 0..3
     uint64_t carry_units = 0;    // units that carry8 without the held prefix decodes to
@@ -911,6 +919,141 @@ int acgpu_stream_replace_utf8_lossy(acgpu_stream *s, const uint8_t *bytes, uint6
                                     const uint64_t *repl_off, uint32_t n_repl, uint8_t *out, uint64_t cap, uint64_t *n_out,
                                     acgpu_utf8_lossy_stream_stats *ust, acgpu_replace_stats *rst) {
     return stream_replace_utf8(s, bytes, n_bytes, final, repl_bytes, repl_off, n_repl, out, cap, n_out, /*lossy=*/true, nullptr, ust, rst);
+}
+
+} // extern "C"
+
+namespace {
+
+// An empty final feed on a cover stream whose text is delivered to its end: all that is left is the close of the span `done`
+// stands in, if it stands in one.  No device: close is the caller's, in host memory.
+int cover_close_on_host(acgpu_stream *s, const acgpu_cover_spec *spec, uint32_t esz, void *out, uint64_t cap, uint64_t *n_out, acgpu_cover_stats *st) {
+    const uint64_t n = s->in_span ? spec->close_len : 0;
+    *n_out = n;
+    if (st) st->units_out = n;
+    if (n > cap) return ACGPU_E_OVERFLOW; // (nothing committed: the same feed again)
+    if (n) std::memcpy(out, spec->close, (size_t)n * esz);
+    s->in_span = false;
+    s->spans.clear();
+    s->finished = true;
+    return ACGPU_OK;
+}
+
+// the stream's state in front of a feed -> f (positions relative to the buffer, whose element 0 is global `origin`)
+void cover_feed_in(const acgpu_stream *s, uint64_t origin, bool final, CoverFeed *f) {
+    f->final = final;
+    f->done = s->done - origin;
+    f->in_span = s->in_span;
+    f->origin = origin;
+    f->carried = s->spans;
+    f->chain = s->chain_entry - (int64_t)s->carry_pos;
+}
+
+// The body of acgpu_stream_cover_utf8 and acgpu_stream_cover_utf8_lossy (ust or lossy_ust: as feed_utf8's stats).
+int stream_cover_utf8(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, const acgpu_cover_spec *spec, uint8_t *out, uint64_t cap,
+                      uint64_t *n_out, bool lossy, acgpu_utf8_stream_stats *ust, acgpu_utf8_lossy_stream_stats *lossy_ust, acgpu_cover_stats *st) {
+    if (!s || !n_out || (n_bytes && !bytes) || (cap && !out) || s->finished) return ACGPU_E_INVALID;
+    if (!s->a) return ACGPU_E_INVALID; // (its automaton has been freed)
+    const acgpu_stream::Fed kind = lossy ? acgpu_stream::kFedCoverBytesLossy : acgpu_stream::kFedCoverBytes;
+    if (s->fed != acgpu_stream::kFedNone && s->fed != kind) return ACGPU_E_INVALID; // (a stream of another kind)
+    acgpu_automaton *a = s->a;
+    int rc = cover_check_spec(spec, 1);
+    if (rc) return rc;
+    if (s->pipelined) return ACGPU_E_UNSUPPORTED;
+    if (n_bytes >= (1ull << 31) || s->carry8.size() + n_bytes >= (1ull << 31)) return ACGPU_E_INVALID;
+    s->fed = kind;
+    *n_out = 0;
+    if (st) *st = acgpu_cover_stats{};
+    ByteFeed bf{bytes, n_bytes, final != 0, ust, lossy_ust, lossy};
+    rc = byte_feed_begin(s, ACGPU_REC_SET, &bf);
+    if (!bf.go) {
+        // (the end of a stream that holds nothing, inside a span: its close; an overflow leaves the stream open for the same feed)
+        if (rc == ACGPU_OK && final && (rc = cover_close_on_host(s, spec, 1, out, cap, n_out, st)) == ACGPU_E_OVERFLOW) s->finished = false;
+        return rc;
+    }
+    const PoolCall &call = *bf.call;
+    const FeedPlan &p = bf.p;
+    if (s->done < s->carry_byte) return call.fail(ACGPU_E_HIP); // (never: the carry invariant, checked at every commit)
+    CoverFeed f;
+    cover_feed_in(s, s->carry_byte, bf.final, &f); // (bytes of the buffer)
+    f.u8 = &bf.text;
+    if (p.own_end > p.own_begin || final) {
+        f.shard = bf.text.shard; // (all the buffer's units: then the owned range and the ends)
+        plan_shard(&f.shard, p, s->carry_pos, f.final);
+        rc = cover_feed(a, *call.d, &f, spec, out, cap, n_out);
+        if (rc == ACGPU_OK || rc == ACGPU_E_OVERFLOW) {
+            if (st) *st = f.st;
+        }
+        if (rc == ACGPU_E_OVERFLOW) return rc; // nothing committed: the same feed again, with *n_out bytes of room
+        if (rc) return call.fail(rc);
+    } else { // (nothing owned yet: the chain passes through)
+        f.chain = piece_exit(bf.rule, piece_entry(bf.rule, f.chain, 0, p.own_begin), p.own_end, nullptr, 0);
+    }
+    if ((rc = byte_feed_commit(s, bf, f.chain, &f.done))) return rc; // (s->done: global again)
+    s->in_span = f.in_span;
+    s->spans.swap(f.carried);
+    return ACGPU_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int acgpu_stream_cover_u16(acgpu_stream *s, const uint16_t *units, uint64_t n_units, int final, const acgpu_cover_spec *spec, uint16_t *out, uint64_t cap,
+                           uint64_t *n_out, acgpu_cover_stats *st) {
+    if (!s || !n_out || (n_units && !units) || (cap && !out) || s->finished) return ACGPU_E_INVALID;
+    if (!s->a) return ACGPU_E_INVALID; // (its automaton has been freed)
+    if (s->fed != acgpu_stream::kFedNone && s->fed != acgpu_stream::kFedCoverUnits) return ACGPU_E_INVALID; // (a stream of another kind)
+    acgpu_automaton *a = s->a;
+    int rc = cover_check_spec(spec, 2);
+    if (rc) return rc;
+    if (s->pipelined) return ACGPU_E_UNSUPPORTED;
+    const ShardRule rule = shard_rule(a->t, ACGPU_REC_SET, /*readable=*/true);
+    const FeedPlan p = plan_feed(rule, s->carry.size(), n_units, s->own_from, s->carry_pos, final != 0);
+    if (n_units >= (1ull << 31) || p.total >= (1ull << 31)) return ACGPU_E_INVALID;
+    s->fed = acgpu_stream::kFedCoverUnits;
+    *n_out = 0;
+    if (st) *st = acgpu_cover_stats{};
+    if (n_units == 0 && !final) return ACGPU_OK; // (nothing new to decide: no device needed)
+    if (s->done < s->carry_pos) return ACGPU_E_HIP; // (never: the carry invariant, checked at every commit)
+    // (the end of a text that has been delivered to its end -- a stream that holds nothing included: no device needed either)
+    if (final && p.own_end == p.own_begin && s->done - s->carry_pos == p.total) return cover_close_on_host(s, spec, 2, out, cap, n_out, st);
+    if ((rc = join_units(s, units, n_units, p))) return rc;
+    CoverFeed f;
+    cover_feed_in(s, s->carry_pos, final != 0, &f);
+    if (p.own_end > p.own_begin || final) {
+        PoolCall call(a);
+        if (call.rc) return call.rc;
+        DeviceState &d = *call.d;
+        if ((rc = call.idle())) return rc; // (the call stream, waited for: see the stream rule)
+        if ((rc = stage_whole_text(d, s->buf.data(), p.total, &f.shard))) return rc; // (the carry and the fed units: then the owned range and the ends)
+        plan_shard(&f.shard, p, s->carry_pos, f.final);
+        rc = cover_feed(a, d, &f, spec, out, cap, n_out);
+        if (rc == ACGPU_OK || rc == ACGPU_E_OVERFLOW) {
+            if (st) *st = f.st;
+        }
+        if (rc == ACGPU_E_OVERFLOW) return rc; // nothing committed: the same feed again, with *n_out units of room
+        if (rc) return call.fail(rc);
+    } else { // (nothing owned yet: the chain passes through)
+        f.chain = piece_exit(rule, piece_entry(rule, f.chain, 0, p.own_begin), p.own_end, nullptr, 0);
+    }
+    // the carry must reach back to `done`: keep_from = own_end - left never lies behind B
+    if (!final && f.done < p.keep_from) return ACGPU_E_HIP;
+    s->done = s->carry_pos + f.done;
+    s->in_span = f.in_span;
+    s->spans.swap(f.carried);
+    commit_units(s, p, f.chain, f.final);
+    return ACGPU_OK;
+}
+
+int acgpu_stream_cover_utf8(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, const acgpu_cover_spec *spec, uint8_t *out, uint64_t cap,
+                            uint64_t *n_out, acgpu_utf8_stream_stats *ust, acgpu_cover_stats *st) {
+    return stream_cover_utf8(s, bytes, n_bytes, final, spec, out, cap, n_out, /*lossy=*/false, ust, nullptr, st);
+}
+
+int acgpu_stream_cover_utf8_lossy(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, const acgpu_cover_spec *spec, uint8_t *out,
+                                  uint64_t cap, uint64_t *n_out, acgpu_utf8_lossy_stream_stats *ust, acgpu_cover_stats *st) {
+    return stream_cover_utf8(s, bytes, n_bytes, final, spec, out, cap, n_out, /*lossy=*/true, nullptr, ust, st);
 }
 
 } // extern "C"

@@ -1291,7 +1291,8 @@ int acgpu_spans_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, uint6
  *              phantoms are not in the buffer and subtracts the haystack's index, which is constant within a segment.  No
  *              wait is added per piece.  The fallback (no free separator unit; a word matcher's table that is not
  *              fold-consistent) validates the whole batch first, so what is refused does not depend on the route.
- * Not built: stream, device-resident and multi-device forms, per-keyword open / close, a one-launch form for tiny batches, the Java
+ * One long text in chunks: acgpu_stream_cover_u16 / _utf8 / _utf8_lossy below.
+ * Not built: device-resident and multi-device forms, per-keyword open / close, a one-launch form for tiny batches, the Java
  * facade.  ACGPU_ABI_VERSION stays as it is.
  */
 enum { ACGPU_COVER_KEEP = 0, ACGPU_COVER_FILL = 1, ACGPU_COVER_DROP = 2 };
@@ -1329,6 +1330,65 @@ int acgpu_cover_batch_utf8(const acgpu_automaton *a, const uint8_t *bytes, const
 int acgpu_cover_batch_utf8_lossy(const acgpu_automaton *a, const uint8_t *bytes, const uint64_t *offsets, uint32_t n_haystacks,
                                  const acgpu_cover_spec *spec, uint8_t *out, uint64_t cap, uint64_t *out_offsets /* n_haystacks + 1 */,
                                  uint64_t *n_out, acgpu_cover_stats *st /* may be NULL */, acgpu_utf8_lossy_stats *ust /* may be NULL */);
+
+/*
+ * Stream cover: acgpu_cover_u16 / acgpu_cover_utf8 / acgpu_cover_utf8_lossy for a text that arrives in chunks of any size and may be
+ * longer than 2^31 elements -- mask, highlight or redact a log file chunk by chunk, for ALL FIVE families (ACGPU_MODE_ALL and, for
+ * bytes, keywords with an unpaired surrogate included).  A stream opened with acgpu_stream_open is fed through ONE of these three
+ * entries; the first feed of any kind, an empty one included, decides what the stream is, and every other entry then returns
+ * ACGPU_E_INVALID (nine kinds in all).  "Element" below: a UTF-16 unit for acgpu_stream_cover_u16, a byte for the byte entries.
+ *  result : let T be the concatenation of everything fed and R the Set records that acgpu_stream_feed / acgpu_stream_feed_utf8 /
+ *           acgpu_stream_feed_utf8_lossy deliver for T over all feeds.  The concatenation of out[0 .. *n_out) over all feeds is the
+ *           cover of T by the spans of R under spec (every span open ++ body ++ close, everything else copied), whatever the
+ *           chunking.  For a fold-consistent word table that is element for element what acgpu_cover_u16 / _utf8 / _utf8_lossy
+ *           return for T; over a word table that is not fold-consistent the STREAM's records are meant (the Readable loops).
+ *  a feed : delivers the rewrite of T[done_before : done_after).  For a feed that is not final done_after = max(done_before, B),
+ *           B the position before which no later record can start, by the carry rule of the spans merge applied to the feed's
+ *           owned range: AhoCorasick and Shortest: owned end + 1 - max_keyword_len; Longest, WholeWord, WholeWordLongest:
+ *           max(owned end, end of the feed's last record); bytes: that unit mapped to bytes, rounded down to a code-point
+ *           boundary and never past the end of the decoded bytes (a held prefix is never delivered before the bytes that
+ *           complete it).  final != 0 delivers everything.  So a feed that is not final withholds at most max_keyword_len + 1
+ *           units (bytes: 4 * (max_keyword_len + 2) + 3) HOWEVER LONG A SPAN IS: "aa" on "aaaa..." is one span through every feed.
+ *  a span that done_after cuts (position done_after - 1 is covered and the span's end is >= done_after; an end EQUAL to done_after
+ *           counts, a later record may start exactly there and touch): its open and its body up to done_after are delivered now
+ *           (DROP: no body), its close by the feed that sees it end -- as the first thing that feed delivers if nothing touched it
+ *           after all -- and no second open is ever written.  The stream carries done (64 bits, global), whether it stands
+ *           inside a span, and the spans the merge withheld (at most max_keyword_len / 2 + 2, global coordinates) on the host.
+ *  spec   : as for the cover entries; uploaded by every feed, and the spec of the feed that emits applies.  Pass the same one.
+ *  cap, *n_out : in elements.  ACGPU_E_OVERFLOW: nothing was committed, *n_out (and st->units_out) is the exact size of THIS feed's
+ *           output, out[0 .. cap) is unspecified and nothing at or beyond cap has been written; call the SAME feed again.
+ *  st     : may be NULL; this feed alone, st->units_out == *n_out, st->n_spans the spans whose OPEN this feed delivered (summed
+ *           over the feeds: the spans of T); n_records, pieces, rescans, max_carry as for the cover entries.  ust (bytes): may be
+ *           NULL, as acgpu_stream_feed_utf8 / _lossy fill it.
+ *  ACGPU_E_INVALID, before any device is touched and with out, st and ust untouched: NULL s or n_out, data without a buffer, cap
+ *           without out, a finished or detached stream, a stream of another kind, what the cover entries refuse about spec
+ *           (NULL, body > 2, a NULL pointer with a length, 2^31 elements of open or close, a fill the element does not hold:
+ *           bytes >= 0x80), n >= 2^31 or carried + n >= 2^31.  Tickets in flight on the pool: ACGPU_E_INVALID as well.
+ *  ACGPU_E_UNSUPPORTED, before any device is touched: a pipelined stream.
+ *  ACGPU_E_ENCODING (strict bytes): as acgpu_stream_replace_utf8 -- ust->first_bad is the GLOBAL offset, *n_out = 0, out untouched,
+ *           the stream is finished, and what earlier feeds had withheld (a pending close included) is NOT delivered.
+ *  no device : an empty feed that is not final; an empty final feed on a stream that holds nothing; and for acgpu_stream_cover_u16
+ *           any empty final feed on a text already delivered to its end -- inside a span it delivers close, copied on the host
+ *           from spec (the byte entries do the same where they carry no bytes, else they go through the device).
+ * Device and lifetime as for acgpu_stream_feed.  Nothing of the stream lives on the device between two feeds, so any other call on
+ * the automaton -- other streams and cover calls with other specs included -- may run between them.
+ * How it works: a feed builds [carry | chunk] as the match feeds do and drives the pieces of the cover entries over its owned
+ * range, scanned by the Readable rule, the merge starting from the spans the stream carries.  Inside a feed a span that is still
+ * open at a piece's end is withheld as ever; the feed's last piece settles at B and emits the span it cuts there as a TAILLESS
+ * item (no close), and the next feed emits the rest of it as a HEADLESS item (no open, body from done on) -- two kinds of item of
+ * the one emit kernel, clipped in its source alone.  The carry always reaches back to done (keep_from = owned end - left context
+ * never lies behind B); a feed that finds otherwise returns ACGPU_E_HIP.
+ * Not built: a stream of spans (acgpu_stream_spans_*: the same state without the text), pipelined and reserved forms,
+ * device-resident and multi-device forms, the Java facade.  ACGPU_ABI_VERSION stays as it is: adding symbols is compatible.
+ */
+int acgpu_stream_cover_u16(acgpu_stream *s, const uint16_t *units, uint64_t n_units, int final, const acgpu_cover_spec *spec,
+                           uint16_t *out, uint64_t cap, uint64_t *n_out, acgpu_cover_stats *st /* may be NULL */);
+int acgpu_stream_cover_utf8(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, const acgpu_cover_spec *spec,
+                            uint8_t *out, uint64_t cap, uint64_t *n_out, acgpu_utf8_stream_stats *ust /* may be NULL */,
+                            acgpu_cover_stats *st /* may be NULL */);
+int acgpu_stream_cover_utf8_lossy(acgpu_stream *s, const uint8_t *bytes, uint64_t n_bytes, int final, const acgpu_cover_spec *spec,
+                                  uint8_t *out, uint64_t cap, uint64_t *n_out, acgpu_utf8_lossy_stream_stats *ust /* may be NULL */,
+                                  acgpu_cover_stats *st /* may be NULL */);
 
 /*
  * Synthetic haystack generator of the benchmark: unit i of the stream is
